@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- xRT (audio-seconds / wall-second) of the MI355X-native ClearConverse hot path.
 
-  python bench.py --gpus N --steps K --warmup W [--workload pipeline|whisper] [--batch B]
+  python bench.py --gpus N --steps K --warmup W [--workload pipeline|whisper] [--batch B] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic 30 s / 16 kHz clips already resident
 in HBM.
@@ -15,9 +15,12 @@ N>1: one process per GPU (launched by torchrun, or by bench.py itself when calle
 data-path collective; the only collectives are the timing barrier/max and one all-gather of the token
 records at the end (weak scaling: B clips per GPU).
 
-The JSON line carries `roofline` for the dominant kernel (per-launch HIP events recorded by libccx on the
-launch stream during one extra step right after the timed region) and `cpu_baseline` (oracle/, fp32 on the host
-cores, bounded sample, rank 0 at N=1 only) -- DESIGN.md "Measurement".
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step`, `config`).  With `--full` it
+also measures, after the timed region, what the headline figure does not need: the span-1 and sequential comparison legs,
+socket power over the timed region, `roofline` for the dominant kernel (per-launch HIP events recorded by libccx on the launch
+stream during one extra step right after the timed region, plus the decode probes), `roofline_mfma`, `kernel_ms_per_step` and
+`cpu_baseline` (oracle/, fp32 on the host cores, bounded sample, rank 0 at N=1 only) -- DESIGN.md "Measurement".  Those keys are
+null in a plain run.  `--dump-outputs DIR` writes what the last timed step computed (rank 0's clips) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -219,6 +222,35 @@ def lane_cross_attention_in_situ(path, bytes_per_sequence):
     return out or None
 
 
+MAX_DUMP_BYTES = 64 << 20
+
+
+def decode_arrays(records, sample_len):
+    """The Whisper records of one step as arrays: tokens [calls, sample_len] (-1 past a record's end; token ids are exact in
+    float32), their count, and the per-call log-probabilities and no-speech probability."""
+    toks = np.full((len(records), sample_len), -1.0, dtype=np.float32)
+    for i, r in enumerate(records):
+        toks[i, :len(r["tokens"])] = r["tokens"]
+    return {"tokens": toks,
+            "n_tokens": np.array([len(r["tokens"]) for r in records], dtype=np.float32),
+            "sum_logprob": np.array([r["sum_logprob"] for r in records], dtype=np.float64),
+            "avg_logprob": np.array([r["avg_logprob"] for r in records], dtype=np.float64),
+            "no_speech_prob": np.array([r["no_speech_prob"] for r in records], dtype=np.float64)}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64, at most MAX_DUMP_BYTES in all."""
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise ValueError(f"dump_outputs: {name} is {a.dtype}, not float32 / float64")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > MAX_DUMP_BYTES:
+        raise ValueError(f"dump_outputs: {total} bytes exceed {MAX_DUMP_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def single_file(args, rank, local_rank, world):
     """The drop-in path as the reference calls it (back/api.py:1204-1280, one task = one file = one process): a step = one
     `EnhancedAudioProcessor.run` on one 30 s / 16 kHz WAV -- file read, gate, VAD, diarization, profiles, per-segment embeddings,
@@ -269,6 +301,16 @@ def single_file(args, rank, local_rank, world):
         step(i)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the last step receives: the transcript text (UTF-8 bytes) and the segment WAVs written beside it
+        from clearconverse_amd.audio import read_wav
+        last = (args.steps - 1) % n_files
+        text = (outs[-1][1] or "").encode("utf-8")
+        seg_audio = [read_wav(str(p))[0].reshape(-1) for p in sorted((Path(work) / f"out{last}").rglob("*.wav"))]
+        dump_outputs(args.dump_outputs, {
+            "transcript_utf8": np.frombuffer(text, dtype=np.uint8).astype(np.float32),
+            "segment_audio": np.concatenate(seg_audio + [np.zeros(0, np.float32)]).astype(np.float32),
+            "segment_samples": np.array([len(a) for a in seg_audio], dtype=np.float32)})
     if rank == 0:
         segs = [o[1].count("\n\n") if o[1] else 0 for o in outs]
         print(json.dumps({
@@ -301,15 +343,23 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="30 s clips per GPU per step (default 32 pipeline / 8 whisper)")
     ap.add_argument("--sample-len", type=int, default=224)
     ap.add_argument("--whisper-group", type=int, default=192, help="sequences decoded together in the pipeline workload")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the comparison legs, power, the per-launch profile (roofline, "
+                         "roofline_mfma, kernel_ms_per_step) and the CPU baseline; a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's clips) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--stage-times", action="store_true", help="one extra (untimed) step with a sync after every stage")
     ap.add_argument("--no-comparisons", action="store_true",
-                    help="skip the span-1 and sequential comparison legs after the timed region (profiling runs: fewer launch shapes per symbol)")
+                    help="with --full: skip the span-1 and sequential comparison legs after the timed region (profiling runs: fewer launch "
+                         "shapes per symbol)")
     ap.add_argument("--decode-span", type=int, default=4,
                     help="pipelined schedule: batches whose Whisper windows are encoded and decoded together (1 = one decode group per batch)")
     ap.add_argument("--schedule", choices=("pipelined", "sequential"), default="pipelined",
                     help="pipeline workload: overlap batch i's Whisper decode with batch i+1's front end (default) or run each batch start to finish")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing has touched the GPU yet (importing torch does not
@@ -321,7 +371,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with --nproc-per-node {args.gpus} or without a launcher")
-    probe = PowerProbe() if (rank == 0 and local_rank == 0) else None      # looks its card up before anything touches the GPU
+    probe = PowerProbe() if (args.full and rank == 0 and local_rank == 0) else None      # looks its card up before anything touches the GPU
     if os.environ.get("CCX_BENCH_SHARE_GPU"):
         local_rank = 0      # rehearsal of the N > 1 code path on a one-GPU box (with CCX_BENCH_BACKEND=gloo): all ranks on cuda:0
     torch.cuda.set_device(local_rank)
@@ -434,90 +484,96 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     power = probe.stop() if probe is not None else None
+    if rank == 0 and args.dump_outputs:
+        arrays = decode_arrays(res["records"], args.sample_len)
+        if pipeline:
+            arrays["segment_similarity"] = np.array(res["sims"], dtype=np.float64)     # regular segment vs its speaker's profile
+        dump_outputs(args.dump_outputs, arrays)
     seq_ms = span1_ms = None
-    if pipelined and args.decode_span > 1 and not args.no_comparisons:
-        # the same pipeline with one decode group per batch, for comparison (untimed for `value`)
-        n1 = min(4, max(2, args.steps))
-        torch.cuda.synchronize()
-        ts = time.perf_counter()
-        bp.run_pinned_pipelined([audio] * n1, span=1)
-        torch.cuda.synchronize()
-        span1_ms = (time.perf_counter() - ts) * 1e3 / n1
-    if pipelined and not args.no_comparisons:
-        # the sequential schedule of the same batch, for comparison (untimed for `value`)
-        nseq = min(3, max(1, args.steps))
-        torch.cuda.synchronize()
-        ts = time.perf_counter()
-        for _ in range(nseq):
+    # which cross attention the decode groups run (CCX_CROSS_X=0 at model creation: round 2's per-layer K/V caches)
+    xstream = os.environ.get("CCX_CROSS_X", "1") != "0" and dims.n_text_state in (128, 256, 384, 512, 768) and dims.n_text_head * 64 == dims.n_text_state
+    if args.full:
+        if pipelined and args.decode_span > 1 and not args.no_comparisons:
+            # the same pipeline with one decode group per batch, for comparison (untimed for `value`)
+            n1 = min(4, max(2, args.steps))
+            torch.cuda.synchronize()
+            ts = time.perf_counter()
+            bp.run_pinned_pipelined([audio] * n1, span=1)
+            torch.cuda.synchronize()
+            span1_ms = (time.perf_counter() - ts) * 1e3 / n1
+        if pipelined and not args.no_comparisons:
+            # the sequential schedule of the same batch, for comparison (untimed for `value`)
+            nseq = min(3, max(1, args.steps))
+            torch.cuda.synchronize()
+            ts = time.perf_counter()
+            for _ in range(nseq):
+                step()
+            torch.cuda.synchronize()
+            seq_ms = (time.perf_counter() - ts) * 1e3 / nseq
+        # per-launch HIP events (~11 k pairs per pipeline step) are kept OUT of the timed region: one more, untimed, step of the same
+        # batch is recorded for the roofline entries
+        prof_steps = 1
+        ctx.prof_enable(True)
+        for _ in range(prof_steps):
             step()
         torch.cuda.synchronize()
-        seq_ms = (time.perf_counter() - ts) * 1e3 / nseq
-    # per-launch HIP events (~11 k pairs per pipeline step) are kept OUT of the timed region: one more, untimed, step of the same
-    # batch is recorded for the roofline entries
-    prof_steps = 1
-    ctx.prof_enable(True)
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize()
-    recs = ctx.prof_records()
-    ctx.prof_enable(False)
+        recs = ctx.prof_records()
+        ctx.prof_enable(False)
+        # ---- decode probe: the decode chain runs inside hipGraphs in the timed region, where single launches
+        # cannot be bracketed by events.  Re-run a few decode steps of the SAME batch eagerly (CCX_NO_GRAPH) with the
+        # per-launch HIP events on, to get the average launch duration of the graph-resident kernels.
+        probe_steps = 6
+        wm = models["whisper_model"] if pipeline else model
+        span = args.decode_span if (pipeline and args.schedule == "pipelined") else 1
+        Bd = min(args.whisper_group, 6 * B * span) if pipeline else B
+        # Two probes.  (1) a group 16 rows per lane SMALLER than the timed one (768 -> 720 sequences = 3 lanes of 240): the same kernels and
+        # lane count but a launch shape of its own, so that rocprofv3's per-grid summary of this command (tools/kernel_trace_by_grid.py,
+        # profiles/) shows exactly these launches in a row of their own next to `roofline.probe_distinct_grid.avg_launch_us`.  (2) the timed
+        # region's own group size: `roofline.achieved` is measured AT the launch shape the timed region runs (a cross-attention launch takes
+        # as long as the CU with the most blocks: 240 rows = 480 blocks leave the chip unevenly loaded, 256 rows = 512 blocks do not).
+        def n_lanes(b):                       # as ccx_whisper_decode cuts a group into lanes
+            if xstream:
+                return 3 if b >= 320 else 1
+            return 2 if b >= 640 else (3 if b >= 144 else (2 if b >= 96 else 1))
+        nl_real = n_lanes(Bd)
+        Bp = Bd - 16 * nl_real
+        if n_lanes(Bp) != nl_real or nl_real == 1:
+            Bp = Bd
+        os.environ["CCX_NO_GRAPH"] = "1"
+        probe_x = None
+        if Bp != Bd:
+            ctx.prof_enable(True)
+            wm.decode_greedy([[rules.sot]] * Bp, sample_len=probe_steps)
+            torch.cuda.synchronize()
+            probe_x = ctx.prof_records()
+            ctx.prof_enable(False)
+        ctx.prof_enable(True)
+        wm.decode_greedy([[rules.sot]] * Bd, sample_len=probe_steps)
+        torch.cuda.synchronize()
+        probe = ctx.prof_records()
+        ctx.prof_enable(False)
+        del os.environ["CCX_NO_GRAPH"]
+        # ---- the same launch IN SITU: graph replay, all lanes of the group stepping concurrently (in-graph time stamps around every
+        # layer's cross attention; the solo figure above times one launch at a time)
+        in_situ = None
+        if rank == 0:
+            import tempfile
+            tr = os.path.join(tempfile.gettempdir(), f"ccx_lane_trace_{os.getpid()}.txt")
+            if os.path.exists(tr):
+                os.remove(tr)
+            wm.trace_lanes(tr, 1)
+            for _ in range(2):                                   # the first decode captures the stamped step graphs, the second replays them
+                wm.decode_greedy([[rules.sot]] * Bd, sample_len=24)
+            torch.cuda.synchronize()
+            wm.trace_lanes(None)
+            if os.path.exists(tr):
+                in_situ = lane_cross_attention_in_situ(tr, cross_bytes_per_sequence(dims, xstream))
+                os.remove(tr)
+        # decode launches per pipeline step: a unit of `span` batches is decoded in ceil(6 B span / Bd) groups
+        decode_steps_per_step = (args.sample_len + 1) * (((6 * B * span + Bd - 1) // Bd) / span if pipeline else 1)
     if pipeline and args.stage_times:
         bp.stage_ms = {}
         bp.run_pinned(audio, timed=True)
-    # which cross attention the decode groups run (CCX_CROSS_X=0 at model creation: round 2's per-layer K/V caches)
-    xstream = os.environ.get("CCX_CROSS_X", "1") != "0" and dims.n_text_state in (128, 256, 384, 512, 768) and dims.n_text_head * 64 == dims.n_text_state
-    # ---- decode probe: the decode chain runs inside hipGraphs in the timed region, where single launches
-    # cannot be bracketed by events.  Re-run a few decode steps of the SAME batch eagerly (CCX_NO_GRAPH) with the
-    # per-launch HIP events on, to get the average launch duration of the graph-resident kernels.
-    probe_steps = 6
-    wm = models["whisper_model"] if pipeline else model
-    span = args.decode_span if (pipeline and args.schedule == "pipelined") else 1
-    Bd = min(args.whisper_group, 6 * B * span) if pipeline else B
-    # Two probes.  (1) a group 16 rows per lane SMALLER than the timed one (768 -> 720 sequences = 3 lanes of 240): the same kernels and
-    # lane count but a launch shape of its own, so that rocprofv3's per-grid summary of this command (tools/kernel_trace_by_grid.py,
-    # profiles/) shows exactly these launches in a row of their own next to `roofline.probe_distinct_grid.avg_launch_us`.  (2) the timed
-    # region's own group size: `roofline.achieved` is measured AT the launch shape the timed region runs (a cross-attention launch takes
-    # as long as the CU with the most blocks: 240 rows = 480 blocks leave the chip unevenly loaded, 256 rows = 512 blocks do not).
-    def n_lanes(b):                       # as ccx_whisper_decode cuts a group into lanes
-        if xstream:
-            return 3 if b >= 320 else 1
-        return 2 if b >= 640 else (3 if b >= 144 else (2 if b >= 96 else 1))
-    nl_real = n_lanes(Bd)
-    Bp = Bd - 16 * nl_real
-    if n_lanes(Bp) != nl_real or nl_real == 1:
-        Bp = Bd
-    os.environ["CCX_NO_GRAPH"] = "1"
-    probe_x = None
-    if Bp != Bd:
-        ctx.prof_enable(True)
-        wm.decode_greedy([[rules.sot]] * Bp, sample_len=probe_steps)
-        torch.cuda.synchronize()
-        probe_x = ctx.prof_records()
-        ctx.prof_enable(False)
-    ctx.prof_enable(True)
-    wm.decode_greedy([[rules.sot]] * Bd, sample_len=probe_steps)
-    torch.cuda.synchronize()
-    probe = ctx.prof_records()
-    ctx.prof_enable(False)
-    del os.environ["CCX_NO_GRAPH"]
-    # ---- the same launch IN SITU: graph replay, all lanes of the group stepping concurrently (in-graph time stamps around every
-    # layer's cross attention; the solo figure above times one launch at a time)
-    in_situ = None
-    if rank == 0:
-        import tempfile
-        tr = os.path.join(tempfile.gettempdir(), f"ccx_lane_trace_{os.getpid()}.txt")
-        if os.path.exists(tr):
-            os.remove(tr)
-        wm.trace_lanes(tr, 1)
-        for _ in range(2):                                   # the first decode captures the stamped step graphs, the second replays them
-            wm.decode_greedy([[rules.sot]] * Bd, sample_len=24)
-        torch.cuda.synchronize()
-        wm.trace_lanes(None)
-        if os.path.exists(tr):
-            in_situ = lane_cross_attention_in_situ(tr, cross_bytes_per_sequence(dims, xstream))
-            os.remove(tr)
-    # decode launches per pipeline step: a unit of `span` batches is decoded in ceil(6 B span / Bd) groups
-    decode_steps_per_step = (args.sample_len + 1) * (((6 * B * span + Bd - 1) // Bd) / span if pipeline else 1)
 
     if dist is not None:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
@@ -533,175 +589,176 @@ def main():
     value = audio_s / dt
 
     if rank == 0:
-        # ---- roofline of the kernel with the largest time per step (HIP events on the launch stream: eager kernels during one extra
-        # step right after the timed region, graph-resident decode kernels during an eager re-run of a few decode steps) ----
-        def aggregate_records(rs):
-            out_ = {}
-            for name, fl, by, ms in rs:
-                a = out_.setdefault(name, [0, 0.0, 0.0, 0.0])
-                a[0] += 1; a[1] += fl; a[2] += by; a[3] += ms
-            return out_
+        roof = roof_mfma = cpu = stage_ms = None
+        if args.full:
+            # ---- roofline of the kernel with the largest time per step (HIP events on the launch stream: eager kernels during one extra
+            # step right after the timed region, graph-resident decode kernels during an eager re-run of a few decode steps) ----
+            def aggregate_records(rs):
+                out_ = {}
+                for name, fl, by, ms in rs:
+                    a = out_.setdefault(name, [0, 0.0, 0.0, 0.0])
+                    a[0] += 1; a[1] += fl; a[2] += by; a[3] += ms
+                return out_
 
-        def roof_entry(name, cnt_, fl, by, ms, where):
-            pmc = {}
-            pfs = sorted((ROOT / "profiles").glob("r*_pmc_traffic.json"))       # the newest round's counter passes
-            if pfs:
-                pmc = json.loads(pfs[-1].read_text()).get(name, {})
-            if name in MFMA_KERNELS:
-                ach = fl / (ms * 1e-3) / 1e12
-                return dict(kernel=name, bound="mfma", achieved=round(ach, 2), peak=PEAK_MFMA_BF16_TFLOPS, unit="TFLOP/s",
-                            frac=round(ach / PEAK_MFMA_BF16_TFLOPS, 4), traffic=pmc.get("hbm_bytes_per_launch"), launches=cnt_,
-                            avg_launch_us=round(ms * 1e3 / cnt_, 2), flops_per_launch=fl / cnt_, measured=where)
-            ach = by / (ms * 1e-3) / 1e9
-            traffic = pmc.get("hbm_bytes_per_launch")
-            if traffic is not None and pmc.get("sequences_per_launch"):
-                # measured at `sequences_per_launch` per launch (counter passes serialise the lanes); equal to this run's launch
-                # shape when the newest committed pass was taken at it, scaled by the sequence count otherwise
-                traffic = traffic / pmc["sequences_per_launch"] * (by / cnt_) / cross_bytes_per_sequence(dims, xstream)
-            return dict(kernel=name, bound="hbm", achieved=round(ach, 1), peak=PEAK_HBM_GBS, unit="GB/s",
-                        frac=round(ach / PEAK_HBM_GBS, 4), traffic=traffic,
-                        traffic_source=(f"{pfs[-1].name}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, {pmc.get('sequences_per_launch')} sequences per launch there"
-                                        if traffic is not None and pfs else None), launches=cnt_,
-                        avg_launch_us=round(ms * 1e3 / cnt_, 2), bytes_per_launch=by / cnt_, measured=where)
+            def roof_entry(name, cnt_, fl, by, ms, where):
+                pmc = {}
+                pfs = sorted((ROOT / "profiles").glob("r*_pmc_traffic.json"))       # the newest round's counter passes
+                if pfs:
+                    pmc = json.loads(pfs[-1].read_text()).get(name, {})
+                if name in MFMA_KERNELS:
+                    ach = fl / (ms * 1e-3) / 1e12
+                    return dict(kernel=name, bound="mfma", achieved=round(ach, 2), peak=PEAK_MFMA_BF16_TFLOPS, unit="TFLOP/s",
+                                frac=round(ach / PEAK_MFMA_BF16_TFLOPS, 4), traffic=pmc.get("hbm_bytes_per_launch"), launches=cnt_,
+                                avg_launch_us=round(ms * 1e3 / cnt_, 2), flops_per_launch=fl / cnt_, measured=where)
+                ach = by / (ms * 1e-3) / 1e9
+                traffic = pmc.get("hbm_bytes_per_launch")
+                if traffic is not None and pmc.get("sequences_per_launch"):
+                    # measured at `sequences_per_launch` per launch (counter passes serialise the lanes); equal to this run's launch
+                    # shape when the newest committed pass was taken at it, scaled by the sequence count otherwise
+                    traffic = traffic / pmc["sequences_per_launch"] * (by / cnt_) / cross_bytes_per_sequence(dims, xstream)
+                return dict(kernel=name, bound="hbm", achieved=round(ach, 1), peak=PEAK_HBM_GBS, unit="GB/s",
+                            frac=round(ach / PEAK_HBM_GBS, 4), traffic=traffic,
+                            traffic_source=(f"{pfs[-1].name}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, {pmc.get('sequences_per_launch')} sequences per launch there"
+                                            if traffic is not None and pfs else None), launches=cnt_,
+                            avg_launch_us=round(ms * 1e3 / cnt_, 2), bytes_per_launch=by / cnt_, measured=where)
 
-        # GEMM launches carry per-shape labels ("gemm<epi1,256x256> M=288000 N=3072 K=768 taps=1"): the encoder's are the ones whose
-        # M is the group's windows x 1500 / 1501 / 3000 rows (layers, conv2, conv1); all of them fold back into the family entry
-        nwin = min(args.whisper_group, 6 * B) if pipeline else B
-        enc_rows = {f" M={nwin * r} " for r in (1500, 1501, 3000)}
-        enc_fl = enc_ms = 0.0
-        enc_n = 0
-        folded = []
-        recs0 = recs
-        for name, fl, by, ms in recs:
-            if name.startswith("gemm<"):
-                if any(t in name for t in enc_rows):
-                    enc_fl += fl; enc_ms += ms; enc_n += 1
-                name = "gemm_bf16_nt_kernel"
-            elif name.startswith("layernorm_kernel"):
-                name = "layernorm_kernel"
-            folded.append((name, fl, by, ms))
-        recs = folded
-        agg = aggregate_records(recs)
-        pagg = aggregate_records([("gemm_bf16_nt_kernel" if n.startswith("gemm<") else n, f, b_, m) for n, f, b_, m in probe])
-        # per-step totals: eager kernels as recorded over the timed steps; graph-resident decode kernels = probe average
-        # launch time x their launches per step
-        where_eager = "HIP events on the launch stream, one extra step of the same batch right after the timed region"
-        per_step = {k: (v[3] / prof_steps, where_eager) for k, v in agg.items() if v[1] > 0 or v[2] > 0}
-        for k, v in pagg.items():
-            if k.startswith("dec_") and (v[1] > 0 or v[2] > 0):
-                launches = v[0] / (probe_steps) * decode_steps_per_step
-                # (scaled from the probe's lane size to the timed group's: these kernels' time is proportional to the rows they stream)
-                per_step[k] = (v[3] / v[0] * launches,
-                               f"HIP events on the lanes' streams, eager re-run of {probe_steps} decode steps of the {Bd}-sequence group of the "
-                               f"timed region on the encoded batch ({nl_real} lane(s); graph-resident in the timed region)")
-        roof = roof_mfma = None
-        if per_step:
-            name = max(per_step, key=lambda k: per_step[k][0])
-            src = pagg if name.startswith("dec_") else agg
-            cnt_, fl, by, ms = src[name]
-            roof = roof_entry(name, cnt_, fl, by, ms, per_step[name][1])
-            roof["ms_per_step"] = round(per_step[name][0], 2)
-            if probe_x is not None and name.startswith("dec_"):
-                xr = [(fl_, by_, ms_) for n_, fl_, by_, ms_ in probe_x if n_ == name]
-                if xr:
-                    roof["probe_distinct_grid"] = dict(sequences=Bp, launches=len(xr), avg_launch_us=round(sum(r_[2] for r_ in xr) * 1e3 / len(xr), 2),
-                                                       bytes_per_launch=sum(r_[1] for r_ in xr) / len(xr),
-                                                       what=f"the same eager probe on a {Bp}-sequence group: a grid no other launch of this process has "
-                                                            "(the row to look for in profiles/*_default_kernel_stats_by_grid.csv)")
-            if name.startswith(("dec_cross_stream_kernel", "dec_xs_stream_kernel")) and in_situ:
-                # the same kernel inside the replayed step graphs with every lane of the group running: bytes of a lane's launch /
-                # median stamp-to-stamp time, averaged over the lanes
-                gbs = float(np.mean([l["gbs"] for l in in_situ]))
-                roof["achieved_in_situ"] = round(gbs, 1)
-                roof["frac_in_situ"] = round(gbs / PEAK_HBM_GBS, 4)
-                # time per pipeline step of this kernel at the in-situ launch time: launches per step x median lane launch (the per-grid
-                # rocprofv3 summary of the same command times the same launches, with the lanes serialised by the tracer)
-                launches_step = pagg[name][0] / probe_steps * decode_steps_per_step
-                roof["ms_per_step_in_situ"] = round(float(np.mean([l["median_us"] for l in in_situ])) * launches_step * 1e-3, 2)
-                steps = [l["step_median_us"] for l in in_situ if l.get("step_median_us")]
-                if steps:
-                    # the WHOLE decode step of the group: every lane's cross-KV + the decoder weights each lane streams once per step
-                    # (self-KV is < 1 % at the trace's <= 24 positions), all lanes concurrent, over the median lane step time
-                    by_step = float(sum(decode_bytes_per_step(dims, l["sequences"], xstream) for l in in_situ))
-                    roof["decode_step_in_situ"] = dict(bytes=by_step, median_us=round(float(np.mean(steps)), 1),
-                                                       achieved=round(by_step / (float(np.mean(steps)) * 1e-6) / 1e9, 1),
-                                                       frac=round(by_step / (float(np.mean(steps)) * 1e-6) / 1e9 / PEAK_HBM_GBS, 4), unit="GB/s",
-                                                       what="all kernels of one decode step of the whole group (cross attention, self attention, "
-                                                            "linears, logits, select), lanes concurrent, graph replay")
-                roof["in_situ"] = dict(lanes=[{k: (round(v, 1) if isinstance(v, float) else v) for k, v in l.items()} for l in in_situ],
-                                       measured="in-graph s_memrealtime stamps around every layer's cross attention (ccx_whisper_trace_lanes), "
-                                                f"graph replay of a {Bd}-sequence group, all lanes concurrent; includes the ~2 us stamp nodes"
-                                                + ("; with the cross attention against the encoder output the stamps bracket its THREE launches (LayerNorm + "
-                                                   "query projection + expansion, the streaming kernel, merge + value projection: 17 + 110 + 8 us alone), and "
-                                                   "`achieved_in_situ` divides the streaming kernel's bytes by the whole bracket" if xstream else ""))
-        if "gemm_bf16_nt_kernel" in agg and (roof is None or roof["kernel"] != "gemm_bf16_nt_kernel"):
-            cnt_, fl, by, ms = agg["gemm_bf16_nt_kernel"]
-            roof_mfma = roof_entry("gemm_bf16_nt_kernel", cnt_, fl, by, ms, where_eager)
-            roof_mfma["scope"] = "every GEMM launch of a step (encoder, ResNet-34, SepFormer, TDNN, heads, logits)"
-            if enc_ms > 0:
-                ach = enc_fl / (enc_ms * 1e-3) / 1e12
-                roof_mfma["whisper_encoder_gemms"] = dict(achieved=round(ach, 2), unit="TFLOP/s", frac=round(ach / PEAK_MFMA_BF16_TFLOPS, 4),
-                                                          launches=enc_n, ms_per_step=round(enc_ms / prof_steps, 2))
-                # the WHOLE encoder: its GEMMs + attention + LayerNorms (every launch between log-mel and the decoder) against the
-                # algorithmic GFLOP per window (encoder 344.2; + cross-KV projection 42.5 only where it is still computed)
-                att_ms = sum(ms for n_, _, _, ms in recs if n_ == "enc_attention_kernel")
-                ln_ms = sum(ms for n_, _, _, ms in recs0 if n_.startswith("layernorm_kernel M=") and f" M={nwin * dims.n_audio_ctx} " in n_ + " ")
-                wins = (6 * B if pipeline else B) * prof_steps
-                tot_ms = enc_ms + att_ms + ln_ms
-                gfl_win = float(enc_flops_per_window(dims)[0] + (0 if xstream else enc_flops_per_window(dims)[1]))
-                fl_tot = wins * gfl_win
-                ach_t = fl_tot / (tot_ms * 1e-3) / 1e12
-                roof_mfma["whisper_encoder_total"] = dict(achieved=round(ach_t, 2), unit="TFLOP/s", frac=round(ach_t / PEAK_MFMA_BF16_TFLOPS, 4),
-                                                          gemm_ms=round(enc_ms / prof_steps, 2), attention_ms=round(att_ms / prof_steps, 2),
-                                                          layernorm_ms=round(ln_ms / prof_steps, 2), windows_per_step=wins // prof_steps,
-                                                          gflop_per_window=round(gfl_win / 1e9, 1))
-        if roof_mfma is not None:
-            # what the matrix cores of this part sustain at the phased GEMM's footprint (tools/microbench_mfma_ceiling.hip, committed once
-            # per round): nothing but MFMAs on random operands, and the same with the main loop's LDS operand reads beside them
-            cf = sorted((ROOT / "profiles").glob("r*_mfma_ceiling.json"))
-            if cf:
-                cj = json.loads(cf[-1].read_text())
-                ceil = cj["mfma_with_lds_operand_reads"]["tflops"]
-                roof_mfma["measured_ceiling"] = dict(file=f"profiles/{cf[-1].name}", bare_mfma_tflops=cj["bare_mfma"]["tflops"],
-                                                     with_lds_operand_reads_tflops=ceil, shader_clock_mhz=cj["mfma_with_lds_operand_reads"]["shader_clock_mhz"],
-                                                     what="v_mfma_f32_16x16x32_bf16 only, 8 waves per CU, 128 accumulator registers, random bf16 operands")
-                roof_mfma["frac_of_measured_ceiling"] = round(roof_mfma["achieved"] / ceil, 4)
-                for k in ("whisper_encoder_gemms", "whisper_encoder_total"):
-                    if k in roof_mfma:
-                        roof_mfma[k]["frac_of_measured_ceiling"] = round(roof_mfma[k]["achieved"] / ceil, 4)
-        stage_ms = {k: round(v[3] / prof_steps, 3) for k, v in agg.items()}
-        stage_ms.update({k: round(v[0], 3) for k, v in per_step.items()})
+            # GEMM launches carry per-shape labels ("gemm<epi1,256x256> M=288000 N=3072 K=768 taps=1"): the encoder's are the ones whose
+            # M is the group's windows x 1500 / 1501 / 3000 rows (layers, conv2, conv1); all of them fold back into the family entry
+            nwin = min(args.whisper_group, 6 * B) if pipeline else B
+            enc_rows = {f" M={nwin * r} " for r in (1500, 1501, 3000)}
+            enc_fl = enc_ms = 0.0
+            enc_n = 0
+            folded = []
+            recs0 = recs
+            for name, fl, by, ms in recs:
+                if name.startswith("gemm<"):
+                    if any(t in name for t in enc_rows):
+                        enc_fl += fl; enc_ms += ms; enc_n += 1
+                    name = "gemm_bf16_nt_kernel"
+                elif name.startswith("layernorm_kernel"):
+                    name = "layernorm_kernel"
+                folded.append((name, fl, by, ms))
+            recs = folded
+            agg = aggregate_records(recs)
+            pagg = aggregate_records([("gemm_bf16_nt_kernel" if n.startswith("gemm<") else n, f, b_, m) for n, f, b_, m in probe])
+            # per-step totals: eager kernels as recorded over the timed steps; graph-resident decode kernels = probe average
+            # launch time x their launches per step
+            where_eager = "HIP events on the launch stream, one extra step of the same batch right after the timed region"
+            per_step = {k: (v[3] / prof_steps, where_eager) for k, v in agg.items() if v[1] > 0 or v[2] > 0}
+            for k, v in pagg.items():
+                if k.startswith("dec_") and (v[1] > 0 or v[2] > 0):
+                    launches = v[0] / (probe_steps) * decode_steps_per_step
+                    # (scaled from the probe's lane size to the timed group's: these kernels' time is proportional to the rows they stream)
+                    per_step[k] = (v[3] / v[0] * launches,
+                                   f"HIP events on the lanes' streams, eager re-run of {probe_steps} decode steps of the {Bd}-sequence group of the "
+                                   f"timed region on the encoded batch ({nl_real} lane(s); graph-resident in the timed region)")
+            roof = roof_mfma = None
+            if per_step:
+                name = max(per_step, key=lambda k: per_step[k][0])
+                src = pagg if name.startswith("dec_") else agg
+                cnt_, fl, by, ms = src[name]
+                roof = roof_entry(name, cnt_, fl, by, ms, per_step[name][1])
+                roof["ms_per_step"] = round(per_step[name][0], 2)
+                if probe_x is not None and name.startswith("dec_"):
+                    xr = [(fl_, by_, ms_) for n_, fl_, by_, ms_ in probe_x if n_ == name]
+                    if xr:
+                        roof["probe_distinct_grid"] = dict(sequences=Bp, launches=len(xr), avg_launch_us=round(sum(r_[2] for r_ in xr) * 1e3 / len(xr), 2),
+                                                           bytes_per_launch=sum(r_[1] for r_ in xr) / len(xr),
+                                                           what=f"the same eager probe on a {Bp}-sequence group: a grid no other launch of this process has "
+                                                                "(the row to look for in profiles/*_default_kernel_stats_by_grid.csv)")
+                if name.startswith(("dec_cross_stream_kernel", "dec_xs_stream_kernel")) and in_situ:
+                    # the same kernel inside the replayed step graphs with every lane of the group running: bytes of a lane's launch /
+                    # median stamp-to-stamp time, averaged over the lanes
+                    gbs = float(np.mean([l["gbs"] for l in in_situ]))
+                    roof["achieved_in_situ"] = round(gbs, 1)
+                    roof["frac_in_situ"] = round(gbs / PEAK_HBM_GBS, 4)
+                    # time per pipeline step of this kernel at the in-situ launch time: launches per step x median lane launch (the per-grid
+                    # rocprofv3 summary of the same command times the same launches, with the lanes serialised by the tracer)
+                    launches_step = pagg[name][0] / probe_steps * decode_steps_per_step
+                    roof["ms_per_step_in_situ"] = round(float(np.mean([l["median_us"] for l in in_situ])) * launches_step * 1e-3, 2)
+                    steps = [l["step_median_us"] for l in in_situ if l.get("step_median_us")]
+                    if steps:
+                        # the WHOLE decode step of the group: every lane's cross-KV + the decoder weights each lane streams once per step
+                        # (self-KV is < 1 % at the trace's <= 24 positions), all lanes concurrent, over the median lane step time
+                        by_step = float(sum(decode_bytes_per_step(dims, l["sequences"], xstream) for l in in_situ))
+                        roof["decode_step_in_situ"] = dict(bytes=by_step, median_us=round(float(np.mean(steps)), 1),
+                                                           achieved=round(by_step / (float(np.mean(steps)) * 1e-6) / 1e9, 1),
+                                                           frac=round(by_step / (float(np.mean(steps)) * 1e-6) / 1e9 / PEAK_HBM_GBS, 4), unit="GB/s",
+                                                           what="all kernels of one decode step of the whole group (cross attention, self attention, "
+                                                                "linears, logits, select), lanes concurrent, graph replay")
+                    roof["in_situ"] = dict(lanes=[{k: (round(v, 1) if isinstance(v, float) else v) for k, v in l.items()} for l in in_situ],
+                                           measured="in-graph s_memrealtime stamps around every layer's cross attention (ccx_whisper_trace_lanes), "
+                                                    f"graph replay of a {Bd}-sequence group, all lanes concurrent; includes the ~2 us stamp nodes"
+                                                    + ("; with the cross attention against the encoder output the stamps bracket its THREE launches (LayerNorm + "
+                                                       "query projection + expansion, the streaming kernel, merge + value projection: 17 + 110 + 8 us alone), and "
+                                                       "`achieved_in_situ` divides the streaming kernel's bytes by the whole bracket" if xstream else ""))
+            if "gemm_bf16_nt_kernel" in agg and (roof is None or roof["kernel"] != "gemm_bf16_nt_kernel"):
+                cnt_, fl, by, ms = agg["gemm_bf16_nt_kernel"]
+                roof_mfma = roof_entry("gemm_bf16_nt_kernel", cnt_, fl, by, ms, where_eager)
+                roof_mfma["scope"] = "every GEMM launch of a step (encoder, ResNet-34, SepFormer, TDNN, heads, logits)"
+                if enc_ms > 0:
+                    ach = enc_fl / (enc_ms * 1e-3) / 1e12
+                    roof_mfma["whisper_encoder_gemms"] = dict(achieved=round(ach, 2), unit="TFLOP/s", frac=round(ach / PEAK_MFMA_BF16_TFLOPS, 4),
+                                                              launches=enc_n, ms_per_step=round(enc_ms / prof_steps, 2))
+                    # the WHOLE encoder: its GEMMs + attention + LayerNorms (every launch between log-mel and the decoder) against the
+                    # algorithmic GFLOP per window (encoder 344.2; + cross-KV projection 42.5 only where it is still computed)
+                    att_ms = sum(ms for n_, _, _, ms in recs if n_ == "enc_attention_kernel")
+                    ln_ms = sum(ms for n_, _, _, ms in recs0 if n_.startswith("layernorm_kernel M=") and f" M={nwin * dims.n_audio_ctx} " in n_ + " ")
+                    wins = (6 * B if pipeline else B) * prof_steps
+                    tot_ms = enc_ms + att_ms + ln_ms
+                    gfl_win = float(enc_flops_per_window(dims)[0] + (0 if xstream else enc_flops_per_window(dims)[1]))
+                    fl_tot = wins * gfl_win
+                    ach_t = fl_tot / (tot_ms * 1e-3) / 1e12
+                    roof_mfma["whisper_encoder_total"] = dict(achieved=round(ach_t, 2), unit="TFLOP/s", frac=round(ach_t / PEAK_MFMA_BF16_TFLOPS, 4),
+                                                              gemm_ms=round(enc_ms / prof_steps, 2), attention_ms=round(att_ms / prof_steps, 2),
+                                                              layernorm_ms=round(ln_ms / prof_steps, 2), windows_per_step=wins // prof_steps,
+                                                              gflop_per_window=round(gfl_win / 1e9, 1))
+            if roof_mfma is not None:
+                # what the matrix cores of this part sustain at the phased GEMM's footprint (tools/microbench_mfma_ceiling.hip, committed once
+                # per round): nothing but MFMAs on random operands, and the same with the main loop's LDS operand reads beside them
+                cf = sorted((ROOT / "profiles").glob("r*_mfma_ceiling.json"))
+                if cf:
+                    cj = json.loads(cf[-1].read_text())
+                    ceil = cj["mfma_with_lds_operand_reads"]["tflops"]
+                    roof_mfma["measured_ceiling"] = dict(file=f"profiles/{cf[-1].name}", bare_mfma_tflops=cj["bare_mfma"]["tflops"],
+                                                         with_lds_operand_reads_tflops=ceil, shader_clock_mhz=cj["mfma_with_lds_operand_reads"]["shader_clock_mhz"],
+                                                         what="v_mfma_f32_16x16x32_bf16 only, 8 waves per CU, 128 accumulator registers, random bf16 operands")
+                    roof_mfma["frac_of_measured_ceiling"] = round(roof_mfma["achieved"] / ceil, 4)
+                    for k in ("whisper_encoder_gemms", "whisper_encoder_total"):
+                        if k in roof_mfma:
+                            roof_mfma[k]["frac_of_measured_ceiling"] = round(roof_mfma[k]["achieved"] / ceil, 4)
+            stage_ms = {k: round(v[3] / prof_steps, 3) for k, v in agg.items()}
+            stage_ms.update({k: round(v[0], 3) for k, v in per_step.items()})
 
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            threads = min(os.cpu_count() or 1, 32)
-            if pipeline:
-                sdims = SepDims()
-                msd = (dims, ck[1] if ck is not None else synthetic_whisper_state_dict(dims, seed=0), sdims,
-                       synthetic_sepformer_state_dict(sdims, seed=1), synthetic_xvector_state_dict(seed=2),
-                       synthetic_pyannet_state_dict(7, seed=3), synthetic_resnet34_state_dict(seed=5))
-                xrt, sample = cpu_baseline_pipeline(msd, clips[0], rules, threads)
-            else:
-                w = cpu_baseline_whisper(dims, sd, clips[0], rules, threads, tokens=args.sample_len)
-                xrt = 30.0 / w["total"]
-                sample = f"1 x 30 s clip: log-mel + small.en encoder + {w['n_tok']}-token greedy decode, fp32 torch, {w['total']:.1f} s"
-            cpu = dict(value=round(xrt, 3), unit="xRT (audio-sec/wall-sec)", cores=threads, kind="port",
-                       method="extrapolated: bounded op samples x one clip's op counts" if pipeline else "measured end to end on one clip",
-                       sample=sample)
-            if pipeline:
-                # one full clip WAS timed end to end through the same oracle pipeline on a GPU box's host cores (tools/cpu_full_clip.py,
-                # ~100 s of CPU work: once per round, committed).  That MEASURED figure is `value`; this run's bounded-sample
-                # extrapolation stays beside it as `extrapolated`
-                full = sorted((ROOT / "profiles").glob("r*_cpu_full_clip.json"))
-                if full:
-                    fc = json.loads(full[-1].read_text())
-                    cpu = dict(value=fc["xrt"], unit="xRT (audio-sec/wall-sec)", cores=fc["threads"], kind="port",
-                               method=f"measured end to end: ONE full 30 s clip through the oracle pipeline on {fc['threads']} host threads of a GPU box "
-                                      f"(tools/cpu_full_clip.py, committed as profiles/{full[-1].name})",
-                               sample=f"one full 30 s clip under the pinned schedule (6 Whisper calls x 224 tokens, 4 separator regions, 62 x-vector crops, "
-                                      f"VAD + diarization): {fc['total_s']} s of CPU work = {fc['xrt']} xRT",
-                               extrapolated=dict(value=round(xrt, 3), cores=threads, sample=sample, over_measured=round(xrt / fc["xrt"], 3),
-                                                 method="this run: bounded op samples x one clip's op counts"))
+            if not args.no_cpu_baseline and world == 1:
+                threads = min(os.cpu_count() or 1, 32)
+                if pipeline:
+                    sdims = SepDims()
+                    msd = (dims, ck[1] if ck is not None else synthetic_whisper_state_dict(dims, seed=0), sdims,
+                           synthetic_sepformer_state_dict(sdims, seed=1), synthetic_xvector_state_dict(seed=2),
+                           synthetic_pyannet_state_dict(7, seed=3), synthetic_resnet34_state_dict(seed=5))
+                    xrt, sample = cpu_baseline_pipeline(msd, clips[0], rules, threads)
+                else:
+                    w = cpu_baseline_whisper(dims, sd, clips[0], rules, threads, tokens=args.sample_len)
+                    xrt = 30.0 / w["total"]
+                    sample = f"1 x 30 s clip: log-mel + small.en encoder + {w['n_tok']}-token greedy decode, fp32 torch, {w['total']:.1f} s"
+                cpu = dict(value=round(xrt, 3), unit="xRT (audio-sec/wall-sec)", cores=threads, kind="port",
+                           method="extrapolated: bounded op samples x one clip's op counts" if pipeline else "measured end to end on one clip",
+                           sample=sample)
+                if pipeline:
+                    # one full clip WAS timed end to end through the same oracle pipeline on a GPU box's host cores (tools/cpu_full_clip.py,
+                    # ~100 s of CPU work: once per round, committed).  That MEASURED figure is `value`; this run's bounded-sample
+                    # extrapolation stays beside it as `extrapolated`
+                    full = sorted((ROOT / "profiles").glob("r*_cpu_full_clip.json"))
+                    if full:
+                        fc = json.loads(full[-1].read_text())
+                        cpu = dict(value=fc["xrt"], unit="xRT (audio-sec/wall-sec)", cores=fc["threads"], kind="port",
+                                   method=f"measured end to end: ONE full 30 s clip through the oracle pipeline on {fc['threads']} host threads of a GPU box "
+                                          f"(tools/cpu_full_clip.py, committed as profiles/{full[-1].name})",
+                                   sample=f"one full 30 s clip under the pinned schedule (6 Whisper calls x 224 tokens, 4 separator regions, 62 x-vector crops, "
+                                          f"VAD + diarization): {fc['total_s']} s of CPU work = {fc['xrt']} xRT",
+                                   extrapolated=dict(value=round(xrt, 3), cores=threads, sample=sample, over_measured=round(xrt / fc["xrt"], 3),
+                                                     method="this run: bounded op samples x one clip's op counts"))
 
         enc_f, cross_f = enc_flops_per_window(dims)
         cfg = {"workload": "full_pipeline_vad_diarize_separate_transcribe (BASELINE configs[3])" if pipeline

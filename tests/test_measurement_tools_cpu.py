@@ -76,6 +76,56 @@ def test_bench_refuses_diagnostic_switches(monkeypatch):
     assert "CCX_ABLATE" in str(e.value)
 
 
+def test_bench_dumps_decode_records_as_float_arrays(tmp_path):
+    """--dump-outputs: the records of the last step as float32 / float64 .npy files that load back to the same values; other dtypes
+    and more than 64 MB in all are refused."""
+    bench = importlib.import_module("bench")
+    recs = [dict(tokens=[50364, 7, 51864], sum_logprob=-1.5, avg_logprob=-0.375, no_speech_prob=0.25),
+            dict(tokens=[], sum_logprob=-0.125, avg_logprob=-0.125, no_speech_prob=0.5)]
+    arrays = bench.decode_arrays(recs, sample_len=4)
+    arrays["segment_similarity"] = np.array([0.5, -0.25])
+    bench.dump_outputs(str(tmp_path / "out"), arrays)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert set(got) == {"tokens", "n_tokens", "sum_logprob", "avg_logprob", "no_speech_prob", "segment_similarity"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["tokens"].tolist() == [[50364, 7, 51864, -1], [-1, -1, -1, -1]] and got["n_tokens"].tolist() == [3, 0]
+    assert got["sum_logprob"].tolist() == [-1.5, -0.125] and got["no_speech_prob"].tolist() == [0.25, 0.5]
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "bad"), {"ids": np.zeros(3, np.int32)})
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.MAX_DUMP_BYTES // 8 + 1, np.float64)})
+    assert not (tmp_path / "bad").exists() and not (tmp_path / "big").exists()
+
+
+def test_bench_plain_run_leaves_the_extra_measurements_to_full(monkeypatch):
+    """The power probe (the first of the --full measurements a run starts, before the GPU) is taken with --full only; a run
+    without timed steps is refused."""
+    bench = importlib.import_module("bench")
+    seen = {}
+
+    class Stop(Exception):
+        pass
+
+    def fake_probe():
+        seen["probe"] = True
+        raise Stop
+
+    def fake_set_device(dev):
+        raise Stop
+    monkeypatch.setattr(bench, "PowerProbe", fake_probe)
+    monkeypatch.setattr(bench.torch.cuda, "set_device", fake_set_device)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    for argv, probed in ((["bench.py", "--steps", "3", "--warmup", "1"], False), (["bench.py", "--full"], True)):
+        seen.clear()
+        monkeypatch.setattr(sys, "argv", argv)
+        with pytest.raises(Stop):
+            bench.main()
+        assert seen.get("probe", False) == probed
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.main()
+
+
 def test_pmc_reduction_doubles_fetch_and_reads_sequences_off_the_grid(tmp_path):
     def write(path, counter, rows):
         with open(path, "w", newline="") as f:
