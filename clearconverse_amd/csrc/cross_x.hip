@@ -535,21 +535,16 @@ int launch_xs(ccx_ctx* ctx, const XsParams& p, hipStream_t stream) {
   using G = XsGeom<D>;
   // p.lds_pad: dynamic LDS the streaming blocks claim without using it -- 64 KB leave ONE block per CU (which pulls the same ~25 GB/s
   // as two), so that the chain kernels of the other decode lanes find wave slots and a shorter memory queue on every CU: 768-sequence
-  // decode step 6.25 -> 5.87 ms with two lanes.  CCX_XS_LDS_PAD overrides (experiments).
-  static const int forced_pad = [] { const char* e = getenv("CCX_XS_LDS_PAD"); return e ? atoi(e) : -1; }();
-  const int lds_pad = forced_pad >= 0 ? forced_pad : p.lds_pad;
+  // decode step 6.25 -> 5.87 ms with two lanes.
   // prompt prefill (rows_per_seq consecutive rows per sequence): four rows of a sequence share one pass over its xa
-  // (CCX_XS_PREFILL_ROWS=1: one row per block, as the decode steps)
-  static const int pf_rows = [] { const char* e = getenv("CCX_XS_PREFILL_ROWS"); return e ? atoi(e) : 4; }();
-  CCX_REQUIRE(ctx, pf_rows == 1 || pf_rows == 4, "xs cross attention: CCX_XS_PREFILL_ROWS=%d unsupported (1 or 4 rows per block)", pf_rows);
   // rows of one sequence per block need the row -> sequence map (without it the kernel would take its row index as the sequence
   // and read xa beyond the encoded windows)
   CCX_REQUIRE(ctx, p.rows_per_seq <= 1 || p.row_seq != nullptr, "xs cross attention: rows_per_seq = %d needs row_seq", p.rows_per_seq);
-  const bool multi = p.rows_per_seq > 1 && pf_rows == 4;
+  const bool multi = p.rows_per_seq > 1;
   static ccx_lds_optin optin1, optin4;       // per device, race-free (ccx_common.h)
   CCX_HIP(ctx, optin1.ensure(ctx->device, (const void*)dec_xs_stream_kernel<D, 1>));
   CCX_HIP(ctx, optin4.ensure(ctx->device, (const void*)dec_xs_stream_kernel<D, 4>));
-  CCX_REQUIRE(ctx, lds_pad >= 0 && G::LDS + lds_pad <= 160 * 1024, "xs cross attention: LDS claim %d too large", lds_pad);
+  CCX_REQUIRE(ctx, p.lds_pad >= 0 && G::LDS + p.lds_pad <= 160 * 1024, "xs cross attention: LDS claim %d too large", p.lds_pad);
   CCX_REQUIRE(ctx, p.rows_per_seq <= 1 || p.rows % p.rows_per_seq == 0, "xs cross attention: %d rows are not a multiple of %d rows per sequence", p.rows, p.rows_per_seq);
   const dim3 small_grid(p.H, ccx_cdiv(p.rows, 16));
   const double wbytes = (double)p.H * 64 * D * 2;
@@ -574,7 +569,7 @@ int launch_xs(ccx_ctx* ctx, const XsParams& p, hipStream_t stream) {
       constexpr int lds4 = XsGeom<D, 4>::LDS;
       hipLaunchKernelGGL((dec_xs_stream_kernel<D, 4>), dim3(units * XS_SPLIT), dim3(256), lds4, stream, p);
     } else {
-      hipLaunchKernelGGL((dec_xs_stream_kernel<D, 1>), dim3(p.rows * XS_SPLIT), dim3(256), G::LDS + lds_pad, stream, p);
+      hipLaunchKernelGGL((dec_xs_stream_kernel<D, 1>), dim3(p.rows * XS_SPLIT), dim3(256), G::LDS + p.lds_pad, stream, p);
     }
   }
   CCX_CHECK_LAUNCH(ctx);

@@ -22,9 +22,6 @@
 #include <string>
 #include "gemm_bf16.h"
 
-#ifndef CCX_GEMM_SETPRIO
-#define CCX_GEMM_SETPRIO 1
-#endif
 // diagnostic builds of the phased kernel (tools/README.md): -DCCX_ABL_NO_MFMA=1 / _NO_DMA (in-loop prefetches) / _NO_EPI /
 // _STORE_LOCAL (every tile stores to the first 256 output rows: the epilogue's instructions without its HBM traffic)
 #ifndef CCX_ABL_NO_MFMA
@@ -35,18 +32,6 @@
 #endif
 #ifndef CCX_ABL_NO_EPI
 #define CCX_ABL_NO_EPI 0
-#endif
-// Experiment switches of the tile epilogue (compile time; tools/README.md): non-temporal stores of the output tile (CCX_EPI_NT_STORE) and
-// non-temporal loads of the residual rows (CCX_EPI_NT_LOAD) -- every output / residual byte of these launches is touched once.
-#ifndef CCX_EPI_NT_STORE
-#define CCX_EPI_NT_STORE 0
-#endif
-#ifndef CCX_EPI_NT_LOAD
-#define CCX_EPI_NT_LOAD 0
-#endif
-// fp32-residual epilogue of FULL 256 x 256 tiles through the LDS (see resid_via_lds below); 0 = the register-staged groups
-#ifndef CCX_EPI_RESID_LDS
-#define CCX_EPI_RESID_LDS 1
 #endif
 #ifndef CCX_ABL_STORE_LOCAL
 #define CCX_ABL_STORE_LOCAL 0
@@ -72,19 +57,10 @@ template <int CM> __device__ __forceinline__ int keyW(int r) {
 template <int CM> __device__ __forceinline__ int col4(int j, int h) {
   return CM == 1 ? 16 * j + 4 * h : 32 * (j >> 1) + 8 * h + 4 * (j & 1);
 }
-typedef unsigned int ccx_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void epi_store16(void* dst, uint4 v) {
-  if (CCX_EPI_NT_STORE) __builtin_nontemporal_store((ccx_u32x4){v.x, v.y, v.z, v.w}, (ccx_u32x4*)dst);
-  else *(uint4*)dst = v;
-}
-__device__ __forceinline__ void epi_store16f(void* dst, float4 v) {
-  if (CCX_EPI_NT_STORE) __builtin_nontemporal_store((f32x4){v.x, v.y, v.z, v.w}, (f32x4*)dst);
-  else *(float4*)dst = v;
-}
-__device__ __forceinline__ float4 epi_load16f(const float* src) {
-  if (CCX_EPI_NT_LOAD) { const f32x4 t = __builtin_nontemporal_load((const f32x4*)src); return make_float4(t[0], t[1], t[2], t[3]); }
-  return *(const float4*)src;
-}
+// (non-temporal stores of the output tile and loads of the residual rows were measured slower: profiles/r03_gemm_nt_epilogue_experiment.txt)
+__device__ __forceinline__ void epi_store16(void* dst, uint4 v) { *(uint4*)dst = v; }
+__device__ __forceinline__ void epi_store16f(void* dst, float4 v) { *(float4*)dst = v; }
+__device__ __forceinline__ float4 epi_load16f(const float* src) { return *(const float4*)src; }
 
 constexpr int colmap_of(int epi) { return (epi == EPI_F32 || epi == EPI_F32_RESID || epi == EPI_F32_GELU_POS) ? 1 : 2; }
 
@@ -445,7 +421,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
     return;
   }
   const bool full = p.rpb_in <= 0 && m0 + WM * MT * 16 <= p.M && n0 + WN * 64 <= p.N;
-  if constexpr (CCX_EPI_RESID_LDS && EPI == EPI_F32_RESID && WM * WN == 8 && MT == 8) {
+  if constexpr (EPI == EPI_F32_RESID && WM * WN == 8 && MT == 8) {
     // fp32 residual of a FULL 256 x 256 tile THROUGH THE LDS (round 3).  The register-staged path above keeps two row tiles of
     // residual (8 float4) in flight per lane = 64 KB per CU and needs four dependent HBM round trips per tile, each ~2.5 us under
     // load: 512 KB of read-modify-write at ~22 GB/s per CU, latency-bound (Little), not bandwidth-bound.  The operand image is dead
@@ -632,7 +608,7 @@ __device__ __forceinline__ void gemm_mainloop_phased(const GemmParams& p, char* 
   __builtin_amdgcn_s_barrier();                                                                             \
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                        \
   __builtin_amdgcn_sched_barrier(0);                                                                        \
-  if (CCX_GEMM_SETPRIO) __builtin_amdgcn_s_setprio(1);                                                      \
+  __builtin_amdgcn_s_setprio(1);                                                                            \
   _Pragma("unroll") for (int ks = 0; ks < 2; ks++)                                                          \
   _Pragma("unroll") for (int m = 0; m < 4; m++)                                                             \
   _Pragma("unroll") for (int jj = 0; jj < 2; jj++) {                                                        \
@@ -640,7 +616,7 @@ __device__ __forceinline__ void gemm_mainloop_phased(const GemmParams& p, char* 
     else if (SWAP) acc[MT0 + m][J0 + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FB[jj][ks], fa[m][ks], acc[MT0 + m][J0 + jj], 0, 0, 0); \
     else      acc[MT0 + m][J0 + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[m][ks], FB[jj][ks], acc[MT0 + m][J0 + jj], 0, 0, 0); \
   }                                                                                                         \
-  if (CCX_GEMM_SETPRIO) __builtin_amdgcn_s_setprio(0);                                                      \
+  __builtin_amdgcn_s_setprio(0);                                                                            \
   __builtin_amdgcn_sched_barrier(0);                                                                        \
   __builtin_amdgcn_s_barrier();
 
@@ -760,20 +736,15 @@ static int launch_phased(ccx_ctx* ctx, const GemmParams& p, hipStream_t stream) 
 template <int EPI>
 static int launch_epi(ccx_ctx* ctx, const GemmParams& p, hipStream_t stream) {
   // 256x256 tiles once there are enough of them to fill the 256 CUs and N is wide enough not to waste half a tile;
-  // the 128x128 kernel (2 blocks per CU) otherwise.  CCX_GEMM_TILE=128|256 forces one for A/B measurements.
-  static const int forced = [] { const char* e = getenv("CCX_GEMM_TILE"); return e ? atoi(e) : 0; }();
+  // the 128x128 kernel (2 blocks per CU) otherwise.  The 256x256 tiles run the phased main loop (the two-stage one was measured
+  // slower: profiles/r02_gemm_phased_experiments.txt).
   const long big_tiles = (long)ccx_cdiv(p.M, 256) * ccx_cdiv(p.N, 256);
   bool fits = p.N >= 256 && (p.N % 256 == 0 || p.N >= 1024);
   if (EPI == EPI_HEADS) fits = fits && p.N % 256 == 0 && p.d_model % 256 == 0;
-  const bool big = fits && (forced == 256 || (forced != 128 && big_tiles >= 224));
-  if (big) {
-    static const bool phased = [] { const char* e = getenv("CCX_GEMM_PHASED"); return e ? atoi(e) != 0 : true; }();
-    if (phased) return launch_phased<EPI>(ctx, p, stream);
-    return launch_epi_geo<EPI, 2, 4, 8>(ctx, p, stream);
-  }
+  if (fits && big_tiles >= 224) return launch_phased<EPI>(ctx, p, stream);
   // narrow layers (ResNet 32/64 channels, SincNet 60): 256 x 64 tiles, 4 waves of 64 rows (80 KB LDS, 2 blocks per CU).
   // Measured over the ResNet-34 convolutions: 128 x 64 / 2 waves 59.6 ms per step, 128 x 64 / 4 waves 51.6, 256 x 64 49.9.
-  if (EPI != EPI_HEADS && p.N <= 64 && forced == 0) return launch_epi_geo<EPI, 4, 1, 4>(ctx, p, stream);
+  if (EPI != EPI_HEADS && p.N <= 64) return launch_epi_geo<EPI, 4, 1, 4>(ctx, p, stream);
   return launch_epi_geo<EPI, 2, 2, 4>(ctx, p, stream);
 }
 

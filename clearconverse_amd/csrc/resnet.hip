@@ -478,8 +478,7 @@ void stage_dims(int T, StageDims (&d)[RN_STAGES]) {
 // one convolution as a GEMM over a strided view of `in` (stage si) writing the padded layout of `out` (stage so)
 int run_conv(ccx_resnet* r, const Conv& cv, int epi, const bf16_t* in, const StageDims& di, bf16_t* out, const StageDims& dn,
              const bf16_t* resid, int n_chunks, hipStream_t st) {
-  static const bool direct = getenv("CCX_RESNET_DIRECT") == nullptr || atoi(getenv("CCX_RESNET_DIRECT")) != 0;
-  if (direct && cv.cin == 32 && cv.cout == 32 && cv.k == 3 && cv.stride == 1 && di.H % 4 == 0 && (epi == EPI_BF16_RELU || epi == EPI_BF16_ADD_RELU)) {
+  if (cv.cin == 32 && cv.cout == 32 && cv.k == 3 && cv.stride == 1 && di.H % 4 == 0 && (epi == EPI_BF16_RELU || epi == EPI_BF16_ADD_RELU)) {
     const dim3 grid(1, di.H / 4, n_chunks);
     {
       ccx_prof_scope ps(r->ctx, st, "conv3x3_c32_kernel", 2.0 * 9 * 32 * 32 * (double)n_chunks * di.H * di.W,
@@ -641,15 +640,7 @@ int ccx_resnet_embed(ccx_resnet* r, const float* wav_dev, int64_t stride, int n_
     n_masks = n_chunks;
     CCX_REQUIRE(ctx, n_masks <= r->max_masks, "resnet_embed: %d chunks exceed the mask capacity %d", n_masks, r->max_masks);
   }
-  static const bool full_clear = getenv("CCX_RESNET_FULL_CLEAR") != nullptr && atoi(getenv("CCX_RESNET_FULL_CLEAR")) != 0;   // A/B: round 2's behaviour
-  if (T != r->last_T) {                                         // the halo cells move with the frame count
-    r->last_T = T; r->halo_chunks = 0;
-    if (full_clear) {
-      for (int s = 0; s < RN_STAGES; s++)
-        for (int k = 0; k < 3; k++) CCX_HIP(ctx, hipMemsetAsync(r->act[s][k], 0, r->act_elems[s] * 2, st));
-      r->halo_chunks = r->max_chunks;
-    }
-  }
+  if (T != r->last_T) { r->last_T = T; r->halo_chunks = 0; }   // the halo cells move with the frame count
   if (n_chunks > r->halo_chunks) {
     for (int s = 0; s < RN_STAGES; s++)
       hipLaunchKernelGGL(halo_zero_kernel, dim3(d[s].H + 2, n_chunks - r->halo_chunks, 3), dim3(256), 0, st, r->act[s][0], r->act[s][1],

@@ -59,13 +59,12 @@ struct EncLayer {
 struct DecLayer {
   float *ln1_g, *ln1_b, *lnc_g, *lnc_b, *ln2_g, *ln2_b;
   bf16_t *Wqkv, *Wo, *Wcq, *Wckv, *Wco, *W1, *W2;
-  bf16_t* W1_plain = nullptr;   // fc1 once more in plain row-major [F][D] for the tiled GEMM (lanes of >= 256 rows, prefill)
   bf16_t* WckT = nullptr;       // cross_attn.key.weight re-laid per head [H][D][64] for the expanded query (cross_x.hip)
   bf16_t* Wcq_plain = nullptr;  // cross_attn.query.weight in plain row-major [D][D] (dec_xq_fused_kernel)
-  // LayerNorm-free chain (decoder.h, ACT_BF16_LN): gamma folded into the consumer weights, s_n = sum_k (gamma o W)_nk over the bf16
-  // values the MFMAs see, c_n = sum_k beta_k W_nk + b_n.  Wqkv_g / W1_g fragment-packed, Wcq_g plain row-major
-  bf16_t *Wqkv_g = nullptr, *Wcq_g = nullptr, *W1_g = nullptr;
-  float *sqkv = nullptr, *cqkv = nullptr, *scq = nullptr, *ccq = nullptr, *s1 = nullptr, *c1 = nullptr;
+  // LayerNorm-free cross-attention query (dec_xq_lnfree_kernel): gamma folded into the weights, Wcq_g = gamma o Wcq (plain
+  // row-major), s_n = sum_k (gamma o Wcq)_nk over the bf16 values the MFMAs see, c_n = sum_k beta_k Wcq_nk + bcq_n
+  bf16_t* Wcq_g = nullptr;
+  float *scq = nullptr, *ccq = nullptr;
   float *bqkv, *bo, *bcq, *bckv, *bco, *b1, *b2;
   bf16_t *crossK, *crossV, *selfK, *selfV;
 };
@@ -102,7 +101,6 @@ struct ccx_whisper {
   std::vector<EncLayer> enc;
   // decoder weights
   float *tok_emb_f32 = nullptr, *dec_pos = nullptr, *lnd_g = nullptr, *lnd_b = nullptr;
-  bf16_t* tok_emb_bf16 = nullptr;   // fragment-packed (dec_linear)
   bf16_t* tok_emb_rm = nullptr;     // row-major [n_vocab][D] (logits through the tiled GEMM)
   std::vector<DecLayer> dec;
   // rules
@@ -139,7 +137,8 @@ struct ccx_whisper {
   // modest (3-4 % at 192 sequences): the small kernels slow down 3-5x while HBM is saturated by another lane.
   static constexpr int kMaxLanes = 4;
   int cross_lds_pad = 0;                     // see ccx_whisper_decode: occupancy cap of the cross-attention blocks while lanes overlap
-  int cross_stream = 0;                      // 1: lean-streaming cross attention (dec_cross_stream_kernel) for batches > 16
+  int cross_stream = 0;                      // 1 (decodes): lean-streaming cross attention (dec_cross_stream_kernel) for batches > 16;
+                                             // 0 (ccx_whisper_decoder_logits): split-KV partials + dec_combine_kernel
   int fuse_cross_q = 1;                      // 1: batches <= 16 compute the cross-attention query inside the attention blocks
   // Cross attention against the encoder output (cross_x.hip) for decodes of more than 80 sequences: no per-layer K/V caches beyond those
   // (42 GB at 768 sequences), half the bytes per step.  xs_on: the instance was built for it (widths cross_x.hip instantiates,
@@ -150,12 +149,10 @@ struct ccx_whisper {
   int last_cross_path = -1;                  // ccx_whisper_last_cross_path: 0 kv16, 1 kv_stream, 2 xa_stream
   int kv_cap = 0, kv_ready = 0;
   bf16_t *xq = nullptr, *pf_xq = nullptr;    // expanded queries [rows][H][D] (step rows, prefill rows)
-  // LayerNorm-free chain: bf16 copy of the resolved residual rows and their (sum, sum of squares) per 16-column tile
+  // LayerNorm-free query of the X-stream path: bf16 copy of the resolved residual rows and their (sum, sum of squares) per 16-column tile
   bf16_t *dxb = nullptr, *pf_xb = nullptr;
   float2 *dst2 = nullptr, *pf_st2 = nullptr;
-  bool lnfree = false;                       // CCX_DEC_LNFREE, read per decode
-  bool lnfree_built = false;                 // the folded weights exist (CCX_DEC_LNFREE was set when the instance was finalized)
-  int lnfree_mode = 0;                       // 1: every producer resolves in place (12-wave second MLP linear); 2: that one keeps split-K slabs
+  bool lnfree = false;                       // the LayerNorm-free query; set per decode (CCX_DEC_LNFREE=0: round 3's query, see dec_step)
   float *xs_po = nullptr, *xs_pml = nullptr, *pf_xs_po = nullptr, *pf_xs_pml = nullptr;   // key-half partials (cross_x.h)
   static constexpr int kLanePool = 8;
   hipStream_t lane_pool[kLanePool] = {};     // candidates; HIP streams share a few hardware queues and two streams on one
@@ -514,7 +511,6 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     NEED(lg, "decoder.ln.weight", D);
     NEED(lb, "decoder.ln.bias", D);
     TRY(up_f32(w, &w->tok_emb_f32, te->data.data(), te->data.size()));
-    TRY(up_bf16_packed(w, &w->tok_emb_bf16, te->data.data(), d.n_vocab, D, 64));
     TRY(up_bf16(w, &w->tok_emb_rm, te->data.data(), (size_t)d.n_vocab * D));
     TRY(up_f32(w, &w->dec_pos, pe->data.data(), pe->data.size()));
     TRY(up_f32(w, &w->lnd_g, lg->data.data(), D));
@@ -553,7 +549,6 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     TRY(up_bf16(w, &L.Wckv, wckv.data(), wckv.size())); TRY(up_f32(w, &L.bckv, bckv.data(), bckv.size()));
     TRY(up_bf16_packed(w, &L.Wco, cow->data.data(), D, D, 16)); TRY(up_f32(w, &L.bco, cob->data.data(), D));
     TRY(up_bf16_packed(w, &L.W1, m0w->data.data(), F, D, 16)); TRY(up_f32(w, &L.b1, m0b->data.data(), F));
-    TRY(up_bf16(w, &L.W1_plain, m0w->data.data(), m0w->data.size()));
     TRY(up_bf16_packed(w, &L.W2, m2w->data.data(), D, F, 16)); TRY(up_f32(w, &L.b2, m2b->data.data(), D));
     TRY(up_f32(w, &L.ln1_g, l1g->data.data(), D)); TRY(up_f32(w, &L.ln1_b, l1b->data.data(), D));
     TRY(up_f32(w, &L.lnc_g, lcg->data.data(), D)); TRY(up_f32(w, &L.lnc_b, lcb->data.data(), D));
@@ -565,39 +560,23 @@ int ccx_whisper_finalize(ccx_whisper* w) {
           for (int dd = 0; dd < 64; dd++) wkt[((size_t)hh * D + f) * 64 + dd] = ckw->data[(size_t)(hh * 64 + dd) * D + f];
       TRY(up_bf16(w, &L.WckT, wkt.data(), wkt.size()));
       TRY(up_bf16(w, &L.Wcq_plain, cqw->data.data(), cqw->data.size()));
-      // LayerNorm folded into the three consumers of a normalised row (q|k|v, the cross-attention query, the first MLP linear):
-      // only built when the experiment is asked for at creation time (CCX_DEC_LNFREE set; 113 MB per small.en instance)
-      w->lnfree_built = getenv("CCX_DEC_LNFREE") != nullptr;
-      {
-      auto fold = [&](const std::vector<float>& W, const std::vector<float>& bias, const std::vector<float>& g, const std::vector<float>& bt,
-                      int N, std::vector<float>& Wg, std::vector<float>& sv, std::vector<float>& cv) {
-        Wg.resize((size_t)N * D); sv.resize(N); cv.resize(N);
-        for (int n = 0; n < N; n++) {
-          double ss = 0.0, cc = 0.0;
-          for (int k = 0; k < D; k++) {
-            const float v = g[k] * W[(size_t)n * D + k];
-            Wg[(size_t)n * D + k] = v;
-            const uint32_t bits = (uint32_t)host_f32_to_bf16(v) << 16;
-            float r;
-            memcpy(&r, &bits, 4);
-            ss += (double)r;                                   // what the MFMA sums: the bf16-rounded products
-            cc += (double)bt[k] * (double)W[(size_t)n * D + k];
-          }
-          sv[n] = (float)ss;
-          cv[n] = (float)(cc + (double)bias[n]);
+      // cross_attn_ln folded into the cross-attention query (the LayerNorm-free query of the X-stream path)
+      std::vector<float> Wg((size_t)D * D), sv(D), cv(D);
+      for (int n = 0; n < D; n++) {
+        double ss = 0.0, cc = 0.0;
+        for (int k = 0; k < D; k++) {
+          const float v = lcg->data[k] * cqw->data[(size_t)n * D + k];
+          Wg[(size_t)n * D + k] = v;
+          const uint32_t bits = (uint32_t)host_f32_to_bf16(v) << 16;
+          float r;
+          memcpy(&r, &bits, 4);
+          ss += (double)r;                                   // what the MFMA sums: the bf16-rounded products
+          cc += (double)lcb->data[k] * (double)cqw->data[(size_t)n * D + k];
         }
-      };
-      std::vector<float> Wg, sv, cv;
-      // the cross-attention query's fold is part of the DEFAULT chain (mode 3); the other two only exist for the experiments
-      fold(cqw->data, cqb->data, lcg->data, lcb->data, D, Wg, sv, cv);
+        sv[n] = (float)ss;
+        cv[n] = (float)(cc + (double)cqb->data[n]);
+      }
       TRY(up_bf16(w, &L.Wcq_g, Wg.data(), Wg.size())); TRY(up_f32(w, &L.scq, sv.data(), sv.size())); TRY(up_f32(w, &L.ccq, cv.data(), cv.size()));
-      if (w->lnfree_built) {
-        fold(wqkv, bqkv, l1g->data, l1b->data, 3 * D, Wg, sv, cv);
-        TRY(up_bf16_packed(w, &L.Wqkv_g, Wg.data(), 3 * D, D, 16)); TRY(up_f32(w, &L.sqkv, sv.data(), sv.size())); TRY(up_f32(w, &L.cqkv, cv.data(), cv.size()));
-        fold(m0w->data, m0b->data, l2g->data, l2b->data, F, Wg, sv, cv);
-        TRY(up_bf16_packed(w, &L.W1_g, Wg.data(), F, D, 16)); TRY(up_f32(w, &L.s1, sv.data(), sv.size())); TRY(up_f32(w, &L.c1, cv.data(), cv.size()));
-      }
-      }
     }
     const size_t ck = (size_t)w->kv_cap * H * w->Spad * 64, sk = (size_t)B * H * Tc * 64;
     TRY(dev_alloc(w, &L.crossK, ck, true)); TRY(dev_alloc(w, &L.crossV, ck, true));
@@ -671,10 +650,9 @@ int ccx_whisper_finalize(ccx_whisper* w) {
   TRY(dev_alloc(w, &w->prompt, (size_t)B * w->max_prompt_cap, true));
   TRY(dev_alloc(w, &w->gen, (size_t)B * w->sample_cap, true));
   // decode streams get the highest priority: when other work shares the GPU (the front end of the next batch on another
-  // stream) the short, latency-bound chain kernels should get the next free wave slot.  CCX_LANE_PRIORITY=0 disables.
+  // stream) the short, latency-bound chain kernels should get the next free wave slot.
   int prio_least = 0, prio_greatest = 0;
   CCX_HIP(w->ctx, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-  { const char* e = getenv("CCX_LANE_PRIORITY"); if (e && atoi(e) == 0) prio_greatest = 0; }
   CCX_HIP(w->ctx, hipStreamCreateWithPriority(&w->own_stream, hipStreamNonBlocking, prio_greatest));
   CCX_HIP(w->ctx, hipEventCreateWithFlags(&w->own_event, hipEventDisableTiming));
   for (int i = 0; i < ccx_whisper::kMaxLanes; i++) {
@@ -921,29 +899,16 @@ const std::vector<hipStream_t>& lane_streams_for(ccx_whisper* w, hipStream_t s0,
   return set;
 }
 
-int cross_split(int B, int H, bool capped, bool lean = false) {
-  if (lean && B > 16) {
-    // lean streaming: one block owns the whole key range of a (sequence, head) -- 12 rolling 32-key pieces per wave, FINAL output,
-    // no partials and no combine launch; CCX_CROSS_SPLIT overrides
-    const char* e = getenv("CCX_CROSS_SPLIT");
-    const int forced = e ? atoi(e) : 0;
-    return (forced >= 1 && forced <= ccx_whisper::kCrossSplitMax) ? forced : 1;
-  }
-  // enough blocks to fill the chip, and <= 256 keys per block (one 64-key chunk per wave)
+// key splits of the cross attention on the K/V caches
+int cross_split(int B, int H, bool lean) {
+  // lean streaming: one block owns the whole key range of a (sequence, head) -- 12 rolling 32-key pieces per wave, FINAL output,
+  // no partials and no combine launch
+  if (lean && B > 16) return 1;
+  // enough blocks to fill the chip, and <= 256 keys per block (one 64-key chunk per wave).  Measured at 64 sequences per lane:
+  // 6 splits 54.5 us per launch, 8 splits 56.8 us (a wave then owns 47 of a chunk's 64 keys).
   int ns = ccx_cdiv(512, B * H);
   if (ns < 6) ns = 6;
   if (ns > ccx_whisper::kCrossSplitMax) ns = ccx_whisper::kCrossSplitMax;
-  if (B > 16) {
-    // lanes with the two-blocks-per-CU cap: 3 splits, i.e. two 64-key chunks per wave and half as many, longer-lived blocks,
-    // which suits the capped kernel better (pipeline step, ms: 2 splits 900, 3 891,
-    // 4 893, 6 912; per 64-sequence launch 49.9 us against 52.0 at 6 splits)
-    if (capped) ns = 3;
-    // many sequences: CCX_CROSS_SPLIT=n overrides (1 = whole key range per block, no partials / combine).  Measured at
-    // 64 sequences per lane: 6 splits 54.5 us per launch, 8 splits 56.8 us (a wave then owns 47 of a chunk's 64 keys).
-    const char* e = getenv("CCX_CROSS_SPLIT");
-    const int forced = e ? atoi(e) : 0;
-    if (forced >= 1 && forced <= ccx_whisper::kCrossSplitMax) ns = forced;
-  }
   return ns;
 }
 
@@ -959,20 +924,11 @@ int dec_head(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
   int* pos = w->pos + b0;
   {
     // logits against the tied embedding through the tiled GEMM (one summation order for every batch size; 284 -> 282 ms
-    // for 192 sequences x 65 steps, no change at 8 sequences); CCX_LOGITS_GEMM=0 selects the skinny kernel
-    static const int gemm_logits = [] { const char* e = getenv("CCX_LOGITS_GEMM"); return e ? atoi(e) : 1; }();
-    if (gemm_logits && D % 64 == 0) {
-      GemmParams gp;
-      memset(&gp, 0, sizeof(gp));
-      gp.A = dxn; gp.lda = D; gp.W = w->tok_emb_rm; gp.ldw = D; gp.M = B; gp.N = d.n_vocab; gp.K = D; gp.out = logits; gp.ldo = ld;
-      TRY(ccx_launch_gemm(ctx, EPI_F32, gp, stream));
-    } else {
-      DecLinearParams lp;
-      memset(&lp, 0, sizeof(lp));
-      lp.M = B; lp.N = d.n_vocab; lp.K = D; lp.W = w->tok_emb_bf16; lp.ldw = D; lp.bias = nullptr;
-      lp.act = dxn; lp.lda = D; lp.out = logits; lp.ldo = ld;
-      TRY(ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_F32, lp, stream));
-    }
+    // for 192 sequences x 65 steps against the skinny kernel, no change at 8 sequences)
+    GemmParams gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.A = dxn; gp.lda = D; gp.W = w->tok_emb_rm; gp.ldw = D; gp.M = B; gp.N = d.n_vocab; gp.K = D; gp.out = logits; gp.ldo = ld;
+    TRY(ccx_launch_gemm(ctx, EPI_F32, gp, stream));
   }
   if (select) {
     DecSelectParams sp;
@@ -1003,7 +959,7 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
   const ccx_whisper_dims& d = w->d;
   const int D = d.n_text_state, F = 4 * D, H = d.n_text_head, Tc = d.n_text_ctx;
   const float scale_log2e = 0.125f * 1.4426950408889634f;
-  const int ns = cross_split(B, H, w->cross_lds_pad > 0, w->cross_stream != 0);
+  const int ns = cross_split(B, H, w->cross_stream != 0);
   long pstride = (long)B * D;
   const long ro = b0;
   const bool pre = prefill_rows > 0;
@@ -1061,112 +1017,27 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     pend_n = ccx_dec_linear_ksplit(K, DEPI_PARTIAL);
     return CCX_OK;
   };
-  // diagnostic only (results are garbage): CCX_ABLATE=cross drops the cross attention launches, =chain everything else of a layer
-  static const int ablate = [] { const char* e = getenv("CCX_ABLATE"); return !e ? 0 : (!strcmp(e, "cross") ? 1 : (!strcmp(e, "chain") ? 2 : 0)); }();
-  // ---- the LayerNorm-free chain of the X-stream path (CCX_DEC_LNFREE=1): 9 launches per layer and no stand-alone resolve / LayerNorm.
-  // The PRODUCERS of the residual stream (self-attention out, cross-attention out, second MLP linear: DEPI_RESOLVE) add their product
-  // to the stream in place -- no split-K slabs, K = 3072 goes to 12 waves per block -- and leave a bf16 copy of the new rows plus
-  // (sum, sum of squares) per 16-column tile; the CONSUMERS of a normalised row (q|k|v, the cross-attention query inside the
-  // expansion, the first MLP linear: ACT_BF16_LN) read the bf16 rows as they are and apply the LayerNorm algebraically in their
-  // epilogue (gamma folded into the weights at load time).  One set of kernels for every row count, statistics per tile in a fixed
-  // order: a row's numbers do not depend on its lane.  Layer 0 normalises the step's embedding the old way (nothing produced it).
-  // (CCX_DEC_LNFREE=3: only the self-attention output projection resolves in place and only the cross-attention query uses the algebra --
-  //  the default chain without the twelve-fold resolve + LayerNorm inside dec_xq_fused_kernel; handled in the default loop below)
-  //  CCX_DEC_LNFREE=4: only the cross-attention output projection resolves in place and only the first MLP linear uses the algebra; 5: both)
-  const bool lnf_on = w->xs_active && ablate == 0;
-  const bool lnfree3 = lnf_on && (w->lnfree_mode == 3 || w->lnfree_mode == 5);
-  const bool lnfree4 = lnf_on && (w->lnfree_mode == 4 || w->lnfree_mode == 5);
-  if (w->lnfree && w->lnfree_mode < 3 && w->xs_active && ablate == 0) {
-    bf16_t* xb = pre ? w->pf_xb : w->dxb + ro * D;
-    float2* st2 = pre ? w->pf_st2 : w->dst2 + ro * (D / 16);
-    auto consumer = [&](int epi, const bf16_t* Wg, const float* sv, const float* cv, int N, void* out, long ldo, DecLinearParams* extra) -> int {
-      DecLinearParams lp;
-      if (extra) lp = *extra; else memset(&lp, 0, sizeof(lp));
-      lp.M = B; lp.N = N; lp.K = D; lp.W = Wg; lp.ldw = D; lp.bias = cv; lp.ln_s = sv; lp.ln_stats = st2; lp.eps = 1e-5f;
-      lp.act = xb; lp.lda = D; lp.out = out; lp.ldo = ldo;
-      return ccx_launch_dec_linear(ctx, ACT_BF16_LN, epi, lp, stream);
-    };
-    auto producer = [&](const bf16_t* W, const float* bias, int K, const bf16_t* a) -> int {
-      DecLinearParams lp;
-      memset(&lp, 0, sizeof(lp));
-      lp.M = B; lp.N = D; lp.K = K; lp.W = W; lp.ldw = K; lp.bias = bias; lp.act = a; lp.lda = K;
-      lp.xres = cur; lp.xb = xb; lp.st_out = st2;
-      return ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_RESOLVE, lp, stream);
-    };
-    for (int l = 0; l < d.n_text_layer; l++) {
-      const DecLayer& L = w->dec[l];
-      DecLinearParams ex;
-      memset(&ex, 0, sizeof(ex));
-      ex.cache_k = L.selfK + self_off; ex.cache_v = L.selfV + self_off; ex.cache_T = Tc; ex.pos = pos; ex.row_seq = row_seq;
-      if (l == 0) TRY(ln_linear(DEPI_SELF_QKV, L.Wqkv, L.bqkv, 3 * D, L.ln1_g, L.ln1_b, dq, D, &ex));
-      else {
-        // (CCX_DEC_LNFREE=2: the second MLP linear kept its split-K slabs -- fold them in here, one small launch)
-        if (pend_n > 0) { TRY(ccx_launch_dec_resolve_stats(ctx, cur, pend, pend_n, pstride, xb, st2, B, D, stream)); pend_n = 0; }
-        TRY(consumer(DEPI_SELF_QKV, L.Wqkv_g, L.sqkv, L.cqkv, 3 * D, dq, D, &ex));
-      }
-      stamp(16, 2);
-      DecAttnParams ap;
-      memset(&ap, 0, sizeof(ap));
-      ap.q = dq; ap.k = L.selfK + self_off; ap.v = L.selfV + self_off; ap.H = H; ap.kv_T = Tc; ap.pos = pos; ap.scale_log2e = scale_log2e;
-      ap.out_bf16 = dattn; ap.row_seq = row_seq;
-      TRY(ccx_launch_dec_attention(ctx, ap, B, 1, true, stream));
-      stamp(17, 2);
-      TRY(producer(L.Wo, L.bo, D, dattn));
-      stamp(18, 2);
-      stamp(1, 1);
-      if (l == 0 && stagger) CCX_HIP(ctx, hipEventRecord(stagger, stream));
-      {
-        XsParams xp;
-        memset(&xp, 0, sizeof(xp));
-        xp.xb = xb; xp.ln_stats = st2; xp.ln_s = L.scq; xp.Wq = L.Wcq_g; xp.bq = L.ccq; xp.eps = 1e-5f;
-        xp.WkT = L.WckT; xp.xq = pre ? w->pf_xq : w->xq + ro * H * D;
-        xp.part_o = pre ? w->pf_xs_po : w->xs_po + ccx_xs_part_o_elems(ro, H, D);
-        xp.part_ml = pre ? w->pf_xs_pml : w->xs_pml + ccx_xs_part_ml_elems(ro);
-        xp.X = pre ? w->xa : w->xa + ro * (long)d.n_audio_ctx * D; xp.x_seq_stride = (long)d.n_audio_ctx * D; xp.row_seq = row_seq;
-        xp.Wv = L.Wckv + (long)D * D; xp.bv = L.bckv + D; xp.out = dattn;
-        xp.rows = B; xp.H = H; xp.S = d.n_audio_ctx; xp.D = D; xp.scale_log2e = scale_log2e;
-        xp.lds_pad = (w->cross_lds_pad > 0 && !pre) ? 65536 : 0;
-        xp.rows_per_seq = pre ? prefill_rows : 0;
-        TRY(ccx_launch_xs_cross_attention(ctx, xp, stream));
-      }
-      stamp(2, 1);
-      TRY(producer(L.Wco, L.bco, D, dattn));
-      stamp(19, 2);
-      TRY(consumer(DEPI_BF16_GELU, L.W1_g, L.s1, L.c1, F, dffn, F, nullptr));
-      stamp(20, 2);
-      if (w->lnfree_mode == 2 && F > 1024) TRY(partial_linear(ACT_BF16, L.W2, L.b2, F, dffn));      // split-K slabs, resolved by the next consumer
-      else TRY(producer(L.W2, L.b2, F, dffn));
-      stamp(21, 2);
-    }
-    TRY(ccx_launch_dec_resolve_ln(ctx, cur, pend, pend_n, pstride, w->lnd_g, w->lnd_b, dxn, nullptr, B, D, 1e-5f, stream));
-    if (pre) return CCX_OK;
-    TRY(dec_head(w, b0, B, logits, ld, select, sample_len, max_prompt, n_done, stream));
-    stamp(3, 1);
-    return CCX_OK;
-  }
+  // The cross-attention form is decided once for the step:
+  //  * X-stream (xs_active: decodes of more than 80 sequences): one pass over the encoder output serves all heads (cross_x.hip).
+  //    Its query is LayerNorm-free by default: the self-attention output projection resolves the residual in place and leaves a bf16
+  //    copy of the rows plus their statistics (DEPI_RESOLVE), and the query applies its LayerNorm algebraically (gamma folded into
+  //    Wcq_g) instead of a twelve-fold resolve + LayerNorm inside the expansion kernel: -1.0 ... -1.2 % per decode step.
+  //    CCX_DEC_LNFREE=0: round 3's query -- resolve + LayerNorm inside the expansion kernel (CCX_XS_FUSE_Q=0: as a launch of its own).
+  //  * <= 16 rows, d_model 768 (the reference's one-window-per-call pattern): the query projection LN(x) Wcq^T runs INSIDE the
+  //    cross-attention blocks (ccx_launch_dec_cross_fused_q: one launch fewer per layer on a chain that is latency-bound launch by
+  //    launch; q is bit-identical to the two-launch path).  CCX_FUSE_CROSS_Q=0 restores the two launches.
+  //  * prefill: all prompt rows of a sequence share its K/V.
+  //  * otherwise the K/V caches: > 16 rows lean streaming (split-KV partials + combine in ccx_whisper_decoder_logits), <= 16 rows
+  //    split-KV partials combined by the out projection.
+  const bool lnfree = w->xs_active && w->lnfree;
+  const bool xs_fused = w->xs_active && !lnfree && w->xs_fuse_q;
+  const bool fuse_q = !w->xs_active && w->fuse_cross_q && !pre && B <= 16 && D == 768;
+  const bool q_launch = !fuse_q && !lnfree && !xs_fused;    // the query projection as a launch of its own
+  // LayerNorm-free query: the resolved rows and their tile statistics (X-stream instances only)
+  bf16_t* xb = !lnfree ? nullptr : (pre ? w->pf_xb : w->dxb + ro * D);
+  float2* st2 = !lnfree ? nullptr : (pre ? w->pf_st2 : w->dst2 + ro * (D / 16));
   for (int l = 0; l < d.n_text_layer; l++) {
     const DecLayer& L = w->dec[l];
-    if (ablate == 2 && w->xs_active) {
-      XsParams xp;
-      memset(&xp, 0, sizeof(xp));
-      xp.q = dq; xp.WkT = L.WckT; xp.xq = w->xq + ro * H * D;
-      xp.part_o = w->xs_po + ccx_xs_part_o_elems(ro, H, D); xp.part_ml = w->xs_pml + ccx_xs_part_ml_elems(ro);
-      xp.X = w->xa + ro * (long)d.n_audio_ctx * D; xp.x_seq_stride = (long)d.n_audio_ctx * D;
-      xp.Wv = L.Wckv + (long)D * D; xp.bv = L.bckv + D; xp.out = dattn;
-      xp.rows = B; xp.H = H; xp.S = d.n_audio_ctx; xp.D = D; xp.scale_log2e = scale_log2e;
-      xp.lds_pad = w->cross_lds_pad > 0 ? 65536 : 0;
-      TRY(ccx_launch_xs_cross_attention(ctx, xp, stream));
-      continue;
-    }
-    if (ablate == 2 && B > 16 && !w->xs_active) {
-      DecAttnParams ap;
-      memset(&ap, 0, sizeof(ap));
-      ap.q = dq; ap.k = L.crossK + cross_off; ap.v = L.crossV + cross_off; ap.H = H; ap.kv_T = w->Spad; ap.pos = nullptr; ap.T = d.n_audio_ctx;
-      ap.scale_log2e = scale_log2e; ap.part_o = part_o; ap.part_ml = part_ml; ap.out_bf16 = dattn;
-      ap.lds_pad = w->cross_lds_pad; ap.stream_mode = w->cross_stream ? 1 : 0;
-      TRY(ccx_launch_dec_attention(ctx, ap, B, ns, ns == 1, stream));
-      continue;
-    }
     // LN + QKV, k/v appended to the self cache at pos[b]
     {
       DecLinearParams ex;
@@ -1181,120 +1052,74 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     ap.out_bf16 = dattn; ap.row_seq = row_seq;
     TRY(ccx_launch_dec_attention(ctx, ap, B, 1, true, stream));
     stamp(17, 2);
-    if (lnfree3) {
+    if (lnfree) {
       DecLinearParams lp;
       memset(&lp, 0, sizeof(lp));
       lp.M = B; lp.N = D; lp.K = D; lp.W = L.Wo; lp.ldw = D; lp.bias = L.bo; lp.act = dattn; lp.lda = D;
-      lp.xres = cur; lp.xb = pre ? w->pf_xb : w->dxb + ro * D; lp.st_out = pre ? w->pf_st2 : w->dst2 + ro * (D / 16);
+      lp.xres = cur; lp.xb = xb; lp.st_out = st2;
       TRY(ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_RESOLVE, lp, stream));
     } else {
       TRY(partial_linear(ACT_BF16, L.Wo, L.bo, D, dattn));
     }
     stamp(18, 2);
-    // cross attention.  Small batches (<= 16 rows, d_model 768: the reference's one-window-per-call pattern): the query projection
-    // LN(x) Wcq^T runs INSIDE the cross-attention blocks (ccx_launch_dec_cross_fused_q: one launch fewer per layer on a chain that
-    // is latency-bound launch by launch; q is bit-identical to the two-launch path).  CCX_FUSE_CROSS_Q=0 restores the two launches.
-    const bool fuse_q = w->fuse_cross_q && !pre && B <= 16 && D == 768 && ablate == 0 && !w->xs_active;
-    // X-stream path: the query projection (with its resolve + LayerNorm) runs inside the expansion kernel -- one launch for three
-    // (CCX_XS_FUSE_Q=0: the three launches)
-    const bool xs_fused = w->xs_active && w->xs_fuse_q;
-    if (!fuse_q && !xs_fused && !lnfree3) TRY(ln_linear(DEPI_F32, L.Wcq, L.bcq, D, L.lnc_g, L.lnc_b, dq, D, nullptr));
+    // cross attention
+    if (q_launch) TRY(ln_linear(DEPI_F32, L.Wcq, L.bcq, D, L.lnc_g, L.lnc_b, dq, D, nullptr));
     stamp(1, 1);
     if (l == 0 && stagger) CCX_HIP(ctx, hipEventRecord(stagger, stream));
     if (w->xs_active) {
-      // decodes of more than 80 sequences: one pass over the encoder output serves all heads (cross_x.hip)
-      if (ablate != 1) {
-        XsParams xp;
-        memset(&xp, 0, sizeof(xp));
-        if (lnfree3) {
-          xp.xb = pre ? w->pf_xb : w->dxb + ro * D; xp.ln_stats = pre ? w->pf_st2 : w->dst2 + ro * (D / 16);
-          xp.ln_s = L.scq; xp.Wq = L.Wcq_g; xp.bq = L.ccq; xp.eps = 1e-5f;
-        } else if (xs_fused) {
-          xp.x = cur; xp.pend = pend; xp.pend_n = pend_n; xp.pend_stride = pstride; xp.x_out = pend_n > 0 ? other : nullptr;
-          xp.ln_g = L.lnc_g; xp.ln_b = L.lnc_b; xp.eps = 1e-5f; xp.Wq = L.Wcq_plain; xp.bq = L.bcq;
-        }
-        xp.q = dq; xp.WkT = L.WckT; xp.xq = pre ? w->pf_xq : w->xq + ro * H * D;
-        xp.part_o = pre ? w->pf_xs_po : w->xs_po + ccx_xs_part_o_elems(ro, H, D);
-        xp.part_ml = pre ? w->pf_xs_pml : w->xs_pml + ccx_xs_part_ml_elems(ro);
-        xp.X = pre ? w->xa : w->xa + ro * (long)d.n_audio_ctx * D; xp.x_seq_stride = (long)d.n_audio_ctx * D; xp.row_seq = row_seq;
-        xp.Wv = L.Wckv + (long)D * D; xp.bv = L.bckv + D; xp.out = dattn;
-        xp.rows = B; xp.H = H; xp.S = d.n_audio_ctx; xp.D = D; xp.scale_log2e = scale_log2e;
-        xp.lds_pad = (w->cross_lds_pad > 0 && !pre) ? 65536 : 0;
-        xp.rows_per_seq = pre ? prefill_rows : 0;
-        TRY(ccx_launch_xs_cross_attention(ctx, xp, stream));
-        if (xs_fused && pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
+      XsParams xp;
+      memset(&xp, 0, sizeof(xp));
+      if (lnfree) {
+        xp.xb = xb; xp.ln_stats = st2; xp.ln_s = L.scq; xp.Wq = L.Wcq_g; xp.bq = L.ccq; xp.eps = 1e-5f;
       } else if (xs_fused) {
-        TRY(ln_linear(DEPI_F32, L.Wcq, L.bcq, D, L.lnc_g, L.lnc_b, dq, D, nullptr));     // chain-only ablation: keep the resolve
+        xp.x = cur; xp.pend = pend; xp.pend_n = pend_n; xp.pend_stride = pstride; xp.x_out = pend_n > 0 ? other : nullptr;
+        xp.ln_g = L.lnc_g; xp.ln_b = L.lnc_b; xp.eps = 1e-5f; xp.Wq = L.Wcq_plain; xp.bq = L.bcq;
       }
+      xp.q = dq; xp.WkT = L.WckT; xp.xq = pre ? w->pf_xq : w->xq + ro * H * D;
+      xp.part_o = pre ? w->pf_xs_po : w->xs_po + ccx_xs_part_o_elems(ro, H, D);
+      xp.part_ml = pre ? w->pf_xs_pml : w->xs_pml + ccx_xs_part_ml_elems(ro);
+      xp.X = pre ? w->xa : w->xa + ro * (long)d.n_audio_ctx * D; xp.x_seq_stride = (long)d.n_audio_ctx * D; xp.row_seq = row_seq;
+      xp.Wv = L.Wckv + (long)D * D; xp.bv = L.bckv + D; xp.out = dattn;
+      xp.rows = B; xp.H = H; xp.S = d.n_audio_ctx; xp.D = D; xp.scale_log2e = scale_log2e;
+      xp.lds_pad = (w->cross_lds_pad > 0 && !pre) ? 65536 : 0;
+      xp.rows_per_seq = pre ? prefill_rows : 0;
+      TRY(ccx_launch_xs_cross_attention(ctx, xp, stream));
+      if (xs_fused && pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
       stamp(2, 1);
-      if (lnfree4) {
-        DecLinearParams lp;
-        memset(&lp, 0, sizeof(lp));
-        lp.M = B; lp.N = D; lp.K = D; lp.W = L.Wco; lp.ldw = D; lp.bias = L.bco; lp.act = dattn; lp.lda = D;
-        lp.xres = cur; lp.xb = pre ? w->pf_xb : w->dxb + ro * D; lp.st_out = pre ? w->pf_st2 : w->dst2 + ro * (D / 16);
-        TRY(ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_RESOLVE, lp, stream));
-      } else {
+      TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
+      stamp(19, 2);
+    } else {
+      memset(&ap, 0, sizeof(ap));
+      ap.q = dq; ap.k = L.crossK + cross_off; ap.v = L.crossV + cross_off; ap.H = H; ap.kv_T = w->Spad; ap.pos = nullptr; ap.T = d.n_audio_ctx;
+      ap.scale_log2e = scale_log2e; ap.part_o = part_o; ap.part_ml = part_ml; ap.out_bf16 = dattn;
+      ap.lds_pad = w->cross_lds_pad;
+      ap.stream_mode = (w->cross_stream && B > 16) ? 1 : 0;
+      if (fuse_q) {
+        ap.qx = cur; ap.q_pend = pend; ap.q_pend_n = pend_n; ap.q_pend_stride = pstride; ap.q_x_out = pend_n > 0 ? other : nullptr;
+        ap.q_ln_g = L.lnc_g; ap.q_ln_b = L.lnc_b; ap.q_eps = 1e-5f; ap.q_W = L.Wcq; ap.q_bias = L.bcq; ap.q_K = D;
+        TRY(ccx_launch_dec_cross_fused_q(ctx, ap, B, ns, stream));
+        if (pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
+        TRY(partial_linear(ACT_COMBINE, L.Wco, L.bco, D, nullptr));
+      } else if (pre) {
+        // two prompt rows and more per sequence share its K/V; a one-row pass runs as a decode step would
+        ap.row_seq = prefill_rows > 1 ? row_seq : nullptr; ap.rows_per_seq = prefill_rows > 1 ? prefill_rows : 0;
+        ap.lds_pad = 0; ap.stream_mode = 1;
+        TRY(ccx_launch_dec_attention(ctx, ap, nseq, 1, true, stream));
         TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
-      }
-      stamp(19, 2);
-    } else {
-    memset(&ap, 0, sizeof(ap));
-    ap.q = dq; ap.k = L.crossK + cross_off; ap.v = L.crossV + cross_off; ap.H = H; ap.kv_T = w->Spad; ap.pos = nullptr; ap.T = d.n_audio_ctx;
-    ap.scale_log2e = scale_log2e; ap.part_o = part_o; ap.part_ml = part_ml; ap.out_bf16 = dattn;
-    ap.lds_pad = w->cross_lds_pad;
-    ap.stream_mode = (w->cross_stream && B > 16) ? 1 : 0;
-    if (fuse_q) {
-      ap.qx = cur; ap.q_pend = pend; ap.q_pend_n = pend_n; ap.q_pend_stride = pstride; ap.q_x_out = pend_n > 0 ? other : nullptr;
-      ap.q_ln_g = L.lnc_g; ap.q_ln_b = L.lnc_b; ap.q_eps = 1e-5f; ap.q_W = L.Wcq; ap.q_bias = L.bcq; ap.q_K = D;
-      TRY(ccx_launch_dec_cross_fused_q(ctx, ap, B, ns, stream));
-      if (pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
-      TRY(partial_linear(ACT_COMBINE, L.Wco, L.bco, D, nullptr));
-    } else if (pre) {
-      ap.row_seq = row_seq; ap.rows_per_seq = prefill_rows; ap.lds_pad = 0; ap.stream_mode = 1;
-      if (prefill_rows > 1) {
-        TRY(ccx_launch_dec_attention(ctx, ap, nseq, 1, true, stream));
+      } else if (B > 16) {
+        TRY(ccx_launch_dec_attention(ctx, ap, B, ns, ns == 1, stream));
+        stamp(2, 1);
+        if (ns > 1) TRY(ccx_launch_dec_combine(ctx, part_o, part_ml, ns, dattn, B, H, stream));
+        TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
+        stamp(19, 2);
       } else {
-        ap.row_seq = nullptr; ap.rows_per_seq = 0;
-        TRY(ccx_launch_dec_attention(ctx, ap, nseq, 1, true, stream));
+        TRY(ccx_launch_dec_attention(ctx, ap, B, ns, false, stream));
+        TRY(partial_linear(ACT_COMBINE, L.Wco, L.bco, D, nullptr));
       }
-      TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
-    } else if (ablate == 1 && B > 16) {
-      TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
-    } else if (B > 16) {
-      TRY(ccx_launch_dec_attention(ctx, ap, B, ns, ns == 1, stream));
-      stamp(2, 1);
-      if (ns > 1) TRY(ccx_launch_dec_combine(ctx, part_o, part_ml, ns, dattn, B, H, stream));
-      TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
-      stamp(19, 2);
-    } else {
-      TRY(ccx_launch_dec_attention(ctx, ap, B, ns, false, stream));
-      TRY(partial_linear(ACT_COMBINE, L.Wco, L.bco, D, nullptr));
     }
-    }   // !xs_active
-    // MLP.  OPTIONAL (CCX_DEC_FC1_GEMM_ROWS=n, off by default): with n rows and more the first linear runs through the tiled GEMM,
-    // which shares the weight and activation tiles of a block through LDS where the skinny kernel re-reads them per 32-column
-    // block out of L2: pipeline step 653.1 -> 647.6 ms at n = 256.  It is off because the GEMM sums K in another order than the
-    // skinny kernel: a sequence's log-probabilities would then depend (in the last bits) on how many rows its lane or its
-    // prefill pass has, and tests/test_pinned_parity_gpu.py holds the records of a clip bit-identical whatever its batch mates.
-    // (The self-attention q|k|v projection the same way -- GEMM into an fp32 scratch plus a scatter kernel for the cache rows --
-    // was measured too: 650.8 against 650.5 ms, removed.)
-    static const int fc1_gemm_rows = [] { const char* e = getenv("CCX_DEC_FC1_GEMM_ROWS"); return e ? atoi(e) : 0; }();
-    if (fc1_gemm_rows > 0 && B >= fc1_gemm_rows && L.W1_plain && D % 64 == 0) {
-      TRY(ccx_launch_dec_resolve_ln(ctx, cur, pend, pend_n, pstride, L.ln2_g, L.ln2_b, dxn, pend_n > 0 ? other : nullptr, B, D, 1e-5f, stream));
-      if (pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
-      GemmParams gp;
-      memset(&gp, 0, sizeof(gp));
-      gp.A = dxn; gp.lda = D; gp.W = L.W1_plain; gp.ldw = D; gp.M = B; gp.N = F; gp.K = D; gp.bias = L.b1; gp.out = dffn; gp.ldo = F;
-      TRY(ccx_launch_gemm(ctx, EPI_BF16_GELU, gp, stream));
-    } else if (lnfree4) {
-      DecLinearParams lp;
-      memset(&lp, 0, sizeof(lp));
-      lp.M = B; lp.N = F; lp.K = D; lp.W = L.W1_g; lp.ldw = D; lp.bias = L.c1; lp.ln_s = L.s1; lp.eps = 1e-5f;
-      lp.ln_stats = pre ? w->pf_st2 : w->dst2 + ro * (D / 16); lp.act = pre ? w->pf_xb : w->dxb + ro * D; lp.lda = D; lp.out = dffn; lp.ldo = F;
-      TRY(ccx_launch_dec_linear(ctx, ACT_BF16_LN, DEPI_BF16_GELU, lp, stream));
-    } else {
-      TRY(ln_linear(DEPI_BF16_GELU, L.W1, L.b1, F, L.ln2_g, L.ln2_b, dffn, F, nullptr));
-    }
+    // MLP.  (fc1 through the tiled GEMM from 256 rows on, 653.1 -> 647.6 ms per pipeline step, was removed: the GEMM sums K in
+    // another order, so a sequence's log-probabilities would depend on its lane's row count -- DESIGN.md)
+    TRY(ln_linear(DEPI_BF16_GELU, L.W1, L.b1, F, L.ln2_g, L.ln2_b, dffn, F, nullptr));
     stamp(20, 2);
     TRY(partial_linear(ACT_BF16, L.W2, L.b2, F, dffn));
     stamp(21, 2);
@@ -1449,10 +1274,9 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
     if (prompt_lens[b] > max_pl) max_pl = prompt_lens[b];
   }
   // prompts of 2 tokens and more are prefilled, kPrefillMax positions per pass (CCX_PREFILL=0: one decode step per prompt token, round
-  // 1's way; CCX_PREFILL_MAX=n: prompts longer than n tokens stepwise -- 16 was round 2's limit)
+  // 1's way)
   const int prefill_on = [] { const char* e = getenv("CCX_PREFILL"); return e ? atoi(e) : 1; }();     // read per call: tests flip it
-  const int prefill_max = [] { const char* e = getenv("CCX_PREFILL_MAX"); return e ? atoi(e) : 1 << 30; }();
-  const bool prefill = prefill_on && max_pl >= 2 && max_pl <= prefill_max;
+  const bool prefill = prefill_on && max_pl >= 2;
   TRY(select_cross_path(w, B, stream));
   TRY(upload_decode_state(w, prompt_ids, prompt_lens, max_prompt, B, temperature, seed, stream, prefill));
   // steps still to run after the (eager) first one: the prefill already covers the prompt AND takes the first sample below
@@ -1485,21 +1309,14 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   // While lanes overlap, the cross attention of one lane (4,608 short blocks that fill every wave slot) makes the other
   // lanes' 5-8 us kernels queue for a slot.  Its blocks therefore claim 64 KB of LDS they do not use: two blocks per CU
   // still keep HBM saturated (each wave has 16 KB of loads in flight; 49.4 -> 51.3 us per launch) and the pipeline step
-  // drops 924 -> 897 ms (3 blocks per CU: 910; 4: 919; 1: 979).  CCX_CROSS_LDS_PAD overrides.
+  // drops 924 -> 897 ms (3 blocks per CU: 910; 4: 919; 1: 979).
   {
-    static const int forced_pad = [] { const char* e = getenv("CCX_CROSS_LDS_PAD"); return e ? atoi(e) : -1; }();
-    static const int lean = [] { const char* e = getenv("CCX_CROSS_STREAM"); return e ? atoi(e) : 1; }();
-    w->cross_stream = lean;
+    w->cross_stream = 1;
     { const char* e = getenv("CCX_FUSE_CROSS_Q"); w->fuse_cross_q = e ? (atoi(e) != 0) : 1; }      // read per decode: tests flip it
-    // default 3: the self-attention output projection resolves the residual in place and the cross-attention query applies its
-    // LayerNorm algebraically (no twelve-fold resolve + LayerNorm inside the expansion kernel; -1.0 ... -1.2 % per decode step);
-    // 0: round 3's chain; 1 / 2 / 4 / 5: the experiments of DESIGN.md section 2 (need the instance created with CCX_DEC_LNFREE set)
-    { const char* e = getenv("CCX_DEC_LNFREE"); w->lnfree_mode = e ? atoi(e) : 3;
-      if (w->lnfree_mode != 0 && w->lnfree_mode != 3 && !w->lnfree_built) w->lnfree_mode = 3;
-      w->lnfree = w->lnfree_mode != 0; }
+    { const char* e = getenv("CCX_DEC_LNFREE"); w->lnfree = !(e && strcmp(e, "0") == 0); }       // read per decode: tests flip it
     // lean streaming: ONE 4-wave block per CU (98 KB of claimed LDS), each wave with 8-16 KB in flight.  The claim only exists to
     // leave room for the OTHER lanes' chain kernels: a single lane runs uncapped.
-    w->cross_lds_pad = forced_pad >= 0 ? forced_pad : (nl > 1 ? (lean ? 98304 : 65536) : 0);
+    w->cross_lds_pad = nl > 1 ? 98304 : 0;
   }
   struct Lane { int b0, B; hipStream_t s; hipGraphExec_t exec; };
   Lane lanes[ccx_whisper::kMaxLanes];
@@ -1534,8 +1351,7 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   int step = prefill ? 1 : 0;                   // the prefill's own sample counts as step 0
   if (step < total_steps) {
     for (int i = 0; i < nl; i++) {
-      static const bool stagger_on = [] { const char* e = getenv("CCX_LANE_STAGGER"); return !e || atoi(e) != 0; }();
-      if (i > 0 && stagger_on) CCX_HIP(ctx, hipStreamWaitEvent(lanes[i].s, w->lane_start[i - 1], 0));
+      if (i > 0) CCX_HIP(ctx, hipStreamWaitEvent(lanes[i].s, w->lane_start[i - 1], 0));
       TRY(step_lane(i, (i + 1 < nl) ? w->lane_start[i] : nullptr));
       if (ctx->prof_on && !use_graph && nl > 1) CCX_HIP(ctx, hipStreamSynchronize(lanes[i].s));
     }
@@ -1543,10 +1359,11 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   }
   if (use_graph && step < total_steps) {
     for (int i = 0; i < nl; i++) {
-      // graphs are specific to (lane rows, sample_len, max_prompt)
-      // ... and to everything else dec_step bakes into kernel parameters: the cross-attention LDS cap and split count
-      const int ns_key = cross_split(lanes[i].B, w->d.n_text_head, w->cross_lds_pad > 0, w->cross_stream != 0);
-      const std::array<int, 9> key = {lanes[i].b0, lanes[i].B, sample_len, max_prompt, w->sampling ? 1 : 0, ns_key, w->cross_lds_pad, w->cross_stream | (w->fuse_cross_q << 4) | ((w->xs_active ? 1 : 0) << 8) | ((w->xs_fuse_q ? 1 : 0) << 9) | (w->lnfree_mode << 16), i};
+      // graphs are specific to (lane rows, sample_len, max_prompt, sampling)
+      // ... and to everything else dec_step bakes into the graph: the cross-attention split count and LDS cap, and the chain's form
+      const int ns_key = cross_split(lanes[i].B, w->d.n_text_head, w->cross_stream != 0);
+      const int form = (w->fuse_cross_q ? 1 : 0) | ((w->xs_active ? 1 : 0) << 1) | ((w->xs_fuse_q ? 1 : 0) << 2) | ((w->lnfree ? 1 : 0) << 3);
+      const std::array<int, 9> key = {lanes[i].b0, lanes[i].B, sample_len, max_prompt, w->sampling ? 1 : 0, ns_key, w->cross_lds_pad, form, i};
       auto it = w->graphs.find(key);
       if (it != w->graphs.end()) { lanes[i].exec = it->second; continue; }
       hipGraph_t graph = nullptr;

@@ -1,6 +1,6 @@
 """Stand-alone timing of ccx_gemm_bf16 on the Whisper encoder's shapes (192 windows: M = 288 000), random operands.
-CCX_GEMM_PHASED=0 selects the two-stage 256 x 256 kernel for an A/B run in a second process; GEMM_ITERS / GEMM_ONLY=<qkv|out|fc1|fc2>
-for long single-shape runs (tools/power_sampler.py)."""
+GEMM_M sets M; GEMM_ITERS / GEMM_ONLY=<qkv|out|fc1|fc2> for long single-shape runs (tools/power_sampler.py).  A diagnostic build
+(-DCCX_ABL_*, tools/README.md) loaded in its place times the phased kernel without parts of its work."""
 import math, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
