@@ -167,9 +167,12 @@ __global__ __launch_bounds__(256) void dec_xq_fused_kernel(XsParams p) {
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The expansion with the query projection of the LayerNorm-FREE chain: the producer of the residual stream (the self-attention output
-// projection, DEPI_RESOLVE in decoder.hip) left the resolved rows as bf16 and (sum, sum of squares) per 16-column tile; the LayerNorm
-// is applied algebraically, q = rstd (xb (gamma o Wq)^T - mean s) + c.  Block = (head, 16 rows): no resolve, no normalisation pass, the
-// rows go from global memory straight into the MFMA B operand.
+// projection, DEPI_RESOLVE in decoder.hip) left the resolved rows, centred by a per-row shift (their attn_ln mean + mean(bo) where that
+// mean exceeds the row's std, else 0), as bf16
+// and their (sum, sum of squares) per 16-column tile; the LayerNorm is applied algebraically, q = rstd (xb (gamma o Wq)^T - mean s) + c
+// with mean, rstd of the centred row (LayerNorm ignores the shift; centring keeps the bf16 rounding and E[x^2] - mean^2 at the
+// row's std instead of its |mean|).  Block = (head, 16 rows): no resolve, no normalisation pass, the rows go from global memory
+// straight into the MFMA B operand.
 // ---------------------------------------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void dec_xq_lnfree_kernel(XsParams p) {

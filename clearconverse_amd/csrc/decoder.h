@@ -4,8 +4,8 @@
 
 enum { ACT_LN = 0, ACT_BF16 = 1, ACT_COMBINE = 2 };
 // DEPI_RESOLVE: the residual add done by the PRODUCER (no split-K slabs): x[m][n] += acc + bias in place (fp32), a bf16 copy of the new
-// row and, per 16-column tile of every row, (sum, sum of squares) -- the statistics with which the cross-attention query of the
-// X-stream path applies its LayerNorm algebraically (dec_xq_lnfree_kernel, cross_x.hip)
+// row centred by a per-row shift and, per 16-column tile of every row, its (sum, sum of squares) -- the statistics with which the
+// cross-attention query of the X-stream path applies its LayerNorm algebraically (dec_xq_lnfree_kernel, cross_x.hip)
 enum { DEPI_BF16_GELU = 1, DEPI_PARTIAL = 2, DEPI_F32 = 3, DEPI_SELF_QKV = 4, DEPI_RESOLVE = 5 };
 
 struct DecLinearParams {
@@ -17,10 +17,14 @@ struct DecLinearParams {
   const float* pend; int pend_n; long pend_stride;  // pending split-K partials [pend_n][M][K] folded into x
   float* x_out;                   // ACT_LN: if non-null, block (0,*,0) writes x + sum(pend) here (must differ from x)
   const float* ln_g; const float* ln_b; float eps;
+  float* ln_mean_out;             // ACT_LN: if non-null, block (0,*,0) writes every row's centring shift here [M] (centre_shift)
   const bf16_t* act; long lda;    // ACT_BF16: [M][K]
   const float* part_o; const float* part_ml; int nsplit;  // ACT_COMBINE: [M][H][nsplit][64], [M][H][nsplit][2]
-  // DEPI_RESOLVE: xres [M][N] f32 (read and written in place), xb [M][N] bf16, st_out [M][N / 16]
-  float* xres; bf16_t* xb; float2* st_out;
+  // DEPI_RESOLVE: xres [M][N] f32 (read and written in place), xb [M][N] bf16, st_out [M][N / 16].  xb and st_out hold the row
+  // CENTRED by shift[m] + shift_c (shift null: uncentred): bf16 rounding of an uncentred row costs ~ulp(|mean|) per element, which the
+  // LayerNorm the query applies afterwards divides by the row's std (uncentred, |mean| / std >= 40 took the teacher-forced logits of
+  // the mini model from rel-L2 5.0e-3 to 1.26e-2: tests/test_whisper_stress_gpu.py)
+  float* xres; bf16_t* xb; float2* st_out; const float* shift; float shift_c;
   // outputs (DEPI_PARTIAL: out[z][m][n] with stride pend_stride between the grid.z slices)
   void* out; long ldo;
   // DEPI_SELF_QKV: q -> out (f32 [M][K]), k/v -> caches [sequence][H][cache_T][64] at pos[m]; the sequence of row m is
@@ -30,9 +34,11 @@ struct DecLinearParams {
 int ccx_launch_dec_linear(ccx_ctx* ctx, int act, int epi, const DecLinearParams& p, hipStream_t stream);
 // number of grid.z K-slices ccx_launch_dec_linear will use (= number of partial slabs written)
 int ccx_dec_linear_ksplit(int K, int epi);
-// out = bf16 LayerNorm(x + sum pend); if x_out != null also writes the resolved x there (must not alias x)
+// out = bf16 LayerNorm(x + sum pend); if x_out != null also writes the resolved x there (must not alias x); if mean_out != null
+// also every row's centring shift from its LayerNorm statistics (the same bits the ACT_LN prologue of dec_linear computes)
 int ccx_launch_dec_resolve_ln(ccx_ctx* ctx, const float* x, const float* pend, int pend_n, long pend_stride, const float* g,
-                              const float* b, bf16_t* out, float* x_out, int M, int K, float eps, hipStream_t stream);
+                              const float* b, bf16_t* out, float* x_out, int M, int K, float eps, hipStream_t stream,
+                              float* mean_out = nullptr);
 
 struct DecAttnParams {
   const float* q;       // [B][H][64] f32

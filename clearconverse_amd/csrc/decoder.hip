@@ -38,6 +38,10 @@ __global__ void dec_embed_kernel(const float* __restrict__ tok_emb, const float*
 
 #include "dec_ln.h"
 
+// The shift DEPI_RESOLVE centres a row by before its bf16 copy (DecLinearParams::shift): the row's LayerNorm mean where it exceeds the
+// row's std, else 0 -- a near-zero-mean row gains nothing from centring and keeps the uncentred arithmetic (and bits) it always had.
+__device__ __forceinline__ float centre_shift(float mean, float rstd) { return fabsf(mean) * rstd > 1.f ? mean : 0.f; }
+
 // ------------------------------------------------------------------------------------------
 // Skinny linear
 // ------------------------------------------------------------------------------------------
@@ -92,6 +96,7 @@ __global__ __launch_bounds__(64 * NW) void dec_linear_kernel(DecLinearParams p) 
   // has no dependent memory round trip of its own
   float4 bias_v[EPI_ITERS];
   float4 xold_v[EPI_ITERS];    // DEPI_RESOLVE: the residual tile this thread finishes
+  float shift_v[EPI_ITERS];    // DEPI_RESOLVE: what its bf16 copy and statistics are centred by
   int pos_v[EPI_ITERS];
 #pragma unroll
   for (int it = 0; it < EPI_ITERS; it++) {
@@ -113,9 +118,12 @@ __global__ __launch_bounds__(64 * NW) void dec_linear_kernel(DecLinearParams p) 
       pos_v[it] = p.pos[m_ < p.M ? m_ : p.M - 1];
     }
     xold_v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+    shift_v[it] = 0.f;
     if (EPI == DEPI_RESOLVE && qd < QUADS) {
       const int m_ = m0 + 16 * tj + (ln & 15);
       xold_v[it] = *(const float4*)(p.xres + (long)(m_ < p.M ? m_ : p.M - 1) * p.N + (n_ + 3 < p.N ? n_ : 0));
+      const float sh = p.shift ? p.shift[m_ < p.M ? m_ : p.M - 1] : 0.f;
+      shift_v[it] = sh != 0.f ? sh + p.shift_c : 0.f;
     }
   }
 
@@ -219,6 +227,7 @@ __global__ __launch_bounds__(64 * NW) void dec_linear_kernel(DecLinearParams p) 
             if (writer) ((float4*)(p.x_out + (long)(m0 + r) * K))[idx] = v[u][i];
           }
         }
+        if (p.ln_mean_out && blockIdx.x == 0 && blockIdx.z == 0 && lane == 0) p.ln_mean_out[m0 + r] = centre_shift(mean[u], rstd[u]);
       }
     }
     // dead rows of the 16-row MFMA tile: zeros
@@ -311,14 +320,16 @@ __global__ __launch_bounds__(64 * NW) void dec_linear_kernel(DecLinearParams p) 
       for (int w = 1; w < NW; w++) v += *(const f32x4*)(red + (((w * NT + i) * MT + j) * 64 + ln) * 4);
       v[0] = (v[0] + bias_v[it].x) + xold_v[it].x; v[1] = (v[1] + bias_v[it].y) + xold_v[it].y;
       v[2] = (v[2] + bias_v[it].z) + xold_v[it].z; v[3] = (v[3] + bias_v[it].w) + xold_v[it].w;
-      float s1 = (v[0] + v[1]) + (v[2] + v[3]);
-      float s2 = fmaf(v[3], v[3], fmaf(v[2], v[2], fmaf(v[1], v[1], v[0] * v[0])));
+      // the residual stays as it is; its bf16 copy and statistics are of the row centred by the shift (DecLinearParams)
+      const float c0 = v[0] - shift_v[it], c1 = v[1] - shift_v[it], c2 = v[2] - shift_v[it], c3 = v[3] - shift_v[it];
+      float s1 = (c0 + c1) + (c2 + c3);
+      float s2 = fmaf(c3, c3, fmaf(c2, c2, fmaf(c1, c1, c0 * c0)));
       s1 += lane_xor16(s1); s2 += lane_xor16(s2);        // the four quads of a row's 16-column tile sit 16 lanes apart
       s1 += lane_xor32(s1); s2 += lane_xor32(s2);
       if (m < p.M && n < p.N) {
         *(float4*)(p.xres + (long)m * p.N + n) = make_float4(v[0], v[1], v[2], v[3]);
         uint2 pk;
-        pk.x = pack_bf16x2(v[0], v[1]); pk.y = pack_bf16x2(v[2], v[3]);
+        pk.x = pack_bf16x2(c0, c1); pk.y = pack_bf16x2(c2, c3);
         *(uint2*)(p.xb + (long)m * p.N + n) = pk;
         if ((ln >> 4) == 0) p.st_out[(long)m * (p.N >> 4) + (n >> 4)] = make_float2(s1, s2);
       }
@@ -369,7 +380,8 @@ __global__ __launch_bounds__(64 * NW) void dec_linear_kernel(DecLinearParams p) 
 __global__ __launch_bounds__(256) void dec_resolve_ln_kernel(const float* __restrict__ x, const float* __restrict__ pend,
                                                              int pend_n, long pend_stride, const float* __restrict__ g,
                                                              const float* __restrict__ b, bf16_t* __restrict__ out,
-                                                             float* __restrict__ x_out, int M, int K, float eps) {
+                                                             float* __restrict__ x_out, int M, int K, float eps,
+                                                             float* __restrict__ mean_out) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= M) return;
@@ -406,6 +418,7 @@ __global__ __launch_bounds__(256) void dec_resolve_ln_kernel(const float* __rest
     sq += (lane + 64 * i < nv) ? t : 0.f;
   }
   const float rstd = rsqrtf(wave_reduce_sum(sq) / (float)K + eps);
+  if (mean_out && lane == 0) mean_out[m] = centre_shift(mean, rstd);
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     const int idx = lane + 64 * i;
@@ -477,13 +490,14 @@ int ccx_launch_dec_combine(ccx_ctx* ctx, const float* part_o, const float* part_
 }
 
 int ccx_launch_dec_resolve_ln(ccx_ctx* ctx, const float* x, const float* pend, int pend_n, long pend_stride, const float* g,
-                              const float* b, bf16_t* out, float* x_out, int M, int K, float eps, hipStream_t stream) {
+                              const float* b, bf16_t* out, float* x_out, int M, int K, float eps, hipStream_t stream,
+                              float* mean_out) {
   CCX_REQUIRE(ctx, K % 4 == 0 && K <= 1024, "dec_resolve_ln: K=%d unsupported", K);
   CCX_REQUIRE(ctx, x_out != x, "dec_resolve_ln: x_out must not alias x");
   // bytes: the residual rows and their pending slabs in, the bf16 rows (and the resolved fp32 rows) out
   ccx_prof_scope ps(ctx, stream, "dec_resolve_ln_kernel", 0.0, (double)M * K * (4.0 * (1 + pend_n) + 2.0 + (x_out ? 4.0 : 0.0)));
   hipLaunchKernelGGL(dec_resolve_ln_kernel, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, pend, pend_n, pend_stride, g, b,
-                     out, x_out, M, K, eps);
+                     out, x_out, M, K, eps, mean_out);
   CCX_CHECK_LAUNCH(ctx);
   return CCX_OK;
 }

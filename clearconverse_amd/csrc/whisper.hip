@@ -65,6 +65,9 @@ struct DecLayer {
   // row-major), s_n = sum_k (gamma o Wcq)_nk over the bf16 values the MFMAs see, c_n = sum_k beta_k Wcq_nk + bcq_n
   bf16_t* Wcq_g = nullptr;
   float *scq = nullptr, *ccq = nullptr;
+  // ... whose rows are centred by the row's attn_ln mean + mean(attn.out.bias) before the bf16 rounding where that mean exceeds the
+  // row's std (DEPI_RESOLVE, centre_shift): the self-attention output adds mean(bias) + a part an offset of the stream does not move
+  float bo_mean = 0.f;
   float *bqkv, *bo, *bcq, *bckv, *bco, *b1, *b2;
   bf16_t *crossK, *crossV, *selfK, *selfV;
 };
@@ -152,7 +155,8 @@ struct ccx_whisper {
   // LayerNorm-free query of the X-stream path: bf16 copy of the resolved residual rows and their (sum, sum of squares) per 16-column tile
   bf16_t *dxb = nullptr, *pf_xb = nullptr;
   float2 *dst2 = nullptr, *pf_st2 = nullptr;
-  bool lnfree = false;                       // the LayerNorm-free query; set per decode (CCX_DEC_LNFREE=0: round 3's query, see dec_step)
+  float *dshift = nullptr, *pf_shift = nullptr;   // ... and the shift they are centred by (the attn_ln mean of the row)
+  bool lnfree = true;                        // the LayerNorm-free query; read per call (read_chain_switches; CCX_DEC_LNFREE=0: round 3's)
   float *xs_po = nullptr, *xs_pml = nullptr, *pf_xs_po = nullptr, *pf_xs_pml = nullptr;   // key-half partials (cross_x.h)
   static constexpr int kLanePool = 8;
   hipStream_t lane_pool[kLanePool] = {};     // candidates; HIP streams share a few hardware queues and two streams on one
@@ -545,6 +549,7 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     std::vector<float> bckv = cat_rows({&zerosD, &cvb->data});
     TRY(up_bf16_packed(w, &L.Wqkv, wqkv.data(), 3 * D, D, 16)); TRY(up_f32(w, &L.bqkv, bqkv.data(), bqkv.size()));
     TRY(up_bf16_packed(w, &L.Wo, ow->data.data(), D, D, 16)); TRY(up_f32(w, &L.bo, obias->data.data(), D));
+    { double sb = 0.0; for (int k = 0; k < D; k++) sb += obias->data[k]; L.bo_mean = (float)(sb / D); }
     TRY(up_bf16_packed(w, &L.Wcq, cqw->data.data(), D, D, 16)); TRY(up_f32(w, &L.bcq, cqb->data.data(), D));
     TRY(up_bf16(w, &L.Wckv, wckv.data(), wckv.size())); TRY(up_f32(w, &L.bckv, bckv.data(), bckv.size()));
     TRY(up_bf16_packed(w, &L.Wco, cow->data.data(), D, D, 16)); TRY(up_f32(w, &L.bco, cob->data.data(), D));
@@ -621,6 +626,8 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     TRY(dev_alloc(w, &w->pf_xb, (size_t)B * ccx_whisper::kPrefillMax * D, true));
     TRY(dev_alloc(w, &w->dst2, (size_t)B * (D / 16), true));
     TRY(dev_alloc(w, &w->pf_st2, (size_t)B * ccx_whisper::kPrefillMax * (D / 16), true));
+    TRY(dev_alloc(w, &w->dshift, (size_t)B, true));
+    TRY(dev_alloc(w, &w->pf_shift, (size_t)B * ccx_whisper::kPrefillMax, true));
   }
   TRY(dev_alloc(w, &w->dx, (size_t)B * D, true));
   TRY(dev_alloc(w, &w->dx2, (size_t)B * D, true));
@@ -771,6 +778,15 @@ static int project_cross_kv(ccx_whisper* w, int n, hipStream_t stream) {
   w->kv_ready = n;
   return CCX_OK;
 }
+// The switches of the decode chain's form, read per call (tests flip them) by BOTH entry points that run dec_step -- decodes and
+// ccx_whisper_decoder_logits -- so that the teacher-forced logits always come from the chain a decode of the same size would run.
+// CCX_FUSE_CROSS_Q=0: the two-launch cross-attention query of <= 16 rows; CCX_DEC_LNFREE=0: round 3's X-stream query;
+// CCX_XS_FUSE_Q=0: that query as a launch of its own.
+static void read_chain_switches(ccx_whisper* w) {
+  { const char* e = getenv("CCX_FUSE_CROSS_Q"); w->fuse_cross_q = e ? (atoi(e) != 0) : 1; }
+  { const char* e = getenv("CCX_DEC_LNFREE"); w->lnfree = !(e && strcmp(e, "0") == 0); }
+  { const char* e = getenv("CCX_XS_FUSE_Q"); w->xs_fuse_q = !e || atoi(e) != 0; }
+}
 // which cross attention a decode of B sequences uses, and the K/V it needs
 static int select_cross_path(ccx_whisper* w, int B, hipStream_t stream) {
   // CCX_CROSS_X_MIN_ROWS (read per call: tests flip it): smallest decode that takes the X-stream path.  Default 81: the streaming kernel
@@ -782,7 +798,6 @@ static int select_cross_path(ccx_whisper* w, int B, hipStream_t stream) {
   const char* e = getenv("CCX_CROSS_X_MIN_ROWS");
   const int min_rows = e ? atoi(e) : ccx_whisper::kKvSeqs + 1;
   w->xs_active = w->xs_on && (B >= min_rows || B > w->kv_cap);
-  { const char* f = getenv("CCX_XS_FUSE_Q"); w->xs_fuse_q = !f || atoi(f) != 0; }      // read per call: tests flip it
   if (w->xs_on && !w->xs_active && w->kv_ready < B) TRY(project_cross_kv(w, B, stream));
   return CCX_OK;
 }
@@ -993,8 +1008,10 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     int rc;
     if (B > 16) {
       // many sequences: normalise ONCE in a stand-alone kernel instead of redundantly in every weight-panel block
-      rc = ccx_launch_dec_resolve_ln(ctx, cur, pend, pend_n, pstride, g, bta, dxn, pend_n > 0 ? other : nullptr, B, D, 1e-5f, stream);
+      rc = ccx_launch_dec_resolve_ln(ctx, cur, pend, pend_n, pstride, g, bta, dxn, pend_n > 0 ? other : nullptr, B, D, 1e-5f, stream,
+                                     lp.ln_mean_out);
       if (rc) return rc;
+      lp.ln_mean_out = nullptr;
       lp.act = dxn; lp.lda = D;
       rc = ccx_launch_dec_linear(ctx, ACT_BF16, epi, lp, stream);
     } else {
@@ -1036,6 +1053,7 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
   // LayerNorm-free query: the resolved rows and their tile statistics (X-stream instances only)
   bf16_t* xb = !lnfree ? nullptr : (pre ? w->pf_xb : w->dxb + ro * D);
   float2* st2 = !lnfree ? nullptr : (pre ? w->pf_st2 : w->dst2 + ro * (D / 16));
+  float* shift = !lnfree ? nullptr : (pre ? w->pf_shift : w->dshift + ro);
   for (int l = 0; l < d.n_text_layer; l++) {
     const DecLayer& L = w->dec[l];
     // LN + QKV, k/v appended to the self cache at pos[b]
@@ -1043,6 +1061,7 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
       DecLinearParams ex;
       memset(&ex, 0, sizeof(ex));
       ex.cache_k = L.selfK + self_off; ex.cache_v = L.selfV + self_off; ex.cache_T = Tc; ex.pos = pos; ex.row_seq = row_seq;
+      ex.ln_mean_out = shift;                      // LayerNorm-free query: the rows' attn_ln means centre their bf16 copies
       TRY(ln_linear(DEPI_SELF_QKV, L.Wqkv, L.bqkv, 3 * D, L.ln1_g, L.ln1_b, dq, D, &ex));
       stamp(16, 2);
     }
@@ -1056,7 +1075,7 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
       DecLinearParams lp;
       memset(&lp, 0, sizeof(lp));
       lp.M = B; lp.N = D; lp.K = D; lp.W = L.Wo; lp.ldw = D; lp.bias = L.bo; lp.act = dattn; lp.lda = D;
-      lp.xres = cur; lp.xb = xb; lp.st_out = st2;
+      lp.xres = cur; lp.xb = xb; lp.st_out = st2; lp.shift = shift; lp.shift_c = L.bo_mean;
       TRY(ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_RESOLVE, lp, stream));
     } else {
       TRY(partial_linear(ACT_BF16, L.Wo, L.bo, D, dattn));
@@ -1213,6 +1232,7 @@ int ccx_whisper_decoder_logits(ccx_whisper* w, const int32_t* tokens, int B, int
     CCX_REQUIRE(ctx, tokens[i] >= 0 && tokens[i] < w->d.n_vocab, "decoder_logits: token id %d out of range", tokens[i]);
   std::vector<int32_t> lens(B, T + 1);  // never leaves the prompt phase: every step feeds tokens[b][pos]
   // prompt buffer rows are `T` wide here
+  read_chain_switches(w);
   TRY(select_cross_path(w, B, stream));
   TRY(upload_decode_state(w, tokens, lens.data(), T, B, 0.f, 0, stream));
   const long V = w->d.n_vocab;
@@ -1277,6 +1297,7 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   // 1's way)
   const int prefill_on = [] { const char* e = getenv("CCX_PREFILL"); return e ? atoi(e) : 1; }();     // read per call: tests flip it
   const bool prefill = prefill_on && max_pl >= 2;
+  read_chain_switches(w);
   TRY(select_cross_path(w, B, stream));
   TRY(upload_decode_state(w, prompt_ids, prompt_lens, max_prompt, B, temperature, seed, stream, prefill));
   // steps still to run after the (eager) first one: the prefill already covers the prompt AND takes the first sample below
@@ -1312,8 +1333,6 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   // drops 924 -> 897 ms (3 blocks per CU: 910; 4: 919; 1: 979).
   {
     w->cross_stream = 1;
-    { const char* e = getenv("CCX_FUSE_CROSS_Q"); w->fuse_cross_q = e ? (atoi(e) != 0) : 1; }      // read per decode: tests flip it
-    { const char* e = getenv("CCX_DEC_LNFREE"); w->lnfree = !(e && strcmp(e, "0") == 0); }       // read per decode: tests flip it
     // lean streaming: ONE 4-wave block per CU (98 KB of claimed LDS), each wave with 8-16 KB in flight.  The claim only exists to
     // leave room for the OTHER lanes' chain kernels: a single lane runs uncapped.
     w->cross_lds_pad = nl > 1 ? 98304 : 0;

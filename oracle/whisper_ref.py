@@ -133,9 +133,12 @@ def sinusoids(length: int, channels: int, max_timescale: float = 10000.0) -> tor
 class WhisperRef:
     """Functional restatement of model.py::Whisper over an openai-layout state dict."""
 
-    def __init__(self, dims: Dims, sd: Dict[str, torch.Tensor]):
+    def __init__(self, dims: Dims, sd: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float32):
+        """dtype: the arithmetic of every op (float32 as openai-whisper runs on a CPU; float64 gives tests a high-precision
+        reference).  Inputs (mel, xa) are converted to it."""
         self.dims = dims
-        self.sd = {k: v.detach().to(torch.float32) for k, v in sd.items()}
+        self.dtype = dtype
+        self.sd = {k: v.detach().to(dtype) for k, v in sd.items()}
 
     # -- helpers --
     def _lin(self, x, name, bias=True):
@@ -154,7 +157,7 @@ class WhisperRef:
         qk = q @ k
         if mask is not None:
             qk = qk + mask[:T, :T]
-        w = F.softmax(qk.float(), dim=-1)
+        w = F.softmax(qk.to(self.dtype), dim=-1)
         return (w @ v).permute(0, 2, 1, 3).flatten(start_dim=2)
 
     def _attn(self, x, prefix, n_head, xa=None, mask=None):
@@ -171,6 +174,7 @@ class WhisperRef:
     def encode(self, mel: torch.Tensor, return_layers: bool = False):
         """mel [B, n_mels, 3000] -> [B, 1500, D]."""
         d = self.dims
+        mel = mel.to(self.dtype)
         x = F.gelu(F.conv1d(mel, self.sd["encoder.conv1.weight"], self.sd["encoder.conv1.bias"], padding=1))
         x = F.gelu(F.conv1d(x, self.sd["encoder.conv2.weight"], self.sd["encoder.conv2.bias"], stride=2, padding=1))
         x = x.permute(0, 2, 1)
@@ -186,18 +190,19 @@ class WhisperRef:
 
     # -- TextDecoder.forward (no kv cache: full recompute, fine for an oracle) --
     def decoder_logits(self, tokens: torch.Tensor, xa: torch.Tensor) -> torch.Tensor:
-        """tokens [B, T] int64, xa [B, 1500, D] -> logits [B, T, V] f32."""
+        """tokens [B, T] int64, xa [B, 1500, D] -> logits [B, T, V] in the model's dtype (f32 by default)."""
         d = self.dims
         T = tokens.shape[-1]
+        xa = xa.to(self.dtype)
         x = self.sd["decoder.token_embedding.weight"][tokens] + self.sd["decoder.positional_embedding"][:T]
-        mask = torch.full((d.n_text_ctx, d.n_text_ctx), float("-inf")).triu_(1)
+        mask = torch.full((d.n_text_ctx, d.n_text_ctx), float("-inf"), dtype=self.dtype).triu_(1)
         for l in range(d.n_text_layer):
             p = f"decoder.blocks.{l}"
             x = x + self._attn(self._ln(x, p + ".attn_ln"), p + ".attn", d.n_text_head, mask=mask)
             x = x + self._attn(self._ln(x, p + ".cross_attn_ln"), p + ".cross_attn", d.n_text_head, xa=xa)
             x = x + self._mlp(self._ln(x, p + ".mlp_ln"), p)
         x = self._ln(x, "decoder.ln")
-        return (x @ self.sd["decoder.token_embedding.weight"].T).float()
+        return (x @ self.sd["decoder.token_embedding.weight"].T).to(self.dtype)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -300,6 +305,7 @@ class CachedDecoder:
     def __init__(self, model: WhisperRef, xa: torch.Tensor):
         self.m = model
         d = model.dims
+        xa = xa.to(model.dtype)
         self.cross = []
         for l in range(d.n_text_layer):
             p = f"decoder.blocks.{l}.cross_attn"
@@ -314,7 +320,7 @@ class CachedDecoder:
         t_new = tokens.shape[-1]
         x = m.sd["decoder.token_embedding.weight"][tokens] + m.sd["decoder.positional_embedding"][self.offset:self.offset + t_new]
         T = self.offset + t_new
-        mask = torch.full((t_new, T), float("-inf")).triu_(self.offset + 1)
+        mask = torch.full((t_new, T), float("-inf"), dtype=m.dtype).triu_(self.offset + 1)
         for l in range(d.n_text_layer):
             p = f"decoder.blocks.{l}"
             h = m._ln(x, p + ".attn_ln")
@@ -329,7 +335,7 @@ class CachedDecoder:
             qh = q.view(B, t_new, nh, -1).permute(0, 2, 1, 3) * sc
             kh = self.self_k[l].view(B, T, nh, -1).permute(0, 2, 3, 1) * sc
             vh = self.self_v[l].view(B, T, nh, -1).permute(0, 2, 1, 3)
-            w = F.softmax((qh @ kh + mask).float(), dim=-1)
+            w = F.softmax((qh @ kh + mask).to(m.dtype), dim=-1)
             x = x + m._lin((w @ vh).permute(0, 2, 1, 3).flatten(start_dim=2), p + ".attn.out")
             h = m._ln(x, p + ".cross_attn_ln")
             q = m._lin(h, p + ".cross_attn.query")
@@ -338,7 +344,7 @@ class CachedDecoder:
             x = x + m._mlp(m._ln(x, p + ".mlp_ln"), p)
         self.offset = T
         x = m._ln(x, "decoder.ln")
-        return (x @ m.sd["decoder.token_embedding.weight"].T).float()
+        return (x @ m.sd["decoder.token_embedding.weight"].T).to(m.dtype)
 
 
 # ---------------------------------------------------------------------------------------------
