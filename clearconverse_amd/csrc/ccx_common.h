@@ -101,6 +101,22 @@ int ccx_fail(ccx_ctx* ctx, int code, const char* fmt, ...);
     if (!(cond)) return ccx_fail((ctx), CCX_ERR_ARG, __VA_ARGS__);        \
   } while (0)
 
+// Pass a callee's error code on (the callee has set the message).
+#define CCX_TRY(expr)      \
+  do {                     \
+    int _rc = (expr);      \
+    if (_rc) return _rc;   \
+  } while (0)
+
+// Host f32 -> bf16, round to nearest even; NaN stays NaN (the device side is f32_to_bf16 below).
+static inline bf16_t ccx_host_f32_to_bf16(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (bf16_t)(u >> 16);
+}
+
 // ---- device helpers -------------------------------------------------------------------
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 

@@ -607,12 +607,6 @@ int ccx_launch_xs_cross_attention(ccx_ctx* ctx, const XsParams& p, hipStream_t s
 // C ABI: one layer's cross attention as a stand-alone operator (kernel-level parity tests, include/ccx.h)
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace {
-inline bf16_t xs_host_bf16(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);
-  return (bf16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
 __global__ void xs_bf16_to_f32_kernel(const bf16_t* __restrict__ in, float* __restrict__ out, long n) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = bf16_to_f32(in[i]);
@@ -638,8 +632,8 @@ extern "C" int ccx_cross_attention_xa(ccx_ctx* ctx, const float* q_dev, const fl
   std::vector<bf16_t> wkt((size_t)D * D), wv((size_t)D * D);
   for (int hh = 0; hh < H; hh++)
     for (int f = 0; f < D; f++)
-      for (int dd = 0; dd < 64; dd++) wkt[((size_t)hh * D + f) * 64 + dd] = xs_host_bf16(wk_host[(size_t)(hh * 64 + dd) * D + f]);
-  for (size_t i = 0; i < wv.size(); i++) wv[i] = xs_host_bf16(wv_host[i]);
+      for (int dd = 0; dd < 64; dd++) wkt[((size_t)hh * D + f) * 64 + dd] = ccx_host_f32_to_bf16(wk_host[(size_t)(hh * 64 + dd) * D + f]);
+  for (size_t i = 0; i < wv.size(); i++) wv[i] = ccx_host_f32_to_bf16(wv_host[i]);
   bf16_t *d_wkt = nullptr, *d_wv = nullptr, *d_xq = nullptr, *d_out = nullptr;
   float *d_bv = nullptr, *d_po = nullptr, *d_pml = nullptr;
   int* d_rs = nullptr;

@@ -17,25 +17,19 @@
 //
 // The convolutional trunk depends only on the chunk, not on the speaker mask, so it runs once per chunk and the
 // pooling + linear run once per (chunk, local speaker) mask.
-#include <map>
 #include <string>
 #include <vector>
 #include <math.h>
 #include "../../include/ccx.h"
 #include "ccx_common.h"
 #include "gemm_bf16.h"
+#include "model_store.h"
 
 namespace {
 
 constexpr int FB_LEN = 400, FB_SHIFT = 160, FB_NFFT = 512, FB_MELS = 80, FB_MELW = 64;
 constexpr int RN_C0 = 32, RN_EMB = 256, RN_STAGES = 4;
 constexpr int RN_BLOCKS[RN_STAGES] = {3, 4, 6, 3};
-
-#define RTRY(expr)        \
-  do {                    \
-    int _rc = (expr);     \
-    if (_rc) return _rc;  \
-  } while (0)
 
 // ------------------------------------------------------------------------------------------------------------
 // Kaldi fbank: one wave per frame, 4 frames per block.  512-point radix-2 FFT in LDS.
@@ -339,16 +333,6 @@ __global__ __launch_bounds__(256) void embed_linear_kernel(const float* __restri
   if (lane == 0) out[(long)j * RN_EMB + o] = s + bias[o];
 }
 
-struct HostT { std::vector<float> data; };
-
-inline bf16_t h2bf(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
-
 struct Conv {
   bf16_t* W = nullptr;   // [cout][ntaps * Kpad], tap = kernel row, columns kw * cin + c (zero padded to Kpad)
   float* b = nullptr;    // folded BatchNorm shift
@@ -366,8 +350,7 @@ struct ccx_resnet {
   int max_chunks = 0, max_masks = 0, max_frames = 0;
   long max_samples = 0;
   bool finalized = false;
-  std::map<std::string, HostT> staged;
-  std::vector<void*> allocs;
+  ccx_dev_store store{"resnet"};
   // fbank tables
   float *window = nullptr, *melw = nullptr;
   float2* twiddle = nullptr;
@@ -388,38 +371,10 @@ struct ccx_resnet {
 
 namespace {
 
-template <typename T>
-int ralloc(ccx_resnet* r, T** out, size_t count) {
-  void* p = nullptr;
-  const size_t bytes = ccx_align(count * sizeof(T), 256);
-  CCX_HIP(r->ctx, hipMalloc(&p, bytes));
-  CCX_HIP(r->ctx, hipMemset(p, 0, bytes));
-  r->allocs.push_back(p);
-  *out = (T*)p;
-  return CCX_OK;
-}
-template <typename T>
-int rup(ccx_resnet* r, T** out, const std::vector<T>& src) {
-  RTRY(ralloc(r, out, src.size()));
-  CCX_HIP(r->ctx, hipMemcpy(*out, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return CCX_OK;
-}
-int rneed(ccx_resnet* r, const std::string& name, size_t numel, const HostT** out) {
-  auto it = r->staged.find(name);
-  if (it == r->staged.end()) return ccx_fail(r->ctx, CCX_ERR_MISSING, "resnet: tensor '%s' was never set", name.c_str());
-  if (it->second.data.size() != numel)
-    return ccx_fail(r->ctx, CCX_ERR_ARG, "resnet: tensor '%s' has %zu elements, expected %zu", name.c_str(), it->second.data.size(), numel);
-  *out = &it->second;
-  return CCX_OK;
-}
-#define RNEED(var, name, numel) \
-  const HostT* var = nullptr;   \
-  RTRY(rneed(r, (name), (size_t)(numel), &var));
-
 // BatchNorm (eval) folded into a per-output-channel scale and shift
 int bn_fold(ccx_resnet* r, const std::string& name, int c, std::vector<float>& scale, std::vector<float>& shift) {
-  RNEED(g, name + ".weight", c); RNEED(be, name + ".bias", c);
-  RNEED(rm, name + ".running_mean", c); RNEED(rv, name + ".running_var", c);
+  CCX_NEED(r->store, g, name + ".weight", c); CCX_NEED(r->store, be, name + ".bias", c);
+  CCX_NEED(r->store, rm, name + ".running_mean", c); CCX_NEED(r->store, rv, name + ".running_var", c);
   scale.resize(c); shift.resize(c);
   for (int i = 0; i < c; i++) {
     scale[i] = g->data[i] / sqrtf(rv->data[i] + 1e-5f);
@@ -430,9 +385,9 @@ int bn_fold(ccx_resnet* r, const std::string& name, int c, std::vector<float>& s
 
 // torch Conv2d weight [cout][cin][k][k] (+ folded BN scale) -> [cout][k taps][Kpad] with columns kw * cin + c
 int load_conv(ccx_resnet* r, const std::string& wname, const std::string& bnname, int cin, int cout, int k, int stride, Conv& cv) {
-  RNEED(w, wname, (size_t)cout * cin * k * k);
+  CCX_NEED(r->store, w, wname, (int64_t)cout * cin * k * k);
   std::vector<float> sc, sh;
-  RTRY(bn_fold(r, bnname, cout, sc, sh));
+  CCX_TRY(bn_fold(r, bnname, cout, sc, sh));
   cv.cin = cin; cv.cout = cout; cv.k = k; cv.stride = stride;
   cv.Kpad = ccx_align(k * cin, 64);
   std::vector<bf16_t> packed((size_t)cout * k * cv.Kpad, 0);
@@ -440,9 +395,9 @@ int load_conv(ccx_resnet* r, const std::string& wname, const std::string& bnname
     for (int c = 0; c < cin; c++)
       for (int kh = 0; kh < k; kh++)
         for (int kw = 0; kw < k; kw++)
-          packed[((size_t)o * k + kh) * cv.Kpad + kw * cin + c] = h2bf(w->data[(((size_t)o * cin + c) * k + kh) * k + kw] * sc[o]);
-  RTRY(rup(r, &cv.W, packed));
-  RTRY(rup(r, &cv.b, sh));
+          packed[((size_t)o * k + kh) * cv.Kpad + kw * cin + c] = ccx_host_f32_to_bf16(w->data[(((size_t)o * cin + c) * k + kh) * k + kw] * sc[o]);
+  CCX_TRY(r->store.upload(&cv.W, packed));
+  CCX_TRY(r->store.upload(&cv.b, sh));
   return CCX_OK;
 }
 
@@ -512,28 +467,25 @@ extern "C" {
 int ccx_resnet_create(ccx_ctx* ctx, int max_chunks, int64_t max_samples, int max_masks, ccx_resnet** out) {
   if (!ctx || !out) return CCX_ERR_ARG;
   CCX_REQUIRE(ctx, max_chunks >= 1 && max_masks >= 1 && max_samples >= FB_LEN + 7 * FB_SHIFT, "resnet_create: bad capacities");
+  const int max_frames = 1 + (int)((max_samples - FB_LEN) / FB_SHIFT);
+  CCX_REQUIRE(ctx, (long)max_chunks * 82 * (max_frames + 2) < (1L << 31), "resnet_create: max_chunks x frames too large for one launch");
   ccx_resnet* r = new ccx_resnet();
-  r->ctx = ctx; r->max_chunks = max_chunks; r->max_masks = max_masks; r->max_samples = max_samples;
-  r->max_frames = 1 + (int)((max_samples - FB_LEN) / FB_SHIFT);
-  CCX_REQUIRE(ctx, (long)max_chunks * 82 * (r->max_frames + 2) < (1L << 31), "resnet_create: max_chunks x frames too large for one launch");
+  r->ctx = ctx; r->store.ctx = ctx; r->max_chunks = max_chunks; r->max_masks = max_masks; r->max_samples = max_samples;
+  r->max_frames = max_frames;
   *out = r;
   return CCX_OK;
 }
 
 void ccx_resnet_destroy(ccx_resnet* r) {
   if (!r) return;
-  for (void* p : r->allocs) hipFree(p);
+  r->store.free_all();
   delete r;
 }
 
 int ccx_resnet_set_tensor(ccx_resnet* r, const char* name, const float* data, int64_t numel) {
   if (!r) return CCX_ERR_ARG;
   CCX_REQUIRE(r->ctx, !r->finalized && name && data && numel > 0, "resnet: set_tensor bad arguments");
-  HostT t;
-  t.data.resize((size_t)numel);
-  CCX_HIP(r->ctx, hipMemcpy(t.data.data(), data, (size_t)numel * 4, hipMemcpyDefault));
-  r->staged[std::string(name)] = std::move(t);
-  return CCX_OK;
+  return r->store.stage(name, data, numel);
 }
 
 int ccx_resnet_finalize(ccx_resnet* r) {
@@ -566,18 +518,18 @@ int ccx_resnet_finalize(ccx_resnet* r) {
       ms[m] = first; ml[m] = last - first + 1;
       for (int k = first; k <= last; k++) mw[(size_t)m * FB_MELW + (k - first)] = wts[k];
     }
-    RTRY(rup(r, &r->window, win)); RTRY(rup(r, &r->twiddle, tw)); RTRY(rup(r, &r->melw, mw));
-    RTRY(rup(r, &r->mel_start, ms)); RTRY(rup(r, &r->mel_len, ml));
+    CCX_TRY(r->store.upload(&r->window, win)); CCX_TRY(r->store.upload(&r->twiddle, tw)); CCX_TRY(r->store.upload(&r->melw, mw));
+    CCX_TRY(r->store.upload(&r->mel_start, ms)); CCX_TRY(r->store.upload(&r->mel_len, ml));
   }
   // ---- conv1 (kept f32: one input channel) ----
   {
-    RNEED(w, "resnet.conv1.weight", RN_C0 * 9);
+    CCX_NEED(r->store, w, "resnet.conv1.weight", RN_C0 * 9);
     std::vector<float> sc, sh;
-    RTRY(bn_fold(r, "resnet.bn1", RN_C0, sc, sh));
+    CCX_TRY(bn_fold(r, "resnet.bn1", RN_C0, sc, sh));
     std::vector<float> wf(RN_C0 * 9);
     for (int c = 0; c < RN_C0; c++)
       for (int k = 0; k < 9; k++) wf[c * 9 + k] = w->data[c * 9 + k] * sc[c];
-    RTRY(rup(r, &r->c1w, wf)); RTRY(rup(r, &r->c1b, sh));
+    CCX_TRY(r->store.upload(&r->c1w, wf)); CCX_TRY(r->store.upload(&r->c1b, sh));
   }
   // ---- residual stages ----
   int cin = RN_C0;
@@ -587,31 +539,31 @@ int ccx_resnet_finalize(ccx_resnet* r) {
       const std::string p = "resnet.layer" + std::to_string(s + 1) + "." + std::to_string(b) + ".";
       const int stride = (s > 0 && b == 0) ? 2 : 1;
       Block blk;
-      RTRY(load_conv(r, p + "conv1.weight", p + "bn1", cin, cout, 3, stride, blk.c1));
-      RTRY(load_conv(r, p + "conv2.weight", p + "bn2", cout, cout, 3, 1, blk.c2));
+      CCX_TRY(load_conv(r, p + "conv1.weight", p + "bn1", cin, cout, 3, stride, blk.c1));
+      CCX_TRY(load_conv(r, p + "conv2.weight", p + "bn2", cout, cout, 3, 1, blk.c2));
       blk.has_sc = stride != 1 || cin != cout;
-      if (blk.has_sc) RTRY(load_conv(r, p + "shortcut.0.weight", p + "shortcut.1", cin, cout, 1, stride, blk.sc));
+      if (blk.has_sc) CCX_TRY(load_conv(r, p + "shortcut.0.weight", p + "shortcut.1", cin, cout, 1, stride, blk.sc));
       r->blocks.push_back(blk);
       cin = cout;
     }
   }
   {
-    RNEED(w, "resnet.seg_1.weight", (size_t)RN_EMB * 5120); RNEED(b, "resnet.seg_1.bias", RN_EMB);
-    RTRY(rup(r, &r->segW, w->data)); RTRY(rup(r, &r->segb, b->data));
+    CCX_NEED(r->store, w, "resnet.seg_1.weight", (int64_t)RN_EMB * 5120); CCX_NEED(r->store, b, "resnet.seg_1.bias", RN_EMB);
+    CCX_TRY(r->store.upload(&r->segW, w->data)); CCX_TRY(r->store.upload(&r->segb, b->data));
   }
-  r->staged.clear();
+  r->store.staged.clear();
   // ---- workspaces ----
   const int T = r->max_frames;
-  RTRY(ralloc(r, &r->feats_t, (size_t)r->max_chunks * FB_MELS * T));
-  RTRY(ralloc(r, &r->fmean, (size_t)r->max_chunks * FB_MELS));
-  RTRY(ralloc(r, &r->pooled, (size_t)r->max_masks * 5120));
-  RTRY(ralloc(r, &r->mask_chunk_dev, (size_t)r->max_masks));
+  CCX_TRY(r->store.alloc(&r->feats_t, (size_t)r->max_chunks * FB_MELS * T, true));
+  CCX_TRY(r->store.alloc(&r->fmean, (size_t)r->max_chunks * FB_MELS, true));
+  CCX_TRY(r->store.alloc(&r->pooled, (size_t)r->max_masks * 5120, true));
+  CCX_TRY(r->store.alloc(&r->mask_chunk_dev, (size_t)r->max_masks, true));
   StageDims d[RN_STAGES];
   stage_dims(T, d);
   for (int s = 0; s < RN_STAGES; s++) {
     // + slack: the strided views read up to two padded rows and one K tile past the last (dropped) row
     r->act_elems[s] = (size_t)r->max_chunks * (d[s].H + 2) * d[s].Wp * d[s].C + 4 * d[s].Wp * d[s].C + 1024;
-    for (int k = 0; k < 3; k++) RTRY(ralloc(r, &r->act[s][k], r->act_elems[s]));
+    for (int k = 0; k < 3; k++) CCX_TRY(r->store.alloc(&r->act[s][k], r->act_elems[s], true));
   }
   r->finalized = true;
   return CCX_OK;
@@ -676,14 +628,14 @@ int ccx_resnet_embed(ccx_resnet* r, const float* wav_dev, int64_t stride, int n_
       } else {  // first block of a stage: x is still in the previous stage's layout
         tbuf = r->act[s][0]; ybuf = r->act[s][1]; scbuf = r->act[s][2];
       }
-      RTRY(run_conv(r, blk.c1, EPI_BF16_RELU, x, d[xs], tbuf, d[s], nullptr, n_chunks, st));
+      CCX_TRY(run_conv(r, blk.c1, EPI_BF16_RELU, x, d[xs], tbuf, d[s], nullptr, n_chunks, st));
       const bf16_t* resid = x;
       if (blk.has_sc) {
         CCX_REQUIRE(ctx, scbuf != nullptr, "resnet: shortcut convolution inside a stage");
-        RTRY(run_conv(r, blk.sc, EPI_BF16, x, d[xs], scbuf, d[s], nullptr, n_chunks, st));
+        CCX_TRY(run_conv(r, blk.sc, EPI_BF16, x, d[xs], scbuf, d[s], nullptr, n_chunks, st));
         resid = scbuf;
       }
-      RTRY(run_conv(r, blk.c2, EPI_BF16_ADD_RELU, tbuf, d[s], ybuf, d[s], resid, n_chunks, st));
+      CCX_TRY(run_conv(r, blk.c2, EPI_BF16_ADD_RELU, tbuf, d[s], ybuf, d[s], resid, n_chunks, st));
       x = ybuf; xs = s;
       cur = (int)(ybuf == r->act[s][0] ? 0 : (ybuf == r->act[s][1] ? 1 : 2));
     }

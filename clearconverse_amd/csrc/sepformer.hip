@@ -10,13 +10,13 @@
 // nothing) on the shared bf16 MFMA GEMM (gemm_bf16.hip).  Sequences (chunks for the segment model,
 // one chunk-mean sequence per utterance for the memory model) are described by a (start, len)
 // table consumed by the attention / global-norm kernels.
-#include <map>
 #include <math.h>
 #include "../../include/ccx.h"
 #include "ccx_common.h"
 #include "elementwise.h"
 #include <type_traits>
 #include "gemm_bf16.h"
+#include "model_store.h"
 
 namespace {
 
@@ -708,11 +708,6 @@ __global__ __launch_bounds__(256) void sep_decoder_kernel(const float* __restric
   if (lane < 8 && t0 + lane < out_stride) dst[lane] = (t0 + lane < T) ? res : make_float2(0.f, 0.f);
 }
 
-struct HostT {
-  std::vector<float> data;
-  std::vector<int64_t> shape;
-};
-
 struct SepLayer {
   float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *bqkv, *bo, *b1, *b2;
   bf16_t *Wqkv, *Wo, *W1, *W2;
@@ -722,14 +717,6 @@ struct SepBlock {
   float *lnf_g, *lnf_b, *gln_g, *gln_b;
 };
 
-inline bf16_t h2bf(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
-
 }  // namespace
 
 struct ccx_sepformer {
@@ -737,8 +724,7 @@ struct ccx_sepformer {
   ccx_sepformer_dims d{};
   int max_tokens = 0, max_utts = 0;
   bool finalized = false;
-  std::map<std::string, HostT> staged;
-  std::vector<void*> allocs;
+  ccx_dev_store store{"sepformer"};
   float *w_enc = nullptr, *w_dec = nullptr, *prelu = nullptr, *b_fc = nullptr, *pe = nullptr;
   bf16_t* W_fc = nullptr;
   std::vector<SepBlock> seg, mem;
@@ -754,70 +740,29 @@ struct ccx_sepformer {
 
 namespace {
 
-#define STRY(expr)        \
-  do {                    \
-    int _rc = (expr);     \
-    if (_rc) return _rc;  \
-  } while (0)
-
-template <typename T>
-int salloc(ccx_sepformer* s, T** out, size_t count) {
-  void* p = nullptr;
-  const size_t bytes = ccx_align(count * sizeof(T), 256);
-  CCX_HIP(s->ctx, hipMalloc(&p, bytes));
-  CCX_HIP(s->ctx, hipMemset(p, 0, bytes));
-  s->allocs.push_back(p);
-  *out = (T*)p;
-  return CCX_OK;
-}
-int sup_f32(ccx_sepformer* s, float** out, const float* src, size_t n) {
-  STRY(salloc(s, out, n));
-  CCX_HIP(s->ctx, hipMemcpy(*out, src, n * 4, hipMemcpyHostToDevice));
-  return CCX_OK;
-}
-int sup_bf16(ccx_sepformer* s, bf16_t** out, const float* src, size_t n) {
-  std::vector<bf16_t> tmp(n);
-  for (size_t i = 0; i < n; i++) tmp[i] = h2bf(src[i]);
-  STRY(salloc(s, out, n));
-  CCX_HIP(s->ctx, hipMemcpy(*out, tmp.data(), n * 2, hipMemcpyHostToDevice));
-  return CCX_OK;
-}
-int sneed(ccx_sepformer* s, const std::string& name, std::vector<int64_t> shape, const HostT** out) {
-  auto it = s->staged.find(name);
-  if (it == s->staged.end()) return ccx_fail(s->ctx, CCX_ERR_MISSING, "sepformer: tensor '%s' was never set", name.c_str());
-  size_t want = 1, got = it->second.data.size();
-  for (auto v : shape) want *= (size_t)v;
-  if (want != got) return ccx_fail(s->ctx, CCX_ERR_ARG, "sepformer: tensor '%s' has %zu elements, expected %zu", name.c_str(), got, want);
-  *out = &it->second;
-  return CCX_OK;
-}
-#define SNEED(var, name, ...)                                              \
-  const HostT* var = nullptr;                                              \
-  STRY(sneed(s, (name), std::vector<int64_t>{__VA_ARGS__}, &var));
-
 int load_block(ccx_sepformer* s, const std::string& prefix, SepBlock& B) {
   const int D = s->d.d_model, F = s->d.d_ffn;
   B.layers.resize(s->d.n_layers);
   for (int l = 0; l < s->d.n_layers; l++) {
     const std::string p = prefix + ".mdl.layers." + std::to_string(l);
     SepLayer& L = B.layers[l];
-    SNEED(wi, p + ".self_att.att.in_proj_weight", 3 * D, D); SNEED(bi, p + ".self_att.att.in_proj_bias", 3 * D);
-    SNEED(wo, p + ".self_att.att.out_proj.weight", D, D); SNEED(bo, p + ".self_att.att.out_proj.bias", D);
-    SNEED(w1, p + ".pos_ffn.ffn.0.weight", F, D); SNEED(b1, p + ".pos_ffn.ffn.0.bias", F);
-    SNEED(w2, p + ".pos_ffn.ffn.3.weight", D, F); SNEED(b2, p + ".pos_ffn.ffn.3.bias", D);
-    SNEED(g1, p + ".norm1.norm.weight", D); SNEED(be1, p + ".norm1.norm.bias", D);
-    SNEED(g2, p + ".norm2.norm.weight", D); SNEED(be2, p + ".norm2.norm.bias", D);
-    STRY(sup_bf16(s, &L.Wqkv, wi->data.data(), wi->data.size())); STRY(sup_f32(s, &L.bqkv, bi->data.data(), 3 * D));
-    STRY(sup_bf16(s, &L.Wo, wo->data.data(), wo->data.size())); STRY(sup_f32(s, &L.bo, bo->data.data(), D));
-    STRY(sup_bf16(s, &L.W1, w1->data.data(), w1->data.size())); STRY(sup_f32(s, &L.b1, b1->data.data(), F));
-    STRY(sup_bf16(s, &L.W2, w2->data.data(), w2->data.size())); STRY(sup_f32(s, &L.b2, b2->data.data(), D));
-    STRY(sup_f32(s, &L.ln1_g, g1->data.data(), D)); STRY(sup_f32(s, &L.ln1_b, be1->data.data(), D));
-    STRY(sup_f32(s, &L.ln2_g, g2->data.data(), D)); STRY(sup_f32(s, &L.ln2_b, be2->data.data(), D));
+    CCX_NEED(s->store, wi, p + ".self_att.att.in_proj_weight", 3 * D, D); CCX_NEED(s->store, bi, p + ".self_att.att.in_proj_bias", 3 * D);
+    CCX_NEED(s->store, wo, p + ".self_att.att.out_proj.weight", D, D); CCX_NEED(s->store, bo, p + ".self_att.att.out_proj.bias", D);
+    CCX_NEED(s->store, w1, p + ".pos_ffn.ffn.0.weight", F, D); CCX_NEED(s->store, b1, p + ".pos_ffn.ffn.0.bias", F);
+    CCX_NEED(s->store, w2, p + ".pos_ffn.ffn.3.weight", D, F); CCX_NEED(s->store, b2, p + ".pos_ffn.ffn.3.bias", D);
+    CCX_NEED(s->store, g1, p + ".norm1.norm.weight", D); CCX_NEED(s->store, be1, p + ".norm1.norm.bias", D);
+    CCX_NEED(s->store, g2, p + ".norm2.norm.weight", D); CCX_NEED(s->store, be2, p + ".norm2.norm.bias", D);
+    CCX_TRY(s->store.upload_bf16(&L.Wqkv, wi->data)); CCX_TRY(s->store.upload(&L.bqkv, bi->data.data(), 3 * D));
+    CCX_TRY(s->store.upload_bf16(&L.Wo, wo->data)); CCX_TRY(s->store.upload(&L.bo, bo->data.data(), D));
+    CCX_TRY(s->store.upload_bf16(&L.W1, w1->data)); CCX_TRY(s->store.upload(&L.b1, b1->data.data(), F));
+    CCX_TRY(s->store.upload_bf16(&L.W2, w2->data)); CCX_TRY(s->store.upload(&L.b2, b2->data.data(), D));
+    CCX_TRY(s->store.upload(&L.ln1_g, g1->data.data(), D)); CCX_TRY(s->store.upload(&L.ln1_b, be1->data.data(), D));
+    CCX_TRY(s->store.upload(&L.ln2_g, g2->data.data(), D)); CCX_TRY(s->store.upload(&L.ln2_b, be2->data.data(), D));
   }
-  SNEED(fg, prefix + ".mdl.norm.norm.weight", D); SNEED(fb, prefix + ".mdl.norm.norm.bias", D);
-  SNEED(gg, prefix + ".norm.weight", D); SNEED(gb, prefix + ".norm.bias", D);
-  STRY(sup_f32(s, &B.lnf_g, fg->data.data(), D)); STRY(sup_f32(s, &B.lnf_b, fb->data.data(), D));
-  STRY(sup_f32(s, &B.gln_g, gg->data.data(), D)); STRY(sup_f32(s, &B.gln_b, gb->data.data(), D));
+  CCX_NEED(s->store, fg, prefix + ".mdl.norm.norm.weight", D); CCX_NEED(s->store, fb, prefix + ".mdl.norm.norm.bias", D);
+  CCX_NEED(s->store, gg, prefix + ".norm.weight", D); CCX_NEED(s->store, gb, prefix + ".norm.bias", D);
+  CCX_TRY(s->store.upload(&B.lnf_g, fg->data.data(), D)); CCX_TRY(s->store.upload(&B.lnf_b, fb->data.data(), D));
+  CCX_TRY(s->store.upload(&B.gln_g, gg->data.data(), D)); CCX_TRY(s->store.upload(&B.gln_b, gb->data.data(), D));
   return CCX_OK;
 }
 
@@ -845,10 +790,10 @@ int run_block(ccx_sepformer* s, const SepBlock& B, const float* x, const float* 
       }
       CCX_CHECK_LAUNCH(ctx);
     } else {
-    STRY(ccx_launch_layernorm(ctx, h, D, L.ln1_g, L.ln1_b, s->xn, nullptr, D, n_tok, D, 1e-6f, st));
+    CCX_TRY(ccx_launch_layernorm(ctx, h, D, L.ln1_g, L.ln1_b, s->xn, nullptr, D, n_tok, D, 1e-6f, st));
     memset(&p, 0, sizeof(p));
     p.A = s->xn; p.lda = D; p.W = L.Wqkv; p.ldw = D; p.M = n_tok; p.N = 3 * D; p.K = D; p.bias = L.bqkv; p.out = s->qkv; p.ldo = 3 * D;
-    STRY(ccx_launch_gemm(ctx, EPI_BF16, p, st));
+    CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16, p, st));
     {
       ccx_prof_scope ps(ctx, st, "sep_attention_kernel", 0.0, 0.0);
       hipLaunchKernelGGL(sep_attention_kernel, dim3(n_seq, s->d.n_head / 4), dim3(256), 0, st, s->qkv, seq_start, seq_len, s->att,
@@ -857,7 +802,7 @@ int run_block(ccx_sepformer* s, const SepBlock& B, const float* x, const float* 
     CCX_CHECK_LAUNCH(ctx);
     memset(&p, 0, sizeof(p));
     p.A = s->att; p.lda = D; p.W = L.Wo; p.ldw = D; p.M = n_tok; p.N = D; p.K = D; p.bias = L.bo; p.out = h; p.ldo = D; p.resid = h; p.ldr = D;
-    STRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, st));
+    CCX_TRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, st));
     }
     {
       // LayerNorm 2 + Linear-ReLU-Linear + residual in one kernel (see sep_ffn_kernel)
@@ -888,7 +833,7 @@ int ccx_sepformer_create(ccx_ctx* ctx, const ccx_sepformer_dims* dims, int max_t
   CCX_REQUIRE(ctx, d.d_ffn % 128 == 0 && d.d_ffn <= 1024 && d.segment >= 16 && d.n_layers >= 1 && d.n_blocks >= 1, "sepformer: bad dims");
   CCX_REQUIRE(ctx, max_tokens >= d.segment && max_utts >= 1, "sepformer: capacity too small");
   ccx_sepformer* s = new ccx_sepformer();
-  s->ctx = ctx; s->d = d;
+  s->ctx = ctx; s->store.ctx = ctx; s->d = d;
   s->max_tokens = ccx_cdiv(max_tokens, d.segment) * d.segment;
   s->max_utts = max_utts;
   *out = s;
@@ -897,7 +842,7 @@ int ccx_sepformer_create(ccx_ctx* ctx, const ccx_sepformer_dims* dims, int max_t
 
 void ccx_sepformer_destroy(ccx_sepformer* s) {
   if (!s) return;
-  for (void* p : s->allocs) hipFree(p);
+  s->store.free_all();
   delete s;
 }
 
@@ -907,11 +852,7 @@ int ccx_sepformer_set_tensor(ccx_sepformer* s, const char* name, const float* da
   const std::string nm(name);
   CCX_REQUIRE(s->ctx, nm.rfind("encoder.", 0) == 0 || nm.rfind("decoder.", 0) == 0 || nm.rfind("masknet.", 0) == 0,
               "sepformer: unknown tensor name '%s'", name);
-  HostT t;
-  t.data.resize((size_t)numel);
-  CCX_HIP(s->ctx, hipMemcpy(t.data.data(), data, (size_t)numel * 4, hipMemcpyDefault));
-  s->staged[nm] = std::move(t);
-  return CCX_OK;
+  return s->store.stage(name, data, numel);
 }
 
 int ccx_sepformer_finalize(ccx_sepformer* s) {
@@ -920,24 +861,24 @@ int ccx_sepformer_finalize(ccx_sepformer* s) {
   const ccx_sepformer_dims& d = s->d;
   const int D = d.d_model, F = d.d_ffn, N = d.n_filters;
   {
-    SNEED(we, "encoder.conv1d.weight", N, 1, d.kernel);
-    SNEED(wd, "decoder.weight", N, 1, d.kernel);
-    SNEED(pr, "masknet.model.output_fc.0.weight", 1);
-    SNEED(wf, "masknet.model.output_fc.1.weight", N * d.n_spk, D, 1);
-    SNEED(bf, "masknet.model.output_fc.1.bias", N * d.n_spk);
-    STRY(sup_f32(s, &s->w_enc, we->data.data(), we->data.size()));
-    STRY(sup_f32(s, &s->w_dec, wd->data.data(), wd->data.size()));
-    STRY(sup_f32(s, &s->prelu, pr->data.data(), 1));
-    STRY(sup_bf16(s, &s->W_fc, wf->data.data(), wf->data.size()));
-    STRY(sup_f32(s, &s->b_fc, bf->data.data(), bf->data.size()));
+    CCX_NEED(s->store, we, "encoder.conv1d.weight", N, 1, d.kernel);
+    CCX_NEED(s->store, wd, "decoder.weight", N, 1, d.kernel);
+    CCX_NEED(s->store, pr, "masknet.model.output_fc.0.weight", 1);
+    CCX_NEED(s->store, wf, "masknet.model.output_fc.1.weight", N * d.n_spk, D, 1);
+    CCX_NEED(s->store, bf, "masknet.model.output_fc.1.bias", N * d.n_spk);
+    CCX_TRY(s->store.upload(&s->w_enc, we->data));
+    CCX_TRY(s->store.upload(&s->w_dec, wd->data));
+    CCX_TRY(s->store.upload(&s->prelu, pr->data.data(), 1));
+    CCX_TRY(s->store.upload_bf16(&s->W_fc, wf->data));
+    CCX_TRY(s->store.upload(&s->b_fc, bf->data));
   }
   s->seg.resize(d.n_blocks);
   s->mem.resize(d.n_blocks > 0 ? d.n_blocks - 1 : 0);
   for (int i = 0; i < d.n_blocks; i++) {
-    STRY(load_block(s, "masknet.model.seg_model." + std::to_string(i), s->seg[i]));
-    if (i < d.n_blocks - 1) STRY(load_block(s, "masknet.model.mem_model." + std::to_string(i), s->mem[i]));
+    CCX_TRY(load_block(s, "masknet.model.seg_model." + std::to_string(i), s->seg[i]));
+    if (i < d.n_blocks - 1) CCX_TRY(load_block(s, "masknet.model.mem_model." + std::to_string(i), s->mem[i]));
   }
-  s->staged.clear();
+  s->store.staged.clear();
   // positional encoding table (interleaved sin/cos), long enough for a chunk and for the longest memory sequence
   const int max_chunks = s->max_tokens / d.segment;
   s->pe_len = d.segment > max_chunks ? d.segment : max_chunks;
@@ -949,20 +890,20 @@ int ccx_sepformer_finalize(ccx_sepformer* s) {
         pe[(size_t)p * D + i] = sinf((float)p * den);
         pe[(size_t)p * D + i + 1] = cosf((float)p * den);
       }
-    STRY(sup_f32(s, &s->pe, pe.data(), pe.size()));
+    CCX_TRY(s->store.upload(&s->pe, pe));
   }
   const size_t T = (size_t)s->max_tokens;
-  STRY(salloc(s, &s->feats, T * D)); STRY(salloc(s, &s->x, T * D)); STRY(salloc(s, &s->xin, T * D)); STRY(salloc(s, &s->h, T * D));
-  STRY(salloc(s, &s->fc, T * 2 * D)); STRY(salloc(s, &s->xn, T * D)); STRY(salloc(s, &s->qkv, T * 3 * D));
-  STRY(salloc(s, &s->att, T * D));
-  STRY(salloc(s, &s->memx, (size_t)max_chunks * D)); STRY(salloc(s, &s->memxin, (size_t)max_chunks * D));
-  STRY(salloc(s, &s->memh, (size_t)max_chunks * D)); STRY(salloc(s, &s->hc, (size_t)max_chunks * D));
-  STRY(salloc(s, &s->tok_utt, T)); STRY(salloc(s, &s->tok_pos, T)); STRY(salloc(s, &s->tok_chunk, T)); STRY(salloc(s, &s->tok_cpos, T));
-  STRY(salloc(s, &s->chunk_start, (size_t)max_chunks)); STRY(salloc(s, &s->chunk_len, (size_t)max_chunks));
-  STRY(salloc(s, &s->mem_utt, (size_t)max_chunks)); STRY(salloc(s, &s->mem_pos, (size_t)max_chunks));
+  CCX_TRY(s->store.alloc(&s->feats, T * D, true)); CCX_TRY(s->store.alloc(&s->x, T * D, true)); CCX_TRY(s->store.alloc(&s->xin, T * D, true)); CCX_TRY(s->store.alloc(&s->h, T * D, true));
+  CCX_TRY(s->store.alloc(&s->fc, T * 2 * D, true)); CCX_TRY(s->store.alloc(&s->xn, T * D, true)); CCX_TRY(s->store.alloc(&s->qkv, T * 3 * D, true));
+  CCX_TRY(s->store.alloc(&s->att, T * D, true));
+  CCX_TRY(s->store.alloc(&s->memx, (size_t)max_chunks * D, true)); CCX_TRY(s->store.alloc(&s->memxin, (size_t)max_chunks * D, true));
+  CCX_TRY(s->store.alloc(&s->memh, (size_t)max_chunks * D, true)); CCX_TRY(s->store.alloc(&s->hc, (size_t)max_chunks * D, true));
+  CCX_TRY(s->store.alloc(&s->tok_utt, T, true)); CCX_TRY(s->store.alloc(&s->tok_pos, T, true)); CCX_TRY(s->store.alloc(&s->tok_chunk, T, true)); CCX_TRY(s->store.alloc(&s->tok_cpos, T, true));
+  CCX_TRY(s->store.alloc(&s->chunk_start, (size_t)max_chunks, true)); CCX_TRY(s->store.alloc(&s->chunk_len, (size_t)max_chunks, true));
+  CCX_TRY(s->store.alloc(&s->mem_utt, (size_t)max_chunks, true)); CCX_TRY(s->store.alloc(&s->mem_pos, (size_t)max_chunks, true));
   const size_t U = (size_t)s->max_utts;
-  STRY(salloc(s, &s->utt_L, U)); STRY(salloc(s, &s->utt_T, U)); STRY(salloc(s, &s->utt_tok0, U)); STRY(salloc(s, &s->utt_chunk0, U));
-  STRY(salloc(s, &s->utt_nchunk, U));
+  CCX_TRY(s->store.alloc(&s->utt_L, U, true)); CCX_TRY(s->store.alloc(&s->utt_T, U, true)); CCX_TRY(s->store.alloc(&s->utt_tok0, U, true)); CCX_TRY(s->store.alloc(&s->utt_chunk0, U, true));
+  CCX_TRY(s->store.alloc(&s->utt_nchunk, U, true));
   s->finalized = true;
   return CCX_OK;
 }
@@ -1014,14 +955,14 @@ int ccx_sepformer_separate(ccx_sepformer* s, const float* mix, int64_t stride, c
   const float* cur = s->feats;
   const float* hc = nullptr;
   for (int i = 0; i < d.n_blocks; i++) {
-    STRY(run_block(s, s->seg[i], cur, hc, s->tok_chunk, s->tok_cpos, s->chunk_start, s->chunk_len, n_tok, n_chunk, seg, s->xin, s->h,
+    CCX_TRY(run_block(s, s->seg[i], cur, hc, s->tok_chunk, s->tok_cpos, s->chunk_start, s->chunk_len, n_tok, n_chunk, seg, s->xin, s->h,
                    s->x, st));
     cur = s->x;
     if (i < d.n_blocks - 1) {
       hipLaunchKernelGGL(sep_chunk_mean_kernel, dim3(n_chunk), dim3(128), 0, st, s->x, s->memx, seg);
       CCX_CHECK_LAUNCH(ctx);
       // memory transformer: one sequence per utterance over its chunk means
-      STRY(run_block(s, s->mem[i], s->memx, nullptr, s->mem_utt, s->mem_pos, s->utt_chunk0, s->utt_nchunk, n_chunk, B, max_nchunk, s->memxin,
+      CCX_TRY(run_block(s, s->mem[i], s->memx, nullptr, s->mem_utt, s->mem_pos, s->utt_chunk0, s->utt_nchunk, n_chunk, B, max_nchunk, s->memxin,
                      s->memh, s->hc, st));
       hc = s->hc;
     }
@@ -1031,7 +972,7 @@ int ccx_sepformer_separate(ccx_sepformer* s, const float* mix, int64_t stride, c
   GemmParams p;
   memset(&p, 0, sizeof(p));
   p.A = s->xn; p.lda = D; p.W = s->W_fc; p.ldw = D; p.M = n_tok; p.N = 2 * D; p.K = D; p.bias = s->b_fc; p.out = s->fc; p.ldo = 2 * D;
-  STRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
   hipLaunchKernelGGL(sep_decoder_kernel, dim3(ccx_cdiv(ccx_cdiv((int)stride, 8), 4), B), dim3(256), 0, st, s->feats, s->fc, s->utt_tok0, s->utt_L,
                      s->utt_T, s->w_dec, out, (long)stride, B);
   CCX_CHECK_LAUNCH(ctx);

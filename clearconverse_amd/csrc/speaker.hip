@@ -12,11 +12,11 @@
 // all crops: a k-tap conv over channel-last rows is a GEMM whose A matrix is a strided VIEW of the
 // activations (row m = k consecutive frames, lda = channels), dilated taps are accumulated GEMMs.
 // Rows whose window crosses a crop end compute garbage that later stages never read.
-#include <map>
 #include <math.h>
 #include "../../include/ccx.h"
 #include "ccx_common.h"
 #include "gemm_bf16.h"
+#include "model_store.h"
 
 namespace {
 
@@ -463,16 +463,6 @@ __global__ void seg_activation_kernel(const float* __restrict__ logits, int ld, 
   }
 }
 
-struct HostT { std::vector<float> data; };
-
-inline bf16_t h2bf(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
-
 struct SincNetW {
   float *nw, *nb, *filt_sum, *n0g, *n0b, *n1g, *n1b, *n2g, *n2b, *b1, *b2;
   bf16_t* bfrag;    // sinc filters as MFMA B fragments [9 steps][5 tiles][hi|lo][64 lanes][8]
@@ -495,8 +485,7 @@ struct ccx_speaker {
   int max_crops = 0;
   long max_samples = 0;
   bool finalized = false;
-  std::map<std::string, HostT> staged;
-  std::vector<void*> allocs;
+  ccx_dev_store store{"speaker"};
   SincNetW sn{};
   // x-vector
   bf16_t* Wt[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // TDNN weights, tap-major [taps][N][Kpad]
@@ -519,46 +508,6 @@ struct ccx_speaker {
 
 namespace {
 
-#define PTRY(expr)        \
-  do {                    \
-    int _rc = (expr);     \
-    if (_rc) return _rc;  \
-  } while (0)
-
-template <typename T>
-int palloc(ccx_speaker* s, T** out, size_t count) {
-  void* p = nullptr;
-  const size_t bytes = ccx_align(count * sizeof(T), 256);
-  CCX_HIP(s->ctx, hipMalloc(&p, bytes));
-  CCX_HIP(s->ctx, hipMemset(p, 0, bytes));
-  s->allocs.push_back(p);
-  *out = (T*)p;
-  return CCX_OK;
-}
-int pup_f32(ccx_speaker* s, float** out, const float* src, size_t n) {
-  PTRY(palloc(s, out, n));
-  CCX_HIP(s->ctx, hipMemcpy(*out, src, n * 4, hipMemcpyHostToDevice));
-  return CCX_OK;
-}
-int pup_bf16(ccx_speaker* s, bf16_t** out, const std::vector<float>& src) {
-  std::vector<bf16_t> tmp(src.size());
-  for (size_t i = 0; i < src.size(); i++) tmp[i] = h2bf(src[i]);
-  PTRY(palloc(s, out, src.size()));
-  CCX_HIP(s->ctx, hipMemcpy(*out, tmp.data(), tmp.size() * 2, hipMemcpyHostToDevice));
-  return CCX_OK;
-}
-int pneed(ccx_speaker* s, const std::string& name, size_t numel, const HostT** out) {
-  auto it = s->staged.find(name);
-  if (it == s->staged.end()) return ccx_fail(s->ctx, CCX_ERR_MISSING, "speaker: tensor '%s' was never set", name.c_str());
-  if (it->second.data.size() != numel)
-    return ccx_fail(s->ctx, CCX_ERR_ARG, "speaker: tensor '%s' has %zu elements, expected %zu", name.c_str(), it->second.data.size(), numel);
-  *out = &it->second;
-  return CCX_OK;
-}
-#define PNEED(var, name, numel) \
-  const HostT* var = nullptr;   \
-  PTRY(pneed(s, (name), (size_t)(numel), &var));
-
 // Conv1d weight [O][I][k] -> GEMM weight [O][Kpad], column tap*Ipad + c
 std::vector<float> conv_w(const std::vector<float>& w, int O, int I, int k, int Ipad, int Kpad) {
   std::vector<float> r((size_t)O * Kpad, 0.f);
@@ -577,13 +526,13 @@ std::vector<float> conv_tap(const std::vector<float>& w, int O, int I, int k, in
 
 int load_sincnet(ccx_speaker* s, const std::string& pre) {
   SincNetW& n = s->sn;
-  PNEED(nw, pre + "wav_norm1d.weight", 1); PNEED(nb, pre + "wav_norm1d.bias", 1);
-  PNEED(fl, pre + "conv1d.0.filters", SN_F * SN_K);
-  PNEED(w1, pre + "conv1d.1.weight", 60 * 80 * 5); PNEED(b1, pre + "conv1d.1.bias", 60);
-  PNEED(w2, pre + "conv1d.2.weight", 60 * 60 * 5); PNEED(b2, pre + "conv1d.2.bias", 60);
-  PNEED(g0, pre + "norm1d.0.weight", 80); PNEED(be0, pre + "norm1d.0.bias", 80);
-  PNEED(g1, pre + "norm1d.1.weight", 60); PNEED(be1, pre + "norm1d.1.bias", 60);
-  PNEED(g2, pre + "norm1d.2.weight", 60); PNEED(be2, pre + "norm1d.2.bias", 60);
+  CCX_NEED(s->store, nw, pre + "wav_norm1d.weight", 1); CCX_NEED(s->store, nb, pre + "wav_norm1d.bias", 1);
+  CCX_NEED(s->store, fl, pre + "conv1d.0.filters", SN_F * SN_K);
+  CCX_NEED(s->store, w1, pre + "conv1d.1.weight", 60 * 80 * 5); CCX_NEED(s->store, b1, pre + "conv1d.1.bias", 60);
+  CCX_NEED(s->store, w2, pre + "conv1d.2.weight", 60 * 60 * 5); CCX_NEED(s->store, b2, pre + "conv1d.2.bias", 60);
+  CCX_NEED(s->store, g0, pre + "norm1d.0.weight", 80); CCX_NEED(s->store, be0, pre + "norm1d.0.bias", 80);
+  CCX_NEED(s->store, g1, pre + "norm1d.1.weight", 60); CCX_NEED(s->store, be1, pre + "norm1d.1.bias", 60);
+  CCX_NEED(s->store, g2, pre + "norm1d.2.weight", 60); CCX_NEED(s->store, be2, pre + "norm1d.2.bias", 60);
   std::vector<float> fs(SN_F, 0.f), frag((size_t)SM_STEPS * 5 * 2 * 64 * 8, 0.f);
   for (int f = 0; f < SN_F; f++)
     for (int k = 0; k < SN_K; k++) fs[f] += fl->data[(size_t)f * SN_K + k];
@@ -593,18 +542,18 @@ int load_sincnet(ccx_speaker* s, const std::string& pre) {
         for (int e = 0; e < 8; e++) {
           const int kk = 8 * (lane >> 4) + e, tap = 30 * t + kk, f = 16 * nt + (lane & 15);
           const float w = (kk < 30 && tap < SN_K) ? fl->data[(size_t)f * SN_K + tap] : 0.f;
-          const bf16_t hb = h2bf(w);
+          const bf16_t hb = ccx_host_f32_to_bf16(w);
           uint32_t hu = (uint32_t)hb << 16; float hf; memcpy(&hf, &hu, 4);
-          frag[((((size_t)t * 5 + nt) * 2 + 0) * 64 + lane) * 8 + e] = hf;       // exactly representable: pup_bf16 keeps it
-          frag[((((size_t)t * 5 + nt) * 2 + 1) * 64 + lane) * 8 + e] = w - hf;   // rounded to bf16 by pup_bf16
+          frag[((((size_t)t * 5 + nt) * 2 + 0) * 64 + lane) * 8 + e] = hf;       // exactly representable: upload_bf16 keeps it
+          frag[((((size_t)t * 5 + nt) * 2 + 1) * 64 + lane) * 8 + e] = w - hf;   // rounded to bf16 by upload_bf16
         }
-  PTRY(pup_f32(s, &n.nw, nw->data.data(), 1)); PTRY(pup_f32(s, &n.nb, nb->data.data(), 1));
-  PTRY(pup_bf16(s, &n.bfrag, frag)); PTRY(pup_f32(s, &n.filt_sum, fs.data(), fs.size()));
-  PTRY(pup_bf16(s, &n.W1, conv_w(w1->data, 60, 80, 5, 80, 448))); PTRY(pup_f32(s, &n.b1, b1->data.data(), 60));
-  PTRY(pup_bf16(s, &n.W2, conv_w(w2->data, 60, 60, 5, 64, 320))); PTRY(pup_f32(s, &n.b2, b2->data.data(), 60));
-  PTRY(pup_f32(s, &n.n0g, g0->data.data(), 80)); PTRY(pup_f32(s, &n.n0b, be0->data.data(), 80));
-  PTRY(pup_f32(s, &n.n1g, g1->data.data(), 60)); PTRY(pup_f32(s, &n.n1b, be1->data.data(), 60));
-  PTRY(pup_f32(s, &n.n2g, g2->data.data(), 60)); PTRY(pup_f32(s, &n.n2b, be2->data.data(), 60));
+  CCX_TRY(s->store.upload(&n.nw, nw->data.data(), 1)); CCX_TRY(s->store.upload(&n.nb, nb->data.data(), 1));
+  CCX_TRY(s->store.upload_bf16(&n.bfrag, frag)); CCX_TRY(s->store.upload(&n.filt_sum, fs));
+  CCX_TRY(s->store.upload_bf16(&n.W1, conv_w(w1->data, 60, 80, 5, 80, 448))); CCX_TRY(s->store.upload(&n.b1, b1->data.data(), 60));
+  CCX_TRY(s->store.upload_bf16(&n.W2, conv_w(w2->data, 60, 60, 5, 64, 320))); CCX_TRY(s->store.upload(&n.b2, b2->data.data(), 60));
+  CCX_TRY(s->store.upload(&n.n0g, g0->data.data(), 80)); CCX_TRY(s->store.upload(&n.n0b, be0->data.data(), 80));
+  CCX_TRY(s->store.upload(&n.n1g, g1->data.data(), 60)); CCX_TRY(s->store.upload(&n.n1b, be1->data.data(), 60));
+  CCX_TRY(s->store.upload(&n.n2g, g2->data.data(), 60)); CCX_TRY(s->store.upload(&n.n2b, be2->data.data(), 60));
   return CCX_OK;
 }
 
@@ -665,7 +614,7 @@ int run_sincnet(ccx_speaker* s, const float* wav, const Plan& P, hipStream_t st)
   GemmParams p;
   memset(&p, 0, sizeof(p));   // conv1d(80 -> 60, k5) as a GEMM over a strided view: row m = frames m..m+4
   p.A = s->s1n; p.lda = 80; p.W = n.W1; p.ldw = 448; p.M = (int)P.R1; p.N = 60; p.K = 448; p.bias = n.b1; p.out = s->c2; p.ldo = 128;
-  PTRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
   hipLaunchKernelGGL(inorm_partial_kernel<3>, dim3(P.n, INORM_CHUNKS, 1), dim3(256), 0, st, s->c2, 128, s->off1, s->nF2, s->inorm_part, 60, 128);
   CCX_CHECK_LAUNCH(ctx);
   hipLaunchKernelGGL(inorm_apply_kernel<3>, dim3(P.n, INORM_CHUNKS, 1), dim3(256), 0, st, s->c2, 128, s->off1, s->s2n, 64, s->off2, s->nF2,
@@ -673,7 +622,7 @@ int run_sincnet(ccx_speaker* s, const float* wav, const Plan& P, hipStream_t st)
   CCX_CHECK_LAUNCH(ctx);
   memset(&p, 0, sizeof(p));   // conv1d(60 -> 60, k5), channels padded to 64
   p.A = s->s2n; p.lda = 64; p.W = n.W2; p.ldw = 320; p.M = (int)P.R2; p.N = 60; p.K = 320; p.bias = n.b2; p.out = s->c3; p.ldo = 128;
-  PTRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
   hipLaunchKernelGGL(inorm_partial_kernel<3>, dim3(P.n, INORM_CHUNKS, 1), dim3(256), 0, st, s->c3, 128, s->off2, s->nF3, s->inorm_part, 60, 128);
   CCX_CHECK_LAUNCH(ctx);
   hipLaunchKernelGGL(inorm_apply_kernel<3>, dim3(P.n, INORM_CHUNKS, 1), dim3(256), 0, st, s->c3, 128, s->off2, s->s3n, 64, s->off3, s->nF3,
@@ -692,90 +641,86 @@ int ccx_speaker_create(ccx_ctx* ctx, int kind, int n_classes, int powerset, int 
   CCX_REQUIRE(ctx, kind == 0 || (n_classes >= 1 && n_classes <= 64), "ccx_speaker_create: n_classes out of range");
   CCX_REQUIRE(ctx, max_crops >= 1 && max_samples >= 1024, "ccx_speaker_create: capacity too small");
   ccx_speaker* s = new ccx_speaker();
-  s->ctx = ctx; s->kind = kind; s->n_classes = n_classes; s->powerset = powerset; s->max_crops = max_crops; s->max_samples = max_samples;
+  s->ctx = ctx; s->store.ctx = ctx; s->kind = kind; s->n_classes = n_classes; s->powerset = powerset; s->max_crops = max_crops; s->max_samples = max_samples;
   *out = s;
   return CCX_OK;
 }
 
 void ccx_speaker_destroy(ccx_speaker* s) {
   if (!s) return;
-  for (void* p : s->allocs) hipFree(p);
+  s->store.free_all();
   delete s;
 }
 
 int ccx_speaker_set_tensor(ccx_speaker* s, const char* name, const float* data, int64_t numel) {
   if (!s) return CCX_ERR_ARG;
   CCX_REQUIRE(s->ctx, !s->finalized && name && data && numel > 0, "speaker: set_tensor bad arguments");
-  HostT t;
-  t.data.resize((size_t)numel);
-  CCX_HIP(s->ctx, hipMemcpy(t.data.data(), data, (size_t)numel * 4, hipMemcpyDefault));
-  s->staged[std::string(name)] = std::move(t);
-  return CCX_OK;
+  return s->store.stage(name, data, numel);
 }
 
 int ccx_speaker_finalize(ccx_speaker* s) {
   if (!s) return CCX_ERR_ARG;
   CCX_REQUIRE(s->ctx, !s->finalized, "speaker: finalize called twice");
-  PTRY(load_sincnet(s, "sincnet."));
+  CCX_TRY(load_sincnet(s, "sincnet."));
   if (s->kind == 0) {
     const int outc[5] = {512, 512, 512, 512, 1500}, ks[5] = {5, 3, 3, 1, 1}, inc[5] = {60, 512, 512, 512, 512};
     for (int l = 0; l < 5; l++) {
       const std::string p = "tdnns." + std::to_string(l);
-      PNEED(w, p + ".0.weight", (size_t)outc[l] * inc[l] * ks[l]); PNEED(b, p + ".0.bias", outc[l]);
-      PNEED(g, p + ".2.weight", outc[l]); PNEED(be, p + ".2.bias", outc[l]);
-      PNEED(rm, p + ".2.running_mean", outc[l]); PNEED(rv, p + ".2.running_var", outc[l]);
+      CCX_NEED(s->store, w, p + ".0.weight", (int64_t)outc[l] * inc[l] * ks[l]); CCX_NEED(s->store, b, p + ".0.bias", outc[l]);
+      CCX_NEED(s->store, g, p + ".2.weight", outc[l]); CCX_NEED(s->store, be, p + ".2.bias", outc[l]);
+      CCX_NEED(s->store, rm, p + ".2.running_mean", outc[l]); CCX_NEED(s->store, rv, p + ".2.running_var", outc[l]);
       std::vector<float> sc(outc[l]), sh(outc[l]);
       for (int c = 0; c < outc[l]; c++) { sc[c] = g->data[c] / sqrtf(rv->data[c] + 1e-5f); sh[c] = be->data[c] - rm->data[c] * sc[c]; }
-      PTRY(pup_f32(s, &s->bt[l], b->data.data(), outc[l])); PTRY(pup_f32(s, &s->sct[l], sc.data(), outc[l])); PTRY(pup_f32(s, &s->sht[l], sh.data(), outc[l]));
+      CCX_TRY(s->store.upload(&s->bt[l], b->data.data(), outc[l])); CCX_TRY(s->store.upload(&s->sct[l], sc.data(), outc[l])); CCX_TRY(s->store.upload(&s->sht[l], sh.data(), outc[l]));
       std::vector<float> all;
       if (l == 0) all = conv_w(w->data, 512, 60, 5, 64, 320);   // dilation 1: one GEMM over the 5-frame view
       else
         for (int t = 0; t < ks[l]; t++) { auto tap = conv_tap(w->data, outc[l], inc[l], ks[l], t, 512); all.insert(all.end(), tap.begin(), tap.end()); }
-      PTRY(pup_bf16(s, &s->Wt[l], all));
+      CCX_TRY(s->store.upload_bf16(&s->Wt[l], all));
     }
-    PNEED(we, "embedding.weight", 512 * 3000); PNEED(bemb, "embedding.bias", 512);
+    CCX_NEED(s->store, we, "embedding.weight", 512 * 3000); CCX_NEED(s->store, bemb, "embedding.bias", 512);
     std::vector<float> wp((size_t)512 * 3072, 0.f);
     for (int o = 0; o < 512; o++) for (int k = 0; k < 3000; k++) wp[(size_t)o * 3072 + k] = we->data[(size_t)o * 3000 + k];
-    PTRY(pup_bf16(s, &s->Wemb, wp)); PTRY(pup_f32(s, &s->bemb, bemb->data.data(), 512));
+    CCX_TRY(s->store.upload_bf16(&s->Wemb, wp)); CCX_TRY(s->store.upload(&s->bemb, bemb->data.data(), 512));
   } else {
     for (int l = 0; l < 4; l++) {
       const int in = l == 0 ? 60 : 256, inp = l == 0 ? 64 : 256;
       std::vector<float> wih((size_t)1024 * inp, 0.f), bias(1024), whh((size_t)2 * 512 * 128);
       for (int dir = 0; dir < 2; dir++) {
         const std::string sfx = "_l" + std::to_string(l) + (dir ? "_reverse" : "");
-        PNEED(wi, "lstm.weight_ih" + sfx, (size_t)512 * in); PNEED(wh, "lstm.weight_hh" + sfx, 512 * 128);
-        PNEED(bi, "lstm.bias_ih" + sfx, 512); PNEED(bh, "lstm.bias_hh" + sfx, 512);
+        CCX_NEED(s->store, wi, "lstm.weight_ih" + sfx, (int64_t)512 * in); CCX_NEED(s->store, wh, "lstm.weight_hh" + sfx, 512 * 128);
+        CCX_NEED(s->store, bi, "lstm.bias_ih" + sfx, 512); CCX_NEED(s->store, bh, "lstm.bias_hh" + sfx, 512);
         for (int r = 0; r < 512; r++) {
           for (int k = 0; k < in; k++) wih[(size_t)(dir * 512 + r) * inp + k] = wi->data[(size_t)r * in + k];
           bias[dir * 512 + r] = bi->data[r] + bh->data[r];
           for (int k = 0; k < 128; k++) whh[((size_t)dir * 512 + r) * 128 + k] = wh->data[(size_t)r * 128 + k];
         }
       }
-      PTRY(pup_bf16(s, &s->Wih[l], wih)); PTRY(pup_f32(s, &s->bih[l], bias.data(), 1024)); PTRY(pup_bf16(s, &s->whh[l], whh));
+      CCX_TRY(s->store.upload_bf16(&s->Wih[l], wih)); CCX_TRY(s->store.upload(&s->bih[l], bias.data(), 1024)); CCX_TRY(s->store.upload_bf16(&s->whh[l], whh));
     }
-    PNEED(l0w, "linear.0.weight", 128 * 256); PNEED(l0b, "linear.0.bias", 128);
-    PNEED(l1w, "linear.1.weight", 128 * 128); PNEED(l1b, "linear.1.bias", 128);
-    PNEED(cw, "classifier.weight", (size_t)s->n_classes * 128); PNEED(cb, "classifier.bias", s->n_classes);
-    PTRY(pup_bf16(s, &s->Wl0, l0w->data)); PTRY(pup_f32(s, &s->bl0, l0b->data.data(), 128));
-    PTRY(pup_bf16(s, &s->Wl1, l1w->data)); PTRY(pup_f32(s, &s->bl1, l1b->data.data(), 128));
-    PTRY(pup_bf16(s, &s->Wcls, cw->data)); PTRY(pup_f32(s, &s->bcls, cb->data.data(), s->n_classes));
+    CCX_NEED(s->store, l0w, "linear.0.weight", 128 * 256); CCX_NEED(s->store, l0b, "linear.0.bias", 128);
+    CCX_NEED(s->store, l1w, "linear.1.weight", 128 * 128); CCX_NEED(s->store, l1b, "linear.1.bias", 128);
+    CCX_NEED(s->store, cw, "classifier.weight", (int64_t)s->n_classes * 128); CCX_NEED(s->store, cb, "classifier.bias", s->n_classes);
+    CCX_TRY(s->store.upload_bf16(&s->Wl0, l0w->data)); CCX_TRY(s->store.upload(&s->bl0, l0b->data.data(), 128));
+    CCX_TRY(s->store.upload_bf16(&s->Wl1, l1w->data)); CCX_TRY(s->store.upload(&s->bl1, l1b->data.data(), 128));
+    CCX_TRY(s->store.upload_bf16(&s->Wcls, cw->data)); CCX_TRY(s->store.upload(&s->bcls, cb->data.data(), s->n_classes));
   }
-  s->staged.clear();
+  s->store.staged.clear();
   // capacity: pooled sinc frames <= samples / 30
   s->R1cap = s->max_samples / 30 + 8 * (long)s->max_crops;
   const size_t R1 = (size_t)s->R1cap + 16, R2 = R1 / 3 + 16, R3 = R2 / 3 + 16, C = (size_t)s->max_crops;
-  PTRY(palloc(s, &s->ac, C)); PTRY(palloc(s, &s->s1, R1 * 80)); PTRY(palloc(s, &s->s1n, R1 * 80 + 1024));
-  PTRY(palloc(s, &s->c2, R1 * 128)); PTRY(palloc(s, &s->s2n, R2 * 64 + 1024)); PTRY(palloc(s, &s->c3, R2 * 128)); PTRY(palloc(s, &s->s3n, R3 * 64 + 1024));
-  PTRY(palloc(s, &s->inorm_part, (size_t)C * INORM_CHUNKS * 128 * 2));
-  PTRY(palloc(s, &s->crop_off, C)); PTRY(palloc(s, &s->crop_len, C)); PTRY(palloc(s, &s->w_off, C)); PTRY(palloc(s, &s->w_len, C));
-  PTRY(palloc(s, &s->off1, C)); PTRY(palloc(s, &s->off2, C)); PTRY(palloc(s, &s->off3, C));
-  PTRY(palloc(s, &s->nF1, C)); PTRY(palloc(s, &s->nF2, C)); PTRY(palloc(s, &s->nF3, C)); PTRY(palloc(s, &s->nFv, C));
+  CCX_TRY(s->store.alloc(&s->ac, C, true)); CCX_TRY(s->store.alloc(&s->s1, R1 * 80, true)); CCX_TRY(s->store.alloc(&s->s1n, R1 * 80 + 1024, true));
+  CCX_TRY(s->store.alloc(&s->c2, R1 * 128, true)); CCX_TRY(s->store.alloc(&s->s2n, R2 * 64 + 1024, true)); CCX_TRY(s->store.alloc(&s->c3, R2 * 128, true)); CCX_TRY(s->store.alloc(&s->s3n, R3 * 64 + 1024, true));
+  CCX_TRY(s->store.alloc(&s->inorm_part, (size_t)C * INORM_CHUNKS * 128 * 2, true));
+  CCX_TRY(s->store.alloc(&s->crop_off, C, true)); CCX_TRY(s->store.alloc(&s->crop_len, C, true)); CCX_TRY(s->store.alloc(&s->w_off, C, true)); CCX_TRY(s->store.alloc(&s->w_len, C, true));
+  CCX_TRY(s->store.alloc(&s->off1, C, true)); CCX_TRY(s->store.alloc(&s->off2, C, true)); CCX_TRY(s->store.alloc(&s->off3, C, true));
+  CCX_TRY(s->store.alloc(&s->nF1, C, true)); CCX_TRY(s->store.alloc(&s->nF2, C, true)); CCX_TRY(s->store.alloc(&s->nF3, C, true)); CCX_TRY(s->store.alloc(&s->nFv, C, true));
   if (s->kind == 0) {
-    PTRY(palloc(s, &s->a1, (R3 + 16) * 512)); PTRY(palloc(s, &s->a2, (R3 + 16) * 512)); PTRY(palloc(s, &s->acc, (R3 + 16) * 512));
-    PTRY(palloc(s, &s->a5, (R3 + 16) * 1536)); PTRY(palloc(s, &s->pooled, C * 3072 + 1024));
+    CCX_TRY(s->store.alloc(&s->a1, (R3 + 16) * 512, true)); CCX_TRY(s->store.alloc(&s->a2, (R3 + 16) * 512, true)); CCX_TRY(s->store.alloc(&s->acc, (R3 + 16) * 512, true));
+    CCX_TRY(s->store.alloc(&s->a5, (R3 + 16) * 1536, true)); CCX_TRY(s->store.alloc(&s->pooled, C * 3072 + 1024, true));
   } else {
-    PTRY(palloc(s, &s->gx, R3 * 1024)); PTRY(palloc(s, &s->hA, R3 * 256 + 1024)); PTRY(palloc(s, &s->hB, R3 * 256 + 1024));
-    PTRY(palloc(s, &s->logit, R3 * 128));
+    CCX_TRY(s->store.alloc(&s->gx, R3 * 1024, true)); CCX_TRY(s->store.alloc(&s->hA, R3 * 256 + 1024, true)); CCX_TRY(s->store.alloc(&s->hB, R3 * 256 + 1024, true));
+    CCX_TRY(s->store.alloc(&s->logit, R3 * 128, true));
   }
   s->finalized = true;
   return CCX_OK;
@@ -790,16 +735,16 @@ int ccx_speaker_embed(ccx_speaker* s, const float* wav, const int64_t* offsets, 
   CCX_REQUIRE(ctx, s->finalized && s->kind == 0 && wav && offsets && n_samples && out && n >= 1 && n <= s->max_crops, "speaker_embed: bad arguments (n=%d, max %d)", n, s->max_crops);
   Plan& P = s->plan_ring[s->plan_slot++ & 3];
   P = Plan();
-  PTRY(make_plan(s, n_samples, offsets, n, P));
-  PTRY(upload_plan(s, P, st));
-  PTRY(run_sincnet(s, wav, P, st));
+  CCX_TRY(make_plan(s, n_samples, offsets, n, P));
+  CCX_TRY(upload_plan(s, P, st));
+  CCX_TRY(run_sincnet(s, wav, P, st));
   const int R3 = (int)P.R3;
   GemmParams p;
   // tdnn 0: k5 d1 over the 5-frame view of s3n
   memset(&p, 0, sizeof(p));
   p.A = s->s3n; p.lda = 64; p.W = s->Wt[0]; p.ldw = 320; p.M = R3; p.N = 512; p.K = 320; p.bias = s->bt[0]; p.out = s->a1; p.ldo = 512;
   p.scale = s->sct[0]; p.shift = s->sht[0]; p.slope = 0.01f;
-  PTRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
   // tdnn 1 (d2) and 2 (d3): three accumulated taps each
   bf16_t* src = s->a1; bf16_t* dst = s->a2;
   for (int l = 1; l <= 2; l++) {
@@ -807,11 +752,11 @@ int ccx_speaker_embed(ccx_speaker* s, const float* wav, const int64_t* offsets, 
     for (int tap = 0; tap < 3; tap++) {
       memset(&p, 0, sizeof(p));
       p.A = src + (long)tap * dil * 512; p.lda = 512; p.W = s->Wt[l] + (long)tap * 512 * 512; p.ldw = 512; p.M = R3; p.N = 512; p.K = 512;
-      if (tap == 0) { p.bias = s->bt[l]; p.out = s->acc; p.ldo = 512; PTRY(ccx_launch_gemm(ctx, EPI_F32, p, st)); }
-      else if (tap == 1) { p.out = s->acc; p.ldo = 512; p.resid = s->acc; p.ldr = 512; PTRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, st)); }
+      if (tap == 0) { p.bias = s->bt[l]; p.out = s->acc; p.ldo = 512; CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st)); }
+      else if (tap == 1) { p.out = s->acc; p.ldo = 512; p.resid = s->acc; p.ldr = 512; CCX_TRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, st)); }
       else {
         p.out = dst; p.ldo = 512; p.resid = s->acc; p.ldr = 512; p.scale = s->sct[l]; p.shift = s->sht[l]; p.slope = 0.01f;
-        PTRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
+        CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
       }
     }
     bf16_t* t = src; src = dst; dst = t;
@@ -820,11 +765,11 @@ int ccx_speaker_embed(ccx_speaker* s, const float* wav, const int64_t* offsets, 
   memset(&p, 0, sizeof(p));
   p.A = src; p.lda = 512; p.W = s->Wt[3]; p.ldw = 512; p.M = R3; p.N = 512; p.K = 512; p.bias = s->bt[3]; p.out = dst; p.ldo = 512;
   p.scale = s->sct[3]; p.shift = s->sht[3]; p.slope = 0.01f;
-  PTRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
   memset(&p, 0, sizeof(p));
   p.A = dst; p.lda = 512; p.W = s->Wt[4]; p.ldw = 512; p.M = R3; p.N = 1500; p.K = 512; p.bias = s->bt[4]; p.out = s->a5; p.ldo = 1536;
   p.scale = s->sct[4]; p.shift = s->sht[4]; p.slope = 0.01f;
-  PTRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
   if (weights) {
     CCX_REQUIRE(ctx, w_offsets && w_lens, "speaker_embed: weights need offsets and lengths");
     std::vector<long> wo(n); std::vector<int> wl(n);
@@ -839,7 +784,7 @@ int ccx_speaker_embed(ccx_speaker* s, const float* wav, const int64_t* offsets, 
   // embedding Linear(3000 -> 512); out rows are 512 wide
   memset(&p, 0, sizeof(p));
   p.A = s->pooled; p.lda = 3072; p.W = s->Wemb; p.ldw = 3072; p.M = n; p.N = 512; p.K = 3072; p.bias = s->bemb; p.out = out; p.ldo = 512;
-  PTRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
   return CCX_OK;
 }
 
@@ -853,11 +798,11 @@ int ccx_speaker_segment(ccx_speaker* s, const float* wav, const int64_t* offsets
   CCX_REQUIRE(ctx, s->finalized && s->kind == 1 && wav && offsets && n_samples && out && frames_out && n >= 1 && n <= s->max_crops, "speaker_segment: bad arguments");
   Plan& P = s->plan_ring[s->plan_slot++ & 3];
   P = Plan();
-  PTRY(make_plan(s, n_samples, offsets, n, P));
+  CCX_TRY(make_plan(s, n_samples, offsets, n, P));
   CCX_REQUIRE(ctx, P.R3 <= out_capacity_rows, "speaker_segment: output needs %ld rows, capacity %ld", P.R3, (long)out_capacity_rows);
   for (int i = 0; i < n; i++) frames_out[i] = P.f3[i];
-  PTRY(upload_plan(s, P, st));
-  PTRY(run_sincnet(s, wav, P, st));
+  CCX_TRY(upload_plan(s, P, st));
+  CCX_TRY(run_sincnet(s, wav, P, st));
   const int R3 = (int)P.R3;
   GemmParams p;
   const bf16_t* x = s->s3n;
@@ -866,7 +811,7 @@ int ccx_speaker_segment(ccx_speaker* s, const float* wav, const int64_t* offsets
   for (int l = 0; l < 4; l++) {
     memset(&p, 0, sizeof(p));
     p.A = x; p.lda = ldx; p.W = s->Wih[l]; p.ldw = K; p.M = R3; p.N = 1024; p.K = K; p.bias = s->bih[l]; p.out = s->gx; p.ldo = 1024;
-    PTRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
+    CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
     {
       ccx_prof_scope ps(ctx, st, "lstm_recurrent_kernel", 0.0, 0.0);
       hipLaunchKernelGGL(lstm_recurrent_kernel, dim3(ccx_cdiv(n, LSTM_SEQS), 2), dim3(512), 0, st, s->gx, s->whh[l], s->off3, s->nF3, n, hbuf[l & 1]);
@@ -877,14 +822,14 @@ int ccx_speaker_segment(ccx_speaker* s, const float* wav, const int64_t* offsets
   bf16_t* t0 = hbuf[0];  // layer 3 wrote hbuf[1]; reuse hbuf[0] for the linear outputs ([R3][128] fits in [R3][256])
   memset(&p, 0, sizeof(p));
   p.A = x; p.lda = 256; p.W = s->Wl0; p.ldw = 256; p.M = R3; p.N = 128; p.K = 256; p.bias = s->bl0; p.out = t0; p.ldo = 128; p.slope = 0.01f;
-  PTRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
   bf16_t* t1 = hbuf[1];
   memset(&p, 0, sizeof(p));
   p.A = t0; p.lda = 128; p.W = s->Wl1; p.ldw = 128; p.M = R3; p.N = 128; p.K = 128; p.bias = s->bl1; p.out = t1; p.ldo = 128; p.slope = 0.01f;
-  PTRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16_LRELU_AFFINE, p, st));
   memset(&p, 0, sizeof(p));
   p.A = t1; p.lda = 128; p.W = s->Wcls; p.ldw = 128; p.M = R3; p.N = s->n_classes; p.K = 128; p.bias = s->bcls; p.out = s->logit; p.ldo = 128;
-  PTRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
   hipLaunchKernelGGL(seg_activation_kernel, dim3(ccx_cdiv(R3, 256)), dim3(256), 0, st, s->logit, 128, out, s->n_classes, R3, s->powerset);
   CCX_CHECK_LAUNCH(ctx);
   return CCX_OK;

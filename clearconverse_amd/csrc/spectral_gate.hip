@@ -15,6 +15,7 @@
 #include <math.h>
 #include "../../include/ccx.h"
 #include "ccx_common.h"
+#include "model_store.h"
 
 namespace {
 
@@ -237,7 +238,7 @@ struct ccx_specgate {
   ccx_ctx* ctx = nullptr;
   int max_clips = 0;
   long max_samples = 0, rows = 0;  // rows = frame capacity per clip
-  std::vector<void*> allocs;
+  ccx_dev_store store{"specgate"};
   float2* tw = nullptr; float* win = nullptr; float* ff = nullptr; float* ft = nullptr;
   float *db = nullptr, *tmp = nullptr, *td = nullptr, *thresh = nullptr, *floorv = nullptr;
   float2* X = nullptr;
@@ -247,33 +248,9 @@ struct ccx_specgate {
 };
 
 namespace {
-template <typename T>
-int galloc(ccx_specgate* g, T** out, size_t count) {
-  void* p = nullptr;
-  const size_t bytes = ccx_align(count * sizeof(T), 256);
-  CCX_HIP(g->ctx, hipMalloc(&p, bytes));
-  CCX_HIP(g->ctx, hipMemset(p, 0, bytes));
-  g->allocs.push_back(p);
-  *out = (T*)p;
-  return CCX_OK;
-}
-#define GTRY(expr)        \
-  do {                    \
-    int _rc = (expr);     \
-    if (_rc) return _rc;  \
-  } while (0)
-}  // namespace
 
-extern "C" {
-
-int ccx_specgate_create(ccx_ctx* ctx, int64_t max_samples, int max_clips, int sample_rate, ccx_specgate** out) {
-  if (!ctx) return CCX_ERR_ARG;
-  CCX_REQUIRE(ctx, out && max_clips >= 1 && max_samples >= 1, "ccx_specgate_create: bad arguments");
-  CCX_REQUIRE(ctx, max_samples <= 600000, "specgate: clips longer than one 600000-sample chunk are not supported (hot path feeds <= 30 s)");
-  CCX_REQUIRE(ctx, sample_rate == 16000, "specgate: smoothing widths are built for 16 kHz");
-  ccx_specgate* g = new ccx_specgate();
-  g->ctx = ctx; g->max_clips = max_clips; g->max_samples = max_samples;
-  g->rows = (max_samples + 2 * SG_PAD) / SG_HOP + 2;
+// FFT twiddles, Hann window, smoothing ramps and every workspace of `g`
+int specgate_build(ccx_specgate* g) {
   std::vector<float2> tw(512);
   std::vector<float> win(SG_N), ff(33), ft(7);
   for (int k = 0; k < 512; k++) { const double a = -2.0 * M_PI * k / SG_N; tw[k] = make_float2((float)cos(a), (float)sin(a)); }
@@ -289,23 +266,40 @@ int ccx_specgate_create(ccx_ctx* ctx, int64_t max_samples, int max_clips, int sa
   };
   tri(16, ff.data());
   tri(3, ft.data());
-  GTRY(galloc(g, &g->tw, 512)); GTRY(galloc(g, &g->win, SG_N)); GTRY(galloc(g, &g->ff, 33)); GTRY(galloc(g, &g->ft, 7));
-  CCX_HIP(ctx, hipMemcpy(g->tw, tw.data(), 512 * 8, hipMemcpyHostToDevice));
-  CCX_HIP(ctx, hipMemcpy(g->win, win.data(), SG_N * 4, hipMemcpyHostToDevice));
-  CCX_HIP(ctx, hipMemcpy(g->ff, ff.data(), 33 * 4, hipMemcpyHostToDevice));
-  CCX_HIP(ctx, hipMemcpy(g->ft, ft.data(), 7 * 4, hipMemcpyHostToDevice));
-  const size_t R = (size_t)g->rows * max_clips;
-  GTRY(galloc(g, &g->db, R * SG_LD)); GTRY(galloc(g, &g->tmp, R * SG_LD)); GTRY(galloc(g, &g->X, R * SG_LD));
-  GTRY(galloc(g, &g->td, R * SG_N));
-  GTRY(galloc(g, &g->thresh, (size_t)max_clips * SG_LD)); GTRY(galloc(g, &g->floorv, (size_t)max_clips * SG_LD));
-  GTRY(galloc(g, &g->n_dev, (size_t)max_clips)); GTRY(galloc(g, &g->nf_noise, (size_t)max_clips)); GTRY(galloc(g, &g->nf_sig, (size_t)max_clips));
+  ccx_dev_store& st = g->store;
+  CCX_TRY(st.upload(&g->tw, tw)); CCX_TRY(st.upload(&g->win, win)); CCX_TRY(st.upload(&g->ff, ff)); CCX_TRY(st.upload(&g->ft, ft));
+  const size_t R = (size_t)g->rows * g->max_clips, C = (size_t)g->max_clips;
+  CCX_TRY(st.alloc(&g->db, R * SG_LD, true)); CCX_TRY(st.alloc(&g->tmp, R * SG_LD, true)); CCX_TRY(st.alloc(&g->X, R * SG_LD, true));
+  CCX_TRY(st.alloc(&g->td, R * SG_N, true));
+  CCX_TRY(st.alloc(&g->thresh, C * SG_LD, true)); CCX_TRY(st.alloc(&g->floorv, C * SG_LD, true));
+  CCX_TRY(st.alloc(&g->n_dev, C, true)); CCX_TRY(st.alloc(&g->nf_noise, C, true)); CCX_TRY(st.alloc(&g->nf_sig, C, true));
+  return CCX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ccx_specgate_create(ccx_ctx* ctx, int64_t max_samples, int max_clips, int sample_rate, ccx_specgate** out) {
+  if (!ctx) return CCX_ERR_ARG;
+  CCX_REQUIRE(ctx, out && max_clips >= 1 && max_samples >= 1, "ccx_specgate_create: bad arguments");
+  CCX_REQUIRE(ctx, max_samples <= 600000, "specgate: clips longer than one 600000-sample chunk are not supported (hot path feeds <= 30 s)");
+  CCX_REQUIRE(ctx, sample_rate == 16000, "specgate: smoothing widths are built for 16 kHz");
+  ccx_specgate* g = new ccx_specgate();
+  g->ctx = ctx; g->store.ctx = ctx; g->max_clips = max_clips; g->max_samples = max_samples;
+  g->rows = (max_samples + 2 * SG_PAD) / SG_HOP + 2;
+  const int rc = specgate_build(g);
+  if (rc) {                      // the caller never sees a half-built handle: free it and what it already owns
+    ccx_specgate_destroy(g);
+    return rc;
+  }
   *out = g;
   return CCX_OK;
 }
 
 void ccx_specgate_destroy(ccx_specgate* g) {
   if (!g) return;
-  for (void* p : g->allocs) hipFree(p);
+  g->store.free_all();
   delete g;
 }
 
@@ -380,7 +374,7 @@ int ccx_specgate_reduce_long(ccx_specgate* g, const float* y, int64_t n, float p
   const long rows_c = (CH + 2 * SG_PAD) / SG_HOP + 2;
   CCX_REQUIRE(ctx, nfn <= R && rows_c <= R, "specgate_reduce_long: %ld samples need %ld frame rows, the workspace holds %ld (max_samples x max_clips)", (long)n, nfn > rows_c ? nfn : rows_c, R);
   CCX_REQUIRE(ctx, n < (1L << 31) - CH, "specgate_reduce_long: signal too long");
-  if (!g->origin) GTRY(galloc(g, &g->origin, (size_t)g->max_clips));
+  if (!g->origin) CCX_TRY(g->store.alloc(&g->origin, (size_t)g->max_clips, true));
   // ---- threshold from the noise clip = the signal itself, cut to its first chunk when clip_noise_stationary is on (one "clip" that
   // owns all rows) ----
   const long n_noise = (g->clip_noise && n > CH) ? CH : n;

@@ -19,37 +19,9 @@
 #include "elementwise.h"
 #include "gemm_bf16.h"
 #include "logmel.h"
+#include "model_store.h"
 
 namespace {
-
-struct HostTensor {
-  std::vector<float> data;
-  std::vector<int64_t> shape;
-};
-
-inline bf16_t host_f32_to_bf16(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);  // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
-inline float host_half_to_f32(uint16_t h) {
-  const uint32_t s = (h >> 15) & 1, e = (h >> 10) & 0x1f, m = h & 0x3ff;
-  uint32_t u;
-  if (e == 0) {
-    if (m == 0) u = s << 31;
-    else {
-      int ee = -1; uint32_t mm = m;
-      do { ee++; mm <<= 1; } while (!(mm & 0x400));
-      u = (s << 31) | ((uint32_t)(127 - 15 - ee) << 23) | ((mm & 0x3ff) << 13);
-    }
-  } else if (e == 31) u = (s << 31) | 0x7f800000u | (m << 13);
-  else u = (s << 31) | ((e + 112) << 23) | (m << 13);
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
 
 struct EncLayer {
   float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
@@ -85,10 +57,7 @@ struct ccx_whisper {
   std::atomic<ccx_whisper*> scratch_owner{nullptr};   // (donor) instance whose staged log-mel waits for its encode: a shared group has ONE user between logmel and encode
   hipEvent_t scratch_free = nullptr;      // (donor) recorded at the end of every encode of the group; every log-mel / set_mel of the
                                           // group waits for it, so that users of the shared workspaces are ordered on ANY streams
-  std::map<std::string, HostTensor> staged;
-  std::vector<void*> allocs;
-  char* arena = nullptr;
-  size_t arena_cap = 0, arena_off = 0;
+  ccx_dev_store store{"whisper"};          // staged tensors, the weight arena and every device allocation of the instance
 
   // derived sizes
   int Spad = 0;    // padded audio context (multiple of 128)
@@ -175,40 +144,6 @@ struct ccx_whisper {
 
 namespace {
 
-// Weights and per-step decode buffers are carved from ONE large allocation (bump pointer, in
-// access order): large contiguous mappings keep the decode chain's weight stream on few, large
-// TLB entries and make consecutive kernels touch consecutive addresses.
-template <typename T>
-int dev_alloc(ccx_whisper* w, T** out, size_t count, bool zero) {
-  const size_t bytes = ccx_align(count * sizeof(T), 256);
-  void* p = nullptr;
-  if (w->arena && w->arena_off + bytes <= w->arena_cap) {
-    p = w->arena + w->arena_off;
-    w->arena_off += bytes;
-  } else {
-    CCX_HIP(w->ctx, hipMalloc(&p, bytes));
-    w->allocs.push_back(p);
-  }
-  if (zero) CCX_HIP(w->ctx, hipMemset(p, 0, bytes));
-  *out = (T*)p;
-  return CCX_OK;
-}
-
-int up_f32(ccx_whisper* w, float** out, const float* src, size_t n) {
-  int rc = dev_alloc(w, out, n, false);
-  if (rc) return rc;
-  CCX_HIP(w->ctx, hipMemcpy(*out, src, n * 4, hipMemcpyHostToDevice));
-  return CCX_OK;
-}
-int up_bf16(ccx_whisper* w, bf16_t** out, const float* src, size_t n) {
-  std::vector<bf16_t> tmp(n);
-  for (size_t i = 0; i < n; i++) tmp[i] = host_f32_to_bf16(src[i]);
-  int rc = dev_alloc(w, out, n, false);
-  if (rc) return rc;
-  CCX_HIP(w->ctx, hipMemcpy(*out, tmp.data(), n * 2, hipMemcpyHostToDevice));
-  return CCX_OK;
-}
-
 // Decode-side weights are stored MFMA-fragment-packed for dec_linear_kernel: tile (n/16, k/32) is 64
 // consecutive 16-byte chunks, chunk l = row n0 + (l & 15), columns k0 + 8*(l >> 4) .. +8.
 // Rows are zero padded to a multiple of `row_pad`.
@@ -222,47 +157,13 @@ int up_bf16_packed(ccx_whisper* w, bf16_t** out, const float* src, int N, int K,
         const int n = nt * 16 + (l & 15), k0 = ks * 32 + 8 * (l >> 4);
         bf16_t* dst = &tmp[(((size_t)nt * kst + ks) * 64 + l) * 8];
         if (n < N)
-          for (int j = 0; j < 8; j++) dst[j] = host_f32_to_bf16(src[(size_t)n * K + k0 + j]);
+          for (int j = 0; j < 8; j++) dst[j] = ccx_host_f32_to_bf16(src[(size_t)n * K + k0 + j]);
       }
-  int rc = dev_alloc(w, out, tmp.size(), false);
-  if (rc) return rc;
-  CCX_HIP(w->ctx, hipMemcpy(*out, tmp.data(), tmp.size() * 2, hipMemcpyHostToDevice));
-  return CCX_OK;
+  return w->store.upload(out, tmp);
 }
-
-const HostTensor* find(ccx_whisper* w, const std::string& name) {
-  auto it = w->staged.find(name);
-  return it == w->staged.end() ? nullptr : &it->second;
-}
-
-int need(ccx_whisper* w, const std::string& name, std::vector<int64_t> shape, const HostTensor** out) {
-  const HostTensor* t = find(w, name);
-  if (!t) return ccx_fail(w->ctx, CCX_ERR_MISSING, "whisper: tensor '%s' was never set", name.c_str());
-  if (t->shape != shape) {
-    std::string got, want;
-    for (auto v : t->shape) got += std::to_string(v) + ",";
-    for (auto v : shape) want += std::to_string(v) + ",";
-    return ccx_fail(w->ctx, CCX_ERR_ARG, "whisper: tensor '%s' has shape [%s] expected [%s]", name.c_str(), got.c_str(),
-                    want.c_str());
-  }
-  *out = t;
-  return CCX_OK;
-}
-
-#define NEED(var, name, ...)                                              \
-  const HostTensor* var = nullptr;                                        \
-  {                                                                       \
-    int _rc = need(w, (name), std::vector<int64_t>{__VA_ARGS__}, &var);   \
-    if (_rc) return _rc;                                                  \
-  }
-#define TRY(expr)            \
-  do {                       \
-    int _rc = (expr);        \
-    if (_rc) return _rc;     \
-  } while (0)
 
 // conv weight [out][in][3] -> GEMM weight [out][Kpad] with k = tap*in + c
-std::vector<float> conv_to_gemm(const HostTensor& t, int Kpad) {
+std::vector<float> conv_to_gemm(const ccx_host_tensor& t, int Kpad) {
   const int64_t O = t.shape[0], I = t.shape[1], T = t.shape[2];
   std::vector<float> r((size_t)O * Kpad, 0.f);
   for (int64_t o = 0; o < O; o++)
@@ -272,7 +173,7 @@ std::vector<float> conv_to_gemm(const HostTensor& t, int Kpad) {
 }
 
 int build_logmel_tables(ccx_whisper* w) {
-  NEED(mf, "mel_filters", w->d.n_mels, 201);
+  CCX_NEED(w->store, mf, "mel_filters", w->d.n_mels, 201);
   CCX_REQUIRE(w->ctx, w->d.n_mels == 80, "whisper: only n_mels == 80 is supported (got %d)", w->d.n_mels);
   std::vector<float> c(400 * 208, 0.f), s(400 * 208, 0.f), fb(80 * 208, 0.f);
   std::vector<int> rg(160);
@@ -297,11 +198,10 @@ int build_logmel_tables(ccx_whisper* w) {
     rg[2 * m] = k0; rg[2 * m + 1] = k1;
   }
   float *dc, *ds, *dfb; int* drg;
-  TRY(up_f32(w, &dc, c.data(), c.size()));
-  TRY(up_f32(w, &ds, s.data(), s.size()));
-  TRY(up_f32(w, &dfb, fb.data(), fb.size()));
-  TRY(dev_alloc(w, &drg, 160, false));
-  CCX_HIP(w->ctx, hipMemcpy(drg, rg.data(), 160 * 4, hipMemcpyHostToDevice));
+  CCX_TRY(w->store.upload(&dc, c));
+  CCX_TRY(w->store.upload(&ds, s));
+  CCX_TRY(w->store.upload(&dfb, fb));
+  CCX_TRY(w->store.upload(&drg, rg));
   w->lm.dft_cos = dc; w->lm.dft_sin = ds; w->lm.mel_fb = dfb; w->lm.mel_range = drg;
   return CCX_OK;
 }
@@ -329,6 +229,8 @@ int ccx_whisper_create(ccx_ctx* ctx, const ccx_whisper_dims* dims, int max_batch
   CCX_REQUIRE(ctx, d.n_vocab % 4 == 0 && d.n_vocab <= 13 * 4096, "whisper: n_vocab must be a multiple of 4 and <= 53248");
   ccx_whisper* w = new ccx_whisper();
   w->ctx = ctx;
+  w->store.ctx = ctx;
+  w->store.zero_uploads = false;   // weight blocks get their copy only, no memset each (the workspaces pass zero = true)
   w->d = d;
   w->max_batch = max_batch;
   w->Spad = ccx_cdiv(d.n_audio_ctx, 128) * 128;
@@ -361,7 +263,7 @@ void ccx_whisper_destroy(ccx_whisper* w) {
   for (int i = 0; i < ccx_whisper::kLanePool; i++)
     if (w->lane_pool[i]) hipStreamDestroy(w->lane_pool[i]);
   if (w->poll_host) hipHostFree(w->poll_host);
-  for (void* p : w->allocs) hipFree(p);
+  w->store.free_all();
   delete w;
 }
 
@@ -372,24 +274,7 @@ int ccx_whisper_set_tensor(ccx_whisper* w, const char* name, const void* data, i
   const std::string nm(name);
   const bool known = nm == "mel_filters" || nm.rfind("encoder.", 0) == 0 || nm.rfind("decoder.", 0) == 0;
   CCX_REQUIRE(w->ctx, known, "whisper: unknown tensor name '%s'", name);
-  size_t n = 1;
-  HostTensor t;
-  for (int i = 0; i < ndim; i++) { CCX_REQUIRE(w->ctx, shape[i] > 0, "whisper: '%s' has an empty dim", name); n *= (size_t)shape[i]; t.shape.push_back(shape[i]); }
-  t.data.resize(n);
-  if (dtype == CCX_DTYPE_F32) {
-    CCX_HIP(w->ctx, hipMemcpy(t.data.data(), data, n * 4, hipMemcpyDefault));
-  } else if (dtype == CCX_DTYPE_BF16 || dtype == CCX_DTYPE_F16) {
-    std::vector<uint16_t> tmp(n);
-    CCX_HIP(w->ctx, hipMemcpy(tmp.data(), data, n * 2, hipMemcpyDefault));
-    for (size_t i = 0; i < n; i++) {
-      if (dtype == CCX_DTYPE_BF16) { uint32_t u = (uint32_t)tmp[i] << 16; memcpy(&t.data[i], &u, 4); }
-      else t.data[i] = host_half_to_f32(tmp[i]);
-    }
-  } else {
-    return ccx_fail(w->ctx, CCX_ERR_ARG, "whisper: set_tensor dtype %d unsupported", dtype);
-  }
-  w->staged[nm] = std::move(t);
-  return CCX_OK;
+  return w->store.stage(name, data, dtype, ndim, shape);
 }
 
 int ccx_whisper_set_max_audio(ccx_whisper* w, double seconds) {
@@ -425,7 +310,7 @@ int ccx_whisper_set_rules(ccx_whisper* w, const ccx_decode_rules* r) {
     mask[r->suppress[i]] = 1;
   }
   if (r->no_timestamps >= 0) mask[r->no_timestamps] = 1;  // ApplyTimestampRules bans <|notimestamps|>
-  if (!w->suppress_mask) TRY(dev_alloc(w, &w->suppress_mask, (size_t)V + 4, false));
+  if (!w->suppress_mask) CCX_TRY(w->store.alloc(&w->suppress_mask, (size_t)V + 4, false));
   CCX_HIP(w->ctx, hipMemcpy(w->suppress_mask, mask.data(), (size_t)V + 4, hipMemcpyHostToDevice));
   w->rules = *r;
   w->rules.suppress = nullptr;
@@ -454,71 +339,65 @@ int ccx_whisper_finalize(ccx_whisper* w) {
   CCX_HIP(w->ctx, hipSetDevice(w->ctx->device));
   const ccx_whisper_dims& d = w->d;
   const int D = d.n_audio_state, F = 4 * D, B = w->max_batch, S = d.n_audio_ctx, H = d.n_audio_head;
-  {
-    // arena for all weights (bf16 copies + fp32 vectors/embedding) and the small decode buffers
-    size_t staged = 0;
-    for (auto& kv : w->staged) staged += kv.second.data.size() * 4;
-    w->arena_cap = ccx_align(staged + ((size_t)64 << 20), (size_t)2 << 20);
-    void* base = nullptr;
-    CCX_HIP(w->ctx, hipMalloc(&base, w->arena_cap));
-    w->allocs.push_back(base);
-    w->arena = (char*)base;
-    w->arena_off = 0;
-  }
-  TRY(build_logmel_tables(w));
+  // Weights and per-step decode buffers are carved from ONE large allocation (bump pointer, in
+  // access order): large contiguous mappings keep the decode chain's weight stream on few, large
+  // TLB entries and make consecutive kernels touch consecutive addresses.  The arena holds all weights
+  // (bf16 copies + fp32 vectors/embedding) and the small decode buffers; what does not fit gets a hipMalloc of its own.
+  CCX_TRY(w->store.open_arena((size_t)64 << 20));
+  CCX_TRY(build_logmel_tables(w));
 
   // ---------------- encoder ----------------
   {
-    NEED(c1w, "encoder.conv1.weight", D, d.n_mels, 3);
-    NEED(c1b, "encoder.conv1.bias", D);
-    NEED(c2w, "encoder.conv2.weight", D, D, 3);
-    NEED(c2b, "encoder.conv2.bias", D);
-    NEED(pe, "encoder.positional_embedding", S, D);
-    NEED(lg, "encoder.ln_post.weight", D);
-    NEED(lb, "encoder.ln_post.bias", D);
+    CCX_NEED(w->store, c1w, "encoder.conv1.weight", D, d.n_mels, 3);
+    CCX_NEED(w->store, c1b, "encoder.conv1.bias", D);
+    CCX_NEED(w->store, c2w, "encoder.conv2.weight", D, D, 3);
+    CCX_NEED(w->store, c2b, "encoder.conv2.bias", D);
+    CCX_NEED(w->store, pe, "encoder.positional_embedding", S, D);
+    CCX_NEED(w->store, lg, "encoder.ln_post.weight", D);
+    CCX_NEED(w->store, lb, "encoder.ln_post.bias", D);
     std::vector<float> g1 = conv_to_gemm(*c1w, 256), g2 = conv_to_gemm(*c2w, 3 * D);
-    TRY(up_bf16(w, &w->Wc1, g1.data(), g1.size()));
-    TRY(up_bf16(w, &w->Wc2, g2.data(), g2.size()));
-    TRY(up_f32(w, &w->bc1, c1b->data.data(), D));
-    TRY(up_f32(w, &w->bc2, c2b->data.data(), D));
-    TRY(up_f32(w, &w->enc_pos, pe->data.data(), (size_t)S * D));
-    TRY(up_f32(w, &w->lnp_g, lg->data.data(), D));
-    TRY(up_f32(w, &w->lnp_b, lb->data.data(), D));
+    CCX_TRY(w->store.upload_bf16(&w->Wc1, g1));
+    CCX_TRY(w->store.upload_bf16(&w->Wc2, g2));
+    CCX_TRY(w->store.upload(&w->bc1, c1b->data.data(), D));
+    CCX_TRY(w->store.upload(&w->bc2, c2b->data.data(), D));
+    CCX_TRY(w->store.upload(&w->enc_pos, pe->data.data(), (size_t)S * D));
+    CCX_TRY(w->store.upload(&w->lnp_g, lg->data.data(), D));
+    CCX_TRY(w->store.upload(&w->lnp_b, lb->data.data(), D));
   }
   w->enc.resize(d.n_audio_layer);
   const std::vector<float> zerosD(D, 0.f);
   for (int l = 0; l < d.n_audio_layer; l++) {
     const std::string p = "encoder.blocks." + std::to_string(l) + ".";
     EncLayer& L = w->enc[l];
-    NEED(qw, p + "attn.query.weight", D, D); NEED(qbias, p + "attn.query.bias", D);
-    NEED(kw, p + "attn.key.weight", D, D);
-    NEED(vw, p + "attn.value.weight", D, D); NEED(vbias, p + "attn.value.bias", D);
-    NEED(ow, p + "attn.out.weight", D, D); NEED(obias, p + "attn.out.bias", D);
-    NEED(l1g, p + "attn_ln.weight", D); NEED(l1b, p + "attn_ln.bias", D);
-    NEED(m0w, p + "mlp.0.weight", F, D); NEED(m0b, p + "mlp.0.bias", F);
-    NEED(m2w, p + "mlp.2.weight", D, F); NEED(m2b, p + "mlp.2.bias", D);
-    NEED(l2g, p + "mlp_ln.weight", D); NEED(l2b, p + "mlp_ln.bias", D);
+    CCX_NEED(w->store, qw, p + "attn.query.weight", D, D); CCX_NEED(w->store, qbias, p + "attn.query.bias", D);
+    CCX_NEED(w->store, kw, p + "attn.key.weight", D, D);
+    CCX_NEED(w->store, vw, p + "attn.value.weight", D, D); CCX_NEED(w->store, vbias, p + "attn.value.bias", D);
+    CCX_NEED(w->store, ow, p + "attn.out.weight", D, D); CCX_NEED(w->store, obias, p + "attn.out.bias", D);
+    CCX_NEED(w->store, l1g, p + "attn_ln.weight", D); CCX_NEED(w->store, l1b, p + "attn_ln.bias", D);
+    CCX_NEED(w->store, m0w, p + "mlp.0.weight", F, D); CCX_NEED(w->store, m0b, p + "mlp.0.bias", F);
+    CCX_NEED(w->store, m2w, p + "mlp.2.weight", D, F); CCX_NEED(w->store, m2b, p + "mlp.2.bias", D);
+    CCX_NEED(w->store, l2g, p + "mlp_ln.weight", D); CCX_NEED(w->store, l2b, p + "mlp_ln.bias", D);
     std::vector<float> wqkv = cat_rows({&qw->data, &kw->data, &vw->data});
     std::vector<float> bqkv = cat_rows({&qbias->data, &zerosD, &vbias->data});
-    TRY(up_bf16(w, &L.Wqkv, wqkv.data(), wqkv.size())); TRY(up_f32(w, &L.bqkv, bqkv.data(), bqkv.size()));
-    TRY(up_bf16(w, &L.Wo, ow->data.data(), ow->data.size())); TRY(up_f32(w, &L.bo, obias->data.data(), D));
-    TRY(up_bf16(w, &L.W1, m0w->data.data(), m0w->data.size())); TRY(up_f32(w, &L.b1, m0b->data.data(), F));
-    TRY(up_bf16(w, &L.W2, m2w->data.data(), m2w->data.size())); TRY(up_f32(w, &L.b2, m2b->data.data(), D));
-    TRY(up_f32(w, &L.ln1_g, l1g->data.data(), D)); TRY(up_f32(w, &L.ln1_b, l1b->data.data(), D));
-    TRY(up_f32(w, &L.ln2_g, l2g->data.data(), D)); TRY(up_f32(w, &L.ln2_b, l2b->data.data(), D));
+    CCX_TRY(w->store.upload_bf16(&L.Wqkv, wqkv)); CCX_TRY(w->store.upload(&L.bqkv, bqkv));
+    CCX_TRY(w->store.upload_bf16(&L.Wo, ow->data)); CCX_TRY(w->store.upload(&L.bo, obias->data.data(), D));
+    CCX_TRY(w->store.upload_bf16(&L.W1, m0w->data)); CCX_TRY(w->store.upload(&L.b1, m0b->data.data(), F));
+    CCX_TRY(w->store.upload_bf16(&L.W2, m2w->data)); CCX_TRY(w->store.upload(&L.b2, m2b->data.data(), D));
+    CCX_TRY(w->store.upload(&L.ln1_g, l1g->data.data(), D)); CCX_TRY(w->store.upload(&L.ln1_b, l1b->data.data(), D));
+    CCX_TRY(w->store.upload(&L.ln2_g, l2g->data.data(), D)); CCX_TRY(w->store.upload(&L.ln2_b, l2b->data.data(), D));
   }
 
   // ---------------- decoder ----------------
   {
-    NEED(te, "decoder.token_embedding.weight", d.n_vocab, D);
-    NEED(pe, "decoder.positional_embedding", d.n_text_ctx, D);
-    NEED(lg, "decoder.ln.weight", D);
-    NEED(lb, "decoder.ln.bias", D);
-    TRY(up_f32(w, &w->tok_emb_f32, te->data.data(), te->data.size()));
-    TRY(up_bf16(w, &w->tok_emb_rm, te->data.data(), (size_t)d.n_vocab * D));
-    TRY(up_f32(w, &w->dec_pos, pe->data.data(), pe->data.size()));
-    TRY(up_f32(w, &w->lnd_g, lg->data.data(), D));
-    TRY(up_f32(w, &w->lnd_b, lb->data.data(), D));
+    CCX_NEED(w->store, te, "decoder.token_embedding.weight", d.n_vocab, D);
+    CCX_NEED(w->store, pe, "decoder.positional_embedding", d.n_text_ctx, D);
+    CCX_NEED(w->store, lg, "decoder.ln.weight", D);
+    CCX_NEED(w->store, lb, "decoder.ln.bias", D);
+    CCX_TRY(w->store.upload(&w->tok_emb_f32, te->data));
+    CCX_TRY(w->store.upload_bf16(&w->tok_emb_rm, te->data.data(), (size_t)d.n_vocab * D));
+    CCX_TRY(w->store.upload(&w->dec_pos, pe->data));
+    CCX_TRY(w->store.upload(&w->lnd_g, lg->data.data(), D));
+    CCX_TRY(w->store.upload(&w->lnd_b, lb->data.data(), D));
   }
   w->dec.resize(d.n_text_layer);
   const int Tc = d.n_text_ctx;
@@ -530,41 +409,41 @@ int ccx_whisper_finalize(ccx_whisper* w) {
   for (int l = 0; l < d.n_text_layer; l++) {
     const std::string p = "decoder.blocks." + std::to_string(l) + ".";
     DecLayer& L = w->dec[l];
-    NEED(qw, p + "attn.query.weight", D, D); NEED(qbias, p + "attn.query.bias", D);
-    NEED(kw, p + "attn.key.weight", D, D);
-    NEED(vw, p + "attn.value.weight", D, D); NEED(vbias, p + "attn.value.bias", D);
-    NEED(ow, p + "attn.out.weight", D, D); NEED(obias, p + "attn.out.bias", D);
-    NEED(l1g, p + "attn_ln.weight", D); NEED(l1b, p + "attn_ln.bias", D);
-    NEED(cqw, p + "cross_attn.query.weight", D, D); NEED(cqb, p + "cross_attn.query.bias", D);
-    NEED(ckw, p + "cross_attn.key.weight", D, D);
-    NEED(cvw, p + "cross_attn.value.weight", D, D); NEED(cvb, p + "cross_attn.value.bias", D);
-    NEED(cow, p + "cross_attn.out.weight", D, D); NEED(cob, p + "cross_attn.out.bias", D);
-    NEED(lcg, p + "cross_attn_ln.weight", D); NEED(lcb, p + "cross_attn_ln.bias", D);
-    NEED(m0w, p + "mlp.0.weight", F, D); NEED(m0b, p + "mlp.0.bias", F);
-    NEED(m2w, p + "mlp.2.weight", D, F); NEED(m2b, p + "mlp.2.bias", D);
-    NEED(l2g, p + "mlp_ln.weight", D); NEED(l2b, p + "mlp_ln.bias", D);
+    CCX_NEED(w->store, qw, p + "attn.query.weight", D, D); CCX_NEED(w->store, qbias, p + "attn.query.bias", D);
+    CCX_NEED(w->store, kw, p + "attn.key.weight", D, D);
+    CCX_NEED(w->store, vw, p + "attn.value.weight", D, D); CCX_NEED(w->store, vbias, p + "attn.value.bias", D);
+    CCX_NEED(w->store, ow, p + "attn.out.weight", D, D); CCX_NEED(w->store, obias, p + "attn.out.bias", D);
+    CCX_NEED(w->store, l1g, p + "attn_ln.weight", D); CCX_NEED(w->store, l1b, p + "attn_ln.bias", D);
+    CCX_NEED(w->store, cqw, p + "cross_attn.query.weight", D, D); CCX_NEED(w->store, cqb, p + "cross_attn.query.bias", D);
+    CCX_NEED(w->store, ckw, p + "cross_attn.key.weight", D, D);
+    CCX_NEED(w->store, cvw, p + "cross_attn.value.weight", D, D); CCX_NEED(w->store, cvb, p + "cross_attn.value.bias", D);
+    CCX_NEED(w->store, cow, p + "cross_attn.out.weight", D, D); CCX_NEED(w->store, cob, p + "cross_attn.out.bias", D);
+    CCX_NEED(w->store, lcg, p + "cross_attn_ln.weight", D); CCX_NEED(w->store, lcb, p + "cross_attn_ln.bias", D);
+    CCX_NEED(w->store, m0w, p + "mlp.0.weight", F, D); CCX_NEED(w->store, m0b, p + "mlp.0.bias", F);
+    CCX_NEED(w->store, m2w, p + "mlp.2.weight", D, F); CCX_NEED(w->store, m2b, p + "mlp.2.bias", D);
+    CCX_NEED(w->store, l2g, p + "mlp_ln.weight", D); CCX_NEED(w->store, l2b, p + "mlp_ln.bias", D);
     std::vector<float> wqkv = cat_rows({&qw->data, &kw->data, &vw->data});
     std::vector<float> bqkv = cat_rows({&qbias->data, &zerosD, &vbias->data});
     std::vector<float> wckv = cat_rows({&ckw->data, &cvw->data});
     std::vector<float> bckv = cat_rows({&zerosD, &cvb->data});
-    TRY(up_bf16_packed(w, &L.Wqkv, wqkv.data(), 3 * D, D, 16)); TRY(up_f32(w, &L.bqkv, bqkv.data(), bqkv.size()));
-    TRY(up_bf16_packed(w, &L.Wo, ow->data.data(), D, D, 16)); TRY(up_f32(w, &L.bo, obias->data.data(), D));
+    CCX_TRY(up_bf16_packed(w, &L.Wqkv, wqkv.data(), 3 * D, D, 16)); CCX_TRY(w->store.upload(&L.bqkv, bqkv));
+    CCX_TRY(up_bf16_packed(w, &L.Wo, ow->data.data(), D, D, 16)); CCX_TRY(w->store.upload(&L.bo, obias->data.data(), D));
     { double sb = 0.0; for (int k = 0; k < D; k++) sb += obias->data[k]; L.bo_mean = (float)(sb / D); }
-    TRY(up_bf16_packed(w, &L.Wcq, cqw->data.data(), D, D, 16)); TRY(up_f32(w, &L.bcq, cqb->data.data(), D));
-    TRY(up_bf16(w, &L.Wckv, wckv.data(), wckv.size())); TRY(up_f32(w, &L.bckv, bckv.data(), bckv.size()));
-    TRY(up_bf16_packed(w, &L.Wco, cow->data.data(), D, D, 16)); TRY(up_f32(w, &L.bco, cob->data.data(), D));
-    TRY(up_bf16_packed(w, &L.W1, m0w->data.data(), F, D, 16)); TRY(up_f32(w, &L.b1, m0b->data.data(), F));
-    TRY(up_bf16_packed(w, &L.W2, m2w->data.data(), D, F, 16)); TRY(up_f32(w, &L.b2, m2b->data.data(), D));
-    TRY(up_f32(w, &L.ln1_g, l1g->data.data(), D)); TRY(up_f32(w, &L.ln1_b, l1b->data.data(), D));
-    TRY(up_f32(w, &L.lnc_g, lcg->data.data(), D)); TRY(up_f32(w, &L.lnc_b, lcb->data.data(), D));
-    TRY(up_f32(w, &L.ln2_g, l2g->data.data(), D)); TRY(up_f32(w, &L.ln2_b, l2b->data.data(), D));
+    CCX_TRY(up_bf16_packed(w, &L.Wcq, cqw->data.data(), D, D, 16)); CCX_TRY(w->store.upload(&L.bcq, cqb->data.data(), D));
+    CCX_TRY(w->store.upload_bf16(&L.Wckv, wckv)); CCX_TRY(w->store.upload(&L.bckv, bckv));
+    CCX_TRY(up_bf16_packed(w, &L.Wco, cow->data.data(), D, D, 16)); CCX_TRY(w->store.upload(&L.bco, cob->data.data(), D));
+    CCX_TRY(up_bf16_packed(w, &L.W1, m0w->data.data(), F, D, 16)); CCX_TRY(w->store.upload(&L.b1, m0b->data.data(), F));
+    CCX_TRY(up_bf16_packed(w, &L.W2, m2w->data.data(), D, F, 16)); CCX_TRY(w->store.upload(&L.b2, m2b->data.data(), D));
+    CCX_TRY(w->store.upload(&L.ln1_g, l1g->data.data(), D)); CCX_TRY(w->store.upload(&L.ln1_b, l1b->data.data(), D));
+    CCX_TRY(w->store.upload(&L.lnc_g, lcg->data.data(), D)); CCX_TRY(w->store.upload(&L.lnc_b, lcb->data.data(), D));
+    CCX_TRY(w->store.upload(&L.ln2_g, l2g->data.data(), D)); CCX_TRY(w->store.upload(&L.ln2_b, l2b->data.data(), D));
     if (w->xs_on) {
       std::vector<float> wkt((size_t)D * D);
       for (int hh = 0; hh < H; hh++)
         for (int f = 0; f < D; f++)
           for (int dd = 0; dd < 64; dd++) wkt[((size_t)hh * D + f) * 64 + dd] = ckw->data[(size_t)(hh * 64 + dd) * D + f];
-      TRY(up_bf16(w, &L.WckT, wkt.data(), wkt.size()));
-      TRY(up_bf16(w, &L.Wcq_plain, cqw->data.data(), cqw->data.size()));
+      CCX_TRY(w->store.upload_bf16(&L.WckT, wkt));
+      CCX_TRY(w->store.upload_bf16(&L.Wcq_plain, cqw->data));
       // cross_attn_ln folded into the cross-attention query (the LayerNorm-free query of the X-stream path)
       std::vector<float> Wg((size_t)D * D), sv(D), cv(D);
       for (int n = 0; n < D; n++) {
@@ -572,7 +451,7 @@ int ccx_whisper_finalize(ccx_whisper* w) {
         for (int k = 0; k < D; k++) {
           const float v = lcg->data[k] * cqw->data[(size_t)n * D + k];
           Wg[(size_t)n * D + k] = v;
-          const uint32_t bits = (uint32_t)host_f32_to_bf16(v) << 16;
+          const uint32_t bits = (uint32_t)ccx_host_f32_to_bf16(v) << 16;
           float r;
           memcpy(&r, &bits, 4);
           ss += (double)r;                                   // what the MFMA sums: the bf16-rounded products
@@ -581,13 +460,13 @@ int ccx_whisper_finalize(ccx_whisper* w) {
         sv[n] = (float)ss;
         cv[n] = (float)(cc + (double)cqb->data[n]);
       }
-      TRY(up_bf16(w, &L.Wcq_g, Wg.data(), Wg.size())); TRY(up_f32(w, &L.scq, sv.data(), sv.size())); TRY(up_f32(w, &L.ccq, cv.data(), cv.size()));
+      CCX_TRY(w->store.upload_bf16(&L.Wcq_g, Wg)); CCX_TRY(w->store.upload(&L.scq, sv)); CCX_TRY(w->store.upload(&L.ccq, cv));
     }
     const size_t ck = (size_t)w->kv_cap * H * w->Spad * 64, sk = (size_t)B * H * Tc * 64;
-    TRY(dev_alloc(w, &L.crossK, ck, true)); TRY(dev_alloc(w, &L.crossV, ck, true));
-    TRY(dev_alloc(w, &L.selfK, sk, true)); TRY(dev_alloc(w, &L.selfV, sk, true));
+    CCX_TRY(w->store.alloc(&L.crossK, ck, true)); CCX_TRY(w->store.alloc(&L.crossV, ck, true));
+    CCX_TRY(w->store.alloc(&L.selfK, sk, true)); CCX_TRY(w->store.alloc(&L.selfV, sk, true));
   }
-  w->staged.clear();
+  w->store.staged.clear();
 
   // ---------------- workspaces ----------------
   // log-mel and encoder: only live between ccx_whisper_logmel and the end of ccx_whisper_encode (the cross-KV it leaves behind is
@@ -597,65 +476,65 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     w->im2col = dn->im2col; w->h1 = dn->h1; w->x = dn->x; w->xn = dn->xn;
     w->qb = dn->qb; w->kb = dn->kb; w->vtb = dn->vtb; w->attn = dn->attn; w->ffn = dn->ffn;
   } else {
-    TRY(dev_alloc(w, &w->lm_raw, (size_t)B * 80 * w->Fraw, true));
-    TRY(dev_alloc(w, &w->lm_max, (size_t)B, true));
-    TRY(dev_alloc(w, &w->lm_n, (size_t)B, true));
-    TRY(dev_alloc(w, &w->lm_seek, (size_t)B, true));
-    TRY(dev_alloc(w, &w->lm_seg, (size_t)B, true));
-    TRY(dev_alloc(w, &w->im2col, (size_t)B * 3000 * 256, true));
-    TRY(dev_alloc(w, &w->h1, ((size_t)B * 3002 + 2) * D, true));
-    TRY(dev_alloc(w, &w->x, (size_t)B * S * D, true));
-    TRY(dev_alloc(w, &w->xn, (size_t)B * S * D, true));
-    TRY(dev_alloc(w, &w->qb, (size_t)B * H * w->Spad * 64, true));
-    TRY(dev_alloc(w, &w->kb, (size_t)B * H * w->Spad * 64, true));
-    TRY(dev_alloc(w, &w->vtb, (size_t)B * H * 64 * w->Spad, true));
-    TRY(dev_alloc(w, &w->attn, (size_t)B * S * D, true));
-    TRY(dev_alloc(w, &w->ffn, (size_t)B * S * F, true));
+    CCX_TRY(w->store.alloc(&w->lm_raw, (size_t)B * 80 * w->Fraw, true));
+    CCX_TRY(w->store.alloc(&w->lm_max, (size_t)B, true));
+    CCX_TRY(w->store.alloc(&w->lm_n, (size_t)B, true));
+    CCX_TRY(w->store.alloc(&w->lm_seek, (size_t)B, true));
+    CCX_TRY(w->store.alloc(&w->lm_seg, (size_t)B, true));
+    CCX_TRY(w->store.alloc(&w->im2col, (size_t)B * 3000 * 256, true));
+    CCX_TRY(w->store.alloc(&w->h1, ((size_t)B * 3002 + 2) * D, true));
+    CCX_TRY(w->store.alloc(&w->x, (size_t)B * S * D, true));
+    CCX_TRY(w->store.alloc(&w->xn, (size_t)B * S * D, true));
+    CCX_TRY(w->store.alloc(&w->qb, (size_t)B * H * w->Spad * 64, true));
+    CCX_TRY(w->store.alloc(&w->kb, (size_t)B * H * w->Spad * 64, true));
+    CCX_TRY(w->store.alloc(&w->vtb, (size_t)B * H * 64 * w->Spad, true));
+    CCX_TRY(w->store.alloc(&w->attn, (size_t)B * S * D, true));
+    CCX_TRY(w->store.alloc(&w->ffn, (size_t)B * S * F, true));
   }
 
   // the encoder output stays with the instance: the decode streams it (cross_x.hip); + one key tile of slack
-  TRY(dev_alloc(w, &w->xa, ((size_t)B * S + 16) * D, true));
+  CCX_TRY(w->store.alloc(&w->xa, ((size_t)B * S + 16) * D, true));
   if (w->xs_on) {
-    TRY(dev_alloc(w, &w->xq, (size_t)B * H * D, true));
-    TRY(dev_alloc(w, &w->pf_xq, (size_t)B * ccx_whisper::kPrefillMax * H * D, true));
-    TRY(dev_alloc(w, &w->xs_po, ccx_xs_part_o_elems(B, H, D), true));
-    TRY(dev_alloc(w, &w->xs_pml, ccx_xs_part_ml_elems(B), true));
-    TRY(dev_alloc(w, &w->pf_xs_po, ccx_xs_part_o_elems((size_t)B * ccx_whisper::kPrefillMax, H, D), true));
-    TRY(dev_alloc(w, &w->pf_xs_pml, ccx_xs_part_ml_elems((size_t)B * ccx_whisper::kPrefillMax), true));
-    TRY(dev_alloc(w, &w->dxb, (size_t)B * D, true));
-    TRY(dev_alloc(w, &w->pf_xb, (size_t)B * ccx_whisper::kPrefillMax * D, true));
-    TRY(dev_alloc(w, &w->dst2, (size_t)B * (D / 16), true));
-    TRY(dev_alloc(w, &w->pf_st2, (size_t)B * ccx_whisper::kPrefillMax * (D / 16), true));
-    TRY(dev_alloc(w, &w->dshift, (size_t)B, true));
-    TRY(dev_alloc(w, &w->pf_shift, (size_t)B * ccx_whisper::kPrefillMax, true));
+    CCX_TRY(w->store.alloc(&w->xq, (size_t)B * H * D, true));
+    CCX_TRY(w->store.alloc(&w->pf_xq, (size_t)B * ccx_whisper::kPrefillMax * H * D, true));
+    CCX_TRY(w->store.alloc(&w->xs_po, ccx_xs_part_o_elems(B, H, D), true));
+    CCX_TRY(w->store.alloc(&w->xs_pml, ccx_xs_part_ml_elems(B), true));
+    CCX_TRY(w->store.alloc(&w->pf_xs_po, ccx_xs_part_o_elems((size_t)B * ccx_whisper::kPrefillMax, H, D), true));
+    CCX_TRY(w->store.alloc(&w->pf_xs_pml, ccx_xs_part_ml_elems((size_t)B * ccx_whisper::kPrefillMax), true));
+    CCX_TRY(w->store.alloc(&w->dxb, (size_t)B * D, true));
+    CCX_TRY(w->store.alloc(&w->pf_xb, (size_t)B * ccx_whisper::kPrefillMax * D, true));
+    CCX_TRY(w->store.alloc(&w->dst2, (size_t)B * (D / 16), true));
+    CCX_TRY(w->store.alloc(&w->pf_st2, (size_t)B * ccx_whisper::kPrefillMax * (D / 16), true));
+    CCX_TRY(w->store.alloc(&w->dshift, (size_t)B, true));
+    CCX_TRY(w->store.alloc(&w->pf_shift, (size_t)B * ccx_whisper::kPrefillMax, true));
   }
-  TRY(dev_alloc(w, &w->dx, (size_t)B * D, true));
-  TRY(dev_alloc(w, &w->dx2, (size_t)B * D, true));
-  TRY(dev_alloc(w, &w->pend, (size_t)4 * B * D, true));
-  TRY(dev_alloc(w, &w->dxn, (size_t)B * D, true));
-  TRY(dev_alloc(w, &w->dq, (size_t)B * D, true));
-  TRY(dev_alloc(w, &w->dattn, (size_t)B * D, true));
-  TRY(dev_alloc(w, &w->dffn, (size_t)B * F, true));
-  TRY(dev_alloc(w, &w->dlogits, (size_t)B * w->Vpad, true));
-  TRY(dev_alloc(w, &w->part_o, (size_t)B * H * ccx_whisper::kCrossSplitMax * 64, true));
-  TRY(dev_alloc(w, &w->part_ml, (size_t)B * H * ccx_whisper::kCrossSplitMax * 2, true));
-  TRY(dev_alloc(w, &w->cur_tok, (size_t)B, true));
-  TRY(dev_alloc(w, &w->pos, (size_t)B, true));
-  TRY(dev_alloc(w, &w->n_done, (size_t)ccx_whisper::kMaxLanes, true));
-  TRY(dev_alloc(w, &w->sample_cfg, (size_t)4, true));
-  TRY(dev_alloc(w, &w->state, (size_t)B, true));
+  CCX_TRY(w->store.alloc(&w->dx, (size_t)B * D, true));
+  CCX_TRY(w->store.alloc(&w->dx2, (size_t)B * D, true));
+  CCX_TRY(w->store.alloc(&w->pend, (size_t)4 * B * D, true));
+  CCX_TRY(w->store.alloc(&w->dxn, (size_t)B * D, true));
+  CCX_TRY(w->store.alloc(&w->dq, (size_t)B * D, true));
+  CCX_TRY(w->store.alloc(&w->dattn, (size_t)B * D, true));
+  CCX_TRY(w->store.alloc(&w->dffn, (size_t)B * F, true));
+  CCX_TRY(w->store.alloc(&w->dlogits, (size_t)B * w->Vpad, true));
+  CCX_TRY(w->store.alloc(&w->part_o, (size_t)B * H * ccx_whisper::kCrossSplitMax * 64, true));
+  CCX_TRY(w->store.alloc(&w->part_ml, (size_t)B * H * ccx_whisper::kCrossSplitMax * 2, true));
+  CCX_TRY(w->store.alloc(&w->cur_tok, (size_t)B, true));
+  CCX_TRY(w->store.alloc(&w->pos, (size_t)B, true));
+  CCX_TRY(w->store.alloc(&w->n_done, (size_t)ccx_whisper::kMaxLanes, true));
+  CCX_TRY(w->store.alloc(&w->sample_cfg, (size_t)4, true));
+  CCX_TRY(w->store.alloc(&w->state, (size_t)B, true));
   {
     const size_t R = (size_t)B * ccx_whisper::kPrefillMax;
-    TRY(dev_alloc(w, &w->pf_x, R * D, true)); TRY(dev_alloc(w, &w->pf_x2, R * D, true)); TRY(dev_alloc(w, &w->pf_pend, 4 * R * D, true));
-    TRY(dev_alloc(w, &w->pf_q, R * D, true)); TRY(dev_alloc(w, &w->pf_xn, R * D, true)); TRY(dev_alloc(w, &w->pf_attn, R * D, true));
-    TRY(dev_alloc(w, &w->pf_ffn, R * F, true));
-    TRY(dev_alloc(w, &w->pf_tok, R, true)); TRY(dev_alloc(w, &w->pf_pos, R, true)); TRY(dev_alloc(w, &w->pf_seq, R, true));
-    TRY(dev_alloc(w, &w->pf_last, (size_t)B, true));
+    CCX_TRY(w->store.alloc(&w->pf_x, R * D, true)); CCX_TRY(w->store.alloc(&w->pf_x2, R * D, true)); CCX_TRY(w->store.alloc(&w->pf_pend, 4 * R * D, true));
+    CCX_TRY(w->store.alloc(&w->pf_q, R * D, true)); CCX_TRY(w->store.alloc(&w->pf_xn, R * D, true)); CCX_TRY(w->store.alloc(&w->pf_attn, R * D, true));
+    CCX_TRY(w->store.alloc(&w->pf_ffn, R * F, true));
+    CCX_TRY(w->store.alloc(&w->pf_tok, R, true)); CCX_TRY(w->store.alloc(&w->pf_pos, R, true)); CCX_TRY(w->store.alloc(&w->pf_seq, R, true));
+    CCX_TRY(w->store.alloc(&w->pf_last, (size_t)B, true));
   }
   w->max_prompt_cap = d.n_text_ctx;
   w->sample_cap = d.n_text_ctx;
-  TRY(dev_alloc(w, &w->prompt, (size_t)B * w->max_prompt_cap, true));
-  TRY(dev_alloc(w, &w->gen, (size_t)B * w->sample_cap, true));
+  CCX_TRY(w->store.alloc(&w->prompt, (size_t)B * w->max_prompt_cap, true));
+  CCX_TRY(w->store.alloc(&w->gen, (size_t)B * w->sample_cap, true));
   // decode streams get the highest priority: when other work shares the GPU (the front end of the next batch on another
   // stream) the short, latency-bound chain kernels should get the next free wave slot.
   int prio_least = 0, prio_greatest = 0;
@@ -668,10 +547,10 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     CCX_HIP(w->ctx, hipEventCreateWithFlags(&w->lane_poll[1][i], hipEventDisableTiming));
   }
   for (int i = 0; i < ccx_whisper::kLanePool; i++) CCX_HIP(w->ctx, hipStreamCreateWithPriority(&w->lane_pool[i], hipStreamNonBlocking, prio_greatest));
-  TRY(dev_alloc(w, &w->probe_sink, (size_t)64, true));
+  CCX_TRY(w->store.alloc(&w->probe_sink, (size_t)64, true));
   // lane trace buffers (2 MB): always there so that ccx_whisper_trace_lanes can switch the trace on later
-  TRY(dev_alloc(w, &w->stamps, (size_t)ccx_whisper::kMaxLanes * ccx_whisper::kStampCap, true));
-  TRY(dev_alloc(w, &w->stamp_count, (size_t)ccx_whisper::kMaxLanes, true));
+  CCX_TRY(w->store.alloc(&w->stamps, (size_t)ccx_whisper::kMaxLanes * ccx_whisper::kStampCap, true));
+  CCX_TRY(w->store.alloc(&w->stamp_count, (size_t)ccx_whisper::kMaxLanes, true));
   if (const char* e = getenv("CCX_DEC_STAMPS")) {
     w->stamps_on = true;
     w->stamp_path = e;
@@ -713,7 +592,7 @@ int ccx_whisper_logmel(ccx_whisper* w, const float* audio, int64_t stride, const
   hipStream_t stream = (hipStream_t)stream_;
   CCX_REQUIRE(w->ctx, w->finalized, "whisper: not finalized");
   CCX_REQUIRE(w->ctx, audio && n_samples && B >= 1 && B <= w->max_batch, "whisper_logmel: bad arguments (B=%d, max %d)", B, w->max_batch);
-  TRY(scratch_acquire(w, stream));
+  CCX_TRY(scratch_acquire(w, stream));
   long fcomp = 32;
   for (int b = 0; b < B; b++) {
     CCX_REQUIRE(w->ctx, n_samples[b] >= 0 && n_samples[b] <= stride, "whisper_logmel: n_samples[%d]=%d exceeds stride", b, n_samples[b]);
@@ -755,7 +634,7 @@ __global__ void mel_to_im2col_kernel(const float* __restrict__ mel, bf16_t* __re
 int ccx_whisper_set_mel(ccx_whisper* w, const float* mel, int B, void* stream_) {
   if (!w) return CCX_ERR_ARG;
   CCX_REQUIRE(w->ctx, w->finalized && mel && B >= 1 && B <= w->max_batch, "whisper_set_mel: bad arguments");
-  TRY(scratch_acquire(w, (hipStream_t)stream_));
+  CCX_TRY(scratch_acquire(w, (hipStream_t)stream_));
   hipLaunchKernelGGL(mel_to_im2col_kernel, dim3(750, B), dim3(1024), 0, (hipStream_t)stream_, mel, w->im2col);
   CCX_CHECK_LAUNCH(w->ctx);
   return CCX_OK;
@@ -773,7 +652,7 @@ static int project_cross_kv(ccx_whisper* w, int n, hipStream_t stream) {
     p.A = w->xa; p.lda = D; p.W = L.Wckv; p.ldw = D; p.M = n * S; p.N = 2 * D; p.K = D; p.bias = L.bckv;
     p.hk = L.crossK; p.hv = L.crossV; p.d_model = D; p.n_head = H; p.S = S; p.Spad = w->Spad; p.v_transposed = 0;
     p.first_block = 1;
-    TRY(ccx_launch_gemm(w->ctx, EPI_HEADS, p, stream));
+    CCX_TRY(ccx_launch_gemm(w->ctx, EPI_HEADS, p, stream));
   }
   w->kv_ready = n;
   return CCX_OK;
@@ -798,7 +677,7 @@ static int select_cross_path(ccx_whisper* w, int B, hipStream_t stream) {
   const char* e = getenv("CCX_CROSS_X_MIN_ROWS");
   const int min_rows = e ? atoi(e) : ccx_whisper::kKvSeqs + 1;
   w->xs_active = w->xs_on && (B >= min_rows || B > w->kv_cap);
-  if (w->xs_on && !w->xs_active && w->kv_ready < B) TRY(project_cross_kv(w, B, stream));
+  if (w->xs_on && !w->xs_active && w->kv_ready < B) CCX_TRY(project_cross_kv(w, B, stream));
   return CCX_OK;
 }
 
@@ -815,41 +694,41 @@ int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out, void* stream_) {
   memset(&p, 0, sizeof(p));
   p.A = w->im2col; p.lda = 256; p.W = w->Wc1; p.ldw = 256; p.M = B * 3000; p.N = D; p.K = 256;
   p.bias = w->bc1; p.out = w->h1; p.ldo = D; p.rpb_in = 3000; p.rpb_out = 3002; p.roff = 1; p.rpb_valid = 3000;
-  TRY(ccx_launch_gemm(ctx, EPI_BF16_GELU, p, stream));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16_GELU, p, stream));
   // conv2 (stride 2) + GELU + positional embedding: row m' = b*1501 + t reads h1 rows 2m' .. 2m'+2
   memset(&p, 0, sizeof(p));
   p.A = w->h1; p.lda = 2 * D; p.W = w->Wc2; p.ldw = 3 * D; p.M = B * 1501; p.N = D; p.K = 3 * D;
   p.bias = w->bc2; p.out = w->x; p.ldo = D; p.resid = w->enc_pos; p.ldr = D; p.resid_mod = S;
   p.rpb_in = 1501; p.rpb_out = S; p.roff = 0; p.rpb_valid = S;
-  TRY(ccx_launch_gemm(ctx, EPI_F32_GELU_POS, p, stream));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_F32_GELU_POS, p, stream));
 
   const int M = B * S;
   for (int l = 0; l < d.n_audio_layer; l++) {
     const EncLayer& L = w->enc[l];
-    TRY(ccx_launch_layernorm(ctx, w->x, D, L.ln1_g, L.ln1_b, w->xn, nullptr, D, M, D, 1e-5f, stream));
+    CCX_TRY(ccx_launch_layernorm(ctx, w->x, D, L.ln1_g, L.ln1_b, w->xn, nullptr, D, M, D, 1e-5f, stream));
     memset(&p, 0, sizeof(p));
     p.A = w->xn; p.lda = D; p.W = L.Wqkv; p.ldw = D; p.M = M; p.N = 3 * D; p.K = D; p.bias = L.bqkv;
     p.hq = w->qb; p.hk = w->kb; p.hv = w->vtb; p.d_model = D; p.n_head = H; p.S = S; p.Spad = w->Spad; p.v_transposed = 1;
-    TRY(ccx_launch_gemm(ctx, EPI_HEADS, p, stream));
-    TRY(ccx_launch_enc_attention(ctx, w->qb, w->kb, w->vtb, w->attn, B, H, S, w->Spad, stream));
+    CCX_TRY(ccx_launch_gemm(ctx, EPI_HEADS, p, stream));
+    CCX_TRY(ccx_launch_enc_attention(ctx, w->qb, w->kb, w->vtb, w->attn, B, H, S, w->Spad, stream));
     memset(&p, 0, sizeof(p));
     p.A = w->attn; p.lda = D; p.W = L.Wo; p.ldw = D; p.M = M; p.N = D; p.K = D; p.bias = L.bo;
     p.out = w->x; p.ldo = D; p.resid = w->x; p.ldr = D;
-    TRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, stream));
-    TRY(ccx_launch_layernorm(ctx, w->x, D, L.ln2_g, L.ln2_b, w->xn, nullptr, D, M, D, 1e-5f, stream));
+    CCX_TRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, stream));
+    CCX_TRY(ccx_launch_layernorm(ctx, w->x, D, L.ln2_g, L.ln2_b, w->xn, nullptr, D, M, D, 1e-5f, stream));
     memset(&p, 0, sizeof(p));
     p.A = w->xn; p.lda = D; p.W = L.W1; p.ldw = D; p.M = M; p.N = F; p.K = D; p.bias = L.b1; p.out = w->ffn; p.ldo = F;
-    TRY(ccx_launch_gemm(ctx, EPI_BF16_GELU, p, stream));
+    CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16_GELU, p, stream));
     memset(&p, 0, sizeof(p));
     p.A = w->ffn; p.lda = F; p.W = L.W2; p.ldw = F; p.M = M; p.N = D; p.K = F; p.bias = L.b2;
     p.out = w->x; p.ldo = D; p.resid = w->x; p.ldr = D;
-    TRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, stream));
+    CCX_TRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, stream));
   }
-  TRY(ccx_launch_layernorm(ctx, w->x, D, w->lnp_g, w->lnp_b, w->xa, xa_out, D, M, D, 1e-5f, stream));
-  TRY(scratch_release(w, stream));
+  CCX_TRY(ccx_launch_layernorm(ctx, w->x, D, w->lnp_g, w->lnp_b, w->xa, xa_out, D, M, D, 1e-5f, stream));
+  CCX_TRY(scratch_release(w, stream));
   // cross-attention K/V: with the X-stream cross attention only decodes of <= 80 sequences use them and project them themselves
   w->kv_ready = 0;
-  if (!w->xs_on) TRY(project_cross_kv(w, B, stream));
+  if (!w->xs_on) CCX_TRY(project_cross_kv(w, B, stream));
   return CCX_OK;
 }
 
@@ -943,7 +822,7 @@ int dec_head(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     GemmParams gp;
     memset(&gp, 0, sizeof(gp));
     gp.A = dxn; gp.lda = D; gp.W = w->tok_emb_rm; gp.ldw = D; gp.M = B; gp.N = d.n_vocab; gp.K = D; gp.out = logits; gp.ldo = ld;
-    TRY(ccx_launch_gemm(ctx, EPI_F32, gp, stream));
+    CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, gp, stream));
   }
   if (select) {
     DecSelectParams sp;
@@ -955,7 +834,7 @@ int dec_head(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     sp.max_initial_ts = w->rules.max_initial_timestamp_index;
     sp.tok_emb = w->tok_emb_f32; sp.pos_emb = w->dec_pos; sp.x = w->dx + ro * D; sp.D = D;
     sp.sample_cfg = w->sample_cfg; sp.row0 = b0; sp.sample = w->sampling ? 1 : 0;
-    TRY(ccx_launch_dec_select(ctx, sp, B, stream));
+    CCX_TRY(ccx_launch_dec_select(ctx, sp, B, stream));
   }
   return CCX_OK;
 }
@@ -1062,27 +941,27 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
       memset(&ex, 0, sizeof(ex));
       ex.cache_k = L.selfK + self_off; ex.cache_v = L.selfV + self_off; ex.cache_T = Tc; ex.pos = pos; ex.row_seq = row_seq;
       ex.ln_mean_out = shift;                      // LayerNorm-free query: the rows' attn_ln means centre their bf16 copies
-      TRY(ln_linear(DEPI_SELF_QKV, L.Wqkv, L.bqkv, 3 * D, L.ln1_g, L.ln1_b, dq, D, &ex));
+      CCX_TRY(ln_linear(DEPI_SELF_QKV, L.Wqkv, L.bqkv, 3 * D, L.ln1_g, L.ln1_b, dq, D, &ex));
       stamp(16, 2);
     }
     DecAttnParams ap;
     memset(&ap, 0, sizeof(ap));
     ap.q = dq; ap.k = L.selfK + self_off; ap.v = L.selfV + self_off; ap.H = H; ap.kv_T = Tc; ap.pos = pos; ap.scale_log2e = scale_log2e;
     ap.out_bf16 = dattn; ap.row_seq = row_seq;
-    TRY(ccx_launch_dec_attention(ctx, ap, B, 1, true, stream));
+    CCX_TRY(ccx_launch_dec_attention(ctx, ap, B, 1, true, stream));
     stamp(17, 2);
     if (lnfree) {
       DecLinearParams lp;
       memset(&lp, 0, sizeof(lp));
       lp.M = B; lp.N = D; lp.K = D; lp.W = L.Wo; lp.ldw = D; lp.bias = L.bo; lp.act = dattn; lp.lda = D;
       lp.xres = cur; lp.xb = xb; lp.st_out = st2; lp.shift = shift; lp.shift_c = L.bo_mean;
-      TRY(ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_RESOLVE, lp, stream));
+      CCX_TRY(ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_RESOLVE, lp, stream));
     } else {
-      TRY(partial_linear(ACT_BF16, L.Wo, L.bo, D, dattn));
+      CCX_TRY(partial_linear(ACT_BF16, L.Wo, L.bo, D, dattn));
     }
     stamp(18, 2);
     // cross attention
-    if (q_launch) TRY(ln_linear(DEPI_F32, L.Wcq, L.bcq, D, L.lnc_g, L.lnc_b, dq, D, nullptr));
+    if (q_launch) CCX_TRY(ln_linear(DEPI_F32, L.Wcq, L.bcq, D, L.lnc_g, L.lnc_b, dq, D, nullptr));
     stamp(1, 1);
     if (l == 0 && stagger) CCX_HIP(ctx, hipEventRecord(stagger, stream));
     if (w->xs_active) {
@@ -1102,10 +981,10 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
       xp.rows = B; xp.H = H; xp.S = d.n_audio_ctx; xp.D = D; xp.scale_log2e = scale_log2e;
       xp.lds_pad = (w->cross_lds_pad > 0 && !pre) ? 65536 : 0;
       xp.rows_per_seq = pre ? prefill_rows : 0;
-      TRY(ccx_launch_xs_cross_attention(ctx, xp, stream));
+      CCX_TRY(ccx_launch_xs_cross_attention(ctx, xp, stream));
       if (xs_fused && pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
       stamp(2, 1);
-      TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
+      CCX_TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
       stamp(19, 2);
     } else {
       memset(&ap, 0, sizeof(ap));
@@ -1116,37 +995,37 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
       if (fuse_q) {
         ap.qx = cur; ap.q_pend = pend; ap.q_pend_n = pend_n; ap.q_pend_stride = pstride; ap.q_x_out = pend_n > 0 ? other : nullptr;
         ap.q_ln_g = L.lnc_g; ap.q_ln_b = L.lnc_b; ap.q_eps = 1e-5f; ap.q_W = L.Wcq; ap.q_bias = L.bcq; ap.q_K = D;
-        TRY(ccx_launch_dec_cross_fused_q(ctx, ap, B, ns, stream));
+        CCX_TRY(ccx_launch_dec_cross_fused_q(ctx, ap, B, ns, stream));
         if (pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
-        TRY(partial_linear(ACT_COMBINE, L.Wco, L.bco, D, nullptr));
+        CCX_TRY(partial_linear(ACT_COMBINE, L.Wco, L.bco, D, nullptr));
       } else if (pre) {
         // two prompt rows and more per sequence share its K/V; a one-row pass runs as a decode step would
         ap.row_seq = prefill_rows > 1 ? row_seq : nullptr; ap.rows_per_seq = prefill_rows > 1 ? prefill_rows : 0;
         ap.lds_pad = 0; ap.stream_mode = 1;
-        TRY(ccx_launch_dec_attention(ctx, ap, nseq, 1, true, stream));
-        TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
+        CCX_TRY(ccx_launch_dec_attention(ctx, ap, nseq, 1, true, stream));
+        CCX_TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
       } else if (B > 16) {
-        TRY(ccx_launch_dec_attention(ctx, ap, B, ns, ns == 1, stream));
+        CCX_TRY(ccx_launch_dec_attention(ctx, ap, B, ns, ns == 1, stream));
         stamp(2, 1);
-        if (ns > 1) TRY(ccx_launch_dec_combine(ctx, part_o, part_ml, ns, dattn, B, H, stream));
-        TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
+        if (ns > 1) CCX_TRY(ccx_launch_dec_combine(ctx, part_o, part_ml, ns, dattn, B, H, stream));
+        CCX_TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
         stamp(19, 2);
       } else {
-        TRY(ccx_launch_dec_attention(ctx, ap, B, ns, false, stream));
-        TRY(partial_linear(ACT_COMBINE, L.Wco, L.bco, D, nullptr));
+        CCX_TRY(ccx_launch_dec_attention(ctx, ap, B, ns, false, stream));
+        CCX_TRY(partial_linear(ACT_COMBINE, L.Wco, L.bco, D, nullptr));
       }
     }
     // MLP.  (fc1 through the tiled GEMM from 256 rows on, 653.1 -> 647.6 ms per pipeline step, was removed: the GEMM sums K in
     // another order, so a sequence's log-probabilities would depend on its lane's row count -- DESIGN.md)
-    TRY(ln_linear(DEPI_BF16_GELU, L.W1, L.b1, F, L.ln2_g, L.ln2_b, dffn, F, nullptr));
+    CCX_TRY(ln_linear(DEPI_BF16_GELU, L.W1, L.b1, F, L.ln2_g, L.ln2_b, dffn, F, nullptr));
     stamp(20, 2);
-    TRY(partial_linear(ACT_BF16, L.W2, L.b2, F, dffn));
+    CCX_TRY(partial_linear(ACT_BF16, L.W2, L.b2, F, dffn));
     stamp(21, 2);
   }
   // resolve the last partials + final LN, then logits against the tied embedding
-  TRY(ccx_launch_dec_resolve_ln(ctx, cur, pend, pend_n, pstride, w->lnd_g, w->lnd_b, dxn, nullptr, B, D, 1e-5f, stream));
+  CCX_TRY(ccx_launch_dec_resolve_ln(ctx, cur, pend, pend_n, pstride, w->lnd_g, w->lnd_b, dxn, nullptr, B, D, 1e-5f, stream));
   if (pre) return CCX_OK;         // the caller gathers the last prompt row of every sequence out of pf_xn
-  TRY(dec_head(w, b0, B, logits, ld, select, sample_len, max_prompt, n_done, stream));
+  CCX_TRY(dec_head(w, b0, B, logits, ld, select, sample_len, max_prompt, n_done, stream));
   stamp(3, 1);       // end of the step
   return CCX_OK;
 }
@@ -1178,7 +1057,7 @@ int upload_decode_state(ccx_whisper* w, const int32_t* prompt_ids, const int32_t
   memcpy(&cfg[0], &temperature, 4);
   CCX_HIP(w->ctx, hipMemcpyAsync(w->sample_cfg, cfg, sizeof(cfg), hipMemcpyHostToDevice, stream));
   // embedding of the first token; later steps get theirs from the select kernel
-  if (!prefilled) TRY(ccx_launch_dec_embed(w->ctx, w->tok_emb_f32, w->dec_pos, w->cur_tok, w->pos, w->dx, B, w->d.n_text_state, stream));
+  if (!prefilled) CCX_TRY(ccx_launch_dec_embed(w->ctx, w->tok_emb_f32, w->dec_pos, w->cur_tok, w->pos, w->dx, B, w->d.n_text_state, stream));
   CCX_HIP(w->ctx, hipStreamSynchronize(stream));  // host vectors go out of scope
   return CCX_OK;
 }
@@ -1210,10 +1089,10 @@ int run_prefill(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_pos, ps.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_seq, sq.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_last, last.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream));
-    TRY(ccx_launch_dec_embed(ctx, w->tok_emb_f32, w->dec_pos, w->pf_tok, w->pf_pos, w->pf_x, R, D, stream));
+    CCX_TRY(ccx_launch_dec_embed(ctx, w->tok_emb_f32, w->dec_pos, w->pf_tok, w->pf_pos, w->pf_x, R, D, stream));
     CCX_HIP(ctx, hipStreamSynchronize(stream));     // host tables go out of scope
-    TRY(dec_step(w, 0, B, nullptr, 0, false, sample_len, max_prompt, nullptr, stream, nullptr, 0, Pc));
-    TRY(ccx_launch_dec_gather_rows(ctx, w->pf_xn, w->pf_last, w->dxn, B, D, stream));
+    CCX_TRY(dec_step(w, 0, B, nullptr, 0, false, sample_len, max_prompt, nullptr, stream, nullptr, 0, Pc));
+    CCX_TRY(ccx_launch_dec_gather_rows(ctx, w->pf_xn, w->pf_last, w->dxn, B, D, stream));
   }
   return CCX_OK;
 }
@@ -1233,8 +1112,8 @@ int ccx_whisper_decoder_logits(ccx_whisper* w, const int32_t* tokens, int B, int
   std::vector<int32_t> lens(B, T + 1);  // never leaves the prompt phase: every step feeds tokens[b][pos]
   // prompt buffer rows are `T` wide here
   read_chain_switches(w);
-  TRY(select_cross_path(w, B, stream));
-  TRY(upload_decode_state(w, tokens, lens.data(), T, B, 0.f, 0, stream));
+  CCX_TRY(select_cross_path(w, B, stream));
+  CCX_TRY(upload_decode_state(w, tokens, lens.data(), T, B, 0.f, 0, stream));
   const long V = w->d.n_vocab;
   w->cross_lds_pad = 0;   // single lane: the cross attention runs uncapped
   w->cross_stream = 0;
@@ -1242,7 +1121,7 @@ int ccx_whisper_decoder_logits(ccx_whisper* w, const int32_t* tokens, int B, int
     // the select kernel (prompt phase) advances cur_tok/pos; on the last step it would read prompt[T] -> skip it.
     // The logits GEMM stores whole 16-column groups, so it writes the padded workspace rows (ld = Vpad) and the n_vocab valid
     // columns are copied out: writing [B, T, V] in place would spill V % 16 columns into the next row / past the tensor.
-    TRY(dec_step(w, 0, B, w->dlogits, w->Vpad, t + 1 < T, 1, T, w->n_done, stream));
+    CCX_TRY(dec_step(w, 0, B, w->dlogits, w->Vpad, t + 1 < T, 1, T, w->n_done, stream));
     CCX_HIP(ctx, hipMemcpy2DAsync(logits_dev + (long)t * V, (size_t)T * V * 4, w->dlogits, (size_t)w->Vpad * 4, (size_t)V * 4, B,
                                   hipMemcpyDeviceToDevice, stream));
   }
@@ -1298,8 +1177,8 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   const int prefill_on = [] { const char* e = getenv("CCX_PREFILL"); return e ? atoi(e) : 1; }();     // read per call: tests flip it
   const bool prefill = prefill_on && max_pl >= 2;
   read_chain_switches(w);
-  TRY(select_cross_path(w, B, stream));
-  TRY(upload_decode_state(w, prompt_ids, prompt_lens, max_prompt, B, temperature, seed, stream, prefill));
+  CCX_TRY(select_cross_path(w, B, stream));
+  CCX_TRY(upload_decode_state(w, prompt_ids, prompt_lens, max_prompt, B, temperature, seed, stream, prefill));
   // steps still to run after the (eager) first one: the prefill already covers the prompt AND takes the first sample below
   const int total_steps = prefill ? sample_len : max_pl - 1 + sample_len;
   const bool use_graph = getenv("CCX_NO_GRAPH") == nullptr;
@@ -1353,10 +1232,10 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   // which cross attention the steps of this decode run (lane 0; a short last lane of <= 16 rows takes the <= 16-row kernels of its path)
   w->last_cross_path = w->xs_active ? 2 : ((w->cross_stream && lanes[0].B > 16) ? 1 : 0);
   if (prefill) {
-    TRY(run_prefill(w, prompt_ids, prompt_lens, max_prompt, B, max_pl, sample_len, stream));
+    CCX_TRY(run_prefill(w, prompt_ids, prompt_lens, max_prompt, B, max_pl, sample_len, stream));
     // first sample of every sequence, lane by lane (each lane counts its own finished sequences)
     for (int i = 0; i < nl; i++)
-      TRY(dec_head(w, lanes[i].b0, lanes[i].B, w->dlogits + (long)lanes[i].b0 * ld, ld, true, sample_len, max_prompt, w->n_done + i, stream));
+      CCX_TRY(dec_head(w, lanes[i].b0, lanes[i].B, w->dlogits + (long)lanes[i].b0 * ld, ld, true, sample_len, max_prompt, w->n_done + i, stream));
   }
   // the state upload (and the prefill) was queued on `stream`: the other lanes start after it
   CCX_HIP(ctx, hipEventRecord(w->own_event, stream));
@@ -1371,7 +1250,7 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   if (step < total_steps) {
     for (int i = 0; i < nl; i++) {
       if (i > 0) CCX_HIP(ctx, hipStreamWaitEvent(lanes[i].s, w->lane_start[i - 1], 0));
-      TRY(step_lane(i, (i + 1 < nl) ? w->lane_start[i] : nullptr));
+      CCX_TRY(step_lane(i, (i + 1 < nl) ? w->lane_start[i] : nullptr));
       if (ctx->prof_on && !use_graph && nl > 1) CCX_HIP(ctx, hipStreamSynchronize(lanes[i].s));
     }
     step += 1;
@@ -1407,7 +1286,7 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
       for (int i = 0; i < nl; i++) {
         if (lanes[i].exec) CCX_HIP(ctx, hipGraphLaunch(lanes[i].exec, lanes[i].s));   // ~50 us of host time per replay
         else {
-          TRY(step_lane(i, nullptr));
+          CCX_TRY(step_lane(i, nullptr));
           // eager profiling runs (ccx_prof_enable + CCX_NO_GRAPH) time every kernel with an event pair: keep the lanes apart so
           // that the durations are those of the kernel alone, as rocprofv3 (which serialises replays) sees them
           if (ctx->prof_on && !use_graph && nl > 1) CCX_HIP(ctx, hipStreamSynchronize(lanes[i].s));
@@ -1431,11 +1310,11 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   bool pending = false;   // chunk c - 1 queued but not polled yet
   while (step < total_steps) {
     const int n = (total_steps - step < kChunk) ? total_steps - step : kChunk;
-    TRY(queue_chunk(c, n));
+    CCX_TRY(queue_chunk(c, n));
     step += n;
     if (pending) {
       bool all;
-      TRY(chunk_done(c - 1, &all));
+      CCX_TRY(chunk_done(c - 1, &all));
       if (all) break;
     }
     pending = true;

@@ -10,8 +10,8 @@ from tests.conftest import within
 
 from clearconverse_amd import _lib
 from clearconverse_amd.audio import synthetic_clip
-from clearconverse_amd.weights import (SepDims, WhisperDims, synthetic_pyannet_state_dict, synthetic_sepformer_state_dict,
-                                       synthetic_whisper_state_dict, synthetic_xvector_state_dict)
+from clearconverse_amd.weights import (SepDims, WhisperDims, synthetic_pyannet_state_dict, synthetic_resnet34_state_dict,
+                                       synthetic_sepformer_state_dict, synthetic_whisper_state_dict, synthetic_xvector_state_dict)
 
 pytestmark = pytest.mark.gpu
 
@@ -102,3 +102,60 @@ def test_spectral_gate_short_and_silent(ccx_ctx):
         g.reduce_batch(torch.zeros(1, 50000, device="cuda"), [50000], prop_decrease=0.5)         # longer than max_samples
     with pytest.raises(_lib.CcxError):
         g(np.zeros(16000, np.float32), sr=8000)                                                  # wrong sample rate
+
+
+def _build_whisper(sd, ctx):
+    from clearconverse_amd.whisper import WhisperModel
+    return WhisperModel(WhisperDims.mini(n_layer=1, n_state=128), sd, max_batch=1, ctx=ctx)
+
+
+def _build_sepformer(sd, ctx):
+    from clearconverse_amd.separator import SepformerSeparator
+    return SepformerSeparator(SepDims(n_layers=1, n_blocks=1), sd, max_tokens=1000, max_utts=1, ctx=ctx)
+
+
+def _build_xvector(sd, ctx):
+    from clearconverse_amd.speaker import XVectorEmbedder
+    return XVectorEmbedder(sd, max_crops=1, max_samples=16000, ctx=ctx)
+
+
+def _build_pyannet(sd, ctx):
+    from clearconverse_amd.speaker import SegmentationNet
+    return SegmentationNet(sd, n_classes=7, powerset=True, max_crops=1, max_samples=16000, ctx=ctx)
+
+
+def _build_resnet(sd, ctx):
+    from clearconverse_amd.speaker import ResNetEmbedder
+    return ResNetEmbedder(sd, max_chunks=1, max_samples=16000, max_masks=1, ctx=ctx)
+
+
+# (message prefix, state dict, constructor, a tensor its finalize requires)
+_FINALIZE_CASES = {
+    "whisper": ("whisper", lambda: synthetic_whisper_state_dict(WhisperDims.mini(n_layer=1, n_state=128), seed=1), _build_whisper,
+                "encoder.conv1.bias"),
+    "sepformer": ("sepformer", lambda: synthetic_sepformer_state_dict(SepDims(n_layers=1, n_blocks=1), seed=1), _build_sepformer,
+                  "masknet.model.output_fc.1.bias"),
+    "xvector": ("speaker", lambda: synthetic_xvector_state_dict(seed=1), _build_xvector, "embedding.bias"),
+    "pyannet": ("speaker", lambda: synthetic_pyannet_state_dict(7, seed=1), _build_pyannet, "classifier.bias"),
+    "resnet": ("resnet", lambda: synthetic_resnet34_state_dict(seed=1), _build_resnet, "resnet.seg_1.bias"),
+}
+
+
+@pytest.mark.parametrize("fault", ["missing", "resized"])
+@pytest.mark.parametrize("model", sorted(_FINALIZE_CASES))
+def test_finalize_rejects_missing_and_missized_tensors(ccx_ctx, model, fault):
+    """A state dict that lacks a required tensor fails finalize with CCX_ERR_MISSING (4), one whose tensor has another element
+    count with CCX_ERR_ARG (1); the text names the model and the tensor.  Only constructors run: nothing is launched."""
+    prefix, make_sd, construct, name = _FINALIZE_CASES[model]
+    sd = dict(make_sd())
+    assert name in sd
+    if fault == "missing":
+        del sd[name]
+        code = 4
+    else:
+        sd[name] = torch.zeros(sd[name].numel() + 1)
+        code = 1
+    with pytest.raises(_lib.CcxError) as ei:
+        construct(sd, ccx_ctx)
+    msg = str(ei.value)
+    assert f"finalize failed ({code})" in msg and f"{prefix}: tensor '{name}'" in msg, msg
