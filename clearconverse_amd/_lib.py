@@ -36,6 +36,23 @@ class DecodeRules(C.Structure):
         "max_initial_timestamp_index", "n_suppress")] + [("suppress", C.POINTER(C.c_int))]
 
 
+class GemmDesc(C.Structure):
+    """ccx_gemm_desc (include/ccx.h): csrc/gemm_bf16.h GemmParams field for field, then the element count of every buffer."""
+    _fields_ = [
+        ("A", C.c_void_p), ("W", C.c_void_p), ("lda", C.c_int64), ("ldw", C.c_int64),
+        ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("ntaps", C.c_int), ("a_tap_stride", C.c_int64),
+        ("bias", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64), ("resid", C.c_void_p), ("ldr", C.c_int64),
+        ("resid_mod", C.c_int), ("scale", C.c_void_p), ("shift", C.c_void_p), ("slope", C.c_float),
+        ("rpb_in", C.c_int), ("rpb_out", C.c_int), ("roff", C.c_int), ("rpb_valid", C.c_int),
+        ("img_rows_in", C.c_int), ("img_rows_valid", C.c_int), ("img_rows_out", C.c_int),
+        ("resid_bf16", C.c_void_p), ("ldrb", C.c_int64),
+        ("hq", C.c_void_p), ("hk", C.c_void_p), ("hv", C.c_void_p),
+        ("d_model", C.c_int), ("n_head", C.c_int), ("S", C.c_int), ("Spad", C.c_int),
+        ("v_transposed", C.c_int), ("first_block", C.c_int),
+        ("a_elems", C.c_int64), ("w_elems", C.c_int64), ("out_elems", C.c_int64), ("resid_elems", C.c_int64),
+        ("resid_bf16_elems", C.c_int64), ("heads_elems", C.c_int64)]
+
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _ip = C.POINTER(C.c_int)
 _i32p = C.POINTER(C.c_int32)
@@ -52,6 +69,7 @@ PROTOTYPES = {
     "ccx_prof_count": (_i, [_vp]),
     "ccx_prof_get": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _fp]),
     "ccx_gemm_bf16": (_i, [_vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp]),
+    "ccx_gemm_bf16_desc": (_i, [_vp, _i, C.POINTER(GemmDesc), _vp]),
     "ccx_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "ccx_gather_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64, _vp]),
     "ccx_peak_normalize": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _f, _vp]),

@@ -95,6 +95,68 @@ int ccx_gemm_bf16(ccx_ctx* ctx, int epi, const void* A, int64_t lda, const void*
   return ccx_launch_gemm(ctx, epi, p, (hipStream_t)stream);
 }
 
+int ccx_gemm_bf16_desc(ccx_ctx* ctx, int epi, const ccx_gemm_desc* d, void* stream) {
+  if (!ctx) return CCX_ERR_ARG;
+  CCX_REQUIRE(ctx, d != nullptr, "ccx_gemm_bf16_desc: desc is NULL");
+  CCX_REQUIRE(ctx, epi >= EPI_BF16 && epi <= EPI_BF16_ADD_RELU, "ccx_gemm_bf16_desc: unknown epilogue %d", epi);
+  GemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.A = (const bf16_t*)d->A; p.W = (const bf16_t*)d->W; p.lda = (long)d->lda; p.ldw = (long)d->ldw;
+  p.M = d->M; p.N = d->N; p.K = d->K; p.ntaps = d->ntaps; p.a_tap_stride = (long)d->a_tap_stride;
+  p.bias = (const float*)d->bias; p.out = (void*)d->out; p.ldo = (long)d->ldo;
+  p.resid = (const float*)d->resid; p.ldr = (long)d->ldr; p.resid_mod = d->resid_mod;
+  p.scale = (const float*)d->scale; p.shift = (const float*)d->shift; p.slope = d->slope;
+  p.rpb_in = d->rpb_in; p.rpb_out = d->rpb_out; p.roff = d->roff; p.rpb_valid = d->rpb_valid;
+  p.img_rows_in = d->img_rows_in; p.img_rows_valid = d->img_rows_valid; p.img_rows_out = d->img_rows_out;
+  p.resid_bf16 = (const bf16_t*)d->resid_bf16; p.ldrb = (long)d->ldrb;
+  p.hq = (bf16_t*)d->hq; p.hk = (bf16_t*)d->hk; p.hv = (bf16_t*)d->hv;
+  p.d_model = d->d_model; p.n_head = d->n_head; p.S = d->S; p.Spad = d->Spad;
+  p.v_transposed = d->v_transposed; p.first_block = d->first_block;
+
+  // ---- the largest element index the kernel can touch in each buffer, against the stated counts ----
+  CCX_REQUIRE(ctx, p.A && p.W && p.M > 0 && p.N > 0 && p.K > 0, "ccx_gemm_bf16_desc: A/W null or empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
+  CCX_REQUIRE(ctx, p.lda >= 0 && p.ldw >= 0 && p.a_tap_stride >= 0 && p.ldo >= 0 && p.ldr >= 0 && p.ldrb >= 0 && p.ntaps >= 0,
+              "ccx_gemm_bf16_desc: negative stride or tap count");
+  CCX_REQUIRE(ctx, p.rpb_in >= 0 && p.rpb_out >= 0 && p.roff >= 0 && p.rpb_valid >= 0 && p.img_rows_in >= 0 && p.img_rows_valid >= 0 &&
+              p.img_rows_out >= 0 && p.resid_mod >= 0, "ccx_gemm_bf16_desc: negative row-remap field or resid_mod");
+  const long taps = p.ntaps > 1 ? p.ntaps : 1;
+  const long Nw = ((long)p.N + 15) / 16 * 16;
+  const long a_need = (long)(p.M - 1) * p.lda + (taps - 1) * p.a_tap_stride + p.K;
+  CCX_REQUIRE(ctx, a_need <= d->a_elems, "ccx_gemm_bf16_desc: A is read up to element %ld, a_elems=%ld", a_need, (long)d->a_elems);
+  const long w_need = (long)(p.N - 1) * p.ldw + taps * p.K;
+  CCX_REQUIRE(ctx, w_need <= d->w_elems, "ccx_gemm_bf16_desc: W is read up to element %ld, w_elems=%ld", w_need, (long)d->w_elems);
+  if (epi == EPI_HEADS) {
+    CCX_REQUIRE(ctx, p.S > 0 && p.Spad >= p.S && p.n_head > 0 && p.M % p.S == 0, "ccx_gemm_bf16_desc: heads need S > 0, Spad >= S, n_head > 0, M %% S == 0");
+    const long h_need = (long)(p.M / p.S) * p.n_head * p.Spad * 64;
+    CCX_REQUIRE(ctx, h_need <= d->heads_elems, "ccx_gemm_bf16_desc: hq/hk/hv are written up to element %ld, heads_elems=%ld", h_need, (long)d->heads_elems);
+  } else {
+    // rows: the kernels' own remap; a row that is dropped stores nothing and reads row 0 of the residual
+    long max_orow = -1, max_rrow = 0;
+    const bool mod = p.resid_mod > 0 && (epi == EPI_F32_RESID || epi == EPI_F32_GELU_POS);
+    for (int m = 0; m < p.M; m++) {
+      bool valid;
+      const long orow = ccx_gemm_remap_row(p, m, valid);
+      if (!valid) continue;
+      if (orow > max_orow) max_orow = orow;
+      const long rrow = mod ? orow % p.resid_mod : orow;
+      if (rrow > max_rrow) max_rrow = rrow;
+    }
+    const long o_need = max_orow < 0 ? 0 : max_orow * p.ldo + Nw;
+    CCX_REQUIRE(ctx, o_need <= d->out_elems, "ccx_gemm_bf16_desc: out is written up to element %ld, out_elems=%ld", o_need, (long)d->out_elems);
+    const bool res_f32 = epi == EPI_F32_RESID || epi == EPI_F32_GELU_POS || epi == EPI_BF16_LRELU_AFFINE;
+    if (res_f32 && p.resid) {
+      const long r_need = max_rrow * p.ldr + Nw;
+      CCX_REQUIRE(ctx, r_need <= d->resid_elems, "ccx_gemm_bf16_desc: resid is read up to element %ld, resid_elems=%ld", r_need, (long)d->resid_elems);
+    }
+    if (epi == EPI_BF16_ADD_RELU && p.resid_bf16) {
+      const long r_need = max_rrow * p.ldrb + Nw;
+      CCX_REQUIRE(ctx, r_need <= d->resid_bf16_elems, "ccx_gemm_bf16_desc: resid_bf16 is read up to element %ld, resid_bf16_elems=%ld", r_need,
+                  (long)d->resid_bf16_elems);
+    }
+  }
+  return ccx_launch_gemm(ctx, epi, p, (hipStream_t)stream);
+}
+
 int ccx_layernorm(ccx_ctx* ctx, const float* x, const float* gamma, const float* beta, void* out_bf16, float* out_f32,
                   int M, int D, float eps, void* stream) {
   if (!ctx) return CCX_ERR_ARG;

@@ -47,5 +47,20 @@ struct GemmParams {
   int first_block;       // which destination the first d_model columns go to (0=q,1=k)
 };
 
+// Destination row of GEMM row m under the output row remap above (host and device: the descriptor entry point of api.hip bounds
+// a launch with the same arithmetic the kernels store with).
+__host__ __device__ inline long ccx_gemm_remap_row(const GemmParams& p, int m, bool& valid) {
+  if (p.rpb_in <= 0) { valid = true; return m; }
+  int g = m / p.rpb_in;
+  const int i = m - g * p.rpb_in;
+  valid = i < p.rpb_valid;
+  if (p.img_rows_in > 0) {
+    const int img = g / p.img_rows_in, r = g - img * p.img_rows_in;
+    valid = valid && r < p.img_rows_valid;
+    g = img * p.img_rows_out + r;
+  }
+  return (long)g * p.rpb_out + i + p.roff;
+}
+
 // Launch on `stream`.  Returns CCX_OK or an error (message in ctx).
 int ccx_launch_gemm(ccx_ctx* ctx, int epi, const GemmParams& p, hipStream_t stream);

@@ -149,18 +149,7 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, char* smem, i
   }
 }
 
-__device__ __forceinline__ long remap_row(const GemmParams& p, int m, bool& valid) {
-  if (p.rpb_in <= 0) { valid = true; return m; }
-  int g = m / p.rpb_in;
-  const int i = m - g * p.rpb_in;
-  valid = i < p.rpb_valid;
-  if (p.img_rows_in > 0) {
-    const int img = g / p.img_rows_in, r = g - img * p.img_rows_in;
-    valid = valid && r < p.img_rows_valid;
-    g = img * p.img_rows_out + r;
-  }
-  return (long)g * p.rpb_out + i + p.roff;
-}
+__device__ __forceinline__ long remap_row(const GemmParams& p, int m, bool& valid) { return ccx_gemm_remap_row(p, m, valid); }
 
 // One output tile: main loop (a functor (p, smem, m0, n0, acc, swap_tag)) and epilogue.  `acc` as left by a SWAP main loop --
 // lane (l15, h): output row l15 of each row tile, accumulator j = the 4 columns col4(j, h) .. +3 of the wave's 64 -- or by the
@@ -688,9 +677,9 @@ static int launch_epi_geo(ccx_ctx* ctx, const GemmParams& p, hipStream_t stream)
     const double obytes = (EPI == EPI_F32 || EPI == EPI_F32_RESID || EPI == EPI_F32_GELU_POS) ? 4.0 : 2.0;  // output element size
     const double kt = (double)p.K * (p.ntaps > 1 ? p.ntaps : 1);
     // CCX_PROF_SHAPES=1: one label per (epilogue, tile, M, N, K, taps) for shape-level timing tables
-    static const bool by_shape = getenv("CCX_PROF_SHAPES") != nullptr;
+    const bool by_shape = ctx->prof_on && getenv("CCX_PROF_SHAPES") != nullptr;   // read per profiled launch (tests flip it)
     const char* label = "gemm_bf16_nt_kernel";
-    if (by_shape && ctx->prof_on) {
+    if (by_shape) {
       static std::mutex mu;
       static std::map<std::string, std::string> names;
       char buf[160];
@@ -715,9 +704,9 @@ static int launch_phased(ccx_ctx* ctx, const GemmParams& p, hipStream_t stream) 
   {
     const double obytes = (EPI == EPI_F32 || EPI == EPI_F32_RESID || EPI == EPI_F32_GELU_POS) ? 4.0 : 2.0;
     const double kt = (double)p.K * (p.ntaps > 1 ? p.ntaps : 1);
-    static const bool by_shape = getenv("CCX_PROF_SHAPES") != nullptr;
+    const bool by_shape = ctx->prof_on && getenv("CCX_PROF_SHAPES") != nullptr;   // read per profiled launch (tests flip it)
     const char* label = "gemm_bf16_nt_kernel";
-    if (by_shape && ctx->prof_on) {
+    if (by_shape) {
       static std::mutex mu;
       static std::map<std::string, std::string> names;
       char buf[160];
@@ -758,11 +747,39 @@ int ccx_launch_gemm(ccx_ctx* ctx, int epi, const GemmParams& p, hipStream_t stre
     CCX_REQUIRE(ctx, p.d_model % 128 == 0 && p.S > 0 && p.S % 4 == 0 && p.Spad >= p.S && p.Spad % 8 == 0,
                 "gemm heads: bad d_model/S/Spad");
     CCX_REQUIRE(ctx, p.N % 128 == 0, "gemm heads: N must be a multiple of 128");
+    CCX_REQUIRE(ctx, p.n_head > 0 && p.d_model == 64 * p.n_head && p.M % p.S == 0, "gemm heads: d_model must be 64 * n_head and M a multiple of S");
+    const int nblk = p.N / p.d_model;
+    CCX_REQUIRE(ctx, p.N % p.d_model == 0 && p.first_block >= 0 && p.first_block + nblk <= 3,
+                "gemm heads: N=%d from block %d does not fit q/k/v of d_model=%d", p.N, p.first_block, p.d_model);
+    for (int b = p.first_block; b < p.first_block + nblk; b++) {
+      const bf16_t* dst = b == 0 ? p.hq : (b == 1 ? p.hk : p.hv);
+      CCX_REQUIRE(ctx, dst != nullptr && ((uintptr_t)dst & 15) == 0, "gemm heads: hq/hk/hv null or not 16-byte aligned (block %d)", b);
+    }
   } else {
     CCX_REQUIRE(ctx, p.out != nullptr && p.ldo % 8 == 0, "gemm: out null or ldo not a multiple of 8");
     // each lane stores 16 consecutive columns; groups wholly past N are skipped
     CCX_REQUIRE(ctx, p.ldo >= (long)ccx_cdiv(p.N, 16) * 16, "gemm: ldo=%ld must cover N rounded up to 16", p.ldo);
+    CCX_REQUIRE(ctx, ((uintptr_t)p.out & 15) == 0, "gemm: out must be 16-byte aligned");
   }
+  // the residual is fetched like the output is stored: float4 / uint4 pieces at columns up to N rounded up to 16
+  const long Nw = (long)ccx_cdiv(p.N, 16) * 16;
+  const bool res_f32 = epi == EPI_F32_RESID || epi == EPI_F32_GELU_POS || epi == EPI_BF16_LRELU_AFFINE;
+  CCX_REQUIRE(ctx, (epi != EPI_F32_RESID && epi != EPI_F32_GELU_POS) || p.resid != nullptr, "gemm: epilogue %d needs resid", epi);
+  if (res_f32 && p.resid) {
+    CCX_REQUIRE(ctx, ((uintptr_t)p.resid & 15) == 0, "gemm: resid must be 16-byte aligned");
+    CCX_REQUIRE(ctx, p.ldr % 4 == 0 && p.ldr >= Nw, "gemm: ldr=%ld must be a multiple of 4 and cover N rounded up to 16", p.ldr);
+  }
+  if (epi == EPI_BF16_ADD_RELU && p.resid_bf16) {
+    CCX_REQUIRE(ctx, ((uintptr_t)p.resid_bf16 & 15) == 0, "gemm: resid_bf16 must be 16-byte aligned");
+    CCX_REQUIRE(ctx, p.ldrb % 8 == 0 && p.ldrb >= Nw, "gemm: ldrb=%ld must be a multiple of 8 and cover N rounded up to 16", p.ldrb);
+  }
+  CCX_REQUIRE(ctx, p.resid_mod >= 0, "gemm: resid_mod=%d must not be negative", p.resid_mod);
+  CCX_REQUIRE(ctx, p.resid_mod == 0 || epi == EPI_F32_RESID || epi == EPI_F32_GELU_POS,
+              "gemm: resid_mod is honoured by epilogues 2 and 6 only (epilogue %d)", epi);
+  CCX_REQUIRE(ctx, p.rpb_in <= 0 || (p.rpb_valid > 0 && p.rpb_valid <= p.rpb_in),
+              "gemm: row remap needs 0 < rpb_valid <= rpb_in (rpb_valid=%d rpb_in=%d)", p.rpb_valid, p.rpb_in);
+  CCX_REQUIRE(ctx, p.img_rows_in <= 0 || (p.img_rows_valid > 0 && p.img_rows_valid <= p.img_rows_in),
+              "gemm: row remap needs 0 < img_rows_valid <= img_rows_in (img_rows_valid=%d img_rows_in=%d)", p.img_rows_valid, p.img_rows_in);
   switch (epi) {
     case EPI_BF16: return launch_epi<EPI_BF16>(ctx, p, stream);
     case EPI_BF16_GELU: return launch_epi<EPI_BF16_GELU>(ctx, p, stream);

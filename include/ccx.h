@@ -50,6 +50,40 @@ int ccx_gemm_bf16(ccx_ctx* ctx, int epi, const void* A_dev, int64_t lda, const v
                   const float* bias_dev, void* out_dev, int64_t ldo, const float* resid_dev, int64_t ldr,
                   int M, int N, int K, void* stream);
 
+/* The full descriptor of the GEMM family (csrc/gemm_bf16.h GemmParams, field for field and in the same order; device pointers as
+ * const void*), followed by the element count of every buffer.  See gemm_bf16.h for the meaning of each field. */
+typedef struct ccx_gemm_desc {
+  const void* A; const void* W;
+  int64_t lda, ldw;
+  int M, N, K;
+  int ntaps; int64_t a_tap_stride;
+  const void* bias;
+  const void* out;
+  int64_t ldo;
+  const void* resid;
+  int64_t ldr;
+  int resid_mod;
+  const void* scale; const void* shift;
+  float slope;
+  int rpb_in, rpb_out, roff, rpb_valid;
+  int img_rows_in, img_rows_valid, img_rows_out;
+  const void* resid_bf16; int64_t ldrb;
+  const void* hq; const void* hk; const void* hv;
+  int d_model, n_head;
+  int S, Spad;
+  int v_transposed;
+  int first_block;
+  /* elements (of the buffer's own type) that may be touched from each pointer above; heads_elems holds for each of hq / hk / hv */
+  int64_t a_elems, w_elems, out_elems, resid_elems, resid_bf16_elems, heads_elems;
+} ccx_gemm_desc;
+
+/* Every epilogue (0 .. 8), tap, row-remap and operand-view path of the GEMM family from one descriptor -- the launches the model
+ * handles make internally (conv stems, ResNet convolutions as shifted GEMMs, head-major Q/K/V, TDNN + BatchNorm).  Before the launch
+ * the largest element index the kernel can touch in A, W, out, resid, resid_bf16 and hq / hk / hv is computed on the host and
+ * compared with the stated counts: a descriptor that reaches past one of them is refused with CCX_ERR_ARG and a message naming the
+ * buffer; nothing is launched.  For kernel parity tests. */
+int ccx_gemm_bf16_desc(ccx_ctx* ctx, int epi, const ccx_gemm_desc* desc, void* stream);
+
 /* LayerNorm over the last dim with fp32 statistics; writes bf16 and/or fp32 (either may be NULL). */
 int ccx_layernorm(ccx_ctx* ctx, const float* x_dev, const float* gamma_dev, const float* beta_dev,
                   void* out_bf16_dev, float* out_f32_dev, int M, int D, float eps, void* stream);
