@@ -53,6 +53,42 @@ class GemmDesc(C.Structure):
         ("resid_bf16_elems", C.c_int64), ("heads_elems", C.c_int64)]
 
 
+class DecAttnDesc(C.Structure):
+    """ccx_dec_attn_desc (include/ccx.h): one decode attention form on its own."""
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p),
+        ("rows", C.c_int), ("n_seq", C.c_int), ("H", C.c_int), ("kv_T", C.c_int), ("T", C.c_int),
+        ("pos", C.POINTER(C.c_int)), ("row_seq", C.POINTER(C.c_int)), ("rows_per_seq", C.c_int),
+        ("nsplit", C.c_int), ("combine", C.c_int), ("lds_pad", C.c_int),
+        ("x", C.c_void_p), ("pend", C.c_void_p), ("pend_n", C.c_int), ("pend_stride", C.c_int64),
+        ("ln_g", C.c_void_p), ("ln_b", C.c_void_p), ("eps", C.c_float),
+        ("wq_host", C.c_void_p), ("bq", C.c_void_p),
+        ("out", C.c_void_p), ("part_o", C.c_void_p), ("part_ml", C.c_void_p), ("q_x_out", C.c_void_p),
+        ("q_elems", C.c_int64), ("kv_elems", C.c_int64), ("out_elems", C.c_int64), ("part_o_elems", C.c_int64),
+        ("part_ml_elems", C.c_int64), ("x_elems", C.c_int64), ("pend_elems", C.c_int64), ("q_x_out_elems", C.c_int64)]
+
+
+DEC_ATTN_SELF, DEC_ATTN_SPLIT, DEC_ATTN_STREAM, DEC_ATTN_PREFILL, DEC_ATTN_FUSED_Q, DEC_ATTN_TWO_LAUNCH_Q = range(6)
+
+
+class DecSeqState(C.Structure):
+    """ccx_dec_seq_state: the select kernel's per-sequence state."""
+    _fields_ = [(n, C.c_int) for n in ("pos", "prompt_len", "n_gen", "done", "last_tok", "pen_tok", "last_ts_tok", "n_tokens")] + [
+        ("sum_logprob", C.c_float), ("no_speech_prob", C.c_float)]
+
+
+class DecSelectDesc(C.Structure):
+    """ccx_dec_select_desc (include/ccx.h): one launch of the select kernel."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("ld", C.c_int64), ("n_vocab", C.c_int), ("B", C.c_int),
+        ("rules", C.POINTER(DecodeRules)), ("state", C.POINTER(DecSeqState)),
+        ("prompt", C.POINTER(C.c_int)), ("max_prompt", C.c_int), ("sample_len", C.c_int),
+        ("gen", C.POINTER(C.c_int)), ("cur_tok", C.POINTER(C.c_int)), ("pos", C.POINTER(C.c_int)), ("n_done", C.POINTER(C.c_int)),
+        ("tok_emb", C.c_void_p), ("pos_emb", C.c_void_p), ("x", C.c_void_p), ("D", C.c_int),
+        ("sample", C.c_int), ("temperature", C.c_float), ("seed", C.c_uint64), ("row0", C.c_int),
+        ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64)]
+
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _ip = C.POINTER(C.c_int)
 _i32p = C.POINTER(C.c_int32)
@@ -91,6 +127,8 @@ PROTOTYPES = {
     "ccx_whisper_encode": (_i, [_vp, _i, _vp, _vp]),
     "ccx_whisper_decoder_logits": (_i, [_vp, _i32p, _i, _i, _vp, _vp]),
     "ccx_whisper_decode_greedy": (_i, [_vp, _i32p, _i32p, _i, _i, _i, _i32p, _i32p, _fp, _fp, _vp]),
+    "ccx_dec_attention_desc": (_i, [_vp, _i, C.POINTER(DecAttnDesc), _vp]),
+    "ccx_dec_select_step": (_i, [_vp, C.POINTER(DecSelectDesc), _vp]),
     "ccx_whisper_last_cross_path": (_i, [_vp]),
     "ccx_whisper_prepare_lanes": (_i, [_vp, _vp]),
     "ccx_whisper_trace_lanes": (_i, [_vp, C.c_char_p, _i]),

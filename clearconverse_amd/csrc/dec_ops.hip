@@ -1,0 +1,264 @@
+// dec_ops.hip -- the decode step's attention forms and its token-select kernel as stand-alone operators of the C ABI (include/ccx.h:
+// ccx_dec_attention_desc, ccx_dec_select_step).  For kernel parity tests: each entry point fills the parameter block the model handle
+// fills (whisper.hip dec_step / dec_head) and calls the production launchers of decoder.hip unchanged.  Everything the kernels assume is
+// checked on the host first; scratch is owned here and freed on every path.
+#include "../../include/ccx.h"
+#include "ccx_common.h"
+#include "decoder.h"
+
+static_assert(sizeof(ccx_dec_seq_state) == sizeof(DecSeqState), "ccx_dec_seq_state mirrors DecSeqState field for field");
+
+namespace {
+
+__global__ void dec_ops_bf16_to_f32_kernel(const bf16_t* __restrict__ in, float* __restrict__ out, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = bf16_to_f32(in[i]);
+}
+
+// device scratch of one call: everything allocated through it is freed when it goes out of scope
+struct Scratch {
+  std::vector<void*> ptrs;
+  ~Scratch() { for (void* p : ptrs) hipFree(p); }
+  template <class T>
+  hipError_t alloc(T** out, size_t n) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, (n ? n : 1) * sizeof(T));
+    if (e == hipSuccess) { ptrs.push_back(p); *out = (T*)p; }
+    return e;
+  }
+  template <class T>
+  hipError_t upload(T** out, const T* src, size_t n) {
+    hipError_t e = alloc(out, n);
+    if (e == hipSuccess) e = hipMemcpy(*out, src, n * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+  }
+};
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn_desc* d, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_attention_desc: desc is NULL");
+  CCX_REQUIRE(ctx, form >= CCX_DEC_ATTN_SELF && form <= CCX_DEC_ATTN_TWO_LAUNCH_Q, "ccx_dec_attention_desc: unknown form %d", form);
+  const bool is_self = form == CCX_DEC_ATTN_SELF, is_split = form == CCX_DEC_ATTN_SPLIT, is_stream = form == CCX_DEC_ATTN_STREAM;
+  const bool is_prefill = form == CCX_DEC_ATTN_PREFILL, with_q = form == CCX_DEC_ATTN_FUSED_Q || form == CCX_DEC_ATTN_TWO_LAUNCH_Q;
+  const bool partials = is_split || with_q;
+  const bool final_out = is_self || is_stream || is_prefill || (is_split && d->combine);
+  const int rows = d->rows, H = d->H, n_seq = d->n_seq, kv_T = d->kv_T;
+  CCX_REQUIRE(ctx, rows >= 1 && rows <= 65536 && n_seq >= 1 && n_seq <= 65536 && H >= 1 && H <= 64 && kv_T >= 1 && kv_T <= (1 << 20),
+              "ccx_dec_attention_desc: rows=%d, n_seq=%d, H=%d or kv_T=%d out of range", rows, n_seq, H, kv_T);
+  CCX_REQUIRE(ctx, d->k && d->v && aligned16(d->k) && aligned16(d->v), "ccx_dec_attention_desc: k / v null or not 16-byte aligned");
+  // K / V are indexed [sequence][H][kv_T][64] up to the last sequence a row may name
+  const int64_t kv_need = (int64_t)n_seq * H * kv_T * 64;
+  CCX_REQUIRE(ctx, kv_need <= d->kv_elems, "ccx_dec_attention_desc: k / v are read up to element %ld, kv_elems=%ld", (long)kv_need, (long)d->kv_elems);
+  // rows -> sequences
+  if (is_self || is_split || is_prefill) {
+    if (d->row_seq)
+      for (int i = 0; i < rows; i++)
+        CCX_REQUIRE(ctx, d->row_seq[i] >= 0 && d->row_seq[i] < n_seq, "ccx_dec_attention_desc: row_seq[%d] = %d out of range [0, %d)", i, d->row_seq[i], n_seq);
+    else CCX_REQUIRE(ctx, rows <= n_seq, "ccx_dec_attention_desc: row_seq is NULL with more rows (%d) than sequences (%d)", rows, n_seq);
+  } else {
+    CCX_REQUIRE(ctx, d->row_seq == nullptr, "ccx_dec_attention_desc: row_seq is not taken by form %d (row r reads sequence r)", form);
+    CCX_REQUIRE(ctx, rows <= n_seq, "ccx_dec_attention_desc: more rows (%d) than sequences (%d)", rows, n_seq);
+  }
+  if (is_prefill) {
+    const int P = d->rows_per_seq;
+    CCX_REQUIRE(ctx, P >= 2 && P <= 4096, "ccx_dec_attention_desc: rows_per_seq = %d, the prefill form needs >= 2", P);
+    CCX_REQUIRE(ctx, d->row_seq && rows % P == 0, "ccx_dec_attention_desc: rows_per_seq needs row_seq and a multiple of it in rows");
+    for (int i = 0; i < rows; i++) {
+      CCX_REQUIRE(ctx, d->row_seq[i] == d->row_seq[i - i % P], "ccx_dec_attention_desc: row %d is not in its group's sequence (row_seq)", i);
+      // the prefill kernels take the sequence from the block index: group g reads sequence g
+      CCX_REQUIRE(ctx, d->row_seq[i] == i / P, "ccx_dec_attention_desc: row_seq[%d] = %d, the prefill form needs group g on sequence g", i, d->row_seq[i]);
+    }
+  } else CCX_REQUIRE(ctx, d->rows_per_seq <= 1, "ccx_dec_attention_desc: rows_per_seq = %d is taken by the prefill form only", d->rows_per_seq);
+  // key range
+  if (is_self) {
+    CCX_REQUIRE(ctx, d->pos != nullptr, "ccx_dec_attention_desc: pos is NULL");
+    for (int i = 0; i < rows; i++)
+      CCX_REQUIRE(ctx, d->pos[i] >= 0 && d->pos[i] < kv_T, "ccx_dec_attention_desc: pos[%d] = %d out of range [0, kv_T = %d)", i, d->pos[i], kv_T);
+  } else {
+    CCX_REQUIRE(ctx, d->pos == nullptr, "ccx_dec_attention_desc: pos is taken by the self form only");
+    CCX_REQUIRE(ctx, d->T >= 1 && d->T <= kv_T, "ccx_dec_attention_desc: T = %d out of range [1, kv_T = %d]", d->T, kv_T);
+  }
+  if (is_prefill) CCX_REQUIRE(ctx, d->T <= 1536, "ccx_dec_attention_desc: T = %d, the prefill form streams at most 1536 keys per block", d->T);
+  const int nsplit = partials ? d->nsplit : 1;
+  CCX_REQUIRE(ctx, nsplit >= 1 && nsplit <= 8, "ccx_dec_attention_desc: nsplit = %d out of range [1, 8]", d->nsplit);
+  CCX_REQUIRE(ctx, d->lds_pad >= 0 && d->lds_pad <= 128 * 1024 && ((is_split || is_stream) || d->lds_pad == 0),
+              "ccx_dec_attention_desc: lds_pad = %d out of range [0, 131072] or given to a form that has none", d->lds_pad);
+  // operands and outputs
+  if (!with_q) {
+    CCX_REQUIRE(ctx, d->q && aligned16(d->q), "ccx_dec_attention_desc: q null or not 16-byte aligned");
+    CCX_REQUIRE(ctx, (int64_t)rows * H * 64 <= d->q_elems, "ccx_dec_attention_desc: q is read up to element %ld, q_elems=%ld", (long)rows * H * 64, (long)d->q_elems);
+  }
+  if (final_out) {
+    CCX_REQUIRE(ctx, d->out != nullptr, "ccx_dec_attention_desc: out is NULL");
+    CCX_REQUIRE(ctx, (int64_t)rows * H * 64 <= d->out_elems, "ccx_dec_attention_desc: out is written up to element %ld, out_elems=%ld", (long)rows * H * 64, (long)d->out_elems);
+  }
+  if (partials) {
+    CCX_REQUIRE(ctx, d->part_o && d->part_ml && aligned16(d->part_o) && aligned16(d->part_ml), "ccx_dec_attention_desc: part_o / part_ml null or not 16-byte aligned");
+    const int64_t po = (int64_t)rows * H * nsplit * 64, pml = (int64_t)rows * H * nsplit * 2;
+    CCX_REQUIRE(ctx, po <= d->part_o_elems, "ccx_dec_attention_desc: part_o is written up to element %ld, part_o_elems=%ld", (long)po, (long)d->part_o_elems);
+    CCX_REQUIRE(ctx, pml <= d->part_ml_elems, "ccx_dec_attention_desc: part_ml is written up to element %ld, part_ml_elems=%ld", (long)pml, (long)d->part_ml_elems);
+  }
+  if (with_q) {
+    // exactly what ccx_launch_dec_cross_fused_q requires, plus the extents
+    CCX_REQUIRE(ctx, rows <= 16 && H == 12, "ccx_dec_attention_desc: the fused query needs rows <= 16 (got %d) and H == 12 (got %d)", rows, H);
+    CCX_REQUIRE(ctx, d->x && d->pend && d->ln_g && d->ln_b && d->bq && d->wq_host, "ccx_dec_attention_desc: x, pend, ln_g, ln_b, bq or wq_host is NULL");
+    CCX_REQUIRE(ctx, aligned16(d->x) && aligned16(d->pend) && aligned16(d->ln_g) && aligned16(d->ln_b) && aligned16(d->bq),
+                "ccx_dec_attention_desc: x, pend, ln_g, ln_b or bq not 16-byte aligned");
+    CCX_REQUIRE(ctx, d->pend_n >= 0 && d->pend_n <= 4, "ccx_dec_attention_desc: pend_n = %d out of range [0, 4]", d->pend_n);
+    CCX_REQUIRE(ctx, d->pend_stride >= (int64_t)rows * 768 && d->pend_stride % 4 == 0, "ccx_dec_attention_desc: pend_stride = %ld smaller than a slab or not a multiple of 4", (long)d->pend_stride);
+    CCX_REQUIRE(ctx, (int64_t)rows * 768 <= d->x_elems, "ccx_dec_attention_desc: x is read up to element %ld, x_elems=%ld", (long)rows * 768, (long)d->x_elems);
+    const int64_t pn = (int64_t)((d->pend_n > 1 ? d->pend_n : 1) - 1) * d->pend_stride + (int64_t)rows * 768;
+    CCX_REQUIRE(ctx, pn <= d->pend_elems, "ccx_dec_attention_desc: pend is read up to element %ld, pend_elems=%ld", (long)pn, (long)d->pend_elems);
+    if (d->q_x_out) {
+      CCX_REQUIRE(ctx, aligned16(d->q_x_out) && d->q_x_out != d->x, "ccx_dec_attention_desc: q_x_out not 16-byte aligned or aliasing x");
+      CCX_REQUIRE(ctx, (int64_t)rows * 768 <= d->q_x_out_elems, "ccx_dec_attention_desc: q_x_out is written up to element %ld, q_x_out_elems=%ld", (long)rows * 768, (long)d->q_x_out_elems);
+    }
+  }
+
+  Scratch sc;
+#define DO_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return ccx_fail(ctx, CCX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+  DecAttnParams ap;
+  memset(&ap, 0, sizeof(ap));
+  ap.q = (const float*)d->q; ap.k = (const bf16_t*)d->k; ap.v = (const bf16_t*)d->v; ap.H = H; ap.kv_T = kv_T; ap.T = is_self ? 0 : d->T;
+  ap.scale_log2e = 0.125f * 1.4426950408889634f;
+  ap.part_o = (float*)d->part_o; ap.part_ml = (float*)d->part_ml; ap.lds_pad = d->lds_pad;
+  const long n_out = (long)rows * H * 64;
+  bf16_t* d_out16 = nullptr;
+  if (final_out) {
+    DO_HIP(sc.alloc(&d_out16, (size_t)n_out));
+    DO_HIP(hipMemsetAsync(d_out16, 0xFF, (size_t)n_out * 2, stream));     // NaN bit patterns: a block that never stores shows in out
+    ap.out_bf16 = d_out16;
+  }
+  int* d_pos = nullptr; int* d_rs = nullptr;
+  if (is_self) { DO_HIP(sc.upload(&d_pos, d->pos, (size_t)rows)); ap.pos = d_pos; }
+  if (d->row_seq) { DO_HIP(sc.upload(&d_rs, d->row_seq, (size_t)rows)); ap.row_seq = d_rs; }
+  bf16_t* d_wq = nullptr; float* d_q = nullptr;
+  if (with_q) {
+    const std::vector<bf16_t> packed = pack_mfma_rows(d->wq_host, 768, 768, 16);
+    DO_HIP(sc.upload(&d_wq, packed.data(), packed.size()));
+  }
+  int rc = CCX_OK;
+  if (is_self) rc = ccx_launch_dec_attention(ctx, ap, rows, 1, true, stream);
+  else if (is_split) {
+    rc = ccx_launch_dec_attention(ctx, ap, rows, nsplit, false, stream);
+    if (rc == CCX_OK && d->combine) rc = ccx_launch_dec_combine(ctx, ap.part_o, ap.part_ml, nsplit, d_out16, rows, H, stream);
+  } else if (is_stream) {
+    ap.stream_mode = 1;
+    rc = ccx_launch_dec_attention(ctx, ap, rows, 1, true, stream);
+  } else if (is_prefill) {
+    ap.stream_mode = 1; ap.rows_per_seq = d->rows_per_seq;
+    rc = ccx_launch_dec_attention(ctx, ap, rows / d->rows_per_seq, 1, true, stream);
+  } else if (form == CCX_DEC_ATTN_FUSED_Q) {
+    ap.qx = (const float*)d->x; ap.q_pend = (const float*)d->pend; ap.q_pend_n = d->pend_n; ap.q_pend_stride = (long)d->pend_stride;
+    ap.q_x_out = (float*)d->q_x_out; ap.q_ln_g = (const float*)d->ln_g; ap.q_ln_b = (const float*)d->ln_b; ap.q_eps = d->eps;
+    ap.q_W = d_wq; ap.q_bias = (const float*)d->bq; ap.q_K = 768;
+    rc = ccx_launch_dec_cross_fused_q(ctx, ap, rows, nsplit, stream);
+  } else {
+    DO_HIP(sc.alloc(&d_q, (size_t)rows * 768));
+    DecLinearParams lp;
+    memset(&lp, 0, sizeof(lp));
+    lp.M = rows; lp.N = 768; lp.K = 768; lp.W = d_wq; lp.ldw = 768; lp.bias = (const float*)d->bq; lp.out = d_q; lp.ldo = 768;
+    lp.x = (const float*)d->x; lp.pend = (const float*)d->pend; lp.pend_n = d->pend_n; lp.pend_stride = (long)d->pend_stride;
+    lp.x_out = (float*)d->q_x_out; lp.ln_g = (const float*)d->ln_g; lp.ln_b = (const float*)d->ln_b; lp.eps = d->eps;
+    rc = ccx_launch_dec_linear(ctx, ACT_LN, DEPI_F32, lp, stream);
+    ap.q = d_q;
+    if (rc == CCX_OK) rc = ccx_launch_dec_attention(ctx, ap, rows, nsplit, false, stream);
+  }
+  if (rc == CCX_OK && final_out) {
+    hipLaunchKernelGGL(dec_ops_bf16_to_f32_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, d_out16, (float*)d->out, n_out);
+    DO_HIP(hipGetLastError());
+  }
+  DO_HIP(hipStreamSynchronize(stream));      // the scratch is freed on return
+  return rc;
+}
+
+extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_select_step: desc is NULL");
+  const int V = d->n_vocab, B = d->B, D = d->D;
+  CCX_REQUIRE(ctx, B >= 1 && B <= 65536, "ccx_dec_select_step: B = %d out of range", B);
+  CCX_REQUIRE(ctx, V >= 4 && V % 4 == 0 && V <= 13 * 4096, "ccx_dec_select_step: n_vocab = %d must be a multiple of 4 and <= 53248", V);
+  CCX_REQUIRE(ctx, d->ld >= V && d->ld % 4 == 0, "ccx_dec_select_step: ld = %ld must be >= n_vocab and a multiple of 4", (long)d->ld);
+  CCX_REQUIRE(ctx, d->logits && aligned16(d->logits), "ccx_dec_select_step: logits null or not 16-byte aligned");
+  CCX_REQUIRE(ctx, (int64_t)(B - 1) * d->ld + V <= d->logits_elems, "ccx_dec_select_step: logits are read up to element %ld, logits_elems=%ld",
+              (long)((int64_t)(B - 1) * d->ld + V), (long)d->logits_elems);
+  CCX_REQUIRE(ctx, d->rules && d->state && d->gen && d->cur_tok && d->pos && d->n_done, "ccx_dec_select_step: rules, state, gen, cur_tok, pos or n_done is NULL");
+  const ccx_decode_rules& r = *d->rules;
+  std::vector<unsigned char> mask;
+  CCX_TRY(ccx_build_suppress_mask(ctx, "ccx_dec_select_step", &r, V, mask));
+  CCX_REQUIRE(ctx, r.no_speech >= 0 && r.timestamp_begin >= 0 && r.blank >= 0, "ccx_dec_select_step: rules.no_speech, timestamp_begin or blank negative");
+  CCX_REQUIRE(ctx, d->sample_len >= 1 && d->sample_len <= (1 << 20), "ccx_dec_select_step: sample_len = %d out of range", d->sample_len);
+  CCX_REQUIRE(ctx, d->max_prompt >= 0 && (d->max_prompt == 0 || d->prompt), "ccx_dec_select_step: prompt is NULL with max_prompt = %d", d->max_prompt);
+  CCX_REQUIRE(ctx, D >= 4 && D % 4 == 0 && D <= 4096, "ccx_dec_select_step: D = %d must be a multiple of 4 in [4, 4096]", D);
+  CCX_REQUIRE(ctx, d->tok_emb && d->pos_emb && d->x && aligned16(d->tok_emb) && aligned16(d->pos_emb) && aligned16(d->x),
+              "ccx_dec_select_step: tok_emb, pos_emb or x null or not 16-byte aligned");
+  CCX_REQUIRE(ctx, (int64_t)V * D <= d->tok_emb_elems, "ccx_dec_select_step: tok_emb is read up to element %ld, tok_emb_elems=%ld", (long)V * D, (long)d->tok_emb_elems);
+  CCX_REQUIRE(ctx, (int64_t)B * D <= d->x_elems, "ccx_dec_select_step: x is written up to element %ld, x_elems=%ld", (long)B * D, (long)d->x_elems);
+  const int64_t pos_rows = d->pos_emb_elems / D;
+  CCX_REQUIRE(ctx, d->sample == 0 || d->sample == 1, "ccx_dec_select_step: sample = %d must be 0 or 1", d->sample);
+  CCX_REQUIRE(ctx, d->sample || d->temperature == 0.f, "ccx_dec_select_step: temperature %g needs sample = 1", (double)d->temperature);
+  CCX_REQUIRE(ctx, d->temperature >= 0.f && d->row0 >= 0, "ccx_dec_select_step: temperature or row0 negative");
+  for (int b = 0; b < B; b++) {
+    const ccx_dec_seq_state& s = d->state[b];
+    CCX_REQUIRE(ctx, s.n_gen >= 0 && s.n_gen <= d->sample_len, "ccx_dec_select_step: state[%d].n_gen = %d out of range [0, sample_len = %d]", b, s.n_gen, d->sample_len);
+    CCX_REQUIRE(ctx, s.pos >= 0 && s.pos + 1 < pos_rows, "ccx_dec_select_step: state[%d].pos = %d, pos + 1 must be a row of pos_emb (%ld rows)", b, s.pos, (long)pos_rows);
+    CCX_REQUIRE(ctx, s.prompt_len >= 0 && s.prompt_len <= d->max_prompt, "ccx_dec_select_step: state[%d].prompt_len = %d out of range [0, max_prompt = %d]", b, s.prompt_len, d->max_prompt);
+    CCX_REQUIRE(ctx, s.done == 0 || s.done == 1, "ccx_dec_select_step: state[%d].done = %d must be 0 or 1", b, s.done);
+    const bool prompt_phase = s.pos < s.prompt_len - 1;
+    if (prompt_phase) {
+      const int tok = d->prompt[(size_t)b * d->max_prompt + s.pos + 1];
+      CCX_REQUIRE(ctx, tok >= 0 && tok < V, "ccx_dec_select_step: prompt[%d][%d] = %d out of range", b, s.pos + 1, tok);
+    } else if (!s.done) {
+      // a live row in the sampling phase writes gen[n_gen]
+      CCX_REQUIRE(ctx, s.n_gen < d->sample_len, "ccx_dec_select_step: state[%d].n_gen = %d leaves no room in gen (sample_len = %d)", b, s.n_gen, d->sample_len);
+      CCX_REQUIRE(ctx, s.last_tok < V && s.pen_tok < V && s.last_ts_tok < V, "ccx_dec_select_step: state[%d] holds a token id >= n_vocab", b);
+    }
+  }
+
+  Scratch sc;
+  unsigned char* d_mask = nullptr; DecSeqState* d_state = nullptr;
+  int *d_prompt = nullptr, *d_cur = nullptr, *d_pos = nullptr, *d_gen = nullptr, *d_ndone = nullptr;
+  unsigned* d_cfg = nullptr;
+  const size_t n_gen_tab = (size_t)B * d->sample_len;
+  constexpr int kGuard = 16;                 // sentinel words behind the gen table: a write past sample_len of the last row
+  std::vector<int> gen_h(n_gen_tab + kGuard, 0x5a5a5a5a);
+  memcpy(gen_h.data(), d->gen, n_gen_tab * 4);
+  DO_HIP(sc.upload(&d_mask, mask.data(), mask.size()));
+  DO_HIP(sc.upload(&d_state, (const DecSeqState*)d->state, (size_t)B));
+  if (d->max_prompt > 0) DO_HIP(sc.upload(&d_prompt, d->prompt, (size_t)B * d->max_prompt));
+  DO_HIP(sc.upload(&d_cur, d->cur_tok, (size_t)B));
+  DO_HIP(sc.upload(&d_pos, d->pos, (size_t)B));
+  DO_HIP(sc.upload(&d_gen, gen_h.data(), gen_h.size()));
+  DO_HIP(sc.upload(&d_ndone, d->n_done, (size_t)1));
+  unsigned cfg[4] = {0u, (unsigned)(d->seed & 0xffffffffu), (unsigned)(d->seed >> 32), 0u};
+  memcpy(&cfg[0], &d->temperature, 4);
+  DO_HIP(sc.upload(&d_cfg, cfg, (size_t)4));
+
+  DecSelectParams sp;
+  memset(&sp, 0, sizeof(sp));
+  sp.logits = (const float*)d->logits; sp.ld_logits = (long)d->ld; sp.n_vocab = V; sp.state = d_state; sp.prompt = d_prompt;
+  sp.max_prompt = d->max_prompt; sp.cur_tok = d_cur; sp.pos = d_pos; sp.gen = d_gen; sp.sample_len = d->sample_len;
+  sp.n_done = d_ndone; sp.suppress_mask = d_mask; sp.eot = r.eot; sp.blank = r.blank;
+  sp.no_speech = r.no_speech; sp.timestamp_begin = r.timestamp_begin;
+  sp.max_initial_ts = r.max_initial_timestamp_index;
+  sp.tok_emb = (const float*)d->tok_emb; sp.pos_emb = (const float*)d->pos_emb; sp.x = (float*)d->x; sp.D = D;
+  sp.sample_cfg = d_cfg; sp.row0 = d->row0; sp.sample = d->sample;
+  CCX_TRY(ccx_launch_dec_select(ctx, sp, B, stream));
+  DO_HIP(hipStreamSynchronize(stream));
+  DO_HIP(hipMemcpy(gen_h.data(), d_gen, gen_h.size() * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < kGuard; i++)
+    if (gen_h[n_gen_tab + i] != 0x5a5a5a5a) return ccx_fail(ctx, CCX_ERR_STATE, "ccx_dec_select_step: the kernel wrote behind the gen table (word %d)", i);
+  memcpy(d->gen, gen_h.data(), n_gen_tab * 4);
+  DO_HIP(hipMemcpy(d->state, d_state, (size_t)B * sizeof(DecSeqState), hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->cur_tok, d_cur, (size_t)B * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->pos, d_pos, (size_t)B * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->n_done, d_ndone, 4, hipMemcpyDeviceToHost));
+#undef DO_HIP
+  return CCX_OK;
+}

@@ -1,5 +1,7 @@
 // decoder.h -- parameter blocks and launchers for the decoder step kernels (decoder.hip).
 #pragma once
+#include <vector>
+#include "../../include/ccx.h"
 #include "ccx_common.h"
 
 enum { ACT_LN = 0, ACT_BF16 = 1, ACT_COMBINE = 2 };
@@ -97,3 +99,39 @@ int ccx_launch_dec_embed(ccx_ctx* ctx, const float* tok_emb, const float* pos_em
 int ccx_launch_dec_gather_rows(ccx_ctx* ctx, const bf16_t* src, const int* idx, bf16_t* dst, int n, int D, hipStream_t stream);
 int ccx_launch_dec_combine(ccx_ctx* ctx, const float* part_o, const float* part_ml, int nsplit, bf16_t* out, int M, int H,
                            hipStream_t stream);
+
+// ---- host helpers shared by the model handle (whisper.hip) and the stand-alone operators (dec_ops.hip) -----------------------
+// Weights of dec_linear_kernel / dec_cross_fused_q_kernel are stored MFMA-fragment-packed: tile (n/16, k/32) is 64 consecutive
+// 16-byte chunks, chunk l = row n0 + (l & 15), columns k0 + 8*(l >> 4) .. +8.  Rows are zero padded to a multiple of `row_pad`.
+static inline std::vector<bf16_t> pack_mfma_rows(const float* src, int N, int K, int row_pad) {
+  const int Np = (N + row_pad - 1) / row_pad * row_pad;
+  const int kst = K / 32;
+  std::vector<bf16_t> tmp((size_t)Np * K, 0);
+  for (int nt = 0; nt < Np / 16; nt++)
+    for (int ks = 0; ks < kst; ks++)
+      for (int l = 0; l < 64; l++) {
+        const int n = nt * 16 + (l & 15), k0 = ks * 32 + 8 * (l >> 4);
+        bf16_t* dst = &tmp[(((size_t)nt * kst + ks) * 64 + l) * 8];
+        if (n < N)
+          for (int j = 0; j < 8; j++) dst[j] = ccx_host_f32_to_bf16(src[(size_t)n * K + k0 + j]);
+      }
+  return tmp;
+}
+
+// The select kernel's suppress mask [V + 4] from the decode rules: SuppressTokens plus <|notimestamps|>, which ApplyTimestampRules
+// bans at every step.  Checks the rule ids against the vocabulary; `who` is the entry point the messages name.
+static inline int ccx_build_suppress_mask(ccx_ctx* ctx, const char* who, const ccx_decode_rules* r, int V, std::vector<unsigned char>& mask) {
+  CCX_REQUIRE(ctx, r->eot >= 0 && r->eot < V, "%s: rules.eot = %d out of range [0, n_vocab = %d)", who, r->eot, V);
+  CCX_REQUIRE(ctx, r->sot < V, "%s: rules.sot = %d out of range (n_vocab = %d)", who, r->sot, V);
+  CCX_REQUIRE(ctx, r->no_speech < V, "%s: rules.no_speech = %d out of range (n_vocab = %d)", who, r->no_speech, V);
+  CCX_REQUIRE(ctx, r->timestamp_begin <= V, "%s: rules.timestamp_begin = %d behind n_vocab = %d", who, r->timestamp_begin, V);
+  CCX_REQUIRE(ctx, r->blank < V, "%s: rules.blank = %d out of range (n_vocab = %d)", who, r->blank, V);
+  CCX_REQUIRE(ctx, r->no_timestamps < V, "%s: rules.no_timestamps = %d out of range (n_vocab = %d)", who, r->no_timestamps, V);
+  mask.assign((size_t)V + 4, 0);
+  for (int i = 0; i < r->n_suppress; i++) {
+    CCX_REQUIRE(ctx, r->suppress[i] >= 0 && r->suppress[i] < V, "%s: rules.suppress[%d] = %d out of range [0, n_vocab = %d)", who, i, r->suppress[i], V);
+    mask[r->suppress[i]] = 1;
+  }
+  if (r->no_timestamps >= 0) mask[r->no_timestamps] = 1;  // ApplyTimestampRules bans <|notimestamps|>
+  return CCX_OK;
+}

@@ -1550,7 +1550,9 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
   // timestamp_logprob > max_text_token_logprob  <=>  lse_ts > max_text (same normaliser)
   const float lse_ts = (se_ts > 0.f) ? mx_all + logf(se_ts) : -INFINITY;
   const bool force_ts = lse_ts > bt;
-  const float lse = force_ts ? lse_ts : mx_all + logf(se_text + se_ts);   // log-normaliser of the re-filtered logits
+  // log-normaliser of the re-filtered logits, kept relative to mx_all: the log-probability is (x - mx_all) - lnorm, two numbers of
+  // the softmax's own magnitude, so that a common offset of the logits does not cost it the offset's ulp
+  const float lnorm = logf(force_ts ? se_ts : se_text + se_ts);
 
   // ---- temperature > 0: Categorical(logits / T) by the Gumbel-max trick (argmax of logits / T + Gumbel noise) ----
   const float temperature = SAMPLE ? __uint_as_float(p.sample_cfg[0]) : 0.f;
@@ -1585,13 +1587,13 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
     int next; float logprob;
     if (samp >= 0) {
       next = samp;
-      logprob = samp_logit - lse;
+      logprob = (samp_logit - mx_all) - lnorm;
     } else if (force_ts) {
       next = is;
-      logprob = bs - lse;   // log_softmax over the re-filtered logits (text banned)
+      logprob = (bs - mx_all) - lnorm;   // log_softmax over the re-filtered logits (text banned)
     } else {
       if (bt > bs || (bt == bs && it < is)) next = it; else next = is;
-      logprob = fmaxf(bt, bs) - lse;
+      logprob = -lnorm;                 // the winner is mx_all itself
     }
     s.sum_logprob += logprob;
     p.gen[(long)b * p.sample_len + i_gen] = next;

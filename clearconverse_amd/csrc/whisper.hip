@@ -144,22 +144,9 @@ struct ccx_whisper {
 
 namespace {
 
-// Decode-side weights are stored MFMA-fragment-packed for dec_linear_kernel: tile (n/16, k/32) is 64
-// consecutive 16-byte chunks, chunk l = row n0 + (l & 15), columns k0 + 8*(l >> 4) .. +8.
-// Rows are zero padded to a multiple of `row_pad`.
+// Decode-side weights are stored MFMA-fragment-packed for dec_linear_kernel (decoder.h pack_mfma_rows).
 int up_bf16_packed(ccx_whisper* w, bf16_t** out, const float* src, int N, int K, int row_pad) {
-  const int Np = (N + row_pad - 1) / row_pad * row_pad;
-  const int kst = K / 32;
-  std::vector<bf16_t> tmp((size_t)Np * K, 0);
-  for (int nt = 0; nt < Np / 16; nt++)
-    for (int ks = 0; ks < kst; ks++)
-      for (int l = 0; l < 64; l++) {
-        const int n = nt * 16 + (l & 15), k0 = ks * 32 + 8 * (l >> 4);
-        bf16_t* dst = &tmp[(((size_t)nt * kst + ks) * 64 + l) * 8];
-        if (n < N)
-          for (int j = 0; j < 8; j++) dst[j] = ccx_host_f32_to_bf16(src[(size_t)n * K + k0 + j]);
-      }
-  return w->store.upload(out, tmp);
+  return w->store.upload(out, pack_mfma_rows(src, N, K, row_pad));
 }
 
 // conv weight [out][in][3] -> GEMM weight [out][Kpad] with k = tap*in + c
@@ -302,14 +289,8 @@ int ccx_whisper_set_rules(ccx_whisper* w, const ccx_decode_rules* r) {
   if (!w) return CCX_ERR_ARG;
   CCX_REQUIRE(w->ctx, r, "whisper: rules null");
   const int V = w->d.n_vocab;
-  CCX_REQUIRE(w->ctx, r->eot >= 0 && r->eot < V && r->sot < V && r->no_speech < V && r->timestamp_begin <= V && r->blank < V &&
-                          r->no_timestamps < V, "whisper: rule token id out of range");
-  std::vector<unsigned char> mask((size_t)V + 4, 0);
-  for (int i = 0; i < r->n_suppress; i++) {
-    CCX_REQUIRE(w->ctx, r->suppress[i] >= 0 && r->suppress[i] < V, "whisper: suppress id %d out of range", r->suppress[i]);
-    mask[r->suppress[i]] = 1;
-  }
-  if (r->no_timestamps >= 0) mask[r->no_timestamps] = 1;  // ApplyTimestampRules bans <|notimestamps|>
+  std::vector<unsigned char> mask;
+  CCX_TRY(ccx_build_suppress_mask(w->ctx, "ccx_whisper_set_rules", r, V, mask));
   if (!w->suppress_mask) CCX_TRY(w->store.alloc(&w->suppress_mask, (size_t)V + 4, false));
   CCX_HIP(w->ctx, hipMemcpy(w->suppress_mask, mask.data(), (size_t)V + 4, hipMemcpyHostToDevice));
   w->rules = *r;

@@ -211,6 +211,69 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
                        int sample_len, float temperature, uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out,
                        float* sum_logprob_out, float* no_speech_prob_out, void* stream);
 
+/* ---- the decode step's attention and token-select kernels on their own (csrc/decoder.hip; for kernel parity tests) ---------
+ * Both entry points check on the host everything the kernels assume (ranges, element counts, 16-byte alignment of every
+ * vector-accessed pointer) before anything is launched: a violation returns CCX_ERR_ARG (1) with a message naming the field.
+ * They own their scratch, free it on every path and synchronise the stream. */
+#define CCX_DEC_ATTN_SELF 0          /* dec_attention_kernel<true>: keys [0, pos[row]] */
+#define CCX_DEC_ATTN_SPLIT 1         /* dec_attention_kernel<false> (nsplit partials), then dec_combine_kernel if `combine` */
+#define CCX_DEC_ATTN_STREAM 2        /* stream_mode = 1: dec_cross_stream_kernel<true, NP>; T > 1536 falls back to dec_attention_kernel<true> */
+#define CCX_DEC_ATTN_PREFILL 3       /* rows_per_seq == 2: dec_cross_stream_kernel<.., true>; >= 3: dec_cross_prefill_kernel<NP, 4> */
+#define CCX_DEC_ATTN_FUSED_Q 4       /* ccx_launch_dec_cross_fused_q: q = LN(x + pending slabs) Wq^T + bq inside the attention blocks */
+#define CCX_DEC_ATTN_TWO_LAUNCH_Q 5  /* dec_linear<ACT_LN, DEPI_F32>, then dec_attention_kernel<false>: what FUSED_Q replaces */
+
+typedef struct ccx_dec_attn_desc {
+  /* device operands.  q f32 [rows][H][64] (forms 0..3); k, v bf16 [n_seq][H][kv_T][64] */
+  const void* q; const void* k; const void* v;
+  int rows, n_seq, H, kv_T;
+  int T;                    /* keys [0, T) of the cross forms (1..5) */
+  const int* pos;           /* HOST [rows], form 0: row r attends to keys [0, pos[r]] */
+  const int* row_seq;       /* HOST [rows] or NULL (row r reads sequence r): forms 0, 1, 3 */
+  int rows_per_seq;         /* form 3: consecutive groups of that many rows belong to one sequence (group g = sequence g) */
+  int nsplit, combine;      /* forms 1, 4, 5: key splits (1..8); form 1: also run dec_combine_kernel into out */
+  int lds_pad;              /* forms 1, 2: dynamic LDS the blocks claim without using it */
+  /* forms 4, 5 (H must be 12): x f32 [rows][768], pend f32 [max(pend_n, 1)] slabs of [rows][768] pend_stride elements apart (slab 0
+   * is read, with weight 0, also when pend_n == 0), ln_g / ln_b / bq f32 [768] on the device, wq f32 [768][768] row-major on the HOST */
+  const void* x; const void* pend; int pend_n; int64_t pend_stride;
+  const void* ln_g; const void* ln_b; float eps;
+  const float* wq_host; const void* bq;
+  /* device outputs: out f32 [rows][H * 64] (the kernels' bf16 output widened; forms 0, 2, 3 and form 1 with combine),
+   * part_o f32 [rows][H][nsplit][64], part_ml f32 [rows][H][nsplit][2] (forms 1, 4, 5), q_x_out f32 [rows][768] (forms 4, 5, may be NULL) */
+  void* out; void* part_o; void* part_ml; void* q_x_out;
+  /* elements (of the buffer's own type) behind each pointer; kv_elems holds for k and for v */
+  int64_t q_elems, kv_elems, out_elems, part_o_elems, part_ml_elems, x_elems, pend_elems, q_x_out_elems;
+} ccx_dec_attn_desc;
+
+/* Fills a DecAttnParams and calls the production launchers unchanged (ccx_launch_dec_attention, ccx_launch_dec_combine,
+ * ccx_launch_dec_cross_fused_q, ccx_launch_dec_linear).  Softmax scale 1/8.  With the profile on (ccx_prof_enable) the records name
+ * the instantiation that ran. */
+int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn_desc* desc, void* stream);
+
+/* Per-sequence state of the select kernel (csrc/decoder.h DecSeqState, field for field). */
+typedef struct ccx_dec_seq_state {
+  int pos, prompt_len, n_gen, done;
+  int last_tok, pen_tok, last_ts_tok, n_tokens;
+  float sum_logprob, no_speech_prob;
+} ccx_dec_seq_state;
+
+typedef struct ccx_dec_select_desc {
+  const void* logits; int64_t ld; int n_vocab; int B;   /* device f32 [B][ld] */
+  const ccx_decode_rules* rules;                        /* the suppress mask is built as ccx_whisper_set_rules builds it */
+  ccx_dec_seq_state* state;                             /* HOST [B], in and out */
+  const int* prompt; int max_prompt;                    /* HOST [B][max_prompt] */
+  int sample_len;
+  int* gen;                                             /* HOST [B][sample_len], in and out */
+  int* cur_tok; int* pos;                               /* HOST [B], in and out */
+  int* n_done;                                          /* HOST [1], in and out */
+  const void* tok_emb; const void* pos_emb; void* x; int D;   /* device f32 [tok rows][D], [pos rows][D], [B][D] (in and out) */
+  int sample; float temperature; uint64_t seed; int row0;     /* sample 1: the kernel with the temperature > 0 branch */
+  int64_t logits_elems, tok_emb_elems, pos_emb_elems, x_elems;
+} ccx_dec_select_desc;
+
+/* One launch of the select kernel (ccx_launch_dec_select) for B rows: filters, argmax / sampling, the per-sequence state machine and
+ * the next step's embedding x[b] = tok_emb[next] + pos_emb[pos]. */
+int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* desc, void* stream);
+
 /* Which cross-attention formulation the last ccx_whisper_decode of this instance ran (measurement / test records; the reference has one
  * formulation, MultiHeadAttention.forward(x, xa) behind back/api.py:1286-1292): 0 = "kv16" (per-layer K / V caches, split-KV kernels,
  * <= 16 sequences), 1 = "kv_stream" (per-layer K / V caches, dec_cross_stream_kernel, 17 - 80 sequences), 2 = "xa_stream" (one pass over
