@@ -89,6 +89,23 @@ class DecSelectDesc(C.Structure):
         ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64)]
 
 
+class SepDesc(C.Structure):
+    """ccx_sep_desc (include/ccx.h): one SepFormer layer kernel on its own."""
+    _fields_ = (
+        [(n, C.c_void_p) for n in ("h", "xin", "y", "qkv", "att", "feats", "fc")]
+        + [(n, C.c_int64) for n in ("h_elems", "xin_elems", "y_elems", "qkv_elems", "att_elems", "feats_elems", "fc_elems")]
+        + [("rows", C.c_int), ("seq_start", C.POINTER(C.c_int)), ("seq_len", C.POINTER(C.c_int)), ("n_seq", C.c_int),
+           ("n_tok", C.c_int), ("d_ffn", C.c_int)]
+        + [(n, C.c_void_p) for n in ("ln_g", "ln_b", "gln_g", "gln_b", "wqkv", "bqkv", "wo", "bo", "w1", "b1", "w2", "b2", "wdec")]
+        + [(n, C.c_int64) for n in ("ln_elems", "gln_elems", "wqkv_elems", "bqkv_elems", "wo_elems", "bo_elems", "w1_elems",
+                                    "b1_elems", "w2_elems", "b2_elems", "wdec_elems")]
+        + [("utt_tok0", C.POINTER(C.c_int)), ("utt_L", C.POINTER(C.c_int)), ("utt_T", C.POINTER(C.c_int)), ("n_utt", C.c_int),
+           ("segment", C.c_int), ("out", C.c_void_p), ("out_stride", C.c_int64), ("out_elems", C.c_int64)])
+
+
+SEP_ATTN_BLOCK, SEP_ATTENTION, SEP_FFN, SEP_FINAL_NORM, SEP_DECODER = range(5)
+
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _ip = C.POINTER(C.c_int)
 _i32p = C.POINTER(C.c_int32)
@@ -138,6 +155,7 @@ PROTOTYPES = {
     "ccx_sepformer_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i64]),
     "ccx_sepformer_finalize": (_i, [_vp]),
     "ccx_sepformer_separate": (_i, [_vp, _vp, _i64, _ip, _i, _vp, _vp]),
+    "ccx_sep_op": (_i, [_vp, _i, C.POINTER(SepDesc), _vp]),
     "ccx_speaker_create": (_i, [_vp, _i, _i, _i, _i, _i64, C.POINTER(_vp)]),
     "ccx_speaker_destroy": (None, [_vp]),
     "ccx_speaker_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i64]),

@@ -17,6 +17,7 @@
 #include <type_traits>
 #include "gemm_bf16.h"
 #include "model_store.h"
+#include "sepformer.h"
 
 namespace {
 
@@ -291,7 +292,7 @@ __device__ __forceinline__ int ff_key2(int r) { return ((r >> 1) & 1) | (((r >> 
 //   4. wave w = output columns 16 w ..: out-proj with the Wo fragments from global memory, C^T orientation (lane = token, four
 //      consecutive columns), residual add, float4 store.
 // ---------------------------------------------------------------------------------------------
-constexpr int AB_MAX_TOK = 160;
+constexpr int AB_MAX_TOK = CCX_SEP_FUSED_MAX_TOK;
 __device__ __forceinline__ int ab_off(int row, int chunk) { return row * 256 + ((chunk ^ (row & 15)) << 4); }   // 16 chunks of 16 B per row
 
 __global__ __launch_bounds__(512) void sep_attn_block_kernel(float* __restrict__ h, const float* __restrict__ ln_g, const float* __restrict__ ln_b,
@@ -719,6 +720,64 @@ struct SepBlock {
 
 }  // namespace
 
+// ---- the launchers of sepformer.h: grid rule, LDS opt-in, profile record and launch check of each layer kernel ----
+static constexpr float kSepScaleLog2e = 0.25f * 1.4426950408889634f;  // 1/sqrt(16)
+static constexpr float kSepLnEps = 1e-6f;
+
+int ccx_launch_sep_attn_block(ccx_ctx* ctx, float* h, const float* ln_g, const float* ln_b, const bf16_t* Wqkv, const float* bqkv,
+                              const bf16_t* Wo, const float* bo, const int* seq_start, const int* seq_len, int n_seq, int n_tok,
+                              int max_len, hipStream_t st) {
+  const int D = 128;
+  {
+    // algorithmic work: QKV + out-proj GEMMs and the two attention products; bytes: the residual rows read and written once
+    ccx_prof_scope ps(ctx, st, "sep_attn_block_kernel", 2.0 * n_tok * (double)D * 4 * D + 4.0 * n_tok * (double)max_len * D,
+                      2.0 * n_tok * D * 4.0 + 2.0 * 4 * D * D);
+    hipLaunchKernelGGL(sep_attn_block_kernel, dim3(n_seq), dim3(512), 0, st, h, ln_g, ln_b, Wqkv, bqkv, Wo, bo, seq_start, seq_len,
+                       kSepScaleLog2e, kSepLnEps);
+  }
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int ccx_launch_sep_attention(ccx_ctx* ctx, const bf16_t* qkv, const int* seq_start, const int* seq_len, int n_seq, int n_head,
+                             bf16_t* out, hipStream_t st) {
+  {
+    ccx_prof_scope ps(ctx, st, "sep_attention_kernel", 0.0, 0.0);
+    hipLaunchKernelGGL(sep_attention_kernel, dim3(n_seq, n_head / 4), dim3(256), 0, st, qkv, seq_start, seq_len, out, kSepScaleLog2e);
+  }
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int ccx_launch_sep_ffn(ccx_ctx* ctx, float* h, const float* ln_g, const float* ln_b, const bf16_t* W1, const float* b1,
+                       const bf16_t* W2, const float* b2, int n_tok, int d_ffn, hipStream_t st) {
+  const int D = 128;
+  {
+    static ccx_lds_optin optin;
+    CCX_HIP(ctx, optin.ensure(ctx->device, (const void*)sep_ffn_kernel, FF_LDS));
+    ccx_prof_scope ps(ctx, st, "sep_ffn_kernel", 4.0 * n_tok * (double)D * d_ffn, 2.0 * n_tok * D * 4.0 + 4.0 * D * d_ffn);
+    hipLaunchKernelGGL(sep_ffn_kernel, dim3(ccx_cdiv(n_tok, FF_TOK)), dim3(512), FF_LDS, st, h, ln_g, ln_b, W1, b1, W2, b2, n_tok, d_ffn,
+                       kSepLnEps);
+  }
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int ccx_launch_sep_final_norm(ccx_ctx* ctx, const float* h, const float* xin, const int* seq_start, const int* seq_len, int n_seq,
+                              const float* ln_g, const float* ln_b, const float* gln_g, const float* gln_b, float* y, hipStream_t st) {
+  hipLaunchKernelGGL(sep_final_norm_kernel, dim3(n_seq), dim3(256), 0, st, h, xin, seq_start, seq_len, ln_g, ln_b, gln_g, gln_b, y);
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int ccx_launch_sep_decoder(ccx_ctx* ctx, const float* feats, const float* fc, const int* utt_tok0, const int* utt_L, const int* utt_T,
+                           const float* wdec, float* out, long out_stride, int n_utt, hipStream_t st) {
+  hipLaunchKernelGGL(sep_decoder_kernel, dim3(ccx_cdiv(ccx_cdiv((int)out_stride, 8), 4), n_utt), dim3(256), 0, st, feats, fc, utt_tok0, utt_L,
+                     utt_T, wdec, out, out_stride, n_utt);
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
 struct ccx_sepformer {
   ccx_ctx* ctx = nullptr;
   ccx_sepformer_dims d{};
@@ -775,48 +834,26 @@ int run_block(ccx_sepformer* s, const SepBlock& B, const float* x, const float* 
   hipLaunchKernelGGL(sep_block_input_kernel, dim3(ccx_cdiv(n_tok * 32, 256)), dim3(256), 0, st, x, hc, tok_seq, tok_pos, s->pe,
                      xin, h, n_tok);
   CCX_CHECK_LAUNCH(ctx);
-  const float scale_log2e = 0.25f * 1.4426950408889634f;  // 1/sqrt(16)
   const char* fenv = getenv("CCX_SEP_FUSED_ATTN");          // read per call: tests compare the two paths in one process
   const bool fused = (fenv ? atoi(fenv) != 0 : true) && max_len <= AB_MAX_TOK;
   for (const SepLayer& L : B.layers) {
     GemmParams p;
     if (fused) {
-      {
-        // algorithmic work: QKV + out-proj GEMMs and the two attention products; bytes: the residual rows read and written once
-        ccx_prof_scope ps(ctx, st, "sep_attn_block_kernel", 2.0 * n_tok * (double)D * 4 * D + 4.0 * n_tok * (double)max_len * D,
-                          2.0 * n_tok * D * 4.0 + 2.0 * 4 * D * D);
-        hipLaunchKernelGGL(sep_attn_block_kernel, dim3(n_seq), dim3(512), 0, st, h, L.ln1_g, L.ln1_b, L.Wqkv, L.bqkv, L.Wo, L.bo, seq_start,
-                           seq_len, scale_log2e, 1e-6f);
-      }
-      CCX_CHECK_LAUNCH(ctx);
+      CCX_TRY(ccx_launch_sep_attn_block(ctx, h, L.ln1_g, L.ln1_b, L.Wqkv, L.bqkv, L.Wo, L.bo, seq_start, seq_len, n_seq, n_tok, max_len, st));
     } else {
     CCX_TRY(ccx_launch_layernorm(ctx, h, D, L.ln1_g, L.ln1_b, s->xn, nullptr, D, n_tok, D, 1e-6f, st));
     memset(&p, 0, sizeof(p));
     p.A = s->xn; p.lda = D; p.W = L.Wqkv; p.ldw = D; p.M = n_tok; p.N = 3 * D; p.K = D; p.bias = L.bqkv; p.out = s->qkv; p.ldo = 3 * D;
     CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16, p, st));
-    {
-      ccx_prof_scope ps(ctx, st, "sep_attention_kernel", 0.0, 0.0);
-      hipLaunchKernelGGL(sep_attention_kernel, dim3(n_seq, s->d.n_head / 4), dim3(256), 0, st, s->qkv, seq_start, seq_len, s->att,
-                         scale_log2e);
-    }
-    CCX_CHECK_LAUNCH(ctx);
+    CCX_TRY(ccx_launch_sep_attention(ctx, s->qkv, seq_start, seq_len, n_seq, s->d.n_head, s->att, st));
     memset(&p, 0, sizeof(p));
     p.A = s->att; p.lda = D; p.W = L.Wo; p.ldw = D; p.M = n_tok; p.N = D; p.K = D; p.bias = L.bo; p.out = h; p.ldo = D; p.resid = h; p.ldr = D;
     CCX_TRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, st));
     }
-    {
-      // LayerNorm 2 + Linear-ReLU-Linear + residual in one kernel (see sep_ffn_kernel)
-      static ccx_lds_optin optin;
-      CCX_HIP(ctx, optin.ensure(ctx->device, (const void*)sep_ffn_kernel, FF_LDS));
-      ccx_prof_scope ps(ctx, st, "sep_ffn_kernel", 4.0 * n_tok * (double)D * F, 2.0 * n_tok * D * 4.0 + 4.0 * D * F);
-      hipLaunchKernelGGL(sep_ffn_kernel, dim3(ccx_cdiv(n_tok, FF_TOK)), dim3(512), FF_LDS, st, h, L.ln2_g, L.ln2_b, L.W1, L.b1, L.W2, L.b2,
-                         n_tok, F, 1e-6f);
-    }
-    CCX_CHECK_LAUNCH(ctx);
+    // LayerNorm 2 + Linear-ReLU-Linear + residual in one kernel (see sep_ffn_kernel)
+    CCX_TRY(ccx_launch_sep_ffn(ctx, h, L.ln2_g, L.ln2_b, L.W1, L.b1, L.W2, L.b2, n_tok, F, st));
   }
-  hipLaunchKernelGGL(sep_final_norm_kernel, dim3(n_seq), dim3(256), 0, st, h, xin, seq_start, seq_len, B.lnf_g, B.lnf_b, B.gln_g,
-                     B.gln_b, y);
-  CCX_CHECK_LAUNCH(ctx);
+  CCX_TRY(ccx_launch_sep_final_norm(ctx, h, xin, seq_start, seq_len, n_seq, B.lnf_g, B.lnf_b, B.gln_g, B.gln_b, y, st));
   return CCX_OK;
 }
 
@@ -973,10 +1010,7 @@ int ccx_sepformer_separate(ccx_sepformer* s, const float* mix, int64_t stride, c
   memset(&p, 0, sizeof(p));
   p.A = s->xn; p.lda = D; p.W = s->W_fc; p.ldw = D; p.M = n_tok; p.N = 2 * D; p.K = D; p.bias = s->b_fc; p.out = s->fc; p.ldo = 2 * D;
   CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
-  hipLaunchKernelGGL(sep_decoder_kernel, dim3(ccx_cdiv(ccx_cdiv((int)stride, 8), 4), B), dim3(256), 0, st, s->feats, s->fc, s->utt_tok0, s->utt_L,
-                     s->utt_T, s->w_dec, out, (long)stride, B);
-  CCX_CHECK_LAUNCH(ctx);
-  return CCX_OK;
+  return ccx_launch_sep_decoder(ctx, s->feats, s->fc, s->utt_tok0, s->utt_L, s->utt_T, s->w_dec, out, (long)stride, B, st);
 }
 
 }  // extern "C"

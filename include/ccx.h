@@ -314,6 +314,44 @@ int ccx_sepformer_finalize(ccx_sepformer* s);
 int ccx_sepformer_separate(ccx_sepformer* s, const float* mix_dev, int64_t stride, const int* n_samples, int B,
                            float* out_dev, void* stream);
 
+/* ---- the SepFormer layer kernels on their own (csrc/sepformer.hip through the launchers of csrc/sepformer.h; for kernel parity
+ *      tests, the product path does not call this) -------------------------------------------------------------------------
+ * One descriptor, one op code.  Device pointers come with the element count (of the buffer's own type) behind them; sequence and
+ * utterance tables are HOST arrays, checked and uploaded into scratch that is freed on every path.  Everything the kernels assume is
+ * checked on the host before anything is launched; a violation returns CCX_ERR_ARG (1) with a message naming "ccx_sep_op" and the
+ * field.  Synchronises the stream. */
+#define CCX_SEP_ATTN_BLOCK 0   /* sep_attn_block_kernel: h += out_proj(attention(LN(h) Wqkv^T + bqkv)) + bo per sequence, len <= 160 */
+#define CCX_SEP_ATTENTION 1    /* sep_attention_kernel: qkv -> att per sequence and head, any len */
+#define CCX_SEP_FFN 2          /* sep_ffn_kernel: h[0 .. n_tok) += W2 relu(W1 LN(h) + b1) + b2 */
+#define CCX_SEP_FINAL_NORM 3   /* sep_final_norm_kernel: y = gLN(LN(h)) + xin per sequence */
+#define CCX_SEP_DECODER 4      /* sep_decoder_kernel: out[u][t][spk] from feats * relu(fc), 16 taps, stride 8 */
+
+typedef struct ccx_sep_desc {
+  /* token buffers, `rows` rows each: h f32 [rows][128] (ops 0, 2: in and out; op 3: in), xin / y f32 [rows][128] (op 3: skip input /
+   * output), qkv bf16 [rows][384] and att bf16 [rows][128] (op 1), feats f32 [rows][128] and fc f32 [rows][256] (op 4) */
+  void* h; const void* xin; void* y; const void* qkv; void* att; const void* feats; const void* fc;
+  int64_t h_elems, xin_elems, y_elems, qkv_elems, att_elems, feats_elems, fc_elems;
+  int rows;
+  /* ops 0, 1, 3: HOST tables of n_seq sequences (start row, len >= 1), each inside [0, rows); pairwise disjoint for op 0 */
+  const int* seq_start; const int* seq_len; int n_seq;
+  /* op 2: tokens [0, n_tok) of h, n_tok >= 1; d_ffn a multiple of 64 in [64, 1024] */
+  int n_tok, d_ffn;
+  /* parameters: ln_g / ln_b f32 [128] (ops 0, 2, 3), gln_g / gln_b f32 [128] (op 3); op 0: wqkv bf16 [384][128], bqkv f32 [384],
+   * wo bf16 [128][128], bo f32 [128]; op 2: w1 bf16 [d_ffn][128], b1 f32 [d_ffn], w2 bf16 [128][d_ffn], b2 f32 [128];
+   * op 4: wdec f32 [128][16] */
+  const void* ln_g; const void* ln_b; const void* gln_g; const void* gln_b;
+  const void* wqkv; const void* bqkv; const void* wo; const void* bo;
+  const void* w1; const void* b1; const void* w2; const void* b2; const void* wdec;
+  int64_t ln_elems, gln_elems, wqkv_elems, bqkv_elems, wo_elems, bo_elems, w1_elems, b1_elems, w2_elems, b2_elems, wdec_elems;
+  /* op 4: HOST tables of n_utt utterances: first token row, frames L >= 1, samples 16 <= T <= out_stride; an utterance owns the rows
+   * of its frames padded to whole `segment`-row chunks (a full extra chunk when L is a multiple of it), all inside [0, rows).
+   * out f32 [n_utt][out_stride][2] */
+  const int* utt_tok0; const int* utt_L; const int* utt_T; int n_utt; int segment;
+  void* out; int64_t out_stride; int64_t out_elems;
+} ccx_sep_desc;
+
+int ccx_sep_op(ccx_ctx* ctx, int op, const ccx_sep_desc* desc, void* stream);
+
 /* ---- pyannote-style speaker networks (replace self.embedding_model = Inference("pyannote/embedding",
  *      window="whole"), reference back/api.py:776-780, called at back/api.py:869; and the segmentation
  *      network inside self.vad_pipeline / self.diarization, reference back/api.py:782-792, called at

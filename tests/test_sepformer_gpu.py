@@ -107,8 +107,8 @@ def test_rejects_too_short_input(small):
 
 @pytest.mark.parametrize("d_ffn", [128, 384])
 def test_fused_ffn_other_widths(ccx_ctx, d_ffn):
-    """The fused LayerNorm + FFN kernel streams W1 / W2 in stages of 128 hidden units over two LDS buffers: one stage and
-    an odd number of stages (the default width is 8 stages) against the oracle."""
+    """The fused LayerNorm + FFN kernel streams W1 / W2 in stages of 64 hidden units over a ring of four LDS stages: two stages
+    and six stages (the default width is 16 stages) against the oracle."""
     from clearconverse_amd.separator import SepformerSeparator
     dims = SepDims(n_layers=1, d_ffn=d_ffn)
     sd = synthetic_sepformer_state_dict(dims, seed=9)
