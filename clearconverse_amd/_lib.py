@@ -106,6 +106,22 @@ class SepDesc(C.Structure):
 SEP_ATTN_BLOCK, SEP_ATTENTION, SEP_FFN, SEP_FINAL_NORM, SEP_DECODER = range(5)
 
 
+class AlignDesc(C.Structure):
+    """ccx_align_desc (include/ccx.h): one word-alignment kernel on its own."""
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("q_elems", C.c_int64), ("k_elems", C.c_int64),
+        ("n_seq", C.c_int), ("H", C.c_int), ("Spad", C.c_int),
+        ("heads", C.POINTER(C.c_int)), ("n_heads", C.c_int), ("head0", C.c_int), ("t", C.c_int),
+        ("Hsel", C.c_int), ("T", C.c_int), ("Mmax", C.c_int),
+        ("n_keys", C.POINTER(C.c_int)), ("n_rows", C.POINTER(C.c_int)), ("r0", C.c_int),
+        ("P", C.c_void_p), ("A", C.c_void_p), ("P_elems", C.c_int64), ("A_elems", C.c_int64),
+        ("text_idx", C.c_void_p), ("time_idx", C.c_void_p), ("path_len", C.c_void_p), ("jump_frame", C.c_void_p),
+        ("text_idx_elems", C.c_int64), ("time_idx_elems", C.c_int64), ("path_len_elems", C.c_int64), ("jump_frame_elems", C.c_int64)]
+
+
+ALIGN_SCORES, ALIGN_MATRIX, ALIGN_DTW = range(3)
+
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _ip = C.POINTER(C.c_int)
 _i32p = C.POINTER(C.c_int32)
@@ -146,6 +162,8 @@ PROTOTYPES = {
     "ccx_whisper_decode_greedy": (_i, [_vp, _i32p, _i32p, _i, _i, _i, _i32p, _i32p, _fp, _fp, _vp]),
     "ccx_dec_attention_desc": (_i, [_vp, _i, C.POINTER(DecAttnDesc), _vp]),
     "ccx_dec_select_step": (_i, [_vp, C.POINTER(DecSelectDesc), _vp]),
+    "ccx_align_op": (_i, [_vp, _i, C.POINTER(AlignDesc), _vp]),
+    "ccx_whisper_align": (_i, [_vp, _i32p, _i32p, _i, _i, _i32p, _i32p, _i, _i, _vp, _vp, _i32p, _vp]),
     "ccx_whisper_last_cross_path": (_i, [_vp]),
     "ccx_whisper_prepare_lanes": (_i, [_vp, _vp]),
     "ccx_whisper_trace_lanes": (_i, [_vp, C.c_char_p, _i]),

@@ -5,6 +5,7 @@
 #include "../../include/ccx.h"
 #include "ccx_common.h"
 #include "decoder.h"
+#include "op_scratch.h"
 
 static_assert(sizeof(ccx_dec_seq_state) == sizeof(DecSeqState), "ccx_dec_seq_state mirrors DecSeqState field for field");
 
@@ -14,27 +15,6 @@ __global__ void dec_ops_bf16_to_f32_kernel(const bf16_t* __restrict__ in, float*
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = bf16_to_f32(in[i]);
 }
-
-// device scratch of one call: everything allocated through it is freed when it goes out of scope
-struct Scratch {
-  std::vector<void*> ptrs;
-  ~Scratch() { for (void* p : ptrs) hipFree(p); }
-  template <class T>
-  hipError_t alloc(T** out, size_t n) {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, (n ? n : 1) * sizeof(T));
-    if (e == hipSuccess) { ptrs.push_back(p); *out = (T*)p; }
-    return e;
-  }
-  template <class T>
-  hipError_t upload(T** out, const T* src, size_t n) {
-    hipError_t e = alloc(out, n);
-    if (e == hipSuccess) e = hipMemcpy(*out, src, n * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-  }
-};
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -50,7 +30,7 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
   const int rows = d->rows, H = d->H, n_seq = d->n_seq, kv_T = d->kv_T;
   CCX_REQUIRE(ctx, rows >= 1 && rows <= 65536 && n_seq >= 1 && n_seq <= 65536 && H >= 1 && H <= 64 && kv_T >= 1 && kv_T <= (1 << 20),
               "ccx_dec_attention_desc: rows=%d, n_seq=%d, H=%d or kv_T=%d out of range", rows, n_seq, H, kv_T);
-  CCX_REQUIRE(ctx, d->k && d->v && aligned16(d->k) && aligned16(d->v), "ccx_dec_attention_desc: k / v null or not 16-byte aligned");
+  CCX_REQUIRE(ctx, d->k && d->v && ccx_aligned16(d->k) && ccx_aligned16(d->v), "ccx_dec_attention_desc: k / v null or not 16-byte aligned");
   // K / V are indexed [sequence][H][kv_T][64] up to the last sequence a row may name
   const int64_t kv_need = (int64_t)n_seq * H * kv_T * 64;
   CCX_REQUIRE(ctx, kv_need <= d->kv_elems, "ccx_dec_attention_desc: k / v are read up to element %ld, kv_elems=%ld", (long)kv_need, (long)d->kv_elems);
@@ -90,7 +70,7 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
               "ccx_dec_attention_desc: lds_pad = %d out of range [0, 131072] or given to a form that has none", d->lds_pad);
   // operands and outputs
   if (!with_q) {
-    CCX_REQUIRE(ctx, d->q && aligned16(d->q), "ccx_dec_attention_desc: q null or not 16-byte aligned");
+    CCX_REQUIRE(ctx, d->q && ccx_aligned16(d->q), "ccx_dec_attention_desc: q null or not 16-byte aligned");
     CCX_REQUIRE(ctx, (int64_t)rows * H * 64 <= d->q_elems, "ccx_dec_attention_desc: q is read up to element %ld, q_elems=%ld", (long)rows * H * 64, (long)d->q_elems);
   }
   if (final_out) {
@@ -98,7 +78,7 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
     CCX_REQUIRE(ctx, (int64_t)rows * H * 64 <= d->out_elems, "ccx_dec_attention_desc: out is written up to element %ld, out_elems=%ld", (long)rows * H * 64, (long)d->out_elems);
   }
   if (partials) {
-    CCX_REQUIRE(ctx, d->part_o && d->part_ml && aligned16(d->part_o) && aligned16(d->part_ml), "ccx_dec_attention_desc: part_o / part_ml null or not 16-byte aligned");
+    CCX_REQUIRE(ctx, d->part_o && d->part_ml && ccx_aligned16(d->part_o) && ccx_aligned16(d->part_ml), "ccx_dec_attention_desc: part_o / part_ml null or not 16-byte aligned");
     const int64_t po = (int64_t)rows * H * nsplit * 64, pml = (int64_t)rows * H * nsplit * 2;
     CCX_REQUIRE(ctx, po <= d->part_o_elems, "ccx_dec_attention_desc: part_o is written up to element %ld, part_o_elems=%ld", (long)po, (long)d->part_o_elems);
     CCX_REQUIRE(ctx, pml <= d->part_ml_elems, "ccx_dec_attention_desc: part_ml is written up to element %ld, part_ml_elems=%ld", (long)pml, (long)d->part_ml_elems);
@@ -107,7 +87,7 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
     // exactly what ccx_launch_dec_cross_fused_q requires, plus the extents
     CCX_REQUIRE(ctx, rows <= 16 && H == 12, "ccx_dec_attention_desc: the fused query needs rows <= 16 (got %d) and H == 12 (got %d)", rows, H);
     CCX_REQUIRE(ctx, d->x && d->pend && d->ln_g && d->ln_b && d->bq && d->wq_host, "ccx_dec_attention_desc: x, pend, ln_g, ln_b, bq or wq_host is NULL");
-    CCX_REQUIRE(ctx, aligned16(d->x) && aligned16(d->pend) && aligned16(d->ln_g) && aligned16(d->ln_b) && aligned16(d->bq),
+    CCX_REQUIRE(ctx, ccx_aligned16(d->x) && ccx_aligned16(d->pend) && ccx_aligned16(d->ln_g) && ccx_aligned16(d->ln_b) && ccx_aligned16(d->bq),
                 "ccx_dec_attention_desc: x, pend, ln_g, ln_b or bq not 16-byte aligned");
     CCX_REQUIRE(ctx, d->pend_n >= 0 && d->pend_n <= 4, "ccx_dec_attention_desc: pend_n = %d out of range [0, 4]", d->pend_n);
     CCX_REQUIRE(ctx, d->pend_stride >= (int64_t)rows * 768 && d->pend_stride % 4 == 0, "ccx_dec_attention_desc: pend_stride = %ld smaller than a slab or not a multiple of 4", (long)d->pend_stride);
@@ -115,12 +95,12 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
     const int64_t pn = (int64_t)((d->pend_n > 1 ? d->pend_n : 1) - 1) * d->pend_stride + (int64_t)rows * 768;
     CCX_REQUIRE(ctx, pn <= d->pend_elems, "ccx_dec_attention_desc: pend is read up to element %ld, pend_elems=%ld", (long)pn, (long)d->pend_elems);
     if (d->q_x_out) {
-      CCX_REQUIRE(ctx, aligned16(d->q_x_out) && d->q_x_out != d->x, "ccx_dec_attention_desc: q_x_out not 16-byte aligned or aliasing x");
+      CCX_REQUIRE(ctx, ccx_aligned16(d->q_x_out) && d->q_x_out != d->x, "ccx_dec_attention_desc: q_x_out not 16-byte aligned or aliasing x");
       CCX_REQUIRE(ctx, (int64_t)rows * 768 <= d->q_x_out_elems, "ccx_dec_attention_desc: q_x_out is written up to element %ld, q_x_out_elems=%ld", (long)rows * 768, (long)d->q_x_out_elems);
     }
   }
 
-  Scratch sc;
+  ccx_op_scratch sc;
 #define DO_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return ccx_fail(ctx, CCX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
   DecAttnParams ap;
   memset(&ap, 0, sizeof(ap));
@@ -185,7 +165,7 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   CCX_REQUIRE(ctx, B >= 1 && B <= 65536, "ccx_dec_select_step: B = %d out of range", B);
   CCX_REQUIRE(ctx, V >= 4 && V % 4 == 0 && V <= 13 * 4096, "ccx_dec_select_step: n_vocab = %d must be a multiple of 4 and <= 53248", V);
   CCX_REQUIRE(ctx, d->ld >= V && d->ld % 4 == 0, "ccx_dec_select_step: ld = %ld must be >= n_vocab and a multiple of 4", (long)d->ld);
-  CCX_REQUIRE(ctx, d->logits && aligned16(d->logits), "ccx_dec_select_step: logits null or not 16-byte aligned");
+  CCX_REQUIRE(ctx, d->logits && ccx_aligned16(d->logits), "ccx_dec_select_step: logits null or not 16-byte aligned");
   CCX_REQUIRE(ctx, (int64_t)(B - 1) * d->ld + V <= d->logits_elems, "ccx_dec_select_step: logits are read up to element %ld, logits_elems=%ld",
               (long)((int64_t)(B - 1) * d->ld + V), (long)d->logits_elems);
   CCX_REQUIRE(ctx, d->rules && d->state && d->gen && d->cur_tok && d->pos && d->n_done, "ccx_dec_select_step: rules, state, gen, cur_tok, pos or n_done is NULL");
@@ -196,7 +176,7 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   CCX_REQUIRE(ctx, d->sample_len >= 1 && d->sample_len <= (1 << 20), "ccx_dec_select_step: sample_len = %d out of range", d->sample_len);
   CCX_REQUIRE(ctx, d->max_prompt >= 0 && (d->max_prompt == 0 || d->prompt), "ccx_dec_select_step: prompt is NULL with max_prompt = %d", d->max_prompt);
   CCX_REQUIRE(ctx, D >= 4 && D % 4 == 0 && D <= 4096, "ccx_dec_select_step: D = %d must be a multiple of 4 in [4, 4096]", D);
-  CCX_REQUIRE(ctx, d->tok_emb && d->pos_emb && d->x && aligned16(d->tok_emb) && aligned16(d->pos_emb) && aligned16(d->x),
+  CCX_REQUIRE(ctx, d->tok_emb && d->pos_emb && d->x && ccx_aligned16(d->tok_emb) && ccx_aligned16(d->pos_emb) && ccx_aligned16(d->x),
               "ccx_dec_select_step: tok_emb, pos_emb or x null or not 16-byte aligned");
   CCX_REQUIRE(ctx, (int64_t)V * D <= d->tok_emb_elems, "ccx_dec_select_step: tok_emb is read up to element %ld, tok_emb_elems=%ld", (long)V * D, (long)d->tok_emb_elems);
   CCX_REQUIRE(ctx, (int64_t)B * D <= d->x_elems, "ccx_dec_select_step: x is written up to element %ld, x_elems=%ld", (long)B * D, (long)d->x_elems);
@@ -221,7 +201,7 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
     }
   }
 
-  Scratch sc;
+  ccx_op_scratch sc;
   unsigned char* d_mask = nullptr; DecSeqState* d_state = nullptr;
   int *d_prompt = nullptr, *d_cur = nullptr, *d_pos = nullptr, *d_gen = nullptr, *d_ndone = nullptr;
   unsigned* d_cfg = nullptr;

@@ -1,37 +1,18 @@
 // sep_ops.hip -- the SepFormer layer kernels as stand-alone operators of the C ABI (include/ccx.h: ccx_sep_op).  For kernel parity
 // tests: the entry point checks on the host everything the kernels assume, uploads the sequence / utterance tables into scratch of
-// its own (freed on every path) and calls the production launchers of sepformer.h unchanged.  The product path does not come here.
+// its own (op_scratch.h: freed on every path) and calls the production launchers of sepformer.h unchanged.  The product path does not come here.
 #include <algorithm>
 #include <vector>
 #include "../../include/ccx.h"
 #include "ccx_common.h"
+#include "op_scratch.h"
 #include "sepformer.h"
-
-namespace {
-
-// device scratch of one call: everything allocated through it is freed when it goes out of scope
-struct Scratch {
-  std::vector<void*> ptrs;
-  ~Scratch() { for (void* p : ptrs) hipFree(p); }
-  hipError_t upload(int** out, const int* src, size_t n) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, (n ? n : 1) * sizeof(int));
-    if (e != hipSuccess) return e;
-    ptrs.push_back(p);
-    *out = (int*)p;
-    return hipMemcpy(p, src, n * sizeof(int), hipMemcpyHostToDevice);
-  }
-};
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-}  // namespace
 
 // a device buffer: present, 16-byte aligned, at least `need` elements stated
 #define SEP_BUF(field, need)                                                                                                        \
   do {                                                                                                                              \
     CCX_REQUIRE(ctx, d->field != nullptr, "ccx_sep_op: %s is NULL", #field);                                                        \
-    CCX_REQUIRE(ctx, aligned16(d->field), "ccx_sep_op: %s is not 16-byte aligned", #field);                                         \
+    CCX_REQUIRE(ctx, ccx_aligned16(d->field), "ccx_sep_op: %s is not 16-byte aligned", #field);                                         \
     CCX_REQUIRE(ctx, d->field##_elems >= (int64_t)(need), "ccx_sep_op: %s is accessed up to element %ld, %s_elems=%ld", #field,     \
                 (long)(need), #field, (long)d->field##_elems);                                                                      \
   } while (0)
@@ -39,7 +20,7 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 #define SEP_PARAM(field, efield, count)                                                                                             \
   do {                                                                                                                              \
     CCX_REQUIRE(ctx, d->field != nullptr, "ccx_sep_op: %s is NULL", #field);                                                        \
-    CCX_REQUIRE(ctx, aligned16(d->field), "ccx_sep_op: %s is not 16-byte aligned", #field);                                         \
+    CCX_REQUIRE(ctx, ccx_aligned16(d->field), "ccx_sep_op: %s is not 16-byte aligned", #field);                                         \
     CCX_REQUIRE(ctx, d->efield == (int64_t)(count), "ccx_sep_op: %s holds %ld elements (%s), the kernel reads %ld", #field,         \
                 (long)d->efield, #efield, (long)(count));                                                                           \
   } while (0)
@@ -125,7 +106,7 @@ extern "C" int ccx_sep_op(ccx_ctx* ctx, int op, const ccx_sep_desc* d, void* str
     }
   }
 
-  Scratch sc;
+  ccx_op_scratch sc;
   int *d_a = nullptr, *d_b = nullptr, *d_c = nullptr;
   if (seq_op) {
     SEP_HIP(sc.upload(&d_a, d->seq_start, (size_t)d->n_seq));

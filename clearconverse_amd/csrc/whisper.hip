@@ -12,6 +12,7 @@
 #include <chrono>
 #include <math.h>
 #include "../../include/ccx.h"
+#include "align.h"
 #include "attention.h"
 #include "ccx_common.h"
 #include "cross_x.h"
@@ -140,6 +141,19 @@ struct ccx_whisper {
   static constexpr int kStampCap = 1 << 16;
   hipEvent_t lane_start[kMaxLanes] = {}, lane_poll[2][kMaxLanes] = {};
   int* poll_host = nullptr;                  // pinned [2][kMaxLanes]
+  // word alignment (ccx_whisper_align; align.hip).  The workspaces are allocated by its first call, nothing at create / finalize.
+  float *al_P = nullptr, *al_A = nullptr;    // [seqs][heads][T][n_audio_ctx], [seqs][T][n_audio_ctx]
+  unsigned char* al_trace = nullptr;
+  int* al_ints = nullptr;                    // tables of one call (heads, n_keys, rows) and its path / jump-frame outputs
+  size_t al_P_elems = 0, al_A_elems = 0, al_trace_bytes = 0, al_ints_elems = 0;   // bytes held by each (own hipMallocs, freed at destroy)
+  const struct AlignPass* align_pass = nullptr;   // non-null only inside ccx_whisper_align's teacher-forced pass: dec_step's hook
+};
+
+// the alignment pass in flight: which heads of which layer go where in P, and the token row the current step writes
+struct AlignPass {
+  std::vector<int> first, count;             // per decoder layer: range of its selected heads in the device tables
+  const int *heads = nullptr, *hsel = nullptr, *n_keys = nullptr;   // device
+  int Hsel = 0, T = 0, Mmax = 0, t = 0;
 };
 
 namespace {
@@ -250,6 +264,8 @@ void ccx_whisper_destroy(ccx_whisper* w) {
   for (int i = 0; i < ccx_whisper::kLanePool; i++)
     if (w->lane_pool[i]) hipStreamDestroy(w->lane_pool[i]);
   if (w->poll_host) hipHostFree(w->poll_host);
+  for (void* p : {(void*)w->al_P, (void*)w->al_A, (void*)w->al_trace, (void*)w->al_ints})
+    if (p) hipFree(p);
   w->store.free_all();
   delete w;
 }
@@ -787,6 +803,15 @@ int cross_split(int B, int H, bool lean) {
   return ns;
 }
 
+// ccx_whisper_align's hook in dec_step: the cross-attention probabilities of layer l's selected heads for the step's query rows
+int align_scores_hook(ccx_whisper* w, int l, const float* dq, int B, hipStream_t stream) {
+  const AlignPass& a = *w->align_pass;
+  if (a.count[l] == 0) return CCX_OK;
+  AlignScoresParams p{dq, w->dec[l].crossK, w->d.n_text_head, w->Spad, a.heads + a.first[l], a.hsel + a.first[l], a.count[l], a.n_keys,
+                      w->al_P, a.Hsel, a.T, a.Mmax, a.t};
+  return ccx_launch_align_scores(w->ctx, p, B, stream);
+}
+
 // Tail of a step for the sequences [b0, b0 + B): logits of the final-LayerNorm rows (w->dxn) against the tied embedding, then
 // the select kernel (filters, argmax / sampling, state machine, next step's embedding).
 int dec_head(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select, int sample_len, int max_prompt, int* n_done,
@@ -943,6 +968,7 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     stamp(18, 2);
     // cross attention
     if (q_launch) CCX_TRY(ln_linear(DEPI_F32, L.Wcq, L.bcq, D, L.lnc_g, L.lnc_b, dq, D, nullptr));
+    if (w->align_pass) CCX_TRY(align_scores_hook(w, l, dq, B, stream));   // ccx_whisper_align only: the step's row of P
     stamp(1, 1);
     if (l == 0 && stagger) CCX_HIP(ctx, hipEventRecord(stagger, stream));
     if (w->xs_active) {
@@ -1106,6 +1132,116 @@ int ccx_whisper_decoder_logits(ccx_whisper* w, const int32_t* tokens, int B, int
     CCX_HIP(ctx, hipMemcpy2DAsync(logits_dev + (long)t * V, (size_t)T * V * 4, w->dlogits, (size_t)w->Vpad * 4, (size_t)V * 4, B,
                                   hipMemcpyDeviceToDevice, stream));
   }
+  return CCX_OK;
+}
+
+int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens, int max_len, int B, const int32_t* n_frames,
+                      const int32_t* heads, int n_heads, int row0, float* probs_out_dev, float* matrix_out_dev, int32_t* jump_frame_out,
+                      void* stream_) {
+  if (!w) return CCX_ERR_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  ccx_ctx* ctx = w->ctx;
+  const ccx_whisper_dims& d = w->d;
+  CCX_REQUIRE(ctx, w->finalized && w->rules_set, "ccx_whisper_align: not finalized or rules not set");
+  CCX_REQUIRE(ctx, tokens && lens && n_frames && heads && jump_frame_out, "ccx_whisper_align: tokens, lens, n_frames, heads or jump_frame_out is NULL");
+  CCX_REQUIRE(ctx, B >= 1 && B <= w->max_batch, "ccx_whisper_align: B = %d out of range [1, max_batch = %d]", B, w->max_batch);
+  CCX_REQUIRE(ctx, B <= w->kv_cap, "ccx_whisper_align: B = %d, the cross-attention K / V caches hold %d sequences", B, w->kv_cap);
+  CCX_REQUIRE(ctx, max_len >= 2 && max_len <= d.n_text_ctx && max_len <= CCX_ALIGN_MAX_TOK, "ccx_whisper_align: max_len = %d out of range [2, %d]", max_len,
+              d.n_text_ctx < CCX_ALIGN_MAX_TOK ? d.n_text_ctx : CCX_ALIGN_MAX_TOK);
+  CCX_REQUIRE(ctx, d.n_audio_ctx <= CCX_ALIGN_MAX_FRAMES, "ccx_whisper_align: n_audio_ctx = %d, the kernels hold %d frames", d.n_audio_ctx, CCX_ALIGN_MAX_FRAMES);
+  CCX_REQUIRE(ctx, n_heads >= 1 && n_heads <= CCX_ALIGN_MAX_HEADS, "ccx_whisper_align: n_heads = %d out of range [1, %d]", n_heads, CCX_ALIGN_MAX_HEADS);
+  CCX_REQUIRE(ctx, row0 >= 0, "ccx_whisper_align: row0 = %d is negative", row0);
+  const int Mmax = d.n_audio_ctx, T = max_len, L = d.n_text_layer;
+  std::vector<int> keys(B), r1(B), nrows(B);
+  std::vector<int32_t> padded((size_t)B * T, w->rules.eot);
+  for (int b = 0; b < B; b++) {
+    CCX_REQUIRE(ctx, lens[b] >= row0 + 2 && lens[b] <= max_len, "ccx_whisper_align: lens[%d] = %d out of range [row0 + 2 = %d, max_len = %d]", b, lens[b], row0 + 2,
+                max_len);
+    CCX_REQUIRE(ctx, n_frames[b] >= 2 && n_frames[b] <= 2 * Mmax, "ccx_whisper_align: n_frames[%d] = %d out of range [2, %d]", b, n_frames[b], 2 * Mmax);
+    keys[b] = n_frames[b] / 2; nrows[b] = lens[b]; r1[b] = lens[b] - 1;
+    for (int t = 0; t < lens[b]; t++) {
+      const int32_t tok = tokens[(size_t)b * max_len + t];
+      CCX_REQUIRE(ctx, tok >= 0 && tok < d.n_vocab, "ccx_whisper_align: tokens[%d][%d] = %d out of range [0, n_vocab = %d)", b, t, tok, d.n_vocab);
+      padded[(size_t)b * T + t] = tok;
+    }
+  }
+  // (layer, head) pairs -> per-layer ranges of the device tables; P's head axis keeps the caller's order
+  AlignPass pass;
+  pass.first.assign(L, 0); pass.count.assign(L, 0);
+  std::vector<int> h_heads, h_hsel;
+  for (int i = 0; i < n_heads; i++) {
+    const int l = heads[2 * i], h = heads[2 * i + 1];
+    CCX_REQUIRE(ctx, l >= 0 && l < L && h >= 0 && h < d.n_text_head, "ccx_whisper_align: heads[%d] = (layer %d, head %d) outside %d layers x %d heads", i, l, h, L,
+                d.n_text_head);
+    for (int j = 0; j < i; j++)
+      CCX_REQUIRE(ctx, heads[2 * j] != l || heads[2 * j + 1] != h, "ccx_whisper_align: heads[%d] repeats heads[%d] = (layer %d, head %d)", i, j, l, h);
+  }
+  for (int l = 0; l < L; l++) {
+    pass.first[l] = (int)h_heads.size();
+    for (int i = 0; i < n_heads; i++)
+      if (heads[2 * i] == l) { h_heads.push_back(heads[2 * i + 1]); h_hsel.push_back(i); }
+    pass.count[l] = (int)h_heads.size() - pass.first[l];
+  }
+  // workspaces: on first use, sized from max_batch (and grown if a later call selects more heads or longer rows)
+  const size_t seqs = (size_t)(w->max_batch < w->kv_cap ? w->max_batch : w->kv_cap);
+  const size_t Tcap = (size_t)(d.n_text_ctx / 2 + 4 > T ? d.n_text_ctx / 2 + 4 : T);
+  const size_t P_need = seqs * n_heads * Tcap * Mmax, A_need = seqs * Tcap * Mmax, tr_need = seqs * (Tcap + 1) * (Mmax + 1);
+  const size_t path_cap = (size_t)T + Mmax;
+  const size_t ints_need = 2 * (size_t)CCX_ALIGN_MAX_HEADS + seqs * (4 + 2 * (Tcap + Mmax) + Tcap);
+  // P is the large one: seqs x n_heads x Tcap x n_audio_ctx x 4 bytes -- 0.79 GB for small.en's 72 default heads at max_batch 8, 7.9 GB
+  // at the 80 sequences the K / V caches of a large instance hold (include/ccx.h).  A buffer that has to grow is freed first.
+  auto grow = [&](void** buf, size_t* have, size_t need_bytes) -> int {
+    if (*have >= need_bytes) return CCX_OK;
+    if (*buf) { CCX_HIP(ctx, hipStreamSynchronize(stream)); CCX_HIP(ctx, hipFree(*buf)); *buf = nullptr; *have = 0; }
+    CCX_HIP(ctx, hipMalloc(buf, need_bytes));
+    *have = need_bytes;
+    return CCX_OK;
+  };
+  CCX_TRY(grow((void**)&w->al_P, &w->al_P_elems, P_need * sizeof(float)));
+  CCX_TRY(grow((void**)&w->al_A, &w->al_A_elems, A_need * sizeof(float)));
+  CCX_TRY(grow((void**)&w->al_trace, &w->al_trace_bytes, tr_need));
+  CCX_TRY(grow((void**)&w->al_ints, &w->al_ints_elems, ints_need * sizeof(int)));
+  int* i_heads = w->al_ints;
+  int* i_hsel = i_heads + CCX_ALIGN_MAX_HEADS;
+  int* i_keys = i_hsel + CCX_ALIGN_MAX_HEADS;
+  int* i_rows = i_keys + seqs;
+  int* i_r1 = i_rows + seqs;
+  int* i_len = i_r1 + seqs;
+  int* i_text = i_len + seqs;
+  int* i_time = i_text + seqs * (Tcap + Mmax);
+  int* i_jump = i_time + seqs * (Tcap + Mmax);
+  CCX_HIP(ctx, hipMemcpyAsync(i_heads, h_heads.data(), (size_t)n_heads * 4, hipMemcpyHostToDevice, stream));
+  CCX_HIP(ctx, hipMemcpyAsync(i_hsel, h_hsel.data(), (size_t)n_heads * 4, hipMemcpyHostToDevice, stream));
+  CCX_HIP(ctx, hipMemcpyAsync(i_keys, keys.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream));
+  CCX_HIP(ctx, hipMemcpyAsync(i_rows, nrows.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream));
+  CCX_HIP(ctx, hipMemcpyAsync(i_r1, r1.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream));
+  CCX_HIP(ctx, hipMemsetAsync(w->al_A, 0, (size_t)B * T * Mmax * 4, stream));
+  pass.heads = i_heads; pass.hsel = i_hsel; pass.n_keys = i_keys; pass.Hsel = n_heads; pass.T = T; pass.Mmax = Mmax;
+
+  // the pass runs on the per-layer K / V form with the query projection as a launch of its own: every row's query is in dq
+  read_chain_switches(w);
+  w->fuse_cross_q = 0;
+  w->xs_active = false;
+  if (w->kv_ready < B) CCX_TRY(project_cross_kv(w, B, stream));
+  std::vector<int32_t> plens(B, T + 1);    // never leaves the prompt phase: every step feeds tokens[b][pos]
+  CCX_TRY(upload_decode_state(w, padded.data(), plens.data(), T, B, 0.f, 0, stream));
+  w->cross_lds_pad = 0;
+  w->cross_stream = 0;
+  struct Guard { ccx_whisper* w; ~Guard() { w->align_pass = nullptr; } } guard{w};
+  w->align_pass = &pass;
+  for (int t = 0; t < T; t++) {
+    pass.t = t;
+    CCX_TRY(dec_step(w, 0, B, w->dlogits, w->Vpad, t + 1 < T, 1, T, w->n_done, stream));
+  }
+  w->align_pass = nullptr;
+  AlignMatrixParams mp{w->al_P, w->al_A, n_heads, T, Mmax, i_rows, i_keys};
+  CCX_TRY(ccx_launch_align_matrix(ctx, mp, B, stream));
+  AlignDtwParams dp{w->al_A, T, Mmax, row0, i_r1, i_keys, w->al_trace, (long)((size_t)(T + 1) * (Mmax + 1)), i_text, i_time, (int)path_cap, i_len, i_jump};
+  CCX_TRY(ccx_launch_align_dtw(ctx, dp, B, stream));
+  if (probs_out_dev) CCX_HIP(ctx, hipMemcpyAsync(probs_out_dev, w->al_P, (size_t)B * n_heads * T * Mmax * 4, hipMemcpyDeviceToDevice, stream));
+  if (matrix_out_dev) CCX_HIP(ctx, hipMemcpyAsync(matrix_out_dev, w->al_A, (size_t)B * T * Mmax * 4, hipMemcpyDeviceToDevice, stream));
+  CCX_HIP(ctx, hipMemcpyAsync(jump_frame_out, i_jump, (size_t)B * T * 4, hipMemcpyDeviceToHost, stream));
+  CCX_HIP(ctx, hipStreamSynchronize(stream));
   return CCX_OK;
 }
 

@@ -99,8 +99,12 @@ def _tracks(annotation) -> List[Tuple[float, float, str]]:
 
 
 class EnhancedAudioProcessor:
-    def __init__(self, config: Config, load_models_immediately: bool = False, model_loader: Optional[Callable] = None):
+    def __init__(self, config: Config, load_models_immediately: bool = False, model_loader: Optional[Callable] = None,
+                 word_alignment: bool = False):
         self.config = config
+        # opt-in (default off: the reference never reads the words): the Whisper object aligns words on the GPU when the calls
+        # below pass word_timestamps=True (back/api.py:1435, 1477); handed to the loader only when set
+        self.word_alignment = bool(word_alignment)
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.resampler = None
         self.models_loaded = {"whisper": False, "resepformer": False, "pyannote": False}
@@ -116,8 +120,12 @@ class EnhancedAudioProcessor:
         from .models import load_models  # libccx-backed objects; raises loudly without the HIP library / GPU
         return load_models
 
+    def _load_objects(self):
+        kw = {"word_alignment": True} if self.word_alignment else {}
+        return self._loader()(self.config, self.device, **kw)
+
     def _initialize_models(self):
-        objs = self._loader()(self.config, self.device)
+        objs = self._load_objects()
         for name in ("whisper_model", "separator", "embedding_model", "vad_pipeline", "diarization", "denoiser"):
             setattr(self, name, objs[name])
         self.models_loaded = {k: True for k in self.models_loaded}
@@ -138,7 +146,7 @@ class EnhancedAudioProcessor:
                     continue
                 tell(pct, msg)
                 if objs is None:
-                    objs = self._loader()(self.config, self.device)
+                    objs = self._load_objects()
                 for a in attrs:
                     setattr(self, a, objs[a])
                 self.models_loaded[key] = True

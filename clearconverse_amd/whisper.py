@@ -20,6 +20,7 @@ from . import _lib
 from .audio import mel_filterbank
 from .tokenizer import DecodeRules, IdTokenizer, get_tokenizer
 from .weights import WhisperDims
+from .word_timing import add_word_timestamps, alignment_tokens, get_end
 
 N_FRAMES = 3000
 HOP = 160
@@ -40,8 +41,10 @@ class WindowLoop:
 
     Deviation: with `word_timestamps=True` (back/api.py:1435, 1477) upstream aligns words by cross-attention DTW
     and, when a window does not end on a single timestamp, moves `seek` to the end of the last aligned word instead of the last
-    timestamp token.  The DTW (K11) is not built -- its words are never read by the reference -- so `seek` keeps the timestamp-token
-    rule; only audio that needs more than one window (longer than 30 s, or a window that ends inside an unfinished segment) can see it."""
+    timestamp token.  That rule is OPT-IN here: `advance(..., last_word_end=)` applies it (a `WhisperModel(word_alignment=True)` passes
+    the end of the last word its DTW aligned, csrc/align.hip); without the argument -- the default, its words are never read by the
+    reference -- `seek` keeps the timestamp-token rule; only audio that needs more than one window (longer than 30 s, or a window
+    that ends inside an unfinished segment) can see the difference."""
 
     def __init__(self, rules: DecodeRules, tokenizer, content_frames: int, initial_prompt: Optional[str], n_text_ctx: int,
                  condition_on_previous_text: bool = True, no_speech_threshold: Optional[float] = 0.6,
@@ -53,6 +56,7 @@ class WindowLoop:
         self.seek, self.all_tokens, self.n_init, self.reset = 0, list(ipt), len(ipt), 0
         self.segments: List[dict] = []
         self.seeks: List[int] = []
+        self.last_speech_timestamp = 0.0        # word alignment only: end of the last aligned word (add_word_timestamps)
 
     def active(self) -> bool:
         return self.seek < self.content
@@ -69,11 +73,11 @@ class WindowLoop:
             toks = [self.rules.sot_prev] + list(p)[-(self.n_text_ctx // 2 - 1):]
         return toks + [self.rules.sot]
 
-    def advance(self, r: dict, temperature: float = 0.0) -> None:
-        """One decoded window (r: tokens before eot, avg_logprob, no_speech_prob) -> segments, tokens, the next seek."""
+    def window_segments(self, r: dict):
+        """The segments one decoded window yields, before empty ones are cleared: (segments, single_timestamp_ending, next seek by the
+        timestamp-token rule), or None when the silence rule skips the window.  Changes nothing."""
         tsb, eot = self.rules.timestamp_begin, self.rules.eot
         seek = self.seek
-        self.seeks.append(seek)
         segment_size = min(N_FRAMES, self.content - seek)
         time_offset = seek * HOP / SAMPLE_RATE
         segment_duration = segment_size * HOP / SAMPLE_RATE
@@ -83,8 +87,7 @@ class WindowLoop:
             if self.logprob_threshold is not None and r["avg_logprob"] > self.logprob_threshold:
                 skip = False
             if skip:
-                self.seek = seek + segment_size
-                return
+                return None
         is_ts = [t >= tsb for t in tokens]
         single_ts_ending = is_ts[-2:] == [False, True]
         consecutive = [i + 1 for i in range(len(tokens) - 1) if is_ts[i] and is_ts[i + 1]]
@@ -104,16 +107,39 @@ class WindowLoop:
                 add(time_offset + (sl[0] - tsb) * TIME_PRECISION, time_offset + (sl[-1] - tsb) * TIME_PRECISION, sl)
                 last = cur
             if single_ts_ending:
-                self.seek = seek + segment_size
+                next_seek = seek + segment_size
             else:
-                self.seek = seek + (tokens[last - 1] - tsb) * INPUT_STRIDE
+                next_seek = seek + (tokens[last - 1] - tsb) * INPUT_STRIDE
         else:
             duration = segment_duration
             ts = [t for t in tokens if t >= tsb]
             if ts and ts[-1] != tsb:
                 duration = (ts[-1] - tsb) * TIME_PRECISION
             add(time_offset, time_offset + duration, tokens)
+            next_seek = seek + segment_size
+        return new_segments, single_ts_ending, next_seek
+
+    def advance(self, r: dict, temperature: float = 0.0, last_word_end: Optional[float] = None,
+                segments: Optional[List[dict]] = None) -> None:
+        """One decoded window (r: tokens before eot, avg_logprob, no_speech_prob) -> segments, tokens, the next seek.
+        last_word_end (word alignment, opt-in): end of the last aligned word of this window in seconds -- when the window did not
+        end on a single timestamp and it lies behind the window's start, `seek` goes there [UPSTREAM-RECALL: transcribe.py, "if not
+        single_timestamp_ending: last_word_end = get_end(current_segments) ..."].  segments: this window's `window_segments()` after
+        add_word_timestamps worked on them (words attached, bounds moved); None: they are built here."""
+        seek = self.seek
+        self.seeks.append(seek)
+        segment_size = min(N_FRAMES, self.content - seek)
+        built = self.window_segments(r)
+        if built is None:
             self.seek = seek + segment_size
+            return
+        new_segments, single_ts_ending, self.seek = built
+        if segments is not None:
+            new_segments = segments
+        if last_word_end is not None:
+            if not single_ts_ending and last_word_end > seek * HOP / SAMPLE_RATE:
+                self.seek = round(last_word_end * FRAMES_PER_SECOND)
+            self.last_speech_timestamp = last_word_end
         for s in new_segments:
             # "if a segment is instantaneous or does not contain text, clear it": its tokens do not reach the prompt or the text
             if s["start"] == s["end"] or s["text"].strip() == "":
@@ -134,7 +160,16 @@ class WhisperModel:
     def __init__(self, dims: WhisperDims, state_dict: Dict[str, torch.Tensor], max_batch: int = 8,
                  device: int = 0, rules: Optional[DecodeRules] = None, tokenizer=None,
                  ctx: Optional[_lib.Context] = None, max_audio_seconds: float = 30.0,
-                 share_encoder_scratch_with: Optional["WhisperModel"] = None):
+                 share_encoder_scratch_with: Optional["WhisperModel"] = None, word_alignment: bool = False,
+                 alignment_heads: Optional[Sequence[Sequence[int]]] = None):
+        """word_alignment (default False: nothing below runs, `transcribe(word_timestamps=True)` has no effect, as before): with it,
+        `transcribe(word_timestamps=True)` aligns the words of every window by cross-attention DTW on the GPU (`align`), attaches
+        `words` to the segments and moves `seek` by upstream's last-word rule (WindowLoop.advance).
+        alignment_heads: (layer, head) pairs whose cross attention is aligned.  Default: every head of the upper half of the decoder
+        layers -- upstream's fallback for a model without a head table [UPSTREAM-RECALL: model.py, `all_heads[n_text_layer // 2:] =
+        True`].  A group of windows is aligned as one batch (windows without text go in as [sot, no_timestamps, eot]), so
+        max_batch must not exceed the sequences the cross-attention K / V caches hold (80 on the instances that read the encoder
+        output directly): a larger group fails in `transcribe` with the library's message.  small.en's published table (`_ALIGNMENT_HEADS`) is not on disk and is not restated here; pass its pairs to use it."""
         if not torch.cuda.is_available():
             raise _lib.CcxError("WhisperModel needs a ROCm GPU: the HIP path has no CPU fallback")
         self.dims = dims
@@ -152,6 +187,10 @@ class WhisperModel:
         self.max_audio_seconds = float(max_audio_seconds)
         self.sample_seed, self._sample_calls = 0, 0     # temperature > 0: Philox seed and per-call counter
         self.last_cross_path = None
+        self.word_alignment = bool(word_alignment)
+        if alignment_heads is None:
+            alignment_heads = [(l, h) for l in range(dims.n_text_layer // 2, dims.n_text_layer) for h in range(dims.n_text_head)]
+        self.alignment_heads = [(int(l), int(h)) for l, h in alignment_heads]
         self.ctx.check(self.lib.ccx_whisper_set_max_audio(self.handle, self.max_audio_seconds), "ccx_whisper_set_max_audio")
         # log-mel / encoder workspaces of another instance (kept alive here): only for instances whose log_mel / encode calls
         # are ordered on one stream, as in BatchPipeline.run_pinned_pipelined (include/ccx.h)
@@ -278,6 +317,53 @@ class WhisperModel:
                      avg_logprob=float(slp[b]) / (int(ntok[b]) + 1), no_speech_prob=float(nsp[b]),
                      cross_path=self.last_cross_path) for b in range(B)]
 
+    def align(self, tokens_per_seq: Sequence[Sequence[int]], n_frames: Sequence[int], return_probs: bool = False,
+              return_matrix: bool = False, row0: int = 1):
+        """Word alignment of the currently encoded windows (ccx_whisper_align; valid after `encode` or a decode of the same
+        windows): a teacher-forced pass over tokens_per_seq[b] (alignment_tokens: [sot, no_timestamps, *text, eot]), the alignment
+        matrix of `alignment_heads` over the first n_frames[b] // 2 encoder positions, and the DTW over rows row0 .. -1.
+        Returns (jump_frames, P, A): jump_frames[b] = int array, the encoder position at which each of those rows starts; P
+        [B, heads, T, n_audio_ctx] / A [B, T, n_audio_ctx] device tensors when asked for, else None."""
+        B = len(tokens_per_seq)
+        T = max(len(t) for t in tokens_per_seq)
+        toks = np.full((B, T), self.rules.eot, dtype=np.int32)
+        lens = np.zeros(B, dtype=np.int32)
+        for b, t in enumerate(tokens_per_seq):
+            toks[b, :len(t)] = t
+            lens[b] = len(t)
+        nf = np.ascontiguousarray(n_frames, dtype=np.int32)
+        if nf.shape != (B,):
+            raise _lib.CcxError("align: one n_frames entry per sequence")
+        heads = np.ascontiguousarray(self.alignment_heads, dtype=np.int32).reshape(-1, 2)
+        P = torch.empty(B, len(heads), T, self.dims.n_audio_ctx, device=self.device, dtype=torch.float32) if return_probs else None
+        A = torch.empty(B, T, self.dims.n_audio_ctx, device=self.device, dtype=torch.float32) if return_matrix else None
+        jump = np.full((B, T), -1, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self.ctx.check(self.lib.ccx_whisper_align(
+            self.handle, toks.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), T, B, nf.ctypes.data_as(i32p),
+            heads.ctypes.data_as(i32p), len(heads), int(row0), _lib.ptr(P), _lib.ptr(A), jump.ctypes.data_as(i32p),
+            _lib.current_stream_ptr()), "ccx_whisper_align")
+        return [jump[b, :max(int(lens[b]) - 1 - int(row0), 0)].copy() for b in range(B)], P, A
+
+    def _advance_with_words(self, grp, results, state, temperature: float):
+        """word_alignment and word_timestamps: align every window of the group that produced text while the windows are still
+        encoded, attach the words, and advance each clip with the end of its last word [UPSTREAM-RECALL: transcribe.py]."""
+        built = [state[i].window_segments(r) for i, r in zip(grp, results)]
+        texts = []
+        for bt in built:
+            texts.append([t for s in bt[0] for t in s["tokens"] if t < self.rules.eot] if bt is not None else [])
+        jumps = None
+        if any(texts):
+            frames = [max(2, min(N_FRAMES, state[i].content - state[i].seek)) for i in grp]
+            jumps, _, _ = self.align([alignment_tokens(t, self.rules) for t in texts], frames)
+        for b, (i, r) in enumerate(zip(grp, results)):
+            segs, end = None, None
+            if built[b] is not None:
+                segs = built[b][0]
+                add_word_timestamps(segs, self.tokenizer, self.rules, lambda toks, b=b: jumps[b], state[i].last_speech_timestamp)
+                end = get_end(segs)
+            state[i].advance(r, temperature, last_word_end=end, segments=segs)
+
     # ------------------------------------------------------------------ transcribe (reference call surface)
     def initial_tokens(self, prompt_tokens: Sequence[int]) -> List[int]:
         """decoding.py::_get_initial_tokens: [sot_prev] + prompt[-(n_ctx//2 - 1):] + [sot]."""
@@ -293,15 +379,18 @@ class WhisperModel:
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
         fallback loop upstream either.  Draws are reproducible: seeded by `self.sample_seed` and a per-call
-        counter.  word_timestamps only changes fields the reference never reads."""
+        counter.  word_timestamps only changes fields the reference never reads, and only on an instance built with
+        `word_alignment=True` (segments get `words`, `seek` follows the last aligned word); otherwise it has no effect."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
                                      temperature=temperature, no_speech_threshold=no_speech_threshold,
-                                     logprob_threshold=logprob_threshold)[0]
+                                     logprob_threshold=logprob_threshold, word_timestamps=word_timestamps)[0]
 
     def transcribe_batch(self, audios: Sequence, initial_prompts: Optional[Sequence[Optional[str]]] = None,
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
-                         no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0) -> List[dict]:
+                         no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0,
+                         word_timestamps: bool = False) -> List[dict]:
         """Independent clips decoded together (each window of each clip is one sequence of a batch)."""
+        with_words = bool(word_timestamps) and self.word_alignment
         if isinstance(temperature, (tuple, list)):
             raise _lib.CcxError("temperature fallback schedules are not implemented: pass one temperature (the reference does)")
         temperature = float(temperature)
@@ -348,6 +437,9 @@ class WhisperModel:
                 prompts = [state[i].initial_tokens() for i in grp]
                 self._sample_calls += 1
                 results = self.decode(prompts, temperature=temperature, seed=(int(self.sample_seed) << 32) + self._sample_calls)
+                if with_words:     # before the next log_mel: the group's windows are still encoded
+                    self._advance_with_words(grp, results, state, temperature)
+                    continue
                 for i, r in zip(grp, results):
                     state[i].advance(r, temperature)
         return [st.result() for st in state]

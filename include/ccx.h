@@ -274,6 +274,61 @@ typedef struct ccx_dec_select_desc {
  * the next step's embedding x[b] = tok_emb[next] + pos_emb[pos]. */
 int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* desc, void* stream);
 
+/* ---- word alignment (csrc/align.hip): what transcribe(word_timestamps=True) of the reference asks for (back/api.py:1435, 1477) --
+ * openai-whisper's timing.py::find_alignment [UPSTREAM-RECALL]: cross-attention probabilities of the alignment heads over the first
+ * num_frames // 2 encoder positions, standardised over the tokens, median-filtered over the frames, averaged over the heads, and a
+ * dynamic-time-warping pass over the negated result.  OPT-IN: nothing of it runs unless ccx_whisper_align / ccx_align_op is called.
+ *
+ * ccx_align_op runs ONE of the three production launchers on caller-supplied device buffers (kernel parity tests; back/api.py:1435,
+ * 1477).  Everything the kernels assume is checked on the host before anything is launched; a violation returns CCX_ERR_ARG (1) with
+ * a message naming "ccx_align_op" and the field.  Scratch (the DTW trace, the uploaded tables) is freed on every path; the stream is
+ * synchronised. */
+#define CCX_ALIGN_SCORES 0   /* align_scores_kernel: P[s][head0 + i][t][:] = softmax_j(q[s][heads[i]] . k[s][heads[i]][j] / 8), j < n_keys[s]; 0 behind */
+#define CCX_ALIGN_MATRIX 1   /* align_matrix_kernel: A[s][t][j] = mean_h median7_j((P - mean_t) / std_t), t < n_rows[s], j < n_keys[s] */
+#define CCX_ALIGN_DTW 2      /* align_dtw_kernel: DTW over -A[s][r0 : n_rows[s]][: n_keys[s]], path and jump frames */
+
+typedef struct ccx_align_desc {
+  /* op 0: q f32 [n_seq][H][64], k bf16 [n_seq][H][Spad][64] (the layout of the model's cross-attention keys); sequence s is row s */
+  const void* q; const void* k;
+  int64_t q_elems, k_elems;
+  int n_seq, H, Spad;
+  const int* heads; int n_heads; int head0;   /* op 0: HOST [n_heads] heads of this launch, each in [0, H); written as heads head0 .. of P */
+  int t;                                      /* op 0: token row of P written, in [0, T) */
+  /* all ops: P f32 [n_seq][Hsel][T][Mmax] (op 0 out, op 1 in), A f32 [n_seq][T][Mmax] (op 1 out, op 2 in); Hsel <= 96, T <= 448,
+   * Mmax <= 1500.  n_keys HOST [n_seq]: keys / frames of each sequence, 1 .. Mmax (op 0: also <= Spad; keys behind are never read) */
+  int Hsel, T, Mmax;
+  const int* n_keys;
+  const int* n_rows;                          /* ops 1, 2: HOST [n_seq].  op 1: token rows, 2 .. T.  op 2: r1 (end of the DTW's rows) */
+  int r0;                                     /* op 2: first row of the DTW, 0 <= r0 < r1 <= T */
+  void* P; void* A;
+  int64_t P_elems, A_elems;
+  /* op 2 outputs (device int32): text_idx / time_idx [n_seq][T + Mmax] (the first path_len entries), path_len [n_seq],
+   * jump_frame [n_seq][T]: time index of the first path cell of text index i < r1 - r0, -1 behind */
+  void* text_idx; void* time_idx; void* path_len; void* jump_frame;
+  int64_t text_idx_elems, time_idx_elems, path_len_elems, jump_frame_elems;
+} ccx_align_desc;
+
+int ccx_align_op(ccx_ctx* ctx, int op, const ccx_align_desc* desc, void* stream);
+
+/* Word alignment of the B windows currently encoded in the instance (back/api.py:1435, 1477): valid after ccx_whisper_encode and
+ * after a decode of the same windows.  A teacher-forced pass over tokens[b][: lens[b]] (host [B][max_len], built as
+ * ccx_whisper_decoder_logits builds its pass) on the per-layer K / V form with the query projection as a launch of its own; at every
+ * layer that holds a selected head, right after that projection, align_scores_kernel writes the step's row of P.  Then the matrix and
+ * DTW kernels with r0 = row0, r1 = lens[b] - 1.
+ *   n_frames   host [B]: mel frames of each window, 2 .. 3000 (n_frames // 2 keys enter the softmax)
+ *   heads      host [n_heads][2] (layer, head) pairs, n_heads <= 96; P's head axis follows this order
+ *   probs_out_dev   optional f32 [B][n_heads][max_len][n_audio_ctx]: P (rows t >= lens[b] come from padding tokens, columns behind
+ *                   n_frames // 2 are 0); matrix_out_dev optional f32 [B][max_len][n_audio_ctx]: A (0 outside the valid block)
+ *   jump_frame_out  host [B][max_len]: entry i < lens[b] - 1 - row0 = encoder position at which text row row0 + i starts, -1 behind
+ * Needs B <= the sequences the K / V caches hold (80 on an instance with the encoder-output cross attention) and lens[b] >= row0 + 2.
+ * The workspaces (P, A, the DTW trace) are allocated on the first call, sized from max_batch: an instance that never aligns
+ * allocates nothing for it.  P is the large one: min(max_batch, K / V sequences) x n_heads x max(n_text_ctx / 2 + 4, max_len) x
+ * n_audio_ctx x 4 bytes, 0.79 GB for small.en's 72 default heads at max_batch 8 and 7.9 GB at 80 sequences; a later call that
+ * selects more heads or longer rows frees it and allocates the larger one.  Synchronises the stream. */
+int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens, int max_len, int B, const int32_t* n_frames,
+                      const int32_t* heads, int n_heads, int row0, float* probs_out_dev, float* matrix_out_dev,
+                      int32_t* jump_frame_out, void* stream);
+
 /* Which cross-attention formulation the last ccx_whisper_decode of this instance ran (measurement / test records; the reference has one
  * formulation, MultiHeadAttention.forward(x, xa) behind back/api.py:1286-1292): 0 = "kv16" (per-layer K / V caches, split-KV kernels,
  * <= 16 sequences), 1 = "kv_stream" (per-layer K / V caches, dec_cross_stream_kernel, 17 - 80 sequences), 2 = "xa_stream" (one pass over
