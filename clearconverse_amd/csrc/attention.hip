@@ -25,12 +25,10 @@ __global__ __launch_bounds__(256, 2) void enc_attention_kernel(
     bf16_t* __restrict__ O, int S, int Spad, int n_head, float scale_log2e, int n_qt) {
   __shared__ __attribute__((aligned(16))) char smem[2 * ATT_STAGE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware bijective remap (blocks b, b + 8 share an XCD and its L2; the same map as gemm_bf16.hip): every XCD gets a
-  // contiguous run of logical tiles, so the n_qt query tiles of one (batch, head) run back to back on ONE XCD and its K / V^T
-  // (384 KB at 1500 keys) is fetched into one L2 once instead of into most of the eight (FETCH 4.6x the algorithmic bytes before).
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int wg = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (orig >> 3);
+  // XCD-aware block order (xcd_remap): every XCD gets a contiguous run of logical tiles, so the n_qt query tiles of one
+  // (batch, head) run back to back on ONE XCD and its K / V^T (384 KB at 1500 keys) is fetched into one L2 once instead of
+  // into most of the eight (FETCH 4.6x the algorithmic bytes before).
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = wg / n_qt;
   const int q0 = (wg - bh * n_qt) * 128 + wave * 32;
   const int l31 = lane & 31, hh = lane >> 5;

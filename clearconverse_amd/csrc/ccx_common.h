@@ -204,3 +204,10 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
 
 __host__ __device__ static inline int ccx_cdiv(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ static inline size_t ccx_align(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// XCD-aware bijective remap of a 1-D grid (blocks b, b + 8 share an XCD and its L2): logical block of launch slot `orig` out of
+// `nwg`, such that every XCD gets a contiguous run of logical blocks and neighbours re-read shared operands from ONE L2.
+__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
+  const int xcd = orig & 7, qq = nwg >> 3, rr = nwg & 7;
+  return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (orig >> 3);
+}

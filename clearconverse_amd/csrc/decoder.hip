@@ -42,6 +42,42 @@ __global__ void dec_embed_kernel(const float* __restrict__ tok_emb, const float*
 // row's std, else 0 -- a near-zero-mean row gains nothing from centring and keeps the uncentred arithmetic (and bits) it always had.
 __device__ __forceinline__ float centre_shift(float mean, float rstd) { return fabsf(mean) * rstd > 1.f ? mean : 0.f; }
 
+// Split-KV combine of one (row, head) = mh and 8-wide d chunk c, packed to bf16: out[d] = sum_s w_s o_s[d] / sum_s w_s l_s with
+// w_s = 2^(m_s - max m).  All partial loads (nsplit <= 8) are issued up front; the slots past nsplit re-read slot 0 with weight 0.
+// Shared by dec_combine_kernel and the ACT_COMBINE prologue of dec_linear_kernel.
+__device__ __forceinline__ uint4 combine_partials(const float* part_o, const float* part_ml, int nsplit, int mh, int c) {
+  const float2* ml = (const float2*)(part_ml + ((long)mh * nsplit) * 2);
+  const float* ob = part_o + ((long)mh * nsplit) * 64 + 8 * c;
+  float2 mlv[8];
+  float4 oa[8], oc[8];
+#pragma unroll
+  for (int s = 0; s < 8; s++) {
+    const int sc = s < nsplit ? s : 0;
+    mlv[s] = ml[sc];
+    oa[s] = *(const float4*)(ob + sc * 64);
+    oc[s] = *(const float4*)(ob + sc * 64 + 4);
+    if (s >= nsplit) mlv[s] = make_float2(-1e30f, 0.f);
+  }
+  float mx = -1e30f;
+#pragma unroll
+  for (int s = 0; s < 8; s++) mx = fmaxf(mx, mlv[s].x);
+  float den = 0.f, o[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) o[j] = 0.f;
+#pragma unroll
+  for (int s = 0; s < 8; s++) {
+    const float w = (s < nsplit) ? __builtin_amdgcn_exp2f(mlv[s].x - mx) : 0.f;
+    den += w * mlv[s].y;
+    o[0] += w * oa[s].x; o[1] += w * oa[s].y; o[2] += w * oa[s].z; o[3] += w * oa[s].w;
+    o[4] += w * oc[s].x; o[5] += w * oc[s].y; o[6] += w * oc[s].z; o[7] += w * oc[s].w;
+  }
+  const float inv = 1.0f / den;
+  uint4 pk;
+  pk.x = pack_bf16x2(o[0] * inv, o[1] * inv); pk.y = pack_bf16x2(o[2] * inv, o[3] * inv);
+  pk.z = pack_bf16x2(o[4] * inv, o[5] * inv); pk.w = pack_bf16x2(o[6] * inv, o[7] * inv);
+  return pk;
+}
+
 // ------------------------------------------------------------------------------------------
 // Skinny linear
 // ------------------------------------------------------------------------------------------
@@ -241,37 +277,7 @@ __global__ __launch_bounds__(64 * NW) void dec_linear_kernel(DecLinearParams p) 
     for (int e = tid; e < MROWS * H * 8; e += 256) {
       const int c = e & 7, h = (e >> 3) % H, r = e / (8 * H);
       const int m = m0 + r;
-      uint4 pk = make_uint4(0, 0, 0, 0);
-      if (m < p.M) {
-        const float2* ml = (const float2*)(p.part_ml + ((long)(m * H + h) * p.nsplit) * 2);
-        const float* ob = p.part_o + ((long)(m * H + h) * p.nsplit) * 64 + 8 * c;
-        float2 mlv[8];
-        float4 oa[8], oc[8];
-#pragma unroll
-        for (int s = 0; s < 8; s++) {
-          const int sc = s < p.nsplit ? s : 0;
-          mlv[s] = ml[sc];
-          oa[s] = *(const float4*)(ob + sc * 64);
-          oc[s] = *(const float4*)(ob + sc * 64 + 4);
-          if (s >= p.nsplit) mlv[s] = make_float2(-1e30f, 0.f);
-        }
-        float mx = -1e30f;
-#pragma unroll
-        for (int s = 0; s < 8; s++) mx = fmaxf(mx, mlv[s].x);
-        float den = 0.f, o[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) o[j] = 0.f;
-#pragma unroll
-        for (int s = 0; s < 8; s++) {
-          const float w = (s < p.nsplit) ? __builtin_amdgcn_exp2f(mlv[s].x - mx) : 0.f;
-          den += w * mlv[s].y;
-          o[0] += w * oa[s].x; o[1] += w * oa[s].y; o[2] += w * oa[s].z; o[3] += w * oa[s].w;
-          o[4] += w * oc[s].x; o[5] += w * oc[s].y; o[6] += w * oc[s].z; o[7] += w * oc[s].w;
-        }
-        const float inv = 1.0f / den;
-        pk.x = pack_bf16x2(o[0] * inv, o[1] * inv); pk.y = pack_bf16x2(o[2] * inv, o[3] * inv);
-        pk.z = pack_bf16x2(o[4] * inv, o[5] * inv); pk.w = pack_bf16x2(o[6] * inv, o[7] * inv);
-      }
+      const uint4 pk = m < p.M ? combine_partials(p.part_o, p.part_ml, p.nsplit, m * H + h, c) : make_uint4(0, 0, 0, 0);
       *(uint4*)(act_s + (long)r * lds_ld + h * 64 + 8 * c) = pk;
     }
     __syncthreads();
@@ -434,36 +440,7 @@ __global__ __launch_bounds__(256) void dec_combine_kernel(const float* __restric
   const int e = blockIdx.x * 256 + threadIdx.x;   // (row, head, 8-wide d chunk)
   if (e >= M * H * 8) return;
   const int c = e & 7, h = (e >> 3) % H, m = e / (8 * H);
-  const float2* ml = (const float2*)(part_ml + ((long)(m * H + h) * nsplit) * 2);
-  const float* ob = part_o + ((long)(m * H + h) * nsplit) * 64 + 8 * c;
-  float2 mlv[8];
-  float4 oa[8], oc[8];
-#pragma unroll
-  for (int s = 0; s < 8; s++) {
-    const int sc = s < nsplit ? s : 0;
-    mlv[s] = ml[sc];
-    oa[s] = *(const float4*)(ob + sc * 64);
-    oc[s] = *(const float4*)(ob + sc * 64 + 4);
-    if (s >= nsplit) mlv[s] = make_float2(-1e30f, 0.f);
-  }
-  float mx = -1e30f;
-#pragma unroll
-  for (int s = 0; s < 8; s++) mx = fmaxf(mx, mlv[s].x);
-  float den = 0.f, o[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) o[j] = 0.f;
-#pragma unroll
-  for (int s = 0; s < 8; s++) {
-    const float w = (s < nsplit) ? __builtin_amdgcn_exp2f(mlv[s].x - mx) : 0.f;
-    den += w * mlv[s].y;
-    o[0] += w * oa[s].x; o[1] += w * oa[s].y; o[2] += w * oa[s].z; o[3] += w * oa[s].w;
-    o[4] += w * oc[s].x; o[5] += w * oc[s].y; o[6] += w * oc[s].z; o[7] += w * oc[s].w;
-  }
-  const float inv = 1.0f / den;
-  uint4 pk;
-  pk.x = pack_bf16x2(o[0] * inv, o[1] * inv); pk.y = pack_bf16x2(o[2] * inv, o[3] * inv);
-  pk.z = pack_bf16x2(o[4] * inv, o[5] * inv); pk.w = pack_bf16x2(o[6] * inv, o[7] * inv);
-  *(uint4*)(out + ((long)m * H + h) * 64 + 8 * c) = pk;
+  *(uint4*)(out + ((long)m * H + h) * 64 + 8 * c) = combine_partials(part_o, part_ml, nsplit, m * H + h, c);
 }
 
 __global__ void dec_gather_rows_kernel(const bf16_t* __restrict__ src, const int* __restrict__ idx, bf16_t* __restrict__ dst, int D) {
@@ -588,20 +565,136 @@ int ccx_launch_dec_linear(ccx_ctx* ctx, int act, int epi, const DecLinearParams&
 // ------------------------------------------------------------------------------------------
 // Single-query attention (self: T = pos+1 keys, FINAL output; cross: split-KV partials)
 // ------------------------------------------------------------------------------------------
+// The online-softmax core every attention kernel below is made of.  A wave instruction covers 8 keys x 128 B (lane group g = lane >> 3
+// = key, c = lane & 7 = 16-byte d chunk), so a lane keeps the running state of ITS key residue and d chunk: the maximum m (log2
+// domain), the sum l and the 8 output values o.  Lane groups merge in registers, waves through LDS.  Every kernel does the same
+// floating-point operations in the same order here, which is what keeps the fused-query path bit-identical to the two-launch one.
 struct SoftState {
   float m, l, o[8];
 };
+// (a function called where the kernels always set their state up, not default member initialisers: those move the SGPR counts of
+//  the prefill kernels)
+__device__ __forceinline__ void soft_init(SoftState& st) {
+  st.m = -1e30f; st.l = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; j++) st.o[j] = 0.f;
+}
+
+__device__ __forceinline__ void load_q8(float (&q)[8], const float* src) {
+  const float4 a = *(const float4*)src, d = *(const float4*)(src + 4);
+  q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w; q[4] = d.x; q[5] = d.y; q[6] = d.z; q[7] = d.w;
+}
+
+// Requests a piece of NIT x 8 keys of K and V from key `base` on, K first (the scores need it first).  Keys from `limit` on re-read
+// row `last` (one cache line) instead of branching, and soft_update masks them.  NONTEMPORAL: the cross-attention K/V of a decode
+// step is read exactly once (0.9 GB per layer and step); the prompt rows of a prefill share theirs through L2, so those loads stay
+// cacheable.
+template <int NIT, bool NONTEMPORAL>
+__device__ __forceinline__ void kv_load(bf16x8 (&kf)[NIT], bf16x8 (&vf)[NIT], const bf16_t* Kb, const bf16_t* Vb, int base, int g,
+                                        int limit, int last) {
+  long off[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; it++) {
+    int key = base + it * 8 + g;
+    key = key < limit ? key : last;
+    off[it] = (long)key * 64;
+  }
+#pragma unroll
+  for (int it = 0; it < NIT; it++) kf[it] = NONTEMPORAL ? __builtin_nontemporal_load((const bf16x8*)(Kb + off[it])) : *(const bf16x8*)(Kb + off[it]);
+#pragma unroll
+  for (int it = 0; it < NIT; it++) vf[it] = NONTEMPORAL ? __builtin_nontemporal_load((const bf16x8*)(Vb + off[it])) : *(const bf16x8*)(Vb + off[it]);
+}
+
+// Folds a piece of NIT x 8 keys into the state: scores q . k (log2 domain), -inf from key `limit` on, running maximum, rescale,
+// accumulate p v.
+template <int NIT>
+__device__ __forceinline__ void soft_update(SoftState& st, const float (&q)[8], const bf16x8 (&kf)[NIT], const bf16x8 (&vf)[NIT],
+                                            int base, int g, int limit, float scale_log2e) {
+  float s[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; it++) {
+    float a = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) a = fmaf(q[j], bf16_to_f32((bf16_t)kf[it][j]), a);
+    a = group8_sum(a) * scale_log2e;
+    s[it] = (base + it * 8 + g < limit) ? a : -INFINITY;
+  }
+  float mn = st.m;
+#pragma unroll
+  for (int it = 0; it < NIT; it++) mn = fmaxf(mn, s[it]);
+  const float al = __builtin_amdgcn_exp2f(st.m - mn);
+  st.l *= al;
+#pragma unroll
+  for (int j = 0; j < 8; j++) st.o[j] *= al;
+#pragma unroll
+  for (int it = 0; it < NIT; it++) {
+    const float pe = __builtin_amdgcn_exp2f(s[it] - mn);
+    st.l += pe;
+#pragma unroll
+    for (int j = 0; j < 8; j++) st.o[j] = fmaf(pe, bf16_to_f32((bf16_t)vf[it][j]), st.o[j]);
+  }
+  st.m = mn;
+}
+
+// state a takes in (bm, bl, bo).  Of x * wa + y * wb an fma can take either product, and the two round differently; left to the
+// compiler the pick depends on the code around the merge.  PINNED: fma(bo, wb, a.o * wa) written out -- what the kernels must
+// share (fused-query and two-launch partials agree bit for bit).  PINNED = false leaves the text to the compiler, see below.
+template <bool PINNED = true>
 __device__ __forceinline__ void soft_merge(SoftState& a, float bm, float bl, const float (&bo)[8]) {
   const float mx = fmaxf(a.m, bm);
   const float wa = __builtin_amdgcn_exp2f(a.m - mx), wb = __builtin_amdgcn_exp2f(bm - mx);
   a.l = a.l * wa + bl * wb;
 #pragma unroll
-  for (int j = 0; j < 8; j++) a.o[j] = a.o[j] * wa + bo[j] * wb;
+  for (int j = 0; j < 8; j++) a.o[j] = PINNED ? fmaf(bo[j], wb, a.o[j] * wa) : a.o[j] * wa + bo[j] * wb;
   a.m = mx;
 }
 
-// A wave instruction covers 8 keys x 128 B (lane group g = key, lane&7 = 16-byte d chunk).  A wave
-// owns 64-key chunks and issues all 16 K/V loads of a chunk before touching the data, so one
+// merge the 8 lane groups (lanes with equal c) in registers: xor 8 via DPP row_ror:8, xor 16 /
+// xor 32 via v_permlane16_swap / v_permlane32_swap (VALU speed, no LDS round trips).
+// PINNED = false (dec_cross_prefill_kernel only): its xor 16 and xor 32 merges have always come out of the compiler fused the other
+// way, fma(a.o, wa, bo * wb).  Writing that out moves the kernel's registers and its s_waitcnt sequence, so there the text stays
+// unpinned and a prompt's numbers stay what they were.
+template <bool PINNED = true>
+__device__ __forceinline__ void soft_merge_lane_groups(SoftState& st) {
+  float om, ol, oo[8];
+  om = dpp_mov<0x128>(st.m); ol = dpp_mov<0x128>(st.l);
+#pragma unroll
+  for (int j = 0; j < 8; j++) oo[j] = dpp_mov<0x128>(st.o[j]);
+  soft_merge(st, om, ol, oo);
+  om = lane_xor16(st.m); ol = lane_xor16(st.l);
+#pragma unroll
+  for (int j = 0; j < 8; j++) oo[j] = lane_xor16(st.o[j]);
+  soft_merge<PINNED>(st, om, ol, oo);
+  om = lane_xor32(st.m); ol = lane_xor32(st.l);
+#pragma unroll
+  for (int j = 0; j < 8; j++) oo[j] = lane_xor32(st.o[j]);
+  soft_merge<PINNED>(st, om, ol, oo);
+}
+
+// The four waves of a block meet in LDS: lane group 0 of every wave stores its merged state (the caller puts the barrier between
+// the two), then the thread that owns output d = 8 cc + j merges the waves in the order w = 0..3.
+__device__ __forceinline__ void soft_store_wave(float (&sm_m)[4][8], float (&sm_l)[4][8], float (&sm_o)[4][8][8], const SoftState& st,
+                                                int wave, int g, int c) {
+  if (g == 0) {
+    sm_m[wave][c] = st.m; sm_l[wave][c] = st.l;
+#pragma unroll
+    for (int j = 0; j < 8; j++) sm_o[wave][c][j] = st.o[j];
+  }
+}
+__device__ __forceinline__ void soft_merge_waves(const float (&sm_m)[4][8], const float (&sm_l)[4][8], const float (&sm_o)[4][8][8], int d,
+                                                 float& mx, float& l, float& o) {
+  const int cc = d >> 3, j = d & 7;
+  mx = fmaxf(fmaxf(sm_m[0][cc], sm_m[1][cc]), fmaxf(sm_m[2][cc], sm_m[3][cc]));
+  l = 0.f; o = 0.f;
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    const float ww = __builtin_amdgcn_exp2f(sm_m[w][cc] - mx);
+    l += ww * sm_l[w][cc];
+    o += ww * sm_o[w][cc][j];
+  }
+}
+
+// A wave owns 64-key chunks and issues all 16 K/V loads of a chunk before touching the data, so one
 // HBM round trip covers the chunk.
 template <bool FINAL>
 __global__ __launch_bounds__(256) void dec_attention_kernel(DecAttnParams p) {
@@ -619,18 +712,14 @@ __global__ __launch_bounds__(256) void dec_attention_kernel(DecAttnParams p) {
   const bf16_t* Kb = p.k + ((long)sq * p.H + h) * p.kv_T * 64 + 8 * c;
   const bf16_t* Vb = p.v + ((long)sq * p.H + h) * p.kv_T * 64 + 8 * c;
 
-  float sm = -1e30f, sl = 0.f, so[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) so[j] = 0.f;
+  SoftState st;
+  soft_init(st);
   float q[8];
-  {
-    const float4* qp = (const float4*)(p.q + ((long)b * p.H + h) * 64 + 8 * c);
-    const float4 a = qp[0], d = qp[1];
-    q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w; q[4] = d.x; q[5] = d.y; q[6] = d.z; q[7] = d.w;
-  }
+  load_q8(q, p.q + ((long)b * p.H + h) * 64 + 8 * c);
 
   for (int base = kbeg + wave * 64; base < kend; base += 256) {
     bf16x8 kf[8], vf[8];
+    // (not kv_load: its K-first order costs this kernel a VGPR less and other SGPRs, and its register figures are pinned)
 #pragma unroll
     for (int it = 0; it < 8; it++) {
       int key = base + it * 8 + g;
@@ -643,73 +732,14 @@ __global__ __launch_bounds__(256) void dec_attention_kernel(DecAttnParams p) {
         vf[it] = __builtin_nontemporal_load((const bf16x8*)(Vb + (long)key * 64));
       }
     }
-    float s[8];
-#pragma unroll
-    for (int it = 0; it < 8; it++) {
-      float a = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; j++) a = fmaf(q[j], bf16_to_f32((bf16_t)kf[it][j]), a);
-      a = group8_sum(a) * p.scale_log2e;
-      s[it] = (base + it * 8 + g < kend) ? a : -INFINITY;
-    }
-    float mn = sm;
-#pragma unroll
-    for (int it = 0; it < 8; it++) mn = fmaxf(mn, s[it]);
-    const float al = __builtin_amdgcn_exp2f(sm - mn);
-    sl *= al;
-#pragma unroll
-    for (int j = 0; j < 8; j++) so[j] *= al;
-#pragma unroll
-    for (int it = 0; it < 8; it++) {
-      const float pe = __builtin_amdgcn_exp2f(s[it] - mn);
-      sl += pe;
-#pragma unroll
-      for (int j = 0; j < 8; j++) so[j] = fmaf(pe, bf16_to_f32((bf16_t)vf[it][j]), so[j]);
-    }
-    sm = mn;
+    soft_update<8>(st, q, kf, vf, base, g, kend, p.scale_log2e);
   }
-  // merge the 8 lane groups (lanes with equal c) in registers: xor 8 via DPP row_ror:8, xor 16 /
-  // xor 32 via v_permlane16_swap / v_permlane32_swap (VALU speed, no LDS round trips)
-  {
-    auto merge_with = [&](float om, float ol, const float (&oo)[8]) {
-      const float mx = fmaxf(sm, om);
-      const float wa = __builtin_amdgcn_exp2f(sm - mx), wb = __builtin_amdgcn_exp2f(om - mx);
-      sl = sl * wa + ol * wb;
-#pragma unroll
-      for (int j = 0; j < 8; j++) so[j] = so[j] * wa + oo[j] * wb;
-      sm = mx;
-    };
-    float om, ol, oo[8];
-    om = dpp_mov<0x128>(sm); ol = dpp_mov<0x128>(sl);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = dpp_mov<0x128>(so[j]);
-    merge_with(om, ol, oo);
-    om = lane_xor16(sm); ol = lane_xor16(sl);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = lane_xor16(so[j]);
-    merge_with(om, ol, oo);
-    om = lane_xor32(sm); ol = lane_xor32(sl);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = lane_xor32(so[j]);
-    merge_with(om, ol, oo);
-  }
-  if (g == 0) {
-    sm_m[wave][c] = sm; sm_l[wave][c] = sl;
-#pragma unroll
-    for (int j = 0; j < 8; j++) sm_o[wave][c][j] = so[j];
-  }
+  soft_merge_lane_groups(st);
+  soft_store_wave(sm_m, sm_l, sm_o, st, wave, g, c);
   __syncthreads();
   if (tid < 64) {
-    // thread -> d = tid = 8*cc + j; merge the 4 waves
-    const int cc = tid >> 3, j = tid & 7;
-    float mx = fmaxf(fmaxf(sm_m[0][cc], sm_m[1][cc]), fmaxf(sm_m[2][cc], sm_m[3][cc]));
-    float l = 0.f, o = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      const float ww = __builtin_amdgcn_exp2f(sm_m[w][cc] - mx);
-      l += ww * sm_l[w][cc];
-      o += ww * sm_o[w][cc][j];
-    }
+    float mx, l, o;
+    soft_merge_waves(sm_m, sm_l, sm_o, tid, mx, l, o);
     if (FINAL) {
       p.out_bf16[((long)b * p.H + h) * 64 + tid] = f32_to_bf16(o / l);
     } else {
@@ -750,10 +780,22 @@ __global__ __launch_bounds__(256, EARLY_V ? 2 : 3) void dec_cross_fused_q_kernel
   const int kbeg = split * per;
   const int kend = (kbeg + per < T) ? kbeg + per : T;
   const int K = p.q_K;                       // 768
-  // block-uniform bases + 32-bit byte offsets per lane (one SGPR pair + one VGPR per address instead of a 64-bit VGPR pair)
+  // block-uniform bases + 32-bit byte offsets per lane (one SGPR pair + one VGPR per address instead of a 64-bit VGPR pair), which is
+  // why this kernel has a chunk loader of its own instead of kv_load: 64 keys of K, of V or of both, clamped like kv_load (a wave
+  // without keys loads row kend - 1 and soft_update masks it)
   const char* Ku = (const char*)(p.k + ((long)b * p.H + h) * p.kv_T * 64);
   const char* Vu = (const char*)(p.v + ((long)b * p.H + h) * p.kv_T * 64);
-  auto kv_off = [&](int key) -> unsigned { return (unsigned)(key * 64 + 8 * c) * 2u; };
+  bf16x8 kf[8], vf[8];
+  auto load_chunk = [&](int base, bool want_k, bool want_v) {
+#pragma unroll
+    for (int it = 0; it < 8; it++) {
+      int key = base + it * 8 + g;
+      key = key < kend ? key : kend - 1;
+      const unsigned off = (unsigned)(key * 64 + 8 * c) * 2u;
+      if (want_k) kf[it] = __builtin_nontemporal_load((const bf16x8*)(Ku + off));
+      if (want_v) vf[it] = __builtin_nontemporal_load((const bf16x8*)(Vu + off));
+    }
+  };
 
   // vmcnt retires IN ORDER, so whatever the LayerNorm waits for must be requested BEFORE the long HBM round trip of the K chunk:
   // ---- 1. the row, its pending split-K slabs and the LayerNorm's affine parameters (L2 hits) ----
@@ -773,18 +815,8 @@ __global__ __launch_bounds__(256, EARLY_V ? 2 : 3) void dec_cross_fused_q_kernel
     bb[i] = *(const float4*)((const char*)p.q_ln_b + o16);
   }
   __builtin_amdgcn_sched_barrier(0);
-  // ---- 2. first K chunk of this wave (clamped like the loop below: a wave without keys loads row kend - 1 and masks it) ----
-  bf16x8 kf[8], vf[8];
-  {
-    const int base = kbeg + wave * 64;
-#pragma unroll
-    for (int it = 0; it < 8; it++) {
-      int key = base + it * 8 + g;
-      key = key < kend ? key : kend - 1;
-      kf[it] = __builtin_nontemporal_load((const bf16x8*)(Ku + kv_off(key)));
-      if (EARLY_V) vf[it] = __builtin_nontemporal_load((const bf16x8*)(Vu + kv_off(key)));
-    }
-  }
+  // ---- 2. first K chunk of this wave ----
+  load_chunk(kbeg + wave * 64, true, EARLY_V);
   // ---- 3. weight fragments: n-tiles 4 h .. 4 h + 3, k-steps 6 wave .. 6 wave + 5 (packed image: tile (n / 16, k / 32) = 1 KB), in three
   // groups of two k-steps (32 registers each, at most two groups in flight).  Default cache policy: the 48 blocks of a head share them.
   const int ksteps = K >> 5;                 // 24
@@ -857,15 +889,7 @@ __global__ __launch_bounds__(256, EARLY_V ? 2 : 3) void dec_cross_fused_q_kernel
     load_group(2, wa);
     bias4 = *(const float4*)(p.q_bias + h * 64 + 4 * (tid & 15));     // (no branch around the load: hipcc would wait at it)
     // first V chunk behind the last weight group (its HBM round trip runs under the remaining MFMAs, the reduction and q . k)
-    if (!EARLY_V) {
-      const int base = kbeg + wave * 64;
-#pragma unroll
-      for (int it = 0; it < 8; it++) {
-        int key = base + it * 8 + g;
-        key = key < kend ? key : kend - 1;
-        vf[it] = __builtin_nontemporal_load((const bf16x8*)(Vu + kv_off(key)));
-      }
-    }
+    if (!EARLY_V) load_chunk(kbeg + wave * 64, false, true);
     __builtin_amdgcn_sched_barrier(0);
     mma_group(1, wb);
     mma_group(2, wa);
@@ -886,89 +910,22 @@ __global__ __launch_bounds__(256, EARLY_V ? 2 : 3) void dec_cross_fused_q_kernel
   }
   __syncthreads();
   float q[8];
-  {
-    const float4 a = *(const float4*)(&q_s[8 * c]), d = *(const float4*)(&q_s[8 * c + 4]);
-    q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w; q[4] = d.x; q[5] = d.y; q[6] = d.z; q[7] = d.w;
-  }
+  load_q8(q, &q_s[8 * c]);
 
-  // ---- attention over this block's keys: dec_attention_kernel<false>'s loop, its first chunk already in registers ----
-  float sm = -1e30f, sl = 0.f, so[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) so[j] = 0.f;
+  // ---- attention over this block's keys: dec_attention_kernel<false>'s loop (the same soft_* calls, so the same partials bit for
+  // bit), its first chunk already in registers ----
+  SoftState st;
+  soft_init(st);
   for (int base = kbeg + wave * 64; base < kend; base += 256) {
-    if (base != kbeg + wave * 64) {
-#pragma unroll
-      for (int it = 0; it < 8; it++) {
-        int key = base + it * 8 + g;
-        key = key < kend ? key : kend - 1;
-        kf[it] = __builtin_nontemporal_load((const bf16x8*)(Ku + kv_off(key)));
-        vf[it] = __builtin_nontemporal_load((const bf16x8*)(Vu + kv_off(key)));
-      }
-    }
-    float s[8];
-#pragma unroll
-    for (int it = 0; it < 8; it++) {
-      float a = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; j++) a = fmaf(q[j], bf16_to_f32((bf16_t)kf[it][j]), a);
-      a = group8_sum(a) * p.scale_log2e;
-      s[it] = (base + it * 8 + g < kend) ? a : -INFINITY;
-    }
-    float mn = sm;
-#pragma unroll
-    for (int it = 0; it < 8; it++) mn = fmaxf(mn, s[it]);
-    const float al = __builtin_amdgcn_exp2f(sm - mn);
-    sl *= al;
-#pragma unroll
-    for (int j = 0; j < 8; j++) so[j] *= al;
-#pragma unroll
-    for (int it = 0; it < 8; it++) {
-      const float pe = __builtin_amdgcn_exp2f(s[it] - mn);
-      sl += pe;
-#pragma unroll
-      for (int j = 0; j < 8; j++) so[j] = fmaf(pe, bf16_to_f32((bf16_t)vf[it][j]), so[j]);
-    }
-    sm = mn;
+    if (base != kbeg + wave * 64) load_chunk(base, true, true);
+    soft_update<8>(st, q, kf, vf, base, g, kend, p.scale_log2e);
   }
-  {
-    auto merge_with = [&](float om, float ol, const float (&oo)[8]) {
-      const float mx = fmaxf(sm, om);
-      const float wa = __builtin_amdgcn_exp2f(sm - mx), wb = __builtin_amdgcn_exp2f(om - mx);
-      sl = sl * wa + ol * wb;
-#pragma unroll
-      for (int j = 0; j < 8; j++) so[j] = so[j] * wa + oo[j] * wb;
-      sm = mx;
-    };
-    float om, ol, oo[8];
-    om = dpp_mov<0x128>(sm); ol = dpp_mov<0x128>(sl);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = dpp_mov<0x128>(so[j]);
-    merge_with(om, ol, oo);
-    om = lane_xor16(sm); ol = lane_xor16(sl);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = lane_xor16(so[j]);
-    merge_with(om, ol, oo);
-    om = lane_xor32(sm); ol = lane_xor32(sl);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = lane_xor32(so[j]);
-    merge_with(om, ol, oo);
-  }
-  if (g == 0) {
-    sm_m[wave][c] = sm; sm_l[wave][c] = sl;
-#pragma unroll
-    for (int j = 0; j < 8; j++) sm_o[wave][c][j] = so[j];
-  }
+  soft_merge_lane_groups(st);
+  soft_store_wave(sm_m, sm_l, sm_o, st, wave, g, c);
   __syncthreads();
   if (tid < 64) {
-    const int cc = tid >> 3, j = tid & 7;
-    float mx = fmaxf(fmaxf(sm_m[0][cc], sm_m[1][cc]), fmaxf(sm_m[2][cc], sm_m[3][cc]));
-    float l = 0.f, o = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      const float ww = __builtin_amdgcn_exp2f(sm_m[w][cc] - mx);
-      l += ww * sm_l[w][cc];
-      o += ww * sm_o[w][cc][j];
-    }
+    float mx, l, o;
+    soft_merge_waves(sm_m, sm_l, sm_o, tid, mx, l, o);
     const long pbase = ((long)b * p.H + h) * gridDim.y + split;
     p.part_o[pbase * 64 + tid] = o;
     if (tid == 0) { p.part_ml[pbase * 2] = mx; p.part_ml[pbase * 2 + 1] = l; }
@@ -1000,7 +957,7 @@ int ccx_launch_dec_cross_fused_q(ccx_ctx* ctx, const DecAttnParams& p, int B, in
 // NP = 32-key pieces per wave (compile-time: the loop is fully unrolled into straight-line code, because with a real loop
 // hipcc keeps the loop-carried piece in other registers than it loads into and copies it at the loop end behind a vmcnt(0)).
 // PRE (prompt prefill): a sequence has rows_per_seq consecutive rows (one per prompt position) that all attend to ITS K/V.  Logical
-// block L = (sequence * H + head) * rows_per_seq + t, and the launch order is remapped (the GEMM's XCD-aware bijective map) so
+// block L = (sequence * H + head) * rows_per_seq + t, and the launch order is remapped (xcd_remap, the GEMM's map) so
 // that the rows of one (sequence, head) run on one XCD at about the same time: the first one brings the 384 KB of K/V into
 // that XCD's L2, the others hit it -- the prompt costs about one step of HBM traffic instead of one per prompt token.  Loads are
 // cacheable here (non-temporal for the decode steps, where every byte is used once).
@@ -1012,9 +969,7 @@ __global__ __launch_bounds__(256) void dec_cross_stream_kernel(DecAttnParams p) 
   const int split = blockIdx.y;
   int b, h, sq;                                      // row (q / out), head, sequence (K/V)
   if (PRE) {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int xcd = orig & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int L = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (orig >> 3);
+    const int L = xcd_remap(blockIdx.x, gridDim.x);
     const int t = L % p.rows_per_seq, sh = L / p.rows_per_seq;
     h = sh % p.H; sq = sh / p.H;
     b = sq * p.rows_per_seq + t;
@@ -1040,55 +995,14 @@ __global__ __launch_bounds__(256) void dec_cross_stream_kernel(DecAttnParams p) 
   const bf16_t* Kb = p.k + ((long)sq * p.H + h) * p.kv_T * 64 + 8 * c;
   const bf16_t* Vb = p.v + ((long)sq * p.H + h) * p.kv_T * 64 + 8 * c;
 
-  float sm = -1e30f, sl = 0.f, so[8];
+  SoftState st;   // set up in place: through soft_init() the PRE instantiations' SGPR counts move by one, and the register figures are pinned
+  st.m = -1e30f; st.l = 0.f;
 #pragma unroll
-  for (int j = 0; j < 8; j++) so[j] = 0.f;
+  for (int j = 0; j < 8; j++) st.o[j] = 0.f;
   float q[8];
-  {
-    const float4* qp = (const float4*)(p.q + ((long)b * p.H + h) * 64 + 8 * c);
-    const float4 a = qp[0], d = qp[1];
-    q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w; q[4] = d.x; q[5] = d.y; q[6] = d.z; q[7] = d.w;
-  }
-  auto load = [&](bf16x8 (&kf)[4], bf16x8 (&vf)[4], int base) {
-    long off[4];
-#pragma unroll
-    for (int it = 0; it < 4; it++) {
-      int key = base + it * 8 + g;
-      key = key < w1 ? key : kend - 1;    // clamped rows (one cache line) are masked below
-      off[it] = (long)key * 64;
-    }
-#pragma unroll
-    for (int it = 0; it < 4; it++)   // K first: the scores need it first
-      kf[it] = PRE ? *(const bf16x8*)(Kb + off[it]) : __builtin_nontemporal_load((const bf16x8*)(Kb + off[it]));
-#pragma unroll
-    for (int it = 0; it < 4; it++) vf[it] = PRE ? *(const bf16x8*)(Vb + off[it]) : __builtin_nontemporal_load((const bf16x8*)(Vb + off[it]));
-  };
-  auto reduce = [&](const bf16x8 (&kf)[4], const bf16x8 (&vf)[4], int base) {
-    float s[4];
-#pragma unroll
-    for (int it = 0; it < 4; it++) {
-      float a = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; j++) a = fmaf(q[j], bf16_to_f32((bf16_t)kf[it][j]), a);
-      a = group8_sum(a) * p.scale_log2e;
-      s[it] = (base + it * 8 + g < w1) ? a : -INFINITY;
-    }
-    float mn = sm;
-#pragma unroll
-    for (int it = 0; it < 4; it++) mn = fmaxf(mn, s[it]);
-    const float al = __builtin_amdgcn_exp2f(sm - mn);
-    sl *= al;
-#pragma unroll
-    for (int j = 0; j < 8; j++) so[j] *= al;
-#pragma unroll
-    for (int it = 0; it < 4; it++) {
-      const float pe = __builtin_amdgcn_exp2f(s[it] - mn);
-      sl += pe;
-#pragma unroll
-      for (int j = 0; j < 8; j++) so[j] = fmaf(pe, bf16_to_f32((bf16_t)vf[it][j]), so[j]);
-    }
-    sm = mn;
-  };
+  load_q8(q, p.q + ((long)b * p.H + h) * 64 + 8 * c);
+  auto load = [&](bf16x8 (&kf)[4], bf16x8 (&vf)[4], int base) { kv_load<4, !PRE>(kf, vf, Kb, Vb, base, g, w1, kend - 1); };
+  auto reduce = [&](const bf16x8 (&kf)[4], const bf16x8 (&vf)[4], int base) { soft_update<4>(st, q, kf, vf, base, g, w1, p.scale_log2e); };
   {
     // no branch around a request or a reduce: one code path, exact load counts.  Pieces past the end of the wave's range
     // re-read its last key row (one cache line) and are masked to -inf scores.  sched_barrier pins the order
@@ -1118,45 +1032,12 @@ __global__ __launch_bounds__(256) void dec_cross_stream_kernel(DecAttnParams p) 
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  {
-    auto merge_with = [&](float om, float ol, const float (&oo)[8]) {
-      const float mx = fmaxf(sm, om);
-      const float wa = __builtin_amdgcn_exp2f(sm - mx), wb = __builtin_amdgcn_exp2f(om - mx);
-      sl = sl * wa + ol * wb;
-#pragma unroll
-      for (int j = 0; j < 8; j++) so[j] = so[j] * wa + oo[j] * wb;
-      sm = mx;
-    };
-    float om, ol, oo[8];
-    om = dpp_mov<0x128>(sm); ol = dpp_mov<0x128>(sl);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = dpp_mov<0x128>(so[j]);
-    merge_with(om, ol, oo);
-    om = lane_xor16(sm); ol = lane_xor16(sl);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = lane_xor16(so[j]);
-    merge_with(om, ol, oo);
-    om = lane_xor32(sm); ol = lane_xor32(sl);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = lane_xor32(so[j]);
-    merge_with(om, ol, oo);
-  }
-  if (g == 0) {
-    sm_m[wave][c] = sm; sm_l[wave][c] = sl;
-#pragma unroll
-    for (int j = 0; j < 8; j++) sm_o[wave][c][j] = so[j];
-  }
+  soft_merge_lane_groups(st);
+  soft_store_wave(sm_m, sm_l, sm_o, st, wave, g, c);
   __syncthreads();
   if (tid < 64) {
-    const int cc = tid >> 3, j = tid & 7;
-    float mx = fmaxf(fmaxf(sm_m[0][cc], sm_m[1][cc]), fmaxf(sm_m[2][cc], sm_m[3][cc]));
-    float l = 0.f, o = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      const float ww = __builtin_amdgcn_exp2f(sm_m[w][cc] - mx);
-      l += ww * sm_l[w][cc];
-      o += ww * sm_o[w][cc][j];
-    }
+    float mx, l, o;
+    soft_merge_waves(sm_m, sm_l, sm_o, tid, mx, l, o);
     p.out_bf16[((long)b * p.H + h) * 64 + tid] = f32_to_bf16(o / l);
   }
 }
@@ -1171,9 +1052,7 @@ __global__ __launch_bounds__(256) void dec_cross_prefill_kernel(DecAttnParams p)
   __shared__ float sm_m[RB][4][8], sm_l[RB][4][8], sm_o[RB][4][8][8];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ngrp = (p.rows_per_seq + RB - 1) / RB;                  // row groups per (sequence, head)
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int L = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (orig >> 3);
+  const int L = xcd_remap(blockIdx.x, gridDim.x);
   const int tg = L % ngrp, sh = L / ngrp;
   const int h = sh % p.H, sq = sh / p.H;
   const int t0 = tg * RB;
@@ -1185,59 +1064,15 @@ __global__ __launch_bounds__(256) void dec_cross_prefill_kernel(DecAttnParams p)
   const bf16_t* Kb = p.k + ((long)sq * p.H + h) * p.kv_T * 64 + 8 * c;
   const bf16_t* Vb = p.v + ((long)sq * p.H + h) * p.kv_T * 64 + 8 * c;
 
-  float q[RB][8], sm[RB], sl[RB], so[RB][8];
+  float q[RB][8];
+  SoftState st[RB];
 #pragma unroll
   for (int r = 0; r < RB; r++) {
     const int t = t0 + r < p.rows_per_seq ? t0 + r : p.rows_per_seq - 1;      // rows past the prompt repeat the last one (not stored)
-    const float4* qp = (const float4*)(p.q + ((long)(sq * p.rows_per_seq + t) * p.H + h) * 64 + 8 * c);
-    const float4 a = qp[0], d = qp[1];
-    q[r][0] = a.x; q[r][1] = a.y; q[r][2] = a.z; q[r][3] = a.w; q[r][4] = d.x; q[r][5] = d.y; q[r][6] = d.z; q[r][7] = d.w;
-    sm[r] = -1e30f; sl[r] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; j++) so[r][j] = 0.f;
+    load_q8(q[r], p.q + ((long)(sq * p.rows_per_seq + t) * p.H + h) * 64 + 8 * c);
+    soft_init(st[r]);
   }
-  auto load = [&](bf16x8 (&kf)[4], bf16x8 (&vf)[4], int base) {
-    long off[4];
-#pragma unroll
-    for (int it = 0; it < 4; it++) {
-      int key = base + it * 8 + g;
-      key = key < w1 ? key : T - 1;
-      off[it] = (long)key * 64;
-    }
-#pragma unroll
-    for (int it = 0; it < 4; it++) kf[it] = *(const bf16x8*)(Kb + off[it]);
-#pragma unroll
-    for (int it = 0; it < 4; it++) vf[it] = *(const bf16x8*)(Vb + off[it]);
-  };
-  auto reduce = [&](const bf16x8 (&kf)[4], const bf16x8 (&vf)[4], int base) {
-#pragma unroll
-    for (int r = 0; r < RB; r++) {
-      float s[4];
-#pragma unroll
-      for (int it = 0; it < 4; it++) {
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; j++) a = fmaf(q[r][j], bf16_to_f32((bf16_t)kf[it][j]), a);
-        a = group8_sum(a) * p.scale_log2e;
-        s[it] = (base + it * 8 + g < w1) ? a : -INFINITY;
-      }
-      float mn = sm[r];
-#pragma unroll
-      for (int it = 0; it < 4; it++) mn = fmaxf(mn, s[it]);
-      const float al = __builtin_amdgcn_exp2f(sm[r] - mn);
-      sl[r] *= al;
-#pragma unroll
-      for (int j = 0; j < 8; j++) so[r][j] *= al;
-#pragma unroll
-      for (int it = 0; it < 4; it++) {
-        const float pe = __builtin_amdgcn_exp2f(s[it] - mn);
-        sl[r] += pe;
-#pragma unroll
-        for (int j = 0; j < 8; j++) so[r][j] = fmaf(pe, bf16_to_f32((bf16_t)vf[it][j]), so[r][j]);
-      }
-      sm[r] = mn;
-    }
-  };
+  auto load = [&](bf16x8 (&kf)[4], bf16x8 (&vf)[4], int base) { kv_load<4, false>(kf, vf, Kb, Vb, base, g, w1, T - 1); };
   {
     // a real loop here (the decode-step kernel is straight-line code for exact load counts; this one runs once per decode
     // and lives within 256 registers only as a loop): the next piece is requested, the current one reduced against RB rows
@@ -1247,115 +1082,82 @@ __global__ __launch_bounds__(256) void dec_cross_prefill_kernel(DecAttnParams p)
     for (int i = 0; i < NP; i++) {
       const int base = w0 + 32 * i;
       load(kB, vB, base + 32 < w1 ? base + 32 : base);
-      reduce(kA, vA, base);
+#pragma unroll
+      for (int r = 0; r < RB; r++) soft_update<4>(st[r], q[r], kA, vA, base, g, w1, p.scale_log2e);
 #pragma unroll
       for (int it = 0; it < 4; it++) { kA[it] = kB[it]; vA[it] = vB[it]; }
     }
   }
 #pragma unroll
   for (int r = 0; r < RB; r++) {
-    auto merge_with = [&](float om, float ol, const float (&oo)[8]) {
-      const float mx = fmaxf(sm[r], om);
-      const float wa = __builtin_amdgcn_exp2f(sm[r] - mx), wb = __builtin_amdgcn_exp2f(om - mx);
-      sl[r] = sl[r] * wa + ol * wb;
-#pragma unroll
-      for (int j = 0; j < 8; j++) so[r][j] = so[r][j] * wa + oo[j] * wb;
-      sm[r] = mx;
-    };
-    float om, ol, oo[8];
-    om = dpp_mov<0x128>(sm[r]); ol = dpp_mov<0x128>(sl[r]);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = dpp_mov<0x128>(so[r][j]);
-    merge_with(om, ol, oo);
-    om = lane_xor16(sm[r]); ol = lane_xor16(sl[r]);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = lane_xor16(so[r][j]);
-    merge_with(om, ol, oo);
-    om = lane_xor32(sm[r]); ol = lane_xor32(sl[r]);
-#pragma unroll
-    for (int j = 0; j < 8; j++) oo[j] = lane_xor32(so[r][j]);
-    merge_with(om, ol, oo);
-    if (g == 0) {
-      sm_m[r][wave][c] = sm[r]; sm_l[r][wave][c] = sl[r];
-#pragma unroll
-      for (int j = 0; j < 8; j++) sm_o[r][wave][c][j] = so[r][j];
-    }
+    soft_merge_lane_groups<false>(st[r]);
+    soft_store_wave(sm_m[r], sm_l[r], sm_o[r], st[r], wave, g, c);
   }
   __syncthreads();
   for (int e = tid; e < RB * 64; e += 256) {
     const int r = e >> 6, d = e & 63;
     if (t0 + r >= p.rows_per_seq) continue;
-    const int cc = d >> 3, j = d & 7;
-    const float mx = fmaxf(fmaxf(sm_m[r][0][cc], sm_m[r][1][cc]), fmaxf(sm_m[r][2][cc], sm_m[r][3][cc]));
-    float l = 0.f, o = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      const float ww = __builtin_amdgcn_exp2f(sm_m[r][w][cc] - mx);
-      l += ww * sm_l[r][w][cc];
-      o += ww * sm_o[r][w][cc][j];
-    }
+    float mx, l, o;
+    soft_merge_waves(sm_m[r], sm_l[r], sm_o[r], d, mx, l, o);
     p.out_bf16[((long)(sq * p.rows_per_seq + t0 + r) * p.H + h) * 64 + d] = f32_to_bf16(o / l);
   }
 }
+
+// One instantiation the launcher below can pick.  label = the symbol that runs (rocprofv3's kernel trace shows the same name), self
+// attention marked as such; optin = its opt-in to static + dynamic LDS beyond 64 KB, for the forms that take lds_pad.
+struct DecAttnKernel {
+  const char* label;
+  void (*fn)(DecAttnParams);
+  ccx_lds_optin optin;
+};
 
 int ccx_launch_dec_attention(ccx_ctx* ctx, const DecAttnParams& p, int B, int nsplit, bool final_out,
                              hipStream_t stream) {
   CCX_REQUIRE(ctx, B > 0 && p.H > 0 && nsplit >= 1, "dec_attention: bad shape");
   CCX_REQUIRE(ctx, !final_out || nsplit == 1, "dec_attention: final output needs nsplit == 1");
+  // the streaming and prefill instantiations by pieces per wave: keys per block / 4 waves, rounded up to 32 (the kernels' own formula)
+  static DecAttnKernel prefill4[3] = {{"dec_cross_prefill_kernel<4,4>", dec_cross_prefill_kernel<4, 4>},
+                                      {"dec_cross_prefill_kernel<6,4>", dec_cross_prefill_kernel<6, 4>},
+                                      {"dec_cross_prefill_kernel<12,4>", dec_cross_prefill_kernel<12, 4>}};
+  static DecAttnKernel prefill1[3] = {{"dec_cross_stream_kernel<true,4,true>", dec_cross_stream_kernel<true, 4, true>},
+                                      {"dec_cross_stream_kernel<true,6,true>", dec_cross_stream_kernel<true, 6, true>},
+                                      {"dec_cross_stream_kernel<true,12,true>", dec_cross_stream_kernel<true, 12, true>}};
+  static DecAttnKernel streaming[3] = {{"dec_cross_stream_kernel<true,4,false>", dec_cross_stream_kernel<true, 4>},
+                                       {"dec_cross_stream_kernel<true,6,false>", dec_cross_stream_kernel<true, 6>},
+                                       {"dec_cross_stream_kernel<true,12,false>", dec_cross_stream_kernel<true, 12>}};
+  static DecAttnKernel split_kv[2][2] = {   // [self][final]
+      {{"dec_attention_kernel<false> (cross)", dec_attention_kernel<false>}, {"dec_attention_kernel<true> (cross)", dec_attention_kernel<true>}},
+      {{"dec_attention_kernel<false> (self)", dec_attention_kernel<false>}, {"dec_attention_kernel<true> (self)", dec_attention_kernel<true>}}};
+  const int np_need = p.pos ? 0 : ((ccx_cdiv(ccx_cdiv(p.T, nsplit), 4) + 31) / 32);
+  const int npi = np_need <= 4 ? 0 : (np_need <= 6 ? 1 : 2);
+  const bool prefill = p.rows_per_seq > 1 && !p.pos;
+  const int pad = p.lds_pad > 0 ? (p.lds_pad < 128 * 1024 ? p.lds_pad : 128 * 1024) : 0;
+
+  DecAttnKernel* k;
   dim3 grid(B * p.H, nsplit);
+  int lds = 0;
+  if (prefill) {
+    // prompt prefill: B = sequences here, whole key range per block.  Three rows and more: four prompt rows per block (the K/V of
+    // a (sequence, head) comes out of L2 once per four rows), else one block per (sequence, head, prompt row)
+    CCX_REQUIRE(ctx, nsplit == 1 && final_out && np_need <= 12, "dec_attention: the prefill cross attention takes the whole key range (T <= 1536)");
+    k = p.rows_per_seq >= 3 ? &prefill4[npi] : &prefill1[npi];
+    grid = dim3(B * p.H * (p.rows_per_seq >= 3 ? ccx_cdiv(p.rows_per_seq, 4) : p.rows_per_seq), 1);
+  } else if (p.stream_mode && !p.pos && np_need <= 12) {
+    CCX_REQUIRE(ctx, final_out, "dec_attention: the streaming cross attention takes the whole key range (nsplit 1)");
+    k = &streaming[npi];
+    lds = pad;
+    CCX_HIP(ctx, k->optin.ensure(ctx->device, (const void*)k->fn, 128 * 1024));
+  } else {
+    k = &split_kv[p.pos != nullptr][final_out];
+    if (!final_out) lds = pad;
+    if (lds > 0) CCX_HIP(ctx, k->optin.ensure(ctx->device, (const void*)k->fn, 128 * 1024));
+  }
   {
     // self-attention length varies per row and is known on the device only: priced at one key (q in, one K/V row, out), so that
     // the launch shows up in the per-kernel times without claiming traffic it may not have moved
     const double keys = p.pos ? 1.0 : (double)p.T;
-    // pieces per wave: keys per block / 4 waves, rounded up to 32 (the kernel's own formula)
-    const int np_need = p.pos ? 0 : ((ccx_cdiv(ccx_cdiv(p.T, nsplit), 4) + 31) / 32);
-    // profile label = the symbol that runs (rocprofv3's kernel trace shows the same name), self attention marked as such
-    const char* label;
-    const int npi = np_need <= 4 ? 0 : (np_need <= 6 ? 1 : 2);
-    if (p.pos) label = final_out ? "dec_attention_kernel<true> (self)" : "dec_attention_kernel<false> (self)";
-    else if (p.rows_per_seq > 1) {
-      static const char* const pf4[3] = {"dec_cross_prefill_kernel<4,4>", "dec_cross_prefill_kernel<6,4>", "dec_cross_prefill_kernel<12,4>"};
-      static const char* const pf1[3] = {"dec_cross_stream_kernel<true,4,true>", "dec_cross_stream_kernel<true,6,true>", "dec_cross_stream_kernel<true,12,true>"};
-      label = p.rows_per_seq >= 3 ? pf4[npi] : pf1[npi];
-    } else if (p.stream_mode && np_need <= 12) {
-      static const char* const st[3] = {"dec_cross_stream_kernel<true,4,false>", "dec_cross_stream_kernel<true,6,false>", "dec_cross_stream_kernel<true,12,false>"};
-      label = st[npi];
-    } else label = final_out ? "dec_attention_kernel<true> (cross)" : "dec_attention_kernel<false> (cross)";
-    ccx_prof_scope ps(ctx, stream, label,
-                      4.0 * B * p.H * keys * 64 * (p.rows_per_seq > 1 && !p.pos ? p.rows_per_seq : 1),
-                      (double)B * p.H * keys * 64 * 2 * 2);
-    if (p.rows_per_seq > 1 && !p.pos) {
-      // prompt prefill: B = sequences here, one block per (sequence, head, prompt row), whole key range per block
-      CCX_REQUIRE(ctx, nsplit == 1 && final_out && np_need <= 12, "dec_attention: the prefill cross attention takes the whole key range (T <= 1536)");
-      if (p.rows_per_seq >= 3) {
-        // four prompt rows per block: the K/V of a (sequence, head) comes out of L2 once per four rows
-        dim3 g4(B * p.H * ccx_cdiv(p.rows_per_seq, 4), 1);
-        if (np_need <= 4) hipLaunchKernelGGL((dec_cross_prefill_kernel<4, 4>), g4, dim3(256), 0, stream, p);
-        else if (np_need <= 6) hipLaunchKernelGGL((dec_cross_prefill_kernel<6, 4>), g4, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((dec_cross_prefill_kernel<12, 4>), g4, dim3(256), 0, stream, p);
-      } else {
-        dim3 pgrid(B * p.H * p.rows_per_seq, 1);
-        if (np_need <= 4) hipLaunchKernelGGL((dec_cross_stream_kernel<true, 4, true>), pgrid, dim3(256), 0, stream, p);
-        else if (np_need <= 6) hipLaunchKernelGGL((dec_cross_stream_kernel<true, 6, true>), pgrid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((dec_cross_stream_kernel<true, 12, true>), pgrid, dim3(256), 0, stream, p);
-      }
-    } else if (p.stream_mode && !p.pos && np_need <= 12) {
-      CCX_REQUIRE(ctx, final_out, "dec_attention: the streaming cross attention takes the whole key range (nsplit 1)");
-      const int pad = p.lds_pad > 0 ? (p.lds_pad < 128 * 1024 ? p.lds_pad : 128 * 1024) : 0;
-#define CROSS_STREAM_LAUNCH(NP_)                                                                                         \
-  do {                                                                                                                       \
-    static ccx_lds_optin optin_;                                                                                             \
-    CCX_HIP(ctx, optin_.ensure(ctx->device, (const void*)dec_cross_stream_kernel<true, NP_>, 128 * 1024));                   \
-    hipLaunchKernelGGL((dec_cross_stream_kernel<true, NP_>), grid, dim3(256), pad, stream, p);                              \
-  } while (0)
-      if (np_need <= 4) CROSS_STREAM_LAUNCH(4); else if (np_need <= 6) CROSS_STREAM_LAUNCH(6); else CROSS_STREAM_LAUNCH(12);
-#undef CROSS_STREAM_LAUNCH
-    } else if (final_out) hipLaunchKernelGGL(dec_attention_kernel<true>, grid, dim3(256), 0, stream, p);
-    else {
-      static ccx_lds_optin optin;
-      if (p.lds_pad > 0) CCX_HIP(ctx, optin.ensure(ctx->device, (const void*)dec_attention_kernel<false>, 128 * 1024));   // static + dynamic LDS beyond 64 KB
-      hipLaunchKernelGGL(dec_attention_kernel<false>, grid, dim3(256), p.lds_pad > 0 ? (p.lds_pad < 128 * 1024 ? p.lds_pad : 128 * 1024) : 0, stream, p);
-    }
+    ccx_prof_scope ps(ctx, stream, k->label, 4.0 * B * p.H * keys * 64 * (prefill ? p.rows_per_seq : 1), (double)B * p.H * keys * 64 * 2 * 2);
+    hipLaunchKernelGGL(k->fn, grid, dim3(256), lds, stream, p);
   }
   CCX_CHECK_LAUNCH(ctx);
   return CCX_OK;

@@ -482,19 +482,12 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, char* smem, int m
   else rows(std::false_type{});
 }
 
-// XCD-aware bijective remap (blocks b, b+8 share an XCD/L2): give each XCD a contiguous
-// run of tiles so the A row-panel and the (small) W are re-read from that XCD's L2.
-__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
-  const int xcd = orig & 7, qq = nwg >> 3, rr = nwg & 7;
-  return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (orig >> 3);
-}
-
 template <int EPI, int WM, int WN, int MT>
 __global__ __launch_bounds__(WM * WN * 64, (WM * WN) >= 4 ? (WM * WN) / 4 * (MT == 4 ? 2 : 1) : 4) void gemm_bf16_nt_kernel(GemmParams p) {
   constexpr int TBM = WM * MT * 16, TBN = WN * 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tiles_n = (p.N + TBN - 1) / TBN;
-  const int wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);   // the A row-panel and the (small) W are re-read from one XCD's L2
   const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
   gemm_tile<EPI, WM, WN, MT>(p, smem, tm * TBM, tn * TBN, [](const GemmParams& pp, char* sm, int m0, int n0, f32x4 (&acc)[MT][4], auto swap) {
     gemm_mainloop<decltype(swap)::value, colmap_of(EPI), WM, WN, MT>(pp, sm, m0, n0, acc);
