@@ -89,6 +89,15 @@ class DecSelectDesc(C.Structure):
         ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64)]
 
 
+class DecTokenProbsDesc(C.Structure):
+    """ccx_dec_token_probs_desc (include/ccx.h): the ranged softmax over logit rows on its own."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("logits_elems", C.c_int64), ("ld", C.c_int64), ("n_vocab", C.c_int), ("rows", C.c_int),
+        ("lo", C.c_int), ("hi", C.c_int), ("pick", C.c_int),
+        ("argmax", C.POINTER(C.c_int)), ("pick_prob", C.POINTER(C.c_float)),
+        ("probs", C.c_void_p), ("probs_elems", C.c_int64)]
+
+
 class SepDesc(C.Structure):
     """ccx_sep_desc (include/ccx.h): one SepFormer layer kernel on its own."""
     _fields_ = (
@@ -162,9 +171,12 @@ PROTOTYPES = {
     "ccx_whisper_decode_greedy": (_i, [_vp, _i32p, _i32p, _i, _i, _i, _i32p, _i32p, _fp, _fp, _vp]),
     "ccx_dec_attention_desc": (_i, [_vp, _i, C.POINTER(DecAttnDesc), _vp]),
     "ccx_dec_select_step": (_i, [_vp, C.POINTER(DecSelectDesc), _vp]),
+    "ccx_dec_token_probs": (_i, [_vp, C.POINTER(DecTokenProbsDesc), _vp]),
     "ccx_align_op": (_i, [_vp, _i, C.POINTER(AlignDesc), _vp]),
     "ccx_whisper_align": (_i, [_vp, _i32p, _i32p, _i, _i, _i32p, _i32p, _i, _i, _vp, _vp, _i32p, _vp]),
     "ccx_whisper_last_cross_path": (_i, [_vp]),
+    "ccx_whisper_set_sot_tail": (_i, [_vp, _i]),
+    "ccx_whisper_detect_language": (_i, [_vp, _i, _i, _i, _i32p, _fp, _vp]),
     "ccx_whisper_prepare_lanes": (_i, [_vp, _vp]),
     "ccx_whisper_trace_lanes": (_i, [_vp, C.c_char_p, _i]),
     "ccx_whisper_decode": (_i, [_vp, _i32p, _i32p, _i, _i, _i, _f, C.c_uint64, _i32p, _i32p, _fp, _fp, _vp]),

@@ -33,6 +33,13 @@ class BatchPipeline:
         self.ctx: _lib.Context = models["ctx"]
         self.win, self.hop, self.nra = sliding_window, sliding_step, noise_reduction_amount
         self.group, self.sample_len = whisper_group, sample_len
+        # The batch schedules decode every group from [sot_prev, prompt, sot] with ONE sample_len and never detect a language:
+        # English-only checkpoints.  A multilingual model goes through WhisperModel.transcribe / transcribe_batch (language
+        # detection, the task token, the per-sequence sample cap); here it would silently be transcribed as English.
+        for w in models.get("whisper_models") or [models["whisper_model"]]:
+            if getattr(w.rules, "is_multilingual", False):
+                raise _lib.CcxError("BatchPipeline drives English-only Whisper checkpoints (.en): a multilingual model needs "
+                                    "WhisperModel.transcribe / transcribe_batch (language detection, task token, sample cap)")
         self.stage_ms: Dict[str, float] = {}
 
     # ------------------------------------------------------------------ helpers

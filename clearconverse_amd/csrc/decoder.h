@@ -95,6 +95,15 @@ struct DecSelectParams {
 int ccx_launch_dec_select(ccx_ctx* ctx, const DecSelectParams& p, int B, hipStream_t stream);
 int ccx_launch_dec_embed(ccx_ctx* ctx, const float* tok_emb, const float* pos_emb, const int* cur_tok, const int* pos,
                          float* x, int B, int D, hipStream_t stream);
+// Softmax of logit rows over the ids [lo, hi) only (dec_probs.hip; everything else counts as -inf): argmax[row] (lowest id on equal
+// values), pick_prob[row] = probability of id `pick` (inside the range), and, if probs != nullptr, probs[row][hi - lo].
+// logits [rows][ld] f32, 16-byte aligned, ld a multiple of 4 and >= hi; hi - (lo rounded down to 4) <= 53248.  All outputs on the device.
+struct DecTokenProbsParams {
+  const float* logits; long ld;
+  int lo, hi, pick;
+  int* argmax; float* pick_prob; float* probs;
+};
+int ccx_launch_dec_token_probs(ccx_ctx* ctx, const DecTokenProbsParams& p, int rows, hipStream_t stream);
 // dst[i][:] = src[idx[i]][:] where idx[i] >= 0 (bf16 rows of D elements): the last prompt row of every sequence after a prefill pass
 int ccx_launch_dec_gather_rows(ccx_ctx* ctx, const bf16_t* src, const int* idx, bf16_t* dst, int n, int D, hipStream_t stream);
 int ccx_launch_dec_combine(ccx_ctx* ctx, const float* part_o, const float* part_ml, int nsplit, bf16_t* out, int M, int H,

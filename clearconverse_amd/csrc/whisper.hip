@@ -63,6 +63,7 @@ struct ccx_whisper {
   // derived sizes
   int Spad = 0;    // padded audio context (multiple of 128)
   int Vpad = 0;    // vocab rounded up to 128
+  int V4 = 0;      // vocab rounded up to 4: what the select kernel runs on (ids [n_vocab, V4) are always suppressed)
   int Fraw = 3008; // frames computed by the log-mel pass (covers 30 s + reflect tail)
   static constexpr int kCrossSplitMax = 8;
 
@@ -147,6 +148,14 @@ struct ccx_whisper {
   int* al_ints = nullptr;                    // tables of one call (heads, n_keys, rows) and its path / jump-frame outputs
   size_t al_P_elems = 0, al_A_elems = 0, al_trace_bytes = 0, al_ints_elems = 0;   // bytes held by each (own hipMallocs, freed at destroy)
   const struct AlignPass* align_pass = nullptr;   // non-null only inside ccx_whisper_align's teacher-forced pass: dec_step's hook
+  // SOT sequences of more than one token, vocabularies that are no multiple of 4, language detection (dec_probs.hip).  The scratch
+  // is allocated by the first call that needs it: an English-only instance allocates nothing and launches nothing for it.
+  int sot_tail = 0;                          // ccx_whisper_set_sot_tail: tokens of the SOT sequence behind <|startoftranscript|>
+  static constexpr int kMaxLang = 128;       // ids of one ccx_whisper_detect_language range
+  bf16_t* tp_xn = nullptr;                   // [max_batch][D]: final-LayerNorm row of every sequence's SOT position (run_prefill)
+  int *tp_idx = nullptr, *tp_arg = nullptr;  // [max_batch]: that row in the prefill pass (or -1); the kernel's argmax
+  float *tp_prob = nullptr, *tp_lang = nullptr;   // [max_batch]: the picked probability; [max_batch][kMaxLang]: the range's distribution
+  bool ns_at_sot() const { return sot_tail > 0 || d.n_vocab % 4 != 0; }   // no_speech_prob comes from dec_token_probs_kernel
 };
 
 // the alignment pass in flight: which heads of which layer go where in P, and the token row the current step writes
@@ -227,7 +236,7 @@ int ccx_whisper_create(ccx_ctx* ctx, const ccx_whisper_dims* dims, int max_batch
   CCX_REQUIRE(ctx, d.n_audio_state <= 1024, "whisper: n_state > 1024 not supported yet");
   CCX_REQUIRE(ctx, d.n_audio_ctx == 1500 && d.n_mels == 80, "whisper: n_audio_ctx must be 1500 and n_mels 80");
   CCX_REQUIRE(ctx, d.n_audio_ctx % 4 == 0, "whisper: n_audio_ctx must be a multiple of 4");
-  CCX_REQUIRE(ctx, d.n_vocab % 4 == 0 && d.n_vocab <= 13 * 4096, "whisper: n_vocab must be a multiple of 4 and <= 53248");
+  CCX_REQUIRE(ctx, d.n_vocab >= 4 && d.n_vocab <= 13 * 4096, "whisper: n_vocab = %d out of range [4, 53248]", d.n_vocab);
   ccx_whisper* w = new ccx_whisper();
   w->ctx = ctx;
   w->store.ctx = ctx;
@@ -236,6 +245,7 @@ int ccx_whisper_create(ccx_ctx* ctx, const ccx_whisper_dims* dims, int max_batch
   w->max_batch = max_batch;
   w->Spad = ccx_cdiv(d.n_audio_ctx, 128) * 128;
   w->Vpad = ccx_cdiv(d.n_vocab, 128) * 128;
+  w->V4 = ccx_cdiv(d.n_vocab, 4) * 4;
   *out = w;
   return CCX_OK;
 }
@@ -307,6 +317,12 @@ int ccx_whisper_set_rules(ccx_whisper* w, const ccx_decode_rules* r) {
   const int V = w->d.n_vocab;
   std::vector<unsigned char> mask;
   CCX_TRY(ccx_build_suppress_mask(w->ctx, "ccx_whisper_set_rules", r, V, mask));
+  // The select kernel runs on V4 ids: those behind the vocabulary never win or count.  Invariant: dec_select_kernel applies the mask
+  // with a select (`allowed ? val : -inf`), never with arithmetic, so whatever the logit columns [n_vocab, V4) hold cannot leak into a
+  // filtered quantity -- and they hold finite values anyway: the logits GEMM stores whole 16-column groups, up to n_vocab rounded up
+  // to 16, from weight rows clamped to n_vocab - 1 (gemm_bf16.hip).  Only the kernel's own no-speech softmax reads them unmasked,
+  // which is why that value is replaced (ns_at_sot).
+  for (int v = V; v < w->V4; v++) mask[v] = 1;
   if (!w->suppress_mask) CCX_TRY(w->store.alloc(&w->suppress_mask, (size_t)V + 4, false));
   CCX_HIP(w->ctx, hipMemcpy(w->suppress_mask, mask.data(), (size_t)V + 4, hipMemcpyHostToDevice));
   w->rules = *r;
@@ -833,7 +849,7 @@ int dec_head(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
   if (select) {
     DecSelectParams sp;
     memset(&sp, 0, sizeof(sp));
-    sp.logits = logits; sp.ld_logits = ld; sp.n_vocab = d.n_vocab; sp.state = w->state + b0; sp.prompt = w->prompt + ro * max_prompt;
+    sp.logits = logits; sp.ld_logits = ld; sp.n_vocab = w->V4; sp.state = w->state + b0; sp.prompt = w->prompt + ro * max_prompt;
     sp.max_prompt = max_prompt; sp.cur_tok = w->cur_tok + b0; sp.pos = pos; sp.gen = w->gen + ro * sample_len; sp.sample_len = sample_len;
     sp.n_done = n_done; sp.suppress_mask = w->suppress_mask; sp.eot = w->rules.eot; sp.blank = w->rules.blank;
     sp.no_speech = w->rules.no_speech; sp.timestamp_begin = w->rules.timestamp_begin;
@@ -1075,14 +1091,15 @@ int upload_decode_state(ccx_whisper* w, const int32_t* prompt_ids, const int32_t
 // segment's transcript as `initial_prompt`, up to 223 tokens: back/api.py:1424-1426) costs one pass per 16 tokens instead of one
 // decode step per token.  Positions past a shorter prompt are dead rows (their K/V land beyond the prompt and are overwritten by the
 // tokens decoded there later).  Leaves the self-KV caches filled and the final-LayerNorm row of every sequence's last prompt
-// position in w->dxn.
+// position in w->dxn -- and, for instances whose no-speech probability is read at the SOT position (ns_at_sot), the row of prompt
+// position prompt_len - 1 - sot_tail in w->tp_xn, gathered in whichever pass holds it (it can be the pass before the last token's).
 int run_prefill(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B, int P, int sample_len,
                 hipStream_t stream) {
   ccx_ctx* ctx = w->ctx;
   const int D = w->d.n_text_state, C = ccx_whisper::kPrefillMax;
   for (int t0 = 0; t0 < P; t0 += C) {
     const int Pc = P - t0 < C ? P - t0 : C, R = B * Pc;
-    std::vector<int> tok(R), ps(R), sq(R), last(B);
+    std::vector<int> tok(R), ps(R), sq(R), last(B), sot_row(B);
     for (int b = 0; b < B; b++) {
       for (int t = 0; t < Pc; t++) {
         const int r = b * Pc + t, ta = t0 + t;
@@ -1091,7 +1108,10 @@ int run_prefill(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
       }
       const int tl = prompt_lens[b] - 1 - t0;        // the sequence's last prompt position, relative to this pass
       last[b] = (tl >= 0 && tl < Pc) ? b * Pc + tl : -1;
+      const int ts = tl - w->sot_tail;               // ... and its <|startoftranscript|>
+      sot_row[b] = (ts >= 0 && ts < Pc) ? b * Pc + ts : -1;
     }
+    if (w->ns_at_sot()) CCX_HIP(ctx, hipMemcpyAsync(w->tp_idx, sot_row.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream));
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_tok, tok.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_pos, ps.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_seq, sq.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
@@ -1100,8 +1120,36 @@ int run_prefill(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
     CCX_HIP(ctx, hipStreamSynchronize(stream));     // host tables go out of scope
     CCX_TRY(dec_step(w, 0, B, nullptr, 0, false, sample_len, max_prompt, nullptr, stream, nullptr, 0, Pc));
     CCX_TRY(ccx_launch_dec_gather_rows(ctx, w->pf_xn, w->pf_last, w->dxn, B, D, stream));
+    if (w->ns_at_sot()) CCX_TRY(ccx_launch_dec_gather_rows(ctx, w->pf_xn, w->tp_idx, w->tp_xn, B, D, stream));
   }
   return CCX_OK;
+}
+
+// scratch of the ranged softmax's users, on first use (sized from max_batch)
+int ensure_token_probs_scratch(ccx_whisper* w) {
+  if (w->tp_xn) return CCX_OK;
+  const size_t B = (size_t)w->max_batch;
+  CCX_TRY(w->store.alloc(&w->tp_idx, B, true));
+  CCX_TRY(w->store.alloc(&w->tp_arg, B, true));
+  CCX_TRY(w->store.alloc(&w->tp_prob, B, true));
+  CCX_TRY(w->store.alloc(&w->tp_lang, B * ccx_whisper::kMaxLang, true));
+  CCX_TRY(w->store.alloc(&w->tp_xn, B * w->d.n_text_state, true));
+  return CCX_OK;
+}
+
+// logits of the B final-LayerNorm rows `xn` against the tied embedding into w->dlogits (dec_head's GEMM), then the softmax over the
+// ids [lo, hi): argmax -> w->tp_arg, probability of `pick` -> w->tp_prob, the range's distribution -> probs (device, may be null)
+int token_probs_of_rows(ccx_whisper* w, const bf16_t* xn, int B, int lo, int hi, int pick, float* probs, hipStream_t stream) {
+  const int D = w->d.n_text_state;
+  GemmParams gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.A = xn; gp.lda = D; gp.W = w->tok_emb_rm; gp.ldw = D; gp.M = B; gp.N = w->d.n_vocab; gp.K = D; gp.out = w->dlogits; gp.ldo = w->Vpad;
+  CCX_TRY(ccx_launch_gemm(w->ctx, EPI_F32, gp, stream));
+  DecTokenProbsParams tp;
+  memset(&tp, 0, sizeof(tp));
+  tp.logits = w->dlogits; tp.ld = w->Vpad; tp.lo = lo; tp.hi = hi; tp.pick = pick;
+  tp.argmax = w->tp_arg; tp.pick_prob = w->tp_prob; tp.probs = probs;
+  return ccx_launch_dec_token_probs(w->ctx, tp, B, stream);
 }
 
 }  // namespace
@@ -1247,6 +1295,53 @@ int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens
 
 int ccx_whisper_last_cross_path(ccx_whisper* w) { return w ? w->last_cross_path : -1; }
 
+int ccx_whisper_set_sot_tail(ccx_whisper* w, int n_tail) {
+  if (!w) return CCX_ERR_ARG;
+  CCX_REQUIRE(w->ctx, n_tail >= 0 && n_tail <= 2, "ccx_whisper_set_sot_tail: n_tail = %d out of range [0, 2]", n_tail);
+  w->sot_tail = n_tail;     // read by the host side of a decode only: the captured step graphs do not depend on it
+  return CCX_OK;
+}
+
+int ccx_whisper_detect_language(ccx_whisper* w, int B, int lang_begin, int n_lang, int32_t* lang_token_out, float* probs_out, void* stream_) {
+  if (!w) return CCX_ERR_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, w->finalized && w->rules_set, "ccx_whisper_detect_language: not finalized or rules not set");
+  CCX_REQUIRE(ctx, B >= 1 && B <= w->max_batch, "ccx_whisper_detect_language: B = %d out of range [1, max_batch = %d]", B, w->max_batch);
+  CCX_REQUIRE(ctx, n_lang >= 1 && n_lang <= ccx_whisper::kMaxLang, "ccx_whisper_detect_language: n_lang = %d out of range [1, %d]", n_lang, ccx_whisper::kMaxLang);
+  CCX_REQUIRE(ctx, lang_begin >= 0 && lang_begin + n_lang <= w->d.n_vocab, "ccx_whisper_detect_language: ids [%d, %d) outside the vocabulary of %d", lang_begin,
+              lang_begin + n_lang, w->d.n_vocab);
+  CCX_REQUIRE(ctx, lang_token_out != nullptr, "ccx_whisper_detect_language: lang_token_out is NULL");
+  CCX_REQUIRE(ctx, w->rules.sot >= 0, "ccx_whisper_detect_language: rules.sot = %d is no token", w->rules.sot);
+  if (stream == nullptr) {
+    // as ccx_whisper_decode: order after everything queued on the caller's (null) stream, then run on our own
+    CCX_HIP(ctx, hipEventRecord(w->own_event, nullptr));
+    CCX_HIP(ctx, hipStreamWaitEvent(w->own_stream, w->own_event, 0));
+    stream = w->own_stream;
+  }
+  CCX_TRY(ensure_token_probs_scratch(w));
+  // one step over [sot] at position 0 for every window: the step kernels and the cross-attention path select_cross_path picks for
+  // B rows, as ONE lane (a decode of 96 rows and more splits into lanes; a row's numbers do not depend on the split)
+  read_chain_switches(w);
+  CCX_TRY(select_cross_path(w, B, stream));
+  const std::vector<int32_t> sot(B, w->rules.sot), one(B, 1);
+  CCX_TRY(upload_decode_state(w, sot.data(), one.data(), 1, B, 0.f, 0, stream));
+  w->cross_stream = 1;
+  w->cross_lds_pad = 0;      // a single lane: the cross attention runs uncapped
+  w->last_cross_path = w->xs_active ? 2 : (B > 16 ? 1 : 0);
+  CCX_TRY(dec_step(w, 0, B, w->dlogits, w->Vpad, false, 1, 1, w->n_done, stream));
+  // dec_step left the logits of every row in w->dlogits: the softmax over the language tokens only (the GEMM is not repeated)
+  DecTokenProbsParams tp;
+  memset(&tp, 0, sizeof(tp));
+  tp.logits = w->dlogits; tp.ld = w->Vpad; tp.lo = lang_begin; tp.hi = lang_begin + n_lang; tp.pick = lang_begin;
+  tp.argmax = w->tp_arg; tp.pick_prob = w->tp_prob; tp.probs = w->tp_lang;
+  CCX_TRY(ccx_launch_dec_token_probs(ctx, tp, B, stream));
+  CCX_HIP(ctx, hipMemcpyAsync(lang_token_out, w->tp_arg, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
+  if (probs_out) CCX_HIP(ctx, hipMemcpyAsync(probs_out, w->tp_lang, (size_t)B * n_lang * 4, hipMemcpyDeviceToHost, stream));
+  CCX_HIP(ctx, hipStreamSynchronize(stream));
+  return CCX_OK;
+}
+
 int ccx_whisper_prepare_lanes(ccx_whisper* w, void* stream_) {
   if (!w) return CCX_ERR_ARG;
   CCX_REQUIRE(w->ctx, w->finalized, "whisper: not finalized");
@@ -1283,6 +1378,8 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   for (int b = 0; b < B; b++) {
     CCX_REQUIRE(ctx, prompt_lens[b] >= 1 && prompt_lens[b] <= max_prompt, "decode_greedy: prompt_lens[%d]=%d out of range", b, prompt_lens[b]);
     CCX_REQUIRE(ctx, prompt_lens[b] + sample_len - 1 <= w->d.n_text_ctx, "decode_greedy: prompt %d + sample_len %d exceeds n_text_ctx", prompt_lens[b], sample_len);
+    CCX_REQUIRE(ctx, prompt_lens[b] > w->sot_tail, "decode: prompt_lens[%d] = %d does not hold a SOT sequence of 1 + %d tokens (ccx_whisper_set_sot_tail)", b,
+                prompt_lens[b], w->sot_tail);
     for (int i = 0; i < prompt_lens[b]; i++) {
       const int t = prompt_ids[(size_t)b * max_prompt + i];
       CCX_REQUIRE(ctx, t >= 0 && t < w->d.n_vocab, "decode_greedy: prompt token %d out of range", t);
@@ -1292,7 +1389,12 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   // prompts of 2 tokens and more are prefilled, kPrefillMax positions per pass (CCX_PREFILL=0: one decode step per prompt token, round
   // 1's way)
   const int prefill_on = [] { const char* e = getenv("CCX_PREFILL"); return e ? atoi(e) : 1; }();     // read per call: tests flip it
-  const bool prefill = prefill_on && max_pl >= 2;
+  // ... and every prompt of an instance that reads its no-speech probability at the SOT position with the ranged softmax
+  const bool ns_at_sot = w->ns_at_sot();
+  CCX_REQUIRE(ctx, !ns_at_sot || prefill_on, "decode: CCX_PREFILL=0 is not available on an instance with a SOT tail (%d) or with n_vocab = %d, no multiple of 4: "
+              "its no-speech probability is taken from the prefill", w->sot_tail, w->d.n_vocab);
+  const bool prefill = prefill_on && (max_pl >= 2 || ns_at_sot);
+  if (ns_at_sot) CCX_TRY(ensure_token_probs_scratch(w));
   read_chain_switches(w);
   CCX_TRY(select_cross_path(w, B, stream));
   CCX_TRY(upload_decode_state(w, prompt_ids, prompt_lens, max_prompt, B, temperature, seed, stream, prefill));
@@ -1350,6 +1452,9 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   w->last_cross_path = w->xs_active ? 2 : ((w->cross_stream && lanes[0].B > 16) ? 1 : 0);
   if (prefill) {
     CCX_TRY(run_prefill(w, prompt_ids, prompt_lens, max_prompt, B, max_pl, sample_len, stream));
+    // no-speech probability from the raw logits at the SOT position, over the ids of the vocabulary (eager, before the captured steps;
+    // w->dlogits is free until the first sample below)
+    if (ns_at_sot) CCX_TRY(token_probs_of_rows(w, w->tp_xn, B, 0, w->d.n_vocab, w->rules.no_speech, nullptr, stream));
     // first sample of every sequence, lane by lane (each lane counts its own finished sequences)
     for (int i = 0; i < nl; i++)
       CCX_TRY(dec_head(w, lanes[i].b0, lanes[i].B, w->dlogits + (long)lanes[i].b0 * ld, ld, true, sample_len, max_prompt, w->n_done + i, stream));
@@ -1463,7 +1568,9 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   }
   std::vector<DecSeqState> st(B);
   std::vector<int> gen((size_t)B * sample_len);
+  std::vector<float> ns_sot(ns_at_sot ? B : 0);
   CCX_HIP(ctx, hipMemcpyAsync(st.data(), w->state, B * sizeof(DecSeqState), hipMemcpyDeviceToHost, stream));
+  if (ns_at_sot) CCX_HIP(ctx, hipMemcpyAsync(ns_sot.data(), w->tp_prob, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
   CCX_HIP(ctx, hipMemcpyAsync(gen.data(), w->gen, gen.size() * 4, hipMemcpyDeviceToHost, stream));
   CCX_HIP(ctx, hipStreamSynchronize(stream));
   for (int b = 0; b < B; b++) {
@@ -1473,7 +1580,8 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
     for (int i = 0; i < sample_len; i++) tokens_out[(size_t)b * sample_len + i] = (i < ntok) ? gen[(size_t)b * sample_len + i] : w->rules.eot;
     if (n_tokens_out) n_tokens_out[b] = ntok;
     if (sum_logprob_out) sum_logprob_out[b] = st[b].sum_logprob;
-    if (no_speech_prob_out) no_speech_prob_out[b] = st[b].no_speech_prob;
+    // (the select kernel's value is that of the LAST prompt position over the ids rounded up to 4: replaced where that is not the rule)
+    if (no_speech_prob_out) no_speech_prob_out[b] = ns_at_sot ? ns_sot[b] : st[b].no_speech_prob;
   }
   return CCX_OK;
 }

@@ -5,6 +5,13 @@ BPE vocabulary is not available offline, so text<->ids goes through `GPT2BPE` on
 `vocab.json`/`merges.txt` exist under MODEL_CACHE_DIR; otherwise `IdTokenizer` provides a reversible
 synthetic codec (documented deviation: transcripts are strings of token placeholders).  The
 special-token ids and the suppress list do not depend on the vocabulary file.
+
+Multilingual checkpoints (`tiny` ... `medium`, n_vocab 51865; 51866 for the 100-language family) use the
+"multilingual" vocabulary: one more text id, so every special sits one higher than its English-only
+counterpart, and the SOT sequence is [sot, <|language|>, <|transcribe|> or <|translate|>].
+`DecodeRules.multilingual()` / `DecodeRules.for_dims(dims)` give the id table, `LANGUAGES` the language
+codes in the order of their tokens, `rules.sot_sequence(language, task)` the sequence.  The tokenizers
+take the `eot` below which an id is text (default: the English-only one).
 """
 from __future__ import annotations
 
@@ -43,6 +50,49 @@ NON_SPEECH_TEXT_TOKENS = [
 SUPPRESS_TOKENS = sorted(NON_SPEECH_TEXT_TOKENS + [TRANSCRIBE, TRANSLATE, SOT, SOT_PREV, SOT_LM, NO_SPEECH])
 
 
+# Multilingual vocabulary (openai-whisper tokenizer.py, `get_encoding("multilingual", num_languages)`) [UPSTREAM-RECALL]: eot 50257,
+# sot 50258, the language tokens from 50259 in the order of LANGUAGES, then translate, transcribe, startoflm, startofprev, nospeech,
+# notimestamps and <|0.00|> = 50265 + num_languages (50364 for 99 languages; 50364 + 1501 = 51865 = n_vocab).
+MULTI_EOT = 50257
+MULTI_BLANK = 220  # " " in the multilingual vocabulary as well
+
+# Language codes in the order of their tokens (whisper/tokenizer.py LANGUAGES; restated from the locally installed `transformers`,
+# models/whisper/tokenization_whisper.py::LANGUAGES, which tests/test_multilingual_cpu.py compares against).  The first 99 belong to
+# the 51865-token checkpoints; "yue" is the 100th language of the 51866-token family.
+LANGUAGES = {
+    "en": "english", "zh": "chinese", "de": "german", "es": "spanish", "ru": "russian", "ko": "korean", "fr": "french",
+    "ja": "japanese", "pt": "portuguese", "tr": "turkish", "pl": "polish", "ca": "catalan", "nl": "dutch", "ar": "arabic",
+    "sv": "swedish", "it": "italian", "id": "indonesian", "hi": "hindi", "fi": "finnish", "vi": "vietnamese", "he": "hebrew",
+    "uk": "ukrainian", "el": "greek", "ms": "malay", "cs": "czech", "ro": "romanian", "da": "danish", "hu": "hungarian",
+    "ta": "tamil", "no": "norwegian", "th": "thai", "ur": "urdu", "hr": "croatian", "bg": "bulgarian", "lt": "lithuanian",
+    "la": "latin", "mi": "maori", "ml": "malayalam", "cy": "welsh", "sk": "slovak", "te": "telugu", "fa": "persian",
+    "lv": "latvian", "bn": "bengali", "sr": "serbian", "az": "azerbaijani", "sl": "slovenian", "kn": "kannada", "et": "estonian",
+    "mk": "macedonian", "br": "breton", "eu": "basque", "is": "icelandic", "hy": "armenian", "ne": "nepali", "mn": "mongolian",
+    "bs": "bosnian", "kk": "kazakh", "sq": "albanian", "sw": "swahili", "gl": "galician", "mr": "marathi", "pa": "punjabi",
+    "si": "sinhala", "km": "khmer", "sn": "shona", "yo": "yoruba", "so": "somali", "af": "afrikaans", "oc": "occitan",
+    "ka": "georgian", "be": "belarusian", "tg": "tajik", "sd": "sindhi", "gu": "gujarati", "am": "amharic", "yi": "yiddish",
+    "lo": "lao", "uz": "uzbek", "fo": "faroese", "ht": "haitian creole", "ps": "pashto", "tk": "turkmen", "nn": "nynorsk",
+    "mt": "maltese", "sa": "sanskrit", "lb": "luxembourgish", "my": "myanmar", "bo": "tibetan", "tl": "tagalog", "mg": "malagasy",
+    "as": "assamese", "tt": "tatar", "haw": "hawaiian", "ln": "lingala", "ha": "hausa", "ba": "bashkir", "jw": "javanese",
+    "su": "sundanese", "yue": "cantonese",
+}
+# language name (and upstream's aliases) -> code
+TO_LANGUAGE_CODE = {
+    **{name: code for code, name in LANGUAGES.items()},
+    "burmese": "my", "valencian": "ca", "flemish": "nl", "haitian": "ht", "letzeburgesch": "lb", "pushto": "ps", "panjabi": "pa",
+    "moldavian": "ro", "moldovan": "ro", "sinhalese": "si", "castilian": "es", "mandarin": "zh",
+}
+
+# Tokenizer.non_speech_tokens for the multilingual vocabulary: the entries below eot of the list `transformers` carries for the
+# multilingual checkpoints (configuration_whisper.py NON_SPEECH_TOKENS_MULTI), taken as NON_SPEECH_TEXT_TOKENS was
+NON_SPEECH_TEXT_TOKENS_MULTI = [
+    1, 2, 7, 8, 9, 10, 14, 25, 26, 27, 28, 29, 31, 58, 59, 60, 61, 62, 63, 90, 91, 92, 93, 359, 503, 522, 542, 873, 893, 902, 918,
+    922, 931, 1350, 1853, 1982, 2460, 2627, 3246, 3253, 3268, 3536, 3846, 3961, 4183, 4667, 6585, 6647, 7273, 9061, 9383, 10428,
+    10929, 11938, 12033, 12331, 12562, 13793, 14157, 14635, 15265, 15618, 16553, 16604, 18362, 18956, 20075, 21675, 22520, 26130,
+    26161, 26435, 28279, 29464, 31650, 32302, 32470, 36865, 42863, 47425, 49870, 50254,
+]
+
+
 @dataclass
 class DecodeRules:
     eot: int = EOT
@@ -54,6 +104,67 @@ class DecodeRules:
     blank: int = BLANK
     max_initial_timestamp_index: int = 50  # 1.0 s / 0.02 s
     suppress: Sequence[int] = field(default_factory=lambda: list(SUPPRESS_TOKENS))
+    # multilingual vocabularies only (0 languages: English-only, the SOT sequence is [sot])
+    num_languages: int = 0
+    translate: int = TRANSLATE
+    transcribe: int = TRANSCRIBE
+    sot_lm: int = SOT_LM
+
+    @property
+    def is_multilingual(self) -> bool:
+        return self.num_languages > 0
+
+    @property
+    def language_begin(self) -> int:
+        """id of the first language token (they are contiguous, in the order of LANGUAGES)"""
+        return self.sot + 1
+
+    @property
+    def languages(self) -> List[str]:
+        return list(LANGUAGES)[: self.num_languages]
+
+    @staticmethod
+    def multilingual(num_languages: int = 99) -> "DecodeRules":
+        """The multilingual id table [UPSTREAM-RECALL: tokenizer.py]: each English-only id one higher, `num_languages` language tokens."""
+        if not 1 <= num_languages <= len(LANGUAGES):
+            raise ValueError(f"num_languages = {num_languages} out of range [1, {len(LANGUAGES)}]")
+        sot = MULTI_EOT + 1
+        translate = sot + 1 + num_languages
+        transcribe, sot_lm, sot_prev, no_speech, no_timestamps, timestamp_begin = (translate + i for i in range(1, 7))
+        suppress = sorted(NON_SPEECH_TEXT_TOKENS_MULTI + [transcribe, translate, sot, sot_prev, sot_lm, no_speech])
+        return DecodeRules(eot=MULTI_EOT, sot=sot, sot_prev=sot_prev, no_speech=no_speech, no_timestamps=no_timestamps,
+                           timestamp_begin=timestamp_begin, blank=MULTI_BLANK, suppress=suppress, num_languages=num_languages,
+                           translate=translate, transcribe=transcribe, sot_lm=sot_lm)
+
+    @staticmethod
+    def for_dims(dims) -> "DecodeRules":
+        """model.py::Whisper.is_multilingual / num_languages: the rules of a checkpoint follow from its n_vocab."""
+        n_vocab = int(dims.n_vocab)
+        if n_vocab < 51865:
+            return DecodeRules()
+        return DecodeRules.multilingual(n_vocab - 51765 - 1)
+
+    def sot_sequence(self, language: Optional[str] = None, task: str = "transcribe") -> List[int]:
+        """tokenizer.py::Tokenizer.sot_sequence: [sot] for an English-only model, else [sot, <|language|>, <|task|>]."""
+        if not self.is_multilingual:
+            return [self.sot]
+        if task not in ("transcribe", "translate"):
+            raise ValueError(f"task must be 'transcribe' or 'translate', not {task!r}")
+        return [self.sot, self.language_token(language or "en"), self.transcribe if task == "transcribe" else self.translate]
+
+    def language_token(self, language: str) -> int:
+        code = language.lower()
+        code = TO_LANGUAGE_CODE.get(code, code)
+        langs = self.languages
+        if code not in langs:
+            raise ValueError(f"unsupported language {language!r}")
+        return self.language_begin + langs.index(code)
+
+    def language_code(self, token: int) -> str:
+        i = int(token) - self.language_begin
+        if not 0 <= i < self.num_languages:
+            raise ValueError(f"token {token} is no language token")
+        return self.languages[i]
 
 
 class IdTokenizer:
@@ -65,8 +176,11 @@ class IdTokenizer:
     name = "id-placeholder"
     _word = re.compile(r"<(\d+)>")
 
+    def __init__(self, eot: int = EOT):
+        self.eot = int(eot)       # ids below it are text
+
     def decode(self, ids: Sequence[int]) -> str:
-        return "".join(f" <{int(t)}>" for t in ids if int(t) < EOT)
+        return "".join(f" <{int(t)}>" for t in ids if int(t) < self.eot)
 
     def encode(self, text: str) -> List[int]:
         out = []
@@ -84,7 +198,8 @@ class GPT2BPE:
     """Byte-level BPE from vocab.json + merges.txt (GPT-2 files) when present under the cache dir."""
     name = "gpt2-bpe"
 
-    def __init__(self, vocab_path: str, merges_path: str):
+    def __init__(self, vocab_path: str, merges_path: str, eot: int = EOT):
+        self.eot = int(eot)
         with open(vocab_path, encoding="utf-8") as f:
             self.enc = json.load(f)
         self.dec = {v: k for k, v in self.enc.items()}
@@ -121,7 +236,7 @@ class GPT2BPE:
         return ids
 
     def decode(self, ids: Sequence[int]) -> str:
-        s = "".join(self.dec[int(t)] for t in ids if int(t) < EOT)
+        s = "".join(self.dec[int(t)] for t in ids if int(t) < self.eot)
         return bytearray(self.u2b[c] for c in s).decode("utf-8", errors="replace")
 
 
@@ -141,8 +256,9 @@ class TiktokenBPE:
     byte-pair merge: within a pre-token, repeatedly merge the adjacent pair whose concatenation has the lowest rank."""
     name = "tiktoken-bpe"
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, eot: int = EOT):
         import base64
+        self.eot = int(eot)
         self.ranks: dict = {}
         with open(path, "rb") as f:
             for line in f.read().splitlines():
@@ -172,18 +288,22 @@ class TiktokenBPE:
         return ids
 
     def decode(self, ids: Sequence[int]) -> str:
-        return b"".join(self.dec[int(t)] for t in ids if int(t) < EOT).decode("utf-8", errors="replace")
+        return b"".join(self.dec[int(t)] for t in ids if int(t) < self.eot).decode("utf-8", errors="replace")
 
 
-def get_tokenizer(cache_dir: Optional[str] = None):
+def get_tokenizer(cache_dir: Optional[str] = None, rules: Optional[DecodeRules] = None):
     """The vocabulary files the reference's whisper package would use, if a copy sits under MODEL_CACHE_DIR:
-    `gpt2.tiktoken` (openai-whisper's own asset) or GPT-2's `vocab.json` + `merges.txt`; else the placeholder codec."""
+    `gpt2.tiktoken` (openai-whisper's own asset) or GPT-2's `vocab.json` + `merges.txt`; else the placeholder codec.
+    rules: those of the model (default English-only).  A multilingual model reads `multilingual.tiktoken`, upstream's asset for it,
+    and filters text with its own eot; the GPT-2 files are the English-only vocabulary and are not offered to it."""
     cache_dir = cache_dir or os.environ.get("MODEL_CACHE_DIR", "models")
+    multi = rules is not None and rules.is_multilingual
+    eot = rules.eot if rules is not None else EOT
     for sub in ("whisper", os.path.join("whisper", "assets"), "gpt2", ""):
-        t = os.path.join(cache_dir, sub, "gpt2.tiktoken")
+        t = os.path.join(cache_dir, sub, "multilingual.tiktoken" if multi else "gpt2.tiktoken")
         if os.path.exists(t):
-            return TiktokenBPE(t)
+            return TiktokenBPE(t, eot)
         v, m = os.path.join(cache_dir, sub, "vocab.json"), os.path.join(cache_dir, sub, "merges.txt")
-        if os.path.exists(v) and os.path.exists(m):
-            return GPT2BPE(v, m)
-    return IdTokenizer()
+        if not multi and os.path.exists(v) and os.path.exists(m):
+            return GPT2BPE(v, m, eot)
+    return IdTokenizer(eot)

@@ -28,14 +28,46 @@ class WhisperDims:
     n_text_head: int = 12
     n_text_layer: int = 12
 
+    @property
+    def is_multilingual(self) -> bool:
+        """model.py::Whisper.is_multilingual: the multilingual vocabulary has one more text token."""
+        return self.n_vocab >= 51865
+
+    @property
+    def num_languages(self) -> int:
+        """model.py::Whisper.num_languages (99 for n_vocab 51865; the English-only models carry the 99 language tokens too)."""
+        return self.n_vocab - 51765 - int(self.is_multilingual)
+
     @staticmethod
     def small_en() -> "WhisperDims":
         return WhisperDims()
 
+    # the multilingual checkpoints up to `medium` (n_vocab 51865) [UPSTREAM-RECALL: the `dims` of openai-whisper's checkpoints]
     @staticmethod
-    def mini(n_layer: int = 2, n_state: int = 128) -> "WhisperDims":
-        """Reduced-depth/width config for fast parity tests (same kernels, same code path)."""
-        return WhisperDims(n_audio_state=n_state, n_audio_head=n_state // 64, n_audio_layer=n_layer,
+    def _sized(n_state: int, n_head: int, n_layer: int, n_vocab: int = 51865) -> "WhisperDims":
+        return WhisperDims(n_audio_state=n_state, n_audio_head=n_head, n_audio_layer=n_layer, n_vocab=n_vocab,
+                           n_text_state=n_state, n_text_head=n_head, n_text_layer=n_layer)
+
+    @staticmethod
+    def tiny() -> "WhisperDims":
+        return WhisperDims._sized(384, 6, 4)
+
+    @staticmethod
+    def base() -> "WhisperDims":
+        return WhisperDims._sized(512, 8, 6)
+
+    @staticmethod
+    def small() -> "WhisperDims":
+        return WhisperDims._sized(768, 12, 12)
+
+    @staticmethod
+    def medium() -> "WhisperDims":
+        return WhisperDims._sized(1024, 16, 24)
+
+    @staticmethod
+    def mini(n_layer: int = 2, n_state: int = 128, n_vocab: int = 51864) -> "WhisperDims":
+        """Reduced-depth/width config for fast parity tests (same kernels, same code path); n_vocab 51865 / 51866: multilingual."""
+        return WhisperDims(n_audio_state=n_state, n_audio_head=n_state // 64, n_audio_layer=n_layer, n_vocab=n_vocab,
                            n_text_state=n_state, n_text_head=n_state // 64, n_text_layer=n_layer)
 
 

@@ -32,6 +32,27 @@ INPUT_STRIDE = 2       # mel frames per encoder position
 CROSS_PATHS = {0: "kv16", 1: "kv_stream", 2: "xa_stream"}
 
 
+def decode_cap(prompt_len: int, n_text_ctx: int) -> int:
+    """Most tokens a sequence samples from `prompt_len` initial tokens [UPSTREAM-RECALL: decoding.py::_main_loop runs sample_len =
+    n_ctx // 2 steps and stops once `tokens.shape[-1] > n_ctx`]: min(n_ctx // 2, n_ctx + 1 - prompt_len) -- 224 for every English-only
+    prompt (at most 225 tokens), 222 for a full multilingual one (1 + 223 + 3 = 227).  No row is cut earlier than upstream cuts it, and
+    prompt_len + cap - 1 <= n_ctx, which is what ccx_whisper_decode asks for."""
+    return max(1, min(n_text_ctx // 2, n_text_ctx + 1 - int(prompt_len)))
+
+
+def groups_by_cap(active: Sequence[int], caps: Sequence[int], max_batch: int) -> List[tuple]:
+    """Decode groups of one pass over the active clips: `decode` takes ONE sample_len per call, so the clips are partitioned by
+    their cap (largest first, clip order kept inside a cap), then chunked by max_batch.  -> [(cap, [clip index, ...]), ...]."""
+    by_cap: Dict[int, List[int]] = {}
+    for i, c in zip(active, caps):
+        by_cap.setdefault(int(c), []).append(i)
+    out = []
+    for c in sorted(by_cap, reverse=True):
+        for c0 in range(0, len(by_cap[c]), max_batch):
+            out.append((c, by_cap[c][c0:c0 + max_batch]))
+    return out
+
+
 class WindowLoop:
     """Host half of openai-whisper's `transcribe()` for ONE clip [UPSTREAM-RECALL: whisper/transcribe.py, main loop]: which 30 s window
     is decoded next and with which prompt, and what a decoded window adds to the segments / tokens / `text` -- the only key the
@@ -48,8 +69,26 @@ class WindowLoop:
 
     def __init__(self, rules: DecodeRules, tokenizer, content_frames: int, initial_prompt: Optional[str], n_text_ctx: int,
                  condition_on_previous_text: bool = True, no_speech_threshold: Optional[float] = 0.6,
-                 logprob_threshold: Optional[float] = -1.0):
+                 logprob_threshold: Optional[float] = -1.0, sot_sequence: Optional[Sequence[int]] = None,
+                 language: Optional[str] = "en", task: str = "transcribe"):
+        """sot_sequence: tokenizer.sot_sequence of the clip; None: the rules' own for `language` and `task` ([sot] on an English-only
+        model).  language: what `result()` reports.  language=None on a multilingual model: PENDING -- the SOT sequence holds a
+        placeholder for the language token (-1; three tokens, so prompt lengths and caps are already right) until `set_language`
+        fills it in from the first window's detection; a pending loop must not be decoded."""
         self.rules, self.tokenizer, self.n_text_ctx = rules, tokenizer, int(n_text_ctx)
+        self.task = task
+        self.language_known = not (rules.is_multilingual and language is None and sot_sequence is None)
+        if sot_sequence is not None:
+            self.sot_sequence = [int(t) for t in sot_sequence]
+        elif self.language_known:
+            self.sot_sequence = rules.sot_sequence(language, task)
+        else:
+            self.sot_sequence = [rules.sot, -1, rules.sot_sequence("en", task)[2]]
+        if not rules.is_multilingual:
+            language = "en"
+        elif self.language_known and sot_sequence is None:
+            language = rules.language_code(self.sot_sequence[1])       # a name ("German") is reported as its code
+        self.language = language
         self.content = int(content_frames)
         self.condition, self.no_speech_threshold, self.logprob_threshold = condition_on_previous_text, no_speech_threshold, logprob_threshold
         ipt = tokenizer.encode(" " + initial_prompt.strip()) if initial_prompt else []
@@ -66,12 +105,21 @@ class WindowLoop:
         return self.all_tokens[self.reset:]
 
     def initial_tokens(self) -> List[int]:
-        """decoding.py::_get_initial_tokens: [sot_prev] + prompt[-(n_ctx // 2 - 1):] + [sot]."""
+        """decoding.py::_get_initial_tokens: [sot_prev] + prompt[-(n_ctx // 2 - 1):] + sot_sequence."""
         p = self.prompt_tokens()
         toks: List[int] = []
         if len(p):
             toks = [self.rules.sot_prev] + list(p)[-(self.n_text_ctx // 2 - 1):]
-        return toks + [self.rules.sot]
+        return toks + list(self.sot_sequence)
+
+    def set_language(self, code: str) -> None:
+        """the detected language of a pending loop"""
+        self.sot_sequence = self.rules.sot_sequence(code, self.task)
+        self.language, self.language_known = code, True
+
+    def sample_cap(self) -> int:
+        """Tokens the next window may sample: decode_cap of its initial tokens."""
+        return decode_cap(len(self.initial_tokens()), self.n_text_ctx)
 
     def window_segments(self, r: dict):
         """The segments one decoded window yields, before empty ones are cleared: (segments, single_timestamp_ending, next seek by the
@@ -153,7 +201,7 @@ class WindowLoop:
 
     def result(self) -> dict:
         text_tokens = self.all_tokens[self.n_init:]
-        return dict(text=self.tokenizer.decode(text_tokens), segments=self.segments, language="en", tokens=list(text_tokens))
+        return dict(text=self.tokenizer.decode(text_tokens), segments=self.segments, language=self.language, tokens=list(text_tokens))
 
 
 class WhisperModel:
@@ -177,8 +225,8 @@ class WhisperModel:
         self.device = torch.device("cuda", device)
         self.ctx = ctx or _lib.Context(device)
         self.lib = self.ctx.lib
-        self.rules = rules or DecodeRules()
-        self.tokenizer = tokenizer or get_tokenizer()
+        self.rules = rules or DecodeRules.for_dims(dims)     # model.py::Whisper.is_multilingual: the vocabulary size decides
+        self.tokenizer = tokenizer or get_tokenizer(rules=self.rules)
         h = C.c_void_p()
         cd = _lib.WhisperDims(**asdict(dims))
         self.ctx.check(self.lib.ccx_whisper_create(self.ctx.handle, C.byref(cd), self.max_batch, C.byref(h)),
@@ -228,6 +276,26 @@ class WhisperModel:
                              len(rules.suppress), sup)
         self.ctx.check(self.lib.ccx_whisper_set_rules(self.handle, C.byref(r)), "ccx_whisper_set_rules")
         self.rules = rules
+        # tokens of the SOT sequence behind sot: the no-speech probability is read at sot's position (decoding.py `sot_index`)
+        self.set_sot_tail(len(rules.sot_sequence()) - 1)
+
+    def set_sot_tail(self, n_tail: int):
+        self.ctx.check(self.lib.ccx_whisper_set_sot_tail(self.handle, int(n_tail)), "ccx_whisper_set_sot_tail")
+        self.sot_tail = int(n_tail)
+
+    def detect_language(self, B: int):
+        """whisper.decoding.detect_language for the B currently encoded windows (ccx_whisper_detect_language): one decoder step
+        on [sot], softmax over the language tokens.  -> (codes [B], probs [B, num_languages] float32 numpy, in LANGUAGES order).
+        A decode of the same windows afterwards is what it is without this call."""
+        if not self.rules.is_multilingual:
+            raise _lib.CcxError("detect_language needs a multilingual model (this one's vocabulary is English-only)")
+        n = self.rules.num_languages
+        tok = np.zeros(B, dtype=np.int32)
+        probs = np.zeros((B, n), dtype=np.float32)
+        self.ctx.check(self.lib.ccx_whisper_detect_language(
+            self.handle, int(B), self.rules.language_begin, n, tok.ctypes.data_as(C.POINTER(C.c_int32)),
+            probs.ctypes.data_as(C.POINTER(C.c_float)), _lib.current_stream_ptr()), "ccx_whisper_detect_language")
+        return [self.rules.language_code(t) for t in tok], probs
 
     def close(self):
         if getattr(self, "handle", None):
@@ -291,12 +359,14 @@ class WhisperModel:
         """DecodingTask.run over the currently encoded windows; prompts[b] are the full initial tokens
         (sot_prev + prompt + sot).  temperature 0: argmax.  temperature > 0: one Categorical(logits / T) sample per
         step (decoding.py::GreedyDecoder.update), drawn on the device from Philox noise keyed by
-        (seed, row, step, token id) -- reproducible, not bit-equal to torch's sampler."""
+        (seed, row, step, token id) -- reproducible, not bit-equal to torch's sampler.
+        sample_len None: decode_cap of the longest prompt -- n_text_ctx // 2 = 224 for every prompt of up to 225 tokens (what the
+        default always was), fewer for a longer one, which the fixed 224 made the library refuse."""
         if not (temperature >= 0.0):
             raise _lib.CcxError("temperature must be >= 0")
         B = len(prompts)
-        sample_len = sample_len or self.dims.n_text_ctx // 2
         mp = max(len(p) for p in prompts)
+        sample_len = sample_len or decode_cap(mp, self.dims.n_text_ctx)
         ids = np.full((B, mp), self.rules.eot, dtype=np.int32)
         lens = np.zeros(B, dtype=np.int32)
         for b, p in enumerate(prompts):
@@ -355,7 +425,10 @@ class WhisperModel:
         jumps = None
         if any(texts):
             frames = [max(2, min(N_FRAMES, state[i].content - state[i].seek)) for i in grp]
-            jumps, _, _ = self.align([alignment_tokens(t, self.rules) for t in texts], frames)
+            # one teacher-forced batch: every window with its own SOT sequence (all of one length: the DTW starts behind it)
+            seqs = [state[i].sot_sequence for i in grp]
+            assert all(len(sq) == len(seqs[0]) for sq in seqs), "one model, one SOT-sequence length: the DTW's row0 is per call"
+            jumps, _, _ = self.align([alignment_tokens(t, self.rules, sq) for t, sq in zip(texts, seqs)], frames, row0=len(seqs[0]))
         for b, (i, r) in enumerate(zip(grp, results)):
             segs, end = None, None
             if built[b] is not None:
@@ -365,31 +438,41 @@ class WhisperModel:
             state[i].advance(r, temperature, last_word_end=end, segments=segs)
 
     # ------------------------------------------------------------------ transcribe (reference call surface)
-    def initial_tokens(self, prompt_tokens: Sequence[int]) -> List[int]:
-        """decoding.py::_get_initial_tokens: [sot_prev] + prompt[-(n_ctx//2 - 1):] + [sot]."""
+    def initial_tokens(self, prompt_tokens: Sequence[int], sot_sequence: Optional[Sequence[int]] = None) -> List[int]:
+        """decoding.py::_get_initial_tokens: [sot_prev] + prompt[-(n_ctx//2 - 1):] + sot_sequence (default: the rules' own --
+        [sot], or [sot, <|en|>, <|transcribe|>] on a multilingual model)."""
         toks: List[int] = []
         if len(prompt_tokens):
             toks = [self.rules.sot_prev] + list(prompt_tokens)[-(self.dims.n_text_ctx // 2 - 1):]
-        return toks + [self.rules.sot]
+        return toks + list(sot_sequence if sot_sequence is not None else self.rules.sot_sequence())
 
     def transcribe(self, audio, initial_prompt: Optional[str] = None, word_timestamps: bool = False,
                    condition_on_previous_text: bool = True, temperature: float = 0.0,
-                   no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0, **_ignored):
+                   no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0,
+                   language: Optional[str] = None, task: str = "transcribe", **_ignored):
         """One clip, same signature as whisper.transcribe as the reference uses it.  temperature 0 is the
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
         fallback loop upstream either.  Draws are reproducible: seeded by `self.sample_seed` and a per-call
         counter.  word_timestamps only changes fields the reference never reads, and only on an instance built with
-        `word_alignment=True` (segments get `words`, `seek` follows the last aligned word); otherwise it has no effect."""
+        `word_alignment=True` (segments get `words`, `seek` follows the last aligned word); otherwise it has no effect.
+        language / task: on a multilingual model the SOT sequence is [sot, <|language|>, <|task|>]; language None (upstream's
+        default, what the reference's calls leave it at) detects it on the first window.  An English-only model reports "en" and
+        ignores both, as upstream's transcribe does."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
                                      temperature=temperature, no_speech_threshold=no_speech_threshold,
-                                     logprob_threshold=logprob_threshold, word_timestamps=word_timestamps)[0]
+                                     logprob_threshold=logprob_threshold, word_timestamps=word_timestamps,
+                                     languages=[language], task=task)[0]
 
     def transcribe_batch(self, audios: Sequence, initial_prompts: Optional[Sequence[Optional[str]]] = None,
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
                          no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0,
-                         word_timestamps: bool = False) -> List[dict]:
-        """Independent clips decoded together (each window of each clip is one sequence of a batch)."""
+                         word_timestamps: bool = False, languages: Optional[Sequence[Optional[str]]] = None,
+                         task: str = "transcribe") -> List[dict]:
+        """Independent clips decoded together (each window of each clip is one sequence of a batch).
+        languages[i] (multilingual models): the clip's language code or name; None: detected on the clip's first window, after its
+        group's `encode` and before its `decode` [UPSTREAM-RECALL: transcribe.py, `if decode_options.get("language") is None`].
+        A pass over the active clips is split into groups of one sample cap (decode_cap) of at most max_batch windows."""
         with_words = bool(word_timestamps) and self.word_alignment
         if isinstance(temperature, (tuple, list)):
             raise _lib.CcxError("temperature fallback schedules are not implemented: pass one temperature (the reference does)")
@@ -407,8 +490,14 @@ class WhisperModel:
                 a = a.detach().to("cpu").numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
                 clips.append(np.ascontiguousarray(a.reshape(-1), dtype=np.float32))
             lens = [len(c) for c in clips]
+        multi = self.rules.is_multilingual
+        languages = list(languages) if languages is not None else [None] * n
+        if len(languages) != n:
+            raise _lib.CcxError("transcribe_batch: one language entry (or None) per clip")
+        # English-only: language "en", task ignored.  Multilingual: the clip's SOT sequence; language None: pending until detected
         state = [WindowLoop(self.rules, self.tokenizer, lens[i] // HOP, initial_prompts[i], self.dims.n_text_ctx,
-                            condition_on_previous_text, no_speech_threshold, logprob_threshold) for i in range(n)]
+                            condition_on_previous_text, no_speech_threshold, logprob_threshold,
+                            language=languages[i] if multi else "en", task=task) for i in range(n)]
         stride = max(max(lens, default=1), 1)
         if stride > self.max_audio_seconds * SAMPLE_RATE:
             raise _lib.CcxError(f"clip of {stride / SAMPLE_RATE:.1f} s exceeds max_audio_seconds={self.max_audio_seconds}")
@@ -426,17 +515,24 @@ class WhisperModel:
             active = [i for i in range(n) if state[i].active()]
             if not active:
                 break
-            for c0 in range(0, len(active), self.max_batch):
-                grp = active[c0:c0 + self.max_batch]
+            # (a clip whose language is still to be detected already holds a three-token SOT sequence: its cap is known)
+            caps = [state[i].sample_cap() for i in active]
+            for cap, grp in groups_by_cap(active, caps, self.max_batch):
                 if len(grp) == n:
                     a = dev_audio
                 else:
                     a = dev_audio.index_select(0, torch.tensor(grp, device=self.device)).contiguous()
                 self.log_mel(a, [lens[i] for i in grp], [state[i].seek for i in grp])
                 self.encode(len(grp))
+                if any(not state[i].language_known for i in grp):     # first window of a clip without a language
+                    codes, _ = self.detect_language(len(grp))
+                    for b, i in enumerate(grp):
+                        if not state[i].language_known:
+                            state[i].set_language(codes[b])
                 prompts = [state[i].initial_tokens() for i in grp]
                 self._sample_calls += 1
-                results = self.decode(prompts, temperature=temperature, seed=(int(self.sample_seed) << 32) + self._sample_calls)
+                results = self.decode(prompts, sample_len=cap, temperature=temperature,
+                                      seed=(int(self.sample_seed) << 32) + self._sample_calls)
                 if with_words:     # before the next log_mel: the group's windows are still encoded
                     self._advance_with_words(grp, results, state, temperature)
                     continue

@@ -90,10 +90,12 @@ def merge_punctuations(alignment: List[WordTiming], prepended: str = PREPEND_PUN
         j += 1
 
 
-def alignment_tokens(text_tokens: Sequence[int], rules) -> List[int]:
-    """[UPSTREAM-RECALL: find_alignment] the teacher-forced sequence of the English-only models:
-    [*sot_sequence, no_timestamps, *text_tokens, eot] with sot_sequence = [sot].  Rows 1 .. -1 go to the DTW."""
-    return [rules.sot, rules.no_timestamps, *[int(t) for t in text_tokens], rules.eot]
+def alignment_tokens(text_tokens: Sequence[int], rules, sot_sequence: Optional[Sequence[int]] = None) -> List[int]:
+    """[UPSTREAM-RECALL: find_alignment] the teacher-forced sequence [*sot_sequence, no_timestamps, *text_tokens, eot]; sot_sequence
+    defaults to [sot] (the English-only models; [sot, <|language|>, <|task|>] on a multilingual one).  Rows len(sot_sequence) .. -1
+    go to the DTW."""
+    sot_sequence = [rules.sot] if sot_sequence is None else [int(t) for t in sot_sequence]
+    return [*sot_sequence, rules.no_timestamps, *[int(t) for t in text_tokens], rules.eot]
 
 
 def find_alignment(tokenizer, rules, text_tokens: Sequence[int], jump_frame: Sequence[int]) -> List[WordTiming]:

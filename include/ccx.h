@@ -274,6 +274,25 @@ typedef struct ccx_dec_select_desc {
  * the next step's embedding x[b] = tok_emb[next] + pos_emb[pos]. */
 int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* desc, void* stream);
 
+/* Softmax of logit rows over an id range (csrc/dec_probs.hip: dec_token_probs_kernel, one block per row).  Over the ids [lo, hi) only --
+ * everything else, the columns [n_vocab, ld) included, counts as -inf and is never looked at: argmax[row] (lowest id on equal values,
+ * as the select kernel and torch.argmax on the CPU), pick_prob[row] = softmax probability of the id `pick`, and, if probs != NULL,
+ * probs[row][hi - lo].  fp32, max-subtracted; -inf inside the range contributes 0.  n_vocab need not be a multiple of 4.
+ * The model uses it for the no-speech probability at the SOT position (lo = 0, hi = n_vocab, pick = <|nospeech|>; decoding.py
+ * `logits[:, self.sot_index].float().softmax(dim=-1)[:, tokenizer.no_speech]`) and for language detection (the contiguous language
+ * tokens; decoding.py::detect_language).  Checked on the host before the launch, CCX_ERR_ARG (1) naming "ccx_dec_token_probs" and the
+ * field: 1 <= rows <= 65536, 1 <= n_vocab <= 53248, ld >= n_vocab and a multiple of 4, 0 <= lo < hi <= n_vocab, lo <= pick < hi, logits
+ * 16-byte aligned with logits_elems >= (rows - 1) * ld + hi rounded up to 4, probs (if given) 4-byte aligned with probs_elems >=
+ * rows * (hi - lo).  Owns and frees its scratch; synchronises the stream. */
+typedef struct ccx_dec_token_probs_desc {
+  const void* logits; int64_t logits_elems;   /* device f32 [rows][ld] */
+  int64_t ld; int n_vocab; int rows;
+  int lo, hi, pick;
+  int* argmax; float* pick_prob;              /* HOST [rows], out */
+  void* probs; int64_t probs_elems;           /* optional device f32 [rows][hi - lo], out */
+} ccx_dec_token_probs_desc;
+int ccx_dec_token_probs(ccx_ctx* ctx, const ccx_dec_token_probs_desc* desc, void* stream);
+
 /* ---- word alignment (csrc/align.hip): what transcribe(word_timestamps=True) of the reference asks for (back/api.py:1435, 1477) --
  * openai-whisper's timing.py::find_alignment [UPSTREAM-RECALL]: cross-attention probabilities of the alignment heads over the first
  * num_frames // 2 encoder positions, standardised over the tokens, median-filtered over the frames, averaged over the heads, and a
@@ -329,11 +348,35 @@ int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens
                       const int32_t* heads, int n_heads, int row0, float* probs_out_dev, float* matrix_out_dev,
                       int32_t* jump_frame_out, void* stream);
 
-/* Which cross-attention formulation the last ccx_whisper_decode of this instance ran (measurement / test records; the reference has one
+/* Which cross-attention formulation the last ccx_whisper_decode (or ccx_whisper_detect_language) of this instance ran (measurement / test records; the reference has one
  * formulation, MultiHeadAttention.forward(x, xa) behind back/api.py:1286-1292): 0 = "kv16" (per-layer K / V caches, split-KV kernels,
  * <= 16 sequences), 1 = "kv_stream" (per-layer K / V caches, dec_cross_stream_kernel, 17 - 80 sequences), 2 = "xa_stream" (one pass over
  * the encoder output per layer, csrc/cross_x.hip, more than 80 sequences); -1 before the first decode. */
 int ccx_whisper_last_cross_path(ccx_whisper* w);
+
+/* ---- multilingual checkpoints (tiny / base / small / medium: n_vocab 51865; the ids of the 51866-token family work too) ----------
+ * Any n_vocab <= 53248 is accepted.  Inside the model the select kernel runs on n_vocab rounded up to 4 with the ids behind n_vocab
+ * always suppressed; for a multiple of 4 nothing changes.
+ *
+ * ccx_whisper_set_sot_tail: n_tail = tokens of the SOT sequence BEHIND <|startoftranscript|> (0 for the English-only models,
+ * 2 for [sot, <|lang|>, <|transcribe|> or <|translate|>]; decoding.py `self.sot_index = self.initial_tokens.index(tokenizer.sot)`).
+ * Default 0, allowed 0 .. 2.  With n_tail > 0, or with n_vocab not a multiple of 4, the no_speech_prob of ccx_whisper_decode is the
+ * softmax probability of rules.no_speech over the ids [0, n_vocab) of the logits at prompt position prompt_len - 1 - n_tail (one more
+ * gathered row per sequence in the prefill, one logits GEMM over those rows and dec_token_probs_kernel, all before the captured
+ * steps); every prompt must then be longer than n_tail tokens and is prefilled -- CCX_PREFILL=0 (a debugging switch) is refused with
+ * CCX_ERR_ARG.  With n_tail == 0 and n_vocab a multiple of 4 a decode issues exactly the launches it issued before. */
+int ccx_whisper_set_sot_tail(ccx_whisper* w, int n_tail);
+/* whisper.decoding.detect_language (what transcribe(language=None), upstream's default and the reference's call at
+ * back/api.py:1286-1292, runs on the first window) for the B windows currently encoded: one decoder pass over the single token
+ * rules.sot at position 0 -- the step kernels and the cross-attention path (ccx_whisper_last_cross_path, which this call sets) of a
+ * decode of B rows, run as one lane whatever B is (large decodes split into lanes; a row's numbers do not depend on the split) and on
+ * the instance's own stream when `stream` is NULL, as ccx_whisper_decode does -- then the logits GEMM and
+ * dec_token_probs_kernel over the ids [lang_begin, lang_begin + n_lang) (n_lang <= 128; upstream's language tokens are contiguous).
+ * lang_token_out host [B]: the most probable language token; probs_out host [B][n_lang] or NULL: the distribution over the range.
+ * Leaves the encoder output as it found it: a ccx_whisper_decode of the same windows afterwards returns what it returns without
+ * this call.  Valid for every B a decode accepts.  Synchronises the stream. */
+int ccx_whisper_detect_language(ccx_whisper* w, int B, int lang_begin, int n_lang, int32_t* lang_token_out, float* probs_out,
+                                void* stream);
 
 /* Batch-driver helper with no counterpart in the reference (it decodes one window at a time, back/api.py:1286): picks, once, the
  * internal streams on which the lanes of a large decode batch will run beside `stream` (HIP maps streams onto a few hardware
