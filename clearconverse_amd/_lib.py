@@ -98,6 +98,14 @@ class DecTokenProbsDesc(C.Structure):
         ("probs", C.c_void_p), ("probs_elems", C.c_int64)]
 
 
+class DecPickProbsDesc(C.Structure):
+    """ccx_dec_pick_probs_desc (include/ccx.h): the probability of one picked id per logit row on its own."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("logits_elems", C.c_int64), ("ld", C.c_int64), ("rows", C.c_int), ("hi", C.c_int),
+        ("picks", C.c_void_p), ("picks_elems", C.c_int64), ("pick_stride", C.c_int64),
+        ("out", C.c_void_p), ("out_elems", C.c_int64), ("out_stride", C.c_int64)]
+
+
 class SepDesc(C.Structure):
     """ccx_sep_desc (include/ccx.h): one SepFormer layer kernel on its own."""
     _fields_ = (
@@ -172,8 +180,10 @@ PROTOTYPES = {
     "ccx_dec_attention_desc": (_i, [_vp, _i, C.POINTER(DecAttnDesc), _vp]),
     "ccx_dec_select_step": (_i, [_vp, C.POINTER(DecSelectDesc), _vp]),
     "ccx_dec_token_probs": (_i, [_vp, C.POINTER(DecTokenProbsDesc), _vp]),
+    "ccx_dec_pick_probs": (_i, [_vp, C.POINTER(DecPickProbsDesc), _vp]),
     "ccx_align_op": (_i, [_vp, _i, C.POINTER(AlignDesc), _vp]),
     "ccx_whisper_align": (_i, [_vp, _i32p, _i32p, _i, _i, _i32p, _i32p, _i, _i, _vp, _vp, _i32p, _vp]),
+    "ccx_whisper_align_probs": (_i, [_vp, _i32p, _i32p, _i, _i, _i32p, _i32p, _i, _i, _vp, _vp, _i32p, _i, _fp, _vp]),
     "ccx_whisper_last_cross_path": (_i, [_vp]),
     "ccx_whisper_set_sot_tail": (_i, [_vp, _i]),
     "ccx_whisper_detect_language": (_i, [_vp, _i, _i, _i, _i32p, _fp, _vp]),

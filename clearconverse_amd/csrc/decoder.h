@@ -104,6 +104,16 @@ struct DecTokenProbsParams {
   int* argmax; float* pick_prob; float* probs;
 };
 int ccx_launch_dec_token_probs(ccx_ctx* ctx, const DecTokenProbsParams& p, int rows, hipStream_t stream);
+// Probability of one picked id per row over the ids [0, hi) (dec_probs.hip, the row pass of the kernel above): out[row * out_stride] =
+// softmax(logits[row][0 : hi])[picks[row * pick_stride]]; a row whose pick is negative is skipped (nothing loaded, nothing written).
+// logits as above, hi <= 53248; picks (int32) and out (f32) on the device, every pick below hi (the caller checks).
+struct DecPickProbsParams {
+  const float* logits; long ld;
+  int hi;
+  const int* picks; long pick_stride;
+  float* out; long out_stride;
+};
+int ccx_launch_dec_pick_probs(ccx_ctx* ctx, const DecPickProbsParams& p, int rows, hipStream_t stream);
 // dst[i][:] = src[idx[i]][:] where idx[i] >= 0 (bf16 rows of D elements): the last prompt row of every sequence after a prefill pass
 int ccx_launch_dec_gather_rows(ccx_ctx* ctx, const bf16_t* src, const int* idx, bf16_t* dst, int n, int D, hipStream_t stream);
 int ccx_launch_dec_combine(ccx_ctx* ctx, const float* part_o, const float* part_ml, int nsplit, bf16_t* out, int M, int H,

@@ -147,6 +147,8 @@ struct ccx_whisper {
   unsigned char* al_trace = nullptr;
   int* al_ints = nullptr;                    // tables of one call (heads, n_keys, rows) and its path / jump-frame outputs
   size_t al_P_elems = 0, al_A_elems = 0, al_trace_bytes = 0, al_ints_elems = 0;   // bytes held by each (own hipMallocs, freed at destroy)
+  int* al_picks = nullptr;                   // ccx_whisper_align_probs only: [seqs][T] picked ids, then [seqs][T] f32 probabilities
+  size_t al_picks_bytes = 0;
   const struct AlignPass* align_pass = nullptr;   // non-null only inside ccx_whisper_align's teacher-forced pass: dec_step's hook
   // SOT sequences of more than one token, vocabularies that are no multiple of 4, language detection (dec_probs.hip).  The scratch
   // is allocated by the first call that needs it: an English-only instance allocates nothing and launches nothing for it.
@@ -274,7 +276,7 @@ void ccx_whisper_destroy(ccx_whisper* w) {
   for (int i = 0; i < ccx_whisper::kLanePool; i++)
     if (w->lane_pool[i]) hipStreamDestroy(w->lane_pool[i]);
   if (w->poll_host) hipHostFree(w->poll_host);
-  for (void* p : {(void*)w->al_P, (void*)w->al_A, (void*)w->al_trace, (void*)w->al_ints})
+  for (void* p : {(void*)w->al_P, (void*)w->al_A, (void*)w->al_trace, (void*)w->al_ints, (void*)w->al_picks})
     if (p) hipFree(p);
   w->store.free_all();
   delete w;
@@ -1186,6 +1188,14 @@ int ccx_whisper_decoder_logits(ccx_whisper* w, const int32_t* tokens, int B, int
 int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens, int max_len, int B, const int32_t* n_frames,
                       const int32_t* heads, int n_heads, int row0, float* probs_out_dev, float* matrix_out_dev, int32_t* jump_frame_out,
                       void* stream_) {
+  return ccx_whisper_align_probs(w, tokens, lens, max_len, B, n_frames, heads, n_heads, row0, probs_out_dev, matrix_out_dev, jump_frame_out, 0,
+                                 nullptr, stream_);
+}
+
+// The messages keep the name ccx_whisper_align: that is the pass, with or without the token probabilities.
+int ccx_whisper_align_probs(ccx_whisper* w, const int32_t* tokens, const int32_t* lens, int max_len, int B, const int32_t* n_frames,
+                            const int32_t* heads, int n_heads, int row0, float* probs_out_dev, float* matrix_out_dev,
+                            int32_t* jump_frame_out, int prob_hi, float* token_prob_out, void* stream_) {
   if (!w) return CCX_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   ccx_ctx* ctx = w->ctx;
@@ -1199,6 +1209,8 @@ int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens
   CCX_REQUIRE(ctx, d.n_audio_ctx <= CCX_ALIGN_MAX_FRAMES, "ccx_whisper_align: n_audio_ctx = %d, the kernels hold %d frames", d.n_audio_ctx, CCX_ALIGN_MAX_FRAMES);
   CCX_REQUIRE(ctx, n_heads >= 1 && n_heads <= CCX_ALIGN_MAX_HEADS, "ccx_whisper_align: n_heads = %d out of range [1, %d]", n_heads, CCX_ALIGN_MAX_HEADS);
   CCX_REQUIRE(ctx, row0 >= 0, "ccx_whisper_align: row0 = %d is negative", row0);
+  if (token_prob_out)
+    CCX_REQUIRE(ctx, prob_hi >= 1 && prob_hi <= d.n_vocab, "ccx_whisper_align_probs: prob_hi = %d out of range [1, n_vocab = %d]", prob_hi, d.n_vocab);
   const int Mmax = d.n_audio_ctx, T = max_len, L = d.n_text_layer;
   std::vector<int> keys(B), r1(B), nrows(B);
   std::vector<int32_t> padded((size_t)B * T, w->rules.eot);
@@ -1212,6 +1224,18 @@ int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens
       CCX_REQUIRE(ctx, tok >= 0 && tok < d.n_vocab, "ccx_whisper_align: tokens[%d][%d] = %d out of range [0, n_vocab = %d)", b, t, tok, d.n_vocab);
       padded[(size_t)b * T + t] = tok;
     }
+  }
+  // token probabilities: row t predicts tokens[b][t + 1]; the text tokens are rows row0 .. lens[b] - 3 (find_alignment's
+  // logits[len(sot_sequence):, :eot] at the text tokens); -1 everywhere else, which the kernel skips
+  std::vector<int32_t> picks;
+  if (token_prob_out) {
+    picks.assign((size_t)B * T, -1);
+    for (int b = 0; b < B; b++)
+      for (int t = row0; t <= lens[b] - 3; t++) {
+        const int32_t tok = padded[(size_t)b * T + t + 1];
+        CCX_REQUIRE(ctx, tok < prob_hi, "ccx_whisper_align_probs: tokens[%d][%d] = %d is a text token at or behind prob_hi = %d", b, t + 1, tok, prob_hi);
+        picks[(size_t)b * T + t] = tok;
+      }
   }
   // (layer, head) pairs -> per-layer ranges of the device tables; P's head axis keeps the caller's order
   AlignPass pass;
@@ -1249,6 +1273,12 @@ int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens
   CCX_TRY(grow((void**)&w->al_A, &w->al_A_elems, A_need * sizeof(float)));
   CCX_TRY(grow((void**)&w->al_trace, &w->al_trace_bytes, tr_need));
   CCX_TRY(grow((void**)&w->al_ints, &w->al_ints_elems, ints_need * sizeof(int)));
+  float* tprob = nullptr;
+  if (token_prob_out) {
+    CCX_TRY(grow((void**)&w->al_picks, &w->al_picks_bytes, 2 * seqs * Tcap * 4));
+    tprob = (float*)(w->al_picks + seqs * Tcap);
+    CCX_HIP(ctx, hipMemcpyAsync(w->al_picks, picks.data(), (size_t)B * T * 4, hipMemcpyHostToDevice, stream));
+  }
   int* i_heads = w->al_ints;
   int* i_hsel = i_heads + CCX_ALIGN_MAX_HEADS;
   int* i_keys = i_hsel + CCX_ALIGN_MAX_HEADS;
@@ -1280,6 +1310,10 @@ int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens
   for (int t = 0; t < T; t++) {
     pass.t = t;
     CCX_TRY(dec_step(w, 0, B, w->dlogits, w->Vpad, t + 1 < T, 1, T, w->n_done, stream));
+    if (token_prob_out && t >= row0 && t <= T - 3) {      // only reads the step's logits: column t of the two [B][T] tables
+      DecPickProbsParams pp{w->dlogits, (long)w->Vpad, prob_hi, w->al_picks + t, (long)T, tprob + t, (long)T};
+      CCX_TRY(ccx_launch_dec_pick_probs(ctx, pp, B, stream));
+    }
   }
   w->align_pass = nullptr;
   AlignMatrixParams mp{w->al_P, w->al_A, n_heads, T, Mmax, i_rows, i_keys};
@@ -1289,7 +1323,16 @@ int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens
   if (probs_out_dev) CCX_HIP(ctx, hipMemcpyAsync(probs_out_dev, w->al_P, (size_t)B * n_heads * T * Mmax * 4, hipMemcpyDeviceToDevice, stream));
   if (matrix_out_dev) CCX_HIP(ctx, hipMemcpyAsync(matrix_out_dev, w->al_A, (size_t)B * T * Mmax * 4, hipMemcpyDeviceToDevice, stream));
   CCX_HIP(ctx, hipMemcpyAsync(jump_frame_out, i_jump, (size_t)B * T * 4, hipMemcpyDeviceToHost, stream));
+  std::vector<float> tp_host;
+  if (token_prob_out) {
+    tp_host.resize((size_t)B * T);
+    CCX_HIP(ctx, hipMemcpyAsync(tp_host.data(), tprob, (size_t)B * T * 4, hipMemcpyDeviceToHost, stream));
+  }
   CCX_HIP(ctx, hipStreamSynchronize(stream));
+  if (token_prob_out)
+    for (int b = 0; b < B; b++)
+      for (int i = 0; i < T; i++)     // row row0 + i holds text token i; skipped rows were never written
+        token_prob_out[(size_t)b * T + i] = i < lens[b] - row0 - 2 ? tp_host[(size_t)b * T + row0 + i] : -1.f;
   return CCX_OK;
 }
 

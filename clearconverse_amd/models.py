@@ -61,7 +61,8 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
                 sep_tokens: int = 160_000, max_crops: int = 256, state_dicts: Optional[Dict[str, object]] = None,
                 seg_max_crops: Optional[int] = None, seg_max_seconds: float = 1200.0, emb_max_crops: Optional[int] = None,
                 resnet_max_chunks: int = 96, whisper_instances: int = 1, share_encoder_scratch: bool = True,
-                gate_max_clips: int = 32, gate_max_seconds: float = 30.0, word_alignment: bool = False) -> Dict[str, object]:
+                gate_max_clips: int = 32, gate_max_seconds: float = 30.0, word_alignment: bool = False,
+                word_probabilities: bool = False) -> Dict[str, object]:
     if not torch.cuda.is_available():
         raise _lib.CcxError("load_models needs a ROCm GPU: the HIP path has no CPU fallback")
     dev_index = device.index if isinstance(device, torch.device) and device.index is not None else (device if isinstance(device, int) else 0)
@@ -80,12 +81,15 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
     # The further instances take the first one's log-mel / encoder workspaces (share_encoder_scratch; 32 GB at 768 windows): those
     # are only live inside log_mel / encode, and the pipelined driver orders every instance's log_mel / encode on one stream.
     # word_alignment (default off): transcribe(word_timestamps=True) then aligns words on the GPU (WhisperModel.__init__)
+    # word_probabilities (default off, needs word_alignment): the words carry `probability` and transcribe() honours
+    # hallucination_silence_threshold; handed on only when set
+    wp = {"word_probabilities": True} if word_probabilities else {}
     whispers = [WhisperModel(wd, wsd, max_batch=whisper_batch, device=dev_index, ctx=ctx, max_audio_seconds=max_audio_seconds,
-                             word_alignment=word_alignment)]
+                             word_alignment=word_alignment, **wp)]
     for _ in range(1, max(1, int(whisper_instances))):
         whispers.append(WhisperModel(wd, wsd, max_batch=whisper_batch, device=dev_index, ctx=ctx, max_audio_seconds=max_audio_seconds,
                                      share_encoder_scratch_with=whispers[0] if share_encoder_scratch else None,
-                                     word_alignment=word_alignment))
+                                     word_alignment=word_alignment, **wp))
     whisper = whispers[0]
     separator = SepformerSeparator(sd_, W["sepformer"], max_tokens=sep_tokens, max_utts=64,
                                    device=dev_index, ctx=ctx)

@@ -10,6 +10,7 @@ module holds only the window/segment bookkeeping of openai-whisper's transcribe.
 from __future__ import annotations
 
 import ctypes as C
+import string
 from dataclasses import asdict
 from typing import Dict, List, Optional, Sequence
 
@@ -53,6 +54,34 @@ def groups_by_cap(active: Sequence[int], caps: Sequence[int], max_batch: int) ->
     return out
 
 
+def word_anomaly_score(word: dict) -> float:
+    """[UPSTREAM-RECALL: transcribe.py::word_anomaly_score] how unlikely a word is to be speech: improbable, very short or very long"""
+    probability = word.get("probability", 0.0)
+    duration = word["end"] - word["start"]
+    score = 0.0
+    if probability < 0.15:
+        score += 1.0
+    if duration < 0.133:
+        score += (0.133 - duration) * 15
+    if duration > 2.0:
+        score += duration - 2.0
+    return score
+
+
+def is_segment_anomaly(segment: Optional[dict]) -> bool:
+    """[UPSTREAM-RECALL: transcribe.py::is_segment_anomaly] over the first 8 words that are not punctuation marks"""
+    if segment is None or not segment.get("words"):
+        return False
+    words = [w for w in segment["words"] if w["word"] not in string.punctuation][:8]
+    score = sum(word_anomaly_score(w) for w in words)
+    return score >= 3 or score + 0.01 >= len(words)
+
+
+def next_words_segment(segments: Sequence[dict]) -> Optional[dict]:
+    """[UPSTREAM-RECALL: transcribe.py::next_words_segment]"""
+    return next((s for s in segments if s.get("words")), None)
+
+
 class WindowLoop:
     """Host half of openai-whisper's `transcribe()` for ONE clip [UPSTREAM-RECALL: whisper/transcribe.py, main loop]: which 30 s window
     is decoded next and with which prompt, and what a decoded window adds to the segments / tokens / `text` -- the only key the
@@ -65,7 +94,9 @@ class WindowLoop:
     timestamp token.  That rule is OPT-IN here: `advance(..., last_word_end=)` applies it (a `WhisperModel(word_alignment=True)` passes
     the end of the last word its DTW aligned, csrc/align.hip); without the argument -- the default, its words are never read by the
     reference -- `seek` keeps the timestamp-token rule; only audio that needs more than one window (longer than 30 s, or a window
-    that ends inside an unfinished segment) can see the difference."""
+    that ends inside an unfinished segment) can see the difference.  `advance(..., hallucination_silence_threshold=)` adds upstream's
+    skipping of silence around probable hallucinations on top of it; it reads the words' `probability`, so a
+    `WhisperModel(word_probabilities=True)` is what passes it."""
 
     def __init__(self, rules: DecodeRules, tokenizer, content_frames: int, initial_prompt: Optional[str], n_text_ctx: int,
                  condition_on_previous_text: bool = True, no_speech_threshold: Optional[float] = 0.6,
@@ -168,12 +199,17 @@ class WindowLoop:
         return new_segments, single_ts_ending, next_seek
 
     def advance(self, r: dict, temperature: float = 0.0, last_word_end: Optional[float] = None,
-                segments: Optional[List[dict]] = None) -> None:
+                segments: Optional[List[dict]] = None, hallucination_silence_threshold: Optional[float] = None) -> None:
         """One decoded window (r: tokens before eot, avg_logprob, no_speech_prob) -> segments, tokens, the next seek.
         last_word_end (word alignment, opt-in): end of the last aligned word of this window in seconds -- when the window did not
         end on a single timestamp and it lies behind the window's start, `seek` goes there [UPSTREAM-RECALL: transcribe.py, "if not
         single_timestamp_ending: last_word_end = get_end(current_segments) ..."].  segments: this window's `window_segments()` after
-        add_word_timestamps worked on them (words attached, bounds moved); None: they are built here."""
+        add_word_timestamps worked on them (words attached, bounds moved); None: they are built here.
+        hallucination_silence_threshold (seconds; None: nothing below runs) [UPSTREAM-RECALL: transcribe.py, "skip silence before
+        possible hallucinations"; parity unpinned]: a window whose words end more than the threshold before its end resumes at the
+        last word, else at the window's end; a window whose first segment with words is anomalous (is_segment_anomaly) behind a
+        leading gap longer than the threshold is dropped whole and `seek` moves over the gap; an anomalous segment with silence (or
+        more anomalies) on both sides cuts the window there."""
         seek = self.seek
         self.seeks.append(seek)
         segment_size = min(N_FRAMES, self.content - seek)
@@ -184,10 +220,49 @@ class WindowLoop:
         new_segments, single_ts_ending, self.seek = built
         if segments is not None:
             new_segments = segments
+        last_speech_before = self.last_speech_timestamp      # the previous window's: what the silence rule measures from
         if last_word_end is not None:
             if not single_ts_ending and last_word_end > seek * HOP / SAMPLE_RATE:
                 self.seek = round(last_word_end * FRAMES_PER_SECOND)
             self.last_speech_timestamp = last_word_end
+        if hallucination_silence_threshold is not None:
+            thr = hallucination_silence_threshold
+            time_offset = seek * HOP / SAMPLE_RATE
+            window_end_time = (seek + segment_size) / FRAMES_PER_SECOND
+            if last_word_end is not None and not single_ts_ending and last_word_end > time_offset:
+                if window_end_time - last_word_end > thr:
+                    self.seek = round(last_word_end * FRAMES_PER_SECOND)
+                else:
+                    self.seek = seek + segment_size
+            # "if first segment might be a hallucination, skip leading silence": upstream's `continue` -- nothing of the window is kept
+            first = next_words_segment(new_segments)
+            if first is not None and is_segment_anomaly(first):
+                gap = first["start"] - time_offset
+                if gap > thr:
+                    self.seek = seek + round(gap * FRAMES_PER_SECOND)
+                    self.last_speech_timestamp = last_speech_before
+                    if self.seek <= seek:
+                        self.seek = seek + segment_size
+                    return
+            # "skip silence before any possible hallucination that is surrounded by silence or more hallucinations"
+            hal_last_end = last_speech_before
+            for si, sg in enumerate(new_segments):
+                if not sg.get("words"):
+                    continue
+                if is_segment_anomaly(sg):
+                    nxt = next_words_segment(new_segments[si + 1:])
+                    hal_next_start = nxt["words"][0]["start"] if nxt is not None else time_offset + segment_size * HOP / SAMPLE_RATE
+                    silence_before = sg["start"] - hal_last_end > thr or sg["start"] < thr or sg["start"] - time_offset < 2.0
+                    silence_after = hal_next_start - sg["end"] > thr or is_segment_anomaly(nxt) or window_end_time - sg["end"] < 2.0
+                    if silence_before and silence_after:
+                        self.seek = round(max(time_offset + 1, sg["start"]) * FRAMES_PER_SECOND)
+                        if self.content / FRAMES_PER_SECOND - sg["end"] < thr:
+                            self.seek = self.content
+                        new_segments = new_segments[:si]
+                        break
+                hal_last_end = sg["end"]
+            end = get_end(new_segments)
+            self.last_speech_timestamp = end if end is not None else last_speech_before
         for s in new_segments:
             # "if a segment is instantaneous or does not contain text, clear it": its tokens do not reach the prompt or the text
             if s["start"] == s["end"] or s["text"].strip() == "":
@@ -209,7 +284,7 @@ class WhisperModel:
                  device: int = 0, rules: Optional[DecodeRules] = None, tokenizer=None,
                  ctx: Optional[_lib.Context] = None, max_audio_seconds: float = 30.0,
                  share_encoder_scratch_with: Optional["WhisperModel"] = None, word_alignment: bool = False,
-                 alignment_heads: Optional[Sequence[Sequence[int]]] = None):
+                 alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False):
         """word_alignment (default False: nothing below runs, `transcribe(word_timestamps=True)` has no effect, as before): with it,
         `transcribe(word_timestamps=True)` aligns the words of every window by cross-attention DTW on the GPU (`align`), attaches
         `words` to the segments and moves `seek` by upstream's last-word rule (WindowLoop.advance).
@@ -217,7 +292,12 @@ class WhisperModel:
         layers -- upstream's fallback for a model without a head table [UPSTREAM-RECALL: model.py, `all_heads[n_text_layer // 2:] =
         True`].  A group of windows is aligned as one batch (windows without text go in as [sot, no_timestamps, eot]), so
         max_batch must not exceed the sequences the cross-attention K / V caches hold (80 on the instances that read the encoder
-        output directly): a larger group fails in `transcribe` with the library's message.  small.en's published table (`_ALIGNMENT_HEADS`) is not on disk and is not restated here; pass its pairs to use it."""
+        output directly): a larger group fails in `transcribe` with the library's message.  small.en's published table (`_ALIGNMENT_HEADS`) is not on disk and is not restated here; pass its pairs to use it.
+        word_probabilities (default False; needs word_alignment): every word also carries `probability`, the mean of its tokens'
+        softmax probabilities over the text ids [UPSTREAM-RECALL: timing.py::find_alignment] -- one more small kernel per step of
+        the alignment pass -- and `transcribe(hallucination_silence_threshold=)` is honoured, which is built on them."""
+        if word_probabilities and not word_alignment:
+            raise _lib.CcxError("word_probabilities=True needs word_alignment=True: the probabilities come out of the alignment pass")
         if not torch.cuda.is_available():
             raise _lib.CcxError("WhisperModel needs a ROCm GPU: the HIP path has no CPU fallback")
         self.dims = dims
@@ -236,6 +316,7 @@ class WhisperModel:
         self.sample_seed, self._sample_calls = 0, 0     # temperature > 0: Philox seed and per-call counter
         self.last_cross_path = None
         self.word_alignment = bool(word_alignment)
+        self.word_probabilities = bool(word_probabilities)
         if alignment_heads is None:
             alignment_heads = [(l, h) for l in range(dims.n_text_layer // 2, dims.n_text_layer) for h in range(dims.n_text_head)]
         self.alignment_heads = [(int(l), int(h)) for l, h in alignment_heads]
@@ -388,12 +469,14 @@ class WhisperModel:
                      cross_path=self.last_cross_path) for b in range(B)]
 
     def align(self, tokens_per_seq: Sequence[Sequence[int]], n_frames: Sequence[int], return_probs: bool = False,
-              return_matrix: bool = False, row0: int = 1):
+              return_matrix: bool = False, row0: int = 1, token_probs: bool = False):
         """Word alignment of the currently encoded windows (ccx_whisper_align; valid after `encode` or a decode of the same
         windows): a teacher-forced pass over tokens_per_seq[b] (alignment_tokens: [sot, no_timestamps, *text, eot]), the alignment
         matrix of `alignment_heads` over the first n_frames[b] // 2 encoder positions, and the DTW over rows row0 .. -1.
         Returns (jump_frames, P, A): jump_frames[b] = int array, the encoder position at which each of those rows starts; P
-        [B, heads, T, n_audio_ctx] / A [B, T, n_audio_ctx] device tensors when asked for, else None."""
+        [B, heads, T, n_audio_ctx] / A [B, T, n_audio_ctx] device tensors when asked for, else None.
+        token_probs: (jump_frames, P, A, probs) instead -- probs[b] = float32 array, one entry per text token: its softmax
+        probability over the ids [0, eot) at the row that predicts it (ccx_whisper_align_probs; timing.py::find_alignment)."""
         B = len(tokens_per_seq)
         T = max(len(t) for t in tokens_per_seq)
         toks = np.full((B, T), self.rules.eot, dtype=np.int32)
@@ -409,33 +492,52 @@ class WhisperModel:
         A = torch.empty(B, T, self.dims.n_audio_ctx, device=self.device, dtype=torch.float32) if return_matrix else None
         jump = np.full((B, T), -1, dtype=np.int32)
         i32p = C.POINTER(C.c_int32)
-        self.ctx.check(self.lib.ccx_whisper_align(
-            self.handle, toks.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), T, B, nf.ctypes.data_as(i32p),
-            heads.ctypes.data_as(i32p), len(heads), int(row0), _lib.ptr(P), _lib.ptr(A), jump.ctypes.data_as(i32p),
-            _lib.current_stream_ptr()), "ccx_whisper_align")
-        return [jump[b, :max(int(lens[b]) - 1 - int(row0), 0)].copy() for b in range(B)], P, A
+        if token_probs:
+            tp = np.full((B, T), -1.0, dtype=np.float32)
+            self.ctx.check(self.lib.ccx_whisper_align_probs(
+                self.handle, toks.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), T, B, nf.ctypes.data_as(i32p),
+                heads.ctypes.data_as(i32p), len(heads), int(row0), _lib.ptr(P), _lib.ptr(A), jump.ctypes.data_as(i32p),
+                int(self.rules.eot), tp.ctypes.data_as(C.POINTER(C.c_float)), _lib.current_stream_ptr()), "ccx_whisper_align_probs")
+        else:
+            self.ctx.check(self.lib.ccx_whisper_align(
+                self.handle, toks.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), T, B, nf.ctypes.data_as(i32p),
+                heads.ctypes.data_as(i32p), len(heads), int(row0), _lib.ptr(P), _lib.ptr(A), jump.ctypes.data_as(i32p),
+                _lib.current_stream_ptr()), "ccx_whisper_align")
+        jumps = [jump[b, :max(int(lens[b]) - 1 - int(row0), 0)].copy() for b in range(B)]
+        if token_probs:
+            return jumps, P, A, [tp[b, :max(int(lens[b]) - 2 - int(row0), 0)].copy() for b in range(B)]
+        return jumps, P, A
 
-    def _advance_with_words(self, grp, results, state, temperature: float):
+    def _advance_with_words(self, grp, results, state, temperature: float, hallucination_silence_threshold: Optional[float] = None):
         """word_alignment and word_timestamps: align every window of the group that produced text while the windows are still
-        encoded, attach the words, and advance each clip with the end of its last word [UPSTREAM-RECALL: transcribe.py]."""
+        encoded, attach the words, and advance each clip with the end of its last word [UPSTREAM-RECALL: transcribe.py].  On an
+        instance with word_probabilities the same pass gives the token probabilities, the words carry `probability` and the
+        threshold reaches `advance`."""
         built = [state[i].window_segments(r) for i, r in zip(grp, results)]
         texts = []
         for bt in built:
             texts.append([t for s in bt[0] for t in s["tokens"] if t < self.rules.eot] if bt is not None else [])
-        jumps = None
+        jumps, probs = None, None
         if any(texts):
             frames = [max(2, min(N_FRAMES, state[i].content - state[i].seek)) for i in grp]
             # one teacher-forced batch: every window with its own SOT sequence (all of one length: the DTW starts behind it)
             seqs = [state[i].sot_sequence for i in grp]
             assert all(len(sq) == len(seqs[0]) for sq in seqs), "one model, one SOT-sequence length: the DTW's row0 is per call"
-            jumps, _, _ = self.align([alignment_tokens(t, self.rules, sq) for t, sq in zip(texts, seqs)], frames, row0=len(seqs[0]))
+            got = self.align([alignment_tokens(t, self.rules, sq) for t, sq in zip(texts, seqs)], frames, row0=len(seqs[0]),
+                             token_probs=self.word_probabilities)
+            jumps, probs = got[0], (got[3] if self.word_probabilities else None)
         for b, (i, r) in enumerate(zip(grp, results)):
             segs, end = None, None
             if built[b] is not None:
                 segs = built[b][0]
-                add_word_timestamps(segs, self.tokenizer, self.rules, lambda toks, b=b: jumps[b], state[i].last_speech_timestamp)
+                add_word_timestamps(segs, self.tokenizer, self.rules, lambda toks, b=b: jumps[b], state[i].last_speech_timestamp,
+                                    prob_fn=(lambda toks, b=b: probs[b]) if self.word_probabilities else None)
                 end = get_end(segs)
-            state[i].advance(r, temperature, last_word_end=end, segments=segs)
+            if self.word_probabilities and hallucination_silence_threshold is not None:
+                state[i].advance(r, temperature, last_word_end=end, segments=segs,
+                                 hallucination_silence_threshold=hallucination_silence_threshold)
+            else:
+                state[i].advance(r, temperature, last_word_end=end, segments=segs)
 
     # ------------------------------------------------------------------ transcribe (reference call surface)
     def initial_tokens(self, prompt_tokens: Sequence[int], sot_sequence: Optional[Sequence[int]] = None) -> List[int]:
@@ -449,7 +551,8 @@ class WhisperModel:
     def transcribe(self, audio, initial_prompt: Optional[str] = None, word_timestamps: bool = False,
                    condition_on_previous_text: bool = True, temperature: float = 0.0,
                    no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0,
-                   language: Optional[str] = None, task: str = "transcribe", **_ignored):
+                   language: Optional[str] = None, task: str = "transcribe",
+                   hallucination_silence_threshold: Optional[float] = None, **_ignored):
         """One clip, same signature as whisper.transcribe as the reference uses it.  temperature 0 is the
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
@@ -458,21 +561,26 @@ class WhisperModel:
         `word_alignment=True` (segments get `words`, `seek` follows the last aligned word); otherwise it has no effect.
         language / task: on a multilingual model the SOT sequence is [sot, <|language|>, <|task|>]; language None (upstream's
         default, what the reference's calls leave it at) detects it on the first window.  An English-only model reports "en" and
-        ignores both, as upstream's transcribe does."""
+        ignores both, as upstream's transcribe does.
+        hallucination_silence_threshold (seconds): with word_timestamps on an instance built with `word_probabilities=True`, silence
+        longer than this around a probable hallucination is skipped (WindowLoop.advance); otherwise no effect -- upstream ignores
+        it without word_timestamps too."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
                                      temperature=temperature, no_speech_threshold=no_speech_threshold,
                                      logprob_threshold=logprob_threshold, word_timestamps=word_timestamps,
-                                     languages=[language], task=task)[0]
+                                     languages=[language], task=task,
+                                     hallucination_silence_threshold=hallucination_silence_threshold)[0]
 
     def transcribe_batch(self, audios: Sequence, initial_prompts: Optional[Sequence[Optional[str]]] = None,
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
                          no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0,
                          word_timestamps: bool = False, languages: Optional[Sequence[Optional[str]]] = None,
-                         task: str = "transcribe") -> List[dict]:
+                         task: str = "transcribe", hallucination_silence_threshold: Optional[float] = None) -> List[dict]:
         """Independent clips decoded together (each window of each clip is one sequence of a batch).
         languages[i] (multilingual models): the clip's language code or name; None: detected on the clip's first window, after its
         group's `encode` and before its `decode` [UPSTREAM-RECALL: transcribe.py, `if decode_options.get("language") is None`].
-        A pass over the active clips is split into groups of one sample cap (decode_cap) of at most max_batch windows."""
+        A pass over the active clips is split into groups of one sample cap (decode_cap) of at most max_batch windows.
+        hallucination_silence_threshold: as in `transcribe`, for every clip."""
         with_words = bool(word_timestamps) and self.word_alignment
         if isinstance(temperature, (tuple, list)):
             raise _lib.CcxError("temperature fallback schedules are not implemented: pass one temperature (the reference does)")
@@ -534,7 +642,7 @@ class WhisperModel:
                 results = self.decode(prompts, sample_len=cap, temperature=temperature,
                                       seed=(int(self.sample_seed) << 32) + self._sample_calls)
                 if with_words:     # before the next log_mel: the group's windows are still encoded
-                    self._advance_with_words(grp, results, state, temperature)
+                    self._advance_with_words(grp, results, state, temperature, hallucination_silence_threshold)
                     continue
                 for i, r in zip(grp, results):
                     state[i].advance(r, temperature)

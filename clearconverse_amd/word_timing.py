@@ -4,8 +4,10 @@ here it is OPT-IN (`WhisperModel(word_alignment=True)`).  The device half -- the
 DTW -- is `WhisperModel.align` (csrc/align.hip); this module only turns its jump frames into words.
 
 Every rule below is restated from recollection [UPSTREAM-RECALL: whisper/timing.py, tokenizer.py]; **parity unpinned**: the
-reference holds no fixture for it and the tests do not import openai-whisper.  Not restated: `probability` of a word (the reference never reads
-it; the words carry no such key), the unicode-only split of the languages without spaces (the models here are English-only).
+reference holds no fixture for it and the tests do not import openai-whisper.  A word's `probability` (the mean of its tokens'
+softmax probabilities over the text ids, timing.py::find_alignment) is OPT-IN on top (`WhisperModel(word_probabilities=True)`; the
+reference never reads it): without it the words carry no such key.  Not restated: the unicode-only split of the languages without
+spaces.
 """
 from __future__ import annotations
 
@@ -28,6 +30,7 @@ class WordTiming:
     tokens: List[int] = field(default_factory=list)
     start: float = 0.0
     end: float = 0.0
+    probability: Optional[float] = None     # only with token probabilities (find_alignment(token_probs=))
 
 
 def split_tokens_on_unicode(tokenizer, tokens: Sequence[int]) -> Tuple[List[str], List[List[int]]]:
@@ -67,7 +70,8 @@ def split_to_word_tokens(tokenizer, tokens: Sequence[int], eot: int) -> Tuple[Li
 
 
 def merge_punctuations(alignment: List[WordTiming], prepended: str = PREPEND_PUNCTUATIONS, appended: str = APPEND_PUNCTUATIONS) -> None:
-    """[UPSTREAM-RECALL: timing.py::merge_punctuations] in place; a merged-away entry keeps word '' and no tokens."""
+    """[UPSTREAM-RECALL: timing.py::merge_punctuations] in place; a merged-away entry keeps word '' and no tokens.  Word and tokens
+    only: the surviving entry keeps its own probability, as upstream's does."""
     i, j = len(alignment) - 2, len(alignment) - 1
     while i >= 0:
         previous, following = alignment[i], alignment[j]
@@ -98,10 +102,13 @@ def alignment_tokens(text_tokens: Sequence[int], rules, sot_sequence: Optional[S
     return [*sot_sequence, rules.no_timestamps, *[int(t) for t in text_tokens], rules.eot]
 
 
-def find_alignment(tokenizer, rules, text_tokens: Sequence[int], jump_frame: Sequence[int]) -> List[WordTiming]:
+def find_alignment(tokenizer, rules, text_tokens: Sequence[int], jump_frame: Sequence[int],
+                   token_probs: Optional[Sequence[float]] = None) -> List[WordTiming]:
     """[UPSTREAM-RECALL: find_alignment], the host half.  jump_frame: the DTW's jump frames of rows 1 .. -1 of alignment_tokens
     (len(text_tokens) + 1 entries: the encoder position at which each row starts).  Word boundaries are cumulative word-token
-    counts; start / end are jump_frame / 50 seconds from the window's start."""
+    counts; start / end are jump_frame / 50 seconds from the window's start.  token_probs (len(text_tokens) entries,
+    WhisperModel.align(token_probs=True)): every word's `probability` is the mean of its tokens' over the same boundaries
+    [`np.mean(text_token_probs[i:j]) for i, j in zip(word_boundaries[:-1], word_boundaries[1:])`]."""
     if len(text_tokens) == 0:
         return []
     words, word_tokens = split_to_word_tokens(tokenizer, list(text_tokens) + [rules.eot], rules.eot)
@@ -110,20 +117,32 @@ def find_alignment(tokenizer, rules, text_tokens: Sequence[int], jump_frame: Seq
     boundaries = np.pad(np.cumsum([len(t) for t in word_tokens[:-1]]), (1, 0))
     jump_times = np.asarray(jump_frame, dtype=np.float64)[: len(text_tokens) + 1] / TOKENS_PER_SECOND
     starts, ends = jump_times[boundaries[:-1]], jump_times[boundaries[1:]]
-    return [WordTiming(w, list(t), float(s), float(e)) for w, t, s, e in zip(words, word_tokens, starts, ends)]
+    timings = [WordTiming(w, list(t), float(s), float(e)) for w, t, s, e in zip(words, word_tokens, starts, ends)]
+    if token_probs is not None:
+        tp = np.asarray(token_probs, dtype=np.float64)
+        if tp.shape != (len(text_tokens),):
+            raise ValueError(f"find_alignment: {tp.shape} token probabilities for {len(text_tokens)} text tokens")
+        for timing, i, j in zip(timings, boundaries[:-1], boundaries[1:]):
+            timing.probability = float(np.mean(tp[i:j]))
+    return timings
 
 
 def add_word_timestamps(segments: List[dict], tokenizer, rules, align_fn: Callable[[List[int]], Sequence[int]],
                         last_speech_timestamp: float = 0.0, prepend_punctuations: str = PREPEND_PUNCTUATIONS,
-                        append_punctuations: str = APPEND_PUNCTUATIONS) -> float:
+                        append_punctuations: str = APPEND_PUNCTUATIONS,
+                        prob_fn: Optional[Callable[[List[int]], Sequence[float]]] = None) -> float:
     """[UPSTREAM-RECALL: timing.py::add_word_timestamps] for the segments of ONE window, in place: `words` on every segment and the
     segment bounds moved to their first / last word.  align_fn(text_tokens) -> jump frames (WhisperModel.align for this window).
-    Returns the new last_speech_timestamp."""
+    prob_fn(text_tokens) -> one probability per text token: every word dict gains `probability`; without it the dicts have no such
+    key.  Returns the new last_speech_timestamp."""
     if len(segments) == 0:
         return last_speech_timestamp
     per_segment = [[t for t in s["tokens"] if t < rules.eot] for s in segments]
     text_tokens = [t for ts in per_segment for t in ts]
-    alignment = find_alignment(tokenizer, rules, text_tokens, align_fn(text_tokens)) if text_tokens else []
+    alignment = []
+    if text_tokens:
+        alignment = find_alignment(tokenizer, rules, text_tokens, align_fn(text_tokens),
+                                   token_probs=prob_fn(text_tokens) if prob_fn is not None else None)
     durations = np.array([t.end - t.start for t in alignment])
     durations = durations[durations.nonzero()]
     median_duration = min(0.7, float(np.median(durations))) if len(durations) > 0 else 0.0
@@ -145,6 +164,8 @@ def add_word_timestamps(segments: List[dict], tokenizer, rules, align_fn: Callab
             timing = alignment[word_index]
             if timing.word:
                 words.append(dict(word=timing.word, start=round(time_offset + timing.start, 2), end=round(time_offset + timing.end, 2)))
+                if prob_fn is not None:
+                    words[-1]["probability"] = timing.probability
             saved += len(timing.tokens)
             word_index += 1
         if len(words) > 0:

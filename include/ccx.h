@@ -293,6 +293,25 @@ typedef struct ccx_dec_token_probs_desc {
 } ccx_dec_token_probs_desc;
 int ccx_dec_token_probs(ccx_ctx* ctx, const ccx_dec_token_probs_desc* desc, void* stream);
 
+/* Probability of ONE picked id per logit row (csrc/dec_probs.hip: dec_pick_probs_kernel, one block per row, the row pass of
+ * dec_token_probs_kernel): out[row * out_stride] = exp(x[pick] - max) / sum_{j < hi} exp(x[j] - max) with pick = picks[row *
+ * pick_stride], over the ids [0, hi) only -- the columns [hi, ld) are never looked at.  fp32, max-subtracted; -inf inside the range
+ * contributes 0.  A row whose pick is -1 is skipped: nothing is loaded and nothing is written for it.  hi need not be a multiple of 4.
+ * The model uses it for the token probabilities behind a word's `probability` (ccx_whisper_align_probs; openai-whisper
+ * timing.py::find_alignment, `logits[len(sot_sequence):, :eot].softmax(dim=-1)[np.arange(len(text_tokens)), text_tokens]`); the
+ * strides let it walk column t of [B][T] tables.  Checked on the host before the launch, CCX_ERR_ARG (1) naming "ccx_dec_pick_probs"
+ * and the field: 1 <= rows <= 65536, 1 <= hi <= 53248, ld >= hi and a multiple of 4, logits 16-byte aligned with logits_elems >=
+ * (rows - 1) * ld + hi rounded up to 4, pick_stride >= 1, out_stride >= 1, picks_elems >= (rows - 1) * pick_stride + 1, out_elems >=
+ * (rows - 1) * out_stride + 1.  The picks are copied to the host once before the launch and every value outside {-1} and [0, hi) is
+ * refused (a test entry: the model path builds its picks on the host and does not go through here).  Synchronises the stream. */
+typedef struct ccx_dec_pick_probs_desc {
+  const void* logits; int64_t logits_elems;  /* device f32 [rows][ld] */
+  int64_t ld; int rows; int hi;
+  const void* picks; int64_t picks_elems; int64_t pick_stride;   /* device int32 */
+  void* out; int64_t out_elems; int64_t out_stride;              /* device f32 */
+} ccx_dec_pick_probs_desc;
+int ccx_dec_pick_probs(ccx_ctx* ctx, const ccx_dec_pick_probs_desc* desc, void* stream);
+
 /* ---- word alignment (csrc/align.hip): what transcribe(word_timestamps=True) of the reference asks for (back/api.py:1435, 1477) --
  * openai-whisper's timing.py::find_alignment [UPSTREAM-RECALL]: cross-attention probabilities of the alignment heads over the first
  * num_frames // 2 encoder positions, standardised over the tokens, median-filtered over the frames, averaged over the heads, and a
@@ -347,6 +366,20 @@ int ccx_align_op(ccx_ctx* ctx, int op, const ccx_align_desc* desc, void* stream)
 int ccx_whisper_align(ccx_whisper* w, const int32_t* tokens, const int32_t* lens, int max_len, int B, const int32_t* n_frames,
                       const int32_t* heads, int n_heads, int row0, float* probs_out_dev, float* matrix_out_dev,
                       int32_t* jump_frame_out, void* stream);
+/* ccx_whisper_align that also returns the probability of every text token -- what upstream's find_alignment turns into a word's
+ * `probability` (timing.py::find_alignment, `token_probs = logits[len(tokenizer.sot_sequence):, :tokenizer.eot].softmax(dim=-1)`,
+ * `text_token_probs = token_probs[np.arange(len(text_tokens)), text_tokens]`).  The pass already writes every step's logits; with
+ * token_prob_out != NULL one dec_pick_probs_kernel launch per step reads them: row t of sequence b (row0 <= t <= lens[b] - 3; row
+ * row0 holds <|notimestamps|> and predicts the first text token, the last text token's row predicts eot and is not used) gives the
+ * softmax probability over the ids [0, prob_hi) of tokens[b][t + 1].  Needs 1 <= prob_hi <= n_vocab (upstream: eot) and every such
+ * token below prob_hi.  The pick table and the [B][max_len] output live in the alignment workspace (uploaded / cleared once per call,
+ * nothing per step).
+ *   token_prob_out  host [B][max_len]: entry i < lens[b] - row0 - 2 = probability of text token i, -1 behind
+ * P, A and the jump frames are the bits of a call without probabilities.  With token_prob_out == NULL this IS ccx_whisper_align:
+ * nothing more is allocated or launched and prob_hi is ignored. */
+int ccx_whisper_align_probs(ccx_whisper* w, const int32_t* tokens, const int32_t* lens, int max_len, int B, const int32_t* n_frames,
+                            const int32_t* heads, int n_heads, int row0, float* probs_out_dev, float* matrix_out_dev,
+                            int32_t* jump_frame_out, int prob_hi, float* token_prob_out, void* stream);
 
 /* Which cross-attention formulation the last ccx_whisper_decode (or ccx_whisper_detect_language) of this instance ran (measurement / test records; the reference has one
  * formulation, MultiHeadAttention.forward(x, xa) behind back/api.py:1286-1292): 0 = "kv16" (per-layer K / V caches, split-KV kernels,
