@@ -95,13 +95,17 @@ __device__ __forceinline__ uint4 combine_partials(const float* part_o, const flo
 // LayerNorm prologue folds them in (x_eff = x_in + sum partials), block (0,*,0) writing x_eff to
 // the other residual buffer (ping-pong: no block may see a half-updated stream).
 // NW = 4 waves per block split K (kept as a template argument: kernel symbols and profile labels carry it).
+// The depth-10 LayerNorm form (K = 1280) asks for two waves per SIMD: left alone the compiler hoists its prologue loads into 254 + 12
+// registers (one block per CU, where the depth-8 form has two); held to 256 it takes 206 .. 209, no scratch.
 template <int MT, int NT, int KMAX, int ACT, int EPI, int NW = 4>
-__global__ __launch_bounds__(64 * NW) void dec_linear_kernel(DecLinearParams p) {
+__global__ __launch_bounds__(64 * NW, (KMAX > 8 && ACT == ACT_LN) ? 2 : 1) void dec_linear_kernel(DecLinearParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int MROWS = 16 * MT;
   constexpr int BN = 16 * NT;
   constexpr int NTHR = 64 * NW;
   constexpr bool BF16IN = (ACT == ACT_BF16);
+  constexpr int LNS = KMAX > 8 ? 5 : 4;  // float4 slots per lane of the LayerNorm prologue (32 KMAX columns per wave x 4 waves / 256)
+  constexpr int LNR = KMAX > 8 ? 1 : 2;  // ... and rows a wave normalises per pass
   static_assert(NW == 4, "the LayerNorm / combine prologues and the launcher are written for four waves");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n0 = blockIdx.x * BN;
@@ -195,31 +199,33 @@ __global__ __launch_bounds__(64 * NW) void dec_linear_kernel(DecLinearParams p) 
 
   // ---------------- 2. activation staging ----------------
   if (ACT == ACT_LN) {
-    // x_eff = x + sum of pending split-K partials; LayerNorm(x_eff) -> bf16 LDS rows (K <= 1024).
-    // A wave owns live rows wave, wave+4, ... and handles two of them per pass.
+    // x_eff = x + sum of pending split-K partials; LayerNorm(x_eff) -> bf16 LDS rows.  A lane keeps LNS float4 of a row:
+    // 4 (K <= 1024) with the prefetch depths 6 and 8, 5 (K <= 1280) with depth 10 -- K is one block's here, so KMAX bounds it.
+    // A wave owns live rows wave, wave+4, ... and handles LNR of them per pass: two, or one in the 5-slot form, whose registers
+    // two rows in flight would not fit beside the depth-10 weight prefetch without scratch or a lower occupancy.
     const int nv = K >> 2;
     int live = p.M - m0;
     live = live > MROWS ? MROWS : live;
     const bool writer = (blockIdx.x == 0 && blockIdx.z == 0 && p.x_out != nullptr);
-    float4 g[4], bb[4];
+    float4 g[LNS], bb[LNS];
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
+    for (int i = 0; i < LNS; i++) {
       const int idx = lane + 64 * i;
       const int ic = idx < nv ? idx : 0;
       g[i] = ((const float4*)p.ln_g)[ic];
       bb[i] = ((const float4*)p.ln_b)[ic];
     }
-    for (int r0 = wave; r0 < live; r0 += 8) {
-      float4 v[2][4];
-      bool ok[2];
+    for (int r0 = wave; r0 < live; r0 += 4 * LNR) {
+      float4 v[LNR][LNS];
+      bool ok[LNR];
 #pragma unroll
-      for (int u = 0; u < 2; u++) {
+      for (int u = 0; u < LNR; u++) {
         const int r = r0 + 4 * u;
         ok[u] = r < live;
         const long row = (long)(m0 + (ok[u] ? r : r0)) * K;
         const float4* xr = (const float4*)(p.x + row);
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
+        for (int i = 0; i < LNS; i++) {
           const int idx = lane + 64 * i;
           const int ic = idx < nv ? idx : 0;
           float4 a = xr[ic];
@@ -233,30 +239,30 @@ __global__ __launch_bounds__(64 * NW) void dec_linear_kernel(DecLinearParams p) 
           v[u][i] = a;
         }
       }
-      float mean[2], rstd[2];
+      float mean[LNR], rstd[LNR];
 #pragma unroll
-      for (int u = 0; u < 2; u++) {
+      for (int u = 0; u < LNR; u++) {
         float sm = 0.f;
 #pragma unroll
-        for (int i = 0; i < 4; i++) sm += ln_sum4(v[u][i]);
+        for (int i = 0; i < LNS; i++) sm += ln_sum4(v[u][i]);
         mean[u] = wave_reduce_sum(sm) / (float)K;
       }
 #pragma unroll
-      for (int u = 0; u < 2; u++) {
+      for (int u = 0; u < LNR; u++) {
         float sq = 0.f;
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
+        for (int i = 0; i < LNS; i++) {
           const float t = ln_sq4(v[u][i], mean[u]);
           sq += (lane + 64 * i < nv) ? t : 0.f;
         }
         rstd[u] = rsqrtf(wave_reduce_sum(sq) / (float)K + p.eps);
       }
 #pragma unroll
-      for (int u = 0; u < 2; u++) {
+      for (int u = 0; u < LNR; u++) {
         if (!ok[u]) continue;
         const int r = r0 + 4 * u;
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
+        for (int i = 0; i < LNS; i++) {
           const int idx = lane + 64 * i;
           if (idx < nv) {
             *(uint2*)(act_s + (long)r * lds_ld + 4 * idx) = ln_pack4(v[u][i], mean[u], rstd[u], g[i], bb[i]);
@@ -383,6 +389,8 @@ __global__ __launch_bounds__(64 * NW) void dec_linear_kernel(DecLinearParams p) 
 }
 
 // Stand-alone residual resolve + LayerNorm -> bf16 (input of the logits GEMV): one wave per row.
+// NS = float4 slots per lane: 4 for K <= 1024, 5 for K <= 1280 (unrolled over the compile-time NS: the 4-slot form is unchanged).
+template <int NS>
 __global__ __launch_bounds__(256) void dec_resolve_ln_kernel(const float* __restrict__ x, const float* __restrict__ pend,
                                                              int pend_n, long pend_stride, const float* __restrict__ g,
                                                              const float* __restrict__ b, bf16_t* __restrict__ out,
@@ -392,9 +400,9 @@ __global__ __launch_bounds__(256) void dec_resolve_ln_kernel(const float* __rest
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= M) return;
   const int nv = K >> 2;
-  float4 v[4], gg[4], bb[4];
+  float4 v[NS], gg[NS], bb[NS];
 #pragma unroll
-  for (int i = 0; i < 4; i++) {   // affine parameters first: no dependent load after the reductions
+  for (int i = 0; i < NS; i++) {   // affine parameters first: no dependent load after the reductions
     const int idx = lane + 64 * i;
     const int ic = idx < nv ? idx : 0;
     gg[i] = ((const float4*)g)[ic];
@@ -402,7 +410,7 @@ __global__ __launch_bounds__(256) void dec_resolve_ln_kernel(const float* __rest
   }
   float sm = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < NS; i++) {
     const int idx = lane + 64 * i;
     const int ic = idx < nv ? idx : 0;
     float4 a = ((const float4*)(x + (long)m * K))[ic];
@@ -419,14 +427,14 @@ __global__ __launch_bounds__(256) void dec_resolve_ln_kernel(const float* __rest
   const float mean = wave_reduce_sum(sm) / (float)K;
   float sq = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < NS; i++) {
     const float t = ln_sq4(v[i], mean);
     sq += (lane + 64 * i < nv) ? t : 0.f;
   }
   const float rstd = rsqrtf(wave_reduce_sum(sq) / (float)K + eps);
   if (mean_out && lane == 0) mean_out[m] = centre_shift(mean, rstd);
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < NS; i++) {
     const int idx = lane + 64 * i;
     if (idx < nv) ((uint2*)(out + (long)m * K))[idx] = ln_pack4(v[i], mean, rstd, gg[i], bb[i]);
   }
@@ -469,12 +477,16 @@ int ccx_launch_dec_combine(ccx_ctx* ctx, const float* part_o, const float* part_
 int ccx_launch_dec_resolve_ln(ccx_ctx* ctx, const float* x, const float* pend, int pend_n, long pend_stride, const float* g,
                               const float* b, bf16_t* out, float* x_out, int M, int K, float eps, hipStream_t stream,
                               float* mean_out) {
-  CCX_REQUIRE(ctx, K % 4 == 0 && K <= 1024, "dec_resolve_ln: K=%d unsupported", K);
+  CCX_REQUIRE(ctx, K % 4 == 0 && K <= 1280, "dec_resolve_ln: K=%d unsupported (a multiple of 4, at most 1280)", K);
   CCX_REQUIRE(ctx, x_out != x, "dec_resolve_ln: x_out must not alias x");
   // bytes: the residual rows and their pending slabs in, the bf16 rows (and the resolved fp32 rows) out
   ccx_prof_scope ps(ctx, stream, "dec_resolve_ln_kernel", 0.0, (double)M * K * (4.0 * (1 + pend_n) + 2.0 + (x_out ? 4.0 : 0.0)));
-  hipLaunchKernelGGL(dec_resolve_ln_kernel, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, pend, pend_n, pend_stride, g, b,
-                     out, x_out, M, K, eps, mean_out);
+  if (K <= 1024)
+    hipLaunchKernelGGL(dec_resolve_ln_kernel<4>, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, pend, pend_n, pend_stride, g, b,
+                       out, x_out, M, K, eps, mean_out);
+  else
+    hipLaunchKernelGGL(dec_resolve_ln_kernel<5>, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, pend, pend_n, pend_stride, g, b,
+                       out, x_out, M, K, eps, mean_out);
   CCX_CHECK_LAUNCH(ctx);
   return CCX_OK;
 }
@@ -515,25 +527,35 @@ static int launch_dec_linear_mt(ccx_ctx* ctx, const DecLinearParams& p, int kspl
     if (M <= 32) return launch_dec_linear_inst<2, NT, 6, ACT, EPI>(ctx, p, ksplit, stream);
     return launch_dec_linear_inst<4, NT, 6, ACT, EPI>(ctx, p, ksplit, stream);
   }
-  if (M <= 16) return launch_dec_linear_inst<1, NT, 8, ACT, EPI>(ctx, p, ksplit, stream);
-  if (M <= 32) return launch_dec_linear_inst<2, NT, 8, ACT, EPI>(ctx, p, ksplit, stream);
-  return launch_dec_linear_inst<4, NT, 8, ACT, EPI>(ctx, p, ksplit, stream);
+  if (need <= 8) {
+    if (M <= 16) return launch_dec_linear_inst<1, NT, 8, ACT, EPI>(ctx, p, ksplit, stream);
+    if (M <= 32) return launch_dec_linear_inst<2, NT, 8, ACT, EPI>(ctx, p, ksplit, stream);
+    return launch_dec_linear_inst<4, NT, 8, ACT, EPI>(ctx, p, ksplit, stream);
+  }
+  // depth 10: K = 1280 in one block (40 k-steps over 4 waves) and the 1280-wide slabs of K = 5120
+  if (M <= 16) return launch_dec_linear_inst<1, NT, 10, ACT, EPI>(ctx, p, ksplit, stream);
+  if (M <= 32) return launch_dec_linear_inst<2, NT, 10, ACT, EPI>(ctx, p, ksplit, stream);
+  return launch_dec_linear_inst<4, NT, 10, ACT, EPI>(ctx, p, ksplit, stream);
 }
 
 int ccx_dec_linear_ksplit(int K, int epi) {
-  // prefetch depth is 8 k-steps (256 elements) per wave, 4 waves per block
+  // prefetch depth is 8 k-steps (256 elements) per wave, 4 waves per block -- or 10 (320 elements), taken only where 8 cannot serve:
+  // a non-partial epilogue at 1024 < K <= 1280, and partial outputs whose 1024-wide slabs would outnumber the 4 pending slabs the
+  // LayerNorm prologues fold in (K = 5120: 4 slabs of 1280 instead of 5 of 1024).  Everything up to K = 4096 splits as before.
   if (epi == DEPI_RESOLVE) return 1;   // the residual is added in place: one block owns all of K
   int ks = ccx_cdiv(K, 1024);
-  if (epi != DEPI_PARTIAL) return ks;  // only partial outputs can be split across blocks
+  if (epi != DEPI_PARTIAL) return K <= 1280 ? 1 : ks;  // only partial outputs can be split across blocks
+  if (ks > 4) ks = ccx_cdiv(K, 1280);
   return ks < 1 ? 1 : ks;
 }
 
 int ccx_launch_dec_linear(ccx_ctx* ctx, int act, int epi, const DecLinearParams& p, hipStream_t stream) {
   CCX_REQUIRE(ctx, p.M > 0 && p.N > 0 && p.K > 0 && p.K % 32 == 0, "dec_linear: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
-  CCX_REQUIRE(ctx, act == ACT_BF16 || p.K <= 1024, "dec_linear: LN/combine activation needs K <= 1024");
+  CCX_REQUIRE(ctx, act == ACT_BF16 || p.K <= 1280, "dec_linear: LN/combine activation needs K <= 1280");
   CCX_REQUIRE(ctx, p.pend_n >= 0 && p.pend_n <= 4, "dec_linear: at most 4 pending slabs");
   const int ksplit = ccx_dec_linear_ksplit(p.K, epi);
   CCX_REQUIRE(ctx, epi == DEPI_PARTIAL || ksplit == 1, "dec_linear: K=%d needs a split-K (partial) epilogue", p.K);
+  CCX_REQUIRE(ctx, ksplit <= 4, "dec_linear: K=%d would leave %d partial slabs (at most 4)", p.K, ksplit);
   CCX_REQUIRE(ctx, epi != DEPI_PARTIAL || p.pend_stride >= (long)p.M * p.ldo, "dec_linear: pend_stride too small");
   // Lanes of 128 rows and more (the decode groups of the pipelined schedule): a block of 16 output columns re-reads all of its 64
   // activation rows for 24 KB of weights, so the launch is bound by activation reads out of L2 (85 MB for the 1.2 MB QKV matrix

@@ -4,45 +4,61 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
+// NS = float4 slots a lane keeps in registers: 4 serve D <= 1024, 5 serve 1024 < D <= 1280 (the fifth slot is ragged: D / 4 - 256
+// lanes are live in it).  The loops are fully unrolled over the compile-time NS and the arithmetic type of the 4-slot form is float,
+// so that instantiation is the code it was.  The 5-slot form (Whisper's large family) does its statistics and the affine map in
+// double and rounds once: a float mean carries ~ulp(|mean|), which every output of the row inherits divided by the row's std -- 4e-6
+// for a residual row offset by 35 std -- and the kernel is HBM-bound either way.
+__device__ __forceinline__ double wave_reduce_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ float ln_rsqrt(float v) { return rsqrtf(v); }
+__device__ __forceinline__ double ln_rsqrt(double v) { return 1.0 / sqrt(v); }
+
+template <int NS>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, long ldx,
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, bf16_t* __restrict__ ob,
                                                         float* __restrict__ of, long ldo, int M, int D, float eps) {
+  using acc_t = typename std::conditional<(NS > 4), double, float>::type;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   const float4* xr = (const float4*)(x + (long)row * ldx);
   const int nv = D >> 2;  // D % 4 == 0
-  // D <= 1024 -> at most 4 float4 per lane kept in registers
-  float4 v[4];
-  float s = 0.f;
+  // D <= 256 NS: a lane keeps at most NS float4 of the row in registers
+  float4 v[NS];
+  acc_t s = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < NS; i++) {
     const int idx = lane + 64 * i;
-    if (idx < nv) { v[i] = xr[idx]; s += v[i].x + v[i].y + v[i].z + v[i].w; }
+    if (idx < nv) { v[i] = xr[idx]; s += (acc_t)v[i].x + (acc_t)v[i].y + (acc_t)v[i].z + (acc_t)v[i].w; }
   }
-  const float mean = wave_reduce_sum(s) / (float)D;
-  float q = 0.f;
+  const acc_t mean = wave_reduce_sum(s) / (acc_t)D;
+  acc_t q = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < NS; i++) {
     const int idx = lane + 64 * i;
     if (idx < nv) {
-      const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
+      const acc_t a = (acc_t)v[i].x - mean, b = (acc_t)v[i].y - mean, c = (acc_t)v[i].z - mean, d = (acc_t)v[i].w - mean;
       q += a * a + b * b + c * c + d * d;
     }
   }
-  const float rstd = rsqrtf(wave_reduce_sum(q) / (float)D + eps);
+  const acc_t rstd = ln_rsqrt(wave_reduce_sum(q) / (acc_t)D + (acc_t)eps);
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < NS; i++) {
     const int idx = lane + 64 * i;
     if (idx < nv) {
       const float4 g = ((const float4*)gamma)[idx], bb = ((const float4*)beta)[idx];
       float4 y;
-      y.x = (v[i].x - mean) * rstd * g.x + bb.x;
-      y.y = (v[i].y - mean) * rstd * g.y + bb.y;
-      y.z = (v[i].z - mean) * rstd * g.z + bb.z;
-      y.w = (v[i].w - mean) * rstd * g.w + bb.w;
+      y.x = (float)(((acc_t)v[i].x - mean) * rstd * (acc_t)g.x + (acc_t)bb.x);
+      y.y = (float)(((acc_t)v[i].y - mean) * rstd * (acc_t)g.y + (acc_t)bb.y);
+      y.z = (float)(((acc_t)v[i].z - mean) * rstd * (acc_t)g.z + (acc_t)bb.z);
+      y.w = (float)(((acc_t)v[i].w - mean) * rstd * (acc_t)g.w + (acc_t)bb.w);
       if (ob) {
         uint2 o;
         o.x = pack_bf16x2(y.x, y.y);
@@ -223,7 +239,7 @@ int ccx_launch_gather_rows(ccx_ctx* ctx, const long* src_ptrs_dev, const int* le
 
 int ccx_launch_layernorm(ccx_ctx* ctx, const float* x, long ldx, const float* gamma, const float* beta,
                          bf16_t* out_bf16, float* out_f32, long ldo, int M, int D, float eps, hipStream_t stream) {
-  CCX_REQUIRE(ctx, M > 0 && D > 0 && D % 4 == 0 && D <= 1024, "layernorm: D=%d must be a multiple of 4 and <= 1024", D);
+  CCX_REQUIRE(ctx, M > 0 && D > 0 && D % 4 == 0 && D <= 1280, "layernorm: D=%d must be a multiple of 4 and <= 1280", D);
   CCX_REQUIRE(ctx, ldx % 4 == 0 && ldo % 4 == 0, "layernorm: ld must be a multiple of 4");
   static const bool by_shape = getenv("CCX_PROF_SHAPES") != nullptr;
   const char* label = "layernorm_kernel";
@@ -236,8 +252,12 @@ int ccx_launch_layernorm(ccx_ctx* ctx, const float* x, long ldx, const float* ga
     label = names.emplace(buf, buf).first->second.c_str();
   }
   ccx_prof_scope ps(ctx, stream, label, 0.0, (double)M * D * (4.0 + (out_bf16 ? 2.0 : 0.0) + (out_f32 ? 4.0 : 0.0)));
-  hipLaunchKernelGGL(layernorm_kernel, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, ldx, gamma, beta, out_bf16,
-                     out_f32, ldo, M, D, eps);
+  if (D <= 1024)
+    hipLaunchKernelGGL(layernorm_kernel<4>, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, ldx, gamma, beta, out_bf16,
+                       out_f32, ldo, M, D, eps);
+  else
+    hipLaunchKernelGGL(layernorm_kernel<5>, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, ldx, gamma, beta, out_bf16,
+                       out_f32, ldo, M, D, eps);
   CCX_CHECK_LAUNCH(ctx);
   return CCX_OK;
 }

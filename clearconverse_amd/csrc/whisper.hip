@@ -186,9 +186,10 @@ std::vector<float> conv_to_gemm(const ccx_host_tensor& t, int Kpad) {
 
 int build_logmel_tables(ccx_whisper* w) {
   CCX_NEED(w->store, mf, "mel_filters", w->d.n_mels, 201);
-  CCX_REQUIRE(w->ctx, w->d.n_mels == 80, "whisper: only n_mels == 80 is supported (got %d)", w->d.n_mels);
-  std::vector<float> c(400 * 208, 0.f), s(400 * 208, 0.f), fb(80 * 208, 0.f);
-  std::vector<int> rg(160);
+  const int NM = w->d.n_mels;
+  CCX_REQUIRE(w->ctx, NM == 80 || NM == 128, "whisper: n_mels must be 80 or 128 (got %d)", NM);
+  std::vector<float> c(400 * 208, 0.f), s(400 * 208, 0.f), fb((size_t)NM * 208, 0.f);
+  std::vector<int> rg(2 * NM);
   const double two_pi = 6.283185307179586476925286766559;
   for (int n = 0; n < 400; n++) {
     const double win = 0.5 - 0.5 * cos(two_pi * n / 400.0);  // periodic Hann (torch.hann_window default)
@@ -199,7 +200,7 @@ int build_logmel_tables(ccx_whisper* w) {
       s[n * 208 + k] = (float)(sin(a) * win);
     }
   }
-  for (int m = 0; m < 80; m++) {
+  for (int m = 0; m < NM; m++) {
     int k0 = 201, k1 = 0;
     for (int k = 0; k < 201; k++) {
       const float v = mf->data[m * 201 + k];
@@ -214,7 +215,7 @@ int build_logmel_tables(ccx_whisper* w) {
   CCX_TRY(w->store.upload(&ds, s));
   CCX_TRY(w->store.upload(&dfb, fb));
   CCX_TRY(w->store.upload(&drg, rg));
-  w->lm.dft_cos = dc; w->lm.dft_sin = ds; w->lm.mel_fb = dfb; w->lm.mel_range = drg;
+  w->lm.dft_cos = dc; w->lm.dft_sin = ds; w->lm.mel_fb = dfb; w->lm.mel_range = drg; w->lm.n_mels = NM;
   return CCX_OK;
 }
 
@@ -235,8 +236,10 @@ int ccx_whisper_create(ccx_ctx* ctx, const ccx_whisper_dims* dims, int max_batch
   const ccx_whisper_dims& d = *dims;
   CCX_REQUIRE(ctx, d.n_audio_state % 128 == 0 && d.n_text_state == d.n_audio_state, "whisper: n_state must be a multiple of 128 and equal for encoder/decoder");
   CCX_REQUIRE(ctx, d.n_audio_state / d.n_audio_head == 64 && d.n_text_state / d.n_text_head == 64, "whisper: head_dim must be 64");
-  CCX_REQUIRE(ctx, d.n_audio_state <= 1024, "whisper: n_state > 1024 not supported yet");
-  CCX_REQUIRE(ctx, d.n_audio_ctx == 1500 && d.n_mels == 80, "whisper: n_audio_ctx must be 1500 and n_mels 80");
+  CCX_REQUIRE(ctx, d.n_audio_state <= 1280, "whisper: n_state = %d exceeds the supported maximum of 1280", d.n_audio_state);
+  CCX_REQUIRE(ctx, d.n_audio_ctx == 1500, "whisper: n_audio_ctx must be 1500 (got %d)", d.n_audio_ctx);
+  CCX_REQUIRE(ctx, d.n_mels == 80 || d.n_mels == 128, "whisper: n_mels must be 80 or 128 (got %d)", d.n_mels);
+  CCX_REQUIRE(ctx, d.n_audio_layer >= 1 && d.n_text_layer >= 1, "whisper: n_audio_layer = %d and n_text_layer = %d must be at least 1", d.n_audio_layer, d.n_text_layer);
   CCX_REQUIRE(ctx, d.n_audio_ctx % 4 == 0, "whisper: n_audio_ctx must be a multiple of 4");
   CCX_REQUIRE(ctx, d.n_vocab >= 4 && d.n_vocab <= 13 * 4096, "whisper: n_vocab = %d out of range [4, 53248]", d.n_vocab);
   ccx_whisper* w = new ccx_whisper();
@@ -370,7 +373,7 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     CCX_NEED(w->store, pe, "encoder.positional_embedding", S, D);
     CCX_NEED(w->store, lg, "encoder.ln_post.weight", D);
     CCX_NEED(w->store, lb, "encoder.ln_post.bias", D);
-    std::vector<float> g1 = conv_to_gemm(*c1w, 256), g2 = conv_to_gemm(*c2w, 3 * D);
+    std::vector<float> g1 = conv_to_gemm(*c1w, ccx_logmel_kpad(d.n_mels)), g2 = conv_to_gemm(*c2w, 3 * D);
     CCX_TRY(w->store.upload_bf16(&w->Wc1, g1));
     CCX_TRY(w->store.upload_bf16(&w->Wc2, g2));
     CCX_TRY(w->store.upload(&w->bc1, c1b->data.data(), D));
@@ -491,12 +494,12 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     w->im2col = dn->im2col; w->h1 = dn->h1; w->x = dn->x; w->xn = dn->xn;
     w->qb = dn->qb; w->kb = dn->kb; w->vtb = dn->vtb; w->attn = dn->attn; w->ffn = dn->ffn;
   } else {
-    CCX_TRY(w->store.alloc(&w->lm_raw, (size_t)B * 80 * w->Fraw, true));
+    CCX_TRY(w->store.alloc(&w->lm_raw, (size_t)B * d.n_mels * w->Fraw, true));
     CCX_TRY(w->store.alloc(&w->lm_max, (size_t)B, true));
     CCX_TRY(w->store.alloc(&w->lm_n, (size_t)B, true));
     CCX_TRY(w->store.alloc(&w->lm_seek, (size_t)B, true));
     CCX_TRY(w->store.alloc(&w->lm_seg, (size_t)B, true));
-    CCX_TRY(w->store.alloc(&w->im2col, (size_t)B * 3000 * 256, true));
+    CCX_TRY(w->store.alloc(&w->im2col, (size_t)B * 3000 * ccx_logmel_kpad(d.n_mels), true));
     CCX_TRY(w->store.alloc(&w->h1, ((size_t)B * 3002 + 2) * D, true));
     CCX_TRY(w->store.alloc(&w->x, (size_t)B * S * D, true));
     CCX_TRY(w->store.alloc(&w->xn, (size_t)B * S * D, true));
@@ -634,25 +637,11 @@ int ccx_whisper_logmel(ccx_whisper* w, const float* audio, int64_t stride, const
                            w->lm_max, mel_out, w->im2col, stream);
 }
 
-__global__ void mel_to_im2col_kernel(const float* __restrict__ mel, bf16_t* __restrict__ im2col) {
-  // mel [B][80][3000] -> im2col [B*3000][256], k = tap*80 + c holds frame t-1+tap
-  const int b = blockIdx.y, t = blockIdx.x * 4 + (threadIdx.x >> 8), k = threadIdx.x & 255;
-  if (t >= 3000) return;
-  float v = 0.f;
-  if (k < 240) {
-    const int tap = k / 80, c = k - tap * 80, fr = t - 1 + tap;
-    if (fr >= 0 && fr < 3000) v = mel[((long)b * 80 + c) * 3000 + fr];
-  }
-  im2col[((long)b * 3000 + t) * 256 + k] = f32_to_bf16(v);
-}
-
 int ccx_whisper_set_mel(ccx_whisper* w, const float* mel, int B, void* stream_) {
   if (!w) return CCX_ERR_ARG;
   CCX_REQUIRE(w->ctx, w->finalized && mel && B >= 1 && B <= w->max_batch, "whisper_set_mel: bad arguments");
   CCX_TRY(scratch_acquire(w, (hipStream_t)stream_));
-  hipLaunchKernelGGL(mel_to_im2col_kernel, dim3(750, B), dim3(1024), 0, (hipStream_t)stream_, mel, w->im2col);
-  CCX_CHECK_LAUNCH(w->ctx);
-  return CCX_OK;
+  return ccx_launch_mel_to_im2col(w->ctx, w->d.n_mels, mel, B, w->im2col, (hipStream_t)stream_);
 }
 
 // cross-attention K/V of sequences [0, n) for every decoder layer out of xa (head-major, not transposed: decode streams rows)
@@ -705,9 +694,10 @@ int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out, void* stream_) {
   const ccx_whisper_dims& d = w->d;
   const int D = d.n_audio_state, F = 4 * D, S = d.n_audio_ctx, H = d.n_audio_head;
   GemmParams p;
-  // conv1 + GELU: [B*3000,256] x [D,256]^T -> h1 rows b*3002 + 1 + t
+  // conv1 + GELU: [B*3000,KP] x [D,KP]^T -> h1 rows b*3002 + 1 + t (KP = 256 for 80 mels, 384 for 128)
+  const int KP = ccx_logmel_kpad(d.n_mels);
   memset(&p, 0, sizeof(p));
-  p.A = w->im2col; p.lda = 256; p.W = w->Wc1; p.ldw = 256; p.M = B * 3000; p.N = D; p.K = 256;
+  p.A = w->im2col; p.lda = KP; p.W = w->Wc1; p.ldw = KP; p.M = B * 3000; p.N = D; p.K = KP;
   p.bias = w->bc1; p.out = w->h1; p.ldo = D; p.rpb_in = 3000; p.rpb_out = 3002; p.roff = 1; p.rpb_valid = 3000;
   CCX_TRY(ccx_launch_gemm(ctx, EPI_BF16_GELU, p, stream));
   // conv2 (stride 2) + GELU + positional embedding: row m' = b*1501 + t reads h1 rows 2m' .. 2m'+2

@@ -64,10 +64,30 @@ class WhisperDims:
     def medium() -> "WhisperDims":
         return WhisperDims._sized(1024, 16, 24)
 
+    # the `large` family: 1280 wide, 20 heads, 32 encoder layers [UPSTREAM-RECALL: the `dims` of openai-whisper's large-v2, large-v3 and
+    # large-v3-turbo checkpoints].  v3 moved to 128 mel bins and added one language token (51866); turbo is v3 with 4 decoder layers.
     @staticmethod
-    def mini(n_layer: int = 2, n_state: int = 128, n_vocab: int = 51864) -> "WhisperDims":
-        """Reduced-depth/width config for fast parity tests (same kernels, same code path); n_vocab 51865 / 51866: multilingual."""
-        return WhisperDims(n_audio_state=n_state, n_audio_head=n_state // 64, n_audio_layer=n_layer, n_vocab=n_vocab,
+    def large() -> "WhisperDims":
+        """large / large-v1 / large-v2: 80 mel bins, n_vocab 51865."""
+        return WhisperDims._sized(1280, 20, 32)
+
+    @staticmethod
+    def large_v3() -> "WhisperDims":
+        d = WhisperDims._sized(1280, 20, 32, n_vocab=51866)
+        d.n_mels = 128
+        return d
+
+    @staticmethod
+    def large_v3_turbo() -> "WhisperDims":
+        d = WhisperDims.large_v3()
+        d.n_text_layer = 4
+        return d
+
+    @staticmethod
+    def mini(n_layer: int = 2, n_state: int = 128, n_vocab: int = 51864, n_mels: int = 80) -> "WhisperDims":
+        """Reduced-depth/width config for fast parity tests (same kernels, same code path); n_vocab 51865 / 51866: multilingual;
+        n_mels 128: the large-v3 front end."""
+        return WhisperDims(n_mels=n_mels, n_audio_state=n_state, n_audio_head=n_state // 64, n_audio_layer=n_layer, n_vocab=n_vocab,
                            n_text_state=n_state, n_text_head=n_state // 64, n_text_layer=n_layer)
 
 

@@ -150,6 +150,11 @@ typedef struct {
   const int* suppress;              /* host array, copied */
 } ccx_decode_rules;
 
+/* Accepted dims: n_audio_state == n_text_state, a multiple of 128 up to 1280 (tiny ... medium, and the 1280-wide large family), with
+ * head_dim 64 on both sides; n_mels 80 or 128 (large-v3, large-v3-turbo); n_audio_ctx 1500; n_vocab in [4, 53248]; n_audio_layer and
+ * n_text_layer >= 1, not necessarily equal (large-v3-turbo: 32 / 4).  max_batch in [1, 1536].  Widths above 768 (medium, the large
+ * family) keep per-layer cross-attention K / V caches for all max_batch sequences: 2 x 1536 x n_state bf16 per decoder layer and
+ * sequence (252 MB per sequence for a 1280-wide model with 32 decoder layers, 31 MB with 4). */
 int ccx_whisper_create(ccx_ctx* ctx, const ccx_whisper_dims* dims, int max_batch, ccx_whisper** out);
 void ccx_whisper_destroy(ccx_whisper* w);
 /* Register one tensor by its openai-whisper state_dict name (the key layout of the reference's
