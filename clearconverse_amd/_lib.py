@@ -69,6 +69,7 @@ class DecAttnDesc(C.Structure):
 
 
 DEC_ATTN_SELF, DEC_ATTN_SPLIT, DEC_ATTN_STREAM, DEC_ATTN_PREFILL, DEC_ATTN_FUSED_Q, DEC_ATTN_TWO_LAUNCH_Q = range(6)
+DEC_ATTN_STREAM_MAPPED = 7       # (6 is no form)
 
 
 class DecSeqState(C.Structure):
@@ -86,7 +87,8 @@ class DecSelectDesc(C.Structure):
         ("gen", C.POINTER(C.c_int)), ("cur_tok", C.POINTER(C.c_int)), ("pos", C.POINTER(C.c_int)), ("n_done", C.POINTER(C.c_int)),
         ("tok_emb", C.c_void_p), ("pos_emb", C.c_void_p), ("x", C.c_void_p), ("D", C.c_int),
         ("sample", C.c_int), ("temperature", C.c_float), ("seed", C.c_uint64), ("row0", C.c_int),
-        ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64)]
+        ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64),
+        ("stream_ids", C.POINTER(C.c_int))]
 
 
 class DecTokenProbsDesc(C.Structure):
@@ -190,6 +192,7 @@ PROTOTYPES = {
     "ccx_whisper_prepare_lanes": (_i, [_vp, _vp]),
     "ccx_whisper_trace_lanes": (_i, [_vp, C.c_char_p, _i]),
     "ccx_whisper_decode": (_i, [_vp, _i32p, _i32p, _i, _i, _i, _f, C.c_uint64, _i32p, _i32p, _fp, _fp, _vp]),
+    "ccx_whisper_decode_rows": (_i, [_vp, _i32p, _i32p, _i, _i, _i32p, _i, _i32p, _i, _f, C.c_uint64, _i32p, _i32p, _fp, _fp, _vp]),
     "ccx_sepformer_create": (_i, [_vp, C.POINTER(SepformerDims), _i, _i, C.POINTER(_vp)]),
     "ccx_sepformer_destroy": (None, [_vp]),
     "ccx_sepformer_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i64]),

@@ -22,8 +22,9 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
   if (!ctx) return CCX_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_attention_desc: desc is NULL");
-  CCX_REQUIRE(ctx, form >= CCX_DEC_ATTN_SELF && form <= CCX_DEC_ATTN_TWO_LAUNCH_Q, "ccx_dec_attention_desc: unknown form %d", form);
-  const bool is_self = form == CCX_DEC_ATTN_SELF, is_split = form == CCX_DEC_ATTN_SPLIT, is_stream = form == CCX_DEC_ATTN_STREAM;
+  CCX_REQUIRE(ctx, (form >= CCX_DEC_ATTN_SELF && form <= CCX_DEC_ATTN_TWO_LAUNCH_Q) || form == CCX_DEC_ATTN_STREAM_MAPPED, "ccx_dec_attention_desc: unknown form %d", form);
+  const bool is_self = form == CCX_DEC_ATTN_SELF, is_split = form == CCX_DEC_ATTN_SPLIT, is_mapped = form == CCX_DEC_ATTN_STREAM_MAPPED,
+             is_stream = form == CCX_DEC_ATTN_STREAM || is_mapped;
   const bool is_prefill = form == CCX_DEC_ATTN_PREFILL, with_q = form == CCX_DEC_ATTN_FUSED_Q || form == CCX_DEC_ATTN_TWO_LAUNCH_Q;
   const bool partials = is_split || with_q;
   const bool final_out = is_self || is_stream || is_prefill || (is_split && d->combine);
@@ -35,7 +36,7 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
   const int64_t kv_need = (int64_t)n_seq * H * kv_T * 64;
   CCX_REQUIRE(ctx, kv_need <= d->kv_elems, "ccx_dec_attention_desc: k / v are read up to element %ld, kv_elems=%ld", (long)kv_need, (long)d->kv_elems);
   // rows -> sequences
-  if (is_self || is_split || is_prefill) {
+  if (is_self || is_split || is_prefill || is_mapped) {
     if (d->row_seq)
       for (int i = 0; i < rows; i++)
         CCX_REQUIRE(ctx, d->row_seq[i] >= 0 && d->row_seq[i] < n_seq, "ccx_dec_attention_desc: row_seq[%d] = %d out of range [0, %d)", i, d->row_seq[i], n_seq);
@@ -128,7 +129,7 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
     rc = ccx_launch_dec_attention(ctx, ap, rows, nsplit, false, stream);
     if (rc == CCX_OK && d->combine) rc = ccx_launch_dec_combine(ctx, ap.part_o, ap.part_ml, nsplit, d_out16, rows, H, stream);
   } else if (is_stream) {
-    ap.stream_mode = 1;
+    ap.stream_mode = 1; ap.kv_map = is_mapped ? 1 : 0;
     rc = ccx_launch_dec_attention(ctx, ap, rows, 1, true, stream);
   } else if (is_prefill) {
     ap.stream_mode = 1; ap.rows_per_seq = d->rows_per_seq;
@@ -184,6 +185,8 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   CCX_REQUIRE(ctx, d->sample == 0 || d->sample == 1, "ccx_dec_select_step: sample = %d must be 0 or 1", d->sample);
   CCX_REQUIRE(ctx, d->sample || d->temperature == 0.f, "ccx_dec_select_step: temperature %g needs sample = 1", (double)d->temperature);
   CCX_REQUIRE(ctx, d->temperature >= 0.f && d->row0 >= 0, "ccx_dec_select_step: temperature or row0 negative");
+  if (d->stream_ids)
+    for (int b = 0; b < B; b++) CCX_REQUIRE(ctx, d->stream_ids[b] >= 0, "ccx_dec_select_step: stream_ids[%d] = %d is negative", b, d->stream_ids[b]);
   for (int b = 0; b < B; b++) {
     const ccx_dec_seq_state& s = d->state[b];
     CCX_REQUIRE(ctx, s.n_gen >= 0 && s.n_gen <= d->sample_len, "ccx_dec_select_step: state[%d].n_gen = %d out of range [0, sample_len = %d]", b, s.n_gen, d->sample_len);
@@ -204,7 +207,7 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   ccx_op_scratch sc;
   unsigned char* d_mask = nullptr; DecSeqState* d_state = nullptr;
   int *d_prompt = nullptr, *d_cur = nullptr, *d_pos = nullptr, *d_gen = nullptr, *d_ndone = nullptr;
-  unsigned* d_cfg = nullptr;
+  unsigned* d_cfg = nullptr; int* d_sid = nullptr;
   const size_t n_gen_tab = (size_t)B * d->sample_len;
   constexpr int kGuard = 16;                 // sentinel words behind the gen table: a write past sample_len of the last row
   std::vector<int> gen_h(n_gen_tab + kGuard, 0x5a5a5a5a);
@@ -229,6 +232,7 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   sp.max_initial_ts = r.max_initial_timestamp_index;
   sp.tok_emb = (const float*)d->tok_emb; sp.pos_emb = (const float*)d->pos_emb; sp.x = (float*)d->x; sp.D = D;
   sp.sample_cfg = d_cfg; sp.row0 = d->row0; sp.sample = d->sample;
+  if (d->stream_ids) { DO_HIP(sc.upload(&d_sid, d->stream_ids, (size_t)B)); sp.stream_id = d_sid; }
   CCX_TRY(ccx_launch_dec_select(ctx, sp, B, stream));
   DO_HIP(hipStreamSynchronize(stream));
   DO_HIP(hipMemcpy(gen_h.data(), d_gen, gen_h.size() * 4, hipMemcpyDeviceToHost));

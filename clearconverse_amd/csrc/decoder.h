@@ -63,6 +63,10 @@ struct DecAttnParams {
   const float* qx; const float* q_pend; int q_pend_n; long q_pend_stride; float* q_x_out;
   const float* q_ln_g; const float* q_ln_b; float q_eps;
   const bf16_t* q_W; const float* q_bias; int q_K;
+  // set by a decode over a row -> window map (ccx_whisper_decode_rows): row_seq is then honoured by the streaming kernel too, and the
+  // prefill kernels take a group's sequence from row_seq instead of from the block index (the mapped instantiations).  The split-KV
+  // kernel reads row_seq either way.  (Last, in the struct's tail padding: no other field moves.)
+  int kv_map;
 };
 int ccx_launch_dec_attention(ccx_ctx* ctx, const DecAttnParams& p, int B, int nsplit, bool final_out, hipStream_t stream);
 // Cross attention of a small batch (B <= 16 rows) WITH its query projection: replaces ln_linear(Wcq) + ccx_launch_dec_attention(split
@@ -91,6 +95,7 @@ struct DecSelectParams {
   // this launch (lanes), so that the noise of a sequence does not depend on how the batch is split
   const unsigned* sample_cfg; int row0;
   int sample;   // 0: greedy kernel (sample_cfg ignored); 1: kernel with the temperature > 0 branch
+  const int* stream_id;   // sampling kernel only: [B] noise stream of every row instead of row0 + b (null: row0 + b)
 };
 int ccx_launch_dec_select(ccx_ctx* ctx, const DecSelectParams& p, int B, hipStream_t stream);
 int ccx_launch_dec_embed(ccx_ctx* ctx, const float* tok_emb, const float* pos_emb, const int* cur_tok, const int* pos,

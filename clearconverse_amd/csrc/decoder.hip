@@ -983,7 +983,11 @@ int ccx_launch_dec_cross_fused_q(ccx_ctx* ctx, const DecAttnParams& p, int B, in
 // that the rows of one (sequence, head) run on one XCD at about the same time: the first one brings the 384 KB of K/V into
 // that XCD's L2, the others hit it -- the prompt costs about one step of HBM traffic instead of one per prompt token.  Loads are
 // cacheable here (non-temporal for the decode steps, where every byte is used once).
-template <bool FINAL, int NP, bool PRE = false>
+// MAP (a decode over a row -> window map, ccx_whisper_decode_rows): the K/V of a row are those of sequence row_seq[row] -- entries may
+// repeat, need not be monotone and may leave sequences unused; q and out stay indexed by the row.  PRE && MAP: the rows of group `sq`
+// read the sequence row_seq[sq * rows_per_seq] (the host composes the prefill's row table with the map).  One scalar load per block on
+// top of the unmapped kernel; MAP = false is that kernel, instruction for instruction.
+template <bool FINAL, int NP, bool PRE = false, bool MAP = false>
 __global__ __launch_bounds__(256) void dec_cross_stream_kernel(DecAttnParams p) {
   static_assert(FINAL, "one block owns the whole key range of a (row, head): final output, no split-KV partials");
   __shared__ float sm_m[4][8], sm_l[4][8], sm_o[4][8][8];
@@ -999,6 +1003,7 @@ __global__ __launch_bounds__(256) void dec_cross_stream_kernel(DecAttnParams p) 
     const int bh = blockIdx.x;
     b = bh / p.H; h = bh - b * p.H; sq = b;
   }
+  const int kvs = MAP ? __builtin_amdgcn_readfirstlane(p.row_seq[PRE ? sq * p.rows_per_seq : b]) : sq;   // sequence of the K/V
   const int g = lane >> 3, c = lane & 7;
   const int T = p.T;
   const int per = (T + gridDim.y - 1) / gridDim.y;
@@ -1014,8 +1019,8 @@ __global__ __launch_bounds__(256) void dec_cross_stream_kernel(DecAttnParams p) 
   const int w1 = __builtin_amdgcn_readfirstlane((w0 + per_w < kend) ? w0 + per_w : kend);
   constexpr int PSTEP = 32;
 
-  const bf16_t* Kb = p.k + ((long)sq * p.H + h) * p.kv_T * 64 + 8 * c;
-  const bf16_t* Vb = p.v + ((long)sq * p.H + h) * p.kv_T * 64 + 8 * c;
+  const bf16_t* Kb = p.k + ((long)kvs * p.H + h) * p.kv_T * 64 + 8 * c;
+  const bf16_t* Vb = p.v + ((long)kvs * p.H + h) * p.kv_T * 64 + 8 * c;
 
   SoftState st;   // set up in place: through soft_init() the PRE instantiations' SGPR counts move by one, and the register figures are pinned
   st.m = -1e30f; st.l = 0.f;
@@ -1069,7 +1074,7 @@ __global__ __launch_bounds__(256) void dec_cross_stream_kernel(DecAttnParams p) 
 // 768-sequence prefill at 10 rows, ~2 TB/s effective).  Here a block streams the K/V of one (sequence, head) ONCE per RB rows:
 // every 32-key piece is reduced against RB queries.  Same wave / piece structure as the streaming kernel (a wave owns a contiguous
 // quarter of the keys, the next piece is requested before the current one is reduced), cacheable loads, XCD-aware block order.
-template <int NP, int RB>
+template <int NP, int RB, bool MAP = false>
 __global__ __launch_bounds__(256) void dec_cross_prefill_kernel(DecAttnParams p) {
   __shared__ float sm_m[RB][4][8], sm_l[RB][4][8], sm_o[RB][4][8][8];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1083,8 +1088,9 @@ __global__ __launch_bounds__(256) void dec_cross_prefill_kernel(DecAttnParams p)
   const int per_w = ((T + 3) / 4 + 31) & ~31;
   const int w0 = __builtin_amdgcn_readfirstlane(wave * per_w);
   const int w1 = __builtin_amdgcn_readfirstlane((w0 + per_w < T) ? w0 + per_w : T);
-  const bf16_t* Kb = p.k + ((long)sq * p.H + h) * p.kv_T * 64 + 8 * c;
-  const bf16_t* Vb = p.v + ((long)sq * p.H + h) * p.kv_T * 64 + 8 * c;
+  const int kvs = MAP ? __builtin_amdgcn_readfirstlane(p.row_seq[sq * p.rows_per_seq]) : sq;   // MAP: as dec_cross_stream_kernel
+  const bf16_t* Kb = p.k + ((long)kvs * p.H + h) * p.kv_T * 64 + 8 * c;
+  const bf16_t* Vb = p.v + ((long)kvs * p.H + h) * p.kv_T * 64 + 8 * c;
 
   float q[RB][8];
   SoftState st[RB];
@@ -1147,6 +1153,16 @@ int ccx_launch_dec_attention(ccx_ctx* ctx, const DecAttnParams& p, int B, int ns
   static DecAttnKernel streaming[3] = {{"dec_cross_stream_kernel<true,4,false>", dec_cross_stream_kernel<true, 4>},
                                        {"dec_cross_stream_kernel<true,6,false>", dec_cross_stream_kernel<true, 6>},
                                        {"dec_cross_stream_kernel<true,12,false>", dec_cross_stream_kernel<true, 12>}};
+  // the same three over a row -> window map (DecAttnParams::kv_map)
+  static DecAttnKernel prefill4_map[3] = {{"dec_cross_prefill_kernel<4,4,true>", dec_cross_prefill_kernel<4, 4, true>},
+                                          {"dec_cross_prefill_kernel<6,4,true>", dec_cross_prefill_kernel<6, 4, true>},
+                                          {"dec_cross_prefill_kernel<12,4,true>", dec_cross_prefill_kernel<12, 4, true>}};
+  static DecAttnKernel prefill1_map[3] = {{"dec_cross_stream_kernel<true,4,true,true>", dec_cross_stream_kernel<true, 4, true, true>},
+                                          {"dec_cross_stream_kernel<true,6,true,true>", dec_cross_stream_kernel<true, 6, true, true>},
+                                          {"dec_cross_stream_kernel<true,12,true,true>", dec_cross_stream_kernel<true, 12, true, true>}};
+  static DecAttnKernel streaming_map[3] = {{"dec_cross_stream_kernel<true,4,false,true>", dec_cross_stream_kernel<true, 4, false, true>},
+                                           {"dec_cross_stream_kernel<true,6,false,true>", dec_cross_stream_kernel<true, 6, false, true>},
+                                           {"dec_cross_stream_kernel<true,12,false,true>", dec_cross_stream_kernel<true, 12, false, true>}};
   static DecAttnKernel split_kv[2][2] = {   // [self][final]
       {{"dec_attention_kernel<false> (cross)", dec_attention_kernel<false>}, {"dec_attention_kernel<true> (cross)", dec_attention_kernel<true>}},
       {{"dec_attention_kernel<false> (self)", dec_attention_kernel<false>}, {"dec_attention_kernel<true> (self)", dec_attention_kernel<true>}}};
@@ -1162,11 +1178,14 @@ int ccx_launch_dec_attention(ccx_ctx* ctx, const DecAttnParams& p, int B, int ns
     // prompt prefill: B = sequences here, whole key range per block.  Three rows and more: four prompt rows per block (the K/V of
     // a (sequence, head) comes out of L2 once per four rows), else one block per (sequence, head, prompt row)
     CCX_REQUIRE(ctx, nsplit == 1 && final_out && np_need <= 12, "dec_attention: the prefill cross attention takes the whole key range (T <= 1536)");
-    k = p.rows_per_seq >= 3 ? &prefill4[npi] : &prefill1[npi];
+    CCX_REQUIRE(ctx, !p.kv_map || p.row_seq, "dec_attention: kv_map needs row_seq");
+    if (p.kv_map) k = p.rows_per_seq >= 3 ? &prefill4_map[npi] : &prefill1_map[npi];
+    else k = p.rows_per_seq >= 3 ? &prefill4[npi] : &prefill1[npi];
     grid = dim3(B * p.H * (p.rows_per_seq >= 3 ? ccx_cdiv(p.rows_per_seq, 4) : p.rows_per_seq), 1);
   } else if (p.stream_mode && !p.pos && np_need <= 12) {
     CCX_REQUIRE(ctx, final_out, "dec_attention: the streaming cross attention takes the whole key range (nsplit 1)");
-    k = &streaming[npi];
+    // (without kv_map the streaming kernel has never looked at row_seq: row r reads sequence r)
+    k = (p.kv_map && p.row_seq) ? &streaming_map[npi] : &streaming[npi];
     lds = pad;
     CCX_HIP(ctx, k->optin.ensure(ctx->device, (const void*)k->fn, 128 * 1024));
   } else {
@@ -1384,11 +1403,14 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
   if (SAMPLE && temperature > 0.f) {
     const uint2 key = make_uint2(p.sample_cfg[1], p.sample_cfg[2]);
     const float inv_t = 1.0f / temperature;
+    // the row's noise stream: its batch row, or what the caller's table names (rows of a window subset / best_of candidates keep
+    // the stream they have in any other launch geometry)
+    const unsigned sid = p.stream_id ? (unsigned)p.stream_id[b] : (unsigned)(p.row0 + b);
     float best = -INFINITY, best_logit = -INFINITY; int best_i = 0x7fffffff;
 #pragma unroll
     for (int i = 0; i < SEL_V4; i++) {
       const int v0 = tid * 4 + i * 4096;
-      const uint4 r = philox4x32_10(make_uint4((unsigned)(v0 >> 2), (unsigned)(p.row0 + b), (unsigned)i_gen, 0u), key);
+      const uint4 r = philox4x32_10(make_uint4((unsigned)(v0 >> 2), sid, (unsigned)i_gen, 0u), key);
       const unsigned rr[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
       for (int j = 0; j < 4; j++) {

@@ -101,6 +101,13 @@ struct ccx_whisper {
   float *pf_x = nullptr, *pf_x2 = nullptr, *pf_pend = nullptr, *pf_q = nullptr;
   bf16_t *pf_xn = nullptr, *pf_attn = nullptr, *pf_ffn = nullptr;
   int *pf_tok = nullptr, *pf_pos = nullptr, *pf_seq = nullptr, *pf_last = nullptr;
+  // decode over a row -> window map (ccx_whisper_decode_rows): row r keeps self-attention cache slot r and reads the cross K/V (or the
+  // encoder output) of window row_win[r]; row_sid[r] is its noise stream.  Allocated by the first mapped decode; map_on / sid_on hold
+  // for the duration of that call only.  pf_win: the prefill pass's row table composed with the map (row -> window).
+  int *row_win = nullptr, *row_sid = nullptr, *pf_win = nullptr;
+  bool map_on = false, sid_on = false;
+  const int32_t* win_host = nullptr;
+  int enc_B = 0;                             // windows of the last ccx_whisper_encode
   // graph cache; decode runs on an internal stream when the caller hands over the legacy null
   // stream (stream capture is illegal there)
   std::map<std::array<int, 9>, hipGraphExec_t> graphs;
@@ -671,7 +678,8 @@ static void read_chain_switches(ccx_whisper* w) {
   { const char* e = getenv("CCX_XS_FUSE_Q"); w->xs_fuse_q = !e || atoi(e) != 0; }
 }
 // which cross attention a decode of B sequences uses, and the K/V it needs
-static int select_cross_path(ccx_whisper* w, int B, hipStream_t stream) {
+// (n_kv: the sequences whose K/V the rows read -- B itself, or the windows of a mapped decode)
+static int select_cross_path(ccx_whisper* w, int B, hipStream_t stream, int n_kv = -1) {
   // CCX_CROSS_X_MIN_ROWS (read per call: tests flip it): smallest decode that takes the X-stream path.  Default 81: the streaming kernel
   // runs two blocks per sequence, and below ~160 blocks they do not fill the chip -- Whisper only, 24 / 32 / 48 / 64 / 96 x 30 s:
   // 300.7 / 311.8 / 340.0 / 357.9 / 404.3 ms per batch on the X-stream path against 208.6 / 223.3 / 289.4 / 329.3 / 427.2 on per-layer
@@ -680,8 +688,9 @@ static int select_cross_path(ccx_whisper* w, int B, hipStream_t stream) {
   // caches cannot hold (kv_cap sequences) always take the X-stream path.
   const char* e = getenv("CCX_CROSS_X_MIN_ROWS");
   const int min_rows = e ? atoi(e) : ccx_whisper::kKvSeqs + 1;
-  w->xs_active = w->xs_on && (B >= min_rows || B > w->kv_cap);
-  if (w->xs_on && !w->xs_active && w->kv_ready < B) CCX_TRY(project_cross_kv(w, B, stream));
+  if (n_kv < 0) n_kv = B;
+  w->xs_active = w->xs_on && (B >= min_rows || n_kv > w->kv_cap);
+  if (w->xs_on && !w->xs_active && w->kv_ready < n_kv) CCX_TRY(project_cross_kv(w, n_kv, stream));
   return CCX_OK;
 }
 
@@ -731,6 +740,7 @@ int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out, void* stream_) {
   }
   CCX_TRY(ccx_launch_layernorm(ctx, w->x, D, w->lnp_g, w->lnp_b, w->xa, xa_out, D, M, D, 1e-5f, stream));
   CCX_TRY(scratch_release(w, stream));
+  w->enc_B = B;
   // cross-attention K/V: with the X-stream cross attention only decodes of <= 80 sequences use them and project them themselves
   w->kv_ready = 0;
   if (!w->xs_on) CCX_TRY(project_cross_kv(w, B, stream));
@@ -848,6 +858,7 @@ int dec_head(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     sp.max_initial_ts = w->rules.max_initial_timestamp_index;
     sp.tok_emb = w->tok_emb_f32; sp.pos_emb = w->dec_pos; sp.x = w->dx + ro * D; sp.D = D;
     sp.sample_cfg = w->sample_cfg; sp.row0 = b0; sp.sample = w->sampling ? 1 : 0;
+    sp.stream_id = w->sid_on ? w->row_sid + b0 : nullptr;
     CCX_TRY(ccx_launch_dec_select(ctx, sp, B, stream));
   }
   return CCX_OK;
@@ -885,7 +896,10 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
   float* part_ml = w->part_ml + ro * H * ccx_whisper::kCrossSplitMax * 2;
   int* pos = pre ? w->pf_pos : w->pos + b0;
   const int* row_seq = pre ? w->pf_seq : nullptr;
-  const long cross_off = ro * H * w->Spad * 64, self_off = ro * H * Tc * 64;
+  // mapped decode: the cross attention of row r reads window win[r] (prefill: the composed table), counted from window 0 -- the lane's
+  // offset is in the map, not in the K/V base
+  const int* win = !w->map_on ? nullptr : (pre ? w->pf_win : w->row_win + b0);
+  const long cross_off = w->map_on ? 0 : ro * H * w->Spad * 64, self_off = ro * H * Tc * 64;
   const int stamp_level = w->stamp_level;
   auto stamp = [&](int tag, int level) {
     if (w->stamps_on && level <= stamp_level)
@@ -941,7 +955,9 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
   //    split-KV partials combined by the out projection.
   const bool lnfree = w->xs_active && w->lnfree;
   const bool xs_fused = w->xs_active && !lnfree && w->xs_fuse_q;
-  const bool fuse_q = !w->xs_active && w->fuse_cross_q && !pre && B <= 16 && D == 768;
+  // (a mapped decode bypasses the fused query for the two launches it replaces: q is bit-identical, and the fused kernel's address
+  //  arithmetic -- block-uniform bases in SGPR pairs under a 168-register cap -- stays what it is)
+  const bool fuse_q = !w->xs_active && w->fuse_cross_q && !pre && B <= 16 && D == 768 && !w->map_on;
   const bool q_launch = !fuse_q && !lnfree && !xs_fused;    // the query projection as a launch of its own
   // LayerNorm-free query: the resolved rows and their tile statistics (X-stream instances only)
   bf16_t* xb = !lnfree ? nullptr : (pre ? w->pf_xb : w->dxb + ro * D);
@@ -991,7 +1007,8 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
       xp.q = dq; xp.WkT = L.WckT; xp.xq = pre ? w->pf_xq : w->xq + ro * H * D;
       xp.part_o = pre ? w->pf_xs_po : w->xs_po + ccx_xs_part_o_elems(ro, H, D);
       xp.part_ml = pre ? w->pf_xs_pml : w->xs_pml + ccx_xs_part_ml_elems(ro);
-      xp.X = pre ? w->xa : w->xa + ro * (long)d.n_audio_ctx * D; xp.x_seq_stride = (long)d.n_audio_ctx * D; xp.row_seq = row_seq;
+      xp.X = (pre || w->map_on) ? w->xa : w->xa + ro * (long)d.n_audio_ctx * D; xp.x_seq_stride = (long)d.n_audio_ctx * D;
+      xp.row_seq = w->map_on ? win : row_seq;
       xp.Wv = L.Wckv + (long)D * D; xp.bv = L.bckv + D; xp.out = dattn;
       xp.rows = B; xp.H = H; xp.S = d.n_audio_ctx; xp.D = D; xp.scale_log2e = scale_log2e;
       xp.lds_pad = (w->cross_lds_pad > 0 && !pre) ? 65536 : 0;
@@ -1007,6 +1024,7 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
       ap.scale_log2e = scale_log2e; ap.part_o = part_o; ap.part_ml = part_ml; ap.out_bf16 = dattn;
       ap.lds_pad = w->cross_lds_pad;
       ap.stream_mode = (w->cross_stream && B > 16) ? 1 : 0;
+      ap.row_seq = win; ap.kv_map = w->map_on ? 1 : 0;
       if (fuse_q) {
         ap.qx = cur; ap.q_pend = pend; ap.q_pend_n = pend_n; ap.q_pend_stride = pstride; ap.q_x_out = pend_n > 0 ? other : nullptr;
         ap.q_ln_g = L.lnc_g; ap.q_ln_b = L.lnc_b; ap.q_eps = 1e-5f; ap.q_W = L.Wcq; ap.q_bias = L.bcq; ap.q_K = D;
@@ -1015,7 +1033,8 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
         CCX_TRY(partial_linear(ACT_COMBINE, L.Wco, L.bco, D, nullptr));
       } else if (pre) {
         // two prompt rows and more per sequence share its K/V; a one-row pass runs as a decode step would
-        ap.row_seq = prefill_rows > 1 ? row_seq : nullptr; ap.rows_per_seq = prefill_rows > 1 ? prefill_rows : 0;
+        if (!w->map_on) ap.row_seq = prefill_rows > 1 ? row_seq : nullptr;
+        ap.rows_per_seq = prefill_rows > 1 ? prefill_rows : 0;
         ap.lds_pad = 0; ap.stream_mode = 1;
         CCX_TRY(ccx_launch_dec_attention(ctx, ap, nseq, 1, true, stream));
         CCX_TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
@@ -1107,6 +1126,11 @@ int run_prefill(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_tok, tok.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_pos, ps.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_seq, sq.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
+    std::vector<int> wn(w->map_on ? R : 0);     // mapped decode: the two maps composed, a prefill row's window is win[pf_seq[row]]
+    if (w->map_on) {
+      for (int r = 0; r < R; r++) wn[r] = w->win_host[sq[r]];
+      CCX_HIP(ctx, hipMemcpyAsync(w->pf_win, wn.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
+    }
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_last, last.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream));
     CCX_TRY(ccx_launch_dec_embed(ctx, w->tok_emb_f32, w->dec_pos, w->pf_tok, w->pf_pos, w->pf_x, R, D, stream));
     CCX_HIP(ctx, hipStreamSynchronize(stream));     // host tables go out of scope
@@ -1391,9 +1415,11 @@ int ccx_whisper_decode_greedy(ccx_whisper* w, const int32_t* prompt_ids, const i
                             no_speech_prob_out, stream_);
 }
 
-int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B, int sample_len,
+// The decode behind ccx_whisper_decode (win == NULL: row r reads window r, noise stream r) and ccx_whisper_decode_rows (B rows over
+// n_windows encoded windows: row r reads window win[r]; sids, if given, names every row's noise stream).  Both checked by the callers.
+static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B, int sample_len,
                        float temperature, uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out,
-                       float* no_speech_prob_out, void* stream_) {
+                       float* no_speech_prob_out, void* stream_, const int32_t* win, int n_windows, const int32_t* sids) {
   if (!w) return CCX_ERR_ARG;
   CCX_REQUIRE(w->ctx, temperature >= 0.f && temperature == temperature, "decode: temperature must be >= 0");
   hipStream_t stream = (hipStream_t)stream_;
@@ -1429,7 +1455,19 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   const bool prefill = prefill_on && (max_pl >= 2 || ns_at_sot);
   if (ns_at_sot) CCX_TRY(ensure_token_probs_scratch(w));
   read_chain_switches(w);
-  CCX_TRY(select_cross_path(w, B, stream));
+  CCX_TRY(select_cross_path(w, B, stream, win ? n_windows : -1));
+  // the map and the ids: uploaded once per call (the state upload below synchronises), in force until the call returns
+  struct MapGuard { ccx_whisper* w; ~MapGuard() { w->map_on = false; w->sid_on = false; w->win_host = nullptr; } } map_guard{w};
+  if (win) {
+    if (!w->row_win) {
+      CCX_TRY(w->store.alloc(&w->row_win, (size_t)w->max_batch, true));
+      CCX_TRY(w->store.alloc(&w->row_sid, (size_t)w->max_batch, true));
+      CCX_TRY(w->store.alloc(&w->pf_win, (size_t)w->max_batch * ccx_whisper::kPrefillMax, true));
+    }
+    CCX_HIP(ctx, hipMemcpyAsync(w->row_win, win, (size_t)B * 4, hipMemcpyHostToDevice, stream));
+    if (sids) CCX_HIP(ctx, hipMemcpyAsync(w->row_sid, sids, (size_t)B * 4, hipMemcpyHostToDevice, stream));
+    w->map_on = true; w->sid_on = sids != nullptr; w->win_host = win;
+  }
   CCX_TRY(upload_decode_state(w, prompt_ids, prompt_lens, max_prompt, B, temperature, seed, stream, prefill));
   // steps still to run after the (eager) first one: the prefill already covers the prompt AND takes the first sample below
   const int total_steps = prefill ? sample_len : max_pl - 1 + sample_len;
@@ -1515,7 +1553,9 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
       // graphs are specific to (lane rows, sample_len, max_prompt, sampling)
       // ... and to everything else dec_step bakes into the graph: the cross-attention split count and LDS cap, and the chain's form
       const int ns_key = cross_split(lanes[i].B, w->d.n_text_head, w->cross_stream != 0);
-      const int form = (w->fuse_cross_q ? 1 : 0) | ((w->xs_active ? 1 : 0) << 1) | ((w->xs_fuse_q ? 1 : 0) << 2) | ((w->lnfree ? 1 : 0) << 3);
+      // ... and whether the step reads a row -> window map / a stream-id table (other launches, other kernel arguments)
+      const int form = (w->fuse_cross_q ? 1 : 0) | ((w->xs_active ? 1 : 0) << 1) | ((w->xs_fuse_q ? 1 : 0) << 2) | ((w->lnfree ? 1 : 0) << 3) |
+                       ((w->map_on ? 1 : 0) << 4) | ((w->sid_on ? 1 : 0) << 5);
       const std::array<int, 9> key = {lanes[i].b0, lanes[i].B, sample_len, max_prompt, w->sampling ? 1 : 0, ns_key, w->cross_lds_pad, form, i};
       auto it = w->graphs.find(key);
       if (it != w->graphs.end()) { lanes[i].exec = it->second; continue; }
@@ -1617,6 +1657,34 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
     if (no_speech_prob_out) no_speech_prob_out[b] = ns_at_sot ? ns_sot[b] : st[b].no_speech_prob;
   }
   return CCX_OK;
+}
+
+int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B, int sample_len,
+                       float temperature, uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out,
+                       float* no_speech_prob_out, void* stream_) {
+  return decode_impl(w, prompt_ids, prompt_lens, max_prompt, B, sample_len, temperature, seed, tokens_out, n_tokens_out, sum_logprob_out,
+                     no_speech_prob_out, stream_, nullptr, 0, nullptr);
+}
+
+int ccx_whisper_decode_rows(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int R,
+                            const int32_t* window_of_row, int n_windows, const int32_t* stream_ids, int sample_len, float temperature,
+                            uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out, float* no_speech_prob_out,
+                            void* stream_) {
+  if (!w) return CCX_ERR_ARG;
+  ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, w->finalized && w->rules_set, "ccx_whisper_decode_rows: not finalized or rules not set");
+  CCX_REQUIRE(ctx, R >= 1 && R <= w->max_batch, "ccx_whisper_decode_rows: R = %d out of range [1, max_batch = %d]", R, w->max_batch);
+  CCX_REQUIRE(ctx, window_of_row != nullptr, "ccx_whisper_decode_rows: window_of_row is NULL");
+  CCX_REQUIRE(ctx, n_windows >= 1 && n_windows <= w->max_batch, "ccx_whisper_decode_rows: n_windows = %d out of range [1, max_batch = %d]", n_windows,
+              w->max_batch);
+  CCX_REQUIRE(ctx, n_windows <= w->enc_B, "ccx_whisper_decode_rows: n_windows = %d, the last ccx_whisper_encode left %d windows", n_windows, w->enc_B);
+  for (int r = 0; r < R; r++) {
+    CCX_REQUIRE(ctx, window_of_row[r] >= 0 && window_of_row[r] < n_windows, "ccx_whisper_decode_rows: window_of_row[%d] = %d out of range [0, n_windows = %d)", r,
+                window_of_row[r], n_windows);
+    if (stream_ids) CCX_REQUIRE(ctx, stream_ids[r] >= 0, "ccx_whisper_decode_rows: stream_ids[%d] = %d is negative", r, stream_ids[r]);
+  }
+  return decode_impl(w, prompt_ids, prompt_lens, max_prompt, R, sample_len, temperature, seed, tokens_out, n_tokens_out, sum_logprob_out,
+                     no_speech_prob_out, stream_, window_of_row, n_windows, stream_ids);
 }
 
 }  // extern "C"

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, fallback
 from .audio import mel_filterbank
 from .tokenizer import DecodeRules, IdTokenizer, get_tokenizer
 from .weights import WhisperDims
@@ -280,12 +280,19 @@ class WindowLoop:
 
 
 class WhisperModel:
+    temperature_fallback = False      # opt-in (the constructor's keyword)
+
     def __init__(self, dims: WhisperDims, state_dict: Dict[str, torch.Tensor], max_batch: int = 8,
                  device: int = 0, rules: Optional[DecodeRules] = None, tokenizer=None,
                  ctx: Optional[_lib.Context] = None, max_audio_seconds: float = 30.0,
                  share_encoder_scratch_with: Optional["WhisperModel"] = None, word_alignment: bool = False,
-                 alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False):
-        """word_alignment (default False: nothing below runs, `transcribe(word_timestamps=True)` has no effect, as before): with it,
+                 alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False,
+                 temperature_fallback: bool = False):
+        """temperature_fallback (default False: a tuple or list temperature raises, `best_of` and `compression_ratio_threshold` are
+        ignored, as before): with it, `transcribe` / `transcribe_batch` take a temperature schedule, `compression_ratio_threshold` and
+        `best_of` and decode a window again, warmer, while it is too repetitive or too improbable (clearconverse_amd/fallback.py) --
+        only the failing windows, over a row -> window map (`decode_rows`), nothing encoded again.
+        word_alignment (default False: nothing below runs, `transcribe(word_timestamps=True)` has no effect, as before): with it,
         `transcribe(word_timestamps=True)` aligns the words of every window by cross-attention DTW on the GPU (`align`), attaches
         `words` to the segments and moves `seek` by upstream's last-word rule (WindowLoop.advance).
         alignment_heads: (layer, head) pairs whose cross attention is aligned.  Default: every head of the upper half of the decoder
@@ -317,6 +324,7 @@ class WhisperModel:
         self.last_cross_path = None
         self.word_alignment = bool(word_alignment)
         self.word_probabilities = bool(word_probabilities)
+        self.temperature_fallback = bool(temperature_fallback)
         if alignment_heads is None:
             alignment_heads = [(l, h) for l in range(dims.n_text_layer // 2, dims.n_text_layer) for h in range(dims.n_text_head)]
         self.alignment_heads = [(int(l), int(h)) for l, h in alignment_heads]
@@ -468,6 +476,72 @@ class WhisperModel:
                      avg_logprob=float(slp[b]) / (int(ntok[b]) + 1), no_speech_prob=float(nsp[b]),
                      cross_path=self.last_cross_path) for b in range(B)]
 
+    def decode_rows(self, prompts: Sequence[Sequence[int]], windows: Sequence[int], stream_ids: Optional[Sequence[int]] = None,
+                    sample_len: Optional[int] = None, temperature: float = 0.0, seed: int = 0, n_windows: Optional[int] = None) -> List[dict]:
+        """`decode` for len(prompts) <= max_batch rows over the currently encoded windows (ccx_whisper_decode_rows): row r decodes
+        window windows[r] -- entries may repeat (best_of), need not be monotone, and windows may go unused (a fallback round decodes
+        only the failing ones).  stream_ids[r]: the row's noise stream at temperature > 0 (None: r), so that its draws do not depend on
+        the rows it shares the call with.  n_windows: how many windows are encoded (default: max(windows) + 1)."""
+        if not (temperature >= 0.0):
+            raise _lib.CcxError("temperature must be >= 0")
+        R = len(prompts)
+        if len(windows) != R or (stream_ids is not None and len(stream_ids) != R):
+            raise _lib.CcxError("decode_rows: one window (and one stream id) per prompt")
+        mp = max(len(p) for p in prompts)
+        sample_len = sample_len or decode_cap(mp, self.dims.n_text_ctx)
+        ids = np.full((R, mp), self.rules.eot, dtype=np.int32)
+        lens = np.zeros(R, dtype=np.int32)
+        for b, p in enumerate(prompts):
+            ids[b, :len(p)] = p
+            lens[b] = len(p)
+        win = np.ascontiguousarray(windows, dtype=np.int32)
+        sid = np.ascontiguousarray(stream_ids, dtype=np.int32) if stream_ids is not None else None
+        nw = int(n_windows) if n_windows is not None else int(win.max()) + 1
+        toks = np.zeros((R, sample_len), dtype=np.int32)
+        ntok = np.zeros(R, dtype=np.int32)
+        slp = np.zeros(R, dtype=np.float32)
+        nsp = np.zeros(R, dtype=np.float32)
+        i32p, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self.ctx.check(self.lib.ccx_whisper_decode_rows(
+            self.handle, ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), mp, R, win.ctypes.data_as(i32p), nw,
+            sid.ctypes.data_as(i32p) if sid is not None else None, sample_len, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            toks.ctypes.data_as(i32p), ntok.ctypes.data_as(i32p), slp.ctypes.data_as(fp), nsp.ctypes.data_as(fp),
+            _lib.current_stream_ptr()), "ccx_whisper_decode_rows")
+        self.last_cross_path = CROSS_PATHS.get(int(self.lib.ccx_whisper_last_cross_path(self.handle)), "unknown")
+        return [dict(tokens=toks[b, :ntok[b]].tolist(), sum_logprob=float(slp[b]),
+                     avg_logprob=float(slp[b]) / (int(ntok[b]) + 1), no_speech_prob=float(nsp[b]),
+                     cross_path=self.last_cross_path) for b in range(R)]
+
+    def _decode_with_fallback(self, prompts, cap: int, schedule, best_of, compression_ratio_threshold, logprob_threshold,
+                              no_speech_threshold) -> List[dict]:
+        """The schedule walk of one encoded group [UPSTREAM-RECALL: transcribe.py::decode_with_fallback]: round 0 over every window,
+        each later round one `decode_rows` (chunked to max_batch rows) over the windows still failing, times best_of above
+        temperature 0.  Round 0 is a plain `decode` whenever it has one row per window, so a group whose windows all pass at the
+        first temperature costs what it costs without a schedule.  One seed per round -- the chunks of a round are one decode split
+        by capacity -- and stream ids from the window's place in the group: a window's outcome does not depend on which other
+        windows fell back.  -> one result per window: tokens, avg_logprob, no_speech_prob, temperature, compression_ratio."""
+        walk = fallback.FallbackWalk(len(prompts), schedule, compression_ratio_threshold, logprob_threshold, no_speech_threshold)
+        self.fallback_walks.append(walk)        # (tests replay every window's rounds from walk.trace)
+        eot = self.rules.eot
+        while not walk.done():
+            t = walk.temperature()
+            n_rows = fallback.rows_per_window(t, best_of)
+            failing = walk.pending()
+            self._sample_calls += 1
+            seed = (int(self.sample_seed) << 32) + self._sample_calls
+            cands: Dict[int, List[dict]] = {w: [] for w in failing}
+            if walk.round == 0 and n_rows == 1:
+                for w, r in enumerate(self.decode(prompts, sample_len=cap, temperature=t, seed=seed)):
+                    cands[w].append(r)
+            else:
+                for ch in fallback.plan_round(failing, prompts, n_rows, self.max_batch):
+                    rows = self.decode_rows(ch["prompts"], ch["windows"], ch["stream_ids"], sample_len=cap, temperature=t, seed=seed,
+                                            n_windows=len(prompts))
+                    for (w, _), r in zip(ch["owners"], rows):
+                        cands[w].append(r)
+            walk.submit({w: fallback.window_result(cands[w], t, self.tokenizer, eot) for w in failing})
+        return [walk.accepted[w] for w in range(len(prompts))]
+
     def align(self, tokens_per_seq: Sequence[Sequence[int]], n_frames: Sequence[int], return_probs: bool = False,
               return_matrix: bool = False, row0: int = 1, token_probs: bool = False):
         """Word alignment of the currently encoded windows (ccx_whisper_align; valid after `encode` or a decode of the same
@@ -512,7 +586,8 @@ class WhisperModel:
         """word_alignment and word_timestamps: align every window of the group that produced text while the windows are still
         encoded, attach the words, and advance each clip with the end of its last word [UPSTREAM-RECALL: transcribe.py].  On an
         instance with word_probabilities the same pass gives the token probabilities, the words carry `probability` and the
-        threshold reaches `advance`."""
+        threshold reaches `advance`.  temperature: one for the group, or one per window (a fallback walk's)."""
+        temps = list(temperature) if isinstance(temperature, (tuple, list)) else [temperature] * len(grp)
         built = [state[i].window_segments(r) for i, r in zip(grp, results)]
         texts = []
         for bt in built:
@@ -534,10 +609,10 @@ class WhisperModel:
                                     prob_fn=(lambda toks, b=b: probs[b]) if self.word_probabilities else None)
                 end = get_end(segs)
             if self.word_probabilities and hallucination_silence_threshold is not None:
-                state[i].advance(r, temperature, last_word_end=end, segments=segs,
+                state[i].advance(r, temps[b], last_word_end=end, segments=segs,
                                  hallucination_silence_threshold=hallucination_silence_threshold)
             else:
-                state[i].advance(r, temperature, last_word_end=end, segments=segs)
+                state[i].advance(r, temps[b], last_word_end=end, segments=segs)
 
     # ------------------------------------------------------------------ transcribe (reference call surface)
     def initial_tokens(self, prompt_tokens: Sequence[int], sot_sequence: Optional[Sequence[int]] = None) -> List[int]:
@@ -552,7 +627,8 @@ class WhisperModel:
                    condition_on_previous_text: bool = True, temperature: float = 0.0,
                    no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0,
                    language: Optional[str] = None, task: str = "transcribe",
-                   hallucination_silence_threshold: Optional[float] = None, **_ignored):
+                   hallucination_silence_threshold: Optional[float] = None, compression_ratio_threshold: Optional[float] = 2.4,
+                   best_of: Optional[int] = None, **_ignored):
         """One clip, same signature as whisper.transcribe as the reference uses it.  temperature 0 is the
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
@@ -564,8 +640,13 @@ class WhisperModel:
         ignores both, as upstream's transcribe does.
         hallucination_silence_threshold (seconds): with word_timestamps on an instance built with `word_probabilities=True`, silence
         longer than this around a probable hallucination is skipped (WindowLoop.advance); otherwise no effect -- upstream ignores
-        it without word_timestamps too."""
+        it without word_timestamps too.
+        On an instance built with `temperature_fallback=True`: temperature may be a schedule (upstream's default is (0.0, 0.2, 0.4,
+        0.6, 0.8, 1.0); here the default stays 0.0), and compression_ratio_threshold / best_of are honoured
+        [UPSTREAM-RECALL: transcribe.py::decode_with_fallback; parity unpinned] -- see `transcribe_batch`.  Otherwise a schedule
+        raises and the two are ignored."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
+                                     compression_ratio_threshold=compression_ratio_threshold, best_of=best_of,
                                      temperature=temperature, no_speech_threshold=no_speech_threshold,
                                      logprob_threshold=logprob_threshold, word_timestamps=word_timestamps,
                                      languages=[language], task=task,
@@ -575,16 +656,33 @@ class WhisperModel:
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
                          no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0,
                          word_timestamps: bool = False, languages: Optional[Sequence[Optional[str]]] = None,
-                         task: str = "transcribe", hallucination_silence_threshold: Optional[float] = None) -> List[dict]:
+                         task: str = "transcribe", hallucination_silence_threshold: Optional[float] = None,
+                         compression_ratio_threshold: Optional[float] = 2.4, best_of: Optional[int] = None) -> List[dict]:
         """Independent clips decoded together (each window of each clip is one sequence of a batch).
         languages[i] (multilingual models): the clip's language code or name; None: detected on the clip's first window, after its
         group's `encode` and before its `decode` [UPSTREAM-RECALL: transcribe.py, `if decode_options.get("language") is None`].
         A pass over the active clips is split into groups of one sample cap (decode_cap) of at most max_batch windows.
-        hallucination_silence_threshold: as in `transcribe`, for every clip."""
+        hallucination_silence_threshold: as in `transcribe`, for every clip.
+        temperature_fallback instances [UPSTREAM-RECALL: transcribe.py::decode_with_fallback; parity unpinned]: with a temperature
+        sequence or a best_of, every window walks the schedule (clearconverse_amd/fallback.py): accepted at the first temperature at
+        which its compression ratio is not above compression_ratio_threshold and its mean log-probability not below
+        logprob_threshold (silence by no_speech_threshold excepted), at the last one whatever it scores; above temperature 0,
+        best_of candidates per window, the most probable per token kept.  Per group `log_mel` and `encode` run once; word alignment
+        runs after the walk on the accepted tokens.  On such calls every segment also carries `temperature`, `avg_logprob`,
+        `compression_ratio` and `no_speech_prob`, as upstream's do; a single float without best_of returns what it always did."""
         with_words = bool(word_timestamps) and self.word_alignment
-        if isinstance(temperature, (tuple, list)):
-            raise _lib.CcxError("temperature fallback schedules are not implemented: pass one temperature (the reference does)")
-        temperature = float(temperature)
+        if not self.temperature_fallback:
+            if isinstance(temperature, (tuple, list)):
+                raise _lib.CcxError("temperature fallback schedules need an instance built with temperature_fallback=True: "
+                                    "pass one temperature (the reference does)")
+            best_of = None          # ignored, as compression_ratio_threshold is
+        try:
+            schedule = fallback.normalize_schedule(temperature)
+        except ValueError as e:
+            raise _lib.CcxError(str(e)) from e
+        walk_on = self.temperature_fallback and (isinstance(temperature, (tuple, list)) or best_of is not None)
+        self.fallback_walks: List[fallback.FallbackWalk] = []     # this call's walks, one per encoded group, in order
+        temperature = schedule[0]
         n = len(audios)
         initial_prompts = list(initial_prompts) if initial_prompts is not None else [None] * n
         # device tensors (the processor's crops) stay on the device; host arrays go up in one transfer
@@ -638,6 +736,22 @@ class WhisperModel:
                         if not state[i].language_known:
                             state[i].set_language(codes[b])
                 prompts = [state[i].initial_tokens() for i in grp]
+                if walk_on:
+                    results = self._decode_with_fallback(prompts, cap, schedule, best_of, compression_ratio_threshold,
+                                                         logprob_threshold, no_speech_threshold)
+                    self.fallback_walks[-1].clips, self.fallback_walks[-1].seeks = list(grp), [state[i].seek for i in grp]
+                    n_seg = [len(state[i].segments) for i in grp]
+                    if with_words:     # the accepted tokens, while the group's windows are still encoded: aligned as one batch, each
+                        # window advanced with the temperature it was accepted at
+                        self._advance_with_words(grp, results, state, [r["temperature"] for r in results], hallucination_silence_threshold)
+                    else:
+                        for i, r in zip(grp, results):
+                            state[i].advance(r, r["temperature"])
+                    for b, (i, r) in enumerate(zip(grp, results)):
+                        for s in state[i].segments[n_seg[b]:]:
+                            s.update(temperature=r["temperature"], avg_logprob=r["avg_logprob"], compression_ratio=r["compression_ratio"],
+                                     no_speech_prob=r["no_speech_prob"])
+                    continue
                 self._sample_calls += 1
                 results = self.decode(prompts, sample_len=cap, temperature=temperature,
                                       seed=(int(self.sample_seed) << 32) + self._sample_calls)

@@ -216,6 +216,21 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
                        int sample_len, float temperature, uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out,
                        float* sum_logprob_out, float* no_speech_prob_out, void* stream);
 
+/* ccx_whisper_decode for R <= max_batch rows over the n_windows <= max_batch windows of the last ccx_whisper_encode: row r keeps
+ * self-attention cache slot r and its cross attention reads window window_of_row[r] (host [R]; entries may repeat, need not be
+ * monotone, and windows may go unused).  What openai-whisper's transcribe.py::decode_with_fallback [UPSTREAM-RECALL] needs when it decodes
+ * a window again at the next temperature -- only the failing windows, nothing encoded again -- and what DecodingOptions.best_of needs
+ * (decoding.py: `audio_features.repeat_interleave(self.n_group, dim=0)`): n rows on one window without copies of its encoder output.
+ * stream_ids (host [R], >= 0, or NULL = the row index): the sampler's noise stream of every row, so that a row's draws do not depend
+ * on which other rows share the call.  The cross-attention path is chosen by R as ccx_whisper_decode chooses it by B; the per-layer
+ * K/V are projected for n_windows (an X-stream instance whose K/V caches cannot hold n_windows takes the X-stream path).  <= 16 rows
+ * at d_model 768 run the two-launch query instead of the fused one (bit-identical q).  Everything ccx_whisper_decode checks is
+ * checked, plus the ranges above: CCX_ERR_ARG (1) naming "ccx_whisper_decode_rows" and the field.  Outputs as ccx_whisper_decode. */
+int ccx_whisper_decode_rows(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int R,
+                            const int32_t* window_of_row, int n_windows, const int32_t* stream_ids, int sample_len, float temperature,
+                            uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out,
+                            float* no_speech_prob_out, void* stream);
+
 /* ---- the decode step's attention and token-select kernels on their own (csrc/decoder.hip; for kernel parity tests) ---------
  * Both entry points check on the host everything the kernels assume (ranges, element counts, 16-byte alignment of every
  * vector-accessed pointer) before anything is launched: a violation returns CCX_ERR_ARG (1) with a message naming the field.
@@ -226,23 +241,25 @@ int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
 #define CCX_DEC_ATTN_PREFILL 3       /* rows_per_seq == 2: dec_cross_stream_kernel<.., true>; >= 3: dec_cross_prefill_kernel<NP, 4> */
 #define CCX_DEC_ATTN_FUSED_Q 4       /* ccx_launch_dec_cross_fused_q: q = LN(x + pending slabs) Wq^T + bq inside the attention blocks */
 #define CCX_DEC_ATTN_TWO_LAUNCH_Q 5  /* dec_linear<ACT_LN, DEPI_F32>, then dec_attention_kernel<false>: what FUSED_Q replaces */
+/* (6 is not a form: it stays the number the rejection tests of the descriptor use for an unknown one) */
+#define CCX_DEC_ATTN_STREAM_MAPPED 7 /* form 2 with row_seq honoured: dec_cross_stream_kernel<true, NP, false, true> (ccx_whisper_decode_rows) */
 
 typedef struct ccx_dec_attn_desc {
-  /* device operands.  q f32 [rows][H][64] (forms 0..3); k, v bf16 [n_seq][H][kv_T][64] */
+  /* device operands.  q f32 [rows][H][64] (forms 0..3, 7); k, v bf16 [n_seq][H][kv_T][64] */
   const void* q; const void* k; const void* v;
   int rows, n_seq, H, kv_T;
-  int T;                    /* keys [0, T) of the cross forms (1..5) */
+  int T;                    /* keys [0, T) of the cross forms (1..5, 7) */
   const int* pos;           /* HOST [rows], form 0: row r attends to keys [0, pos[r]] */
-  const int* row_seq;       /* HOST [rows] or NULL (row r reads sequence r): forms 0, 1, 3 */
+  const int* row_seq;       /* HOST [rows] or NULL (row r reads sequence r): forms 0, 1, 3, 7 */
   int rows_per_seq;         /* form 3: consecutive groups of that many rows belong to one sequence (group g = sequence g) */
   int nsplit, combine;      /* forms 1, 4, 5: key splits (1..8); form 1: also run dec_combine_kernel into out */
-  int lds_pad;              /* forms 1, 2: dynamic LDS the blocks claim without using it */
+  int lds_pad;              /* forms 1, 2, 7: dynamic LDS the blocks claim without using it */
   /* forms 4, 5 (H must be 12): x f32 [rows][768], pend f32 [max(pend_n, 1)] slabs of [rows][768] pend_stride elements apart (slab 0
    * is read, with weight 0, also when pend_n == 0), ln_g / ln_b / bq f32 [768] on the device, wq f32 [768][768] row-major on the HOST */
   const void* x; const void* pend; int pend_n; int64_t pend_stride;
   const void* ln_g; const void* ln_b; float eps;
   const float* wq_host; const void* bq;
-  /* device outputs: out f32 [rows][H * 64] (the kernels' bf16 output widened; forms 0, 2, 3 and form 1 with combine),
+  /* device outputs: out f32 [rows][H * 64] (the kernels' bf16 output widened; forms 0, 2, 3, 7 and form 1 with combine),
    * part_o f32 [rows][H][nsplit][64], part_ml f32 [rows][H][nsplit][2] (forms 1, 4, 5), q_x_out f32 [rows][768] (forms 4, 5, may be NULL) */
   void* out; void* part_o; void* part_ml; void* q_x_out;
   /* elements (of the buffer's own type) behind each pointer; kv_elems holds for k and for v */
@@ -273,6 +290,7 @@ typedef struct ccx_dec_select_desc {
   const void* tok_emb; const void* pos_emb; void* x; int D;   /* device f32 [tok rows][D], [pos rows][D], [B][D] (in and out) */
   int sample; float temperature; uint64_t seed; int row0;     /* sample 1: the kernel with the temperature > 0 branch */
   int64_t logits_elems, tok_emb_elems, pos_emb_elems, x_elems;
+  const int* stream_ids;                                      /* HOST [B] (>= 0) or NULL: the noise stream of row b instead of row0 + b */
 } ccx_dec_select_desc;
 
 /* One launch of the select kernel (ccx_launch_dec_select) for B rows: filters, argmax / sampling, the per-sequence state machine and
