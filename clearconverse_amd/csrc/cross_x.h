@@ -36,7 +36,11 @@ struct XsParams {
   int rows, H, S, D;
   float scale_log2e;     // (d_head ^ -0.25)^2 * log2(e)
   int lds_pad;           // LDS the streaming blocks claim without using it (occupancy cap while decode lanes overlap)
+  int full_lines;        // how the streaming blocks ask for xa (ccx_xs_full_lines_switch): 0 half lines, 1 full lines
 };
+
+// CCX_XS_FULL_LINES (default 1; read per decode and per call of the stand-alone operator): the value for XsParams::full_lines
+int ccx_xs_full_lines_switch();
 
 // key ranges per row, each streamed by a block of its own (fixed: a row's arithmetic must not depend on the launch)
 #define XS_SPLIT 2

@@ -337,17 +337,30 @@ __global__ __launch_bounds__(256) void dec_xv_project_kernel(XsParams p) {
 // the streaming kernel
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace {
-template <int D, int RB = 1>
+// FL: how a wave asks for its quarter of a key tile -- 0: half lines (16 keys x 64 B per instruction, the score operand's own image),
+// 1: full lines (8 keys x 128 B per instruction; the score operand comes back from the staging strip).
+// The full-line loads carry the non-temporal hint: xa is read once per launch, one instruction asks for a whole line, and the L2s keep
+// the chain's activations and the GEMMs' W panels (768-sequence decode step 5.20 -> 4.93 ms, pipeline step 550 -> 533 ms against the
+// same form with cacheable loads, which -DCCX_XS_FULL_NT=0 builds; profiles/xs_full_lines_experiment.txt).
+#ifndef CCX_XS_FULL_NT
+#define CCX_XS_FULL_NT 1
+#endif
+template <int D, int RB = 1, int FL = 0>
 struct XsGeom {
   static constexpr int FW = D / 4;             // features per wave
   static constexpr int NKS = FW / 32;          // k-steps of a wave's partial scores
   static constexpr int NMT = FW / 16;          // M tiles of a wave's context slice
   static constexpr int PF = 4;                 // key tiles a wave keeps in flight (in situ, 768 sequences in 3 lanes: 2 -> 5.92, 3 -> 5.70, 4 -> 5.65, 6 -> 6.0 ms per step)
   static constexpr int RS = 2 * FW + 32;       // bytes per staged key row: +32 makes the transposed reads of 8 rows hit 64 different banks
-  static constexpr int STRIP = 16 * RS;        // one wave's staging strip (private: no barrier)
-  static constexpr int S_OFF = 4 * STRIP;      // partial-score exchange: [2 buffers][RB rows][4 waves][64 lanes] f32x4
+  static constexpr int STRIP = 16 * RS;        // one staging strip (private to a wave: no barrier)
+  static constexpr int NSTRIP = FL ? 2 : 1;    // strips per wave; full lines: tile t + 1 is written while tile t is consumed
+  static constexpr int S_OFF = 4 * NSTRIP * STRIP;   // partial-score exchange: [2 buffers][RB rows][4 waves][64 lanes] f32x4
   static constexpr int LDS = S_OFF + 2 * RB * 4 * 1024;
+  static_assert(!FL || (D / 2) % 128 == 0, "full lines: a wave's quarter of a key row must be whole 128-byte lines");
+  static_assert(!FL || PF % 2 == 0, "full lines: the strip of a tile is the parity of its slot");
 };
+// widths whose quarter rows are whole lines take the full-line form when it is asked for
+template <int D> constexpr bool xs_full_lines_ok = (D / 2) % 128 == 0;
 }  // namespace
 
 // One block per (row, key half): XS_SPLIT = 2 blocks per sequence, ALWAYS -- a CU pulls ~25 GB/s whatever its occupancy, so the kernel
@@ -355,27 +368,39 @@ struct XsGeom {
 // 768 half-rows every CU gets three (the split is fixed so that a row's arithmetic never depends on the launch).  Two blocks per CU.
 // The four waves work on the SAME 16-key tile of xa, each on its quarter of the
 // D features (wave w: features [w D/4, (w+1) D/4)):
-//   1. the wave's quarter of the tile is requested PF = 4 tiles ahead into named register images (D/128 16-byte loads per lane and
-//      tile: lane = key l%16, feature chunk l/16 -- the MFMA A-operand image of S^T = xa_tile q'^T; the block's loads of one tile
-//      cover 24 KB of contiguous memory; cacheable loads: with the non-temporal hint the two 64-byte halves of a line, which two
-//      consecutive instructions ask for, cost 15 % of the rate),
+//   1. the wave's quarter of the tile is requested PF = 4 tiles ahead into named register images, D/128 16-byte loads per lane and
+//      tile (the block's loads of one tile cover 24 KB of contiguous memory), in one of two forms (FL, CCX_XS_FULL_LINES):
+//      FULL LINES (the default where D/2 bytes are whole lines: D = 256, 512, 768): lane = key l/8 (+ 8 for the odd instructions),
+//      16-byte chunk l%8 -- one instruction asks for 8 keys x one whole 128-byte line, with the non-temporal hint.  A CU pulls
+//      ~50 GB/s this way against ~36 GB/s in half lines, which is what counts whenever the kernel shares the CUs (160 CUs: 128
+//      against 164 us per 256-row launch; alone on all 256 CUs 98 against 109 us with the hint, which then costs nothing because a
+//      line is asked for once).  The image goes to one of the wave's TWO staging strips at its (key, chunk) position -- tile t + 1
+//      is written between the softmax and the context MFMAs of tile t -- and the score operand of k-step ks comes back with one
+//      ds_read_b128 from key l%16, chunk l/16 + 4 ks: the same 16 bytes in the same lane as in the other form;
+//      HALF LINES (D = 128, 384; CCX_XS_FULL_LINES=0): lane = key l%16, feature chunk l/16 -- the MFMA A-operand image of
+//      S^T = xa_tile q'^T itself, so the scores need no staging; the two 64-byte halves of a line come with two consecutive
+//      instructions (cacheable loads: with the non-temporal hint the halves no longer meet in the L2, -15 % of the rate).
+//      Both forms run the same MFMAs in the same order on the same values in the same lanes: bit-identical,
 //   2. partial scores over the wave's features: D/128 v_mfma_f32_16x16x32_bf16 against its slice of q' (registers, loaded once),
 //   3. the four partial S^T [16 keys x 16 heads] meet in LDS (one barrier per tile, two buffers) and every wave adds them in the
 //      same order, so all four hold the same scores and run the same softmax: base 2, against a FIXED reference (the maximum of
 //      the row's first tile, see below) -- nothing is ever rescaled and the waves never exchange anything else,
-//   4. the wave's quarter tile goes to its private LDS strip as it came ([key][feature], 32 B of row padding) and comes back
+//   4. the wave's quarter tile goes to its private LDS strip ([key][feature], 32 B of row padding; half lines: as it came, after the
+//      score MFMAs; full lines: see 1 -- eight lanes write one key row's 128 contiguous bytes, conflict-free) and comes back
 //      TRANSPOSED through ds_read_b64_tr_b16 as the A operand of ctx^T [16 features x 16 heads] += xa_tile^T p^T -- D/64
 //      v_mfma_f32_16x16x16_bf16 whose B operand (4 keys x 1 head per lane) is exactly what the S^T accumulator holds after exp2.
-// ~200 registers, 35 KB of LDS: two blocks per CU, 8 waves x 4 tiles x 6 KB = 192 KB of loads in flight per CU.
+// D = 768: full lines 248 registers, 60 KB of LDS (two strips per wave); half lines 224 registers, 34 KB; no scratch.  Either way
+// two blocks per CU, 8 waves x 4 tiles x 6 KB = 192 KB of loads in flight per CU.
 // The halves' partials (contexts relative to their own reference, reference, denominator) are merged by dec_xv_project_kernel.
 // Deterministic: a row's numbers depend on nothing but its own q' and xa.
 // RB > 1 (prompt prefill: p.rows_per_seq consecutive rows attend to ONE sequence's xa): a block takes RB rows of a sequence through
 // the same pass -- RB sets of q', scores, references and accumulators against one stream of tiles and one set of transposed reads;
-// per row the arithmetic is that of RB = 1, operation for operation.  One block per CU (RB = 4: ~430 registers).
-template <int D, int RB>
+// per row the arithmetic is that of RB = 1, operation for operation.  One block per CU (RB = 4, D = 768: 500 registers and 84 KB of LDS in the full-line form, no scratch).
+template <int D, int RB, int FL>
 __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsParams p) {
-  using G = XsGeom<D, RB>;
-  constexpr int FW = G::FW, NKS = G::NKS, NMT = G::NMT, PF = G::PF, RS = G::RS;
+  using G = XsGeom<D, RB, FL>;
+  constexpr int FW = G::FW, NKS = G::NKS, NMT = G::NMT, PF = G::PF, RS = G::RS, STRIP = G::STRIP;
+  constexpr bool FULL = FL != 0, NT_HINT = CCX_XS_FULL_NT != 0;
   extern __shared__ __attribute__((aligned(16))) char xs_smem[];
   const int unit = blockIdx.x / XS_SPLIT, sp = blockIdx.x % XS_SPLIT;
   // rows of this block: RB == 1: row = unit; RB > 1: sequence s = unit / groups, rows s * rows_per_seq + gi * RB + j
@@ -390,20 +415,34 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
   const int seq = p.row_seq ? p.row_seq[row0] : row0;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
   const int H = p.H, S = p.S;
-  char* strip = xs_smem + wave * G::STRIP;
+  char* strip = xs_smem + wave * (G::NSTRIP * STRIP);
   char* sbuf = xs_smem + G::S_OFF;
 
-  const bf16_t* Xp = p.X + (long)seq * p.x_seq_stride + wave * FW + g * 8;
+  // half lines: lane = key l % 16, 16-byte chunk l / 16 (+ 4 per instruction); full lines: lane = key l / 8 (+ 8 for the odd
+  // instructions), chunk l % 8 of the 128-byte line i / 2 of the wave's quarter row
+  const int lk = FULL ? lane >> 3 : r, lc = FULL ? lane & 7 : g;
+  const bf16_t* Xp = p.X + (long)seq * p.x_seq_stride + wave * FW + lc * 8;
   const int NTall = (S + 15) >> 4;
   const int T0 = NTall * sp / XS_SPLIT, NT = NTall * (sp + 1) / XS_SPLIT;      // this block's key tiles [T0, NT)
 
   bf16x8 img[PF][NKS];
   auto load_tile = [&](bf16x8 (&X)[NKS], int t) {
-    int key = t * 16 + r;
+    int key = t * 16 + lk;
     key = key < S ? key : S - 1;                 // the last tile's missing keys re-read the last row; their p is 0
     const bf16_t* src = Xp + (long)key * D;
+    if constexpr (FULL) {
+      int key8 = t * 16 + 8 + lk;
+      key8 = key8 < S ? key8 : S - 1;
+      const bf16_t* src8 = Xp + (long)key8 * D;
 #pragma unroll
-    for (int ks = 0; ks < NKS; ks++) X[ks] = *(const bf16x8*)(src + ks * 32);
+      for (int i = 0; i < NKS; i++) {
+        const bf16x8* a = (const bf16x8*)(((i & 1) ? src8 : src) + (i >> 1) * 64);
+        X[i] = NT_HINT ? __builtin_nontemporal_load(a) : *a;
+      }
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < NKS; ks++) X[ks] = *(const bf16x8*)(src + ks * 32);
+    }
   };
 #pragma unroll
   for (int j = 0; j < PF; j++)
@@ -432,7 +471,22 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
   const char* s_rd = sbuf + lane * 16;
   const float scale = p.scale_log2e;
 
-  auto tile = [&](const bf16x8 (&X)[NKS], int t, bool first) {
+  // full lines: a loaded image goes to strip `sel` at its (key, chunk) position -- eight consecutive lanes write the 128 contiguous
+  // bytes of one key row (no bank conflict; the half-line form's write is 2-way) -- and the score operand of k-step ks comes back
+  // from where the half-line form writes it (key r, chunk g + 4 ks): the same 16 bytes in the same lane
+  char* fl_wr = strip + lk * RS + lc * 16;
+  auto stage_full = [&](const bf16x8 (&X)[NKS], int sel) {
+#pragma unroll
+    for (int i = 0; i < NKS; i++) *(bf16x8*)(fl_wr + sel * STRIP + (i & 1) * (8 * RS) + (i >> 1) * 128) = X[i];
+  };
+  auto read_back = [&](bf16x8 (&X)[NKS], int sel) {
+#pragma unroll
+    for (int ks = 0; ks < NKS; ks++) X[ks] = *(const bf16x8*)(st_wr + sel * STRIP + ks * 64);
+  };
+
+  // X: the score operand of tile t; sel: the strip that holds (FULL) or takes (!FULL) the tile; next(): what a wave does between the
+  // softmax and the context MFMAs (FULL: tile t + 1 to the other strip)
+  auto tile = [&](const bf16x8 (&X)[NKS], int t, bool first, int sel, auto&& next) {
     const int boff = (t & 1) * (RB * 4096);
 #pragma unroll
     for (int jr = 0; jr < RB; jr++) {
@@ -445,8 +499,10 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
       *(f32x4*)(s_wr + boff + jr * 4096) = NKS > 1 ? sa + sb : sa;
     }
     // stage the quarter tile as it is (read back transposed below): private strip, the wave's own LDS operations stay in order
+    if constexpr (!FULL) {
 #pragma unroll
-    for (int ks = 0; ks < NKS; ks++) *(bf16x8*)(st_wr + ks * 64) = X[ks];
+      for (int ks = 0; ks < NKS; ks++) *(bf16x8*)(st_wr + ks * 64) = X[ks];
+    }
     __syncthreads();
     bf16x4 pb[RB];
     const int key0 = t * 16 + g * 4;             // lane: head r, keys 16 t + 4 g + j
@@ -470,9 +526,10 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
       const u32x2 pp = {pack_bf16x2(pv[0], pv[1]), pack_bf16x2(pv[2], pv[3])};
       pb[jr] = __builtin_bit_cast(bf16x4, pp);
     }
+    next();
 #pragma unroll
     for (int mt = 0; mt < NMT; mt++) {
-      const bf16x4 xt = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(tr_rd + mt * 32));
+      const bf16x4 xt = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(tr_rd + sel * STRIP + mt * 32));
 #pragma unroll
       for (int jr = 0; jr < RB; jr++) acc[jr][mt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(xt, pb[jr], acc[jr][mt], 0, 0, 0);
     }
@@ -501,13 +558,32 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
 #pragma unroll
       for (int mt = 0; mt < NMT; mt++) acc[jr][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
+    if constexpr (FULL) {
+      // the range's first tile to strip 0; from then on slot j holds tile t + PF of the tile in slot j - 1
+      if (T0 < NT) {
+        stage_full(img[0], 0);
+        if (T0 + PF < NT) load_tile(img[0], T0 + PF);
+      }
+    }
     for (int t0 = T0; t0 < NT; t0 += PF) {
 #pragma unroll
       for (int j = 0; j < PF; j++) {
         const int t = t0 + j;
         if (t < NT) {
-          tile(img[j], t, pass == 0 && t == T0);
-          if (t + PF < NT) load_tile(img[j], t + PF);
+          if constexpr (FULL) {
+            const int jn = (j + 1) % PF;           // the slot of tile t + 1
+            bf16x8 X[NKS];
+            read_back(X, j & 1);
+            tile(X, t, pass == 0 && t == T0, j & 1, [&]() {
+              if (t + 1 < NT) {
+                stage_full(img[jn], (j & 1) ^ 1);
+                if (t + 1 + PF < NT) load_tile(img[jn], t + 1 + PF);
+              }
+            });
+          } else {
+            tile(img[j], t, pass == 0 && t == T0, 0, []() {});
+            if (t + PF < NT) load_tile(img[j], t + PF);
+          }
         }
       }
     }
@@ -533,9 +609,26 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
 
 namespace {
 
+// the streaming launch of one load form
+template <int D, int FL>
+int launch_xs_stream(ccx_ctx* ctx, const XsParams& p, hipStream_t stream) {
+  using G = XsGeom<D, 1, FL>;
+  static ccx_lds_optin optin1, optin4;       // per device, race-free (ccx_common.h)
+  CCX_HIP(ctx, optin1.ensure(ctx->device, (const void*)dec_xs_stream_kernel<D, 1, FL>));
+  CCX_HIP(ctx, optin4.ensure(ctx->device, (const void*)dec_xs_stream_kernel<D, 4, FL>));
+  CCX_REQUIRE(ctx, p.lds_pad >= 0 && G::LDS + p.lds_pad <= 160 * 1024, "xs cross attention: LDS claim %d too large", p.lds_pad);
+  if (p.rows_per_seq > 1) {
+    const int units = p.rows / p.rows_per_seq * ccx_cdiv(p.rows_per_seq, 4);
+    constexpr int lds4 = XsGeom<D, 4, FL>::LDS;
+    hipLaunchKernelGGL((dec_xs_stream_kernel<D, 4, FL>), dim3(units * XS_SPLIT), dim3(256), lds4, stream, p);
+  } else {
+    hipLaunchKernelGGL((dec_xs_stream_kernel<D, 1, FL>), dim3(p.rows * XS_SPLIT), dim3(256), G::LDS + p.lds_pad, stream, p);
+  }
+  return CCX_OK;
+}
+
 template <int D>
 int launch_xs(ccx_ctx* ctx, const XsParams& p, hipStream_t stream) {
-  using G = XsGeom<D>;
   // p.lds_pad: dynamic LDS the streaming blocks claim without using it -- 64 KB leave ONE block per CU (which pulls the same ~25 GB/s
   // as two), so that the chain kernels of the other decode lanes find wave slots and a shorter memory queue on every CU: 768-sequence
   // decode step 6.25 -> 5.87 ms with two lanes.
@@ -544,10 +637,6 @@ int launch_xs(ccx_ctx* ctx, const XsParams& p, hipStream_t stream) {
   // and read xa beyond the encoded windows)
   CCX_REQUIRE(ctx, p.rows_per_seq <= 1 || p.row_seq != nullptr, "xs cross attention: rows_per_seq = %d needs row_seq", p.rows_per_seq);
   const bool multi = p.rows_per_seq > 1;
-  static ccx_lds_optin optin1, optin4;       // per device, race-free (ccx_common.h)
-  CCX_HIP(ctx, optin1.ensure(ctx->device, (const void*)dec_xs_stream_kernel<D, 1>));
-  CCX_HIP(ctx, optin4.ensure(ctx->device, (const void*)dec_xs_stream_kernel<D, 4>));
-  CCX_REQUIRE(ctx, p.lds_pad >= 0 && G::LDS + p.lds_pad <= 160 * 1024, "xs cross attention: LDS claim %d too large", p.lds_pad);
   CCX_REQUIRE(ctx, p.rows_per_seq <= 1 || p.rows % p.rows_per_seq == 0, "xs cross attention: %d rows are not a multiple of %d rows per sequence", p.rows, p.rows_per_seq);
   const dim3 small_grid(p.H, ccx_cdiv(p.rows, 16));
   const double wbytes = (double)p.H * 64 * D * 2;
@@ -567,13 +656,15 @@ int launch_xs(ccx_ctx* ctx, const XsParams& p, hipStream_t stream) {
   {
     ccx_prof_scope ps(ctx, stream, D == 768 ? (multi ? "dec_xs_stream_kernel<768,4>" : "dec_xs_stream_kernel<768,1>") : "dec_xs_stream_kernel", 4.0 * p.rows * 16 * (double)p.S * D,
                       (double)p.rows * ((double)p.S * D * 2 + p.H * D * 2.0 + XS_SPLIT * p.H * D * 4.0));
-    if (multi) {
-      const int units = p.rows / p.rows_per_seq * ccx_cdiv(p.rows_per_seq, 4);
-      constexpr int lds4 = XsGeom<D, 4>::LDS;
-      hipLaunchKernelGGL((dec_xs_stream_kernel<D, 4>), dim3(units * XS_SPLIT), dim3(256), lds4, stream, p);
+    // p.full_lines (CCX_XS_FULL_LINES): 0 = half-line loads, otherwise full lines; widths whose quarter rows are no whole lines
+    // (128, 384) have the half-line form only.  The forms are bit-identical.
+    int rc;
+    if constexpr (xs_full_lines_ok<D>) {
+      rc = p.full_lines ? launch_xs_stream<D, 1>(ctx, p, stream) : launch_xs_stream<D, 0>(ctx, p, stream);
     } else {
-      hipLaunchKernelGGL((dec_xs_stream_kernel<D, 1>), dim3(p.rows * XS_SPLIT), dim3(256), G::LDS + p.lds_pad, stream, p);
+      rc = launch_xs_stream<D, 0>(ctx, p, stream);
     }
+    if (rc != CCX_OK) return rc;
   }
   CCX_CHECK_LAUNCH(ctx);
   {
@@ -585,6 +676,11 @@ int launch_xs(ccx_ctx* ctx, const XsParams& p, hipStream_t stream) {
 }
 
 }  // namespace
+
+int ccx_xs_full_lines_switch() {
+  const char* e = getenv("CCX_XS_FULL_LINES");
+  return !e || atoi(e) != 0;
+}
 
 bool ccx_xs_supported(int D, int H) { return H >= 1 && H <= 16 && H * 64 == D && (D == 128 || D == 256 || D == 384 || D == 512 || D == 768); }
 
@@ -654,7 +750,8 @@ extern "C" int ccx_cross_attention_xa(ccx_ctx* ctx, const float* q_dev, const fl
   p.q = q_dev; p.WkT = d_wkt; p.xq = d_xq; p.X = xa_dev; p.x_seq_stride = (long)S * D; p.row_seq = d_rs; p.Wv = d_wv; p.bv = d_bv; p.out = d_out; p.part_o = d_po; p.part_ml = d_pml;
   p.rows = rows; p.H = H; p.S = S; p.D = D; p.scale_log2e = 0.125f * 1.4426950408889634f;
   p.rows_per_seq = rows_per_seq > 1 ? rows_per_seq : 0;
-  int rc = ccx_launch_xs_cross_attention(ctx, p, stream);
+  p.full_lines = ccx_xs_full_lines_switch();
+  int rc =ccx_launch_xs_cross_attention(ctx, p, stream);
   if (rc == CCX_OK) {
     const long n = (long)rows * D;
     hipLaunchKernelGGL(xs_bf16_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_out, out_dev, n);

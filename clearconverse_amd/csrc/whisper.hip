@@ -127,6 +127,7 @@ struct ccx_whisper {
   // that takes the K/V path (kv_ready = sequences valid since the last encode).
   static constexpr int kKvSeqs = 80;         // sequences the K/V caches of an X-stream instance hold (4.5 GB at small.en)
   bool xs_on = false, xs_active = false, xs_fuse_q = true;
+  int xs_full_lines = 1;                     // XsParams::full_lines; read per call (read_chain_switches)
   int last_cross_path = -1;                  // ccx_whisper_last_cross_path: 0 kv16, 1 kv_stream, 2 xa_stream
   int kv_cap = 0, kv_ready = 0;
   bf16_t *xq = nullptr, *pf_xq = nullptr;    // expanded queries [rows][H][D] (step rows, prefill rows)
@@ -671,11 +672,12 @@ static int project_cross_kv(ccx_whisper* w, int n, hipStream_t stream) {
 // The switches of the decode chain's form, read per call (tests flip them) by BOTH entry points that run dec_step -- decodes and
 // ccx_whisper_decoder_logits -- so that the teacher-forced logits always come from the chain a decode of the same size would run.
 // CCX_FUSE_CROSS_Q=0: the two-launch cross-attention query of <= 16 rows; CCX_DEC_LNFREE=0: round 3's X-stream query;
-// CCX_XS_FUSE_Q=0: that query as a launch of its own.
+// CCX_XS_FUSE_Q=0: that query as a launch of its own; CCX_XS_FULL_LINES=0: the streaming kernel's half-line loads (cross_x.h).
 static void read_chain_switches(ccx_whisper* w) {
   { const char* e = getenv("CCX_FUSE_CROSS_Q"); w->fuse_cross_q = e ? (atoi(e) != 0) : 1; }
   { const char* e = getenv("CCX_DEC_LNFREE"); w->lnfree = !(e && strcmp(e, "0") == 0); }
   { const char* e = getenv("CCX_XS_FUSE_Q"); w->xs_fuse_q = !e || atoi(e) != 0; }
+  w->xs_full_lines = ccx_xs_full_lines_switch();
 }
 // which cross attention a decode of B sequences uses, and the K/V it needs
 // (n_kv: the sequences whose K/V the rows read -- B itself, or the windows of a mapped decode)
@@ -1013,6 +1015,7 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
       xp.rows = B; xp.H = H; xp.S = d.n_audio_ctx; xp.D = D; xp.scale_log2e = scale_log2e;
       xp.lds_pad = (w->cross_lds_pad > 0 && !pre) ? 65536 : 0;
       xp.rows_per_seq = pre ? prefill_rows : 0;
+      xp.full_lines = w->xs_full_lines;
       CCX_TRY(ccx_launch_xs_cross_attention(ctx, xp, stream));
       if (xs_fused && pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
       stamp(2, 1);
@@ -1555,7 +1558,7 @@ static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
       const int ns_key = cross_split(lanes[i].B, w->d.n_text_head, w->cross_stream != 0);
       // ... and whether the step reads a row -> window map / a stream-id table (other launches, other kernel arguments)
       const int form = (w->fuse_cross_q ? 1 : 0) | ((w->xs_active ? 1 : 0) << 1) | ((w->xs_fuse_q ? 1 : 0) << 2) | ((w->lnfree ? 1 : 0) << 3) |
-                       ((w->map_on ? 1 : 0) << 4) | ((w->sid_on ? 1 : 0) << 5);
+                       ((w->map_on ? 1 : 0) << 4) | ((w->sid_on ? 1 : 0) << 5) | (w->xs_full_lines << 6);
       const std::array<int, 9> key = {lanes[i].b0, lanes[i].B, sample_len, max_prompt, w->sampling ? 1 : 0, ns_key, w->cross_lds_pad, form, i};
       auto it = w->graphs.find(key);
       if (it != w->graphs.end()) { lanes[i].exec = it->second; continue; }

@@ -30,12 +30,54 @@ def conflicts_b128(addr_of_lane):
     return worst, total  # total = LDS cycles for the instruction (4 if conflict-free)
 
 
+def conflicts_write_b128(addr_of_lane):
+    """ds_write_b128: eight groups of 8 contiguous lanes, bank = (addr/4) % 32 (a 16-byte store covers 4 banks)."""
+    worst = 1
+    for g0 in range(0, 64, 8):
+        slots = {}
+        for l in range(g0, g0 + 8):
+            a = addr_of_lane[l]
+            slots.setdefault((a // 16) % 8, set()).add(a)
+        worst = max(worst, max(len(v) for v in slots.values()))
+    return worst
+
+
+def conflicts_tr_b64(addr_of_lane):
+    """ds_read_b64_tr_b16 / ds_read_b64: two 32-lane halves, bank = (addr/4) % 64 (an 8-byte read covers 2 banks)."""
+    worst = 1
+    for h0 in (0, 32):
+        slots = {}
+        for l in range(h0, h0 + 32):
+            a = addr_of_lane[l]
+            slots.setdefault((a // 8) % 32, set()).add(a)
+        worst = max(worst, max(len(v) for v in slots.values()))
+    return worst
+
+
+def xs_strip(D):
+    """The staging strip of dec_xs_stream_kernel (csrc/cross_x.hip): [16 keys][RS = D/2 + 32 bytes].  Worst ways of the full-line
+    write (lane = key l/8 (+8), chunk l%8 of a 128-byte line), the half-line write (key l%16, chunk l/16 + 4 ks), the b128
+    read-back of the score operand at the half-line write's addresses, and the transposed read of the context operand."""
+    FW = D // 4
+    RS = 2 * FW + 32
+    NKS = FW // 32
+    w_full = max(conflicts_write_b128([((l >> 3) + 8 * (i & 1)) * RS + (i >> 1) * 128 + (l & 7) * 16 for l in range(64)]) for i in range(NKS))
+    half = [[(l & 15) * RS + ((l >> 4) + 4 * ks) * 16 for l in range(64)] for ks in range(NKS)]
+    w_half = max(conflicts_write_b128(a) for a in half)
+    r_back = max(conflicts_b128(a)[0] for a in half)
+    tr = max(conflicts_tr_b64([((l >> 4) * 4 + ((l & 15) >> 2)) * RS + (l & 3) * 8 + mt * 32 for l in range(64)]) for mt in range(FW // 16))
+    return RS, w_full, w_half, r_back, tr
+
+
 def swz128(row, chunk, key):
     """128-byte rows (8 chunks of 16 B). key(row) -> 3-bit xor."""
     return row * 128 + ((chunk ^ key(row)) & 7) * 16
 
 
 if __name__ == "__main__":
+    for D in (256, 512, 768):
+        RS, w_full, w_half, r_back, tr = xs_strip(D)
+        print(f"xs strip D={D} RS={RS}: full-line write {w_full}-way, half-line write {w_half}-way, b128 read-back {r_back}-way, transposed read {tr}-way")
     keyA = lambda r: (r >> 1) & 7
     # 16x16x32 operand, natural rows: lane l -> row l&15, chunk c0 + (l>>4)
     for c0 in (0, 4):

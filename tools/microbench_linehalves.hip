@@ -68,7 +68,7 @@ int main() {
   }
   // the same kernel on a stream restricted to N CUs (hipExtStreamCreateWithCUMask, the first N mask bits = N / 8 CUs of every XCD):
   // how many CUs does it take to pull the whole HBM rate, with half and with full lines, at 1 - 4 blocks per CU?
-  for (int ncu : {64, 96, 128, 160}) {
+  for (int ncu : {64, 96, 128, 160, 192, 256}) {
     unsigned mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int i = 0; i < ncu; i++) mask[i >> 5] |= 1u << (i & 31);
     hipStream_t st;

@@ -1,6 +1,8 @@
 """Stand-alone timing of the X-stream cross attention (csrc/cross_x.hip) through ccx_cross_attention_xa: per-launch HIP-event times
-of its three kernels for a range of row counts (one row per sequence), full small.en width.
-usage: python tools/xs_bench.py [rows ...]"""
+of its three kernels for a range of row counts (one row per sequence), full small.en width; the streaming kernel once per load form
+(CCX_XS_FULL_LINES = 0 half lines, 1 full lines; the operator reads the switch per call), `reps` timed launches each: mean and (min .. max).
+usage: python tools/xs_bench.py [rows ...]      XS_BENCH_FORMS=0,1 XS_BENCH_REPS=5 override the forms and the repetitions"""
+import os
 import sys
 import numpy as np
 import torch
@@ -21,20 +23,29 @@ def main():
     q = torch.randn(nmax, D, generator=g).cuda()
     out = torch.empty(nmax, D, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
+    forms = os.environ.get("XS_BENCH_FORMS", "0,1").split(",")
+    reps = int(os.environ.get("XS_BENCH_REPS", "5"))
+    names = {"0": "half lines", "1": "full lines"}
     for rows in rows_list:
-        for it in range(3):
-            if it == 2:
-                ctx.prof_enable(True)
-            ctx.check(lib.ccx_cross_attention_xa(ctx.handle, q.data_ptr(), wk.ctypes.data, wv.ctypes.data, bv.ctypes.data, xa.data_ptr(), None,
-                                                 0, rows, rows, H, S, out.data_ptr(), st))
-        torch.cuda.synchronize()
-        recs = ctx.prof_records()
-        ctx.prof_enable(False)
         line = f"rows {rows:4d}:"
-        for name, fl, by, ms in recs[-3:]:
-            line += f"  {name.split('<')[0][4:]} {ms * 1e3:7.1f} us"
-            if "stream" in name:
-                line += f" ({by / (ms * 1e-3) / 1e12:.2f} TB/s)"
+        for form in forms:
+            os.environ["CCX_XS_FULL_LINES"] = form
+            for it in range(2 + reps):
+                if it == 2:
+                    ctx.prof_enable(True)
+                ctx.check(lib.ccx_cross_attention_xa(ctx.handle, q.data_ptr(), wk.ctypes.data, wv.ctypes.data, bv.ctypes.data, xa.data_ptr(), None,
+                                                     0, rows, rows, H, S, out.data_ptr(), st))
+            torch.cuda.synchronize()
+            recs = ctx.prof_records()
+            ctx.prof_enable(False)
+            if form == forms[0]:
+                for name, fl, by, ms in recs[-3:]:
+                    if "stream" not in name:
+                        line += f"  {name.split('<')[0][4:]} {ms * 1e3:6.1f} us"
+            v = [(ms * 1e3, by) for name, fl, by, ms in recs if "stream" in name]
+            mean = sum(t for t, _ in v) / len(v)
+            line += f"  | {names.get(form, form)}: {mean:6.1f} us ({min(t for t, _ in v):.1f} .. {max(t for t, _ in v):.1f}; {v[0][1] / (mean * 1e-6) / 1e12:.2f} TB/s)"
+        os.environ.pop("CCX_XS_FULL_LINES", None)
         print(line, flush=True)
 
 if __name__ == "__main__":
