@@ -65,11 +65,13 @@ class DecAttnDesc(C.Structure):
         ("wq_host", C.c_void_p), ("bq", C.c_void_p),
         ("out", C.c_void_p), ("part_o", C.c_void_p), ("part_ml", C.c_void_p), ("q_x_out", C.c_void_p),
         ("q_elems", C.c_int64), ("kv_elems", C.c_int64), ("out_elems", C.c_int64), ("part_o_elems", C.c_int64),
-        ("part_ml_elems", C.c_int64), ("x_elems", C.c_int64), ("pend_elems", C.c_int64), ("q_x_out_elems", C.c_int64)]
+        ("part_ml_elems", C.c_int64), ("x_elems", C.c_int64), ("pend_elems", C.c_int64), ("q_x_out_elems", C.c_int64),
+        ("ind", C.POINTER(C.c_uint16)), ("ind_ld", C.c_int)]
 
 
 DEC_ATTN_SELF, DEC_ATTN_SPLIT, DEC_ATTN_STREAM, DEC_ATTN_PREFILL, DEC_ATTN_FUSED_Q, DEC_ATTN_TWO_LAUNCH_Q = range(6)
 DEC_ATTN_STREAM_MAPPED = 7       # (6 is no form)
+DEC_ATTN_SELF_IND = 8            # the self form through a cache indirection (beam search)
 
 
 class DecSeqState(C.Structure):
@@ -89,6 +91,28 @@ class DecSelectDesc(C.Structure):
         ("sample", C.c_int), ("temperature", C.c_float), ("seed", C.c_uint64), ("row0", C.c_int),
         ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64),
         ("stream_ids", C.POINTER(C.c_int))]
+
+
+class DecBeamDesc(C.Structure):
+    """ccx_dec_beam_desc (include/ccx.h): one beam-search step (top-k kernel + update kernel) on its own."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("ld", C.c_int64), ("n_vocab", C.c_int),
+        ("G", C.c_int), ("beam_size", C.c_int), ("max_candidates", C.c_int),
+        ("rules", C.POINTER(DecodeRules)), ("state", C.POINTER(DecSeqState)), ("sample_len", C.c_int),
+        ("hist", C.POINTER(C.c_int)), ("cur_tok", C.POINTER(C.c_int)), ("pos", C.POINTER(C.c_int)), ("n_done", C.POINTER(C.c_int)),
+        ("tok_emb", C.c_void_p), ("pos_emb", C.c_void_p), ("x", C.c_void_p), ("D", C.c_int),
+        ("ind", C.POINTER(C.c_uint16)), ("ind_ld", C.c_int),
+        ("fin_tok", C.POINTER(C.c_int)), ("fin_score", C.POINTER(C.c_float)), ("fin_n", C.POINTER(C.c_int)),
+        ("fin_count", C.POINTER(C.c_int)),
+        ("cand_id", C.POINTER(C.c_int)), ("cand_lp", C.POINTER(C.c_float)), ("tok_out", C.POINTER(C.c_int)),
+        ("parent_out", C.POINTER(C.c_int)),
+        ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64)]
+
+
+class BeamTrace(C.Structure):
+    """ccx_beam_trace (include/ccx.h): host buffers a traced ccx_whisper_decode_beam fills."""
+    _fields_ = [("n_steps", C.c_int), ("cand_id", C.POINTER(C.c_int32)), ("cand_lp", C.POINTER(C.c_float)),
+                ("tok", C.POINTER(C.c_int32)), ("parent", C.POINTER(C.c_int32)), ("score", C.POINTER(C.c_float))]
 
 
 class DecTokenProbsDesc(C.Structure):
@@ -181,6 +205,9 @@ PROTOTYPES = {
     "ccx_whisper_decode_greedy": (_i, [_vp, _i32p, _i32p, _i, _i, _i, _i32p, _i32p, _fp, _fp, _vp]),
     "ccx_dec_attention_desc": (_i, [_vp, _i, C.POINTER(DecAttnDesc), _vp]),
     "ccx_dec_select_step": (_i, [_vp, C.POINTER(DecSelectDesc), _vp]),
+    "ccx_dec_beam_step": (_i, [_vp, C.POINTER(DecBeamDesc), _vp]),
+    "ccx_whisper_decode_beam": (_i, [_vp, _i32p, _i32p, _i, _i, _i32p, _i, _i, _i, _i, _i32p, _i32p, _fp, _i32p, _fp,
+                                     C.POINTER(BeamTrace), _vp]),
     "ccx_dec_token_probs": (_i, [_vp, C.POINTER(DecTokenProbsDesc), _vp]),
     "ccx_dec_pick_probs": (_i, [_vp, C.POINTER(DecPickProbsDesc), _vp]),
     "ccx_align_op": (_i, [_vp, _i, C.POINTER(AlignDesc), _vp]),

@@ -22,8 +22,10 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
   if (!ctx) return CCX_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_attention_desc: desc is NULL");
-  CCX_REQUIRE(ctx, (form >= CCX_DEC_ATTN_SELF && form <= CCX_DEC_ATTN_TWO_LAUNCH_Q) || form == CCX_DEC_ATTN_STREAM_MAPPED, "ccx_dec_attention_desc: unknown form %d", form);
-  const bool is_self = form == CCX_DEC_ATTN_SELF, is_split = form == CCX_DEC_ATTN_SPLIT, is_mapped = form == CCX_DEC_ATTN_STREAM_MAPPED,
+  CCX_REQUIRE(ctx, (form >= CCX_DEC_ATTN_SELF && form <= CCX_DEC_ATTN_TWO_LAUNCH_Q) || form == CCX_DEC_ATTN_STREAM_MAPPED || form == CCX_DEC_ATTN_SELF_IND,
+              "ccx_dec_attention_desc: unknown form %d", form);
+  const bool is_ind = form == CCX_DEC_ATTN_SELF_IND;
+  const bool is_self = form == CCX_DEC_ATTN_SELF || is_ind, is_split = form == CCX_DEC_ATTN_SPLIT, is_mapped = form == CCX_DEC_ATTN_STREAM_MAPPED,
              is_stream = form == CCX_DEC_ATTN_STREAM || is_mapped;
   const bool is_prefill = form == CCX_DEC_ATTN_PREFILL, with_q = form == CCX_DEC_ATTN_FUSED_Q || form == CCX_DEC_ATTN_TWO_LAUNCH_Q;
   const bool partials = is_split || with_q;
@@ -36,7 +38,9 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
   const int64_t kv_need = (int64_t)n_seq * H * kv_T * 64;
   CCX_REQUIRE(ctx, kv_need <= d->kv_elems, "ccx_dec_attention_desc: k / v are read up to element %ld, kv_elems=%ld", (long)kv_need, (long)d->kv_elems);
   // rows -> sequences
-  if (is_self || is_split || is_prefill || is_mapped) {
+  if (is_ind) {
+    CCX_REQUIRE(ctx, d->row_seq == nullptr, "ccx_dec_attention_desc: row_seq is not taken by form %d (the rows read through ind)", form);
+  } else if (is_self || is_split || is_prefill || is_mapped) {
     if (d->row_seq)
       for (int i = 0; i < rows; i++)
         CCX_REQUIRE(ctx, d->row_seq[i] >= 0 && d->row_seq[i] < n_seq, "ccx_dec_attention_desc: row_seq[%d] = %d out of range [0, %d)", i, d->row_seq[i], n_seq);
@@ -60,6 +64,15 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
     CCX_REQUIRE(ctx, d->pos != nullptr, "ccx_dec_attention_desc: pos is NULL");
     for (int i = 0; i < rows; i++)
       CCX_REQUIRE(ctx, d->pos[i] >= 0 && d->pos[i] < kv_T, "ccx_dec_attention_desc: pos[%d] = %d out of range [0, kv_T = %d)", i, d->pos[i], kv_T);
+    if (is_ind) {
+      CCX_REQUIRE(ctx, d->ind != nullptr && d->ind_ld >= 1 && d->ind_ld <= kv_T, "ccx_dec_attention_desc: ind is NULL or ind_ld = %d out of range [1, kv_T = %d]", d->ind_ld, kv_T);
+      for (int i = 0; i < rows; i++) {
+        CCX_REQUIRE(ctx, d->pos[i] < d->ind_ld, "ccx_dec_attention_desc: pos[%d] = %d needs ind_ld > it (ind_ld = %d)", i, d->pos[i], d->ind_ld);
+        for (int t = 0; t <= d->pos[i]; t++)
+          CCX_REQUIRE(ctx, d->ind[(size_t)i * d->ind_ld + t] < n_seq, "ccx_dec_attention_desc: ind[%d][%d] = %d out of range [0, n_seq = %d)", i, t,
+                      (int)d->ind[(size_t)i * d->ind_ld + t], n_seq);
+      }
+    }
   } else {
     CCX_REQUIRE(ctx, d->pos == nullptr, "ccx_dec_attention_desc: pos is taken by the self form only");
     CCX_REQUIRE(ctx, d->T >= 1 && d->T <= kv_T, "ccx_dec_attention_desc: T = %d out of range [1, kv_T = %d]", d->T, kv_T);
@@ -118,6 +131,8 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
   int* d_pos = nullptr; int* d_rs = nullptr;
   if (is_self) { DO_HIP(sc.upload(&d_pos, d->pos, (size_t)rows)); ap.pos = d_pos; }
   if (d->row_seq) { DO_HIP(sc.upload(&d_rs, d->row_seq, (size_t)rows)); ap.row_seq = d_rs; }
+  unsigned short* d_ind = nullptr;
+  if (is_ind) { DO_HIP(sc.upload(&d_ind, (const unsigned short*)d->ind, (size_t)rows * d->ind_ld)); ap.ind = d_ind; ap.ind_ld = d->ind_ld; }
   bf16_t* d_wq = nullptr; float* d_q = nullptr;
   if (with_q) {
     const std::vector<bf16_t> packed = pack_mfma_rows(d->wq_host, 768, 768, 16);
@@ -243,6 +258,127 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   DO_HIP(hipMemcpy(d->cur_tok, d_cur, (size_t)B * 4, hipMemcpyDeviceToHost));
   DO_HIP(hipMemcpy(d->pos, d_pos, (size_t)B * 4, hipMemcpyDeviceToHost));
   DO_HIP(hipMemcpy(d->n_done, d_ndone, 4, hipMemcpyDeviceToHost));
+#undef DO_HIP
+  return CCX_OK;
+}
+
+extern "C" int ccx_dec_beam_step(ccx_ctx* ctx, const ccx_dec_beam_desc* d, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_beam_step: desc is NULL");
+  const int V = d->n_vocab, G = d->G, beam = d->beam_size, mc = d->max_candidates, D = d->D, SL = d->sample_len;
+  CCX_REQUIRE(ctx, beam >= 1 && beam <= kBeamMax, "ccx_dec_beam_step: beam_size = %d out of range [1, %d]", beam, kBeamMax);
+  CCX_REQUIRE(ctx, mc >= 1 && mc <= kBeamCandMax, "ccx_dec_beam_step: max_candidates = %d out of range [1, %d]", mc, kBeamCandMax);
+  CCX_REQUIRE(ctx, G >= 1 && (int64_t)G * beam <= 65536, "ccx_dec_beam_step: G = %d out of range (G * beam_size <= 65536)", G);
+  const int R = G * beam, K = beam + 1;
+  CCX_REQUIRE(ctx, V >= 4 && V % 4 == 0 && V <= 13 * 4096, "ccx_dec_beam_step: n_vocab = %d must be a multiple of 4 and <= 53248", V);
+  CCX_REQUIRE(ctx, d->ld >= V && d->ld % 4 == 0, "ccx_dec_beam_step: ld = %ld must be >= n_vocab and a multiple of 4", (long)d->ld);
+  CCX_REQUIRE(ctx, d->logits && ccx_aligned16(d->logits), "ccx_dec_beam_step: logits null or not 16-byte aligned");
+  CCX_REQUIRE(ctx, (int64_t)(R - 1) * d->ld + V <= d->logits_elems, "ccx_dec_beam_step: logits are read up to element %ld, logits_elems=%ld",
+              (long)((int64_t)(R - 1) * d->ld + V), (long)d->logits_elems);
+  CCX_REQUIRE(ctx, d->rules && d->state && d->hist && d->cur_tok && d->pos && d->n_done, "ccx_dec_beam_step: rules, state, hist, cur_tok, pos or n_done is NULL");
+  CCX_REQUIRE(ctx, d->ind && d->fin_tok && d->fin_score && d->fin_n && d->fin_count, "ccx_dec_beam_step: ind, fin_tok, fin_score, fin_n or fin_count is NULL");
+  CCX_REQUIRE(ctx, d->cand_id && d->cand_lp && d->tok_out && d->parent_out, "ccx_dec_beam_step: cand_id, cand_lp, tok_out or parent_out is NULL");
+  const ccx_decode_rules& r = *d->rules;
+  std::vector<unsigned char> mask;
+  CCX_TRY(ccx_build_suppress_mask(ctx, "ccx_dec_beam_step", &r, V, mask));
+  CCX_REQUIRE(ctx, r.no_speech >= 0 && r.timestamp_begin >= 0 && r.blank >= 0, "ccx_dec_beam_step: rules.no_speech, timestamp_begin or blank negative");
+  CCX_REQUIRE(ctx, SL >= 1 && SL <= 1024, "ccx_dec_beam_step: sample_len = %d out of range [1, 1024]", SL);
+  CCX_REQUIRE(ctx, d->ind_ld >= 1 && d->ind_ld <= 2048, "ccx_dec_beam_step: ind_ld = %d out of range [1, 2048]", d->ind_ld);
+  CCX_REQUIRE(ctx, D >= 4 && D % 4 == 0 && D <= 4096, "ccx_dec_beam_step: D = %d must be a multiple of 4 in [4, 4096]", D);
+  CCX_REQUIRE(ctx, d->tok_emb && d->pos_emb && d->x && ccx_aligned16(d->tok_emb) && ccx_aligned16(d->pos_emb) && ccx_aligned16(d->x),
+              "ccx_dec_beam_step: tok_emb, pos_emb or x null or not 16-byte aligned");
+  CCX_REQUIRE(ctx, (int64_t)V * D <= d->tok_emb_elems, "ccx_dec_beam_step: tok_emb is read up to element %ld, tok_emb_elems=%ld", (long)V * D, (long)d->tok_emb_elems);
+  CCX_REQUIRE(ctx, (int64_t)R * D <= d->x_elems, "ccx_dec_beam_step: x is written up to element %ld, x_elems=%ld", (long)R * D, (long)d->x_elems);
+  const int64_t pos_rows = d->pos_emb_elems / D;
+  for (int g = 0; g < G; g++) {
+    const ccx_dec_seq_state& s0 = d->state[(size_t)g * beam];
+    CCX_REQUIRE(ctx, d->fin_count[g] >= 0 && d->fin_count[g] <= mc, "ccx_dec_beam_step: fin_count[%d] = %d out of range [0, max_candidates = %d]", g, d->fin_count[g], mc);
+    for (int j = 0; j < beam; j++) {
+      const int b = g * beam + j;
+      const ccx_dec_seq_state& s = d->state[b];
+      CCX_REQUIRE(ctx, s.done == 0 || s.done == 1, "ccx_dec_beam_step: state[%d].done = %d must be 0 or 1", b, s.done);
+      CCX_REQUIRE(ctx, s.done == s0.done && s.n_gen == s0.n_gen && s.pos == s0.pos, "ccx_dec_beam_step: state[%d] differs from its window's first row in done, n_gen or pos", b);
+      CCX_REQUIRE(ctx, s.n_gen >= 0 && s.n_gen <= SL, "ccx_dec_beam_step: state[%d].n_gen = %d out of range [0, sample_len = %d]", b, s.n_gen, SL);
+      if (s.done) continue;
+      CCX_REQUIRE(ctx, s.n_gen < SL, "ccx_dec_beam_step: state[%d].n_gen = %d leaves no room in hist (sample_len = %d)", b, s.n_gen, SL);
+      CCX_REQUIRE(ctx, s.prompt_len >= 1 && s.pos == s.prompt_len - 1 + s.n_gen, "ccx_dec_beam_step: state[%d] is not in the sampling phase (pos = %d, prompt_len = %d, n_gen = %d)", b,
+                  s.pos, s.prompt_len, s.n_gen);
+      CCX_REQUIRE(ctx, s.pos + 1 < pos_rows, "ccx_dec_beam_step: state[%d].pos = %d, pos + 1 must be a row of pos_emb (%ld rows)", b, s.pos, (long)pos_rows);
+      CCX_REQUIRE(ctx, s.pos + 1 < d->ind_ld, "ccx_dec_beam_step: state[%d].pos = %d, pos + 1 must be a column of ind (ind_ld = %d)", b, s.pos, d->ind_ld);
+      CCX_REQUIRE(ctx, s.last_tok < V && s.pen_tok < V && s.last_ts_tok < V, "ccx_dec_beam_step: state[%d] holds a token id >= n_vocab", b);
+    }
+  }
+  const size_t lds = (size_t)beam * SL * 4 + ccx_align((size_t)beam * d->ind_ld * 2, 16);
+  CCX_REQUIRE(ctx, lds <= 48 * 1024, "ccx_dec_beam_step: beam_size %d x (sample_len %d, ind_ld %d) needs %zu bytes of LDS (at most 49152)", beam, SL, d->ind_ld, lds);
+
+#define DO_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return ccx_fail(ctx, CCX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+  ccx_op_scratch sc;
+  constexpr int kGuard = 16;                 // sentinel words behind the tables the update kernel writes row by row
+  const size_t n_hist = (size_t)R * SL, n_ind = (size_t)R * d->ind_ld, n_fin = (size_t)G * mc * SL;
+  std::vector<int> hist_h(n_hist + kGuard, 0x5a5a5a5a), fin_h(n_fin + kGuard, 0x5a5a5a5a);
+  std::vector<unsigned short> ind_h(n_ind + kGuard, 0x5a5a);
+  memcpy(hist_h.data(), d->hist, n_hist * 4);
+  memcpy(fin_h.data(), d->fin_tok, n_fin * 4);
+  memcpy(ind_h.data(), d->ind, n_ind * 2);
+  unsigned char* d_mask = nullptr; DecSeqState* d_state = nullptr;
+  int *d_cur = nullptr, *d_pos = nullptr, *d_hist = nullptr, *d_ndone = nullptr, *d_fin = nullptr, *d_finn = nullptr, *d_finc = nullptr;
+  int *d_cid = nullptr, *d_tok = nullptr, *d_par = nullptr;
+  float *d_fins = nullptr, *d_clp = nullptr;
+  unsigned short* d_ind = nullptr;
+  DO_HIP(sc.upload(&d_mask, mask.data(), mask.size()));
+  DO_HIP(sc.upload(&d_state, (const DecSeqState*)d->state, (size_t)R));
+  DO_HIP(sc.upload(&d_cur, d->cur_tok, (size_t)R));
+  DO_HIP(sc.upload(&d_pos, d->pos, (size_t)R));
+  DO_HIP(sc.upload(&d_hist, hist_h.data(), hist_h.size()));
+  DO_HIP(sc.upload(&d_ndone, d->n_done, (size_t)1));
+  DO_HIP(sc.upload(&d_ind, ind_h.data(), ind_h.size()));
+  DO_HIP(sc.upload(&d_fin, fin_h.data(), fin_h.size()));
+  DO_HIP(sc.upload(&d_fins, d->fin_score, (size_t)G * mc));
+  DO_HIP(sc.upload(&d_finn, d->fin_n, (size_t)G * mc));
+  DO_HIP(sc.upload(&d_finc, d->fin_count, (size_t)G));
+  DO_HIP(sc.alloc(&d_cid, (size_t)R * K));
+  DO_HIP(sc.alloc(&d_clp, (size_t)R * K));
+  DO_HIP(sc.alloc(&d_tok, (size_t)R));
+  DO_HIP(sc.alloc(&d_par, (size_t)R));
+  DO_HIP(hipMemsetAsync(d_cid, 0xFF, (size_t)R * K * 4, stream));
+  DO_HIP(hipMemsetAsync(d_clp, 0xFF, (size_t)R * K * 4, stream));
+  DO_HIP(hipMemsetAsync(d_tok, 0xFF, (size_t)R * 4, stream));
+  DO_HIP(hipMemsetAsync(d_par, 0xFF, (size_t)R * 4, stream));
+
+  DecBeamParams bp;
+  memset(&bp, 0, sizeof(bp));
+  DecSelectParams& sp = bp.sel;
+  sp.logits = (const float*)d->logits; sp.ld_logits = (long)d->ld; sp.n_vocab = V; sp.state = d_state;
+  sp.cur_tok = d_cur; sp.pos = d_pos; sp.gen = d_hist; sp.sample_len = SL;
+  sp.n_done = d_ndone; sp.suppress_mask = d_mask; sp.eot = r.eot; sp.blank = r.blank;
+  sp.no_speech = r.no_speech; sp.timestamp_begin = r.timestamp_begin;
+  sp.max_initial_ts = r.max_initial_timestamp_index;
+  sp.tok_emb = (const float*)d->tok_emb; sp.pos_emb = (const float*)d->pos_emb; sp.x = (float*)d->x; sp.D = D;
+  bp.beam = beam; bp.max_cand = mc; bp.cand_id = d_cid; bp.cand_lp = d_clp; bp.ind = d_ind; bp.ind_ld = d->ind_ld; bp.row0 = 0;
+  bp.fin_tok = d_fin; bp.fin_score = d_fins; bp.fin_n = d_finn; bp.fin_count = d_finc; bp.step_tok = d_tok; bp.step_parent = d_par;
+  CCX_TRY(ccx_launch_dec_beam(ctx, bp, G, stream));
+  DO_HIP(hipStreamSynchronize(stream));
+  DO_HIP(hipMemcpy(hist_h.data(), d_hist, hist_h.size() * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(fin_h.data(), d_fin, fin_h.size() * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(ind_h.data(), d_ind, ind_h.size() * 2, hipMemcpyDeviceToHost));
+  for (int i = 0; i < kGuard; i++)
+    if (hist_h[n_hist + i] != 0x5a5a5a5a || fin_h[n_fin + i] != 0x5a5a5a5a || ind_h[n_ind + i] != 0x5a5a)
+      return ccx_fail(ctx, CCX_ERR_STATE, "ccx_dec_beam_step: a kernel wrote behind the hist, fin_tok or ind table (word %d)", i);
+  memcpy(d->hist, hist_h.data(), n_hist * 4);
+  memcpy(d->fin_tok, fin_h.data(), n_fin * 4);
+  memcpy(d->ind, ind_h.data(), n_ind * 2);
+  DO_HIP(hipMemcpy(d->state, d_state, (size_t)R * sizeof(DecSeqState), hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->cur_tok, d_cur, (size_t)R * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->pos, d_pos, (size_t)R * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->n_done, d_ndone, 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->fin_score, d_fins, (size_t)G * mc * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->fin_n, d_finn, (size_t)G * mc * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->fin_count, d_finc, (size_t)G * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->cand_id, d_cid, (size_t)R * K * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->cand_lp, d_clp, (size_t)R * K * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->tok_out, d_tok, (size_t)R * 4, hipMemcpyDeviceToHost));
+  DO_HIP(hipMemcpy(d->parent_out, d_par, (size_t)R * 4, hipMemcpyDeviceToHost));
 #undef DO_HIP
   return CCX_OK;
 }

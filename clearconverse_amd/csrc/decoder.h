@@ -67,6 +67,10 @@ struct DecAttnParams {
   // prefill kernels take a group's sequence from row_seq instead of from the block index (the mapped instantiations).  The split-KV
   // kernel reads row_seq either way.  (Last, in the struct's tail padding: no other field moves.)
   int kv_map;
+  // beam search (ccx_whisper_decode_beam): self attention through a cache indirection -- key t of row r is read from cache slot
+  // ind[r * ind_ld + t] instead of slot r (dec_attention_kernel<true, true>).  Null: the unflagged kernels.  (Appended: no other
+  // field moves; the kernel argument block of every attention kernel grows by these 16 bytes.)
+  const unsigned short* ind; int ind_ld;
 };
 int ccx_launch_dec_attention(ccx_ctx* ctx, const DecAttnParams& p, int B, int nsplit, bool final_out, hipStream_t stream);
 // Cross attention of a small batch (B <= 16 rows) WITH its query projection: replaces ln_linear(Wcq) + ccx_launch_dec_attention(split
@@ -98,6 +102,25 @@ struct DecSelectParams {
   const int* stream_id;   // sampling kernel only: [B] noise stream of every row instead of row0 + b (null: row0 + b)
 };
 int ccx_launch_dec_select(ccx_ctx* ctx, const DecSelectParams& p, int B, hipStream_t stream);
+
+// Beam search head of a step (dec_beam.hip; openai-whisper decoding.py::BeamSearchDecoder.update restated in tests/beam_reference.py).
+// Rows are grouped in windows of `beam` consecutive rows.  dec_beam_topk_kernel (one block per row) writes every row's top beam + 1
+// (id, log-probability) pairs of the filtered logits; dec_beam_update_kernel (one block per window) ranks the window's candidates,
+// walks them, and rewrites the rows in place: state, token history, cache-indirection rows, next embedding, finished tables.
+constexpr int kBeamMax = 8;            // rows per window
+constexpr int kBeamCandMax = 16;       // finished hypotheses kept per window (max_candidates)
+struct DecBeamParams {
+  DecSelectParams sel;                 // logits, state, cur_tok, pos, gen (= the rows' token histories), n_done, rules, embeddings
+  int beam, max_cand;
+  int* cand_id; float* cand_lp;        // [rows][beam + 1]: the proposals of this step (id -1: none)
+  unsigned short* ind; int ind_ld;     // [rows][ind_ld] cache slots of every row's keys (absolute rows of the launch's row 0 = slot 0)
+  int row0;                            // ... the slot of this launch's first row
+  int* fin_tok; float* fin_score; int* fin_n; int* fin_count;   // [windows][max_cand][sample_len], [windows][max_cand] x 2, [windows]
+  int* step_tok; int* step_parent;     // [rows] or null: this step's chosen token and source row (-1: the window did not step)
+  // test aid (null: off), indexed [step = tokens sampled so far][row]: proposals, chosen (token, parent) and cumulative score
+  int* tr_cand_id; float* tr_cand_lp; int* tr_tok; int* tr_parent; float* tr_score; int tr_rows;
+};
+int ccx_launch_dec_beam(ccx_ctx* ctx, const DecBeamParams& p, int n_windows, hipStream_t stream);
 int ccx_launch_dec_embed(ccx_ctx* ctx, const float* tok_emb, const float* pos_emb, const int* cur_tok, const int* pos,
                          float* x, int B, int D, hipStream_t stream);
 // Softmax of logit rows over the ids [lo, hi) only (dec_probs.hip; everything else counts as -inf): argmax[row] (lowest id on equal

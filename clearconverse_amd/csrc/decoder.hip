@@ -718,7 +718,11 @@ __device__ __forceinline__ void soft_merge_waves(const float (&sm_m)[4][8], cons
 
 // A wave owns 64-key chunks and issues all 16 K/V loads of a chunk before touching the data, so one
 // HBM round trip covers the chunk.
-template <bool FINAL>
+// IND (beam search, self attention only): key t of row b is read from cache slot ind[b][t] instead of slot sq -- a hypothesis that moved
+// to another row keeps reading the K/V its ancestors wrote, no cache row is ever copied.  A chunk's 8 slot entries are requested
+// before any of its K/V loads (they are the head of a dependent chain: one more round trip per 64-key chunk, out of L2).  The
+// unflagged instantiations are the kernels they always were.
+template <bool FINAL, bool IND = false>
 __global__ __launch_bounds__(256) void dec_attention_kernel(DecAttnParams p) {
   __shared__ float sm_m[4][8], sm_l[4][8], sm_o[4][8][8];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -741,6 +745,26 @@ __global__ __launch_bounds__(256) void dec_attention_kernel(DecAttnParams p) {
 
   for (int base = kbeg + wave * 64; base < kend; base += 256) {
     bf16x8 kf[8], vf[8];
+    if (IND) {
+      const unsigned short* ir = p.ind + (long)b * p.ind_ld;
+      const bf16_t* K0 = p.k + 8 * c;
+      const bf16_t* V0 = p.v + 8 * c;
+      int key[8]; unsigned slot[8];
+#pragma unroll
+      for (int it = 0; it < 8; it++) {
+        key[it] = base + it * 8 + g;
+        key[it] = key[it] < kend ? key[it] : kend - 1;
+        slot[it] = ir[key[it]];
+      }
+#pragma unroll
+      for (int it = 0; it < 8; it++) {
+        const long off = (((long)slot[it] * p.H + h) * p.kv_T + key[it]) * 64;
+        kf[it] = *(const bf16x8*)(K0 + off);
+        vf[it] = *(const bf16x8*)(V0 + off);
+      }
+      soft_update<8>(st, q, kf, vf, base, g, kend, p.scale_log2e);
+      continue;
+    }
     // (not kv_load: its K-first order costs this kernel a VGPR less and other SGPRs, and its register figures are pinned)
 #pragma unroll
     for (int it = 0; it < 8; it++) {
@@ -1188,6 +1212,10 @@ int ccx_launch_dec_attention(ccx_ctx* ctx, const DecAttnParams& p, int B, int ns
     k = (p.kv_map && p.row_seq) ? &streaming_map[npi] : &streaming[npi];
     lds = pad;
     CCX_HIP(ctx, k->optin.ensure(ctx->device, (const void*)k->fn, 128 * 1024));
+  } else if (p.ind) {
+    static DecAttnKernel self_ind = {"dec_attention_kernel<true,true> (self, indirect)", dec_attention_kernel<true, true>};
+    CCX_REQUIRE(ctx, p.pos && final_out && !p.row_seq && p.ind_ld >= 1, "dec_attention: the cache indirection is taken by the self attention of a decode step only");
+    k = &self_ind;
   } else {
     k = &split_kv[p.pos != nullptr][final_out];
     if (!final_out) lds = pad;

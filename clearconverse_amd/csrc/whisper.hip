@@ -6,6 +6,7 @@
 // back/api.py:1286-1292, 1432-1438, 1474-1480).  Model semantics follow openai-whisper
 // model.py / decoding.py [UPSTREAM-RECALL -- not vendored in the reference]; the CPU restatement
 // the tests compare against is oracle/whisper_ref.py.
+#include <algorithm>
 #include <array>
 #include <atomic>
 #include <map>
@@ -108,6 +109,18 @@ struct ccx_whisper {
   bool map_on = false, sid_on = false;
   const int32_t* win_host = nullptr;
   int enc_B = 0;                             // windows of the last ccx_whisper_encode
+  // beam search (ccx_whisper_decode_beam; dec_beam.hip).  Allocated by the first beam decode, sized from max_batch; beam_on and the
+  // trace pointers hold for the duration of that call only.  beam_ind [max_batch][n_text_ctx]: cache slot of every row's self-attention
+  // keys; beam_cand_*: [max_batch][kBeamMax + 1] proposals of a step; beam_fin_*: the windows' finished hypotheses ([max_batch x
+  // kBeamCandMax] slots: at beam_size 1 every row is a window).
+  bool beam_on = false;
+  int beam_size = 0, beam_maxc = 0;
+  unsigned short* beam_ind = nullptr;
+  int *beam_cand_id = nullptr, *beam_fin_tok = nullptr, *beam_fin_n = nullptr, *beam_fin_count = nullptr;
+  float *beam_cand_lp = nullptr, *beam_fin_score = nullptr;
+  int *beam_tr_cid = nullptr, *beam_tr_tok = nullptr, *beam_tr_par = nullptr;    // per traced call (device), else null
+  float *beam_tr_clp = nullptr, *beam_tr_score = nullptr;
+  int beam_tr_rows = 0;
   // graph cache; decode runs on an internal stream when the caller hands over the legacy null
   // stream (stream capture is illegal there)
   std::map<std::array<int, 9>, hipGraphExec_t> graphs;
@@ -850,7 +863,24 @@ int dec_head(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     gp.A = dxn; gp.lda = D; gp.W = w->tok_emb_rm; gp.ldw = D; gp.M = B; gp.N = d.n_vocab; gp.K = D; gp.out = logits; gp.ldo = ld;
     CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, gp, stream));
   }
-  if (select) {
+  if (select && w->beam_on) {
+    // beam search: the row's top beam + 1 proposals, then one block per window ranks, walks and rewrites its rows in place
+    DecBeamParams bp;
+    memset(&bp, 0, sizeof(bp));
+    DecSelectParams& sp = bp.sel;
+    CCX_REQUIRE(ctx, b0 == 0 && B % w->beam_size == 0, "dec_head: a beam decode runs in one lane of whole windows");
+    sp.logits = logits; sp.ld_logits = ld; sp.n_vocab = w->V4; sp.state = w->state; sp.cur_tok = w->cur_tok; sp.pos = pos; sp.gen = w->gen;
+    sp.sample_len = sample_len; sp.n_done = n_done; sp.suppress_mask = w->suppress_mask; sp.eot = w->rules.eot; sp.blank = w->rules.blank;
+    sp.no_speech = w->rules.no_speech; sp.timestamp_begin = w->rules.timestamp_begin;
+    sp.max_initial_ts = w->rules.max_initial_timestamp_index;
+    sp.tok_emb = w->tok_emb_f32; sp.pos_emb = w->dec_pos; sp.x = w->dx; sp.D = D;
+    bp.beam = w->beam_size; bp.max_cand = w->beam_maxc; bp.cand_id = w->beam_cand_id; bp.cand_lp = w->beam_cand_lp;
+    bp.ind = w->beam_ind; bp.ind_ld = d.n_text_ctx; bp.row0 = 0;
+    bp.fin_tok = w->beam_fin_tok; bp.fin_score = w->beam_fin_score; bp.fin_n = w->beam_fin_n; bp.fin_count = w->beam_fin_count;
+    bp.tr_cand_id = w->beam_tr_cid; bp.tr_cand_lp = w->beam_tr_clp; bp.tr_tok = w->beam_tr_tok; bp.tr_parent = w->beam_tr_par;
+    bp.tr_score = w->beam_tr_score; bp.tr_rows = w->beam_tr_rows;
+    CCX_TRY(ccx_launch_dec_beam(ctx, bp, B / w->beam_size, stream));
+  } else if (select) {
     DecSelectParams sp;
     memset(&sp, 0, sizeof(sp));
     sp.logits = logits; sp.ld_logits = ld; sp.n_vocab = w->V4; sp.state = w->state + b0; sp.prompt = w->prompt + ro * max_prompt;
@@ -980,6 +1010,8 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     memset(&ap, 0, sizeof(ap));
     ap.q = dq; ap.k = L.selfK + self_off; ap.v = L.selfV + self_off; ap.H = H; ap.kv_T = Tc; ap.pos = pos; ap.scale_log2e = scale_log2e;
     ap.out_bf16 = dattn; ap.row_seq = row_seq;
+    // beam search: a step's keys come through the cache indirection (the prefill writes and reads every row's own slot)
+    if (w->beam_on && !pre) { ap.ind = w->beam_ind; ap.ind_ld = Tc; }
     CCX_TRY(ccx_launch_dec_attention(ctx, ap, B, 1, true, stream));
     stamp(17, 2);
     if (lnfree) {
@@ -1420,9 +1452,17 @@ int ccx_whisper_decode_greedy(ccx_whisper* w, const int32_t* prompt_ids, const i
 
 // The decode behind ccx_whisper_decode (win == NULL: row r reads window r, noise stream r) and ccx_whisper_decode_rows (B rows over
 // n_windows encoded windows: row r reads window win[r]; sids, if given, names every row's noise stream).  Both checked by the callers.
+// beam != NULL (ccx_whisper_decode_beam): the B rows are beam->G windows of beam->beam rows over the map; tokens_out / n_tokens_out /
+// sum_logprob_out are then [G][C][sample_len] / [G][C] / [G][C] and no_speech_prob_out [G].
+struct BeamCall {
+  int G, beam, maxc;
+  int32_t* n_hyp_out;
+  const ccx_beam_trace* trace;
+};
 static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B, int sample_len,
                        float temperature, uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out,
-                       float* no_speech_prob_out, void* stream_, const int32_t* win, int n_windows, const int32_t* sids) {
+                       float* no_speech_prob_out, void* stream_, const int32_t* win, int n_windows, const int32_t* sids,
+                       const BeamCall* beam = nullptr) {
   if (!w) return CCX_ERR_ARG;
   CCX_REQUIRE(w->ctx, temperature >= 0.f && temperature == temperature, "decode: temperature must be >= 0");
   hipStream_t stream = (hipStream_t)stream_;
@@ -1460,7 +1500,16 @@ static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   read_chain_switches(w);
   CCX_TRY(select_cross_path(w, B, stream, win ? n_windows : -1));
   // the map and the ids: uploaded once per call (the state upload below synchronises), in force until the call returns
-  struct MapGuard { ccx_whisper* w; ~MapGuard() { w->map_on = false; w->sid_on = false; w->win_host = nullptr; } } map_guard{w};
+  struct MapGuard {
+    ccx_whisper* w;
+    ~MapGuard() {
+      w->map_on = false; w->sid_on = false; w->win_host = nullptr; w->beam_on = false;
+      if (w->beam_tr_cid) {
+        hipFree(w->beam_tr_cid); hipFree(w->beam_tr_clp); hipFree(w->beam_tr_tok); hipFree(w->beam_tr_par); hipFree(w->beam_tr_score);
+        w->beam_tr_cid = w->beam_tr_tok = w->beam_tr_par = nullptr; w->beam_tr_clp = w->beam_tr_score = nullptr;
+      }
+    }
+  } map_guard{w};
   if (win) {
     if (!w->row_win) {
       CCX_TRY(w->store.alloc(&w->row_win, (size_t)w->max_batch, true));
@@ -1471,10 +1520,46 @@ static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
     if (sids) CCX_HIP(ctx, hipMemcpyAsync(w->row_sid, sids, (size_t)B * 4, hipMemcpyHostToDevice, stream));
     w->map_on = true; w->sid_on = sids != nullptr; w->win_host = win;
   }
+  std::vector<unsigned short> ind_init;
+  if (beam) {
+    CCX_REQUIRE(ctx, prefill_on, "ccx_whisper_decode_beam: CCX_PREFILL=0 is not available to a beam decode (its kernels have no prompt phase)");
+    const int Tc = w->d.n_text_ctx;
+    if (!w->beam_ind) {
+      const size_t mb = (size_t)w->max_batch;
+      CCX_TRY(w->store.alloc(&w->beam_ind, mb * Tc, true));
+      CCX_TRY(w->store.alloc(&w->beam_cand_id, mb * (kBeamMax + 1), true));
+      CCX_TRY(w->store.alloc(&w->beam_cand_lp, mb * (kBeamMax + 1), true));
+      CCX_TRY(w->store.alloc(&w->beam_fin_tok, mb * kBeamCandMax * w->sample_cap, true));
+      CCX_TRY(w->store.alloc(&w->beam_fin_score, mb * kBeamCandMax, true));
+      CCX_TRY(w->store.alloc(&w->beam_fin_n, mb * kBeamCandMax, true));
+      CCX_TRY(w->store.alloc(&w->beam_fin_count, mb, true));
+    }
+    // after the prefill every row's keys are its own: ind[r][t] = r (the update kernel rewrites a row's entries from its parent's)
+    ind_init.resize((size_t)B * Tc);
+    for (int r = 0; r < B; r++)
+      for (int t = 0; t < Tc; t++) ind_init[(size_t)r * Tc + t] = (unsigned short)r;
+    CCX_HIP(ctx, hipMemcpyAsync(w->beam_ind, ind_init.data(), ind_init.size() * 2, hipMemcpyHostToDevice, stream));
+    CCX_HIP(ctx, hipMemsetAsync(w->beam_fin_count, 0, (size_t)beam->G * 4, stream));
+    if (beam->trace) {
+      const size_t n = (size_t)sample_len * B, K = (size_t)beam->beam + 1;
+      CCX_HIP(ctx, hipMalloc((void**)&w->beam_tr_cid, n * K * 4));
+      CCX_HIP(ctx, hipMalloc((void**)&w->beam_tr_clp, n * K * 4));
+      CCX_HIP(ctx, hipMalloc((void**)&w->beam_tr_tok, n * 4));
+      CCX_HIP(ctx, hipMalloc((void**)&w->beam_tr_par, n * 4));
+      CCX_HIP(ctx, hipMalloc((void**)&w->beam_tr_score, n * 4));
+      CCX_HIP(ctx, hipMemsetAsync(w->beam_tr_cid, 0xFF, n * K * 4, stream));
+      CCX_HIP(ctx, hipMemsetAsync(w->beam_tr_clp, 0xFF, n * K * 4, stream));
+      CCX_HIP(ctx, hipMemsetAsync(w->beam_tr_tok, 0xFF, n * 4, stream));
+      CCX_HIP(ctx, hipMemsetAsync(w->beam_tr_par, 0xFF, n * 4, stream));
+      CCX_HIP(ctx, hipMemsetAsync(w->beam_tr_score, 0xFF, n * 4, stream));
+      w->beam_tr_rows = B;
+    }
+    w->beam_on = true; w->beam_size = beam->beam; w->beam_maxc = beam->maxc;
+  }
   CCX_TRY(upload_decode_state(w, prompt_ids, prompt_lens, max_prompt, B, temperature, seed, stream, prefill));
   // steps still to run after the (eager) first one: the prefill already covers the prompt AND takes the first sample below
   const int total_steps = prefill ? sample_len : max_pl - 1 + sample_len;
-  const bool use_graph = getenv("CCX_NO_GRAPH") == nullptr;
+  const bool use_graph = getenv("CCX_NO_GRAPH") == nullptr && !(beam && beam->trace);   // (a traced beam decode: per-call buffers)
   const long ld = w->Vpad;
 
   // ---- lanes: row ranges [b0, b0 + Bl) stepping concurrently (CCX_DEC_LANES overrides the default) ----
@@ -1493,6 +1578,7 @@ static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
     else nl = B >= 640 ? 2 : (B >= 144 ? 3 : (B >= 96 ? 2 : 1));
     if (nl > ccx_whisper::kMaxLanes) nl = ccx_whisper::kMaxLanes;
     while (nl > 1 && B / nl < 16) nl--;
+    if (beam) nl = 1;      // a window's rows are rewritten by one block and counted by one n_done: one lane
   }
   const std::vector<hipStream_t>* extra = nullptr;
   if (nl > 1) {
@@ -1558,7 +1644,9 @@ static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
       const int ns_key = cross_split(lanes[i].B, w->d.n_text_head, w->cross_stream != 0);
       // ... and whether the step reads a row -> window map / a stream-id table (other launches, other kernel arguments)
       const int form = (w->fuse_cross_q ? 1 : 0) | ((w->xs_active ? 1 : 0) << 1) | ((w->xs_fuse_q ? 1 : 0) << 2) | ((w->lnfree ? 1 : 0) << 3) |
-                       ((w->map_on ? 1 : 0) << 4) | ((w->sid_on ? 1 : 0) << 5) | (w->xs_full_lines << 6);
+                       ((w->map_on ? 1 : 0) << 4) | ((w->sid_on ? 1 : 0) << 5) | ((w->xs_full_lines & 3) << 6) |
+                       // ... and a beam decode's head: other kernels, with beam_size and max_candidates in their arguments
+                       ((w->beam_on ? w->beam_size : 0) << 8) | ((w->beam_on ? w->beam_maxc : 0) << 12);
       const std::array<int, 9> key = {lanes[i].b0, lanes[i].B, sample_len, max_prompt, w->sampling ? 1 : 0, ns_key, w->cross_lds_pad, form, i};
       auto it = w->graphs.find(key);
       if (it != w->graphs.end()) { lanes[i].exec = it->second; continue; }
@@ -1648,6 +1736,59 @@ static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
   CCX_HIP(ctx, hipMemcpyAsync(st.data(), w->state, B * sizeof(DecSeqState), hipMemcpyDeviceToHost, stream));
   if (ns_at_sot) CCX_HIP(ctx, hipMemcpyAsync(ns_sot.data(), w->tp_prob, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
   CCX_HIP(ctx, hipMemcpyAsync(gen.data(), w->gen, gen.size() * 4, hipMemcpyDeviceToHost, stream));
+  if (beam) {
+    // BeamSearchDecoder.finalize: the finished hypotheses in insertion order, topped up with the live rows by descending score
+    const int G = beam->G, bs = beam->beam, mc = beam->maxc, C = bs > mc ? bs : mc, eot = w->rules.eot;
+    std::vector<int> fin_tok((size_t)G * mc * sample_len), fin_n((size_t)G * mc), fin_count(G);
+    std::vector<float> fin_score((size_t)G * mc);
+    CCX_HIP(ctx, hipMemcpyAsync(fin_tok.data(), w->beam_fin_tok, fin_tok.size() * 4, hipMemcpyDeviceToHost, stream));
+    CCX_HIP(ctx, hipMemcpyAsync(fin_n.data(), w->beam_fin_n, fin_n.size() * 4, hipMemcpyDeviceToHost, stream));
+    CCX_HIP(ctx, hipMemcpyAsync(fin_score.data(), w->beam_fin_score, fin_score.size() * 4, hipMemcpyDeviceToHost, stream));
+    CCX_HIP(ctx, hipMemcpyAsync(fin_count.data(), w->beam_fin_count, (size_t)G * 4, hipMemcpyDeviceToHost, stream));
+    CCX_HIP(ctx, hipStreamSynchronize(stream));
+    if (const ccx_beam_trace* tr = beam->trace) {
+      const size_t n = (size_t)sample_len * B, K = (size_t)bs + 1;
+      CCX_HIP(ctx, hipMemcpy(tr->cand_id, w->beam_tr_cid, n * K * 4, hipMemcpyDeviceToHost));
+      CCX_HIP(ctx, hipMemcpy(tr->cand_lp, w->beam_tr_clp, n * K * 4, hipMemcpyDeviceToHost));
+      CCX_HIP(ctx, hipMemcpy(tr->tok, w->beam_tr_tok, n * 4, hipMemcpyDeviceToHost));
+      CCX_HIP(ctx, hipMemcpy(tr->parent, w->beam_tr_par, n * 4, hipMemcpyDeviceToHost));
+      CCX_HIP(ctx, hipMemcpy(tr->score, w->beam_tr_score, n * 4, hipMemcpyDeviceToHost));
+    }
+    for (int g = 0; g < G; g++) {
+      int n_hyp = 0;
+      auto put = [&](const int* toks, int n, float score) {
+        const size_t at = (size_t)g * C + n_hyp;
+        for (int i = 0; i < sample_len; i++) tokens_out[at * sample_len + i] = i < n ? toks[i] : eot;
+        if (n_tokens_out) n_tokens_out[at] = n;
+        if (sum_logprob_out) sum_logprob_out[at] = score;
+        n_hyp++;
+      };
+      const int nf = fin_count[g] < mc ? fin_count[g] : mc;
+      for (int k = 0; k < nf; k++) {
+        const size_t slot = (size_t)g * mc + k;
+        put(&fin_tok[slot * sample_len], fin_n[slot], fin_score[slot]);
+      }
+      if (n_hyp < bs) {
+        std::vector<int> rows(bs);
+        for (int j = 0; j < bs; j++) rows[j] = g * bs + j;
+        std::stable_sort(rows.begin(), rows.end(), [&](int a, int b) { return st[a].sum_logprob > st[b].sum_logprob; });
+        for (int j = 0; j < bs && n_hyp < bs; j++) {
+          const int r = rows[j];
+          const int ng = st[r].n_gen < sample_len ? st[r].n_gen : sample_len;
+          put(&gen[(size_t)r * sample_len], ng, st[r].sum_logprob);
+        }
+      }
+      for (int k = n_hyp; k < C; k++) {          // unused slots: empty
+        const size_t at = (size_t)g * C + k;
+        for (int i = 0; i < sample_len; i++) tokens_out[at * sample_len + i] = eot;
+        if (n_tokens_out) n_tokens_out[at] = 0;
+        if (sum_logprob_out) sum_logprob_out[at] = 0.f;
+      }
+      if (beam->n_hyp_out) beam->n_hyp_out[g] = n_hyp;
+      if (no_speech_prob_out) no_speech_prob_out[g] = ns_at_sot ? ns_sot[(size_t)g * bs] : st[(size_t)g * bs].no_speech_prob;
+    }
+    return CCX_OK;
+  }
   CCX_HIP(ctx, hipStreamSynchronize(stream));
   for (int b = 0; b < B; b++) {
     const int ng = st[b].n_gen < sample_len ? st[b].n_gen : sample_len;
@@ -1688,6 +1829,41 @@ int ccx_whisper_decode_rows(ccx_whisper* w, const int32_t* prompt_ids, const int
   }
   return decode_impl(w, prompt_ids, prompt_lens, max_prompt, R, sample_len, temperature, seed, tokens_out, n_tokens_out, sum_logprob_out,
                      no_speech_prob_out, stream_, window_of_row, n_windows, stream_ids);
+}
+
+int ccx_whisper_decode_beam(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int G,
+                            const int32_t* window_of_group, int n_windows, int beam_size, int max_candidates, int sample_len,
+                            int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out, int32_t* n_hyp_out,
+                            float* no_speech_prob_out, const ccx_beam_trace* trace, void* stream_) {
+  if (!w) return CCX_ERR_ARG;
+  ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, w->finalized && w->rules_set, "ccx_whisper_decode_beam: not finalized or rules not set");
+  CCX_REQUIRE(ctx, beam_size >= 1 && beam_size <= kBeamMax, "ccx_whisper_decode_beam: beam_size = %d out of range [1, %d]", beam_size, kBeamMax);
+  CCX_REQUIRE(ctx, max_candidates >= 1 && max_candidates <= kBeamCandMax, "ccx_whisper_decode_beam: max_candidates = %d out of range [1, %d]", max_candidates,
+              kBeamCandMax);
+  CCX_REQUIRE(ctx, G >= 1 && (long)G * beam_size <= w->max_batch, "ccx_whisper_decode_beam: G = %d, G * beam_size must lie in [1, max_batch = %d]", G, w->max_batch);
+  CCX_REQUIRE(ctx, n_windows >= 1 && n_windows <= w->max_batch, "ccx_whisper_decode_beam: n_windows = %d out of range [1, max_batch = %d]", n_windows, w->max_batch);
+  CCX_REQUIRE(ctx, n_windows <= w->enc_B, "ccx_whisper_decode_beam: n_windows = %d, the last ccx_whisper_encode left %d windows", n_windows, w->enc_B);
+  CCX_REQUIRE(ctx, prompt_ids && prompt_lens && tokens_out && max_prompt >= 1 && max_prompt <= w->max_prompt_cap, "ccx_whisper_decode_beam: prompt_ids, prompt_lens or tokens_out is NULL, or max_prompt = %d out of range",
+              max_prompt);
+  CCX_REQUIRE(ctx, window_of_group || G <= n_windows, "ccx_whisper_decode_beam: window_of_group is NULL with more groups (%d) than windows (%d)", G, n_windows);
+  if (trace)
+    CCX_REQUIRE(ctx, trace->n_steps >= sample_len && trace->cand_id && trace->cand_lp && trace->tok && trace->parent && trace->score,
+                "ccx_whisper_decode_beam: trace.n_steps = %d below sample_len = %d, or a trace buffer is NULL", trace->n_steps, sample_len);
+  const int R = G * beam_size;
+  std::vector<int32_t> ids((size_t)R * max_prompt), lens(R), win(R);
+  for (int g = 0; g < G; g++) {
+    const int wg = window_of_group ? window_of_group[g] : g;
+    CCX_REQUIRE(ctx, wg >= 0 && wg < n_windows, "ccx_whisper_decode_beam: window_of_group[%d] = %d out of range [0, n_windows = %d)", g, wg, n_windows);
+    for (int j = 0; j < beam_size; j++) {
+      const int r = g * beam_size + j;
+      memcpy(&ids[(size_t)r * max_prompt], &prompt_ids[(size_t)g * max_prompt], (size_t)max_prompt * 4);
+      lens[r] = prompt_lens[g]; win[r] = wg;
+    }
+  }
+  const BeamCall bc{G, beam_size, max_candidates, n_hyp_out, trace};
+  return decode_impl(w, ids.data(), lens.data(), max_prompt, R, sample_len, 0.f, 0, tokens_out, n_tokens_out, sum_logprob_out, no_speech_prob_out,
+                     stream_, win.data(), n_windows, nullptr, &bc);
 }
 
 }  // extern "C"

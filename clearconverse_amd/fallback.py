@@ -7,7 +7,9 @@ tests/test_fallback_reference_cpu.py drives the same functions against tests/fal
 
 The walk, per window: the temperatures of the schedule in order; the window is accepted at the first temperature at which it needs no
 fallback, and at the last one whatever it scores.  At temperature 0 there is one row per window (best_of is dropped); above 0 with
-best_of = n there are n, ranked by mean log-probability.
+best_of = n there are n, ranked by mean log-probability.  On an instance built with `beam_search=True` a temperature-0 round with
+`beam_size` set decodes every window by beam search instead (`WhisperModel.decode_beam`), `beam_size` and `patience` are dropped above 0
+as `best_of` is at 0, and `length_penalty` applies to both.
 """
 from __future__ import annotations
 
@@ -59,15 +61,21 @@ def needs_fallback(compression: float, avg_logprob: float, no_speech_prob: float
     return need
 
 
-def rank_candidates(candidates: Sequence[dict], eot: int) -> int:
-    """[UPSTREAM-RECALL: decoding.py::MaximumLikelihoodRanker with length_penalty None] index of the candidate a window keeps:
-    tokens cut at the first eot, score = sum_logprob / len(tokens), an empty candidate scores -inf, the first maximum wins."""
+def rank_candidates(candidates: Sequence[dict], eot: int, length_penalty: Optional[float] = None) -> int:
+    """[UPSTREAM-RECALL: decoding.py::MaximumLikelihoodRanker] index of the candidate a window keeps: tokens cut at the first eot,
+    score = sum_logprob / len(tokens) with length_penalty None (the default: today's arithmetic), else sum_logprob /
+    ((5 + len) / 6) ** length_penalty (the Google NMT penalty); an empty candidate scores -inf, the first maximum wins."""
     best, best_score = 0, None
     for k, c in enumerate(candidates):
         toks = list(c["tokens"])
         if eot in toks:
             toks = toks[:toks.index(eot)]
-        score = c["sum_logprob"] / len(toks) if toks else -math.inf
+        if not toks:
+            score = -math.inf
+        elif length_penalty is None:
+            score = c["sum_logprob"] / len(toks)
+        else:
+            score = c["sum_logprob"] / (((5 + len(toks)) / 6) ** length_penalty)
         if best_score is None or score > best_score:
             best, best_score = k, score
     return best
@@ -94,10 +102,10 @@ def plan_round(failing: Sequence[int], prompts: Sequence[Sequence[int]], n_rows:
     return chunks
 
 
-def window_result(candidates: Sequence[dict], temperature: float, tokenizer, eot: int) -> dict:
+def window_result(candidates: Sequence[dict], temperature: float, tokenizer, eot: int, length_penalty: Optional[float] = None) -> dict:
     """What a window keeps of one round's rows [UPSTREAM-RECALL: DecodingTask.run / DecodingResult]: the ranker's pick, avg_logprob =
     sum_logprob / (n_tokens + 1), no_speech_prob of the group's FIRST row, compression_ratio of the pick's text."""
-    k = rank_candidates(candidates, eot)
+    k = rank_candidates(candidates, eot, length_penalty)
     c = candidates[k]
     toks = list(c["tokens"])
     if eot in toks:

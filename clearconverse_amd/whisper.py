@@ -281,14 +281,19 @@ class WindowLoop:
 
 class WhisperModel:
     temperature_fallback = False      # opt-in (the constructor's keyword)
+    beam_search = False               # opt-in too
 
     def __init__(self, dims: WhisperDims, state_dict: Dict[str, torch.Tensor], max_batch: int = 8,
                  device: int = 0, rules: Optional[DecodeRules] = None, tokenizer=None,
                  ctx: Optional[_lib.Context] = None, max_audio_seconds: float = 30.0,
                  share_encoder_scratch_with: Optional["WhisperModel"] = None, word_alignment: bool = False,
                  alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False,
-                 temperature_fallback: bool = False):
-        """temperature_fallback (default False: a tuple or list temperature raises, `best_of` and `compression_ratio_threshold` are
+                 temperature_fallback: bool = False, beam_search: bool = False):
+        """beam_search (default False: `beam_size`, `patience` and `length_penalty` are accepted and ignored, as before): with it,
+        `transcribe` / `transcribe_batch` honour them [UPSTREAM-RECALL: decoding.py::BeamSearchDecoder, transcribe.py::decode_with_fallback;
+        parity unpinned] -- a temperature-0 round with `beam_size` set decodes every window by beam search on the GPU (`decode_beam`),
+        `length_penalty` enters the ranker of beam and best_of rounds alike.
+        temperature_fallback (default False: a tuple or list temperature raises, `best_of` and `compression_ratio_threshold` are
         ignored, as before): with it, `transcribe` / `transcribe_batch` take a temperature schedule, `compression_ratio_threshold` and
         `best_of` and decode a window again, warmer, while it is too repetitive or too improbable (clearconverse_amd/fallback.py) --
         only the failing windows, over a row -> window map (`decode_rows`), nothing encoded again.
@@ -325,6 +330,7 @@ class WhisperModel:
         self.word_alignment = bool(word_alignment)
         self.word_probabilities = bool(word_probabilities)
         self.temperature_fallback = bool(temperature_fallback)
+        self.beam_search = bool(beam_search)
         if alignment_heads is None:
             alignment_heads = [(l, h) for l in range(dims.n_text_layer // 2, dims.n_text_layer) for h in range(dims.n_text_head)]
         self.alignment_heads = [(int(l), int(h)) for l, h in alignment_heads]
@@ -512,14 +518,67 @@ class WhisperModel:
                      avg_logprob=float(slp[b]) / (int(ntok[b]) + 1), no_speech_prob=float(nsp[b]),
                      cross_path=self.last_cross_path) for b in range(R)]
 
+    def decode_beam(self, prompts: Sequence[Sequence[int]], beam_size: int, patience: Optional[float] = None,
+                    sample_len: Optional[int] = None, windows: Optional[Sequence[int]] = None, n_windows: Optional[int] = None,
+                    trace: bool = False):
+        """Beam search at temperature 0 over the currently encoded windows (ccx_whisper_decode_beam) [UPSTREAM-RECALL:
+        decoding.py::BeamSearchDecoder]: prompts[g] is decoded on window windows[g] (None: window g) by beam_size rows that share the
+        window's encoder output; len(prompts) * beam_size <= max_batch.  patience (None: 1.0): a window is complete once
+        round(beam_size * patience) hypotheses have finished.  -> per prompt the list of its hypotheses in insertion order (finished
+        ones first, then live rows by descending score while fewer than beam_size finished): dicts of tokens (before the eot),
+        sum_logprob, avg_logprob, no_speech_prob (the window's), cross_path.  The ranker (`fallback.rank_candidates`) picks among them.
+        trace=True (a test aid; the steps then run eagerly): -> (results, dict of numpy arrays cand_id / cand_lp [steps, rows,
+        beam_size + 1], tok / parent / score [steps, rows]; rows = prompt-major; -1 / NaN where a window no longer stepped)."""
+        G, bs = len(prompts), int(beam_size)
+        if patience is not None and not (patience > 0):
+            raise _lib.CcxError("decode_beam: patience must be > 0")
+        mc = round(bs * (1.0 if patience is None else float(patience)))
+        mp = max(len(p) for p in prompts)
+        sample_len = sample_len or decode_cap(mp, self.dims.n_text_ctx)
+        ids = np.full((G, mp), self.rules.eot, dtype=np.int32)
+        lens = np.zeros(G, dtype=np.int32)
+        for g, p in enumerate(prompts):
+            ids[g, :len(p)] = p
+            lens[g] = len(p)
+        win = np.ascontiguousarray(windows, dtype=np.int32) if windows is not None else None
+        if win is not None and win.shape != (G,):
+            raise _lib.CcxError("decode_beam: one window per prompt")
+        nw = int(n_windows) if n_windows is not None else (int(win.max()) + 1 if win is not None else G)
+        Cn = max(bs, mc, 1)
+        toks = np.zeros((G, Cn, sample_len), dtype=np.int32)
+        ntok = np.zeros((G, Cn), dtype=np.int32)
+        slp = np.zeros((G, Cn), dtype=np.float32)
+        nhyp = np.zeros(G, dtype=np.int32)
+        nsp = np.zeros(G, dtype=np.float32)
+        i32p, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        tr, tr_c = None, None
+        if trace:
+            R, K = G * max(bs, 1), bs + 1
+            tr = dict(cand_id=np.full((sample_len, R, K), -1, dtype=np.int32), cand_lp=np.full((sample_len, R, K), np.nan, dtype=np.float32),
+                      tok=np.full((sample_len, R), -1, dtype=np.int32), parent=np.full((sample_len, R), -1, dtype=np.int32),
+                      score=np.full((sample_len, R), np.nan, dtype=np.float32))
+            tr_c = _lib.BeamTrace(sample_len, tr["cand_id"].ctypes.data_as(i32p), tr["cand_lp"].ctypes.data_as(fp),
+                                  tr["tok"].ctypes.data_as(i32p), tr["parent"].ctypes.data_as(i32p), tr["score"].ctypes.data_as(fp))
+        self.ctx.check(self.lib.ccx_whisper_decode_beam(
+            self.handle, ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), mp, G, win.ctypes.data_as(i32p) if win is not None else None,
+            nw, bs, mc, sample_len, toks.ctypes.data_as(i32p), ntok.ctypes.data_as(i32p), slp.ctypes.data_as(fp), nhyp.ctypes.data_as(i32p),
+            nsp.ctypes.data_as(fp), C.byref(tr_c) if tr_c is not None else None, _lib.current_stream_ptr()), "ccx_whisper_decode_beam")
+        self.last_cross_path = CROSS_PATHS.get(int(self.lib.ccx_whisper_last_cross_path(self.handle)), "unknown")
+        out = [[dict(tokens=toks[g, k, :ntok[g, k]].tolist(), sum_logprob=float(slp[g, k]),
+                     avg_logprob=float(slp[g, k]) / (int(ntok[g, k]) + 1), no_speech_prob=float(nsp[g]), cross_path=self.last_cross_path)
+                for k in range(int(nhyp[g]))] for g in range(G)]
+        return (out, tr) if trace else out
+
     def _decode_with_fallback(self, prompts, cap: int, schedule, best_of, compression_ratio_threshold, logprob_threshold,
-                              no_speech_threshold) -> List[dict]:
+                              no_speech_threshold, beam_size=None, patience=None, length_penalty=None) -> List[dict]:
         """The schedule walk of one encoded group [UPSTREAM-RECALL: transcribe.py::decode_with_fallback]: round 0 over every window,
         each later round one `decode_rows` (chunked to max_batch rows) over the windows still failing, times best_of above
         temperature 0.  Round 0 is a plain `decode` whenever it has one row per window, so a group whose windows all pass at the
         first temperature costs what it costs without a schedule.  One seed per round -- the chunks of a round are one decode split
         by capacity -- and stream ids from the window's place in the group: a window's outcome does not depend on which other
-        windows fell back.  -> one result per window: tokens, avg_logprob, no_speech_prob, temperature, compression_ratio."""
+        windows fell back.  beam_size (beam_search instances): a temperature-0 round is a beam search instead -- `decode_beam` over the
+        group's window map, max_batch // beam_size windows per call -- and best_of rounds above 0 stay what they are; length_penalty
+        enters the ranker of both.  -> one result per window: tokens, avg_logprob, no_speech_prob, temperature, compression_ratio."""
         walk = fallback.FallbackWalk(len(prompts), schedule, compression_ratio_threshold, logprob_threshold, no_speech_threshold)
         self.fallback_walks.append(walk)        # (tests replay every window's rounds from walk.trace)
         eot = self.rules.eot
@@ -530,7 +589,17 @@ class WhisperModel:
             self._sample_calls += 1
             seed = (int(self.sample_seed) << 32) + self._sample_calls
             cands: Dict[int, List[dict]] = {w: [] for w in failing}
-            if walk.round == 0 and n_rows == 1:
+            if t == 0.0 and beam_size is not None:
+                per_call = self.max_batch // int(beam_size)
+                if per_call < 1:
+                    raise _lib.CcxError(f"beam_size = {beam_size} exceeds max_batch = {self.max_batch}")
+                for at in range(0, len(failing), per_call):
+                    part = failing[at:at + per_call]
+                    hyps = self.decode_beam([prompts[w] for w in part], beam_size, patience=patience, sample_len=cap, windows=part,
+                                            n_windows=len(prompts))
+                    for w, h in zip(part, hyps):
+                        cands[w] = h
+            elif walk.round == 0 and n_rows == 1:
                 for w, r in enumerate(self.decode(prompts, sample_len=cap, temperature=t, seed=seed)):
                     cands[w].append(r)
             else:
@@ -539,7 +608,7 @@ class WhisperModel:
                                             n_windows=len(prompts))
                     for (w, _), r in zip(ch["owners"], rows):
                         cands[w].append(r)
-            walk.submit({w: fallback.window_result(cands[w], t, self.tokenizer, eot) for w in failing})
+            walk.submit({w: fallback.window_result(cands[w], t, self.tokenizer, eot, length_penalty) for w in failing})
         return [walk.accepted[w] for w in range(len(prompts))]
 
     def align(self, tokens_per_seq: Sequence[Sequence[int]], n_frames: Sequence[int], return_probs: bool = False,
@@ -628,7 +697,8 @@ class WhisperModel:
                    no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0,
                    language: Optional[str] = None, task: str = "transcribe",
                    hallucination_silence_threshold: Optional[float] = None, compression_ratio_threshold: Optional[float] = 2.4,
-                   best_of: Optional[int] = None, **_ignored):
+                   best_of: Optional[int] = None, beam_size: Optional[int] = None, patience: Optional[float] = None,
+                   length_penalty: Optional[float] = None, **_ignored):
         """One clip, same signature as whisper.transcribe as the reference uses it.  temperature 0 is the
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
@@ -644,20 +714,25 @@ class WhisperModel:
         On an instance built with `temperature_fallback=True`: temperature may be a schedule (upstream's default is (0.0, 0.2, 0.4,
         0.6, 0.8, 1.0); here the default stays 0.0), and compression_ratio_threshold / best_of are honoured
         [UPSTREAM-RECALL: transcribe.py::decode_with_fallback; parity unpinned] -- see `transcribe_batch`.  Otherwise a schedule
-        raises and the two are ignored."""
+        raises and the two are ignored.
+        On an instance built with `beam_search=True`: beam_size / patience / length_penalty are honoured (see `transcribe_batch`);
+        otherwise they are accepted and ignored."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
                                      compression_ratio_threshold=compression_ratio_threshold, best_of=best_of,
                                      temperature=temperature, no_speech_threshold=no_speech_threshold,
                                      logprob_threshold=logprob_threshold, word_timestamps=word_timestamps,
                                      languages=[language], task=task,
-                                     hallucination_silence_threshold=hallucination_silence_threshold)[0]
+                                     hallucination_silence_threshold=hallucination_silence_threshold, beam_size=beam_size,
+                                     patience=patience, length_penalty=length_penalty)[0]
 
     def transcribe_batch(self, audios: Sequence, initial_prompts: Optional[Sequence[Optional[str]]] = None,
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
                          no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0,
                          word_timestamps: bool = False, languages: Optional[Sequence[Optional[str]]] = None,
                          task: str = "transcribe", hallucination_silence_threshold: Optional[float] = None,
-                         compression_ratio_threshold: Optional[float] = 2.4, best_of: Optional[int] = None) -> List[dict]:
+                         compression_ratio_threshold: Optional[float] = 2.4, best_of: Optional[int] = None,
+                         beam_size: Optional[int] = None, patience: Optional[float] = None,
+                         length_penalty: Optional[float] = None) -> List[dict]:
         """Independent clips decoded together (each window of each clip is one sequence of a batch).
         languages[i] (multilingual models): the clip's language code or name; None: detected on the clip's first window, after its
         group's `encode` and before its `decode` [UPSTREAM-RECALL: transcribe.py, `if decode_options.get("language") is None`].
@@ -669,18 +744,31 @@ class WhisperModel:
         logprob_threshold (silence by no_speech_threshold excepted), at the last one whatever it scores; above temperature 0,
         best_of candidates per window, the most probable per token kept.  Per group `log_mel` and `encode` run once; word alignment
         runs after the walk on the accepted tokens.  On such calls every segment also carries `temperature`, `avg_logprob`,
-        `compression_ratio` and `no_speech_prob`, as upstream's do; a single float without best_of returns what it always did."""
+        `compression_ratio` and `no_speech_prob`, as upstream's do; a single float without best_of returns what it always did.
+        beam_search instances [UPSTREAM-RECALL: decode_with_fallback, BeamSearchDecoder; parity unpinned]: with beam_size, every
+        temperature-0 round decodes its windows by beam search (`decode_beam`: beam_size rows per window over the group's window map,
+        nothing encoded again; `patience` sets when a window is complete) and keeps the ranker's pick among the hypotheses; above 0
+        beam_size and patience are dropped as best_of is at 0; length_penalty enters the ranker of both.  The same thresholds apply, the
+        segments carry the walk's fields, word alignment runs afterwards on the accepted tokens.  beam_size with a single temperature
+        above 0, or patience without beam_size, raises.  Without the opt-in all three are ignored: the call is what it is without them."""
         with_words = bool(word_timestamps) and self.word_alignment
         if not self.temperature_fallback:
             if isinstance(temperature, (tuple, list)):
                 raise _lib.CcxError("temperature fallback schedules need an instance built with temperature_fallback=True: "
                                     "pass one temperature (the reference does)")
             best_of = None          # ignored, as compression_ratio_threshold is
+        if not self.beam_search:
+            beam_size = patience = length_penalty = None     # accepted and ignored
+        if patience is not None and beam_size is None:
+            raise _lib.CcxError("patience needs beam_size")
+        if beam_size is not None and not isinstance(temperature, (tuple, list)) and float(temperature) > 0.0:
+            raise _lib.CcxError("beam_size needs temperature 0 (or a schedule that starts there): beam search does not sample")
         try:
             schedule = fallback.normalize_schedule(temperature)
         except ValueError as e:
             raise _lib.CcxError(str(e)) from e
-        walk_on = self.temperature_fallback and (isinstance(temperature, (tuple, list)) or best_of is not None)
+        walk_on = (self.temperature_fallback and (isinstance(temperature, (tuple, list)) or best_of is not None)) or \
+            beam_size is not None or length_penalty is not None
         self.fallback_walks: List[fallback.FallbackWalk] = []     # this call's walks, one per encoded group, in order
         temperature = schedule[0]
         n = len(audios)
@@ -738,7 +826,7 @@ class WhisperModel:
                 prompts = [state[i].initial_tokens() for i in grp]
                 if walk_on:
                     results = self._decode_with_fallback(prompts, cap, schedule, best_of, compression_ratio_threshold,
-                                                         logprob_threshold, no_speech_threshold)
+                                                         logprob_threshold, no_speech_threshold, beam_size, patience, length_penalty)
                     self.fallback_walks[-1].clips, self.fallback_walks[-1].seeks = list(grp), [state[i].seek for i in grp]
                     n_seg = [len(state[i].segments) for i in grp]
                     if with_words:     # the accepted tokens, while the group's windows are still encoded: aligned as one batch, each

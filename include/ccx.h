@@ -231,6 +231,33 @@ int ccx_whisper_decode_rows(ccx_whisper* w, const int32_t* prompt_ids, const int
                             uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out,
                             float* no_speech_prob_out, void* stream);
 
+/* Beam search (decoding.py::BeamSearchDecoder + DecodingTask._main_loop [UPSTREAM-RECALL]; parity unpinned) at temperature 0 for G
+ * groups of beam_size consecutive rows over the n_windows windows of the last ccx_whisper_encode: group g decodes window
+ * window_of_group[g] (host [G]; NULL: group g reads window g, G <= n_windows), its rows share that window's encoder output or K/V
+ * through the row -> window map of ccx_whisper_decode_rows, so nothing is copied.  prompt_ids host [G][max_prompt], prompt_lens [G]:
+ * one prompt per group (every row prefills it into its own cache slot).  Each step: logits GEMM, then dec_beam_topk_kernel and
+ * dec_beam_update_kernel (csrc/dec_beam.hip) instead of the select kernel; the self attention reads its keys through a cache
+ * indirection (uint16 [max_batch][n_text_ctx], allocated by the first beam decode) that follows a hypothesis when it moves to another
+ * row -- no cache is copied or doubled.  A group is complete when it holds max_candidates finished hypotheses (round(beam_size *
+ * patience)) and freezes; the call ends when all are, or at sample_len.  A group with fewer than beam_size finished hypotheses is
+ * topped up with its live rows by descending score.  A beam decode runs in ONE lane whatever its row count; it takes the prefill
+ * (CCX_PREFILL=0 is refused) and the step graphs, keyed by beam_size and max_candidates too.
+ * Outputs (host), C = max(beam_size, max_candidates): tokens_out [G][C][sample_len] (tokens before the eot, eot-padded), n_tokens_out
+ * / sum_logprob_out [G][C], n_hyp_out [G] (hypotheses of group g, in insertion order: finished ones first), no_speech_prob_out [G].
+ * trace (NULL: off; a test aid -- a traced decode runs its steps eagerly): host buffers, n_steps rows of R = G * beam_size entries,
+ * that receive per sampled step and row the proposals (cand_id / cand_lp [n_steps][R][beam_size + 1]), the chosen token, the row it
+ * continues and its cumulative score (tok / parent / score [n_steps][R]); entries of steps a group no longer took stay -1 / NaN.
+ * Checks everything ccx_whisper_decode_rows checks, plus 1 <= beam_size <= 8, 1 <= max_candidates <= 16, G * beam_size <= max_batch:
+ * CCX_ERR_ARG (1) naming "ccx_whisper_decode_beam" and the field. */
+typedef struct ccx_beam_trace {
+  int n_steps;
+  int32_t* cand_id; float* cand_lp; int32_t* tok; int32_t* parent; float* score;
+} ccx_beam_trace;
+int ccx_whisper_decode_beam(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int G,
+                            const int32_t* window_of_group, int n_windows, int beam_size, int max_candidates, int sample_len,
+                            int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out, int32_t* n_hyp_out,
+                            float* no_speech_prob_out, const ccx_beam_trace* trace, void* stream);
+
 /* ---- the decode step's attention and token-select kernels on their own (csrc/decoder.hip; for kernel parity tests) ---------
  * Both entry points check on the host everything the kernels assume (ranges, element counts, 16-byte alignment of every
  * vector-accessed pointer) before anything is launched: a violation returns CCX_ERR_ARG (1) with a message naming the field.
@@ -243,13 +270,14 @@ int ccx_whisper_decode_rows(ccx_whisper* w, const int32_t* prompt_ids, const int
 #define CCX_DEC_ATTN_TWO_LAUNCH_Q 5  /* dec_linear<ACT_LN, DEPI_F32>, then dec_attention_kernel<false>: what FUSED_Q replaces */
 /* (6 is not a form: it stays the number the rejection tests of the descriptor use for an unknown one) */
 #define CCX_DEC_ATTN_STREAM_MAPPED 7 /* form 2 with row_seq honoured: dec_cross_stream_kernel<true, NP, false, true> (ccx_whisper_decode_rows) */
+#define CCX_DEC_ATTN_SELF_IND 8      /* form 0 through a cache indirection: dec_attention_kernel<true, true> (ccx_whisper_decode_beam) */
 
 typedef struct ccx_dec_attn_desc {
-  /* device operands.  q f32 [rows][H][64] (forms 0..3, 7); k, v bf16 [n_seq][H][kv_T][64] */
+  /* device operands.  q f32 [rows][H][64] (forms 0..3, 7, 8); k, v bf16 [n_seq][H][kv_T][64] */
   const void* q; const void* k; const void* v;
   int rows, n_seq, H, kv_T;
   int T;                    /* keys [0, T) of the cross forms (1..5, 7) */
-  const int* pos;           /* HOST [rows], form 0: row r attends to keys [0, pos[r]] */
+  const int* pos;           /* HOST [rows], forms 0, 8: row r attends to keys [0, pos[r]] */
   const int* row_seq;       /* HOST [rows] or NULL (row r reads sequence r): forms 0, 1, 3, 7 */
   int rows_per_seq;         /* form 3: consecutive groups of that many rows belong to one sequence (group g = sequence g) */
   int nsplit, combine;      /* forms 1, 4, 5: key splits (1..8); form 1: also run dec_combine_kernel into out */
@@ -259,11 +287,14 @@ typedef struct ccx_dec_attn_desc {
   const void* x; const void* pend; int pend_n; int64_t pend_stride;
   const void* ln_g; const void* ln_b; float eps;
   const float* wq_host; const void* bq;
-  /* device outputs: out f32 [rows][H * 64] (the kernels' bf16 output widened; forms 0, 2, 3, 7 and form 1 with combine),
+  /* device outputs: out f32 [rows][H * 64] (the kernels' bf16 output widened; forms 0, 2, 3, 7, 8 and form 1 with combine),
    * part_o f32 [rows][H][nsplit][64], part_ml f32 [rows][H][nsplit][2] (forms 1, 4, 5), q_x_out f32 [rows][768] (forms 4, 5, may be NULL) */
   void* out; void* part_o; void* part_ml; void* q_x_out;
   /* elements (of the buffer's own type) behind each pointer; kv_elems holds for k and for v */
   int64_t q_elems, kv_elems, out_elems, part_o_elems, part_ml_elems, x_elems, pend_elems, q_x_out_elems;
+  /* form 8: HOST [rows][ind_ld], ind_ld > every pos[r]: key t <= pos[r] of row r is read from sequence ind[r * ind_ld + t], which must
+   * lie in [0, n_seq); row_seq must be NULL.  (Appended: the forms before it read nothing here.) */
+  const uint16_t* ind; int ind_ld;
 } ccx_dec_attn_desc;
 
 /* Fills a DecAttnParams and calls the production launchers unchanged (ccx_launch_dec_attention, ccx_launch_dec_combine,
@@ -296,6 +327,35 @@ typedef struct ccx_dec_select_desc {
 /* One launch of the select kernel (ccx_launch_dec_select) for B rows: filters, argmax / sampling, the per-sequence state machine and
  * the next step's embedding x[b] = tok_emb[next] + pos_emb[pos]. */
 int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* desc, void* stream);
+
+/* One beam-search step on its own (csrc/dec_beam.hip: dec_beam_topk_kernel, one block per row, then dec_beam_update_kernel, one block
+ * per window; the rule is restated in tests/beam_reference.py) for G windows of beam_size consecutive rows, R = G * beam_size.
+ * Every row must be in the sampling phase (pos == prompt_len - 1 + n_gen); the rows of a window share n_gen, pos and done (a window
+ * whose rows are done is complete: nothing of it is touched).  Tables, all HOST, in and out unless marked:
+ *   state [R], hist [R][sample_len] (the tokens sampled so far first), cur_tok / pos [R], n_done [1] (+ beam_size per window that
+ *   completes or runs out of its sample_len budget), ind uint16 [R][ind_ld] (the cache slots of every row's keys; ind_ld > pos + 1),
+ *   fin_tok [G][max_candidates][sample_len] / fin_score / fin_n [G][max_candidates] / fin_count [G] (finished hypotheses: tokens before
+ *   the eot, cumulative log-probability, token count; appended in descending score while a window holds fewer than max_candidates)
+ *   out only: cand_id / cand_lp [R][beam_size + 1] (the proposals; id -1 where a row proposes nothing), tok_out / parent_out [R] (the
+ *   chosen token and the row it continues; -1 for a window that did not step)
+ * Device: logits f32 [R][ld], tok_emb, pos_emb, x f32 [R][D] (in and out).  Checked on the host before any launch, CCX_ERR_ARG (1)
+ * naming "ccx_dec_beam_step" and the field: 1 <= G, R <= 65536, 1 <= beam_size <= 8, 1 <= max_candidates <= 16, n_vocab a multiple of 4
+ * up to 53248, ld >= n_vocab and a multiple of 4, 16-byte alignment of every vector-accessed pointer, the element counts, every
+ * state, ind entries of a live window < 65536, fin_count <= max_candidates.  Owns its scratch; synchronises the stream. */
+typedef struct ccx_dec_beam_desc {
+  const void* logits; int64_t ld; int n_vocab;
+  int G, beam_size, max_candidates;
+  const ccx_decode_rules* rules;
+  ccx_dec_seq_state* state;
+  int sample_len;
+  int* hist; int* cur_tok; int* pos; int* n_done;
+  const void* tok_emb; const void* pos_emb; void* x; int D;
+  uint16_t* ind; int ind_ld;
+  int* fin_tok; float* fin_score; int* fin_n; int* fin_count;
+  int* cand_id; float* cand_lp; int* tok_out; int* parent_out;
+  int64_t logits_elems, tok_emb_elems, pos_emb_elems, x_elems;
+} ccx_dec_beam_desc;
+int ccx_dec_beam_step(ccx_ctx* ctx, const ccx_dec_beam_desc* desc, void* stream);
 
 /* Softmax of logit rows over an id range (csrc/dec_probs.hip: dec_token_probs_kernel, one block per row).  Over the ids [lo, hi) only --
  * everything else, the columns [n_vocab, ld) included, counts as -inf and is never looked at: argmax[row] (lowest id on equal values,
