@@ -149,6 +149,30 @@ class SepDesc(C.Structure):
 SEP_ATTN_BLOCK, SEP_ATTENTION, SEP_FFN, SEP_FINAL_NORM, SEP_DECODER = range(5)
 
 
+class EcapaDesc(C.Structure):
+    """ccx_ecapa_desc (include/ccx.h): one ECAPA-TDNN kernel on its own."""
+    _fields_ = [
+        ("n", C.c_int), ("row_off", C.POINTER(C.c_int)), ("frames", C.POINTER(C.c_int)), ("rows", C.c_int),
+        ("wav", C.c_void_p), ("wav_elems", C.c_int64), ("offsets", C.POINTER(C.c_int64)), ("n_samples", C.POINTER(C.c_int)),
+        ("window", C.c_void_p), ("window_elems", C.c_int64), ("filters", C.c_void_p), ("filters_elems", C.c_int64),
+        ("feats", C.c_void_p), ("feats_elems", C.c_int64),
+        ("x", C.c_void_p), ("x_elems", C.c_int64), ("ldx", C.c_int64), ("y", C.c_void_p), ("y_elems", C.c_int64), ("ldy", C.c_int64),
+        ("dilation", C.c_int), ("w_host", C.POINTER(C.c_float)), ("aff_host", C.POINTER(C.c_float)),
+        ("resid", C.c_void_p), ("resid_elems", C.c_int64), ("ld_resid", C.c_int64),
+        ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
+        ("w1_elems", C.c_int64), ("b1_elems", C.c_int64), ("w2_elems", C.c_int64), ("b2_elems", C.c_int64),
+        ("gates", C.c_void_p), ("gates_elems", C.c_int64),
+        ("channels", C.c_int), ("hidden", C.c_void_p), ("hidden_elems", C.c_int64),
+        ("wa", C.c_void_p), ("ba", C.c_void_p), ("bn_scale", C.c_void_p), ("bn_shift", C.c_void_p),
+        ("wa_elems", C.c_int64), ("ba_elems", C.c_int64), ("bn_elems", C.c_int64),
+        ("pooled", C.c_void_p), ("pooled_elems", C.c_int64)]
+
+
+ECAPA_FBANK, ECAPA_RES2NET, ECAPA_SE, ECAPA_ASP_POOL = range(4)
+ECAPA_R2_TILE = 128              # csrc/ecapa.h ECAPA_R2_TILE: output frames of one Res2Net block
+ECAPA_MIN_SAMPLES = 8000         # csrc/ecapa.h ECAPA_MIN_SAMPLES
+
+
 class AlignDesc(C.Structure):
     """ccx_align_desc (include/ccx.h): one word-alignment kernel on its own."""
     _fields_ = [
@@ -232,6 +256,12 @@ PROTOTYPES = {
     "ccx_speaker_finalize": (_i, [_vp]),
     "ccx_speaker_embed": (_i, [_vp, _vp, _i64p, _ip, _i, _vp, _i64p, _ip, _vp, _vp]),
     "ccx_speaker_segment": (_i, [_vp, _vp, _i64p, _ip, _i, _vp, _i64, _ip, _vp]),
+    "ccx_ecapa_create": (_i, [_vp, _i, _i64, C.POINTER(_vp)]),
+    "ccx_ecapa_destroy": (None, [_vp]),
+    "ccx_ecapa_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i64]),
+    "ccx_ecapa_finalize": (_i, [_vp]),
+    "ccx_ecapa_embed": (_i, [_vp, _vp, _i64p, _ip, _i, _vp, _vp]),
+    "ccx_ecapa_op": (_i, [_vp, _i, C.POINTER(EcapaDesc), _vp]),
     "ccx_resnet_create": (_i, [_vp, _i, _i64, _i, C.POINTER(_vp)]),
     "ccx_resnet_destroy": (None, [_vp]),
     "ccx_resnet_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i64]),

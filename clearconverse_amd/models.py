@@ -15,18 +15,29 @@ from . import _lib
 from .denoise import SpectralGate
 from .pipelines import SpeakerDiarization, VoiceActivityDetection
 from .separator import SepformerSeparator
-from .speaker import ResNetEmbedder, SegmentationNet, XVectorEmbedder
-from .weights import (SepDims, WhisperDims, find_pipeline_config, find_pyannote_checkpoint, find_sepformer_checkpoint,
+from .speaker import ECAPAEmbedder, ResNetEmbedder, SegmentationNet, XVectorEmbedder
+from .weights import (SepDims, WhisperDims, find_ecapa_checkpoint, find_pipeline_config, find_pyannote_checkpoint, find_sepformer_checkpoint,
                       find_whisper_checkpoint, synthetic_pyannet_state_dict, synthetic_resnet34_state_dict,
-                      synthetic_sepformer_state_dict, synthetic_whisper_state_dict, synthetic_xvector_state_dict)
+                      synthetic_ecapa_state_dict, synthetic_sepformer_state_dict, synthetic_whisper_state_dict,
+                      synthetic_xvector_state_dict)
 from .whisper import WhisperModel
 
 
+EMBEDDINGS = ("xvector", "ecapa")
+
+
+def _check_embedding(embedding: str) -> str:
+    if embedding not in EMBEDDINGS:
+        raise ValueError(f"embedding={embedding!r}: must be one of {EMBEDDINGS}")
+    return embedding
+
+
 def build_state_dicts(config=None, whisper_dims: Optional[WhisperDims] = None, sep_dims: Optional[SepDims] = None,
-                      seed: int = 0) -> Dict[str, object]:
+                      seed: int = 0, embedding: str = "xvector") -> Dict[str, object]:
     """Every weight of the path as host tensors: the real Whisper checkpoint when MODEL_CACHE_DIR holds one, seeded
     synthetic weights of the same architectures otherwise.  In a multi-GPU job rank 0 calls this and the result
     travels by ONE broadcast (batch.broadcast_weights)."""
+    _check_embedding(embedding)
     size = getattr(config, "whisper_model_size", "small.en") if config is not None else "small.en"
     ck = find_whisper_checkpoint(size) if whisper_dims is None else None
     if ck is not None:
@@ -45,6 +56,10 @@ def build_state_dicts(config=None, whisper_dims: Optional[WhisperDims] = None, s
         real = find_pyannote_checkpoint(kind)
         nets[kind] = real if real is not None else make()
         sources[kind] = "checkpoint" if real is not None else "synthetic"
+    if embedding == "ecapa":            # built only when asked: 80 MB of host tensors the default path never reads
+        real = find_ecapa_checkpoint()
+        nets["ecapa"] = real if real is not None else synthetic_ecapa_state_dict(seed=seed + 6)
+        sources["ecapa"] = "checkpoint" if real is not None else "synthetic"
     return {
         "whisper_dims": dict(wd.__dict__), "whisper": wsd, "whisper_source": sources["whisper"],
         "sep_dims": dict(sd_.__dict__),
@@ -62,12 +77,17 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
                 seg_max_crops: Optional[int] = None, seg_max_seconds: float = 1200.0, emb_max_crops: Optional[int] = None,
                 resnet_max_chunks: int = 96, whisper_instances: int = 1, share_encoder_scratch: bool = True,
                 gate_max_clips: int = 32, gate_max_seconds: float = 30.0, word_alignment: bool = False,
-                word_probabilities: bool = False) -> Dict[str, object]:
+                word_probabilities: bool = False, embedding: str = "xvector") -> Dict[str, object]:
+    """embedding: "xvector" (default: `pyannote/embedding`, what the reference loads) or "ecapa" (ECAPA-TDNN, 192-d) for
+    `models["embedding_model"]`; the diarization pipeline keeps its ResNet-34 either way."""
+    _check_embedding(embedding)
     if not torch.cuda.is_available():
         raise _lib.CcxError("load_models needs a ROCm GPU: the HIP path has no CPU fallback")
     dev_index = device.index if isinstance(device, torch.device) and device.index is not None else (device if isinstance(device, int) else 0)
     ctx = ctx or _lib.Context(dev_index)
-    W = state_dicts if state_dicts is not None else build_state_dicts(config, whisper_dims, sep_dims, seed)
+    W = state_dicts if state_dicts is not None else build_state_dicts(config, whisper_dims, sep_dims, seed, embedding=embedding)
+    if embedding == "ecapa" and "ecapa" not in W:
+        raise ValueError("load_models(embedding='ecapa'): state_dicts has no 'ecapa' entry (build_state_dicts(embedding='ecapa'))")
     wd, wsd = WhisperDims(**W["whisper_dims"]), W["whisper"]
     if state_dicts is not None:         # the geometry travels WITH the weights: a contradicting argument is an error, not ignored
         if whisper_dims is not None and whisper_dims != wd:
@@ -93,8 +113,11 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
     whisper = whispers[0]
     separator = SepformerSeparator(sd_, W["sepformer"], max_tokens=sep_tokens, max_utts=64,
                                    device=dev_index, ctx=ctx)
-    embedder = XVectorEmbedder(W["xvector"], max_crops=int(emb_max_crops or max_crops), max_samples=16000 * 1200,
-                               device=dev_index, ctx=ctx)
+    if embedding == "ecapa":            # the x-vector handle is then not created
+        embedder = ECAPAEmbedder(W["ecapa"], max_crops=int(emb_max_crops or max_crops), max_samples=16000 * 600, device=dev_index, ctx=ctx)
+    else:
+        embedder = XVectorEmbedder(W["xvector"], max_crops=int(emb_max_crops or max_crops), max_samples=16000 * 1200,
+                                   device=dev_index, ctx=ctx)
     # embedding model of the diarization pipeline (speaker-diarization-3.1 uses WeSpeaker ResNet-34, not pyannote/embedding)
     diar_embedder = ResNetEmbedder(W["resnet34"], max_chunks=int(resnet_max_chunks), max_samples=160000, max_masks=max(512, 3 * int(resnet_max_chunks)),
                                    device=dev_index, ctx=ctx)

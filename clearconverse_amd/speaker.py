@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import sinc_filters
+from .weights import ecapa_fbank_tables, sinc_filters
 
 
 class _SpeakerNet:
@@ -110,6 +110,59 @@ class XVectorEmbedder(_SpeakerNet):
             raise _lib.CcxError("XVectorEmbedder expects 16 kHz input (the reference always passes target_sample_rate)")
         w = item["waveform"]
         return self.embed_batch([w.reshape(-1)])[0].cpu().numpy()
+
+
+class ECAPAEmbedder(_SpeakerNet):
+    """ECAPA-TDNN (`speechbrain/spkrec-ecapa-voxceleb`, 192-d; csrc/ecapa.hip): the embedder to swap in for `pyannote/embedding`
+    when attribution on short crops is weak.  Same call shapes as `XVectorEmbedder` (the reference's call at back/api.py:869-872 and
+    the batched `embed_batch`), selected with `load_models(embedding="ecapa")`.  16 kHz only; every crop is its own utterance."""
+    DIM = 192
+    MIN_SAMPLES = _lib.ECAPA_MIN_SAMPLES
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], max_crops: int = 256, max_samples: int = 16000 * 600, device: int = 0,
+                 ctx: Optional[_lib.Context] = None):
+        if not torch.cuda.is_available():
+            raise _lib.CcxError("speaker networks need a ROCm GPU: the HIP path has no CPU fallback")
+        self.device = torch.device("cuda", device)
+        self.ctx = ctx or _lib.Context(device)
+        self.lib = self.ctx.lib
+        self.max_crops, self.max_samples = int(max_crops), int(max_samples)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.ccx_ecapa_create(self.ctx.handle, self.max_crops, self.max_samples, C.byref(h)), "ccx_ecapa_create")
+        self.handle = h
+        sd = dict(state_dict)
+        sd.update(ecapa_fbank_tables())
+        for name, t in sd.items():
+            if not torch.is_tensor(t) or name.endswith("num_batches_tracked"):
+                continue
+            t = t.detach().to("cpu", torch.float32).contiguous()
+            self.ctx.check(self.lib.ccx_ecapa_set_tensor(self.handle, name.encode(), t.data_ptr(), t.numel()), f"set_tensor({name})")
+        self.ctx.check(self.lib.ccx_ecapa_finalize(self.handle), "ccx_ecapa_finalize")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.ccx_ecapa_destroy(self.handle)
+            self.handle = None
+
+    def embed_batch(self, crops: Sequence, weights: Optional[Sequence] = None) -> torch.Tensor:
+        """crops: list of 1-D waveforms (16 kHz, at least 8000 samples each) -> [n, 192] f32 tensor on the GPU."""
+        if weights is not None:
+            raise _lib.CcxError("ECAPAEmbedder takes no frame weights: mask-weighted embeddings inside the diarization pipeline "
+                                "stay with ResNetEmbedder")
+        out = torch.empty(len(crops), self.DIM, device=self.device, dtype=torch.float32)
+        i64p, ip = C.POINTER(C.c_int64), C.POINTER(C.c_int)
+        for i0, i1 in self._groups(crops):
+            part = crops[i0:i1]
+            buf, offs, lens = self._pack(part)
+            self.ctx.check(self.lib.ccx_ecapa_embed(self.handle, buf.data_ptr(), offs.ctypes.data_as(i64p), lens.ctypes.data_as(ip),
+                                                    len(part), out[i0:i1].data_ptr(), _lib.current_stream_ptr()), "ccx_ecapa_embed")
+        return out
+
+    def __call__(self, item: dict) -> np.ndarray:
+        """Inference(window='whole') call shape: {'waveform': [1,T], 'sample_rate': sr} -> np [192]."""
+        if int(item.get("sample_rate", 16000)) != 16000:
+            raise _lib.CcxError("ECAPAEmbedder expects 16 kHz input (the reference always passes target_sample_rate)")
+        return self.embed_batch([item["waveform"].reshape(-1)])[0].cpu().numpy()
 
 
 class ResNetEmbedder:

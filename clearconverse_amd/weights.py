@@ -320,6 +320,92 @@ def synthetic_xvector_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
     return sd
 
 
+# ----------------------------------------------------------------------------------------------
+# ECAPA-TDNN (speechbrain/spkrec-ecapa-voxceleb hyper-parameters [UPSTREAM-RECALL: hyperparams.yaml of the model card,
+# lobes/models/ECAPA_TDNN.py]).  Fixed geometry: the kernels of csrc/ecapa.hip are written for exactly this network.
+# ----------------------------------------------------------------------------------------------
+ECAPA_CHANNELS = (1024, 1024, 1024, 1024, 3072)
+ECAPA_KERNELS = (5, 3, 3, 3, 1)
+ECAPA_DILATIONS = (1, 2, 3, 4, 1)
+ECAPA_SCALE, ECAPA_SE, ECAPA_ATT, ECAPA_DIM, ECAPA_MELS = 8, 128, 128, 192, 80
+
+
+def synthetic_ecapa_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """`speechbrain/spkrec-ecapa-voxceleb` `embedding_model.ckpt` key layout with seeded weights (also the schema `_conform` checks
+    a real checkpoint against).  Convolutions are fan-in scaled and every BatchNorm's running statistics sit near those of a
+    rectified unit-variance input (mean 0.4, variance 0.34), so activations stay O(1) through the trunk; blocks.0 is scaled down for
+    the dB-valued features (tens of dB after the mean subtraction); the SE and attention output convolutions are scaled UP so that the
+    gates leave the middle of the sigmoid and the attention is far from uniform over time (a N(0, 1/sqrt(fan_in)) draw would leave
+    both nearly constant and hide errors in them)."""
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+
+    def tdnn(p, cout, cin, k, gain=1.0):
+        sd[p + ".conv.conv.weight"] = torch.randn(cout, cin, k, generator=g) * (gain / math.sqrt(cin * k))
+        sd[p + ".conv.conv.bias"] = 0.1 * torch.randn(cout, generator=g)
+        bn(p + ".norm.norm", cout, 0.4, 0.34)
+
+    def bn(p, c, mean, var):
+        sd[p + ".weight"] = 1 + 0.1 * torch.randn(c, generator=g)
+        sd[p + ".bias"] = 0.1 * torch.randn(c, generator=g)
+        sd[p + ".running_mean"] = mean + 0.1 * torch.randn(c, generator=g)
+        sd[p + ".running_var"] = var * (0.5 + torch.rand(c, generator=g))
+
+    C = ECAPA_CHANNELS
+    tdnn("blocks.0", C[0], ECAPA_MELS, ECAPA_KERNELS[0], gain=0.04)
+    for i in (1, 2, 3):
+        p = f"blocks.{i}"
+        tdnn(p + ".tdnn1", C[i], C[i - 1], 1, gain=0.6)
+        for m in range(ECAPA_SCALE - 1):
+            tdnn(f"{p}.res2net_block.blocks.{m}", C[i] // ECAPA_SCALE, C[i] // ECAPA_SCALE, ECAPA_KERNELS[i], gain=0.8 if m == 0 else 0.5)
+        tdnn(p + ".tdnn2", C[i], C[i], 1, gain=0.6)
+        sd[p + ".se_block.conv1.conv.weight"] = torch.randn(ECAPA_SE, C[i], 1, generator=g) * (2.0 / math.sqrt(C[i]))
+        sd[p + ".se_block.conv1.conv.bias"] = 0.1 * torch.randn(ECAPA_SE, generator=g)
+        sd[p + ".se_block.conv2.conv.weight"] = torch.randn(C[i], ECAPA_SE, 1, generator=g) * (1.5 / math.sqrt(ECAPA_SE))
+        sd[p + ".se_block.conv2.conv.bias"] = 0.5 * torch.randn(C[i], generator=g)
+    tdnn("mfa", C[4], 3 * C[3], 1, gain=0.5)
+    tdnn("asp.tdnn", ECAPA_ATT, 3 * C[4], 1, gain=0.8)
+    sd["asp.conv.conv.weight"] = torch.randn(C[4], ECAPA_ATT, 1, generator=g) * (4.0 / math.sqrt(ECAPA_ATT))
+    sd["asp.conv.conv.bias"] = 0.1 * torch.randn(C[4], generator=g)
+    bn("asp_bn.norm", 2 * C[4], 0.0, 0.5)
+    sd["asp_bn.norm.running_mean"][C[4]:] += 0.7
+    sd["fc.conv.weight"] = torch.randn(ECAPA_DIM, 2 * C[4], 1, generator=g) / math.sqrt(2 * C[4])
+    sd["fc.conv.bias"] = 0.1 * torch.randn(ECAPA_DIM, generator=g)
+    return sd
+
+
+def ecapa_fbank_tables(sample_rate: int = 16000, n_fft: int = 400, n_mels: int = ECAPA_MELS, f_min: float = 0.0,
+                       f_max: float = 8000.0) -> Dict[str, torch.Tensor]:
+    """The two host-computed tables of the ECAPA front end, handed to the library as tensors (a mistaken recollection is then fixed
+    here, not in a kernel): `fbank.window` = torch.hamming_window(400) (periodic) and `fbank.filters` [80][201], speechbrain's
+    triangular HTK-mel filterbank [UPSTREAM-RECALL: processing/features.py::Filterbank] -- band edges equally spaced in mel over
+    [f_min, f_max], and BOTH slopes of triangle i use its LEFT band width hz[i+1] - hz[i] (a symmetric triangle around hz[i+1])."""
+    to_mel = lambda hz: 2595.0 * math.log10(1.0 + hz / 700.0)
+    mel = torch.linspace(to_mel(f_min), to_mel(f_max), n_mels + 2, dtype=torch.float64)
+    hz = 700.0 * (10.0 ** (mel / 2595.0) - 1.0)
+    band = (hz[1:] - hz[:-1])[:-1]                    # left band width of each filter
+    centre = hz[1:-1]
+    freqs = torch.linspace(0.0, sample_rate / 2, n_fft // 2 + 1, dtype=torch.float64)
+    slope = (freqs[None, :] - centre[:, None]) / band[:, None]
+    filters = torch.clamp(torch.minimum(slope + 1.0, 1.0 - slope), min=0.0)
+    return {"fbank.window": torch.hamming_window(n_fft, periodic=True), "fbank.filters": filters.float()}
+
+
+def find_ecapa_checkpoint(cache_dir: Optional[str] = None, log=None) -> Optional[Dict[str, torch.Tensor]]:
+    """State dict of `speechbrain/spkrec-ecapa-voxceleb/embedding_model.ckpt` (a plain state dict) from the hub cache layouts under
+    MODEL_CACHE_DIR[/ecapa] or HF_HOME, conformed to the architecture built here; None when no usable file exists."""
+    cache_dir = cache_dir or os.environ.get("MODEL_CACHE_DIR", "models")
+    path = _hub_file(_hub_roots(cache_dir, ("ecapa", "embedding")), "speechbrain/spkrec-ecapa-voxceleb", ("embedding_model.ckpt",))
+    if path is None:
+        return None
+    try:
+        sd = load_state_dict_file(path)
+    except CheckpointRefused as e:
+        (log or print)(f"[ccx weights] {e}; using synthetic weights for ecapa")
+        return None
+    return _conform("ecapa", sd, synthetic_ecapa_state_dict(), path)
+
+
 RESNET34_LAYERS = (3, 4, 6, 3)
 
 

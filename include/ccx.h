@@ -593,6 +593,61 @@ int ccx_speaker_embed(ccx_speaker* s, const float* wav_dev, const int64_t* offse
 int ccx_speaker_segment(ccx_speaker* s, const float* wav_dev, const int64_t* offsets, const int* n_samples, int n,
                         float* out_dev, int64_t out_capacity_rows, int* frames_out, void* stream);
 
+/* ---- ECAPA-TDNN speaker embedder (speechbrain/spkrec-ecapa-voxceleb, 192-d): an alternative to the x-vector above for
+ *      self.embedding_model (reference back/api.py:776-780), called with the same crops (back/api.py:869-872, 961-1006).
+ *      The reference itself does not use it; it is selected with load_models(embedding="ecapa"). ------------------------- */
+typedef struct ccx_ecapa ccx_ecapa;
+/* max_samples: total samples of all crops of one call (replaces the model construction at back/api.py:776-780) */
+int ccx_ecapa_create(ccx_ctx* ctx, int max_crops, int64_t max_samples, ccx_ecapa** out);
+void ccx_ecapa_destroy(ccx_ecapa* e);
+/* Tensors by speechbrain checkpoint key (f32): "blocks.0.conv.conv.weight", "blocks.1.res2net_block.blocks.0.norm.norm.running_var",
+ * "blocks.1.se_block.conv1.conv.weight", "mfa.conv.conv.weight", "asp.tdnn.conv.conv.weight", "asp.conv.conv.weight",
+ * "asp_bn.norm.weight", "fc.conv.weight", ... and the two host-computed front-end tables "fbank.window" [400] and "fbank.filters"
+ * [80][201] (replaces EncoderClassifier's checkpoint loading; the reference has no counterpart). */
+int ccx_ecapa_set_tensor(ccx_ecapa* e, const char* name, const float* data, int64_t numel);
+int ccx_ecapa_finalize(ccx_ecapa* e);
+/* n crops stored in wav_dev at sample offsets[i], n_samples[i] >= 8000 long (host arrays, the convention of ccx_speaker_embed)
+ * -> out_dev [n, 192] f32.  Every crop is its own utterance (replaces the call at back/api.py:869-872). */
+int ccx_ecapa_embed(ccx_ecapa* e, const float* wav_dev, const int64_t* offsets, const int* n_samples, int n, float* out_dev,
+                    void* stream);
+
+/* ---- the ECAPA-TDNN kernels on their own (csrc/ecapa.hip through the launchers of csrc/ecapa.h; for kernel parity tests, the
+ *      product path does not call this; no counterpart in the reference).  Device pointers come with the element count of the buffer's
+ *      own type; crop tables and the Res2Net weights are HOST arrays.  Everything the kernels assume is checked on the host before
+ *      anything is launched; a violation returns CCX_ERR_ARG (1) with a message naming "ccx_ecapa_op" and the field.  Synchronises
+ *      the stream.
+ *      Rows: crop i owns rows row_off[i] .. row_off[i] + frames[i] + 8 of every [rows][C] buffer (4 halo rows, frames, 4 halo rows). */
+#define CCX_ECAPA_FBANK 0      /* ecapa_fbank_kernel + mean + apply: wav -> feats bf16 [rows][80] with halos */
+#define CCX_ECAPA_RES2NET 1    /* ecapa_res2net_kernel: x [rows][ldx] -> y [rows][ldy], 1024 columns, halos written */
+#define CCX_ECAPA_SE 2         /* ecapa_se_mean / excite / apply: y = gates * x + resid, gates f32 [n][1024] (optional output) */
+#define CCX_ECAPA_ASP_POOL 3   /* ecapa_asp_pool_kernel: hidden [rows][128], x [rows][ldx] -> pooled bf16 [n][2 channels] */
+
+typedef struct ccx_ecapa_desc {
+  /* HOST crop tables: n crops, first row and frame count (>= 5) of each; crops pairwise disjoint inside [0, rows) */
+  int n; const int* row_off; const int* frames; int rows;
+  /* op 0: wav f32, HOST offsets / n_samples (>= 8000 each; frames[i] must be 1 + n_samples[i] / 160), window f32 [400],
+   * filters f32 [80][201] (device), feats bf16 [rows][80] */
+  const void* wav; int64_t wav_elems; const int64_t* offsets; const int* n_samples;
+  const void* window; int64_t window_elems; const void* filters; int64_t filters_elems;
+  void* feats; int64_t feats_elems;
+  /* ops 1, 2, 3: x bf16 [rows][ldx] in; ops 1, 2: y bf16 [rows][ldy] out (1024 live columns each; ld a multiple of 8) */
+  const void* x; int64_t x_elems; int64_t ldx; void* y; int64_t y_elems; int64_t ldy;
+  /* op 1: dilation 1..4; HOST conv weights f32 [7][128][128][3] and HOST (bias | scale | shift) f32 [7][3][128] */
+  int dilation; const float* w_host; const float* aff_host;
+  /* op 2: resid bf16 [rows][ld_resid]; w1 f32 [128][1024], b1 f32 [128], w2 f32 [1024][128], b2 f32 [1024] (device);
+   * gates f32 [n][1024] (device, may be NULL) */
+  const void* resid; int64_t resid_elems; int64_t ld_resid;
+  const void* w1; const void* b1; const void* w2; const void* b2; int64_t w1_elems, b1_elems, w2_elems, b2_elems;
+  void* gates; int64_t gates_elems;
+  /* op 3: channels (a multiple of 64, <= ldx); hidden bf16 [rows][128]; wa bf16 [channels][128], ba f32 [channels], bn_scale /
+   * bn_shift f32 [2 channels] (device); pooled bf16 [n][2 channels] */
+  int channels; const void* hidden; int64_t hidden_elems;
+  const void* wa; const void* ba; const void* bn_scale; const void* bn_shift; int64_t wa_elems, ba_elems, bn_elems;
+  void* pooled; int64_t pooled_elems;
+} ccx_ecapa_desc;
+
+int ccx_ecapa_op(ccx_ctx* ctx, int op, const ccx_ecapa_desc* desc, void* stream);
+
 /* ---- WeSpeaker ResNet-34 speaker embedder: the embedding model inside self.diarization =
  *      Pipeline.from_pretrained("pyannote/speaker-diarization-3.1"), reference back/api.py:788-792, called at
  *      back/api.py:1056-1060 and 1124-1128 (one embedding per 10 s chunk and local speaker) ---------------- */
