@@ -189,6 +189,15 @@ class AlignDesc(C.Structure):
 ALIGN_SCORES, ALIGN_MATRIX, ALIGN_DTW = range(3)
 
 
+class SpecgateOpts(C.Structure):
+    """ccx_specgate_opts (include/ccx.h): mode, tunables and noise clip of one spectral-gate call; ccx_specgate_opts_default fills
+    upstream's defaults."""
+    _fields_ = [
+        ("stationary", C.c_int), ("prop_decrease", C.c_float), ("n_std_thresh", C.c_float), ("time_constant_s", C.c_float),
+        ("thresh_n_mult", C.c_float), ("sigmoid_slope", C.c_float),
+        ("noise_dev", C.c_void_p), ("noise_stride", C.c_int64), ("n_noise", C.POINTER(C.c_int)), ("noise_rows", C.c_int)]
+
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _ip = C.POINTER(C.c_int)
 _i32p = C.POINTER(C.c_int32)
@@ -272,6 +281,10 @@ PROTOTYPES = {
     "ccx_specgate_reduce": (_i, [_vp, _vp, _i64, _ip, _i, _f, _vp, _vp]),
     "ccx_specgate_reduce_long": (_i, [_vp, _vp, _i64, _f, _vp, _vp]),
     "ccx_specgate_set_clip_noise": (_i, [_vp, _i]),
+    "ccx_specgate_opts_default": (None, [C.POINTER(SpecgateOpts)]),
+    "ccx_specgate_reduce_ex": (_i, [_vp, C.POINTER(SpecgateOpts), _vp, _i64, _ip, _i, _vp, _vp]),
+    "ccx_specgate_reduce_long_ex": (_i, [_vp, C.POINTER(SpecgateOpts), _vp, _i64, _vp, _vp]),
+    "ccx_specgate_time_smooth": (_i, [_vp, _vp, _vp, _ip, _i, _i64, _f, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,7 +1,16 @@
-"""`SpectralGate`: libccx-backed replacement of `noisereduce.reduce_noise(y=, sr=, stationary=True,
-prop_decrease=)` as the reference uses it (/root/reference/back/api.py:349, 832-833).  Calling the
-object with (np1d, sr, prop_decrease) returns a float32 numpy array of the same length -- the
-`denoiser` contract of clearconverse_amd.processor.  `reduce_batch` is the batched device entry."""
+"""`SpectralGate`: libccx-backed replacement of `noisereduce.reduce_noise(y=, sr=, stationary=, prop_decrease=, y_noise=, ...)`.
+The reference uses it as `reduce_noise(y=, sr=, stationary=True, prop_decrease=)` (/root/reference/back/api.py:349, 832-833), and
+that is the default here.  Calling the object with (np1d, sr, prop_decrease) returns a float32 numpy array of the same length -- the
+`denoiser` contract of clearconverse_amd.processor.  `reduce_batch` is the batched device entry.
+
+Modes and options, named as in noisereduce (all follow the package from recollection, **parity unpinned**: it is not installed and
+no fixture exists; CPU restatements: oracle/spectral_gate_ref.py, tests/nonstationary_gate_reference.py):
+  stationary=True   one threshold per bin for the whole clip, from the noise clip `y_noise` (default: the signal itself),
+                    mean + n_std_thresh_stationary * std of its dB spectrogram.
+  stationary=False  the package's own default: the threshold follows the signal, a forward-backward smoothing of |X| over
+                    `time_constant_s`; mask = sigmoid(((|X| - S) / S - thresh_n_mult_nonstationary) * sigmoid_slope_nonstationary).
+                    `y_noise` is ignored, as upstream ignores it.  Deviation: an all-zero signal returns zeros (upstream: NaN).
+"""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,16 +21,19 @@ import torch
 
 from . import _lib
 
+MODES = ("stationary", "nonstationary")
+
 
 class SpectralGate:
     def __init__(self, max_samples: int = 480000, max_clips: int = 32, sample_rate: int = 16000, device: int = 0,
-                 ctx: Optional[_lib.Context] = None, clip_noise_stationary: bool = True):
+                 ctx: Optional[_lib.Context] = None, clip_noise_stationary: bool = True, stationary: bool = True):
         if not torch.cuda.is_available():
             raise _lib.CcxError("SpectralGate needs a ROCm GPU: the HIP path has no CPU fallback")
         self.device = torch.device("cuda", device)
         self.ctx = ctx or _lib.Context(device)
         self.lib = self.ctx.lib
         self.max_samples, self.max_clips, self.sr = int(max_samples), int(max_clips), int(sample_rate)
+        self.stationary = bool(stationary)          # the mode of every call that does not name one
         h = C.c_void_p()
         self.ctx.check(self.lib.ccx_specgate_create(self.ctx.handle, self.max_samples, self.max_clips, self.sr, C.byref(h)),
                        "ccx_specgate_create")
@@ -42,32 +54,80 @@ class SpectralGate:
         except Exception:
             pass
 
-    def reduce_batch(self, y: torch.Tensor, n_samples: Sequence[int], prop_decrease: float) -> torch.Tensor:
-        """y [B, stride] f32 on the GPU -> denoised [B, stride]."""
+    def _opts(self, prop_decrease, stationary, n_std_thresh_stationary, time_constant_s, thresh_n_mult_nonstationary,
+              sigmoid_slope_nonstationary) -> _lib.SpecgateOpts:
+        o = _lib.SpecgateOpts()
+        self.lib.ccx_specgate_opts_default(C.byref(o))
+        o.stationary = 1 if (self.stationary if stationary is None else bool(stationary)) else 0
+        o.prop_decrease = float(prop_decrease)
+        o.n_std_thresh = float(n_std_thresh_stationary)
+        o.time_constant_s = float(time_constant_s)
+        o.thresh_n_mult = float(thresh_n_mult_nonstationary)
+        o.sigmoid_slope = float(sigmoid_slope_nonstationary)
+        return o
+
+    def reduce_batch(self, y: torch.Tensor, n_samples: Sequence[int], prop_decrease: float, *, stationary: Optional[bool] = None,
+                     y_noise: Optional[torch.Tensor] = None, n_noise: Optional[Sequence[int]] = None,
+                     n_std_thresh_stationary: float = 1.5, time_constant_s: float = 2.0, thresh_n_mult_nonstationary: float = 2.0,
+                     sigmoid_slope_nonstationary: float = 10.0) -> torch.Tensor:
+        """y [B, stride] f32 on the GPU -> denoised [B, stride].  y_noise: [1, L] (one noise clip for every row) or [B, L] f32 on the
+        GPU with n_noise, the samples of each of its rows (default: L)."""
         assert y.is_cuda and y.dtype == torch.float32 and y.is_contiguous()
         B, stride = y.shape
+        o = self._opts(prop_decrease, stationary, n_std_thresh_stationary, time_constant_s, thresh_n_mult_nonstationary,
+                       sigmoid_slope_nonstationary)
+        NR = 0
+        if y_noise is not None:
+            assert y_noise.is_cuda and y_noise.dtype == torch.float32 and y_noise.dim() == 2 and y_noise.is_contiguous()
+            NR = int(y_noise.shape[0])
+            if NR not in (1, B):
+                raise _lib.CcxError(f"SpectralGate.reduce_batch: y_noise has {NR} rows, expected 1 or {B}")
+            n_noise = [int(y_noise.shape[1])] * NR if n_noise is None else [int(v) for v in n_noise]
+            if len(n_noise) != NR:
+                raise _lib.CcxError(f"SpectralGate.reduce_batch: n_noise has {len(n_noise)} entries for {NR} noise clips")
+            o.noise_stride = int(y_noise.shape[1])
         out = torch.empty_like(y)
         for b0 in range(0, B, self.max_clips):
             nb = min(self.max_clips, B - b0)
             ns = (C.c_int * nb)(*[int(v) for v in n_samples[b0:b0 + nb]])
-            self.ctx.check(self.lib.ccx_specgate_reduce(self.handle, y[b0:b0 + nb].data_ptr(), stride, ns, nb, float(prop_decrease),
-                                                        out[b0:b0 + nb].data_ptr(), _lib.current_stream_ptr()), "ccx_specgate_reduce")
+            if NR:                                  # a shared clip goes with every group, per-row clips with their rows
+                rows = slice(0, 1) if NR == 1 else slice(b0, b0 + nb)
+                nn = (C.c_int * (1 if NR == 1 else nb))(*n_noise[rows])
+                o.noise_dev, o.n_noise, o.noise_rows = y_noise[rows].data_ptr(), nn, (1 if NR == 1 else nb)
+            self.ctx.check(self.lib.ccx_specgate_reduce_ex(self.handle, C.byref(o), y[b0:b0 + nb].data_ptr(), stride, ns, nb,
+                                                           out[b0:b0 + nb].data_ptr(), _lib.current_stream_ptr()), "ccx_specgate_reduce_ex")
         return out
 
-    def reduce_long(self, y: torch.Tensor, prop_decrease: float) -> torch.Tensor:
-        """One 1-D signal of any length (GPU tensor): noisereduce's chunked path -- threshold from the whole signal, 600000-sample
-        chunks with 30000 samples of context (ccx_specgate_reduce_long).  Whole conversations go through this."""
+    def reduce_long(self, y: torch.Tensor, prop_decrease: float, *, stationary: Optional[bool] = None,
+                    y_noise: Optional[torch.Tensor] = None, n_std_thresh_stationary: float = 1.5, time_constant_s: float = 2.0,
+                    thresh_n_mult_nonstationary: float = 2.0, sigmoid_slope_nonstationary: float = 10.0) -> torch.Tensor:
+        """One 1-D signal of any length (GPU tensor): noisereduce's chunked path -- threshold from the noise clip (the signal itself, or
+        the 1-D GPU tensor y_noise; cut to its first 600000 samples while clip_noise_stationary is on), 600000-sample chunks with
+        30000 samples of context (ccx_specgate_reduce_long_ex).  Whole conversations go through this."""
         assert y.is_cuda and y.dtype == torch.float32 and y.dim() == 1 and y.is_contiguous()
+        o = self._opts(prop_decrease, stationary, n_std_thresh_stationary, time_constant_s, thresh_n_mult_nonstationary,
+                       sigmoid_slope_nonstationary)
+        if y_noise is not None:
+            assert y_noise.is_cuda and y_noise.dtype == torch.float32 and y_noise.dim() == 1 and y_noise.is_contiguous()
+            nn = (C.c_int * 1)(int(y_noise.numel()))
+            o.noise_dev, o.noise_stride, o.n_noise, o.noise_rows = y_noise.data_ptr(), int(y_noise.numel()), nn, 1
         out = torch.empty_like(y)
-        self.ctx.check(self.lib.ccx_specgate_reduce_long(self.handle, y.data_ptr(), int(y.numel()), float(prop_decrease), out.data_ptr(),
-                                                         _lib.current_stream_ptr()), "ccx_specgate_reduce_long")
+        self.ctx.check(self.lib.ccx_specgate_reduce_long_ex(self.handle, C.byref(o), y.data_ptr(), int(y.numel()), out.data_ptr(),
+                                                            _lib.current_stream_ptr()), "ccx_specgate_reduce_long_ex")
         return out
 
-    def __call__(self, y, sr: int = 16000, prop_decrease: float = 1.0) -> np.ndarray:
+    def __call__(self, y, sr: int = 16000, prop_decrease: float = 1.0, *, stationary: Optional[bool] = None, y_noise=None,
+                 n_std_thresh_stationary: float = 1.5, time_constant_s: float = 2.0, thresh_n_mult_nonstationary: float = 2.0,
+                 sigmoid_slope_nonstationary: float = 10.0) -> np.ndarray:
         if int(sr) != self.sr:
             raise _lib.CcxError(f"SpectralGate was built for {self.sr} Hz, got {sr}")
+        kw = dict(stationary=stationary, n_std_thresh_stationary=n_std_thresh_stationary, time_constant_s=time_constant_s,
+                  thresh_n_mult_nonstationary=thresh_n_mult_nonstationary, sigmoid_slope_nonstationary=sigmoid_slope_nonstationary)
         x = np.ascontiguousarray(np.asarray(y, dtype=np.float32).reshape(1, -1))
         d = torch.from_numpy(x).to(self.device)
+        nz = None
+        if y_noise is not None:
+            nz = torch.from_numpy(np.ascontiguousarray(np.asarray(y_noise, dtype=np.float32).reshape(1, -1))).to(self.device)
         if x.shape[1] > self.max_samples:
-            return self.reduce_long(d[0], prop_decrease).cpu().numpy()
-        return self.reduce_batch(d, [x.shape[1]], prop_decrease)[0].cpu().numpy()
+            return self.reduce_long(d[0], prop_decrease, y_noise=None if nz is None else nz[0], **kw).cpu().numpy()
+        return self.reduce_batch(d, [x.shape[1]], prop_decrease, y_noise=nz, **kw)[0].cpu().numpy()

@@ -32,6 +32,15 @@ def _check_embedding(embedding: str) -> str:
     return embedding
 
 
+DENOISE_MODES = ("stationary", "nonstationary")
+
+
+def _check_denoise(denoise: str) -> str:
+    if denoise not in DENOISE_MODES:
+        raise ValueError(f"denoise={denoise!r}: must be one of {DENOISE_MODES}")
+    return denoise
+
+
 def build_state_dicts(config=None, whisper_dims: Optional[WhisperDims] = None, sep_dims: Optional[SepDims] = None,
                       seed: int = 0, embedding: str = "xvector") -> Dict[str, object]:
     """Every weight of the path as host tensors: the real Whisper checkpoint when MODEL_CACHE_DIR holds one, seeded
@@ -77,10 +86,13 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
                 seg_max_crops: Optional[int] = None, seg_max_seconds: float = 1200.0, emb_max_crops: Optional[int] = None,
                 resnet_max_chunks: int = 96, whisper_instances: int = 1, share_encoder_scratch: bool = True,
                 gate_max_clips: int = 32, gate_max_seconds: float = 30.0, word_alignment: bool = False,
-                word_probabilities: bool = False, embedding: str = "xvector") -> Dict[str, object]:
+                word_probabilities: bool = False, embedding: str = "xvector", denoise: str = "stationary") -> Dict[str, object]:
     """embedding: "xvector" (default: `pyannote/embedding`, what the reference loads) or "ecapa" (ECAPA-TDNN, 192-d) for
-    `models["embedding_model"]`; the diarization pipeline keeps its ResNet-34 either way."""
+    `models["embedding_model"]`; the diarization pipeline keeps its ResNet-34 either way.
+    denoise: the mode of `models["denoiser"]` -- "stationary" (default: what the reference asks noisereduce for) or "nonstationary"
+    (noisereduce's own default mode, SpectralGate(stationary=False))."""
     _check_embedding(embedding)
+    _check_denoise(denoise)
     if not torch.cuda.is_available():
         raise _lib.CcxError("load_models needs a ROCm GPU: the HIP path has no CPU fallback")
     dev_index = device.index if isinstance(device, torch.device) and device.index is not None else (device if isinstance(device, int) else 0)
@@ -129,7 +141,8 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
     seg_vad = SegmentationNet(W["pyannet_vad"], n_classes=3, powerset=False, max_crops=seg_crops,
                               max_samples=int(16000 * seg_max_seconds), device=dev_index, ctx=ctx)
     # one launch of the spectral gate holds gate_max_clips rows of gate_max_seconds (longer inputs take the chunked path)
-    gate = SpectralGate(max_samples=int(16000 * gate_max_seconds), max_clips=int(gate_max_clips), device=dev_index, ctx=ctx)
+    gate = SpectralGate(max_samples=int(16000 * gate_max_seconds), max_clips=int(gate_max_clips), device=dev_index, ctx=ctx,
+                        stationary=denoise == "stationary")
     return {
         "ctx": ctx,
         "weights_source": W.get("whisper_source", "given"),

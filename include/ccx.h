@@ -666,8 +666,8 @@ int ccx_resnet_finalize(ccx_resnet* r);
 int ccx_resnet_embed(ccx_resnet* r, const float* wav_dev, int64_t stride, int n_samples, int n_chunks, const float* weights_dev,
                      int n_w, const int* mask_chunk, int n_masks, float* out_dev, void* stream);
 
-/* ---- stationary spectral-gate denoiser (replaces nr.reduce_noise(y=, sr=, stationary=True,
- *      prop_decrease=), reference back/api.py:349 and 832-833) ---------------------------------------- */
+/* ---- spectral-gate denoiser (replaces nr.reduce_noise(y=, sr=, stationary=True, prop_decrease=),
+ *      reference back/api.py:349 and 832-833; the package's other mode and options: *_ex below) ------- */
 typedef struct ccx_specgate ccx_specgate;
 int ccx_specgate_create(ccx_ctx* ctx, int64_t max_samples, int max_clips, int sample_rate, ccx_specgate** out);
 void ccx_specgate_destroy(ccx_specgate* g);
@@ -683,6 +683,52 @@ int ccx_specgate_set_clip_noise(ccx_specgate* g, int on);
  * (the reference passes whole files to nr.reduce_noise, back/api.py:832-833).  Capacity: n / 256 + 1 <= frame rows of the
  * workspace = (max_samples + 60000) / 256 + 2 per clip x max_clips.  y_dev and out_dev must not overlap. */
 int ccx_specgate_reduce_long(ccx_specgate* g, const float* y_dev, int64_t n, float prop_decrease, float* out_dev, void* stream);
+
+/* ---- the rest of nr.reduce_noise: non-stationary mode, a separate noise clip, the tunables ---------------------------------------
+ * ccx_specgate_reduce / _reduce_long above are ccx_specgate_reduce_ex / _reduce_long_ex with ccx_specgate_opts_default and the
+ * caller's prop_decrease: same kernels, same arguments, same bits.
+ *
+ * stationary = 1 (noisereduce's SpectralGateStationary): threshold = mean + n_std_thresh * std per bin of the dB spectrogram of the
+ *   noise clip -- the signal itself (noise_rows = 0), ONE clip shared by all B rows (noise_rows = 1, noise_stride unused) or one per
+ *   row (noise_rows = B, clip b at noise_dev + b * noise_stride).  The noise pass is unpadded and floors at 80 dB under the noise
+ *   clip's own per-bin maximum.  n_noise is a HOST array of noise_rows lengths, each in [1, max_samples]; in reduce_long_ex the one
+ *   clip may be as long as the workspace's frame rows hold and is cut to its first 600000 samples while clip_noise is on.
+ * stationary = 0 (SpectralGateNonStationary, the package's default mode; [UPSTREAM-RECALL], PARITY UNPINNED like the stationary mode:
+ *   the package is not importable here and no fixture exists; CPU restatement: tests/nonstationary_gate_reference.py).  Per padded
+ *   chunk, with the chunking, padding and STFT of the stationary path:
+ *     A = |X|;  t = time_constant_s * 16000 / 256;  b = (sqrt(1 + 4 t^2) - 1) / (2 t^2)
+ *     S = filtfilt([b], [1, b - 1], A, axis = time, padtype = None)
+ *     M = 1 / (1 + exp(-((A - S) / S - thresh_n_mult) * sigmoid_slope)), smoothed with the same 33 x 7 triangle,
+ *     then M * prop_decrease + (1 - prop_decrease) -- AFTER smoothing (the stationary mode scales before) -- and out = istft(X * M).
+ *   A noise clip is validated and ignored, as upstream ignores it.  DEVIATION: a bin whose S is 0 (an all-zero row; upstream divides
+ *   0 by 0 and returns NaN) takes mask 0, so an all-zero signal returns exact zeros.
+ * Every field is checked on the host before anything is launched; a violation returns CCX_ERR_ARG (1) with a message naming the
+ * field: prop_decrease / n_std_thresh / thresh_n_mult / sigmoid_slope finite, time_constant_s > 0, noise_rows in {0, 1, B},
+ * n_noise[i] within capacity and (noise_rows = B) within noise_stride. */
+typedef struct ccx_specgate_opts {
+  int stationary;
+  float prop_decrease;      /* 1.0 */
+  float n_std_thresh;       /* n_std_thresh_stationary, 1.5 */
+  float time_constant_s;    /* 2.0 */
+  float thresh_n_mult;      /* thresh_n_mult_nonstationary, 2.0 */
+  float sigmoid_slope;      /* sigmoid_slope_nonstationary, 10.0 */
+  const float* noise_dev;   /* device; NULL with noise_rows = 0 */
+  int64_t noise_stride;
+  const int* n_noise;       /* host [noise_rows] */
+  int noise_rows;
+} ccx_specgate_opts;
+/* stationary = 1, the defaults above, no noise clip */
+void ccx_specgate_opts_default(ccx_specgate_opts* opts);
+int ccx_specgate_reduce_ex(ccx_specgate* g, const ccx_specgate_opts* opts, const float* y_dev, int64_t stride, const int* n_samples,
+                           int B, float* out_dev, void* stream);
+int ccx_specgate_reduce_long_ex(ccx_specgate* g, const ccx_specgate_opts* opts, const float* y_dev, int64_t n, float* out_dev,
+                                void* stream);
+/* Kernel parity tests: exactly the product's time-smoothing launches (csrc/spectral_gate.hip: forward-backward first-order
+ * recursion over 64-frame segments, three launches) on a caller's matrices, then a stream synchronise.  a_dev / s_dev: device
+ * [B][clip_stride_rows][520] f32 (513 bins used), n_frames host [B], each in [1, min(2580, clip_stride_rows)]; B <= max_clips;
+ * b in (0, 1].  Rows at and beyond n_frames[b] of s_dev are not written.  s_dev must not alias a_dev. */
+int ccx_specgate_time_smooth(ccx_specgate* g, const float* a_dev, float* s_dev, const int* n_frames, int B, int64_t clip_stride_rows,
+                             float b, void* stream);
 
 #ifdef __cplusplus
 }
