@@ -7,11 +7,11 @@
 // model.py / decoding.py [UPSTREAM-RECALL -- not vendored in the reference]; the CPU restatement
 // the tests compare against is oracle/whisper_ref.py.
 #include <algorithm>
-#include <array>
 #include <atomic>
 #include <map>
 #include <chrono>
 #include <math.h>
+#include <tuple>
 #include "../../include/ccx.h"
 #include "align.h"
 #include "attention.h"
@@ -45,6 +45,34 @@ struct DecLayer {
   float *bqkv, *bo, *bcq, *bckv, *bco, *b1, *b2;
   bf16_t *crossK, *crossV, *selfK, *selfV;
 };
+
+// The mode of one decoder step (or prefill pass) of one lane, as a value -- and, being everything a captured step bakes in, the key
+// of the step-graph cache.  Invariant: a field dec_step / dec_head branches on or passes by value is in the plan; anything else
+// they read from the instance is constant between ccx_whisper_set_rules calls (weights, workspaces, dimensions, rule ids), and
+// what is neither (logits, counters, streams, per-call buffers) comes in through StepIo.
+struct StepPlan {
+  int b0, B;                      // the lane's rows [b0, b0 + B)
+  int sample_len, max_prompt;
+  int select;                     // the step ends in the select (or beam) kernel; 0: logits only
+  int sampling;                   // temperature > 0: the sampling variant of the select kernel
+  int cross_stream;               // 1 (decodes): lean-streaming cross attention (dec_cross_stream_kernel) for lanes > 16 rows;
+                                  // 0 (teacher-forced passes): split-KV partials + dec_combine_kernel
+  int cross_lds_pad;              // occupancy cap of the cross-attention blocks while lanes overlap (plan_lanes)
+  int xs_active;                  // cross attention against the encoder output (select_cross_path)
+  int lnfree, xs_fuse_q, fuse_cross_q, xs_full_lines;   // the chain's form (read_chain_switches)
+  int map_on, sid_on;             // the rows read a row -> window map / a stream-id table (ccx_whisper_decode_rows)
+  int beam_size, beam_maxc;       // beam search (0: none) and its max_candidates
+  int lane_idx;                   // whose stamp trace and stagger slot
+  int stamp_level;                // diagnostic stamp nodes (0: none)
+  int prefill_rows;               // P > 0: the prompt prefill pass over B sequences x P positions instead of a step
+  auto tie() const {
+    return std::tie(b0, B, sample_len, max_prompt, select, sampling, cross_stream, cross_lds_pad, xs_active, lnfree, xs_fuse_q, fuse_cross_q,
+                    xs_full_lines, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows);
+  }
+  bool operator<(const StepPlan& o) const { return tie() < o.tie(); }
+};
+static_assert(sizeof(StepPlan) == 20 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 20,
+              "StepPlan: ints only, and every one of them in tie()");
 
 }  // namespace
 
@@ -92,7 +120,6 @@ struct ccx_whisper {
   float *dx = nullptr, *dx2 = nullptr, *pend = nullptr, *dq = nullptr, *dlogits = nullptr, *part_o = nullptr, *part_ml = nullptr;
   bf16_t *dattn = nullptr, *dffn = nullptr, *dxn = nullptr;
   int *cur_tok = nullptr, *pos = nullptr, *prompt = nullptr, *gen = nullptr, *n_done = nullptr;
-  bool sampling = false;            // temperature > 0 in the current decode call (selects the kernel variant)
   unsigned* sample_cfg = nullptr;   // {temperature bits, seed lo, seed hi, 0}: read by the select kernel every step
   DecSeqState* state = nullptr;
   int max_prompt_cap = 0, sample_cap = 0;
@@ -103,44 +130,32 @@ struct ccx_whisper {
   bf16_t *pf_xn = nullptr, *pf_attn = nullptr, *pf_ffn = nullptr;
   int *pf_tok = nullptr, *pf_pos = nullptr, *pf_seq = nullptr, *pf_last = nullptr;
   // decode over a row -> window map (ccx_whisper_decode_rows): row r keeps self-attention cache slot r and reads the cross K/V (or the
-  // encoder output) of window row_win[r]; row_sid[r] is its noise stream.  Allocated by the first mapped decode; map_on / sid_on hold
-  // for the duration of that call only.  pf_win: the prefill pass's row table composed with the map (row -> window).
+  // encoder output) of window row_win[r]; row_sid[r] is its noise stream.  Allocated by the first mapped decode; whether a step
+  // reads them is in its plan.  pf_win: the prefill pass's row table composed with the map (row -> window).
   int *row_win = nullptr, *row_sid = nullptr, *pf_win = nullptr;
-  bool map_on = false, sid_on = false;
-  const int32_t* win_host = nullptr;
   int enc_B = 0;                             // windows of the last ccx_whisper_encode
-  // beam search (ccx_whisper_decode_beam; dec_beam.hip).  Allocated by the first beam decode, sized from max_batch; beam_on and the
-  // trace pointers hold for the duration of that call only.  beam_ind [max_batch][n_text_ctx]: cache slot of every row's self-attention
+  // beam search (ccx_whisper_decode_beam; dec_beam.hip).  Allocated by the first beam decode, sized from max_batch (a traced
+  // call's buffers are its own: BeamTrace).  beam_ind [max_batch][n_text_ctx]: cache slot of every row's self-attention
   // keys; beam_cand_*: [max_batch][kBeamMax + 1] proposals of a step; beam_fin_*: the windows' finished hypotheses ([max_batch x
   // kBeamCandMax] slots: at beam_size 1 every row is a window).
-  bool beam_on = false;
-  int beam_size = 0, beam_maxc = 0;
   unsigned short* beam_ind = nullptr;
   int *beam_cand_id = nullptr, *beam_fin_tok = nullptr, *beam_fin_n = nullptr, *beam_fin_count = nullptr;
   float *beam_cand_lp = nullptr, *beam_fin_score = nullptr;
-  int *beam_tr_cid = nullptr, *beam_tr_tok = nullptr, *beam_tr_par = nullptr;    // per traced call (device), else null
-  float *beam_tr_clp = nullptr, *beam_tr_score = nullptr;
-  int beam_tr_rows = 0;
-  // graph cache; decode runs on an internal stream when the caller hands over the legacy null
+  // graph cache, keyed by the step plan; decode runs on an internal stream when the caller hands over the legacy null
   // stream (stream capture is illegal there)
-  std::map<std::array<int, 9>, hipGraphExec_t> graphs;
+  std::map<StepPlan, hipGraphExec_t> graphs;
   hipStream_t own_stream = nullptr;
   hipEvent_t own_event = nullptr;
   // decode lanes: disjoint row ranges of one batch stepping concurrently on their own streams, staggered so
   // that one lane's HBM-bound cross attention overlaps the other lanes' latency-bound linears.  The gain is
   // modest (3-4 % at 192 sequences): the small kernels slow down 3-5x while HBM is saturated by another lane.
   static constexpr int kMaxLanes = 4;
-  int cross_lds_pad = 0;                     // see ccx_whisper_decode: occupancy cap of the cross-attention blocks while lanes overlap
-  int cross_stream = 0;                      // 1 (decodes): lean-streaming cross attention (dec_cross_stream_kernel) for batches > 16;
-                                             // 0 (ccx_whisper_decoder_logits): split-KV partials + dec_combine_kernel
-  int fuse_cross_q = 1;                      // 1: batches <= 16 compute the cross-attention query inside the attention blocks
   // Cross attention against the encoder output (cross_x.hip) for decodes of more than 80 sequences: no per-layer K/V caches beyond those
   // (42 GB at 768 sequences), half the bytes per step.  xs_on: the instance was built for it (widths cross_x.hip instantiates,
   // CCX_CROSS_X != 0 at finalize); the K/V caches then hold kv_cap <= 80 sequences and are filled from xa at the start of a decode
   // that takes the K/V path (kv_ready = sequences valid since the last encode).
   static constexpr int kKvSeqs = 80;         // sequences the K/V caches of an X-stream instance hold (4.5 GB at small.en)
-  bool xs_on = false, xs_active = false, xs_fuse_q = true;
-  int xs_full_lines = 1;                     // XsParams::full_lines; read per call (read_chain_switches)
+  bool xs_on = false;
   int last_cross_path = -1;                  // ccx_whisper_last_cross_path: 0 kv16, 1 kv_stream, 2 xa_stream
   int kv_cap = 0, kv_ready = 0;
   bf16_t *xq = nullptr, *pf_xq = nullptr;    // expanded queries [rows][H][D] (step rows, prefill rows)
@@ -148,7 +163,6 @@ struct ccx_whisper {
   bf16_t *dxb = nullptr, *pf_xb = nullptr;
   float2 *dst2 = nullptr, *pf_st2 = nullptr;
   float *dshift = nullptr, *pf_shift = nullptr;   // ... and the shift they are centred by (the attn_ln mean of the row)
-  bool lnfree = true;                        // the LayerNorm-free query; read per call (read_chain_switches; CCX_DEC_LNFREE=0: round 3's)
   float *xs_po = nullptr, *xs_pml = nullptr, *pf_xs_po = nullptr, *pf_xs_pml = nullptr;   // key-half partials (cross_x.h)
   static constexpr int kLanePool = 8;
   hipStream_t lane_pool[kLanePool] = {};     // candidates; HIP streams share a few hardware queues and two streams on one
@@ -157,7 +171,7 @@ struct ccx_whisper {
   int* probe_sink = nullptr;
   unsigned long long* stamps = nullptr;      // [kMaxLanes][kStampCap] diagnostic trace (ccx_whisper_trace_lanes / CCX_DEC_STAMPS)
   int* stamp_count = nullptr;                // [kMaxLanes]
-  bool stamps_on = false;                    // stamp nodes are captured into the step graphs while set
+  bool stamps_on = false;                    // decodes run with plan.stamp_level = stamp_level while set, and append to stamp_path
   int stamp_level = 1;
   std::string stamp_path;
   static constexpr int kStampCap = 1 << 16;
@@ -170,7 +184,6 @@ struct ccx_whisper {
   size_t al_P_elems = 0, al_A_elems = 0, al_trace_bytes = 0, al_ints_elems = 0;   // bytes held by each (own hipMallocs, freed at destroy)
   int* al_picks = nullptr;                   // ccx_whisper_align_probs only: [seqs][T] picked ids, then [seqs][T] f32 probabilities
   size_t al_picks_bytes = 0;
-  const struct AlignPass* align_pass = nullptr;   // non-null only inside ccx_whisper_align's teacher-forced pass: dec_step's hook
   // SOT sequences of more than one token, vocabularies that are no multiple of 4, language detection (dec_probs.hip).  The scratch
   // is allocated by the first call that needs it: an English-only instance allocates nothing and launches nothing for it.
   int sot_tail = 0;                          // ccx_whisper_set_sot_tail: tokens of the SOT sequence behind <|startoftranscript|>
@@ -246,6 +259,20 @@ std::vector<float> cat_rows(std::initializer_list<const std::vector<float>*> par
   return r;
 }
 
+void drop_graphs(ccx_whisper* w) {
+  for (auto& g : w->graphs) hipGraphExecDestroy(g.second);
+  w->graphs.clear();
+}
+
+// the legacy null stream handed over: order after everything queued on it, then run on the instance's own stream
+int own_stream_if_null(ccx_whisper* w, hipStream_t* stream) {
+  if (*stream) return CCX_OK;
+  CCX_HIP(w->ctx, hipEventRecord(w->own_event, nullptr));
+  CCX_HIP(w->ctx, hipStreamWaitEvent(w->own_stream, w->own_event, 0));
+  *stream = w->own_stream;
+  return CCX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -289,7 +316,7 @@ void ccx_whisper_destroy(ccx_whisper* w) {
     if (--dn->scratch_takers == 0 && dn->destroy_pending) ccx_whisper_destroy(dn);
   }
   if (w->scratch_free) hipEventDestroy(w->scratch_free);
-  for (auto& g : w->graphs) hipGraphExecDestroy(g.second);
+  drop_graphs(w);
   if (w->own_stream) hipStreamDestroy(w->own_stream);
   if (w->own_event) hipEventDestroy(w->own_event);
   for (int i = 0; i < ccx_whisper::kMaxLanes; i++) {
@@ -354,9 +381,7 @@ int ccx_whisper_set_rules(ccx_whisper* w, const ccx_decode_rules* r) {
   w->rules = *r;
   w->rules.suppress = nullptr;
   w->rules_set = true;
-  // captured step graphs bake the rule ids into the select kernel's parameters: drop them
-  for (auto& g : w->graphs) hipGraphExecDestroy(g.second);
-  w->graphs.clear();
+  drop_graphs(w);      // captured step graphs bake the rule ids into the select kernel's parameters
   return CCX_OK;
 }
 
@@ -366,10 +391,7 @@ int ccx_whisper_trace_lanes(ccx_whisper* w, const char* path, int level) {
   w->stamp_path = w->stamps_on ? path : "";
   w->stamp_level = level >= 2 ? 2 : 1;
   CCX_HIP(w->ctx, hipMemset(w->stamp_count, 0, ccx_whisper::kMaxLanes * 4));
-  // the stamp kernels are nodes of the captured step graphs: drop the graphs so that the next decode captures the other kind
-  for (auto& g : w->graphs) hipGraphExecDestroy(g.second);
-  w->graphs.clear();
-  return CCX_OK;
+  return CCX_OK;      // (the stamp level is in the step plan: traced and untraced step graphs live side by side)
 }
 
 int ccx_whisper_finalize(ccx_whisper* w) {
@@ -686,15 +708,16 @@ static int project_cross_kv(ccx_whisper* w, int n, hipStream_t stream) {
 // ccx_whisper_decoder_logits -- so that the teacher-forced logits always come from the chain a decode of the same size would run.
 // CCX_FUSE_CROSS_Q=0: the two-launch cross-attention query of <= 16 rows; CCX_DEC_LNFREE=0: round 3's X-stream query;
 // CCX_XS_FUSE_Q=0: that query as a launch of its own; CCX_XS_FULL_LINES=0: the streaming kernel's half-line loads (cross_x.h).
-static void read_chain_switches(ccx_whisper* w) {
-  { const char* e = getenv("CCX_FUSE_CROSS_Q"); w->fuse_cross_q = e ? (atoi(e) != 0) : 1; }
-  { const char* e = getenv("CCX_DEC_LNFREE"); w->lnfree = !(e && strcmp(e, "0") == 0); }
-  { const char* e = getenv("CCX_XS_FUSE_Q"); w->xs_fuse_q = !e || atoi(e) != 0; }
-  w->xs_full_lines = ccx_xs_full_lines_switch();
+static void read_chain_switches(StepPlan& p) {
+  { const char* e = getenv("CCX_FUSE_CROSS_Q"); p.fuse_cross_q = e ? (atoi(e) != 0) : 1; }
+  { const char* e = getenv("CCX_DEC_LNFREE"); p.lnfree = !(e && strcmp(e, "0") == 0); }
+  { const char* e = getenv("CCX_XS_FUSE_Q"); p.xs_fuse_q = !e || atoi(e) != 0; }
+  p.xs_full_lines = ccx_xs_full_lines_switch();
 }
-// which cross attention a decode of B sequences uses, and the K/V it needs
+// which cross attention a decode of B = p.B sequences uses (-> p.xs_active), and the K/V it needs
 // (n_kv: the sequences whose K/V the rows read -- B itself, or the windows of a mapped decode)
-static int select_cross_path(ccx_whisper* w, int B, hipStream_t stream, int n_kv = -1) {
+static int select_cross_path(ccx_whisper* w, StepPlan& p, hipStream_t stream, int n_kv = -1) {
+  const int B = p.B;
   // CCX_CROSS_X_MIN_ROWS (read per call: tests flip it): smallest decode that takes the X-stream path.  Default 81: the streaming kernel
   // runs two blocks per sequence, and below ~160 blocks they do not fill the chip -- Whisper only, 24 / 32 / 48 / 64 / 96 x 30 s:
   // 300.7 / 311.8 / 340.0 / 357.9 / 404.3 ms per batch on the X-stream path against 208.6 / 223.3 / 289.4 / 329.3 / 427.2 on per-layer
@@ -704,9 +727,18 @@ static int select_cross_path(ccx_whisper* w, int B, hipStream_t stream, int n_kv
   const char* e = getenv("CCX_CROSS_X_MIN_ROWS");
   const int min_rows = e ? atoi(e) : ccx_whisper::kKvSeqs + 1;
   if (n_kv < 0) n_kv = B;
-  w->xs_active = w->xs_on && (B >= min_rows || n_kv > w->kv_cap);
-  if (w->xs_on && !w->xs_active && w->kv_ready < n_kv) CCX_TRY(project_cross_kv(w, n_kv, stream));
+  p.xs_active = w->xs_on && (B >= min_rows || n_kv > w->kv_cap);
+  if (w->xs_on && !p.xs_active && w->kv_ready < n_kv) CCX_TRY(project_cross_kv(w, n_kv, stream));
   return CCX_OK;
+}
+// the plan of a single lane of B rows whose cross attention runs uncapped (no other lane to leave room for): the chain switches of
+// the call, one token per step.  What a caller's steps do differently is set at its call site.
+static StepPlan single_lane_plan(const ccx_whisper* w, int B, int max_prompt) {
+  StepPlan p{};
+  p.B = B; p.sample_len = 1; p.max_prompt = max_prompt; p.cross_stream = 1;
+  p.stamp_level = w->stamps_on ? w->stamp_level : 0;
+  read_chain_switches(p);
+  return p;
 }
 
 int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out, void* stream_) {
@@ -802,11 +834,10 @@ double lane_probe_time(ccx_whisper* w, hipStream_t a, hipStream_t b) {
   return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// streams (up to `want`) that run concurrently with s0 and with each other; fewer if the probe finds fewer
-const std::vector<hipStream_t>& lane_streams_for(ccx_whisper* w, hipStream_t s0, int want) {
+// streams (up to kMaxLanes - 1) that run concurrently with s0 and with each other; fewer if the probe finds fewer
+const std::vector<hipStream_t>& lane_streams_for(ccx_whisper* w, hipStream_t s0) {
   auto it = w->lane_sets.find(s0);
   if (it != w->lane_sets.end()) return it->second;   // probed once per lane-0 stream (always for the maximum)
-  (void)want;
   std::vector<hipStream_t>& set = w->lane_sets[s0];
   set.clear();
   lane_probe_time(w, s0, nullptr);                        // warm-up (code object load)
@@ -836,87 +867,103 @@ int cross_split(int B, int H, bool lean) {
   return ns;
 }
 
+// device buffers of one traced beam decode: [steps][rows][beam + 1] proposals, [steps][rows] outcomes
+struct BeamTrace {
+  int *cid = nullptr, *tok = nullptr, *par = nullptr;
+  float *clp = nullptr, *score = nullptr;
+};
+
+// What a step reads and writes that is not mode: where its logits go, the lane's done counter, its stream -- and the per-call
+// buffers of the two kinds of step that are never captured (step_graph checks): ccx_whisper_align's pass and a traced beam decode.
+struct StepIo {
+  float* logits = nullptr;                   // row 0 = sequence plan.b0, row stride ld
+  long ld = 0;
+  int* n_done = nullptr;
+  hipStream_t stream = nullptr;
+  hipEvent_t stagger = nullptr;              // if set, recorded right before layer 0's cross attention
+  const AlignPass* align = nullptr;
+  const BeamTrace* trace = nullptr;
+};
+
 // ccx_whisper_align's hook in dec_step: the cross-attention probabilities of layer l's selected heads for the step's query rows
-int align_scores_hook(ccx_whisper* w, int l, const float* dq, int B, hipStream_t stream) {
-  const AlignPass& a = *w->align_pass;
+int align_scores_hook(ccx_whisper* w, const AlignPass& a, int l, const float* dq, int B, hipStream_t stream) {
   if (a.count[l] == 0) return CCX_OK;
   AlignScoresParams p{dq, w->dec[l].crossK, w->d.n_text_head, w->Spad, a.heads + a.first[l], a.hsel + a.first[l], a.count[l], a.n_keys,
                       w->al_P, a.Hsel, a.T, a.Mmax, a.t};
   return ccx_launch_align_scores(w->ctx, p, B, stream);
 }
 
+// what the select kernel and the beam kernels share; the row-addressed fields are the caller's
+void fill_select_params(const ccx_whisper* w, const StepPlan& p, const StepIo& io, DecSelectParams& sp) {
+  sp.logits = io.logits; sp.ld_logits = io.ld; sp.n_vocab = w->V4; sp.pos = w->pos + p.b0; sp.sample_len = p.sample_len; sp.n_done = io.n_done;
+  sp.suppress_mask = w->suppress_mask; sp.eot = w->rules.eot; sp.blank = w->rules.blank;
+  sp.no_speech = w->rules.no_speech; sp.timestamp_begin = w->rules.timestamp_begin;
+  sp.max_initial_ts = w->rules.max_initial_timestamp_index;
+  sp.tok_emb = w->tok_emb_f32; sp.pos_emb = w->dec_pos; sp.D = w->d.n_text_state;
+}
+
 // Tail of a step for the sequences [b0, b0 + B): logits of the final-LayerNorm rows (w->dxn) against the tied embedding, then
 // the select kernel (filters, argmax / sampling, state machine, next step's embedding).
-int dec_head(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select, int sample_len, int max_prompt, int* n_done,
-             hipStream_t stream) {
+int dec_head(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
   ccx_ctx* ctx = w->ctx;
   const ccx_whisper_dims& d = w->d;
-  const int D = d.n_text_state;
+  const int D = d.n_text_state, b0 = p.b0, B = p.B;
   const long ro = b0;
-  bf16_t* dxn = w->dxn + ro * D;
-  int* pos = w->pos + b0;
   {
     // logits against the tied embedding through the tiled GEMM (one summation order for every batch size; 284 -> 282 ms
     // for 192 sequences x 65 steps against the skinny kernel, no change at 8 sequences)
     GemmParams gp;
     memset(&gp, 0, sizeof(gp));
-    gp.A = dxn; gp.lda = D; gp.W = w->tok_emb_rm; gp.ldw = D; gp.M = B; gp.N = d.n_vocab; gp.K = D; gp.out = logits; gp.ldo = ld;
-    CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, gp, stream));
+    gp.A = w->dxn + ro * D; gp.lda = D; gp.W = w->tok_emb_rm; gp.ldw = D; gp.M = B; gp.N = d.n_vocab; gp.K = D; gp.out = io.logits; gp.ldo = io.ld;
+    CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, gp, io.stream));
   }
-  if (select && w->beam_on) {
+  if (p.select && p.beam_size > 0) {
     // beam search: the row's top beam + 1 proposals, then one block per window ranks, walks and rewrites its rows in place
     DecBeamParams bp;
     memset(&bp, 0, sizeof(bp));
-    DecSelectParams& sp = bp.sel;
-    CCX_REQUIRE(ctx, b0 == 0 && B % w->beam_size == 0, "dec_head: a beam decode runs in one lane of whole windows");
-    sp.logits = logits; sp.ld_logits = ld; sp.n_vocab = w->V4; sp.state = w->state; sp.cur_tok = w->cur_tok; sp.pos = pos; sp.gen = w->gen;
-    sp.sample_len = sample_len; sp.n_done = n_done; sp.suppress_mask = w->suppress_mask; sp.eot = w->rules.eot; sp.blank = w->rules.blank;
-    sp.no_speech = w->rules.no_speech; sp.timestamp_begin = w->rules.timestamp_begin;
-    sp.max_initial_ts = w->rules.max_initial_timestamp_index;
-    sp.tok_emb = w->tok_emb_f32; sp.pos_emb = w->dec_pos; sp.x = w->dx; sp.D = D;
-    bp.beam = w->beam_size; bp.max_cand = w->beam_maxc; bp.cand_id = w->beam_cand_id; bp.cand_lp = w->beam_cand_lp;
+    CCX_REQUIRE(ctx, b0 == 0 && B % p.beam_size == 0, "dec_head: a beam decode runs in one lane of whole windows");
+    fill_select_params(w, p, io, bp.sel);
+    bp.sel.state = w->state; bp.sel.cur_tok = w->cur_tok; bp.sel.gen = w->gen; bp.sel.x = w->dx;
+    bp.beam = p.beam_size; bp.max_cand = p.beam_maxc; bp.cand_id = w->beam_cand_id; bp.cand_lp = w->beam_cand_lp;
     bp.ind = w->beam_ind; bp.ind_ld = d.n_text_ctx; bp.row0 = 0;
     bp.fin_tok = w->beam_fin_tok; bp.fin_score = w->beam_fin_score; bp.fin_n = w->beam_fin_n; bp.fin_count = w->beam_fin_count;
-    bp.tr_cand_id = w->beam_tr_cid; bp.tr_cand_lp = w->beam_tr_clp; bp.tr_tok = w->beam_tr_tok; bp.tr_parent = w->beam_tr_par;
-    bp.tr_score = w->beam_tr_score; bp.tr_rows = w->beam_tr_rows;
-    CCX_TRY(ccx_launch_dec_beam(ctx, bp, B / w->beam_size, stream));
-  } else if (select) {
+    if (const BeamTrace* t = io.trace) {
+      bp.tr_cand_id = t->cid; bp.tr_cand_lp = t->clp; bp.tr_tok = t->tok; bp.tr_parent = t->par; bp.tr_score = t->score; bp.tr_rows = B;
+    }
+    CCX_TRY(ccx_launch_dec_beam(ctx, bp, B / p.beam_size, io.stream));
+  } else if (p.select) {
     DecSelectParams sp;
     memset(&sp, 0, sizeof(sp));
-    sp.logits = logits; sp.ld_logits = ld; sp.n_vocab = w->V4; sp.state = w->state + b0; sp.prompt = w->prompt + ro * max_prompt;
-    sp.max_prompt = max_prompt; sp.cur_tok = w->cur_tok + b0; sp.pos = pos; sp.gen = w->gen + ro * sample_len; sp.sample_len = sample_len;
-    sp.n_done = n_done; sp.suppress_mask = w->suppress_mask; sp.eot = w->rules.eot; sp.blank = w->rules.blank;
-    sp.no_speech = w->rules.no_speech; sp.timestamp_begin = w->rules.timestamp_begin;
-    sp.max_initial_ts = w->rules.max_initial_timestamp_index;
-    sp.tok_emb = w->tok_emb_f32; sp.pos_emb = w->dec_pos; sp.x = w->dx + ro * D; sp.D = D;
-    sp.sample_cfg = w->sample_cfg; sp.row0 = b0; sp.sample = w->sampling ? 1 : 0;
-    sp.stream_id = w->sid_on ? w->row_sid + b0 : nullptr;
-    CCX_TRY(ccx_launch_dec_select(ctx, sp, B, stream));
+    fill_select_params(w, p, io, sp);
+    sp.state = w->state + b0; sp.prompt = w->prompt + ro * p.max_prompt; sp.max_prompt = p.max_prompt;
+    sp.cur_tok = w->cur_tok + b0; sp.gen = w->gen + ro * p.sample_len; sp.x = w->dx + ro * D;
+    sp.sample_cfg = w->sample_cfg; sp.row0 = b0; sp.sample = p.sampling ? 1 : 0;
+    sp.stream_id = p.sid_on ? w->row_sid + b0 : nullptr;
+    CCX_TRY(ccx_launch_dec_select(ctx, sp, B, io.stream));
   }
   return CCX_OK;
 }
 
-// One decoder step for the B sequences [b0, b0 + B) on `stream` (a "lane": every per-sequence buffer is
+// One decoder step for the B sequences [b0, b0 + B) of the plan on io.stream (a "lane": every per-sequence buffer is
 // addressed through its row offset, so disjoint lanes can step concurrently on different streams).
-// logits go to `logits` (row 0 = sequence b0) with row stride ld.  The residual stream ping-pongs between
-// dx and dx2: out-proj / cross-out / FFN2 only write split-K partial slabs (pend) and the next LayerNorm
-// folds them in (decoder.hip).  `stagger`, if set, is recorded right before layer 0's cross attention.
-// `prefill_rows` = P > 0: the PROMPT PREFILL pass instead of a step -- B sequences x P prompt positions as B * P rows of the pf_*
+// The residual stream ping-pongs between dx and dx2: out-proj / cross-out / FFN2 only write split-K partial slabs (pend) and the
+// next LayerNorm folds them in (decoder.hip).
+// plan.prefill_rows = P > 0: the PROMPT PREFILL pass instead of a step -- B sequences x P prompt positions as B * P rows of the pf_*
 // buffers (row = sequence * P + position), self-KV written at every position, cross attention with all rows of a sequence
 // sharing its K/V, no logits / select (the caller takes the last prompt row of every sequence).
-int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select, int sample_len, int max_prompt, int* n_done,
-             hipStream_t stream, hipEvent_t stagger = nullptr, int lane_idx = 0, int prefill_rows = 0) {
+// Reads the plan, io and instance-constant members of w only (StepPlan's invariant).
+int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
   ccx_ctx* ctx = w->ctx;
   const ccx_whisper_dims& d = w->d;
   const int D = d.n_text_state, F = 4 * D, H = d.n_text_head, Tc = d.n_text_ctx;
   const float scale_log2e = 0.125f * 1.4426950408889634f;
-  const int ns = cross_split(B, H, w->cross_stream != 0);
-  long pstride = (long)B * D;
+  const int b0 = p.b0, nseq = p.B, prefill_rows = p.prefill_rows, lane_idx = p.lane_idx;
+  const bool pre = prefill_rows > 0, map_on = p.map_on != 0, xs_active = p.xs_active != 0;
+  const int B = pre ? nseq * prefill_rows : nseq;      // rows the chain works on
+  const int ns = cross_split(nseq, H, p.cross_stream != 0);
+  const long pstride = (long)B * D;
   const long ro = b0;
-  const bool pre = prefill_rows > 0;
-  const int nseq = B;                                  // sequences of this call
-  if (pre) B = nseq * prefill_rows;                    // rows the chain works on
-  pstride = (long)B * D;
+  hipStream_t stream = io.stream;
   float* cur = pre ? w->pf_x : w->dx + ro * D;     // stream (minus the pending partials); the step's embedding is in dx
   float* other = pre ? w->pf_x2 : w->dx2 + ro * D;
   float* pend = pre ? w->pf_pend : w->pend + 4 * ro * D;
@@ -930,11 +977,10 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
   const int* row_seq = pre ? w->pf_seq : nullptr;
   // mapped decode: the cross attention of row r reads window win[r] (prefill: the composed table), counted from window 0 -- the lane's
   // offset is in the map, not in the K/V base
-  const int* win = !w->map_on ? nullptr : (pre ? w->pf_win : w->row_win + b0);
-  const long cross_off = w->map_on ? 0 : ro * H * w->Spad * 64, self_off = ro * H * Tc * 64;
-  const int stamp_level = w->stamp_level;
+  const int* win = !map_on ? nullptr : (pre ? w->pf_win : w->row_win + b0);
+  const long cross_off = map_on ? 0 : ro * H * w->Spad * 64, self_off = ro * H * Tc * 64;
   auto stamp = [&](int tag, int level) {
-    if (w->stamps_on && level <= stamp_level)
+    if (level <= p.stamp_level)
       hipLaunchKernelGGL(dec_stamp_kernel, dim3(1), dim3(1), 0, stream, w->stamps + (size_t)lane_idx * ccx_whisper::kStampCap,
                          w->stamp_count + lane_idx, ccx_whisper::kStampCap, tag);
   };
@@ -985,11 +1031,11 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
   //  * prefill: all prompt rows of a sequence share its K/V.
   //  * otherwise the K/V caches: > 16 rows lean streaming (split-KV partials + combine in ccx_whisper_decoder_logits), <= 16 rows
   //    split-KV partials combined by the out projection.
-  const bool lnfree = w->xs_active && w->lnfree;
-  const bool xs_fused = w->xs_active && !lnfree && w->xs_fuse_q;
+  const bool lnfree = xs_active && p.lnfree;
+  const bool xs_fused = xs_active && !lnfree && p.xs_fuse_q;
   // (a mapped decode bypasses the fused query for the two launches it replaces: q is bit-identical, and the fused kernel's address
   //  arithmetic -- block-uniform bases in SGPR pairs under a 168-register cap -- stays what it is)
-  const bool fuse_q = !w->xs_active && w->fuse_cross_q && !pre && B <= 16 && D == 768 && !w->map_on;
+  const bool fuse_q = !xs_active && p.fuse_cross_q && !pre && B <= 16 && D == 768 && !map_on;
   const bool q_launch = !fuse_q && !lnfree && !xs_fused;    // the query projection as a launch of its own
   // LayerNorm-free query: the resolved rows and their tile statistics (X-stream instances only)
   bf16_t* xb = !lnfree ? nullptr : (pre ? w->pf_xb : w->dxb + ro * D);
@@ -1011,7 +1057,7 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     ap.q = dq; ap.k = L.selfK + self_off; ap.v = L.selfV + self_off; ap.H = H; ap.kv_T = Tc; ap.pos = pos; ap.scale_log2e = scale_log2e;
     ap.out_bf16 = dattn; ap.row_seq = row_seq;
     // beam search: a step's keys come through the cache indirection (the prefill writes and reads every row's own slot)
-    if (w->beam_on && !pre) { ap.ind = w->beam_ind; ap.ind_ld = Tc; }
+    if (p.beam_size > 0 && !pre) { ap.ind = w->beam_ind; ap.ind_ld = Tc; }
     CCX_TRY(ccx_launch_dec_attention(ctx, ap, B, 1, true, stream));
     stamp(17, 2);
     if (lnfree) {
@@ -1026,10 +1072,10 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
     stamp(18, 2);
     // cross attention
     if (q_launch) CCX_TRY(ln_linear(DEPI_F32, L.Wcq, L.bcq, D, L.lnc_g, L.lnc_b, dq, D, nullptr));
-    if (w->align_pass) CCX_TRY(align_scores_hook(w, l, dq, B, stream));   // ccx_whisper_align only: the step's row of P
+    if (io.align) CCX_TRY(align_scores_hook(w, *io.align, l, dq, B, stream));   // ccx_whisper_align only: the step's row of P
     stamp(1, 1);
-    if (l == 0 && stagger) CCX_HIP(ctx, hipEventRecord(stagger, stream));
-    if (w->xs_active) {
+    if (l == 0 && io.stagger) CCX_HIP(ctx, hipEventRecord(io.stagger, stream));
+    if (xs_active) {
       XsParams xp;
       memset(&xp, 0, sizeof(xp));
       if (lnfree) {
@@ -1041,13 +1087,13 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
       xp.q = dq; xp.WkT = L.WckT; xp.xq = pre ? w->pf_xq : w->xq + ro * H * D;
       xp.part_o = pre ? w->pf_xs_po : w->xs_po + ccx_xs_part_o_elems(ro, H, D);
       xp.part_ml = pre ? w->pf_xs_pml : w->xs_pml + ccx_xs_part_ml_elems(ro);
-      xp.X = (pre || w->map_on) ? w->xa : w->xa + ro * (long)d.n_audio_ctx * D; xp.x_seq_stride = (long)d.n_audio_ctx * D;
-      xp.row_seq = w->map_on ? win : row_seq;
+      xp.X = (pre || map_on) ? w->xa : w->xa + ro * (long)d.n_audio_ctx * D; xp.x_seq_stride = (long)d.n_audio_ctx * D;
+      xp.row_seq = map_on ? win : row_seq;
       xp.Wv = L.Wckv + (long)D * D; xp.bv = L.bckv + D; xp.out = dattn;
       xp.rows = B; xp.H = H; xp.S = d.n_audio_ctx; xp.D = D; xp.scale_log2e = scale_log2e;
-      xp.lds_pad = (w->cross_lds_pad > 0 && !pre) ? 65536 : 0;
+      xp.lds_pad = (p.cross_lds_pad > 0 && !pre) ? 65536 : 0;
       xp.rows_per_seq = pre ? prefill_rows : 0;
-      xp.full_lines = w->xs_full_lines;
+      xp.full_lines = p.xs_full_lines;
       CCX_TRY(ccx_launch_xs_cross_attention(ctx, xp, stream));
       if (xs_fused && pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
       stamp(2, 1);
@@ -1057,9 +1103,9 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
       memset(&ap, 0, sizeof(ap));
       ap.q = dq; ap.k = L.crossK + cross_off; ap.v = L.crossV + cross_off; ap.H = H; ap.kv_T = w->Spad; ap.pos = nullptr; ap.T = d.n_audio_ctx;
       ap.scale_log2e = scale_log2e; ap.part_o = part_o; ap.part_ml = part_ml; ap.out_bf16 = dattn;
-      ap.lds_pad = w->cross_lds_pad;
-      ap.stream_mode = (w->cross_stream && B > 16) ? 1 : 0;
-      ap.row_seq = win; ap.kv_map = w->map_on ? 1 : 0;
+      ap.lds_pad = p.cross_lds_pad;
+      ap.stream_mode = (p.cross_stream && B > 16) ? 1 : 0;
+      ap.row_seq = win; ap.kv_map = map_on ? 1 : 0;
       if (fuse_q) {
         ap.qx = cur; ap.q_pend = pend; ap.q_pend_n = pend_n; ap.q_pend_stride = pstride; ap.q_x_out = pend_n > 0 ? other : nullptr;
         ap.q_ln_g = L.lnc_g; ap.q_ln_b = L.lnc_b; ap.q_eps = 1e-5f; ap.q_W = L.Wcq; ap.q_bias = L.bcq; ap.q_K = D;
@@ -1068,7 +1114,7 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
         CCX_TRY(partial_linear(ACT_COMBINE, L.Wco, L.bco, D, nullptr));
       } else if (pre) {
         // two prompt rows and more per sequence share its K/V; a one-row pass runs as a decode step would
-        if (!w->map_on) ap.row_seq = prefill_rows > 1 ? row_seq : nullptr;
+        if (!map_on) ap.row_seq = prefill_rows > 1 ? row_seq : nullptr;
         ap.rows_per_seq = prefill_rows > 1 ? prefill_rows : 0;
         ap.lds_pad = 0; ap.stream_mode = 1;
         CCX_TRY(ccx_launch_dec_attention(ctx, ap, nseq, 1, true, stream));
@@ -1094,7 +1140,7 @@ int dec_step(ccx_whisper* w, int b0, int B, float* logits, long ld, bool select,
   // resolve the last partials + final LN, then logits against the tied embedding
   CCX_TRY(ccx_launch_dec_resolve_ln(ctx, cur, pend, pend_n, pstride, w->lnd_g, w->lnd_b, dxn, nullptr, B, D, 1e-5f, stream));
   if (pre) return CCX_OK;         // the caller gathers the last prompt row of every sequence out of pf_xn
-  CCX_TRY(dec_head(w, b0, B, logits, ld, select, sample_len, max_prompt, n_done, stream));
+  CCX_TRY(dec_head(w, p, io));
   stamp(3, 1);       // end of the step
   return CCX_OK;
 }
@@ -1121,7 +1167,6 @@ int upload_decode_state(ccx_whisper* w, const int32_t* prompt_ids, const int32_t
   CCX_HIP(w->ctx, hipMemcpyAsync(w->pos, ps.data(), B * 4, hipMemcpyHostToDevice, stream));
   CCX_HIP(w->ctx, hipMemcpyAsync(w->prompt, prompt_ids, (size_t)B * max_prompt * 4, hipMemcpyHostToDevice, stream));
   CCX_HIP(w->ctx, hipMemsetAsync(w->n_done, 0, ccx_whisper::kMaxLanes * 4, stream));
-  w->sampling = temperature > 0.f;
   unsigned cfg[4] = {0u, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), 0u};
   memcpy(&cfg[0], &temperature, 4);
   CCX_HIP(w->ctx, hipMemcpyAsync(w->sample_cfg, cfg, sizeof(cfg), hipMemcpyHostToDevice, stream));
@@ -1139,10 +1184,15 @@ int upload_decode_state(ccx_whisper* w, const int32_t* prompt_ids, const int32_t
 // tokens decoded there later).  Leaves the self-KV caches filled and the final-LayerNorm row of every sequence's last prompt
 // position in w->dxn -- and, for instances whose no-speech probability is read at the SOT position (ns_at_sot), the row of prompt
 // position prompt_len - 1 - sot_tail in w->tp_xn, gathered in whichever pass holds it (it can be the pass before the last token's).
-int run_prefill(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B, int P, int sample_len,
+// `plan`: the decode's plan over all its rows; `win_host`: the host copy of its row -> window map (plan.map_on), else null.
+int run_prefill(ccx_whisper* w, const StepPlan& plan, const int32_t* win_host, const int32_t* prompt_ids, const int32_t* prompt_lens, int P,
                 hipStream_t stream) {
   ccx_ctx* ctx = w->ctx;
-  const int D = w->d.n_text_state, C = ccx_whisper::kPrefillMax;
+  const int D = w->d.n_text_state, C = ccx_whisper::kPrefillMax, B = plan.B, max_prompt = plan.max_prompt;
+  StepPlan pass = plan;
+  pass.select = 0;
+  StepIo io;
+  io.stream = stream;
   for (int t0 = 0; t0 < P; t0 += C) {
     const int Pc = P - t0 < C ? P - t0 : C, R = B * Pc;
     std::vector<int> tok(R), ps(R), sq(R), last(B), sot_row(B);
@@ -1161,15 +1211,16 @@ int run_prefill(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_tok, tok.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_pos, ps.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_seq, sq.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
-    std::vector<int> wn(w->map_on ? R : 0);     // mapped decode: the two maps composed, a prefill row's window is win[pf_seq[row]]
-    if (w->map_on) {
-      for (int r = 0; r < R; r++) wn[r] = w->win_host[sq[r]];
+    std::vector<int> wn(plan.map_on ? R : 0);   // mapped decode: the two maps composed, a prefill row's window is win[pf_seq[row]]
+    if (plan.map_on) {
+      for (int r = 0; r < R; r++) wn[r] = win_host[sq[r]];
       CCX_HIP(ctx, hipMemcpyAsync(w->pf_win, wn.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
     }
     CCX_HIP(ctx, hipMemcpyAsync(w->pf_last, last.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream));
     CCX_TRY(ccx_launch_dec_embed(ctx, w->tok_emb_f32, w->dec_pos, w->pf_tok, w->pf_pos, w->pf_x, R, D, stream));
     CCX_HIP(ctx, hipStreamSynchronize(stream));     // host tables go out of scope
-    CCX_TRY(dec_step(w, 0, B, nullptr, 0, false, sample_len, max_prompt, nullptr, stream, nullptr, 0, Pc));
+    pass.prefill_rows = Pc;
+    CCX_TRY(dec_step(w, pass, io));
     CCX_TRY(ccx_launch_dec_gather_rows(ctx, w->pf_xn, w->pf_last, w->dxn, B, D, stream));
     if (w->ns_at_sot()) CCX_TRY(ccx_launch_dec_gather_rows(ctx, w->pf_xn, w->tp_idx, w->tp_xn, B, D, stream));
   }
@@ -1217,17 +1268,19 @@ int ccx_whisper_decoder_logits(ccx_whisper* w, const int32_t* tokens, int B, int
     CCX_REQUIRE(ctx, tokens[i] >= 0 && tokens[i] < w->d.n_vocab, "decoder_logits: token id %d out of range", tokens[i]);
   std::vector<int32_t> lens(B, T + 1);  // never leaves the prompt phase: every step feeds tokens[b][pos]
   // prompt buffer rows are `T` wide here
-  read_chain_switches(w);
-  CCX_TRY(select_cross_path(w, B, stream));
+  StepPlan plan = single_lane_plan(w, B, T);
+  plan.cross_stream = 0;
+  CCX_TRY(select_cross_path(w, plan, stream));
   CCX_TRY(upload_decode_state(w, tokens, lens.data(), T, B, 0.f, 0, stream));
   const long V = w->d.n_vocab;
-  w->cross_lds_pad = 0;   // single lane: the cross attention runs uncapped
-  w->cross_stream = 0;
+  StepIo io;
+  io.logits = w->dlogits; io.ld = w->Vpad; io.n_done = w->n_done; io.stream = stream;
   for (int t = 0; t < T; t++) {
     // the select kernel (prompt phase) advances cur_tok/pos; on the last step it would read prompt[T] -> skip it.
     // The logits GEMM stores whole 16-column groups, so it writes the padded workspace rows (ld = Vpad) and the n_vocab valid
     // columns are copied out: writing [B, T, V] in place would spill V % 16 columns into the next row / past the tensor.
-    CCX_TRY(dec_step(w, 0, B, w->dlogits, w->Vpad, t + 1 < T, 1, T, w->n_done, stream));
+    plan.select = t + 1 < T;
+    CCX_TRY(dec_step(w, plan, io));
     CCX_HIP(ctx, hipMemcpy2DAsync(logits_dev + (long)t * V, (size_t)T * V * 4, w->dlogits, (size_t)w->Vpad * 4, (size_t)V * 4, B,
                                   hipMemcpyDeviceToDevice, stream));
   }
@@ -1346,25 +1399,24 @@ int ccx_whisper_align_probs(ccx_whisper* w, const int32_t* tokens, const int32_t
   pass.heads = i_heads; pass.hsel = i_hsel; pass.n_keys = i_keys; pass.Hsel = n_heads; pass.T = T; pass.Mmax = Mmax;
 
   // the pass runs on the per-layer K / V form with the query projection as a launch of its own: every row's query is in dq
-  read_chain_switches(w);
-  w->fuse_cross_q = 0;
-  w->xs_active = false;
+  StepPlan plan = single_lane_plan(w, B, T);
+  plan.cross_stream = 0;
+  plan.fuse_cross_q = 0;
+  plan.xs_active = 0;       // whatever the size: no select_cross_path here
   if (w->kv_ready < B) CCX_TRY(project_cross_kv(w, B, stream));
   std::vector<int32_t> plens(B, T + 1);    // never leaves the prompt phase: every step feeds tokens[b][pos]
   CCX_TRY(upload_decode_state(w, padded.data(), plens.data(), T, B, 0.f, 0, stream));
-  w->cross_lds_pad = 0;
-  w->cross_stream = 0;
-  struct Guard { ccx_whisper* w; ~Guard() { w->align_pass = nullptr; } } guard{w};
-  w->align_pass = &pass;
+  StepIo io;
+  io.logits = w->dlogits; io.ld = w->Vpad; io.n_done = w->n_done; io.stream = stream; io.align = &pass;
   for (int t = 0; t < T; t++) {
     pass.t = t;
-    CCX_TRY(dec_step(w, 0, B, w->dlogits, w->Vpad, t + 1 < T, 1, T, w->n_done, stream));
+    plan.select = t + 1 < T;
+    CCX_TRY(dec_step(w, plan, io));
     if (token_prob_out && t >= row0 && t <= T - 3) {      // only reads the step's logits: column t of the two [B][T] tables
       DecPickProbsParams pp{w->dlogits, (long)w->Vpad, prob_hi, w->al_picks + t, (long)T, tprob + t, (long)T};
       CCX_TRY(ccx_launch_dec_pick_probs(ctx, pp, B, stream));
     }
   }
-  w->align_pass = nullptr;
   AlignMatrixParams mp{w->al_P, w->al_A, n_heads, T, Mmax, i_rows, i_keys};
   CCX_TRY(ccx_launch_align_matrix(ctx, mp, B, stream));
   AlignDtwParams dp{w->al_A, T, Mmax, row0, i_r1, i_keys, w->al_trace, (long)((size_t)(T + 1) * (Mmax + 1)), i_text, i_time, (int)path_cap, i_len, i_jump};
@@ -1405,23 +1457,18 @@ int ccx_whisper_detect_language(ccx_whisper* w, int B, int lang_begin, int n_lan
               lang_begin + n_lang, w->d.n_vocab);
   CCX_REQUIRE(ctx, lang_token_out != nullptr, "ccx_whisper_detect_language: lang_token_out is NULL");
   CCX_REQUIRE(ctx, w->rules.sot >= 0, "ccx_whisper_detect_language: rules.sot = %d is no token", w->rules.sot);
-  if (stream == nullptr) {
-    // as ccx_whisper_decode: order after everything queued on the caller's (null) stream, then run on our own
-    CCX_HIP(ctx, hipEventRecord(w->own_event, nullptr));
-    CCX_HIP(ctx, hipStreamWaitEvent(w->own_stream, w->own_event, 0));
-    stream = w->own_stream;
-  }
+  CCX_TRY(own_stream_if_null(w, &stream));     // as ccx_whisper_decode
   CCX_TRY(ensure_token_probs_scratch(w));
   // one step over [sot] at position 0 for every window: the step kernels and the cross-attention path select_cross_path picks for
   // B rows, as ONE lane (a decode of 96 rows and more splits into lanes; a row's numbers do not depend on the split)
-  read_chain_switches(w);
-  CCX_TRY(select_cross_path(w, B, stream));
+  StepPlan plan = single_lane_plan(w, B, 1);
+  CCX_TRY(select_cross_path(w, plan, stream));
   const std::vector<int32_t> sot(B, w->rules.sot), one(B, 1);
   CCX_TRY(upload_decode_state(w, sot.data(), one.data(), 1, B, 0.f, 0, stream));
-  w->cross_stream = 1;
-  w->cross_lds_pad = 0;      // a single lane: the cross attention runs uncapped
-  w->last_cross_path = w->xs_active ? 2 : (B > 16 ? 1 : 0);
-  CCX_TRY(dec_step(w, 0, B, w->dlogits, w->Vpad, false, 1, 1, w->n_done, stream));
+  w->last_cross_path = plan.xs_active ? 2 : (B > 16 ? 1 : 0);
+  StepIo io;
+  io.logits = w->dlogits; io.ld = w->Vpad; io.n_done = w->n_done; io.stream = stream;
+  CCX_TRY(dec_step(w, plan, io));
   // dec_step left the logits of every row in w->dlogits: the softmax over the language tokens only (the GEMM is not repeated)
   DecTokenProbsParams tp;
   memset(&tp, 0, sizeof(tp));
@@ -1439,7 +1486,7 @@ int ccx_whisper_prepare_lanes(ccx_whisper* w, void* stream_) {
   CCX_REQUIRE(w->ctx, w->finalized, "whisper: not finalized");
   hipStream_t stream = stream_ ? (hipStream_t)stream_ : w->own_stream;
   CCX_HIP(w->ctx, hipDeviceSynchronize());
-  (void)lane_streams_for(w, stream, ccx_whisper::kMaxLanes - 1);
+  (void)lane_streams_for(w, stream);
   return CCX_OK;
 }
 
@@ -1450,33 +1497,42 @@ int ccx_whisper_decode_greedy(ccx_whisper* w, const int32_t* prompt_ids, const i
                             no_speech_prob_out, stream_);
 }
 
-// The decode behind ccx_whisper_decode (win == NULL: row r reads window r, noise stream r) and ccx_whisper_decode_rows (B rows over
-// n_windows encoded windows: row r reads window win[r]; sids, if given, names every row's noise stream).  Both checked by the callers.
-// beam != NULL (ccx_whisper_decode_beam): the B rows are beam->G windows of beam->beam rows over the map; tokens_out / n_tokens_out /
-// sum_logprob_out are then [G][C][sample_len] / [G][C] / [G][C] and no_speech_prob_out [G].
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// the decode driver behind ccx_whisper_decode, ccx_whisper_decode_rows and ccx_whisper_decode_beam: decode_impl and its phases
+// ---------------------------------------------------------------------------------------------
+namespace {
+
 struct BeamCall {
   int G, beam, maxc;
   int32_t* n_hyp_out;
   const ccx_beam_trace* trace;
 };
-static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B, int sample_len,
-                       float temperature, uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out,
-                       float* no_speech_prob_out, void* stream_, const int32_t* win, int n_windows, const int32_t* sids,
-                       const BeamCall* beam = nullptr) {
-  if (!w) return CCX_ERR_ARG;
-  CCX_REQUIRE(w->ctx, temperature >= 0.f && temperature == temperature, "decode: temperature must be >= 0");
-  hipStream_t stream = (hipStream_t)stream_;
+
+// what one beam decode owns: the staged cache indirection (until the state upload synchronises) and a traced call's device buffers
+struct BeamWork {
+  std::vector<unsigned short> ind_init;
+  BeamTrace trace;
+  ~BeamWork() { hipFree(trace.cid); hipFree(trace.clp); hipFree(trace.tok); hipFree(trace.par); hipFree(trace.score); }
+};
+
+// a lane: its plan (select = 1), its io (its own stream, logits rows, done counter) and the step graph it replays, if any
+struct Lane { StepPlan plan; StepIo io; hipGraphExec_t exec; };
+struct Lanes {
+  Lane lane[ccx_whisper::kMaxLanes];
+  int n = 0;
+};
+
+// (1) the arguments of a decode.  -> *max_pl: the longest prompt
+int check_decode_args(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B, int sample_len, float temperature,
+                      const int32_t* tokens_out, int* max_pl) {
   ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, temperature >= 0.f && temperature == temperature, "decode: temperature must be >= 0");
   CCX_REQUIRE(ctx, w->finalized && w->rules_set, "whisper: not finalized or rules not set");
   CCX_REQUIRE(ctx, prompt_ids && prompt_lens && tokens_out && B >= 1 && B <= w->max_batch, "decode_greedy: bad arguments");
-  if (stream == nullptr) {
-    // order after everything already queued on the caller's (null) stream, then run on our own
-    CCX_HIP(ctx, hipEventRecord(w->own_event, nullptr));
-    CCX_HIP(ctx, hipStreamWaitEvent(w->own_stream, w->own_event, 0));
-    stream = w->own_stream;
-  }
   CCX_REQUIRE(ctx, sample_len >= 1 && sample_len <= w->sample_cap && max_prompt >= 1 && max_prompt <= w->max_prompt_cap, "decode_greedy: sample_len/max_prompt out of range");
-  int max_pl = 0;
+  *max_pl = 0;
   for (int b = 0; b < B; b++) {
     CCX_REQUIRE(ctx, prompt_lens[b] >= 1 && prompt_lens[b] <= max_prompt, "decode_greedy: prompt_lens[%d]=%d out of range", b, prompt_lens[b]);
     CCX_REQUIRE(ctx, prompt_lens[b] + sample_len - 1 <= w->d.n_text_ctx, "decode_greedy: prompt %d + sample_len %d exceeds n_text_ctx", prompt_lens[b], sample_len);
@@ -1486,201 +1542,183 @@ static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
       const int t = prompt_ids[(size_t)b * max_prompt + i];
       CCX_REQUIRE(ctx, t >= 0 && t < w->d.n_vocab, "decode_greedy: prompt token %d out of range", t);
     }
-    if (prompt_lens[b] > max_pl) max_pl = prompt_lens[b];
+    if (prompt_lens[b] > *max_pl) *max_pl = prompt_lens[b];
   }
-  // prompts of 2 tokens and more are prefilled, kPrefillMax positions per pass (CCX_PREFILL=0: one decode step per prompt token, round
-  // 1's way)
-  const int prefill_on = [] { const char* e = getenv("CCX_PREFILL"); return e ? atoi(e) : 1; }();     // read per call: tests flip it
-  // ... and every prompt of an instance that reads its no-speech probability at the SOT position with the ranged softmax
-  const bool ns_at_sot = w->ns_at_sot();
-  CCX_REQUIRE(ctx, !ns_at_sot || prefill_on, "decode: CCX_PREFILL=0 is not available on an instance with a SOT tail (%d) or with n_vocab = %d, no multiple of 4: "
-              "its no-speech probability is taken from the prefill", w->sot_tail, w->d.n_vocab);
-  const bool prefill = prefill_on && (max_pl >= 2 || ns_at_sot);
-  if (ns_at_sot) CCX_TRY(ensure_token_probs_scratch(w));
-  read_chain_switches(w);
-  CCX_TRY(select_cross_path(w, B, stream, win ? n_windows : -1));
-  // the map and the ids: uploaded once per call (the state upload below synchronises), in force until the call returns
-  struct MapGuard {
-    ccx_whisper* w;
-    ~MapGuard() {
-      w->map_on = false; w->sid_on = false; w->win_host = nullptr; w->beam_on = false;
-      if (w->beam_tr_cid) {
-        hipFree(w->beam_tr_cid); hipFree(w->beam_tr_clp); hipFree(w->beam_tr_tok); hipFree(w->beam_tr_par); hipFree(w->beam_tr_score);
-        w->beam_tr_cid = w->beam_tr_tok = w->beam_tr_par = nullptr; w->beam_tr_clp = w->beam_tr_score = nullptr;
-      }
-    }
-  } map_guard{w};
-  if (win) {
-    if (!w->row_win) {
-      CCX_TRY(w->store.alloc(&w->row_win, (size_t)w->max_batch, true));
-      CCX_TRY(w->store.alloc(&w->row_sid, (size_t)w->max_batch, true));
-      CCX_TRY(w->store.alloc(&w->pf_win, (size_t)w->max_batch * ccx_whisper::kPrefillMax, true));
-    }
-    CCX_HIP(ctx, hipMemcpyAsync(w->row_win, win, (size_t)B * 4, hipMemcpyHostToDevice, stream));
-    if (sids) CCX_HIP(ctx, hipMemcpyAsync(w->row_sid, sids, (size_t)B * 4, hipMemcpyHostToDevice, stream));
-    w->map_on = true; w->sid_on = sids != nullptr; w->win_host = win;
-  }
-  std::vector<unsigned short> ind_init;
-  if (beam) {
-    CCX_REQUIRE(ctx, prefill_on, "ccx_whisper_decode_beam: CCX_PREFILL=0 is not available to a beam decode (its kernels have no prompt phase)");
-    const int Tc = w->d.n_text_ctx;
-    if (!w->beam_ind) {
-      const size_t mb = (size_t)w->max_batch;
-      CCX_TRY(w->store.alloc(&w->beam_ind, mb * Tc, true));
-      CCX_TRY(w->store.alloc(&w->beam_cand_id, mb * (kBeamMax + 1), true));
-      CCX_TRY(w->store.alloc(&w->beam_cand_lp, mb * (kBeamMax + 1), true));
-      CCX_TRY(w->store.alloc(&w->beam_fin_tok, mb * kBeamCandMax * w->sample_cap, true));
-      CCX_TRY(w->store.alloc(&w->beam_fin_score, mb * kBeamCandMax, true));
-      CCX_TRY(w->store.alloc(&w->beam_fin_n, mb * kBeamCandMax, true));
-      CCX_TRY(w->store.alloc(&w->beam_fin_count, mb, true));
-    }
-    // after the prefill every row's keys are its own: ind[r][t] = r (the update kernel rewrites a row's entries from its parent's)
-    ind_init.resize((size_t)B * Tc);
-    for (int r = 0; r < B; r++)
-      for (int t = 0; t < Tc; t++) ind_init[(size_t)r * Tc + t] = (unsigned short)r;
-    CCX_HIP(ctx, hipMemcpyAsync(w->beam_ind, ind_init.data(), ind_init.size() * 2, hipMemcpyHostToDevice, stream));
-    CCX_HIP(ctx, hipMemsetAsync(w->beam_fin_count, 0, (size_t)beam->G * 4, stream));
-    if (beam->trace) {
-      const size_t n = (size_t)sample_len * B, K = (size_t)beam->beam + 1;
-      CCX_HIP(ctx, hipMalloc((void**)&w->beam_tr_cid, n * K * 4));
-      CCX_HIP(ctx, hipMalloc((void**)&w->beam_tr_clp, n * K * 4));
-      CCX_HIP(ctx, hipMalloc((void**)&w->beam_tr_tok, n * 4));
-      CCX_HIP(ctx, hipMalloc((void**)&w->beam_tr_par, n * 4));
-      CCX_HIP(ctx, hipMalloc((void**)&w->beam_tr_score, n * 4));
-      CCX_HIP(ctx, hipMemsetAsync(w->beam_tr_cid, 0xFF, n * K * 4, stream));
-      CCX_HIP(ctx, hipMemsetAsync(w->beam_tr_clp, 0xFF, n * K * 4, stream));
-      CCX_HIP(ctx, hipMemsetAsync(w->beam_tr_tok, 0xFF, n * 4, stream));
-      CCX_HIP(ctx, hipMemsetAsync(w->beam_tr_par, 0xFF, n * 4, stream));
-      CCX_HIP(ctx, hipMemsetAsync(w->beam_tr_score, 0xFF, n * 4, stream));
-      w->beam_tr_rows = B;
-    }
-    w->beam_on = true; w->beam_size = beam->beam; w->beam_maxc = beam->maxc;
-  }
-  CCX_TRY(upload_decode_state(w, prompt_ids, prompt_lens, max_prompt, B, temperature, seed, stream, prefill));
-  // steps still to run after the (eager) first one: the prefill already covers the prompt AND takes the first sample below
-  const int total_steps = prefill ? sample_len : max_pl - 1 + sample_len;
-  const bool use_graph = getenv("CCX_NO_GRAPH") == nullptr && !(beam && beam->trace);   // (a traced beam decode: per-call buffers)
-  const long ld = w->Vpad;
+  return CCX_OK;
+}
 
-  // ---- lanes: row ranges [b0, b0 + Bl) stepping concurrently (CCX_DEC_LANES overrides the default) ----
-  int nl = 1;
-  {
-    const char* e = getenv("CCX_DEC_LANES");
-    const int forced = e ? atoi(e) : 0;
-    if (forced >= 1) nl = forced;
-    // measured at 192 sequences x 65 steps: 1 lane 292.5, 2 286.8, 3 284.9, 4 284.8 ms; pipeline step with 384-sequence groups: 2 lanes
-    // 710.0, 3 lanes 698.0 ms; with 768-sequence groups: 1 lane 721.5, 2 lanes 676.6, 3 lanes 687.5, 4 lanes 704.0 ms
-    // with the cross attention against the encoder output (half the bytes: the chain weighs more): 768-sequence groups 2 lanes 561.3,
-    // 3 lanes 557.9 ms per pipeline step
-    // ... 384-sequence groups 3 lanes 598.6, 2 lanes 616.6 ms; 192-sequence groups (the sequential schedule) 1 lane 768.1, 2 lanes
-    // 779.5, 3 lanes 793.2 ms: below ~128 rows per lane the streaming launches no longer fill the chip
-    else if (w->xs_on) nl = B >= 320 ? 3 : 1;
-    else nl = B >= 640 ? 2 : (B >= 144 ? 3 : (B >= 96 ? 2 : 1));
-    if (nl > ccx_whisper::kMaxLanes) nl = ccx_whisper::kMaxLanes;
-    while (nl > 1 && B / nl < 16) nl--;
-    if (beam) nl = 1;      // a window's rows are rewritten by one block and counted by one n_done: one lane
+// (2) the row -> window map and the stream ids of a mapped decode: uploaded once per call (the state upload synchronises)
+int upload_row_map(ccx_whisper* w, const int32_t* win, const int32_t* sids, int B, hipStream_t stream) {
+  if (!w->row_win) {
+    CCX_TRY(w->store.alloc(&w->row_win, (size_t)w->max_batch, true));
+    CCX_TRY(w->store.alloc(&w->row_sid, (size_t)w->max_batch, true));
+    CCX_TRY(w->store.alloc(&w->pf_win, (size_t)w->max_batch * ccx_whisper::kPrefillMax, true));
   }
+  CCX_HIP(w->ctx, hipMemcpyAsync(w->row_win, win, (size_t)B * 4, hipMemcpyHostToDevice, stream));
+  if (sids) CCX_HIP(w->ctx, hipMemcpyAsync(w->row_sid, sids, (size_t)B * 4, hipMemcpyHostToDevice, stream));
+  return CCX_OK;
+}
+
+// (2) a beam decode's workspaces (first use), its cache indirection and finished counts, and a traced call's buffers
+int setup_beam(ccx_whisper* w, const BeamCall& beam, int B, int sample_len, hipStream_t stream, BeamWork* bw) {
+  ccx_ctx* ctx = w->ctx;
+  const int Tc = w->d.n_text_ctx;
+  if (!w->beam_ind) {
+    const size_t mb = (size_t)w->max_batch;
+    CCX_TRY(w->store.alloc(&w->beam_ind, mb * Tc, true));
+    CCX_TRY(w->store.alloc(&w->beam_cand_id, mb * (kBeamMax + 1), true));
+    CCX_TRY(w->store.alloc(&w->beam_cand_lp, mb * (kBeamMax + 1), true));
+    CCX_TRY(w->store.alloc(&w->beam_fin_tok, mb * kBeamCandMax * w->sample_cap, true));
+    CCX_TRY(w->store.alloc(&w->beam_fin_score, mb * kBeamCandMax, true));
+    CCX_TRY(w->store.alloc(&w->beam_fin_n, mb * kBeamCandMax, true));
+    CCX_TRY(w->store.alloc(&w->beam_fin_count, mb, true));
+  }
+  // after the prefill every row's keys are its own: ind[r][t] = r (the update kernel rewrites a row's entries from its parent's)
+  bw->ind_init.resize((size_t)B * Tc);
+  for (int r = 0; r < B; r++)
+    for (int t = 0; t < Tc; t++) bw->ind_init[(size_t)r * Tc + t] = (unsigned short)r;
+  CCX_HIP(ctx, hipMemcpyAsync(w->beam_ind, bw->ind_init.data(), bw->ind_init.size() * 2, hipMemcpyHostToDevice, stream));
+  CCX_HIP(ctx, hipMemsetAsync(w->beam_fin_count, 0, (size_t)beam.G * 4, stream));
+  if (beam.trace) {
+    const size_t n = (size_t)sample_len * B, K = (size_t)beam.beam + 1;
+    BeamTrace& t = bw->trace;
+    const size_t bytes[5] = {n * K * 4, n * K * 4, n * 4, n * 4, n * 4};
+    void** bufs[5] = {(void**)&t.cid, (void**)&t.clp, (void**)&t.tok, (void**)&t.par, (void**)&t.score};
+    for (int i = 0; i < 5; i++) CCX_HIP(ctx, hipMalloc(bufs[i], bytes[i]));
+    for (int i = 0; i < 5; i++) CCX_HIP(ctx, hipMemsetAsync(*bufs[i], 0xFF, bytes[i], stream));
+  }
+  return CCX_OK;
+}
+
+// (4) The lane policy: the row ranges [b0, b0 + B) that step concurrently.  `forced`: CCX_DEC_LANES (0: the default below);
+// `max_lanes`: kMaxLanes, or the concurrent streams the probe found.
+struct RowRange { int b0, B; };
+std::vector<RowRange> lane_policy(int B, bool xs_on, bool beam, int forced, int max_lanes) {
+  int nl = 1;
+  if (forced >= 1) nl = forced;
+  // measured at 192 sequences x 65 steps: 1 lane 292.5, 2 286.8, 3 284.9, 4 284.8 ms; pipeline step with 384-sequence groups: 2 lanes
+  // 710.0, 3 lanes 698.0 ms; with 768-sequence groups: 1 lane 721.5, 2 lanes 676.6, 3 lanes 687.5, 4 lanes 704.0 ms
+  // with the cross attention against the encoder output (half the bytes: the chain weighs more): 768-sequence groups 2 lanes 561.3,
+  // 3 lanes 557.9 ms per pipeline step
+  // ... 384-sequence groups 3 lanes 598.6, 2 lanes 616.6 ms; 192-sequence groups (the sequential schedule) 1 lane 768.1, 2 lanes
+  // 779.5, 3 lanes 793.2 ms: below ~128 rows per lane the streaming launches no longer fill the chip
+  else if (xs_on) nl = B >= 320 ? 3 : 1;
+  else nl = B >= 640 ? 2 : (B >= 144 ? 3 : (B >= 96 ? 2 : 1));
+  if (nl > max_lanes) nl = max_lanes;
+  while (nl > 1 && B / nl < 16) nl--;
+  if (beam) nl = 1;      // a window's rows are rewritten by one block and counted by one n_done: one lane
+  const int per = ccx_cdiv(ccx_cdiv(B, nl), 16) * 16;   // lane sizes in multiples of one MFMA row tile
+  std::vector<RowRange> r;
+  for (int b0 = 0; (int)r.size() < nl && b0 < B; b0 += per) r.push_back({b0, b0 + per <= B ? per : B - b0});
+  return r;
+}
+
+// (4) the lanes of a decode: the policy's ranges (fewer if the probe finds fewer concurrent streams), each with the decode's plan
+// narrowed to its rows and with its own stream, logits rows and done counter.  Sets base.cross_lds_pad, which the lanes share.
+int plan_lanes(ccx_whisper* w, StepPlan& base, hipStream_t stream, const BeamTrace* trace, Lanes* L) {
+  const char* e = getenv("CCX_DEC_LANES");
+  const int forced = e ? atoi(e) : 0;
+  const bool beam = base.beam_size > 0;
+  std::vector<RowRange> rows = lane_policy(base.B, w->xs_on, beam, forced, ccx_whisper::kMaxLanes);
   const std::vector<hipStream_t>* extra = nullptr;
-  if (nl > 1) {
-    extra = &lane_streams_for(w, stream, nl - 1);
-    if ((int)extra->size() + 1 < nl) nl = (int)extra->size() + 1;
+  if (rows.size() > 1) {
+    extra = &lane_streams_for(w, stream);
+    if (extra->size() + 1 < rows.size()) rows = lane_policy(base.B, w->xs_on, beam, forced, (int)extra->size() + 1);
   }
   // While lanes overlap, the cross attention of one lane (4,608 short blocks that fill every wave slot) makes the other
   // lanes' 5-8 us kernels queue for a slot.  Its blocks therefore claim 64 KB of LDS they do not use: two blocks per CU
   // still keep HBM saturated (each wave has 16 KB of loads in flight; 49.4 -> 51.3 us per launch) and the pipeline step
   // drops 924 -> 897 ms (3 blocks per CU: 910; 4: 919; 1: 979).
-  {
-    w->cross_stream = 1;
-    // lean streaming: ONE 4-wave block per CU (98 KB of claimed LDS), each wave with 8-16 KB in flight.  The claim only exists to
-    // leave room for the OTHER lanes' chain kernels: a single lane runs uncapped.
-    w->cross_lds_pad = nl > 1 ? 98304 : 0;
+  // Lean streaming: ONE 4-wave block per CU (98 KB of claimed LDS), each wave with 8-16 KB in flight.  The claim only exists to
+  // leave room for the OTHER lanes' chain kernels: a single lane runs uncapped.
+  base.cross_lds_pad = rows.size() > 1 ? 98304 : 0;
+  const long ld = w->Vpad;
+  L->n = (int)rows.size();
+  for (int i = 0; i < L->n; i++) {
+    Lane& l = L->lane[i];
+    l.plan = base;
+    l.plan.b0 = rows[i].b0; l.plan.B = rows[i].B; l.plan.lane_idx = i; l.plan.select = 1;
+    l.io = StepIo{};
+    l.io.logits = w->dlogits + (long)rows[i].b0 * ld; l.io.ld = ld; l.io.n_done = w->n_done + i;
+    l.io.stream = i == 0 ? stream : (*extra)[i - 1];
+    l.io.trace = trace;
+    l.exec = nullptr;
   }
-  struct Lane { int b0, B; hipStream_t s; hipGraphExec_t exec; };
-  Lane lanes[ccx_whisper::kMaxLanes];
-  {
-    const int per = ccx_cdiv(ccx_cdiv(B, nl), 16) * 16;   // lane sizes in multiples of one MFMA row tile
-    int b0 = 0, n = 0;
-    for (; n < nl && b0 < B; n++) {
-      lanes[n].b0 = b0; lanes[n].B = (b0 + per <= B) ? per : B - b0;
-      lanes[n].s = n == 0 ? stream : (*extra)[n - 1];
-      lanes[n].exec = nullptr;
-      b0 += lanes[n].B;
-    }
-    nl = n;
+  return CCX_OK;
+}
+
+// (5) the prompt prefill, the no-speech probability at the SOT position and the first sample of every sequence, all on `stream`
+int prefill_and_first_sample(ccx_whisper* w, const StepPlan& base, const Lanes& L, const int32_t* win, const int32_t* prompt_ids,
+                             const int32_t* prompt_lens, int max_pl, hipStream_t stream) {
+  CCX_TRY(run_prefill(w, base, win, prompt_ids, prompt_lens, max_pl, stream));
+  // no-speech probability from the raw logits at the SOT position, over the ids of the vocabulary (eager, before the captured steps;
+  // w->dlogits is free until the first sample below)
+  if (w->ns_at_sot()) CCX_TRY(token_probs_of_rows(w, w->tp_xn, base.B, 0, w->d.n_vocab, w->rules.no_speech, nullptr, stream));
+  // first sample of every sequence, lane by lane (each lane counts its own finished sequences)
+  for (int i = 0; i < L.n; i++) {
+    StepIo io = L.lane[i].io;
+    io.stream = stream;
+    CCX_TRY(dec_head(w, L.lane[i].plan, io));
   }
-  // which cross attention the steps of this decode run (lane 0; a short last lane of <= 16 rows takes the <= 16-row kernels of its path)
-  w->last_cross_path = w->xs_active ? 2 : ((w->cross_stream && lanes[0].B > 16) ? 1 : 0);
-  if (prefill) {
-    CCX_TRY(run_prefill(w, prompt_ids, prompt_lens, max_prompt, B, max_pl, sample_len, stream));
-    // no-speech probability from the raw logits at the SOT position, over the ids of the vocabulary (eager, before the captured steps;
-    // w->dlogits is free until the first sample below)
-    if (ns_at_sot) CCX_TRY(token_probs_of_rows(w, w->tp_xn, B, 0, w->d.n_vocab, w->rules.no_speech, nullptr, stream));
-    // first sample of every sequence, lane by lane (each lane counts its own finished sequences)
-    for (int i = 0; i < nl; i++)
-      CCX_TRY(dec_head(w, lanes[i].b0, lanes[i].B, w->dlogits + (long)lanes[i].b0 * ld, ld, true, sample_len, max_prompt, w->n_done + i, stream));
+  return CCX_OK;
+}
+
+// (6) The first step runs eagerly (also performs one-time kernel attribute setup outside of capture).  Lane i + 1
+// starts when lane i reaches its first cross attention, which sets the stagger the later steps keep.
+int first_step_eager(ccx_whisper* w, const Lanes& L, bool sync_lanes) {
+  for (int i = 0; i < L.n; i++) {
+    StepIo io = L.lane[i].io;
+    if (i > 0) CCX_HIP(w->ctx, hipStreamWaitEvent(io.stream, w->lane_start[i - 1], 0));
+    io.stagger = (i + 1 < L.n) ? w->lane_start[i] : nullptr;
+    CCX_TRY(dec_step(w, L.lane[i].plan, io));
+    if (sync_lanes) CCX_HIP(w->ctx, hipStreamSynchronize(io.stream));
   }
-  // the state upload (and the prefill) was queued on `stream`: the other lanes start after it
-  CCX_HIP(ctx, hipEventRecord(w->own_event, stream));
-  for (int i = 1; i < nl; i++) CCX_HIP(ctx, hipStreamWaitEvent(lanes[i].s, w->own_event, 0));
-  auto step_lane = [&](int i, hipEvent_t stagger) -> int {
-    const Lane& L = lanes[i];
-    return dec_step(w, L.b0, L.B, w->dlogits + (long)L.b0 * ld, ld, true, sample_len, max_prompt, w->n_done + i, L.s, stagger, i);
-  };
-  // first step runs eagerly (also performs one-time kernel attribute setup outside of capture).  Lane i + 1
-  // starts when lane i reaches its first cross attention, which sets the stagger the later steps keep.
-  int step = prefill ? 1 : 0;                   // the prefill's own sample counts as step 0
-  if (step < total_steps) {
-    for (int i = 0; i < nl; i++) {
-      if (i > 0) CCX_HIP(ctx, hipStreamWaitEvent(lanes[i].s, w->lane_start[i - 1], 0));
-      CCX_TRY(step_lane(i, (i + 1 < nl) ? w->lane_start[i] : nullptr));
-      if (ctx->prof_on && !use_graph && nl > 1) CCX_HIP(ctx, hipStreamSynchronize(lanes[i].s));
-    }
-    step += 1;
-  }
-  if (use_graph && step < total_steps) {
-    for (int i = 0; i < nl; i++) {
-      // graphs are specific to (lane rows, sample_len, max_prompt, sampling)
-      // ... and to everything else dec_step bakes into the graph: the cross-attention split count and LDS cap, and the chain's form
-      const int ns_key = cross_split(lanes[i].B, w->d.n_text_head, w->cross_stream != 0);
-      // ... and whether the step reads a row -> window map / a stream-id table (other launches, other kernel arguments)
-      const int form = (w->fuse_cross_q ? 1 : 0) | ((w->xs_active ? 1 : 0) << 1) | ((w->xs_fuse_q ? 1 : 0) << 2) | ((w->lnfree ? 1 : 0) << 3) |
-                       ((w->map_on ? 1 : 0) << 4) | ((w->sid_on ? 1 : 0) << 5) | ((w->xs_full_lines & 3) << 6) |
-                       // ... and a beam decode's head: other kernels, with beam_size and max_candidates in their arguments
-                       ((w->beam_on ? w->beam_size : 0) << 8) | ((w->beam_on ? w->beam_maxc : 0) << 12);
-      const std::array<int, 9> key = {lanes[i].b0, lanes[i].B, sample_len, max_prompt, w->sampling ? 1 : 0, ns_key, w->cross_lds_pad, form, i};
-      auto it = w->graphs.find(key);
-      if (it != w->graphs.end()) { lanes[i].exec = it->second; continue; }
-      hipGraph_t graph = nullptr;
-      hipGraphExec_t exec = nullptr;
-      CCX_HIP(ctx, hipStreamBeginCapture(lanes[i].s, hipStreamCaptureModeThreadLocal));
-      int rc = step_lane(i, nullptr);
-      hipError_t e = hipStreamEndCapture(lanes[i].s, &graph);
-      if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
-      if (e != hipSuccess) return ccx_fail(ctx, CCX_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-      e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
-      if (e != hipSuccess) return ccx_fail(ctx, CCX_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-      w->graphs[key] = exec;
-      lanes[i].exec = exec;
-    }
-  }
-  // Steps are queued in chunks; the done counters of chunk c are polled only after chunk c + 1 is queued,
-  // so no stream runs dry while the host waits.
-  const int kChunk = 8;
+  return CCX_OK;
+}
+
+// (7) The step graph of a lane: the cached one of its plan, or captured now -- the only place that captures.  The plan is
+// everything a captured step depends on besides instance constants (StepPlan); the per-call buffers io can carry are not in it,
+// so a step with such buffers is never captured.
+int step_graph(ccx_whisper* w, Lane& lane) {
+  ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, !lane.io.align && !lane.io.trace && !lane.io.stagger, "step_graph: a step with per-call buffers cannot be captured");
+  auto it = w->graphs.find(lane.plan);
+  if (it != w->graphs.end()) { lane.exec = it->second; return CCX_OK; }
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  CCX_HIP(ctx, hipStreamBeginCapture(lane.io.stream, hipStreamCaptureModeThreadLocal));
+  int rc = dec_step(w, lane.plan, lane.io);
+  hipError_t e = hipStreamEndCapture(lane.io.stream, &graph);
+  if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
+  if (e != hipSuccess) return ccx_fail(ctx, CCX_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+  e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+  hipGraphDestroy(graph);
+  if (e != hipSuccess) return ccx_fail(ctx, CCX_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+  w->graphs[lane.plan] = exec;
+  lane.exec = exec;
+  return CCX_OK;
+}
+
+// (8) The steps [step, total_steps), queued in chunks; the done counters of chunk c are polled only after chunk c + 1 is queued,
+// so no stream runs dry while the host waits.  Ends early once every sequence of every lane is done.
+int run_chunks(ccx_whisper* w, const Lanes& L, int step, int total_steps, bool sync_lanes) {
+  ccx_ctx* ctx = w->ctx;
+  const int kChunk = 8, nl = L.n;
   auto queue_chunk = [&](int c, int n) -> int {
     for (int k = 0; k < n; k++)
       for (int i = 0; i < nl; i++) {
-        if (lanes[i].exec) CCX_HIP(ctx, hipGraphLaunch(lanes[i].exec, lanes[i].s));   // ~50 us of host time per replay
+        const Lane& l = L.lane[i];
+        if (l.exec) CCX_HIP(ctx, hipGraphLaunch(l.exec, l.io.stream));   // ~50 us of host time per replay
         else {
-          CCX_TRY(step_lane(i, nullptr));
+          CCX_TRY(dec_step(w, l.plan, l.io));
           // eager profiling runs (ccx_prof_enable + CCX_NO_GRAPH) time every kernel with an event pair: keep the lanes apart so
           // that the durations are those of the kernel alone, as rocprofv3 (which serialises replays) sees them
-          if (ctx->prof_on && !use_graph && nl > 1) CCX_HIP(ctx, hipStreamSynchronize(lanes[i].s));
+          if (sync_lanes) CCX_HIP(ctx, hipStreamSynchronize(l.io.stream));
         }
       }
     for (int i = 0; i < nl; i++) {
-      CCX_HIP(ctx, hipMemcpyAsync(&w->poll_host[(c & 1) * ccx_whisper::kMaxLanes + i], w->n_done + i, 4, hipMemcpyDeviceToHost, lanes[i].s));
-      CCX_HIP(ctx, hipEventRecord(w->lane_poll[c & 1][i], lanes[i].s));
+      CCX_HIP(ctx, hipMemcpyAsync(&w->poll_host[(c & 1) * ccx_whisper::kMaxLanes + i], w->n_done + i, 4, hipMemcpyDeviceToHost, L.lane[i].io.stream));
+      CCX_HIP(ctx, hipEventRecord(w->lane_poll[c & 1][i], L.lane[i].io.stream));
     }
     return CCX_OK;
   };
@@ -1688,7 +1726,7 @@ static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
     *all = true;
     for (int i = 0; i < nl; i++) {
       CCX_HIP(ctx, hipEventSynchronize(w->lane_poll[c & 1][i]));
-      if (w->poll_host[(c & 1) * ccx_whisper::kMaxLanes + i] < lanes[i].B) *all = false;
+      if (w->poll_host[(c & 1) * ccx_whisper::kMaxLanes + i] < L.lane[i].plan.B) *all = false;
     }
     return CCX_OK;
   };
@@ -1706,102 +1744,201 @@ static int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t*
     pending = true;
     c++;
   }
-  // join the lanes back into `stream`
-  for (int i = 1; i < nl; i++) {
-    CCX_HIP(ctx, hipEventRecord(w->lane_start[i], lanes[i].s));
-    CCX_HIP(ctx, hipStreamWaitEvent(stream, w->lane_start[i], 0));
-  }
-  if (w->stamps_on) {
-    // append this decode's trace: one line per lane "lane <i> <n> <stamp> ..." (stamp = realtime << 8 | tag), then reset
-    CCX_HIP(ctx, hipStreamSynchronize(stream));
-    std::vector<int> cnt(ccx_whisper::kMaxLanes);
-    CCX_HIP(ctx, hipMemcpy(cnt.data(), w->stamp_count, cnt.size() * 4, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(w->stamp_path.c_str(), "a")) {
-      fprintf(f, "decode B %d lanes %d\n", B, nl);
-      for (int i = 0; i < nl; i++) {
-        const int n = cnt[i] < ccx_whisper::kStampCap ? cnt[i] : ccx_whisper::kStampCap;
-        std::vector<unsigned long long> buf(n);
-        CCX_HIP(ctx, hipMemcpy(buf.data(), w->stamps + (size_t)i * ccx_whisper::kStampCap, (size_t)n * 8, hipMemcpyDeviceToHost));
-        fprintf(f, "lane %d %d", i, n);
-        for (int k = 0; k < n; k++) fprintf(f, " %llu", buf[k]);
-        fprintf(f, "\n");
-      }
-      fclose(f);
-    }
-    CCX_HIP(ctx, hipMemset(w->stamp_count, 0, ccx_whisper::kMaxLanes * 4));
-  }
-  std::vector<DecSeqState> st(B);
-  std::vector<int> gen((size_t)B * sample_len);
-  std::vector<float> ns_sot(ns_at_sot ? B : 0);
-  CCX_HIP(ctx, hipMemcpyAsync(st.data(), w->state, B * sizeof(DecSeqState), hipMemcpyDeviceToHost, stream));
-  if (ns_at_sot) CCX_HIP(ctx, hipMemcpyAsync(ns_sot.data(), w->tp_prob, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-  CCX_HIP(ctx, hipMemcpyAsync(gen.data(), w->gen, gen.size() * 4, hipMemcpyDeviceToHost, stream));
-  if (beam) {
-    // BeamSearchDecoder.finalize: the finished hypotheses in insertion order, topped up with the live rows by descending score
-    const int G = beam->G, bs = beam->beam, mc = beam->maxc, C = bs > mc ? bs : mc, eot = w->rules.eot;
-    std::vector<int> fin_tok((size_t)G * mc * sample_len), fin_n((size_t)G * mc), fin_count(G);
-    std::vector<float> fin_score((size_t)G * mc);
-    CCX_HIP(ctx, hipMemcpyAsync(fin_tok.data(), w->beam_fin_tok, fin_tok.size() * 4, hipMemcpyDeviceToHost, stream));
-    CCX_HIP(ctx, hipMemcpyAsync(fin_n.data(), w->beam_fin_n, fin_n.size() * 4, hipMemcpyDeviceToHost, stream));
-    CCX_HIP(ctx, hipMemcpyAsync(fin_score.data(), w->beam_fin_score, fin_score.size() * 4, hipMemcpyDeviceToHost, stream));
-    CCX_HIP(ctx, hipMemcpyAsync(fin_count.data(), w->beam_fin_count, (size_t)G * 4, hipMemcpyDeviceToHost, stream));
-    CCX_HIP(ctx, hipStreamSynchronize(stream));
-    if (const ccx_beam_trace* tr = beam->trace) {
-      const size_t n = (size_t)sample_len * B, K = (size_t)bs + 1;
-      CCX_HIP(ctx, hipMemcpy(tr->cand_id, w->beam_tr_cid, n * K * 4, hipMemcpyDeviceToHost));
-      CCX_HIP(ctx, hipMemcpy(tr->cand_lp, w->beam_tr_clp, n * K * 4, hipMemcpyDeviceToHost));
-      CCX_HIP(ctx, hipMemcpy(tr->tok, w->beam_tr_tok, n * 4, hipMemcpyDeviceToHost));
-      CCX_HIP(ctx, hipMemcpy(tr->parent, w->beam_tr_par, n * 4, hipMemcpyDeviceToHost));
-      CCX_HIP(ctx, hipMemcpy(tr->score, w->beam_tr_score, n * 4, hipMemcpyDeviceToHost));
-    }
-    for (int g = 0; g < G; g++) {
-      int n_hyp = 0;
-      auto put = [&](const int* toks, int n, float score) {
-        const size_t at = (size_t)g * C + n_hyp;
-        for (int i = 0; i < sample_len; i++) tokens_out[at * sample_len + i] = i < n ? toks[i] : eot;
-        if (n_tokens_out) n_tokens_out[at] = n;
-        if (sum_logprob_out) sum_logprob_out[at] = score;
-        n_hyp++;
-      };
-      const int nf = fin_count[g] < mc ? fin_count[g] : mc;
-      for (int k = 0; k < nf; k++) {
-        const size_t slot = (size_t)g * mc + k;
-        put(&fin_tok[slot * sample_len], fin_n[slot], fin_score[slot]);
-      }
-      if (n_hyp < bs) {
-        std::vector<int> rows(bs);
-        for (int j = 0; j < bs; j++) rows[j] = g * bs + j;
-        std::stable_sort(rows.begin(), rows.end(), [&](int a, int b) { return st[a].sum_logprob > st[b].sum_logprob; });
-        for (int j = 0; j < bs && n_hyp < bs; j++) {
-          const int r = rows[j];
-          const int ng = st[r].n_gen < sample_len ? st[r].n_gen : sample_len;
-          put(&gen[(size_t)r * sample_len], ng, st[r].sum_logprob);
-        }
-      }
-      for (int k = n_hyp; k < C; k++) {          // unused slots: empty
-        const size_t at = (size_t)g * C + k;
-        for (int i = 0; i < sample_len; i++) tokens_out[at * sample_len + i] = eot;
-        if (n_tokens_out) n_tokens_out[at] = 0;
-        if (sum_logprob_out) sum_logprob_out[at] = 0.f;
-      }
-      if (beam->n_hyp_out) beam->n_hyp_out[g] = n_hyp;
-      if (no_speech_prob_out) no_speech_prob_out[g] = ns_at_sot ? ns_sot[(size_t)g * bs] : st[(size_t)g * bs].no_speech_prob;
-    }
-    return CCX_OK;
-  }
+  return CCX_OK;
+}
+
+// (10) append this decode's stamp trace: one line per lane "lane <i> <n> <stamp> ..." (stamp = realtime << 8 | tag), then reset
+int dump_stamps(ccx_whisper* w, int B, int nl, hipStream_t stream) {
+  ccx_ctx* ctx = w->ctx;
   CCX_HIP(ctx, hipStreamSynchronize(stream));
+  std::vector<int> cnt(ccx_whisper::kMaxLanes);
+  CCX_HIP(ctx, hipMemcpy(cnt.data(), w->stamp_count, cnt.size() * 4, hipMemcpyDeviceToHost));
+  if (FILE* f = fopen(w->stamp_path.c_str(), "a")) {
+    fprintf(f, "decode B %d lanes %d\n", B, nl);
+    for (int i = 0; i < nl; i++) {
+      const int n = cnt[i] < ccx_whisper::kStampCap ? cnt[i] : ccx_whisper::kStampCap;
+      std::vector<unsigned long long> buf(n);
+      CCX_HIP(ctx, hipMemcpy(buf.data(), w->stamps + (size_t)i * ccx_whisper::kStampCap, (size_t)n * 8, hipMemcpyDeviceToHost));
+      fprintf(f, "lane %d %d", i, n);
+      for (int k = 0; k < n; k++) fprintf(f, " %llu", buf[k]);
+      fprintf(f, "\n");
+    }
+    fclose(f);
+  }
+  CCX_HIP(ctx, hipMemset(w->stamp_count, 0, ccx_whisper::kMaxLanes * 4));
+  return CCX_OK;
+}
+
+// (11) what every decode reads back: the rows' final states, their sampled tokens, the no-speech probabilities taken at the SOT
+struct RowsBack {
+  std::vector<DecSeqState> st;
+  std::vector<int> gen;
+  std::vector<float> ns_sot;
+};
+int queue_rows_back(ccx_whisper* w, int B, int sample_len, hipStream_t stream, RowsBack* rb) {
+  rb->st.resize(B);
+  rb->gen.resize((size_t)B * sample_len);
+  rb->ns_sot.resize(w->ns_at_sot() ? B : 0);
+  CCX_HIP(w->ctx, hipMemcpyAsync(rb->st.data(), w->state, B * sizeof(DecSeqState), hipMemcpyDeviceToHost, stream));
+  if (w->ns_at_sot()) CCX_HIP(w->ctx, hipMemcpyAsync(rb->ns_sot.data(), w->tp_prob, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
+  CCX_HIP(w->ctx, hipMemcpyAsync(rb->gen.data(), w->gen, rb->gen.size() * 4, hipMemcpyDeviceToHost, stream));
+  return CCX_OK;
+}
+
+// (11) a plain or mapped decode: one result per row
+int read_back_rows(ccx_whisper* w, int B, int sample_len, hipStream_t stream, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out,
+                   float* no_speech_prob_out) {
+  RowsBack rb;
+  CCX_TRY(queue_rows_back(w, B, sample_len, stream, &rb));
+  CCX_HIP(w->ctx, hipStreamSynchronize(stream));
+  const std::vector<DecSeqState>& st = rb.st;
   for (int b = 0; b < B; b++) {
     const int ng = st[b].n_gen < sample_len ? st[b].n_gen : sample_len;
     // not done after the step budget: treat everything sampled as text (no eot was produced)
     const int ntok = st[b].done ? st[b].n_tokens : ng;
-    for (int i = 0; i < sample_len; i++) tokens_out[(size_t)b * sample_len + i] = (i < ntok) ? gen[(size_t)b * sample_len + i] : w->rules.eot;
+    for (int i = 0; i < sample_len; i++) tokens_out[(size_t)b * sample_len + i] = (i < ntok) ? rb.gen[(size_t)b * sample_len + i] : w->rules.eot;
     if (n_tokens_out) n_tokens_out[b] = ntok;
     if (sum_logprob_out) sum_logprob_out[b] = st[b].sum_logprob;
     // (the select kernel's value is that of the LAST prompt position over the ids rounded up to 4: replaced where that is not the rule)
-    if (no_speech_prob_out) no_speech_prob_out[b] = ns_at_sot ? ns_sot[b] : st[b].no_speech_prob;
+    if (no_speech_prob_out) no_speech_prob_out[b] = w->ns_at_sot() ? rb.ns_sot[b] : st[b].no_speech_prob;
   }
   return CCX_OK;
 }
+
+// (11) a beam decode -- BeamSearchDecoder.finalize: per window the finished hypotheses in insertion order, topped up with the live
+// rows by descending score; tokens_out / n_tokens_out / sum_logprob_out are [G][C][sample_len] / [G][C] / [G][C], C = max(beam, maxc)
+int read_back_beam(ccx_whisper* w, const BeamCall& beam, const BeamTrace& trace, int B, int sample_len, hipStream_t stream, int32_t* tokens_out,
+                   int32_t* n_tokens_out, float* sum_logprob_out, float* no_speech_prob_out) {
+  ccx_ctx* ctx = w->ctx;
+  RowsBack rb;
+  CCX_TRY(queue_rows_back(w, B, sample_len, stream, &rb));
+  const std::vector<DecSeqState>& st = rb.st;
+  const int G = beam.G, bs = beam.beam, mc = beam.maxc, C = bs > mc ? bs : mc, eot = w->rules.eot;
+  std::vector<int> fin_tok((size_t)G * mc * sample_len), fin_n((size_t)G * mc), fin_count(G);
+  std::vector<float> fin_score((size_t)G * mc);
+  CCX_HIP(ctx, hipMemcpyAsync(fin_tok.data(), w->beam_fin_tok, fin_tok.size() * 4, hipMemcpyDeviceToHost, stream));
+  CCX_HIP(ctx, hipMemcpyAsync(fin_n.data(), w->beam_fin_n, fin_n.size() * 4, hipMemcpyDeviceToHost, stream));
+  CCX_HIP(ctx, hipMemcpyAsync(fin_score.data(), w->beam_fin_score, fin_score.size() * 4, hipMemcpyDeviceToHost, stream));
+  CCX_HIP(ctx, hipMemcpyAsync(fin_count.data(), w->beam_fin_count, (size_t)G * 4, hipMemcpyDeviceToHost, stream));
+  CCX_HIP(ctx, hipStreamSynchronize(stream));
+  if (const ccx_beam_trace* tr = beam.trace) {
+    const size_t n = (size_t)sample_len * B, K = (size_t)bs + 1;
+    CCX_HIP(ctx, hipMemcpy(tr->cand_id, trace.cid, n * K * 4, hipMemcpyDeviceToHost));
+    CCX_HIP(ctx, hipMemcpy(tr->cand_lp, trace.clp, n * K * 4, hipMemcpyDeviceToHost));
+    CCX_HIP(ctx, hipMemcpy(tr->tok, trace.tok, n * 4, hipMemcpyDeviceToHost));
+    CCX_HIP(ctx, hipMemcpy(tr->parent, trace.par, n * 4, hipMemcpyDeviceToHost));
+    CCX_HIP(ctx, hipMemcpy(tr->score, trace.score, n * 4, hipMemcpyDeviceToHost));
+  }
+  for (int g = 0; g < G; g++) {
+    int n_hyp = 0;
+    auto put = [&](const int* toks, int n, float score) {
+      const size_t at = (size_t)g * C + n_hyp;
+      for (int i = 0; i < sample_len; i++) tokens_out[at * sample_len + i] = i < n ? toks[i] : eot;
+      if (n_tokens_out) n_tokens_out[at] = n;
+      if (sum_logprob_out) sum_logprob_out[at] = score;
+      n_hyp++;
+    };
+    const int nf = fin_count[g] < mc ? fin_count[g] : mc;
+    for (int k = 0; k < nf; k++) {
+      const size_t slot = (size_t)g * mc + k;
+      put(&fin_tok[slot * sample_len], fin_n[slot], fin_score[slot]);
+    }
+    if (n_hyp < bs) {
+      std::vector<int> rows(bs);
+      for (int j = 0; j < bs; j++) rows[j] = g * bs + j;
+      std::stable_sort(rows.begin(), rows.end(), [&](int a, int b) { return st[a].sum_logprob > st[b].sum_logprob; });
+      for (int j = 0; j < bs && n_hyp < bs; j++) {
+        const int r = rows[j];
+        const int ng = st[r].n_gen < sample_len ? st[r].n_gen : sample_len;
+        put(&rb.gen[(size_t)r * sample_len], ng, st[r].sum_logprob);
+      }
+    }
+    for (int k = n_hyp; k < C; k++) {          // unused slots: empty
+      const size_t at = (size_t)g * C + k;
+      for (int i = 0; i < sample_len; i++) tokens_out[at * sample_len + i] = eot;
+      if (n_tokens_out) n_tokens_out[at] = 0;
+      if (sum_logprob_out) sum_logprob_out[at] = 0.f;
+    }
+    if (beam.n_hyp_out) beam.n_hyp_out[g] = n_hyp;
+    if (no_speech_prob_out) no_speech_prob_out[g] = w->ns_at_sot() ? rb.ns_sot[(size_t)g * bs] : st[(size_t)g * bs].no_speech_prob;
+  }
+  return CCX_OK;
+}
+
+// The decode behind ccx_whisper_decode (win == NULL: row r reads window r, noise stream r) and ccx_whisper_decode_rows (B rows over
+// n_windows encoded windows: row r reads window win[r]; sids, if given, names every row's noise stream).  Both checked by the callers.
+// beam != NULL (ccx_whisper_decode_beam): the B rows are beam->G windows of beam->beam rows over the map (read_back_beam).
+int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B, int sample_len,
+                float temperature, uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out,
+                float* no_speech_prob_out, void* stream_, const int32_t* win, int n_windows, const int32_t* sids,
+                const BeamCall* beam = nullptr) {
+  if (!w) return CCX_ERR_ARG;
+  ccx_ctx* ctx = w->ctx;
+  hipStream_t stream = (hipStream_t)stream_;
+  int max_pl = 0;
+  CCX_TRY(check_decode_args(w, prompt_ids, prompt_lens, max_prompt, B, sample_len, temperature, tokens_out, &max_pl));
+  CCX_TRY(own_stream_if_null(w, &stream));
+  // prompts of 2 tokens and more are prefilled, kPrefillMax positions per pass (CCX_PREFILL=0: one decode step per prompt token, round
+  // 1's way)
+  const int prefill_on = [] { const char* e = getenv("CCX_PREFILL"); return e ? atoi(e) : 1; }();     // read per call: tests flip it
+  // ... and every prompt of an instance that reads its no-speech probability at the SOT position with the ranged softmax
+  const bool ns_at_sot = w->ns_at_sot();
+  CCX_REQUIRE(ctx, !ns_at_sot || prefill_on, "decode: CCX_PREFILL=0 is not available on an instance with a SOT tail (%d) or with n_vocab = %d, no multiple of 4: "
+              "its no-speech probability is taken from the prefill", w->sot_tail, w->d.n_vocab);
+  const bool prefill = prefill_on && (max_pl >= 2 || ns_at_sot);
+  if (ns_at_sot) CCX_TRY(ensure_token_probs_scratch(w));
+
+  // the plan of the whole decode: the lanes narrow it to their rows, the prefill takes it as it is
+  StepPlan base{};
+  base.B = B; base.sample_len = sample_len; base.max_prompt = max_prompt; base.sampling = temperature > 0.f;
+  base.cross_stream = 1;
+  base.map_on = win != nullptr; base.sid_on = win && sids;
+  if (beam) { base.beam_size = beam->beam; base.beam_maxc = beam->maxc; }
+  base.stamp_level = w->stamps_on ? w->stamp_level : 0;
+  read_chain_switches(base);
+  CCX_TRY(select_cross_path(w, base, stream, win ? n_windows : -1));
+  if (win) CCX_TRY(upload_row_map(w, win, sids, B, stream));
+  BeamWork bw;
+  if (beam) {
+    CCX_REQUIRE(ctx, prefill_on, "ccx_whisper_decode_beam: CCX_PREFILL=0 is not available to a beam decode (its kernels have no prompt phase)");
+    CCX_TRY(setup_beam(w, *beam, B, sample_len, stream, &bw));
+  }
+  CCX_TRY(upload_decode_state(w, prompt_ids, prompt_lens, max_prompt, B, temperature, seed, stream, prefill));
+
+  Lanes L;
+  CCX_TRY(plan_lanes(w, base, stream, bw.trace.cid ? &bw.trace : nullptr, &L));
+  // which cross attention the steps of this decode run (lane 0; a short last lane of <= 16 rows takes the <= 16-row kernels of its path)
+  w->last_cross_path = base.xs_active ? 2 : (L.lane[0].plan.B > 16 ? 1 : 0);
+  // steps still to run after the (eager) first one: the prefill already covers the prompt AND takes the first sample
+  const int total_steps = prefill ? sample_len : max_pl - 1 + sample_len;
+  const bool use_graph = getenv("CCX_NO_GRAPH") == nullptr && !L.lane[0].io.trace;   // (a traced beam decode: per-call buffers)
+  const bool sync_lanes = ctx->prof_on && !use_graph && L.n > 1;     // eager profiling runs: see run_chunks
+
+  if (prefill) CCX_TRY(prefill_and_first_sample(w, base, L, win, prompt_ids, prompt_lens, max_pl, stream));
+  // the state upload (and the prefill) was queued on `stream`: the other lanes start after it
+  CCX_HIP(ctx, hipEventRecord(w->own_event, stream));
+  for (int i = 1; i < L.n; i++) CCX_HIP(ctx, hipStreamWaitEvent(L.lane[i].io.stream, w->own_event, 0));
+  int step = prefill ? 1 : 0;                   // the prefill's own sample counts as step 0
+  if (step < total_steps) {
+    CCX_TRY(first_step_eager(w, L, sync_lanes));
+    step += 1;
+  }
+  if (use_graph && step < total_steps)
+    for (int i = 0; i < L.n; i++) CCX_TRY(step_graph(w, L.lane[i]));
+  CCX_TRY(run_chunks(w, L, step, total_steps, sync_lanes));
+  // join the lanes back into `stream`
+  for (int i = 1; i < L.n; i++) {
+    CCX_HIP(ctx, hipEventRecord(w->lane_start[i], L.lane[i].io.stream));
+    CCX_HIP(ctx, hipStreamWaitEvent(stream, w->lane_start[i], 0));
+  }
+  if (w->stamps_on) CCX_TRY(dump_stamps(w, B, L.n, stream));
+  if (beam) return read_back_beam(w, *beam, bw.trace, B, sample_len, stream, tokens_out, n_tokens_out, sum_logprob_out, no_speech_prob_out);
+  return read_back_rows(w, B, sample_len, stream, tokens_out, n_tokens_out, sum_logprob_out, no_speech_prob_out);
+}
+
+}  // namespace
+
+extern "C" {
 
 int ccx_whisper_decode(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B, int sample_len,
                        float temperature, uint64_t seed, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out,
