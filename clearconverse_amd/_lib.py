@@ -36,6 +36,12 @@ class DecodeRules(C.Structure):
         "max_initial_timestamp_index", "n_suppress")] + [("suppress", C.POINTER(C.c_int))]
 
 
+class DecodeOptions(C.Structure):
+    """ccx_decode_options (include/ccx.h): the per-call decoding options; ccx_decode_options_default fills the defaults."""
+    _fields_ = [("without_timestamps", C.c_int), ("suppress_blank", C.c_int), ("max_initial_timestamp_index", C.c_int),
+                ("n_suppress", C.c_int), ("suppress", C.POINTER(C.c_int))]
+
+
 class GemmDesc(C.Structure):
     """ccx_gemm_desc (include/ccx.h): csrc/gemm_bf16.h GemmParams field for field, then the element count of every buffer."""
     _fields_ = [
@@ -90,7 +96,7 @@ class DecSelectDesc(C.Structure):
         ("tok_emb", C.c_void_p), ("pos_emb", C.c_void_p), ("x", C.c_void_p), ("D", C.c_int),
         ("sample", C.c_int), ("temperature", C.c_float), ("seed", C.c_uint64), ("row0", C.c_int),
         ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64),
-        ("stream_ids", C.POINTER(C.c_int))]
+        ("stream_ids", C.POINTER(C.c_int)), ("opts", C.POINTER(DecodeOptions))]
 
 
 class DecBeamDesc(C.Structure):
@@ -106,7 +112,8 @@ class DecBeamDesc(C.Structure):
         ("fin_count", C.POINTER(C.c_int)),
         ("cand_id", C.POINTER(C.c_int)), ("cand_lp", C.POINTER(C.c_float)), ("tok_out", C.POINTER(C.c_int)),
         ("parent_out", C.POINTER(C.c_int)),
-        ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64)]
+        ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64),
+        ("opts", C.POINTER(DecodeOptions))]
 
 
 class BeamTrace(C.Structure):
@@ -232,6 +239,10 @@ PROTOTYPES = {
     "ccx_whisper_finalize": (_i, [_vp]),
     "ccx_whisper_set_rules": (_i, [_vp, C.POINTER(DecodeRules)]),
     "ccx_whisper_logmel": (_i, [_vp, _vp, _i64, _ip, _ip, _i, _vp, _vp]),
+    "ccx_whisper_logmel_ex": (_i, [_vp, _vp, _i64, _ip, _ip, _ip, _i, _vp, _vp]),
+    "ccx_decode_options_default": (None, [C.POINTER(DecodeOptions)]),
+    "ccx_whisper_set_decode_options": (_i, [_vp, C.POINTER(DecodeOptions)]),
+    "ccx_whisper_graph_count": (_i, [_vp, _i]),
     "ccx_whisper_set_mel": (_i, [_vp, _vp, _i, _vp]),
     "ccx_whisper_encode": (_i, [_vp, _i, _vp, _vp]),
     "ccx_whisper_decoder_logits": (_i, [_vp, _i32p, _i, _i, _vp, _vp]),
@@ -248,6 +259,7 @@ PROTOTYPES = {
     "ccx_whisper_align_probs": (_i, [_vp, _i32p, _i32p, _i, _i, _i32p, _i32p, _i, _i, _vp, _vp, _i32p, _i, _fp, _vp]),
     "ccx_whisper_last_cross_path": (_i, [_vp]),
     "ccx_whisper_set_sot_tail": (_i, [_vp, _i]),
+    "ccx_whisper_set_prefix_len": (_i, [_vp, _i]),
     "ccx_whisper_detect_language": (_i, [_vp, _i, _i, _i, _i32p, _fp, _vp]),
     "ccx_whisper_prepare_lanes": (_i, [_vp, _vp]),
     "ccx_whisper_trace_lanes": (_i, [_vp, C.c_char_p, _i]),

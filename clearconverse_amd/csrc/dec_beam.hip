@@ -38,6 +38,9 @@ __device__ __forceinline__ float beam_reduce_sum(float v, float* sh) {
 
 #define BEAM_V4 13   // float4 per thread: 1024 threads x 13 x 4 = 53248 ids, as the select kernel
 
+// RULES = false: the decode without ApplyTimestampRules (ccx_decode_options.without_timestamps), an instantiation of its own as in
+// the select kernel -- one allowed set (the call's mask, plus " " and eot on the first sampled step with SuppressBlank on), one softmax.
+template <bool RULES>
 __global__ __launch_bounds__(1024) void dec_beam_topk_kernel(DecBeamParams bp) {
   __shared__ float sh[16];
   __shared__ float sh_v[16];
@@ -94,29 +97,6 @@ __global__ __launch_bounds__(1024) void dec_beam_topk_kernel(DecBeamParams bp) {
     if (tid == 0) p.state[b].no_speech_prob = expf(lg[p.no_speech] - mx) / sum;
   }
 
-  // ---- timestamp-rule state folded into two allowed id ranges (as dec_select_kernel) ----
-  const bool last_ts = i_gen >= 1 && s.last_tok >= tsb;
-  const bool pen_ts = i_gen < 2 || s.pen_tok >= tsb;
-  int s_lo = tsb;
-  if (s.last_ts_tok >= 0) s_lo = (last_ts && !pen_ts) ? s.last_ts_tok : s.last_ts_tok + 1;
-  int s_hi = V;
-  if (i_gen == 0 && p.max_initial_ts >= 0) s_hi = tsb + p.max_initial_ts + 1;
-  if (last_ts && pen_ts) s_hi = s_lo;
-  const int t_lo = (i_gen == 0) ? tsb : ((last_ts && !pen_ts) ? p.eot : 0);
-
-  float mx_text = -INFINITY, mx_ts = -INFINITY;
-  int am_text = 0x7fffffff, am_ts = 0x7fffffff;
-#pragma unroll
-  for (int i = 0; i < BEAM_V4 * 4; i++) {
-    const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-    const bool is_text = v < tsb;
-    const bool allowed = !((sup >> i) & 1) && (is_text ? (v >= t_lo) : (v >= s_lo && v < s_hi));
-    const float x = allowed ? val[i] : -INFINITY;
-    val[i] = x;
-    const bool bt_ = is_text && x > mx_text, bs_ = !is_text && x > mx_ts;
-    mx_text = bt_ ? x : mx_text; am_text = bt_ ? v : am_text;
-    mx_ts = bs_ ? x : mx_ts; am_ts = bs_ ? v : am_ts;
-  }
   auto block_argmax = [&](float v_, int idx, float& oval, int& oidx) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -131,32 +111,76 @@ __global__ __launch_bounds__(1024) void dec_beam_topk_kernel(DecBeamParams bp) {
     for (int w = 1; w < (int)(blockDim.x >> 6); w++)
       if (sh_v[w] > oval || (sh_v[w] == oval && sh_i[w] < oidx)) { oval = sh_v[w]; oidx = sh_i[w]; }
   };
-  float bt, bs; int it, is;
-  block_argmax(mx_text, am_text, bt, it);
-  block_argmax(mx_ts, am_ts, bs, is);
-  const float mx_all = fmaxf(bt, bs);
+  float mx_all, lnorm;
+  if constexpr (RULES) {
+    // ---- timestamp-rule state folded into two allowed id ranges (as dec_select_kernel) ----
+    const bool last_ts = i_gen >= 1 && s.last_tok >= tsb;
+    const bool pen_ts = i_gen < 2 || s.pen_tok >= tsb;
+    int s_lo = tsb;
+    if (s.last_ts_tok >= 0) s_lo = (last_ts && !pen_ts) ? s.last_ts_tok : s.last_ts_tok + 1;
+    int s_hi = V;
+    if (i_gen == 0 && p.max_initial_ts >= 0) s_hi = tsb + p.max_initial_ts + 1;
+    if (last_ts && pen_ts) s_hi = s_lo;
+    const int t_lo = (i_gen == 0) ? tsb : ((last_ts && !pen_ts) ? p.eot : 0);
 
-  float se_text = 0.f, se_ts = 0.f;
-#pragma unroll
-  for (int i = 0; i < BEAM_V4 * 4; i++) {
-    const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-    const float e = __builtin_amdgcn_exp2f((val[i] - mx_all) * 1.4426950408889634f);
-    se_text += (v < tsb) ? e : 0.f;
-    se_ts += (v < tsb) ? 0.f : e;
-  }
-  se_text = beam_reduce_sum(se_text, sh);
-  se_ts = beam_reduce_sum(se_ts, sh);
-  const float lse_ts = (se_ts > 0.f) ? mx_all + logf(se_ts) : -INFINITY;
-  const bool force_ts = lse_ts > bt;
-  const float lnorm = logf(force_ts ? se_ts : se_text + se_ts);
-
-  // ---- the row's top beam + 1: masked block arg-max rounds out of the registers ----
-  if (force_ts) {
+    float mx_text = -INFINITY, mx_ts = -INFINITY;
+    int am_text = 0x7fffffff, am_ts = 0x7fffffff;
 #pragma unroll
     for (int i = 0; i < BEAM_V4 * 4; i++) {
       const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-      val[i] = (v < tsb) ? -INFINITY : val[i];
+      const bool is_text = v < tsb;
+      const bool allowed = !((sup >> i) & 1) && (is_text ? (v >= t_lo) : (v >= s_lo && v < s_hi));
+      const float x = allowed ? val[i] : -INFINITY;
+      val[i] = x;
+      const bool bt_ = is_text && x > mx_text, bs_ = !is_text && x > mx_ts;
+      mx_text = bt_ ? x : mx_text; am_text = bt_ ? v : am_text;
+      mx_ts = bs_ ? x : mx_ts; am_ts = bs_ ? v : am_ts;
     }
+    float bt, bs; int it, is;
+    block_argmax(mx_text, am_text, bt, it);
+    block_argmax(mx_ts, am_ts, bs, is);
+    mx_all = fmaxf(bt, bs);
+
+    float se_text = 0.f, se_ts = 0.f;
+#pragma unroll
+    for (int i = 0; i < BEAM_V4 * 4; i++) {
+      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
+      const float e = __builtin_amdgcn_exp2f((val[i] - mx_all) * 1.4426950408889634f);
+      se_text += (v < tsb) ? e : 0.f;
+      se_ts += (v < tsb) ? 0.f : e;
+    }
+    se_text = beam_reduce_sum(se_text, sh);
+    se_ts = beam_reduce_sum(se_ts, sh);
+    const float lse_ts = (se_ts > 0.f) ? mx_all + logf(se_ts) : -INFINITY;
+    const bool force_ts = lse_ts > bt;
+    lnorm = logf(force_ts ? se_ts : se_text + se_ts);
+
+    // ---- the row's top beam + 1: masked block arg-max rounds out of the registers ----
+    if (force_ts) {
+#pragma unroll
+      for (int i = 0; i < BEAM_V4 * 4; i++) {
+        const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
+        val[i] = (v < tsb) ? -INFINITY : val[i];
+      }
+    }
+  } else {
+    // ---- no ApplyTimestampRules: the call's mask, and " " / eot on the first sampled step (SuppressBlank) ----
+    const bool ban0 = p.suppress_blank && i_gen == 0;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < BEAM_V4 * 4; i++) {
+      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
+      const bool allowed = !((sup >> i) & 1) && !(ban0 && (v == p.blank || v == p.eot));
+      const float x = allowed ? val[i] : -INFINITY;
+      val[i] = x;
+      mx = fmaxf(mx, x);
+    }
+    mx_all = beam_reduce_max(mx, sh);
+    float se = 0.f;
+#pragma unroll
+    for (int i = 0; i < BEAM_V4 * 4; i++) se += __builtin_amdgcn_exp2f((val[i] - mx_all) * 1.4426950408889634f);
+    se = beam_reduce_sum(se, sh);
+    lnorm = logf(se);
   }
 #pragma unroll 1
   for (int k = 0; k < K; k++) {
@@ -325,8 +349,9 @@ int ccx_launch_dec_beam(ccx_ctx* ctx, const DecBeamParams& p, int n_windows, hip
               p.sel.sample_len, p.ind_ld, lds);
   const int rows = n_windows * p.beam;
   {
-    ccx_prof_scope ps(ctx, stream, "dec_beam_topk_kernel", 0.0, (double)rows * p.sel.n_vocab * 5.0);
-    hipLaunchKernelGGL(dec_beam_topk_kernel, dim3(rows), dim3(1024), 0, stream, p);
+    ccx_prof_scope ps(ctx, stream, p.sel.no_rules ? "dec_beam_topk_kernel (no rules)" : "dec_beam_topk_kernel", 0.0, (double)rows * p.sel.n_vocab * 5.0);
+    if (p.sel.no_rules) hipLaunchKernelGGL(dec_beam_topk_kernel<false>, dim3(rows), dim3(1024), 0, stream, p);
+    else hipLaunchKernelGGL(dec_beam_topk_kernel<true>, dim3(rows), dim3(1024), 0, stream, p);
   }
   CCX_CHECK_LAUNCH(ctx);
   {

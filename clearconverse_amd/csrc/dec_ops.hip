@@ -188,6 +188,12 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   const ccx_decode_rules& r = *d->rules;
   std::vector<unsigned char> mask;
   CCX_TRY(ccx_build_suppress_mask(ctx, "ccx_dec_select_step", &r, V, mask));
+  int max_init_ts = r.max_initial_timestamp_index, no_rules = 0, sup_blank = 1;
+  if (const ccx_decode_options* o = d->opts) {     // the call's options: their mask, the kernels without the rules, the index
+    CCX_TRY(ccx_build_options_mask(ctx, "ccx_dec_select_step", &r, o, V, mask));
+    no_rules = o->without_timestamps; sup_blank = o->suppress_blank;
+    if (o->max_initial_timestamp_index != -2) max_init_ts = o->max_initial_timestamp_index;
+  }
   CCX_REQUIRE(ctx, r.no_speech >= 0 && r.timestamp_begin >= 0 && r.blank >= 0, "ccx_dec_select_step: rules.no_speech, timestamp_begin or blank negative");
   CCX_REQUIRE(ctx, d->sample_len >= 1 && d->sample_len <= (1 << 20), "ccx_dec_select_step: sample_len = %d out of range", d->sample_len);
   CCX_REQUIRE(ctx, d->max_prompt >= 0 && (d->max_prompt == 0 || d->prompt), "ccx_dec_select_step: prompt is NULL with max_prompt = %d", d->max_prompt);
@@ -244,7 +250,7 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   sp.max_prompt = d->max_prompt; sp.cur_tok = d_cur; sp.pos = d_pos; sp.gen = d_gen; sp.sample_len = d->sample_len;
   sp.n_done = d_ndone; sp.suppress_mask = d_mask; sp.eot = r.eot; sp.blank = r.blank;
   sp.no_speech = r.no_speech; sp.timestamp_begin = r.timestamp_begin;
-  sp.max_initial_ts = r.max_initial_timestamp_index;
+  sp.max_initial_ts = max_init_ts; sp.no_rules = no_rules; sp.suppress_blank = sup_blank;
   sp.tok_emb = (const float*)d->tok_emb; sp.pos_emb = (const float*)d->pos_emb; sp.x = (float*)d->x; sp.D = D;
   sp.sample_cfg = d_cfg; sp.row0 = d->row0; sp.sample = d->sample;
   if (d->stream_ids) { DO_HIP(sc.upload(&d_sid, d->stream_ids, (size_t)B)); sp.stream_id = d_sid; }
@@ -282,6 +288,12 @@ extern "C" int ccx_dec_beam_step(ccx_ctx* ctx, const ccx_dec_beam_desc* d, void*
   const ccx_decode_rules& r = *d->rules;
   std::vector<unsigned char> mask;
   CCX_TRY(ccx_build_suppress_mask(ctx, "ccx_dec_beam_step", &r, V, mask));
+  int max_init_ts = r.max_initial_timestamp_index, no_rules = 0, sup_blank = 1;
+  if (const ccx_decode_options* o = d->opts) {     // the call's options: their mask, the kernels without the rules, the index
+    CCX_TRY(ccx_build_options_mask(ctx, "ccx_dec_beam_step", &r, o, V, mask));
+    no_rules = o->without_timestamps; sup_blank = o->suppress_blank;
+    if (o->max_initial_timestamp_index != -2) max_init_ts = o->max_initial_timestamp_index;
+  }
   CCX_REQUIRE(ctx, r.no_speech >= 0 && r.timestamp_begin >= 0 && r.blank >= 0, "ccx_dec_beam_step: rules.no_speech, timestamp_begin or blank negative");
   CCX_REQUIRE(ctx, SL >= 1 && SL <= 1024, "ccx_dec_beam_step: sample_len = %d out of range [1, 1024]", SL);
   CCX_REQUIRE(ctx, d->ind_ld >= 1 && d->ind_ld <= 2048, "ccx_dec_beam_step: ind_ld = %d out of range [1, 2048]", d->ind_ld);
@@ -353,7 +365,7 @@ extern "C" int ccx_dec_beam_step(ccx_ctx* ctx, const ccx_dec_beam_desc* d, void*
   sp.cur_tok = d_cur; sp.pos = d_pos; sp.gen = d_hist; sp.sample_len = SL;
   sp.n_done = d_ndone; sp.suppress_mask = d_mask; sp.eot = r.eot; sp.blank = r.blank;
   sp.no_speech = r.no_speech; sp.timestamp_begin = r.timestamp_begin;
-  sp.max_initial_ts = r.max_initial_timestamp_index;
+  sp.max_initial_ts = max_init_ts; sp.no_rules = no_rules; sp.suppress_blank = sup_blank;
   sp.tok_emb = (const float*)d->tok_emb; sp.pos_emb = (const float*)d->pos_emb; sp.x = (float*)d->x; sp.D = D;
   bp.beam = beam; bp.max_cand = mc; bp.cand_id = d_cid; bp.cand_lp = d_clp; bp.ind = d_ind; bp.ind_ld = d->ind_ld; bp.row0 = 0;
   bp.fin_tok = d_fin; bp.fin_score = d_fins; bp.fin_n = d_finn; bp.fin_count = d_finc; bp.step_tok = d_tok; bp.step_parent = d_par;

@@ -100,6 +100,10 @@ struct DecSelectParams {
   const unsigned* sample_cfg; int row0;
   int sample;   // 0: greedy kernel (sample_cfg ignored); 1: kernel with the temperature > 0 branch
   const int* stream_id;   // sampling kernel only: [B] noise stream of every row instead of row0 + b (null: row0 + b)
+  // decoding options (ccx_decode_options).  no_rules: the instantiations without ApplyTimestampRules (host side: which kernel is
+  // launched); suppress_blank: those kernels ban rules.blank and eot on the first sampled step (the ruled kernels ban every text id
+  // and eot there anyway and do not read it).  (Appended: no other field moves.)
+  int no_rules, suppress_blank;
 };
 int ccx_launch_dec_select(ccx_ctx* ctx, const DecSelectParams& p, int B, hipStream_t stream);
 
@@ -180,5 +184,34 @@ static inline int ccx_build_suppress_mask(ccx_ctx* ctx, const char* who, const c
     mask[r->suppress[i]] = 1;
   }
   if (r->no_timestamps >= 0) mask[r->no_timestamps] = 1;  // ApplyTimestampRules bans <|notimestamps|>
+  return CCX_OK;
+}
+
+// Its sibling for a call's options (ccx_decode_options): the options' list instead of the rules' where one is given, and
+// <|notimestamps|> only while the timestamp rules run -- without them upstream bans neither it nor the timestamp ids.  `r` carries
+// the rules' own list; it is checked as above.
+static inline int ccx_build_options_mask(ccx_ctx* ctx, const char* who, const ccx_decode_rules* r, const ccx_decode_options* o, int V,
+                                         std::vector<unsigned char>& mask) {
+  CCX_TRY(ccx_build_suppress_mask(ctx, who, r, V, mask));
+  CCX_REQUIRE(ctx, o->without_timestamps == 0 || o->without_timestamps == 1, "%s: opts.without_timestamps = %d must be 0 or 1", who, o->without_timestamps);
+  CCX_REQUIRE(ctx, o->suppress_blank == 0 || o->suppress_blank == 1, "%s: opts.suppress_blank = %d must be 0 or 1", who, o->suppress_blank);
+  const int mi = o->max_initial_timestamp_index;
+  CCX_REQUIRE(ctx, mi >= -2 && (mi < 0 || (r->timestamp_begin >= 0 && mi < V - r->timestamp_begin)),
+              "%s: opts.max_initial_timestamp_index = %d out of range [-2, n_vocab - timestamp_begin = %d)", who, mi, V - r->timestamp_begin);
+  CCX_REQUIRE(ctx, o->n_suppress >= 0 && (o->n_suppress == 0 || o->suppress), "%s: opts.n_suppress = %d with opts.suppress NULL", who, o->n_suppress);
+  if (o->suppress) {
+    mask.assign((size_t)V + 4, 0);
+    for (int i = 0; i < o->n_suppress; i++) {
+      CCX_REQUIRE(ctx, o->suppress[i] >= 0 && o->suppress[i] < V, "%s: opts.suppress[%d] = %d out of range [0, n_vocab = %d)", who, i, o->suppress[i], V);
+      mask[o->suppress[i]] = 1;
+    }
+  }
+  if (r->no_timestamps >= 0) {
+    bool listed = false;                     // <|notimestamps|> in the list that holds (then it stays suppressed either way)
+    const int n = o->suppress ? o->n_suppress : r->n_suppress;
+    const int* l = o->suppress ? o->suppress : r->suppress;
+    for (int i = 0; i < n; i++) listed |= l[i] == r->no_timestamps;
+    mask[r->no_timestamps] = (listed || !o->without_timestamps) ? 1 : 0;
+  }
   return CCX_OK;
 }

@@ -1280,7 +1280,9 @@ __device__ __forceinline__ float gumbel_from_u32(unsigned x) {
 #define SEL_V4 13
 // SAMPLE = false is the greedy kernel (no noise code, no extra registers: the sampling branch costs the 1024-thread
 // block its register budget and spills); SAMPLE = true adds the temperature > 0 draw.
-template <bool SAMPLE>
+// RULES = false is the decode without ApplyTimestampRules (ccx_decode_options.without_timestamps): its own instantiations, so that
+// the ruled ones keep their code and their registers.
+template <bool SAMPLE, bool RULES = true>
 __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
   __shared__ float sh[16];
   __shared__ float sh_v[16];
@@ -1357,35 +1359,6 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
     if (tid == 0) s.no_speech_prob = expf(lg[p.no_speech] - mx) / sum;
   }
 
-  // ---- timestamp-rule state (ApplyTimestampRules) folded into two allowed id ranges ----
-  // text ids   [t_lo, tsb):  empty on the first step (must start with a timestamp); only >= eot after
-  //                          "text, timestamp" (a timestamp must be paired or followed by eot)
-  // timestamps [s_lo, s_hi): >= the last timestamp (+1 unless it is still unpaired); empty after a
-  //                          closed pair "timestamp, timestamp"; <= max_initial_timestamp on the first step
-  // SuppressBlank only matters on the first step, where every text id is banned anyway.
-  const bool last_ts = i_gen >= 1 && s.last_tok >= tsb;
-  const bool pen_ts = i_gen < 2 || s.pen_tok >= tsb;
-  int s_lo = tsb;
-  if (s.last_ts_tok >= 0) s_lo = (last_ts && !pen_ts) ? s.last_ts_tok : s.last_ts_tok + 1;
-  int s_hi = V;
-  if (i_gen == 0 && p.max_initial_ts >= 0) s_hi = tsb + p.max_initial_ts + 1;
-  if (last_ts && pen_ts) s_hi = s_lo;
-  const int t_lo = (i_gen == 0) ? tsb : ((last_ts && !pen_ts) ? p.eot : 0);
-
-  // pass 1 (registers): apply the filters in place (-inf) and take text / timestamp maxima
-  float mx_text = -INFINITY, mx_ts = -INFINITY;
-  int am_text = 0x7fffffff, am_ts = 0x7fffffff;
-#pragma unroll
-  for (int i = 0; i < SEL_V4 * 4; i++) {
-    const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-    const bool is_text = v < tsb;
-    const bool allowed = !((sup >> i) & 1) && (is_text ? (v >= t_lo) : (v >= s_lo && v < s_hi));
-    const float x = allowed ? val[i] : -INFINITY;
-    val[i] = x;
-    const bool bt_ = is_text && x > mx_text, bs_ = !is_text && x > mx_ts;
-    mx_text = bt_ ? x : mx_text; am_text = bt_ ? v : am_text;
-    mx_ts = bs_ ? x : mx_ts; am_ts = bs_ ? v : am_ts;
-  }
   // block argmax (ties -> lowest index, as torch.argmax on CPU)
   auto block_argmax = [&](float v_, int idx, float& oval, int& oidx) {
 #pragma unroll
@@ -1401,29 +1374,83 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
     for (int w = 1; w < (int)(blockDim.x >> 6); w++)
       if (sh_v[w] > oval || (sh_v[w] == oval && sh_i[w] < oidx)) { oval = sh_v[w]; oidx = sh_i[w]; }
   };
-  float bt, bs; int it, is;
-  block_argmax(mx_text, am_text, bt, it);
-  block_argmax(mx_ts, am_ts, bs, is);
-  const float mx_all = fmaxf(bt, bs);
+  float bt, bs, mx_all, lnorm; int it, is; bool force_ts;
+  if constexpr (RULES) {
+    // ---- timestamp-rule state (ApplyTimestampRules) folded into two allowed id ranges ----
+    // text ids   [t_lo, tsb):  empty on the first step (must start with a timestamp); only >= eot after
+    //                          "text, timestamp" (a timestamp must be paired or followed by eot)
+    // timestamps [s_lo, s_hi): >= the last timestamp (+1 unless it is still unpaired); empty after a
+    //                          closed pair "timestamp, timestamp"; <= max_initial_timestamp on the first step
+    // SuppressBlank only matters on the first step, where every text id is banned anyway.
+    const bool last_ts = i_gen >= 1 && s.last_tok >= tsb;
+    const bool pen_ts = i_gen < 2 || s.pen_tok >= tsb;
+    int s_lo = tsb;
+    if (s.last_ts_tok >= 0) s_lo = (last_ts && !pen_ts) ? s.last_ts_tok : s.last_ts_tok + 1;
+    int s_hi = V;
+    if (i_gen == 0 && p.max_initial_ts >= 0) s_hi = tsb + p.max_initial_ts + 1;
+    if (last_ts && pen_ts) s_hi = s_lo;
+    const int t_lo = (i_gen == 0) ? tsb : ((last_ts && !pen_ts) ? p.eot : 0);
 
-  // pass 2 (registers): sum exp over text and over timestamps (relative to mx_all)
-  float se_text = 0.f, se_ts = 0.f;
+    // pass 1 (registers): apply the filters in place (-inf) and take text / timestamp maxima
+    float mx_text = -INFINITY, mx_ts = -INFINITY;
+    int am_text = 0x7fffffff, am_ts = 0x7fffffff;
 #pragma unroll
-  for (int i = 0; i < SEL_V4 * 4; i++) {
-    const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-    const float e = __builtin_amdgcn_exp2f((val[i] - mx_all) * 1.4426950408889634f);  // banned entries are -inf -> 0
-    se_text += (v < tsb) ? e : 0.f;
-    se_ts += (v < tsb) ? 0.f : e;
-  }
-  se_text = block_reduce_sum(se_text, sh);
-  se_ts = block_reduce_sum(se_ts, sh);
+    for (int i = 0; i < SEL_V4 * 4; i++) {
+      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
+      const bool is_text = v < tsb;
+      const bool allowed = !((sup >> i) & 1) && (is_text ? (v >= t_lo) : (v >= s_lo && v < s_hi));
+      const float x = allowed ? val[i] : -INFINITY;
+      val[i] = x;
+      const bool bt_ = is_text && x > mx_text, bs_ = !is_text && x > mx_ts;
+      mx_text = bt_ ? x : mx_text; am_text = bt_ ? v : am_text;
+      mx_ts = bs_ ? x : mx_ts; am_ts = bs_ ? v : am_ts;
+    }
+    block_argmax(mx_text, am_text, bt, it);
+    block_argmax(mx_ts, am_ts, bs, is);
+    mx_all = fmaxf(bt, bs);
 
-  // timestamp_logprob > max_text_token_logprob  <=>  lse_ts > max_text (same normaliser)
-  const float lse_ts = (se_ts > 0.f) ? mx_all + logf(se_ts) : -INFINITY;
-  const bool force_ts = lse_ts > bt;
-  // log-normaliser of the re-filtered logits, kept relative to mx_all: the log-probability is (x - mx_all) - lnorm, two numbers of
-  // the softmax's own magnitude, so that a common offset of the logits does not cost it the offset's ulp
-  const float lnorm = logf(force_ts ? se_ts : se_text + se_ts);
+    // pass 2 (registers): sum exp over text and over timestamps (relative to mx_all)
+    float se_text = 0.f, se_ts = 0.f;
+#pragma unroll
+    for (int i = 0; i < SEL_V4 * 4; i++) {
+      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
+      const float e = __builtin_amdgcn_exp2f((val[i] - mx_all) * 1.4426950408889634f);  // banned entries are -inf -> 0
+      se_text += (v < tsb) ? e : 0.f;
+      se_ts += (v < tsb) ? 0.f : e;
+    }
+    se_text = block_reduce_sum(se_text, sh);
+    se_ts = block_reduce_sum(se_ts, sh);
+
+    // timestamp_logprob > max_text_token_logprob  <=>  lse_ts > max_text (same normaliser)
+    const float lse_ts = (se_ts > 0.f) ? mx_all + logf(se_ts) : -INFINITY;
+    force_ts = lse_ts > bt;
+    // log-normaliser of the re-filtered logits, kept relative to mx_all: the log-probability is (x - mx_all) - lnorm, two numbers of
+    // the softmax's own magnitude, so that a common offset of the logits does not cost it the offset's ulp
+    lnorm = logf(force_ts ? se_ts : se_text + se_ts);
+  } else {
+    // ---- no ApplyTimestampRules (without_timestamps): one allowed set, one argmax, one softmax ----
+    // allowed: not suppressed by the call's mask, and on the first sampled step, with SuppressBlank on, neither " " nor eot.
+    // Timestamp ids and <|notimestamps|> are ids like any other here.
+    const bool ban0 = p.suppress_blank && i_gen == 0;
+    float mx = -INFINITY; int am = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < SEL_V4 * 4; i++) {
+      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
+      const bool allowed = !((sup >> i) & 1) && !(ban0 && (v == p.blank || v == p.eot));
+      const float x = allowed ? val[i] : -INFINITY;
+      val[i] = x;
+      const bool b_ = x > mx;            // ids ascend with i: the lowest id of equal values stays
+      mx = b_ ? x : mx; am = b_ ? v : am;
+    }
+    block_argmax(mx, am, bt, it);
+    bs = -INFINITY; is = 0x7fffffff; force_ts = false;
+    mx_all = bt;
+    float se = 0.f;
+#pragma unroll
+    for (int i = 0; i < SEL_V4 * 4; i++) se += __builtin_amdgcn_exp2f((val[i] - mx_all) * 1.4426950408889634f);   // banned: -inf -> 0
+    se = block_reduce_sum(se, sh);
+    lnorm = logf(se);                    // relative to mx_all, as the ruled kernel keeps it
+  }
 
   // ---- temperature > 0: Categorical(logits / T) by the Gumbel-max trick (argmax of logits / T + Gumbel noise) ----
   const float temperature = SAMPLE ? __uint_as_float(p.sample_cfg[0]) : 0.f;
@@ -1469,6 +1496,7 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
       if (bt > bs || (bt == bs && it < is)) next = it; else next = is;
       logprob = -lnorm;                 // the winner is mx_all itself
     }
+    if (!RULES && (unsigned)next >= (unsigned)V) next = p.eot;   // a call whose list suppresses every id: the row ends
     s.sum_logprob += logprob;
     p.gen[(long)b * p.sample_len + i_gen] = next;
     s.n_gen = i_gen + 1;
@@ -1506,8 +1534,11 @@ int ccx_launch_dec_embed(ccx_ctx* ctx, const float* tok_emb, const float* pos_em
 }
 
 int ccx_launch_dec_select(ccx_ctx* ctx, const DecSelectParams& p, int B, hipStream_t stream) {
-  ccx_prof_scope ps(ctx, stream, "dec_select_kernel", 0.0, (double)B * p.n_vocab * 5.0);     // the logit row + its suppress mask
-  if (p.sample) hipLaunchKernelGGL(dec_select_kernel<true>, dim3(B), dim3(1024), 0, stream, p);
+  ccx_prof_scope ps(ctx, stream, p.no_rules ? "dec_select_kernel (no rules)" : "dec_select_kernel", 0.0, (double)B * p.n_vocab * 5.0);     // the logit row + its suppress mask
+  if (p.no_rules) {
+    if (p.sample) hipLaunchKernelGGL((dec_select_kernel<true, false>), dim3(B), dim3(1024), 0, stream, p);
+    else hipLaunchKernelGGL((dec_select_kernel<false, false>), dim3(B), dim3(1024), 0, stream, p);
+  } else if (p.sample) hipLaunchKernelGGL(dec_select_kernel<true>, dim3(B), dim3(1024), 0, stream, p);
   else hipLaunchKernelGGL(dec_select_kernel<false>, dim3(B), dim3(1024), 0, stream, p);
   CCX_CHECK_LAUNCH(ctx);
   return CCX_OK;

@@ -48,7 +48,8 @@ struct DecLayer {
 
 // The mode of one decoder step (or prefill pass) of one lane, as a value -- and, being everything a captured step bakes in, the key
 // of the step-graph cache.  Invariant: a field dec_step / dec_head branches on or passes by value is in the plan; anything else
-// they read from the instance is constant between ccx_whisper_set_rules calls (weights, workspaces, dimensions, rule ids), and
+// they read from the instance is constant between ccx_whisper_set_rules calls (weights, workspaces, dimensions, rule ids) -- the
+// options' mask between the ccx_whisper_set_decode_options calls that change it, which drop the graphs of the plans that read it -- and
 // what is neither (logits, counters, streams, per-call buffers) comes in through StepIo.
 struct StepPlan {
   int b0, B;                      // the lane's rows [b0, b0 + B)
@@ -65,13 +66,19 @@ struct StepPlan {
   int lane_idx;                   // whose stamp trace and stagger slot
   int stamp_level;                // diagnostic stamp nodes (0: none)
   int prefill_rows;               // P > 0: the prompt prefill pass over B sequences x P positions instead of a step
+  // decoding options (ccx_whisper_set_decode_options; all 0 / the rules' index in a default decode)
+  int opt_mask;                   // the head reads the options' suppress mask (w->opt_mask) instead of the rules'
+  int no_ts;                      // without_timestamps: the select / beam kernels without ApplyTimestampRules
+  int sup_blank;                  // suppress_blank as set (read by the no_ts kernels only)
+  int max_init_ts;                // the max_initial_timestamp index the ruled kernels apply (< 0: rule off)
   auto tie() const {
     return std::tie(b0, B, sample_len, max_prompt, select, sampling, cross_stream, cross_lds_pad, xs_active, lnfree, xs_fuse_q, fuse_cross_q,
-                    xs_full_lines, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows);
+                    xs_full_lines, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows, opt_mask, no_ts, sup_blank,
+                    max_init_ts);
   }
   bool operator<(const StepPlan& o) const { return tie() < o.tie(); }
 };
-static_assert(sizeof(StepPlan) == 20 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 20,
+static_assert(sizeof(StepPlan) == 24 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 24,
               "StepPlan: ints only, and every one of them in tie()");
 
 }  // namespace
@@ -110,6 +117,12 @@ struct ccx_whisper {
   ccx_decode_rules rules{};
   unsigned char* suppress_mask = nullptr;
   bool rules_set = false;
+  std::vector<int> rules_suppress;          // the rules' own list (rules.suppress points at the caller's array: not kept)
+  // the call's options (ccx_whisper_set_decode_options) and their device mask; opts_on: they differ from the defaults
+  ccx_decode_options opts{0, 1, -2, 0, nullptr};
+  bool opts_on = false;
+  unsigned char* opt_mask = nullptr;
+  std::vector<unsigned char> opt_mask_host; // what opt_mask holds: a call that changes nothing keeps the option graphs
 
   // workspaces (encoder)
   float* lm_raw = nullptr; unsigned int* lm_max = nullptr; int *lm_n = nullptr, *lm_seek = nullptr, *lm_seg = nullptr;
@@ -187,11 +200,12 @@ struct ccx_whisper {
   // SOT sequences of more than one token, vocabularies that are no multiple of 4, language detection (dec_probs.hip).  The scratch
   // is allocated by the first call that needs it: an English-only instance allocates nothing and launches nothing for it.
   int sot_tail = 0;                          // ccx_whisper_set_sot_tail: tokens of the SOT sequence behind <|startoftranscript|>
+  int prefix_len = 0;                        // ccx_whisper_set_prefix_len: prompt tokens behind the SOT sequence (DecodingOptions.prefix)
   static constexpr int kMaxLang = 128;       // ids of one ccx_whisper_detect_language range
   bf16_t* tp_xn = nullptr;                   // [max_batch][D]: final-LayerNorm row of every sequence's SOT position (run_prefill)
   int *tp_idx = nullptr, *tp_arg = nullptr;  // [max_batch]: that row in the prefill pass (or -1); the kernel's argmax
   float *tp_prob = nullptr, *tp_lang = nullptr;   // [max_batch]: the picked probability; [max_batch][kMaxLang]: the range's distribution
-  bool ns_at_sot() const { return sot_tail > 0 || d.n_vocab % 4 != 0; }   // no_speech_prob comes from dec_token_probs_kernel
+  bool ns_at_sot() const { return sot_tail + prefix_len > 0 || d.n_vocab % 4 != 0; }   // no_speech_prob comes from dec_token_probs_kernel
 };
 
 // the alignment pass in flight: which heads of which layer go where in P, and the token row the current step writes
@@ -259,9 +273,13 @@ std::vector<float> cat_rows(std::initializer_list<const std::vector<float>*> par
   return r;
 }
 
-void drop_graphs(ccx_whisper* w) {
-  for (auto& g : w->graphs) hipGraphExecDestroy(g.second);
-  w->graphs.clear();
+// only_options: the graphs whose steps read the options' mask (a default decode's graphs stay)
+void drop_graphs(ccx_whisper* w, bool only_options = false) {
+  for (auto it = w->graphs.begin(); it != w->graphs.end();) {
+    if (only_options && !it->first.opt_mask) { ++it; continue; }
+    hipGraphExecDestroy(it->second);
+    it = w->graphs.erase(it);
+  }
 }
 
 // the legacy null stream handed over: order after everything queued on it, then run on the instance's own stream
@@ -379,9 +397,50 @@ int ccx_whisper_set_rules(ccx_whisper* w, const ccx_decode_rules* r) {
   if (!w->suppress_mask) CCX_TRY(w->store.alloc(&w->suppress_mask, (size_t)V + 4, false));
   CCX_HIP(w->ctx, hipMemcpy(w->suppress_mask, mask.data(), (size_t)V + 4, hipMemcpyHostToDevice));
   w->rules = *r;
+  w->rules_suppress.assign(r->suppress, r->suppress + (r->n_suppress > 0 ? r->n_suppress : 0));
   w->rules.suppress = nullptr;
   w->rules_set = true;
+  w->opts = ccx_decode_options{0, 1, -2, 0, nullptr};   // the options name ids of the rules they were set under
+  w->opts_on = false;
   drop_graphs(w);      // captured step graphs bake the rule ids into the select kernel's parameters
+  return CCX_OK;
+}
+
+int ccx_whisper_graph_count(ccx_whisper* w, int options_only) {
+  if (!w) return -1;
+  int n = 0;
+  for (auto& g : w->graphs) n += (!options_only || g.first.opt_mask) ? 1 : 0;
+  return n;
+}
+
+void ccx_decode_options_default(ccx_decode_options* o) {
+  if (o) *o = ccx_decode_options{0, 1, -2, 0, nullptr};
+}
+
+int ccx_whisper_set_decode_options(ccx_whisper* w, const ccx_decode_options* opts) {
+  if (!w) return CCX_ERR_ARG;
+  ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, w->rules_set, "ccx_whisper_set_decode_options: the rules are not set (ccx_whisper_set_rules)");
+  ccx_decode_options o{0, 1, -2, 0, nullptr};
+  if (opts) o = *opts;
+  const int V = w->d.n_vocab;
+  ccx_decode_rules r = w->rules;
+  r.suppress = w->rules_suppress.data();
+  std::vector<unsigned char> mask;
+  CCX_TRY(ccx_build_options_mask(ctx, "ccx_whisper_set_decode_options", &r, &o, V, mask));
+  for (int v = V; v < w->V4; v++) mask[v] = 1;     // as ccx_whisper_set_rules: the select kernel runs on V4 ids
+  // suppress_blank alone changes nothing under the rules (the first step bans every text id and eot anyway): still a default decode
+  const bool on = o.without_timestamps != 0 || o.suppress != nullptr ||
+                  (o.max_initial_timestamp_index != -2 && o.max_initial_timestamp_index != w->rules.max_initial_timestamp_index);
+  if (on && mask != w->opt_mask_host) {
+    if (!w->opt_mask) CCX_TRY(w->store.alloc(&w->opt_mask, (size_t)V + 4, false));
+    drop_graphs(w, true);                          // the option plans' graphs: their head reads this mask (a default decode's stay)
+    CCX_HIP(ctx, hipMemcpy(w->opt_mask, mask.data(), (size_t)V + 4, hipMemcpyHostToDevice));
+    w->opt_mask_host = mask;
+  }
+  w->opts = o;
+  w->opts.suppress = nullptr; w->opts.n_suppress = 0;   // the list lives in the mask
+  w->opts_on = on;
   return CCX_OK;
 }
 
@@ -649,6 +708,11 @@ static int scratch_release(ccx_whisper* w, hipStream_t stream) {
 
 int ccx_whisper_logmel(ccx_whisper* w, const float* audio, int64_t stride, const int* n_samples, const int* seek, int B,
                        float* mel_out, void* stream_) {
+  return ccx_whisper_logmel_ex(w, audio, stride, n_samples, seek, nullptr, B, mel_out, stream_);
+}
+
+int ccx_whisper_logmel_ex(ccx_whisper* w, const float* audio, int64_t stride, const int* n_samples, const int* seek, const int* max_frames,
+                          int B, float* mel_out, void* stream_) {
   if (!w) return CCX_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   CCX_REQUIRE(w->ctx, w->finalized, "whisper: not finalized");
@@ -663,13 +727,16 @@ int ccx_whisper_logmel(ccx_whisper* w, const float* audio, int64_t stride, const
     CCX_REQUIRE(w->ctx, need_frames <= w->Fraw, "whisper_logmel: clip %d (%d samples) exceeds the configured maximum of %d frames (ccx_whisper_set_max_audio)", b, n_samples[b], w->Fraw);
     if (need_frames > fcomp) fcomp = need_frames;
     CCX_REQUIRE(w->ctx, s >= 0, "whisper_logmel: negative seek");
+    CCX_REQUIRE(w->ctx, !max_frames || max_frames[b] >= 0, "ccx_whisper_logmel_ex: max_frames[%d] = %d is negative", b, max_frames ? max_frames[b] : 0);
   }
-  // segment_size = min(N_FRAMES, content_frames - seek), content_frames = n_samples // 160 (transcribe.py)
+  // segment_size = min(N_FRAMES, content_frames - seek[, clip end - seek]), content_frames = n_samples // 160 (transcribe.py); the
+  // kernel writes literal zeros behind it, which is pad_or_trim on the cropped mel
   std::vector<int> seg(B), sk(B);
   for (int b = 0; b < B; b++) {
     sk[b] = seek ? seek[b] : 0;
     int sl = n_samples[b] / 160 - sk[b];
     seg[b] = sl < 0 ? 0 : (sl > 3000 ? 3000 : sl);
+    if (max_frames && max_frames[b] < seg[b]) seg[b] = max_frames[b];
   }
   CCX_HIP(w->ctx, hipMemcpyAsync(w->lm_n, n_samples, B * 4, hipMemcpyHostToDevice, stream));
   CCX_HIP(w->ctx, hipMemcpyAsync(w->lm_seek, sk.data(), B * 4, hipMemcpyHostToDevice, stream));
@@ -896,9 +963,10 @@ int align_scores_hook(ccx_whisper* w, const AlignPass& a, int l, const float* dq
 // what the select kernel and the beam kernels share; the row-addressed fields are the caller's
 void fill_select_params(const ccx_whisper* w, const StepPlan& p, const StepIo& io, DecSelectParams& sp) {
   sp.logits = io.logits; sp.ld_logits = io.ld; sp.n_vocab = w->V4; sp.pos = w->pos + p.b0; sp.sample_len = p.sample_len; sp.n_done = io.n_done;
-  sp.suppress_mask = w->suppress_mask; sp.eot = w->rules.eot; sp.blank = w->rules.blank;
+  sp.suppress_mask = p.opt_mask ? w->opt_mask : w->suppress_mask; sp.eot = w->rules.eot; sp.blank = w->rules.blank;
   sp.no_speech = w->rules.no_speech; sp.timestamp_begin = w->rules.timestamp_begin;
-  sp.max_initial_ts = w->rules.max_initial_timestamp_index;
+  sp.max_initial_ts = p.max_init_ts;
+  sp.no_rules = p.no_ts; sp.suppress_blank = p.sup_blank;
   sp.tok_emb = w->tok_emb_f32; sp.pos_emb = w->dec_pos; sp.D = w->d.n_text_state;
 }
 
@@ -1204,7 +1272,7 @@ int run_prefill(ccx_whisper* w, const StepPlan& plan, const int32_t* win_host, c
       }
       const int tl = prompt_lens[b] - 1 - t0;        // the sequence's last prompt position, relative to this pass
       last[b] = (tl >= 0 && tl < Pc) ? b * Pc + tl : -1;
-      const int ts = tl - w->sot_tail;               // ... and its <|startoftranscript|>
+      const int ts = tl - w->sot_tail - w->prefix_len;   // ... and its <|startoftranscript|>
       sot_row[b] = (ts >= 0 && ts < Pc) ? b * Pc + ts : -1;
     }
     if (w->ns_at_sot()) CCX_HIP(ctx, hipMemcpyAsync(w->tp_idx, sot_row.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream));
@@ -1441,8 +1509,18 @@ int ccx_whisper_last_cross_path(ccx_whisper* w) { return w ? w->last_cross_path 
 
 int ccx_whisper_set_sot_tail(ccx_whisper* w, int n_tail) {
   if (!w) return CCX_ERR_ARG;
-  CCX_REQUIRE(w->ctx, n_tail >= 0 && n_tail <= 2, "ccx_whisper_set_sot_tail: n_tail = %d out of range [0, 2]", n_tail);
+  // [sot, <|language|>, <|task|>, <|notimestamps|>] is the longest SOT sequence there is, and a multilingual vocabulary's
+  const int max_tail = w->d.n_vocab >= 51865 ? 3 : 2;
+  CCX_REQUIRE(w->ctx, n_tail >= 0 && n_tail <= max_tail, "ccx_whisper_set_sot_tail: n_tail = %d out of range [0, %d]", n_tail, max_tail);
   w->sot_tail = n_tail;     // read by the host side of a decode only: the captured step graphs do not depend on it
+  return CCX_OK;
+}
+
+int ccx_whisper_set_prefix_len(ccx_whisper* w, int n_prefix) {
+  if (!w) return CCX_ERR_ARG;
+  CCX_REQUIRE(w->ctx, n_prefix >= 0 && n_prefix <= w->d.n_text_ctx / 2, "ccx_whisper_set_prefix_len: n_prefix = %d out of range [0, n_text_ctx / 2 = %d]",
+              n_prefix, w->d.n_text_ctx / 2);
+  w->prefix_len = n_prefix;  // host side only, as the SOT tail
   return CCX_OK;
 }
 
@@ -1536,8 +1614,8 @@ int check_decode_args(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* 
   for (int b = 0; b < B; b++) {
     CCX_REQUIRE(ctx, prompt_lens[b] >= 1 && prompt_lens[b] <= max_prompt, "decode_greedy: prompt_lens[%d]=%d out of range", b, prompt_lens[b]);
     CCX_REQUIRE(ctx, prompt_lens[b] + sample_len - 1 <= w->d.n_text_ctx, "decode_greedy: prompt %d + sample_len %d exceeds n_text_ctx", prompt_lens[b], sample_len);
-    CCX_REQUIRE(ctx, prompt_lens[b] > w->sot_tail, "decode: prompt_lens[%d] = %d does not hold a SOT sequence of 1 + %d tokens (ccx_whisper_set_sot_tail)", b,
-                prompt_lens[b], w->sot_tail);
+    CCX_REQUIRE(ctx, prompt_lens[b] > w->sot_tail + w->prefix_len, "decode: prompt_lens[%d] = %d does not hold a SOT sequence of 1 + %d tokens (ccx_whisper_set_sot_tail) and a prefix of %d (ccx_whisper_set_prefix_len)", b,
+                prompt_lens[b], w->sot_tail, w->prefix_len);
     for (int i = 0; i < prompt_lens[b]; i++) {
       const int t = prompt_ids[(size_t)b * max_prompt + i];
       CCX_REQUIRE(ctx, t >= 0 && t < w->d.n_vocab, "decode_greedy: prompt token %d out of range", t);
@@ -1895,6 +1973,13 @@ int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
   base.map_on = win != nullptr; base.sid_on = win && sids;
   if (beam) { base.beam_size = beam->beam; base.beam_maxc = beam->maxc; }
   base.stamp_level = w->stamps_on ? w->stamp_level : 0;
+  // the call's options: a default decode keeps the plan it always had (the rules' mask and index, the ruled kernels)
+  base.max_init_ts = w->rules.max_initial_timestamp_index;
+  if (w->opts_on) {
+    base.opt_mask = 1; base.no_ts = w->opts.without_timestamps != 0; base.sup_blank = w->opts.suppress_blank != 0;
+    if (w->opts.max_initial_timestamp_index != -2) base.max_init_ts = w->opts.max_initial_timestamp_index;
+    if (base.no_ts) base.max_init_ts = -1;         // not read without the rules: one plan whatever the caller left there
+  }
   read_chain_switches(base);
   CCX_TRY(select_cross_path(w, base, stream, win ? n_windows : -1));
   if (win) CCX_TRY(upload_row_map(w, win, sids, B, stream));

@@ -86,7 +86,8 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
                 seg_max_crops: Optional[int] = None, seg_max_seconds: float = 1200.0, emb_max_crops: Optional[int] = None,
                 resnet_max_chunks: int = 96, whisper_instances: int = 1, share_encoder_scratch: bool = True,
                 gate_max_clips: int = 32, gate_max_seconds: float = 30.0, word_alignment: bool = False,
-                word_probabilities: bool = False, embedding: str = "xvector", denoise: str = "stationary") -> Dict[str, object]:
+                word_probabilities: bool = False, embedding: str = "xvector", denoise: str = "stationary",
+                decoding_options: bool = False) -> Dict[str, object]:
     """embedding: "xvector" (default: `pyannote/embedding`, what the reference loads) or "ecapa" (ECAPA-TDNN, 192-d) for
     `models["embedding_model"]`; the diarization pipeline keeps its ResNet-34 either way.
     denoise: the mode of `models["denoiser"]` -- "stationary" (default: what the reference asks noisereduce for) or "nonstationary"
@@ -115,7 +116,11 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
     # word_alignment (default off): transcribe(word_timestamps=True) then aligns words on the GPU (WhisperModel.__init__)
     # word_probabilities (default off, needs word_alignment): the words carry `probability` and transcribe() honours
     # hallucination_silence_threshold; handed on only when set
+    # decoding_options (default off): transcribe() then honours without_timestamps, prefix, clip_timestamps and the rest of upstream's
+    # per-call decoding options (WhisperModel.__init__); handed on only when set
     wp = {"word_probabilities": True} if word_probabilities else {}
+    if decoding_options:
+        wp["decoding_options"] = True
     whispers = [WhisperModel(wd, wsd, max_batch=whisper_batch, device=dev_index, ctx=ctx, max_audio_seconds=max_audio_seconds,
                              word_alignment=word_alignment, **wp)]
     for _ in range(1, max(1, int(whisper_instances))):

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, fallback
+from . import _lib, decoding_options, fallback
 from .audio import mel_filterbank
 from .tokenizer import DecodeRules, IdTokenizer, get_tokenizer
 from .weights import WhisperDims
@@ -101,11 +101,20 @@ class WindowLoop:
     def __init__(self, rules: DecodeRules, tokenizer, content_frames: int, initial_prompt: Optional[str], n_text_ctx: int,
                  condition_on_previous_text: bool = True, no_speech_threshold: Optional[float] = 0.6,
                  logprob_threshold: Optional[float] = -1.0, sot_sequence: Optional[Sequence[int]] = None,
-                 language: Optional[str] = "en", task: str = "transcribe"):
+                 language: Optional[str] = "en", task: str = "transcribe", without_timestamps: bool = False,
+                 prefix_tokens: Optional[Sequence[int]] = None, sample_len: Optional[int] = None,
+                 clips: Optional[Sequence[Sequence[int]]] = None, carry_initial_prompt: bool = False):
         """sot_sequence: tokenizer.sot_sequence of the clip; None: the rules' own for `language` and `task` ([sot] on an English-only
         model).  language: what `result()` reports.  language=None on a multilingual model: PENDING -- the SOT sequence holds a
         placeholder for the language token (-1; three tokens, so prompt lengths and caps are already right) until `set_language`
-        fills it in from the first window's detection; a pending loop must not be decoded."""
+        fills it in from the first window's detection; a pending loop must not be decoded.
+        The decoding options [UPSTREAM-RECALL: decoding.py::_get_initial_tokens, transcribe.py main loop; parity unpinned], all off by
+        default: without_timestamps -- <|notimestamps|> ends the SOT sequence; prefix_tokens -- appended behind it in every window
+        (part of the prompt: never in the result); sample_len -- caps every window's samples; clips -- (start, end) frame pairs
+        (decoding_options.parse_clip_timestamps): `seek` jumps to the next clip's start once it is at or behind the current clip's
+        end, a window ends where its clip ends, and the loop is over when the clips are (a clip at or behind the content's end holds
+        no window: upstream leaves that case to a negative segment size); carry_initial_prompt -- the initial prompt leads every
+        window's prompt, whatever was reset."""
         self.rules, self.tokenizer, self.n_text_ctx = rules, tokenizer, int(n_text_ctx)
         self.task = task
         self.language_known = not (rules.is_multilingual and language is None and sot_sequence is None)
@@ -124,16 +133,57 @@ class WindowLoop:
         self.condition, self.no_speech_threshold, self.logprob_threshold = condition_on_previous_text, no_speech_threshold, logprob_threshold
         ipt = tokenizer.encode(" " + initial_prompt.strip()) if initial_prompt else []
         self.seek, self.all_tokens, self.n_init, self.reset = 0, list(ipt), len(ipt), 0
+        self.without_timestamps = bool(without_timestamps)
+        self.prefix_tokens = [int(t) for t in prefix_tokens] if prefix_tokens is not None else []
+        self.sample_len = None if sample_len is None else int(sample_len)
+        self.carry_initial_prompt, self.initial_prompt_tokens = bool(carry_initial_prompt), list(ipt)
+        self.clips = [(int(a), int(b)) for a, b in clips] if clips is not None else None
+        self.clip_idx = 0
+        if self.clips is not None:
+            self.seek = self.clips[0][0] if self.clips else 0
+            self._settle_clip()
         self.segments: List[dict] = []
         self.seeks: List[int] = []
         self.last_speech_timestamp = 0.0        # word alignment only: end of the last aligned word (add_word_timestamps)
 
     def active(self) -> bool:
+        if self.clips is not None:
+            return self.clip_idx < len(self.clips)
         return self.seek < self.content
 
+    def _settle_clip(self) -> None:
+        """transcribe.py's loop head: `seek` into the current clip, or on to the next one once this one (or the content) is used up"""
+        while self.clip_idx < len(self.clips):
+            start, end = self.clips[self.clip_idx]
+            if self.seek < start:
+                self.seek = start
+            if self.seek >= end or self.seek >= self.content:
+                self.clip_idx += 1
+                if self.clip_idx < len(self.clips):
+                    self.seek = self.clips[self.clip_idx][0]
+                continue
+            return
+
+    def segment_size(self) -> int:
+        """frames of the window at `seek`: min(N_FRAMES, content_frames - seek[, clip end - seek])"""
+        size = min(N_FRAMES, self.content - self.seek)
+        if self.clips is not None and self.clip_idx < len(self.clips):
+            size = min(size, self.clips[self.clip_idx][1] - self.seek)
+        return size
+
     def prompt_tokens(self) -> List[int]:
-        """decode_options["prompt"] = all_tokens[prompt_reset_since:]"""
+        """decode_options["prompt"] = all_tokens[prompt_reset_since:]; carry_initial_prompt: the initial prompt, then what fits of
+        the tokens behind max(its length, prompt_reset_since)"""
+        if self.carry_initial_prompt:
+            ipt = self.initial_prompt_tokens
+            nignored = max(len(ipt), self.reset)
+            return ipt + self.all_tokens[nignored:][-(self.n_text_ctx // 2 - 1 - len(ipt)):]
         return self.all_tokens[self.reset:]
+
+    def sot_tail(self) -> int:
+        """tokens of the SOT sequence behind <|startoftranscript|>, <|notimestamps|> included (ccx_whisper_set_sot_tail); with the
+        prefix's length (ccx_whisper_set_prefix_len) it tells the library where to read the no-speech probability"""
+        return len(self.sot_sequence) - 1 + int(self.without_timestamps)
 
     def initial_tokens(self) -> List[int]:
         """decoding.py::_get_initial_tokens: [sot_prev] + prompt[-(n_ctx // 2 - 1):] + sot_sequence."""
@@ -141,7 +191,8 @@ class WindowLoop:
         toks: List[int] = []
         if len(p):
             toks = [self.rules.sot_prev] + list(p)[-(self.n_text_ctx // 2 - 1):]
-        return toks + list(self.sot_sequence)
+        tail = [self.rules.no_timestamps] if self.without_timestamps else []
+        return toks + list(self.sot_sequence) + tail + self.prefix_tokens
 
     def set_language(self, code: str) -> None:
         """the detected language of a pending loop"""
@@ -150,14 +201,15 @@ class WindowLoop:
 
     def sample_cap(self) -> int:
         """Tokens the next window may sample: decode_cap of its initial tokens."""
-        return decode_cap(len(self.initial_tokens()), self.n_text_ctx)
+        cap = decode_cap(len(self.initial_tokens()), self.n_text_ctx)
+        return cap if self.sample_len is None else min(self.sample_len, cap)
 
     def window_segments(self, r: dict):
         """The segments one decoded window yields, before empty ones are cleared: (segments, single_timestamp_ending, next seek by the
         timestamp-token rule), or None when the silence rule skips the window.  Changes nothing."""
         tsb, eot = self.rules.timestamp_begin, self.rules.eot
         seek = self.seek
-        segment_size = min(N_FRAMES, self.content - seek)
+        segment_size = self.segment_size()
         time_offset = seek * HOP / SAMPLE_RATE
         segment_duration = segment_size * HOP / SAMPLE_RATE
         tokens = list(r["tokens"])
@@ -212,10 +264,12 @@ class WindowLoop:
         more anomalies) on both sides cuts the window there."""
         seek = self.seek
         self.seeks.append(seek)
-        segment_size = min(N_FRAMES, self.content - seek)
+        segment_size = self.segment_size()
         built = self.window_segments(r)
         if built is None:
             self.seek = seek + segment_size
+            if self.clips is not None:
+                self._settle_clip()
             return
         new_segments, single_ts_ending, self.seek = built
         if segments is not None:
@@ -243,6 +297,8 @@ class WindowLoop:
                     self.last_speech_timestamp = last_speech_before
                     if self.seek <= seek:
                         self.seek = seek + segment_size
+                    if self.clips is not None:
+                        self._settle_clip()
                     return
             # "skip silence before any possible hallucination that is surrounded by silence or more hallucinations"
             hal_last_end = last_speech_before
@@ -273,6 +329,8 @@ class WindowLoop:
             self.reset = len(self.all_tokens)
         if self.seek <= seek:  # cannot happen under ApplyTimestampRules (a closing timestamp is > its opening one); never loop forever
             self.seek = seek + segment_size
+        if self.clips is not None:
+            self._settle_clip()
 
     def result(self) -> dict:
         text_tokens = self.all_tokens[self.n_init:]
@@ -282,14 +340,19 @@ class WindowLoop:
 class WhisperModel:
     temperature_fallback = False      # opt-in (the constructor's keyword)
     beam_search = False               # opt-in too
+    decoding_options = False          # and so are upstream's remaining per-call decoding options
 
     def __init__(self, dims: WhisperDims, state_dict: Dict[str, torch.Tensor], max_batch: int = 8,
                  device: int = 0, rules: Optional[DecodeRules] = None, tokenizer=None,
                  ctx: Optional[_lib.Context] = None, max_audio_seconds: float = 30.0,
                  share_encoder_scratch_with: Optional["WhisperModel"] = None, word_alignment: bool = False,
                  alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False,
-                 temperature_fallback: bool = False, beam_search: bool = False):
-        """beam_search (default False: `beam_size`, `patience` and `length_penalty` are accepted and ignored, as before): with it,
+                 temperature_fallback: bool = False, beam_search: bool = False, decoding_options: bool = False):
+        """decoding_options (default False: `without_timestamps`, `prefix`, `suppress_blank`, `suppress_tokens`, `max_initial_timestamp`,
+        `sample_len`, `clip_timestamps` and `carry_initial_prompt` are accepted and ignored, as before): with it, `transcribe` /
+        `transcribe_batch` honour them [UPSTREAM-RECALL: decoding.py::DecodingOptions, transcribe.py; parity unpinned] -- see
+        `transcribe_batch`; `decode`, `decode_rows` and `decode_beam` take the ones a single decode reads.
+        beam_search (default False: `beam_size`, `patience` and `length_penalty` are accepted and ignored, as before): with it,
         `transcribe` / `transcribe_batch` honour them [UPSTREAM-RECALL: decoding.py::BeamSearchDecoder, transcribe.py::decode_with_fallback;
         parity unpinned] -- a temperature-0 round with `beam_size` set decodes every window by beam search on the GPU (`decode_beam`),
         `length_penalty` enters the ranker of beam and best_of rounds alike.
@@ -331,6 +394,7 @@ class WhisperModel:
         self.word_probabilities = bool(word_probabilities)
         self.temperature_fallback = bool(temperature_fallback)
         self.beam_search = bool(beam_search)
+        self.decoding_options = bool(decoding_options)
         if alignment_heads is None:
             alignment_heads = [(l, h) for l in range(dims.n_text_layer // 2, dims.n_text_layer) for h in range(dims.n_text_head)]
         self.alignment_heads = [(int(l), int(h)) for l, h in alignment_heads]
@@ -374,6 +438,47 @@ class WhisperModel:
         # tokens of the SOT sequence behind sot: the no-speech probability is read at sot's position (decoding.py `sot_index`)
         self.set_sot_tail(len(rules.sot_sequence()) - 1)
 
+    def set_decode_options(self, without_timestamps: bool = False, suppress_blank: bool = True,
+                           suppress: Optional[Sequence[int]] = None, max_initial_timestamp_index: int = -2):
+        """ccx_whisper_set_decode_options (sticky, like the rules; `set_rules` resets it): without_timestamps -- the select / beam
+        kernels without ApplyTimestampRules (the prompts then end in <|notimestamps|>: the caller's part); suppress -- the id list that
+        replaces the rules' (None: the rules'; []: nothing suppressed); max_initial_timestamp_index -- -2 the rules' own, -1 off."""
+        sup = None if suppress is None else (C.c_int * max(len(suppress), 1))(*[int(x) for x in suppress])
+        o = _lib.DecodeOptions(int(bool(without_timestamps)), int(bool(suppress_blank)), int(max_initial_timestamp_index),
+                               0 if suppress is None else len(suppress), sup)
+        self.ctx.check(self.lib.ccx_whisper_set_decode_options(self.handle, C.byref(o)), "ccx_whisper_set_decode_options")
+
+    def graph_count(self, options_only: bool = False) -> int:
+        """captured step graphs the instance holds (ccx_whisper_graph_count)"""
+        return int(self.lib.ccx_whisper_graph_count(self.handle, int(bool(options_only))))
+
+    def reset_decode_options(self):
+        self.ctx.check(self.lib.ccx_whisper_set_decode_options(self.handle, None), "ccx_whisper_set_decode_options")
+
+    def _with_call_options(self, decoding: dict, fn):
+        """`fn()` under the decoding subset a single decode takes (without_timestamps, suppress_blank, suppress_tokens,
+        max_initial_timestamp); the defaults are back afterwards.  Without the opt-in, or without any of them, just `fn()`."""
+        unknown = set(decoding) - {"without_timestamps", "suppress_blank", "suppress_tokens", "max_initial_timestamp"}
+        if unknown:
+            raise TypeError(f"unexpected decoding option(s): {sorted(unknown)}")
+        if not self.decoding_options or not decoding:
+            return fn()
+        try:
+            opt = decoding_options.resolve(self.rules, **decoding)
+        except ValueError as e:
+            raise _lib.CcxError(str(e)) from e
+        self.set_decode_options(opt.without_timestamps, opt.suppress_blank, None if opt.suppress_default else opt.suppress,
+                                opt.max_initial_timestamp_index)
+        try:
+            return fn()
+        finally:
+            self.reset_decode_options()
+
+    def set_prefix_len(self, n_prefix: int):
+        """prompt tokens behind the SOT sequence (a decode with a prefix): ccx_whisper_set_prefix_len"""
+        self.ctx.check(self.lib.ccx_whisper_set_prefix_len(self.handle, int(n_prefix)), "ccx_whisper_set_prefix_len")
+        self.prefix_len = int(n_prefix)
+
     def set_sot_tail(self, n_tail: int):
         self.ctx.check(self.lib.ccx_whisper_set_sot_tail(self.handle, int(n_tail)), "ccx_whisper_set_sot_tail")
         self.sot_tail = int(n_tail)
@@ -405,13 +510,19 @@ class WhisperModel:
 
     # ------------------------------------------------------------------ stage entry points
     def log_mel(self, audio: torch.Tensor, n_samples: Sequence[int], seek: Optional[Sequence[int]] = None,
-                return_mel: bool = False) -> Optional[torch.Tensor]:
-        """audio: [B, stride] f32 on the GPU.  Stages the conv-stem input inside the model."""
+                return_mel: bool = False, max_frames: Optional[Sequence[int]] = None) -> Optional[torch.Tensor]:
+        """audio: [B, stride] f32 on the GPU.  Stages the conv-stem input inside the model.  max_frames (ccx_whisper_logmel_ex): a
+        cap on every window's frames -- zeros behind it, as pad_or_trim leaves a cropped mel."""
         B = audio.shape[0]
         assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
         ns = (C.c_int * B)(*[int(x) for x in n_samples])
         sk = (C.c_int * B)(*[int(x) for x in seek]) if seek is not None else None
         mel = torch.empty(B, self.dims.n_mels, N_FRAMES, device=self.device, dtype=torch.float32) if return_mel else None
+        if max_frames is not None:
+            mf = (C.c_int * B)(*[int(x) for x in max_frames])
+            self.ctx.check(self.lib.ccx_whisper_logmel_ex(self.handle, audio.data_ptr(), audio.shape[1], ns, sk, mf, B,
+                                                          _lib.ptr(mel), _lib.current_stream_ptr()), "ccx_whisper_logmel_ex")
+            return mel
         self.ctx.check(self.lib.ccx_whisper_logmel(self.handle, audio.data_ptr(), audio.shape[1], ns, sk, B,
                                                    _lib.ptr(mel), _lib.current_stream_ptr()), "ccx_whisper_logmel")
         return mel
@@ -442,7 +553,8 @@ class WhisperModel:
         self.ctx.check(self.lib.ccx_whisper_prepare_lanes(self.handle, sp), "ccx_whisper_prepare_lanes")
 
     def trace_lanes(self, path: Optional[str], level: int = 1):
-        """Switch the in-graph lane trace on (path) or off (None): ccx_whisper_trace_lanes.  Drops the captured step graphs."""
+        """Switch the in-graph lane trace on (path) or off (None): ccx_whisper_trace_lanes.  The stamp level is part of the step plan: traced and
+        untraced step graphs live side by side."""
         self.ctx.check(self.lib.ccx_whisper_trace_lanes(self.handle, path.encode() if path else None, int(level)), "ccx_whisper_trace_lanes")
 
     def decode_greedy(self, prompts: Sequence[Sequence[int]], sample_len: Optional[int] = None) -> List[dict]:
@@ -450,13 +562,18 @@ class WhisperModel:
         return self.decode(prompts, sample_len, temperature=0.0)
 
     def decode(self, prompts: Sequence[Sequence[int]], sample_len: Optional[int] = None, temperature: float = 0.0,
-               seed: int = 0) -> List[dict]:
+               seed: int = 0, **decoding) -> List[dict]:
         """DecodingTask.run over the currently encoded windows; prompts[b] are the full initial tokens
         (sot_prev + prompt + sot).  temperature 0: argmax.  temperature > 0: one Categorical(logits / T) sample per
         step (decoding.py::GreedyDecoder.update), drawn on the device from Philox noise keyed by
         (seed, row, step, token id) -- reproducible, not bit-equal to torch's sampler.
         sample_len None: decode_cap of the longest prompt -- n_text_ctx // 2 = 224 for every prompt of up to 225 tokens (what the
-        default always was), fewer for a longer one, which the fixed 224 made the library refuse."""
+        default always was), fewer for a longer one, which the fixed 224 made the library refuse.
+        **decoding (decoding_options instances; ignored otherwise): without_timestamps, suppress_blank, suppress_tokens,
+        max_initial_timestamp for this call (`_with_call_options`); the prompts, the SOT tail, the prefix length and sample_len stay
+        the caller's."""
+        if decoding:
+            return self._with_call_options(decoding, lambda: self.decode(prompts, sample_len, temperature, seed))
         if not (temperature >= 0.0):
             raise _lib.CcxError("temperature must be >= 0")
         B = len(prompts)
@@ -483,11 +600,15 @@ class WhisperModel:
                      cross_path=self.last_cross_path) for b in range(B)]
 
     def decode_rows(self, prompts: Sequence[Sequence[int]], windows: Sequence[int], stream_ids: Optional[Sequence[int]] = None,
-                    sample_len: Optional[int] = None, temperature: float = 0.0, seed: int = 0, n_windows: Optional[int] = None) -> List[dict]:
+                    sample_len: Optional[int] = None, temperature: float = 0.0, seed: int = 0, n_windows: Optional[int] = None,
+                    **decoding) -> List[dict]:
         """`decode` for len(prompts) <= max_batch rows over the currently encoded windows (ccx_whisper_decode_rows): row r decodes
         window windows[r] -- entries may repeat (best_of), need not be monotone, and windows may go unused (a fallback round decodes
         only the failing ones).  stream_ids[r]: the row's noise stream at temperature > 0 (None: r), so that its draws do not depend on
-        the rows it shares the call with.  n_windows: how many windows are encoded (default: max(windows) + 1)."""
+        the rows it shares the call with.  n_windows: how many windows are encoded (default: max(windows) + 1).  **decoding: as `decode`."""
+        if decoding:
+            return self._with_call_options(decoding, lambda: self.decode_rows(prompts, windows, stream_ids, sample_len, temperature, seed,
+                                                                             n_windows))
         if not (temperature >= 0.0):
             raise _lib.CcxError("temperature must be >= 0")
         R = len(prompts)
@@ -520,7 +641,7 @@ class WhisperModel:
 
     def decode_beam(self, prompts: Sequence[Sequence[int]], beam_size: int, patience: Optional[float] = None,
                     sample_len: Optional[int] = None, windows: Optional[Sequence[int]] = None, n_windows: Optional[int] = None,
-                    trace: bool = False):
+                    trace: bool = False, **decoding):
         """Beam search at temperature 0 over the currently encoded windows (ccx_whisper_decode_beam) [UPSTREAM-RECALL:
         decoding.py::BeamSearchDecoder]: prompts[g] is decoded on window windows[g] (None: window g) by beam_size rows that share the
         window's encoder output; len(prompts) * beam_size <= max_batch.  patience (None: 1.0): a window is complete once
@@ -528,7 +649,11 @@ class WhisperModel:
         ones first, then live rows by descending score while fewer than beam_size finished): dicts of tokens (before the eot),
         sum_logprob, avg_logprob, no_speech_prob (the window's), cross_path.  The ranker (`fallback.rank_candidates`) picks among them.
         trace=True (a test aid; the steps then run eagerly): -> (results, dict of numpy arrays cand_id / cand_lp [steps, rows,
-        beam_size + 1], tok / parent / score [steps, rows]; rows = prompt-major; -1 / NaN where a window no longer stepped)."""
+        beam_size + 1], tok / parent / score [steps, rows]; rows = prompt-major; -1 / NaN where a window no longer stepped).
+        **decoding: as `decode`."""
+        if decoding:
+            return self._with_call_options(decoding, lambda: self.decode_beam(prompts, beam_size, patience, sample_len, windows, n_windows,
+                                                                             trace))
         G, bs = len(prompts), int(beam_size)
         if patience is not None and not (patience > 0):
             raise _lib.CcxError("decode_beam: patience must be > 0")
@@ -663,7 +788,7 @@ class WhisperModel:
             texts.append([t for s in bt[0] for t in s["tokens"] if t < self.rules.eot] if bt is not None else [])
         jumps, probs = None, None
         if any(texts):
-            frames = [max(2, min(N_FRAMES, state[i].content - state[i].seek)) for i in grp]
+            frames = [max(2, state[i].segment_size()) for i in grp]
             # one teacher-forced batch: every window with its own SOT sequence (all of one length: the DTW starts behind it)
             seqs = [state[i].sot_sequence for i in grp]
             assert all(len(sq) == len(seqs[0]) for sq in seqs), "one model, one SOT-sequence length: the DTW's row0 is per call"
@@ -698,7 +823,9 @@ class WhisperModel:
                    language: Optional[str] = None, task: str = "transcribe",
                    hallucination_silence_threshold: Optional[float] = None, compression_ratio_threshold: Optional[float] = 2.4,
                    best_of: Optional[int] = None, beam_size: Optional[int] = None, patience: Optional[float] = None,
-                   length_penalty: Optional[float] = None, **_ignored):
+                   length_penalty: Optional[float] = None, without_timestamps: bool = False, prefix=None,
+                   suppress_blank: bool = True, suppress_tokens="-1", max_initial_timestamp: Optional[float] = 1.0,
+                   sample_len: Optional[int] = None, clip_timestamps="0", carry_initial_prompt: bool = False, **_ignored):
         """One clip, same signature as whisper.transcribe as the reference uses it.  temperature 0 is the
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
@@ -716,14 +843,20 @@ class WhisperModel:
         [UPSTREAM-RECALL: transcribe.py::decode_with_fallback; parity unpinned] -- see `transcribe_batch`.  Otherwise a schedule
         raises and the two are ignored.
         On an instance built with `beam_search=True`: beam_size / patience / length_penalty are honoured (see `transcribe_batch`);
-        otherwise they are accepted and ignored."""
+        otherwise they are accepted and ignored.
+        On an instance built with `decoding_options=True`: without_timestamps, prefix, suppress_blank, suppress_tokens,
+        max_initial_timestamp, sample_len, clip_timestamps and carry_initial_prompt are honoured (see `transcribe_batch`); otherwise
+        they are accepted and ignored."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
                                      compression_ratio_threshold=compression_ratio_threshold, best_of=best_of,
                                      temperature=temperature, no_speech_threshold=no_speech_threshold,
                                      logprob_threshold=logprob_threshold, word_timestamps=word_timestamps,
                                      languages=[language], task=task,
                                      hallucination_silence_threshold=hallucination_silence_threshold, beam_size=beam_size,
-                                     patience=patience, length_penalty=length_penalty)[0]
+                                     patience=patience, length_penalty=length_penalty, without_timestamps=without_timestamps,
+                                     prefixes=[prefix], suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
+                                     max_initial_timestamp=max_initial_timestamp, sample_len=sample_len,
+                                     clip_timestamps=clip_timestamps, carry_initial_prompt=carry_initial_prompt)[0]
 
     def transcribe_batch(self, audios: Sequence, initial_prompts: Optional[Sequence[Optional[str]]] = None,
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
@@ -732,7 +865,10 @@ class WhisperModel:
                          task: str = "transcribe", hallucination_silence_threshold: Optional[float] = None,
                          compression_ratio_threshold: Optional[float] = 2.4, best_of: Optional[int] = None,
                          beam_size: Optional[int] = None, patience: Optional[float] = None,
-                         length_penalty: Optional[float] = None) -> List[dict]:
+                         length_penalty: Optional[float] = None, without_timestamps: bool = False,
+                         prefixes: Optional[Sequence] = None, suppress_blank: bool = True, suppress_tokens="-1",
+                         max_initial_timestamp: Optional[float] = 1.0, sample_len: Optional[int] = None, clip_timestamps="0",
+                         carry_initial_prompt: bool = False) -> List[dict]:
         """Independent clips decoded together (each window of each clip is one sequence of a batch).
         languages[i] (multilingual models): the clip's language code or name; None: detected on the clip's first window, after its
         group's `encode` and before its `decode` [UPSTREAM-RECALL: transcribe.py, `if decode_options.get("language") is None`].
@@ -750,7 +886,38 @@ class WhisperModel:
         nothing encoded again; `patience` sets when a window is complete) and keeps the ranker's pick among the hypotheses; above 0
         beam_size and patience are dropped as best_of is at 0; length_penalty enters the ranker of both.  The same thresholds apply, the
         segments carry the walk's fields, word alignment runs afterwards on the accepted tokens.  beam_size with a single temperature
-        above 0, or patience without beam_size, raises.  Without the opt-in all three are ignored: the call is what it is without them."""
+        above 0, or patience without beam_size, raises.  Without the opt-in all three are ignored: the call is what it is without them.
+        decoding_options instances [UPSTREAM-RECALL: decoding.py::DecodingOptions, transcribe.py; parity unpinned]:
+        without_timestamps -- every window's SOT sequence ends in <|notimestamps|> and the steps run the kernels without
+        ApplyTimestampRules: plain text, one segment per window, `seek` advances by the window; prefixes[i] -- a string (encoded as
+        " " + prefix.strip()) or token ids appended behind the SOT sequence of every window of clip i: part of the prompt, never of
+        the result (with sample_len, its last n_ctx // 2 - sample_len tokens; the prefixes of one call must hold equally many tokens
+        -- the library reads the no-speech probability a fixed number of positions before the prompt's end); suppress_blank;
+        suppress_tokens -- comma-separated ids or a list, -1 = the non-speech list, the specials always added, empty or None = no
+        SuppressTokens at all; max_initial_timestamp -- seconds, None = rule off; sample_len -- caps every window's samples;
+        clip_timestamps -- comma-separated seconds or a list: the window loop walks the (start, end) pairs (an odd count is closed by
+        the clip's end), a window ends where its pair ends (`log_mel(max_frames=)`); carry_initial_prompt -- the initial prompt leads
+        every window's prompt.  One ccx_whisper_set_decode_options per call serves every round of a fallback walk or beam search;
+        the defaults are back when the call returns.  without_timestamps with hallucination_silence_threshold raises.  Without the
+        opt-in all of them are ignored."""
+        opt, prefix_toks, clip_spec = None, None, None
+        if self.decoding_options:
+            try:
+                opt = decoding_options.resolve(self.rules, without_timestamps, suppress_blank, suppress_tokens, max_initial_timestamp,
+                                               sample_len, carry_initial_prompt)
+            except ValueError as e:
+                raise _lib.CcxError(str(e)) from e
+            if opt.without_timestamps and hallucination_silence_threshold is not None:
+                raise _lib.CcxError("without_timestamps=True cannot be combined with hallucination_silence_threshold: that rule is "
+                                    "defined on segment timestamps")
+            prefixes = list(prefixes) if prefixes is not None else [None] * len(audios)
+            if len(prefixes) != len(audios):
+                raise _lib.CcxError("transcribe_batch: one prefix (or None) per clip")
+            prefix_toks = [decoding_options.prefix_tokens(self.tokenizer, p, self.dims.n_text_ctx, opt.sample_len) for p in prefixes]
+            if len(set(len(t) for t in prefix_toks)) > 1:
+                raise _lib.CcxError("transcribe_batch: the prefixes of one call must hold equally many tokens (transcribe the clips "
+                                    "one by one otherwise)")
+            clip_spec = clip_timestamps
         with_words = bool(word_timestamps) and self.word_alignment
         if not self.temperature_fallback:
             if isinstance(temperature, (tuple, list)):
@@ -789,9 +956,19 @@ class WhisperModel:
         if len(languages) != n:
             raise _lib.CcxError("transcribe_batch: one language entry (or None) per clip")
         # English-only: language "en", task ignored.  Multilingual: the clip's SOT sequence; language None: pending until detected
+        def loop_options(i):
+            if opt is None:
+                return {}
+            try:
+                clips_i = decoding_options.parse_clip_timestamps(clip_spec, lens[i] // HOP)
+            except ValueError as e:
+                raise _lib.CcxError(f"clip_timestamps: {e}") from e
+            return dict(without_timestamps=opt.without_timestamps, prefix_tokens=prefix_toks[i], sample_len=opt.sample_len,
+                        clips=clips_i, carry_initial_prompt=opt.carry_initial_prompt)
+
         state = [WindowLoop(self.rules, self.tokenizer, lens[i] // HOP, initial_prompts[i], self.dims.n_text_ctx,
                             condition_on_previous_text, no_speech_threshold, logprob_threshold,
-                            language=languages[i] if multi else "en", task=task) for i in range(n)]
+                            language=languages[i] if multi else "en", task=task, **loop_options(i)) for i in range(n)]
         stride = max(max(lens, default=1), 1)
         if stride > self.max_audio_seconds * SAMPLE_RATE:
             raise _lib.CcxError(f"clip of {stride / SAMPLE_RATE:.1f} s exceeds max_audio_seconds={self.max_audio_seconds}")
@@ -805,47 +982,71 @@ class WhisperModel:
             for i, c in enumerate(clips):
                 host[i, :lens[i]] = c
             dev_audio = torch.from_numpy(host).to(self.device)
-        while True:
-            active = [i for i in range(n) if state[i].active()]
-            if not active:
-                break
-            # (a clip whose language is still to be detected already holds a three-token SOT sequence: its cap is known)
-            caps = [state[i].sample_cap() for i in active]
-            for cap, grp in groups_by_cap(active, caps, self.max_batch):
-                if len(grp) == n:
-                    a = dev_audio
-                else:
-                    a = dev_audio.index_select(0, torch.tensor(grp, device=self.device)).contiguous()
-                self.log_mel(a, [lens[i] for i in grp], [state[i].seek for i in grp])
-                self.encode(len(grp))
-                if any(not state[i].language_known for i in grp):     # first window of a clip without a language
-                    codes, _ = self.detect_language(len(grp))
-                    for b, i in enumerate(grp):
-                        if not state[i].language_known:
-                            state[i].set_language(codes[b])
-                prompts = [state[i].initial_tokens() for i in grp]
-                if walk_on:
-                    results = self._decode_with_fallback(prompts, cap, schedule, best_of, compression_ratio_threshold,
-                                                         logprob_threshold, no_speech_threshold, beam_size, patience, length_penalty)
-                    self.fallback_walks[-1].clips, self.fallback_walks[-1].seeks = list(grp), [state[i].seek for i in grp]
-                    n_seg = [len(state[i].segments) for i in grp]
-                    if with_words:     # the accepted tokens, while the group's windows are still encoded: aligned as one batch, each
-                        # window advanced with the temperature it was accepted at
-                        self._advance_with_words(grp, results, state, [r["temperature"] for r in results], hallucination_silence_threshold)
+        # the call's options on the device (one call for every round of the walk) and the SOT tail its prompts carry; both are the
+        # instance's defaults again when the call returns
+        tail0 = self.sot_tail if opt is not None else None
+        dev_opts = opt is not None and not opt.device_default(self.rules)
+        if dev_opts:
+            self.set_decode_options(opt.without_timestamps, opt.suppress_blank, None if opt.suppress_default else opt.suppress,
+                                    opt.max_initial_timestamp_index)
+        if opt is not None and n > 0 and state[0].sot_tail() != tail0:
+            self.set_sot_tail(state[0].sot_tail())
+        n_prefix = len(prefix_toks[0]) if opt is not None and n > 0 else 0
+        if n_prefix:
+            self.set_prefix_len(n_prefix)
+        try:
+            while True:
+                active = [i for i in range(n) if state[i].active()]
+                if not active:
+                    break
+                # (a clip whose language is still to be detected already holds a three-token SOT sequence: its cap is known)
+                caps = [state[i].sample_cap() for i in active]
+                for cap, grp in groups_by_cap(active, caps, self.max_batch):
+                    if len(grp) == n:
+                        a = dev_audio
                     else:
-                        for i, r in zip(grp, results):
-                            state[i].advance(r, r["temperature"])
-                    for b, (i, r) in enumerate(zip(grp, results)):
-                        for s in state[i].segments[n_seg[b]:]:
-                            s.update(temperature=r["temperature"], avg_logprob=r["avg_logprob"], compression_ratio=r["compression_ratio"],
-                                     no_speech_prob=r["no_speech_prob"])
-                    continue
-                self._sample_calls += 1
-                results = self.decode(prompts, sample_len=cap, temperature=temperature,
-                                      seed=(int(self.sample_seed) << 32) + self._sample_calls)
-                if with_words:     # before the next log_mel: the group's windows are still encoded
-                    self._advance_with_words(grp, results, state, temperature, hallucination_silence_threshold)
-                    continue
-                for i, r in zip(grp, results):
-                    state[i].advance(r, temperature)
+                        a = dev_audio.index_select(0, torch.tensor(grp, device=self.device)).contiguous()
+                    if opt is not None:     # a window ends where its clip ends
+                        self.log_mel(a, [lens[i] for i in grp], [state[i].seek for i in grp],
+                                     max_frames=[state[i].segment_size() for i in grp])
+                    else:
+                        self.log_mel(a, [lens[i] for i in grp], [state[i].seek for i in grp])
+                    self.encode(len(grp))
+                    if any(not state[i].language_known for i in grp):     # first window of a clip without a language
+                        codes, _ = self.detect_language(len(grp))
+                        for b, i in enumerate(grp):
+                            if not state[i].language_known:
+                                state[i].set_language(codes[b])
+                    prompts = [state[i].initial_tokens() for i in grp]
+                    if walk_on:
+                        results = self._decode_with_fallback(prompts, cap, schedule, best_of, compression_ratio_threshold,
+                                                             logprob_threshold, no_speech_threshold, beam_size, patience, length_penalty)
+                        self.fallback_walks[-1].clips, self.fallback_walks[-1].seeks = list(grp), [state[i].seek for i in grp]
+                        n_seg = [len(state[i].segments) for i in grp]
+                        if with_words:     # the accepted tokens, while the group's windows are still encoded: aligned as one batch, each
+                            # window advanced with the temperature it was accepted at
+                            self._advance_with_words(grp, results, state, [r["temperature"] for r in results], hallucination_silence_threshold)
+                        else:
+                            for i, r in zip(grp, results):
+                                state[i].advance(r, r["temperature"])
+                        for b, (i, r) in enumerate(zip(grp, results)):
+                            for s in state[i].segments[n_seg[b]:]:
+                                s.update(temperature=r["temperature"], avg_logprob=r["avg_logprob"], compression_ratio=r["compression_ratio"],
+                                         no_speech_prob=r["no_speech_prob"])
+                        continue
+                    self._sample_calls += 1
+                    results = self.decode(prompts, sample_len=cap, temperature=temperature,
+                                          seed=(int(self.sample_seed) << 32) + self._sample_calls)
+                    if with_words:     # before the next log_mel: the group's windows are still encoded
+                        self._advance_with_words(grp, results, state, temperature, hallucination_silence_threshold)
+                        continue
+                    for i, r in zip(grp, results):
+                        state[i].advance(r, temperature)
+        finally:
+            if dev_opts:
+                self.reset_decode_options()
+            if opt is not None and self.sot_tail != tail0:
+                self.set_sot_tail(tail0)
+            if n_prefix:
+                self.set_prefix_len(0)
         return [st.result() for st in state]

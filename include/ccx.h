@@ -178,11 +178,47 @@ int ccx_whisper_share_encoder_scratch(ccx_whisper* w, ccx_whisper* donor);
 int ccx_whisper_finalize(ccx_whisper* w);
 int ccx_whisper_set_rules(ccx_whisper* w, const ccx_decode_rules* rules);
 
+/* Per-call decoding options (openai-whisper decoding.py::DecodingOptions without_timestamps, suppress_blank, suppress_tokens,
+ * max_initial_timestamp [UPSTREAM-RECALL]; parity unpinned).  ccx_decode_options_default fills {0, 1, -2, 0, NULL}: the decode the
+ * rules alone give.
+ *   without_timestamps 1: the step ends in the select / beam kernels WITHOUT ApplyTimestampRules (their own instantiations): an id
+ *     is allowed when the call's mask does not suppress it and, on the first sampled step with suppress_blank on, it is neither
+ *     rules.blank nor rules.eot.  No text / timestamp ranges, no forced timestamp, no max_initial_timestamp; timestamp ids and
+ *     <|notimestamps|> are not banned.  The caller's prompts end in <|notimestamps|>.
+ *   suppress_blank: read by the kernels without the rules only -- with the rules the first step bans every text id and eot anyway.
+ *   max_initial_timestamp_index: -2 the rules' own value, -1 the rule off, >= 0 this index (at most n_vocab - timestamp_begin - 1).
+ *   suppress / n_suppress: NULL = the rules' list; otherwise the list that REPLACES it (host array, copied; n_suppress 0 with a
+ *     non-NULL pointer: nothing is suppressed).  Every id must lie in [0, n_vocab).
+ * ccx_whisper_set_decode_options is sticky like ccx_whisper_set_rules (NULL: back to the defaults) and checked like it: CCX_ERR_ARG
+ * (1) naming "ccx_whisper_set_decode_options" and the field.  It needs the rules.  The instance keeps a SECOND device mask for the
+ * options: the list above (or the rules'), <|notimestamps|> unless without_timestamps is set, and always the ids [n_vocab, n_vocab
+ * rounded up to 4).  Whether a step reads that mask, without_timestamps, suppress_blank and the max_initial_timestamp index are part
+ * of the step plan, so the captured graphs of default decodes and of option decodes live side by side; a call that changes the
+ * mask's contents drops the graphs of the option plans only.  ccx_whisper_set_rules resets the options to the defaults.
+ * ccx_whisper_decode, _decode_rows, _decode_beam and _decode_greedy honour them. */
+typedef struct ccx_decode_options {
+  int without_timestamps;
+  int suppress_blank;
+  int max_initial_timestamp_index;
+  int n_suppress; const int* suppress;
+} ccx_decode_options;
+void ccx_decode_options_default(ccx_decode_options* opts);
+int ccx_whisper_set_decode_options(ccx_whisper* w, const ccx_decode_options* opts);
+/* Captured step graphs the instance holds (options_only != 0: those of option plans only); -1 for a NULL handle.  A test aid: a
+ * default decode after an option decode must find its graph where it left it. */
+int ccx_whisper_graph_count(ccx_whisper* w, int options_only);
+
 /* Log-mel of B clips (whisper.audio.log_mel_spectrogram + pad_or_trim to 3000 frames).
  * audio_dev: [B, stride] f32; n_samples / seek_frames: host int arrays (seek may be NULL = 0).
  * Fills the model's conv-stem input; if mel_out_dev != NULL also writes [B, n_mels, 3000] f32. */
 int ccx_whisper_logmel(ccx_whisper* w, const float* audio_dev, int64_t stride, const int* n_samples,
                        const int* seek_frames, int B, float* mel_out_dev, void* stream);
+/* ccx_whisper_logmel with a cap on every window's frames (transcribe.py's clip_timestamps [UPSTREAM-RECALL]: a window ends where its
+ * clip ends): max_frames host [B] (>= 0) or NULL; window b holds min(3000, content_frames - seek, max_frames[b]) frames of the clip's
+ * log-mel and literal zeros behind them -- pad_or_trim of the cropped mel.  Still normalised by the WHOLE clip's maximum.
+ * ccx_whisper_logmel is the NULL case. */
+int ccx_whisper_logmel_ex(ccx_whisper* w, const float* audio_dev, int64_t stride, const int* n_samples, const int* seek_frames,
+                          const int* max_frames, int B, float* mel_out_dev, void* stream);
 /* Alternative input: take a ready [B, n_mels, 3000] f32 mel (BASELINE config 2 "mel [8,80,3000]"). */
 int ccx_whisper_set_mel(ccx_whisper* w, const float* mel_dev, int B, void* stream);
 /* AudioEncoder.forward for the B staged windows.  The encoder output (bf16) stays with the instance: decodes of more than 80 sequences
@@ -322,6 +358,7 @@ typedef struct ccx_dec_select_desc {
   int sample; float temperature; uint64_t seed; int row0;     /* sample 1: the kernel with the temperature > 0 branch */
   int64_t logits_elems, tok_emb_elems, pos_emb_elems, x_elems;
   const int* stream_ids;                                      /* HOST [B] (>= 0) or NULL: the noise stream of row b instead of row0 + b */
+  const ccx_decode_options* opts;                             /* NULL: the rules alone (appended: nothing before it moves) */
 } ccx_dec_select_desc;
 
 /* One launch of the select kernel (ccx_launch_dec_select) for B rows: filters, argmax / sampling, the per-sequence state machine and
@@ -354,6 +391,7 @@ typedef struct ccx_dec_beam_desc {
   int* fin_tok; float* fin_score; int* fin_n; int* fin_count;
   int* cand_id; float* cand_lp; int* tok_out; int* parent_out;
   int64_t logits_elems, tok_emb_elems, pos_emb_elems, x_elems;
+  const ccx_decode_options* opts;                             /* NULL: the rules alone (appended) */
 } ccx_dec_beam_desc;
 int ccx_dec_beam_step(ccx_ctx* ctx, const ccx_dec_beam_desc* desc, void* stream);
 
@@ -476,12 +514,18 @@ int ccx_whisper_last_cross_path(ccx_whisper* w);
  *
  * ccx_whisper_set_sot_tail: n_tail = tokens of the SOT sequence BEHIND <|startoftranscript|> (0 for the English-only models,
  * 2 for [sot, <|lang|>, <|transcribe|> or <|translate|>]; decoding.py `self.sot_index = self.initial_tokens.index(tokenizer.sot)`).
- * Default 0, allowed 0 .. 2.  With n_tail > 0, or with n_vocab not a multiple of 4, the no_speech_prob of ccx_whisper_decode is the
+ * 3 with <|notimestamps|> behind them: ccx_decode_options.without_timestamps).
+ * Default 0, allowed 0 .. 3 on a multilingual vocabulary (n_vocab >= 51865), 0 .. 2 otherwise.  With n_tail > 0, or with n_vocab not a multiple of 4, the no_speech_prob of ccx_whisper_decode is the
  * softmax probability of rules.no_speech over the ids [0, n_vocab) of the logits at prompt position prompt_len - 1 - n_tail (one more
  * gathered row per sequence in the prefill, one logits GEMM over those rows and dec_token_probs_kernel, all before the captured
  * steps); every prompt must then be longer than n_tail tokens and is prefilled -- CCX_PREFILL=0 (a debugging switch) is refused with
  * CCX_ERR_ARG.  With n_tail == 0 and n_vocab a multiple of 4 a decode issues exactly the launches it issued before. */
 int ccx_whisper_set_sot_tail(ccx_whisper* w, int n_tail);
+/* DecodingOptions.prefix [UPSTREAM-RECALL: decoding.py::_get_initial_tokens]: the last n_prefix tokens of every prompt stand BEHIND the
+ * SOT sequence -- part of the prompt, so the first-step rules apply to the first token sampled after them -- and the no-speech
+ * probability is read at prompt position prompt_len - 1 - n_tail - n_prefix, as above (n_prefix > 0 takes the same path as n_tail > 0).
+ * Sticky; default 0, allowed 0 .. n_text_ctx / 2; every prompt must be longer than n_tail + n_prefix tokens. */
+int ccx_whisper_set_prefix_len(ccx_whisper* w, int n_prefix);
 /* whisper.decoding.detect_language (what transcribe(language=None), upstream's default and the reference's call at
  * back/api.py:1286-1292, runs on the first window) for the B windows currently encoded: one decoder pass over the single token
  * rules.sot at position 0 -- the step kernels and the cross-attention path (ccx_whisper_last_cross_path, which this call sets) of a
@@ -502,8 +546,8 @@ int ccx_whisper_prepare_lanes(ccx_whisper* w, void* stream);
 /* Measurement helper (no counterpart in the reference): while `path` is non-NULL every hipGraph-captured decode step carries
  * one-thread stamp kernels (100 MHz s_memrealtime) around the cross attention of every layer (level 1) or after every kernel of
  * the chain (level 2), per decode lane; each ccx_whisper_decode appends its trace to `path` ("decode B <n> lanes <l>" + one line
- * per lane; tools/decode_stamps.py, bench.py `roofline.frac_in_situ`).  NULL switches it off.  Either call drops the captured
- * step graphs.  Equivalent to creating the model with CCX_DEC_STAMPS=<path> in the environment. */
+ * per lane; tools/decode_stamps.py, bench.py `roofline.frac_in_situ`).  NULL switches it off.  The stamp level is part
+ * of the step plan: traced and untraced step graphs live side by side.  Equivalent to creating the model with CCX_DEC_STAMPS=<path> in the environment. */
 int ccx_whisper_trace_lanes(ccx_whisper* w, const char* path, int level);
 
 /* ---- RE-SepFormer separator (replaces self.separator, reference back/api.py:713-717; call at
