@@ -180,6 +180,30 @@ ECAPA_R2_TILE = 128              # csrc/ecapa.h ECAPA_R2_TILE: output frames of 
 ECAPA_MIN_SAMPLES = 8000         # csrc/ecapa.h ECAPA_MIN_SAMPLES
 
 
+class ResnetDesc(C.Structure):
+    """ccx_resnet_desc (include/ccx.h): one ResNet-34 kernel on its own."""
+    _fields_ = [
+        ("n_chunks", C.c_int),
+        ("wav", C.c_void_p), ("wav_elems", C.c_int64), ("stride", C.c_int64), ("n_samples", C.c_int),
+        ("feats_t", C.c_void_p), ("feats_t_elems", C.c_int64), ("fmean", C.c_void_p), ("fmean_elems", C.c_int64),
+        ("T", C.c_int), ("c1w", C.c_void_p), ("c1w_elems", C.c_int64), ("c1b", C.c_void_p), ("c1b_elems", C.c_int64),
+        ("cin", C.c_int), ("cout", C.c_int), ("k", C.c_int), ("conv_stride", C.c_int), ("H", C.c_int), ("W", C.c_int), ("epi", C.c_int),
+        ("w_host", C.POINTER(C.c_float)), ("scale_host", C.POINTER(C.c_float)), ("shift_host", C.POINTER(C.c_float)),
+        ("in_", C.c_void_p), ("in_elems", C.c_int64), ("out", C.c_void_p), ("out_elems", C.c_int64),
+        ("resid", C.c_void_p), ("resid_elems", C.c_int64),
+        ("halo0", C.c_void_p), ("halo1", C.c_void_p), ("halo2", C.c_void_p), ("halo0_elems", C.c_int64),
+        ("c0", C.c_int), ("n", C.c_int), ("Wp", C.c_int), ("C", C.c_int),
+        ("act", C.c_void_p), ("act_elems", C.c_int64), ("W4", C.c_int),
+        ("weights", C.c_void_p), ("weights_elems", C.c_int64), ("n_w", C.c_int), ("mask_chunk", C.POINTER(C.c_int)), ("n_masks", C.c_int),
+        ("pooled", C.c_void_p), ("pooled_elems", C.c_int64),
+        ("lin_w", C.c_void_p), ("lin_w_elems", C.c_int64), ("lin_b", C.c_void_p), ("lin_b_elems", C.c_int64),
+        ("emb", C.c_void_p), ("emb_elems", C.c_int64)]
+
+
+RESNET_FBANK, RESNET_CONV1, RESNET_CONV, RESNET_HALO_ZERO, RESNET_TSTP, RESNET_LINEAR = range(6)
+RESNET_EPI_PLAIN, RESNET_EPI_RELU, RESNET_EPI_ADD_RELU = range(3)
+
+
 class AlignDesc(C.Structure):
     """ccx_align_desc (include/ccx.h): one word-alignment kernel on its own."""
     _fields_ = [
@@ -288,6 +312,7 @@ PROTOTYPES = {
     "ccx_resnet_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i64]),
     "ccx_resnet_finalize": (_i, [_vp]),
     "ccx_resnet_embed": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _ip, _i, _vp, _vp]),
+    "ccx_resnet_op": (_i, [_vp, _i, C.POINTER(ResnetDesc), _vp]),
     "ccx_specgate_create": (_i, [_vp, _i64, _i, _i, C.POINTER(_vp)]),
     "ccx_specgate_destroy": (None, [_vp]),
     "ccx_specgate_reduce": (_i, [_vp, _vp, _i64, _ip, _i, _f, _vp, _vp]),

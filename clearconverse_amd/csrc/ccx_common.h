@@ -127,6 +127,12 @@ __device__ __forceinline__ bf16_t f32_to_bf16(float f) {
   return __builtin_bit_cast(uint16_t, b);
 }
 
+// Source index of destination element t under F.interpolate(mode="nearest") from n_in to n_out elements, the way torch computes it:
+// scale = (float)n_in / (float)n_out in fp32 (the caller hoists it), src = min(floor(t * scale), n_in - 1).  The exact rational
+// (t * n_in) / n_out is NOT the same map: where t * n_in / n_out is an integer the fp32 product can round below it (n_out = 14,
+// n_in = 62, t = 7: torch 30, exact 31).  Both weighted pooling kernels (resnet.hip tstp_kernel, speaker.hip stats_pool_kernel) use this.
+__device__ __forceinline__ int ccx_nearest_src(int t, float scale, int n_in) { return min((int)floorf(t * scale), n_in - 1); }
+
 // two round-to-nearest-even conversions in ONE v_cvt_pk_bf16_f32 (the scalar form costs a convert, a shift and an or per value)
 typedef __attribute__((ext_vector_type(2))) float ccx_f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 ccx_bf16x2;

@@ -17,6 +17,13 @@
 //
 // The convolutional trunk depends only on the chunk, not on the speaker mask, so it runs once per chunk and the
 // pooling + linear run once per (chunk, local speaker) mask.
+//
+// The kernels on their own.  ccx_resnet_op (include/ccx.h; for kernel parity tests, ccx_resnet_embed does not call it) runs one of
+// FBANK, CONV1, CONV, HALO_ZERO, TSTP, LINEAR on buffers a test chooses.  Both it and ccx_resnet_embed launch through the same
+// functions below (launch_fbank, launch_conv1, run_conv, launch_halo_zero, launch_tstp, launch_embed_linear), build the fbank tables
+// with fbank_tables and pack convolution weights with pack_conv, so a test of the entry is a test of the product's code.  CONV takes
+// host torch-layout weights with a host scale / shift and dispatches as run_conv does; its input count must cover conv_in_need, the
+// read slack of the strided view that ccx_resnet_finalize adds to every activation buffer.
 #include <string>
 #include <vector>
 #include <math.h>
@@ -24,6 +31,7 @@
 #include "ccx_common.h"
 #include "gemm_bf16.h"
 #include "model_store.h"
+#include "op_scratch.h"
 
 namespace {
 
@@ -298,9 +306,9 @@ __global__ __launch_bounds__(256) void tstp_kernel(const bf16_t* __restrict__ ac
   const bf16_t* base = act + (((long)chunk * 12 + h + 1) * Wp + 1) * 256 + c;
   const float* wj = weights ? weights + (long)j * n_w : nullptr;
   float v1 = 0.f, v2 = 0.f, sx = 0.f;
-  const float scale = (float)n_w / (float)W4;   // F.interpolate(mode="nearest"): src = min(floor(dst * in/out), in - 1)
+  const float scale = (float)n_w / (float)W4;   // F.interpolate(mode="nearest"): ccx_nearest_src (ccx_common.h)
   for (int t = 0; t < W4; t++) {
-    const float w = wj ? wj[min((int)floorf(t * scale), n_w - 1)] : 1.f;
+    const float w = wj ? wj[ccx_nearest_src(t, scale, n_w)] : 1.f;
     v1 += w; v2 += w * w;
     sx = fmaf(w, bf16_to_f32(base[(long)t * 256]), sx);
   }
@@ -308,7 +316,7 @@ __global__ __launch_bounds__(256) void tstp_kernel(const bf16_t* __restrict__ ac
   const float mean = sx / v1;
   float sq = 0.f;
   for (int t = 0; t < W4; t++) {
-    const float w = wj ? wj[min((int)floorf(t * scale), n_w - 1)] : 1.f;
+    const float w = wj ? wj[ccx_nearest_src(t, scale, n_w)] : 1.f;
     const float d = bf16_to_f32(base[(long)t * 256]) - mean;
     sq = fmaf(w, d * d, sq);
   }
@@ -383,19 +391,24 @@ int bn_fold(ccx_resnet* r, const std::string& name, int c, std::vector<float>& s
   return CCX_OK;
 }
 
-// torch Conv2d weight [cout][cin][k][k] (+ folded BN scale) -> [cout][k taps][Kpad] with columns kw * cin + c
-int load_conv(ccx_resnet* r, const std::string& wname, const std::string& bnname, int cin, int cout, int k, int stride, Conv& cv) {
-  CCX_NEED(r->store, w, wname, (int64_t)cout * cin * k * k);
-  std::vector<float> sc, sh;
-  CCX_TRY(bn_fold(r, bnname, cout, sc, sh));
+// torch Conv2d weight [cout][cin][k][k] (+ folded BN scale) -> [cout][k taps][Kpad] with columns kw * cin + c; sets cv's geometry
+void pack_conv(const float* w, const float* scale, int cin, int cout, int k, int stride, Conv& cv, std::vector<bf16_t>& packed) {
   cv.cin = cin; cv.cout = cout; cv.k = k; cv.stride = stride;
   cv.Kpad = ccx_align(k * cin, 64);
-  std::vector<bf16_t> packed((size_t)cout * k * cv.Kpad, 0);
+  packed.assign((size_t)cout * k * cv.Kpad, 0);
   for (int o = 0; o < cout; o++)
     for (int c = 0; c < cin; c++)
       for (int kh = 0; kh < k; kh++)
         for (int kw = 0; kw < k; kw++)
-          packed[((size_t)o * k + kh) * cv.Kpad + kw * cin + c] = ccx_host_f32_to_bf16(w->data[(((size_t)o * cin + c) * k + kh) * k + kw] * sc[o]);
+          packed[((size_t)o * k + kh) * cv.Kpad + kw * cin + c] = ccx_host_f32_to_bf16(w[(((size_t)o * cin + c) * k + kh) * k + kw] * scale[o]);
+}
+
+int load_conv(ccx_resnet* r, const std::string& wname, const std::string& bnname, int cin, int cout, int k, int stride, Conv& cv) {
+  CCX_NEED(r->store, w, wname, (int64_t)cout * cin * k * k);
+  std::vector<float> sc, sh;
+  CCX_TRY(bn_fold(r, bnname, cout, sc, sh));
+  std::vector<bf16_t> packed;
+  pack_conv(w->data.data(), sc.data(), cin, cout, k, stride, cv, packed);
   CCX_TRY(r->store.upload(&cv.W, packed));
   CCX_TRY(r->store.upload(&cv.b, sh));
   return CCX_OK;
@@ -430,18 +443,99 @@ void stage_dims(int T, StageDims (&d)[RN_STAGES]) {
   }
 }
 
-// one convolution as a GEMM over a strided view of `in` (stage si) writing the padded layout of `out` (stage so)
-int run_conv(ccx_resnet* r, const Conv& cv, int epi, const bf16_t* in, const StageDims& di, bf16_t* out, const StageDims& dn,
+// ---- fbank tables (Kaldi mel scale, triangular filters linear in mel, 20 Hz .. Nyquist) ----
+struct FbankTables {
+  std::vector<float> win, mw;
+  std::vector<float2> tw;
+  std::vector<int> ms, ml;
+};
+int fbank_tables(ccx_ctx* ctx, FbankTables& t) {
+  t.win.resize(FB_LEN);
+  for (int i = 0; i < FB_LEN; i++) t.win[i] = (float)(0.54 - 0.46 * cos(2.0 * M_PI * i / (FB_LEN - 1)));
+  t.tw.resize(FB_NFFT / 2);
+  for (int i = 0; i < FB_NFFT / 2; i++) t.tw[i] = make_float2((float)cos(-2.0 * M_PI * i / FB_NFFT), (float)sin(-2.0 * M_PI * i / FB_NFFT));
+  auto mel = [](double f) { return 1127.0 * log(1.0 + f / 700.0); };
+  const double mlo = mel(20.0), mhi = mel(8000.0), delta = (mhi - mlo) / (FB_MELS + 1);
+  t.mw.assign((size_t)FB_MELS * FB_MELW, 0.f);
+  t.ms.assign(FB_MELS, 0); t.ml.assign(FB_MELS, 0);
+  for (int m = 0; m < FB_MELS; m++) {
+    const double left = mlo + m * delta, center = left + delta, right = center + delta;
+    int first = -1, last = -1;
+    std::vector<float> wts(FB_NFFT / 2, 0.f);
+    for (int k = 0; k < FB_NFFT / 2; k++) {
+      const double mk = mel(16000.0 / FB_NFFT * k);
+      const double up = (mk - left) / (center - left), down = (right - mk) / (right - center);
+      const double wv = fmax(0.0, fmin(up, down));
+      wts[k] = (float)wv;
+      if (wv > 0.0) { if (first < 0) first = k; last = k; }
+    }
+    if (first < 0) { first = 0; last = -1; }
+    CCX_REQUIRE(ctx, last - first + 1 <= FB_MELW, "resnet: mel filter %d spans %d bins", m, last - first + 1);
+    t.ms[m] = first; t.ml[m] = last - first + 1;
+    for (int k = first; k <= last; k++) t.mw[(size_t)m * FB_MELW + (k - first)] = wts[k];
+  }
+  return CCX_OK;
+}
+
+// ---- launchers: ccx_resnet_embed and ccx_resnet_op both launch through these ----
+struct FbankDev { const float* window; const float2* twiddle; const float* melw; const int* mel_start; const int* mel_len; };
+
+int launch_fbank(ccx_ctx* ctx, const float* wav, long stride, int n_samples, int T, int n_chunks, const FbankDev& tb, float* feats_t,
+                 float* fmean, hipStream_t st) {
+  {
+    ccx_prof_scope ps(ctx, st, "fbank_kernel", 0.0, (double)n_chunks * n_samples * 4 + (double)n_chunks * T * FB_MELS * 4);
+    hipLaunchKernelGGL(fbank_kernel, dim3(ccx_cdiv(T, 4), n_chunks), dim3(256), 0, st, wav, stride, T, tb.window, tb.twiddle, tb.melw,
+                       tb.mel_start, tb.mel_len, feats_t);
+  }
+  CCX_CHECK_LAUNCH(ctx);
+  hipLaunchKernelGGL(fbank_mean_kernel, dim3(n_chunks * FB_MELS), dim3(256), 0, st, feats_t, T, fmean);
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int launch_conv1(ccx_ctx* ctx, const float* feats_t, const float* fmean, int T, int n_chunks, const float* w, const float* bias, bf16_t* out,
+                 hipStream_t st) {
+  {
+    ccx_prof_scope ps(ctx, st, "conv1_kernel", 2.0 * 9 * RN_C0 * (double)n_chunks * FB_MELS * T, (double)n_chunks * FB_MELS * T * (4 + RN_C0 * 2));
+    hipLaunchKernelGGL(conv1_kernel, dim3(ccx_cdiv(T, 256), FB_MELS, n_chunks), dim3(256), 0, st, feats_t, fmean, T, w, bias, out);
+  }
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+// halo cells of chunks [c0, c0 + n) of three [chunk][H + 2][Wp][C] buffers
+int launch_halo_zero(ccx_ctx* ctx, bf16_t* b0, bf16_t* b1, bf16_t* b2, int c0, int n, int H, long Wp, int C, hipStream_t st) {
+  hipLaunchKernelGGL(halo_zero_kernel, dim3(H + 2, n, 3), dim3(256), 0, st, b0, b1, b2, c0, H, Wp, C);
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int launch_tstp(ccx_ctx* ctx, const bf16_t* act, int W4, const int* mask_chunk_dev, const float* weights, int n_w, int n_masks, float* pooled,
+                hipStream_t st) {
+  hipLaunchKernelGGL(tstp_kernel, dim3(10, n_masks), dim3(256), 0, st, act, W4, mask_chunk_dev, weights, n_w, pooled);
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int launch_embed_linear(ccx_ctx* ctx, const float* pooled, const float* W, const float* bias, int n_masks, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(embed_linear_kernel, dim3(RN_EMB / 4, n_masks), dim3(256), 0, st, pooled, W, bias, out);
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+// one convolution: the direct stage-1 kernel where it applies, else a GEMM over a strided view of `in` (layout di) writing the padded
+// layout of `out` (layout dn)
+int run_conv(ccx_ctx* ctx, const Conv& cv, int epi, const bf16_t* in, const StageDims& di, bf16_t* out, const StageDims& dn,
              const bf16_t* resid, int n_chunks, hipStream_t st) {
   if (cv.cin == 32 && cv.cout == 32 && cv.k == 3 && cv.stride == 1 && di.H % 4 == 0 && (epi == EPI_BF16_RELU || epi == EPI_BF16_ADD_RELU)) {
     const dim3 grid(1, di.H / 4, n_chunks);
     {
-      ccx_prof_scope ps(r->ctx, st, "conv3x3_c32_kernel", 2.0 * 9 * 32 * 32 * (double)n_chunks * di.H * di.W,
+      ccx_prof_scope ps(ctx, st, "conv3x3_c32_kernel", 2.0 * 9 * 32 * 32 * (double)n_chunks * di.H * di.W,
                         (double)n_chunks * di.H * di.W * 64.0 * (resid ? 3 : 2));
       if (resid) hipLaunchKernelGGL(conv3x3_c32_kernel<true>, grid, dim3(256), 0, st, in, cv.W, cv.b, resid, out, di.H, di.W);
       else hipLaunchKernelGGL(conv3x3_c32_kernel<false>, grid, dim3(256), 0, st, in, cv.W, cv.b, resid, out, di.H, di.W);
     }
-    CCX_CHECK_LAUNCH(r->ctx);
+    CCX_CHECK_LAUNCH(ctx);
     return CCX_OK;
   }
   GemmParams p;
@@ -457,7 +551,16 @@ int run_conv(ccx_resnet* r, const Conv& cv, int epi, const bf16_t* in, const Sta
   p.rpb_in = (int)di.Wp; p.rpb_valid = dn.W; p.rpb_out = (int)dn.Wp; p.roff = (int)dn.Wp + 1;
   p.img_rows_in = RI; p.img_rows_valid = dn.H; p.img_rows_out = dn.H + 2;
   p.resid_bf16 = resid; p.ldrb = cv.cout;
-  return ccx_launch_gemm(r->ctx, epi, p, st);
+  return ccx_launch_gemm(ctx, epi, p, st);
+}
+
+// Elements of `in` the convolution's reads stay below: the padded layout for the direct kernel's tile loads, and for the GEMM's
+// strided view the last (dropped) row's taps -- up to two padded rows and one K tile past the layout.
+long conv_in_need(const Conv& cv, const StageDims& di, int n_chunks) {
+  const long layout = (long)n_chunks * (di.H + 2) * di.Wp * di.C;
+  const long M = (long)n_chunks * ((di.H + 2) / cv.stride) * di.Wp;
+  const long view = (cv.k == 1 ? (di.Wp + 1) * di.C : 0) + (M - 1) * cv.stride * di.C + (long)(cv.k - 1) * di.Wp * di.C + cv.Kpad;
+  return view > layout ? view : layout;
 }
 
 }  // namespace
@@ -492,34 +595,11 @@ int ccx_resnet_finalize(ccx_resnet* r) {
   if (!r) return CCX_ERR_ARG;
   ccx_ctx* ctx = r->ctx;
   CCX_REQUIRE(ctx, !r->finalized, "resnet: finalize called twice");
-  // ---- fbank tables (Kaldi mel scale, triangular filters linear in mel, 20 Hz .. Nyquist) ----
   {
-    std::vector<float> win(FB_LEN);
-    for (int i = 0; i < FB_LEN; i++) win[i] = (float)(0.54 - 0.46 * cos(2.0 * M_PI * i / (FB_LEN - 1)));
-    std::vector<float2> tw(FB_NFFT / 2);
-    for (int i = 0; i < FB_NFFT / 2; i++) tw[i] = make_float2((float)cos(-2.0 * M_PI * i / FB_NFFT), (float)sin(-2.0 * M_PI * i / FB_NFFT));
-    auto mel = [](double f) { return 1127.0 * log(1.0 + f / 700.0); };
-    const double mlo = mel(20.0), mhi = mel(8000.0), delta = (mhi - mlo) / (FB_MELS + 1);
-    std::vector<float> mw((size_t)FB_MELS * FB_MELW, 0.f);
-    std::vector<int> ms(FB_MELS, 0), ml(FB_MELS, 0);
-    for (int m = 0; m < FB_MELS; m++) {
-      const double left = mlo + m * delta, center = left + delta, right = center + delta;
-      int first = -1, last = -1;
-      std::vector<float> wts(FB_NFFT / 2, 0.f);
-      for (int k = 0; k < FB_NFFT / 2; k++) {
-        const double mk = mel(16000.0 / FB_NFFT * k);
-        const double up = (mk - left) / (center - left), down = (right - mk) / (right - center);
-        const double wv = fmax(0.0, fmin(up, down));
-        wts[k] = (float)wv;
-        if (wv > 0.0) { if (first < 0) first = k; last = k; }
-      }
-      if (first < 0) { first = 0; last = -1; }
-      CCX_REQUIRE(ctx, last - first + 1 <= FB_MELW, "resnet: mel filter %d spans %d bins", m, last - first + 1);
-      ms[m] = first; ml[m] = last - first + 1;
-      for (int k = first; k <= last; k++) mw[(size_t)m * FB_MELW + (k - first)] = wts[k];
-    }
-    CCX_TRY(r->store.upload(&r->window, win)); CCX_TRY(r->store.upload(&r->twiddle, tw)); CCX_TRY(r->store.upload(&r->melw, mw));
-    CCX_TRY(r->store.upload(&r->mel_start, ms)); CCX_TRY(r->store.upload(&r->mel_len, ml));
+    FbankTables t;
+    CCX_TRY(fbank_tables(ctx, t));
+    CCX_TRY(r->store.upload(&r->window, t.win)); CCX_TRY(r->store.upload(&r->twiddle, t.tw)); CCX_TRY(r->store.upload(&r->melw, t.mw));
+    CCX_TRY(r->store.upload(&r->mel_start, t.ms)); CCX_TRY(r->store.upload(&r->mel_len, t.ml));
   }
   // ---- conv1 (kept f32: one input channel) ----
   {
@@ -565,6 +645,13 @@ int ccx_resnet_finalize(ccx_resnet* r) {
     r->act_elems[s] = (size_t)r->max_chunks * (d[s].H + 2) * d[s].Wp * d[s].C + 4 * d[s].Wp * d[s].C + 1024;
     for (int k = 0; k < 3; k++) CCX_TRY(r->store.alloc(&r->act[s][k], r->act_elems[s], true));
   }
+  for (int s = 0, bi = 0; s < RN_STAGES; s++)
+    for (int b = 0; b < RN_BLOCKS[s]; b++, bi++) {
+      const Block& blk = r->blocks[bi];
+      const int si = (b == 0 && s > 0) ? s - 1 : s;   // the stage whose layout the block's input has
+      CCX_REQUIRE(ctx, (size_t)conv_in_need(blk.c1, d[si], r->max_chunks) <= r->act_elems[si] && (size_t)conv_in_need(blk.c2, d[s], r->max_chunks) <= r->act_elems[s] &&
+                  (!blk.has_sc || (size_t)conv_in_need(blk.sc, d[si], r->max_chunks) <= r->act_elems[si]), "resnet: the activation slack does not cover block %d's views", bi);
+    }
   r->finalized = true;
   return CCX_OK;
 }
@@ -595,26 +682,13 @@ int ccx_resnet_embed(ccx_resnet* r, const float* wav_dev, int64_t stride, int n_
   if (T != r->last_T) { r->last_T = T; r->halo_chunks = 0; }   // the halo cells move with the frame count
   if (n_chunks > r->halo_chunks) {
     for (int s = 0; s < RN_STAGES; s++)
-      hipLaunchKernelGGL(halo_zero_kernel, dim3(d[s].H + 2, n_chunks - r->halo_chunks, 3), dim3(256), 0, st, r->act[s][0], r->act[s][1],
-                         r->act[s][2], r->halo_chunks, d[s].H, d[s].Wp, d[s].C);
-    CCX_CHECK_LAUNCH(ctx);
+      CCX_TRY(launch_halo_zero(ctx, r->act[s][0], r->act[s][1], r->act[s][2], r->halo_chunks, n_chunks - r->halo_chunks, d[s].H, d[s].Wp,
+                               d[s].C, st));
     r->halo_chunks = n_chunks;
   }
-  {
-    ccx_prof_scope ps(ctx, st, "fbank_kernel", 0.0, (double)n_chunks * n_samples * 4 + (double)n_chunks * T * FB_MELS * 4);
-    hipLaunchKernelGGL(fbank_kernel, dim3(ccx_cdiv(T, 4), n_chunks), dim3(256), 0, st, wav_dev, (long)stride, T, r->window, r->twiddle,
-                       r->melw, r->mel_start, r->mel_len, r->feats_t);
-  }
-  CCX_CHECK_LAUNCH(ctx);
-  hipLaunchKernelGGL(fbank_mean_kernel, dim3(n_chunks * FB_MELS), dim3(256), 0, st, r->feats_t, T, r->fmean);
-  CCX_CHECK_LAUNCH(ctx);
-  {
-    ccx_prof_scope ps(ctx, st, "conv1_kernel", 2.0 * 9 * RN_C0 * (double)n_chunks * FB_MELS * T,
-                      (double)n_chunks * FB_MELS * T * (4 + RN_C0 * 2));
-    hipLaunchKernelGGL(conv1_kernel, dim3(ccx_cdiv(T, 256), FB_MELS, n_chunks), dim3(256), 0, st, r->feats_t, r->fmean, T, r->c1w, r->c1b,
-                       r->act[0][0]);
-  }
-  CCX_CHECK_LAUNCH(ctx);
+  const FbankDev tb{r->window, r->twiddle, r->melw, r->mel_start, r->mel_len};
+  CCX_TRY(launch_fbank(ctx, wav_dev, (long)stride, n_samples, T, n_chunks, tb, r->feats_t, r->fmean, st));
+  CCX_TRY(launch_conv1(ctx, r->feats_t, r->fmean, T, n_chunks, r->c1w, r->c1b, r->act[0][0], st));
   // residual stages: x lives in act[s][cur]; t = relu(conv1(x)); y = relu(conv2(t) + shortcut(x))
   int bi = 0, cur = 0;
   const bf16_t* x = r->act[0][0];
@@ -628,24 +702,157 @@ int ccx_resnet_embed(ccx_resnet* r, const float* wav_dev, int64_t stride, int n_
       } else {  // first block of a stage: x is still in the previous stage's layout
         tbuf = r->act[s][0]; ybuf = r->act[s][1]; scbuf = r->act[s][2];
       }
-      CCX_TRY(run_conv(r, blk.c1, EPI_BF16_RELU, x, d[xs], tbuf, d[s], nullptr, n_chunks, st));
+      CCX_TRY(run_conv(ctx, blk.c1, EPI_BF16_RELU, x, d[xs], tbuf, d[s], nullptr, n_chunks, st));
       const bf16_t* resid = x;
       if (blk.has_sc) {
         CCX_REQUIRE(ctx, scbuf != nullptr, "resnet: shortcut convolution inside a stage");
-        CCX_TRY(run_conv(r, blk.sc, EPI_BF16, x, d[xs], scbuf, d[s], nullptr, n_chunks, st));
+        CCX_TRY(run_conv(ctx, blk.sc, EPI_BF16, x, d[xs], scbuf, d[s], nullptr, n_chunks, st));
         resid = scbuf;
       }
-      CCX_TRY(run_conv(r, blk.c2, EPI_BF16_ADD_RELU, tbuf, d[s], ybuf, d[s], resid, n_chunks, st));
+      CCX_TRY(run_conv(ctx, blk.c2, EPI_BF16_ADD_RELU, tbuf, d[s], ybuf, d[s], resid, n_chunks, st));
       x = ybuf; xs = s;
       cur = (int)(ybuf == r->act[s][0] ? 0 : (ybuf == r->act[s][1] ? 1 : 2));
     }
   }
-  hipLaunchKernelGGL(tstp_kernel, dim3(10, n_masks), dim3(256), 0, st, x, d[3].W, weights_dev ? r->mask_chunk_dev : nullptr, weights_dev,
-                     n_w, r->pooled);
-  CCX_CHECK_LAUNCH(ctx);
-  hipLaunchKernelGGL(embed_linear_kernel, dim3(RN_EMB / 4, n_masks), dim3(256), 0, st, r->pooled, r->segW, r->segb, out_dev);
-  CCX_CHECK_LAUNCH(ctx);
+  CCX_TRY(launch_tstp(ctx, x, d[3].W, weights_dev ? r->mask_chunk_dev : nullptr, weights_dev, n_w, n_masks, r->pooled, st));
+  CCX_TRY(launch_embed_linear(ctx, r->pooled, r->segW, r->segb, n_masks, out_dev, st));
   return CCX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the kernels on their own (include/ccx.h: ccx_resnet_op)
+// ---------------------------------------------------------------------------------------------
+#define RN_BUF(field, need)                                                                                                         \
+  do {                                                                                                                              \
+    CCX_REQUIRE(ctx, d->field != nullptr, "ccx_resnet_op: %s is NULL", #field);                                                     \
+    CCX_REQUIRE(ctx, ccx_aligned16(d->field), "ccx_resnet_op: %s is not 16-byte aligned", #field);                                  \
+    CCX_REQUIRE(ctx, d->field##_elems >= (int64_t)(need), "ccx_resnet_op: %s is accessed up to element %ld, %s_elems=%ld", #field,  \
+                (long)(need), #field, (long)d->field##_elems);                                                                      \
+  } while (0)
+#define RN_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return ccx_fail(ctx, CCX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+
+int ccx_resnet_op(ccx_ctx* ctx, int op, const ccx_resnet_desc* d, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream_;
+  CCX_REQUIRE(ctx, d != nullptr, "ccx_resnet_op: desc is NULL");
+  CCX_REQUIRE(ctx, op >= CCX_RESNET_FBANK && op <= CCX_RESNET_LINEAR, "ccx_resnet_op: unknown op %d", op);
+  const long n = d->n_chunks;
+  if (op != CCX_RESNET_HALO_ZERO && op != CCX_RESNET_LINEAR)
+    CCX_REQUIRE(ctx, n >= 1 && n <= 65535, "ccx_resnet_op: n_chunks = %d out of range [1, 65535]", d->n_chunks);
+  Conv cv;
+  StageDims di{}, dn{};
+  std::vector<bf16_t> packed;
+  int T = 0, epi = EPI_BF16;
+  switch (op) {
+    case CCX_RESNET_FBANK:
+      CCX_REQUIRE(ctx, d->n_samples >= FB_LEN && d->n_samples <= (1 << 24), "ccx_resnet_op: n_samples = %d out of range [%d, 2^24]", d->n_samples, FB_LEN);
+      CCX_REQUIRE(ctx, d->stride >= d->n_samples && d->stride <= (1L << 32), "ccx_resnet_op: stride = %ld is below n_samples = %d (or above 2^32)",
+                  (long)d->stride, d->n_samples);
+      T = 1 + (d->n_samples - FB_LEN) / FB_SHIFT;
+      CCX_REQUIRE(ctx, d->wav != nullptr && ((uintptr_t)d->wav & 3) == 0, "ccx_resnet_op: wav is NULL or not 4-byte aligned");
+      CCX_REQUIRE(ctx, d->wav_elems >= (n - 1) * d->stride + d->n_samples, "ccx_resnet_op: wav is read up to element %ld, wav_elems=%ld",
+                  (long)((n - 1) * d->stride + d->n_samples), (long)d->wav_elems);
+      RN_BUF(feats_t, n * FB_MELS * T); RN_BUF(fmean, n * FB_MELS);
+      break;
+    case CCX_RESNET_CONV1:
+      T = d->T;
+      CCX_REQUIRE(ctx, T >= 1 && T <= (1 << 20), "ccx_resnet_op: T = %d out of range [1, 2^20]", T);
+      CCX_REQUIRE(ctx, n * (FB_MELS + 2) * (T + 2) < (1L << 31), "ccx_resnet_op: n_chunks x T too large for one launch");
+      RN_BUF(feats_t, n * FB_MELS * T); RN_BUF(fmean, n * FB_MELS);
+      RN_BUF(c1w, RN_C0 * 9); RN_BUF(c1b, RN_C0);
+      RN_BUF(out, n * (FB_MELS + 2) * (T + 2) * RN_C0);
+      break;
+    case CCX_RESNET_CONV: {
+      const int cin = d->cin, cout = d->cout, k = d->k, s = d->conv_stride;
+      const bool chan = cin == 32 || cin == 64 || cin == 128 || cin == 256;
+      const bool same = chan && cout == cin && k == 3 && s == 1;                         // inside a stage
+      const bool down = chan && cin <= 128 && cout == 2 * cin && (k == 3 || k == 1) && s == 2;   // first block of stages 2..4 and its shortcut
+      CCX_REQUIRE(ctx, same || down, "ccx_resnet_op: (cin, cout, k, conv_stride) = (%d, %d, %d, %d) is no convolution of the network", cin, cout, k, s);
+      CCX_REQUIRE(ctx, d->H >= 2 && d->H % 2 == 0 && d->H <= 4096, "ccx_resnet_op: H = %d must be even in [2, 4096]", d->H);
+      CCX_REQUIRE(ctx, d->W >= 2 && d->W <= (1 << 20), "ccx_resnet_op: W = %d out of range [2, 2^20]", d->W);
+      CCX_REQUIRE(ctx, d->epi >= CCX_RESNET_EPI_PLAIN && d->epi <= CCX_RESNET_EPI_ADD_RELU, "ccx_resnet_op: epi = %d is none of plain, ReLU, add-ReLU", d->epi);
+      epi = d->epi == CCX_RESNET_EPI_PLAIN ? EPI_BF16 : (d->epi == CCX_RESNET_EPI_RELU ? EPI_BF16_RELU : EPI_BF16_ADD_RELU);
+      CCX_REQUIRE(ctx, d->w_host && d->scale_host && d->shift_host, "ccx_resnet_op: w_host, scale_host or shift_host is NULL");
+      di = {d->H, d->W, cin, (long)d->W + 2};
+      dn = s == 1 ? StageDims{d->H, d->W, cout, (long)d->W + 2} : StageDims{d->H / 2, (d->W - 1) / 2 + 1, cout, (long)(d->W - 1) / 2 + 3};
+      CCX_REQUIRE(ctx, n * (d->H + 2) * di.Wp < (1L << 31), "ccx_resnet_op: n_chunks x H x W too large for one launch");
+      pack_conv(d->w_host, d->scale_host, cin, cout, k, s, cv, packed);
+      RN_BUF(in, conv_in_need(cv, di, (int)n));
+      RN_BUF(out, n * (dn.H + 2) * dn.Wp * cout);
+      if (d->epi == CCX_RESNET_EPI_ADD_RELU) RN_BUF(resid, n * (dn.H + 2) * dn.Wp * cout);
+      else CCX_REQUIRE(ctx, d->resid == nullptr, "ccx_resnet_op: resid is given, epi = %d does not add it", d->epi);
+      {
+        const bf16_t *i0 = (const bf16_t*)d->in, *i1 = i0 + d->in_elems, *o0 = (const bf16_t*)d->out, *o1 = o0 + d->out_elems;
+        CCX_REQUIRE(ctx, o1 <= i0 || i1 <= o0, "ccx_resnet_op: out overlaps in");
+      }
+      break;
+    }
+    case CCX_RESNET_HALO_ZERO:
+      CCX_REQUIRE(ctx, d->C == 32 || d->C == 64 || d->C == 128 || d->C == 256, "ccx_resnet_op: C = %d is none of 32, 64, 128, 256", d->C);
+      CCX_REQUIRE(ctx, d->H >= 1 && d->H <= 4096, "ccx_resnet_op: H = %d out of range [1, 4096]", d->H);
+      CCX_REQUIRE(ctx, d->Wp >= 3 && d->Wp <= (1 << 20), "ccx_resnet_op: Wp = %d out of range [3, 2^20]", d->Wp);
+      CCX_REQUIRE(ctx, d->c0 >= 0 && d->n >= 1 && d->n <= 65535 && d->c0 <= (1 << 20), "ccx_resnet_op: c0 = %d, n = %d: need c0 in [0, 2^20] and n in [1, 65535]", d->c0, d->n);
+      RN_BUF(halo0, (long)(d->c0 + d->n) * (d->H + 2) * d->Wp * d->C);
+      CCX_REQUIRE(ctx, d->halo1 && d->halo2 && ccx_aligned16(d->halo1) && ccx_aligned16(d->halo2), "ccx_resnet_op: halo1 or halo2 is NULL or not 16-byte aligned (halo0_elems counts each of the three)");
+      break;
+    case CCX_RESNET_TSTP:
+      CCX_REQUIRE(ctx, d->W4 >= 2 && d->W4 <= (1 << 20), "ccx_resnet_op: W4 = %d out of range [2, 2^20] (two pooled frames are needed)", d->W4);
+      CCX_REQUIRE(ctx, d->n_masks >= 1 && d->n_masks <= 65535, "ccx_resnet_op: n_masks = %d out of range [1, 65535]", d->n_masks);
+      RN_BUF(act, n * 12 * (d->W4 + 2) * 256);
+      RN_BUF(pooled, (long)d->n_masks * 5120);
+      if (d->weights) {
+        CCX_REQUIRE(ctx, d->mask_chunk != nullptr, "ccx_resnet_op: weights are given without mask_chunk");
+        CCX_REQUIRE(ctx, d->n_w >= 1 && d->n_w <= (1 << 20), "ccx_resnet_op: n_w = %d out of range [1, 2^20]", d->n_w);
+        RN_BUF(weights, (long)d->n_masks * d->n_w);
+      }
+      if (d->mask_chunk) {
+        for (int j = 0; j < d->n_masks; j++)
+          CCX_REQUIRE(ctx, d->mask_chunk[j] >= 0 && d->mask_chunk[j] < n, "ccx_resnet_op: mask_chunk[%d] = %d out of range [0, n_chunks = %d)", j, d->mask_chunk[j], d->n_chunks);
+      } else {
+        CCX_REQUIRE(ctx, d->n_masks == n, "ccx_resnet_op: n_masks = %d without mask_chunk must equal n_chunks = %d", d->n_masks, d->n_chunks);
+      }
+      break;
+    default:
+      CCX_REQUIRE(ctx, d->n_masks >= 1 && d->n_masks <= 65535, "ccx_resnet_op: n_masks = %d out of range [1, 65535]", d->n_masks);
+      RN_BUF(pooled, (long)d->n_masks * 5120); RN_BUF(lin_w, (long)RN_EMB * 5120); RN_BUF(lin_b, RN_EMB); RN_BUF(emb, (long)d->n_masks * RN_EMB);
+  }
+
+  ccx_op_scratch sc;
+  int rc = CCX_OK;
+  switch (op) {
+    case CCX_RESNET_FBANK: {
+      FbankTables t;
+      CCX_TRY(fbank_tables(ctx, t));
+      float *win = nullptr, *mw = nullptr; float2* tw = nullptr; int *ms = nullptr, *ml = nullptr;
+      RN_HIP(sc.upload(&win, t.win.data(), t.win.size())); RN_HIP(sc.upload(&tw, t.tw.data(), t.tw.size()));
+      RN_HIP(sc.upload(&mw, t.mw.data(), t.mw.size()));
+      RN_HIP(sc.upload(&ms, t.ms.data(), t.ms.size())); RN_HIP(sc.upload(&ml, t.ml.data(), t.ml.size()));
+      const FbankDev tb{win, tw, mw, ms, ml};
+      rc = launch_fbank(ctx, (const float*)d->wav, (long)d->stride, d->n_samples, T, (int)n, tb, (float*)d->feats_t, (float*)d->fmean, st);
+      break;
+    }
+    case CCX_RESNET_CONV1:
+      rc = launch_conv1(ctx, (const float*)d->feats_t, (const float*)d->fmean, T, (int)n, (const float*)d->c1w, (const float*)d->c1b, (bf16_t*)d->out, st);
+      break;
+    case CCX_RESNET_CONV:
+      RN_HIP(sc.upload(&cv.W, packed.data(), packed.size()));
+      RN_HIP(sc.upload(&cv.b, d->shift_host, (size_t)cv.cout));
+      rc = run_conv(ctx, cv, epi, (const bf16_t*)d->in, di, (bf16_t*)d->out, dn, (const bf16_t*)d->resid, (int)n, st);
+      break;
+    case CCX_RESNET_HALO_ZERO:
+      rc = launch_halo_zero(ctx, (bf16_t*)d->halo0, (bf16_t*)d->halo1, (bf16_t*)d->halo2, d->c0, d->n, d->H, (long)d->Wp, d->C, st);
+      break;
+    case CCX_RESNET_TSTP: {
+      int* mc = nullptr;
+      if (d->mask_chunk) RN_HIP(sc.upload(&mc, d->mask_chunk, (size_t)d->n_masks));
+      rc = launch_tstp(ctx, (const bf16_t*)d->act, d->W4, mc, (const float*)d->weights, d->n_w, d->n_masks, (float*)d->pooled, st);
+      break;
+    }
+    default:
+      rc = launch_embed_linear(ctx, (const float*)d->pooled, (const float*)d->lin_w, (const float*)d->lin_b, d->n_masks, (float*)d->emb, st);
+  }
+  RN_HIP(hipStreamSynchronize(st));      // the scratch is freed on return
+  return rc;
 }
 
 }  // extern "C"

@@ -320,15 +320,16 @@ __global__ __launch_bounds__(256) void stats_pool_kernel(const bf16_t* __restric
   } else {
     const float* w = weights + w_off[crop];
     const int nw = w_len[crop];
+    const float scale = (float)nw / (float)n;          // F.interpolate(mode="nearest"), torch's fp32 index map
     float v1 = 1e-8f, v2 = 0.f, s = 0.f;
     for (int t = 0; t < n; t++) {
-      const float wt = w[(int)(((long)t * nw) / n)];   // F.interpolate(mode="nearest")
+      const float wt = w[ccx_nearest_src(t, scale, nw)];
       v1 += wt; v2 += wt * wt; s += wt * bf16_to_f32(p[(long)t * ld_in]);
     }
     mean = s / v1;
     float q = 0.f;
     for (int t = 0; t < n; t++) {
-      const float wt = w[(int)(((long)t * nw) / n)];
+      const float wt = w[ccx_nearest_src(t, scale, nw)];
       const float d = bf16_to_f32(p[(long)t * ld_in]) - mean;
       q += wt * d * d;
     }

@@ -710,6 +710,52 @@ int ccx_resnet_finalize(ccx_resnet* r);
 int ccx_resnet_embed(ccx_resnet* r, const float* wav_dev, int64_t stride, int n_samples, int n_chunks, const float* weights_dev,
                      int n_w, const int* mask_chunk, int n_masks, float* out_dev, void* stream);
 
+/* ---- the ResNet-34 kernels on their own (csrc/resnet.hip through the launch functions ccx_resnet_embed uses; for kernel parity
+ *      tests, the product path does not call this; no counterpart in the reference).  Device pointers come with the element count of
+ *      the buffer's own type; convolution weights and mask_chunk are HOST arrays.  Everything the kernels assume is checked on the host
+ *      before anything is launched; a violation returns CCX_ERR_ARG (1) with a message naming "ccx_resnet_op" and the field.
+ *      Synchronises the stream.
+ *      Padded layout: bf16 [chunk][H + 2][W + 2][C], a one-pixel halo around every image. */
+#define CCX_RESNET_FBANK 0      /* fbank_kernel + fbank_mean_kernel: wav -> feats_t f32 [chunk][80][T], fmean f32 [chunk][80] */
+#define CCX_RESNET_CONV1 1      /* conv1_kernel: feats_t, fmean -> out, padded [chunk][82][T + 2][32] (interior only) */
+#define CCX_RESNET_CONV 2       /* one folded convolution of the trunk, dispatched as the product does (direct kernel or GEMM) */
+#define CCX_RESNET_HALO_ZERO 3  /* halo_zero_kernel: halo cells of chunks [c0, c0 + n) of three padded buffers */
+#define CCX_RESNET_TSTP 4       /* tstp_kernel: act, padded [chunk][12][W4 + 2][256] -> pooled f32 [n_masks][5120] */
+#define CCX_RESNET_LINEAR 5     /* embed_linear_kernel: pooled -> emb f32 [n_masks][256] */
+#define CCX_RESNET_EPI_PLAIN 0     /* out = conv + shift */
+#define CCX_RESNET_EPI_RELU 1      /* out = relu(conv + shift) */
+#define CCX_RESNET_EPI_ADD_RELU 2  /* out = relu(conv + shift + resid) */
+
+typedef struct ccx_resnet_desc {
+  int n_chunks;                 /* ops 0, 1, 2, 4 */
+  /* op 0: wav f32 [n_chunks][stride], the first n_samples (>= 400) of every row are read; T = 1 + (n_samples - 400) / 160.
+   * ops 0, 1: feats_t f32 [n_chunks][80][T], fmean f32 [n_chunks][80] (op 0 writes them, op 1 reads them) */
+  const void* wav; int64_t wav_elems; int64_t stride; int n_samples;
+  void* feats_t; int64_t feats_t_elems; void* fmean; int64_t fmean_elems;
+  /* op 1: T frames; c1w f32 [32][9] and c1b f32 [32] (device, BatchNorm folded); writes out */
+  int T; const void* c1w; int64_t c1w_elems; const void* c1b; int64_t c1b_elems;
+  /* op 2: (cin, cout, k, conv_stride) one of the network's: k 3 stride 1 with cin == cout in {32, 64, 128, 256}, or k 3 / k 1
+   * stride 2 with (cin, cout) in {(32, 64), (64, 128), (128, 256)}.  H (even) x W (>= 2) is the INPUT image; the output image is
+   * H x W (stride 1) or H / 2 x ((W - 1) / 2 + 1) (stride 2).  epi: CCX_RESNET_EPI_*.  HOST w_host f32 [cout][cin][k][k] (torch
+   * layout), HOST scale_host / shift_host f32 [cout] (the folded BatchNorm).  in / out / resid in the padded layouts of their
+   * images; resid (output layout) with ADD_RELU only.  in_elems must cover the read slack of the strided view behind the layout:
+   * two padded rows and one K tile (align(k cin, 64) elements).  Only interior cells of out are written. */
+  int cin, cout, k, conv_stride, H, W, epi;
+  const float* w_host; const float* scale_host; const float* shift_host;
+  const void* in; int64_t in_elems; void* out; int64_t out_elems; const void* resid; int64_t resid_elems;
+  /* op 3: three buffers [>= c0 + n][H + 2][Wp][C] of halo0_elems elements each, C in {32, 64, 128, 256} (H as above, any >= 1) */
+  void* halo0; void* halo1; void* halo2; int64_t halo0_elems; int c0, n, Wp, C;
+  /* op 4: act bf16; weights f32 [n_masks][n_w] (device, may be NULL: unbiased std); HOST mask_chunk [n_masks] (the chunk a mask
+   * pools over; required with weights; without it n_masks must equal n_chunks).  ops 4, 5: pooled f32 [n_masks][5120] */
+  const void* act; int64_t act_elems; int W4;
+  const void* weights; int64_t weights_elems; int n_w; const int* mask_chunk; int n_masks;
+  void* pooled; int64_t pooled_elems;
+  /* op 5: lin_w f32 [256][5120], lin_b f32 [256] (device) -> emb f32 [n_masks][256] */
+  const void* lin_w; int64_t lin_w_elems; const void* lin_b; int64_t lin_b_elems; void* emb; int64_t emb_elems;
+} ccx_resnet_desc;
+
+int ccx_resnet_op(ccx_ctx* ctx, int op, const ccx_resnet_desc* desc, void* stream);
+
 /* ---- spectral-gate denoiser (replaces nr.reduce_noise(y=, sr=, stationary=True, prop_decrease=),
  *      reference back/api.py:349 and 832-833; the package's other mode and options: *_ex below) ------- */
 typedef struct ccx_specgate ccx_specgate;

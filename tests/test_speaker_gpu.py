@@ -74,6 +74,45 @@ def test_xvector_weighted_pooling(ccx_ctx):
         m.close()
 
 
+def _xvector_frames(n):
+    """Pooling frames of an n-sample crop: SincNet (k 251 stride 10, then three times max-pool 3 with k 5 convolutions between), then
+    the TDNN contexts k 5, k 3 dilation 2, k 3 dilation 3 (4 + 4 + 6 frames)."""
+    f = ((n - 251) // 10 + 1) // 3
+    f = ((f - 4) // 3 - 4) // 3
+    return f - 14
+
+
+def test_xvector_weighted_pooling_where_the_index_maps_differ(ccx_ctx):
+    """A crop of 8300 samples pools over 14 frames; with 62 weights, F.interpolate(mode="nearest") reads weight 30 for frame 7
+    (floor(7 * fp32(62 / 14)) in fp32) where the exact rational 7 * 62 / 14 gives 31.  The weights are live only around that place,
+    with the whole difference between weights 30 and 31, so a kernel on the exact map pools over a different frame set."""
+    from clearconverse_amd.speaker import XVectorEmbedder
+    from tests import resnet_reference as R
+    TOL = 2e-2                                                   # the tolerance of test_xvector_weighted_pooling
+    n, nw = 8300, 62
+    assert _xvector_frames(n) == 14 and _xvector_frames(160000) == 575
+    torch_map, exact_map = R.nearest_index(14, nw), torch.from_numpy(R.nearest_index_exact(14, nw))
+    assert torch_map[7] == 30 and exact_map[7] == 31 and int((torch_map != exact_map).sum()) == 1
+    w = torch.zeros(nw)
+    w[26], w[30], w[31], w[35] = 0.3, 1.0, 0.0, 0.2              # frames 6, 7, 8 under torch's map; frame 7 drops out under the exact one
+    sd = synthetic_xvector_state_dict(seed=5)
+    crop = _crops([n])[0]
+    ref = P.xvector_forward(sd, crop[None], weights=w)
+    # 14 weights map one to one onto 14 frames: this is what each map makes of w (and it pins the frame count of the oracle)
+    assert _rel(P.xvector_forward(sd, crop[None], weights=w[torch_map]), ref) < 1e-6
+    moved = _rel(P.xvector_forward(sd, crop[None], weights=w[exact_map]), ref)
+    print(f"x-vector (14 frames, 62 weights): the exact-rational map moves the oracle's embedding by rel-L2 {moved:.3f}")
+    assert moved > 10 * TOL, moved
+    m = XVectorEmbedder(sd, max_crops=4, max_samples=16000 * 25, ctx=ccx_ctx)
+    try:
+        got = m.embed_batch([crop], weights=[w]).cpu()[0]
+        e = _rel(got, ref)
+        print(f"x-vector (14 frames, 62 weights): embedding rel-L2 {e:.3e}")
+        within("x-vector: embedding rel-L2 (weighted, 14 frames / 62 weights)", e, TOL)
+    finally:
+        m.close()
+
+
 def test_xvector_rejects_short_crop(ccx_ctx):
     from clearconverse_amd._lib import CcxError
     from clearconverse_amd.speaker import XVectorEmbedder
