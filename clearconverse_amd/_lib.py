@@ -116,6 +116,19 @@ class DecBeamDesc(C.Structure):
         ("opts", C.POINTER(DecodeOptions))]
 
 
+class DecodeHistoryOptions(C.Structure):
+    """ccx_decode_history_options (include/ccx.h): repetition_penalty and no_repeat_ngram_size; the defaults are {1.0, 0}."""
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int)]
+
+
+class DecHistoryDesc(C.Structure):
+    """ccx_dec_history_desc (include/ccx.h): one launch of the history kernel on its own."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("logits_elems", C.c_int64), ("ld", C.c_int64), ("n_vocab", C.c_int), ("rows", C.c_int),
+        ("state", C.POINTER(DecSeqState)), ("hist", C.POINTER(C.c_int)), ("sample_len", C.c_int), ("text_end", C.c_int),
+        ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int)]
+
+
 class BeamTrace(C.Structure):
     """ccx_beam_trace (include/ccx.h): host buffers a traced ccx_whisper_decode_beam fills."""
     _fields_ = [("n_steps", C.c_int), ("cand_id", C.POINTER(C.c_int32)), ("cand_lp", C.POINTER(C.c_float)),
@@ -267,6 +280,10 @@ PROTOTYPES = {
     "ccx_decode_options_default": (None, [C.POINTER(DecodeOptions)]),
     "ccx_whisper_set_decode_options": (_i, [_vp, C.POINTER(DecodeOptions)]),
     "ccx_whisper_graph_count": (_i, [_vp, _i]),
+    "ccx_decode_history_options_default": (None, [C.POINTER(DecodeHistoryOptions)]),
+    "ccx_whisper_set_history_options": (_i, [_vp, C.POINTER(DecodeHistoryOptions)]),
+    "ccx_whisper_history_graph_count": (_i, [_vp]),
+    "ccx_dec_history_step": (_i, [_vp, C.POINTER(DecHistoryDesc), _vp]),
     "ccx_whisper_set_mel": (_i, [_vp, _vp, _i, _vp]),
     "ccx_whisper_encode": (_i, [_vp, _i, _vp, _vp]),
     "ccx_whisper_decoder_logits": (_i, [_vp, _i32p, _i, _i, _vp, _vp]),

@@ -125,6 +125,19 @@ struct DecBeamParams {
   int* tr_cand_id; float* tr_cand_lp; int* tr_tok; int* tr_parent; float* tr_score; int tr_rows;
 };
 int ccx_launch_dec_beam(ccx_ctx* ctx, const DecBeamParams& p, int n_windows, hipStream_t stream);
+
+// The rules over a row's own sampled history (dec_history.hip: repetition_penalty, no_repeat_ngram_size), applied to the fp32 logit
+// rows in place BEFORE the select / beam kernels: one block per row; rows that are done or in the prompt phase are not touched.
+// gen [rows][sample_len] holds state[row].n_gen sampled ids; ids >= text_end (rules.eot) are never edited.
+constexpr int kDecHistoryMax = 2048;   // ids of one row's history the block stages in LDS (sample_len <= it)
+struct DecHistoryParams {
+  float* logits; long ld;              // [rows][ld], edited in place
+  const DecSeqState* state;            // [rows]
+  const int* gen; int sample_len;
+  int text_end;
+  float penalty; int ngram;            // 1.0 / 0: off
+};
+int ccx_launch_dec_history(ccx_ctx* ctx, const DecHistoryParams& p, int rows, hipStream_t stream);
 int ccx_launch_dec_embed(ccx_ctx* ctx, const float* tok_emb, const float* pos_emb, const int* cur_tok, const int* pos,
                          float* x, int B, int D, hipStream_t stream);
 // Softmax of logit rows over the ids [lo, hi) only (dec_probs.hip; everything else counts as -inf): argmax[row] (lowest id on equal

@@ -71,14 +71,18 @@ struct StepPlan {
   int no_ts;                      // without_timestamps: the select / beam kernels without ApplyTimestampRules
   int sup_blank;                  // suppress_blank as set (read by the no_ts kernels only)
   int max_init_ts;                // the max_initial_timestamp index the ruled kernels apply (< 0: rule off)
+  // the rules over a row's own sampled history (ccx_whisper_set_history_options; both 0 in a default decode): dec_history_kernel
+  // runs in front of the select / beam kernels when either is set
+  int hist_ngram;                 // no_repeat_ngram_size
+  int hist_pen_bits;              // repetition_penalty's float bits (0 when it is 1.0)
   auto tie() const {
     return std::tie(b0, B, sample_len, max_prompt, select, sampling, cross_stream, cross_lds_pad, xs_active, lnfree, xs_fuse_q, fuse_cross_q,
                     xs_full_lines, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows, opt_mask, no_ts, sup_blank,
-                    max_init_ts);
+                    max_init_ts, hist_ngram, hist_pen_bits);
   }
   bool operator<(const StepPlan& o) const { return tie() < o.tie(); }
 };
-static_assert(sizeof(StepPlan) == 24 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 24,
+static_assert(sizeof(StepPlan) == 26 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 26,
               "StepPlan: ints only, and every one of them in tie()");
 
 }  // namespace
@@ -123,6 +127,8 @@ struct ccx_whisper {
   bool opts_on = false;
   unsigned char* opt_mask = nullptr;
   std::vector<unsigned char> opt_mask_host; // what opt_mask holds: a call that changes nothing keeps the option graphs
+  // the call's history rules (ccx_whisper_set_history_options); {1.0, 0}: off, the plans and launches of a default decode
+  ccx_decode_history_options hist{1.0f, 0};
 
   // workspaces (encoder)
   float* lm_raw = nullptr; unsigned int* lm_max = nullptr; int *lm_n = nullptr, *lm_seek = nullptr, *lm_seg = nullptr;
@@ -402,6 +408,7 @@ int ccx_whisper_set_rules(ccx_whisper* w, const ccx_decode_rules* r) {
   w->rules_set = true;
   w->opts = ccx_decode_options{0, 1, -2, 0, nullptr};   // the options name ids of the rules they were set under
   w->opts_on = false;
+  w->hist = ccx_decode_history_options{1.0f, 0};
   drop_graphs(w);      // captured step graphs bake the rule ids into the select kernel's parameters
   return CCX_OK;
 }
@@ -442,6 +449,26 @@ int ccx_whisper_set_decode_options(ccx_whisper* w, const ccx_decode_options* opt
   w->opts.suppress = nullptr; w->opts.n_suppress = 0;   // the list lives in the mask
   w->opts_on = on;
   return CCX_OK;
+}
+
+int ccx_whisper_set_history_options(ccx_whisper* w, const ccx_decode_history_options* opts) {
+  if (!w) return CCX_ERR_ARG;
+  ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, w->rules_set, "ccx_whisper_set_history_options: the rules are not set (ccx_whisper_set_rules)");
+  ccx_decode_history_options o{1.0f, 0};
+  if (opts) o = *opts;
+  CCX_REQUIRE(ctx, o.repetition_penalty > 0.f && o.repetition_penalty <= 3.4028234e38f,
+              "ccx_whisper_set_history_options: opts.repetition_penalty = %g must be finite and > 0", (double)o.repetition_penalty);
+  CCX_REQUIRE(ctx, o.no_repeat_ngram_size >= 0, "ccx_whisper_set_history_options: opts.no_repeat_ngram_size = %d is negative", o.no_repeat_ngram_size);
+  w->hist = o;         // both values are in the step plan: nothing captured depends on the setting itself
+  return CCX_OK;
+}
+
+int ccx_whisper_history_graph_count(ccx_whisper* w) {
+  if (!w) return -1;
+  int n = 0;
+  for (auto& g : w->graphs) n += (g.first.hist_ngram || g.first.hist_pen_bits) ? 1 : 0;
+  return n;
 }
 
 int ccx_whisper_trace_lanes(ccx_whisper* w, const char* path, int level) {
@@ -984,6 +1011,16 @@ int dec_head(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
     memset(&gp, 0, sizeof(gp));
     gp.A = w->dxn + ro * D; gp.lda = D; gp.W = w->tok_emb_rm; gp.ldw = D; gp.M = B; gp.N = d.n_vocab; gp.K = D; gp.out = io.logits; gp.ldo = io.ld;
     CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, gp, io.stream));
+  }
+  if (p.select && (p.hist_ngram || p.hist_pen_bits)) {
+    // the history rules edit the logit rows in place before any filter reads them (beam rows: the history that follows the hypothesis)
+    DecHistoryParams hp;
+    memset(&hp, 0, sizeof(hp));
+    hp.logits = io.logits; hp.ld = io.ld; hp.state = w->state + b0; hp.gen = w->gen + ro * p.sample_len; hp.sample_len = p.sample_len;
+    hp.text_end = w->rules.eot; hp.ngram = p.hist_ngram;
+    hp.penalty = 1.f;
+    if (p.hist_pen_bits) memcpy(&hp.penalty, &p.hist_pen_bits, 4);
+    CCX_TRY(ccx_launch_dec_history(ctx, hp, B, io.stream));
   }
   if (p.select && p.beam_size > 0) {
     // beam search: the row's top beam + 1 proposals, then one block per window ranks, walks and rewrites its rows in place
@@ -1980,6 +2017,9 @@ int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
     if (w->opts.max_initial_timestamp_index != -2) base.max_init_ts = w->opts.max_initial_timestamp_index;
     if (base.no_ts) base.max_init_ts = -1;         // not read without the rules: one plan whatever the caller left there
   }
+  // the history rules: {1.0, 0}, set or not, is the default plan
+  base.hist_ngram = w->hist.no_repeat_ngram_size;
+  if (w->hist.repetition_penalty != 1.0f) memcpy(&base.hist_pen_bits, &w->hist.repetition_penalty, 4);
   read_chain_switches(base);
   CCX_TRY(select_cross_path(w, base, stream, win ? n_windows : -1));
   if (win) CCX_TRY(upload_row_map(w, win, sids, B, stream));

@@ -341,14 +341,23 @@ class WhisperModel:
     temperature_fallback = False      # opt-in (the constructor's keyword)
     beam_search = False               # opt-in too
     decoding_options = False          # and so are upstream's remaining per-call decoding options
+    repetition_control = False        # and repetition_penalty / no_repeat_ngram_size
 
     def __init__(self, dims: WhisperDims, state_dict: Dict[str, torch.Tensor], max_batch: int = 8,
                  device: int = 0, rules: Optional[DecodeRules] = None, tokenizer=None,
                  ctx: Optional[_lib.Context] = None, max_audio_seconds: float = 30.0,
                  share_encoder_scratch_with: Optional["WhisperModel"] = None, word_alignment: bool = False,
                  alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False,
-                 temperature_fallback: bool = False, beam_search: bool = False, decoding_options: bool = False):
-        """decoding_options (default False: `without_timestamps`, `prefix`, `suppress_blank`, `suppress_tokens`, `max_initial_timestamp`,
+                 temperature_fallback: bool = False, beam_search: bool = False, decoding_options: bool = False,
+                 repetition_control: bool = False):
+        """repetition_control (default False: `repetition_penalty` and `no_repeat_ngram_size` are accepted and ignored): with it,
+        `transcribe` / `transcribe_batch` and `decode`, `decode_rows`, `decode_beam` honour them (the names CTranslate2 /
+        faster-whisper and Hugging Face use; the rule is this project's, include/ccx.h ccx_decode_history_options; parity unpinned):
+        the logit of every text id a window has sampled so far is divided (> 0) or multiplied (<= 0) by repetition_penalty, and an id
+        that would complete an n-gram the window already holds is banned -- over the tokens THIS decode sampled only (no prompt, SOT
+        sequence or prefix), ids >= eot exempt.  One kernel more per step (csrc/dec_history.hip) and only on calls that set a value:
+        with the defaults 1.0 and 0 a call is what it is without the opt-in.
+        decoding_options (default False: `without_timestamps`, `prefix`, `suppress_blank`, `suppress_tokens`, `max_initial_timestamp`,
         `sample_len`, `clip_timestamps` and `carry_initial_prompt` are accepted and ignored, as before): with it, `transcribe` /
         `transcribe_batch` honour them [UPSTREAM-RECALL: decoding.py::DecodingOptions, transcribe.py; parity unpinned] -- see
         `transcribe_batch`; `decode`, `decode_rows` and `decode_beam` take the ones a single decode reads.
@@ -395,6 +404,7 @@ class WhisperModel:
         self.temperature_fallback = bool(temperature_fallback)
         self.beam_search = bool(beam_search)
         self.decoding_options = bool(decoding_options)
+        self.repetition_control = bool(repetition_control)
         if alignment_heads is None:
             alignment_heads = [(l, h) for l in range(dims.n_text_layer // 2, dims.n_text_layer) for h in range(dims.n_text_head)]
         self.alignment_heads = [(int(l), int(h)) for l, h in alignment_heads]
@@ -473,6 +483,47 @@ class WhisperModel:
             return fn()
         finally:
             self.reset_decode_options()
+
+    @staticmethod
+    def check_history_options(repetition_penalty: float, no_repeat_ngram_size: int):
+        """the ranges ccx_whisper_set_history_options checks -> (float, int), or ValueError naming the argument"""
+        try:
+            p = float(repetition_penalty)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"repetition_penalty = {repetition_penalty!r} must be a finite number > 0") from e
+        if not (1.5e-45 <= p <= 3.4028234e38):       # what a C float holds as a finite number > 0
+            raise ValueError(f"repetition_penalty = {repetition_penalty!r} must be a finite number > 0")
+        n = no_repeat_ngram_size
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n > 2 ** 31 - 1:
+            raise ValueError(f"no_repeat_ngram_size = {no_repeat_ngram_size!r} must be an integer >= 0")
+        return p, int(n)
+
+    def set_history_options(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
+        """ccx_whisper_set_history_options (sticky, like the rules; `set_rules` resets it); (1.0, 0) is the default decode"""
+        p, n = self.check_history_options(repetition_penalty, no_repeat_ngram_size)
+        o = _lib.DecodeHistoryOptions(p, n)
+        self.ctx.check(self.lib.ccx_whisper_set_history_options(self.handle, C.byref(o)), "ccx_whisper_set_history_options")
+
+    def reset_history_options(self):
+        self.ctx.check(self.lib.ccx_whisper_set_history_options(self.handle, None), "ccx_whisper_set_history_options")
+
+    def history_graph_count(self) -> int:
+        """captured step graphs of history plans (ccx_whisper_history_graph_count)"""
+        return int(self.lib.ccx_whisper_history_graph_count(self.handle))
+
+    def _with_history_options(self, repetition_penalty, no_repeat_ngram_size, fn):
+        """`fn()` under the call's repetition_penalty / no_repeat_ngram_size; the defaults are back afterwards.  Without the opt-in
+        the two are ignored; with the default values nothing is set."""
+        if not self.repetition_control:
+            return fn()
+        p, n = self.check_history_options(repetition_penalty, no_repeat_ngram_size)
+        if p == 1.0 and n == 0:
+            return fn()
+        self.set_history_options(p, n)
+        try:
+            return fn()
+        finally:
+            self.reset_history_options()
 
     def set_prefix_len(self, n_prefix: int):
         """prompt tokens behind the SOT sequence (a decode with a prefix): ccx_whisper_set_prefix_len"""
@@ -562,7 +613,7 @@ class WhisperModel:
         return self.decode(prompts, sample_len, temperature=0.0)
 
     def decode(self, prompts: Sequence[Sequence[int]], sample_len: Optional[int] = None, temperature: float = 0.0,
-               seed: int = 0, **decoding) -> List[dict]:
+               seed: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, **decoding) -> List[dict]:
         """DecodingTask.run over the currently encoded windows; prompts[b] are the full initial tokens
         (sot_prev + prompt + sot).  temperature 0: argmax.  temperature > 0: one Categorical(logits / T) sample per
         step (decoding.py::GreedyDecoder.update), drawn on the device from Philox noise keyed by
@@ -571,7 +622,11 @@ class WhisperModel:
         default always was), fewer for a longer one, which the fixed 224 made the library refuse.
         **decoding (decoding_options instances; ignored otherwise): without_timestamps, suppress_blank, suppress_tokens,
         max_initial_timestamp for this call (`_with_call_options`); the prompts, the SOT tail, the prefix length and sample_len stay
-        the caller's."""
+        the caller's.  repetition_penalty / no_repeat_ngram_size (repetition_control instances; ignored otherwise): this call's
+        history rules (`_with_history_options`)."""
+        if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
+            return self._with_history_options(repetition_penalty, no_repeat_ngram_size,
+                                              lambda: self.decode(prompts, sample_len, temperature, seed, **decoding))
         if decoding:
             return self._with_call_options(decoding, lambda: self.decode(prompts, sample_len, temperature, seed))
         if not (temperature >= 0.0):
@@ -601,11 +656,15 @@ class WhisperModel:
 
     def decode_rows(self, prompts: Sequence[Sequence[int]], windows: Sequence[int], stream_ids: Optional[Sequence[int]] = None,
                     sample_len: Optional[int] = None, temperature: float = 0.0, seed: int = 0, n_windows: Optional[int] = None,
-                    **decoding) -> List[dict]:
+                    repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, **decoding) -> List[dict]:
         """`decode` for len(prompts) <= max_batch rows over the currently encoded windows (ccx_whisper_decode_rows): row r decodes
         window windows[r] -- entries may repeat (best_of), need not be monotone, and windows may go unused (a fallback round decodes
         only the failing ones).  stream_ids[r]: the row's noise stream at temperature > 0 (None: r), so that its draws do not depend on
-        the rows it shares the call with.  n_windows: how many windows are encoded (default: max(windows) + 1).  **decoding: as `decode`."""
+        the rows it shares the call with.  n_windows: how many windows are encoded (default: max(windows) + 1).  repetition_penalty,
+        no_repeat_ngram_size, **decoding: as `decode`."""
+        if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
+            return self._with_history_options(repetition_penalty, no_repeat_ngram_size, lambda: self.decode_rows(
+                prompts, windows, stream_ids, sample_len, temperature, seed, n_windows, **decoding))
         if decoding:
             return self._with_call_options(decoding, lambda: self.decode_rows(prompts, windows, stream_ids, sample_len, temperature, seed,
                                                                              n_windows))
@@ -641,7 +700,7 @@ class WhisperModel:
 
     def decode_beam(self, prompts: Sequence[Sequence[int]], beam_size: int, patience: Optional[float] = None,
                     sample_len: Optional[int] = None, windows: Optional[Sequence[int]] = None, n_windows: Optional[int] = None,
-                    trace: bool = False, **decoding):
+                    trace: bool = False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, **decoding):
         """Beam search at temperature 0 over the currently encoded windows (ccx_whisper_decode_beam) [UPSTREAM-RECALL:
         decoding.py::BeamSearchDecoder]: prompts[g] is decoded on window windows[g] (None: window g) by beam_size rows that share the
         window's encoder output; len(prompts) * beam_size <= max_batch.  patience (None: 1.0): a window is complete once
@@ -650,7 +709,10 @@ class WhisperModel:
         sum_logprob, avg_logprob, no_speech_prob (the window's), cross_path.  The ranker (`fallback.rank_candidates`) picks among them.
         trace=True (a test aid; the steps then run eagerly): -> (results, dict of numpy arrays cand_id / cand_lp [steps, rows,
         beam_size + 1], tok / parent / score [steps, rows]; rows = prompt-major; -1 / NaN where a window no longer stepped).
-        **decoding: as `decode`."""
+        repetition_penalty, no_repeat_ngram_size, **decoding: as `decode`; every row reads the history that follows its hypothesis."""
+        if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
+            return self._with_history_options(repetition_penalty, no_repeat_ngram_size, lambda: self.decode_beam(
+                prompts, beam_size, patience, sample_len, windows, n_windows, trace, **decoding))
         if decoding:
             return self._with_call_options(decoding, lambda: self.decode_beam(prompts, beam_size, patience, sample_len, windows, n_windows,
                                                                              trace))
@@ -825,7 +887,8 @@ class WhisperModel:
                    best_of: Optional[int] = None, beam_size: Optional[int] = None, patience: Optional[float] = None,
                    length_penalty: Optional[float] = None, without_timestamps: bool = False, prefix=None,
                    suppress_blank: bool = True, suppress_tokens="-1", max_initial_timestamp: Optional[float] = 1.0,
-                   sample_len: Optional[int] = None, clip_timestamps="0", carry_initial_prompt: bool = False, **_ignored):
+                   sample_len: Optional[int] = None, clip_timestamps="0", carry_initial_prompt: bool = False,
+                   repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, **_ignored):
         """One clip, same signature as whisper.transcribe as the reference uses it.  temperature 0 is the
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
@@ -846,7 +909,9 @@ class WhisperModel:
         otherwise they are accepted and ignored.
         On an instance built with `decoding_options=True`: without_timestamps, prefix, suppress_blank, suppress_tokens,
         max_initial_timestamp, sample_len, clip_timestamps and carry_initial_prompt are honoured (see `transcribe_batch`); otherwise
-        they are accepted and ignored."""
+        they are accepted and ignored.
+        On an instance built with `repetition_control=True`: repetition_penalty and no_repeat_ngram_size are honoured (see
+        `transcribe_batch`); otherwise they are accepted and ignored."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
                                      compression_ratio_threshold=compression_ratio_threshold, best_of=best_of,
                                      temperature=temperature, no_speech_threshold=no_speech_threshold,
@@ -856,7 +921,8 @@ class WhisperModel:
                                      patience=patience, length_penalty=length_penalty, without_timestamps=without_timestamps,
                                      prefixes=[prefix], suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
                                      max_initial_timestamp=max_initial_timestamp, sample_len=sample_len,
-                                     clip_timestamps=clip_timestamps, carry_initial_prompt=carry_initial_prompt)[0]
+                                     clip_timestamps=clip_timestamps, carry_initial_prompt=carry_initial_prompt,
+                                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)[0]
 
     def transcribe_batch(self, audios: Sequence, initial_prompts: Optional[Sequence[Optional[str]]] = None,
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
@@ -868,7 +934,8 @@ class WhisperModel:
                          length_penalty: Optional[float] = None, without_timestamps: bool = False,
                          prefixes: Optional[Sequence] = None, suppress_blank: bool = True, suppress_tokens="-1",
                          max_initial_timestamp: Optional[float] = 1.0, sample_len: Optional[int] = None, clip_timestamps="0",
-                         carry_initial_prompt: bool = False) -> List[dict]:
+                         carry_initial_prompt: bool = False, repetition_penalty: float = 1.0,
+                         no_repeat_ngram_size: int = 0) -> List[dict]:
         """Independent clips decoded together (each window of each clip is one sequence of a batch).
         languages[i] (multilingual models): the clip's language code or name; None: detected on the clip's first window, after its
         group's `encode` and before its `decode` [UPSTREAM-RECALL: transcribe.py, `if decode_options.get("language") is None`].
@@ -899,7 +966,16 @@ class WhisperModel:
         the clip's end), a window ends where its pair ends (`log_mel(max_frames=)`); carry_initial_prompt -- the initial prompt leads
         every window's prompt.  One ccx_whisper_set_decode_options per call serves every round of a fallback walk or beam search;
         the defaults are back when the call returns.  without_timestamps with hallucination_silence_threshold raises.  Without the
-        opt-in all of them are ignored."""
+        opt-in all of them are ignored.
+        repetition_control instances: repetition_penalty (finite, > 0; 1.0 = off) and no_repeat_ngram_size (>= 0; 0 = off) hold for
+        every window of the call -- every round of a fallback walk, every best_of row and every beam row gets them (one
+        ccx_whisper_set_history_options per call, the defaults back when it returns); a value outside its range raises ValueError.
+        A window's history is what that window's decode sampled: nothing carries over from the prompt or from earlier windows.
+        Without the opt-in both are ignored."""
+        hist_on = False
+        if self.repetition_control:
+            hist_p, hist_n = self.check_history_options(repetition_penalty, no_repeat_ngram_size)
+            hist_on = hist_p != 1.0 or hist_n != 0
         opt, prefix_toks, clip_spec = None, None, None
         if self.decoding_options:
             try:
@@ -994,6 +1070,8 @@ class WhisperModel:
         n_prefix = len(prefix_toks[0]) if opt is not None and n > 0 else 0
         if n_prefix:
             self.set_prefix_len(n_prefix)
+        if hist_on:
+            self.set_history_options(hist_p, hist_n)
         try:
             while True:
                 active = [i for i in range(n) if state[i].active()]
@@ -1043,6 +1121,8 @@ class WhisperModel:
                     for i, r in zip(grp, results):
                         state[i].advance(r, temperature)
         finally:
+            if hist_on:
+                self.reset_history_options()
             if dev_opts:
                 self.reset_decode_options()
             if opt is not None and self.sot_tail != tail0:

@@ -208,6 +208,36 @@ int ccx_whisper_set_decode_options(ccx_whisper* w, const ccx_decode_options* opt
  * default decode after an option decode must find its graph where it left it. */
 int ccx_whisper_graph_count(ccx_whisper* w, int options_only);
 
+/* The two per-call rules over a row's own sampled history: repetition_penalty and no_repeat_ngram_size, as CTranslate2 /
+ * faster-whisper and Hugging Face name them (the rule is ours, in the form of HF's RepetitionPenaltyLogitsProcessor and
+ * NoRepeatNGramLogitsProcessor; parity unpinned; restated in tests/history_rules_reference.py).  ccx_decode_history_options_default
+ * fills {1.0f, 0}: both off.  For one row in the sampling phase, H = the m tokens THIS decode has sampled so far (not the prompt, the
+ * SOT sequence or a prefix) and E = rules.eot; ids >= E -- eot, the specials, the timestamps -- are never edited, so the timestamp
+ * rules and closed pairs <|t|><|t|> keep working:
+ *   1. repetition_penalty p (finite, > 0; 1.0 = off): every distinct v in H with v < E: x = logits[v]; logits[v] = x > 0 ? x / p : x * p
+ *      in fp32, once per id however often it occurs.
+ *   2. no_repeat_ngram_size n (>= 0; 0 = off), only when m >= n: for every i in [0, m - n] with H[i : i+n-1] == H[m-n+1 : m] and
+ *      H[i+n-1] < E: logits[H[i+n-1]] = -inf.  n = 1 bans every text id sampled so far; the matched context may hold ids >= E.
+ *   1 comes before 2; both come BEFORE SuppressBlank, SuppressTokens, ApplyTimestampRules and the sampler (csrc/dec_history.hip:
+ *   dec_history_kernel, one block per row, between the logits GEMM and the select / beam top-k kernel), so sum_logprob is taken from
+ *   the edited logits, as HF does; no_speech_prob is untouched (it is read where H is empty).  Rows that are done or still in the
+ *   prompt phase are not touched.  DEVIATION from HF, stated: HF penalises and bans over prompt + generated ids and exempts nothing.
+ * ccx_whisper_set_history_options is sticky like ccx_whisper_set_decode_options (NULL: back to the defaults), needs the rules, and
+ * is checked like it: CCX_ERR_ARG (1) naming "ccx_whisper_set_history_options" and the field for a repetition_penalty that is not
+ * finite or <= 0 and a negative no_repeat_ngram_size (one above sample_len is legal and never fires).  ccx_whisper_set_rules resets
+ * it.  Both values are part of the step plan: with {1.0, 0}, set or not, a decode takes the plan, the launches and the graphs it
+ * always took; the graphs of history plans live beside those of default and option plans.  ccx_whisper_decode, _decode_greedy,
+ * _decode_rows and _decode_beam (whose rows read the history that follows their hypothesis) honour the setting;
+ * ccx_whisper_decoder_logits, _align and _align_probs do not: word probabilities stay those of the raw model. */
+typedef struct ccx_decode_history_options {
+  float repetition_penalty;
+  int no_repeat_ngram_size;
+} ccx_decode_history_options;
+void ccx_decode_history_options_default(ccx_decode_history_options* opts);
+int ccx_whisper_set_history_options(ccx_whisper* w, const ccx_decode_history_options* opts);
+/* Captured step graphs of history plans the instance holds (a test aid, like ccx_whisper_graph_count); -1 for a NULL handle. */
+int ccx_whisper_history_graph_count(ccx_whisper* w);
+
 /* Log-mel of B clips (whisper.audio.log_mel_spectrogram + pad_or_trim to 3000 frames).
  * audio_dev: [B, stride] f32; n_samples / seek_frames: host int arrays (seek may be NULL = 0).
  * Fills the model's conv-stem input; if mel_out_dev != NULL also writes [B, n_mels, 3000] f32. */
@@ -394,6 +424,23 @@ typedef struct ccx_dec_beam_desc {
   const ccx_decode_options* opts;                             /* NULL: the rules alone (appended) */
 } ccx_dec_beam_desc;
 int ccx_dec_beam_step(ccx_ctx* ctx, const ccx_dec_beam_desc* desc, void* stream);
+
+/* The history rules on their own (csrc/dec_history.hip: dec_history_kernel, one block per row; the rule: ccx_decode_history_options
+ * above): edits the device logit rows in place for the rows in the sampling phase (done == 0 and pos >= prompt_len - 1) from their
+ * histories hist[row][0 : n_gen].  Checked on the host before the launch, CCX_ERR_ARG (1) naming "ccx_dec_history_step" and the
+ * field: 1 <= rows <= 65536, 1 <= n_vocab <= 53248, ld >= n_vocab, logits 4-byte aligned with logits_elems >= (rows - 1) * ld +
+ * n_vocab, 1 <= sample_len <= 2048, 0 <= text_end <= n_vocab, repetition_penalty finite and > 0, no_repeat_ngram_size >= 0, every
+ * n_gen in [0, sample_len] and done in {0, 1}, history ids of live rows in [0, n_vocab).  Owns and frees its scratch; synchronises
+ * the stream. */
+typedef struct ccx_dec_history_desc {
+  void* logits; int64_t logits_elems;         /* device f32 [rows][ld], in and out */
+  int64_t ld; int n_vocab; int rows;
+  const ccx_dec_seq_state* state;             /* HOST [rows] */
+  const int* hist; int sample_len;            /* HOST [rows][sample_len] */
+  int text_end;                               /* rules.eot: ids >= it are never edited */
+  float repetition_penalty; int no_repeat_ngram_size;
+} ccx_dec_history_desc;
+int ccx_dec_history_step(ccx_ctx* ctx, const ccx_dec_history_desc* desc, void* stream);
 
 /* Softmax of logit rows over an id range (csrc/dec_probs.hip: dec_token_probs_kernel, one block per row).  Over the ids [lo, hi) only --
  * everything else, the columns [n_vocab, ld) included, counts as -inf and is never looked at: argmax[row] (lowest id on equal values,
