@@ -217,6 +217,25 @@ RESNET_FBANK, RESNET_CONV1, RESNET_CONV, RESNET_HALO_ZERO, RESNET_TSTP, RESNET_L
 RESNET_EPI_PLAIN, RESNET_EPI_RELU, RESNET_EPI_ADD_RELU = range(3)
 
 
+class SpeakerDesc(C.Structure):
+    """ccx_speaker_desc (include/ccx.h): one SincNet / x-vector / PyanNet kernel on its own."""
+    _fields_ = [
+        ("n", C.c_int),
+        ("wav", C.c_void_p), ("wav_elems", C.c_int64), ("crop_off", C.POINTER(C.c_int64)), ("crop_len", C.POINTER(C.c_int)),
+        ("norm_w", C.c_float), ("norm_b", C.c_float),
+        ("filters_host", C.POINTER(C.c_float)),
+        ("frames", C.POINTER(C.c_int)),
+        ("in_", C.c_void_p), ("in_elems", C.c_int64), ("ld_in", C.c_int64), ("in_off", C.POINTER(C.c_int)),
+        ("out", C.c_void_p), ("out_elems", C.c_int64), ("ld_out", C.c_int64), ("out_off", C.POINTER(C.c_int)),
+        ("pool", C.c_int), ("C", C.c_int), ("gamma", C.c_void_p), ("gamma_elems", C.c_int64), ("beta", C.c_void_p), ("beta_elems", C.c_int64),
+        ("weights", C.c_void_p), ("weights_elems", C.c_int64), ("w_off", C.POINTER(C.c_int64)), ("w_len", C.POINTER(C.c_int)),
+        ("whh_host", C.POINTER(C.c_float)),
+        ("rows", C.c_int), ("powerset", C.c_int)]
+
+
+SPEAKER_WAV_STATS, SPEAKER_SINC_POOL, SPEAKER_INORM, SPEAKER_STATS_POOL, SPEAKER_LSTM, SPEAKER_ACTIVATION = range(6)
+
+
 class AlignDesc(C.Structure):
     """ccx_align_desc (include/ccx.h): one word-alignment kernel on its own."""
     _fields_ = [
@@ -318,6 +337,7 @@ PROTOTYPES = {
     "ccx_speaker_finalize": (_i, [_vp]),
     "ccx_speaker_embed": (_i, [_vp, _vp, _i64p, _ip, _i, _vp, _i64p, _ip, _vp, _vp]),
     "ccx_speaker_segment": (_i, [_vp, _vp, _i64p, _ip, _i, _vp, _i64, _ip, _vp]),
+    "ccx_speaker_op": (_i, [_vp, _i, C.POINTER(SpeakerDesc), _vp]),
     "ccx_ecapa_create": (_i, [_vp, _i, _i64, C.POINTER(_vp)]),
     "ccx_ecapa_destroy": (None, [_vp]),
     "ccx_ecapa_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i64]),

@@ -17,6 +17,7 @@
 #include "ccx_common.h"
 #include "gemm_bf16.h"
 #include "model_store.h"
+#include "op_scratch.h"
 
 namespace {
 
@@ -24,11 +25,14 @@ namespace {
 #define SN_STRIDE 10
 #define SN_F 80
 
-// per-crop mean / rstd of the raw waveform (InstanceNorm1d(1, affine) -> a*x + c folded into the sinc conv)
+// per-crop mean / rstd of the raw waveform (InstanceNorm1d(1, affine) is a (x - mean) + b, folded into the sinc conv):
+// ac[crop] = (a = w rstd, c = b - mean a, mean_hi, mean_lo).  The mean is kept as two floats: mean_hi is the fp32 mean, mean_lo the
+// mean of the deviations from it (the second pass has them anyway).  One float holds a mean of 0.5 to 3e-8 only, which is 3e-5 of
+// a signal of std 1e-3 riding on it, and the sinc stage scales that by a sum(w) (measured: 1e-4 of the output rms on dense filters).
 __global__ __launch_bounds__(256) void wav_stats_kernel(const float* __restrict__ wav, const long* __restrict__ crop_off,
                                                         const int* __restrict__ crop_len, const float* __restrict__ nw,
-                                                        const float* __restrict__ nb, float2* __restrict__ ac) {
-  __shared__ float red[8];
+                                                        const float* __restrict__ nb, float4* __restrict__ ac) {
+  __shared__ float red[12];
   const int i = blockIdx.x, tid = threadIdx.x;
   const float* x = wav + crop_off[i];
   const int n = crop_len[i];
@@ -49,31 +53,38 @@ __global__ __launch_bounds__(256) void wav_stats_kernel(const float* __restrict_
   if ((tid & 63) == 0) red[tid >> 6] = s;
   __syncthreads();
   const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)n;
-  float q = 0.f;
+  float q = 0.f, sd = 0.f;
   {
-    float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, r[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int t = tid;
     for (; t + 7 * 256 < n; t += 8 * 256) {
 #pragma unroll
-      for (int u = 0; u < 8; u++) { const float d = x[t + 256 * u] - mean; p[u] += d * d; }
+      for (int u = 0; u < 8; u++) { const float d = x[t + 256 * u] - mean; p[u] += d * d; r[u] += d; }
     }
-    for (; t < n; t += 256) { const float d = x[t] - mean; p[0] += d * d; }
+    for (; t < n; t += 256) { const float d = x[t] - mean; p[0] += d * d; r[0] += d; }
     q = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+    sd = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
   }
   q = wave_reduce_sum(q);
-  if ((tid & 63) == 0) red[4 + (tid >> 6)] = q;
+  sd = wave_reduce_sum(sd);
+  if ((tid & 63) == 0) { red[4 + (tid >> 6)] = q; red[8 + (tid >> 6)] = sd; }
   __syncthreads();
   if (tid == 0) {
-    const float var = (red[4] + red[5] + red[6] + red[7]) / (float)n;
+    const float lo = (red[8] + red[9] + red[10] + red[11]) / (float)n;            // mean = mean_hi + lo
+    const float var = fmaxf((red[4] + red[5] + red[6] + red[7]) / (float)n - lo * lo, 0.f);
     const float a = nw[0] * rsqrtf(var + 1e-5f);
-    ac[i] = make_float2(a, nb[0] - mean * a);
+    ac[i] = make_float4(a, nb[0] - (mean + lo) * a, mean, lo);
   }
 }
 
 // ---------------------------------------------------------------------------------------------
 // Sinc convolution (80 filters x 251 taps, stride 10) + |.| + max-pool(3) on the matrix cores with
-// fp32-grade operands: x = xh + xl and w = wh + wl (two bf16 each), out = xh wh + xl wh + xh wl (the
-// dropped xl wl term is 2^-18 relative; bf16 products are exact in the fp32 accumulator).
+// fp32-grade operands: v = vh + vl and w = wh + wl (two bf16 each), out = vh wh + vl wh + vh wl (the
+// dropped vl wl term and the two split residuals are 2^-18 of |v w| each; bf16 products are exact in the
+// fp32 accumulator).  v is the CENTRED sample x - mean: the error is relative to the operand's magnitude, and
+// under a DC offset the raw samples are orders of magnitude larger than the signal the norm keeps (measured
+// on DC 0.5 + noise of std 1e-3: worst error 6.8e-3 of the output rms with raw samples split, against 2e-5
+// for a zero-mean input).
 //   * k axis: stride 10 divides the taps into groups of 10 consecutive samples; an MFMA step takes 30 taps
 //     = the 30 consecutive samples x[10 p + 30 t ..] of position p (k slots 30, 31 carry zero weights),
 //     9 steps cover taps 0..269 (>= 251: zero weights);
@@ -82,7 +93,8 @@ __global__ __launch_bounds__(256) void wav_stats_kernel(const float* __restrict_
 //   * a wave = 16 pooled frames x all 80 filters (15 accumulators); the filter fragments (9 steps x 5
 //     tiles x hi/lo, 90 KB) sit lane-linear in LDS for the life of the (persistent) block, the block's
 //     samples are split into hi / lo bf16 arrays once per work item (128 pooled frames).
-// The waveform's instance norm (a x + c) is folded as before: conv(a x + c) = a conv(x) + c sum(w).
+// The waveform's instance norm a (x - mean) + b is folded around the convolution of the centred samples (x - mean_hi) - mean_lo:
+// conv(a (x - mean) + b) = a conv(x - mean) + b sum(w).  Positions past the crop's end are zeros of the centred signal.
 // ---------------------------------------------------------------------------------------------
 #define SM_FRAMES 128
 #define SM_STEPS 9
@@ -91,9 +103,10 @@ __global__ __launch_bounds__(256) void wav_stats_kernel(const float* __restrict_
 #define SM_LDS (SM_BBYTES + 2 * SM_NS * 2)
 __global__ __launch_bounds__(512) void sinc_conv_pool_kernel(const float* __restrict__ wav, const long* __restrict__ crop_off,
                                                              const int* __restrict__ crop_len, const int* __restrict__ row_off,
-                                                             const int* __restrict__ n_pool, const float2* __restrict__ ac,
+                                                             const int* __restrict__ n_pool, const float4* __restrict__ ac,
                                                              const bf16_t* __restrict__ bfrag,   // [9][5][hi|lo][64 lanes][8]
                                                              const float* __restrict__ filt_sum, // [80]
+                                                             const float* __restrict__ nb,       // [1]: the waveform norm's bias
                                                              float* __restrict__ out, int n_crops, int chunks_per_crop) {
   extern __shared__ __attribute__((aligned(16))) char sm_raw[];
   bf16_t* Bs = (bf16_t*)sm_raw;
@@ -110,9 +123,10 @@ __global__ __launch_bounds__(512) void sinc_conv_pool_kernel(const float* __rest
     if (p0 >= np) continue;                                         // uniform over the block
     const float* x = wav + crop_off[crop];
     const int n = crop_len[crop], s0 = p0 * 3 * SN_STRIDE;
+    const float4 a_c = ac[crop];                                    // (a, c, mean_hi, mean_lo)
     __syncthreads();                                                // the previous item's fragment reads are done
     for (int i = tid; i < SM_NS; i += 512) {
-      const float v = (s0 + i < n) ? x[s0 + i] : 0.f;
+      const float v = (s0 + i < n) ? (x[s0 + i] - a_c.z) - a_c.w : 0.f;
       const bf16_t h = f32_to_bf16(v);
       xh[i] = h;
       xl[i] = f32_to_bf16(v - bf16_to_f32(h));
@@ -147,12 +161,12 @@ __global__ __launch_bounds__(512) void sinc_conv_pool_kernel(const float* __rest
         }
       }
     }
-    const float2 a_c = ac[crop];
     const long orow = (long)row_off[crop] + p0 + 16 * wave + 4 * hq;
+    const float bias = nb[0];
 #pragma unroll
     for (int nt = 0; nt < 5; nt++) {
       const int f = 16 * nt + l15;
-      const float cs = a_c.y * filt_sum[f];
+      const float cs = bias * filt_sum[f];
 #pragma unroll
       for (int reg = 0; reg < 4; reg++) {
         if (p0 + 16 * wave + 4 * hq + reg < np) {
@@ -207,8 +221,8 @@ __global__ __launch_bounds__(256) void inorm_partial_kernel(const float* __restr
   if (cnt > 0) {
 #pragma unroll
     for (int g = 0; g < 8; g++) { const float4 r = red[g][q]; mean.x += r.x; mean.y += r.y; mean.z += r.z; mean.w += r.w; }
-    const float inv = 1.f / (float)cnt;
-    mean.x *= inv; mean.y *= inv; mean.z *= inv; mean.w *= inv;
+    const float fc = (float)cnt;    // a division, not a reciprocal: the mean of a constant channel is that constant exactly
+    mean.x /= fc; mean.y /= fc; mean.z /= fc; mean.w /= fc;
   }
   __syncthreads();
   float4 m2 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -464,6 +478,101 @@ __global__ void seg_activation_kernel(const float* __restrict__ logits, int ld, 
   }
 }
 
+// ---- launchers and weight packers: the networks below and ccx_speaker_op both go through these ----
+#define INORM_CPAD 128   // channel stride of the (mean, M2) partials: 32 channel quads
+
+int launch_wav_stats(ccx_ctx* ctx, const float* wav, const long* crop_off, const int* crop_len, const float* nw, const float* nb, int n,
+                     float4* ac, hipStream_t st) {
+  hipLaunchKernelGGL(wav_stats_kernel, dim3(n), dim3(256), 0, st, wav, crop_off, crop_len, nw, nb, ac);
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+// n_pool_host: the host copy of n_pool (the grid is sized by the longest crop)
+int launch_sinc_pool(ccx_ctx* ctx, const float* wav, const long* crop_off, const int* crop_len, const int* row_off, const int* n_pool,
+                     const int* n_pool_host, int n, const float4* ac, const bf16_t* bfrag, const float* filt_sum, const float* nb, float* out,
+                     hipStream_t st) {
+  int maxp = 0;
+  long positions = 0;
+  for (int i = 0; i < n; i++) { maxp = n_pool_host[i] > maxp ? n_pool_host[i] : maxp; positions += 3L * n_pool_host[i]; }
+  static ccx_lds_optin optin;
+  CCX_HIP(ctx, optin.ensure(ctx->device, (const void*)sinc_conv_pool_kernel, SM_LDS));
+  const int chunks = ccx_cdiv(maxp, SM_FRAMES);
+  const long items = (long)chunks * n;
+  {
+    ccx_prof_scope ps(ctx, st, "sinc_conv_pool_kernel", 2.0 * positions * SN_F * SN_K, 0.0);
+    hipLaunchKernelGGL(sinc_conv_pool_kernel, dim3((unsigned)(items < 256 ? items : 256)), dim3(512), SM_LDS, st, wav, crop_off, crop_len,
+                       row_off, n_pool, ac, bfrag, filt_sum, nb, out, n, chunks);
+  }
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+// part: f32 [n][INORM_CHUNKS][INORM_CPAD][2]
+int launch_inorm(ccx_ctx* ctx, int pool, const float* in, int ld_in, const int* in_off, bf16_t* out, int ld_out, const int* out_off,
+                 const int* n_out, float* part, const float* g, const float* b, int C, int n, hipStream_t st) {
+  const dim3 grid(n, INORM_CHUNKS, 1);
+  if (pool == 3) hipLaunchKernelGGL(inorm_partial_kernel<3>, grid, dim3(256), 0, st, in, ld_in, in_off, n_out, part, C, INORM_CPAD);
+  else hipLaunchKernelGGL(inorm_partial_kernel<1>, grid, dim3(256), 0, st, in, ld_in, in_off, n_out, part, C, INORM_CPAD);
+  CCX_CHECK_LAUNCH(ctx);
+  if (pool == 3) hipLaunchKernelGGL(inorm_apply_kernel<3>, grid, dim3(256), 0, st, in, ld_in, in_off, out, ld_out, out_off, n_out, part, g, b, C, INORM_CPAD);
+  else hipLaunchKernelGGL(inorm_apply_kernel<1>, grid, dim3(256), 0, st, in, ld_in, in_off, out, ld_out, out_off, n_out, part, g, b, C, INORM_CPAD);
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int launch_stats_pool(ccx_ctx* ctx, const bf16_t* x, int ld_in, const int* row_off, const int* n_valid, const float* weights, const long* w_off,
+                      const int* w_len, bf16_t* out, int ld_out, int C, int n, hipStream_t st) {
+  hipLaunchKernelGGL(stats_pool_kernel, dim3(n, ccx_cdiv(C, 256)), dim3(256), 0, st, x, ld_in, row_off, n_valid, weights, w_off, w_len, out, ld_out, C);
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int launch_lstm(ccx_ctx* ctx, const float* gx, const bf16_t* whh, const int* row_off, const int* n_rows, int n, bf16_t* hout, hipStream_t st) {
+  {
+    ccx_prof_scope ps(ctx, st, "lstm_recurrent_kernel", 0.0, 0.0);
+    hipLaunchKernelGGL(lstm_recurrent_kernel, dim3(ccx_cdiv(n, LSTM_SEQS), 2), dim3(512), 0, st, gx, whh, row_off, n_rows, n, hout);
+  }
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int launch_activation(ccx_ctx* ctx, const float* logits, int ld, float* out, int C, int rows, int powerset, hipStream_t st) {
+  hipLaunchKernelGGL(seg_activation_kernel, dim3(ccx_cdiv(rows, 256)), dim3(256), 0, st, logits, ld, out, C, rows, powerset);
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+// sinc filters f32 [80][251] -> the B fragments of sinc_conv_pool_kernel as f32 [9 steps][5 tiles][hi|lo][64 lanes][8] (hi is exactly
+// representable in bf16, lo is rounded to bf16 on upload) and the filter sums [80] (summed in fp64, rounded once)
+void pack_sinc_filters(const float* fl, std::vector<float>& frag, std::vector<float>& fs) {
+  fs.assign(SN_F, 0.f);
+  frag.assign((size_t)SM_STEPS * 5 * 2 * 64 * 8, 0.f);
+  for (int f = 0; f < SN_F; f++) {
+    double sum = 0.0;   // (an fp32 running sum of 251 band-pass taps that cancel is off by up to 1e-5 of sum |w|)
+    for (int k = 0; k < SN_K; k++) sum += fl[(size_t)f * SN_K + k];
+    fs[f] = (float)sum;
+  }
+  for (int t = 0; t < SM_STEPS; t++)
+    for (int nt = 0; nt < 5; nt++)
+      for (int lane = 0; lane < 64; lane++)
+        for (int e = 0; e < 8; e++) {
+          const int kk = 8 * (lane >> 4) + e, tap = 30 * t + kk, f = 16 * nt + (lane & 15);
+          const float w = (kk < 30 && tap < SN_K) ? fl[(size_t)f * SN_K + tap] : 0.f;
+          const bf16_t hb = ccx_host_f32_to_bf16(w);
+          uint32_t hu = (uint32_t)hb << 16; float hf; memcpy(&hf, &hu, 4);
+          frag[((((size_t)t * 5 + nt) * 2 + 0) * 64 + lane) * 8 + e] = hf;       // exactly representable: the bf16 rounding keeps it
+          frag[((((size_t)t * 5 + nt) * 2 + 1) * 64 + lane) * 8 + e] = w - hf;   // rounded to bf16 on upload
+        }
+}
+
+// W_hh of the two directions, f32 [512][128] each (rows i|f|g|o) -> lstm_recurrent_kernel's bf16 [2][512][128]
+std::vector<bf16_t> pack_whh(const float* fwd, const float* rev) {
+  std::vector<bf16_t> r((size_t)2 * 512 * 128);
+  for (size_t i = 0; i < (size_t)512 * 128; i++) { r[i] = ccx_host_f32_to_bf16(fwd[i]); r[(size_t)512 * 128 + i] = ccx_host_f32_to_bf16(rev[i]); }
+  return r;
+}
+
 struct SincNetW {
   float *nw, *nb, *filt_sum, *n0g, *n0b, *n1g, *n1b, *n2g, *n2b, *b1, *b2;
   bf16_t* bfrag;    // sinc filters as MFMA B fragments [9 steps][5 tiles][hi|lo][64 lanes][8]
@@ -497,7 +606,7 @@ struct ccx_speaker {
   bf16_t *Wl0 = nullptr, *Wl1 = nullptr, *Wcls = nullptr; float *bl0 = nullptr, *bl1 = nullptr, *bcls = nullptr;
   // workspaces
   long R1cap = 0;
-  float2* ac = nullptr;
+  float4* ac = nullptr;
   float *s1 = nullptr, *c2 = nullptr, *c3 = nullptr, *acc = nullptr, *gx = nullptr, *logit = nullptr, *inorm_part = nullptr;
   bf16_t *s1n = nullptr, *s2n = nullptr, *s3n = nullptr, *a1 = nullptr, *a2 = nullptr, *a5 = nullptr, *pooled = nullptr, *hA = nullptr, *hB = nullptr;
   // host copies of the per-call tables: the uploads are asynchronous, so the last few calls' tables stay alive here
@@ -534,20 +643,8 @@ int load_sincnet(ccx_speaker* s, const std::string& pre) {
   CCX_NEED(s->store, g0, pre + "norm1d.0.weight", 80); CCX_NEED(s->store, be0, pre + "norm1d.0.bias", 80);
   CCX_NEED(s->store, g1, pre + "norm1d.1.weight", 60); CCX_NEED(s->store, be1, pre + "norm1d.1.bias", 60);
   CCX_NEED(s->store, g2, pre + "norm1d.2.weight", 60); CCX_NEED(s->store, be2, pre + "norm1d.2.bias", 60);
-  std::vector<float> fs(SN_F, 0.f), frag((size_t)SM_STEPS * 5 * 2 * 64 * 8, 0.f);
-  for (int f = 0; f < SN_F; f++)
-    for (int k = 0; k < SN_K; k++) fs[f] += fl->data[(size_t)f * SN_K + k];
-  for (int t = 0; t < SM_STEPS; t++)
-    for (int nt = 0; nt < 5; nt++)
-      for (int lane = 0; lane < 64; lane++)
-        for (int e = 0; e < 8; e++) {
-          const int kk = 8 * (lane >> 4) + e, tap = 30 * t + kk, f = 16 * nt + (lane & 15);
-          const float w = (kk < 30 && tap < SN_K) ? fl->data[(size_t)f * SN_K + tap] : 0.f;
-          const bf16_t hb = ccx_host_f32_to_bf16(w);
-          uint32_t hu = (uint32_t)hb << 16; float hf; memcpy(&hf, &hu, 4);
-          frag[((((size_t)t * 5 + nt) * 2 + 0) * 64 + lane) * 8 + e] = hf;       // exactly representable: upload_bf16 keeps it
-          frag[((((size_t)t * 5 + nt) * 2 + 1) * 64 + lane) * 8 + e] = w - hf;   // rounded to bf16 by upload_bf16
-        }
+  std::vector<float> fs, frag;
+  pack_sinc_filters(fl->data.data(), frag, fs);
   CCX_TRY(s->store.upload(&n.nw, nw->data.data(), 1)); CCX_TRY(s->store.upload(&n.nb, nb->data.data(), 1));
   CCX_TRY(s->store.upload_bf16(&n.bfrag, frag)); CCX_TRY(s->store.upload(&n.filt_sum, fs));
   CCX_TRY(s->store.upload_bf16(&n.W1, conv_w(w1->data, 60, 80, 5, 80, 448))); CCX_TRY(s->store.upload(&n.b1, b1->data.data(), 60));
@@ -591,44 +688,18 @@ int upload_plan(ccx_speaker* s, const Plan& P, hipStream_t st) {
 int run_sincnet(ccx_speaker* s, const float* wav, const Plan& P, hipStream_t st) {
   ccx_ctx* ctx = s->ctx;
   const SincNetW& n = s->sn;
-  hipLaunchKernelGGL(wav_stats_kernel, dim3(P.n), dim3(256), 0, st, wav, s->crop_off, s->crop_len, n.nw, n.nb, s->ac);
-  CCX_CHECK_LAUNCH(ctx);
-  int maxp = 0;
-  for (int i = 0; i < P.n; i++) maxp = P.f1[i] > maxp ? P.f1[i] : maxp;
-  {
-    static ccx_lds_optin optin;
-    CCX_HIP(ctx, optin.ensure(ctx->device, (const void*)sinc_conv_pool_kernel, SM_LDS));
-    const int chunks = ccx_cdiv(maxp, SM_FRAMES);
-    const long items = (long)chunks * P.n;
-    long positions = 0;
-    for (int i = 0; i < P.n; i++) positions += 3L * P.f1[i];
-    ccx_prof_scope ps(ctx, st, "sinc_conv_pool_kernel", 2.0 * positions * SN_F * SN_K, 0.0);
-    hipLaunchKernelGGL(sinc_conv_pool_kernel, dim3((unsigned)(items < 256 ? items : 256)), dim3(512), SM_LDS, st, wav, s->crop_off, s->crop_len,
-                       s->off1, s->nF1, s->ac, n.bfrag, n.filt_sum, s->s1, P.n, chunks);
-  }
-  CCX_CHECK_LAUNCH(ctx);
-  hipLaunchKernelGGL(inorm_partial_kernel<1>, dim3(P.n, INORM_CHUNKS, 1), dim3(256), 0, st, s->s1, 80, s->off1, s->nF1, s->inorm_part, 80, 128);
-  CCX_CHECK_LAUNCH(ctx);
-  hipLaunchKernelGGL(inorm_apply_kernel<1>, dim3(P.n, INORM_CHUNKS, 1), dim3(256), 0, st, s->s1, 80, s->off1, s->s1n, 80, s->off1, s->nF1,
-                     s->inorm_part, n.n0g, n.n0b, 80, 128);
-  CCX_CHECK_LAUNCH(ctx);
+  CCX_TRY(launch_wav_stats(ctx, wav, s->crop_off, s->crop_len, n.nw, n.nb, P.n, s->ac, st));
+  CCX_TRY(launch_sinc_pool(ctx, wav, s->crop_off, s->crop_len, s->off1, s->nF1, P.f1.data(), P.n, s->ac, n.bfrag, n.filt_sum, n.nb, s->s1, st));
+  CCX_TRY(launch_inorm(ctx, 1, s->s1, 80, s->off1, s->s1n, 80, s->off1, s->nF1, s->inorm_part, n.n0g, n.n0b, 80, P.n, st));
   GemmParams p;
   memset(&p, 0, sizeof(p));   // conv1d(80 -> 60, k5) as a GEMM over a strided view: row m = frames m..m+4
   p.A = s->s1n; p.lda = 80; p.W = n.W1; p.ldw = 448; p.M = (int)P.R1; p.N = 60; p.K = 448; p.bias = n.b1; p.out = s->c2; p.ldo = 128;
   CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
-  hipLaunchKernelGGL(inorm_partial_kernel<3>, dim3(P.n, INORM_CHUNKS, 1), dim3(256), 0, st, s->c2, 128, s->off1, s->nF2, s->inorm_part, 60, 128);
-  CCX_CHECK_LAUNCH(ctx);
-  hipLaunchKernelGGL(inorm_apply_kernel<3>, dim3(P.n, INORM_CHUNKS, 1), dim3(256), 0, st, s->c2, 128, s->off1, s->s2n, 64, s->off2, s->nF2,
-                     s->inorm_part, n.n1g, n.n1b, 60, 128);
-  CCX_CHECK_LAUNCH(ctx);
+  CCX_TRY(launch_inorm(ctx, 3, s->c2, 128, s->off1, s->s2n, 64, s->off2, s->nF2, s->inorm_part, n.n1g, n.n1b, 60, P.n, st));
   memset(&p, 0, sizeof(p));   // conv1d(60 -> 60, k5), channels padded to 64
   p.A = s->s2n; p.lda = 64; p.W = n.W2; p.ldw = 320; p.M = (int)P.R2; p.N = 60; p.K = 320; p.bias = n.b2; p.out = s->c3; p.ldo = 128;
   CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
-  hipLaunchKernelGGL(inorm_partial_kernel<3>, dim3(P.n, INORM_CHUNKS, 1), dim3(256), 0, st, s->c3, 128, s->off2, s->nF3, s->inorm_part, 60, 128);
-  CCX_CHECK_LAUNCH(ctx);
-  hipLaunchKernelGGL(inorm_apply_kernel<3>, dim3(P.n, INORM_CHUNKS, 1), dim3(256), 0, st, s->c3, 128, s->off2, s->s3n, 64, s->off3, s->nF3,
-                     s->inorm_part, n.n2g, n.n2b, 60, 128);
-  CCX_CHECK_LAUNCH(ctx);
+  CCX_TRY(launch_inorm(ctx, 3, s->c3, 128, s->off2, s->s3n, 64, s->off3, s->nF3, s->inorm_part, n.n2g, n.n2b, 60, P.n, st));
   return CCX_OK;
 }
 
@@ -686,7 +757,8 @@ int ccx_speaker_finalize(ccx_speaker* s) {
   } else {
     for (int l = 0; l < 4; l++) {
       const int in = l == 0 ? 60 : 256, inp = l == 0 ? 64 : 256;
-      std::vector<float> wih((size_t)1024 * inp, 0.f), bias(1024), whh((size_t)2 * 512 * 128);
+      std::vector<float> wih((size_t)1024 * inp, 0.f), bias(1024);
+      const float* whd[2] = {nullptr, nullptr};
       for (int dir = 0; dir < 2; dir++) {
         const std::string sfx = "_l" + std::to_string(l) + (dir ? "_reverse" : "");
         CCX_NEED(s->store, wi, "lstm.weight_ih" + sfx, (int64_t)512 * in); CCX_NEED(s->store, wh, "lstm.weight_hh" + sfx, 512 * 128);
@@ -694,10 +766,10 @@ int ccx_speaker_finalize(ccx_speaker* s) {
         for (int r = 0; r < 512; r++) {
           for (int k = 0; k < in; k++) wih[(size_t)(dir * 512 + r) * inp + k] = wi->data[(size_t)r * in + k];
           bias[dir * 512 + r] = bi->data[r] + bh->data[r];
-          for (int k = 0; k < 128; k++) whh[((size_t)dir * 512 + r) * 128 + k] = wh->data[(size_t)r * 128 + k];
         }
+        whd[dir] = wh->data.data();
       }
-      CCX_TRY(s->store.upload_bf16(&s->Wih[l], wih)); CCX_TRY(s->store.upload(&s->bih[l], bias.data(), 1024)); CCX_TRY(s->store.upload_bf16(&s->whh[l], whh));
+      CCX_TRY(s->store.upload_bf16(&s->Wih[l], wih)); CCX_TRY(s->store.upload(&s->bih[l], bias.data(), 1024)); CCX_TRY(s->store.upload(&s->whh[l], pack_whh(whd[0], whd[1])));
     }
     CCX_NEED(s->store, l0w, "linear.0.weight", 128 * 256); CCX_NEED(s->store, l0b, "linear.0.bias", 128);
     CCX_NEED(s->store, l1w, "linear.1.weight", 128 * 128); CCX_NEED(s->store, l1b, "linear.1.bias", 128);
@@ -712,7 +784,7 @@ int ccx_speaker_finalize(ccx_speaker* s) {
   const size_t R1 = (size_t)s->R1cap + 16, R2 = R1 / 3 + 16, R3 = R2 / 3 + 16, C = (size_t)s->max_crops;
   CCX_TRY(s->store.alloc(&s->ac, C, true)); CCX_TRY(s->store.alloc(&s->s1, R1 * 80, true)); CCX_TRY(s->store.alloc(&s->s1n, R1 * 80 + 1024, true));
   CCX_TRY(s->store.alloc(&s->c2, R1 * 128, true)); CCX_TRY(s->store.alloc(&s->s2n, R2 * 64 + 1024, true)); CCX_TRY(s->store.alloc(&s->c3, R2 * 128, true)); CCX_TRY(s->store.alloc(&s->s3n, R3 * 64 + 1024, true));
-  CCX_TRY(s->store.alloc(&s->inorm_part, (size_t)C * INORM_CHUNKS * 128 * 2, true));
+  CCX_TRY(s->store.alloc(&s->inorm_part, (size_t)C * INORM_CHUNKS * INORM_CPAD * 2, true));
   CCX_TRY(s->store.alloc(&s->crop_off, C, true)); CCX_TRY(s->store.alloc(&s->crop_len, C, true)); CCX_TRY(s->store.alloc(&s->w_off, C, true)); CCX_TRY(s->store.alloc(&s->w_len, C, true));
   CCX_TRY(s->store.alloc(&s->off1, C, true)); CCX_TRY(s->store.alloc(&s->off2, C, true)); CCX_TRY(s->store.alloc(&s->off3, C, true));
   CCX_TRY(s->store.alloc(&s->nF1, C, true)); CCX_TRY(s->store.alloc(&s->nF2, C, true)); CCX_TRY(s->store.alloc(&s->nF3, C, true)); CCX_TRY(s->store.alloc(&s->nFv, C, true));
@@ -779,9 +851,7 @@ int ccx_speaker_embed(ccx_speaker* s, const float* wav, const int64_t* offsets, 
     CCX_HIP(ctx, hipMemcpyAsync(s->w_len, wl.data(), n * 4, hipMemcpyHostToDevice, st));
     CCX_HIP(ctx, hipStreamSynchronize(st));
   }
-  hipLaunchKernelGGL(stats_pool_kernel, dim3(n, ccx_cdiv(1500, 256)), dim3(256), 0, st, s->a5, 1536, s->off3, s->nFv, weights, s->w_off,
-                     s->w_len, s->pooled, 3072, 1500);
-  CCX_CHECK_LAUNCH(ctx);
+  CCX_TRY(launch_stats_pool(ctx, s->a5, 1536, s->off3, s->nFv, weights, s->w_off, s->w_len, s->pooled, 3072, 1500, n, st));
   // embedding Linear(3000 -> 512); out rows are 512 wide
   memset(&p, 0, sizeof(p));
   p.A = s->pooled; p.lda = 3072; p.W = s->Wemb; p.ldw = 3072; p.M = n; p.N = 512; p.K = 3072; p.bias = s->bemb; p.out = out; p.ldo = 512;
@@ -813,11 +883,7 @@ int ccx_speaker_segment(ccx_speaker* s, const float* wav, const int64_t* offsets
     memset(&p, 0, sizeof(p));
     p.A = x; p.lda = ldx; p.W = s->Wih[l]; p.ldw = K; p.M = R3; p.N = 1024; p.K = K; p.bias = s->bih[l]; p.out = s->gx; p.ldo = 1024;
     CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
-    {
-      ccx_prof_scope ps(ctx, st, "lstm_recurrent_kernel", 0.0, 0.0);
-      hipLaunchKernelGGL(lstm_recurrent_kernel, dim3(ccx_cdiv(n, LSTM_SEQS), 2), dim3(512), 0, st, s->gx, s->whh[l], s->off3, s->nF3, n, hbuf[l & 1]);
-    }
-    CCX_CHECK_LAUNCH(ctx);
+    CCX_TRY(launch_lstm(ctx, s->gx, s->whh[l], s->off3, s->nF3, n, hbuf[l & 1], st));
     x = hbuf[l & 1]; ldx = 256; K = 256;
   }
   bf16_t* t0 = hbuf[0];  // layer 3 wrote hbuf[1]; reuse hbuf[0] for the linear outputs ([R3][128] fits in [R3][256])
@@ -831,9 +897,168 @@ int ccx_speaker_segment(ccx_speaker* s, const float* wav, const int64_t* offsets
   memset(&p, 0, sizeof(p));
   p.A = t1; p.lda = 128; p.W = s->Wcls; p.ldw = 128; p.M = R3; p.N = s->n_classes; p.K = 128; p.bias = s->bcls; p.out = s->logit; p.ldo = 128;
   CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
-  hipLaunchKernelGGL(seg_activation_kernel, dim3(ccx_cdiv(R3, 256)), dim3(256), 0, st, s->logit, 128, out, s->n_classes, R3, s->powerset);
-  CCX_CHECK_LAUNCH(ctx);
+  CCX_TRY(launch_activation(ctx, s->logit, 128, out, s->n_classes, R3, s->powerset, st));
   return CCX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the kernels on their own (include/ccx.h: ccx_speaker_op)
+// ---------------------------------------------------------------------------------------------
+#define SP_BUF(field, need)                                                                                                          \
+  do {                                                                                                                               \
+    CCX_REQUIRE(ctx, d->field != nullptr, "ccx_speaker_op: %s is NULL", #field);                                                     \
+    CCX_REQUIRE(ctx, ccx_aligned16(d->field), "ccx_speaker_op: %s is not 16-byte aligned", #field);                                  \
+    CCX_REQUIRE(ctx, d->field##_elems >= (int64_t)(need), "ccx_speaker_op: %s is accessed up to element %ld, %s_elems=%ld", #field,  \
+                (long)(need), #field, (long)d->field##_elems);                                                                       \
+  } while (0)
+#define SP_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return ccx_fail(ctx, CCX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+#define SP_ROWS_MAX (1L << 24)   // rows of any buffer: keeps every int row index and row x ld product of the kernels in range
+
+int ccx_speaker_op(ccx_ctx* ctx, int op, const ccx_speaker_desc* d, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream_;
+  CCX_REQUIRE(ctx, d != nullptr, "ccx_speaker_op: desc is NULL");
+  CCX_REQUIRE(ctx, op >= CCX_SPEAKER_WAV_STATS && op <= CCX_SPEAKER_ACTIVATION, "ccx_speaker_op: unknown op %d", op);
+  const int n = d->n;
+  long in_rows = 0, out_rows = 0;      // rows of in / out the crops reach
+  const bool ragged = op != CCX_SPEAKER_WAV_STATS && op != CCX_SPEAKER_ACTIVATION;   // per-crop frame counts and row offsets
+  if (op != CCX_SPEAKER_ACTIVATION) CCX_REQUIRE(ctx, n >= 1 && n <= 65535, "ccx_speaker_op: n = %d out of range [1, 65535]", n);
+  if (ragged) CCX_REQUIRE(ctx, d->frames != nullptr, "ccx_speaker_op: frames is NULL");
+  if (op == CCX_SPEAKER_WAV_STATS || op == CCX_SPEAKER_SINC_POOL) {
+    CCX_REQUIRE(ctx, d->wav != nullptr && ((uintptr_t)d->wav & 3) == 0, "ccx_speaker_op: wav is NULL or not 4-byte aligned");
+    CCX_REQUIRE(ctx, d->crop_off != nullptr && d->crop_len != nullptr, "ccx_speaker_op: crop_off or crop_len is NULL");
+    for (int i = 0; i < n; i++) {
+      CCX_REQUIRE(ctx, d->crop_len[i] >= SN_K && d->crop_len[i] <= (1 << 30), "ccx_speaker_op: crop_len[%d] = %d out of range [%d, 2^30]", i, d->crop_len[i], SN_K);
+      CCX_REQUIRE(ctx, d->crop_off[i] >= 0 && d->crop_off[i] + d->crop_len[i] <= d->wav_elems,
+                  "ccx_speaker_op: crop %d is read up to element %ld, wav_elems=%ld", i, (long)(d->crop_off[i] + d->crop_len[i]), (long)d->wav_elems);
+    }
+  }
+  if (ragged) {
+    // ragged rows: crop i reads rows in_off[i] .. of in and writes rows out_off[i] .. (STATS_POOL: row i) of out
+    const bool has_in = op != CCX_SPEAKER_SINC_POOL, has_out_off = op != CCX_SPEAKER_STATS_POOL;
+    CCX_REQUIRE(ctx, !has_in || d->in_off != nullptr, "ccx_speaker_op: in_off is NULL");
+    CCX_REQUIRE(ctx, !has_out_off || d->out_off != nullptr, "ccx_speaker_op: out_off is NULL");
+    const int f_min = op == CCX_SPEAKER_STATS_POOL && !d->weights ? 2 : 1;
+    const int in_per = op == CCX_SPEAKER_INORM && d->pool == 3 ? 3 : 1;
+    for (int i = 0; i < n; i++) {
+      const long f = d->frames[i];
+      CCX_REQUIRE(ctx, f >= f_min && f <= SP_ROWS_MAX, "ccx_speaker_op: frames[%d] = %ld out of range [%d, 2^24]", i, f, f_min);
+      if (has_in) {
+        CCX_REQUIRE(ctx, d->in_off[i] >= 0 && d->in_off[i] <= SP_ROWS_MAX, "ccx_speaker_op: in_off[%d] = %d out of range [0, 2^24]", i, d->in_off[i]);
+        in_rows = std::max(in_rows, d->in_off[i] + in_per * f);
+      }
+      if (has_out_off) {
+        CCX_REQUIRE(ctx, d->out_off[i] >= 0 && d->out_off[i] <= SP_ROWS_MAX, "ccx_speaker_op: out_off[%d] = %d out of range [0, 2^24]", i, d->out_off[i]);
+        out_rows = std::max(out_rows, d->out_off[i] + f);
+      }
+    }
+    if (!has_out_off) out_rows = n;
+  }
+  const long ld_in = d->ld_in, ld_out = d->ld_out;
+  const int C = d->C;
+  switch (op) {
+    case CCX_SPEAKER_WAV_STATS:
+      SP_BUF(out, 4L * n);
+      break;
+    case CCX_SPEAKER_SINC_POOL:
+      CCX_REQUIRE(ctx, d->filters_host != nullptr, "ccx_speaker_op: filters_host is NULL");
+      for (int i = 0; i < n; i++) {
+        const int most = ((d->crop_len[i] - SN_K) / SN_STRIDE + 1) / 3;
+        CCX_REQUIRE(ctx, d->frames[i] <= most, "ccx_speaker_op: frames[%d] = %d, crop_len[%d] = %d holds %d pooled frames", i, d->frames[i], i, d->crop_len[i], most);
+      }
+      SP_BUF(out, out_rows * SN_F);
+      break;
+    case CCX_SPEAKER_INORM:
+      CCX_REQUIRE(ctx, d->pool == 1 || d->pool == 3, "ccx_speaker_op: pool = %d is neither 1 nor 3", d->pool);
+      CCX_REQUIRE(ctx, C >= 4 && C <= INORM_CPAD && C % 4 == 0, "ccx_speaker_op: C = %d must be a multiple of 4 in [4, %d]", C, INORM_CPAD);
+      CCX_REQUIRE(ctx, ld_in >= C && ld_in % 4 == 0 && ld_in <= 4096, "ccx_speaker_op: ld_in = %ld must be a multiple of 4 in [C = %d, 4096]", ld_in, C);
+      CCX_REQUIRE(ctx, ld_out >= C && ld_out % 4 == 0 && ld_out <= INORM_CPAD, "ccx_speaker_op: ld_out = %ld must be a multiple of 4 in [C = %d, %d]", ld_out, C, INORM_CPAD);
+      SP_BUF(in, in_rows * ld_in); SP_BUF(out, out_rows * ld_out); SP_BUF(gamma, C); SP_BUF(beta, C);
+      break;
+    case CCX_SPEAKER_STATS_POOL:
+      CCX_REQUIRE(ctx, C >= 1 && C <= 4096, "ccx_speaker_op: C = %d out of range [1, 4096]", C);
+      CCX_REQUIRE(ctx, ld_in >= C && ld_in <= 8192, "ccx_speaker_op: ld_in = %ld out of range [C = %d, 8192]", ld_in, C);
+      CCX_REQUIRE(ctx, ld_out >= 2 * C && ld_out <= 16384, "ccx_speaker_op: ld_out = %ld out of range [2 C = %d, 16384]", ld_out, 2 * C);
+      SP_BUF(in, (in_rows - 1) * ld_in + C); SP_BUF(out, (long)(n - 1) * ld_out + 2 * C);
+      if (d->weights) {
+        CCX_REQUIRE(ctx, d->w_off != nullptr && d->w_len != nullptr, "ccx_speaker_op: weights are given without w_off or w_len");
+        long w_need = 0;
+        for (int i = 0; i < n; i++) {
+          CCX_REQUIRE(ctx, d->w_len[i] >= 1 && d->w_len[i] <= (1 << 20), "ccx_speaker_op: w_len[%d] = %d out of range [1, 2^20]", i, d->w_len[i]);
+          CCX_REQUIRE(ctx, d->w_off[i] >= 0, "ccx_speaker_op: w_off[%d] = %ld is negative", i, (long)d->w_off[i]);
+          w_need = std::max(w_need, (long)d->w_off[i] + d->w_len[i]);
+        }
+        SP_BUF(weights, w_need);
+      }
+      break;
+    case CCX_SPEAKER_LSTM:
+      CCX_REQUIRE(ctx, d->whh_host != nullptr, "ccx_speaker_op: whh_host is NULL");
+      for (int i = 0; i < n; i++)
+        CCX_REQUIRE(ctx, d->in_off[i] == d->out_off[i], "ccx_speaker_op: in_off[%d] = %d and out_off[%d] = %d differ (gx and hout share their rows)", i, d->in_off[i], i, d->out_off[i]);
+      SP_BUF(in, in_rows * 1024); SP_BUF(out, out_rows * 256);
+      break;
+    default:
+      CCX_REQUIRE(ctx, d->rows >= 1 && d->rows <= SP_ROWS_MAX, "ccx_speaker_op: rows = %d out of range [1, 2^24]", d->rows);
+      CCX_REQUIRE(ctx, C >= 1 && C <= 4096, "ccx_speaker_op: C = %d out of range [1, 4096]", C);
+      CCX_REQUIRE(ctx, ld_in >= C && ld_in <= 8192, "ccx_speaker_op: ld_in = %ld out of range [C = %d, 8192]", ld_in, C);
+      SP_BUF(in, (long)(d->rows - 1) * ld_in + C); SP_BUF(out, (long)d->rows * C);
+  }
+
+  ccx_op_scratch sc;
+  int rc = CCX_OK;
+  long* crop_off = nullptr; long* w_off = nullptr;
+  int *crop_len = nullptr, *in_off = nullptr, *out_off = nullptr, *frames = nullptr, *w_len = nullptr;
+  float *nw = nullptr, *nb = nullptr;
+  if (ragged) SP_HIP(sc.upload(&frames, d->frames, (size_t)n));
+  if (op == CCX_SPEAKER_WAV_STATS || op == CCX_SPEAKER_SINC_POOL) {
+    std::vector<long> co(d->crop_off, d->crop_off + n);
+    SP_HIP(sc.upload(&crop_off, co.data(), co.size())); SP_HIP(sc.upload(&crop_len, d->crop_len, (size_t)n));
+    SP_HIP(sc.upload(&nw, &d->norm_w, 1)); SP_HIP(sc.upload(&nb, &d->norm_b, 1));
+  }
+  if (op == CCX_SPEAKER_INORM || op == CCX_SPEAKER_STATS_POOL || op == CCX_SPEAKER_LSTM) SP_HIP(sc.upload(&in_off, d->in_off, (size_t)n));
+  if (op == CCX_SPEAKER_SINC_POOL || op == CCX_SPEAKER_INORM) SP_HIP(sc.upload(&out_off, d->out_off, (size_t)n));
+  switch (op) {
+    case CCX_SPEAKER_WAV_STATS:
+      rc = launch_wav_stats(ctx, (const float*)d->wav, crop_off, crop_len, nw, nb, n, (float4*)d->out, st);
+      break;
+    case CCX_SPEAKER_SINC_POOL: {
+      std::vector<float> frag, fs;
+      pack_sinc_filters(d->filters_host, frag, fs);
+      std::vector<bf16_t> fb(frag.size());
+      for (size_t i = 0; i < frag.size(); i++) fb[i] = ccx_host_f32_to_bf16(frag[i]);
+      bf16_t* bfrag = nullptr; float* filt_sum = nullptr; float4* ac = nullptr;
+      SP_HIP(sc.upload(&bfrag, fb.data(), fb.size())); SP_HIP(sc.upload(&filt_sum, fs.data(), fs.size())); SP_HIP(sc.alloc(&ac, (size_t)n));
+      rc = launch_wav_stats(ctx, (const float*)d->wav, crop_off, crop_len, nw, nb, n, ac, st);
+      if (rc == CCX_OK)
+        rc = launch_sinc_pool(ctx, (const float*)d->wav, crop_off, crop_len, out_off, frames, d->frames, n, ac, bfrag, filt_sum, nb, (float*)d->out, st);
+      break;
+    }
+    case CCX_SPEAKER_INORM: {
+      float* part = nullptr;
+      SP_HIP(sc.alloc(&part, (size_t)n * INORM_CHUNKS * INORM_CPAD * 2));
+      rc = launch_inorm(ctx, d->pool, (const float*)d->in, (int)ld_in, in_off, (bf16_t*)d->out, (int)ld_out, out_off, frames, part, (const float*)d->gamma,
+                        (const float*)d->beta, C, n, st);
+      break;
+    }
+    case CCX_SPEAKER_STATS_POOL:
+      if (d->weights) {
+        std::vector<long> wo(d->w_off, d->w_off + n);
+        SP_HIP(sc.upload(&w_off, wo.data(), wo.size())); SP_HIP(sc.upload(&w_len, d->w_len, (size_t)n));
+      }
+      rc = launch_stats_pool(ctx, (const bf16_t*)d->in, (int)ld_in, in_off, frames, (const float*)d->weights, w_off, w_len, (bf16_t*)d->out, (int)ld_out, C, n, st);
+      break;
+    case CCX_SPEAKER_LSTM: {
+      const std::vector<bf16_t> wp = pack_whh(d->whh_host, d->whh_host + 512 * 128);
+      bf16_t* whh = nullptr;
+      SP_HIP(sc.upload(&whh, wp.data(), wp.size()));
+      rc = launch_lstm(ctx, (const float*)d->in, whh, in_off, frames, n, (bf16_t*)d->out, st);
+      break;
+    }
+    default:
+      rc = launch_activation(ctx, (const float*)d->in, (int)ld_in, (float*)d->out, C, d->rows, d->powerset, st);
+  }
+  SP_HIP(hipStreamSynchronize(st));      // the scratch is freed on return
+  return rc;
 }
 
 }  // extern "C"

@@ -684,6 +684,47 @@ int ccx_speaker_embed(ccx_speaker* s, const float* wav_dev, const int64_t* offse
 int ccx_speaker_segment(ccx_speaker* s, const float* wav_dev, const int64_t* offsets, const int* n_samples, int n,
                         float* out_dev, int64_t out_capacity_rows, int* frames_out, void* stream);
 
+/* ---- the SincNet / x-vector / PyanNet kernels on their own (csrc/speaker.hip through the launch functions and weight packers
+ *      ccx_speaker_embed and ccx_speaker_segment use; for kernel parity tests, the product path does not call this; no counterpart
+ *      in the reference).  Device pointers come with the element count of the buffer's own type; crop tables, the sinc filters and
+ *      W_hh are HOST arrays.  Everything the kernels assume is checked on the host before anything is launched; a violation returns
+ *      CCX_ERR_ARG (1) with a message naming "ccx_speaker_op" and the field.  Synchronises the stream.
+ *      Ragged rows: crop i reads frames of `in` from row in_off[i] and writes frames[i] rows of `out` from row out_off[i]. */
+#define CCX_SPEAKER_WAV_STATS 0   /* wav_stats_kernel: wav crops -> out f32 [n][4] = (a, c, mean_hi, mean_lo): the norm is a x + c, the mean mean_hi + mean_lo */
+#define CCX_SPEAKER_SINC_POOL 1   /* wav_stats_kernel + sinc_conv_pool_kernel: wav crops -> out f32 [.][80], frames[i] pooled frames */
+#define CCX_SPEAKER_INORM 2       /* inorm_partial_kernel + inorm_apply_kernel<pool>: in f32 [.][ld_in] -> out bf16 [.][ld_out] */
+#define CCX_SPEAKER_STATS_POOL 3  /* stats_pool_kernel: in bf16 [.][ld_in] -> out bf16 [n][ld_out] (mean at [0, C) || std at [C, 2 C)) */
+#define CCX_SPEAKER_LSTM 4        /* lstm_recurrent_kernel: in = gx f32 [.][1024] (fwd | rev gates i|f|g|o) -> out = h bf16 [.][256] */
+#define CCX_SPEAKER_ACTIVATION 5  /* seg_activation_kernel: in = logits f32 [rows][ld_in] -> out f32 [rows][C] */
+
+typedef struct ccx_speaker_desc {
+  int n;                        /* ops 0-4: crops (sequences), 1..65535 */
+  /* ops 0, 1: wav f32 (4-byte aligned); HOST crop_off (samples, >= 0) and crop_len (>= 251) [n]; the waveform norm's weight and bias */
+  const void* wav; int64_t wav_elems; const int64_t* crop_off; const int* crop_len; float norm_w, norm_b;
+  /* op 1: HOST sinc filters f32 [80][251], packed into MFMA fragments as the loader does */
+  const float* filters_host;
+  /* ops 1-4: HOST frames [n].  op 1: pooled frames written, 1 .. ((crop_len - 251) / 10 + 1) / 3.  op 2: frames after the pool
+   * (pool x frames input rows are read).  op 3: frames pooled over (>= 2 without weights).  op 4: steps of the sequence. */
+  const int* frames;
+  /* ops 2-5: in, with ld_in elements per row; ops 2-4: HOST in_off [n], the first input row of each crop */
+  const void* in; int64_t in_elems; int64_t ld_in; const int* in_off;
+  /* all ops: out.  ops 1, 2, 4: HOST out_off [n], the first output row of each crop (op 1: rows are 80 wide; op 4: out_off must
+   * equal in_off).  ops 2, 3: ld_out elements per row (op 2: columns [C, ld_out) are written as zeros). */
+  void* out; int64_t out_elems; int64_t ld_out; const int* out_off;
+  /* op 2: pool 1 or 3 (max over 3 input rows first); C live channels, a multiple of 4, <= ld_in, <= ld_out <= 128; ld_in and ld_out
+   * multiples of 4; gamma / beta f32 [C] (device).  ops 3, 5: C columns. */
+  int pool, C; const void* gamma; int64_t gamma_elems; const void* beta; int64_t beta_elems;
+  /* op 3: weights f32 (device, may be NULL: unbiased std); HOST w_off / w_len [n]: w_len[i] >= 1 weights at w_off[i], nearest-
+   * interpolated to the crop's frames */
+  const void* weights; int64_t weights_elems; const int64_t* w_off; const int* w_len;
+  /* op 4: HOST whh f32 [2][512][128] (fwd | rev, rows i|f|g|o), rounded to bf16 as the loader does */
+  const float* whh_host;
+  /* op 5: rows; powerset != 0 -> log-softmax over the C columns, else sigmoid */
+  int rows, powerset;
+} ccx_speaker_desc;
+
+int ccx_speaker_op(ccx_ctx* ctx, int op, const ccx_speaker_desc* desc, void* stream);
+
 /* ---- ECAPA-TDNN speaker embedder (speechbrain/spkrec-ecapa-voxceleb, 192-d): an alternative to the x-vector above for
  *      self.embedding_model (reference back/api.py:776-780), called with the same crops (back/api.py:869-872, 961-1006).
  *      The reference itself does not use it; it is selected with load_models(embedding="ecapa"). ------------------------- */
