@@ -129,6 +129,19 @@ class DecHistoryDesc(C.Structure):
         ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int)]
 
 
+class DecodeBiasOptions(C.Structure):
+    """ccx_decode_bias_options (include/ccx.h): a sequence-bias table as three HOST arrays; all zero: off."""
+    _fields_ = [("n_entries", C.c_int), ("offsets", C.POINTER(C.c_int)), ("ids", C.POINTER(C.c_int)), ("bias", C.POINTER(C.c_float))]
+
+
+class DecBiasDesc(C.Structure):
+    """ccx_dec_bias_desc (include/ccx.h): one launch of the sequence-bias kernel on its own."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("logits_elems", C.c_int64), ("ld", C.c_int64), ("n_vocab", C.c_int), ("rows", C.c_int),
+        ("state", C.POINTER(DecSeqState)), ("hist", C.POINTER(C.c_int)), ("sample_len", C.c_int), ("text_end", C.c_int),
+        ("table", DecodeBiasOptions)]
+
+
 class BeamTrace(C.Structure):
     """ccx_beam_trace (include/ccx.h): host buffers a traced ccx_whisper_decode_beam fills."""
     _fields_ = [("n_steps", C.c_int), ("cand_id", C.POINTER(C.c_int32)), ("cand_lp", C.POINTER(C.c_float)),
@@ -303,6 +316,10 @@ PROTOTYPES = {
     "ccx_whisper_set_history_options": (_i, [_vp, C.POINTER(DecodeHistoryOptions)]),
     "ccx_whisper_history_graph_count": (_i, [_vp]),
     "ccx_dec_history_step": (_i, [_vp, C.POINTER(DecHistoryDesc), _vp]),
+    "ccx_decode_bias_options_default": (None, [C.POINTER(DecodeBiasOptions)]),
+    "ccx_whisper_set_bias_options": (_i, [_vp, C.POINTER(DecodeBiasOptions)]),
+    "ccx_whisper_bias_graph_count": (_i, [_vp]),
+    "ccx_dec_bias_step": (_i, [_vp, C.POINTER(DecBiasDesc), _vp]),
     "ccx_whisper_set_mel": (_i, [_vp, _vp, _i, _vp]),
     "ccx_whisper_encode": (_i, [_vp, _i, _vp, _vp]),
     "ccx_whisper_decoder_logits": (_i, [_vp, _i32p, _i, _i, _vp, _vp]),

@@ -138,6 +138,42 @@ struct DecHistoryParams {
   float penalty; int ngram;            // 1.0 / 0: off
 };
 int ccx_launch_dec_history(ccx_ctx* ctx, const DecHistoryParams& p, int rows, hipStream_t stream);
+
+// The sequence bias (dec_bias.hip: sequence_bias / bad_words_ids / hotwords; the rule: include/ccx.h ccx_decode_bias_options), applied
+// to the fp32 logit rows in place BEFORE the history rules: one block per row; rows that are done or in the prompt phase are not
+// touched.  `tab` is the compiled table, kBiasTabInts ints of device memory at fixed offsets (floats as their bits):
+//   [kBiasHdr ..)   header: {n1, n_keys, n_groups, n_multi}; the kernel reads every count from here, so a captured launch serves
+//                   every table uploaded later
+//   [kBiasL1Tgt ..) / [kBiasL1Bias ..)   the n1 distinct targets of the length-1 entries, ascending, and their sums b1
+//   [kBiasKey ..)   the n_keys distinct LAST context ids of the longer entries, ascending;  [kBiasKeyOff ..) n_keys + 1 group offsets
+//   [kBiasGrpTgt ..) one target per group (a group: one (key, target) pair);  [kBiasGrpOff ..) n_groups + 1 entry offsets
+//   [kBiasEntLen ..) / [kBiasEntCtx ..) / [kBiasEntBias ..)   per entry, table order inside a group: context length L - 1, where its
+//                   context starts in the pool, bias;  [kBiasCtx ..) the pool of context ids
+constexpr int kBiasMaxEntries = 8192, kBiasMaxIds = 65536, kBiasMaxLen = 32;      // CCX_BIAS_MAX_* (static_assert in dec_bias.hip)
+constexpr int kBiasHdr = 0;
+constexpr int kBiasL1Tgt = 8;
+constexpr int kBiasL1Bias = kBiasL1Tgt + kBiasMaxEntries;
+constexpr int kBiasKey = kBiasL1Bias + kBiasMaxEntries;
+constexpr int kBiasKeyOff = kBiasKey + kBiasMaxEntries;
+constexpr int kBiasGrpTgt = kBiasKeyOff + kBiasMaxEntries + 8;
+constexpr int kBiasGrpOff = kBiasGrpTgt + kBiasMaxEntries;
+constexpr int kBiasEntLen = kBiasGrpOff + kBiasMaxEntries + 8;
+constexpr int kBiasEntCtx = kBiasEntLen + kBiasMaxEntries;
+constexpr int kBiasEntBias = kBiasEntCtx + kBiasMaxEntries;
+constexpr int kBiasCtx = kBiasEntBias + kBiasMaxEntries;
+constexpr int kBiasTabInts = kBiasCtx + kBiasMaxIds;
+struct DecBiasParams {
+  float* logits; long ld;              // [rows][ld], edited in place
+  const DecSeqState* state;            // [rows]
+  const int* gen; int sample_len;
+  int text_end;
+  const int* tab;                      // [kBiasTabInts]
+};
+int ccx_launch_dec_bias(ccx_ctx* ctx, const DecBiasParams& p, int rows, hipStream_t stream);
+// Checks a caller's table and compiles it into `tab` (kBiasTabInts ints, host); `who` names the entry point in the messages.
+// has_len1: whether any length-1 entry exists.  An empty table (opts null or n_entries == 0) compiles to a header of zeros.
+int ccx_compile_bias_table(ccx_ctx* ctx, const char* who, const ccx_decode_bias_options* opts, int n_vocab, int text_end,
+                           std::vector<int>& tab, bool* has_len1);
 int ccx_launch_dec_embed(ccx_ctx* ctx, const float* tok_emb, const float* pos_emb, const int* cur_tok, const int* pos,
                          float* x, int B, int D, hipStream_t stream);
 // Softmax of logit rows over the ids [lo, hi) only (dec_probs.hip; everything else counts as -inf): argmax[row] (lowest id on equal

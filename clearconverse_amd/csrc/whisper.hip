@@ -49,7 +49,8 @@ struct DecLayer {
 // The mode of one decoder step (or prefill pass) of one lane, as a value -- and, being everything a captured step bakes in, the key
 // of the step-graph cache.  Invariant: a field dec_step / dec_head branches on or passes by value is in the plan; anything else
 // they read from the instance is constant between ccx_whisper_set_rules calls (weights, workspaces, dimensions, rule ids) -- the
-// options' mask between the ccx_whisper_set_decode_options calls that change it, which drop the graphs of the plans that read it -- and
+// options' mask between the ccx_whisper_set_decode_options calls that change it, which drop the graphs of the plans that read it; the
+// bias table's buffer keeps its address and the kernel reads its CONTENT, counts included, on the device, so no graph depends on it -- and
 // what is neither (logits, counters, streams, per-call buffers) comes in through StepIo.
 struct StepPlan {
   int b0, B;                      // the lane's rows [b0, b0 + B)
@@ -75,14 +76,17 @@ struct StepPlan {
   // runs in front of the select / beam kernels when either is set
   int hist_ngram;                 // no_repeat_ngram_size
   int hist_pen_bits;              // repetition_penalty's float bits (0 when it is 1.0)
+  // a sequence-bias table is set (ccx_whisper_set_bias_options; 0 in a default decode): dec_bias_kernel runs in front of
+  // dec_history_kernel and the select / beam kernels.  The table itself is not in the plan: the kernel reads it through its header.
+  int bias_on;
   auto tie() const {
     return std::tie(b0, B, sample_len, max_prompt, select, sampling, cross_stream, cross_lds_pad, xs_active, lnfree, xs_fuse_q, fuse_cross_q,
                     xs_full_lines, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows, opt_mask, no_ts, sup_blank,
-                    max_init_ts, hist_ngram, hist_pen_bits);
+                    max_init_ts, hist_ngram, hist_pen_bits, bias_on);
   }
   bool operator<(const StepPlan& o) const { return tie() < o.tie(); }
 };
-static_assert(sizeof(StepPlan) == 26 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 26,
+static_assert(sizeof(StepPlan) == 27 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 27,
               "StepPlan: ints only, and every one of them in tie()");
 
 }  // namespace
@@ -129,6 +133,10 @@ struct ccx_whisper {
   std::vector<unsigned char> opt_mask_host; // what opt_mask holds: a call that changes nothing keeps the option graphs
   // the call's history rules (ccx_whisper_set_history_options); {1.0, 0}: off, the plans and launches of a default decode
   ccx_decode_history_options hist{1.0f, 0};
+  // the call's sequence-bias table (ccx_whisper_set_bias_options), compiled (decoder.h: kBiasTabInts ints); off: the plans and
+  // launches of a default decode.  The buffer is allocated at the first non-empty table and keeps its address.
+  bool bias_on = false;
+  int* bias_tab = nullptr;
 
   // workspaces (encoder)
   float* lm_raw = nullptr; unsigned int* lm_max = nullptr; int *lm_n = nullptr, *lm_seek = nullptr, *lm_seg = nullptr;
@@ -409,6 +417,7 @@ int ccx_whisper_set_rules(ccx_whisper* w, const ccx_decode_rules* r) {
   w->opts = ccx_decode_options{0, 1, -2, 0, nullptr};   // the options name ids of the rules they were set under
   w->opts_on = false;
   w->hist = ccx_decode_history_options{1.0f, 0};
+  w->bias_on = false;  // the table's targets were checked against the eot of the rules it was set under
   drop_graphs(w);      // captured step graphs bake the rule ids into the select kernel's parameters
   return CCX_OK;
 }
@@ -468,6 +477,27 @@ int ccx_whisper_history_graph_count(ccx_whisper* w) {
   if (!w) return -1;
   int n = 0;
   for (auto& g : w->graphs) n += (g.first.hist_ngram || g.first.hist_pen_bits) ? 1 : 0;
+  return n;
+}
+
+int ccx_whisper_set_bias_options(ccx_whisper* w, const ccx_decode_bias_options* opts) {
+  if (!w) return CCX_ERR_ARG;
+  ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, w->rules_set, "ccx_whisper_set_bias_options: the rules are not set (ccx_whisper_set_rules)");
+  if (!opts || opts->n_entries == 0) { w->bias_on = false; return CCX_OK; }
+  std::vector<int> tab;
+  CCX_TRY(ccx_compile_bias_table(ctx, "ccx_whisper_set_bias_options", opts, w->d.n_vocab, w->rules.eot, tab, nullptr));
+  if (!w->bias_tab) CCX_TRY(w->store.alloc(&w->bias_tab, (size_t)kBiasTabInts, false));
+  // no decode is in flight between two calls; captured bias plans read the new table through the same buffer and its header
+  CCX_HIP(ctx, hipMemcpy(w->bias_tab, tab.data(), (size_t)kBiasTabInts * sizeof(int), hipMemcpyHostToDevice));
+  w->bias_on = true;
+  return CCX_OK;
+}
+
+int ccx_whisper_bias_graph_count(ccx_whisper* w) {
+  if (!w) return -1;
+  int n = 0;
+  for (auto& g : w->graphs) n += g.first.bias_on ? 1 : 0;
   return n;
 }
 
@@ -1011,6 +1041,15 @@ int dec_head(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
     memset(&gp, 0, sizeof(gp));
     gp.A = w->dxn + ro * D; gp.lda = D; gp.W = w->tok_emb_rm; gp.ldw = D; gp.M = B; gp.N = d.n_vocab; gp.K = D; gp.out = io.logits; gp.ldo = io.ld;
     CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, gp, io.stream));
+  }
+  if (p.select && p.bias_on) {
+    // the sequence bias edits the logit rows in place before the history rules and every filter (beam rows: the history that follows
+    // the hypothesis)
+    DecBiasParams bp;
+    memset(&bp, 0, sizeof(bp));
+    bp.logits = io.logits; bp.ld = io.ld; bp.state = w->state + b0; bp.gen = w->gen + ro * p.sample_len; bp.sample_len = p.sample_len;
+    bp.text_end = w->rules.eot; bp.tab = w->bias_tab;
+    CCX_TRY(ccx_launch_dec_bias(ctx, bp, B, io.stream));
   }
   if (p.select && (p.hist_ngram || p.hist_pen_bits)) {
     // the history rules edit the logit rows in place before any filter reads them (beam rows: the history that follows the hypothesis)
@@ -2020,6 +2059,7 @@ int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
   // the history rules: {1.0, 0}, set or not, is the default plan
   base.hist_ngram = w->hist.no_repeat_ngram_size;
   if (w->hist.repetition_penalty != 1.0f) memcpy(&base.hist_pen_bits, &w->hist.repetition_penalty, 4);
+  base.bias_on = w->bias_on ? 1 : 0;      // no table, set or not, is the default plan
   read_chain_switches(base);
   CCX_TRY(select_cross_path(w, base, stream, win ? n_windows : -1));
   if (win) CCX_TRY(upload_row_map(w, win, sids, B, stream));

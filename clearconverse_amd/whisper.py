@@ -342,6 +342,7 @@ class WhisperModel:
     beam_search = False               # opt-in too
     decoding_options = False          # and so are upstream's remaining per-call decoding options
     repetition_control = False        # and repetition_penalty / no_repeat_ngram_size
+    contextual_bias = False           # and sequence_bias / bad_words_ids / hotwords
 
     def __init__(self, dims: WhisperDims, state_dict: Dict[str, torch.Tensor], max_batch: int = 8,
                  device: int = 0, rules: Optional[DecodeRules] = None, tokenizer=None,
@@ -349,8 +350,15 @@ class WhisperModel:
                  share_encoder_scratch_with: Optional["WhisperModel"] = None, word_alignment: bool = False,
                  alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False,
                  temperature_fallback: bool = False, beam_search: bool = False, decoding_options: bool = False,
-                 repetition_control: bool = False):
-        """repetition_control (default False: `repetition_penalty` and `no_repeat_ngram_size` are accepted and ignored): with it,
+                 repetition_control: bool = False, contextual_bias: bool = False):
+        """contextual_bias (default False: `sequence_bias`, `bad_words_ids`, `hotwords` and `hotword_boost` are accepted and ignored):
+        with it, `transcribe` / `transcribe_batch` and `decode`, `decode_rows`, `decode_beam` honour them (Hugging Face's names and
+        forms for the first two, faster-whisper's name for hotwords; the rule is this project's, include/ccx.h
+        ccx_decode_bias_options; parity unpinned): a bias is added to the logit of the last id of a sequence whenever the tokens THIS
+        decode has just sampled end in the ids before it (no prompt, SOT sequence or prefix; a target >= eot is refused); a bad word is
+        a bias of -inf; a hotword boosts its first token always and each next one once the ones before it were sampled
+        (`decode_bias.compile_bias_table`).  One kernel more per step (csrc/dec_bias.hip) and only on calls that give a table.
+        repetition_control (default False: `repetition_penalty` and `no_repeat_ngram_size` are accepted and ignored): with it,
         `transcribe` / `transcribe_batch` and `decode`, `decode_rows`, `decode_beam` honour them (the names CTranslate2 /
         faster-whisper and Hugging Face use; the rule is this project's, include/ccx.h ccx_decode_history_options; parity unpinned):
         the logit of every text id a window has sampled so far is divided (> 0) or multiplied (<= 0) by repetition_penalty, and an id
@@ -405,6 +413,7 @@ class WhisperModel:
         self.beam_search = bool(beam_search)
         self.decoding_options = bool(decoding_options)
         self.repetition_control = bool(repetition_control)
+        self.contextual_bias = bool(contextual_bias)
         if alignment_heads is None:
             alignment_heads = [(l, h) for l in range(dims.n_text_layer // 2, dims.n_text_layer) for h in range(dims.n_text_head)]
         self.alignment_heads = [(int(l), int(h)) for l, h in alignment_heads]
@@ -525,6 +534,43 @@ class WhisperModel:
         finally:
             self.reset_history_options()
 
+    def compile_bias_options(self, sequence_bias=None, bad_words_ids=None, hotwords=None, hotword_boost=None):
+        """`decode_bias.compile_bias_table` with this model's tokenizer, eot and vocabulary -> (offsets, ids, bias)"""
+        from .decode_bias import compile_bias_table
+        return compile_bias_table(sequence_bias, bad_words_ids, hotwords, hotword_boost, encode=self.tokenizer.encode,
+                                  eot=self.rules.eot, n_vocab=self.dims.n_vocab)
+
+    def set_bias_options(self, sequence_bias=None, bad_words_ids=None, hotwords=None, hotword_boost=None):
+        """ccx_whisper_set_bias_options (sticky, like the rules; `set_rules` resets it); nothing given: off, the default decode"""
+        self._set_bias_table(*self.compile_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost))
+
+    def _set_bias_table(self, offsets, ids, bias):
+        """a compiled table (`compile_bias_options`) -> ccx_whisper_set_bias_options, which copies the arrays"""
+        o = _lib.DecodeBiasOptions(len(bias), offsets.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data_as(C.POINTER(C.c_int)),
+                                   bias.ctypes.data_as(C.POINTER(C.c_float)))
+        self.ctx.check(self.lib.ccx_whisper_set_bias_options(self.handle, C.byref(o)), "ccx_whisper_set_bias_options")
+
+    def reset_bias_options(self):
+        self.ctx.check(self.lib.ccx_whisper_set_bias_options(self.handle, None), "ccx_whisper_set_bias_options")
+
+    def bias_graph_count(self) -> int:
+        """captured step graphs of bias plans (ccx_whisper_bias_graph_count)"""
+        return int(self.lib.ccx_whisper_bias_graph_count(self.handle))
+
+    def _with_bias_options(self, sequence_bias, bad_words_ids, hotwords, hotword_boost, fn):
+        """`fn()` under the call's sequence_bias / bad_words_ids / hotwords; no table is set afterwards.  Without the opt-in the
+        arguments are ignored; with none of the three given (or an empty table) nothing is set."""
+        if not self.contextual_bias:
+            return fn()
+        table = self.compile_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost)
+        if len(table[2]) == 0:
+            return fn()
+        self._set_bias_table(*table)
+        try:
+            return fn()
+        finally:
+            self.reset_bias_options()
+
     def set_prefix_len(self, n_prefix: int):
         """prompt tokens behind the SOT sequence (a decode with a prefix): ccx_whisper_set_prefix_len"""
         self.ctx.check(self.lib.ccx_whisper_set_prefix_len(self.handle, int(n_prefix)), "ccx_whisper_set_prefix_len")
@@ -613,7 +659,8 @@ class WhisperModel:
         return self.decode(prompts, sample_len, temperature=0.0)
 
     def decode(self, prompts: Sequence[Sequence[int]], sample_len: Optional[int] = None, temperature: float = 0.0,
-               seed: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, **decoding) -> List[dict]:
+               seed: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None,
+               bad_words_ids=None, hotwords=None, hotword_boost=None, **decoding) -> List[dict]:
         """DecodingTask.run over the currently encoded windows; prompts[b] are the full initial tokens
         (sot_prev + prompt + sot).  temperature 0: argmax.  temperature > 0: one Categorical(logits / T) sample per
         step (decoding.py::GreedyDecoder.update), drawn on the device from Philox noise keyed by
@@ -623,7 +670,11 @@ class WhisperModel:
         **decoding (decoding_options instances; ignored otherwise): without_timestamps, suppress_blank, suppress_tokens,
         max_initial_timestamp for this call (`_with_call_options`); the prompts, the SOT tail, the prefix length and sample_len stay
         the caller's.  repetition_penalty / no_repeat_ngram_size (repetition_control instances; ignored otherwise): this call's
-        history rules (`_with_history_options`)."""
+        history rules (`_with_history_options`).  sequence_bias / bad_words_ids / hotwords / hotword_boost (contextual_bias instances;
+        ignored otherwise): this call's bias table (`_with_bias_options`), applied before the history rules."""
+        if sequence_bias is not None or bad_words_ids is not None or hotwords is not None:
+            return self._with_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost, lambda: self.decode(
+                prompts, sample_len, temperature, seed, repetition_penalty, no_repeat_ngram_size, **decoding))
         if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
             return self._with_history_options(repetition_penalty, no_repeat_ngram_size,
                                               lambda: self.decode(prompts, sample_len, temperature, seed, **decoding))
@@ -656,12 +707,17 @@ class WhisperModel:
 
     def decode_rows(self, prompts: Sequence[Sequence[int]], windows: Sequence[int], stream_ids: Optional[Sequence[int]] = None,
                     sample_len: Optional[int] = None, temperature: float = 0.0, seed: int = 0, n_windows: Optional[int] = None,
-                    repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, **decoding) -> List[dict]:
+                    repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None,
+                    hotwords=None, hotword_boost=None, **decoding) -> List[dict]:
         """`decode` for len(prompts) <= max_batch rows over the currently encoded windows (ccx_whisper_decode_rows): row r decodes
         window windows[r] -- entries may repeat (best_of), need not be monotone, and windows may go unused (a fallback round decodes
         only the failing ones).  stream_ids[r]: the row's noise stream at temperature > 0 (None: r), so that its draws do not depend on
         the rows it shares the call with.  n_windows: how many windows are encoded (default: max(windows) + 1).  repetition_penalty,
-        no_repeat_ngram_size, **decoding: as `decode`."""
+        no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost, **decoding: as `decode`."""
+        if sequence_bias is not None or bad_words_ids is not None or hotwords is not None:
+            return self._with_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost, lambda: self.decode_rows(
+                prompts, windows, stream_ids, sample_len, temperature, seed, n_windows, repetition_penalty, no_repeat_ngram_size,
+                **decoding))
         if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
             return self._with_history_options(repetition_penalty, no_repeat_ngram_size, lambda: self.decode_rows(
                 prompts, windows, stream_ids, sample_len, temperature, seed, n_windows, **decoding))
@@ -700,7 +756,8 @@ class WhisperModel:
 
     def decode_beam(self, prompts: Sequence[Sequence[int]], beam_size: int, patience: Optional[float] = None,
                     sample_len: Optional[int] = None, windows: Optional[Sequence[int]] = None, n_windows: Optional[int] = None,
-                    trace: bool = False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, **decoding):
+                    trace: bool = False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None,
+                    bad_words_ids=None, hotwords=None, hotword_boost=None, **decoding):
         """Beam search at temperature 0 over the currently encoded windows (ccx_whisper_decode_beam) [UPSTREAM-RECALL:
         decoding.py::BeamSearchDecoder]: prompts[g] is decoded on window windows[g] (None: window g) by beam_size rows that share the
         window's encoder output; len(prompts) * beam_size <= max_batch.  patience (None: 1.0): a window is complete once
@@ -709,7 +766,12 @@ class WhisperModel:
         sum_logprob, avg_logprob, no_speech_prob (the window's), cross_path.  The ranker (`fallback.rank_candidates`) picks among them.
         trace=True (a test aid; the steps then run eagerly): -> (results, dict of numpy arrays cand_id / cand_lp [steps, rows,
         beam_size + 1], tok / parent / score [steps, rows]; rows = prompt-major; -1 / NaN where a window no longer stepped).
-        repetition_penalty, no_repeat_ngram_size, **decoding: as `decode`; every row reads the history that follows its hypothesis."""
+        repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost, **decoding: as `decode`; every
+        row reads the history that follows its hypothesis."""
+        if sequence_bias is not None or bad_words_ids is not None or hotwords is not None:
+            return self._with_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost, lambda: self.decode_beam(
+                prompts, beam_size, patience, sample_len, windows, n_windows, trace, repetition_penalty, no_repeat_ngram_size,
+                **decoding))
         if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
             return self._with_history_options(repetition_penalty, no_repeat_ngram_size, lambda: self.decode_beam(
                 prompts, beam_size, patience, sample_len, windows, n_windows, trace, **decoding))
@@ -888,7 +950,8 @@ class WhisperModel:
                    length_penalty: Optional[float] = None, without_timestamps: bool = False, prefix=None,
                    suppress_blank: bool = True, suppress_tokens="-1", max_initial_timestamp: Optional[float] = 1.0,
                    sample_len: Optional[int] = None, clip_timestamps="0", carry_initial_prompt: bool = False,
-                   repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, **_ignored):
+                   repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None,
+                   hotwords=None, hotword_boost=None, **_ignored):
         """One clip, same signature as whisper.transcribe as the reference uses it.  temperature 0 is the
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
@@ -911,6 +974,8 @@ class WhisperModel:
         max_initial_timestamp, sample_len, clip_timestamps and carry_initial_prompt are honoured (see `transcribe_batch`); otherwise
         they are accepted and ignored.
         On an instance built with `repetition_control=True`: repetition_penalty and no_repeat_ngram_size are honoured (see
+        `transcribe_batch`); otherwise they are accepted and ignored.
+        On an instance built with `contextual_bias=True`: sequence_bias, bad_words_ids, hotwords and hotword_boost are honoured (see
         `transcribe_batch`); otherwise they are accepted and ignored."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
                                      compression_ratio_threshold=compression_ratio_threshold, best_of=best_of,
@@ -922,7 +987,9 @@ class WhisperModel:
                                      prefixes=[prefix], suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
                                      max_initial_timestamp=max_initial_timestamp, sample_len=sample_len,
                                      clip_timestamps=clip_timestamps, carry_initial_prompt=carry_initial_prompt,
-                                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)[0]
+                                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                     sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotwords=hotwords,
+                                     hotword_boost=hotword_boost)[0]
 
     def transcribe_batch(self, audios: Sequence, initial_prompts: Optional[Sequence[Optional[str]]] = None,
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
@@ -935,7 +1002,8 @@ class WhisperModel:
                          prefixes: Optional[Sequence] = None, suppress_blank: bool = True, suppress_tokens="-1",
                          max_initial_timestamp: Optional[float] = 1.0, sample_len: Optional[int] = None, clip_timestamps="0",
                          carry_initial_prompt: bool = False, repetition_penalty: float = 1.0,
-                         no_repeat_ngram_size: int = 0) -> List[dict]:
+                         no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None, hotwords=None,
+                         hotword_boost=None) -> List[dict]:
         """Independent clips decoded together (each window of each clip is one sequence of a batch).
         languages[i] (multilingual models): the clip's language code or name; None: detected on the clip's first window, after its
         group's `encode` and before its `decode` [UPSTREAM-RECALL: transcribe.py, `if decode_options.get("language") is None`].
@@ -971,7 +1039,16 @@ class WhisperModel:
         every window of the call -- every round of a fallback walk, every best_of row and every beam row gets them (one
         ccx_whisper_set_history_options per call, the defaults back when it returns); a value outside its range raises ValueError.
         A window's history is what that window's decode sampled: nothing carries over from the prompt or from earlier windows.
-        Without the opt-in both are ignored."""
+        Without the opt-in both are ignored.
+        contextual_bias instances: sequence_bias (dict tuple -> float, or list of [ids, float]), bad_words_ids (list of id lists) and
+        hotwords (a phrase or a list of them, with hotword_boost, which has no default) are compiled into one table
+        (`decode_bias.compile_bias_table`) that holds for every window of the call and every round of a fallback walk (one
+        ccx_whisper_set_bias_options per call, no table set when it returns); what the compile refuses raises ValueError.  A window
+        matches over what that window's decode sampled only.  Without the opt-in all four are ignored."""
+        bias_table = None
+        if self.contextual_bias and (sequence_bias is not None or bad_words_ids is not None or hotwords is not None):
+            bias_table = self.compile_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost)
+        bias_on = bias_table is not None and len(bias_table[2]) > 0
         hist_on = False
         if self.repetition_control:
             hist_p, hist_n = self.check_history_options(repetition_penalty, no_repeat_ngram_size)
@@ -1072,6 +1149,8 @@ class WhisperModel:
             self.set_prefix_len(n_prefix)
         if hist_on:
             self.set_history_options(hist_p, hist_n)
+        if bias_on:
+            self._set_bias_table(*bias_table)
         try:
             while True:
                 active = [i for i in range(n) if state[i].active()]
@@ -1121,6 +1200,8 @@ class WhisperModel:
                     for i, r in zip(grp, results):
                         state[i].advance(r, temperature)
         finally:
+            if bias_on:
+                self.reset_bias_options()
             if hist_on:
                 self.reset_history_options()
             if dev_opts:

@@ -238,6 +238,57 @@ int ccx_whisper_set_history_options(ccx_whisper* w, const ccx_decode_history_opt
 /* Captured step graphs of history plans the instance holds (a test aid, like ccx_whisper_graph_count); -1 for a NULL handle. */
 int ccx_whisper_history_graph_count(ccx_whisper* w);
 
+/* Vocabulary control per call: sequence_bias, and through it bad_words_ids and hotwords (the rule is ours, in the form of Hugging
+ * Face's SequenceBiasLogitsProcessor and NoBadWordsLogitsProcessor; parity unpinned; restated in tests/bias_reference.py).  The
+ * single-token suppress masks cannot express it: the bias on the last id of a phrase depends on what the row has just sampled.
+ *   TABLE.  An ordered list of n_entries entries (ids[0 .. L), bias): entry e holds ids[offsets[e] .. offsets[e + 1]) and bias[e].
+ *     1 <= L <= CCX_BIAS_MAX_LEN; every id in [0, n_vocab); the TARGET ids[L - 1] is < E = rules.eot (ids >= E -- eot, the specials,
+ *     the timestamps -- are never edited, as with the history rules; context ids may be any id); bias is finite or -inf (+inf and NaN
+ *     are refused).  bad_words_ids are entries with bias -inf.  At most CCX_BIAS_MAX_ENTRIES entries and CCX_BIAS_MAX_IDS ids.
+ *   HISTORY.  For one row in the sampling phase, H = the m = n_gen ids THIS decode has sampled: the H of the history rules, without
+ *     the prompt, the SOT sequence or a prefix; for beam rows the history that follows the hypothesis.
+ *   TERMS.  b1[v] = the fp32 sum, in table order, of the length-1 entries with target v.  S[v] = the fp32 sum, in table order, of
+ *     the entries with L >= 2, target v, L - 1 <= m and H[m - L + 1 : m] == ids[0 : L - 1].
+ *   EDIT.  logits[v] = (logits[v] + b1[v]) + S[v] in fp32.  A term that does not exist is skipped, not added as zero; each term
+ *     lands once per id.  Rows that are done or still in the prompt phase are not touched.
+ *   ORDER.  The edit comes BEFORE the history rules (ccx_decode_history_options), the order of transformers' _get_logits_processor
+ *     (sequence bias, repetition penalty, no-repeat n-gram; a -inf commutes with all of them), and so before SuppressBlank,
+ *     SuppressTokens, ApplyTimestampRules, the temperature and the sampler; sum_logprob is taken from the edited logits.
+ *   DEVIATION from HF, stated: HF matches over prompt + generated ids and exempts no id; and the installed processor skips an entry
+ *     whose L ids outnumber its input_ids, so an entry whose context is the WHOLE history (L - 1 == m) never fires there; here it
+ *     does (a bad bigram holds from the second sampled token on).
+ *   CONSEQUENCE, stated: with length-1 entries the first sampled step's row is edited, and where no_speech_prob is read from that
+ *     row (<|startoftranscript|> is the prompt's last token: no SOT tail, no prefix, n_vocab a multiple of 4) it is the softmax of the
+ *     EDITED row.  Without a length-1 entry, and wherever it is read at an earlier prompt position, it is bit-identical to an unbiased
+ *     decode's.
+ * csrc/dec_bias.hip: dec_bias_kernel, one block per row between the logits GEMM and dec_history_kernel / the select / beam top-k
+ * kernel; no atomics, so the sums' order and bits are fixed.  The table is compiled on the host (a stable sort: length-1 entries by
+ * target, the others by (last context id, target), the caller's order kept inside a group) into fixed-capacity device buffers the
+ * instance owns, allocated at the first non-empty table; the kernel reads every count from a small device header, so a captured
+ * step graph serves every later table.
+ * ccx_decode_bias_options_default fills zeros: off.  ccx_whisper_set_bias_options is sticky like ccx_whisper_set_history_options
+ * (NULL or n_entries == 0: off), needs the rules, is reset by ccx_whisper_set_rules, and is checked on the host: CCX_ERR_ARG (1)
+ * naming "ccx_whisper_set_bias_options" and the field for n_entries outside [0, CCX_BIAS_MAX_ENTRIES], NULL arrays, offsets that do
+ * not start at 0 or do not ascend, an entry length outside [1, CCX_BIAS_MAX_LEN], more than CCX_BIAS_MAX_IDS ids, an id outside
+ * [0, n_vocab), a target >= eot, a bias that is +inf or NaN, and length-1 entries of one target whose sum is.  All three arrays are
+ * HOST memory and are copied.  One step-plan field says whether a table is set: with none, set or not, a decode takes the plan, the
+ * launches and the graphs it always took; the graphs of bias plans live beside those of default, option and history plans.
+ * ccx_whisper_decode, _decode_greedy, _decode_rows and _decode_beam honour the setting; ccx_whisper_decoder_logits, _align and
+ * _align_probs do not. */
+#define CCX_BIAS_MAX_ENTRIES 8192
+#define CCX_BIAS_MAX_IDS 65536
+#define CCX_BIAS_MAX_LEN 32
+typedef struct ccx_decode_bias_options {
+  int n_entries;
+  const int* offsets;       /* HOST [n_entries + 1] */
+  const int* ids;           /* HOST [offsets[n_entries]] */
+  const float* bias;        /* HOST [n_entries] */
+} ccx_decode_bias_options;
+void ccx_decode_bias_options_default(ccx_decode_bias_options* opts);
+int ccx_whisper_set_bias_options(ccx_whisper* w, const ccx_decode_bias_options* opts);
+/* Captured step graphs of bias plans the instance holds (a test aid, like ccx_whisper_history_graph_count); -1 for a NULL handle. */
+int ccx_whisper_bias_graph_count(ccx_whisper* w);
+
 /* Log-mel of B clips (whisper.audio.log_mel_spectrogram + pad_or_trim to 3000 frames).
  * audio_dev: [B, stride] f32; n_samples / seek_frames: host int arrays (seek may be NULL = 0).
  * Fills the model's conv-stem input; if mel_out_dev != NULL also writes [B, n_mels, 3000] f32. */
@@ -441,6 +492,23 @@ typedef struct ccx_dec_history_desc {
   float repetition_penalty; int no_repeat_ngram_size;
 } ccx_dec_history_desc;
 int ccx_dec_history_step(ccx_ctx* ctx, const ccx_dec_history_desc* desc, void* stream);
+
+/* The sequence bias on its own (csrc/dec_bias.hip: dec_bias_kernel, one block per row; the rule: ccx_decode_bias_options above):
+ * edits the device logit rows in place for the rows in the sampling phase (done == 0 and pos >= prompt_len - 1) from their histories
+ * hist[row][0 : n_gen] under `table` (HOST arrays; an empty table edits nothing).  Checked on the host before the launch,
+ * CCX_ERR_ARG (1) naming "ccx_dec_bias_step" and the field: everything ccx_whisper_set_bias_options checks (with text_end in the
+ * place of eot), and 1 <= rows <= 65536, 1 <= n_vocab <= 53248, ld >= n_vocab, logits 4-byte aligned with logits_elems >=
+ * (rows - 1) * ld + n_vocab, 1 <= sample_len <= 2048, 0 <= text_end <= n_vocab, every n_gen in [0, sample_len] and done in {0, 1},
+ * history ids of live rows in [0, n_vocab).  Owns and frees its scratch; synchronises the stream. */
+typedef struct ccx_dec_bias_desc {
+  void* logits; int64_t logits_elems;         /* device f32 [rows][ld], in and out */
+  int64_t ld; int n_vocab; int rows;
+  const ccx_dec_seq_state* state;             /* HOST [rows] */
+  const int* hist; int sample_len;            /* HOST [rows][sample_len] */
+  int text_end;                               /* rules.eot: ids >= it are never a target */
+  ccx_decode_bias_options table;
+} ccx_dec_bias_desc;
+int ccx_dec_bias_step(ccx_ctx* ctx, const ccx_dec_bias_desc* desc, void* stream);
 
 /* Softmax of logit rows over an id range (csrc/dec_probs.hip: dec_token_probs_kernel, one block per row).  Over the ids [lo, hi) only --
  * everything else, the columns [n_vocab, ld) included, counts as -inf and is never looked at: argmax[row] (lowest id on equal values,
