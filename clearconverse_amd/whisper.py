@@ -4,15 +4,15 @@
 Only `.transcribe(audio_np, initial_prompt=, word_timestamps=, condition_on_previous_text=,
 temperature=)['text']` is consumed by the reference (back/api.py:1103, 1447, 1488); the same call
 shape is kept.  All arithmetic runs in libccx (hand-written HIP for gfx950) through the C ABI; this
-module holds only the window/segment bookkeeping of openai-whisper's transcribe.py
-[UPSTREAM-RECALL] and a batch entry point the reference lacks.
+module drives it and adds a batch entry point the reference lacks.  The window/segment bookkeeping of
+openai-whisper's transcribe.py [UPSTREAM-RECALL] is clearconverse_amd/window_loop.py (GPU-free).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-import string
 from dataclasses import asdict
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -21,320 +21,21 @@ from . import _lib, decoding_options, fallback
 from .audio import mel_filterbank
 from .tokenizer import DecodeRules, IdTokenizer, get_tokenizer
 from .weights import WhisperDims
+from .window_loop import (FRAMES_PER_SECOND, HOP, INPUT_STRIDE, N_FRAMES, SAMPLE_RATE, TIME_PRECISION,  # noqa: F401 (re-exported)
+                          WindowLoop, decode_cap, groups_by_cap, is_segment_anomaly, next_words_segment, word_anomaly_score)
 from .word_timing import add_word_timestamps, alignment_tokens, get_end
 
-N_FRAMES = 3000
-HOP = 160
-SAMPLE_RATE = 16000
 N_SAMPLES = 480000
-FRAMES_PER_SECOND = 100
-TIME_PRECISION = 0.02  # seconds per timestamp token
-INPUT_STRIDE = 2       # mel frames per encoder position
 CROSS_PATHS = {0: "kv16", 1: "kv_stream", 2: "xa_stream"}
 
 
-def decode_cap(prompt_len: int, n_text_ctx: int) -> int:
-    """Most tokens a sequence samples from `prompt_len` initial tokens [UPSTREAM-RECALL: decoding.py::_main_loop runs sample_len =
-    n_ctx // 2 steps and stops once `tokens.shape[-1] > n_ctx`]: min(n_ctx // 2, n_ctx + 1 - prompt_len) -- 224 for every English-only
-    prompt (at most 225 tokens), 222 for a full multilingual one (1 + 223 + 3 = 227).  No row is cut earlier than upstream cuts it, and
-    prompt_len + cap - 1 <= n_ctx, which is what ccx_whisper_decode asks for."""
-    return max(1, min(n_text_ctx // 2, n_text_ctx + 1 - int(prompt_len)))
-
-
-def groups_by_cap(active: Sequence[int], caps: Sequence[int], max_batch: int) -> List[tuple]:
-    """Decode groups of one pass over the active clips: `decode` takes ONE sample_len per call, so the clips are partitioned by
-    their cap (largest first, clip order kept inside a cap), then chunked by max_batch.  -> [(cap, [clip index, ...]), ...]."""
-    by_cap: Dict[int, List[int]] = {}
-    for i, c in zip(active, caps):
-        by_cap.setdefault(int(c), []).append(i)
-    out = []
-    for c in sorted(by_cap, reverse=True):
-        for c0 in range(0, len(by_cap[c]), max_batch):
-            out.append((c, by_cap[c][c0:c0 + max_batch]))
-    return out
-
-
-def word_anomaly_score(word: dict) -> float:
-    """[UPSTREAM-RECALL: transcribe.py::word_anomaly_score] how unlikely a word is to be speech: improbable, very short or very long"""
-    probability = word.get("probability", 0.0)
-    duration = word["end"] - word["start"]
-    score = 0.0
-    if probability < 0.15:
-        score += 1.0
-    if duration < 0.133:
-        score += (0.133 - duration) * 15
-    if duration > 2.0:
-        score += duration - 2.0
-    return score
-
-
-def is_segment_anomaly(segment: Optional[dict]) -> bool:
-    """[UPSTREAM-RECALL: transcribe.py::is_segment_anomaly] over the first 8 words that are not punctuation marks"""
-    if segment is None or not segment.get("words"):
-        return False
-    words = [w for w in segment["words"] if w["word"] not in string.punctuation][:8]
-    score = sum(word_anomaly_score(w) for w in words)
-    return score >= 3 or score + 0.01 >= len(words)
-
-
-def next_words_segment(segments: Sequence[dict]) -> Optional[dict]:
-    """[UPSTREAM-RECALL: transcribe.py::next_words_segment]"""
-    return next((s for s in segments if s.get("words")), None)
-
-
-class WindowLoop:
-    """Host half of openai-whisper's `transcribe()` for ONE clip [UPSTREAM-RECALL: whisper/transcribe.py, main loop]: which 30 s window
-    is decoded next and with which prompt, and what a decoded window adds to the segments / tokens / `text` -- the only key the
-    reference reads (back/api.py:1103, 1447, 1488).  No GPU state: `WhisperModel.transcribe_batch` owns the device work and calls
-    `next_window()` / `advance()`; tests/test_transcribe_loop_cpu.py drives the same object with scripted decode results against
-    oracle/whisper_transcribe_ref.py.
-
-    Deviation: with `word_timestamps=True` (back/api.py:1435, 1477) upstream aligns words by cross-attention DTW
-    and, when a window does not end on a single timestamp, moves `seek` to the end of the last aligned word instead of the last
-    timestamp token.  That rule is OPT-IN here: `advance(..., last_word_end=)` applies it (a `WhisperModel(word_alignment=True)` passes
-    the end of the last word its DTW aligned, csrc/align.hip); without the argument -- the default, its words are never read by the
-    reference -- `seek` keeps the timestamp-token rule; only audio that needs more than one window (longer than 30 s, or a window
-    that ends inside an unfinished segment) can see the difference.  `advance(..., hallucination_silence_threshold=)` adds upstream's
-    skipping of silence around probable hallucinations on top of it; it reads the words' `probability`, so a
-    `WhisperModel(word_probabilities=True)` is what passes it."""
-
-    def __init__(self, rules: DecodeRules, tokenizer, content_frames: int, initial_prompt: Optional[str], n_text_ctx: int,
-                 condition_on_previous_text: bool = True, no_speech_threshold: Optional[float] = 0.6,
-                 logprob_threshold: Optional[float] = -1.0, sot_sequence: Optional[Sequence[int]] = None,
-                 language: Optional[str] = "en", task: str = "transcribe", without_timestamps: bool = False,
-                 prefix_tokens: Optional[Sequence[int]] = None, sample_len: Optional[int] = None,
-                 clips: Optional[Sequence[Sequence[int]]] = None, carry_initial_prompt: bool = False):
-        """sot_sequence: tokenizer.sot_sequence of the clip; None: the rules' own for `language` and `task` ([sot] on an English-only
-        model).  language: what `result()` reports.  language=None on a multilingual model: PENDING -- the SOT sequence holds a
-        placeholder for the language token (-1; three tokens, so prompt lengths and caps are already right) until `set_language`
-        fills it in from the first window's detection; a pending loop must not be decoded.
-        The decoding options [UPSTREAM-RECALL: decoding.py::_get_initial_tokens, transcribe.py main loop; parity unpinned], all off by
-        default: without_timestamps -- <|notimestamps|> ends the SOT sequence; prefix_tokens -- appended behind it in every window
-        (part of the prompt: never in the result); sample_len -- caps every window's samples; clips -- (start, end) frame pairs
-        (decoding_options.parse_clip_timestamps): `seek` jumps to the next clip's start once it is at or behind the current clip's
-        end, a window ends where its clip ends, and the loop is over when the clips are (a clip at or behind the content's end holds
-        no window: upstream leaves that case to a negative segment size); carry_initial_prompt -- the initial prompt leads every
-        window's prompt, whatever was reset."""
-        self.rules, self.tokenizer, self.n_text_ctx = rules, tokenizer, int(n_text_ctx)
-        self.task = task
-        self.language_known = not (rules.is_multilingual and language is None and sot_sequence is None)
-        if sot_sequence is not None:
-            self.sot_sequence = [int(t) for t in sot_sequence]
-        elif self.language_known:
-            self.sot_sequence = rules.sot_sequence(language, task)
-        else:
-            self.sot_sequence = [rules.sot, -1, rules.sot_sequence("en", task)[2]]
-        if not rules.is_multilingual:
-            language = "en"
-        elif self.language_known and sot_sequence is None:
-            language = rules.language_code(self.sot_sequence[1])       # a name ("German") is reported as its code
-        self.language = language
-        self.content = int(content_frames)
-        self.condition, self.no_speech_threshold, self.logprob_threshold = condition_on_previous_text, no_speech_threshold, logprob_threshold
-        ipt = tokenizer.encode(" " + initial_prompt.strip()) if initial_prompt else []
-        self.seek, self.all_tokens, self.n_init, self.reset = 0, list(ipt), len(ipt), 0
-        self.without_timestamps = bool(without_timestamps)
-        self.prefix_tokens = [int(t) for t in prefix_tokens] if prefix_tokens is not None else []
-        self.sample_len = None if sample_len is None else int(sample_len)
-        self.carry_initial_prompt, self.initial_prompt_tokens = bool(carry_initial_prompt), list(ipt)
-        self.clips = [(int(a), int(b)) for a, b in clips] if clips is not None else None
-        self.clip_idx = 0
-        if self.clips is not None:
-            self.seek = self.clips[0][0] if self.clips else 0
-            self._settle_clip()
-        self.segments: List[dict] = []
-        self.seeks: List[int] = []
-        self.last_speech_timestamp = 0.0        # word alignment only: end of the last aligned word (add_word_timestamps)
-
-    def active(self) -> bool:
-        if self.clips is not None:
-            return self.clip_idx < len(self.clips)
-        return self.seek < self.content
-
-    def _settle_clip(self) -> None:
-        """transcribe.py's loop head: `seek` into the current clip, or on to the next one once this one (or the content) is used up"""
-        while self.clip_idx < len(self.clips):
-            start, end = self.clips[self.clip_idx]
-            if self.seek < start:
-                self.seek = start
-            if self.seek >= end or self.seek >= self.content:
-                self.clip_idx += 1
-                if self.clip_idx < len(self.clips):
-                    self.seek = self.clips[self.clip_idx][0]
-                continue
-            return
-
-    def segment_size(self) -> int:
-        """frames of the window at `seek`: min(N_FRAMES, content_frames - seek[, clip end - seek])"""
-        size = min(N_FRAMES, self.content - self.seek)
-        if self.clips is not None and self.clip_idx < len(self.clips):
-            size = min(size, self.clips[self.clip_idx][1] - self.seek)
-        return size
-
-    def prompt_tokens(self) -> List[int]:
-        """decode_options["prompt"] = all_tokens[prompt_reset_since:]; carry_initial_prompt: the initial prompt, then what fits of
-        the tokens behind max(its length, prompt_reset_since)"""
-        if self.carry_initial_prompt:
-            ipt = self.initial_prompt_tokens
-            nignored = max(len(ipt), self.reset)
-            return ipt + self.all_tokens[nignored:][-(self.n_text_ctx // 2 - 1 - len(ipt)):]
-        return self.all_tokens[self.reset:]
-
-    def sot_tail(self) -> int:
-        """tokens of the SOT sequence behind <|startoftranscript|>, <|notimestamps|> included (ccx_whisper_set_sot_tail); with the
-        prefix's length (ccx_whisper_set_prefix_len) it tells the library where to read the no-speech probability"""
-        return len(self.sot_sequence) - 1 + int(self.without_timestamps)
-
-    def initial_tokens(self) -> List[int]:
-        """decoding.py::_get_initial_tokens: [sot_prev] + prompt[-(n_ctx // 2 - 1):] + sot_sequence."""
-        p = self.prompt_tokens()
-        toks: List[int] = []
-        if len(p):
-            toks = [self.rules.sot_prev] + list(p)[-(self.n_text_ctx // 2 - 1):]
-        tail = [self.rules.no_timestamps] if self.without_timestamps else []
-        return toks + list(self.sot_sequence) + tail + self.prefix_tokens
-
-    def set_language(self, code: str) -> None:
-        """the detected language of a pending loop"""
-        self.sot_sequence = self.rules.sot_sequence(code, self.task)
-        self.language, self.language_known = code, True
-
-    def sample_cap(self) -> int:
-        """Tokens the next window may sample: decode_cap of its initial tokens."""
-        cap = decode_cap(len(self.initial_tokens()), self.n_text_ctx)
-        return cap if self.sample_len is None else min(self.sample_len, cap)
-
-    def window_segments(self, r: dict):
-        """The segments one decoded window yields, before empty ones are cleared: (segments, single_timestamp_ending, next seek by the
-        timestamp-token rule), or None when the silence rule skips the window.  Changes nothing."""
-        tsb, eot = self.rules.timestamp_begin, self.rules.eot
-        seek = self.seek
-        segment_size = self.segment_size()
-        time_offset = seek * HOP / SAMPLE_RATE
-        segment_duration = segment_size * HOP / SAMPLE_RATE
-        tokens = list(r["tokens"])
-        if self.no_speech_threshold is not None:
-            skip = r["no_speech_prob"] > self.no_speech_threshold
-            if self.logprob_threshold is not None and r["avg_logprob"] > self.logprob_threshold:
-                skip = False
-            if skip:
-                return None
-        is_ts = [t >= tsb for t in tokens]
-        single_ts_ending = is_ts[-2:] == [False, True]
-        consecutive = [i + 1 for i in range(len(tokens) - 1) if is_ts[i] and is_ts[i + 1]]
-        new_segments = []
-
-        def add(start, end, toks):
-            new_segments.append(dict(seek=seek, start=start, end=end, tokens=list(toks),
-                                     text=self.tokenizer.decode([t for t in toks if t < eot])))
-
-        if consecutive:
-            slices = list(consecutive)
-            if single_ts_ending:
-                slices.append(len(tokens))
-            last = 0
-            for cur in slices:
-                sl = tokens[last:cur]
-                add(time_offset + (sl[0] - tsb) * TIME_PRECISION, time_offset + (sl[-1] - tsb) * TIME_PRECISION, sl)
-                last = cur
-            if single_ts_ending:
-                next_seek = seek + segment_size
-            else:
-                next_seek = seek + (tokens[last - 1] - tsb) * INPUT_STRIDE
-        else:
-            duration = segment_duration
-            ts = [t for t in tokens if t >= tsb]
-            if ts and ts[-1] != tsb:
-                duration = (ts[-1] - tsb) * TIME_PRECISION
-            add(time_offset, time_offset + duration, tokens)
-            next_seek = seek + segment_size
-        return new_segments, single_ts_ending, next_seek
-
-    def advance(self, r: dict, temperature: float = 0.0, last_word_end: Optional[float] = None,
-                segments: Optional[List[dict]] = None, hallucination_silence_threshold: Optional[float] = None) -> None:
-        """One decoded window (r: tokens before eot, avg_logprob, no_speech_prob) -> segments, tokens, the next seek.
-        last_word_end (word alignment, opt-in): end of the last aligned word of this window in seconds -- when the window did not
-        end on a single timestamp and it lies behind the window's start, `seek` goes there [UPSTREAM-RECALL: transcribe.py, "if not
-        single_timestamp_ending: last_word_end = get_end(current_segments) ..."].  segments: this window's `window_segments()` after
-        add_word_timestamps worked on them (words attached, bounds moved); None: they are built here.
-        hallucination_silence_threshold (seconds; None: nothing below runs) [UPSTREAM-RECALL: transcribe.py, "skip silence before
-        possible hallucinations"; parity unpinned]: a window whose words end more than the threshold before its end resumes at the
-        last word, else at the window's end; a window whose first segment with words is anomalous (is_segment_anomaly) behind a
-        leading gap longer than the threshold is dropped whole and `seek` moves over the gap; an anomalous segment with silence (or
-        more anomalies) on both sides cuts the window there."""
-        seek = self.seek
-        self.seeks.append(seek)
-        segment_size = self.segment_size()
-        built = self.window_segments(r)
-        if built is None:
-            self.seek = seek + segment_size
-            if self.clips is not None:
-                self._settle_clip()
-            return
-        new_segments, single_ts_ending, self.seek = built
-        if segments is not None:
-            new_segments = segments
-        last_speech_before = self.last_speech_timestamp      # the previous window's: what the silence rule measures from
-        if last_word_end is not None:
-            if not single_ts_ending and last_word_end > seek * HOP / SAMPLE_RATE:
-                self.seek = round(last_word_end * FRAMES_PER_SECOND)
-            self.last_speech_timestamp = last_word_end
-        if hallucination_silence_threshold is not None:
-            thr = hallucination_silence_threshold
-            time_offset = seek * HOP / SAMPLE_RATE
-            window_end_time = (seek + segment_size) / FRAMES_PER_SECOND
-            if last_word_end is not None and not single_ts_ending and last_word_end > time_offset:
-                if window_end_time - last_word_end > thr:
-                    self.seek = round(last_word_end * FRAMES_PER_SECOND)
-                else:
-                    self.seek = seek + segment_size
-            # "if first segment might be a hallucination, skip leading silence": upstream's `continue` -- nothing of the window is kept
-            first = next_words_segment(new_segments)
-            if first is not None and is_segment_anomaly(first):
-                gap = first["start"] - time_offset
-                if gap > thr:
-                    self.seek = seek + round(gap * FRAMES_PER_SECOND)
-                    self.last_speech_timestamp = last_speech_before
-                    if self.seek <= seek:
-                        self.seek = seek + segment_size
-                    if self.clips is not None:
-                        self._settle_clip()
-                    return
-            # "skip silence before any possible hallucination that is surrounded by silence or more hallucinations"
-            hal_last_end = last_speech_before
-            for si, sg in enumerate(new_segments):
-                if not sg.get("words"):
-                    continue
-                if is_segment_anomaly(sg):
-                    nxt = next_words_segment(new_segments[si + 1:])
-                    hal_next_start = nxt["words"][0]["start"] if nxt is not None else time_offset + segment_size * HOP / SAMPLE_RATE
-                    silence_before = sg["start"] - hal_last_end > thr or sg["start"] < thr or sg["start"] - time_offset < 2.0
-                    silence_after = hal_next_start - sg["end"] > thr or is_segment_anomaly(nxt) or window_end_time - sg["end"] < 2.0
-                    if silence_before and silence_after:
-                        self.seek = round(max(time_offset + 1, sg["start"]) * FRAMES_PER_SECOND)
-                        if self.content / FRAMES_PER_SECOND - sg["end"] < thr:
-                            self.seek = self.content
-                        new_segments = new_segments[:si]
-                        break
-                hal_last_end = sg["end"]
-            end = get_end(new_segments)
-            self.last_speech_timestamp = end if end is not None else last_speech_before
-        for s in new_segments:
-            # "if a segment is instantaneous or does not contain text, clear it": its tokens do not reach the prompt or the text
-            if s["start"] == s["end"] or s["text"].strip() == "":
-                s["text"], s["tokens"] = "", []
-            self.segments.append(s)
-            self.all_tokens.extend(s["tokens"])
-        if not self.condition or temperature > 0.5:      # "do not feed the prompt tokens if a high temperature was used"
-            self.reset = len(self.all_tokens)
-        if self.seek <= seek:  # cannot happen under ApplyTimestampRules (a closing timestamp is > its opening one); never loop forever
-            self.seek = seek + segment_size
-        if self.clips is not None:
-            self._settle_clip()
-
-    def result(self) -> dict:
-        text_tokens = self.all_tokens[self.n_init:]
-        return dict(text=self.tokenizer.decode(text_tokens), segments=self.segments, language=self.language, tokens=list(text_tokens))
+class CallSettings(NamedTuple):
+    """What one call wants set on the instance while it runs (`WhisperModel._settings`); a field that is None sets nothing."""
+    options: Optional[decoding_options.CallOptions] = None      # -> set_decode_options
+    history: Optional[Tuple[float, int]] = None                 # (repetition_penalty, no_repeat_ngram_size)
+    bias: Optional[tuple] = None                                # the compiled table (offsets, ids, bias)
+    sot_tail: Optional[int] = None
+    prefix_len: Optional[int] = None
 
 
 class WhisperModel:
@@ -407,6 +108,7 @@ class WhisperModel:
         self.max_audio_seconds = float(max_audio_seconds)
         self.sample_seed, self._sample_calls = 0, 0     # temperature > 0: Philox seed and per-call counter
         self.last_cross_path = None
+        self.prefix_len = 0     # what the library starts with; `set_prefix_len` keeps it
         self.word_alignment = bool(word_alignment)
         self.word_probabilities = bool(word_probabilities)
         self.temperature_fallback = bool(temperature_fallback)
@@ -474,25 +176,6 @@ class WhisperModel:
     def reset_decode_options(self):
         self.ctx.check(self.lib.ccx_whisper_set_decode_options(self.handle, None), "ccx_whisper_set_decode_options")
 
-    def _with_call_options(self, decoding: dict, fn):
-        """`fn()` under the decoding subset a single decode takes (without_timestamps, suppress_blank, suppress_tokens,
-        max_initial_timestamp); the defaults are back afterwards.  Without the opt-in, or without any of them, just `fn()`."""
-        unknown = set(decoding) - {"without_timestamps", "suppress_blank", "suppress_tokens", "max_initial_timestamp"}
-        if unknown:
-            raise TypeError(f"unexpected decoding option(s): {sorted(unknown)}")
-        if not self.decoding_options or not decoding:
-            return fn()
-        try:
-            opt = decoding_options.resolve(self.rules, **decoding)
-        except ValueError as e:
-            raise _lib.CcxError(str(e)) from e
-        self.set_decode_options(opt.without_timestamps, opt.suppress_blank, None if opt.suppress_default else opt.suppress,
-                                opt.max_initial_timestamp_index)
-        try:
-            return fn()
-        finally:
-            self.reset_decode_options()
-
     @staticmethod
     def check_history_options(repetition_penalty: float, no_repeat_ngram_size: int):
         """the ranges ccx_whisper_set_history_options checks -> (float, int), or ValueError naming the argument"""
@@ -520,20 +203,6 @@ class WhisperModel:
         """captured step graphs of history plans (ccx_whisper_history_graph_count)"""
         return int(self.lib.ccx_whisper_history_graph_count(self.handle))
 
-    def _with_history_options(self, repetition_penalty, no_repeat_ngram_size, fn):
-        """`fn()` under the call's repetition_penalty / no_repeat_ngram_size; the defaults are back afterwards.  Without the opt-in
-        the two are ignored; with the default values nothing is set."""
-        if not self.repetition_control:
-            return fn()
-        p, n = self.check_history_options(repetition_penalty, no_repeat_ngram_size)
-        if p == 1.0 and n == 0:
-            return fn()
-        self.set_history_options(p, n)
-        try:
-            return fn()
-        finally:
-            self.reset_history_options()
-
     def compile_bias_options(self, sequence_bias=None, bad_words_ids=None, hotwords=None, hotword_boost=None):
         """`decode_bias.compile_bias_table` with this model's tokenizer, eot and vocabulary -> (offsets, ids, bias)"""
         from .decode_bias import compile_bias_table
@@ -557,20 +226,6 @@ class WhisperModel:
         """captured step graphs of bias plans (ccx_whisper_bias_graph_count)"""
         return int(self.lib.ccx_whisper_bias_graph_count(self.handle))
 
-    def _with_bias_options(self, sequence_bias, bad_words_ids, hotwords, hotword_boost, fn):
-        """`fn()` under the call's sequence_bias / bad_words_ids / hotwords; no table is set afterwards.  Without the opt-in the
-        arguments are ignored; with none of the three given (or an empty table) nothing is set."""
-        if not self.contextual_bias:
-            return fn()
-        table = self.compile_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost)
-        if len(table[2]) == 0:
-            return fn()
-        self._set_bias_table(*table)
-        try:
-            return fn()
-        finally:
-            self.reset_bias_options()
-
     def set_prefix_len(self, n_prefix: int):
         """prompt tokens behind the SOT sequence (a decode with a prefix): ccx_whisper_set_prefix_len"""
         self.ctx.check(self.lib.ccx_whisper_set_prefix_len(self.handle, int(n_prefix)), "ccx_whisper_set_prefix_len")
@@ -579,6 +234,115 @@ class WhisperModel:
     def set_sot_tail(self, n_tail: int):
         self.ctx.check(self.lib.ccx_whisper_set_sot_tail(self.handle, int(n_tail)), "ccx_whisper_set_sot_tail")
         self.sot_tail = int(n_tail)
+
+    # ------------------------------------------------------------------ a call's settings: resolved first, then set in one scope
+    def _bias_setting(self, sequence_bias, bad_words_ids, hotwords, hotword_boost):
+        """the call's compiled bias table; None without the opt-in, with none of the three given, or for an empty table"""
+        if not self.contextual_bias or (sequence_bias is None and bad_words_ids is None and hotwords is None):
+            return None
+        table = self.compile_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost)
+        return table if len(table[2]) else None
+
+    def _history_setting(self, repetition_penalty, no_repeat_ngram_size):
+        """the call's checked (repetition_penalty, no_repeat_ngram_size); None without the opt-in or for the defaults (1.0, 0)"""
+        if not self.repetition_control:
+            return None
+        history = self.check_history_options(repetition_penalty, no_repeat_ngram_size)
+        return None if history == (1.0, 0) else history
+
+    def _decode_settings(self, bias_args, repetition_penalty, no_repeat_ngram_size, decoding: dict) -> CallSettings:
+        """What a single decode sets, every refusal made before anything is set: the bias compile (ValueError), the history ranges
+        (ValueError), then the decoding keys (TypeError, with or without the opt-in) and `resolve` (CcxError).  **decoding is the
+        subset a single decode takes: without_timestamps, suppress_blank, suppress_tokens, max_initial_timestamp."""
+        bias = self._bias_setting(*bias_args)
+        history = None
+        if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
+            history = self._history_setting(repetition_penalty, no_repeat_ngram_size)
+        unknown = set(decoding) - {"without_timestamps", "suppress_blank", "suppress_tokens", "max_initial_timestamp"}
+        if unknown:
+            raise TypeError(f"unexpected decoding option(s): {sorted(unknown)}")
+        options = None
+        if self.decoding_options and decoding:
+            try:
+                options = decoding_options.resolve(self.rules, **decoding)
+            except ValueError as e:
+                raise _lib.CcxError(str(e)) from e
+        return CallSettings(options, history, bias)
+
+    def _transcribe_settings(self, n: int, hallucination_silence_threshold, without_timestamps, prefixes, suppress_blank,
+                             suppress_tokens, max_initial_timestamp, sample_len, carry_initial_prompt, repetition_penalty,
+                             no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost):
+        """What a `transcribe_batch` of n clips sets, every refusal made before anything is set -> (CallSettings, the resolved
+        decoding options, every clip's prefix tokens); the last two are None without the decoding_options opt-in."""
+        bias = self._bias_setting(sequence_bias, bad_words_ids, hotwords, hotword_boost)
+        history = self._history_setting(repetition_penalty, no_repeat_ngram_size)
+        if not self.decoding_options:
+            return CallSettings(history=history, bias=bias), None, None
+        try:
+            opt = decoding_options.resolve(self.rules, without_timestamps, suppress_blank, suppress_tokens, max_initial_timestamp,
+                                           sample_len, carry_initial_prompt)
+        except ValueError as e:
+            raise _lib.CcxError(str(e)) from e
+        if opt.without_timestamps and hallucination_silence_threshold is not None:
+            raise _lib.CcxError("without_timestamps=True cannot be combined with hallucination_silence_threshold: that rule is "
+                                "defined on segment timestamps")
+        prefixes = list(prefixes) if prefixes is not None else [None] * n
+        if len(prefixes) != n:
+            raise _lib.CcxError("transcribe_batch: one prefix (or None) per clip")
+        prefix_toks = [decoding_options.prefix_tokens(self.tokenizer, p, self.dims.n_text_ctx, opt.sample_len) for p in prefixes]
+        if len(set(len(t) for t in prefix_toks)) > 1:
+            raise _lib.CcxError("transcribe_batch: the prefixes of one call must hold equally many tokens (transcribe the clips "
+                                "one by one otherwise)")
+        # the SOT tail the call's prompts carry (WindowLoop.sot_tail: one length per model) and the length of their prefix
+        tail = len(self.rules.sot_sequence()) - 1 + int(opt.without_timestamps)
+        n_prefix = len(prefix_toks[0]) if n > 0 else 0
+        return CallSettings(None if opt.device_default(self.rules) else opt, history, bias,
+                            tail if n > 0 and tail != self.sot_tail else None, n_prefix or None), opt, prefix_toks
+
+    @contextlib.contextmanager
+    def _settings(self, s: CallSettings):
+        """The call's settings on the instance while the body runs, for however many decodes: applied once, in one order (options, SOT
+        tail, prefix length, history, bias), and taken back in reverse -- exactly those that were applied, also when a later setter
+        or the body raises.  The SOT tail and the prefix length go back to what the instance held before."""
+        with contextlib.ExitStack() as undo:
+            if s.options is not None:
+                o = s.options
+                self.set_decode_options(o.without_timestamps, o.suppress_blank, None if o.suppress_default else o.suppress,
+                                        o.max_initial_timestamp_index)
+                undo.callback(self.reset_decode_options)
+            if s.sot_tail is not None:
+                tail0 = self.sot_tail
+                self.set_sot_tail(s.sot_tail)
+                undo.callback(self.set_sot_tail, tail0)
+            if s.prefix_len is not None:
+                prefix0 = self.prefix_len
+                self.set_prefix_len(s.prefix_len)
+                undo.callback(self.set_prefix_len, prefix0)
+            if s.history is not None:
+                self.set_history_options(*s.history)
+                undo.callback(self.reset_history_options)
+            if s.bias is not None:
+                self._set_bias_table(*s.bias)
+                undo.callback(self.reset_bias_options)
+            yield
+
+    def _pack_prompts(self, seqs: Sequence[Sequence[int]]):
+        """-> (ids [n, max_len] int32, padded with eot; lens [n] int32; max_len)"""
+        max_len = max(len(p) for p in seqs)
+        ids = np.full((len(seqs), max_len), self.rules.eot, dtype=np.int32)
+        lens = np.zeros(len(seqs), dtype=np.int32)
+        for b, p in enumerate(seqs):
+            ids[b, :len(p)] = p
+            lens[b] = len(p)
+        return ids, lens, max_len
+
+    def _records(self, toks, ntok, slp, nsp) -> List[dict]:
+        """One record per row of a decode's outputs (toks [n, sample_len]; ntok, slp, nsp [n]).  Which cross-attention formulation the
+        decode ran (include/ccx.h: ccx_whisper_last_cross_path) is read here and kept in every record."""
+        self.last_cross_path = CROSS_PATHS.get(int(self.lib.ccx_whisper_last_cross_path(self.handle)), "unknown")
+        return [dict(tokens=toks[b, :ntok[b]].tolist(), sum_logprob=float(slp[b]),
+                     avg_logprob=float(slp[b]) / (int(ntok[b]) + 1), no_speech_prob=float(nsp[b]),
+                     cross_path=self.last_cross_path) for b in range(len(ntok))]
 
     def detect_language(self, B: int):
         """whisper.decoding.detect_language for the B currently encoded windows (ccx_whisper_detect_language): one decoder step
@@ -668,42 +432,29 @@ class WhisperModel:
         sample_len None: decode_cap of the longest prompt -- n_text_ctx // 2 = 224 for every prompt of up to 225 tokens (what the
         default always was), fewer for a longer one, which the fixed 224 made the library refuse.
         **decoding (decoding_options instances; ignored otherwise): without_timestamps, suppress_blank, suppress_tokens,
-        max_initial_timestamp for this call (`_with_call_options`); the prompts, the SOT tail, the prefix length and sample_len stay
-        the caller's.  repetition_penalty / no_repeat_ngram_size (repetition_control instances; ignored otherwise): this call's
-        history rules (`_with_history_options`).  sequence_bias / bad_words_ids / hotwords / hotword_boost (contextual_bias instances;
-        ignored otherwise): this call's bias table (`_with_bias_options`), applied before the history rules."""
-        if sequence_bias is not None or bad_words_ids is not None or hotwords is not None:
-            return self._with_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost, lambda: self.decode(
-                prompts, sample_len, temperature, seed, repetition_penalty, no_repeat_ngram_size, **decoding))
-        if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
-            return self._with_history_options(repetition_penalty, no_repeat_ngram_size,
-                                              lambda: self.decode(prompts, sample_len, temperature, seed, **decoding))
-        if decoding:
-            return self._with_call_options(decoding, lambda: self.decode(prompts, sample_len, temperature, seed))
+        max_initial_timestamp for this call; the prompts, the SOT tail, the prefix length and sample_len stay the caller's.
+        repetition_penalty / no_repeat_ngram_size (repetition_control instances; ignored otherwise): this call's history rules.
+        sequence_bias / bad_words_ids / hotwords / hotword_boost (contextual_bias instances; ignored otherwise): this call's bias
+        table, which a step adds before the history rules.  All of them are resolved first (`_decode_settings`: a refused call sets
+        nothing) and hold for this call alone (`_settings`)."""
+        settings = self._decode_settings((sequence_bias, bad_words_ids, hotwords, hotword_boost), repetition_penalty,
+                                         no_repeat_ngram_size, decoding)
         if not (temperature >= 0.0):
             raise _lib.CcxError("temperature must be >= 0")
         B = len(prompts)
-        mp = max(len(p) for p in prompts)
+        ids, lens, mp = self._pack_prompts(prompts)
         sample_len = sample_len or decode_cap(mp, self.dims.n_text_ctx)
-        ids = np.full((B, mp), self.rules.eot, dtype=np.int32)
-        lens = np.zeros(B, dtype=np.int32)
-        for b, p in enumerate(prompts):
-            ids[b, :len(p)] = p
-            lens[b] = len(p)
         toks = np.zeros((B, sample_len), dtype=np.int32)
         ntok = np.zeros(B, dtype=np.int32)
         slp = np.zeros(B, dtype=np.float32)
         nsp = np.zeros(B, dtype=np.float32)
         i32p, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
-        self.ctx.check(self.lib.ccx_whisper_decode(
-            self.handle, ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), mp, B, sample_len, float(temperature),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, toks.ctypes.data_as(i32p), ntok.ctypes.data_as(i32p), slp.ctypes.data_as(fp),
-            nsp.ctypes.data_as(fp), _lib.current_stream_ptr()), "ccx_whisper_decode")
-        # which cross-attention formulation the decode ran (include/ccx.h: ccx_whisper_last_cross_path), kept in every record
-        self.last_cross_path = CROSS_PATHS.get(int(self.lib.ccx_whisper_last_cross_path(self.handle)), "unknown")
-        return [dict(tokens=toks[b, :ntok[b]].tolist(), sum_logprob=float(slp[b]),
-                     avg_logprob=float(slp[b]) / (int(ntok[b]) + 1), no_speech_prob=float(nsp[b]),
-                     cross_path=self.last_cross_path) for b in range(B)]
+        with self._settings(settings):
+            self.ctx.check(self.lib.ccx_whisper_decode(
+                self.handle, ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), mp, B, sample_len, float(temperature),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, toks.ctypes.data_as(i32p), ntok.ctypes.data_as(i32p), slp.ctypes.data_as(fp),
+                nsp.ctypes.data_as(fp), _lib.current_stream_ptr()), "ccx_whisper_decode")
+            return self._records(toks, ntok, slp, nsp)
 
     def decode_rows(self, prompts: Sequence[Sequence[int]], windows: Sequence[int], stream_ids: Optional[Sequence[int]] = None,
                     sample_len: Optional[int] = None, temperature: float = 0.0, seed: int = 0, n_windows: Optional[int] = None,
@@ -714,28 +465,15 @@ class WhisperModel:
         only the failing ones).  stream_ids[r]: the row's noise stream at temperature > 0 (None: r), so that its draws do not depend on
         the rows it shares the call with.  n_windows: how many windows are encoded (default: max(windows) + 1).  repetition_penalty,
         no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost, **decoding: as `decode`."""
-        if sequence_bias is not None or bad_words_ids is not None or hotwords is not None:
-            return self._with_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost, lambda: self.decode_rows(
-                prompts, windows, stream_ids, sample_len, temperature, seed, n_windows, repetition_penalty, no_repeat_ngram_size,
-                **decoding))
-        if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
-            return self._with_history_options(repetition_penalty, no_repeat_ngram_size, lambda: self.decode_rows(
-                prompts, windows, stream_ids, sample_len, temperature, seed, n_windows, **decoding))
-        if decoding:
-            return self._with_call_options(decoding, lambda: self.decode_rows(prompts, windows, stream_ids, sample_len, temperature, seed,
-                                                                             n_windows))
+        settings = self._decode_settings((sequence_bias, bad_words_ids, hotwords, hotword_boost), repetition_penalty,
+                                         no_repeat_ngram_size, decoding)
         if not (temperature >= 0.0):
             raise _lib.CcxError("temperature must be >= 0")
         R = len(prompts)
         if len(windows) != R or (stream_ids is not None and len(stream_ids) != R):
             raise _lib.CcxError("decode_rows: one window (and one stream id) per prompt")
-        mp = max(len(p) for p in prompts)
+        ids, lens, mp = self._pack_prompts(prompts)
         sample_len = sample_len or decode_cap(mp, self.dims.n_text_ctx)
-        ids = np.full((R, mp), self.rules.eot, dtype=np.int32)
-        lens = np.zeros(R, dtype=np.int32)
-        for b, p in enumerate(prompts):
-            ids[b, :len(p)] = p
-            lens[b] = len(p)
         win = np.ascontiguousarray(windows, dtype=np.int32)
         sid = np.ascontiguousarray(stream_ids, dtype=np.int32) if stream_ids is not None else None
         nw = int(n_windows) if n_windows is not None else int(win.max()) + 1
@@ -744,15 +482,13 @@ class WhisperModel:
         slp = np.zeros(R, dtype=np.float32)
         nsp = np.zeros(R, dtype=np.float32)
         i32p, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
-        self.ctx.check(self.lib.ccx_whisper_decode_rows(
-            self.handle, ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), mp, R, win.ctypes.data_as(i32p), nw,
-            sid.ctypes.data_as(i32p) if sid is not None else None, sample_len, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
-            toks.ctypes.data_as(i32p), ntok.ctypes.data_as(i32p), slp.ctypes.data_as(fp), nsp.ctypes.data_as(fp),
-            _lib.current_stream_ptr()), "ccx_whisper_decode_rows")
-        self.last_cross_path = CROSS_PATHS.get(int(self.lib.ccx_whisper_last_cross_path(self.handle)), "unknown")
-        return [dict(tokens=toks[b, :ntok[b]].tolist(), sum_logprob=float(slp[b]),
-                     avg_logprob=float(slp[b]) / (int(ntok[b]) + 1), no_speech_prob=float(nsp[b]),
-                     cross_path=self.last_cross_path) for b in range(R)]
+        with self._settings(settings):
+            self.ctx.check(self.lib.ccx_whisper_decode_rows(
+                self.handle, ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), mp, R, win.ctypes.data_as(i32p), nw,
+                sid.ctypes.data_as(i32p) if sid is not None else None, sample_len, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                toks.ctypes.data_as(i32p), ntok.ctypes.data_as(i32p), slp.ctypes.data_as(fp), nsp.ctypes.data_as(fp),
+                _lib.current_stream_ptr()), "ccx_whisper_decode_rows")
+            return self._records(toks, ntok, slp, nsp)
 
     def decode_beam(self, prompts: Sequence[Sequence[int]], beam_size: int, patience: Optional[float] = None,
                     sample_len: Optional[int] = None, windows: Optional[Sequence[int]] = None, n_windows: Optional[int] = None,
@@ -768,27 +504,14 @@ class WhisperModel:
         beam_size + 1], tok / parent / score [steps, rows]; rows = prompt-major; -1 / NaN where a window no longer stepped).
         repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost, **decoding: as `decode`; every
         row reads the history that follows its hypothesis."""
-        if sequence_bias is not None or bad_words_ids is not None or hotwords is not None:
-            return self._with_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost, lambda: self.decode_beam(
-                prompts, beam_size, patience, sample_len, windows, n_windows, trace, repetition_penalty, no_repeat_ngram_size,
-                **decoding))
-        if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
-            return self._with_history_options(repetition_penalty, no_repeat_ngram_size, lambda: self.decode_beam(
-                prompts, beam_size, patience, sample_len, windows, n_windows, trace, **decoding))
-        if decoding:
-            return self._with_call_options(decoding, lambda: self.decode_beam(prompts, beam_size, patience, sample_len, windows, n_windows,
-                                                                             trace))
+        settings = self._decode_settings((sequence_bias, bad_words_ids, hotwords, hotword_boost), repetition_penalty,
+                                         no_repeat_ngram_size, decoding)
         G, bs = len(prompts), int(beam_size)
         if patience is not None and not (patience > 0):
             raise _lib.CcxError("decode_beam: patience must be > 0")
         mc = round(bs * (1.0 if patience is None else float(patience)))
-        mp = max(len(p) for p in prompts)
+        ids, lens, mp = self._pack_prompts(prompts)
         sample_len = sample_len or decode_cap(mp, self.dims.n_text_ctx)
-        ids = np.full((G, mp), self.rules.eot, dtype=np.int32)
-        lens = np.zeros(G, dtype=np.int32)
-        for g, p in enumerate(prompts):
-            ids[g, :len(p)] = p
-            lens[g] = len(p)
         win = np.ascontiguousarray(windows, dtype=np.int32) if windows is not None else None
         if win is not None and win.shape != (G,):
             raise _lib.CcxError("decode_beam: one window per prompt")
@@ -808,14 +531,14 @@ class WhisperModel:
                       score=np.full((sample_len, R), np.nan, dtype=np.float32))
             tr_c = _lib.BeamTrace(sample_len, tr["cand_id"].ctypes.data_as(i32p), tr["cand_lp"].ctypes.data_as(fp),
                                   tr["tok"].ctypes.data_as(i32p), tr["parent"].ctypes.data_as(i32p), tr["score"].ctypes.data_as(fp))
-        self.ctx.check(self.lib.ccx_whisper_decode_beam(
-            self.handle, ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), mp, G, win.ctypes.data_as(i32p) if win is not None else None,
-            nw, bs, mc, sample_len, toks.ctypes.data_as(i32p), ntok.ctypes.data_as(i32p), slp.ctypes.data_as(fp), nhyp.ctypes.data_as(i32p),
-            nsp.ctypes.data_as(fp), C.byref(tr_c) if tr_c is not None else None, _lib.current_stream_ptr()), "ccx_whisper_decode_beam")
-        self.last_cross_path = CROSS_PATHS.get(int(self.lib.ccx_whisper_last_cross_path(self.handle)), "unknown")
-        out = [[dict(tokens=toks[g, k, :ntok[g, k]].tolist(), sum_logprob=float(slp[g, k]),
-                     avg_logprob=float(slp[g, k]) / (int(ntok[g, k]) + 1), no_speech_prob=float(nsp[g]), cross_path=self.last_cross_path)
-                for k in range(int(nhyp[g]))] for g in range(G)]
+        with self._settings(settings):
+            self.ctx.check(self.lib.ccx_whisper_decode_beam(
+                self.handle, ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), mp, G, win.ctypes.data_as(i32p) if win is not None else None,
+                nw, bs, mc, sample_len, toks.ctypes.data_as(i32p), ntok.ctypes.data_as(i32p), slp.ctypes.data_as(fp), nhyp.ctypes.data_as(i32p),
+                nsp.ctypes.data_as(fp), C.byref(tr_c) if tr_c is not None else None, _lib.current_stream_ptr()), "ccx_whisper_decode_beam")
+            # the candidate slots as rows, every one with its window's no-speech probability; a window keeps its first nhyp[g]
+            rows = self._records(toks.reshape(G * Cn, sample_len), ntok.reshape(-1), slp.reshape(-1), np.repeat(nsp, Cn))
+        out = [rows[g * Cn:g * Cn + int(nhyp[g])] for g in range(G)]
         return (out, tr) if trace else out
 
     def _decode_with_fallback(self, prompts, cap: int, schedule, best_of, compression_ratio_threshold, logprob_threshold,
@@ -870,13 +593,8 @@ class WhisperModel:
         token_probs: (jump_frames, P, A, probs) instead -- probs[b] = float32 array, one entry per text token: its softmax
         probability over the ids [0, eot) at the row that predicts it (ccx_whisper_align_probs; timing.py::find_alignment)."""
         B = len(tokens_per_seq)
-        T = max(len(t) for t in tokens_per_seq)
-        toks = np.full((B, T), self.rules.eot, dtype=np.int32)
-        lens = np.zeros(B, dtype=np.int32)
-        for b, t in enumerate(tokens_per_seq):
-            toks[b, :len(t)] = t
-            lens[b] = len(t)
-        nf = np.ascontiguousarray(n_frames, dtype=np.int32)
+        toks, lens, T = self._pack_prompts(tokens_per_seq)
+        nf =np.ascontiguousarray(n_frames, dtype=np.int32)
         if nf.shape != (B,):
             raise _lib.CcxError("align: one n_frames entry per sequence")
         heads = np.ascontiguousarray(self.alignment_heads, dtype=np.int32).reshape(-1, 2)
@@ -900,12 +618,11 @@ class WhisperModel:
             return jumps, P, A, [tp[b, :max(int(lens[b]) - 2 - int(row0), 0)].copy() for b in range(B)]
         return jumps, P, A
 
-    def _advance_with_words(self, grp, results, state, temperature: float, hallucination_silence_threshold: Optional[float] = None):
+    def _advance_with_words(self, grp, results, state, temps: Sequence[float], hallucination_silence_threshold: Optional[float] = None):
         """word_alignment and word_timestamps: align every window of the group that produced text while the windows are still
         encoded, attach the words, and advance each clip with the end of its last word [UPSTREAM-RECALL: transcribe.py].  On an
         instance with word_probabilities the same pass gives the token probabilities, the words carry `probability` and the
-        threshold reaches `advance`.  temperature: one for the group, or one per window (a fallback walk's)."""
-        temps = list(temperature) if isinstance(temperature, (tuple, list)) else [temperature] * len(grp)
+        threshold reaches `advance`.  temps: the temperature every window was decoded at."""
         built = [state[i].window_segments(r) for i, r in zip(grp, results)]
         texts = []
         for bt in built:
@@ -940,6 +657,56 @@ class WhisperModel:
         if len(prompt_tokens):
             toks = [self.rules.sot_prev] + list(prompt_tokens)[-(self.dims.n_text_ctx // 2 - 1):]
         return toks + list(sot_sequence if sot_sequence is not None else self.rules.sot_sequence())
+
+    def _walk_options(self, temperature, best_of, beam_size, patience, length_penalty):
+        """A `transcribe_batch` call's temperature / best_of / beam arguments, refused or dropped as its opt-ins say -> (schedule,
+        whether the windows walk it (`_decode_with_fallback`), best_of, beam_size, patience, length_penalty)"""
+        if not self.temperature_fallback:
+            if isinstance(temperature, (tuple, list)):
+                raise _lib.CcxError("temperature fallback schedules need an instance built with temperature_fallback=True: "
+                                    "pass one temperature (the reference does)")
+            best_of = None          # ignored, as compression_ratio_threshold is
+        if not self.beam_search:
+            beam_size = patience = length_penalty = None     # accepted and ignored
+        if patience is not None and beam_size is None:
+            raise _lib.CcxError("patience needs beam_size")
+        if beam_size is not None and not isinstance(temperature, (tuple, list)) and float(temperature) > 0.0:
+            raise _lib.CcxError("beam_size needs temperature 0 (or a schedule that starts there): beam search does not sample")
+        try:
+            schedule = fallback.normalize_schedule(temperature)
+        except ValueError as e:
+            raise _lib.CcxError(str(e)) from e
+        walk_on = (self.temperature_fallback and (isinstance(temperature, (tuple, list)) or best_of is not None)) or \
+            beam_size is not None or length_penalty is not None
+        return schedule, walk_on, best_of, beam_size, patience, length_penalty
+
+    def _stage_clips(self, audios: Sequence):
+        """The clips as one zero-padded [n, longest] float32 tensor that stays on the device for all their windows -> (it, the clips'
+        lengths in samples).  Device tensors (the processor's crops) stay on the device; host arrays go up in one transfer."""
+        n = len(audios)
+        on_dev = n > 0 and all(isinstance(a, torch.Tensor) and a.is_cuda for a in audios)
+        if on_dev:
+            clips = [a.detach().reshape(-1) for a in audios]
+            lens = [int(c.numel()) for c in clips]
+        else:
+            clips = []
+            for a in audios:
+                a = a.detach().to("cpu").numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+                clips.append(np.ascontiguousarray(a.reshape(-1), dtype=np.float32))
+            lens = [len(c) for c in clips]
+        stride = max(max(lens, default=1), 1)
+        if stride > self.max_audio_seconds * SAMPLE_RATE:
+            raise _lib.CcxError(f"clip of {stride / SAMPLE_RATE:.1f} s exceeds max_audio_seconds={self.max_audio_seconds}")
+        if on_dev:
+            dev_audio = torch.zeros(n, stride, device=self.device, dtype=torch.float32)
+            for i, c in enumerate(clips):
+                dev_audio[i, :lens[i]] = c.to(self.device, torch.float32)
+        else:
+            host = np.zeros((n, stride), dtype=np.float32)
+            for i, c in enumerate(clips):
+                host[i, :lens[i]] = c
+            dev_audio = torch.from_numpy(host).to(self.device)
+        return dev_audio, lens
 
     def transcribe(self, audio, initial_prompt: Optional[str] = None, word_timestamps: bool = False,
                    condition_on_previous_text: bool = True, temperature: float = 0.0,
@@ -1045,75 +812,27 @@ class WhisperModel:
         (`decode_bias.compile_bias_table`) that holds for every window of the call and every round of a fallback walk (one
         ccx_whisper_set_bias_options per call, no table set when it returns); what the compile refuses raises ValueError.  A window
         matches over what that window's decode sampled only.  Without the opt-in all four are ignored."""
-        bias_table = None
-        if self.contextual_bias and (sequence_bias is not None or bad_words_ids is not None or hotwords is not None):
-            bias_table = self.compile_bias_options(sequence_bias, bad_words_ids, hotwords, hotword_boost)
-        bias_on = bias_table is not None and len(bias_table[2]) > 0
-        hist_on = False
-        if self.repetition_control:
-            hist_p, hist_n = self.check_history_options(repetition_penalty, no_repeat_ngram_size)
-            hist_on = hist_p != 1.0 or hist_n != 0
-        opt, prefix_toks, clip_spec = None, None, None
-        if self.decoding_options:
-            try:
-                opt = decoding_options.resolve(self.rules, without_timestamps, suppress_blank, suppress_tokens, max_initial_timestamp,
-                                               sample_len, carry_initial_prompt)
-            except ValueError as e:
-                raise _lib.CcxError(str(e)) from e
-            if opt.without_timestamps and hallucination_silence_threshold is not None:
-                raise _lib.CcxError("without_timestamps=True cannot be combined with hallucination_silence_threshold: that rule is "
-                                    "defined on segment timestamps")
-            prefixes = list(prefixes) if prefixes is not None else [None] * len(audios)
-            if len(prefixes) != len(audios):
-                raise _lib.CcxError("transcribe_batch: one prefix (or None) per clip")
-            prefix_toks = [decoding_options.prefix_tokens(self.tokenizer, p, self.dims.n_text_ctx, opt.sample_len) for p in prefixes]
-            if len(set(len(t) for t in prefix_toks)) > 1:
-                raise _lib.CcxError("transcribe_batch: the prefixes of one call must hold equally many tokens (transcribe the clips "
-                                    "one by one otherwise)")
-            clip_spec = clip_timestamps
-        with_words = bool(word_timestamps) and self.word_alignment
-        if not self.temperature_fallback:
-            if isinstance(temperature, (tuple, list)):
-                raise _lib.CcxError("temperature fallback schedules need an instance built with temperature_fallback=True: "
-                                    "pass one temperature (the reference does)")
-            best_of = None          # ignored, as compression_ratio_threshold is
-        if not self.beam_search:
-            beam_size = patience = length_penalty = None     # accepted and ignored
-        if patience is not None and beam_size is None:
-            raise _lib.CcxError("patience needs beam_size")
-        if beam_size is not None and not isinstance(temperature, (tuple, list)) and float(temperature) > 0.0:
-            raise _lib.CcxError("beam_size needs temperature 0 (or a schedule that starts there): beam search does not sample")
-        try:
-            schedule = fallback.normalize_schedule(temperature)
-        except ValueError as e:
-            raise _lib.CcxError(str(e)) from e
-        walk_on = (self.temperature_fallback and (isinstance(temperature, (tuple, list)) or best_of is not None)) or \
-            beam_size is not None or length_penalty is not None
-        self.fallback_walks: List[fallback.FallbackWalk] = []     # this call's walks, one per encoded group, in order
-        temperature = schedule[0]
         n = len(audios)
+        settings, opt, prefix_toks = self._transcribe_settings(
+            n, hallucination_silence_threshold, without_timestamps, prefixes, suppress_blank, suppress_tokens, max_initial_timestamp,
+            sample_len, carry_initial_prompt, repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords,
+            hotword_boost)
+        schedule, walk_on, best_of, beam_size, patience, length_penalty = self._walk_options(temperature, best_of, beam_size, patience,
+                                                                                            length_penalty)
+        with_words = bool(word_timestamps) and self.word_alignment
+        self.fallback_walks: List[fallback.FallbackWalk] = []     # this call's walks, one per encoded group, in order
         initial_prompts = list(initial_prompts) if initial_prompts is not None else [None] * n
-        # device tensors (the processor's crops) stay on the device; host arrays go up in one transfer
-        on_dev = n > 0 and all(isinstance(a, torch.Tensor) and a.is_cuda for a in audios)
-        if on_dev:
-            clips = [a.detach().reshape(-1) for a in audios]
-            lens = [int(c.numel()) for c in clips]
-        else:
-            clips = []
-            for a in audios:
-                a = a.detach().to("cpu").numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-                clips.append(np.ascontiguousarray(a.reshape(-1), dtype=np.float32))
-            lens = [len(c) for c in clips]
         multi = self.rules.is_multilingual
         languages = list(languages) if languages is not None else [None] * n
         if len(languages) != n:
             raise _lib.CcxError("transcribe_batch: one language entry (or None) per clip")
+        dev_audio, lens = self._stage_clips(audios)
         # English-only: language "en", task ignored.  Multilingual: the clip's SOT sequence; language None: pending until detected
         def loop_options(i):
             if opt is None:
                 return {}
             try:
-                clips_i = decoding_options.parse_clip_timestamps(clip_spec, lens[i] // HOP)
+                clips_i = decoding_options.parse_clip_timestamps(clip_timestamps, lens[i] // HOP)
             except ValueError as e:
                 raise _lib.CcxError(f"clip_timestamps: {e}") from e
             return dict(without_timestamps=opt.without_timestamps, prefix_tokens=prefix_toks[i], sample_len=opt.sample_len,
@@ -1122,36 +841,8 @@ class WhisperModel:
         state = [WindowLoop(self.rules, self.tokenizer, lens[i] // HOP, initial_prompts[i], self.dims.n_text_ctx,
                             condition_on_previous_text, no_speech_threshold, logprob_threshold,
                             language=languages[i] if multi else "en", task=task, **loop_options(i)) for i in range(n)]
-        stride = max(max(lens, default=1), 1)
-        if stride > self.max_audio_seconds * SAMPLE_RATE:
-            raise _lib.CcxError(f"clip of {stride / SAMPLE_RATE:.1f} s exceeds max_audio_seconds={self.max_audio_seconds}")
-        # clips stay resident on the GPU for all windows
-        if on_dev:
-            dev_audio = torch.zeros(n, stride, device=self.device, dtype=torch.float32)
-            for i, c in enumerate(clips):
-                dev_audio[i, :lens[i]] = c.to(self.device, torch.float32)
-        else:
-            host = np.zeros((n, stride), dtype=np.float32)
-            for i, c in enumerate(clips):
-                host[i, :lens[i]] = c
-            dev_audio = torch.from_numpy(host).to(self.device)
-        # the call's options on the device (one call for every round of the walk) and the SOT tail its prompts carry; both are the
-        # instance's defaults again when the call returns
-        tail0 = self.sot_tail if opt is not None else None
-        dev_opts = opt is not None and not opt.device_default(self.rules)
-        if dev_opts:
-            self.set_decode_options(opt.without_timestamps, opt.suppress_blank, None if opt.suppress_default else opt.suppress,
-                                    opt.max_initial_timestamp_index)
-        if opt is not None and n > 0 and state[0].sot_tail() != tail0:
-            self.set_sot_tail(state[0].sot_tail())
-        n_prefix = len(prefix_toks[0]) if opt is not None and n > 0 else 0
-        if n_prefix:
-            self.set_prefix_len(n_prefix)
-        if hist_on:
-            self.set_history_options(hist_p, hist_n)
-        if bias_on:
-            self._set_bias_table(*bias_table)
-        try:
+        # one set per family for every window, group and round of the call; the instance's own values are back when it returns
+        with self._settings(settings):
             while True:
                 active = [i for i in range(n) if state[i].active()]
                 if not active:
@@ -1179,35 +870,21 @@ class WhisperModel:
                         results = self._decode_with_fallback(prompts, cap, schedule, best_of, compression_ratio_threshold,
                                                              logprob_threshold, no_speech_threshold, beam_size, patience, length_penalty)
                         self.fallback_walks[-1].clips, self.fallback_walks[-1].seeks = list(grp), [state[i].seek for i in grp]
-                        n_seg = [len(state[i].segments) for i in grp]
-                        if with_words:     # the accepted tokens, while the group's windows are still encoded: aligned as one batch, each
-                            # window advanced with the temperature it was accepted at
-                            self._advance_with_words(grp, results, state, [r["temperature"] for r in results], hallucination_silence_threshold)
-                        else:
-                            for i, r in zip(grp, results):
-                                state[i].advance(r, r["temperature"])
+                        temps = [r["temperature"] for r in results]     # what each window was accepted at
+                    else:
+                        self._sample_calls += 1
+                        results = self.decode(prompts, sample_len=cap, temperature=schedule[0],
+                                              seed=(int(self.sample_seed) << 32) + self._sample_calls)
+                        temps = [schedule[0]] * len(grp)
+                    n_seg = [len(state[i].segments) for i in grp]
+                    if with_words:     # before the next log_mel: the group's windows are still encoded, aligned as one batch
+                        self._advance_with_words(grp, results, state, temps, hallucination_silence_threshold)
+                    else:
+                        for i, r, t in zip(grp, results, temps):
+                            state[i].advance(r, t)
+                    if walk_on:     # the walk's fields on the window's new segments, as upstream's carry them
                         for b, (i, r) in enumerate(zip(grp, results)):
                             for s in state[i].segments[n_seg[b]:]:
                                 s.update(temperature=r["temperature"], avg_logprob=r["avg_logprob"], compression_ratio=r["compression_ratio"],
                                          no_speech_prob=r["no_speech_prob"])
-                        continue
-                    self._sample_calls += 1
-                    results = self.decode(prompts, sample_len=cap, temperature=temperature,
-                                          seed=(int(self.sample_seed) << 32) + self._sample_calls)
-                    if with_words:     # before the next log_mel: the group's windows are still encoded
-                        self._advance_with_words(grp, results, state, temperature, hallucination_silence_threshold)
-                        continue
-                    for i, r in zip(grp, results):
-                        state[i].advance(r, temperature)
-        finally:
-            if bias_on:
-                self.reset_bias_options()
-            if hist_on:
-                self.reset_history_options()
-            if dev_opts:
-                self.reset_decode_options()
-            if opt is not None and self.sot_tail != tail0:
-                self.set_sot_tail(tail0)
-            if n_prefix:
-                self.set_prefix_len(0)
         return [st.result() for st in state]

@@ -1,0 +1,322 @@
+"""The GPU-free half of `WhisperModel.transcribe_batch`: openai-whisper's window loop for one clip (`WindowLoop`), the sample cap of a
+prompt and the decode groups of one pass [UPSTREAM-RECALL: whisper/transcribe.py, whisper/decoding.py].  `clearconverse_amd.whisper` owns
+the device work and imports these by name.
+"""
+from __future__ import annotations
+
+import string
+from typing import Dict, List, Optional, Sequence
+
+from .tokenizer import DecodeRules
+from .word_timing import get_end
+
+N_FRAMES = 3000
+HOP = 160
+SAMPLE_RATE = 16000
+FRAMES_PER_SECOND = 100
+TIME_PRECISION = 0.02  # seconds per timestamp token
+INPUT_STRIDE = 2       # mel frames per encoder position
+
+
+def decode_cap(prompt_len: int, n_text_ctx: int) -> int:
+    """Most tokens a sequence samples from `prompt_len` initial tokens [UPSTREAM-RECALL: decoding.py::_main_loop runs sample_len =
+    n_ctx // 2 steps and stops once `tokens.shape[-1] > n_ctx`]: min(n_ctx // 2, n_ctx + 1 - prompt_len) -- 224 for every English-only
+    prompt (at most 225 tokens), 222 for a full multilingual one (1 + 223 + 3 = 227).  No row is cut earlier than upstream cuts it, and
+    prompt_len + cap - 1 <= n_ctx, which is what ccx_whisper_decode asks for."""
+    return max(1, min(n_text_ctx // 2, n_text_ctx + 1 - int(prompt_len)))
+
+
+def groups_by_cap(active: Sequence[int], caps: Sequence[int], max_batch: int) -> List[tuple]:
+    """Decode groups of one pass over the active clips: `decode` takes ONE sample_len per call, so the clips are partitioned by
+    their cap (largest first, clip order kept inside a cap), then chunked by max_batch.  -> [(cap, [clip index, ...]), ...]."""
+    by_cap: Dict[int, List[int]] = {}
+    for i, c in zip(active, caps):
+        by_cap.setdefault(int(c), []).append(i)
+    out = []
+    for c in sorted(by_cap, reverse=True):
+        for c0 in range(0, len(by_cap[c]), max_batch):
+            out.append((c, by_cap[c][c0:c0 + max_batch]))
+    return out
+
+
+def word_anomaly_score(word: dict) -> float:
+    """[UPSTREAM-RECALL: transcribe.py::word_anomaly_score] how unlikely a word is to be speech: improbable, very short or very long"""
+    probability = word.get("probability", 0.0)
+    duration = word["end"] - word["start"]
+    score = 0.0
+    if probability < 0.15:
+        score += 1.0
+    if duration < 0.133:
+        score += (0.133 - duration) * 15
+    if duration > 2.0:
+        score += duration - 2.0
+    return score
+
+
+def is_segment_anomaly(segment: Optional[dict]) -> bool:
+    """[UPSTREAM-RECALL: transcribe.py::is_segment_anomaly] over the first 8 words that are not punctuation marks"""
+    if segment is None or not segment.get("words"):
+        return False
+    words = [w for w in segment["words"] if w["word"] not in string.punctuation][:8]
+    score = sum(word_anomaly_score(w) for w in words)
+    return score >= 3 or score + 0.01 >= len(words)
+
+
+def next_words_segment(segments: Sequence[dict]) -> Optional[dict]:
+    """[UPSTREAM-RECALL: transcribe.py::next_words_segment]"""
+    return next((s for s in segments if s.get("words")), None)
+
+
+class WindowLoop:
+    """Host half of openai-whisper's `transcribe()` for ONE clip [UPSTREAM-RECALL: whisper/transcribe.py, main loop]: which 30 s window
+    is decoded next and with which prompt, and what a decoded window adds to the segments / tokens / `text` -- the only key the
+    reference reads (back/api.py:1103, 1447, 1488).  No GPU state: `WhisperModel.transcribe_batch` owns the device work and calls
+    `next_window()` / `advance()`; tests/test_transcribe_loop_cpu.py drives the same object with scripted decode results against
+    oracle/whisper_transcribe_ref.py.
+
+    Deviation: with `word_timestamps=True` (back/api.py:1435, 1477) upstream aligns words by cross-attention DTW
+    and, when a window does not end on a single timestamp, moves `seek` to the end of the last aligned word instead of the last
+    timestamp token.  That rule is OPT-IN here: `advance(..., last_word_end=)` applies it (a `WhisperModel(word_alignment=True)` passes
+    the end of the last word its DTW aligned, csrc/align.hip); without the argument -- the default, its words are never read by the
+    reference -- `seek` keeps the timestamp-token rule; only audio that needs more than one window (longer than 30 s, or a window
+    that ends inside an unfinished segment) can see the difference.  `advance(..., hallucination_silence_threshold=)` adds upstream's
+    skipping of silence around probable hallucinations on top of it; it reads the words' `probability`, so a
+    `WhisperModel(word_probabilities=True)` is what passes it."""
+
+    def __init__(self, rules: DecodeRules, tokenizer, content_frames: int, initial_prompt: Optional[str], n_text_ctx: int,
+                 condition_on_previous_text: bool = True, no_speech_threshold: Optional[float] = 0.6,
+                 logprob_threshold: Optional[float] = -1.0, sot_sequence: Optional[Sequence[int]] = None,
+                 language: Optional[str] = "en", task: str = "transcribe", without_timestamps: bool = False,
+                 prefix_tokens: Optional[Sequence[int]] = None, sample_len: Optional[int] = None,
+                 clips: Optional[Sequence[Sequence[int]]] = None, carry_initial_prompt: bool = False):
+        """sot_sequence: tokenizer.sot_sequence of the clip; None: the rules' own for `language` and `task` ([sot] on an English-only
+        model).  language: what `result()` reports.  language=None on a multilingual model: PENDING -- the SOT sequence holds a
+        placeholder for the language token (-1; three tokens, so prompt lengths and caps are already right) until `set_language`
+        fills it in from the first window's detection; a pending loop must not be decoded.
+        The decoding options [UPSTREAM-RECALL: decoding.py::_get_initial_tokens, transcribe.py main loop; parity unpinned], all off by
+        default: without_timestamps -- <|notimestamps|> ends the SOT sequence; prefix_tokens -- appended behind it in every window
+        (part of the prompt: never in the result); sample_len -- caps every window's samples; clips -- (start, end) frame pairs
+        (decoding_options.parse_clip_timestamps): `seek` jumps to the next clip's start once it is at or behind the current clip's
+        end, a window ends where its clip ends, and the loop is over when the clips are (a clip at or behind the content's end holds
+        no window: upstream leaves that case to a negative segment size); carry_initial_prompt -- the initial prompt leads every
+        window's prompt, whatever was reset."""
+        self.rules, self.tokenizer, self.n_text_ctx = rules, tokenizer, int(n_text_ctx)
+        self.task = task
+        self.language_known = not (rules.is_multilingual and language is None and sot_sequence is None)
+        if sot_sequence is not None:
+            self.sot_sequence = [int(t) for t in sot_sequence]
+        elif self.language_known:
+            self.sot_sequence = rules.sot_sequence(language, task)
+        else:
+            self.sot_sequence = [rules.sot, -1, rules.sot_sequence("en", task)[2]]
+        if not rules.is_multilingual:
+            language = "en"
+        elif self.language_known and sot_sequence is None:
+            language = rules.language_code(self.sot_sequence[1])       # a name ("German") is reported as its code
+        self.language = language
+        self.content = int(content_frames)
+        self.condition, self.no_speech_threshold, self.logprob_threshold = condition_on_previous_text, no_speech_threshold, logprob_threshold
+        ipt = tokenizer.encode(" " + initial_prompt.strip()) if initial_prompt else []
+        self.seek, self.all_tokens, self.n_init, self.reset = 0, list(ipt), len(ipt), 0
+        self.without_timestamps = bool(without_timestamps)
+        self.prefix_tokens = [int(t) for t in prefix_tokens] if prefix_tokens is not None else []
+        self.sample_len = None if sample_len is None else int(sample_len)
+        self.carry_initial_prompt, self.initial_prompt_tokens = bool(carry_initial_prompt), list(ipt)
+        self.clips = [(int(a), int(b)) for a, b in clips] if clips is not None else None
+        self.clip_idx = 0
+        if self.clips is not None:
+            self.seek = self.clips[0][0] if self.clips else 0
+            self._settle_clip()
+        self.segments: List[dict] = []
+        self.seeks: List[int] = []
+        self.last_speech_timestamp = 0.0        # word alignment only: end of the last aligned word (add_word_timestamps)
+
+    def active(self) -> bool:
+        if self.clips is not None:
+            return self.clip_idx < len(self.clips)
+        return self.seek < self.content
+
+    def _settle_clip(self) -> None:
+        """transcribe.py's loop head: `seek` into the current clip, or on to the next one once this one (or the content) is used up"""
+        while self.clip_idx < len(self.clips):
+            start, end = self.clips[self.clip_idx]
+            if self.seek < start:
+                self.seek = start
+            if self.seek >= end or self.seek >= self.content:
+                self.clip_idx += 1
+                if self.clip_idx < len(self.clips):
+                    self.seek = self.clips[self.clip_idx][0]
+                continue
+            return
+
+    def segment_size(self) -> int:
+        """frames of the window at `seek`: min(N_FRAMES, content_frames - seek[, clip end - seek])"""
+        size = min(N_FRAMES, self.content - self.seek)
+        if self.clips is not None and self.clip_idx < len(self.clips):
+            size = min(size, self.clips[self.clip_idx][1] - self.seek)
+        return size
+
+    def prompt_tokens(self) -> List[int]:
+        """decode_options["prompt"] = all_tokens[prompt_reset_since:]; carry_initial_prompt: the initial prompt, then what fits of
+        the tokens behind max(its length, prompt_reset_since)"""
+        if self.carry_initial_prompt:
+            ipt = self.initial_prompt_tokens
+            nignored = max(len(ipt), self.reset)
+            return ipt + self.all_tokens[nignored:][-(self.n_text_ctx // 2 - 1 - len(ipt)):]
+        return self.all_tokens[self.reset:]
+
+    def sot_tail(self) -> int:
+        """tokens of the SOT sequence behind <|startoftranscript|>, <|notimestamps|> included (ccx_whisper_set_sot_tail); with the
+        prefix's length (ccx_whisper_set_prefix_len) it tells the library where to read the no-speech probability"""
+        return len(self.sot_sequence) - 1 + int(self.without_timestamps)
+
+    def initial_tokens(self) -> List[int]:
+        """decoding.py::_get_initial_tokens: [sot_prev] + prompt[-(n_ctx // 2 - 1):] + sot_sequence."""
+        p = self.prompt_tokens()
+        toks: List[int] = []
+        if len(p):
+            toks = [self.rules.sot_prev] + list(p)[-(self.n_text_ctx // 2 - 1):]
+        tail = [self.rules.no_timestamps] if self.without_timestamps else []
+        return toks + list(self.sot_sequence) + tail + self.prefix_tokens
+
+    def set_language(self, code: str) -> None:
+        """the detected language of a pending loop"""
+        self.sot_sequence = self.rules.sot_sequence(code, self.task)
+        self.language, self.language_known = code, True
+
+    def sample_cap(self) -> int:
+        """Tokens the next window may sample: decode_cap of its initial tokens."""
+        cap = decode_cap(len(self.initial_tokens()), self.n_text_ctx)
+        return cap if self.sample_len is None else min(self.sample_len, cap)
+
+    def window_segments(self, r: dict):
+        """The segments one decoded window yields, before empty ones are cleared: (segments, single_timestamp_ending, next seek by the
+        timestamp-token rule), or None when the silence rule skips the window.  Changes nothing."""
+        tsb, eot = self.rules.timestamp_begin, self.rules.eot
+        seek = self.seek
+        segment_size = self.segment_size()
+        time_offset = seek * HOP / SAMPLE_RATE
+        segment_duration = segment_size * HOP / SAMPLE_RATE
+        tokens = list(r["tokens"])
+        if self.no_speech_threshold is not None:
+            skip = r["no_speech_prob"] > self.no_speech_threshold
+            if self.logprob_threshold is not None and r["avg_logprob"] > self.logprob_threshold:
+                skip = False
+            if skip:
+                return None
+        is_ts = [t >= tsb for t in tokens]
+        single_ts_ending = is_ts[-2:] == [False, True]
+        consecutive = [i + 1 for i in range(len(tokens) - 1) if is_ts[i] and is_ts[i + 1]]
+        new_segments = []
+
+        def add(start, end, toks):
+            new_segments.append(dict(seek=seek, start=start, end=end, tokens=list(toks),
+                                     text=self.tokenizer.decode([t for t in toks if t < eot])))
+
+        if consecutive:
+            slices = list(consecutive)
+            if single_ts_ending:
+                slices.append(len(tokens))
+            last = 0
+            for cur in slices:
+                sl = tokens[last:cur]
+                add(time_offset + (sl[0] - tsb) * TIME_PRECISION, time_offset + (sl[-1] - tsb) * TIME_PRECISION, sl)
+                last = cur
+            if single_ts_ending:
+                next_seek = seek + segment_size
+            else:
+                next_seek = seek + (tokens[last - 1] - tsb) * INPUT_STRIDE
+        else:
+            duration = segment_duration
+            ts = [t for t in tokens if t >= tsb]
+            if ts and ts[-1] != tsb:
+                duration = (ts[-1] - tsb) * TIME_PRECISION
+            add(time_offset, time_offset + duration, tokens)
+            next_seek = seek + segment_size
+        return new_segments, single_ts_ending, next_seek
+
+    def advance(self, r: dict, temperature: float = 0.0, last_word_end: Optional[float] = None,
+                segments: Optional[List[dict]] = None, hallucination_silence_threshold: Optional[float] = None) -> None:
+        """One decoded window (r: tokens before eot, avg_logprob, no_speech_prob) -> segments, tokens, the next seek.
+        last_word_end (word alignment, opt-in): end of the last aligned word of this window in seconds -- when the window did not
+        end on a single timestamp and it lies behind the window's start, `seek` goes there [UPSTREAM-RECALL: transcribe.py, "if not
+        single_timestamp_ending: last_word_end = get_end(current_segments) ..."].  segments: this window's `window_segments()` after
+        add_word_timestamps worked on them (words attached, bounds moved); None: they are built here.
+        hallucination_silence_threshold (seconds; None: nothing below runs) [UPSTREAM-RECALL: transcribe.py, "skip silence before
+        possible hallucinations"; parity unpinned]: a window whose words end more than the threshold before its end resumes at the
+        last word, else at the window's end; a window whose first segment with words is anomalous (is_segment_anomaly) behind a
+        leading gap longer than the threshold is dropped whole and `seek` moves over the gap; an anomalous segment with silence (or
+        more anomalies) on both sides cuts the window there."""
+        seek = self.seek
+        self.seeks.append(seek)
+        segment_size = self.segment_size()
+        built = self.window_segments(r)
+        if built is None:
+            self.seek = seek + segment_size
+            if self.clips is not None:
+                self._settle_clip()
+            return
+        new_segments, single_ts_ending, self.seek = built
+        if segments is not None:
+            new_segments = segments
+        last_speech_before = self.last_speech_timestamp      # the previous window's: what the silence rule measures from
+        if last_word_end is not None:
+            if not single_ts_ending and last_word_end > seek * HOP / SAMPLE_RATE:
+                self.seek = round(last_word_end * FRAMES_PER_SECOND)
+            self.last_speech_timestamp = last_word_end
+        if hallucination_silence_threshold is not None:
+            thr = hallucination_silence_threshold
+            time_offset = seek * HOP / SAMPLE_RATE
+            window_end_time = (seek + segment_size) / FRAMES_PER_SECOND
+            if last_word_end is not None and not single_ts_ending and last_word_end > time_offset:
+                if window_end_time - last_word_end > thr:
+                    self.seek = round(last_word_end * FRAMES_PER_SECOND)
+                else:
+                    self.seek = seek + segment_size
+            # "if first segment might be a hallucination, skip leading silence": upstream's `continue` -- nothing of the window is kept
+            first = next_words_segment(new_segments)
+            if first is not None and is_segment_anomaly(first):
+                gap = first["start"] - time_offset
+                if gap > thr:
+                    self.seek = seek + round(gap * FRAMES_PER_SECOND)
+                    self.last_speech_timestamp = last_speech_before
+                    if self.seek <= seek:
+                        self.seek = seek + segment_size
+                    if self.clips is not None:
+                        self._settle_clip()
+                    return
+            # "skip silence before any possible hallucination that is surrounded by silence or more hallucinations"
+            hal_last_end = last_speech_before
+            for si, sg in enumerate(new_segments):
+                if not sg.get("words"):
+                    continue
+                if is_segment_anomaly(sg):
+                    nxt = next_words_segment(new_segments[si + 1:])
+                    hal_next_start = nxt["words"][0]["start"] if nxt is not None else time_offset + segment_size * HOP / SAMPLE_RATE
+                    silence_before = sg["start"] - hal_last_end > thr or sg["start"] < thr or sg["start"] - time_offset < 2.0
+                    silence_after = hal_next_start - sg["end"] > thr or is_segment_anomaly(nxt) or window_end_time - sg["end"] < 2.0
+                    if silence_before and silence_after:
+                        self.seek = round(max(time_offset + 1, sg["start"]) * FRAMES_PER_SECOND)
+                        if self.content / FRAMES_PER_SECOND - sg["end"] < thr:
+                            self.seek = self.content
+                        new_segments = new_segments[:si]
+                        break
+                hal_last_end = sg["end"]
+            end = get_end(new_segments)
+            self.last_speech_timestamp = end if end is not None else last_speech_before
+        for s in new_segments:
+            # "if a segment is instantaneous or does not contain text, clear it": its tokens do not reach the prompt or the text
+            if s["start"] == s["end"] or s["text"].strip() == "":
+                s["text"], s["tokens"] = "", []
+            self.segments.append(s)
+            self.all_tokens.extend(s["tokens"])
+        if not self.condition or temperature > 0.5:      # "do not feed the prompt tokens if a high temperature was used"
+            self.reset = len(self.all_tokens)
+        if self.seek <= seek:  # cannot happen under ApplyTimestampRules (a closing timestamp is > its opening one); never loop forever
+            self.seek = seek + segment_size
+        if self.clips is not None:
+            self._settle_clip()
+
+    def result(self) -> dict:
+        text_tokens = self.all_tokens[self.n_init:]
+        return dict(text=self.tokenizer.decode(text_tokens), segments=self.segments, language=self.language, tokens=list(text_tokens))
