@@ -80,6 +80,11 @@ DEC_ATTN_STREAM_MAPPED = 7       # (6 is no form)
 DEC_ATTN_SELF_IND = 8            # the self form through a cache indirection (beam search)
 
 
+class DecodeSamplingOptions(C.Structure):
+    """ccx_decode_sampling_options (include/ccx.h): top_k, top_p and min_p; the defaults are {0, 1.0, 0.0}."""
+    _fields_ = [("top_k", C.c_int), ("top_p", C.c_float), ("min_p", C.c_float)]
+
+
 class DecSeqState(C.Structure):
     """ccx_dec_seq_state: the select kernel's per-sequence state."""
     _fields_ = [(n, C.c_int) for n in ("pos", "prompt_len", "n_gen", "done", "last_tok", "pen_tok", "last_ts_tok", "n_tokens")] + [
@@ -96,7 +101,9 @@ class DecSelectDesc(C.Structure):
         ("tok_emb", C.c_void_p), ("pos_emb", C.c_void_p), ("x", C.c_void_p), ("D", C.c_int),
         ("sample", C.c_int), ("temperature", C.c_float), ("seed", C.c_uint64), ("row0", C.c_int),
         ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64),
-        ("stream_ids", C.POINTER(C.c_int)), ("opts", C.POINTER(DecodeOptions))]
+        ("stream_ids", C.POINTER(C.c_int)), ("opts", C.POINTER(DecodeOptions)),
+        ("sampling", C.POINTER(DecodeSamplingOptions)), ("cut_out", C.POINTER(C.c_float)), ("kept_out", C.POINTER(C.c_int)),
+        ("kept_mass_out", C.POINTER(C.c_float))]
 
 
 class DecBeamDesc(C.Structure):
@@ -320,6 +327,9 @@ PROTOTYPES = {
     "ccx_whisper_set_bias_options": (_i, [_vp, C.POINTER(DecodeBiasOptions)]),
     "ccx_whisper_bias_graph_count": (_i, [_vp]),
     "ccx_dec_bias_step": (_i, [_vp, C.POINTER(DecBiasDesc), _vp]),
+    "ccx_decode_sampling_options_default": (None, [C.POINTER(DecodeSamplingOptions)]),
+    "ccx_whisper_set_sampling_options": (_i, [_vp, C.POINTER(DecodeSamplingOptions)]),
+    "ccx_whisper_sampling_graph_count": (_i, [_vp]),
     "ccx_whisper_set_mel": (_i, [_vp, _vp, _i, _vp]),
     "ccx_whisper_encode": (_i, [_vp, _i, _vp, _vp]),
     "ccx_whisper_decoder_logits": (_i, [_vp, _i32p, _i, _i, _vp, _vp]),

@@ -206,6 +206,13 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   CCX_REQUIRE(ctx, d->sample == 0 || d->sample == 1, "ccx_dec_select_step: sample = %d must be 0 or 1", d->sample);
   CCX_REQUIRE(ctx, d->sample || d->temperature == 0.f, "ccx_dec_select_step: temperature %g needs sample = 1", (double)d->temperature);
   CCX_REQUIRE(ctx, d->temperature >= 0.f && d->row0 >= 0, "ccx_dec_select_step: temperature or row0 negative");
+  ccx_decode_sampling_options trunc{0, 1.0f, 0.0f};
+  if (d->sampling) {
+    CCX_REQUIRE(ctx, d->sample == 1, "ccx_dec_select_step: sampling options need sample = 1");
+    trunc = *d->sampling;
+    CCX_TRY(ccx_check_sampling_options(ctx, "ccx_dec_select_step", &trunc));
+  }
+  CCX_REQUIRE(ctx, d->sampling || (!d->cut_out && !d->kept_out && !d->kept_mass_out), "ccx_dec_select_step: cut_out, kept_out and kept_mass_out need sampling options");
   if (d->stream_ids)
     for (int b = 0; b < B; b++) CCX_REQUIRE(ctx, d->stream_ids[b] >= 0, "ccx_dec_select_step: stream_ids[%d] = %d is negative", b, d->stream_ids[b]);
   for (int b = 0; b < B; b++) {
@@ -240,9 +247,14 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   DO_HIP(sc.upload(&d_pos, d->pos, (size_t)B));
   DO_HIP(sc.upload(&d_gen, gen_h.data(), gen_h.size()));
   DO_HIP(sc.upload(&d_ndone, d->n_done, (size_t)1));
-  unsigned cfg[4] = {0u, (unsigned)(d->seed & 0xffffffffu), (unsigned)(d->seed >> 32), 0u};
-  memcpy(&cfg[0], &d->temperature, 4);
-  DO_HIP(sc.upload(&d_cfg, cfg, (size_t)4));
+  unsigned cfg[8];
+  ccx_fill_sample_cfg(cfg, d->temperature, d->seed, trunc);
+  DO_HIP(sc.upload(&d_cfg, cfg, (size_t)8));
+  // the truncation outputs: uploaded as the caller left them, so that rows which do not sample come back untouched
+  float *d_cut = nullptr, *d_mass = nullptr; int* d_kept = nullptr;
+  if (d->cut_out) DO_HIP(sc.upload(&d_cut, d->cut_out, (size_t)B));
+  if (d->kept_out) DO_HIP(sc.upload(&d_kept, d->kept_out, (size_t)B));
+  if (d->kept_mass_out) DO_HIP(sc.upload(&d_mass, d->kept_mass_out, (size_t)B));
 
   DecSelectParams sp;
   memset(&sp, 0, sizeof(sp));
@@ -253,6 +265,7 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   sp.max_initial_ts = max_init_ts; sp.no_rules = no_rules; sp.suppress_blank = sup_blank;
   sp.tok_emb = (const float*)d->tok_emb; sp.pos_emb = (const float*)d->pos_emb; sp.x = (float*)d->x; sp.D = D;
   sp.sample_cfg = d_cfg; sp.row0 = d->row0; sp.sample = d->sample;
+  sp.trunc = d->sampling ? 1 : 0; sp.cut_out = d_cut; sp.kept_out = d_kept; sp.kept_mass_out = d_mass;
   if (d->stream_ids) { DO_HIP(sc.upload(&d_sid, d->stream_ids, (size_t)B)); sp.stream_id = d_sid; }
   CCX_TRY(ccx_launch_dec_select(ctx, sp, B, stream));
   DO_HIP(hipStreamSynchronize(stream));
@@ -264,6 +277,9 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   DO_HIP(hipMemcpy(d->cur_tok, d_cur, (size_t)B * 4, hipMemcpyDeviceToHost));
   DO_HIP(hipMemcpy(d->pos, d_pos, (size_t)B * 4, hipMemcpyDeviceToHost));
   DO_HIP(hipMemcpy(d->n_done, d_ndone, 4, hipMemcpyDeviceToHost));
+  if (d_cut) DO_HIP(hipMemcpy(d->cut_out, d_cut, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (d_kept) DO_HIP(hipMemcpy(d->kept_out, d_kept, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (d_mass) DO_HIP(hipMemcpy(d->kept_mass_out, d_mass, (size_t)B * 4, hipMemcpyDeviceToHost));
 #undef DO_HIP
   return CCX_OK;
 }

@@ -1,5 +1,6 @@
 // decoder.h -- parameter blocks and launchers for the decoder step kernels (decoder.hip).
 #pragma once
+#include <cstring>
 #include <vector>
 #include "../../include/ccx.h"
 #include "ccx_common.h"
@@ -94,7 +95,8 @@ struct DecSelectParams {
   int eot, blank, no_speech, timestamp_begin, max_initial_ts;
   // next-step embedding written by the select kernel: x[b] = tok_emb[next] + pos_emb[pos]
   const float* tok_emb; const float* pos_emb; float* x; int D;
-  // sampling (GreedyDecoder.update with temperature > 0): sample_cfg = {float temperature, u32 seed_lo, u32 seed_hi} in
+  // sampling (GreedyDecoder.update with temperature > 0): sample_cfg = {float temperature, u32 seed_lo, u32 seed_hi, int top_k,
+  // float top_p, float min_p, 0, 0} (8 words; the plain kernels read the first three) in
   // device memory (so that a captured step graph serves every temperature / seed); row0 = batch row of sequence 0 of
   // this launch (lanes), so that the noise of a sequence does not depend on how the batch is split
   const unsigned* sample_cfg; int row0;
@@ -104,6 +106,12 @@ struct DecSelectParams {
   // launched); suppress_blank: those kernels ban rules.blank and eot on the first sampled step (the ruled kernels ban every text id
   // and eot there anyway and do not read it).  (Appended: no other field moves.)
   int no_rules, suppress_blank;
+  // truncated sampling (ccx_decode_sampling_options; dec_truncate.h).  trunc: the TRUNC instantiations (host side: which kernel is
+  // launched; needs sample); they read {int top_k, float top_p, float min_p} from sample_cfg[3 .. 5].  cut_out / kept_out /
+  // kept_mass_out: device [B] or null (the model): the smallest kept logit, |K| and the mass of K, written by rows that sampled.
+  // (Appended: no other field moves.)
+  int trunc;
+  float* cut_out; int* kept_out; float* kept_mass_out;
 };
 int ccx_launch_dec_select(ccx_ctx* ctx, const DecSelectParams& p, int B, hipStream_t stream);
 
@@ -234,6 +242,23 @@ static inline int ccx_build_suppress_mask(ccx_ctx* ctx, const char* who, const c
   }
   if (r->no_timestamps >= 0) mask[r->no_timestamps] = 1;  // ApplyTimestampRules bans <|notimestamps|>
   return CCX_OK;
+}
+
+// The checks of ccx_decode_sampling_options (written so that a NaN fails them); `who` is the entry point the messages name.
+static inline int ccx_check_sampling_options(ccx_ctx* ctx, const char* who, const ccx_decode_sampling_options* o) {
+  CCX_REQUIRE(ctx, o->top_k >= 0, "%s: opts.top_k = %d is negative", who, o->top_k);
+  CCX_REQUIRE(ctx, o->top_p > 0.f && o->top_p <= 1.f, "%s: opts.top_p = %g must lie in (0, 1]", who, (double)o->top_p);
+  CCX_REQUIRE(ctx, o->min_p >= 0.f && o->min_p <= 1.f, "%s: opts.min_p = %g must lie in [0, 1]", who, (double)o->min_p);
+  return CCX_OK;
+}
+// sample_cfg as the select kernels read it (DecSelectParams::sample_cfg)
+static inline void ccx_fill_sample_cfg(unsigned (&cfg)[8], float temperature, uint64_t seed, const ccx_decode_sampling_options& s) {
+  memset(cfg, 0, sizeof(cfg));
+  memcpy(&cfg[0], &temperature, 4);
+  cfg[1] = (unsigned)(seed & 0xffffffffu); cfg[2] = (unsigned)(seed >> 32);
+  cfg[3] = (unsigned)s.top_k;
+  memcpy(&cfg[4], &s.top_p, 4);
+  memcpy(&cfg[5], &s.min_p, 4);
 }
 
 // Its sibling for a call's options (ccx_decode_options): the options' list instead of the rules' where one is given, and

@@ -1278,11 +1278,14 @@ __device__ __forceinline__ float gumbel_from_u32(unsigned x) {
 }
 
 #define SEL_V4 13
+#include "dec_truncate.h"
 // SAMPLE = false is the greedy kernel (no noise code, no extra registers: the sampling branch costs the 1024-thread
 // block its register budget and spills); SAMPLE = true adds the temperature > 0 draw.
 // RULES = false is the decode without ApplyTimestampRules (ccx_decode_options.without_timestamps): its own instantiations, so that
 // the ruled ones keep their code and their registers.
-template <bool SAMPLE, bool RULES = true>
+// TRUNC = true (SAMPLE only) cuts the filtered row by top_k / top_p / min_p before the draw (dec_truncate.h; ccx_decode_sampling_options,
+// the three values behind {temperature, seed} in sample_cfg): again its own instantiations, for the same reason.
+template <bool SAMPLE, bool RULES = true, bool TRUNC = false>
 __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
   __shared__ float sh[16];
   __shared__ float sh_v[16];
@@ -1461,6 +1464,20 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
     // the row's noise stream: its batch row, or what the caller's table names (rows of a window subset / best_of candidates keep
     // the stream they have in any other launch geometry)
     const unsigned sid = p.stream_id ? (unsigned)p.stream_id[b] : (unsigned)(p.row0 + b);
+    float cut = -INFINITY;
+    if constexpr (TRUNC) {
+      // the row as the draw sees it: a forced-timestamp row has lost its text ids.  lnorm, taken above, stays the normaliser of the
+      // untruncated row, so sum_logprob keeps its meaning
+      const float m_row = force_ts ? bs : mx_all;
+      if (force_ts) {
+#pragma unroll
+        for (int i = 0; i < SEL_V4 * 4; i++) val[i] = (tid * 4 + (i >> 2) * 4096 + (i & 3) < tsb) ? -INFINITY : val[i];
+      }
+      if (m_row > -INFINITY)      // a row with nothing allowed: as without truncation
+        cut = dec_trunc::row_cut(val, m_row, temperature, (int)p.sample_cfg[3], __uint_as_float(p.sample_cfg[4]), __uint_as_float(p.sample_cfg[5]),
+                                 sh, sh_i, p.kept_out ? p.kept_out + b : nullptr, p.kept_mass_out ? p.kept_mass_out + b : nullptr);
+      if (tid == 0 && p.cut_out) p.cut_out[b] = cut;
+    }
     float best = -INFINITY, best_logit = -INFINITY; int best_i = 0x7fffffff;
 #pragma unroll
     for (int i = 0; i < SEL_V4; i++) {
@@ -1470,7 +1487,8 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const int v = v0 + j;
-        const float x = (force_ts && v < tsb) ? -INFINITY : val[4 * i + j];
+        float x = (force_ts && v < tsb) ? -INFINITY : val[4 * i + j];
+        if constexpr (TRUNC) x = (x < cut) ? -INFINITY : x;
         const float sc = x * inv_t + gumbel_from_u32(rr[j]);      // -inf stays -inf
         if (sc > best) { best = sc; best_i = v; best_logit = x; }
       }
@@ -1534,8 +1552,13 @@ int ccx_launch_dec_embed(ccx_ctx* ctx, const float* tok_emb, const float* pos_em
 }
 
 int ccx_launch_dec_select(ccx_ctx* ctx, const DecSelectParams& p, int B, hipStream_t stream) {
-  ccx_prof_scope ps(ctx, stream, p.no_rules ? "dec_select_kernel (no rules)" : "dec_select_kernel", 0.0, (double)B * p.n_vocab * 5.0);     // the logit row + its suppress mask
-  if (p.no_rules) {
+  ccx_prof_scope ps(ctx, stream, p.trunc ? (p.no_rules ? "dec_select_kernel (truncated, no rules)" : "dec_select_kernel (truncated)") : p.no_rules ? "dec_select_kernel (no rules)" : "dec_select_kernel", 0.0, (double)B * p.n_vocab * 5.0);     // the logit row + its suppress mask
+  if (p.trunc) {
+    // truncated sampling: the instantiations with the top_k / top_p / min_p block (a plan sets it only with sampling on)
+    if (!p.sample) return ccx_fail(ctx, CCX_ERR_ARG, "dec_select: truncation needs the sampling kernel");
+    if (p.no_rules) hipLaunchKernelGGL((dec_select_kernel<true, false, true>), dim3(B), dim3(1024), 0, stream, p);
+    else hipLaunchKernelGGL((dec_select_kernel<true, true, true>), dim3(B), dim3(1024), 0, stream, p);
+  } else if (p.no_rules) {
     if (p.sample) hipLaunchKernelGGL((dec_select_kernel<true, false>), dim3(B), dim3(1024), 0, stream, p);
     else hipLaunchKernelGGL((dec_select_kernel<false, false>), dim3(B), dim3(1024), 0, stream, p);
   } else if (p.sample) hipLaunchKernelGGL(dec_select_kernel<true>, dim3(B), dim3(1024), 0, stream, p);

@@ -79,14 +79,17 @@ struct StepPlan {
   // a sequence-bias table is set (ccx_whisper_set_bias_options; 0 in a default decode): dec_bias_kernel runs in front of
   // dec_history_kernel and the select / beam kernels.  The table itself is not in the plan: the kernel reads it through its header.
   int bias_on;
+  // truncated sampling (ccx_whisper_set_sampling_options; 0 in a default decode): the select kernel's truncating instantiation.  Set
+  // only with `sampling`, and only while one of the three values is off its default; the values themselves sit in sample_cfg.
+  int trunc_on;
   auto tie() const {
     return std::tie(b0, B, sample_len, max_prompt, select, sampling, cross_stream, cross_lds_pad, xs_active, lnfree, xs_fuse_q, fuse_cross_q,
                     xs_full_lines, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows, opt_mask, no_ts, sup_blank,
-                    max_init_ts, hist_ngram, hist_pen_bits, bias_on);
+                    max_init_ts, hist_ngram, hist_pen_bits, bias_on, trunc_on);
   }
   bool operator<(const StepPlan& o) const { return tie() < o.tie(); }
 };
-static_assert(sizeof(StepPlan) == 27 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 27,
+static_assert(sizeof(StepPlan) == 28 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 28,
               "StepPlan: ints only, and every one of them in tie()");
 
 }  // namespace
@@ -137,6 +140,8 @@ struct ccx_whisper {
   // launches of a default decode.  The buffer is allocated at the first non-empty table and keeps its address.
   bool bias_on = false;
   int* bias_tab = nullptr;
+  // the call's truncated sampling (ccx_whisper_set_sampling_options); {0, 1.0, 0.0}: off, the plans and launches of a default decode
+  ccx_decode_sampling_options trunc{0, 1.0f, 0.0f};
 
   // workspaces (encoder)
   float* lm_raw = nullptr; unsigned int* lm_max = nullptr; int *lm_n = nullptr, *lm_seek = nullptr, *lm_seg = nullptr;
@@ -147,7 +152,7 @@ struct ccx_whisper {
   float *dx = nullptr, *dx2 = nullptr, *pend = nullptr, *dq = nullptr, *dlogits = nullptr, *part_o = nullptr, *part_ml = nullptr;
   bf16_t *dattn = nullptr, *dffn = nullptr, *dxn = nullptr;
   int *cur_tok = nullptr, *pos = nullptr, *prompt = nullptr, *gen = nullptr, *n_done = nullptr;
-  unsigned* sample_cfg = nullptr;   // {temperature bits, seed lo, seed hi, 0}: read by the select kernel every step
+  unsigned* sample_cfg = nullptr;   // {temperature bits, seed lo, seed hi, top_k, top_p bits, min_p bits, 0, 0}: read by the select kernel every step
   DecSeqState* state = nullptr;
   int max_prompt_cap = 0, sample_cap = 0;
   // prompt prefill: one pass over every prompt position of every sequence (rows = sequence * P + position) instead of one
@@ -418,6 +423,7 @@ int ccx_whisper_set_rules(ccx_whisper* w, const ccx_decode_rules* r) {
   w->opts_on = false;
   w->hist = ccx_decode_history_options{1.0f, 0};
   w->bias_on = false;  // the table's targets were checked against the eot of the rules it was set under
+  w->trunc = ccx_decode_sampling_options{0, 1.0f, 0.0f};
   drop_graphs(w);      // captured step graphs bake the rule ids into the select kernel's parameters
   return CCX_OK;
 }
@@ -477,6 +483,28 @@ int ccx_whisper_history_graph_count(ccx_whisper* w) {
   if (!w) return -1;
   int n = 0;
   for (auto& g : w->graphs) n += (g.first.hist_ngram || g.first.hist_pen_bits) ? 1 : 0;
+  return n;
+}
+
+void ccx_decode_sampling_options_default(ccx_decode_sampling_options* o) {
+  if (o) *o = ccx_decode_sampling_options{0, 1.0f, 0.0f};
+}
+
+int ccx_whisper_set_sampling_options(ccx_whisper* w, const ccx_decode_sampling_options* opts) {
+  if (!w) return CCX_ERR_ARG;
+  ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, w->rules_set, "ccx_whisper_set_sampling_options: the rules are not set (ccx_whisper_set_rules)");
+  ccx_decode_sampling_options o{0, 1.0f, 0.0f};
+  if (opts) o = *opts;
+  CCX_TRY(ccx_check_sampling_options(ctx, "ccx_whisper_set_sampling_options", &o));
+  w->trunc = o;        // uploaded with {temperature, seed} by every decode: nothing captured depends on the values
+  return CCX_OK;
+}
+
+int ccx_whisper_sampling_graph_count(ccx_whisper* w) {
+  if (!w) return -1;
+  int n = 0;
+  for (auto& g : w->graphs) n += g.first.trunc_on ? 1 : 0;
   return n;
 }
 
@@ -698,7 +726,7 @@ int ccx_whisper_finalize(ccx_whisper* w) {
   CCX_TRY(w->store.alloc(&w->cur_tok, (size_t)B, true));
   CCX_TRY(w->store.alloc(&w->pos, (size_t)B, true));
   CCX_TRY(w->store.alloc(&w->n_done, (size_t)ccx_whisper::kMaxLanes, true));
-  CCX_TRY(w->store.alloc(&w->sample_cfg, (size_t)4, true));
+  CCX_TRY(w->store.alloc(&w->sample_cfg, (size_t)8, true));
   CCX_TRY(w->store.alloc(&w->state, (size_t)B, true));
   {
     const size_t R = (size_t)B * ccx_whisper::kPrefillMax;
@@ -1082,6 +1110,7 @@ int dec_head(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
     sp.state = w->state + b0; sp.prompt = w->prompt + ro * p.max_prompt; sp.max_prompt = p.max_prompt;
     sp.cur_tok = w->cur_tok + b0; sp.gen = w->gen + ro * p.sample_len; sp.x = w->dx + ro * D;
     sp.sample_cfg = w->sample_cfg; sp.row0 = b0; sp.sample = p.sampling ? 1 : 0;
+    sp.trunc = p.trunc_on;
     sp.stream_id = p.sid_on ? w->row_sid + b0 : nullptr;
     CCX_TRY(ccx_launch_dec_select(ctx, sp, B, io.stream));
   }
@@ -1311,8 +1340,8 @@ int upload_decode_state(ccx_whisper* w, const int32_t* prompt_ids, const int32_t
   CCX_HIP(w->ctx, hipMemcpyAsync(w->pos, ps.data(), B * 4, hipMemcpyHostToDevice, stream));
   CCX_HIP(w->ctx, hipMemcpyAsync(w->prompt, prompt_ids, (size_t)B * max_prompt * 4, hipMemcpyHostToDevice, stream));
   CCX_HIP(w->ctx, hipMemsetAsync(w->n_done, 0, ccx_whisper::kMaxLanes * 4, stream));
-  unsigned cfg[4] = {0u, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), 0u};
-  memcpy(&cfg[0], &temperature, 4);
+  unsigned cfg[8];
+  ccx_fill_sample_cfg(cfg, temperature, seed, w->trunc);
   CCX_HIP(w->ctx, hipMemcpyAsync(w->sample_cfg, cfg, sizeof(cfg), hipMemcpyHostToDevice, stream));
   // embedding of the first token; later steps get theirs from the select kernel
   if (!prefilled) CCX_TRY(ccx_launch_dec_embed(w->ctx, w->tok_emb_f32, w->dec_pos, w->cur_tok, w->pos, w->dx, B, w->d.n_text_state, stream));
@@ -2060,6 +2089,8 @@ int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
   base.hist_ngram = w->hist.no_repeat_ngram_size;
   if (w->hist.repetition_penalty != 1.0f) memcpy(&base.hist_pen_bits, &w->hist.repetition_penalty, 4);
   base.bias_on = w->bias_on ? 1 : 0;      // no table, set or not, is the default plan
+  // truncated sampling: {0, 1.0, 0.0}, set or not, and every decode at temperature 0 (greedy, beam) is the plan it always was
+  base.trunc_on = (base.sampling && (w->trunc.top_k != 0 || w->trunc.top_p != 1.0f || w->trunc.min_p != 0.0f)) ? 1 : 0;
   read_chain_switches(base);
   CCX_TRY(select_cross_path(w, base, stream, win ? n_windows : -1));
   if (win) CCX_TRY(upload_row_map(w, win, sids, B, stream));

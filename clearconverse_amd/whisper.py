@@ -36,6 +36,7 @@ class CallSettings(NamedTuple):
     bias: Optional[tuple] = None                                # the compiled table (offsets, ids, bias)
     sot_tail: Optional[int] = None
     prefix_len: Optional[int] = None
+    sampling: Optional[Tuple[int, float, float]] = None         # (top_k, top_p, min_p)
 
 
 class WhisperModel:
@@ -44,6 +45,7 @@ class WhisperModel:
     decoding_options = False          # and so are upstream's remaining per-call decoding options
     repetition_control = False        # and repetition_penalty / no_repeat_ngram_size
     contextual_bias = False           # and sequence_bias / bad_words_ids / hotwords
+    truncated_sampling = False        # and top_k / top_p / min_p
 
     def __init__(self, dims: WhisperDims, state_dict: Dict[str, torch.Tensor], max_batch: int = 8,
                  device: int = 0, rules: Optional[DecodeRules] = None, tokenizer=None,
@@ -51,8 +53,15 @@ class WhisperModel:
                  share_encoder_scratch_with: Optional["WhisperModel"] = None, word_alignment: bool = False,
                  alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False,
                  temperature_fallback: bool = False, beam_search: bool = False, decoding_options: bool = False,
-                 repetition_control: bool = False, contextual_bias: bool = False):
-        """contextual_bias (default False: `sequence_bias`, `bad_words_ids`, `hotwords` and `hotword_boost` are accepted and ignored):
+                 repetition_control: bool = False, contextual_bias: bool = False, truncated_sampling: bool = False):
+        """truncated_sampling (default False: a `top_k`, `top_p` or `min_p` off its default 0, 1.0, 0.0 is REFUSED with ValueError --
+        a caller who asks for a cut must not get the whole vocabulary): with it, `transcribe` / `transcribe_batch` and `decode`,
+        `decode_rows` honour them (Hugging Face's names and order: temperature, top-k, top-p, min-p; the rule is this project's,
+        include/ccx.h ccx_decode_sampling_options; parity unpinned) on every decode at temperature > 0 -- the warm rounds of a
+        fallback walk, best_of candidates included; a temperature-0 round, greedy or beam, is bit-identical to one without them.  The
+        cut is computed inside the select kernel (csrc/dec_truncate.h) after every filter; the draw is the untruncated sampler's
+        Gumbel-max over the same noise, restricted to the kept ids; sum_logprob stays the log-probability under the untruncated row.
+        contextual_bias (default False: `sequence_bias`, `bad_words_ids`, `hotwords` and `hotword_boost` are accepted and ignored):
         with it, `transcribe` / `transcribe_batch` and `decode`, `decode_rows`, `decode_beam` honour them (Hugging Face's names and
         forms for the first two, faster-whisper's name for hotwords; the rule is this project's, include/ccx.h
         ccx_decode_bias_options; parity unpinned): a bias is added to the logit of the last id of a sequence whenever the tokens THIS
@@ -116,6 +125,7 @@ class WhisperModel:
         self.decoding_options = bool(decoding_options)
         self.repetition_control = bool(repetition_control)
         self.contextual_bias = bool(contextual_bias)
+        self.truncated_sampling = bool(truncated_sampling)
         if alignment_heads is None:
             alignment_heads = [(l, h) for l in range(dims.n_text_layer // 2, dims.n_text_layer) for h in range(dims.n_text_head)]
         self.alignment_heads = [(int(l), int(h)) for l, h in alignment_heads]
@@ -226,6 +236,39 @@ class WhisperModel:
         """captured step graphs of bias plans (ccx_whisper_bias_graph_count)"""
         return int(self.lib.ccx_whisper_bias_graph_count(self.handle))
 
+    @staticmethod
+    def check_sampling_options(top_k: int, top_p: float, min_p: float):
+        """the ranges ccx_whisper_set_sampling_options checks -> (int, float, float), or ValueError naming the argument"""
+        k = top_k
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0 or k > 2 ** 31 - 1:
+            raise ValueError(f"top_k = {top_k!r} must be an integer >= 0")
+        try:
+            p = float(np.float32(top_p))       # the value the library will see
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"top_p = {top_p!r} must be a number in (0, 1]") from e
+        if not (0.0 < p <= 1.0):
+            raise ValueError(f"top_p = {top_p!r} must be a number in (0, 1]")
+        try:
+            m = float(np.float32(min_p))
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"min_p = {min_p!r} must be a number in [0, 1]") from e
+        if not (0.0 <= m <= 1.0):
+            raise ValueError(f"min_p = {min_p!r} must be a number in [0, 1]")
+        return int(k), p, m
+
+    def set_sampling_options(self, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+        """ccx_whisper_set_sampling_options (sticky, like the rules; `set_rules` resets it); (0, 1.0, 0.0) is the default decode"""
+        k, p, m = self.check_sampling_options(top_k, top_p, min_p)
+        o = _lib.DecodeSamplingOptions(k, p, m)
+        self.ctx.check(self.lib.ccx_whisper_set_sampling_options(self.handle, C.byref(o)), "ccx_whisper_set_sampling_options")
+
+    def reset_sampling_options(self):
+        self.ctx.check(self.lib.ccx_whisper_set_sampling_options(self.handle, None), "ccx_whisper_set_sampling_options")
+
+    def sampling_graph_count(self) -> int:
+        """captured step graphs of truncation plans (ccx_whisper_sampling_graph_count)"""
+        return int(self.lib.ccx_whisper_sampling_graph_count(self.handle))
+
     def set_prefix_len(self, n_prefix: int):
         """prompt tokens behind the SOT sequence (a decode with a prefix): ccx_whisper_set_prefix_len"""
         self.ctx.check(self.lib.ccx_whisper_set_prefix_len(self.handle, int(n_prefix)), "ccx_whisper_set_prefix_len")
@@ -250,11 +293,23 @@ class WhisperModel:
         history = self.check_history_options(repetition_penalty, no_repeat_ngram_size)
         return None if history == (1.0, 0) else history
 
-    def _decode_settings(self, bias_args, repetition_penalty, no_repeat_ngram_size, decoding: dict) -> CallSettings:
+    def _sampling_setting(self, top_k, top_p, min_p):
+        """the call's checked (top_k, top_p, min_p); None for the defaults (0, 1.0, 0.0).  Anything else is refused without the
+        opt-in: ValueError, like a value outside its range."""
+        sampling = self.check_sampling_options(top_k, top_p, min_p)
+        if sampling == (0, 1.0, 0.0):
+            return None
+        if not self.truncated_sampling:
+            raise ValueError("top_k / top_p / min_p need a model built with truncated_sampling=True")
+        return sampling
+
+    def _decode_settings(self, bias_args, repetition_penalty, no_repeat_ngram_size, decoding: dict,
+                         top_k=0, top_p=1.0, min_p=0.0) -> CallSettings:
         """What a single decode sets, every refusal made before anything is set: the bias compile (ValueError), the history ranges
         (ValueError), then the decoding keys (TypeError, with or without the opt-in) and `resolve` (CcxError).  **decoding is the
         subset a single decode takes: without_timestamps, suppress_blank, suppress_tokens, max_initial_timestamp."""
         bias = self._bias_setting(*bias_args)
+        sampling = self._sampling_setting(top_k, top_p, min_p)
         history = None
         if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
             history = self._history_setting(repetition_penalty, no_repeat_ngram_size)
@@ -267,17 +322,19 @@ class WhisperModel:
                 options = decoding_options.resolve(self.rules, **decoding)
             except ValueError as e:
                 raise _lib.CcxError(str(e)) from e
-        return CallSettings(options, history, bias)
+        return CallSettings(options, history, bias, sampling=sampling)
 
     def _transcribe_settings(self, n: int, hallucination_silence_threshold, without_timestamps, prefixes, suppress_blank,
                              suppress_tokens, max_initial_timestamp, sample_len, carry_initial_prompt, repetition_penalty,
-                             no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost):
+                             no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost, top_k=0, top_p=1.0,
+                             min_p=0.0):
         """What a `transcribe_batch` of n clips sets, every refusal made before anything is set -> (CallSettings, the resolved
         decoding options, every clip's prefix tokens); the last two are None without the decoding_options opt-in."""
         bias = self._bias_setting(sequence_bias, bad_words_ids, hotwords, hotword_boost)
         history = self._history_setting(repetition_penalty, no_repeat_ngram_size)
+        sampling = self._sampling_setting(top_k, top_p, min_p)
         if not self.decoding_options:
-            return CallSettings(history=history, bias=bias), None, None
+            return CallSettings(history=history, bias=bias, sampling=sampling), None, None
         try:
             opt = decoding_options.resolve(self.rules, without_timestamps, suppress_blank, suppress_tokens, max_initial_timestamp,
                                            sample_len, carry_initial_prompt)
@@ -297,12 +354,12 @@ class WhisperModel:
         tail = len(self.rules.sot_sequence()) - 1 + int(opt.without_timestamps)
         n_prefix = len(prefix_toks[0]) if n > 0 else 0
         return CallSettings(None if opt.device_default(self.rules) else opt, history, bias,
-                            tail if n > 0 and tail != self.sot_tail else None, n_prefix or None), opt, prefix_toks
+                            tail if n > 0 and tail != self.sot_tail else None, n_prefix or None, sampling), opt, prefix_toks
 
     @contextlib.contextmanager
     def _settings(self, s: CallSettings):
         """The call's settings on the instance while the body runs, for however many decodes: applied once, in one order (options, SOT
-        tail, prefix length, history, bias), and taken back in reverse -- exactly those that were applied, also when a later setter
+        tail, prefix length, history, bias, sampling), and taken back in reverse -- exactly those that were applied, also when a later setter
         or the body raises.  The SOT tail and the prefix length go back to what the instance held before."""
         with contextlib.ExitStack() as undo:
             if s.options is not None:
@@ -324,6 +381,9 @@ class WhisperModel:
             if s.bias is not None:
                 self._set_bias_table(*s.bias)
                 undo.callback(self.reset_bias_options)
+            if s.sampling is not None:
+                self.set_sampling_options(*s.sampling)
+                undo.callback(self.reset_sampling_options)
             yield
 
     def _pack_prompts(self, seqs: Sequence[Sequence[int]]):
@@ -424,7 +484,8 @@ class WhisperModel:
 
     def decode(self, prompts: Sequence[Sequence[int]], sample_len: Optional[int] = None, temperature: float = 0.0,
                seed: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None,
-               bad_words_ids=None, hotwords=None, hotword_boost=None, **decoding) -> List[dict]:
+               bad_words_ids=None, hotwords=None, hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
+               **decoding) -> List[dict]:
         """DecodingTask.run over the currently encoded windows; prompts[b] are the full initial tokens
         (sot_prev + prompt + sot).  temperature 0: argmax.  temperature > 0: one Categorical(logits / T) sample per
         step (decoding.py::GreedyDecoder.update), drawn on the device from Philox noise keyed by
@@ -435,10 +496,12 @@ class WhisperModel:
         max_initial_timestamp for this call; the prompts, the SOT tail, the prefix length and sample_len stay the caller's.
         repetition_penalty / no_repeat_ngram_size (repetition_control instances; ignored otherwise): this call's history rules.
         sequence_bias / bad_words_ids / hotwords / hotword_boost (contextual_bias instances; ignored otherwise): this call's bias
-        table, which a step adds before the history rules.  All of them are resolved first (`_decode_settings`: a refused call sets
+        table, which a step adds before the history rules.
+        top_k / top_p / min_p (truncated_sampling instances; a non-default value raises ValueError otherwise): this call's cut of the
+        distribution a temperature > 0 step draws from; without effect at temperature 0.  All of them are resolved first (`_decode_settings`: a refused call sets
         nothing) and hold for this call alone (`_settings`)."""
         settings = self._decode_settings((sequence_bias, bad_words_ids, hotwords, hotword_boost), repetition_penalty,
-                                         no_repeat_ngram_size, decoding)
+                                         no_repeat_ngram_size, decoding, top_k, top_p, min_p)
         if not (temperature >= 0.0):
             raise _lib.CcxError("temperature must be >= 0")
         B = len(prompts)
@@ -459,14 +522,15 @@ class WhisperModel:
     def decode_rows(self, prompts: Sequence[Sequence[int]], windows: Sequence[int], stream_ids: Optional[Sequence[int]] = None,
                     sample_len: Optional[int] = None, temperature: float = 0.0, seed: int = 0, n_windows: Optional[int] = None,
                     repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None,
-                    hotwords=None, hotword_boost=None, **decoding) -> List[dict]:
+                    hotwords=None, hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
+                    **decoding) -> List[dict]:
         """`decode` for len(prompts) <= max_batch rows over the currently encoded windows (ccx_whisper_decode_rows): row r decodes
         window windows[r] -- entries may repeat (best_of), need not be monotone, and windows may go unused (a fallback round decodes
         only the failing ones).  stream_ids[r]: the row's noise stream at temperature > 0 (None: r), so that its draws do not depend on
         the rows it shares the call with.  n_windows: how many windows are encoded (default: max(windows) + 1).  repetition_penalty,
-        no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost, **decoding: as `decode`."""
+        no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost, top_k, top_p, min_p, **decoding: as `decode`."""
         settings = self._decode_settings((sequence_bias, bad_words_ids, hotwords, hotword_boost), repetition_penalty,
-                                         no_repeat_ngram_size, decoding)
+                                         no_repeat_ngram_size, decoding, top_k, top_p, min_p)
         if not (temperature >= 0.0):
             raise _lib.CcxError("temperature must be >= 0")
         R = len(prompts)
@@ -718,7 +782,7 @@ class WhisperModel:
                    suppress_blank: bool = True, suppress_tokens="-1", max_initial_timestamp: Optional[float] = 1.0,
                    sample_len: Optional[int] = None, clip_timestamps="0", carry_initial_prompt: bool = False,
                    repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None,
-                   hotwords=None, hotword_boost=None, **_ignored):
+                   hotwords=None, hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, **_ignored):
         """One clip, same signature as whisper.transcribe as the reference uses it.  temperature 0 is the
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
@@ -743,7 +807,9 @@ class WhisperModel:
         On an instance built with `repetition_control=True`: repetition_penalty and no_repeat_ngram_size are honoured (see
         `transcribe_batch`); otherwise they are accepted and ignored.
         On an instance built with `contextual_bias=True`: sequence_bias, bad_words_ids, hotwords and hotword_boost are honoured (see
-        `transcribe_batch`); otherwise they are accepted and ignored."""
+        `transcribe_batch`); otherwise they are accepted and ignored.
+        On an instance built with `truncated_sampling=True`: top_k, top_p and min_p are honoured (see `transcribe_batch`); otherwise
+        a value off its default raises ValueError."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
                                      compression_ratio_threshold=compression_ratio_threshold, best_of=best_of,
                                      temperature=temperature, no_speech_threshold=no_speech_threshold,
@@ -756,7 +822,7 @@ class WhisperModel:
                                      clip_timestamps=clip_timestamps, carry_initial_prompt=carry_initial_prompt,
                                      repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                                      sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotwords=hotwords,
-                                     hotword_boost=hotword_boost)[0]
+                                     hotword_boost=hotword_boost, top_k=top_k, top_p=top_p, min_p=min_p)[0]
 
     def transcribe_batch(self, audios: Sequence, initial_prompts: Optional[Sequence[Optional[str]]] = None,
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
@@ -770,7 +836,7 @@ class WhisperModel:
                          max_initial_timestamp: Optional[float] = 1.0, sample_len: Optional[int] = None, clip_timestamps="0",
                          carry_initial_prompt: bool = False, repetition_penalty: float = 1.0,
                          no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None, hotwords=None,
-                         hotword_boost=None) -> List[dict]:
+                         hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> List[dict]:
         """Independent clips decoded together (each window of each clip is one sequence of a batch).
         languages[i] (multilingual models): the clip's language code or name; None: detected on the clip's first window, after its
         group's `encode` and before its `decode` [UPSTREAM-RECALL: transcribe.py, `if decode_options.get("language") is None`].
@@ -811,12 +877,17 @@ class WhisperModel:
         hotwords (a phrase or a list of them, with hotword_boost, which has no default) are compiled into one table
         (`decode_bias.compile_bias_table`) that holds for every window of the call and every round of a fallback walk (one
         ccx_whisper_set_bias_options per call, no table set when it returns); what the compile refuses raises ValueError.  A window
-        matches over what that window's decode sampled only.  Without the opt-in all four are ignored."""
+        matches over what that window's decode sampled only.  Without the opt-in all four are ignored.
+        truncated_sampling instances: top_k (>= 0; 0 = off), top_p (in (0, 1]; 1 = off) and min_p (in [0, 1]; 0 = off) hold for every
+        decode of the call at temperature > 0 -- a single positive temperature, the warm rounds of a fallback walk, every best_of
+        candidate (one ccx_whisper_set_sampling_options per call, the defaults back when it returns); a temperature-0 round, greedy
+        or beam, is what it is without them, and so are the thresholds: avg_logprob stays the log-probability under the untruncated
+        distribution.  A value outside its range raises ValueError; so does a value off its default without the opt-in."""
         n = len(audios)
         settings, opt, prefix_toks = self._transcribe_settings(
             n, hallucination_silence_threshold, without_timestamps, prefixes, suppress_blank, suppress_tokens, max_initial_timestamp,
             sample_len, carry_initial_prompt, repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords,
-            hotword_boost)
+            hotword_boost, top_k, top_p, min_p)
         schedule, walk_on, best_of, beam_size, patience, length_penalty = self._walk_options(temperature, best_of, beam_size, patience,
                                                                                             length_penalty)
         with_words = bool(word_timestamps) and self.word_alignment

@@ -289,6 +289,43 @@ int ccx_whisper_set_bias_options(ccx_whisper* w, const ccx_decode_bias_options* 
 /* Captured step graphs of bias plans the instance holds (a test aid, like ccx_whisper_history_graph_count); -1 for a NULL handle. */
 int ccx_whisper_bias_graph_count(ccx_whisper* w);
 
+/* Truncated sampling per call: top_k, top_p and min_p, as Hugging Face `generate` names them (the rule is ours, in the form of HF's
+ * TopKLogitsWarper, TopPLogitsWarper and MinPLogitsWarper applied after the temperature, in that order; parity unpinned; restated in
+ * tests/truncation_reference.py).  ccx_decode_sampling_options_default fills {0, 1.0f, 0.0f}: all off.  For one row in the sampling
+ * phase of a decode at temperature T > 0, x = the row after EVERY filter of the select kernel (SuppressTokens, SuppressBlank,
+ * ApplyTimestampRules, and the ban on text ids where the timestamp mass forces a timestamp), A = {v : x_v > -inf}, p = softmax(x / T)
+ * over A:
+ *   1. top_k (>= 0; 0 = off): c1 = the k-th largest x over A, multiplicity counted (the minimum when |A| < k); keep x_v >= c1.  Ties
+ *      at the k-th value all stay, as in HF.
+ *   2. top_p (0 < top_p <= 1; 1 = off): over the survivors of 1, renormalised, keep v iff the mass of the survivors with x_u > x_v
+ *      (strictly) is < top_p.  Without ties this is HF's removal of `cumulative_probs <= 1 - top_p`.  DEVIATION from HF, stated: of
+ *      equal values HF keeps whichever its sort put last; here a tie is kept or dropped as a whole.
+ *   3. min_p (0 <= min_p <= 1; 0 = off): keep v iff x_v >= x_max + T * ln(min_p), evaluated in fp32 as written (product and sum each
+ *      rounded); HF's p_v >= min_p * p_max in logit space.
+ *   All three keep an upper set of x, so K = {v : x_v >= cut} for one value cut; the maximum always survives.  The draw is the
+ *   Gumbel-max of the untruncated sampler over the same Philox stream (seed, stream id, step, vocabulary id), restricted to K: a draw
+ *   that lands in K is the draw an untruncated decode makes.  sum_logprob keeps its meaning, the unscaled log-softmax over the
+ *   filtered UNTRUNCATED row; no_speech_prob is untouched; a row with A empty, a finished row and a row in its prompt phase behave as
+ *   without truncation.  At T == 0 the three values have no effect.  The mass is exp2((x - max) * log2(e) / T) in fp32, summed in one
+ *   fixed order without atomics (csrc/dec_truncate.h inside dec_select_kernel<SAMPLE, RULES, TRUNC = true>): the same row, seed and
+ *   stream id give the same token in every launch geometry.
+ * ccx_whisper_set_sampling_options is sticky like ccx_whisper_set_history_options (NULL: back to the defaults), needs the rules, is
+ * reset by ccx_whisper_set_rules, and is checked: CCX_ERR_ARG (1) naming "ccx_whisper_set_sampling_options" and the field for
+ * top_k < 0, top_p NaN or outside (0, 1], min_p NaN or outside [0, 1].  The three values live in device memory beside {temperature,
+ * seed}, so a captured step graph serves every value; ONE step-plan field says whether truncation is on (any value off its default,
+ * in a decode with T > 0): with {0, 1.0, 0.0}, set or not, a decode takes the plan, the launches and the graphs it always took.
+ * ccx_whisper_decode and _decode_rows honour the setting on every cross-attention path and in every lane; ccx_whisper_decode_greedy
+ * and _decode_beam ignore it. */
+typedef struct ccx_decode_sampling_options {
+  int top_k;
+  float top_p;
+  float min_p;
+} ccx_decode_sampling_options;
+void ccx_decode_sampling_options_default(ccx_decode_sampling_options* opts);
+int ccx_whisper_set_sampling_options(ccx_whisper* w, const ccx_decode_sampling_options* opts);
+/* Captured step graphs of truncation plans the instance holds (a test aid, like ccx_whisper_history_graph_count); -1 for a NULL handle. */
+int ccx_whisper_sampling_graph_count(ccx_whisper* w);
+
 /* Log-mel of B clips (whisper.audio.log_mel_spectrogram + pad_or_trim to 3000 frames).
  * audio_dev: [B, stride] f32; n_samples / seek_frames: host int arrays (seek may be NULL = 0).
  * Fills the model's conv-stem input; if mel_out_dev != NULL also writes [B, n_mels, 3000] f32. */
@@ -440,6 +477,12 @@ typedef struct ccx_dec_select_desc {
   int64_t logits_elems, tok_emb_elems, pos_emb_elems, x_elems;
   const int* stream_ids;                                      /* HOST [B] (>= 0) or NULL: the noise stream of row b instead of row0 + b */
   const ccx_decode_options* opts;                             /* NULL: the rules alone (appended: nothing before it moves) */
+  /* truncated sampling (appended: nothing before it moves).  sampling != NULL launches the truncating instantiation (needs sample = 1;
+   * checked as ccx_whisper_set_sampling_options checks it), whatever the three values are.  cut_out / kept_out / kept_mass_out: HOST
+   * [B] or NULL, written only for rows that sampled in this launch (temperature > 0, not done, not in the prompt phase): the smallest
+   * kept logit (-inf for a row with nothing allowed), |K|, and the mass of K under softmax(x / T).  They need `sampling`. */
+  const ccx_decode_sampling_options* sampling;
+  float* cut_out; int* kept_out; float* kept_mass_out;
 } ccx_dec_select_desc;
 
 /* One launch of the select kernel (ccx_launch_dec_select) for B rows: filters, argmax / sampling, the per-sequence state machine and
