@@ -80,6 +80,15 @@ DEC_ATTN_STREAM_MAPPED = 7       # (6 is no form)
 DEC_ATTN_SELF_IND = 8            # the self form through a cache indirection (beam search)
 
 
+class DecLnLinearDesc(C.Structure):
+    """ccx_dec_ln_linear_desc (include/ccx.h): a LayerNorm -> linear pair of the > 16-row decode chain on its own."""
+    _fields_ = [
+        ("M", C.c_int), ("K", C.c_int), ("F", C.c_int), ("N", C.c_int), ("epi", C.c_int), ("packed", C.c_int),
+        ("x", C.c_void_p), ("ln_g", C.c_void_p), ("ln_b", C.c_void_p), ("eps", C.c_float),
+        ("w1_host", C.c_void_p), ("b1", C.c_void_p), ("w_host", C.c_void_p), ("bias", C.c_void_p),
+        ("out", C.c_void_p), ("x_elems", C.c_int64), ("out_elems", C.c_int64)]
+
+
 class DecodeSamplingOptions(C.Structure):
     """ccx_decode_sampling_options (include/ccx.h): top_k, top_p and min_p; the defaults are {0, 1.0, 0.0}."""
     _fields_ = [("top_k", C.c_int), ("top_p", C.c_float), ("min_p", C.c_float)]
@@ -335,6 +344,7 @@ PROTOTYPES = {
     "ccx_whisper_decoder_logits": (_i, [_vp, _i32p, _i, _i, _vp, _vp]),
     "ccx_whisper_decode_greedy": (_i, [_vp, _i32p, _i32p, _i, _i, _i, _i32p, _i32p, _fp, _fp, _vp]),
     "ccx_dec_attention_desc": (_i, [_vp, _i, C.POINTER(DecAttnDesc), _vp]),
+    "ccx_dec_ln_linear": (_i, [_vp, C.POINTER(DecLnLinearDesc), _vp]),
     "ccx_dec_select_step": (_i, [_vp, C.POINTER(DecSelectDesc), _vp]),
     "ccx_dec_beam_step": (_i, [_vp, C.POINTER(DecBeamDesc), _vp]),
     "ccx_whisper_decode_beam": (_i, [_vp, _i32p, _i32p, _i, _i, _i32p, _i, _i, _i, _i, _i32p, _i32p, _fp, _i32p, _fp,

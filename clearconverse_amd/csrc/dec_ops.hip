@@ -1,5 +1,5 @@
 // dec_ops.hip -- the decode step's attention forms and its token-select kernel as stand-alone operators of the C ABI (include/ccx.h:
-// ccx_dec_attention_desc, ccx_dec_select_step).  For kernel parity tests: each entry point fills the parameter block the model handle
+// ccx_dec_attention_desc, ccx_dec_ln_linear, ccx_dec_select_step).  For kernel parity tests: each entry point fills the parameter block the model handle
 // fills (whisper.hip dec_step / dec_head) and calls the production launchers of decoder.hip unchanged.  Everything the kernels assume is
 // checked on the host first; scratch is owned here and freed on every path.
 #include "../../include/ccx.h"
@@ -168,6 +168,104 @@ extern "C" int ccx_dec_attention_desc(ccx_ctx* ctx, int form, const ccx_dec_attn
   if (rc == CCX_OK && final_out) {
     hipLaunchKernelGGL(dec_ops_bf16_to_f32_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, d_out16, (float*)d->out, n_out);
     DO_HIP(hipGetLastError());
+  }
+  DO_HIP(hipStreamSynchronize(stream));      // the scratch is freed on return
+  return rc;
+}
+
+namespace {
+
+// bf16 rows [M][K], row-major or as the fragment image, widened to row-major f32
+__global__ void dec_ops_rows_to_f32_kernel(const bf16_t* __restrict__ in, float* __restrict__ out, int M, int K, int packed) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)M * K) return;
+  const int m = (int)(i / K), k = (int)(i - (long)m * K);
+  out[i] = bf16_to_f32(in[packed ? dec_frag_off(m, k, K >> 5) : i]);
+}
+
+}  // namespace
+
+extern "C" int ccx_dec_ln_linear(ccx_ctx* ctx, const ccx_dec_ln_linear_desc* d, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_ln_linear: desc is NULL");
+  const int M = d->M, K = d->K, F = d->F, N = d->N, epi = d->epi, packed = d->packed;
+  CCX_REQUIRE(ctx, M >= 1 && M <= 4096, "ccx_dec_ln_linear: M = %d out of range [1, 4096]", M);
+  CCX_REQUIRE(ctx, K >= 32 && K % 32 == 0 && K <= 1280, "ccx_dec_ln_linear: K = %d must be a multiple of 32 in [32, 1280]", K);
+  CCX_REQUIRE(ctx, F == 0 || (F >= 32 && F % 32 == 0 && F <= 5120), "ccx_dec_ln_linear: F = %d must be 0 or a multiple of 32 up to 5120", F);
+  CCX_REQUIRE(ctx, N >= 4 && N % 4 == 0 && N <= 8192, "ccx_dec_ln_linear: N = %d must be a multiple of 4 in [4, 8192]", N);
+  CCX_REQUIRE(ctx, epi >= CCX_DEC_EPI_PARTIAL && epi <= CCX_DEC_EPI_GELU, "ccx_dec_ln_linear: unknown epi %d", epi);
+  CCX_REQUIRE(ctx, packed == 0 || packed == 1, "ccx_dec_ln_linear: packed = %d must be 0 or 1", packed);
+  CCX_REQUIRE(ctx, epi != CCX_DEC_EPI_SELF_QKV || (F == 0 && K % 64 == 0 && N == 3 * K), "ccx_dec_ln_linear: SELF_QKV needs F == 0, K a multiple of 64 and N == 3 K");
+  CCX_REQUIRE(ctx, epi != CCX_DEC_EPI_GELU || N % 32 == 0, "ccx_dec_ln_linear: the GELU epilogue needs N = %d to be a multiple of 32", N);
+  const int Kin = F > 0 ? F : K;                       // input columns of the last linear
+  const int depi = epi == CCX_DEC_EPI_PARTIAL ? DEPI_PARTIAL : epi == CCX_DEC_EPI_F32 ? DEPI_F32 : epi == CCX_DEC_EPI_SELF_QKV ? DEPI_SELF_QKV : DEPI_BF16_GELU;
+  const int ksplit = ccx_dec_linear_ksplit(Kin, depi);
+  CCX_REQUIRE(ctx, epi == CCX_DEC_EPI_PARTIAL || ksplit == 1, "ccx_dec_ln_linear: %d input columns need the PARTIAL epilogue", Kin);
+  CCX_REQUIRE(ctx, ksplit <= 4, "ccx_dec_ln_linear: %d input columns leave %d slabs (at most 4)", Kin, ksplit);
+  CCX_REQUIRE(ctx, d->x && d->ln_g && d->ln_b && d->w_host && d->out, "ccx_dec_ln_linear: x, ln_g, ln_b, w_host or out is NULL");
+  CCX_REQUIRE(ctx, F == 0 || d->w1_host, "ccx_dec_ln_linear: w1_host is NULL with F = %d", F);
+  CCX_REQUIRE(ctx, ccx_aligned16(d->x) && ccx_aligned16(d->ln_g) && ccx_aligned16(d->ln_b) && ccx_aligned16(d->out) && ccx_aligned16(d->b1) && ccx_aligned16(d->bias),
+              "ccx_dec_ln_linear: x, ln_g, ln_b, b1, bias or out not 16-byte aligned");
+  CCX_REQUIRE(ctx, (int64_t)M * K <= d->x_elems, "ccx_dec_ln_linear: x is read up to element %ld, x_elems=%ld", (long)M * K, (long)d->x_elems);
+  const int64_t n_out = epi == CCX_DEC_EPI_PARTIAL ? (int64_t)ksplit * M * N : epi == CCX_DEC_EPI_SELF_QKV ? (int64_t)3 * M * K : (int64_t)M * N;
+  CCX_REQUIRE(ctx, n_out <= d->out_elems, "ccx_dec_ln_linear: out is written up to element %ld, out_elems=%ld", (long)n_out, (long)d->out_elems);
+
+  ccx_op_scratch sc;
+  const size_t Mp = (size_t)(M + 15) / 16 * 16;        // whole 16-row tiles
+  bf16_t *d_xn = nullptr, *d_ffn = nullptr, *d_w1 = nullptr, *d_w = nullptr, *d_g16 = nullptr, *d_ck = nullptr, *d_cv = nullptr;
+  float* d_pend = nullptr; int* d_pos = nullptr;
+  DO_HIP(sc.alloc(&d_xn, Mp * K));
+  DO_HIP(hipMemsetAsync(d_xn, 0xFF, Mp * K * 2, stream));
+  DO_HIP(sc.alloc(&d_pend, (size_t)M * K));             // slab 0 is read with weight 0
+  DO_HIP(hipMemsetAsync(d_pend, 0, (size_t)M * K * 4, stream));
+  DO_HIP(hipMemsetAsync(d->out, 0xFF, (size_t)n_out * 4, stream));
+  {
+    const std::vector<bf16_t> pw = pack_mfma_rows(d->w_host, N, Kin, 32);
+    DO_HIP(sc.upload(&d_w, pw.data(), pw.size()));
+  }
+  int rc = ccx_launch_dec_resolve_ln(ctx, (const float*)d->x, d_pend, 0, (long)M * K, (const float*)d->ln_g, (const float*)d->ln_b, d_xn, nullptr, M, K,
+                                     d->eps, stream, nullptr, packed);
+  const bf16_t* act = d_xn;
+  if (rc == CCX_OK && F > 0) {
+    const std::vector<bf16_t> pw1 = pack_mfma_rows(d->w1_host, F, K, 32);
+    DO_HIP(sc.upload(&d_w1, pw1.data(), pw1.size()));
+    DO_HIP(sc.alloc(&d_ffn, Mp * F));
+    DO_HIP(hipMemsetAsync(d_ffn, 0xFF, Mp * F * 2, stream));
+    DecLinearParams lp;
+    memset(&lp, 0, sizeof(lp));
+    lp.M = M; lp.N = F; lp.K = K; lp.W = d_w1; lp.ldw = K; lp.bias = (const float*)d->b1; lp.act = d_xn; lp.lda = K; lp.act_packed = packed;
+    lp.out = d_ffn; lp.ldo = F; lp.out_packed = packed;
+    rc = ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_BF16_GELU, lp, stream);
+    act = d_ffn;
+  }
+  if (rc == CCX_OK) {
+    DecLinearParams lp;
+    memset(&lp, 0, sizeof(lp));
+    lp.M = M; lp.N = N; lp.K = Kin; lp.W = d_w; lp.ldw = Kin; lp.bias = (const float*)d->bias; lp.act = act; lp.lda = Kin; lp.act_packed = packed;
+    lp.out = d->out; lp.ldo = N; lp.pend_stride = (long)M * N;
+    if (epi == CCX_DEC_EPI_SELF_QKV) {
+      const std::vector<int> pos((size_t)M, 0);
+      DO_HIP(sc.upload(&d_pos, pos.data(), pos.size()));
+      DO_HIP(sc.alloc(&d_ck, (size_t)M * K)); DO_HIP(sc.alloc(&d_cv, (size_t)M * K));
+      DO_HIP(hipMemsetAsync(d_ck, 0xFF, (size_t)M * K * 2, stream)); DO_HIP(hipMemsetAsync(d_cv, 0xFF, (size_t)M * K * 2, stream));
+      lp.ldo = K; lp.cache_k = d_ck; lp.cache_v = d_cv; lp.cache_T = 1; lp.pos = d_pos;
+    } else if (epi == CCX_DEC_EPI_GELU) {
+      DO_HIP(sc.alloc(&d_g16, Mp * N));
+      DO_HIP(hipMemsetAsync(d_g16, 0xFF, Mp * N * 2, stream));
+      lp.out = d_g16; lp.out_packed = packed;
+    }
+    rc = ccx_launch_dec_linear(ctx, ACT_BF16, depi, lp, stream);
+    if (rc == CCX_OK && epi == CCX_DEC_EPI_SELF_QKV) {
+      const long n = (long)M * K;
+      hipLaunchKernelGGL(dec_ops_rows_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_ck, (float*)d->out + n, M, K, 0);
+      hipLaunchKernelGGL(dec_ops_rows_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_cv, (float*)d->out + 2 * n, M, K, 0);
+      DO_HIP(hipGetLastError());
+    } else if (rc == CCX_OK && epi == CCX_DEC_EPI_GELU) {
+      const long n = (long)M * N;
+      hipLaunchKernelGGL(dec_ops_rows_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_g16, (float*)d->out, M, N, packed);
+      DO_HIP(hipGetLastError());
+    }
   }
   DO_HIP(hipStreamSynchronize(stream));      // the scratch is freed on return
   return rc;

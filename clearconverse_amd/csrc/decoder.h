@@ -33,6 +33,10 @@ struct DecLinearParams {
   // DEPI_SELF_QKV: q -> out (f32 [M][K]), k/v -> caches [sequence][H][cache_T][64] at pos[m]; the sequence of row m is
   // row_seq[m] (prompt prefill: several rows per sequence) or m itself when row_seq is null
   bf16_t* cache_k; bf16_t* cache_v; int cache_T; const int* pos; const int* row_seq;
+  // ACT_BF16 only.  act_packed: `act` is the fragment image of the rows instead (dec_frag_off: ceil(M / 16) x K / 32 tiles of 1 KB, so a
+  // wave load is 1 KB contiguous and not 16 rows x 64 B; lda is not read).  DEPI_BF16_GELU, out_packed: `out` is written as that
+  // image of [M][N] (N a multiple of 32; ldo is not read).  The values a lane holds, and so the results, are the same either way.
+  int act_packed, out_packed;
 };
 int ccx_launch_dec_linear(ccx_ctx* ctx, int act, int epi, const DecLinearParams& p, hipStream_t stream);
 // number of grid.z K-slices ccx_launch_dec_linear will use (= number of partial slabs written)
@@ -41,7 +45,17 @@ int ccx_dec_linear_ksplit(int K, int epi);
 // also every row's centring shift from its LayerNorm statistics (the same bits the ACT_LN prologue of dec_linear computes)
 int ccx_launch_dec_resolve_ln(ccx_ctx* ctx, const float* x, const float* pend, int pend_n, long pend_stride, const float* g,
                               const float* b, bf16_t* out, float* x_out, int M, int K, float eps, hipStream_t stream,
-                              float* mean_out = nullptr);
+                              float* mean_out = nullptr, int out_packed = 0);
+
+// The fragment image of a bf16 activation matrix [M][K] (K a multiple of 32), the layout pack_mfma_rows gives the weights: tile
+// (m / 16, k / 32) holds the 64 lanes' 16-byte MFMA operands back to back, lane l = row m0 + (l & 15), columns k0 + 8 (l >> 4) .. + 7.
+// Element offset of (m, k); 8 consecutive k from a multiple of 8 on stay together.  The image takes ceil(M / 16) * 16 * K elements.
+__host__ __device__ __forceinline__ long dec_frag_off(int m, int k, int ksteps) {
+  return (((long)(m >> 4) * ksteps + (k >> 5)) * 64 + (((k >> 3) & 3) * 16 + (m & 15))) * 8 + (k & 7);
+}
+// CCX_DEC_PACKED_ACT (default 1; read per decode): the > 16-row chain hands its LayerNorm rows and its GELU rows from kernel to kernel
+// as fragment images; 0: row-major, as the <= 16-row chain and every other reader of these buffers keep them
+int ccx_dec_packed_act_switch();
 
 struct DecAttnParams {
   const float* q;       // [B][H][64] f32

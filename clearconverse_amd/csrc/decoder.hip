@@ -184,15 +184,20 @@ __global__ __launch_bounds__(64 * NW, (KMAX > 8 && ACT == ACT_LN) ? 2 : 1) void 
   }
   bf16x8 af[MT][KMAX];
   if (BF16IN) {
+    // row-major rows: 16 rows x 64 B per wave load, k-steps 64 B apart; act_packed (decoder.h): the rows' fragment image, 1 KB
+    // contiguous per wave load like the weights, k-steps 1 KB apart.  Either way lane l gets row l & 15, columns 8 (l >> 4) .. + 7.
+    const int kstride = p.act_packed ? 512 : 32;
 #pragma unroll
     for (int j = 0; j < MT; j++) {
       int m = m0 + 16 * j + l15;
       m = m < p.M ? m : p.M - 1;  // rows >= M compute garbage that is never stored
-      const bf16_t* ar = p.act + (long)m * p.lda + 8 * h4 + 32 * ks0;
+      int mt = blockIdx.y * MT + j;
+      mt = mt <= ((p.M - 1) >> 4) ? mt : ((p.M - 1) >> 4);   // (tiles behind the image: re-read its last one)
+      const bf16_t* ar = p.act_packed ? p.act + (((long)mt * ksteps + (nks > 0 ? ks0 : 0)) * 64 + lane) * 8 : p.act + (long)m * p.lda + 8 * h4 + 32 * ks0;
 #pragma unroll
       for (int k = 0; k < KMAX; k++) {
         const int kk = k < nks ? k : 0;
-        af[j][k] = *(const bf16x8*)(ar + 32 * kk);
+        af[j][k] = *(const bf16x8*)(ar + kstride * kk);
       }
     }
   }
@@ -354,7 +359,8 @@ __global__ __launch_bounds__(64 * NW, (KMAX > 8 && ACT == ACT_LN) ? 2 : 1) void 
     v[0] += bias_v[it].x; v[1] += bias_v[it].y; v[2] += bias_v[it].z; v[3] += bias_v[it].w;
     const bool full = n + 3 < p.N;       // N is a multiple of 4 everywhere but a guard costs nothing
     if (EPI == DEPI_BF16_GELU) {
-      bf16_t* o = (bf16_t*)p.out + (long)m * p.ldo + n;
+      // out_packed: the quad's 8 bytes go into the fragment image the next linear loads (N % 32 == 0, so every quad is full)
+      bf16_t* o = (bf16_t*)p.out + (BF16IN && p.out_packed ? dec_frag_off(m, n, p.N >> 5) : (long)m * p.ldo + n);
       if (full) {
         uint2 pk;
         pk.x = pack_bf16x2(gelu_erf(v[0]), gelu_erf(v[1]));
@@ -395,7 +401,7 @@ __global__ __launch_bounds__(256) void dec_resolve_ln_kernel(const float* __rest
                                                              int pend_n, long pend_stride, const float* __restrict__ g,
                                                              const float* __restrict__ b, bf16_t* __restrict__ out,
                                                              float* __restrict__ x_out, int M, int K, float eps,
-                                                             float* __restrict__ mean_out) {
+                                                             float* __restrict__ mean_out, int out_packed) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= M) return;
@@ -436,7 +442,8 @@ __global__ __launch_bounds__(256) void dec_resolve_ln_kernel(const float* __rest
 #pragma unroll
   for (int i = 0; i < NS; i++) {
     const int idx = lane + 64 * i;
-    if (idx < nv) ((uint2*)(out + (long)m * K))[idx] = ln_pack4(v[i], mean, rstd, gg[i], bb[i]);
+    // out_packed: the row's 8-byte pieces go into the fragment image the next linear loads (decoder.h dec_frag_off)
+    if (idx < nv) *(uint2*)(out + (out_packed ? dec_frag_off(m, 4 * idx, K >> 5) : (long)m * K + 4 * idx)) = ln_pack4(v[i], mean, rstd, gg[i], bb[i]);
   }
 }
 
@@ -476,17 +483,18 @@ int ccx_launch_dec_combine(ccx_ctx* ctx, const float* part_o, const float* part_
 
 int ccx_launch_dec_resolve_ln(ccx_ctx* ctx, const float* x, const float* pend, int pend_n, long pend_stride, const float* g,
                               const float* b, bf16_t* out, float* x_out, int M, int K, float eps, hipStream_t stream,
-                              float* mean_out) {
+                              float* mean_out, int out_packed) {
   CCX_REQUIRE(ctx, K % 4 == 0 && K <= 1280, "dec_resolve_ln: K=%d unsupported (a multiple of 4, at most 1280)", K);
+  CCX_REQUIRE(ctx, !out_packed || K % 32 == 0, "dec_resolve_ln: the fragment image needs K=%d to be a multiple of 32", K);
   CCX_REQUIRE(ctx, x_out != x, "dec_resolve_ln: x_out must not alias x");
   // bytes: the residual rows and their pending slabs in, the bf16 rows (and the resolved fp32 rows) out
   ccx_prof_scope ps(ctx, stream, "dec_resolve_ln_kernel", 0.0, (double)M * K * (4.0 * (1 + pend_n) + 2.0 + (x_out ? 4.0 : 0.0)));
   if (K <= 1024)
     hipLaunchKernelGGL(dec_resolve_ln_kernel<4>, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, pend, pend_n, pend_stride, g, b,
-                       out, x_out, M, K, eps, mean_out);
+                       out, x_out, M, K, eps, mean_out, out_packed);
   else
     hipLaunchKernelGGL(dec_resolve_ln_kernel<5>, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, pend, pend_n, pend_stride, g, b,
-                       out, x_out, M, K, eps, mean_out);
+                       out, x_out, M, K, eps, mean_out, out_packed);
   CCX_CHECK_LAUNCH(ctx);
   return CCX_OK;
 }
@@ -538,6 +546,11 @@ static int launch_dec_linear_mt(ccx_ctx* ctx, const DecLinearParams& p, int kspl
   return launch_dec_linear_inst<4, NT, 10, ACT, EPI>(ctx, p, ksplit, stream);
 }
 
+int ccx_dec_packed_act_switch() {
+  const char* e = getenv("CCX_DEC_PACKED_ACT");
+  return !(e && strcmp(e, "0") == 0);
+}
+
 int ccx_dec_linear_ksplit(int K, int epi) {
   // prefetch depth is 8 k-steps (256 elements) per wave, 4 waves per block -- or 10 (320 elements), taken only where 8 cannot serve:
   // a non-partial epilogue at 1024 < K <= 1280, and partial outputs whose 1024-wide slabs would outnumber the 4 pending slabs the
@@ -553,6 +566,8 @@ int ccx_launch_dec_linear(ccx_ctx* ctx, int act, int epi, const DecLinearParams&
   CCX_REQUIRE(ctx, p.M > 0 && p.N > 0 && p.K > 0 && p.K % 32 == 0, "dec_linear: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
   CCX_REQUIRE(ctx, act == ACT_BF16 || p.K <= 1280, "dec_linear: LN/combine activation needs K <= 1280");
   CCX_REQUIRE(ctx, p.pend_n >= 0 && p.pend_n <= 4, "dec_linear: at most 4 pending slabs");
+  CCX_REQUIRE(ctx, !p.act_packed || act == ACT_BF16, "dec_linear: act_packed is taken with bf16 activations only");
+  CCX_REQUIRE(ctx, !p.out_packed || (act == ACT_BF16 && epi == DEPI_BF16_GELU && p.N % 32 == 0), "dec_linear: out_packed needs the GELU epilogue and N=%d a multiple of 32", p.N);
   const int ksplit = ccx_dec_linear_ksplit(p.K, epi);
   CCX_REQUIRE(ctx, epi == DEPI_PARTIAL || ksplit == 1, "dec_linear: K=%d needs a split-K (partial) epilogue", p.K);
   CCX_REQUIRE(ctx, ksplit <= 4, "dec_linear: K=%d would leave %d partial slabs (at most 4)", p.K, ksplit);

@@ -61,7 +61,7 @@ struct StepPlan {
                                   // 0 (teacher-forced passes): split-KV partials + dec_combine_kernel
   int cross_lds_pad;              // occupancy cap of the cross-attention blocks while lanes overlap (plan_lanes)
   int xs_active;                  // cross attention against the encoder output (select_cross_path)
-  int lnfree, xs_fuse_q, fuse_cross_q, xs_full_lines;   // the chain's form (read_chain_switches)
+  int lnfree, xs_fuse_q, fuse_cross_q, xs_full_lines, packed_act;   // the chain's form (read_chain_switches)
   int map_on, sid_on;             // the rows read a row -> window map / a stream-id table (ccx_whisper_decode_rows)
   int beam_size, beam_maxc;       // beam search (0: none) and its max_candidates
   int lane_idx;                   // whose stamp trace and stagger slot
@@ -84,12 +84,12 @@ struct StepPlan {
   int trunc_on;
   auto tie() const {
     return std::tie(b0, B, sample_len, max_prompt, select, sampling, cross_stream, cross_lds_pad, xs_active, lnfree, xs_fuse_q, fuse_cross_q,
-                    xs_full_lines, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows, opt_mask, no_ts, sup_blank,
+                    xs_full_lines, packed_act, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows, opt_mask, no_ts, sup_blank,
                     max_init_ts, hist_ngram, hist_pen_bits, bias_on, trunc_on);
   }
   bool operator<(const StepPlan& o) const { return tie() < o.tie(); }
 };
-static_assert(sizeof(StepPlan) == 28 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 28,
+static_assert(sizeof(StepPlan) == 29 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 29,
               "StepPlan: ints only, and every one of them in tie()");
 
 }  // namespace
@@ -859,12 +859,14 @@ static int project_cross_kv(ccx_whisper* w, int n, hipStream_t stream) {
 // The switches of the decode chain's form, read per call (tests flip them) by BOTH entry points that run dec_step -- decodes and
 // ccx_whisper_decoder_logits -- so that the teacher-forced logits always come from the chain a decode of the same size would run.
 // CCX_FUSE_CROSS_Q=0: the two-launch cross-attention query of <= 16 rows; CCX_DEC_LNFREE=0: round 3's X-stream query;
-// CCX_XS_FUSE_Q=0: that query as a launch of its own; CCX_XS_FULL_LINES=0: the streaming kernel's half-line loads (cross_x.h).
+// CCX_XS_FUSE_Q=0: that query as a launch of its own; CCX_XS_FULL_LINES=0: the streaming kernel's half-line loads (cross_x.h);
+// CCX_DEC_PACKED_ACT=0: the > 16-row chain's LayerNorm and GELU rows row-major between its kernels (decoder.h).
 static void read_chain_switches(StepPlan& p) {
   { const char* e = getenv("CCX_FUSE_CROSS_Q"); p.fuse_cross_q = e ? (atoi(e) != 0) : 1; }
   { const char* e = getenv("CCX_DEC_LNFREE"); p.lnfree = !(e && strcmp(e, "0") == 0); }
   { const char* e = getenv("CCX_XS_FUSE_Q"); p.xs_fuse_q = !e || atoi(e) != 0; }
   p.xs_full_lines = ccx_xs_full_lines_switch();
+  p.packed_act = ccx_dec_packed_act_switch();
 }
 // which cross attention a decode of B = p.B sequences uses (-> p.xs_active), and the K/V it needs
 // (n_kv: the sequences whose K/V the rows read -- B itself, or the windows of a mapped decode)
@@ -1157,6 +1159,12 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
       hipLaunchKernelGGL(dec_stamp_kernel, dim3(1), dim3(1), 0, stream, w->stamps + (size_t)lane_idx * ccx_whisper::kStampCap,
                          w->stamp_count + lane_idx, ccx_whisper::kStampCap, tag);
   };
+  // The > 16-row chain hands dxn (LayerNorm rows -> q|k|v, fc1, the query of its own launch) and dffn (fc1's GELU rows -> fc2) from
+  // kernel to kernel as fragment images: the consumers' column blocks (72 - 96 per launch) each re-read all rows out of L2, and a CU
+  // pulls a 1 KB-contiguous wave load about three times as fast as 16 rows x 64 B (profiles/dec_full_lines_experiment.txt).  Whole
+  // 16-row tiles only, so that a lane's image ends where the next lane's begins; the rows the head and the prefill gather read (the
+  // final LayerNorm) stay row-major.
+  const int packed = (p.packed_act && B > 16 && B % 16 == 0) ? 1 : 0;
   int pend_n = 0;
   auto ln_linear = [&](int epi, const bf16_t* W, const float* bias, int N, const float* g, const float* bta, void* out, long ldo,
                        DecLinearParams* extra) -> int {
@@ -1167,10 +1175,10 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
     if (B > 16) {
       // many sequences: normalise ONCE in a stand-alone kernel instead of redundantly in every weight-panel block
       rc = ccx_launch_dec_resolve_ln(ctx, cur, pend, pend_n, pstride, g, bta, dxn, pend_n > 0 ? other : nullptr, B, D, 1e-5f, stream,
-                                     lp.ln_mean_out);
+                                     lp.ln_mean_out, packed);
       if (rc) return rc;
       lp.ln_mean_out = nullptr;
-      lp.act = dxn; lp.lda = D;
+      lp.act = dxn; lp.lda = D; lp.act_packed = packed;
       rc = ccx_launch_dec_linear(ctx, ACT_BF16, epi, lp, stream);
     } else {
       lp.x = cur; lp.pend = pend; lp.pend_n = pend_n; lp.pend_stride = pstride; lp.x_out = pend_n > 0 ? other : nullptr;
@@ -1181,10 +1189,10 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
     if (pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
     return CCX_OK;
   };
-  auto partial_linear = [&](int act, const bf16_t* W, const float* bias, int K, const bf16_t* a) -> int {
+  auto partial_linear = [&](int act, const bf16_t* W, const float* bias, int K, const bf16_t* a, int a_packed = 0) -> int {
     DecLinearParams lp;
     memset(&lp, 0, sizeof(lp));
-    lp.M = B; lp.N = D; lp.K = K; lp.W = W; lp.ldw = K; lp.bias = bias; lp.act = a; lp.lda = K;
+    lp.M = B; lp.N = D; lp.K = K; lp.W = W; lp.ldw = K; lp.bias = bias; lp.act = a; lp.lda = K; lp.act_packed = a_packed;
     lp.part_o = part_o; lp.part_ml = part_ml; lp.nsplit = ns;
     lp.out = pend; lp.ldo = D; lp.pend_stride = pstride;
     int rc = ccx_launch_dec_linear(ctx, act, DEPI_PARTIAL, lp, stream);
@@ -1305,9 +1313,14 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
     }
     // MLP.  (fc1 through the tiled GEMM from 256 rows on, 653.1 -> 647.6 ms per pipeline step, was removed: the GEMM sums K in
     // another order, so a sequence's log-probabilities would depend on its lane's row count -- DESIGN.md)
-    CCX_TRY(ln_linear(DEPI_BF16_GELU, L.W1, L.b1, F, L.ln2_g, L.ln2_b, dffn, F, nullptr));
+    {
+      DecLinearParams ex;
+      memset(&ex, 0, sizeof(ex));
+      ex.out_packed = packed;
+      CCX_TRY(ln_linear(DEPI_BF16_GELU, L.W1, L.b1, F, L.ln2_g, L.ln2_b, dffn, F, &ex));
+    }
     stamp(20, 2);
-    CCX_TRY(partial_linear(ACT_BF16, L.W2, L.b2, F, dffn));
+    CCX_TRY(partial_linear(ACT_BF16, L.W2, L.b2, F, dffn, packed));
     stamp(21, 2);
   }
   // resolve the last partials + final LN, then logits against the tied embedding

@@ -489,6 +489,34 @@ typedef struct ccx_dec_select_desc {
  * the next step's embedding x[b] = tok_emb[next] + pos_emb[pos]. */
 int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* desc, void* stream);
 
+/* The > 16-row decode chain's LayerNorm -> linear pairs on their own (csrc/decoder.hip; for kernel parity tests): the production
+ * launchers unchanged, dec_resolve_ln_kernel (no pending slabs) into bf16 rows, then
+ *   F == 0:  dec_linear<ACT_BF16, epi>(W [N][K]) on those rows;
+ *   F  > 0:  dec_linear<ACT_BF16, GELU>(W1 [F][K]) into bf16 rows [M][F], then dec_linear<ACT_BF16, epi>(W [N][F]) on those.
+ * packed = 1 passes every bf16 row buffer between two kernels as the fragment image (csrc/decoder.h dec_frag_off), 0 row-major; the
+ * buffers hold whole 16-row tiles and start out as NaN bit patterns, as does `out`.  epi and what `out` (device f32) receives:
+ *   CCX_DEC_EPI_PARTIAL   [ksplit][M][N], the split-K slabs (ksplit = 1 up to 1024 input columns, 3 at 3072)
+ *   CCX_DEC_EPI_F32       [M][N]
+ *   CCX_DEC_EPI_SELF_QKV  [3][M][K]: q, then the k and v rows the epilogue appended to a one-position cache (N == 3 K, F == 0)
+ *   CCX_DEC_EPI_GELU      [M][N]: the bf16 rows widened, read back through the layout they were written in
+ * Checked on the host, CCX_ERR_ARG (1) naming "ccx_dec_ln_linear" and the field: 1 <= M <= 4096; K a multiple of 32 (64 for SELF_QKV)
+ * up to 1280; F 0 or a multiple of 32 up to 5120; N a multiple of 4 (32 for GELU) up to 8192; 16-byte alignment and the element
+ * counts.  x f32 [M][K], ln_g / ln_b f32 [K], b1 f32 [F], bias f32 [N] on the device; w1 f32 [F][K] and w f32 [N][K or F] row-major
+ * on the HOST.  Owns its scratch; synchronises the stream. */
+#define CCX_DEC_EPI_PARTIAL 0
+#define CCX_DEC_EPI_F32 1
+#define CCX_DEC_EPI_SELF_QKV 2
+#define CCX_DEC_EPI_GELU 3
+typedef struct ccx_dec_ln_linear_desc {
+  int M, K, F, N, epi, packed;
+  const void* x; const void* ln_g; const void* ln_b; float eps;
+  const float* w1_host; const void* b1;
+  const float* w_host; const void* bias;
+  void* out;
+  int64_t x_elems, out_elems;
+} ccx_dec_ln_linear_desc;
+int ccx_dec_ln_linear(ccx_ctx* ctx, const ccx_dec_ln_linear_desc* desc, void* stream);
+
 /* One beam-search step on its own (csrc/dec_beam.hip: dec_beam_topk_kernel, one block per row, then dec_beam_update_kernel, one block
  * per window; the rule is restated in tests/beam_reference.py) for G windows of beam_size consecutive rows, R = G * beam_size.
  * Every row must be in the sampling phase (pos == prompt_len - 1 + n_gen); the rows of a window share n_gen, pos and done (a window
