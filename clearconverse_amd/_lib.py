@@ -80,6 +80,20 @@ DEC_ATTN_STREAM_MAPPED = 7       # (6 is no form)
 DEC_ATTN_SELF_IND = 8            # the self form through a cache indirection (beam search)
 
 
+class DecMidChainDesc(C.Structure):
+    """ccx_dec_mid_chain_desc (include/ccx.h): self attention .. cross-attention out projection of the X-stream decode chain on its own."""
+    _fields_ = [
+        ("M", C.c_int), ("D", C.c_int), ("H", C.c_int), ("S", C.c_int), ("kv_T", C.c_int), ("packed", C.c_int),
+        ("q", C.c_void_p), ("self_k", C.c_void_p), ("self_v", C.c_void_p), ("x", C.c_void_p), ("shift", C.c_void_p), ("xa", C.c_void_p),
+        ("pos", C.c_void_p),
+        ("wo", C.c_void_p), ("bo", C.c_void_p),
+        ("lnc_g", C.c_void_p), ("lnc_b", C.c_void_p), ("cq_w", C.c_void_p), ("cq_b", C.c_void_p),
+        ("ck_w", C.c_void_p), ("cv_w", C.c_void_p), ("cv_b", C.c_void_p),
+        ("co_w", C.c_void_p), ("co_b", C.c_void_p),
+        ("out", C.c_void_p), ("packed_used", C.POINTER(C.c_int)),
+        ("q_elems", C.c_int64), ("kv_elems", C.c_int64), ("x_elems", C.c_int64), ("xa_elems", C.c_int64), ("out_elems", C.c_int64)]
+
+
 class DecLnLinearDesc(C.Structure):
     """ccx_dec_ln_linear_desc (include/ccx.h): a LayerNorm -> linear pair of the > 16-row decode chain on its own."""
     _fields_ = [
@@ -345,6 +359,8 @@ PROTOTYPES = {
     "ccx_whisper_decode_greedy": (_i, [_vp, _i32p, _i32p, _i, _i, _i, _i32p, _i32p, _fp, _fp, _vp]),
     "ccx_dec_attention_desc": (_i, [_vp, _i, C.POINTER(DecAttnDesc), _vp]),
     "ccx_dec_ln_linear": (_i, [_vp, C.POINTER(DecLnLinearDesc), _vp]),
+    "ccx_dec_mid_chain_out_elems": (_i64, [_i, _i, _i]),
+    "ccx_dec_mid_chain": (_i, [_vp, C.POINTER(DecMidChainDesc), _vp]),
     "ccx_dec_select_step": (_i, [_vp, C.POINTER(DecSelectDesc), _vp]),
     "ccx_dec_beam_step": (_i, [_vp, C.POINTER(DecBeamDesc), _vp]),
     "ccx_whisper_decode_beam": (_i, [_vp, _i32p, _i32p, _i, _i, _i32p, _i, _i, _i, _i, _i32p, _i32p, _fp, _i32p, _fp,

@@ -10,6 +10,7 @@
 // (the kernels carry their own descriptions)
 #include "cross_x.h"
 #include "dec_ln.h"
+#include "decoder.h"
 
 namespace {
 
@@ -41,12 +42,12 @@ __global__ __launch_bounds__(256) void dec_xq_expand_kernel(XsParams p) {
     const float4* src = (const float4*)(p.q + (long)row * D + h * 64 + ks * 32 + g * 8);
     qb[ks] = pack8(src[0], src[1]);
   }
-  const bf16_t* wbase = p.WkT + ((long)h * D + wave * FW + n) * 64 + g * 8;
+  const bf16_t* wbase = p.WkT + ((long)h * D + wave * FW) * 64 + lane * 8;   // fragment image (cross_x.h): M tile = two 1 KB tiles
   bf16_t* dst = p.xq + ((long)row * p.H + h) * D + wave * FW + g * 4;
 #pragma unroll
   for (int mt = 0; mt < NMT; mt++) {
     const bf16x8 a0 = *(const bf16x8*)(wbase + (long)mt * 16 * 64);
-    const bf16x8 a1 = *(const bf16x8*)(wbase + (long)mt * 16 * 64 + 32);
+    const bf16x8 a1 = *(const bf16x8*)(wbase + (long)mt * 16 * 64 + 512);
     f32x4 c = {0.f, 0.f, 0.f, 0.f};
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, qb[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qb[1], c, 0, 0, 0);
@@ -73,12 +74,12 @@ __global__ __launch_bounds__(256) void dec_xq_fused_kernel(XsParams p) {
   __shared__ __attribute__((aligned(16))) char q_s[16 * RSQ];
   const int h = blockIdx.x, r0 = blockIdx.y * 16;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
-  // the head's slice of Wq: wave w -> rows h*64 + 16 w + n
+  // the head's slice of Wq: wave w -> rows h*64 + 16 w + n = row tile 4 h + w of the fragment image, a k-step = the next 1 KB
   bf16x8 wq[NKS];
   {
-    const bf16_t* wsrc = p.Wq + (long)(h * 64 + wave * 16 + n) * D + g * 8;
+    const bf16_t* wsrc = p.Wq + ((long)(h * 4 + wave) * NKS * 64 + lane) * 8;
 #pragma unroll
-    for (int ks = 0; ks < NKS; ks++) wq[ks] = *(const bf16x8*)(wsrc + ks * 32);
+    for (int ks = 0; ks < NKS; ks++) wq[ks] = *(const bf16x8*)(wsrc + ks * 512);
   }
   // A. resolve + LayerNorm of rows 4 wave .. 4 wave + 3
   {
@@ -139,12 +140,12 @@ __global__ __launch_bounds__(256) void dec_xq_fused_kernel(XsParams p) {
     }
   }
   // the expansion's weights fly under the LDS round trip of q
-  const bf16_t* wbase = p.WkT + ((long)h * D + wave * FW + n) * 64 + g * 8;
+  const bf16_t* wbase = p.WkT + ((long)h * D + wave * FW) * 64 + lane * 8;
   bf16x8 wk[NMT][2];
 #pragma unroll
   for (int mt = 0; mt < NMT; mt++) {
     wk[mt][0] = *(const bf16x8*)(wbase + (long)mt * 16 * 64);
-    wk[mt][1] = *(const bf16x8*)(wbase + (long)mt * 16 * 64 + 32);
+    wk[mt][1] = *(const bf16x8*)(wbase + (long)mt * 16 * 64 + 512);
   }
   {
     const float4 bias = *(const float4*)(p.bq + h * 64 + wave * 16 + g * 4);
@@ -184,15 +185,17 @@ __global__ __launch_bounds__(256) void dec_xq_lnfree_kernel(XsParams p) {
   int row = r0 + n;
   const bool live = row < p.rows;
   if (!live) row = p.rows - 1;
-  // the head's slice of gamma o Wq: wave w -> rows h*64 + 16 w + n; and the 16 raw rows (B operand)
+  // the head's slice of gamma o Wq: wave w -> rows h*64 + 16 w + n = row tile 4 h + w of the fragment image; and the 16 raw rows
+  // (B operand): row-major, or (xb_packed) row tile blockIdx.y of their image -- 1 KB per wave load either way but the first
   bf16x8 wq[NKS], xb[NKS];
   {
-    const bf16_t* wsrc = p.Wq + (long)(h * 64 + wave * 16 + n) * D + g * 8;
-    const bf16_t* xsrc = p.xb + (long)row * D + g * 8;
+    const bf16_t* wsrc = p.Wq + ((long)(h * 4 + wave) * NKS * 64 + lane) * 8;
+    const bf16_t* xsrc = p.xb_packed ? p.xb + ((long)blockIdx.y * NKS * 64 + lane) * 8 : p.xb + (long)row * D + g * 8;
+    const int xstep = p.xb_packed ? 512 : 32;
 #pragma unroll
-    for (int ks = 0; ks < NKS; ks++) wq[ks] = *(const bf16x8*)(wsrc + ks * 32);
+    for (int ks = 0; ks < NKS; ks++) wq[ks] = *(const bf16x8*)(wsrc + ks * 512);
 #pragma unroll
-    for (int ks = 0; ks < NKS; ks++) xb[ks] = *(const bf16x8*)(xsrc + ks * 32);
+    for (int ks = 0; ks < NKS; ks++) xb[ks] = *(const bf16x8*)(xsrc + ks * xstep);
   }
   // (mean, rstd) of the 16 rows: four threads per row, a quarter of the D / 16 tiles each, (q0 + q1) + (q2 + q3) -- the order of
   // dec_linear_kernel<ACT_BF16_LN>
@@ -215,12 +218,12 @@ __global__ __launch_bounds__(256) void dec_xq_lnfree_kernel(XsParams p) {
     if (qt == 0) st_s[r] = make_float2(mean, rsqrtf(fmaxf(var, 0.f) + p.eps));
   }
   // the expansion's weights and the folded constants fly under the MFMAs
-  const bf16_t* wbase = p.WkT + ((long)h * D + wave * FW + n) * 64 + g * 8;
+  const bf16_t* wbase = p.WkT + ((long)h * D + wave * FW) * 64 + lane * 8;
   bf16x8 wk[NMT][2];
 #pragma unroll
   for (int mt = 0; mt < NMT; mt++) {
     wk[mt][0] = *(const bf16x8*)(wbase + (long)mt * 16 * 64);
-    wk[mt][1] = *(const bf16x8*)(wbase + (long)mt * 16 * 64 + 32);
+    wk[mt][1] = *(const bf16x8*)(wbase + (long)mt * 16 * 64 + 512);
   }
   const float4 cc = *(const float4*)(p.bq + h * 64 + wave * 16 + g * 4);
   const float4 ss = *(const float4*)(p.ln_s + h * 64 + wave * 16 + g * 4);
@@ -263,12 +266,12 @@ __global__ __launch_bounds__(256) void dec_xv_project_kernel(XsParams p) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
   const int o0 = h * 64 + wave * 16;
   // weights first: they do not depend on the merge
-  const bf16_t* wsrc = p.Wv + (long)(o0 + n) * D + g * 8;
+  const bf16_t* wsrc = p.Wv + ((long)(h * 4 + wave) * NKS * 64 + lane) * 8;   // row tile 4 h + w of the fragment image
   constexpr int CH = NKS % 6 == 0 ? 6 : 4;      // k-steps requested together
   static_assert(NKS % CH == 0, "D must be a multiple of 128");
   bf16x8 a[CH];
 #pragma unroll
-  for (int k = 0; k < CH; k++) a[k] = *(const bf16x8*)(wsrc + k * 32);
+  for (int k = 0; k < CH; k++) a[k] = *(const bf16x8*)(wsrc + k * 512);
   {
     const int rr = threadIdx.x >> 4, c = threadIdx.x & 15;       // row of the tile, float4 column phase
     int row = r0 + rr;
@@ -312,7 +315,7 @@ __global__ __launch_bounds__(256) void dec_xv_project_kernel(XsParams p) {
     bf16x8 an[CH];
     if (c0 + CH < NKS) {
 #pragma unroll
-      for (int k = 0; k < CH; k++) an[k] = *(const bf16x8*)(wsrc + (c0 + CH + k) * 32);
+      for (int k = 0; k < CH; k++) an[k] = *(const bf16x8*)(wsrc + (c0 + CH + k) * 512);
     }
 #pragma unroll
     for (int k = 0; k < CH; k++) {
@@ -329,7 +332,9 @@ __global__ __launch_bounds__(256) void dec_xv_project_kernel(XsParams p) {
   if (row < p.rows) {
     const float4 bias = *(const float4*)(p.bv + o0 + g * 4);
     const float v0 = ca[0] + cb[0] + bias.x, v1 = ca[1] + cb[1] + bias.y, v2 = ca[2] + cb[2] + bias.z, v3 = ca[3] + cb[3] + bias.w;
-    *(u32x2*)(p.out + (long)row * D + o0 + g * 4) = (u32x2){pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
+    // out_packed: the 8 bytes go into the fragment image the out projection loads (decoder.h dec_frag_off)
+    bf16_t* o = p.out + (p.out_packed ? dec_frag_off(row, o0 + g * 4, D >> 5) : (long)row * D + o0 + g * 4);
+    *(u32x2*)o = (u32x2){pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
   }
 }
 
@@ -690,6 +695,8 @@ int ccx_launch_xs_cross_attention(ccx_ctx* ctx, const XsParams& p, hipStream_t s
   CCX_REQUIRE(ctx, !p.xb || (p.ln_stats && p.ln_s && p.Wq && p.bq), "xs cross attention: bad LayerNorm-free query arguments");
   CCX_REQUIRE(ctx, !p.x || (p.pend && p.ln_g && p.ln_b && p.Wq && p.bq && p.pend_n >= 0 && p.pend_n <= 4 && p.x_out != p.x), "xs cross attention: bad fused-query arguments");
   CCX_REQUIRE(ctx, p.part_o && p.part_ml, "xs cross attention: partial buffers missing");
+  CCX_REQUIRE(ctx, !(p.xb_packed || p.out_packed) || p.rows % 16 == 0, "xs cross attention: fragment images need rows=%d to be a multiple of 16", p.rows);
+  CCX_REQUIRE(ctx, !p.xb_packed || p.xb, "xs cross attention: xb_packed without xb");
   switch (p.D) {
     case 128: return launch_xs<128>(ctx, p, stream);
     case 256: return launch_xs<256>(ctx, p, stream);
@@ -725,11 +732,9 @@ extern "C" int ccx_cross_attention_xa(ccx_ctx* ctx, const float* q_dev, const fl
     for (int i = 0; i < rows; i++)
       CCX_REQUIRE(ctx, row_seq_host[i] == row_seq_host[i - i % rows_per_seq], "cross_attention_xa: row %d is not in its group's sequence", i);
   }
-  std::vector<bf16_t> wkt((size_t)D * D), wv((size_t)D * D);
-  for (int hh = 0; hh < H; hh++)
-    for (int f = 0; f < D; f++)
-      for (int dd = 0; dd < 64; dd++) wkt[((size_t)hh * D + f) * 64 + dd] = ccx_host_f32_to_bf16(wk_host[(size_t)(hh * 64 + dd) * D + f]);
-  for (size_t i = 0; i < wv.size(); i++) wv[i] = ccx_host_f32_to_bf16(wv_host[i]);
+  // the weights as the model stores them: fragment images (cross_x.h)
+  const std::vector<float> wkt_f = ccx_xs_relay_key(wk_host, H, D);
+  const std::vector<bf16_t> wkt = pack_mfma_rows(wkt_f.data(), H * D, 64, 16), wv = pack_mfma_rows(wv_host, D, D, 16);
   bf16_t *d_wkt = nullptr, *d_wv = nullptr, *d_xq = nullptr, *d_out = nullptr;
   float *d_bv = nullptr, *d_po = nullptr, *d_pml = nullptr;
   int* d_rs = nullptr;

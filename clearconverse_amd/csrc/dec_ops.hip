@@ -5,6 +5,7 @@
 #include "../../include/ccx.h"
 #include "ccx_common.h"
 #include "decoder.h"
+#include "cross_x.h"
 #include "op_scratch.h"
 
 static_assert(sizeof(ccx_dec_seq_state) == sizeof(DecSeqState), "ccx_dec_seq_state mirrors DecSeqState field for field");
@@ -266,6 +267,121 @@ extern "C" int ccx_dec_ln_linear(ccx_ctx* ctx, const ccx_dec_ln_linear_desc* d, 
       hipLaunchKernelGGL(dec_ops_rows_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_g16, (float*)d->out, M, N, packed);
       DO_HIP(hipGetLastError());
     }
+  }
+  DO_HIP(hipStreamSynchronize(stream));      // the scratch is freed on return
+  return rc;
+}
+
+extern "C" int64_t ccx_dec_mid_chain_out_elems(int M, int D, int H) {
+  return (int64_t)M * D * 5 + (int64_t)M * (D / 16) * 2 + (int64_t)M * H * D;
+}
+
+extern "C" int ccx_dec_mid_chain(ccx_ctx* ctx, const ccx_dec_mid_chain_desc* d, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_mid_chain: desc is NULL");
+  const int M = d->M, D = d->D, H = d->H, S = d->S, Tc = d->kv_T;
+  CCX_REQUIRE(ctx, M >= 1 && M <= 4096, "ccx_dec_mid_chain: M = %d out of range [1, 4096]", M);
+  CCX_REQUIRE(ctx, H >= 1 && H <= 64 && D == 64 * H && ccx_xs_supported(D, H), "ccx_dec_mid_chain: D = %d with H = %d heads is not a width the X-stream kernels have (D == 64 H, H in {2, 4, 6, 8, 12})", D, H);
+  CCX_REQUIRE(ctx, S >= 16 && S <= 4096, "ccx_dec_mid_chain: S = %d out of range [16, 4096]", S);
+  CCX_REQUIRE(ctx, Tc >= 1 && Tc <= 4096, "ccx_dec_mid_chain: kv_T = %d out of range [1, 4096]", Tc);
+  CCX_REQUIRE(ctx, d->packed == 0 || d->packed == 1, "ccx_dec_mid_chain: packed = %d must be 0 or 1", d->packed);
+  CCX_REQUIRE(ctx, d->q && d->self_k && d->self_v && d->x && d->xa && d->out && d->pos && d->packed_used, "ccx_dec_mid_chain: q, self_k, self_v, x, xa, pos, out or packed_used is NULL");
+  CCX_REQUIRE(ctx, d->wo && d->bo && d->lnc_g && d->lnc_b && d->cq_w && d->cq_b && d->ck_w && d->cv_w && d->cv_b && d->co_w && d->co_b, "ccx_dec_mid_chain: a host weight is NULL");
+  CCX_REQUIRE(ctx, ccx_aligned16(d->q) && ccx_aligned16(d->self_k) && ccx_aligned16(d->self_v) && ccx_aligned16(d->x) && ccx_aligned16(d->shift) && ccx_aligned16(d->xa) && ccx_aligned16(d->out),
+              "ccx_dec_mid_chain: q, self_k, self_v, x, shift, xa or out not 16-byte aligned");
+  for (int i = 0; i < M; i++) CCX_REQUIRE(ctx, d->pos[i] >= 0 && d->pos[i] < Tc, "ccx_dec_mid_chain: pos[%d] = %d out of range [0, kv_T = %d)", i, d->pos[i], Tc);
+  const int64_t MD = (int64_t)M * D;
+  CCX_REQUIRE(ctx, MD <= d->q_elems, "ccx_dec_mid_chain: q is read up to element %ld, q_elems=%ld", (long)MD, (long)d->q_elems);
+  CCX_REQUIRE(ctx, MD * Tc <= d->kv_elems, "ccx_dec_mid_chain: self_k / self_v are read up to element %ld, kv_elems=%ld", (long)(MD * Tc), (long)d->kv_elems);
+  CCX_REQUIRE(ctx, MD <= d->x_elems, "ccx_dec_mid_chain: x is read up to element %ld, x_elems=%ld", (long)MD, (long)d->x_elems);
+  CCX_REQUIRE(ctx, MD * S <= d->xa_elems, "ccx_dec_mid_chain: xa is read up to element %ld, xa_elems=%ld", (long)(MD * S), (long)d->xa_elems);
+  const int64_t n_out = ccx_dec_mid_chain_out_elems(M, D, H);
+  CCX_REQUIRE(ctx, n_out <= d->out_elems, "ccx_dec_mid_chain: out is written up to element %ld, out_elems=%ld", (long)n_out, (long)d->out_elems);
+
+  // the rule of the model's chain (whisper.hip dec_step)
+  const int pk = ccx_dec_rows_as_image(d->packed, M);
+  *d->packed_used = pk;
+  float* o_attn = (float*)d->out;
+  float* o_x = o_attn + MD;
+  float* o_xb = o_x + MD;
+  float* o_st = o_xb + MD;
+  float* o_xq = o_st + (int64_t)M * (D / 16) * 2;
+  float* o_cross = o_xq + MD * H;
+  float* o_co = o_cross + MD;
+
+  ccx_op_scratch sc;
+  const size_t Mp = (size_t)(M + 15) / 16 * 16;        // whole 16-row tiles
+  bf16_t *d_attn = nullptr, *d_xb = nullptr, *d_xq = nullptr, *d_wo = nullptr, *d_wco = nullptr, *d_wg = nullptr, *d_wkt = nullptr, *d_wv = nullptr;
+  float *d_bo = nullptr, *d_bco = nullptr, *d_s = nullptr, *d_c = nullptr, *d_bv = nullptr, *d_po = nullptr, *d_pml = nullptr;
+  float2* d_st = nullptr; int* d_pos = nullptr;
+  DO_HIP(hipMemsetAsync(d->out, 0xFF, (size_t)n_out * 4, stream));
+  DO_HIP(sc.alloc(&d_attn, Mp * D)); DO_HIP(hipMemsetAsync(d_attn, 0xFF, Mp * D * 2, stream));
+  DO_HIP(sc.alloc(&d_xb, Mp * D)); DO_HIP(hipMemsetAsync(d_xb, 0xFF, Mp * D * 2, stream));
+  DO_HIP(sc.alloc(&d_st, (size_t)M * (D / 16))); DO_HIP(hipMemsetAsync(d_st, 0xFF, (size_t)M * (D / 16) * 8, stream));
+  DO_HIP(sc.alloc(&d_xq, (size_t)MD * H)); DO_HIP(hipMemsetAsync(d_xq, 0xFF, (size_t)MD * H * 2, stream));
+  DO_HIP(sc.alloc(&d_po, ccx_xs_part_o_elems(M, H, D))); DO_HIP(hipMemsetAsync(d_po, 0xFF, ccx_xs_part_o_elems(M, H, D) * 4, stream));
+  DO_HIP(sc.alloc(&d_pml, ccx_xs_part_ml_elems(M))); DO_HIP(hipMemsetAsync(d_pml, 0xFF, ccx_xs_part_ml_elems(M) * 4, stream));
+  DO_HIP(sc.upload(&d_pos, d->pos, (size_t)M));
+  float bo_mean;
+  {
+    // the weights as ccx_whisper_finalize stores them
+    const std::vector<bf16_t> wo = pack_mfma_rows(d->wo, D, D, 16), wco = pack_mfma_rows(d->co_w, D, D, 16), wv = pack_mfma_rows(d->cv_w, D, D, 16);
+    const std::vector<float> wkt_f = ccx_xs_relay_key(d->ck_w, H, D);
+    const std::vector<bf16_t> wkt = pack_mfma_rows(wkt_f.data(), H * D, 64, 16);
+    std::vector<float> Wg, sv, cv;
+    ccx_xs_fold_query_ln(d->lnc_g, d->lnc_b, d->cq_w, d->cq_b, D, Wg, sv, cv);
+    const std::vector<bf16_t> wg = pack_mfma_rows(Wg.data(), D, D, 16);
+    double sb = 0.0;
+    for (int k = 0; k < D; k++) sb += d->bo[k];
+    bo_mean = (float)(sb / D);
+    DO_HIP(sc.upload(&d_wo, wo.data(), wo.size())); DO_HIP(sc.upload(&d_wco, wco.data(), wco.size())); DO_HIP(sc.upload(&d_wv, wv.data(), wv.size()));
+    DO_HIP(sc.upload(&d_wkt, wkt.data(), wkt.size())); DO_HIP(sc.upload(&d_wg, wg.data(), wg.size()));
+    DO_HIP(sc.upload(&d_s, sv.data(), sv.size())); DO_HIP(sc.upload(&d_c, cv.data(), cv.size()));
+    DO_HIP(sc.upload(&d_bo, d->bo, (size_t)D)); DO_HIP(sc.upload(&d_bco, d->co_b, (size_t)D)); DO_HIP(sc.upload(&d_bv, d->cv_b, (size_t)D));
+  }
+  const float scale_log2e = 0.125f * 1.4426950408889634f;
+  const dim3 cgrid((unsigned)((MD + 255) / 256));
+  // self attention
+  DecAttnParams ap;
+  memset(&ap, 0, sizeof(ap));
+  ap.q = (const float*)d->q; ap.k = (const bf16_t*)d->self_k; ap.v = (const bf16_t*)d->self_v; ap.H = H; ap.kv_T = Tc; ap.pos = d_pos;
+  ap.scale_log2e = scale_log2e; ap.out_bf16 = d_attn; ap.out_packed = pk;
+  int rc = ccx_launch_dec_attention(ctx, ap, M, 1, true, stream);
+  if (rc == CCX_OK) { hipLaunchKernelGGL(dec_ops_rows_to_f32_kernel, cgrid, dim3(256), 0, stream, d_attn, o_attn, M, D, pk); DO_HIP(hipGetLastError()); }
+  // out projection, residual resolved in place
+  if (rc == CCX_OK) {
+    DO_HIP(hipMemcpyAsync(o_x, d->x, (size_t)MD * 4, hipMemcpyDeviceToDevice, stream));
+    DecLinearParams lp;
+    memset(&lp, 0, sizeof(lp));
+    lp.M = M; lp.N = D; lp.K = D; lp.W = d_wo; lp.ldw = D; lp.bias = d_bo; lp.act = d_attn; lp.lda = D; lp.act_packed = pk; lp.out_packed = pk;
+    lp.xres = o_x; lp.xb = d_xb; lp.st_out = d_st; lp.shift = (const float*)d->shift; lp.shift_c = bo_mean;
+    rc = ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_RESOLVE, lp, stream);
+  }
+  if (rc == CCX_OK) {
+    hipLaunchKernelGGL(dec_ops_rows_to_f32_kernel, cgrid, dim3(256), 0, stream, d_xb, o_xb, M, D, pk); DO_HIP(hipGetLastError());
+    DO_HIP(hipMemcpyAsync(o_st, d_st, (size_t)M * (D / 16) * 8, hipMemcpyDeviceToDevice, stream));
+    // query + expansion, streaming kernel, merge + value projection
+    XsParams xp;
+    memset(&xp, 0, sizeof(xp));
+    xp.xb = d_xb; xp.xb_packed = pk; xp.ln_stats = d_st; xp.ln_s = d_s; xp.Wq = d_wg; xp.bq = d_c; xp.eps = 1e-5f;
+    xp.WkT = d_wkt; xp.xq = d_xq; xp.part_o = d_po; xp.part_ml = d_pml;
+    xp.X = (const bf16_t*)d->xa; xp.x_seq_stride = (long)S * D;
+    xp.Wv = d_wv; xp.bv = d_bv; xp.out = d_attn; xp.out_packed = pk;
+    xp.rows = M; xp.H = H; xp.S = S; xp.D = D; xp.scale_log2e = scale_log2e; xp.full_lines = ccx_xs_full_lines_switch();
+    rc = ccx_launch_xs_cross_attention(ctx, xp, stream);
+  }
+  if (rc == CCX_OK) {
+    const long nq = (long)MD * H;
+    hipLaunchKernelGGL(dec_ops_bf16_to_f32_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, d_xq, o_xq, nq);
+    hipLaunchKernelGGL(dec_ops_rows_to_f32_kernel, cgrid, dim3(256), 0, stream, d_attn, o_cross, M, D, pk);
+    DO_HIP(hipGetLastError());
+    // cross-attention out projection
+    DecLinearParams lp;
+    memset(&lp, 0, sizeof(lp));
+    lp.M = M; lp.N = D; lp.K = D; lp.W = d_wco; lp.ldw = D; lp.bias = d_bco; lp.act = d_attn; lp.lda = D; lp.act_packed = pk;
+    lp.out = o_co; lp.ldo = D; lp.pend_stride = (long)MD;
+    rc = ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_PARTIAL, lp, stream);
   }
   DO_HIP(hipStreamSynchronize(stream));      // the scratch is freed on return
   return rc;

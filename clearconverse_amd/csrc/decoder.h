@@ -35,7 +35,8 @@ struct DecLinearParams {
   bf16_t* cache_k; bf16_t* cache_v; int cache_T; const int* pos; const int* row_seq;
   // ACT_BF16 only.  act_packed: `act` is the fragment image of the rows instead (dec_frag_off: ceil(M / 16) x K / 32 tiles of 1 KB, so a
   // wave load is 1 KB contiguous and not 16 rows x 64 B; lda is not read).  DEPI_BF16_GELU, out_packed: `out` is written as that
-  // image of [M][N] (N a multiple of 32; ldo is not read).  The values a lane holds, and so the results, are the same either way.
+  // image of [M][N] (N a multiple of 32; ldo is not read); DEPI_RESOLVE, out_packed: `xb` is.  The values a lane holds, and so the
+  // results, are the same either way.
   int act_packed, out_packed;
 };
 int ccx_launch_dec_linear(ccx_ctx* ctx, int act, int epi, const DecLinearParams& p, hipStream_t stream);
@@ -56,6 +57,12 @@ __host__ __device__ __forceinline__ long dec_frag_off(int m, int k, int ksteps) 
 // CCX_DEC_PACKED_ACT (default 1; read per decode): the > 16-row chain hands its LayerNorm rows and its GELU rows from kernel to kernel
 // as fragment images; 0: row-major, as the <= 16-row chain and every other reader of these buffers keep them
 int ccx_dec_packed_act_switch();
+// CCX_DEC_PACKED_MID (default 1; read per decode): the same for the rest of that chain's bf16 rows -- dattn (self attention -> out
+// projection, value projection -> cross-attention out projection) and xb (out projection -> LayerNorm-free query)
+int ccx_dec_packed_mid_switch();
+// The rule both switches share: lanes of more than 16 rows in whole 16-row tiles (a lane's image then ends where the next lane's
+// begins); every other launch keeps row-major rows.
+static inline int ccx_dec_rows_as_image(int on, int rows) { return (on && rows > 16 && rows % 16 == 0) ? 1 : 0; }
 
 struct DecAttnParams {
   const float* q;       // [B][H][64] f32
@@ -86,6 +93,9 @@ struct DecAttnParams {
   // ind[r * ind_ld + t] instead of slot r (dec_attention_kernel<true, true>).  Null: the unflagged kernels.  (Appended: no other
   // field moves; the kernel argument block of every attention kernel grows by these 16 bytes.)
   const unsigned short* ind; int ind_ld;
+  // self attention of a decode step only (pos set, no row_seq, no ind; B a multiple of 16): out_bf16 is written as the fragment image
+  // of the rows (dec_frag_off) instead of row-major (dec_attention_kernel<true, false, true>).  (Appended.)
+  int out_packed;
 };
 int ccx_launch_dec_attention(ccx_ctx* ctx, const DecAttnParams& p, int B, int nsplit, bool final_out, hipStream_t stream);
 // Cross attention of a small batch (B <= 16 rows) WITH its query projection: replaces ln_linear(Wcq) + ccx_launch_dec_attention(split

@@ -347,7 +347,8 @@ __global__ __launch_bounds__(64 * NW, (KMAX > 8 && ACT == ACT_LN) ? 2 : 1) void 
         *(float4*)(p.xres + (long)m * p.N + n) = make_float4(v[0], v[1], v[2], v[3]);
         uint2 pk;
         pk.x = pack_bf16x2(c0, c1); pk.y = pack_bf16x2(c2, c3);
-        *(uint2*)(p.xb + (long)m * p.N + n) = pk;
+        // out_packed: the quad's 8 bytes go into the fragment image the query kernel loads (N % 32 == 0)
+        *(uint2*)(p.xb + (p.out_packed ? dec_frag_off(m, n, p.N >> 5) : (long)m * p.N + n)) = pk;
         if ((ln >> 4) == 0) p.st_out[(long)m * (p.N >> 4) + (n >> 4)] = make_float2(s1, s2);
       }
       continue;
@@ -551,6 +552,11 @@ int ccx_dec_packed_act_switch() {
   return !(e && strcmp(e, "0") == 0);
 }
 
+int ccx_dec_packed_mid_switch() {
+  const char* e = getenv("CCX_DEC_PACKED_MID");
+  return !(e && strcmp(e, "0") == 0);
+}
+
 int ccx_dec_linear_ksplit(int K, int epi) {
   // prefetch depth is 8 k-steps (256 elements) per wave, 4 waves per block -- or 10 (320 elements), taken only where 8 cannot serve:
   // a non-partial epilogue at 1024 < K <= 1280, and partial outputs whose 1024-wide slabs would outnumber the 4 pending slabs the
@@ -567,7 +573,8 @@ int ccx_launch_dec_linear(ccx_ctx* ctx, int act, int epi, const DecLinearParams&
   CCX_REQUIRE(ctx, act == ACT_BF16 || p.K <= 1280, "dec_linear: LN/combine activation needs K <= 1280");
   CCX_REQUIRE(ctx, p.pend_n >= 0 && p.pend_n <= 4, "dec_linear: at most 4 pending slabs");
   CCX_REQUIRE(ctx, !p.act_packed || act == ACT_BF16, "dec_linear: act_packed is taken with bf16 activations only");
-  CCX_REQUIRE(ctx, !p.out_packed || (act == ACT_BF16 && epi == DEPI_BF16_GELU && p.N % 32 == 0), "dec_linear: out_packed needs the GELU epilogue and N=%d a multiple of 32", p.N);
+  CCX_REQUIRE(ctx, !p.out_packed || (act == ACT_BF16 && (epi == DEPI_BF16_GELU || epi == DEPI_RESOLVE) && p.N % 32 == 0),
+              "dec_linear: out_packed needs the GELU or the resolve epilogue and N=%d a multiple of 32", p.N);
   const int ksplit = ccx_dec_linear_ksplit(p.K, epi);
   CCX_REQUIRE(ctx, epi == DEPI_PARTIAL || ksplit == 1, "dec_linear: K=%d needs a split-K (partial) epilogue", p.K);
   CCX_REQUIRE(ctx, ksplit <= 4, "dec_linear: K=%d would leave %d partial slabs (at most 4)", p.K, ksplit);
@@ -737,7 +744,9 @@ __device__ __forceinline__ void soft_merge_waves(const float (&sm_m)[4][8], cons
 // to another row keeps reading the K/V its ancestors wrote, no cache row is ever copied.  A chunk's 8 slot entries are requested
 // before any of its K/V loads (they are the head of a dependent chain: one more round trip per 64-key chunk, out of L2).  The
 // unflagged instantiations are the kernels they always were.
-template <bool FINAL, bool IND = false>
+// IMG (FINAL self attention of a decode step, DecAttnParams::out_packed): the output rows are written as the fragment image the out
+// projection loads (decoder.h dec_frag_off) instead of row-major.  A compile-time flag: the other instantiations' code does not change.
+template <bool FINAL, bool IND = false, bool IMG = false>
 __global__ __launch_bounds__(256) void dec_attention_kernel(DecAttnParams p) {
   __shared__ float sm_m[4][8], sm_l[4][8], sm_o[4][8][8];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -802,7 +811,7 @@ __global__ __launch_bounds__(256) void dec_attention_kernel(DecAttnParams p) {
     float mx, l, o;
     soft_merge_waves(sm_m, sm_l, sm_o, tid, mx, l, o);
     if (FINAL) {
-      p.out_bf16[((long)b * p.H + h) * 64 + tid] = f32_to_bf16(o / l);
+      p.out_bf16[IMG ? dec_frag_off(b, h * 64 + tid, p.H * 2) : ((long)b * p.H + h) * 64 + tid] = f32_to_bf16(o / l);
     } else {
       const long pbase = ((long)b * p.H + h) * gridDim.y + split;
       p.part_o[pbase * 64 + tid] = o;
@@ -1205,6 +1214,9 @@ int ccx_launch_dec_attention(ccx_ctx* ctx, const DecAttnParams& p, int B, int ns
   static DecAttnKernel split_kv[2][2] = {   // [self][final]
       {{"dec_attention_kernel<false> (cross)", dec_attention_kernel<false>}, {"dec_attention_kernel<true> (cross)", dec_attention_kernel<true>}},
       {{"dec_attention_kernel<false> (self)", dec_attention_kernel<false>}, {"dec_attention_kernel<true> (self)", dec_attention_kernel<true>}}};
+  // the image is written by the self attention of a decode step only: every other form would drop the flag or ignore it
+  CCX_REQUIRE(ctx, !p.out_packed || (p.pos && final_out && nsplit == 1 && !p.row_seq && !p.ind && !p.stream_mode && p.rows_per_seq <= 1 && B % 16 == 0),
+              "dec_attention: out_packed is taken by the self attention of a decode step (pos, nsplit 1, no row_seq, no ind) over whole 16-row tiles only (B=%d, nsplit=%d)", B, nsplit);
   const int np_need = p.pos ? 0 : ((ccx_cdiv(ccx_cdiv(p.T, nsplit), 4) + 31) / 32);
   const int npi = np_need <= 4 ? 0 : (np_need <= 6 ? 1 : 2);
   const bool prefill = p.rows_per_seq > 1 && !p.pos;
@@ -1227,6 +1239,9 @@ int ccx_launch_dec_attention(ccx_ctx* ctx, const DecAttnParams& p, int B, int ns
     k = (p.kv_map && p.row_seq) ? &streaming_map[npi] : &streaming[npi];
     lds = pad;
     CCX_HIP(ctx, k->optin.ensure(ctx->device, (const void*)k->fn, 128 * 1024));
+  } else if (p.out_packed) {
+    static DecAttnKernel self_image = {"dec_attention_kernel<true,false,true> (self, image)", dec_attention_kernel<true, false, true>};
+    k = &self_image;
   } else if (p.ind) {
     static DecAttnKernel self_ind = {"dec_attention_kernel<true,true> (self, indirect)", dec_attention_kernel<true, true>};
     CCX_REQUIRE(ctx, p.pos && final_out && !p.row_seq && p.ind_ld >= 1, "dec_attention: the cache indirection is taken by the self attention of a decode step only");

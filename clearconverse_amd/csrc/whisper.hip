@@ -33,10 +33,12 @@ struct EncLayer {
 struct DecLayer {
   float *ln1_g, *ln1_b, *lnc_g, *lnc_b, *ln2_g, *ln2_b;
   bf16_t *Wqkv, *Wo, *Wcq, *Wckv, *Wco, *W1, *W2;
-  bf16_t* WckT = nullptr;       // cross_attn.key.weight re-laid per head [H][D][64] for the expanded query (cross_x.hip)
-  bf16_t* Wcq_plain = nullptr;  // cross_attn.query.weight in plain row-major [D][D] (dec_xq_fused_kernel)
-  // LayerNorm-free cross-attention query (dec_xq_lnfree_kernel): gamma folded into the weights, Wcq_g = gamma o Wcq (plain
-  // row-major), s_n = sum_k (gamma o Wcq)_nk over the bf16 values the MFMAs see, c_n = sum_k beta_k Wcq_nk + bcq_n
+  // the X-stream kernels' weights (cross_x.hip), each as the fragment image of its matrix (cross_x.h)
+  bf16_t* WckT = nullptr;       // cross_attn.key.weight re-laid per head [H][D][64] for the expanded query
+  bf16_t* Wcq_plain = nullptr;  // cross_attn.query.weight [D][D] (dec_xq_fused_kernel; Wcq is the same image padded to 16 rows: the same bytes)
+  bf16_t* Wcv_x = nullptr;      // cross_attn.value.weight [D][D] (dec_xv_project_kernel; the row-major Wckv stays for project_cross_kv)
+  // LayerNorm-free cross-attention query (dec_xq_lnfree_kernel): gamma folded into the weights, Wcq_g = gamma o Wcq (fragment
+  // image), s_n = sum_k (gamma o Wcq)_nk over the bf16 values the MFMAs see, c_n = sum_k beta_k Wcq_nk + bcq_n
   bf16_t* Wcq_g = nullptr;
   float *scq = nullptr, *ccq = nullptr;
   // ... whose rows are centred by the row's attn_ln mean + mean(attn.out.bias) before the bf16 rounding where that mean exceeds the
@@ -61,7 +63,7 @@ struct StepPlan {
                                   // 0 (teacher-forced passes): split-KV partials + dec_combine_kernel
   int cross_lds_pad;              // occupancy cap of the cross-attention blocks while lanes overlap (plan_lanes)
   int xs_active;                  // cross attention against the encoder output (select_cross_path)
-  int lnfree, xs_fuse_q, fuse_cross_q, xs_full_lines, packed_act;   // the chain's form (read_chain_switches)
+  int lnfree, xs_fuse_q, fuse_cross_q, xs_full_lines, packed_act, packed_mid;   // the chain's form (read_chain_switches)
   int map_on, sid_on;             // the rows read a row -> window map / a stream-id table (ccx_whisper_decode_rows)
   int beam_size, beam_maxc;       // beam search (0: none) and its max_candidates
   int lane_idx;                   // whose stamp trace and stagger slot
@@ -84,12 +86,12 @@ struct StepPlan {
   int trunc_on;
   auto tie() const {
     return std::tie(b0, B, sample_len, max_prompt, select, sampling, cross_stream, cross_lds_pad, xs_active, lnfree, xs_fuse_q, fuse_cross_q,
-                    xs_full_lines, packed_act, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows, opt_mask, no_ts, sup_blank,
+                    xs_full_lines, packed_act, packed_mid, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows, opt_mask, no_ts, sup_blank,
                     max_init_ts, hist_ngram, hist_pen_bits, bias_on, trunc_on);
   }
   bool operator<(const StepPlan& o) const { return tie() < o.tie(); }
 };
-static_assert(sizeof(StepPlan) == 29 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 29,
+static_assert(sizeof(StepPlan) == 30 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 30,
               "StepPlan: ints only, and every one of them in tie()");
 
 }  // namespace
@@ -643,29 +645,14 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     CCX_TRY(w->store.upload(&L.lnc_g, lcg->data.data(), D)); CCX_TRY(w->store.upload(&L.lnc_b, lcb->data.data(), D));
     CCX_TRY(w->store.upload(&L.ln2_g, l2g->data.data(), D)); CCX_TRY(w->store.upload(&L.ln2_b, l2b->data.data(), D));
     if (w->xs_on) {
-      std::vector<float> wkt((size_t)D * D);
-      for (int hh = 0; hh < H; hh++)
-        for (int f = 0; f < D; f++)
-          for (int dd = 0; dd < 64; dd++) wkt[((size_t)hh * D + f) * 64 + dd] = ckw->data[(size_t)(hh * 64 + dd) * D + f];
-      CCX_TRY(w->store.upload_bf16(&L.WckT, wkt));
-      CCX_TRY(w->store.upload_bf16(&L.Wcq_plain, cqw->data));
+      const std::vector<float> wkt = ccx_xs_relay_key(ckw->data.data(), H, D);
+      CCX_TRY(up_bf16_packed(w, &L.WckT, wkt.data(), H * D, 64, 16));
+      L.Wcq_plain = L.Wcq;
+      CCX_TRY(up_bf16_packed(w, &L.Wcv_x, cvw->data.data(), D, D, 16));
       // cross_attn_ln folded into the cross-attention query (the LayerNorm-free query of the X-stream path)
-      std::vector<float> Wg((size_t)D * D), sv(D), cv(D);
-      for (int n = 0; n < D; n++) {
-        double ss = 0.0, cc = 0.0;
-        for (int k = 0; k < D; k++) {
-          const float v = lcg->data[k] * cqw->data[(size_t)n * D + k];
-          Wg[(size_t)n * D + k] = v;
-          const uint32_t bits = (uint32_t)ccx_host_f32_to_bf16(v) << 16;
-          float r;
-          memcpy(&r, &bits, 4);
-          ss += (double)r;                                   // what the MFMA sums: the bf16-rounded products
-          cc += (double)lcb->data[k] * (double)cqw->data[(size_t)n * D + k];
-        }
-        sv[n] = (float)ss;
-        cv[n] = (float)(cc + (double)cqb->data[n]);
-      }
-      CCX_TRY(w->store.upload_bf16(&L.Wcq_g, Wg)); CCX_TRY(w->store.upload(&L.scq, sv)); CCX_TRY(w->store.upload(&L.ccq, cv));
+      std::vector<float> Wg, sv, cv;
+      ccx_xs_fold_query_ln(lcg->data.data(), lcb->data.data(), cqw->data.data(), cqb->data.data(), D, Wg, sv, cv);
+      CCX_TRY(up_bf16_packed(w, &L.Wcq_g, Wg.data(), D, D, 16)); CCX_TRY(w->store.upload(&L.scq, sv)); CCX_TRY(w->store.upload(&L.ccq, cv));
     }
     const size_t ck = (size_t)w->kv_cap * H * w->Spad * 64, sk = (size_t)B * H * Tc * 64;
     CCX_TRY(w->store.alloc(&L.crossK, ck, true)); CCX_TRY(w->store.alloc(&L.crossV, ck, true));
@@ -860,13 +847,15 @@ static int project_cross_kv(ccx_whisper* w, int n, hipStream_t stream) {
 // ccx_whisper_decoder_logits -- so that the teacher-forced logits always come from the chain a decode of the same size would run.
 // CCX_FUSE_CROSS_Q=0: the two-launch cross-attention query of <= 16 rows; CCX_DEC_LNFREE=0: round 3's X-stream query;
 // CCX_XS_FUSE_Q=0: that query as a launch of its own; CCX_XS_FULL_LINES=0: the streaming kernel's half-line loads (cross_x.h);
-// CCX_DEC_PACKED_ACT=0: the > 16-row chain's LayerNorm and GELU rows row-major between its kernels (decoder.h).
+// CCX_DEC_PACKED_ACT=0: the > 16-row chain's LayerNorm and GELU rows row-major between its kernels (decoder.h); CCX_DEC_PACKED_MID=0:
+// its attention outputs and the resolved rows of the LayerNorm-free query.
 static void read_chain_switches(StepPlan& p) {
   { const char* e = getenv("CCX_FUSE_CROSS_Q"); p.fuse_cross_q = e ? (atoi(e) != 0) : 1; }
   { const char* e = getenv("CCX_DEC_LNFREE"); p.lnfree = !(e && strcmp(e, "0") == 0); }
   { const char* e = getenv("CCX_XS_FUSE_Q"); p.xs_fuse_q = !e || atoi(e) != 0; }
   p.xs_full_lines = ccx_xs_full_lines_switch();
   p.packed_act = ccx_dec_packed_act_switch();
+  p.packed_mid = ccx_dec_packed_mid_switch();
 }
 // which cross attention a decode of B = p.B sequences uses (-> p.xs_active), and the K/V it needs
 // (n_kv: the sequences whose K/V the rows read -- B itself, or the windows of a mapped decode)
@@ -1164,7 +1153,12 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
   // pulls a 1 KB-contiguous wave load about three times as fast as 16 rows x 64 B (profiles/dec_full_lines_experiment.txt).  Whole
   // 16-row tiles only, so that a lane's image ends where the next lane's begins; the rows the head and the prefill gather read (the
   // final LayerNorm) stay row-major.
-  const int packed = (p.packed_act && B > 16 && B % 16 == 0) ? 1 : 0;
+  const int packed = ccx_dec_rows_as_image(p.packed_act, B);
+  // ... and, under a switch of their own, the rest of its bf16 rows: dattn (self attention -> Wo, value projection -> Wco: 24 column
+  // blocks each) and xb (Wo's resolve epilogue -> the LayerNorm-free query, 12 heads' blocks per row tile).  A decode step's lanes only:
+  // the prefill, mapped rows (their launches stay what they were), the beam's indirect self attention and every K/V-cache path keep
+  // row-major rows.
+  const int packed_mid = (ccx_dec_rows_as_image(p.packed_mid, B) && !pre && !map_on && p.beam_size == 0 && xs_active && p.lnfree) ? 1 : 0;
   int pend_n = 0;
   auto ln_linear = [&](int epi, const bf16_t* W, const float* bias, int N, const float* g, const float* bta, void* out, long ldo,
                        DecLinearParams* extra) -> int {
@@ -1239,12 +1233,14 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
     ap.out_bf16 = dattn; ap.row_seq = row_seq;
     // beam search: a step's keys come through the cache indirection (the prefill writes and reads every row's own slot)
     if (p.beam_size > 0 && !pre) { ap.ind = w->beam_ind; ap.ind_ld = Tc; }
+    ap.out_packed = packed_mid;
     CCX_TRY(ccx_launch_dec_attention(ctx, ap, B, 1, true, stream));
     stamp(17, 2);
     if (lnfree) {
       DecLinearParams lp;
       memset(&lp, 0, sizeof(lp));
       lp.M = B; lp.N = D; lp.K = D; lp.W = L.Wo; lp.ldw = D; lp.bias = L.bo; lp.act = dattn; lp.lda = D;
+      lp.act_packed = packed_mid; lp.out_packed = packed_mid;     // dattn in, xb out
       lp.xres = cur; lp.xb = xb; lp.st_out = st2; lp.shift = shift; lp.shift_c = L.bo_mean;
       CCX_TRY(ccx_launch_dec_linear(ctx, ACT_BF16, DEPI_RESOLVE, lp, stream));
     } else {
@@ -1260,7 +1256,7 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
       XsParams xp;
       memset(&xp, 0, sizeof(xp));
       if (lnfree) {
-        xp.xb = xb; xp.ln_stats = st2; xp.ln_s = L.scq; xp.Wq = L.Wcq_g; xp.bq = L.ccq; xp.eps = 1e-5f;
+        xp.xb = xb; xp.xb_packed = packed_mid; xp.ln_stats = st2; xp.ln_s = L.scq; xp.Wq = L.Wcq_g; xp.bq = L.ccq; xp.eps = 1e-5f;
       } else if (xs_fused) {
         xp.x = cur; xp.pend = pend; xp.pend_n = pend_n; xp.pend_stride = pstride; xp.x_out = pend_n > 0 ? other : nullptr;
         xp.ln_g = L.lnc_g; xp.ln_b = L.lnc_b; xp.eps = 1e-5f; xp.Wq = L.Wcq_plain; xp.bq = L.bcq;
@@ -1270,7 +1266,7 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
       xp.part_ml = pre ? w->pf_xs_pml : w->xs_pml + ccx_xs_part_ml_elems(ro);
       xp.X = (pre || map_on) ? w->xa : w->xa + ro * (long)d.n_audio_ctx * D; xp.x_seq_stride = (long)d.n_audio_ctx * D;
       xp.row_seq = map_on ? win : row_seq;
-      xp.Wv = L.Wckv + (long)D * D; xp.bv = L.bckv + D; xp.out = dattn;
+      xp.Wv = L.Wcv_x; xp.bv = L.bckv + D; xp.out = dattn; xp.out_packed = packed_mid;
       xp.rows = B; xp.H = H; xp.S = d.n_audio_ctx; xp.D = D; xp.scale_log2e = scale_log2e;
       xp.lds_pad = (p.cross_lds_pad > 0 && !pre) ? 65536 : 0;
       xp.rows_per_seq = pre ? prefill_rows : 0;
@@ -1278,7 +1274,7 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
       CCX_TRY(ccx_launch_xs_cross_attention(ctx, xp, stream));
       if (xs_fused && pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
       stamp(2, 1);
-      CCX_TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn));
+      CCX_TRY(partial_linear(ACT_BF16, L.Wco, L.bco, D, dattn, packed_mid));
       stamp(19, 2);
     } else {
       memset(&ap, 0, sizeof(ap));

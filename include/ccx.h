@@ -517,6 +517,40 @@ typedef struct ccx_dec_ln_linear_desc {
 } ccx_dec_ln_linear_desc;
 int ccx_dec_ln_linear(ccx_ctx* ctx, const ccx_dec_ln_linear_desc* desc, void* stream);
 
+/* The middle of a decode step's layer on the X-stream path, from the self attention to the cross-attention out projection, on its own
+ * (for kernel parity tests): the production launchers unchanged, in the model's order --
+ *   self attention (q, the self K/V cache, pos)                      -> attention rows (bf16)
+ *   out projection Wo with the in-place residual resolve             -> x, its centred bf16 copy xb, xb's 16-column tile statistics
+ *   LayerNorm-free cross-attention query + per-head expansion        -> xq (bf16)
+ *   the streaming kernel over xa, then merge + value projection      -> attention rows (bf16)
+ *   cross-attention out projection Wco, split-K partial epilogue     -> one f32 slab
+ * packed = 1 asks for the bf16 rows between the kernels (both attention outputs, xb) as fragment images (csrc/decoder.h dec_frag_off); the
+ * launcher takes them under the model's rule only (more than 16 rows, a multiple of 16) and reports what it took in *packed_used.
+ * Inputs.  Device: q f32 [M][D]; self_k / self_v bf16 [M][H][kv_T][64]; x f32 [M][D]; shift f32 [M] or NULL (the rows' centring
+ * shifts); xa bf16 [M][S][D] (row r attends to sequence r).  HOST: pos int [M] (row r attends to keys 0 .. pos[r]); row-major f32
+ * weights wo, cq_w, ck_w, cv_w, co_w [D][D] and vectors bo, lnc_g, lnc_b, cq_b, cv_b, co_b [D], packed and folded inside as the model
+ * does at finalize.
+ * Output.  out, device f32, the parts back to back, every bf16 part widened and read back through the layout it was written in:
+ *   attn_self [M][D] | x [M][D] | xb [M][D] | xb_stats [M][D / 16][2] | xq [M][H][D] | attn_cross [M][D] | co [M][D]
+ * (ccx_dec_mid_chain_out_elems).  The scratch buffers hold whole 16-row tiles and start out as NaN bit patterns, as does `out`.
+ * Checked on the host, CCX_ERR_ARG (1) naming "ccx_dec_mid_chain" and the field: 1 <= M <= 4096; H in {2, 4, 6, 8, 12} and D == 64 H
+ * (the widths the X-stream kernels are instantiated for); 16 <= S <= 4096; 1 <= kv_T <= 4096 and 0 <= pos[r] < kv_T; packed 0 or 1;
+ * non-NULL pointers, 16-byte alignment of the device ones, and the element counts.  Owns its scratch; synchronises the stream. */
+typedef struct ccx_dec_mid_chain_desc {
+  int M, D, H, S, kv_T, packed;
+  const void* q; const void* self_k; const void* self_v; const void* x; const void* shift; const void* xa;
+  const int* pos;
+  const float* wo; const float* bo;
+  const float* lnc_g; const float* lnc_b; const float* cq_w; const float* cq_b;
+  const float* ck_w; const float* cv_w; const float* cv_b;
+  const float* co_w; const float* co_b;
+  void* out;
+  int* packed_used;                                     /* HOST [1], out */
+  int64_t q_elems, kv_elems, x_elems, xa_elems, out_elems;
+} ccx_dec_mid_chain_desc;
+int64_t ccx_dec_mid_chain_out_elems(int M, int D, int H);
+int ccx_dec_mid_chain(ccx_ctx* ctx, const ccx_dec_mid_chain_desc* desc, void* stream);
+
 /* One beam-search step on its own (csrc/dec_beam.hip: dec_beam_topk_kernel, one block per row, then dec_beam_update_kernel, one block
  * per window; the rule is restated in tests/beam_reference.py) for G windows of beam_size consecutive rows, R = G * beam_size.
  * Every row must be in the sampling phase (pos == prompt_len - 1 + n_gen); the rows of a window share n_gen, pos and done (a window

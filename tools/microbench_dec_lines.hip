@@ -10,6 +10,12 @@
 //      asks for them: row-major fragments (16 rows x 64 B per instruction) against a fragment-packed image (tile (m / 16, k / 32) =
 //      64 lanes x 16 B back to back, 1 KB per instruction).  REPS passes per launch; "same" re-reads one matrix (L2 hits after the
 //      first pass), "rotate" walks 8 matrices (12 MB at K = 3072: past one XCD's 4 MB L2).
+//  (c) (profiles/dec_chain_images_experiment.txt) the same [256][768] operand at the out projections' grid: 24 column blocks x 4 row
+//      blocks of 64 rows (dec_linear_kernel<4, 2, 6, ACT_BF16>), and the two ways of filling the chip: 24 x 8 blocks of 32 rows, 24 x 16
+//      of 16.
+//  (d) one (head, 16 rows) block of the LayerNorm-free query + expansion (dec_xq_lnfree_kernel<768>), 12 heads x 16 row tiles: 64 x 768
+//      of Wcq_g and 16 x 768 of xb (24 k-steps each, wave w the head's rows 16 w ..), then WckT's [768][64] head slice (wave w: 12 M
+//      tiles x 2 k-steps), row-major as the kernel asked for them against fragment-packed images.
 // build: hipcc -w --offload-arch=gfx950 -O3 tools/microbench_dec_lines.hip -o microbench_dec_lines && ./microbench_dec_lines
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -61,30 +67,60 @@ __global__ __launch_bounds__(256) void kv_kernel(const unsigned short* Kc, const
 }
 
 // PACKED 0: row-major fragments, 1: fragment-packed image.  grid (NB, 4, ksplit); KMAX k-steps per wave.
-template <int PACKED, int KMAX>
+template <int PACKED, int KMAX, int MT = 4>
 __global__ __launch_bounds__(256) void act_kernel(const unsigned short* A, unsigned* sink, int K, int reps, long rot_stride) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int l15 = lane & 15, h4 = lane >> 4;
   const int ksteps = K >> 5;
   const int ks0 = (blockIdx.z * 4 + wave) * KMAX;
-  const int m0 = blockIdx.y * 64;
+  const int m0 = blockIdx.y * 16 * MT;
   u4 acc = {0, 0, 0, 0};
   for (int r = 0; r < reps; r++) {
     const unsigned short* Ar = A + (long)((r + blockIdx.x) & 7) * rot_stride;
-    u4 af[4][KMAX];
+    u4 af[MT][KMAX];
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
+    for (int j = 0; j < MT; j++) {
 #pragma unroll
       for (int k = 0; k < KMAX; k++) {
-        const unsigned short* a = PACKED ? Ar + ((((long)(blockIdx.y * 4 + j)) * ksteps + ks0 + k) * 64 + lane) * 8
+        const unsigned short* a = PACKED ? Ar + ((((long)(blockIdx.y * MT + j)) * ksteps + ks0 + k) * 64 + lane) * 8
                                          : Ar + (long)(m0 + 16 * j + l15) * K + 8 * h4 + 32 * (ks0 + k);
         af[j][k] = *(const u4*)a;
       }
     }
 #pragma unroll
-    for (int j = 0; j < 4; j++)
+    for (int j = 0; j < MT; j++)
 #pragma unroll
       for (int k = 0; k < KMAX; k++) acc ^= af[j][k];
+    if (acc.x == 0x12345678u) sink[1] = r;   // keeps the passes apart
+  }
+  if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) sink[0] = acc.x;
+}
+
+// PACKED 0: the operands row-major (Wq [768][768], xb [256][768], WkT [12][768][64]), 1: their fragment images.  grid (12, 16).
+template <int PACKED>
+__global__ __launch_bounds__(256) void xq_kernel(const unsigned short* Wq, const unsigned short* xb, const unsigned short* WkT, unsigned* sink, int reps) {
+  constexpr int D = 768, NKS = 24, FW = 192, NMT = 12;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
+  const int h = blockIdx.x, row = blockIdx.y * 16 + n;
+  u4 acc = {0, 0, 0, 0};
+  for (int r = 0; r < reps; r++) {
+    u4 wq[NKS], xr[NKS], wk[NMT][2];
+    const unsigned short* wsrc = PACKED ? Wq + ((long)(h * 4 + wave) * NKS * 64 + lane) * 8 : Wq + (long)(h * 64 + wave * 16 + n) * D + g * 8;
+    const unsigned short* xsrc = PACKED ? xb + ((long)blockIdx.y * NKS * 64 + lane) * 8 : xb + (long)row * D + g * 8;
+    const unsigned short* ksrc = PACKED ? WkT + ((long)h * D + wave * FW) * 64 + lane * 8 : WkT + ((long)h * D + wave * FW + n) * 64 + g * 8;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ks++) wq[ks] = *(const u4*)(wsrc + ks * (PACKED ? 512 : 32));
+#pragma unroll
+    for (int ks = 0; ks < NKS; ks++) xr[ks] = *(const u4*)(xsrc + ks * (PACKED ? 512 : 32));
+#pragma unroll
+    for (int mt = 0; mt < NMT; mt++) {
+      wk[mt][0] = *(const u4*)(ksrc + mt * 1024);
+      wk[mt][1] = *(const u4*)(ksrc + mt * 1024 + (PACKED ? 512 : 32));
+    }
+#pragma unroll
+    for (int ks = 0; ks < NKS; ks++) acc ^= wq[ks] ^ xr[ks];
+#pragma unroll
+    for (int mt = 0; mt < NMT; mt++) acc ^= wk[mt][0] ^ wk[mt][1];
     if (acc.x == 0x12345678u) sink[1] = r;   // keeps the passes apart
   }
   if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) sink[0] = acc.x;
@@ -164,6 +200,47 @@ int main() {
             printf("\n");
           }
         }
+      }
+      // (c)
+      for (int mt : {4, 2, 1}) {
+        const int reps = 16;
+        printf("(c) %3d CUs  256 x  768, 24 column blocks x %2d row blocks :", ncu, 16 / mt);
+        for (int packed = 0; packed < 2; packed++) {
+          std::vector<float> t;
+          for (int it = 0; it < 9; it++) {
+            const dim3 grid(24, 16 / mt, 1);
+            CHECK(hipEventRecord(ea, st));
+            if (mt == 4) { if (packed) hipLaunchKernelGGL((act_kernel<1, 6, 4>), grid, dim3(256), 0, st, A, sink, 768, reps, 0L); else hipLaunchKernelGGL((act_kernel<0, 6, 4>), grid, dim3(256), 0, st, A, sink, 768, reps, 0L); }
+            else if (mt == 2) { if (packed) hipLaunchKernelGGL((act_kernel<1, 6, 2>), grid, dim3(256), 0, st, A, sink, 768, reps, 0L); else hipLaunchKernelGGL((act_kernel<0, 6, 2>), grid, dim3(256), 0, st, A, sink, 768, reps, 0L); }
+            else { if (packed) hipLaunchKernelGGL((act_kernel<1, 6, 1>), grid, dim3(256), 0, st, A, sink, 768, reps, 0L); else hipLaunchKernelGGL((act_kernel<0, 6, 1>), grid, dim3(256), 0, st, A, sink, 768, reps, 0L); }
+            CHECK(hipEventRecord(eb, st)); CHECK(hipEventSynchronize(eb));
+            float ms; CHECK(hipEventElapsedTime(&ms, ea, eb));
+            if (it >= 2) t.push_back(ms);
+          }
+          const float lo = *std::min_element(t.begin(), t.end()), hi = *std::max_element(t.begin(), t.end()), md = median(t);
+          printf("  %s %6.2f us per pass (%6.2f .. %6.2f) |", packed ? "packed   " : "row-major", md * 1e3 / reps, lo * 1e3 / reps, hi * 1e3 / reps);
+        }
+        printf("\n");
+      }
+      // (d): Wq, xb and WkT side by side in A (1.2 + 0.4 + 1.2 MB)
+      {
+        const int reps = 16;
+        const unsigned short *Wq = A, *xb = A + 768 * 768, *WkT = A + 768 * 768 + 256 * 768;
+        printf("(d) %3d CUs  query + expansion operands, 12 heads x 16 row tiles :", ncu);
+        for (int packed = 0; packed < 2; packed++) {
+          std::vector<float> t;
+          for (int it = 0; it < 9; it++) {
+            CHECK(hipEventRecord(ea, st));
+            if (packed) hipLaunchKernelGGL(xq_kernel<1>, dim3(12, 16), dim3(256), 0, st, Wq, xb, WkT, sink, reps);
+            else hipLaunchKernelGGL(xq_kernel<0>, dim3(12, 16), dim3(256), 0, st, Wq, xb, WkT, sink, reps);
+            CHECK(hipEventRecord(eb, st)); CHECK(hipEventSynchronize(eb));
+            float ms; CHECK(hipEventElapsedTime(&ms, ea, eb));
+            if (it >= 2) t.push_back(ms);
+          }
+          const float lo = *std::min_element(t.begin(), t.end()), hi = *std::max_element(t.begin(), t.end()), md = median(t);
+          printf("  %s %6.2f us per pass (%6.2f .. %6.2f) |", packed ? "packed   " : "row-major", md * 1e3 / reps, lo * 1e3 / reps, hi * 1e3 / reps);
+        }
+        printf("\n");
       }
       CHECK(hipStreamDestroy(st));
     }
