@@ -326,6 +326,7 @@ PROTOTYPES = {
     "ccx_peak_normalize": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _f, _vp]),
     "ccx_row_variance": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp]),
     "ccx_cross_attention_xa": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ccx_cross_attention_xa_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ccx_cosine_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "ccx_speaker_profiles": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ccx_resample_sinc": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i, _vp]),
@@ -334,6 +335,8 @@ PROTOTYPES = {
     "ccx_whisper_destroy": (None, [_vp]),
     "ccx_whisper_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i, _i, _i64p]),
     "ccx_whisper_set_max_audio": (_i, [_vp, C.c_double]),
+    "ccx_whisper_set_cross_fp8": (_i, [_vp, _i]),
+    "ccx_whisper_cross_fp8": (_i, [_vp]),
     "ccx_whisper_share_encoder_scratch": (_i, [_vp, _vp]),
     "ccx_whisper_finalize": (_i, [_vp]),
     "ccx_whisper_set_rules": (_i, [_vp, C.POINTER(DecodeRules)]),

@@ -3,6 +3,7 @@
 #include <cstring>
 #include <vector>
 #include "ccx_common.h"
+#include "xa_fp8.h"
 
 // Whisper's decoder cross attention (openai-whisper model.py MultiHeadAttention with xa; called once per layer and decode step from
 // back/api.py:1286-1292 / 1432-1438 / 1474-1480 through transcribe()) reads, per layer, K = xa Wk^T and V = xa Wv^T + bv of every
@@ -31,6 +32,10 @@ struct XsParams {
   float* part_ml;        // [rows][XS_SPLIT][16][2]: reference maximum and denominator of each key half (ccx_xs_part_ml_elems)
   const bf16_t* X;       // [sequences][x_seq_stride]: encoder output rows [S][D] per sequence
   long x_seq_stride;     // elements between sequences
+  // FP8 stream (xa_fp8.h): non-null: the streaming blocks read this block-scaled E4M3 image of the same sequences instead of X and
+  // convert it to bf16 in registers.  The image decodes to X exactly, so the results are the bits of the bf16 stream on X.
+  const unsigned char* X8;
+  long x8_seq_stride;    // bytes between sequences
   const int* row_seq;    // row -> sequence (prompt prefill: several rows per sequence); null: identity
   int rows_per_seq;      // > 1: rows s * rows_per_seq .. + rows_per_seq - 1 all belong to sequence row_seq[s * rows_per_seq] (prefill)
   const bf16_t* Wv;      // cross_attn.value.weight [D][D] as its fragment image
@@ -39,7 +44,8 @@ struct XsParams {
   int rows, H, S, D;
   float scale_log2e;     // (d_head ^ -0.25)^2 * log2(e)
   int lds_pad;           // LDS the streaming blocks claim without using it (occupancy cap while decode lanes overlap)
-  int full_lines;        // how the streaming blocks ask for xa (ccx_xs_full_lines_switch): 0 half lines, 1 full lines
+  int full_lines;        // how the streaming blocks ask for xa (ccx_xs_full_lines_switch): 0 half lines, 1 full lines; no effect on
+                         // the FP8 stream, whose image has one load form
   // rows a multiple of 16 only.  xb_packed: `xb` is the fragment image of the rows (decoder.h dec_frag_off) instead of row-major;
   // out_packed: `out` is written as that image.  The values a lane holds, and so the results, are the same either way.
   int xb_packed, out_packed;
@@ -50,7 +56,8 @@ struct XsParams {
 // 16-byte MFMA operands back to back), so that a wave load is 1 KB contiguous and not 16 rows x 64 B, which a CU pulls out of L2
 // three to four times as fast (profiles/dec_full_lines_experiment.txt section 0b).  A lane receives the 16 bytes a row-major load gave it.
 
-// CCX_XS_FULL_LINES (default 1; read per decode and per call of the stand-alone operator): the value for XsParams::full_lines
+// CCX_XS_FULL_LINES (default 1; read per decode and per call of the stand-alone operator): the value for XsParams::full_lines.
+// It chooses between the two load forms of the bf16 stream and has no effect on the FP8 stream (XsParams::X8).
 int ccx_xs_full_lines_switch();
 
 // cross_attn_ln folded into the cross-attention query (dec_xq_lnfree_kernel): Wg = gamma o Wq [D][D], s_n = sum_k Wg_nk over the bf16
@@ -90,3 +97,12 @@ static inline size_t ccx_xs_part_ml_elems(size_t rows) { return rows * XS_SPLIT 
 int ccx_launch_xs_cross_attention(ccx_ctx* ctx, const XsParams& p, hipStream_t stream);
 // widths the kernels are instantiated for
 bool ccx_xs_supported(int D, int H);
+
+// FP8 encoder-output stream (xa_fp8.h; the format rule is in include/ccx.h).  quantise: rows [n_seq][S][D] of xa (x_seq_stride elements
+// between sequences) -> the image (img_seq_stride bytes between sequences, >= xa_fp8_seq_bytes(S, D)), and xa overwritten with the
+// dequantised values, which bf16 holds exactly (xhat_f32, optional: a dense [n_seq][S][D] f32 copy of them).  The image's unused scale
+// bytes are not written: allocate it zeroed.  readback: the image decoded to bf16 rows with the streaming kernel's conversion.
+int ccx_launch_xa_fp8_quantise(ccx_ctx* ctx, bf16_t* xa, long x_seq_stride, unsigned char* img, long img_seq_stride, float* xhat_f32, int n_seq,
+                               int S, int D, hipStream_t stream);
+int ccx_launch_xa_fp8_readback(ccx_ctx* ctx, const unsigned char* img, long img_seq_stride, bf16_t* out, long out_seq_stride, int n_seq, int S,
+                               int D, hipStream_t stream);

@@ -350,20 +350,43 @@ namespace {
 #ifndef CCX_XS_FULL_NT
 #define CCX_XS_FULL_NT 1
 #endif
+// FL = 2: the FP8 stream -- the tile comes as the block-scaled E4M3 image of xa_fp8.h (its own layout: one load form, whole lines at
+// every width, non-temporal), is converted to bf16 in registers and then takes the full-line form's way through the two strips.
+// CCX_XS_FP8_PF: key tiles in flight in that form (even; the images are half the registers of the bf16 form's).  6 instead of 4 (D = 768:
+// 234 instead of 214 registers) is level alone (65.9 / 193 against 65.6 / 192 us at 256 / 768 rows) and 1 - 2 % slower in the 768-sequence
+// decode step (3.77 against 3.72 ms); 8 spills (profiles/xs_fp8_experiment.txt).
+#ifndef CCX_XS_FP8_PF
+#define CCX_XS_FP8_PF 4
+#endif
 template <int D, int RB = 1, int FL = 0>
 struct XsGeom {
   static constexpr int FW = D / 4;             // features per wave
   static constexpr int NKS = FW / 32;          // k-steps of a wave's partial scores
   static constexpr int NMT = FW / 16;          // M tiles of a wave's context slice
-  static constexpr int PF = 4;                 // key tiles a wave keeps in flight (in situ, 768 sequences in 3 lanes: 2 -> 5.92, 3 -> 5.70, 4 -> 5.65, 6 -> 6.0 ms per step)
+  static constexpr int PF = FL == 2 ? CCX_XS_FP8_PF : 4;   // key tiles a wave keeps in flight (in situ, 768 sequences in 3 lanes: 2 -> 5.92, 3 -> 5.70, 4 -> 5.65, 6 -> 6.0 ms per step)
   static constexpr int RS = 2 * FW + 32;       // bytes per staged key row: +32 makes the transposed reads of 8 rows hit 64 different banks
   static constexpr int STRIP = 16 * RS;        // one staging strip (private to a wave: no barrier)
   static constexpr int NSTRIP = FL ? 2 : 1;    // strips per wave; full lines: tile t + 1 is written while tile t is consumed
   static constexpr int S_OFF = 4 * NSTRIP * STRIP;   // partial-score exchange: [2 buffers][RB rows][4 waves][64 lanes] f32x4
   static constexpr int LDS = S_OFF + 2 * RB * 4 * 1024;
-  static_assert(!FL || (D / 2) % 128 == 0, "full lines: a wave's quarter of a key row must be whole 128-byte lines");
+  static_assert(FL != 1 || (D / 2) % 128 == 0, "full lines: a wave's quarter of a key row must be whole 128-byte lines");
   static_assert(!FL || PF % 2 == 0, "full lines: the strip of a tile is the parity of its slot");
 };
+// one key tile of the FP8 image in a wave's registers (xa_fp8.h): NKS / 2 16-byte loads, an 8-byte load when NKS is odd, the scales
+template <int NKS>
+struct XsFp8Img {
+  u32x4 c[NKS / 2 > 0 ? NKS / 2 : 1];
+  u32x2 t, s;
+};
+// 8 codes (two dwords) times 2^(e8m0 - 127) as 8 bf16: v_cvt_scalef32_pk_bf16_fp8, exact for the images the quantiser writes
+__device__ __forceinline__ bf16x8 xs_fp8x8_to_bf16(uint32_t c0, uint32_t c1, uint32_t e8m0) {
+  const float sc = __builtin_bit_cast(float, e8m0 << 23);
+  const u32x4 v = {__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c0, sc, false)),
+                   __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c0, sc, true)),
+                   __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c1, sc, false)),
+                   __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c1, sc, true))};
+  return __builtin_bit_cast(bf16x8, v);
+}
 // widths whose quarter rows are whole lines take the full-line form when it is asked for
 template <int D> constexpr bool xs_full_lines_ok = (D / 2) % 128 == 0;
 }  // namespace
@@ -394,8 +417,16 @@ template <int D> constexpr bool xs_full_lines_ok = (D / 2) % 128 == 0;
 //      score MFMAs; full lines: see 1 -- eight lanes write one key row's 128 contiguous bytes, conflict-free) and comes back
 //      TRANSPOSED through ds_read_b64_tr_b16 as the A operand of ctx^T [16 features x 16 heads] += xa_tile^T p^T -- D/64
 //      v_mfma_f32_16x16x16_bf16 whose B operand (4 keys x 1 head per lane) is exactly what the S^T accumulator holds after exp2.
-// D = 768: full lines 248 registers, 60 KB of LDS (two strips per wave); half lines 224 registers, 34 KB; no scratch.  Either way
-// two blocks per CU, 8 waves x 4 tiles x 6 KB = 192 KB of loads in flight per CU.
+//      THE FP8 STREAM (FL = 2, XsParams::X8; every width): the tile comes out of the block-scaled E4M3 image of xa (xa_fp8.h): per
+//      wave and tile one 128-byte line of scales and D/8 bytes of codes per key in whole lines (D = 768: three 16-byte loads and one
+//      8-byte load per lane, 3.1 KB instead of 6 KB), non-temporal, PF tiles ahead.  The image is laid out so that a 16-byte load holds
+//      the codes of exactly the two full-line images of one line (key l/8 and key l/8 + 8, chunk l%8) and the lane's 8 scale bytes are
+//      the ones it needs: v_cvt_scalef32_pk_bf16_fp8 turns code pairs into bf16 pairs with the block scale (exact: the codes were
+//      made from bf16 values, xa_fp8.h), and the converted images are staged, read back and consumed exactly as in the full-line
+//      form.  The strips hold bf16, so everything from the score operand on is that form's code: bit-identical to it on the
+//      dequantised rows, which is what an FP8 instance keeps as its bf16 encoder output,
+// D = 768: full lines 248 registers, 60 KB of LDS (two strips per wave); half lines 224 registers, 34 KB; FP8 214 registers, 60 KB;
+// no scratch.  Either way two blocks per CU; in flight per CU: 8 waves x 4 tiles x 6 KB = 192 KB (bf16), x 3.1 KB = 100 KB (FP8).
 // The halves' partials (contexts relative to their own reference, reference, denominator) are merged by dec_xv_project_kernel.
 // Deterministic: a row's numbers depend on nothing but its own q' and xa.
 // RB > 1 (prompt prefill: p.rows_per_seq consecutive rows attend to ONE sequence's xa): a block takes RB rows of a sequence through
@@ -405,7 +436,7 @@ template <int D, int RB, int FL>
 __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsParams p) {
   using G = XsGeom<D, RB, FL>;
   constexpr int FW = G::FW, NKS = G::NKS, NMT = G::NMT, PF = G::PF, RS = G::RS, STRIP = G::STRIP;
-  constexpr bool FULL = FL != 0, NT_HINT = CCX_XS_FULL_NT != 0;
+  constexpr bool FULL = FL != 0, FP8 = FL == 2, NT_HINT = CCX_XS_FULL_NT != 0;
   extern __shared__ __attribute__((aligned(16))) char xs_smem[];
   const int unit = blockIdx.x / XS_SPLIT, sp = blockIdx.x % XS_SPLIT;
   // rows of this block: RB == 1: row = unit; RB > 1: sequence s = unit / groups, rows s * rows_per_seq + gi * RB + j
@@ -430,7 +461,18 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
   const int NTall = (S + 15) >> 4;
   const int T0 = NTall * sp / XS_SPLIT, NT = NTall * (sp + 1) / XS_SPLIT;      // this block's key tiles [T0, NT)
 
-  bf16x8 img[PF][NKS];
+  // FP8: tile t of the sequence's image, this wave's quarter; lane l reads its scales at 8 (l / 4), its codes at 16 l (8 l in the
+  // odd last block).  Every key of the last tile is there (copies of key S - 1, as the bf16 forms re-read it): no clamp
+  const unsigned char* X8p = FP8 ? p.X8 + (long)seq * p.x8_seq_stride + wave * xa_fp8_quarter_bytes(D) : nullptr;
+  XsFp8Img<NKS> img8[FP8 ? PF : 1];
+  auto load_tile8 = [&](XsFp8Img<NKS>& X, int t) {
+    const unsigned char* src = X8p + (long)t * xa_fp8_tile_bytes(D);
+    X.s = __builtin_nontemporal_load((const u32x2*)(src + (lane >> 2) * 8));
+#pragma unroll
+    for (int i2 = 0; i2 < NKS / 2; i2++) X.c[i2] = __builtin_nontemporal_load((const u32x4*)(src + 128 + i2 * 1024 + lane * 16));
+    if constexpr (NKS & 1) X.t = __builtin_nontemporal_load((const u32x2*)(src + 128 + (NKS / 2) * 1024 + lane * 8));
+  };
+  bf16x8 img[FP8 ? 1 : PF][NKS];
   auto load_tile = [&](bf16x8 (&X)[NKS], int t) {
     int key = t * 16 + lk;
     key = key < S ? key : S - 1;                 // the last tile's missing keys re-read the last row; their p is 0
@@ -451,7 +493,10 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
   };
 #pragma unroll
   for (int j = 0; j < PF; j++)
-    if (T0 + j < NT) load_tile(img[j], T0 + j);
+    if (T0 + j < NT) {
+      if constexpr (FP8) load_tile8(img8[j], T0 + j);
+      else load_tile(img[j], T0 + j);
+    }
 
   // the wave's slice of q' (B operand of the scores: head r, feature chunk g); heads >= H: zero; rows past the group: the last row's
   bf16x8 qf[RB][NKS];
@@ -483,6 +528,17 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
   auto stage_full = [&](const bf16x8 (&X)[NKS], int sel) {
 #pragma unroll
     for (int i = 0; i < NKS; i++) *(bf16x8*)(fl_wr + sel * STRIP + (i & 1) * (8 * RS) + (i >> 1) * 128) = X[i];
+  };
+  // FP8: the image converted -- group i2 gives the full-line form's images 2 i2 (key l / 8) and 2 i2 + 1 (key l / 8 + 8) of line i2,
+  // scale bytes i2 and 4 + i2; the odd last block gives chunk l % 4 of key l / 8 + 8 ((l / 4) % 2), scale byte 3 -- to the same places
+  char* t8_wr = strip + (lk + 8 * ((lane >> 2) & 1)) * RS + (NKS - 1) * 64 + (lane & 3) * 16;
+  auto stage_fp8 = [&](const XsFp8Img<NKS>& X, int sel) {
+#pragma unroll
+    for (int i2 = 0; i2 < NKS / 2; i2++) {
+      *(bf16x8*)(fl_wr + sel * STRIP + i2 * 128) = xs_fp8x8_to_bf16(X.c[i2][0], X.c[i2][1], (X.s[0] >> (8 * i2)) & 0xffu);
+      *(bf16x8*)(fl_wr + sel * STRIP + 8 * RS + i2 * 128) = xs_fp8x8_to_bf16(X.c[i2][2], X.c[i2][3], (X.s[1] >> (8 * i2)) & 0xffu);
+    }
+    if constexpr (NKS & 1) *(bf16x8*)(t8_wr + sel * STRIP) = xs_fp8x8_to_bf16(X.t[0], X.t[1], X.s[0] >> 24);
   };
   auto read_back = [&](bf16x8 (&X)[NKS], int sel) {
 #pragma unroll
@@ -555,7 +611,10 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
       __syncthreads();
 #pragma unroll
       for (int j = 0; j < PF; j++)
-        if (T0 + j < NT) load_tile(img[j], T0 + j);
+        if (T0 + j < NT) {
+          if constexpr (FP8) load_tile8(img8[j], T0 + j);
+          else load_tile(img[j], T0 + j);
+        }
     }
 #pragma unroll
     for (int jr = 0; jr < RB; jr++) {
@@ -563,7 +622,12 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
 #pragma unroll
       for (int mt = 0; mt < NMT; mt++) acc[jr][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-    if constexpr (FULL) {
+    if constexpr (FP8) {
+      if (T0 < NT) {
+        stage_fp8(img8[0], 0);
+        if (T0 + PF < NT) load_tile8(img8[0], T0 + PF);
+      }
+    } else if constexpr (FULL) {
       // the range's first tile to strip 0; from then on slot j holds tile t + PF of the tile in slot j - 1
       if (T0 < NT) {
         stage_full(img[0], 0);
@@ -575,7 +639,17 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
       for (int j = 0; j < PF; j++) {
         const int t = t0 + j;
         if (t < NT) {
-          if constexpr (FULL) {
+          if constexpr (FP8) {
+            const int jn = (j + 1) % PF;
+            bf16x8 X[NKS];
+            read_back(X, j & 1);
+            tile(X, t, pass == 0 && t == T0, j & 1, [&]() {
+              if (t + 1 < NT) {
+                stage_fp8(img8[jn], (j & 1) ^ 1);
+                if (t + 1 + PF < NT) load_tile8(img8[jn], t + 1 + PF);
+              }
+            });
+          } else if constexpr (FULL) {
             const int jn = (j + 1) % PF;           // the slot of tile t + 1
             bf16x8 X[NKS];
             read_back(X, j & 1);
@@ -659,12 +733,18 @@ int launch_xs(ccx_ctx* ctx, const XsParams& p, hipStream_t stream) {
   }
   CCX_CHECK_LAUNCH(ctx);
   {
-    ccx_prof_scope ps(ctx, stream, D == 768 ? (multi ? "dec_xs_stream_kernel<768,4>" : "dec_xs_stream_kernel<768,1>") : "dec_xs_stream_kernel", 4.0 * p.rows * 16 * (double)p.S * D,
-                      (double)p.rows * ((double)p.S * D * 2 + p.H * D * 2.0 + XS_SPLIT * p.H * D * 4.0));
+    const char* name = D != 768 ? (p.X8 ? "dec_xs_stream_kernel<fp8>" : "dec_xs_stream_kernel")
+                       : p.X8 ? (multi ? "dec_xs_stream_kernel<768,4,fp8>" : "dec_xs_stream_kernel<768,1,fp8>")
+                              : (multi ? "dec_xs_stream_kernel<768,4>" : "dec_xs_stream_kernel<768,1>");
+    const double xbytes = p.X8 ? (double)xa_fp8_seq_bytes(p.S, D) : (double)p.S * D * 2;
+    ccx_prof_scope ps(ctx, stream, name, 4.0 * p.rows * 16 * (double)p.S * D, (double)p.rows * (xbytes + p.H * D * 2.0 + XS_SPLIT * p.H * D * 4.0));
+    // p.X8: the FP8 stream, one load form at every width (p.full_lines has no effect on it).
     // p.full_lines (CCX_XS_FULL_LINES): 0 = half-line loads, otherwise full lines; widths whose quarter rows are no whole lines
     // (128, 384) have the half-line form only.  The forms are bit-identical.
     int rc;
-    if constexpr (xs_full_lines_ok<D>) {
+    if (p.X8) {
+      rc = launch_xs_stream<D, 2>(ctx, p, stream);
+    } else if constexpr (xs_full_lines_ok<D>) {
       rc = p.full_lines ? launch_xs_stream<D, 1>(ctx, p, stream) : launch_xs_stream<D, 0>(ctx, p, stream);
     } else {
       rc = launch_xs_stream<D, 0>(ctx, p, stream);
@@ -697,6 +777,8 @@ int ccx_launch_xs_cross_attention(ccx_ctx* ctx, const XsParams& p, hipStream_t s
   CCX_REQUIRE(ctx, p.part_o && p.part_ml, "xs cross attention: partial buffers missing");
   CCX_REQUIRE(ctx, !(p.xb_packed || p.out_packed) || p.rows % 16 == 0, "xs cross attention: fragment images need rows=%d to be a multiple of 16", p.rows);
   CCX_REQUIRE(ctx, !p.xb_packed || p.xb, "xs cross attention: xb_packed without xb");
+  CCX_REQUIRE(ctx, !p.X8 || (p.x8_seq_stride >= xa_fp8_seq_bytes(p.S, p.D) && p.x8_seq_stride % 128 == 0 && ((uintptr_t)p.X8 & 127) == 0),
+              "xs cross attention: FP8 image stride %ld too small for %d keys, or image not line-aligned", p.x8_seq_stride, p.S);
   switch (p.D) {
     case 128: return launch_xs<128>(ctx, p, stream);
     case 256: return launch_xs<256>(ctx, p, stream);
@@ -704,6 +786,135 @@ int ccx_launch_xs_cross_attention(ccx_ctx* ctx, const XsParams& p, hipStream_t s
     case 512: return launch_xs<512>(ctx, p, stream);
     default: return launch_xs<768>(ctx, p, stream);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// FP8 encoder-output stream: the quantise kernel (once per encode) and the read-back of its image (tests).  Format: include/ccx.h;
+// arithmetic and layout: xa_fp8.h.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+// One thread per (sequence, key, wave quarter): D / 128 blocks of 32 features.  Per block: amax over the bf16 magnitudes, the block
+// exponent, 32 codes (integer arithmetic, xa_fp8.h), their values back into the row (and into xhat_f32 when given: [n_seq][S][D]
+// dense), and the codes and the scale byte to their places in the image.  The thread of a sequence's last key also writes the
+// copies that pad the last tile, so that the image's bytes depend on nothing but the rows.
+template <int D>
+__global__ __launch_bounds__(256) void xa_fp8_quantise_kernel(bf16_t* __restrict__ xa, long x_seq_stride, unsigned char* __restrict__ img,
+                                                               long img_seq_stride, float* __restrict__ xhat_f32, int S, long total) {
+  constexpr int NKS = D / 128, FW = D / 4;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int w = (int)(i & 3);
+  const long sk = i >> 2;
+  const int key = (int)(sk % S);
+  const long seq = sk / S;
+  bf16_t* row = xa + seq * x_seq_stride + (long)key * D + w * FW;
+  float* frow = xhat_f32 ? xhat_f32 + (seq * S + key) * D + w * FW : nullptr;
+  unsigned char* q = img + seq * img_seq_stride + (long)(key >> 4) * xa_fp8_tile_bytes(D) + w * xa_fp8_quarter_bytes(D);
+  const int k = key & 15, kend = key == S - 1 ? 16 : k + 1;
+#pragma unroll
+  for (int lb = 0; lb < NKS; lb++) {
+    uint32_t v[16];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const u32x4 t = *(const u32x4*)(row + lb * 32 + j * 8);
+      v[4 * j] = t[0]; v[4 * j + 1] = t[1]; v[4 * j + 2] = t[2]; v[4 * j + 3] = t[3];
+    }
+    uint32_t amax = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const uint32_t lo = v[j] & 0x7fffu, hi = (v[j] >> 16) & 0x7fffu;
+      amax = amax > lo ? amax : lo;
+      amax = amax > hi ? amax : hi;
+    }
+    const int e = xa_fp8_block_exp(amax);
+    uint32_t codes[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const uint32_t c0 = xa_fp8_code(v[2 * j] & 0xffffu, e), c1 = xa_fp8_code(v[2 * j] >> 16, e);
+      const uint32_t c2 = xa_fp8_code(v[2 * j + 1] & 0xffffu, e), c3 = xa_fp8_code(v[2 * j + 1] >> 16, e);
+      codes[j] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+      v[2 * j] = xa_fp8_value_bits(c0, e) | (xa_fp8_value_bits(c1, e) << 16);
+      v[2 * j + 1] = xa_fp8_value_bits(c2, e) | (xa_fp8_value_bits(c3, e) << 16);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) *(u32x4*)(row + lb * 32 + j * 8) = (u32x4){v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
+    if (frow) {
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        *(float4*)(frow + lb * 32 + j * 4) = make_float4(__builtin_bit_cast(float, v[2 * j] << 16), __builtin_bit_cast(float, v[2 * j] & 0xffff0000u),
+                                                         __builtin_bit_cast(float, v[2 * j + 1] << 16), __builtin_bit_cast(float, v[2 * j + 1] & 0xffff0000u));
+    }
+    for (int kd = k; kd < kend; kd++) {
+      q[xa_fp8_scale_off(kd, lb, NKS)] = (unsigned char)(e + 127);
+#pragma unroll
+      for (int c = 0; c < 4; c++) *(u32x2*)(q + xa_fp8_code_off(kd, lb * 32 + c * 8, NKS)) = (u32x2){codes[2 * c], codes[2 * c + 1]};
+    }
+  }
+}
+
+// One thread per (sequence, key, 8 features): the image's 8 codes and their scale byte through the streaming kernel's conversion
+template <int D>
+__global__ __launch_bounds__(256) void xa_fp8_readback_kernel(const unsigned char* __restrict__ img, long img_seq_stride, bf16_t* __restrict__ out,
+                                                               long out_seq_stride, int S, long total) {
+  constexpr int NKS = D / 128, FW = D / 4, NC = D / 8;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int f = (int)(i % NC) * 8;
+  const long sk = i / NC;
+  const int key = (int)(sk % S);
+  const long seq = sk / S;
+  const int w = f / FW, fq = f % FW;
+  const unsigned char* q = img + seq * img_seq_stride + (long)(key >> 4) * xa_fp8_tile_bytes(D) + w * xa_fp8_quarter_bytes(D);
+  const u32x2 cd = *(const u32x2*)(q + xa_fp8_code_off(key & 15, fq, NKS));
+  const uint32_t sc = q[xa_fp8_scale_off(key & 15, fq >> 5, NKS)];
+  *(bf16x8*)(out + seq * out_seq_stride + (long)key * D + f) = xs_fp8x8_to_bf16(cd[0], cd[1], sc);
+}
+
+template <int D>
+void launch_xa_fp8_quantise(bf16_t* xa, long xs, unsigned char* img, long is, float* f32, int n_seq, int S, hipStream_t stream) {
+  const long total = (long)n_seq * S * 4;
+  hipLaunchKernelGGL(xa_fp8_quantise_kernel<D>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, xa, xs, img, is, f32, S, total);
+}
+template <int D>
+void launch_xa_fp8_readback(const unsigned char* img, long is, bf16_t* out, long os, int n_seq, int S, hipStream_t stream) {
+  const long total = (long)n_seq * S * (D / 8);
+  hipLaunchKernelGGL(xa_fp8_readback_kernel<D>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, img, is, out, os, S, total);
+}
+}  // namespace
+
+int ccx_launch_xa_fp8_quantise(ccx_ctx* ctx, bf16_t* xa, long x_seq_stride, unsigned char* img, long img_seq_stride, float* xhat_f32, int n_seq,
+                               int S, int D, hipStream_t stream) {
+  CCX_REQUIRE(ctx, ccx_xs_supported(D, D / 64), "xa fp8 quantise: width %d is not instantiated", D);
+  CCX_REQUIRE(ctx, xa && img && n_seq >= 1 && S >= 1 && x_seq_stride >= (long)S * D && img_seq_stride >= xa_fp8_seq_bytes(S, D) &&
+                       img_seq_stride % 128 == 0 && ((uintptr_t)img & 127) == 0 && ((uintptr_t)xa & 15) == 0 && x_seq_stride % 8 == 0,
+              "xa fp8 quantise: bad arguments");
+  ccx_prof_scope ps(ctx, stream, "xa_fp8_quantise_kernel", 0.0, (double)n_seq * (4.0 * S * D + (double)xa_fp8_seq_bytes(S, D)));
+  switch (D) {
+    case 128: launch_xa_fp8_quantise<128>(xa, x_seq_stride, img, img_seq_stride, xhat_f32, n_seq, S, stream); break;
+    case 256: launch_xa_fp8_quantise<256>(xa, x_seq_stride, img, img_seq_stride, xhat_f32, n_seq, S, stream); break;
+    case 384: launch_xa_fp8_quantise<384>(xa, x_seq_stride, img, img_seq_stride, xhat_f32, n_seq, S, stream); break;
+    case 512: launch_xa_fp8_quantise<512>(xa, x_seq_stride, img, img_seq_stride, xhat_f32, n_seq, S, stream); break;
+    default: launch_xa_fp8_quantise<768>(xa, x_seq_stride, img, img_seq_stride, xhat_f32, n_seq, S, stream); break;
+  }
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
+int ccx_launch_xa_fp8_readback(ccx_ctx* ctx, const unsigned char* img, long img_seq_stride, bf16_t* out, long out_seq_stride, int n_seq, int S,
+                               int D, hipStream_t stream) {
+  CCX_REQUIRE(ctx, ccx_xs_supported(D, D / 64), "xa fp8 readback: width %d is not instantiated", D);
+  CCX_REQUIRE(ctx, img && out && n_seq >= 1 && S >= 1 && out_seq_stride >= (long)S * D && img_seq_stride >= xa_fp8_seq_bytes(S, D) &&
+                       ((uintptr_t)out & 15) == 0 && out_seq_stride % 8 == 0,
+              "xa fp8 readback: bad arguments");
+  switch (D) {
+    case 128: launch_xa_fp8_readback<128>(img, img_seq_stride, out, out_seq_stride, n_seq, S, stream); break;
+    case 256: launch_xa_fp8_readback<256>(img, img_seq_stride, out, out_seq_stride, n_seq, S, stream); break;
+    case 384: launch_xa_fp8_readback<384>(img, img_seq_stride, out, out_seq_stride, n_seq, S, stream); break;
+    case 512: launch_xa_fp8_readback<512>(img, img_seq_stride, out, out_seq_stride, n_seq, S, stream); break;
+    default: launch_xa_fp8_readback<768>(img, img_seq_stride, out, out_seq_stride, n_seq, S, stream); break;
+  }
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -716,11 +927,10 @@ __global__ void xs_bf16_to_f32_kernel(const bf16_t* __restrict__ in, float* __re
 }
 }  // namespace
 
-extern "C" int ccx_cross_attention_xa(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
-                                      const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head,
-                                      int n_ctx, float* out_dev, void* stream_) {
-  if (!ctx) return CCX_ERR_ARG;
-  hipStream_t stream = (hipStream_t)stream_;
+// fp8: the FP8 stream on an image quantised here from a copy of xa_dev; xhat_out_dev then receives the image's read-back
+static int cross_attention_xa_impl(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
+                                   const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head, int n_ctx,
+                                   float* out_dev, bool fp8, uint16_t* xhat_out_dev, hipStream_t stream) {
   const int H = n_head, D = 64 * n_head, S = n_ctx;
   CCX_REQUIRE(ctx, ccx_xs_supported(D, H), "cross_attention_xa: %d heads (width %d) not instantiated", H, D);
   CCX_REQUIRE(ctx, q_dev && wk_host && wv_host && bv_host && xa_dev && out_dev && rows >= 1 && n_seq >= 1 && S >= 16, "cross_attention_xa: bad arguments");
@@ -735,10 +945,11 @@ extern "C" int ccx_cross_attention_xa(ccx_ctx* ctx, const float* q_dev, const fl
   // the weights as the model stores them: fragment images (cross_x.h)
   const std::vector<float> wkt_f = ccx_xs_relay_key(wk_host, H, D);
   const std::vector<bf16_t> wkt = pack_mfma_rows(wkt_f.data(), H * D, 64, 16), wv = pack_mfma_rows(wv_host, D, D, 16);
-  bf16_t *d_wkt = nullptr, *d_wv = nullptr, *d_xq = nullptr, *d_out = nullptr;
+  bf16_t *d_wkt = nullptr, *d_wv = nullptr, *d_xq = nullptr, *d_out = nullptr, *d_xc = nullptr;
   float *d_bv = nullptr, *d_po = nullptr, *d_pml = nullptr;
   int* d_rs = nullptr;
-  auto cleanup = [&]() { hipFree(d_wkt); hipFree(d_wv); hipFree(d_xq); hipFree(d_out); hipFree(d_bv); hipFree(d_rs); hipFree(d_po); hipFree(d_pml); };
+  unsigned char* d_img = nullptr;
+  auto cleanup = [&]() { hipFree(d_wkt); hipFree(d_wv); hipFree(d_xq); hipFree(d_out); hipFree(d_bv); hipFree(d_rs); hipFree(d_po); hipFree(d_pml); hipFree(d_xc); hipFree(d_img); };
 #define XS_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return ccx_fail(ctx, CCX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
   XS_TRY(hipMalloc(&d_wkt, wkt.size() * 2)); XS_TRY(hipMalloc(&d_wv, wv.size() * 2)); XS_TRY(hipMalloc(&d_bv, (size_t)D * 4));
   XS_TRY(hipMalloc(&d_xq, (size_t)rows * H * D * 2)); XS_TRY(hipMalloc(&d_out, (size_t)rows * D * 2));
@@ -756,13 +967,42 @@ extern "C" int ccx_cross_attention_xa(ccx_ctx* ctx, const float* q_dev, const fl
   p.rows = rows; p.H = H; p.S = S; p.D = D; p.scale_log2e = 0.125f * 1.4426950408889634f;
   p.rows_per_seq = rows_per_seq > 1 ? rows_per_seq : 0;
   p.full_lines = ccx_xs_full_lines_switch();
-  int rc =ccx_launch_xs_cross_attention(ctx, p, stream);
+  int rc = CCX_OK;
+  if (fp8) {
+    const size_t xbytes = (size_t)n_seq * S * D * 2, ibytes = (size_t)n_seq * xa_fp8_seq_bytes(S, D);
+    XS_TRY(hipMalloc(&d_xc, xbytes)); XS_TRY(hipMalloc(&d_img, ibytes));
+    XS_TRY(hipMemsetAsync(d_img, 0, ibytes, stream));
+    XS_TRY(hipMemcpyAsync(d_xc, xa_dev, xbytes, hipMemcpyDeviceToDevice, stream));
+    rc = ccx_launch_xa_fp8_quantise(ctx, d_xc, (long)S * D, d_img, xa_fp8_seq_bytes(S, D), nullptr, n_seq, S, D, stream);
+    p.X = d_xc; p.X8 = d_img; p.x8_seq_stride = xa_fp8_seq_bytes(S, D);
+  }
+  if (rc == CCX_OK) rc = ccx_launch_xs_cross_attention(ctx, p, stream);
+  if (rc == CCX_OK && fp8) rc = ccx_launch_xa_fp8_readback(ctx, d_img, xa_fp8_seq_bytes(S, D), xhat_out_dev, (long)S * D, n_seq, S, D, stream);
   if (rc == CCX_OK) {
     const long n = (long)rows * D;
     hipLaunchKernelGGL(xs_bf16_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_out, out_dev, n);
     XS_TRY(hipStreamSynchronize(stream));
+  } else {
+    hipStreamSynchronize(stream);        // (FP8: the quantise may be in flight on buffers freed below)
   }
   cleanup();
 #undef XS_TRY
   return rc;
+}
+
+extern "C" int ccx_cross_attention_xa(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
+                                      const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head,
+                                      int n_ctx, float* out_dev, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  return cross_attention_xa_impl(ctx, q_dev, wk_host, wv_host, bv_host, xa_dev, row_seq_host, rows_per_seq, rows, n_seq, n_head, n_ctx, out_dev,
+                                 false, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int ccx_cross_attention_xa_fp8(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
+                                          const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head,
+                                          int n_ctx, float* out_dev, uint16_t* xhat_out_dev, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  CCX_REQUIRE(ctx, xhat_out_dev, "cross_attention_xa_fp8: xhat_out_dev is null");
+  return cross_attention_xa_impl(ctx, q_dev, wk_host, wv_host, bv_host, xa_dev, row_seq_host, rows_per_seq, rows, n_seq, n_head, n_ctx, out_dev,
+                                 true, xhat_out_dev, (hipStream_t)stream_);
 }

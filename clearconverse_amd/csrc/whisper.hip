@@ -64,6 +64,7 @@ struct StepPlan {
   int cross_lds_pad;              // occupancy cap of the cross-attention blocks while lanes overlap (plan_lanes)
   int xs_active;                  // cross attention against the encoder output (select_cross_path)
   int lnfree, xs_fuse_q, fuse_cross_q, xs_full_lines, packed_act, packed_mid;   // the chain's form (read_chain_switches)
+  int xs_fp8;                     // the X-stream reads the FP8 image (an FP8 instance, unless CCX_XS_FP8=0); 0 on a default instance
   int map_on, sid_on;             // the rows read a row -> window map / a stream-id table (ccx_whisper_decode_rows)
   int beam_size, beam_maxc;       // beam search (0: none) and its max_candidates
   int lane_idx;                   // whose stamp trace and stagger slot
@@ -87,11 +88,11 @@ struct StepPlan {
   auto tie() const {
     return std::tie(b0, B, sample_len, max_prompt, select, sampling, cross_stream, cross_lds_pad, xs_active, lnfree, xs_fuse_q, fuse_cross_q,
                     xs_full_lines, packed_act, packed_mid, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows, opt_mask, no_ts, sup_blank,
-                    max_init_ts, hist_ngram, hist_pen_bits, bias_on, trunc_on);
+                    max_init_ts, hist_ngram, hist_pen_bits, bias_on, trunc_on, xs_fp8);
   }
   bool operator<(const StepPlan& o) const { return tie() < o.tie(); }
 };
-static_assert(sizeof(StepPlan) == 30 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 30,
+static_assert(sizeof(StepPlan) == 31 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 31,
               "StepPlan: ints only, and every one of them in tie()");
 
 }  // namespace
@@ -190,6 +191,11 @@ struct ccx_whisper {
   // that takes the K/V path (kv_ready = sequences valid since the last encode).
   static constexpr int kKvSeqs = 80;         // sequences the K/V caches of an X-stream instance hold (4.5 GB at small.en)
   bool xs_on = false;
+  // FP8 encoder-output stream (ccx_whisper_set_cross_fp8, CCX_CROSS_FP8; cross_x.h): the image of xa that the X-stream reads, written by
+  // the quantise kernel at the end of every encode, which also leaves xa holding the dequantised values.  Off: nothing allocated.
+  bool cross_fp8 = false, cross_fp8_called = false;
+  unsigned char* xa8 = nullptr;
+  long xa8_stride = 0;                       // bytes between sequences
   int last_cross_path = -1;                  // ccx_whisper_last_cross_path: 0 kv16, 1 kv_stream, 2 xa_stream
   int kv_cap = 0, kv_ready = 0;
   bf16_t *xq = nullptr, *pf_xq = nullptr;    // expanded queries [rows][H][D] (step rows, prefill rows)
@@ -391,6 +397,26 @@ int ccx_whisper_set_max_audio(ccx_whisper* w, double seconds) {
   if (w->Fraw < 3008) w->Fraw = 3008;
   return CCX_OK;
 }
+
+int ccx_whisper_set_cross_fp8(ccx_whisper* w, int on) {
+  if (!w) return CCX_ERR_ARG;
+  CCX_REQUIRE(w->ctx, !w->finalized, "whisper: set_cross_fp8 after finalize");
+  if (on) {
+    const ccx_whisper_dims& d = w->d;
+    CCX_REQUIRE(w->ctx, d.n_text_state == d.n_audio_state && d.n_text_head == d.n_audio_head,
+                "whisper: set_cross_fp8: decoder width %d (%d heads) differs from the encoder's %d (%d heads): the instance has no X-stream path",
+                d.n_text_state, d.n_text_head, d.n_audio_state, d.n_audio_head);
+    CCX_REQUIRE(w->ctx, ccx_xs_supported(d.n_audio_state, d.n_audio_head),
+                "whisper: set_cross_fp8: width %d is not one the X-stream cross attention is instantiated for (128, 256, 384, 512, 768)", d.n_audio_state);
+    const char* e = getenv("CCX_CROSS_X");
+    CCX_REQUIRE(w->ctx, !e || atoi(e) != 0, "whisper: set_cross_fp8: CCX_CROSS_X=0 turns the X-stream path off, which is the only reader of the FP8 image");
+  }
+  w->cross_fp8 = on != 0;
+  w->cross_fp8_called = true;
+  return CCX_OK;
+}
+
+int ccx_whisper_cross_fp8(ccx_whisper* w) { return w && w->cross_fp8 ? 1 : 0; }
 
 int ccx_whisper_share_encoder_scratch(ccx_whisper* w, ccx_whisper* donor) {
   if (!w) return CCX_ERR_ARG;
@@ -612,6 +638,11 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     const char* e = getenv("CCX_CROSS_X");      // 0: round 2's per-layer cross K/V caches for every sequence (A/B)
     w->xs_on = (!e || atoi(e) != 0) && d.n_text_state == D && d.n_text_head == H && ccx_xs_supported(D, H);
     w->kv_cap = w->xs_on ? (B < ccx_whisper::kKvSeqs ? B : ccx_whisper::kKvSeqs) : B;
+    // the FP8 stream: the setter's word, else CCX_CROSS_FP8 (the benchmark's A/B); the setter was refused where there is no X-stream
+    // path, and CCX_CROSS_X may have changed since
+    const char* f = getenv("CCX_CROSS_FP8");
+    if (!w->cross_fp8_called) w->cross_fp8 = w->xs_on && f && atoi(f) != 0;
+    CCX_REQUIRE(w->ctx, !w->cross_fp8 || w->xs_on, "whisper: the FP8 encoder-output stream needs the X-stream path (CCX_CROSS_X=0?)");
   }
   for (int l = 0; l < d.n_text_layer; l++) {
     const std::string p = "decoder.blocks." + std::to_string(l) + ".";
@@ -686,6 +717,10 @@ int ccx_whisper_finalize(ccx_whisper* w) {
 
   // the encoder output stays with the instance: the decode streams it (cross_x.hip); + one key tile of slack
   CCX_TRY(w->store.alloc(&w->xa, ((size_t)B * S + 16) * D, true));
+  if (w->cross_fp8) {       // + one key tile of slack as well; zeroed: the quantise kernel leaves the unused scale bytes alone
+    w->xa8_stride = xa_fp8_seq_bytes(S, D);
+    CCX_TRY(w->store.alloc(&w->xa8, (size_t)B * w->xa8_stride + xa_fp8_tile_bytes(D), true));
+  }
   if (w->xs_on) {
     CCX_TRY(w->store.alloc(&w->xq, (size_t)B * H * D, true));
     CCX_TRY(w->store.alloc(&w->pf_xq, (size_t)B * ccx_whisper::kPrefillMax * H * D, true));
@@ -849,13 +884,15 @@ static int project_cross_kv(ccx_whisper* w, int n, hipStream_t stream) {
 // CCX_XS_FUSE_Q=0: that query as a launch of its own; CCX_XS_FULL_LINES=0: the streaming kernel's half-line loads (cross_x.h);
 // CCX_DEC_PACKED_ACT=0: the > 16-row chain's LayerNorm and GELU rows row-major between its kernels (decoder.h); CCX_DEC_PACKED_MID=0:
 // its attention outputs and the resolved rows of the LayerNorm-free query.
-static void read_chain_switches(StepPlan& p) {
+// CCX_XS_FP8=0: an FP8 instance streams its bf16 encoder output (the dequantised values: the same bits) instead of the image.
+static void read_chain_switches(const ccx_whisper* w, StepPlan& p) {
   { const char* e = getenv("CCX_FUSE_CROSS_Q"); p.fuse_cross_q = e ? (atoi(e) != 0) : 1; }
   { const char* e = getenv("CCX_DEC_LNFREE"); p.lnfree = !(e && strcmp(e, "0") == 0); }
   { const char* e = getenv("CCX_XS_FUSE_Q"); p.xs_fuse_q = !e || atoi(e) != 0; }
   p.xs_full_lines = ccx_xs_full_lines_switch();
   p.packed_act = ccx_dec_packed_act_switch();
   p.packed_mid = ccx_dec_packed_mid_switch();
+  { const char* e = getenv("CCX_XS_FP8"); p.xs_fp8 = w->cross_fp8 && (!e || atoi(e) != 0); }
 }
 // which cross attention a decode of B = p.B sequences uses (-> p.xs_active), and the K/V it needs
 // (n_kv: the sequences whose K/V the rows read -- B itself, or the windows of a mapped decode)
@@ -880,7 +917,7 @@ static StepPlan single_lane_plan(const ccx_whisper* w, int B, int max_prompt) {
   StepPlan p{};
   p.B = B; p.sample_len = 1; p.max_prompt = max_prompt; p.cross_stream = 1;
   p.stamp_level = w->stamps_on ? w->stamp_level : 0;
-  read_chain_switches(p);
+  read_chain_switches(w, p);
   return p;
 }
 
@@ -928,7 +965,9 @@ int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out, void* stream_) {
     p.out = w->x; p.ldo = D; p.resid = w->x; p.ldr = D;
     CCX_TRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, stream));
   }
-  CCX_TRY(ccx_launch_layernorm(ctx, w->x, D, w->lnp_g, w->lnp_b, w->xa, xa_out, D, M, D, 1e-5f, stream));
+  CCX_TRY(ccx_launch_layernorm(ctx, w->x, D, w->lnp_g, w->lnp_b, w->xa, w->cross_fp8 ? nullptr : xa_out, D, M, D, 1e-5f, stream));
+  // FP8 instance: the image for the X-stream, and xa (and xa_out) become the dequantised values every consumer then shares
+  if (w->cross_fp8) CCX_TRY(ccx_launch_xa_fp8_quantise(ctx, w->xa, (long)S * D, w->xa8, w->xa8_stride, xa_out, B, S, D, stream));
   CCX_TRY(scratch_release(w, stream));
   w->enc_B = B;
   // cross-attention K/V: with the X-stream cross attention only decodes of <= 80 sequences use them and project them themselves
@@ -1271,6 +1310,7 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
       xp.lds_pad = (p.cross_lds_pad > 0 && !pre) ? 65536 : 0;
       xp.rows_per_seq = pre ? prefill_rows : 0;
       xp.full_lines = p.xs_full_lines;
+      if (p.xs_fp8) { xp.X8 = (pre || map_on) ? w->xa8 : w->xa8 + ro * w->xa8_stride; xp.x8_seq_stride = w->xa8_stride; }
       CCX_TRY(ccx_launch_xs_cross_attention(ctx, xp, stream));
       if (xs_fused && pend_n > 0) { float* t = cur; cur = other; other = t; pend_n = 0; }
       stamp(2, 1);
@@ -2100,7 +2140,7 @@ int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
   base.bias_on = w->bias_on ? 1 : 0;      // no table, set or not, is the default plan
   // truncated sampling: {0, 1.0, 0.0}, set or not, and every decode at temperature 0 (greedy, beam) is the plan it always was
   base.trunc_on = (base.sampling && (w->trunc.top_k != 0 || w->trunc.top_p != 1.0f || w->trunc.min_p != 0.0f)) ? 1 : 0;
-  read_chain_switches(base);
+  read_chain_switches(w, base);
   CCX_TRY(select_cross_path(w, base, stream, win ? n_windows : -1));
   if (win) CCX_TRY(upload_row_map(w, win, sids, B, stream));
   BeamWork bw;

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import os
 from dataclasses import asdict
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
@@ -27,6 +28,22 @@ from .word_timing import add_word_timestamps, alignment_tokens, get_end
 
 N_SAMPLES = 480000
 CROSS_PATHS = {0: "kv16", 1: "kv_stream", 2: "xa_stream"}
+XS_WIDTHS = (128, 256, 384, 512, 768)      # widths the X-stream cross attention is instantiated for (csrc/cross_x.hip ccx_xs_supported)
+
+
+def cross_fp8_refusal(dims: WhisperDims) -> Optional[str]:
+    """Why an instance of these dims cannot keep the FP8 encoder-output image (include/ccx.h ccx_whisper_set_cross_fp8), or None: the
+    library's own conditions, checked here before anything is created."""
+    if dims.n_text_state != dims.n_audio_state or dims.n_text_head != dims.n_audio_head:
+        return (f"decoder width {dims.n_text_state} ({dims.n_text_head} heads) differs from the encoder's {dims.n_audio_state} "
+                f"({dims.n_audio_head} heads): the instance has no X-stream path")
+    if dims.n_audio_state not in XS_WIDTHS or dims.n_audio_head * 64 != dims.n_audio_state:
+        return (f"width {dims.n_audio_state} is not one the X-stream cross attention is instantiated for {XS_WIDTHS} "
+                "(the 1280-wide family keeps per-layer K / V caches)")
+    e = os.environ.get("CCX_CROSS_X")
+    if e is not None and e.strip().lstrip("+-").isdigit() and int(e) == 0:
+        return "CCX_CROSS_X=0 turns the X-stream path off, which is the only reader of the FP8 image"
+    return None
 
 
 class CallSettings(NamedTuple):
@@ -46,6 +63,7 @@ class WhisperModel:
     repetition_control = False        # and repetition_penalty / no_repeat_ngram_size
     contextual_bias = False           # and sequence_bias / bad_words_ids / hotwords
     truncated_sampling = False        # and top_k / top_p / min_p
+    cross_fp8 = False                 # the FP8 encoder-output stream (a property of the instance; the library's state after finalize)
 
     def __init__(self, dims: WhisperDims, state_dict: Dict[str, torch.Tensor], max_batch: int = 8,
                  device: int = 0, rules: Optional[DecodeRules] = None, tokenizer=None,
@@ -53,8 +71,16 @@ class WhisperModel:
                  share_encoder_scratch_with: Optional["WhisperModel"] = None, word_alignment: bool = False,
                  alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False,
                  temperature_fallback: bool = False, beam_search: bool = False, decoding_options: bool = False,
-                 repetition_control: bool = False, contextual_bias: bool = False, truncated_sampling: bool = False):
-        """truncated_sampling (default False: a `top_k`, `top_p` or `min_p` off its default 0, 1.0, 0.0 is REFUSED with ValueError --
+                 repetition_control: bool = False, contextual_bias: bool = False, truncated_sampling: bool = False,
+                 cross_fp8: bool = False):
+        """cross_fp8 (default False: the instance allocates nothing more, runs no other kernel and keeps its bits): with it, the
+        instance keeps a block-scaled FP8 image of the encoder output (32-feature blocks, E4M3 codes, power-of-two scales; the rule
+        is in include/ccx.h) and the cross attention of decodes on the "xa_stream" path reads it instead of the bf16 rows.  `encode`
+        then leaves the DEQUANTISED encoder output with the instance -- what `encode(return_xa=True)` returns and every decode path
+        and `align` read.  A property of the instance, like max_batch; refused with CcxError, before anything is allocated, for dims
+        without that path (the 1280-wide family, unequal widths) or under CCX_CROSS_X=0.  `self.cross_fp8` is the library's state.
+        What the quantisation costs in transcript quality on real checkpoints is NOT measured: that is why it is off by default.
+        truncated_sampling (default False: a `top_k`, `top_p` or `min_p` off its default 0, 1.0, 0.0 is REFUSED with ValueError --
         a caller who asks for a cut must not get the whole vocabulary): with it, `transcribe` / `transcribe_batch` and `decode`,
         `decode_rows` honour them (Hugging Face's names and order: temperature, top-k, top-p, min-p; the rule is this project's,
         include/ccx.h ccx_decode_sampling_options; parity unpinned) on every decode at temperature > 0 -- the warm rounds of a
@@ -100,6 +126,10 @@ class WhisperModel:
         the alignment pass -- and `transcribe(hallucination_silence_threshold=)` is honoured, which is built on them."""
         if word_probabilities and not word_alignment:
             raise _lib.CcxError("word_probabilities=True needs word_alignment=True: the probabilities come out of the alignment pass")
+        if cross_fp8:
+            why = cross_fp8_refusal(dims)
+            if why is not None:
+                raise _lib.CcxError(f"cross_fp8=True refused: {why}")
         if not torch.cuda.is_available():
             raise _lib.CcxError("WhisperModel needs a ROCm GPU: the HIP path has no CPU fallback")
         self.dims = dims
@@ -130,6 +160,8 @@ class WhisperModel:
             alignment_heads = [(l, h) for l in range(dims.n_text_layer // 2, dims.n_text_layer) for h in range(dims.n_text_head)]
         self.alignment_heads = [(int(l), int(h)) for l, h in alignment_heads]
         self.ctx.check(self.lib.ccx_whisper_set_max_audio(self.handle, self.max_audio_seconds), "ccx_whisper_set_max_audio")
+        if cross_fp8:
+            self.ctx.check(self.lib.ccx_whisper_set_cross_fp8(self.handle, 1), "ccx_whisper_set_cross_fp8")
         # log-mel / encoder workspaces of another instance (kept alive here): only for instances whose log_mel / encode calls
         # are ordered on one stream, as in BatchPipeline.run_pinned_pipelined (include/ccx.h)
         self._scratch_donor = share_encoder_scratch_with
@@ -158,6 +190,7 @@ class WhisperModel:
             self.ctx.check(self.lib.ccx_whisper_set_tensor(self.handle, name.encode(), t.data_ptr(), code, t.dim(), shape),
                            f"set_tensor({name})")
         self.ctx.check(self.lib.ccx_whisper_finalize(self.handle), "ccx_whisper_finalize")
+        self.cross_fp8 = bool(self.lib.ccx_whisper_cross_fp8(self.handle))      # CCX_CROSS_FP8 at finalize included
 
     def set_rules(self, rules: DecodeRules):
         sup = (C.c_int * len(rules.suppress))(*[int(x) for x in rules.suppress])

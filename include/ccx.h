@@ -108,6 +108,25 @@ int ccx_peak_normalize(ccx_ctx* ctx, const float* x_dev, float* y_dev, int64_t s
 int ccx_cross_attention_xa(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
                            const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head, int n_ctx,
                            float* out_dev, void* stream);
+/* ---- FP8 encoder-output stream (opt-in, ccx_whisper_set_cross_fp8) --------------------------------------------------------------
+ * The format (project-defined, MX-style).  Each key row of xa (D features, bf16) is quantised in blocks of 32 consecutive features:
+ *   block scale   amax = the largest magnitude in the block.  The scale is 2^e, e the smallest integer with amax <= 448 * 2^e,
+ *                 clamped to [-64, 64]; amax == 0 gives e = -64.  e is stored as one E8M0 byte, e + 127.  e comes from the exponent
+ *                 bits of amax (frexp), not from a float log2.
+ *   codes         code = e4m3fn(x / 2^e): OCP E4M3, round to nearest even, clamped to +-448 (only the clamp of e can make that bite).
+ *   value         xhat = code * 2^e.  xhat is always exactly representable in bf16 (at most 4 significant bits, exponent within
+ *                 bf16's range), so the FP8 stream computes, bit for bit, what the bf16 stream computes on xhat.
+ *   inputs        finite (ln_post of finite activations).  NaN and Inf are NOT handled: their codes are unspecified.
+ * Where the bytes sit in HBM (key order within a 16-key tile, the scale bytes, the padding of the last tile) is the streaming
+ * kernel's business (csrc/xa_fp8.h); only the quantise kernel writes the image and only the stream and the read-back below read it.
+ *
+ * ccx_cross_attention_xa with the FP8 stream: xa_dev (not modified) is quantised with the model's quantise kernel, the three launches
+ * run with the streaming kernel reading the image, and xhat_out_dev [n_seq][n_ctx][64 n_head] bf16 (required) receives xhat DECODED
+ * FROM THE IMAGE by a read-back kernel, with the stream's own conversion.  out_dev is bit-identical to ccx_cross_attention_xa on
+ * xhat_out_dev.  CCX_XS_FULL_LINES has no effect here.  Synchronises the stream.  For kernel parity tests. */
+int ccx_cross_attention_xa_fp8(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
+                               const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head,
+                               int n_ctx, float* out_dev, uint16_t* xhat_out_dev, void* stream);
 /* Embedding-quality weight of `_build_speaker_profiles`: out[b] = torch.var(x[b][0 .. n_b)) (unbiased; reference back/api.py:939).
  * fp64 accumulation in a fixed order: a row's value does not depend on its batch mates. */
 int ccx_row_variance(ccx_ctx* ctx, const float* x_dev, int64_t stride, const int* n_samples_dev, int B, float* out_dev, void* stream);
@@ -165,6 +184,21 @@ int ccx_whisper_set_tensor(ccx_whisper* w, const char* name, const void* data, i
 /* Longest clip (seconds) ccx_whisper_logmel must accept (default 30); call before finalize.  The log-mel of the
  * whole clip is normalised with its global maximum, exactly like whisper.audio.log_mel_spectrogram. */
 int ccx_whisper_set_max_audio(ccx_whisper* w, double seconds);
+/* Opt-in, before finalize (default off): keep a block-scaled FP8 image of the encoder output ("FP8 encoder-output stream" above) and
+ * let the cross attention of decodes on the X-stream path (ccx_whisper_last_cross_path == 2) stream it instead of the bf16 rows: half
+ * the bytes per element.  ccx_whisper_encode then ends with a quantise kernel that writes the image AND overwrites the instance's
+ * bf16 encoder output with xhat, so every other consumer (the K / V projection of the <= 80-sequence paths, the alignment kernels,
+ * xa_out_dev) sees the values the stream sees.  Refused (CCX_ERR_ARG, the message names the reason) when the instance has no X-stream
+ * path: n_audio_state not a width csrc/cross_x.hip instantiates (128, 256, 384, 512, 768 -- so not the 1280-wide family), decoder and
+ * encoder width different, or CCX_CROSS_X=0 in the environment.  Where this was not called, CCX_CROSS_FP8=1 in the environment at
+ * ccx_whisper_finalize turns it on (ignored, not refused, on an instance without an X-stream path).  An instance with it off
+ * allocates nothing more, runs no other kernel and computes the bits it always did.
+ * CCX_XS_FP8=0 (read per call with the other chain switches, part of the step graphs' key): an FP8 instance streams its bf16 xhat
+ * instead of the image -- the same bits, for A/B; no effect on a default instance.
+ * What the quantisation costs in transcript quality on real checkpoints is NOT measured. */
+int ccx_whisper_set_cross_fp8(ccx_whisper* w, int on);
+/* 1 when the instance keeps and streams the FP8 image (after finalize: the environment switch included), else 0. */
+int ccx_whisper_cross_fp8(ccx_whisper* w);
 /* Optional, before finalize: take the log-mel / encoder workspaces of `donor` (finalized, same dimensions, at least this
  * instance's capacity) instead of allocating them.  They are only live between ccx_whisper_logmel / set_mel and the end of
  * ccx_whisper_encode.  Users of one group are ordered by the library: every logmel / set_mel waits (event) for the end of the
@@ -343,7 +377,8 @@ int ccx_whisper_set_mel(ccx_whisper* w, const float* mel_dev, int B, void* strea
  * read it directly in their cross attention (csrc/cross_x.hip), decodes of <= 80 sequences project the per-layer cross-attention K / V
  * of their sequences out of it when they start (with CCX_CROSS_X=0 at ccx_whisper_finalize this call projects K / V for all B, as in
  * openai-whisper's kv_cache hooks).
- * xa_out_dev (optional): [B, n_audio_ctx, n_audio_state] f32 copy of the encoder output. */
+ * xa_out_dev (optional): [B, n_audio_ctx, n_audio_state] f32 copy of the encoder output.  On an FP8 instance
+ * (ccx_whisper_set_cross_fp8) it is xhat, the dequantised encoder output that the instance keeps and every decode reads. */
 int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out_dev, void* stream);
 
 /* Teacher-forced decoder pass for parity tests: tokens [B, T] (host int32) -> logits

@@ -1,7 +1,8 @@
 """Stand-alone timing of the X-stream cross attention (csrc/cross_x.hip) through ccx_cross_attention_xa: per-launch HIP-event times
 of its three kernels for a range of row counts (one row per sequence), full small.en width; the streaming kernel once per load form
-(CCX_XS_FULL_LINES = 0 half lines, 1 full lines; the operator reads the switch per call), `reps` timed launches each: mean and (min .. max).
-usage: python tools/xs_bench.py [rows ...]      XS_BENCH_FORMS=0,1 XS_BENCH_REPS=5 override the forms and the repetitions"""
+(CCX_XS_FULL_LINES = 0 half lines, 1 full lines; the operator reads the switch per call; 8 = the FP8 stream, through
+ccx_cross_attention_xa_fp8), `reps` timed launches each: mean and (min .. max); TB/s of the bytes the form actually moves.
+usage: python tools/xs_bench.py [rows ...]      XS_BENCH_FORMS=0,1,8 XS_BENCH_REPS=5 override the forms and the repetitions"""
 import os
 import sys
 import numpy as np
@@ -23,23 +24,29 @@ def main():
     q = torch.randn(nmax, D, generator=g).cuda()
     out = torch.empty(nmax, D, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
-    forms = os.environ.get("XS_BENCH_FORMS", "0,1").split(",")
+    forms = os.environ.get("XS_BENCH_FORMS", "0,1,8").split(",")
+    xhat = torch.empty(nmax, S, D, dtype=torch.bfloat16, device="cuda") if "8" in forms else None
     reps = int(os.environ.get("XS_BENCH_REPS", "5"))
-    names = {"0": "half lines", "1": "full lines"}
+    names = {"0": "half lines", "1": "full lines", "8": "fp8"}
     for rows in rows_list:
         line = f"rows {rows:4d}:"
         for form in forms:
-            os.environ["CCX_XS_FULL_LINES"] = form
+            if form != "8":
+                os.environ["CCX_XS_FULL_LINES"] = form
             for it in range(2 + reps):
                 if it == 2:
                     ctx.prof_enable(True)
-                ctx.check(lib.ccx_cross_attention_xa(ctx.handle, q.data_ptr(), wk.ctypes.data, wv.ctypes.data, bv.ctypes.data, xa.data_ptr(), None,
-                                                     0, rows, rows, H, S, out.data_ptr(), st))
+                if form == "8":
+                    ctx.check(lib.ccx_cross_attention_xa_fp8(ctx.handle, q.data_ptr(), wk.ctypes.data, wv.ctypes.data, bv.ctypes.data, xa.data_ptr(),
+                                                             None, 0, rows, rows, H, S, out.data_ptr(), xhat.data_ptr(), st))
+                else:
+                    ctx.check(lib.ccx_cross_attention_xa(ctx.handle, q.data_ptr(), wk.ctypes.data, wv.ctypes.data, bv.ctypes.data, xa.data_ptr(), None,
+                                                         0, rows, rows, H, S, out.data_ptr(), st))
             torch.cuda.synchronize()
             recs = ctx.prof_records()
             ctx.prof_enable(False)
             if form == forms[0]:
-                for name, fl, by, ms in recs[-3:]:
+                for name, fl, by, ms in [r for r in recs if r[0].startswith("dec_x")][-3:]:
                     if "stream" not in name:
                         line += f"  {name.split('<')[0][4:]} {ms * 1e3:6.1f} us"
             v = [(ms * 1e3, by) for name, fl, by, ms in recs if "stream" in name]
