@@ -103,6 +103,27 @@ class DecLnLinearDesc(C.Structure):
         ("out", C.c_void_p), ("x_elems", C.c_int64), ("out_elems", C.c_int64)]
 
 
+class DecLinearDesc(C.Structure):
+    """ccx_dec_linear_desc (include/ccx.h): one launch of dec_linear_kernel on its own, every device buffer the caller's."""
+    _fields_ = [
+        ("act", C.c_int), ("epi", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+        ("w_host", C.c_void_p), ("bias", C.c_void_p),
+        ("x", C.c_void_p), ("pend", C.c_void_p), ("pend_n", C.c_int), ("pend_stride", C.c_int64), ("x_out", C.c_void_p),
+        ("ln_g", C.c_void_p), ("ln_b", C.c_void_p), ("eps", C.c_float), ("ln_mean_out", C.c_void_p),
+        ("act_rows", C.c_void_p), ("lda", C.c_int64),
+        ("part_o", C.c_void_p), ("part_ml", C.c_void_p), ("nsplit", C.c_int),
+        ("out", C.c_void_p), ("ldo", C.c_int64), ("out_stride", C.c_int64),
+        ("cache_k", C.c_void_p), ("cache_v", C.c_void_p), ("cache_T", C.c_int), ("n_seq", C.c_int),
+        ("pos", C.POINTER(C.c_int)), ("row_seq", C.POINTER(C.c_int)),
+        ("bias_elems", C.c_int64), ("x_elems", C.c_int64), ("pend_elems", C.c_int64), ("x_out_elems", C.c_int64),
+        ("ln_elems", C.c_int64), ("ln_mean_out_elems", C.c_int64), ("act_elems", C.c_int64), ("part_o_elems", C.c_int64),
+        ("part_ml_elems", C.c_int64), ("out_elems", C.c_int64), ("cache_elems", C.c_int64)]
+
+
+DEC_ACT_LN, DEC_ACT_BF16, DEC_ACT_COMBINE = range(3)
+DEC_EPI_PARTIAL, DEC_EPI_F32, DEC_EPI_SELF_QKV, DEC_EPI_GELU = range(4)
+
+
 class DecodeSamplingOptions(C.Structure):
     """ccx_decode_sampling_options (include/ccx.h): top_k, top_p and min_p; the defaults are {0, 1.0, 0.0}."""
     _fields_ = [("top_k", C.c_int), ("top_p", C.c_float), ("min_p", C.c_float)]
@@ -362,6 +383,7 @@ PROTOTYPES = {
     "ccx_whisper_decode_greedy": (_i, [_vp, _i32p, _i32p, _i, _i, _i, _i32p, _i32p, _fp, _fp, _vp]),
     "ccx_dec_attention_desc": (_i, [_vp, _i, C.POINTER(DecAttnDesc), _vp]),
     "ccx_dec_ln_linear": (_i, [_vp, C.POINTER(DecLnLinearDesc), _vp]),
+    "ccx_dec_linear_op": (_i, [_vp, C.POINTER(DecLinearDesc), _vp]),
     "ccx_dec_mid_chain_out_elems": (_i64, [_i, _i, _i]),
     "ccx_dec_mid_chain": (_i, [_vp, C.POINTER(DecMidChainDesc), _vp]),
     "ccx_dec_select_step": (_i, [_vp, C.POINTER(DecSelectDesc), _vp]),

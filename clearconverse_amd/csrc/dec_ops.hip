@@ -1,5 +1,5 @@
-// dec_ops.hip -- the decode step's attention forms and its token-select kernel as stand-alone operators of the C ABI (include/ccx.h:
-// ccx_dec_attention_desc, ccx_dec_ln_linear, ccx_dec_select_step).  For kernel parity tests: each entry point fills the parameter block the model handle
+// dec_ops.hip -- the decode step's attention forms, its skinny linear and its token-select kernel as stand-alone operators of the C ABI
+// (include/ccx.h: ccx_dec_attention_desc, ccx_dec_ln_linear, ccx_dec_linear_op, ccx_dec_select_step).  For kernel parity tests: each entry point fills the parameter block the model handle
 // fills (whisper.hip dec_step / dec_head) and calls the production launchers of decoder.hip unchanged.  Everything the kernels assume is
 // checked on the host first; scratch is owned here and freed on every path.
 #include "../../include/ccx.h"
@@ -204,6 +204,13 @@ extern "C" int ccx_dec_ln_linear(ccx_ctx* ctx, const ccx_dec_ln_linear_desc* d, 
   const int ksplit = ccx_dec_linear_ksplit(Kin, depi);
   CCX_REQUIRE(ctx, epi == CCX_DEC_EPI_PARTIAL || ksplit == 1, "ccx_dec_ln_linear: %d input columns need the PARTIAL epilogue", Kin);
   CCX_REQUIRE(ctx, ksplit <= 4, "ccx_dec_ln_linear: %d input columns leave %d slabs (at most 4)", Kin, ksplit);
+  {
+    // the launcher's rule (ccx_dec_linear_starved_slice), here before the LayerNorm kernel is launched
+    int len = 0;
+    CCX_REQUIRE(ctx, F == 0 || ccx_dec_linear_starved_slice(K, 1, &len) < 0, "ccx_dec_ln_linear: K = %d is a K slice of %d k-steps, too few for each of the 4 waves to own one", K, len);
+    CCX_REQUIRE(ctx, ccx_dec_linear_starved_slice(Kin, ksplit, &len) < 0, "ccx_dec_ln_linear: %s = %d leaves a K slice of %d k-steps, too few for each of the 4 waves to own one",
+                F > 0 ? "F" : "K", Kin, len);
+  }
   CCX_REQUIRE(ctx, d->x && d->ln_g && d->ln_b && d->w_host && d->out, "ccx_dec_ln_linear: x, ln_g, ln_b, w_host or out is NULL");
   CCX_REQUIRE(ctx, F == 0 || d->w1_host, "ccx_dec_ln_linear: w1_host is NULL with F = %d", F);
   CCX_REQUIRE(ctx, ccx_aligned16(d->x) && ccx_aligned16(d->ln_g) && ccx_aligned16(d->ln_b) && ccx_aligned16(d->out) && ccx_aligned16(d->b1) && ccx_aligned16(d->bias),
@@ -268,6 +275,126 @@ extern "C" int ccx_dec_ln_linear(ccx_ctx* ctx, const ccx_dec_ln_linear_desc* d, 
       DO_HIP(hipGetLastError());
     }
   }
+  DO_HIP(hipStreamSynchronize(stream));      // the scratch is freed on return
+  return rc;
+}
+
+// One launch of dec_linear_kernel as the <= 16-row chain makes it (whisper.hip dec_step: the ln_linear / partial_linear lambdas): the
+// caller's device buffers in their native types, so that a test can pre-fill them with sentinels and see which bytes changed.
+extern "C" int ccx_dec_linear_op(ccx_ctx* ctx, const ccx_dec_linear_desc* d, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_linear_op: desc is NULL");
+  const int act = d->act, epi = d->epi, M = d->M, N = d->N, K = d->K;
+  CCX_REQUIRE(ctx, act == CCX_DEC_ACT_LN || act == CCX_DEC_ACT_BF16 || act == CCX_DEC_ACT_COMBINE, "ccx_dec_linear_op: unknown act %d", act);
+  CCX_REQUIRE(ctx, epi >= CCX_DEC_EPI_PARTIAL && epi <= CCX_DEC_EPI_GELU, "ccx_dec_linear_op: unknown epi %d", epi);
+  const bool is_ln = act == CCX_DEC_ACT_LN, is_bf16 = act == CCX_DEC_ACT_BF16, is_comb = act == CCX_DEC_ACT_COMBINE;
+  const bool is_part = epi == CCX_DEC_EPI_PARTIAL, is_qkv = epi == CCX_DEC_EPI_SELF_QKV;
+  // the pairs ccx_launch_dec_linear dispatches
+  CCX_REQUIRE(ctx, is_bf16 || (is_ln && !is_part) || (is_comb && is_part), "ccx_dec_linear_op: act %d with epi %d is not a pair the launcher has", act, epi);
+  const int kact = is_ln ? ACT_LN : is_bf16 ? ACT_BF16 : ACT_COMBINE;
+  const int depi = is_part ? DEPI_PARTIAL : epi == CCX_DEC_EPI_F32 ? DEPI_F32 : is_qkv ? DEPI_SELF_QKV : DEPI_BF16_GELU;
+  CCX_REQUIRE(ctx, M >= 1 && M <= (is_bf16 ? 4096 : 16), "ccx_dec_linear_op: M = %d out of range [1, %d]", M, is_bf16 ? 4096 : 16);
+  CCX_REQUIRE(ctx, K >= 32 && K % 32 == 0 && K <= (is_bf16 ? 5120 : 1280), "ccx_dec_linear_op: K = %d must be a multiple of 32 in [32, %d]", K, is_bf16 ? 5120 : 1280);
+  CCX_REQUIRE(ctx, (!is_comb && !is_qkv) || K % 64 == 0, "ccx_dec_linear_op: K = %d must be a multiple of 64 (whole heads)", K);
+  CCX_REQUIRE(ctx, N >= 4 && N % 4 == 0 && N <= 8192, "ccx_dec_linear_op: N = %d must be a multiple of 4 in [4, 8192]", N);
+  CCX_REQUIRE(ctx, !is_qkv || N == 3 * K, "ccx_dec_linear_op: SELF_QKV needs N == 3 K (N = %d, K = %d)", N, K);
+  const int ksplit = ccx_dec_linear_ksplit(K, depi);
+  CCX_REQUIRE(ctx, is_part || ksplit == 1, "ccx_dec_linear_op: K = %d needs the PARTIAL epilogue", K);
+  CCX_REQUIRE(ctx, ksplit <= 4, "ccx_dec_linear_op: K = %d leaves %d slabs (at most 4)", K, ksplit);
+  {
+    int len = 0;
+    const int z = ccx_dec_linear_starved_slice(K, ksplit, &len);
+    CCX_REQUIRE(ctx, z < 0, "ccx_dec_linear_op: K = %d leaves K slice %d of %d with %d k-steps, too few for each of the 4 waves to own one", K, z, ksplit, len);
+  }
+  CCX_REQUIRE(ctx, d->w_host != nullptr, "ccx_dec_linear_op: w_host is NULL");
+  if (d->bias) {
+    CCX_REQUIRE(ctx, ccx_aligned16(d->bias), "ccx_dec_linear_op: bias not 16-byte aligned");
+    CCX_REQUIRE(ctx, N <= d->bias_elems, "ccx_dec_linear_op: bias is read up to element %d, bias_elems=%ld", N, (long)d->bias_elems);
+  }
+  const int64_t MK = (int64_t)M * K;
+  if (is_ln) {
+    CCX_REQUIRE(ctx, d->x && d->pend && d->ln_g && d->ln_b, "ccx_dec_linear_op: x, pend, ln_g or ln_b is NULL");
+    CCX_REQUIRE(ctx, ccx_aligned16(d->x) && ccx_aligned16(d->pend) && ccx_aligned16(d->ln_g) && ccx_aligned16(d->ln_b), "ccx_dec_linear_op: x, pend, ln_g or ln_b not 16-byte aligned");
+    CCX_REQUIRE(ctx, d->pend_n >= 0 && d->pend_n <= 4, "ccx_dec_linear_op: pend_n = %d out of range [0, 4]", d->pend_n);
+    CCX_REQUIRE(ctx, d->pend_stride >= MK && d->pend_stride % 4 == 0, "ccx_dec_linear_op: pend_stride = %ld smaller than a slab or not a multiple of 4", (long)d->pend_stride);
+    CCX_REQUIRE(ctx, MK <= d->x_elems, "ccx_dec_linear_op: x is read up to element %ld, x_elems=%ld", (long)MK, (long)d->x_elems);
+    const int64_t pn = (int64_t)((d->pend_n > 1 ? d->pend_n : 1) - 1) * d->pend_stride + MK;     // slab 0 is read also when pend_n == 0
+    CCX_REQUIRE(ctx, pn <= d->pend_elems, "ccx_dec_linear_op: pend is read up to element %ld, pend_elems=%ld", (long)pn, (long)d->pend_elems);
+    CCX_REQUIRE(ctx, K <= d->ln_elems, "ccx_dec_linear_op: ln_g / ln_b are read up to element %d, ln_elems=%ld", K, (long)d->ln_elems);
+    if (d->x_out) {
+      CCX_REQUIRE(ctx, ccx_aligned16(d->x_out) && d->x_out != d->x, "ccx_dec_linear_op: x_out not 16-byte aligned or aliasing x");
+      CCX_REQUIRE(ctx, MK <= d->x_out_elems, "ccx_dec_linear_op: x_out is written up to element %ld, x_out_elems=%ld", (long)MK, (long)d->x_out_elems);
+    }
+    if (d->ln_mean_out)
+      CCX_REQUIRE(ctx, M <= d->ln_mean_out_elems, "ccx_dec_linear_op: ln_mean_out is written up to element %d, ln_mean_out_elems=%ld", M, (long)d->ln_mean_out_elems);
+  } else if (is_bf16) {
+    CCX_REQUIRE(ctx, d->act_rows && ccx_aligned16(d->act_rows), "ccx_dec_linear_op: act_rows null or not 16-byte aligned");
+    CCX_REQUIRE(ctx, d->lda >= K && d->lda % 8 == 0, "ccx_dec_linear_op: lda = %ld must be >= K and a multiple of 8", (long)d->lda);
+    const int64_t an = (int64_t)(M - 1) * d->lda + K;
+    CCX_REQUIRE(ctx, an <= d->act_elems, "ccx_dec_linear_op: act_rows are read up to element %ld, act_elems=%ld", (long)an, (long)d->act_elems);
+  } else {
+    CCX_REQUIRE(ctx, d->nsplit >= 1 && d->nsplit <= 8, "ccx_dec_linear_op: nsplit = %d out of range [1, 8]", d->nsplit);
+    CCX_REQUIRE(ctx, d->part_o && d->part_ml && ccx_aligned16(d->part_o) && ccx_aligned16(d->part_ml), "ccx_dec_linear_op: part_o / part_ml null or not 16-byte aligned");
+    const int64_t po = MK * d->nsplit, pml = (int64_t)M * (K / 64) * d->nsplit * 2;
+    CCX_REQUIRE(ctx, po <= d->part_o_elems, "ccx_dec_linear_op: part_o is read up to element %ld, part_o_elems=%ld", (long)po, (long)d->part_o_elems);
+    CCX_REQUIRE(ctx, pml <= d->part_ml_elems, "ccx_dec_linear_op: part_ml is read up to element %ld, part_ml_elems=%ld", (long)pml, (long)d->part_ml_elems);
+  }
+  // output
+  CCX_REQUIRE(ctx, d->out && ccx_aligned16(d->out), "ccx_dec_linear_op: out null or not 16-byte aligned");
+  const int ncol = is_qkv ? K : N;                     // columns of a row of `out`
+  CCX_REQUIRE(ctx, d->ldo >= ncol && d->ldo % 4 == 0, "ccx_dec_linear_op: ldo = %ld must be >= %d and a multiple of 4", (long)d->ldo, ncol);
+  // (the SELF_QKV epilogue does not read ldo: its q rows lie K apart)
+  int64_t n_out = (int64_t)(M - 1) * (is_qkv ? K : d->ldo) + ncol;
+  if (is_part) {
+    CCX_REQUIRE(ctx, d->out_stride >= (int64_t)M * d->ldo && d->out_stride % 4 == 0, "ccx_dec_linear_op: out_stride = %ld smaller than a slab (M ldo) or not a multiple of 4", (long)d->out_stride);
+    n_out += (int64_t)(ksplit - 1) * d->out_stride;
+  }
+  CCX_REQUIRE(ctx, n_out <= d->out_elems, "ccx_dec_linear_op: out is written up to element %ld, out_elems=%ld", (long)n_out, (long)d->out_elems);
+  if (is_qkv) {
+    const int H = K / 64, Tc = d->cache_T, n_seq = d->n_seq;
+    CCX_REQUIRE(ctx, Tc >= 1 && Tc <= 4096 && n_seq >= 1 && n_seq <= 4096, "ccx_dec_linear_op: cache_T = %d or n_seq = %d out of range [1, 4096]", Tc, n_seq);
+    CCX_REQUIRE(ctx, d->cache_k && d->cache_v && ccx_aligned16(d->cache_k) && ccx_aligned16(d->cache_v), "ccx_dec_linear_op: cache_k / cache_v null or not 16-byte aligned");
+    const int64_t cn = (int64_t)n_seq * H * Tc * 64;
+    CCX_REQUIRE(ctx, cn <= d->cache_elems, "ccx_dec_linear_op: cache_k / cache_v are written up to element %ld, cache_elems=%ld", (long)cn, (long)d->cache_elems);
+    CCX_REQUIRE(ctx, d->pos != nullptr, "ccx_dec_linear_op: pos is NULL");
+    if (!d->row_seq) CCX_REQUIRE(ctx, M <= n_seq, "ccx_dec_linear_op: row_seq is NULL with more rows (%d) than sequences (%d)", M, n_seq);
+    std::vector<unsigned char> taken((size_t)n_seq * Tc, 0);
+    for (int m = 0; m < M; m++) {
+      CCX_REQUIRE(ctx, d->pos[m] >= 0 && d->pos[m] < Tc, "ccx_dec_linear_op: pos[%d] = %d out of range [0, cache_T = %d)", m, d->pos[m], Tc);
+      const int sq = d->row_seq ? d->row_seq[m] : m;
+      CCX_REQUIRE(ctx, sq >= 0 && sq < n_seq, "ccx_dec_linear_op: row_seq[%d] = %d out of range [0, %d)", m, sq, n_seq);
+      unsigned char& t = taken[(size_t)sq * Tc + d->pos[m]];
+      CCX_REQUIRE(ctx, !t, "ccx_dec_linear_op: row %d names (sequence %d, pos %d) a second time", m, sq, d->pos[m]);
+      t = 1;
+    }
+  }
+
+  ccx_op_scratch sc;
+  bf16_t* d_w = nullptr; int* d_pos = nullptr; int* d_rs = nullptr;
+  {
+    const std::vector<bf16_t> pw = pack_mfma_rows(d->w_host, N, K, 32);
+    DO_HIP(sc.upload(&d_w, pw.data(), pw.size()));
+  }
+  DecLinearParams lp;
+  memset(&lp, 0, sizeof(lp));
+  lp.M = M; lp.N = N; lp.K = K; lp.W = d_w; lp.ldw = K; lp.bias = (const float*)d->bias; lp.out = d->out; lp.ldo = (long)d->ldo;
+  if (is_ln) {
+    lp.x = (const float*)d->x; lp.pend = (const float*)d->pend; lp.pend_n = d->pend_n; lp.pend_stride = (long)d->pend_stride;
+    lp.x_out = (float*)d->x_out; lp.ln_g = (const float*)d->ln_g; lp.ln_b = (const float*)d->ln_b; lp.eps = d->eps;
+    lp.ln_mean_out = (float*)d->ln_mean_out;
+  } else if (is_bf16) {
+    lp.act = (const bf16_t*)d->act_rows; lp.lda = (long)d->lda;
+  } else {
+    lp.part_o = (const float*)d->part_o; lp.part_ml = (const float*)d->part_ml; lp.nsplit = d->nsplit;
+  }
+  if (is_part) lp.pend_stride = (long)d->out_stride;   // (ACT_LN has no PARTIAL pair: the field is free)
+  if (is_qkv) {
+    DO_HIP(sc.upload(&d_pos, d->pos, (size_t)M));
+    if (d->row_seq) DO_HIP(sc.upload(&d_rs, d->row_seq, (size_t)M));
+    lp.cache_k = (bf16_t*)d->cache_k; lp.cache_v = (bf16_t*)d->cache_v; lp.cache_T = d->cache_T; lp.pos = d_pos; lp.row_seq = d_rs;
+  }
+  const int rc = ccx_launch_dec_linear(ctx, kact, depi, lp, stream);
   DO_HIP(hipStreamSynchronize(stream));      // the scratch is freed on return
   return rc;
 }

@@ -42,6 +42,18 @@ struct DecLinearParams {
 int ccx_launch_dec_linear(ccx_ctx* ctx, int act, int epi, const DecLinearParams& p, hipStream_t stream);
 // number of grid.z K-slices ccx_launch_dec_linear will use (= number of partial slabs written)
 int ccx_dec_linear_ksplit(int K, int epi);
+// The launcher's rule on K: every one of a block's 4 waves must own a k-step of the block's grid.z slice.  A slice of L k-steps
+// (per_z = ceil(K / 32 / ksplit) of them, the last slice what is left) gives a wave per_w = ceil(L / 4); the last wave starts at
+// 3 per_w, so the rule is 3 per_w < L -- it fails for L = 1, 2, 3, 5, 6 and 9 (and for an empty slice).  Returns the first slice
+// that breaks it and its length in *len, or -1.
+static inline int ccx_dec_linear_starved_slice(int K, int ksplit, int* len) {
+  const int ksteps = K / 32, per_z = (ksteps + ksplit - 1) / ksplit;
+  for (int z = 0; z < ksplit; z++) {
+    const int L = ksteps - z * per_z < per_z ? ksteps - z * per_z : per_z;
+    if (L <= 0 || 3 * ((L + 3) / 4) >= L) { *len = L; return z; }
+  }
+  return -1;
+}
 // out = bf16 LayerNorm(x + sum pend); if x_out != null also writes the resolved x there (must not alias x); if mean_out != null
 // also every row's centring shift from its LayerNorm statistics (the same bits the ACT_LN prologue of dec_linear computes)
 int ccx_launch_dec_resolve_ln(ccx_ctx* ctx, const float* x, const float* pend, int pend_n, long pend_stride, const float* g,

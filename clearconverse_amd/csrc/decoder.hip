@@ -579,6 +579,14 @@ int ccx_launch_dec_linear(ccx_ctx* ctx, int act, int epi, const DecLinearParams&
   CCX_REQUIRE(ctx, epi == DEPI_PARTIAL || ksplit == 1, "dec_linear: K=%d needs a split-K (partial) epilogue", p.K);
   CCX_REQUIRE(ctx, ksplit <= 4, "dec_linear: K=%d would leave %d partial slabs (at most 4)", p.K, ksplit);
   CCX_REQUIRE(ctx, epi != DEPI_PARTIAL || p.pend_stride >= (long)p.M * p.ldo, "dec_linear: pend_stride too small");
+  // Every wave of a block must own a k-step of its grid.z slice: a wave left without one (slices of 1, 2, 3, 5, 6 or 9 k-steps) still
+  // issues its clamped weight and activation prefetch from ks0 = kz0 + wave * per_w, which then lies behind the slice -- for the
+  // last column tile behind the packed weight image.  The model never asks for one: n_state is a multiple of 128, the MLP 4 x that.
+  {
+    int len = 0;
+    const int z = ccx_dec_linear_starved_slice(p.K, ksplit, &len);
+    CCX_REQUIRE(ctx, z < 0, "dec_linear: K=%d leaves K slice %d of %d with %d k-steps, too few for each of the 4 waves to own one", p.K, z, ksplit, len);
+  }
   // Lanes of 128 rows and more (the decode groups of the pipelined schedule): a block of 16 output columns re-reads all of its 64
   // activation rows for 24 KB of weights, so the launch is bound by activation reads out of L2 (85 MB for the 1.2 MB QKV matrix
   // at 384 rows); 32 columns per block halve that: pipeline step 678.3 -> 653.8 ms with 2 lanes x 384 rows, 698 -> 683 with

@@ -535,7 +535,8 @@ int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* desc, void* str
  *   CCX_DEC_EPI_SELF_QKV  [3][M][K]: q, then the k and v rows the epilogue appended to a one-position cache (N == 3 K, F == 0)
  *   CCX_DEC_EPI_GELU      [M][N]: the bf16 rows widened, read back through the layout they were written in
  * Checked on the host, CCX_ERR_ARG (1) naming "ccx_dec_ln_linear" and the field: 1 <= M <= 4096; K a multiple of 32 (64 for SELF_QKV)
- * up to 1280; F 0 or a multiple of 32 up to 5120; N a multiple of 4 (32 for GELU) up to 8192; 16-byte alignment and the element
+ * in [128, 1280] but 160, 192 and 288; F 0 or a multiple of 32 up to 5120 -- K, and F where given, must leave no K slice of 1, 2, 3,
+ * 5, 6 or 9 k-steps of 32 columns, in which one of a block's 4 waves would own none (ccx_launch_dec_linear refuses them); N a multiple of 4 (32 for GELU) up to 8192; 16-byte alignment and the element
  * counts.  x f32 [M][K], ln_g / ln_b f32 [K], b1 f32 [F], bias f32 [N] on the device; w1 f32 [F][K] and w f32 [N][K or F] row-major
  * on the HOST.  Owns its scratch; synchronises the stream. */
 #define CCX_DEC_EPI_PARTIAL 0
@@ -551,6 +552,52 @@ typedef struct ccx_dec_ln_linear_desc {
   int64_t x_elems, out_elems;
 } ccx_dec_ln_linear_desc;
 int ccx_dec_ln_linear(ccx_ctx* ctx, const ccx_dec_ln_linear_desc* desc, void* stream);
+
+/* ONE launch of dec_linear_kernel on its own (csrc/decoder.hip; for kernel parity tests; the product path does not call it): the
+ * parameter block filled as the decode step fills it (whisper.hip dec_step: ln_linear, partial_linear) and ccx_launch_dec_linear
+ * unchanged.  act picks the prologue, epi (CCX_DEC_EPI_*) the epilogue; the pairs the launcher has are LN with F32, SELF_QKV and GELU,
+ * COMBINE with PARTIAL, and BF16 with all four.  out[M][N] = act[M][K] W[N][K]^T + bias, W rounded to bf16.
+ *   CCX_DEC_ACT_LN       act = bf16(LayerNorm(x + pend[0] + .. + pend[pend_n - 1])): x f32 [M][K]; pend f32 slabs of [M][K] pend_stride
+ *                        elements apart, added in fp32 one after the other.  Slab 0 is READ ALSO WHEN pend_n == 0 (with weight 0):
+ *                        it must be readable and finite then.  x_out (or NULL) receives the resolved rows, ln_mean_out (or NULL) [M]
+ *                        every row's centring shift: its mean where |mean| exceeds its std, else 0.  ln_g / ln_b f32 [K].
+ *   CCX_DEC_ACT_BF16     act_rows bf16 [M][lda] row-major.
+ *   CCX_DEC_ACT_COMBINE  act = bf16(merge of the split-KV partials part_o f32 [M][K / 64][nsplit][64], part_ml f32 [..][nsplit][2]).
+ * What `out` receives:
+ *   CCX_DEC_EPI_F32       f32 [M][ldo]
+ *   CCX_DEC_EPI_GELU      bf16 [M][ldo]: erf-GELU of the sums
+ *   CCX_DEC_EPI_PARTIAL   f32 [ksplit][M][ldo], the slabs out_stride elements apart; ksplit = ceil(K / 1024), or ceil(K / 1280) where that
+ *                         exceeds 4; slab z sums the k-steps [z per_z, (z + 1) per_z), per_z = ceil(K / 32 / ksplit); the bias is in slab 0
+ *   CCX_DEC_EPI_SELF_QKV  N == 3 K: q f32 [M][K] (the epilogue does not read ldo) and the k / v rows as bf16 into cache_k / cache_v
+ *                         [n_seq][K / 64][cache_T][64] at (row_seq[m] or m, head, pos[m]); pos and row_seq are HOST [M]
+ * Every device buffer is the caller's, in its own type, and nothing else of it is written.  Checked on the host before any launch,
+ * CCX_ERR_ARG (1) naming "ccx_dec_linear_op" and the field: the pair; 1 <= M <= 16 for LN and COMBINE (the product's range), <= 4096
+ * for BF16; K a multiple of 32 (64 for COMBINE and SELF_QKV), <= 1280 for LN and COMBINE, and such that no K slice leaves a wave
+ * without a k-step (a slice of 1, 2, 3, 5, 6 or 9 k-steps of 32 columns: K = 32, 64, 96, 160, 192, 288); at most 4 slabs, and one
+ * unless PARTIAL; N a multiple of 4; ldo >= N (K for SELF_QKV) and a multiple of 4; lda >= K and a multiple of 8; 0 <= pend_n <= 4;
+ * pend_stride >= M K and a multiple of 4; x_out != x; 1 <= nsplit <= 8; out_stride >= M ldo and a multiple of 4; 0 <= pos[m] <
+ * cache_T, 0 <= row_seq[m] < n_seq (M <= n_seq without row_seq), no (sequence, pos) named twice; 16-byte alignment of every device
+ * pointer but ln_mean_out; every extent within its element count (of the buffer's own type).  Owns the packed weights and the two
+ * index arrays only; synchronises the stream. */
+#define CCX_DEC_ACT_LN 0
+#define CCX_DEC_ACT_BF16 1
+#define CCX_DEC_ACT_COMBINE 2
+typedef struct ccx_dec_linear_desc {
+  int act, epi, M, N, K;
+  const float* w_host;                                  /* HOST f32 [N][K] row-major */
+  const void* bias;                                     /* device f32 [N] or NULL */
+  const void* x; const void* pend; int pend_n; int64_t pend_stride; void* x_out;       /* ACT_LN */
+  const void* ln_g; const void* ln_b; float eps; void* ln_mean_out;
+  const void* act_rows; int64_t lda;                    /* ACT_BF16 */
+  const void* part_o; const void* part_ml; int nsplit;  /* ACT_COMBINE */
+  void* out; int64_t ldo; int64_t out_stride;           /* out_stride: PARTIAL only */
+  void* cache_k; void* cache_v; int cache_T, n_seq;     /* SELF_QKV */
+  const int* pos; const int* row_seq;                   /* HOST [M]; row_seq may be NULL (row m is sequence m) */
+  /* elements behind each pointer; ln_elems holds for ln_g and ln_b, cache_elems for cache_k and cache_v */
+  int64_t bias_elems, x_elems, pend_elems, x_out_elems, ln_elems, ln_mean_out_elems, act_elems, part_o_elems, part_ml_elems,
+      out_elems, cache_elems;
+} ccx_dec_linear_desc;
+int ccx_dec_linear_op(ccx_ctx* ctx, const ccx_dec_linear_desc* desc, void* stream);
 
 /* The middle of a decode step's layer on the X-stream path, from the self attention to the cross-attention out projection, on its own
  * (for kernel parity tests): the production launchers unchanged, in the model's order --
