@@ -1,45 +1,23 @@
 // dec_beam.hip -- the beam-search head of a decode step (openai-whisper decoding.py::BeamSearchDecoder.update [UPSTREAM-RECALL], restated
 // in tests/beam_reference.py).  Rows come in windows of `beam` consecutive rows; a step is two launches behind the logits GEMM:
 //
-//  * dec_beam_topk_kernel, one block per row, shaped like dec_select_kernel (decoder.hip): the logit row is loaded once into registers,
-//    the same filter passes and force-timestamp rule run on it, the log-normaliser is formed the same way ((x - max) - log(sum)), and
-//    beam + 1 masked block arg-max rounds out of registers leave the row's best (id, log-probability) pairs.  The filter code is a COPY
-//    of the select kernel's, not shared with it: the select kernel's instantiations keep their text and their bits.
+//  * dec_beam_topk_kernel, one block per row, the select kernel's (dec_select_kernel, decoder.hip) front half with another tail: the
+//    row load, the no-speech softmax and the filter -- suppress mask, timestamp rules, force-timestamp rule, log-normaliser
+//    ((x - max) - log(sum)) -- are the functions of dec_head_row.h that the select kernel calls too, so a rule is changed there, once,
+//    for both (tests/test_dec_head_agreement_gpu.py holds the two kernels to the same bits).  What is written here is the window
+//    prologue and beam + 1 masked block arg-max rounds out of the filtered registers: the row's best (id, log-probability) pairs.
 //  * dec_beam_update_kernel, one block per window: ranks the window's beam x (beam + 1) candidates by cumulative score, walks them
 //    (eot candidates finish, the others become the next live rows until `beam` are taken), and rewrites the window IN PLACE -- read
 //    everything, barrier, write: per-row state, token history, the rows of the self-attention cache indirection, the next step's
 //    embedding, the finished tables.  A captured step graph replays with fixed arguments, so nothing alternates between steps.
 //
 // Tie rule: equal cumulative scores go to the lower source row, then to the lower id (the select kernel's arg-max order).
-#include "decoder.h"
+#include "dec_head_row.h"
 
 namespace {
 
-__device__ __forceinline__ float beam_reduce_max(float v, float* sh) {
-  v = wave_reduce_max(v);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < nw; i++) r = fmaxf(r, sh[i]);
-  return r;
-}
-__device__ __forceinline__ float beam_reduce_sum(float v, float* sh) {
-  v = wave_reduce_sum(v);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  float r = 0.f;
-  for (int i = 0; i < nw; i++) r += sh[i];
-  return r;
-}
-
-#define BEAM_V4 13   // float4 per thread: 1024 threads x 13 x 4 = 53248 ids, as the select kernel
-
 // RULES = false: the decode without ApplyTimestampRules (ccx_decode_options.without_timestamps), an instantiation of its own as in
-// the select kernel -- one allowed set (the call's mask, plus " " and eot on the first sampled step with SuppressBlank on), one softmax.
+// the select kernel (head_filter<false>).
 template <bool RULES>
 __global__ __launch_bounds__(1024) void dec_beam_topk_kernel(DecBeamParams bp) {
   __shared__ float sh[16];
@@ -66,133 +44,31 @@ __global__ __launch_bounds__(1024) void dec_beam_topk_kernel(DecBeamParams bp) {
     return;
   }
 
-  // ---- load the row + mask once (as dec_select_kernel) ----
-  float val[BEAM_V4 * 4];
-  unsigned long long sup = 0;
-#pragma unroll
-  for (int i = 0; i < BEAM_V4; i++) {
-    const int v0 = tid * 4 + i * 4096;
-    if (v0 + 3 < V) {
-      const float4 f = *(const float4*)(lg + v0);
-      const uchar4 m = *(const uchar4*)(p.suppress_mask + v0);
-      val[4 * i] = f.x; val[4 * i + 1] = f.y; val[4 * i + 2] = f.z; val[4 * i + 3] = f.w;
-      sup |= ((unsigned long long)((m.x ? 1 : 0) | (m.y ? 2 : 0) | (m.z ? 4 : 0) | (m.w ? 8 : 0))) << (4 * i);
-    } else {
-      val[4 * i] = val[4 * i + 1] = val[4 * i + 2] = val[4 * i + 3] = -INFINITY;
-      sup |= 0xFull << (4 * i);
-    }
-  }
-  const int tsb = p.timestamp_begin;
-
-  // ---- no-speech probability from the raw logits (first sampled step; the update kernel hands it to every row of the window) ----
+  float val[kHeadV4 * 4];
+  const unsigned long long sup = head_load_row(tid, lg, p.suppress_mask, V, val);
+  // the no-speech probability of the first sampled step: the update kernel hands it to every row of the window
   if (i_gen == 0) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < BEAM_V4 * 4; i++) mx = fmaxf(mx, val[i]);
-    mx = beam_reduce_max(mx, sh);
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < BEAM_V4 * 4; i++) sum += __builtin_amdgcn_exp2f((val[i] - mx) * 1.4426950408889634f);
-    sum = beam_reduce_sum(sum, sh);
-    if (tid == 0) p.state[b].no_speech_prob = expf(lg[p.no_speech] - mx) / sum;
+    const float nsp = head_no_speech(tid, lg, p.no_speech, val, sh);
+    if (tid == 0) p.state[b].no_speech_prob = nsp;
   }
-
-  auto block_argmax = [&](float v_, int idx, float& oval, int& oidx) {
+  const HeadFilter f = head_filter<RULES>(tid, p, s, val, sup, sh, sh_v, sh_i);
+  const float mx_all = f.mx_all, lnorm = f.lnorm;
+  if (f.force_ts) {                          // the summed timestamp mass beats the best text token: timestamps only
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(v_, o, 64);
-      const int oi = __shfl_xor(idx, o, 64);
-      if (ov > v_ || (ov == v_ && oi < idx)) { v_ = ov; idx = oi; }
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) { sh_v[tid >> 6] = v_; sh_i[tid >> 6] = idx; }
-    __syncthreads();
-    oval = sh_v[0]; oidx = sh_i[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); w++)
-      if (sh_v[w] > oval || (sh_v[w] == oval && sh_i[w] < oidx)) { oval = sh_v[w]; oidx = sh_i[w]; }
-  };
-  float mx_all, lnorm;
-  if constexpr (RULES) {
-    // ---- timestamp-rule state folded into two allowed id ranges (as dec_select_kernel) ----
-    const bool last_ts = i_gen >= 1 && s.last_tok >= tsb;
-    const bool pen_ts = i_gen < 2 || s.pen_tok >= tsb;
-    int s_lo = tsb;
-    if (s.last_ts_tok >= 0) s_lo = (last_ts && !pen_ts) ? s.last_ts_tok : s.last_ts_tok + 1;
-    int s_hi = V;
-    if (i_gen == 0 && p.max_initial_ts >= 0) s_hi = tsb + p.max_initial_ts + 1;
-    if (last_ts && pen_ts) s_hi = s_lo;
-    const int t_lo = (i_gen == 0) ? tsb : ((last_ts && !pen_ts) ? p.eot : 0);
-
-    float mx_text = -INFINITY, mx_ts = -INFINITY;
-    int am_text = 0x7fffffff, am_ts = 0x7fffffff;
-#pragma unroll
-    for (int i = 0; i < BEAM_V4 * 4; i++) {
-      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-      const bool is_text = v < tsb;
-      const bool allowed = !((sup >> i) & 1) && (is_text ? (v >= t_lo) : (v >= s_lo && v < s_hi));
-      const float x = allowed ? val[i] : -INFINITY;
-      val[i] = x;
-      const bool bt_ = is_text && x > mx_text, bs_ = !is_text && x > mx_ts;
-      mx_text = bt_ ? x : mx_text; am_text = bt_ ? v : am_text;
-      mx_ts = bs_ ? x : mx_ts; am_ts = bs_ ? v : am_ts;
-    }
-    float bt, bs; int it, is;
-    block_argmax(mx_text, am_text, bt, it);
-    block_argmax(mx_ts, am_ts, bs, is);
-    mx_all = fmaxf(bt, bs);
-
-    float se_text = 0.f, se_ts = 0.f;
-#pragma unroll
-    for (int i = 0; i < BEAM_V4 * 4; i++) {
-      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-      const float e = __builtin_amdgcn_exp2f((val[i] - mx_all) * 1.4426950408889634f);
-      se_text += (v < tsb) ? e : 0.f;
-      se_ts += (v < tsb) ? 0.f : e;
-    }
-    se_text = beam_reduce_sum(se_text, sh);
-    se_ts = beam_reduce_sum(se_ts, sh);
-    const float lse_ts = (se_ts > 0.f) ? mx_all + logf(se_ts) : -INFINITY;
-    const bool force_ts = lse_ts > bt;
-    lnorm = logf(force_ts ? se_ts : se_text + se_ts);
-
-    // ---- the row's top beam + 1: masked block arg-max rounds out of the registers ----
-    if (force_ts) {
-#pragma unroll
-      for (int i = 0; i < BEAM_V4 * 4; i++) {
-        const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-        val[i] = (v < tsb) ? -INFINITY : val[i];
-      }
-    }
-  } else {
-    // ---- no ApplyTimestampRules: the call's mask, and " " / eot on the first sampled step (SuppressBlank) ----
-    const bool ban0 = p.suppress_blank && i_gen == 0;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < BEAM_V4 * 4; i++) {
-      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-      const bool allowed = !((sup >> i) & 1) && !(ban0 && (v == p.blank || v == p.eot));
-      const float x = allowed ? val[i] : -INFINITY;
-      val[i] = x;
-      mx = fmaxf(mx, x);
-    }
-    mx_all = beam_reduce_max(mx, sh);
-    float se = 0.f;
-#pragma unroll
-    for (int i = 0; i < BEAM_V4 * 4; i++) se += __builtin_amdgcn_exp2f((val[i] - mx_all) * 1.4426950408889634f);
-    se = beam_reduce_sum(se, sh);
-    lnorm = logf(se);
+    for (int i = 0; i < kHeadV4 * 4; i++) val[i] = (head_id(tid, i) < p.timestamp_begin) ? -INFINITY : val[i];
   }
+  // ---- the row's top beam + 1: masked block arg-max rounds out of the registers ----
 #pragma unroll 1
   for (int k = 0; k < K; k++) {
     float bv = -INFINITY; int bi = 0x7fffffff;
 #pragma unroll
-    for (int i = 0; i < BEAM_V4 * 4; i++) {
-      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
+    for (int i = 0; i < kHeadV4 * 4; i++) {
+      const int v = head_id(tid, i);
       const bool up = val[i] > bv;            // ids ascend with i: the lowest id of equal values stays
       bv = up ? val[i] : bv; bi = up ? v : bi;
     }
     float ov; int oi;
-    block_argmax(bv, bi, ov, oi);
+    block_argmax(tid, bv, bi, ov, oi, sh_v, sh_i);
     if (tid == 0) {
       const bool some = ov > -INFINITY;
       const int id = some ? oi : -1;
@@ -201,10 +77,7 @@ __global__ __launch_bounds__(1024) void dec_beam_topk_kernel(DecBeamParams bp) {
       if (tr_id) { tr_id[k] = id; tr_lp[k] = lp; }
     }
 #pragma unroll
-    for (int i = 0; i < BEAM_V4 * 4; i++) {
-      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-      val[i] = (v == oi) ? -INFINITY : val[i];
-    }
+    for (int i = 0; i < kHeadV4 * 4; i++) val[i] = (head_id(tid, i) == oi) ? -INFINITY : val[i];
   }
 }
 

@@ -17,6 +17,7 @@
 #include "../../include/ccx.h"
 #include "ccx_common.h"
 #include "decoder.h"
+#include "dec_head_row.h"
 #include "op_scratch.h"
 
 namespace {
@@ -87,7 +88,7 @@ extern "C" int ccx_dec_history_step(ccx_ctx* ctx, const ccx_dec_history_desc* d,
   CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_history_step: desc is NULL");
   const int V = d->n_vocab, R = d->rows, SL = d->sample_len;
   CCX_REQUIRE(ctx, R >= 1 && R <= 65536, "ccx_dec_history_step: rows = %d out of range [1, 65536]", R);
-  CCX_REQUIRE(ctx, V >= 1 && V <= 13 * 4096, "ccx_dec_history_step: n_vocab = %d out of range [1, 53248]", V);
+  CCX_REQUIRE(ctx, V >= 1 && V <= kHeadMaxVocab, "ccx_dec_history_step: n_vocab = %d out of range [1, 53248]", V);
   CCX_REQUIRE(ctx, d->ld >= V && d->ld <= (1 << 24), "ccx_dec_history_step: ld = %ld must be >= n_vocab = %d", (long)d->ld, V);
   CCX_REQUIRE(ctx, d->logits && ((uintptr_t)d->logits & 3) == 0, "ccx_dec_history_step: logits null or not 4-byte aligned");
   CCX_REQUIRE(ctx, (int64_t)(R - 1) * d->ld + V <= d->logits_elems, "ccx_dec_history_step: logits are written up to element %ld, logits_elems = %ld",

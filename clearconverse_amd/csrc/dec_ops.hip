@@ -5,6 +5,7 @@
 #include "../../include/ccx.h"
 #include "ccx_common.h"
 #include "decoder.h"
+#include "dec_head_row.h"
 #include "cross_x.h"
 #include "op_scratch.h"
 
@@ -520,7 +521,7 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_select_step: desc is NULL");
   const int V = d->n_vocab, B = d->B, D = d->D;
   CCX_REQUIRE(ctx, B >= 1 && B <= 65536, "ccx_dec_select_step: B = %d out of range", B);
-  CCX_REQUIRE(ctx, V >= 4 && V % 4 == 0 && V <= 13 * 4096, "ccx_dec_select_step: n_vocab = %d must be a multiple of 4 and <= 53248", V);
+  CCX_REQUIRE(ctx, V >= 4 && V % 4 == 0 && V <= kHeadMaxVocab, "ccx_dec_select_step: n_vocab = %d must be a multiple of 4 and <= 53248", V);
   CCX_REQUIRE(ctx, d->ld >= V && d->ld % 4 == 0, "ccx_dec_select_step: ld = %ld must be >= n_vocab and a multiple of 4", (long)d->ld);
   CCX_REQUIRE(ctx, d->logits && ccx_aligned16(d->logits), "ccx_dec_select_step: logits null or not 16-byte aligned");
   CCX_REQUIRE(ctx, (int64_t)(B - 1) * d->ld + V <= d->logits_elems, "ccx_dec_select_step: logits are read up to element %ld, logits_elems=%ld",
@@ -634,7 +635,7 @@ extern "C" int ccx_dec_beam_step(ccx_ctx* ctx, const ccx_dec_beam_desc* d, void*
   CCX_REQUIRE(ctx, mc >= 1 && mc <= kBeamCandMax, "ccx_dec_beam_step: max_candidates = %d out of range [1, %d]", mc, kBeamCandMax);
   CCX_REQUIRE(ctx, G >= 1 && (int64_t)G * beam <= 65536, "ccx_dec_beam_step: G = %d out of range (G * beam_size <= 65536)", G);
   const int R = G * beam, K = beam + 1;
-  CCX_REQUIRE(ctx, V >= 4 && V % 4 == 0 && V <= 13 * 4096, "ccx_dec_beam_step: n_vocab = %d must be a multiple of 4 and <= 53248", V);
+  CCX_REQUIRE(ctx, V >= 4 && V % 4 == 0 && V <= kHeadMaxVocab, "ccx_dec_beam_step: n_vocab = %d must be a multiple of 4 and <= 53248", V);
   CCX_REQUIRE(ctx, d->ld >= V && d->ld % 4 == 0, "ccx_dec_beam_step: ld = %ld must be >= n_vocab and a multiple of 4", (long)d->ld);
   CCX_REQUIRE(ctx, d->logits && ccx_aligned16(d->logits), "ccx_dec_beam_step: logits null or not 16-byte aligned");
   CCX_REQUIRE(ctx, (int64_t)(R - 1) * d->ld + V <= d->logits_elems, "ccx_dec_beam_step: logits are read up to element %ld, logits_elems=%ld",

@@ -12,12 +12,11 @@
 #include <math.h>
 #include "../../include/ccx.h"
 #include "ccx_common.h"
-#include "decoder.h"
+#include "dec_head_row.h"   // kHeadV4, kHeadMaxVocab: a block holds what the head kernels' blocks hold
 #include "op_scratch.h"
 
 namespace {
 
-#define TP_V4 13   // float4 per thread: 1024 threads x 13 x 4 = 53248 ids
 
 // The row pass both kernels share: one block (1024 threads) reads the ids [lo, hi) of the row `lg` once and leaves them in `val`
 // (everything outside the range as -inf), bit i of `inb` = element i of this thread lies inside the range, and returns the block's
@@ -30,7 +29,7 @@ namespace {
 // every reduction runs out of registers.  fp32 throughout, max-subtracted; -inf inside the range contributes exp2(-inf) = 0.
 // A range whose entries are all -inf gives argmax = lo and NaN probabilities, and a +inf inside the range gives NaN probabilities
 // too (inf - inf), both as torch.softmax does; a NaN inside the range is the caller's to avoid (the model's logits are finite).
-__device__ __forceinline__ void tp_row_pass(const float* lg, int lo, int hi, float (&val)[TP_V4 * 4], unsigned long long& inb_out,
+__device__ __forceinline__ void tp_row_pass(const float* lg, int lo, int hi, float (&val)[kHeadV4 * 4], unsigned long long& inb_out,
                                             float& bmx_out, int& bam_out, float& tot_out) {
   __shared__ float sh_v[16];
   __shared__ int sh_i[16];
@@ -40,7 +39,7 @@ __device__ __forceinline__ void tp_row_pass(const float* lg, int lo, int hi, flo
 
   const int rounds = (hi - base + 4095) >> 12;   // 4096-id rounds of the block that hold an id of the range (1 for the language tokens)
 #pragma unroll
-  for (int i = 0; i < TP_V4; i++) {
+  for (int i = 0; i < kHeadV4; i++) {
     const int v0 = base + tid * 4 + i * 4096;
     // unconditional, at a clamped address (the last float4 that holds an id below hi; hi rounded up to 4 <= ld): straight-line
     // loads that the compiler issues back to back; what a clamped load brings is out of range and dropped by the predicates below
@@ -53,7 +52,7 @@ __device__ __forceinline__ void tp_row_pass(const float* lg, int lo, int hi, flo
   int am = 0x7fffffff;
   unsigned long long inb = 0;   // bit i: element i of this thread lies inside [lo, hi) (52 predicates kept as such would not fit the scalar registers)
 #pragma unroll
-  for (int i = 0; i < TP_V4 * 4; i++) {
+  for (int i = 0; i < kHeadV4 * 4; i++) {
     const int v = base + tid * 4 + (i >> 2) * 4096 + (i & 3);
     const bool in = v >= lo && v < hi;
     const float x = in ? val[i] : -INFINITY;
@@ -78,7 +77,7 @@ __device__ __forceinline__ void tp_row_pass(const float* lg, int lo, int hi, flo
 
   float sum = 0.f;
 #pragma unroll
-  for (int i = 0; i < TP_V4 * 4; i++) sum += __builtin_amdgcn_exp2f((val[i] - bmx) * 1.4426950408889634f);
+  for (int i = 0; i < kHeadV4 * 4; i++) sum += __builtin_amdgcn_exp2f((val[i] - bmx) * 1.4426950408889634f);
   sum = wave_reduce_sum(sum);
   if ((tid & 63) == 0) sh_s[tid >> 6] = sum;
   __syncthreads();
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(1024) void dec_token_probs_kernel(DecTokenProbsPara
   const int row = blockIdx.x, tid = threadIdx.x;
   const float* lg = p.logits + (long)row * p.ld;
   const int base = p.lo & ~3;
-  float val[TP_V4 * 4];
+  float val[kHeadV4 * 4];
   unsigned long long inb;
   float bmx, tot;
   int bam;
@@ -105,7 +104,7 @@ __global__ __launch_bounds__(1024) void dec_token_probs_kernel(DecTokenProbsPara
   if (p.probs) {
     float* pr = p.probs + (long)row * (p.hi - p.lo);
 #pragma unroll
-    for (int i = 0; i < TP_V4 * 4; i++) {
+    for (int i = 0; i < kHeadV4 * 4; i++) {
       const int v = base + tid * 4 + (i >> 2) * 4096 + (i & 3);
       if ((inb >> i) & 1) pr[v - p.lo] = __builtin_amdgcn_exp2f((val[i] - bmx) * 1.4426950408889634f) / tot;
     }
@@ -122,7 +121,7 @@ __global__ __launch_bounds__(1024) void dec_pick_probs_kernel(DecPickProbsParams
   const int pick = p.picks[(long)row * p.pick_stride];
   if (pick < 0 || pick >= p.hi) return;      // block-uniform
   const float* lg = p.logits + (long)row * p.ld;
-  float val[TP_V4 * 4];
+  float val[kHeadV4 * 4];
   unsigned long long inb;
   float bmx, tot;
   int bam;
@@ -135,8 +134,8 @@ __global__ __launch_bounds__(1024) void dec_pick_probs_kernel(DecPickProbsParams
 
 int ccx_launch_dec_token_probs(ccx_ctx* ctx, const DecTokenProbsParams& p, int rows, hipStream_t stream) {
   CCX_REQUIRE(ctx, p.logits && p.argmax && p.pick_prob && rows >= 1, "dec_token_probs: null argument or no rows");
-  CCX_REQUIRE(ctx, p.lo >= 0 && p.lo < p.hi && p.hi <= p.ld && p.ld % 4 == 0 && p.hi - (p.lo & ~3) <= TP_V4 * 4096,
-              "dec_token_probs: range [%d, %d) does not fit ld = %ld or the %d ids a block holds", p.lo, p.hi, p.ld, TP_V4 * 4096);
+  CCX_REQUIRE(ctx, p.lo >= 0 && p.lo < p.hi && p.hi <= p.ld && p.ld % 4 == 0 && p.hi - (p.lo & ~3) <= kHeadMaxVocab,
+              "dec_token_probs: range [%d, %d) does not fit ld = %ld or the %d ids a block holds", p.lo, p.hi, p.ld, kHeadMaxVocab);
   CCX_REQUIRE(ctx, p.pick >= p.lo && p.pick < p.hi, "dec_token_probs: pick = %d outside [%d, %d)", p.pick, p.lo, p.hi);
   CCX_REQUIRE(ctx, ((uintptr_t)p.logits & 15) == 0, "dec_token_probs: logits must be 16-byte aligned");
   const double n = (double)rows * (p.hi - p.lo);
@@ -148,8 +147,8 @@ int ccx_launch_dec_token_probs(ccx_ctx* ctx, const DecTokenProbsParams& p, int r
 
 int ccx_launch_dec_pick_probs(ccx_ctx* ctx, const DecPickProbsParams& p, int rows, hipStream_t stream) {
   CCX_REQUIRE(ctx, p.logits && p.picks && p.out && rows >= 1, "dec_pick_probs: null argument or no rows");
-  CCX_REQUIRE(ctx, p.hi >= 1 && p.hi <= p.ld && p.ld % 4 == 0 && p.hi <= TP_V4 * 4096,
-              "dec_pick_probs: range [0, %d) does not fit ld = %ld or the %d ids a block holds", p.hi, p.ld, TP_V4 * 4096);
+  CCX_REQUIRE(ctx, p.hi >= 1 && p.hi <= p.ld && p.ld % 4 == 0 && p.hi <= kHeadMaxVocab,
+              "dec_pick_probs: range [0, %d) does not fit ld = %ld or the %d ids a block holds", p.hi, p.ld, kHeadMaxVocab);
   CCX_REQUIRE(ctx, p.pick_stride >= 1 && p.out_stride >= 1, "dec_pick_probs: pick_stride = %ld, out_stride = %ld must be >= 1", p.pick_stride, p.out_stride);
   CCX_REQUIRE(ctx, ((uintptr_t)p.logits & 15) == 0, "dec_pick_probs: logits must be 16-byte aligned");
   ccx_prof_scope ps(ctx, stream, "dec_pick_probs_kernel", 0.0, (double)rows * p.hi * 4.0 + rows * 8.0);
@@ -164,7 +163,7 @@ extern "C" int ccx_dec_token_probs(ccx_ctx* ctx, const ccx_dec_token_probs_desc*
   CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_token_probs: desc is NULL");
   const int V = d->n_vocab, rows = d->rows;
   CCX_REQUIRE(ctx, rows >= 1 && rows <= 65536, "ccx_dec_token_probs: rows = %d out of range [1, 65536]", rows);
-  CCX_REQUIRE(ctx, V >= 1 && V <= TP_V4 * 4096, "ccx_dec_token_probs: n_vocab = %d out of range [1, %d]", V, TP_V4 * 4096);
+  CCX_REQUIRE(ctx, V >= 1 && V <= kHeadMaxVocab, "ccx_dec_token_probs: n_vocab = %d out of range [1, %d]", V, kHeadMaxVocab);
   CCX_REQUIRE(ctx, d->ld >= V && d->ld % 4 == 0 && d->ld <= (1 << 24), "ccx_dec_token_probs: ld = %ld must be >= n_vocab = %d and a multiple of 4", (long)d->ld, V);
   CCX_REQUIRE(ctx, d->lo >= 0 && d->lo < d->hi, "ccx_dec_token_probs: lo = %d, hi = %d is not a range", d->lo, d->hi);
   CCX_REQUIRE(ctx, d->hi <= V, "ccx_dec_token_probs: hi = %d behind n_vocab = %d", d->hi, V);
@@ -202,7 +201,7 @@ extern "C" int ccx_dec_pick_probs(ccx_ctx* ctx, const ccx_dec_pick_probs_desc* d
   CCX_REQUIRE(ctx, d != nullptr, "ccx_dec_pick_probs: desc is NULL");
   const int rows = d->rows, hi = d->hi;
   CCX_REQUIRE(ctx, rows >= 1 && rows <= 65536, "ccx_dec_pick_probs: rows = %d out of range [1, 65536]", rows);
-  CCX_REQUIRE(ctx, hi >= 1 && hi <= TP_V4 * 4096, "ccx_dec_pick_probs: hi = %d out of range [1, %d]", hi, TP_V4 * 4096);
+  CCX_REQUIRE(ctx, hi >= 1 && hi <= kHeadMaxVocab, "ccx_dec_pick_probs: hi = %d out of range [1, %d]", hi, kHeadMaxVocab);
   CCX_REQUIRE(ctx, d->ld >= hi && d->ld % 4 == 0 && d->ld <= (1 << 24), "ccx_dec_pick_probs: ld = %ld must be >= hi = %d and a multiple of 4", (long)d->ld, hi);
   CCX_REQUIRE(ctx, d->logits && ccx_aligned16(d->logits), "ccx_dec_pick_probs: logits null or not 16-byte aligned");
   // the last float4 a row loads ends at hi rounded up to 4

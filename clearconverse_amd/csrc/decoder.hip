@@ -1273,31 +1273,13 @@ int ccx_launch_dec_attention(ccx_ctx* ctx, const DecAttnParams& p, int B, int ns
 // ------------------------------------------------------------------------------------------
 // Logit filters + greedy selection + per-sequence state machine
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_reduce_max(float v, float* sh) {
-  v = wave_reduce_max(v);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < nw; i++) r = fmaxf(r, sh[i]);
-  return r;
-}
-__device__ __forceinline__ float block_reduce_sum(float v, float* sh) {
-  v = wave_reduce_sum(v);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  float r = 0.f;
-  for (int i = 0; i < nw; i++) r += sh[i];
-  return r;
-}
-
 // One block (1024 threads) per sequence.  The whole logit row (<= 53248 values) is loaded ONCE
 // into registers (13 float4 per thread, all loads issued before any use) together with the
-// suppress mask; every reduction then runs out of registers.  The kernel also writes the input
-// embedding of the NEXT step (token + position), so the step chain needs no separate embed launch.
+// suppress mask; every reduction then runs out of registers.  The row load, the no-speech softmax and the
+// filter (SuppressBlank / SuppressTokens / ApplyTimestampRules, the force-timestamp rule, the log-normaliser)
+// are dec_head_row.h's, shared with dec_beam_topk_kernel (dec_beam.hip); what is written here is the prompt
+// phase, the draw, the truncation, the per-sequence state machine and the input embedding of the NEXT step
+// (token + position), so the step chain needs no separate embed launch.
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, so every (seed, sequence, step, vocabulary quad) has its own
 // four 32-bit draws regardless of launch geometry.  oracle/whisper_ref.py::philox4x32 is the same function in numpy.
 __device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
@@ -1315,7 +1297,7 @@ __device__ __forceinline__ float gumbel_from_u32(unsigned x) {
   return -logf(-logf(u));
 }
 
-#define SEL_V4 13
+#include "dec_head_row.h"
 #include "dec_truncate.h"
 // SAMPLE = false is the greedy kernel (no noise code, no extra registers: the sampling branch costs the 1024-thread
 // block its register budget and spills); SAMPLE = true adds the temperature > 0 draw.
@@ -1368,130 +1350,20 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
     return;
   }
 
-  // ---- load the row + mask once ----
-  float val[SEL_V4 * 4];
-  unsigned long long sup = 0;  // bit i: element i of this thread is suppressed / out of range
-#pragma unroll
-  for (int i = 0; i < SEL_V4; i++) {
-    const int v0 = tid * 4 + i * 4096;
-    if (v0 + 3 < V) {
-      const float4 f = *(const float4*)(lg + v0);
-      const uchar4 m = *(const uchar4*)(p.suppress_mask + v0);
-      val[4 * i] = f.x; val[4 * i + 1] = f.y; val[4 * i + 2] = f.z; val[4 * i + 3] = f.w;
-      sup |= ((unsigned long long)((m.x ? 1 : 0) | (m.y ? 2 : 0) | (m.z ? 4 : 0) | (m.w ? 8 : 0))) << (4 * i);
-    } else {  // n_vocab % 4 == 0 (checked on the host): a float4 is either fully inside or fully outside
-      val[4 * i] = val[4 * i + 1] = val[4 * i + 2] = val[4 * i + 3] = -INFINITY;
-      sup |= 0xFull << (4 * i);
-    }
-  }
+  // ---- the shared head (dec_head_row.h): row + mask into registers, no-speech probability, filter ----
+  float val[kHeadV4 * 4];
+  const unsigned long long sup = head_load_row(tid, lg, p.suppress_mask, V, val);
   const int i_gen = s.n_gen;
   const int tsb = p.timestamp_begin;
-
-  // ---- no-speech probability from the raw logits at the SOT position (first sampling step) ----
   if (i_gen == 0) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < SEL_V4 * 4; i++) mx = fmaxf(mx, val[i]);
-    mx = block_reduce_max(mx, sh);
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < SEL_V4 * 4; i++) sum += __builtin_amdgcn_exp2f((val[i] - mx) * 1.4426950408889634f);  // -inf -> 0
-    sum = block_reduce_sum(sum, sh);
-    if (tid == 0) s.no_speech_prob = expf(lg[p.no_speech] - mx) / sum;
+    const float nsp = head_no_speech(tid, lg, p.no_speech, val, sh);
+    if (tid == 0) s.no_speech_prob = nsp;
   }
-
-  // block argmax (ties -> lowest index, as torch.argmax on CPU)
-  auto block_argmax = [&](float v_, int idx, float& oval, int& oidx) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(v_, o, 64);
-      const int oi = __shfl_xor(idx, o, 64);
-      if (ov > v_ || (ov == v_ && oi < idx)) { v_ = ov; idx = oi; }
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) { sh_v[tid >> 6] = v_; sh_i[tid >> 6] = idx; }
-    __syncthreads();
-    oval = sh_v[0]; oidx = sh_i[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); w++)
-      if (sh_v[w] > oval || (sh_v[w] == oval && sh_i[w] < oidx)) { oval = sh_v[w]; oidx = sh_i[w]; }
-  };
-  float bt, bs, mx_all, lnorm; int it, is; bool force_ts;
-  if constexpr (RULES) {
-    // ---- timestamp-rule state (ApplyTimestampRules) folded into two allowed id ranges ----
-    // text ids   [t_lo, tsb):  empty on the first step (must start with a timestamp); only >= eot after
-    //                          "text, timestamp" (a timestamp must be paired or followed by eot)
-    // timestamps [s_lo, s_hi): >= the last timestamp (+1 unless it is still unpaired); empty after a
-    //                          closed pair "timestamp, timestamp"; <= max_initial_timestamp on the first step
-    // SuppressBlank only matters on the first step, where every text id is banned anyway.
-    const bool last_ts = i_gen >= 1 && s.last_tok >= tsb;
-    const bool pen_ts = i_gen < 2 || s.pen_tok >= tsb;
-    int s_lo = tsb;
-    if (s.last_ts_tok >= 0) s_lo = (last_ts && !pen_ts) ? s.last_ts_tok : s.last_ts_tok + 1;
-    int s_hi = V;
-    if (i_gen == 0 && p.max_initial_ts >= 0) s_hi = tsb + p.max_initial_ts + 1;
-    if (last_ts && pen_ts) s_hi = s_lo;
-    const int t_lo = (i_gen == 0) ? tsb : ((last_ts && !pen_ts) ? p.eot : 0);
-
-    // pass 1 (registers): apply the filters in place (-inf) and take text / timestamp maxima
-    float mx_text = -INFINITY, mx_ts = -INFINITY;
-    int am_text = 0x7fffffff, am_ts = 0x7fffffff;
-#pragma unroll
-    for (int i = 0; i < SEL_V4 * 4; i++) {
-      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-      const bool is_text = v < tsb;
-      const bool allowed = !((sup >> i) & 1) && (is_text ? (v >= t_lo) : (v >= s_lo && v < s_hi));
-      const float x = allowed ? val[i] : -INFINITY;
-      val[i] = x;
-      const bool bt_ = is_text && x > mx_text, bs_ = !is_text && x > mx_ts;
-      mx_text = bt_ ? x : mx_text; am_text = bt_ ? v : am_text;
-      mx_ts = bs_ ? x : mx_ts; am_ts = bs_ ? v : am_ts;
-    }
-    block_argmax(mx_text, am_text, bt, it);
-    block_argmax(mx_ts, am_ts, bs, is);
-    mx_all = fmaxf(bt, bs);
-
-    // pass 2 (registers): sum exp over text and over timestamps (relative to mx_all)
-    float se_text = 0.f, se_ts = 0.f;
-#pragma unroll
-    for (int i = 0; i < SEL_V4 * 4; i++) {
-      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-      const float e = __builtin_amdgcn_exp2f((val[i] - mx_all) * 1.4426950408889634f);  // banned entries are -inf -> 0
-      se_text += (v < tsb) ? e : 0.f;
-      se_ts += (v < tsb) ? 0.f : e;
-    }
-    se_text = block_reduce_sum(se_text, sh);
-    se_ts = block_reduce_sum(se_ts, sh);
-
-    // timestamp_logprob > max_text_token_logprob  <=>  lse_ts > max_text (same normaliser)
-    const float lse_ts = (se_ts > 0.f) ? mx_all + logf(se_ts) : -INFINITY;
-    force_ts = lse_ts > bt;
-    // log-normaliser of the re-filtered logits, kept relative to mx_all: the log-probability is (x - mx_all) - lnorm, two numbers of
-    // the softmax's own magnitude, so that a common offset of the logits does not cost it the offset's ulp
-    lnorm = logf(force_ts ? se_ts : se_text + se_ts);
-  } else {
-    // ---- no ApplyTimestampRules (without_timestamps): one allowed set, one argmax, one softmax ----
-    // allowed: not suppressed by the call's mask, and on the first sampled step, with SuppressBlank on, neither " " nor eot.
-    // Timestamp ids and <|notimestamps|> are ids like any other here.
-    const bool ban0 = p.suppress_blank && i_gen == 0;
-    float mx = -INFINITY; int am = 0x7fffffff;
-#pragma unroll
-    for (int i = 0; i < SEL_V4 * 4; i++) {
-      const int v = tid * 4 + (i >> 2) * 4096 + (i & 3);
-      const bool allowed = !((sup >> i) & 1) && !(ban0 && (v == p.blank || v == p.eot));
-      const float x = allowed ? val[i] : -INFINITY;
-      val[i] = x;
-      const bool b_ = x > mx;            // ids ascend with i: the lowest id of equal values stays
-      mx = b_ ? x : mx; am = b_ ? v : am;
-    }
-    block_argmax(mx, am, bt, it);
-    bs = -INFINITY; is = 0x7fffffff; force_ts = false;
-    mx_all = bt;
-    float se = 0.f;
-#pragma unroll
-    for (int i = 0; i < SEL_V4 * 4; i++) se += __builtin_amdgcn_exp2f((val[i] - mx_all) * 1.4426950408889634f);   // banned: -inf -> 0
-    se = block_reduce_sum(se, sh);
-    lnorm = logf(se);                    // relative to mx_all, as the ruled kernel keeps it
-  }
+  const HeadFilter f = head_filter<RULES>(tid, p, s, val, sup, sh, sh_v, sh_i);
+  // without the rules there is no timestamp side: stated here as constants, so that the tail below folds as it always did
+  const float bt = f.bt, bs = RULES ? f.bs : -INFINITY, mx_all = f.mx_all, lnorm = f.lnorm;
+  const int it = f.it, is = RULES ? f.is : 0x7fffffff;
+  const bool force_ts = RULES && f.force_ts;
 
   // ---- temperature > 0: Categorical(logits / T) by the Gumbel-max trick (argmax of logits / T + Gumbel noise) ----
   const float temperature = SAMPLE ? __uint_as_float(p.sample_cfg[0]) : 0.f;
@@ -1509,7 +1381,7 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
       const float m_row = force_ts ? bs : mx_all;
       if (force_ts) {
 #pragma unroll
-        for (int i = 0; i < SEL_V4 * 4; i++) val[i] = (tid * 4 + (i >> 2) * 4096 + (i & 3) < tsb) ? -INFINITY : val[i];
+        for (int i = 0; i < kHeadV4 * 4; i++) val[i] = (head_id(tid, i) < tsb) ? -INFINITY : val[i];
       }
       if (m_row > -INFINITY)      // a row with nothing allowed: as without truncation
         cut = dec_trunc::row_cut(val, m_row, temperature, (int)p.sample_cfg[3], __uint_as_float(p.sample_cfg[4]), __uint_as_float(p.sample_cfg[5]),
@@ -1518,7 +1390,7 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
     }
     float best = -INFINITY, best_logit = -INFINITY; int best_i = 0x7fffffff;
 #pragma unroll
-    for (int i = 0; i < SEL_V4; i++) {
+    for (int i = 0; i < kHeadV4; i++) {
       const int v0 = tid * 4 + i * 4096;
       const uint4 r = philox4x32_10(make_uint4((unsigned)(v0 >> 2), sid, (unsigned)i_gen, 0u), key);
       const unsigned rr[4] = {r.x, r.y, r.z, r.w};
@@ -1532,7 +1404,7 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
       }
     }
     float ov; int oi;
-    block_argmax(best, best_i, ov, oi);
+    block_argmax(tid, best, best_i, ov, oi, sh_v, sh_i);
     samp = oi;
     __syncthreads();
     if (best_i == samp && best == ov) sh[0] = best_logit;         // exactly one thread owns the winner

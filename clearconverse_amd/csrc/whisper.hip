@@ -18,6 +18,7 @@
 #include "ccx_common.h"
 #include "cross_x.h"
 #include "decoder.h"
+#include "dec_head_row.h"
 #include "elementwise.h"
 #include "gemm_bf16.h"
 #include "logmel.h"
@@ -334,7 +335,7 @@ int ccx_whisper_create(ccx_ctx* ctx, const ccx_whisper_dims* dims, int max_batch
   CCX_REQUIRE(ctx, d.n_mels == 80 || d.n_mels == 128, "whisper: n_mels must be 80 or 128 (got %d)", d.n_mels);
   CCX_REQUIRE(ctx, d.n_audio_layer >= 1 && d.n_text_layer >= 1, "whisper: n_audio_layer = %d and n_text_layer = %d must be at least 1", d.n_audio_layer, d.n_text_layer);
   CCX_REQUIRE(ctx, d.n_audio_ctx % 4 == 0, "whisper: n_audio_ctx must be a multiple of 4");
-  CCX_REQUIRE(ctx, d.n_vocab >= 4 && d.n_vocab <= 13 * 4096, "whisper: n_vocab = %d out of range [4, 53248]", d.n_vocab);
+  CCX_REQUIRE(ctx, d.n_vocab >= 4 && d.n_vocab <= kHeadMaxVocab, "whisper: n_vocab = %d out of range [4, 53248]", d.n_vocab);
   ccx_whisper* w = new ccx_whisper();
   w->ctx = ctx;
   w->store.ctx = ctx;
