@@ -348,16 +348,21 @@ PROTOTYPES = {
     "ccx_row_variance": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp]),
     "ccx_cross_attention_xa": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ccx_cross_attention_xa_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ccx_cross_attention_xa_keys": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ccx_cross_attention_xa_fp8_keys": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ccx_cosine_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "ccx_speaker_profiles": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ccx_resample_sinc": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i, _vp]),
     "ccx_enc_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ccx_enc_attention_keys": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ccx_whisper_create": (_i, [_vp, C.POINTER(WhisperDims), _i, C.POINTER(_vp)]),
     "ccx_whisper_destroy": (None, [_vp]),
     "ccx_whisper_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i, _i, _i64p]),
     "ccx_whisper_set_max_audio": (_i, [_vp, C.c_double]),
     "ccx_whisper_set_cross_fp8": (_i, [_vp, _i]),
     "ccx_whisper_cross_fp8": (_i, [_vp]),
+    "ccx_whisper_set_audio_ctx": (_i, [_vp, _i]),
+    "ccx_whisper_audio_ctx": (_i, [_vp]),
     "ccx_whisper_share_encoder_scratch": (_i, [_vp, _vp]),
     "ccx_whisper_finalize": (_i, [_vp]),
     "ccx_whisper_set_rules": (_i, [_vp, C.POINTER(DecodeRules)]),
@@ -379,6 +384,7 @@ PROTOTYPES = {
     "ccx_whisper_sampling_graph_count": (_i, [_vp]),
     "ccx_whisper_set_mel": (_i, [_vp, _vp, _i, _vp]),
     "ccx_whisper_encode": (_i, [_vp, _i, _vp, _vp]),
+    "ccx_whisper_encode_ctx": (_i, [_vp, _i, _vp, _vp, _vp]),
     "ccx_whisper_decoder_logits": (_i, [_vp, _i32p, _i, _i, _vp, _vp]),
     "ccx_whisper_decode_greedy": (_i, [_vp, _i32p, _i32p, _i, _i, _i, _i32p, _i32p, _fp, _fp, _vp]),
     "ccx_dec_attention_desc": (_i, [_vp, _i, C.POINTER(DecAttnDesc), _vp]),

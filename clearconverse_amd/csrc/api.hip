@@ -196,4 +196,21 @@ int ccx_enc_attention(ccx_ctx* ctx, const void* q, const void* k, const void* vt
                                   (hipStream_t)stream);
 }
 
+int ccx_enc_attention_keys(ccx_ctx* ctx, const void* q, const void* k, const void* vt, void* o, int B, int H, int S, int Spad,
+                           const int* n_keys_host, void* stream) {
+  if (!ctx) return CCX_ERR_ARG;
+  CCX_REQUIRE(ctx, n_keys_host && B > 0, "enc_attention_keys: n_keys_host is null or the batch is empty");
+  for (int b = 0; b < B; b++)
+    CCX_REQUIRE(ctx, n_keys_host[b] >= 1 && n_keys_host[b] <= S, "enc_attention_keys: n_keys[%d]=%d outside [1, %d]", b, n_keys_host[b], S);
+  int* d_n = nullptr;
+  CCX_HIP(ctx, hipMalloc(&d_n, (size_t)B * sizeof(int)));
+  hipError_t e = hipMemcpyAsync(d_n, n_keys_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream);
+  int rc = e == hipSuccess ? ccx_launch_enc_attention(ctx, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)o, B, H, S, Spad,
+                                                      (hipStream_t)stream, d_n)
+                           : ccx_fail(ctx, CCX_ERR_HIP, "enc_attention_keys: copy of the counts failed: %s", hipGetErrorString(e));
+  hipStreamSynchronize((hipStream_t)stream);     // the counts are freed below
+  hipFree(d_n);
+  return rc;
+}
+
 }  // extern "C"

@@ -22,7 +22,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 
 __global__ __launch_bounds__(256, 2) void enc_attention_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kc, const bf16_t* __restrict__ Vt,
-    bf16_t* __restrict__ O, int S, int Spad, int n_head, float scale_log2e, int n_qt) {
+    bf16_t* __restrict__ O, int S, int Spad, int n_head, float scale_log2e, int n_qt, const int* __restrict__ n_keys) {
   __shared__ __attribute__((aligned(16))) char smem[2 * ATT_STAGE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // XCD-aware block order (xcd_remap): every XCD gets a contiguous run of logical tiles, so the n_qt query tiles of one
@@ -32,6 +32,20 @@ __global__ __launch_bounds__(256, 2) void enc_attention_kernel(
   const int bh = wg / n_qt;
   const int q0 = (wg - bh * n_qt) * 128 + wave * 32;
   const int l31 = lane & 31, hh = lane >> 5;
+  // keys of this block's sequence: n_keys[b] (reduced audio context: the sequence attends over its first Sk positions only), else S.
+  // Block-uniform, so it lives in a scalar register; the key loop and the TAIL mask below run on it.
+  const int Sk = n_keys ? n_keys[bh / n_head] : S;
+  if (q0 - wave * 32 >= Sk) {
+    // a query tile wholly at or beyond the sequence's keys: no attention work, its rows of O are zeros
+    const int q = q0 + l31;
+    if (q < S) {
+      const int b = bh / n_head, h = bh - b * n_head;
+      uint2* dst = (uint2*)(O + ((long)(b * S + q) * n_head + h) * 64 + 32 * hh);
+#pragma unroll
+      for (int i = 0; i < 8; i++) dst[i] = make_uint2(0u, 0u);
+    }
+    return;
+  }
 
   const bf16_t* Qb = Q + (long)bh * Spad * 64;
   const bf16_t* Kb = Kc + (long)bh * Spad * 64;
@@ -81,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void enc_attention_kernel(
   for (int i = 0; i < 16; i++) { oT[0][i] = 0.f; oT[1][i] = 0.f; }
   float m_run = -1e30f, l_run = 0.f;
 
-  const int nT = (S + 63) >> 6;
+  const int nT = (Sk + 63) >> 6;
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   // One K/V tile.  TAIL (only the last tile can be ragged) is a compile-time tag: the key-range masking costs two VALU
   // slots per score when it sits in the common path.
@@ -112,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void enc_attention_kernel(
       for (int r = 0; r < 16; r++) {
         if (TAIL) {
           const int key = t * 64 + kt * 32 + 16 * (r >> 3) + 8 * hh + (r & 7);
-          if (key >= S) sT[kt][r] = -INFINITY;
+          if (key >= Sk) sT[kt][r] = -INFINITY;
         }
         mx = fmaxf(mx, sT[kt][r]);
       }
@@ -162,12 +176,13 @@ __global__ __launch_bounds__(256, 2) void enc_attention_kernel(
   stage(0, 0);
   __syncthreads();
   for (int t = 0; t < nT - 1; t++) tile(t, std::false_type{});
-  if ((S & 63) != 0) tile(nT - 1, std::true_type{});
+  if ((Sk & 63) != 0) tile(nT - 1, std::true_type{});
   else tile(nT - 1, std::false_type{});
 
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l_tot;
   const int q = q0 + l31;
+  const bool keep = q < Sk;                            // rows at or beyond the sequence's keys (never read as keys): zeros
   if (q < S) {
     const int b = bh / n_head, h = bh - b * n_head;
     bf16_t* dst = O + ((long)(b * S + q) * n_head + h) * 64;
@@ -179,13 +194,14 @@ __global__ __launch_bounds__(256, 2) void enc_attention_kernel(
         uint2 v;
         v.x = pack_bf16x2(oT[dt][4 * g + 0] * inv, oT[dt][4 * g + 1] * inv);
         v.y = pack_bf16x2(oT[dt][4 * g + 2] * inv, oT[dt][4 * g + 3] * inv);
+        if (!keep) v = make_uint2(0u, 0u);
         *(uint2*)(dst + dt * 32 + 8 * g + 4 * hh) = v;
       }
   }
 }
 
 int ccx_launch_enc_attention(ccx_ctx* ctx, const bf16_t* Q, const bf16_t* K, const bf16_t* Vt, bf16_t* O,
-                             int B, int n_head, int S, int Spad, hipStream_t stream) {
+                             int B, int n_head, int S, int Spad, hipStream_t stream, const int* n_keys_dev) {
   CCX_REQUIRE(ctx, B > 0 && n_head > 0 && S > 0, "enc_attention: empty problem");
   CCX_REQUIRE(ctx, Spad % 64 == 0 && Spad >= S, "enc_attention: Spad=%d must be a multiple of 64 and >= S=%d", Spad, S);
   const float scale_log2e = 0.125f * 1.4426950408889634f;  // head_dim 64: (64^-0.25)^2 = 1/8
@@ -194,7 +210,7 @@ int ccx_launch_enc_attention(ccx_ctx* ctx, const bf16_t* Q, const bf16_t* K, con
   {
     const double bh = (double)B * n_head;
     ccx_prof_scope ps(ctx, stream, "enc_attention_kernel", 4.0 * bh * S * (double)S * 64, 2.0 * bh * S * 64 * 4);
-    hipLaunchKernelGGL(enc_attention_kernel, grid, dim3(256), 0, stream, Q, K, Vt, O, S, Spad, n_head, scale_log2e, n_qt);
+    hipLaunchKernelGGL(enc_attention_kernel, grid, dim3(256), 0, stream, Q, K, Vt, O, S, Spad, n_head, scale_log2e, n_qt, n_keys_dev);
   }
   CCX_CHECK_LAUNCH(ctx);
   return CCX_OK;

@@ -37,6 +37,9 @@ struct XsParams {
   const unsigned char* X8;
   long x8_seq_stride;    // bytes between sequences
   const int* row_seq;    // row -> sequence (prompt prefill: several rows per sequence); null: identity
+  const int* seq_S;      // device, indexed by sequence exactly as X / X8 are (after row_seq, relative to the same base): the keys of that
+                         // sequence, each in [1, S] (reduced audio context: the stream stops after them); null: S for every sequence.
+                         // Rows of X between a sequence's count and the end of its last 16-key tile must be finite (their p is 0).
   int rows_per_seq;      // > 1: rows s * rows_per_seq .. + rows_per_seq - 1 all belong to sequence row_seq[s * rows_per_seq] (prefill)
   const bf16_t* Wv;      // cross_attn.value.weight [D][D] as its fragment image
   const float* bv;       // [D]

@@ -450,7 +450,9 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
   }
   const int seq = p.row_seq ? p.row_seq[row0] : row0;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
-  const int H = p.H, S = p.S;
+  // keys of this block's sequence: p.seq_S[seq] (reduced audio context) or p.S -- block-uniform, a scalar; everything below that says
+  // S (the tile count, the two key halves, the clamp of the last tile's loads, the p = 0 rule) means this sequence's count
+  const int H = p.H, S = p.seq_S ? p.seq_S[seq] : p.S;
   char* strip = xs_smem + wave * (G::NSTRIP * STRIP);
   char* sbuf = xs_smem + G::S_OFF;
 
@@ -462,7 +464,8 @@ __global__ __launch_bounds__(256, RB == 1 ? 2 : 1) void dec_xs_stream_kernel(XsP
   const int T0 = NTall * sp / XS_SPLIT, NT = NTall * (sp + 1) / XS_SPLIT;      // this block's key tiles [T0, NT)
 
   // FP8: tile t of the sequence's image, this wave's quarter; lane l reads its scales at 8 (l / 4), its codes at 16 l (8 l in the
-  // odd last block).  Every key of the last tile is there (copies of key S - 1, as the bf16 forms re-read it): no clamp
+  // odd last block).  Every key of the last tile is there (copies of key p.S - 1, as the bf16 forms re-read it; under p.seq_S the
+  // sequence's own last tile holds the rows that follow its count, finite, whose p is 0): no clamp
   const unsigned char* X8p = FP8 ? p.X8 + (long)seq * p.x8_seq_stride + wave * xa_fp8_quarter_bytes(D) : nullptr;
   XsFp8Img<NKS> img8[FP8 ? PF : 1];
   auto load_tile8 = [&](XsFp8Img<NKS>& X, int t) {
@@ -771,7 +774,7 @@ bool ccx_xs_supported(int D, int H) { return H >= 1 && H <= 16 && H * 64 == D &&
 
 int ccx_launch_xs_cross_attention(ccx_ctx* ctx, const XsParams& p, hipStream_t stream) {
   CCX_REQUIRE(ctx, ccx_xs_supported(p.D, p.H), "xs cross attention: width %d with %d heads is not instantiated", p.D, p.H);
-  CCX_REQUIRE(ctx, p.rows >= 1 && p.S >= 16 && (p.q || p.x || p.xb) && p.WkT && p.xq && p.X && p.Wv && p.bv && p.out, "xs cross attention: bad arguments");
+  CCX_REQUIRE(ctx, p.rows >= 1 && p.S >= 1 && (p.q || p.x || p.xb) && p.WkT && p.xq && p.X && p.Wv && p.bv && p.out, "xs cross attention: bad arguments");
   CCX_REQUIRE(ctx, !p.xb || (p.ln_stats && p.ln_s && p.Wq && p.bq), "xs cross attention: bad LayerNorm-free query arguments");
   CCX_REQUIRE(ctx, !p.x || (p.pend && p.ln_g && p.ln_b && p.Wq && p.bq && p.pend_n >= 0 && p.pend_n <= 4 && p.x_out != p.x), "xs cross attention: bad fused-query arguments");
   CCX_REQUIRE(ctx, p.part_o && p.part_ml, "xs cross attention: partial buffers missing");
@@ -930,10 +933,10 @@ __global__ void xs_bf16_to_f32_kernel(const bf16_t* __restrict__ in, float* __re
 // fp8: the FP8 stream on an image quantised here from a copy of xa_dev; xhat_out_dev then receives the image's read-back
 static int cross_attention_xa_impl(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
                                    const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head, int n_ctx,
-                                   float* out_dev, bool fp8, uint16_t* xhat_out_dev, hipStream_t stream) {
+                                   float* out_dev, bool fp8, uint16_t* xhat_out_dev, const int* n_keys_host, hipStream_t stream) {
   const int H = n_head, D = 64 * n_head, S = n_ctx;
   CCX_REQUIRE(ctx, ccx_xs_supported(D, H), "cross_attention_xa: %d heads (width %d) not instantiated", H, D);
-  CCX_REQUIRE(ctx, q_dev && wk_host && wv_host && bv_host && xa_dev && out_dev && rows >= 1 && n_seq >= 1 && S >= 16, "cross_attention_xa: bad arguments");
+  CCX_REQUIRE(ctx, q_dev && wk_host && wv_host && bv_host && xa_dev && out_dev && rows >= 1 && n_seq >= 1 && S >= 1, "cross_attention_xa: bad arguments");
   if (row_seq_host)
     for (int i = 0; i < rows; i++) CCX_REQUIRE(ctx, row_seq_host[i] >= 0 && row_seq_host[i] < n_seq, "cross_attention_xa: row_seq[%d] out of range", i);
   else CCX_REQUIRE(ctx, rows <= n_seq, "cross_attention_xa: more rows than sequences without a row map");
@@ -942,14 +945,17 @@ static int cross_attention_xa_impl(ccx_ctx* ctx, const float* q_dev, const float
     for (int i = 0; i < rows; i++)
       CCX_REQUIRE(ctx, row_seq_host[i] == row_seq_host[i - i % rows_per_seq], "cross_attention_xa: row %d is not in its group's sequence", i);
   }
+  if (n_keys_host)
+    for (int i = 0; i < n_seq; i++)
+      CCX_REQUIRE(ctx, n_keys_host[i] >= 1 && n_keys_host[i] <= S, "cross_attention_xa: n_keys[%d]=%d outside [1, %d]", i, n_keys_host[i], S);
   // the weights as the model stores them: fragment images (cross_x.h)
   const std::vector<float> wkt_f = ccx_xs_relay_key(wk_host, H, D);
   const std::vector<bf16_t> wkt = pack_mfma_rows(wkt_f.data(), H * D, 64, 16), wv = pack_mfma_rows(wv_host, D, D, 16);
   bf16_t *d_wkt = nullptr, *d_wv = nullptr, *d_xq = nullptr, *d_out = nullptr, *d_xc = nullptr;
   float *d_bv = nullptr, *d_po = nullptr, *d_pml = nullptr;
-  int* d_rs = nullptr;
+  int *d_rs = nullptr, *d_nk = nullptr;
   unsigned char* d_img = nullptr;
-  auto cleanup = [&]() { hipFree(d_wkt); hipFree(d_wv); hipFree(d_xq); hipFree(d_out); hipFree(d_bv); hipFree(d_rs); hipFree(d_po); hipFree(d_pml); hipFree(d_xc); hipFree(d_img); };
+  auto cleanup = [&]() { hipFree(d_wkt); hipFree(d_wv); hipFree(d_xq); hipFree(d_out); hipFree(d_bv); hipFree(d_rs); hipFree(d_po); hipFree(d_pml); hipFree(d_xc); hipFree(d_img); hipFree(d_nk); };
 #define XS_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return ccx_fail(ctx, CCX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
   XS_TRY(hipMalloc(&d_wkt, wkt.size() * 2)); XS_TRY(hipMalloc(&d_wv, wv.size() * 2)); XS_TRY(hipMalloc(&d_bv, (size_t)D * 4));
   XS_TRY(hipMalloc(&d_xq, (size_t)rows * H * D * 2)); XS_TRY(hipMalloc(&d_out, (size_t)rows * D * 2));
@@ -961,8 +967,13 @@ static int cross_attention_xa_impl(ccx_ctx* ctx, const float* q_dev, const float
     XS_TRY(hipMalloc(&d_rs, (size_t)rows * 4));
     XS_TRY(hipMemcpy(d_rs, row_seq_host, (size_t)rows * 4, hipMemcpyHostToDevice));
   }
+  if (n_keys_host) {
+    XS_TRY(hipMalloc(&d_nk, (size_t)n_seq * 4));
+    XS_TRY(hipMemcpy(d_nk, n_keys_host, (size_t)n_seq * 4, hipMemcpyHostToDevice));
+  }
   XsParams p;
   memset(&p, 0, sizeof(p));
+  p.seq_S = d_nk;
   p.q = q_dev; p.WkT = d_wkt; p.xq = d_xq; p.X = xa_dev; p.x_seq_stride = (long)S * D; p.row_seq = d_rs; p.Wv = d_wv; p.bv = d_bv; p.out = d_out; p.part_o = d_po; p.part_ml = d_pml;
   p.rows = rows; p.H = H; p.S = S; p.D = D; p.scale_log2e = 0.125f * 1.4426950408889634f;
   p.rows_per_seq = rows_per_seq > 1 ? rows_per_seq : 0;
@@ -995,7 +1006,7 @@ extern "C" int ccx_cross_attention_xa(ccx_ctx* ctx, const float* q_dev, const fl
                                       int n_ctx, float* out_dev, void* stream_) {
   if (!ctx) return CCX_ERR_ARG;
   return cross_attention_xa_impl(ctx, q_dev, wk_host, wv_host, bv_host, xa_dev, row_seq_host, rows_per_seq, rows, n_seq, n_head, n_ctx, out_dev,
-                                 false, nullptr, (hipStream_t)stream_);
+                                 false, nullptr, nullptr, (hipStream_t)stream_);
 }
 
 extern "C" int ccx_cross_attention_xa_fp8(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
@@ -1004,5 +1015,25 @@ extern "C" int ccx_cross_attention_xa_fp8(ccx_ctx* ctx, const float* q_dev, cons
   if (!ctx) return CCX_ERR_ARG;
   CCX_REQUIRE(ctx, xhat_out_dev, "cross_attention_xa_fp8: xhat_out_dev is null");
   return cross_attention_xa_impl(ctx, q_dev, wk_host, wv_host, bv_host, xa_dev, row_seq_host, rows_per_seq, rows, n_seq, n_head, n_ctx, out_dev,
-                                 true, xhat_out_dev, (hipStream_t)stream_);
+                                 true, xhat_out_dev, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int ccx_cross_attention_xa_keys(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
+                                           const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head,
+                                           int n_ctx, const int* n_keys_host, float* out_dev, void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  CCX_REQUIRE(ctx, n_keys_host, "cross_attention_xa_keys: n_keys_host is null");
+  return cross_attention_xa_impl(ctx, q_dev, wk_host, wv_host, bv_host, xa_dev, row_seq_host, rows_per_seq, rows, n_seq, n_head, n_ctx, out_dev,
+                                 false, nullptr, n_keys_host, (hipStream_t)stream_);
+}
+
+extern "C" int ccx_cross_attention_xa_fp8_keys(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host,
+                                               const float* bv_host, const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows,
+                                               int n_seq, int n_head, int n_ctx, const int* n_keys_host, float* out_dev, uint16_t* xhat_out_dev,
+                                               void* stream_) {
+  if (!ctx) return CCX_ERR_ARG;
+  CCX_REQUIRE(ctx, n_keys_host, "cross_attention_xa_fp8_keys: n_keys_host is null");
+  CCX_REQUIRE(ctx, xhat_out_dev, "cross_attention_xa_fp8_keys: xhat_out_dev is null");
+  return cross_attention_xa_impl(ctx, q_dev, wk_host, wv_host, bv_host, xa_dev, row_seq_host, rows_per_seq, rows, n_seq, n_head, n_ctx, out_dev,
+                                 true, xhat_out_dev, n_keys_host, (hipStream_t)stream_);
 }

@@ -23,11 +23,14 @@ template <int NS>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, long ldx,
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, bf16_t* __restrict__ ob,
-                                                        float* __restrict__ of, long ldo, int M, int D, float eps) {
+                                                        float* __restrict__ of, long ldo, int M, int D, float eps, int rpb_in,
+                                                        int rpb_out) {
   using acc_t = typename std::conditional<(NS > 4), double, float>::type;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
+  // output row remap (ccx_launch_layernorm_rows): rows arrive in groups of rpb_in, group g row i -> g * rpb_out + i; 0: identity
+  const long orow = rpb_in > 0 ? (long)(row / rpb_in) * rpb_out + row % rpb_in : row;
   const float4* xr = (const float4*)(x + (long)row * ldx);
   const int nv = D >> 2;  // D % 4 == 0
   // D <= 256 NS: a lane keeps at most NS float4 of the row in registers
@@ -63,9 +66,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         uint2 o;
         o.x = pack_bf16x2(y.x, y.y);
         o.y = pack_bf16x2(y.z, y.w);
-        ((uint2*)(ob + (long)row * ldo))[idx] = o;
+        ((uint2*)(ob + orow * ldo))[idx] = o;
       }
-      if (of) ((float4*)(of + (long)row * ldo))[idx] = y;
+      if (of) ((float4*)(of + orow * ldo))[idx] = y;
     }
   }
 }
@@ -239,6 +242,12 @@ int ccx_launch_gather_rows(ccx_ctx* ctx, const long* src_ptrs_dev, const int* le
 
 int ccx_launch_layernorm(ccx_ctx* ctx, const float* x, long ldx, const float* gamma, const float* beta,
                          bf16_t* out_bf16, float* out_f32, long ldo, int M, int D, float eps, hipStream_t stream) {
+  return ccx_launch_layernorm_rows(ctx, x, ldx, gamma, beta, out_bf16, out_f32, ldo, M, D, eps, 0, 0, stream);
+}
+
+int ccx_launch_layernorm_rows(ccx_ctx* ctx, const float* x, long ldx, const float* gamma, const float* beta, bf16_t* out_bf16, float* out_f32,
+                              long ldo, int M, int D, float eps, int rpb_in, int rpb_out, hipStream_t stream) {
+  CCX_REQUIRE(ctx, rpb_in >= 0 && (rpb_in == 0 || rpb_out >= rpb_in), "layernorm: row groups of %d do not fit groups of %d", rpb_in, rpb_out);
   CCX_REQUIRE(ctx, M > 0 && D > 0 && D % 4 == 0 && D <= 1280, "layernorm: D=%d must be a multiple of 4 and <= 1280", D);
   CCX_REQUIRE(ctx, ldx % 4 == 0 && ldo % 4 == 0, "layernorm: ld must be a multiple of 4");
   static const bool by_shape = getenv("CCX_PROF_SHAPES") != nullptr;
@@ -254,10 +263,10 @@ int ccx_launch_layernorm(ccx_ctx* ctx, const float* x, long ldx, const float* ga
   ccx_prof_scope ps(ctx, stream, label, 0.0, (double)M * D * (4.0 + (out_bf16 ? 2.0 : 0.0) + (out_f32 ? 4.0 : 0.0)));
   if (D <= 1024)
     hipLaunchKernelGGL(layernorm_kernel<4>, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, ldx, gamma, beta, out_bf16,
-                       out_f32, ldo, M, D, eps);
+                       out_f32, ldo, M, D, eps, rpb_in, rpb_out);
   else
     hipLaunchKernelGGL(layernorm_kernel<5>, dim3(ccx_cdiv(M, 4)), dim3(256), 0, stream, x, ldx, gamma, beta, out_bf16,
-                       out_f32, ldo, M, D, eps);
+                       out_f32, ldo, M, D, eps, rpb_in, rpb_out);
   CCX_CHECK_LAUNCH(ctx);
   return CCX_OK;
 }

@@ -197,6 +197,12 @@ struct ccx_whisper {
   bool cross_fp8 = false, cross_fp8_called = false;
   unsigned char* xa8 = nullptr;
   long xa8_stride = 0;                       // bytes between sequences
+  // Reduced audio context (ccx_whisper_set_audio_ctx; include/ccx.h): ccx_whisper_encode_ctx keeps positions [0, n_ctx[b]) of window b,
+  // xa_n holds the counts the X-stream reads (XsParams::seq_S), and every decode takes the X-stream path.  Off: nothing allocated.
+  bool audio_ctx = false;
+  int* xa_n = nullptr;                       // device [max_batch]: keys of every window of the last encode
+  std::vector<int> enc_ctx;                  // the same on the host ([max_batch]; the alignment pass checks its windows against it)
+  bool ctx_full = false;                     // xa_n holds n_audio_ctx everywhere
   int last_cross_path = -1;                  // ccx_whisper_last_cross_path: 0 kv16, 1 kv_stream, 2 xa_stream
   int kv_cap = 0, kv_ready = 0;
   bf16_t *xq = nullptr, *pf_xq = nullptr;    // expanded queries [rows][H][D] (step rows, prefill rows)
@@ -418,6 +424,26 @@ int ccx_whisper_set_cross_fp8(ccx_whisper* w, int on) {
 }
 
 int ccx_whisper_cross_fp8(ccx_whisper* w) { return w && w->cross_fp8 ? 1 : 0; }
+
+int ccx_whisper_set_audio_ctx(ccx_whisper* w, int on) {
+  if (!w) return CCX_ERR_ARG;
+  CCX_REQUIRE(w->ctx, !w->finalized, "whisper: set_audio_ctx after finalize");
+  if (on) {      // the rule of ccx_whisper_set_cross_fp8: the X-stream is the only cross attention that reads a count per sequence
+    const ccx_whisper_dims& d = w->d;
+    CCX_REQUIRE(w->ctx, d.n_text_state == d.n_audio_state && d.n_text_head == d.n_audio_head,
+                "whisper: set_audio_ctx: decoder width %d (%d heads) differs from the encoder's %d (%d heads): the instance has no X-stream path",
+                d.n_text_state, d.n_text_head, d.n_audio_state, d.n_audio_head);
+    CCX_REQUIRE(w->ctx, ccx_xs_supported(d.n_audio_state, d.n_audio_head),
+                "whisper: set_audio_ctx: width %d is not one the X-stream cross attention is instantiated for (128, 256, 384, 512, 768)", d.n_audio_state);
+    const char* e = getenv("CCX_CROSS_X");
+    CCX_REQUIRE(w->ctx, !e || atoi(e) != 0, "whisper: set_audio_ctx: CCX_CROSS_X=0 turns the X-stream path off, which is the only cross attention with a key count per sequence");
+    CCX_REQUIRE(w->ctx, d.n_audio_ctx >= 64, "whisper: set_audio_ctx: n_audio_ctx = %d is below the smallest context, 64", d.n_audio_ctx);
+  }
+  w->audio_ctx = on != 0;
+  return CCX_OK;
+}
+
+int ccx_whisper_audio_ctx(ccx_whisper* w) { return w && w->audio_ctx ? 1 : 0; }
 
 int ccx_whisper_share_encoder_scratch(ccx_whisper* w, ccx_whisper* donor) {
   if (!w) return CCX_ERR_ARG;
@@ -644,6 +670,7 @@ int ccx_whisper_finalize(ccx_whisper* w) {
     const char* f = getenv("CCX_CROSS_FP8");
     if (!w->cross_fp8_called) w->cross_fp8 = w->xs_on && f && atoi(f) != 0;
     CCX_REQUIRE(w->ctx, !w->cross_fp8 || w->xs_on, "whisper: the FP8 encoder-output stream needs the X-stream path (CCX_CROSS_X=0?)");
+    CCX_REQUIRE(w->ctx, !w->audio_ctx || w->xs_on, "whisper: the reduced audio context needs the X-stream path (CCX_CROSS_X=0?)");
   }
   for (int l = 0; l < d.n_text_layer; l++) {
     const std::string p = "decoder.blocks." + std::to_string(l) + ".";
@@ -721,6 +748,11 @@ int ccx_whisper_finalize(ccx_whisper* w) {
   if (w->cross_fp8) {       // + one key tile of slack as well; zeroed: the quantise kernel leaves the unused scale bytes alone
     w->xa8_stride = xa_fp8_seq_bytes(S, D);
     CCX_TRY(w->store.alloc(&w->xa8, (size_t)B * w->xa8_stride + xa_fp8_tile_bytes(D), true));
+  }
+  if (w->audio_ctx) {
+    w->enc_ctx.assign(B, S);
+    CCX_TRY(w->store.upload(&w->xa_n, w->enc_ctx));
+    w->ctx_full = true;
   }
   if (w->xs_on) {
     CCX_TRY(w->store.alloc(&w->xq, (size_t)B * H * D, true));
@@ -908,7 +940,8 @@ static int select_cross_path(ccx_whisper* w, StepPlan& p, hipStream_t stream, in
   const char* e = getenv("CCX_CROSS_X_MIN_ROWS");
   const int min_rows = e ? atoi(e) : ccx_whisper::kKvSeqs + 1;
   if (n_kv < 0) n_kv = B;
-  p.xs_active = w->xs_on && (B >= min_rows || n_kv > w->kv_cap);
+  // a reduced-audio-context instance: always -- the K / V-cache kernels know no key count per sequence
+  p.xs_active = w->xs_on && (w->audio_ctx || B >= min_rows || n_kv > w->kv_cap);
   if (w->xs_on && !p.xs_active && w->kv_ready < n_kv) CCX_TRY(project_cross_kv(w, n_kv, stream));
   return CCX_OK;
 }
@@ -922,14 +955,33 @@ static StepPlan single_lane_plan(const ccx_whisper* w, int B, int max_prompt) {
   return p;
 }
 
-int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out, void* stream_) {
-  if (!w) return CCX_ERR_ARG;
-  hipStream_t stream = (hipStream_t)stream_;
+// the counts of the windows [0, B) to the device (n_ctx null: n_audio_ctx for every window of the instance)
+static int upload_audio_ctx(ccx_whisper* w, const int* n_ctx, int B, hipStream_t stream) {
+  if (!n_ctx && w->ctx_full) return CCX_OK;
+  const int n = n_ctx ? B : w->max_batch;
+  for (int b = 0; b < n; b++) w->enc_ctx[b] = n_ctx ? n_ctx[b] : w->d.n_audio_ctx;
+  CCX_HIP(w->ctx, hipMemcpyAsync(w->xa_n, w->enc_ctx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
+  CCX_HIP(w->ctx, hipStreamSynchronize(stream));     // enc_ctx is written again by the next encode
+  w->ctx_full = !n_ctx;
+  return CCX_OK;
+}
+
+// n_ctx (host [B], or null: the whole window for every sequence): the encoder at S = max(n_ctx) rows per sequence, sequence b attending
+// over its first n_ctx[b] positions (include/ccx.h, ccx_whisper_encode_ctx).  S = n_audio_ctx runs the launches of the plain encode.
+static int encode_impl(ccx_whisper* w, int B, const int* n_ctx, float* xa_out, hipStream_t stream) {
   ccx_ctx* ctx = w->ctx;
-  CCX_REQUIRE(ctx, w->finalized, "whisper: not finalized");
-  CCX_REQUIRE(ctx, B >= 1 && B <= w->max_batch, "whisper_encode: B=%d out of range (max %d)", B, w->max_batch);
   const ccx_whisper_dims& d = w->d;
-  const int D = d.n_audio_state, F = 4 * D, S = d.n_audio_ctx, H = d.n_audio_head;
+  const int D = d.n_audio_state, F = 4 * D, Sfull = d.n_audio_ctx, H = d.n_audio_head;
+  int S = Sfull;
+  const int* n_keys = nullptr;       // device: the attention's count per sequence
+  if (n_ctx) {
+    S = 0;
+    for (int b = 0; b < B; b++) S = n_ctx[b] > S ? n_ctx[b] : S;
+    S = (S + 3) & ~3;                // the heads epilogue of the q | k | v GEMM stores V^T four rows at a time
+    if (S > Sfull) S = Sfull;
+    n_keys = w->xa_n;
+  }
+  if (w->audio_ctx) CCX_TRY(upload_audio_ctx(w, n_ctx, B, stream));
   GemmParams p;
   // conv1 + GELU: [B*3000,KP] x [D,KP]^T -> h1 rows b*3002 + 1 + t (KP = 256 for 80 mels, 384 for 128)
   const int KP = ccx_logmel_kpad(d.n_mels);
@@ -942,7 +994,7 @@ int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out, void* stream_) {
   p.A = w->h1; p.lda = 2 * D; p.W = w->Wc2; p.ldw = 3 * D; p.M = B * 1501; p.N = D; p.K = 3 * D;
   p.bias = w->bc2; p.out = w->x; p.ldo = D; p.resid = w->enc_pos; p.ldr = D; p.resid_mod = S;
   p.rpb_in = 1501; p.rpb_out = S; p.roff = 0; p.rpb_valid = S;
-  CCX_TRY(ccx_launch_gemm(ctx, EPI_F32_GELU_POS, p, stream));
+  CCX_TRY(ccx_launch_gemm(ctx, EPI_F32_GELU_POS, p, stream));   // (S < n_audio_ctx: the rows behind S are dropped by the row remap)
 
   const int M = B * S;
   for (int l = 0; l < d.n_audio_layer; l++) {
@@ -952,7 +1004,7 @@ int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out, void* stream_) {
     p.A = w->xn; p.lda = D; p.W = L.Wqkv; p.ldw = D; p.M = M; p.N = 3 * D; p.K = D; p.bias = L.bqkv;
     p.hq = w->qb; p.hk = w->kb; p.hv = w->vtb; p.d_model = D; p.n_head = H; p.S = S; p.Spad = w->Spad; p.v_transposed = 1;
     CCX_TRY(ccx_launch_gemm(ctx, EPI_HEADS, p, stream));
-    CCX_TRY(ccx_launch_enc_attention(ctx, w->qb, w->kb, w->vtb, w->attn, B, H, S, w->Spad, stream));
+    CCX_TRY(ccx_launch_enc_attention(ctx, w->qb, w->kb, w->vtb, w->attn, B, H, S, w->Spad, stream, n_keys));
     memset(&p, 0, sizeof(p));
     p.A = w->attn; p.lda = D; p.W = L.Wo; p.ldw = D; p.M = M; p.N = D; p.K = D; p.bias = L.bo;
     p.out = w->x; p.ldo = D; p.resid = w->x; p.ldr = D;
@@ -966,15 +1018,39 @@ int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out, void* stream_) {
     p.out = w->x; p.ldo = D; p.resid = w->x; p.ldr = D;
     CCX_TRY(ccx_launch_gemm(ctx, EPI_F32_RESID, p, stream));
   }
-  CCX_TRY(ccx_launch_layernorm(ctx, w->x, D, w->lnp_g, w->lnp_b, w->xa, w->cross_fp8 ? nullptr : xa_out, D, M, D, 1e-5f, stream));
-  // FP8 instance: the image for the X-stream, and xa (and xa_out) become the dequantised values every consumer then shares
-  if (w->cross_fp8) CCX_TRY(ccx_launch_xa_fp8_quantise(ctx, w->xa, (long)S * D, w->xa8, w->xa8_stride, xa_out, B, S, D, stream));
+  // xa keeps its slot stride of n_audio_ctx rows per window whatever S is: lane offsets, row maps, the FP8 image's stride and captured
+  // step graphs stay what they are
+  CCX_TRY(ccx_launch_layernorm_rows(ctx, w->x, D, w->lnp_g, w->lnp_b, w->xa, w->cross_fp8 ? nullptr : xa_out, D, M, D, 1e-5f, S == Sfull ? 0 : S,
+                                    Sfull, stream));
+  // FP8 instance: the image for the X-stream, and xa (and xa_out) become the dequantised values every consumer then shares.  All
+  // n_audio_ctx rows of a slot, as always: the rows behind S are an earlier encode's (or zeros), finite, and no key of this one
+  if (w->cross_fp8) CCX_TRY(ccx_launch_xa_fp8_quantise(ctx, w->xa, (long)Sfull * D, w->xa8, w->xa8_stride, xa_out, B, Sfull, D, stream));
   CCX_TRY(scratch_release(w, stream));
   w->enc_B = B;
   // cross-attention K/V: with the X-stream cross attention only decodes of <= 80 sequences use them and project them themselves
   w->kv_ready = 0;
   if (!w->xs_on) CCX_TRY(project_cross_kv(w, B, stream));
   return CCX_OK;
+}
+
+int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out, void* stream_) {
+  if (!w) return CCX_ERR_ARG;
+  CCX_REQUIRE(w->ctx, w->finalized, "whisper: not finalized");
+  CCX_REQUIRE(w->ctx, B >= 1 && B <= w->max_batch, "whisper_encode: B=%d out of range (max %d)", B, w->max_batch);
+  return encode_impl(w, B, nullptr, xa_out, (hipStream_t)stream_);
+}
+
+int ccx_whisper_encode_ctx(ccx_whisper* w, int B, const int* n_ctx, float* xa_out, void* stream_) {
+  if (!w) return CCX_ERR_ARG;
+  ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, w->finalized, "whisper: not finalized");
+  CCX_REQUIRE(ctx, w->audio_ctx, "ccx_whisper_encode_ctx: the instance was not built for a reduced audio context (ccx_whisper_set_audio_ctx before finalize)");
+  CCX_REQUIRE(ctx, B >= 1 && B <= w->max_batch, "ccx_whisper_encode_ctx: B = %d out of range [1, max_batch = %d]", B, w->max_batch);
+  CCX_REQUIRE(ctx, n_ctx != nullptr, "ccx_whisper_encode_ctx: n_ctx is NULL");
+  for (int b = 0; b < B; b++)
+    CCX_REQUIRE(ctx, n_ctx[b] >= 64 && n_ctx[b] <= w->d.n_audio_ctx, "ccx_whisper_encode_ctx: n_ctx[%d] = %d out of range [64, n_audio_ctx = %d]", b, n_ctx[b],
+                w->d.n_audio_ctx);
+  return encode_impl(w, B, n_ctx, xa_out, (hipStream_t)stream_);
 }
 
 }  // extern "C"
@@ -1306,6 +1382,7 @@ int dec_step(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
       xp.part_ml = pre ? w->pf_xs_pml : w->xs_pml + ccx_xs_part_ml_elems(ro);
       xp.X = (pre || map_on) ? w->xa : w->xa + ro * (long)d.n_audio_ctx * D; xp.x_seq_stride = (long)d.n_audio_ctx * D;
       xp.row_seq = map_on ? win : row_seq;
+      if (w->audio_ctx) xp.seq_S = (pre || map_on) ? w->xa_n : w->xa_n + ro;      // indexed as X is
       xp.Wv = L.Wcv_x; xp.bv = L.bckv + D; xp.out = dattn; xp.out_packed = packed_mid;
       xp.rows = B; xp.H = H; xp.S = d.n_audio_ctx; xp.D = D; xp.scale_log2e = scale_log2e;
       xp.lds_pad = (p.cross_lds_pad > 0 && !pre) ? 65536 : 0;
@@ -1544,6 +1621,9 @@ int ccx_whisper_align_probs(ccx_whisper* w, const int32_t* tokens, const int32_t
                 max_len);
     CCX_REQUIRE(ctx, n_frames[b] >= 2 && n_frames[b] <= 2 * Mmax, "ccx_whisper_align: n_frames[%d] = %d out of range [2, %d]", b, n_frames[b], 2 * Mmax);
     keys[b] = n_frames[b] / 2; nrows[b] = lens[b]; r1[b] = lens[b] - 1;
+    if (w->audio_ctx)
+      CCX_REQUIRE(ctx, keys[b] <= w->enc_ctx[b], "ccx_whisper_align: n_frames[%d] = %d needs %d positions, window %d was encoded with an audio context of %d", b,
+                  n_frames[b], keys[b], b, w->enc_ctx[b]);
     for (int t = 0; t < lens[b]; t++) {
       const int32_t tok = tokens[(size_t)b * max_len + t];
       CCX_REQUIRE(ctx, tok >= 0 && tok < d.n_vocab, "ccx_whisper_align: tokens[%d][%d] = %d out of range [0, n_vocab = %d)", b, t, tok, d.n_vocab);
@@ -1626,6 +1706,9 @@ int ccx_whisper_align_probs(ccx_whisper* w, const int32_t* tokens, const int32_t
   plan.cross_stream = 0;
   plan.fuse_cross_q = 0;
   plan.xs_active = 0;       // whatever the size: no select_cross_path here
+  // a reduced-audio-context instance: the rows' cross attention must stop at their window's count, which only the X-stream does -- with
+  // the query still a launch of its own (dq is what the hook reads).  K is projected as always and read up to n_frames / 2 <= the count
+  if (w->audio_ctx) { plan.xs_active = 1; plan.lnfree = 0; plan.xs_fuse_q = 0; }
   if (w->kv_ready < B) CCX_TRY(project_cross_kv(w, B, stream));
   std::vector<int32_t> plens(B, T + 1);    // never leaves the prompt phase: every step feeds tokens[b][pos]
   CCX_TRY(upload_decode_state(w, padded.data(), plens.data(), T, B, 0.f, 0, stream));

@@ -18,7 +18,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, decoding_options, fallback
+from . import _lib, audio_ctx as audio_ctx_policy, decoding_options, fallback
 from .audio import mel_filterbank
 from .tokenizer import DecodeRules, IdTokenizer, get_tokenizer
 from .weights import WhisperDims
@@ -46,6 +46,15 @@ def cross_fp8_refusal(dims: WhisperDims) -> Optional[str]:
     return None
 
 
+def audio_ctx_refusal(dims: WhisperDims) -> Optional[str]:
+    """Why an instance of these dims cannot run a reduced audio context (include/ccx.h ccx_whisper_set_audio_ctx), or None: the rule of
+    `cross_fp8_refusal` -- the X-stream is the only cross attention with a key count per sequence -- checked before anything is created."""
+    why = cross_fp8_refusal(dims)
+    if why is None:
+        return None
+    return why.replace("which is the only reader of the FP8 image", "which is the only cross attention with a key count per sequence")
+
+
 class CallSettings(NamedTuple):
     """What one call wants set on the instance while it runs (`WhisperModel._settings`); a field that is None sets nothing."""
     options: Optional[decoding_options.CallOptions] = None      # -> set_decode_options
@@ -64,6 +73,9 @@ class WhisperModel:
     contextual_bias = False           # and sequence_bias / bad_words_ids / hotwords
     truncated_sampling = False        # and top_k / top_p / min_p
     cross_fp8 = False                 # the FP8 encoder-output stream (a property of the instance; the library's state after finalize)
+    audio_ctx = None                  # the reduced audio context: None (off), "auto" or the positions every window keeps
+    _staged_frames = None             # content frames of the windows `log_mel` staged last (None: `set_mel`, or nothing staged)
+    last_audio_ctx: Sequence[int] = ()  # the contexts of the windows of the last `encode`
 
     def __init__(self, dims: WhisperDims, state_dict: Dict[str, torch.Tensor], max_batch: int = 8,
                  device: int = 0, rules: Optional[DecodeRules] = None, tokenizer=None,
@@ -72,8 +84,18 @@ class WhisperModel:
                  alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False,
                  temperature_fallback: bool = False, beam_search: bool = False, decoding_options: bool = False,
                  repetition_control: bool = False, contextual_bias: bool = False, truncated_sampling: bool = False,
-                 cross_fp8: bool = False):
-        """cross_fp8 (default False: the instance allocates nothing more, runs no other kernel and keeps its bits): with it, the
+                 cross_fp8: bool = False, audio_ctx=None):
+        """audio_ctx (default None: the instance allocates nothing more, launches what it always launched and keeps its bits): "auto" or
+        an integer in [64, n_audio_ctx] builds the instance for a REDUCED AUDIO CONTEXT -- `encode` keeps only the first n encoder
+        positions of a window (n = `audio_ctx.positions_for(content frames)` per window under "auto", the integer otherwise), every
+        encoder layer attends over those only, and the cross attention of every decode reads those n rows (every decode then takes
+        the "xa_stream" path, whatever its size).  `encode(audio_ctx=)`, `transcribe(audio_ctx=)` override it per call ("full": the
+        whole window).  This is NOT upstream's arithmetic: Whisper was trained on zero-padded 30 s windows, and what fewer positions
+        cost in transcript quality on real checkpoints is NOT measured: that is why it is off by default.  Refused with CcxError,
+        before anything is allocated, under the rule of cross_fp8 (the 1280-wide family, unequal widths, CCX_CROSS_X=0); a value
+        that is neither raises ValueError.  Where the keyword is absent, CCX_AUDIO_CTX (`auto` or an integer) in the environment
+        sets it on instances that can run it -- for A/B runs of an unmodified bench.py only.
+        cross_fp8 (default False: the instance allocates nothing more, runs no other kernel and keeps its bits): with it, the
         instance keeps a block-scaled FP8 image of the encoder output (32-feature blocks, E4M3 codes, power-of-two scales; the rule
         is in include/ccx.h) and the cross attention of decodes on the "xa_stream" path reads it instead of the bf16 rows.  `encode`
         then leaves the DEQUANTISED encoder output with the instance -- what `encode(return_xa=True)` returns and every decode path
@@ -130,9 +152,17 @@ class WhisperModel:
             why = cross_fp8_refusal(dims)
             if why is not None:
                 raise _lib.CcxError(f"cross_fp8=True refused: {why}")
+        if audio_ctx is not None:
+            audio_ctx = audio_ctx_policy.parse_setting(audio_ctx, dims.n_audio_ctx)
+            why = audio_ctx_refusal(dims)
+            if why is not None:
+                raise _lib.CcxError(f"audio_ctx={audio_ctx!r} refused: {why}")
+        elif audio_ctx_refusal(dims) is None:       # the environment: ignored, not refused, where the instance cannot run it
+            audio_ctx = audio_ctx_policy.from_environment(dims.n_audio_ctx)
         if not torch.cuda.is_available():
             raise _lib.CcxError("WhisperModel needs a ROCm GPU: the HIP path has no CPU fallback")
         self.dims = dims
+        self.audio_ctx = audio_ctx
         self.max_batch = int(max_batch)
         self.device = torch.device("cuda", device)
         self.ctx = ctx or _lib.Context(device)
@@ -162,6 +192,8 @@ class WhisperModel:
         self.ctx.check(self.lib.ccx_whisper_set_max_audio(self.handle, self.max_audio_seconds), "ccx_whisper_set_max_audio")
         if cross_fp8:
             self.ctx.check(self.lib.ccx_whisper_set_cross_fp8(self.handle, 1), "ccx_whisper_set_cross_fp8")
+        if self.audio_ctx is not None:
+            self.ctx.check(self.lib.ccx_whisper_set_audio_ctx(self.handle, 1), "ccx_whisper_set_audio_ctx")
         # log-mel / encoder workspaces of another instance (kept alive here): only for instances whose log_mel / encode calls
         # are ordered on one stream, as in BatchPipeline.run_pinned_pipelined (include/ccx.h)
         self._scratch_donor = share_encoder_scratch_with
@@ -469,6 +501,10 @@ class WhisperModel:
         cap on every window's frames -- zeros behind it, as pad_or_trim leaves a cropped mel."""
         B = audio.shape[0]
         assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
+        # every staged window's content frames (the library's segment_size): what `encode` sizes a reduced audio context from
+        self._staged_frames = [min(max(int(n_samples[b]) // HOP - (int(seek[b]) if seek is not None else 0), 0), N_FRAMES) for b in range(B)]
+        if max_frames is not None:
+            self._staged_frames = [min(f, int(m)) for f, m in zip(self._staged_frames, max_frames)]
         ns = (C.c_int * B)(*[int(x) for x in n_samples])
         sk = (C.c_int * B)(*[int(x) for x in seek]) if seek is not None else None
         mel = torch.empty(B, self.dims.n_mels, N_FRAMES, device=self.device, dtype=torch.float32) if return_mel else None
@@ -485,10 +521,46 @@ class WhisperModel:
         assert mel.is_cuda and mel.dtype == torch.float32 and mel.is_contiguous() and mel.shape[1:] == (self.dims.n_mels, N_FRAMES)
         self.ctx.check(self.lib.ccx_whisper_set_mel(self.handle, mel.data_ptr(), mel.shape[0], _lib.current_stream_ptr()),
                        "ccx_whisper_set_mel")
+        self._staged_frames = None      # a ready mel says nothing about its content: the whole window
 
-    def encode(self, B: int, return_xa: bool = False) -> Optional[torch.Tensor]:
+    def _window_contexts(self, B: int, audio_ctx) -> Optional[List[int]]:
+        """The audio context of each of the B staged windows, or None for the plain encode: audio_ctx None applies the instance's policy
+        (the whole window when it is off, or after `set_mel`), "full" the whole window, "auto" / an int that setting, a list explicit
+        values.  Anything but None / "full" needs an instance built with `audio_ctx`."""
+        S = self.dims.n_audio_ctx
+        if isinstance(audio_ctx, str) and audio_ctx.strip().lower() == "full":
+            return None
+        if audio_ctx is None:
+            setting = self.audio_ctx
+        elif self.audio_ctx is None:
+            raise ValueError(f"audio_ctx={audio_ctx!r}: the instance was not built for a reduced audio context (WhisperModel(audio_ctx=...))")
+        elif isinstance(audio_ctx, (list, tuple, np.ndarray)):
+            vals = [int(v) for v in audio_ctx]
+            if len(vals) != B or any(not audio_ctx_policy.FLOOR <= v <= S for v in vals):
+                raise ValueError(f"audio_ctx={vals}: one value in [{audio_ctx_policy.FLOOR}, {S}] per window ({B}) expected")
+            return vals
+        else:
+            setting = audio_ctx_policy.parse_setting(audio_ctx, S)
+        if setting is None or (setting == "auto" and self._staged_frames is None):
+            return None
+        if setting == "auto" and len(self._staged_frames) < B:
+            raise _lib.CcxError(f"encode: {B} windows asked for, `log_mel` staged {len(self._staged_frames)}")
+        return [audio_ctx_policy.context_of(setting, self._staged_frames[b] if setting == "auto" else 0, S) for b in range(B)]
+
+    def encode(self, B: int, return_xa: bool = False, audio_ctx=None) -> Optional[torch.Tensor]:
+        """AudioEncoder.forward for the B staged windows.  audio_ctx (instances built with `audio_ctx` only): None -- the instance's
+        policy, sized from the content frames `log_mel` staged (the whole window after `set_mel`); "full"; "auto"; an int; or a list of
+        B explicit contexts.  `self.last_audio_ctx` holds what the windows were encoded with.  return_xa: [B, n_audio_ctx, D]; the rows
+        of window b at or beyond its context are unspecified."""
         xa = torch.empty(B, self.dims.n_audio_ctx, self.dims.n_audio_state, device=self.device, dtype=torch.float32) if return_xa else None
-        self.ctx.check(self.lib.ccx_whisper_encode(self.handle, B, _lib.ptr(xa), _lib.current_stream_ptr()), "ccx_whisper_encode")
+        ctxs = self._window_contexts(B, audio_ctx)
+        if ctxs is None:
+            self.ctx.check(self.lib.ccx_whisper_encode(self.handle, B, _lib.ptr(xa), _lib.current_stream_ptr()), "ccx_whisper_encode")
+            self.last_audio_ctx = [self.dims.n_audio_ctx] * B
+        else:
+            n = (C.c_int * B)(*ctxs)
+            self.ctx.check(self.lib.ccx_whisper_encode_ctx(self.handle, B, n, _lib.ptr(xa), _lib.current_stream_ptr()), "ccx_whisper_encode_ctx")
+            self.last_audio_ctx = list(ctxs)
         return xa
 
     def decoder_logits(self, tokens: np.ndarray) -> torch.Tensor:
@@ -815,7 +887,8 @@ class WhisperModel:
                    suppress_blank: bool = True, suppress_tokens="-1", max_initial_timestamp: Optional[float] = 1.0,
                    sample_len: Optional[int] = None, clip_timestamps="0", carry_initial_prompt: bool = False,
                    repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None,
-                   hotwords=None, hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, **_ignored):
+                   hotwords=None, hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, audio_ctx=None,
+                   **_ignored):
         """One clip, same signature as whisper.transcribe as the reference uses it.  temperature 0 is the
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
@@ -842,7 +915,9 @@ class WhisperModel:
         On an instance built with `contextual_bias=True`: sequence_bias, bad_words_ids, hotwords and hotword_boost are honoured (see
         `transcribe_batch`); otherwise they are accepted and ignored.
         On an instance built with `truncated_sampling=True`: top_k, top_p and min_p are honoured (see `transcribe_batch`); otherwise
-        a value off its default raises ValueError."""
+        a value off its default raises ValueError.
+        On an instance built with `audio_ctx`: audio_ctx overrides the instance's setting for this call ("full", "auto" or an int;
+        see `transcribe_batch`), and the result carries `audio_ctx`; otherwise anything but None / "full" raises ValueError."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
                                      compression_ratio_threshold=compression_ratio_threshold, best_of=best_of,
                                      temperature=temperature, no_speech_threshold=no_speech_threshold,
@@ -855,7 +930,7 @@ class WhisperModel:
                                      clip_timestamps=clip_timestamps, carry_initial_prompt=carry_initial_prompt,
                                      repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                                      sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotwords=hotwords,
-                                     hotword_boost=hotword_boost, top_k=top_k, top_p=top_p, min_p=min_p)[0]
+                                     hotword_boost=hotword_boost, top_k=top_k, top_p=top_p, min_p=min_p, audio_ctx=audio_ctx)[0]
 
     def transcribe_batch(self, audios: Sequence, initial_prompts: Optional[Sequence[Optional[str]]] = None,
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
@@ -869,7 +944,7 @@ class WhisperModel:
                          max_initial_timestamp: Optional[float] = 1.0, sample_len: Optional[int] = None, clip_timestamps="0",
                          carry_initial_prompt: bool = False, repetition_penalty: float = 1.0,
                          no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None, hotwords=None,
-                         hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> List[dict]:
+                         hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, audio_ctx=None) -> List[dict]:
         """Independent clips decoded together (each window of each clip is one sequence of a batch).
         languages[i] (multilingual models): the clip's language code or name; None: detected on the clip's first window, after its
         group's `encode` and before its `decode` [UPSTREAM-RECALL: transcribe.py, `if decode_options.get("language") is None`].
@@ -915,8 +990,15 @@ class WhisperModel:
         decode of the call at temperature > 0 -- a single positive temperature, the warm rounds of a fallback walk, every best_of
         candidate (one ccx_whisper_set_sampling_options per call, the defaults back when it returns); a temperature-0 round, greedy
         or beam, is what it is without them, and so are the thresholds: avg_logprob stays the log-probability under the untruncated
-        distribution.  A value outside its range raises ValueError; so does a value off its default without the opt-in."""
+        distribution.  A value outside its range raises ValueError; so does a value off its default without the opt-in.
+        audio_ctx instances (the reduced audio context, WhisperModel.__init__; not upstream's arithmetic, quality unmeasured): every
+        window is encoded with the instance's setting, or with this call's audio_ctx -- "full" (all n_audio_ctx positions: the tokens of
+        an instance without the opt-in), "auto" or an int; every result carries `audio_ctx`, the context of each of the clip's
+        windows, in order.  Without the opt-in anything but None / "full" raises ValueError."""
         n = len(audios)
+        if audio_ctx is not None:       # refuse before anything runs
+            self._window_contexts(0, audio_ctx)
+        clip_ctx: List[List[int]] = [[] for _ in range(n)]
         settings, opt, prefix_toks = self._transcribe_settings(
             n, hallucination_silence_threshold, without_timestamps, prefixes, suppress_blank, suppress_tokens, max_initial_timestamp,
             sample_len, carry_initial_prompt, repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords,
@@ -963,7 +1045,13 @@ class WhisperModel:
                                      max_frames=[state[i].segment_size() for i in grp])
                     else:
                         self.log_mel(a, [lens[i] for i in grp], [state[i].seek for i in grp])
-                    self.encode(len(grp))
+                    if audio_ctx is None:       # (the instance's setting; a call without the keyword is the call it always was)
+                        self.encode(len(grp))
+                    else:
+                        self.encode(len(grp), audio_ctx=audio_ctx)
+                    if self.audio_ctx is not None:
+                        for b, i in enumerate(grp):
+                            clip_ctx[i].append(self.last_audio_ctx[b])
                     if any(not state[i].language_known for i in grp):     # first window of a clip without a language
                         codes, _ = self.detect_language(len(grp))
                         for b, i in enumerate(grp):
@@ -991,4 +1079,8 @@ class WhisperModel:
                             for s in state[i].segments[n_seg[b]:]:
                                 s.update(temperature=r["temperature"], avg_logprob=r["avg_logprob"], compression_ratio=r["compression_ratio"],
                                          no_speech_prob=r["no_speech_prob"])
-        return [st.result() for st in state]
+        results_out = [st.result() for st in state]
+        if self.audio_ctx is not None:
+            for r, c in zip(results_out, clip_ctx):
+                r["audio_ctx"] = c
+        return results_out

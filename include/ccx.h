@@ -127,6 +127,16 @@ int ccx_cross_attention_xa(ccx_ctx* ctx, const float* q_dev, const float* wk_hos
 int ccx_cross_attention_xa_fp8(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
                                const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head,
                                int n_ctx, float* out_dev, uint16_t* xhat_out_dev, void* stream);
+/* The two operators above with a key count PER SEQUENCE (reduced audio context, XsParams::seq_S of the streaming kernel): n_keys_host
+ * [n_seq], each in [1, n_ctx]; sequence s is attended over its first n_keys_host[s] rows of xa only, and a row's output is, bit for
+ * bit, what the plain operator gives for that sequence alone with n_ctx = n_keys_host[s].  The FP8 image is the one of all n_ctx
+ * rows (no new format): the keys of a sequence's last 16-key tile beyond its count are real, finite rows whose weight is 0. */
+int ccx_cross_attention_xa_keys(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
+                                const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head,
+                                int n_ctx, const int* n_keys_host, float* out_dev, void* stream);
+int ccx_cross_attention_xa_fp8_keys(ccx_ctx* ctx, const float* q_dev, const float* wk_host, const float* wv_host, const float* bv_host,
+                                    const uint16_t* xa_dev, const int* row_seq_host, int rows_per_seq, int rows, int n_seq, int n_head,
+                                    int n_ctx, const int* n_keys_host, float* out_dev, uint16_t* xhat_out_dev, void* stream);
 /* Embedding-quality weight of `_build_speaker_profiles`: out[b] = torch.var(x[b][0 .. n_b)) (unbiased; reference back/api.py:939).
  * fp64 accumulation in a fixed order: a row's value does not depend on its batch mates. */
 int ccx_row_variance(ccx_ctx* ctx, const float* x_dev, int64_t stride, const int* n_samples_dev, int B, float* out_dev, void* stream);
@@ -151,6 +161,12 @@ int ccx_resample_sinc(ccx_ctx* ctx, const float* x_dev, int64_t stride_in, const
  * zero; vt: [B*H, 64, Spad] bf16; o: [B*S, H*64] bf16.  Softmax scale 1/8 (= 64^-0.25 on q and k). */
 int ccx_enc_attention(ccx_ctx* ctx, const void* q_dev, const void* k_dev, const void* vt_dev, void* o_dev,
                       int B, int H, int S, int Spad, void* stream);
+/* The same with a key count per sequence (reduced audio context): n_keys_host [B], each in [1, S].  Sequence b attends over its first
+ * n_keys_host[b] positions only; its rows of o below the count are, bit for bit, those of ccx_enc_attention on that sequence alone
+ * with S = n_keys_host[b] (same Spad); its rows at or beyond the count are zeros.  Rows of q, k, vt between the count and Spad need
+ * only be finite.  All counts equal to S: the bits of ccx_enc_attention.  Synchronises the stream.  For kernel parity tests. */
+int ccx_enc_attention_keys(ccx_ctx* ctx, const void* q_dev, const void* k_dev, const void* vt_dev, void* o_dev,
+                           int B, int H, int S, int Spad, const int* n_keys_host, void* stream);
 
 /* ---- Whisper (replaces self.whisper_model, reference back/api.py:665-703; calls at
  *      back/api.py:1286-1292, 1432-1438, 1474-1480) ---------------------------------------------- */
@@ -199,6 +215,20 @@ int ccx_whisper_set_max_audio(ccx_whisper* w, double seconds);
 int ccx_whisper_set_cross_fp8(ccx_whisper* w, int on);
 /* 1 when the instance keeps and streams the FP8 image (after finalize: the environment switch included), else 0. */
 int ccx_whisper_cross_fp8(ccx_whisper* w);
+/* Opt-in, before finalize (default off): the reduced audio context ("audio_ctx" of other Whisper runtimes) -- the instance accepts
+ * ccx_whisper_encode_ctx, which keeps only the first n_ctx[b] of the n_audio_ctx encoder positions of window b, and the cross attention
+ * of every decode reads those n_ctx[b] rows only.  This is NOT upstream's arithmetic: Whisper was trained on zero-padded 30 s windows,
+ * and what attending over fewer positions costs in transcript quality on real checkpoints is NOT measured.
+ * The counts live in a device array of max_batch ints which the X-stream cross attention (csrc/cross_x.hip, XsParams::seq_S) reads;
+ * it is the only cross attention with a count per sequence, so on such an instance EVERY decode entry point (decode, decode_greedy,
+ * decode_rows, decode_beam, decoder_logits, detect_language; prefill and lanes included) takes the X-stream path at every batch size
+ * (ccx_whisper_last_cross_path == 2), and the alignment pass runs its decoder rows on it as well.  Refused (CCX_ERR_ARG, the message
+ * names the reason) under the rule of ccx_whisper_set_cross_fp8: no X-stream path (the 1280-wide family, unequal encoder / decoder
+ * widths, CCX_CROSS_X=0).  An instance with it off allocates nothing more, launches what it always launched and computes the bits it
+ * always did. */
+int ccx_whisper_set_audio_ctx(ccx_whisper* w, int on);
+/* 1 when the instance was built for the reduced audio context, else 0. */
+int ccx_whisper_audio_ctx(ccx_whisper* w);
 /* Optional, before finalize: take the log-mel / encoder workspaces of `donor` (finalized, same dimensions, at least this
  * instance's capacity) instead of allocating them.  They are only live between ccx_whisper_logmel / set_mel and the end of
  * ccx_whisper_encode.  Users of one group are ordered by the library: every logmel / set_mel waits (event) for the end of the
@@ -380,6 +410,17 @@ int ccx_whisper_set_mel(ccx_whisper* w, const float* mel_dev, int B, void* strea
  * xa_out_dev (optional): [B, n_audio_ctx, n_audio_state] f32 copy of the encoder output.  On an FP8 instance
  * (ccx_whisper_set_cross_fp8) it is xhat, the dequantised encoder output that the instance keeps and every decode reads. */
 int ccx_whisper_encode(ccx_whisper* w, int B, float* xa_out_dev, void* stream);
+/* The same at a reduced audio context (ccx_whisper_set_audio_ctx instances only): n_ctx host [B], every value in [64, n_audio_ctx].
+ * The conv stem runs on the usual 3000-frame log-mel; positions [0, n_ctx[b]) of window b are kept, with rows [0, n_ctx[b]) of the
+ * positional embedding; every encoder layer attends over those positions only; then ln_post.  The call runs S_run = max(n_ctx) rows (rounded
+ * up to a multiple of 4) per sequence through the GEMMs and LayerNorms, and the attention takes the count per sequence (csrc/attention.hip, n_keys): rows of
+ * a sequence between n_ctx[b] and S_run are computed and never read as keys, so a window's valid rows are, bit for bit, those of the
+ * window encoded alone.  All n_ctx[b] == n_audio_ctx: the bits of ccx_whisper_encode.
+ * The encoder output keeps its slot stride of n_audio_ctx rows per window (lane offsets, row maps, the FP8 image's stride and
+ * captured step graphs stay valid), and the counts stay with the instance until the next encode: a plain ccx_whisper_encode resets
+ * them to n_audio_ctx.  xa_out_dev (optional) is [B, n_audio_ctx, n_audio_state]; its rows at or beyond n_ctx[b] are unspecified.
+ * ccx_whisper_align* after such an encode refuses a window whose n_frames / 2 exceeds its n_ctx. */
+int ccx_whisper_encode_ctx(ccx_whisper* w, int B, const int* n_ctx, float* xa_out_dev, void* stream);
 
 /* Teacher-forced decoder pass for parity tests: tokens [B, T] (host int32) -> logits
  * [B, T, n_vocab] f32 on device.  Uses the same step kernels as greedy decoding. */
