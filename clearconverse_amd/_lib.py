@@ -129,6 +129,14 @@ class DecodeSamplingOptions(C.Structure):
     _fields_ = [("top_k", C.c_int), ("top_p", C.c_float), ("min_p", C.c_float)]
 
 
+class DecodeLogprobOptions(C.Structure):
+    """ccx_decode_logprob_options (include/ccx.h): top_n in [0, LOGPROB_MAX_TOP]; a NULL pointer is off."""
+    _fields_ = [("top_n", C.c_int)]
+
+
+LOGPROB_MAX_TOP = 8     # CCX_LOGPROB_MAX_TOP
+
+
 class DecSeqState(C.Structure):
     """ccx_dec_seq_state: the select kernel's per-sequence state."""
     _fields_ = [(n, C.c_int) for n in ("pos", "prompt_len", "n_gen", "done", "last_tok", "pen_tok", "last_ts_tok", "n_tokens")] + [
@@ -147,7 +155,9 @@ class DecSelectDesc(C.Structure):
         ("logits_elems", C.c_int64), ("tok_emb_elems", C.c_int64), ("pos_emb_elems", C.c_int64), ("x_elems", C.c_int64),
         ("stream_ids", C.POINTER(C.c_int)), ("opts", C.POINTER(DecodeOptions)),
         ("sampling", C.POINTER(DecodeSamplingOptions)), ("cut_out", C.POINTER(C.c_float)), ("kept_out", C.POINTER(C.c_int)),
-        ("kept_mass_out", C.POINTER(C.c_float))]
+        ("kept_mass_out", C.POINTER(C.c_float)),
+        ("logprobs", C.POINTER(DecodeLogprobOptions)), ("tok_logprob_out", C.POINTER(C.c_float)),
+        ("top_id_out", C.POINTER(C.c_int)), ("top_lp_out", C.POINTER(C.c_float))]
 
 
 class DecBeamDesc(C.Structure):
@@ -382,6 +392,10 @@ PROTOTYPES = {
     "ccx_decode_sampling_options_default": (None, [C.POINTER(DecodeSamplingOptions)]),
     "ccx_whisper_set_sampling_options": (_i, [_vp, C.POINTER(DecodeSamplingOptions)]),
     "ccx_whisper_sampling_graph_count": (_i, [_vp]),
+    "ccx_whisper_set_token_logprobs": (_i, [_vp, _i]),
+    "ccx_whisper_set_logprob_options": (_i, [_vp, C.POINTER(DecodeLogprobOptions)]),
+    "ccx_whisper_token_logprobs": (_i, [_vp, _i, _i, C.POINTER(C.c_float), _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _vp]),
+    "ccx_whisper_logprob_graph_count": (_i, [_vp]),
     "ccx_whisper_set_mel": (_i, [_vp, _vp, _i, _vp]),
     "ccx_whisper_encode": (_i, [_vp, _i, _vp, _vp]),
     "ccx_whisper_encode_ctx": (_i, [_vp, _i, _vp, _vp, _vp]),

@@ -555,6 +555,16 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
     CCX_TRY(ccx_check_sampling_options(ctx, "ccx_dec_select_step", &trunc));
   }
   CCX_REQUIRE(ctx, d->sampling || (!d->cut_out && !d->kept_out && !d->kept_mass_out), "ccx_dec_select_step: cut_out, kept_out and kept_mass_out need sampling options");
+  int top_n = 0;
+  if (d->logprobs) {
+    CCX_TRY(ccx_check_logprob_options(ctx, "ccx_dec_select_step", d->logprobs));
+    top_n = d->logprobs->top_n;
+    CCX_REQUIRE(ctx, d->tok_logprob_out, "ccx_dec_select_step: logprobs set with tok_logprob_out NULL");
+    CCX_REQUIRE(ctx, top_n == 0 || (d->top_id_out && d->top_lp_out), "ccx_dec_select_step: logprobs.top_n = %d with top_id_out or top_lp_out NULL", top_n);
+    // the kernel's tables are [B][sample_len] and [B][sample_len][8], staged whole
+    CCX_REQUIRE(ctx, (int64_t)B * d->sample_len <= (1 << 22), "ccx_dec_select_step: logprobs with B * sample_len = %ld above %d", (long)B * d->sample_len, 1 << 22);
+  }
+  CCX_REQUIRE(ctx, d->logprobs || (!d->tok_logprob_out && !d->top_id_out && !d->top_lp_out), "ccx_dec_select_step: tok_logprob_out, top_id_out and top_lp_out need logprobs");
   if (d->stream_ids)
     for (int b = 0; b < B; b++) CCX_REQUIRE(ctx, d->stream_ids[b] >= 0, "ccx_dec_select_step: stream_ids[%d] = %d is negative", b, d->stream_ids[b]);
   for (int b = 0; b < B; b++) {
@@ -597,6 +607,23 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   if (d->cut_out) DO_HIP(sc.upload(&d_cut, d->cut_out, (size_t)B));
   if (d->kept_out) DO_HIP(sc.upload(&d_kept, d->kept_out, (size_t)B));
   if (d->kept_mass_out) DO_HIP(sc.upload(&d_mass, d->kept_mass_out, (size_t)B));
+  // the log-probability tables as the kernel indexes them, [row][step] and [row][step][8], under a fill pattern: behind the launch
+  // only the slots of the rows that sampled may differ from it
+  constexpr unsigned kFill = 0x5a5a5a5au;
+  unsigned *d_tlp = nullptr, *d_tid = nullptr, *d_tpl = nullptr;
+  std::vector<unsigned> tlp_h, tid_h, tpl_h;
+  if (d->logprobs) {
+    tlp_h.assign(n_gen_tab, kFill);
+    DO_HIP(sc.upload(&d_tlp, tlp_h.data(), tlp_h.size()));
+    if (top_n > 0) {
+      tid_h.assign(n_gen_tab * kLogprobMaxTop, kFill); tpl_h = tid_h;
+      DO_HIP(sc.upload(&d_tid, tid_h.data(), tid_h.size()));
+      DO_HIP(sc.upload(&d_tpl, tpl_h.data(), tpl_h.size()));
+    }
+  }
+  std::vector<int> step_of(B, -1);           // the step a row samples in this launch (-1: prompt phase or done)
+  for (int b = 0; b < B; b++)
+    if (!(d->state[b].pos < d->state[b].prompt_len - 1) && !d->state[b].done) step_of[b] = d->state[b].n_gen;
 
   DecSelectParams sp;
   memset(&sp, 0, sizeof(sp));
@@ -609,6 +636,7 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   sp.sample_cfg = d_cfg; sp.row0 = d->row0; sp.sample = d->sample;
   sp.trunc = d->sampling ? 1 : 0; sp.cut_out = d_cut; sp.kept_out = d_kept; sp.kept_mass_out = d_mass;
   if (d->stream_ids) { DO_HIP(sc.upload(&d_sid, d->stream_ids, (size_t)B)); sp.stream_id = d_sid; }
+  sp.tok_logprob = (float*)d_tlp; sp.top_id = (int*)d_tid; sp.top_lp = (float*)d_tpl; sp.top_n = top_n;
   CCX_TRY(ccx_launch_dec_select(ctx, sp, B, stream));
   DO_HIP(hipStreamSynchronize(stream));
   DO_HIP(hipMemcpy(gen_h.data(), d_gen, gen_h.size() * 4, hipMemcpyDeviceToHost));
@@ -622,6 +650,31 @@ extern "C" int ccx_dec_select_step(ccx_ctx* ctx, const ccx_dec_select_desc* d, v
   if (d_cut) DO_HIP(hipMemcpy(d->cut_out, d_cut, (size_t)B * 4, hipMemcpyDeviceToHost));
   if (d_kept) DO_HIP(hipMemcpy(d->kept_out, d_kept, (size_t)B * 4, hipMemcpyDeviceToHost));
   if (d_mass) DO_HIP(hipMemcpy(d->kept_mass_out, d_mass, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (d->logprobs) {
+    DO_HIP(hipMemcpy(tlp_h.data(), d_tlp, tlp_h.size() * 4, hipMemcpyDeviceToHost));
+    if (top_n > 0) {
+      DO_HIP(hipMemcpy(tid_h.data(), d_tid, tid_h.size() * 4, hipMemcpyDeviceToHost));
+      DO_HIP(hipMemcpy(tpl_h.data(), d_tpl, tpl_h.size() * 4, hipMemcpyDeviceToHost));
+    }
+    for (int b = 0; b < B; b++)
+      for (int i = 0; i < d->sample_len; i++) {
+        const size_t at = (size_t)b * d->sample_len + i;
+        const bool mine = i == step_of[b];
+        if (!mine && tlp_h[at] != kFill)
+          return ccx_fail(ctx, CCX_ERR_STATE, "ccx_dec_select_step: the kernel wrote tok_logprob[%d][%d], a slot of no sampled step", b, i);
+        for (int k = 0; k < (top_n > 0 ? kLogprobMaxTop : 0); k++) {
+          const size_t ak = at * kLogprobMaxTop + k;
+          if (!(mine && k < top_n) && (tid_h[ak] != kFill || tpl_h[ak] != kFill))
+            return ccx_fail(ctx, CCX_ERR_STATE, "ccx_dec_select_step: the kernel wrote top[%d][%d][%d], a slot of no sampled step or behind top_n = %d", b, i, k, top_n);
+        }
+        if (!mine) continue;
+        memcpy(&d->tok_logprob_out[b], &tlp_h[at], 4);
+        for (int k = 0; k < top_n; k++) {
+          memcpy(&d->top_id_out[(size_t)b * top_n + k], &tid_h[at * kLogprobMaxTop + k], 4);
+          memcpy(&d->top_lp_out[(size_t)b * top_n + k], &tpl_h[at * kLogprobMaxTop + k], 4);
+        }
+      }
+  }
 #undef DO_HIP
   return CCX_OK;
 }

@@ -148,7 +148,14 @@ struct DecSelectParams {
   // (Appended: no other field moves.)
   int trunc;
   float* cut_out; int* kept_out; float* kept_mass_out;
+  // per-token log-probabilities (ccx_decode_logprob_options; dec_logprobs.h).  tok_logprob set: the LOGP instantiations (host side:
+  // which kernel is launched).  A row that samples at step i = its n_gen stores the float it adds to sum_logprob in
+  // tok_logprob[row][i] (device [B][sample_len]) and its top_n (id, log-probability) pairs in top_id / top_lp[row][i][0 .. top_n)
+  // (device [B][sample_len][kLogprobMaxTop]; null allowed where top_n == 0).  Rows in the prompt phase and done rows write nothing.
+  // (Appended: no other field moves.)
+  float* tok_logprob; int* top_id; float* top_lp; int top_n;
 };
+constexpr int kLogprobMaxTop = CCX_LOGPROB_MAX_TOP;
 int ccx_launch_dec_select(ccx_ctx* ctx, const DecSelectParams& p, int B, hipStream_t stream);
 
 // Beam search head of a step (dec_beam.hip; openai-whisper decoding.py::BeamSearchDecoder.update restated in tests/beam_reference.py).
@@ -285,6 +292,11 @@ static inline int ccx_check_sampling_options(ccx_ctx* ctx, const char* who, cons
   CCX_REQUIRE(ctx, o->top_k >= 0, "%s: opts.top_k = %d is negative", who, o->top_k);
   CCX_REQUIRE(ctx, o->top_p > 0.f && o->top_p <= 1.f, "%s: opts.top_p = %g must lie in (0, 1]", who, (double)o->top_p);
   CCX_REQUIRE(ctx, o->min_p >= 0.f && o->min_p <= 1.f, "%s: opts.min_p = %g must lie in [0, 1]", who, (double)o->min_p);
+  return CCX_OK;
+}
+// The check of ccx_decode_logprob_options; `who` is the entry point the messages name.
+static inline int ccx_check_logprob_options(ccx_ctx* ctx, const char* who, const ccx_decode_logprob_options* o) {
+  CCX_REQUIRE(ctx, o->top_n >= 0 && o->top_n <= CCX_LOGPROB_MAX_TOP, "%s: opts.top_n = %d out of range [0, %d]", who, o->top_n, CCX_LOGPROB_MAX_TOP);
   return CCX_OK;
 }
 // sample_cfg as the select kernels read it (DecSelectParams::sample_cfg)

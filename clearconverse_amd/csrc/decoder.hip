@@ -1299,13 +1299,16 @@ __device__ __forceinline__ float gumbel_from_u32(unsigned x) {
 
 #include "dec_head_row.h"
 #include "dec_truncate.h"
+#include "dec_logprobs.h"
 // SAMPLE = false is the greedy kernel (no noise code, no extra registers: the sampling branch costs the 1024-thread
 // block its register budget and spills); SAMPLE = true adds the temperature > 0 draw.
 // RULES = false is the decode without ApplyTimestampRules (ccx_decode_options.without_timestamps): its own instantiations, so that
 // the ruled ones keep their code and their registers.
 // TRUNC = true (SAMPLE only) cuts the filtered row by top_k / top_p / min_p before the draw (dec_truncate.h; ccx_decode_sampling_options,
 // the three values behind {temperature, seed} in sample_cfg): again its own instantiations, for the same reason.
-template <bool SAMPLE, bool RULES = true, bool TRUNC = false>
+// LOGP = true (ccx_decode_logprob_options; dec_logprobs.h) stores the log-probability the step adds to sum_logprob and the row's
+// top_n (id, log-probability) pairs: once more its own instantiations of all six, so that the six without it keep their code.
+template <bool SAMPLE, bool RULES = true, bool TRUNC = false, bool LOGP = false>
 __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
   __shared__ float sh[16];
   __shared__ float sh_v[16];
@@ -1412,6 +1415,17 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
     samp_logit = sh[0];
   }
 
+  if constexpr (LOGP) {
+    // the row's top_n out of the registers the draw is done with: the row as sum_logprob sees it (unscaled, untruncated, no noise),
+    // so a forced-timestamp row loses its text ids first where the truncation above has not already taken them
+    if (force_ts && !(TRUNC && temperature > 0.f)) {
+#pragma unroll
+      for (int i = 0; i < kHeadV4 * 4; i++) val[i] = (head_id(tid, i) < tsb) ? -INFINITY : val[i];
+    }
+    const long at = ((long)b * p.sample_len + i_gen) * kLogprobMaxTop;
+    dec_logp::top_rounds(tid, val, p.top_n, mx_all, lnorm, p.top_id + at, p.top_lp + at, sh_v, sh_i);
+  }
+
   if (tid == 0) {
     int next; float logprob;
     if (samp >= 0) {
@@ -1427,6 +1441,7 @@ __global__ __launch_bounds__(1024) void dec_select_kernel(DecSelectParams p) {
     if (!RULES && (unsigned)next >= (unsigned)V) next = p.eot;   // a call whose list suppresses every id: the row ends
     s.sum_logprob += logprob;
     p.gen[(long)b * p.sample_len + i_gen] = next;
+    if constexpr (LOGP) p.tok_logprob[(long)b * p.sample_len + i_gen] = logprob;
     s.n_gen = i_gen + 1;
     s.pen_tok = s.last_tok;
     s.last_tok = next;
@@ -1463,7 +1478,21 @@ int ccx_launch_dec_embed(ccx_ctx* ctx, const float* tok_emb, const float* pos_em
 
 int ccx_launch_dec_select(ccx_ctx* ctx, const DecSelectParams& p, int B, hipStream_t stream) {
   ccx_prof_scope ps(ctx, stream, p.trunc ? (p.no_rules ? "dec_select_kernel (truncated, no rules)" : "dec_select_kernel (truncated)") : p.no_rules ? "dec_select_kernel (no rules)" : "dec_select_kernel", 0.0, (double)B * p.n_vocab * 5.0);     // the logit row + its suppress mask
-  if (p.trunc) {
+  if (p.tok_logprob) {
+    // per-token log-probabilities: the LOGP instantiations of the same six
+    if (p.top_n < 0 || p.top_n > kLogprobMaxTop || (p.top_n > 0 && (!p.top_id || !p.top_lp)))
+      return ccx_fail(ctx, CCX_ERR_ARG, "dec_select: top_n = %d out of range [0, %d], or top_id / top_lp null", p.top_n, kLogprobMaxTop);
+    if (p.trunc && !p.sample) return ccx_fail(ctx, CCX_ERR_ARG, "dec_select: truncation needs the sampling kernel");
+    const dim3 g(B), t(1024);
+    if (p.trunc) {
+      if (p.no_rules) hipLaunchKernelGGL((dec_select_kernel<true, false, true, true>), g, t, 0, stream, p);
+      else hipLaunchKernelGGL((dec_select_kernel<true, true, true, true>), g, t, 0, stream, p);
+    } else if (p.no_rules) {
+      if (p.sample) hipLaunchKernelGGL((dec_select_kernel<true, false, false, true>), g, t, 0, stream, p);
+      else hipLaunchKernelGGL((dec_select_kernel<false, false, false, true>), g, t, 0, stream, p);
+    } else if (p.sample) hipLaunchKernelGGL((dec_select_kernel<true, true, false, true>), g, t, 0, stream, p);
+    else hipLaunchKernelGGL((dec_select_kernel<false, true, false, true>), g, t, 0, stream, p);
+  } else if (p.trunc) {
     // truncated sampling: the instantiations with the top_k / top_p / min_p block (a plan sets it only with sampling on)
     if (!p.sample) return ccx_fail(ctx, CCX_ERR_ARG, "dec_select: truncation needs the sampling kernel");
     if (p.no_rules) hipLaunchKernelGGL((dec_select_kernel<true, false, true>), dim3(B), dim3(1024), 0, stream, p);

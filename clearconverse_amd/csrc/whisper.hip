@@ -86,14 +86,17 @@ struct StepPlan {
   // truncated sampling (ccx_whisper_set_sampling_options; 0 in a default decode): the select kernel's truncating instantiation.  Set
   // only with `sampling`, and only while one of the three values is off its default; the values themselves sit in sample_cfg.
   int trunc_on;
+  // per-token log-probabilities (ccx_whisper_set_logprob_options; 0 in a default decode): 1 + top_n -- the select kernel's LOGP
+  // instantiation, which takes top_n as a launch parameter
+  int logp;
   auto tie() const {
     return std::tie(b0, B, sample_len, max_prompt, select, sampling, cross_stream, cross_lds_pad, xs_active, lnfree, xs_fuse_q, fuse_cross_q,
                     xs_full_lines, packed_act, packed_mid, map_on, sid_on, beam_size, beam_maxc, lane_idx, stamp_level, prefill_rows, opt_mask, no_ts, sup_blank,
-                    max_init_ts, hist_ngram, hist_pen_bits, bias_on, trunc_on, xs_fp8);
+                    max_init_ts, hist_ngram, hist_pen_bits, bias_on, trunc_on, xs_fp8, logp);
   }
   bool operator<(const StepPlan& o) const { return tie() < o.tie(); }
 };
-static_assert(sizeof(StepPlan) == 31 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 31,
+static_assert(sizeof(StepPlan) == 32 * sizeof(int) && std::tuple_size<decltype(StepPlan{}.tie())>::value == 32,
               "StepPlan: ints only, and every one of them in tie()");
 
 }  // namespace
@@ -146,6 +149,13 @@ struct ccx_whisper {
   int* bias_tab = nullptr;
   // the call's truncated sampling (ccx_whisper_set_sampling_options); {0, 1.0, 0.0}: off, the plans and launches of a default decode
   ccx_decode_sampling_options trunc{0, 1.0f, 0.0f};
+  // per-token log-probabilities (ccx_whisper_set_token_logprobs: the buffers, beside gen; ccx_whisper_set_logprob_options: the
+  // call's top_n, -1 = off, the plans and launches of a default decode).  Off: nothing allocated.
+  bool tok_logp = false;
+  float *tok_lp = nullptr, *top_lp = nullptr;   // [max_batch][sample_cap], [max_batch][sample_cap][CCX_LOGPROB_MAX_TOP]
+  int* top_id = nullptr;
+  int logp_n = -1;
+  int logp_R = 0, logp_SL = 0, logp_top = -1;   // the last decode: rows, sample_len and top_n it recorded with (-1: it did not)
 
   // workspaces (encoder)
   float* lm_raw = nullptr; unsigned int* lm_max = nullptr; int *lm_n = nullptr, *lm_seek = nullptr, *lm_seg = nullptr;
@@ -425,6 +435,13 @@ int ccx_whisper_set_cross_fp8(ccx_whisper* w, int on) {
 
 int ccx_whisper_cross_fp8(ccx_whisper* w) { return w && w->cross_fp8 ? 1 : 0; }
 
+int ccx_whisper_set_token_logprobs(ccx_whisper* w, int on) {
+  if (!w) return CCX_ERR_ARG;
+  CCX_REQUIRE(w->ctx, !w->finalized, "whisper: set_token_logprobs after finalize");
+  w->tok_logp = on != 0;
+  return CCX_OK;
+}
+
 int ccx_whisper_set_audio_ctx(ccx_whisper* w, int on) {
   if (!w) return CCX_ERR_ARG;
   CCX_REQUIRE(w->ctx, !w->finalized, "whisper: set_audio_ctx after finalize");
@@ -479,6 +496,7 @@ int ccx_whisper_set_rules(ccx_whisper* w, const ccx_decode_rules* r) {
   w->hist = ccx_decode_history_options{1.0f, 0};
   w->bias_on = false;  // the table's targets were checked against the eot of the rules it was set under
   w->trunc = ccx_decode_sampling_options{0, 1.0f, 0.0f};
+  w->logp_n = -1;
   drop_graphs(w);      // captured step graphs bake the rule ids into the select kernel's parameters
   return CCX_OK;
 }
@@ -561,6 +579,46 @@ int ccx_whisper_sampling_graph_count(ccx_whisper* w) {
   int n = 0;
   for (auto& g : w->graphs) n += g.first.trunc_on ? 1 : 0;
   return n;
+}
+
+int ccx_whisper_set_logprob_options(ccx_whisper* w, const ccx_decode_logprob_options* opts) {
+  if (!w) return CCX_ERR_ARG;
+  ccx_ctx* ctx = w->ctx;
+  CCX_REQUIRE(ctx, w->rules_set, "ccx_whisper_set_logprob_options: the rules are not set (ccx_whisper_set_rules)");
+  if (!opts) { w->logp_n = -1; return CCX_OK; }
+  CCX_REQUIRE(ctx, w->tok_lp != nullptr, "ccx_whisper_set_logprob_options: opts.top_n = %d on an instance without the buffers (ccx_whisper_set_token_logprobs before finalize)", opts->top_n);
+  CCX_TRY(ccx_check_logprob_options(ctx, "ccx_whisper_set_logprob_options", opts));
+  w->logp_n = opts->top_n;       // in the step plan: nothing captured depends on the setting itself
+  return CCX_OK;
+}
+
+int ccx_whisper_logprob_graph_count(ccx_whisper* w) {
+  if (!w) return -1;
+  int n = 0;
+  for (auto& g : w->graphs) n += g.first.logp ? 1 : 0;
+  return n;
+}
+
+int ccx_whisper_token_logprobs(ccx_whisper* w, int R, int sample_len, float* tok_lp_out, int top_n, int32_t* top_id_out, float* top_lp_out,
+                               void* stream_) {
+  if (!w) return CCX_ERR_ARG;
+  ccx_ctx* ctx = w->ctx;
+  if (w->logp_top < 0) return ccx_fail(ctx, CCX_ERR_STATE, "ccx_whisper_token_logprobs: the last decode did not record log-probabilities (ccx_whisper_set_logprob_options)");
+  CCX_REQUIRE(ctx, R == w->logp_R && sample_len == w->logp_SL, "ccx_whisper_token_logprobs: R = %d, sample_len = %d, the last decode had %d rows of %d", R,
+              sample_len, w->logp_R, w->logp_SL);
+  CCX_REQUIRE(ctx, tok_lp_out != nullptr, "ccx_whisper_token_logprobs: tok_lp_out is NULL");
+  CCX_REQUIRE(ctx, top_n >= 0 && top_n <= w->logp_top, "ccx_whisper_token_logprobs: top_n = %d out of range [0, the last decode's %d]", top_n, w->logp_top);
+  CCX_REQUIRE(ctx, top_n == 0 || (top_id_out && top_lp_out), "ccx_whisper_token_logprobs: top_n = %d with top_id_out or top_lp_out NULL", top_n);
+  hipStream_t stream = (hipStream_t)stream_;
+  const size_t n = (size_t)R * sample_len;
+  CCX_HIP(ctx, hipMemcpyAsync(tok_lp_out, w->tok_lp, n * 4, hipMemcpyDeviceToHost, stream));
+  if (top_n > 0) {
+    // the device tables are [row][step][CCX_LOGPROB_MAX_TOP]: the first top_n of every step
+    CCX_HIP(ctx, hipMemcpy2DAsync(top_id_out, (size_t)top_n * 4, w->top_id, (size_t)CCX_LOGPROB_MAX_TOP * 4, (size_t)top_n * 4, n, hipMemcpyDeviceToHost, stream));
+    CCX_HIP(ctx, hipMemcpy2DAsync(top_lp_out, (size_t)top_n * 4, w->top_lp, (size_t)CCX_LOGPROB_MAX_TOP * 4, (size_t)top_n * 4, n, hipMemcpyDeviceToHost, stream));
+  }
+  CCX_HIP(ctx, hipStreamSynchronize(stream));
+  return CCX_OK;
 }
 
 int ccx_whisper_set_bias_options(ccx_whisper* w, const ccx_decode_bias_options* opts) {
@@ -795,6 +853,11 @@ int ccx_whisper_finalize(ccx_whisper* w) {
   w->sample_cap = d.n_text_ctx;
   CCX_TRY(w->store.alloc(&w->prompt, (size_t)B * w->max_prompt_cap, true));
   CCX_TRY(w->store.alloc(&w->gen, (size_t)B * w->sample_cap, true));
+  if (w->tok_logp) {
+    CCX_TRY(w->store.alloc(&w->tok_lp, (size_t)B * w->sample_cap, false));
+    CCX_TRY(w->store.alloc(&w->top_id, (size_t)B * w->sample_cap * CCX_LOGPROB_MAX_TOP, false));
+    CCX_TRY(w->store.alloc(&w->top_lp, (size_t)B * w->sample_cap * CCX_LOGPROB_MAX_TOP, false));
+  }
   // decode streams get the highest priority: when other work shares the GPU (the front end of the next batch on another
   // stream) the short, latency-bound chain kernels should get the next free wave slot.
   int prio_least = 0, prio_greatest = 0;
@@ -1218,6 +1281,10 @@ int dec_head(ccx_whisper* w, const StepPlan& p, const StepIo& io) {
     sp.cur_tok = w->cur_tok + b0; sp.gen = w->gen + ro * p.sample_len; sp.x = w->dx + ro * D;
     sp.sample_cfg = w->sample_cfg; sp.row0 = b0; sp.sample = p.sampling ? 1 : 0;
     sp.trunc = p.trunc_on;
+    if (p.logp) {
+      sp.tok_logprob = w->tok_lp + ro * p.sample_len; sp.top_n = p.logp - 1;
+      sp.top_id = w->top_id + ro * p.sample_len * CCX_LOGPROB_MAX_TOP; sp.top_lp = w->top_lp + ro * p.sample_len * CCX_LOGPROB_MAX_TOP;
+    }
     sp.stream_id = p.sid_on ? w->row_sid + b0 : nullptr;
     CCX_TRY(ccx_launch_dec_select(ctx, sp, B, io.stream));
   }
@@ -1809,8 +1876,13 @@ int ccx_whisper_prepare_lanes(ccx_whisper* w, void* stream_) {
 int ccx_whisper_decode_greedy(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt_lens, int max_prompt, int B,
                               int sample_len, int32_t* tokens_out, int32_t* n_tokens_out, float* sum_logprob_out,
                               float* no_speech_prob_out, void* stream_) {
-  return ccx_whisper_decode(w, prompt_ids, prompt_lens, max_prompt, B, sample_len, 0.f, 0, tokens_out, n_tokens_out, sum_logprob_out,
-                            no_speech_prob_out, stream_);
+  // (the log-probability setting is not this entry point's: off for the call, as it was left behind it)
+  const int logp_n = w ? w->logp_n : -1;
+  if (w) w->logp_n = -1;
+  const int rc = ccx_whisper_decode(w, prompt_ids, prompt_lens, max_prompt, B, sample_len, 0.f, 0, tokens_out, n_tokens_out, sum_logprob_out,
+                                    no_speech_prob_out, stream_);
+  if (w) w->logp_n = logp_n;
+  return rc;
 }
 
 }  // extern "C"
@@ -2224,6 +2296,17 @@ int decode_impl(ccx_whisper* w, const int32_t* prompt_ids, const int32_t* prompt
   base.bias_on = w->bias_on ? 1 : 0;      // no table, set or not, is the default plan
   // truncated sampling: {0, 1.0, 0.0}, set or not, and every decode at temperature 0 (greedy, beam) is the plan it always was
   base.trunc_on = (base.sampling && (w->trunc.top_k != 0 || w->trunc.top_p != 1.0f || w->trunc.min_p != 0.0f)) ? 1 : 0;
+  // per-token log-probabilities: off, set or not, and every beam decode is the plan it always was
+  base.logp = (!beam && w->logp_n >= 0) ? 1 + w->logp_n : 0;
+  w->logp_top = -1;
+  if (base.logp) {
+    // what no sampled step writes reads NaN, -1 and -inf (on `stream`, ahead of the state upload every lane waits for)
+    const size_t n = (size_t)B * sample_len;
+    CCX_HIP(ctx, hipMemsetAsync(w->tok_lp, 0xFF, n * 4, stream));
+    CCX_HIP(ctx, hipMemsetAsync(w->top_id, 0xFF, n * CCX_LOGPROB_MAX_TOP * 4, stream));
+    CCX_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)w->top_lp, (int)0xFF800000u, n * CCX_LOGPROB_MAX_TOP, stream));
+    w->logp_R = B; w->logp_SL = sample_len; w->logp_top = w->logp_n;
+  }
   read_chain_switches(w, base);
   CCX_TRY(select_cross_path(w, base, stream, win ? n_windows : -1));
   if (win) CCX_TRY(upload_row_map(w, win, sids, B, stream));

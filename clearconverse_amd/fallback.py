@@ -104,7 +104,8 @@ def plan_round(failing: Sequence[int], prompts: Sequence[Sequence[int]], n_rows:
 
 def window_result(candidates: Sequence[dict], temperature: float, tokenizer, eot: int, length_penalty: Optional[float] = None) -> dict:
     """What a window keeps of one round's rows [UPSTREAM-RECALL: DecodingTask.run / DecodingResult]: the ranker's pick, avg_logprob =
-    sum_logprob / (n_tokens + 1), no_speech_prob of the group's FIRST row, compression_ratio of the pick's text."""
+    sum_logprob / (n_tokens + 1), no_speech_prob of the group's FIRST row, compression_ratio of the pick's text.  Every other key of
+    the pick comes along as it is: its `token_logprobs` / `top_logprobs` (a decode with logprobs=n) are the picked candidate's."""
     k = rank_candidates(candidates, eot, length_penalty)
     c = candidates[k]
     toks = list(c["tokens"])

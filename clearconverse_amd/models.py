@@ -87,7 +87,8 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
                 resnet_max_chunks: int = 96, whisper_instances: int = 1, share_encoder_scratch: bool = True,
                 gate_max_clips: int = 32, gate_max_seconds: float = 30.0, word_alignment: bool = False,
                 word_probabilities: bool = False, embedding: str = "xvector", denoise: str = "stationary",
-                decoding_options: bool = False, whisper_cross_fp8: bool = False, whisper_audio_ctx=None) -> Dict[str, object]:
+                decoding_options: bool = False, whisper_cross_fp8: bool = False, whisper_audio_ctx=None,
+                whisper_token_logprobs: bool = False) -> Dict[str, object]:
     """embedding: "xvector" (default: `pyannote/embedding`, what the reference loads) or "ecapa" (ECAPA-TDNN, 192-d) for
     `models["embedding_model"]`; the diarization pipeline keeps its ResNet-34 either way.
     denoise: the mode of `models["denoiser"]` -- "stationary" (default: what the reference asks noisereduce for) or "nonstationary"
@@ -95,7 +96,9 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
     whisper_cross_fp8 (default off): every Whisper instance keeps the FP8 image of its encoder output and streams it in the decode's
     cross attention (WhisperModel.__init__ `cross_fp8`; transcript quality on real checkpoints unmeasured).
     whisper_audio_ctx (default None: off): "auto" or an integer builds every Whisper instance for the reduced audio context
-    (WhisperModel.__init__ `audio_ctx`; not upstream's arithmetic, transcript quality on real checkpoints unmeasured)."""
+    (WhisperModel.__init__ `audio_ctx`; not upstream's arithmetic, transcript quality on real checkpoints unmeasured).
+    whisper_token_logprobs (default off): every Whisper instance holds the buffers of the per-token log-probabilities, and its
+    `transcribe` / `decode` take `logprobs=n` (WhisperModel.__init__ `token_logprobs`; parity unpinned)."""
     _check_embedding(embedding)
     _check_denoise(denoise)
     if not torch.cuda.is_available():
@@ -129,6 +132,8 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
         wp["cross_fp8"] = True
     if whisper_audio_ctx is not None:
         wp["audio_ctx"] = whisper_audio_ctx
+    if whisper_token_logprobs:
+        wp["token_logprobs"] = True
     whispers = [WhisperModel(wd, wsd, max_batch=whisper_batch, device=dev_index, ctx=ctx, max_audio_seconds=max_audio_seconds,
                              word_alignment=word_alignment, **wp)]
     for _ in range(1, max(1, int(whisper_instances))):

@@ -63,6 +63,7 @@ class CallSettings(NamedTuple):
     sot_tail: Optional[int] = None
     prefix_len: Optional[int] = None
     sampling: Optional[Tuple[int, float, float]] = None         # (top_k, top_p, min_p)
+    logprobs: Optional[int] = None                              # top_n of the per-token log-probabilities
 
 
 class WhisperModel:
@@ -72,6 +73,7 @@ class WhisperModel:
     repetition_control = False        # and repetition_penalty / no_repeat_ngram_size
     contextual_bias = False           # and sequence_bias / bad_words_ids / hotwords
     truncated_sampling = False        # and top_k / top_p / min_p
+    token_logprobs = False            # and per-token log-probabilities with top-N alternatives (a property of the instance: buffers)
     cross_fp8 = False                 # the FP8 encoder-output stream (a property of the instance; the library's state after finalize)
     audio_ctx = None                  # the reduced audio context: None (off), "auto" or the positions every window keeps
     _staged_frames = None             # content frames of the windows `log_mel` staged last (None: `set_mel`, or nothing staged)
@@ -84,8 +86,17 @@ class WhisperModel:
                  alignment_heads: Optional[Sequence[Sequence[int]]] = None, word_probabilities: bool = False,
                  temperature_fallback: bool = False, beam_search: bool = False, decoding_options: bool = False,
                  repetition_control: bool = False, contextual_bias: bool = False, truncated_sampling: bool = False,
-                 cross_fp8: bool = False, audio_ctx=None):
-        """audio_ctx (default None: the instance allocates nothing more, launches what it always launched and keeps its bits): "auto" or
+                 cross_fp8: bool = False, audio_ctx=None, token_logprobs: bool = False):
+        """token_logprobs (default False: the instance allocates nothing more, launches what it always launched and keeps its bits; a
+        `logprobs` that is not None is then REFUSED with ValueError -- a caller who asks must not silently get nothing): with it, the
+        instance holds three buffers beside its token histories and `decode`, `decode_rows`, `transcribe`, `transcribe_batch` take
+        `logprobs=n`, n an int in [0, 8]: every record (every segment) gains `token_logprobs`, the log-probability of each sampled
+        token under the row the step drew from -- after every filter, not divided by the temperature, not truncated; the eot's entry
+        last when the row ended by eot; their fp32 sum in step order is `sum_logprob`, bit for bit -- and, for n > 0, `top_logprobs`,
+        per step the n most probable allowed (id, logprob) pairs in descending order, the lower id first among equals (the rule is
+        this project's, include/ccx.h ccx_decode_logprob_options; parity unpinned).  Formed inside the select kernel
+        (csrc/dec_logprobs.h); tokens, sum_logprob and no_speech_prob keep their bits.  Not available to beam search.
+        audio_ctx (default None: the instance allocates nothing more, launches what it always launched and keeps its bits): "auto" or
         an integer in [64, n_audio_ctx] builds the instance for a REDUCED AUDIO CONTEXT -- `encode` keeps only the first n encoder
         positions of a window (n = `audio_ctx.positions_for(content frames)` per window under "auto", the integer otherwise), every
         encoder layer attends over those only, and the cross attention of every decode reads those n rows (every decode then takes
@@ -186,6 +197,7 @@ class WhisperModel:
         self.repetition_control = bool(repetition_control)
         self.contextual_bias = bool(contextual_bias)
         self.truncated_sampling = bool(truncated_sampling)
+        self.token_logprobs = bool(token_logprobs)
         if alignment_heads is None:
             alignment_heads = [(l, h) for l in range(dims.n_text_layer // 2, dims.n_text_layer) for h in range(dims.n_text_head)]
         self.alignment_heads = [(int(l), int(h)) for l, h in alignment_heads]
@@ -194,6 +206,8 @@ class WhisperModel:
             self.ctx.check(self.lib.ccx_whisper_set_cross_fp8(self.handle, 1), "ccx_whisper_set_cross_fp8")
         if self.audio_ctx is not None:
             self.ctx.check(self.lib.ccx_whisper_set_audio_ctx(self.handle, 1), "ccx_whisper_set_audio_ctx")
+        if self.token_logprobs:
+            self.ctx.check(self.lib.ccx_whisper_set_token_logprobs(self.handle, 1), "ccx_whisper_set_token_logprobs")
         # log-mel / encoder workspaces of another instance (kept alive here): only for instances whose log_mel / encode calls
         # are ordered on one stream, as in BatchPipeline.run_pinned_pipelined (include/ccx.h)
         self._scratch_donor = share_encoder_scratch_with
@@ -368,13 +382,61 @@ class WhisperModel:
             raise ValueError("top_k / top_p / min_p need a model built with truncated_sampling=True")
         return sampling
 
+    def set_logprob_options(self, top_n: int):
+        """ccx_whisper_set_logprob_options (sticky, like the rules; `set_rules` resets it): record every sampled token's
+        log-probability and its top_n alternatives"""
+        o = _lib.DecodeLogprobOptions(int(top_n))
+        self.ctx.check(self.lib.ccx_whisper_set_logprob_options(self.handle, C.byref(o)), "ccx_whisper_set_logprob_options")
+
+    def reset_logprob_options(self):
+        self.ctx.check(self.lib.ccx_whisper_set_logprob_options(self.handle, None), "ccx_whisper_set_logprob_options")
+
+    def logprob_graph_count(self) -> int:
+        """captured step graphs of log-probability plans (ccx_whisper_logprob_graph_count)"""
+        return int(self.lib.ccx_whisper_logprob_graph_count(self.handle))
+
+    def _logprob_setting(self, logprobs, beam_size=None):
+        """the call's checked top_n; None for None.  Anything else is refused with ValueError: without the opt-in, outside [0, 8],
+        not an int (a bool is not one), or together with beam search."""
+        if logprobs is None:
+            return None
+        if not self.token_logprobs:
+            raise ValueError("logprobs needs a model built with token_logprobs=True")
+        if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or not 0 <= int(logprobs) <= _lib.LOGPROB_MAX_TOP:
+            raise ValueError(f"logprobs = {logprobs!r} must be None or an int in [0, {_lib.LOGPROB_MAX_TOP}]")
+        if beam_size is not None:
+            raise ValueError("logprobs is not available to beam search (beam_size): its rows are rewritten every step")
+        return int(logprobs)
+
+    def _with_logprobs(self, records: List[dict], n: Optional[int], sample_len: int) -> List[dict]:
+        """the records of the decode that just ran, with `token_logprobs` (and, n > 0, `top_logprobs`) of its rows
+        (ccx_whisper_token_logprobs): one entry per sampled step -- the row's tokens, and the eot's where the fetch holds one"""
+        if n is None:
+            return records
+        R = len(records)
+        lp = np.full((R, sample_len), np.nan, dtype=np.float32)
+        tid = np.full((R, sample_len, n), -1, dtype=np.int32)
+        tlp = np.full((R, sample_len, n), -np.inf, dtype=np.float32)
+        self.ctx.check(self.lib.ccx_whisper_token_logprobs(
+            self.handle, R, int(sample_len), lp.ctypes.data_as(C.POINTER(C.c_float)), n,
+            tid.ctypes.data_as(C.POINTER(C.c_int)) if n else None, tlp.ctypes.data_as(C.POINTER(C.c_float)) if n else None,
+            _lib.current_stream_ptr()), "ccx_whisper_token_logprobs")
+        for b, r in enumerate(records):
+            # a row with fewer tokens than sample_len ended by eot, and that step has an entry too
+            steps = min(len(r["tokens"]) + 1, sample_len)
+            r["token_logprobs"] = lp[b, :steps].tolist()
+            if n:
+                r["top_logprobs"] = [[(int(i), float(v)) for i, v in zip(tid[b, t], tlp[b, t]) if i >= 0] for t in range(steps)]
+        return records
+
     def _decode_settings(self, bias_args, repetition_penalty, no_repeat_ngram_size, decoding: dict,
-                         top_k=0, top_p=1.0, min_p=0.0) -> CallSettings:
+                         top_k=0, top_p=1.0, min_p=0.0, logprobs=None) -> CallSettings:
         """What a single decode sets, every refusal made before anything is set: the bias compile (ValueError), the history ranges
         (ValueError), then the decoding keys (TypeError, with or without the opt-in) and `resolve` (CcxError).  **decoding is the
         subset a single decode takes: without_timestamps, suppress_blank, suppress_tokens, max_initial_timestamp."""
         bias = self._bias_setting(*bias_args)
         sampling = self._sampling_setting(top_k, top_p, min_p)
+        logprobs = self._logprob_setting(logprobs, decoding.get("beam_size"))
         history = None
         if repetition_penalty != 1.0 or no_repeat_ngram_size != 0:
             history = self._history_setting(repetition_penalty, no_repeat_ngram_size)
@@ -387,7 +449,7 @@ class WhisperModel:
                 options = decoding_options.resolve(self.rules, **decoding)
             except ValueError as e:
                 raise _lib.CcxError(str(e)) from e
-        return CallSettings(options, history, bias, sampling=sampling)
+        return CallSettings(options, history, bias, sampling=sampling, logprobs=logprobs)
 
     def _transcribe_settings(self, n: int, hallucination_silence_threshold, without_timestamps, prefixes, suppress_blank,
                              suppress_tokens, max_initial_timestamp, sample_len, carry_initial_prompt, repetition_penalty,
@@ -424,7 +486,7 @@ class WhisperModel:
     @contextlib.contextmanager
     def _settings(self, s: CallSettings):
         """The call's settings on the instance while the body runs, for however many decodes: applied once, in one order (options, SOT
-        tail, prefix length, history, bias, sampling), and taken back in reverse -- exactly those that were applied, also when a later setter
+        tail, prefix length, history, bias, sampling, logprobs), and taken back in reverse -- exactly those that were applied, also when a later setter
         or the body raises.  The SOT tail and the prefix length go back to what the instance held before."""
         with contextlib.ExitStack() as undo:
             if s.options is not None:
@@ -449,7 +511,19 @@ class WhisperModel:
             if s.sampling is not None:
                 self.set_sampling_options(*s.sampling)
                 undo.callback(self.reset_sampling_options)
+            if s.logprobs is not None:
+                self.set_logprob_options(s.logprobs)
+                undo.callback(self.reset_logprob_options)
             yield
+
+    @contextlib.contextmanager
+    def _logprobs_of_call(self, n: Optional[int]):
+        """while the body runs, `_call_decode` fetches the lists of every decode (n: the top_n `_settings` has set; None: nothing)"""
+        self._call_logprobs = n
+        try:
+            yield
+        finally:
+            self._call_logprobs = None
 
     def _pack_prompts(self, seqs: Sequence[Sequence[int]]):
         """-> (ids [n, max_len] int32, padded with eot; lens [n] int32; max_len)"""
@@ -590,7 +664,7 @@ class WhisperModel:
     def decode(self, prompts: Sequence[Sequence[int]], sample_len: Optional[int] = None, temperature: float = 0.0,
                seed: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None,
                bad_words_ids=None, hotwords=None, hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
-               **decoding) -> List[dict]:
+               logprobs: Optional[int] = None, **decoding) -> List[dict]:
         """DecodingTask.run over the currently encoded windows; prompts[b] are the full initial tokens
         (sot_prev + prompt + sot).  temperature 0: argmax.  temperature > 0: one Categorical(logits / T) sample per
         step (decoding.py::GreedyDecoder.update), drawn on the device from Philox noise keyed by
@@ -603,10 +677,12 @@ class WhisperModel:
         sequence_bias / bad_words_ids / hotwords / hotword_boost (contextual_bias instances; ignored otherwise): this call's bias
         table, which a step adds before the history rules.
         top_k / top_p / min_p (truncated_sampling instances; a non-default value raises ValueError otherwise): this call's cut of the
-        distribution a temperature > 0 step draws from; without effect at temperature 0.  All of them are resolved first (`_decode_settings`: a refused call sets
+        distribution a temperature > 0 step draws from; without effect at temperature 0.
+        logprobs (token_logprobs instances; not None raises ValueError otherwise, as does a value that is no int in [0, 8]): every
+        record gains `token_logprobs` and, for n > 0, `top_logprobs` (see the constructor).  All of them are resolved first (`_decode_settings`: a refused call sets
         nothing) and hold for this call alone (`_settings`)."""
         settings = self._decode_settings((sequence_bias, bad_words_ids, hotwords, hotword_boost), repetition_penalty,
-                                         no_repeat_ngram_size, decoding, top_k, top_p, min_p)
+                                         no_repeat_ngram_size, decoding, top_k, top_p, min_p, logprobs)
         if not (temperature >= 0.0):
             raise _lib.CcxError("temperature must be >= 0")
         B = len(prompts)
@@ -622,20 +698,20 @@ class WhisperModel:
                 self.handle, ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), mp, B, sample_len, float(temperature),
                 int(seed) & 0xFFFFFFFFFFFFFFFF, toks.ctypes.data_as(i32p), ntok.ctypes.data_as(i32p), slp.ctypes.data_as(fp),
                 nsp.ctypes.data_as(fp), _lib.current_stream_ptr()), "ccx_whisper_decode")
-            return self._records(toks, ntok, slp, nsp)
+            return self._with_logprobs(self._records(toks, ntok, slp, nsp), settings.logprobs, sample_len)
 
     def decode_rows(self, prompts: Sequence[Sequence[int]], windows: Sequence[int], stream_ids: Optional[Sequence[int]] = None,
                     sample_len: Optional[int] = None, temperature: float = 0.0, seed: int = 0, n_windows: Optional[int] = None,
                     repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None,
                     hotwords=None, hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
-                    **decoding) -> List[dict]:
+                    logprobs: Optional[int] = None, **decoding) -> List[dict]:
         """`decode` for len(prompts) <= max_batch rows over the currently encoded windows (ccx_whisper_decode_rows): row r decodes
         window windows[r] -- entries may repeat (best_of), need not be monotone, and windows may go unused (a fallback round decodes
         only the failing ones).  stream_ids[r]: the row's noise stream at temperature > 0 (None: r), so that its draws do not depend on
         the rows it shares the call with.  n_windows: how many windows are encoded (default: max(windows) + 1).  repetition_penalty,
-        no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost, top_k, top_p, min_p, **decoding: as `decode`."""
+        no_repeat_ngram_size, sequence_bias, bad_words_ids, hotwords, hotword_boost, top_k, top_p, min_p, logprobs, **decoding: as `decode`."""
         settings = self._decode_settings((sequence_bias, bad_words_ids, hotwords, hotword_boost), repetition_penalty,
-                                         no_repeat_ngram_size, decoding, top_k, top_p, min_p)
+                                         no_repeat_ngram_size, decoding, top_k, top_p, min_p, logprobs)
         if not (temperature >= 0.0):
             raise _lib.CcxError("temperature must be >= 0")
         R = len(prompts)
@@ -657,7 +733,7 @@ class WhisperModel:
                 sid.ctypes.data_as(i32p) if sid is not None else None, sample_len, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
                 toks.ctypes.data_as(i32p), ntok.ctypes.data_as(i32p), slp.ctypes.data_as(fp), nsp.ctypes.data_as(fp),
                 _lib.current_stream_ptr()), "ccx_whisper_decode_rows")
-            return self._records(toks, ntok, slp, nsp)
+            return self._with_logprobs(self._records(toks, ntok, slp, nsp), settings.logprobs, sample_len)
 
     def decode_beam(self, prompts: Sequence[Sequence[int]], beam_size: int, patience: Optional[float] = None,
                     sample_len: Optional[int] = None, windows: Optional[Sequence[int]] = None, n_windows: Optional[int] = None,
@@ -710,6 +786,17 @@ class WhisperModel:
         out = [rows[g * Cn:g * Cn + int(nhyp[g])] for g in range(G)]
         return (out, tr) if trace else out
 
+    _call_logprobs: Optional[int] = None      # the top_n the running `transcribe_batch` has set (`_settings`); None: not set
+
+    def _call_decode(self, prompts, cap, temperature, seed, windows=None, stream_ids=None, n_windows=None) -> List[dict]:
+        """A decode inside `transcribe_batch`: `decode` (windows None) or `decode_rows` under the call's settings, which are set
+        already -- so nothing is passed again; only the lists of a call with logprobs are fetched behind it."""
+        if windows is None:
+            rows = self.decode(prompts, sample_len=cap, temperature=temperature, seed=seed)
+        else:
+            rows = self.decode_rows(prompts, windows, stream_ids, sample_len=cap, temperature=temperature, seed=seed, n_windows=n_windows)
+        return self._with_logprobs(rows, self._call_logprobs, cap)
+
     def _decode_with_fallback(self, prompts, cap: int, schedule, best_of, compression_ratio_threshold, logprob_threshold,
                               no_speech_threshold, beam_size=None, patience=None, length_penalty=None) -> List[dict]:
         """The schedule walk of one encoded group [UPSTREAM-RECALL: transcribe.py::decode_with_fallback]: round 0 over every window,
@@ -741,12 +828,11 @@ class WhisperModel:
                     for w, h in zip(part, hyps):
                         cands[w] = h
             elif walk.round == 0 and n_rows == 1:
-                for w, r in enumerate(self.decode(prompts, sample_len=cap, temperature=t, seed=seed)):
+                for w, r in enumerate(self._call_decode(prompts, cap, t, seed)):
                     cands[w].append(r)
             else:
                 for ch in fallback.plan_round(failing, prompts, n_rows, self.max_batch):
-                    rows = self.decode_rows(ch["prompts"], ch["windows"], ch["stream_ids"], sample_len=cap, temperature=t, seed=seed,
-                                            n_windows=len(prompts))
+                    rows = self._call_decode(ch["prompts"], cap, t, seed, ch["windows"], ch["stream_ids"], len(prompts))
                     for (w, _), r in zip(ch["owners"], rows):
                         cands[w].append(r)
             walk.submit({w: fallback.window_result(cands[w], t, self.tokenizer, eot, length_penalty) for w in failing})
@@ -888,7 +974,7 @@ class WhisperModel:
                    sample_len: Optional[int] = None, clip_timestamps="0", carry_initial_prompt: bool = False,
                    repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None,
                    hotwords=None, hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, audio_ctx=None,
-                   **_ignored):
+                   logprobs: Optional[int] = None, **_ignored):
         """One clip, same signature as whisper.transcribe as the reference uses it.  temperature 0 is the
         parity mode (greedy); a positive float (the reference's Config.temperature = 0.1,
         back/api.py:128) samples every token from Categorical(logits / T) -- a single temperature means no
@@ -916,6 +1002,8 @@ class WhisperModel:
         `transcribe_batch`); otherwise they are accepted and ignored.
         On an instance built with `truncated_sampling=True`: top_k, top_p and min_p are honoured (see `transcribe_batch`); otherwise
         a value off its default raises ValueError.
+        On an instance built with `token_logprobs=True`: logprobs=n gives every segment `token_logprobs` (and `top_logprobs` for
+        n > 0; see `transcribe_batch`); otherwise anything but None raises ValueError.
         On an instance built with `audio_ctx`: audio_ctx overrides the instance's setting for this call ("full", "auto" or an int;
         see `transcribe_batch`), and the result carries `audio_ctx`; otherwise anything but None / "full" raises ValueError."""
         return self.transcribe_batch([audio], [initial_prompt], condition_on_previous_text=condition_on_previous_text,
@@ -930,7 +1018,8 @@ class WhisperModel:
                                      clip_timestamps=clip_timestamps, carry_initial_prompt=carry_initial_prompt,
                                      repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                                      sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotwords=hotwords,
-                                     hotword_boost=hotword_boost, top_k=top_k, top_p=top_p, min_p=min_p, audio_ctx=audio_ctx)[0]
+                                     hotword_boost=hotword_boost, top_k=top_k, top_p=top_p, min_p=min_p, audio_ctx=audio_ctx,
+                                     logprobs=logprobs)[0]
 
     def transcribe_batch(self, audios: Sequence, initial_prompts: Optional[Sequence[Optional[str]]] = None,
                          condition_on_previous_text: bool = True, temperature: float = 0.0,
@@ -944,7 +1033,8 @@ class WhisperModel:
                          max_initial_timestamp: Optional[float] = 1.0, sample_len: Optional[int] = None, clip_timestamps="0",
                          carry_initial_prompt: bool = False, repetition_penalty: float = 1.0,
                          no_repeat_ngram_size: int = 0, sequence_bias=None, bad_words_ids=None, hotwords=None,
-                         hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, audio_ctx=None) -> List[dict]:
+                         hotword_boost=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, audio_ctx=None,
+                         logprobs: Optional[int] = None) -> List[dict]:
         """Independent clips decoded together (each window of each clip is one sequence of a batch).
         languages[i] (multilingual models): the clip's language code or name; None: detected on the clip's first window, after its
         group's `encode` and before its `decode` [UPSTREAM-RECALL: transcribe.py, `if decode_options.get("language") is None`].
@@ -994,7 +1084,13 @@ class WhisperModel:
         audio_ctx instances (the reduced audio context, WhisperModel.__init__; not upstream's arithmetic, quality unmeasured): every
         window is encoded with the instance's setting, or with this call's audio_ctx -- "full" (all n_audio_ctx positions: the tokens of
         an instance without the opt-in), "auto" or an int; every result carries `audio_ctx`, the context of each of the clip's
-        windows, in order.  Without the opt-in anything but None / "full" raises ValueError."""
+        windows, in order.  Without the opt-in anything but None / "full" raises ValueError.
+        token_logprobs instances: logprobs=n (an int in [0, 8]) holds for every decode of the call (one
+        ccx_whisper_set_logprob_options per call, off again when it returns): every segment carries `token_logprobs` and, n > 0,
+        `top_logprobs`, the slices of its window's lists over the index range its `tokens` are cut with (a segment whose tokens are
+        cleared gets empty lists); on a fallback walk or best_of they are the accepted candidate's.  None (the default): the result
+        and its segments are what they always were.  Anything but None without the opt-in, a value that is no int in [0, 8], and
+        logprobs together with beam_size on a beam_search instance raise ValueError before anything runs."""
         n = len(audios)
         if audio_ctx is not None:       # refuse before anything runs
             self._window_contexts(0, audio_ctx)
@@ -1005,6 +1101,7 @@ class WhisperModel:
             hotword_boost, top_k, top_p, min_p)
         schedule, walk_on, best_of, beam_size, patience, length_penalty = self._walk_options(temperature, best_of, beam_size, patience,
                                                                                             length_penalty)
+        settings = settings._replace(logprobs=self._logprob_setting(logprobs, beam_size))
         with_words = bool(word_timestamps) and self.word_alignment
         self.fallback_walks: List[fallback.FallbackWalk] = []     # this call's walks, one per encoded group, in order
         initial_prompts = list(initial_prompts) if initial_prompts is not None else [None] * n
@@ -1028,7 +1125,7 @@ class WhisperModel:
                             condition_on_previous_text, no_speech_threshold, logprob_threshold,
                             language=languages[i] if multi else "en", task=task, **loop_options(i)) for i in range(n)]
         # one set per family for every window, group and round of the call; the instance's own values are back when it returns
-        with self._settings(settings):
+        with self._settings(settings), self._logprobs_of_call(settings.logprobs):
             while True:
                 active = [i for i in range(n) if state[i].active()]
                 if not active:
@@ -1065,8 +1162,7 @@ class WhisperModel:
                         temps = [r["temperature"] for r in results]     # what each window was accepted at
                     else:
                         self._sample_calls += 1
-                        results = self.decode(prompts, sample_len=cap, temperature=schedule[0],
-                                              seed=(int(self.sample_seed) << 32) + self._sample_calls)
+                        results = self._call_decode(prompts, cap, schedule[0], (int(self.sample_seed) << 32) + self._sample_calls)
                         temps = [schedule[0]] * len(grp)
                     n_seg = [len(state[i].segments) for i in grp]
                     if with_words:     # before the next log_mel: the group's windows are still encoded, aligned as one batch

@@ -191,7 +191,10 @@ class WindowLoop:
 
     def window_segments(self, r: dict):
         """The segments one decoded window yields, before empty ones are cleared: (segments, single_timestamp_ending, next seek by the
-        timestamp-token rule), or None when the silence rule skips the window.  Changes nothing."""
+        timestamp-token rule), or None when the silence rule skips the window.  Changes nothing.
+        A result that carries `token_logprobs` (and `top_logprobs`; WhisperModel(token_logprobs=True), logprobs=n) hands every
+        segment the slice of those lists over the index range its `tokens` are cut with; one without them yields segments without
+        the keys."""
         tsb, eot = self.rules.timestamp_begin, self.rules.eot
         seek = self.seek
         segment_size = self.segment_size()
@@ -209,9 +212,13 @@ class WindowLoop:
         consecutive = [i + 1 for i in range(len(tokens) - 1) if is_ts[i] and is_ts[i + 1]]
         new_segments = []
 
-        def add(start, end, toks):
+        def add(start, end, lo, hi):
+            toks = tokens[lo:hi]
             new_segments.append(dict(seek=seek, start=start, end=end, tokens=list(toks),
                                      text=self.tokenizer.decode([t for t in toks if t < eot])))
+            for key in ("token_logprobs", "top_logprobs"):
+                if key in r:
+                    new_segments[-1][key] = list(r[key][lo:hi])
 
         if consecutive:
             slices = list(consecutive)
@@ -220,7 +227,7 @@ class WindowLoop:
             last = 0
             for cur in slices:
                 sl = tokens[last:cur]
-                add(time_offset + (sl[0] - tsb) * TIME_PRECISION, time_offset + (sl[-1] - tsb) * TIME_PRECISION, sl)
+                add(time_offset + (sl[0] - tsb) * TIME_PRECISION, time_offset + (sl[-1] - tsb) * TIME_PRECISION, last, cur)
                 last = cur
             if single_ts_ending:
                 next_seek = seek + segment_size
@@ -231,7 +238,7 @@ class WindowLoop:
             ts = [t for t in tokens if t >= tsb]
             if ts and ts[-1] != tsb:
                 duration = (ts[-1] - tsb) * TIME_PRECISION
-            add(time_offset, time_offset + duration, tokens)
+            add(time_offset, time_offset + duration, 0, len(tokens))
             next_seek = seek + segment_size
         return new_segments, single_ts_ending, next_seek
 
@@ -308,6 +315,9 @@ class WindowLoop:
             # "if a segment is instantaneous or does not contain text, clear it": its tokens do not reach the prompt or the text
             if s["start"] == s["end"] or s["text"].strip() == "":
                 s["text"], s["tokens"] = "", []
+                for key in ("token_logprobs", "top_logprobs"):
+                    if key in s:
+                        s[key] = []
             self.segments.append(s)
             self.all_tokens.extend(s["tokens"])
         if not self.condition or temperature > 0.5:      # "do not feed the prompt tokens if a high temperature was used"

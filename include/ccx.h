@@ -390,6 +390,49 @@ int ccx_whisper_set_sampling_options(ccx_whisper* w, const ccx_decode_sampling_o
 /* Captured step graphs of truncation plans the instance holds (a test aid, like ccx_whisper_history_graph_count); -1 for a NULL handle. */
 int ccx_whisper_sampling_graph_count(ccx_whisper* w);
 
+/* Per-token log-probabilities and top-N alternatives (opt-in: ccx_whisper_set_token_logprobs before finalize, then
+ * ccx_whisper_set_logprob_options per call; the rule is ours, parity unpinned; restated in tests/logprobs_reference.py).
+ * Take a row that samples at this step (not in its prompt phase, not done).  x = its logit row as the step draws from it: after the
+ * bias kernel, the history kernel, the suppress mask of the rules or the call's options, SuppressBlank, ApplyTimestampRules on ruled
+ * plans, and the removal of the text ids when the summed timestamp mass beats the best text token.  x is NOT divided by the
+ * temperature, NOT truncated by top_k / top_p / min_p, and carries no noise: it is the row sum_logprob is defined over.
+ * A = {v : x_v > -inf}; lp_v = (x_v - mx_all) - lnorm in fp32, mx_all the maximum over A and lnorm = log sum_A exp(x - mx_all), as the
+ * select kernel forms the chosen token's value (csrc/dec_head_row.h).
+ *   token_logprob[step] is the float the kernel adds to sum_logprob at that step, bit for bit (whatever that is for a row with A
+ *     empty).  One entry per sampled step; the step that samples eot has one; a finished row writes none.
+ *   top[step][k], k < top_n, is (id, lp_id) of the top_n largest x_v over A in descending order; of equal values the lower id comes
+ *     first (torch.argmax on the CPU); where |A| < top_n the rest is (-1, -inf).
+ *   top_n lies in [0, CCX_LOGPROB_MAX_TOP]; 0 gives the chosen token's log-probability only.
+ * So: at temperature 0 top[step][0] is the chosen token and its lp equals token_logprob[step] bit for bit; whenever the chosen id is
+ * listed its lp there equals token_logprob[step] bit for bit; and the fp32 sum of a row's token_logprob entries, added in step order
+ * from 0.0f, equals the returned sum_logprob bit for bit.
+ * ccx_whisper_set_token_logprobs(w, 1) (before finalize) makes finalize allocate the three buffers beside the token histories:
+ * [max_batch][n_text_ctx] floats and [max_batch][n_text_ctx][8] ids and floats; without it nothing more is allocated.
+ * ccx_whisper_set_logprob_options is sticky like ccx_whisper_set_sampling_options (NULL: off), needs the rules, is reset by
+ * ccx_whisper_set_rules, and is refused with CCX_ERR_ARG (1) naming "ccx_whisper_set_logprob_options" and the field when the instance
+ * lacks the buffers or top_n lies outside [0, 8].  WHERE top_n LIVES: in the step plan -- its one new field is 0 with the setting
+ * off and 1 + top_n with it on -- so the select kernel gets top_n as a launch parameter and a first decode with another top_n
+ * captures exactly ONE more step graph per lane plan (ccx_whisper_logprob_graph_count); with the setting off, set or not, a decode
+ * takes the plan, the launches and the graphs it always took.  The buffers keep their addresses and a row's step index is its own
+ * state, so the captured graphs stay valid across decodes.
+ * ccx_whisper_decode and _decode_rows honour the setting at any temperature, on every cross-attention path and in every lane;
+ * ccx_whisper_decode_greedy and _decode_beam ignore it (a beam's rows are rewritten by parent every step).
+ * ccx_whisper_token_logprobs copies the values of the LAST decode to host arrays: tok_lp_out [R][sample_len], and, top_n > 0,
+ * top_id_out / top_lp_out [R][sample_len][top_n] (top_n <= the decode's; NULL with top_n == 0).  R and sample_len are the decode's.
+ * Entries at or beyond a row's sampled steps are NaN, -1 and -inf: the library fills the buffers when a recording decode starts.
+ * Refused (CCX_ERR_STATE) when the last decode did not record them. */
+#define CCX_LOGPROB_MAX_TOP 8
+typedef struct ccx_decode_logprob_options {
+  int top_n;
+} ccx_decode_logprob_options;
+int ccx_whisper_set_token_logprobs(ccx_whisper* w, int on);
+int ccx_whisper_set_logprob_options(ccx_whisper* w, const ccx_decode_logprob_options* opts);
+int ccx_whisper_token_logprobs(ccx_whisper* w, int R, int sample_len, float* tok_lp_out, int top_n, int32_t* top_id_out, float* top_lp_out,
+                               void* stream);
+/* Captured step graphs of log-probability plans the instance holds (a test aid, like ccx_whisper_history_graph_count); -1 for a NULL
+ * handle. */
+int ccx_whisper_logprob_graph_count(ccx_whisper* w);
+
 /* Log-mel of B clips (whisper.audio.log_mel_spectrogram + pad_or_trim to 3000 frames).
  * audio_dev: [B, stride] f32; n_samples / seek_frames: host int arrays (seek may be NULL = 0).
  * Fills the model's conv-stem input; if mel_out_dev != NULL also writes [B, n_mels, 3000] f32. */
@@ -559,6 +602,12 @@ typedef struct ccx_dec_select_desc {
    * kept logit (-inf for a row with nothing allowed), |K|, and the mass of K under softmax(x / T).  They need `sampling`. */
   const ccx_decode_sampling_options* sampling;
   float* cut_out; int* kept_out; float* kept_mass_out;
+  /* per-token log-probabilities (appended: nothing before it moves).  logprobs != NULL launches the LOGP instantiation (top_n checked
+   * as ccx_whisper_set_logprob_options checks it).  HOST outputs, in and out, written only for rows that sampled in this launch:
+   * tok_logprob_out [B] (required), top_id_out / top_lp_out [B][top_n] (required when top_n > 0, not read when it is 0).  The
+   * outputs need `logprobs`. */
+  const ccx_decode_logprob_options* logprobs;
+  float* tok_logprob_out; int* top_id_out; float* top_lp_out;
 } ccx_dec_select_desc;
 
 /* One launch of the select kernel (ccx_launch_dec_select) for B rows: filters, argmax / sampling, the per-sequence state machine and
