@@ -237,7 +237,7 @@ class SepDesc(C.Structure):
         + [(n, C.c_int64) for n in ("ln_elems", "gln_elems", "wqkv_elems", "bqkv_elems", "wo_elems", "bo_elems", "w1_elems",
                                     "b1_elems", "w2_elems", "b2_elems", "wdec_elems")]
         + [("utt_tok0", C.POINTER(C.c_int)), ("utt_L", C.POINTER(C.c_int)), ("utt_T", C.POINTER(C.c_int)), ("n_utt", C.c_int),
-           ("segment", C.c_int), ("out", C.c_void_p), ("out_stride", C.c_int64), ("out_elems", C.c_int64)])
+           ("segment", C.c_int), ("out", C.c_void_p), ("out_stride", C.c_int64), ("out_elems", C.c_int64), ("n_spk", C.c_int)])
 
 
 SEP_ATTN_BLOCK, SEP_ATTENTION, SEP_FFN, SEP_FINAL_NORM, SEP_DECODER = range(5)

@@ -40,6 +40,11 @@ class BatchPipeline:
             if getattr(w.rules, "is_multilingual", False):
                 raise _lib.CcxError("BatchPipeline drives English-only Whisper checkpoints (.en): a multilingual model needs "
                                     "WhisperModel.transcribe / transcribe_batch (language detection, task token, sample cap)")
+        # the pinned schedule and its records are two-source (two embeddings and two similarities per overlap region)
+        n_spk = int(getattr(models.get("separator"), "n_spk", 2))
+        if n_spk != 2:
+            raise ValueError(f"BatchPipeline drives a two-source separator, this one returns {n_spk} sources: "
+                             "use EnhancedAudioProcessor(all_overlap_sources=True) for an N-source model")
         self.stage_ms: Dict[str, float] = {}
 
     # ------------------------------------------------------------------ helpers

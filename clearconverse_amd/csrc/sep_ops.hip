@@ -59,6 +59,8 @@ extern "C" int ccx_sep_op(ccx_ctx* ctx, int op, const ccx_sep_desc* d, void* str
     }
   }
   const int64_t tok128 = (int64_t)rows * 128;
+  CCX_REQUIRE(ctx, op != CCX_SEP_DECODER || (d->n_spk >= 0 && d->n_spk <= 4), "ccx_sep_op: n_spk = %d out of range [1, 4] (0 means 2)", d->n_spk);
+  const int n_spk = d->n_spk == 0 ? 2 : d->n_spk;      // op 4 only
   switch (op) {
     case CCX_SEP_ATTN_BLOCK:
       SEP_BUF(h, tok128);
@@ -100,9 +102,9 @@ extern "C" int ccx_sep_op(ccx_ctx* ctx, int op, const ccx_sep_desc* d, void* str
                     rows);
       }
       SEP_BUF(feats, tok128);
-      SEP_BUF(fc, (int64_t)rows * 256);
+      SEP_BUF(fc, (int64_t)rows * 128 * n_spk);
       SEP_PARAM(wdec, wdec_elems, 128 * 16);
-      SEP_BUF(out, (int64_t)d->n_utt * d->out_stride * 2);
+      SEP_BUF(out, (int64_t)d->n_utt * d->out_stride * n_spk);
     }
   }
 
@@ -135,7 +137,7 @@ extern "C" int ccx_sep_op(ccx_ctx* ctx, int op, const ccx_sep_desc* d, void* str
       break;
     default:
       rc = ccx_launch_sep_decoder(ctx, (const float*)d->feats, (const float*)d->fc, d_a, d_b, d_c, (const float*)d->wdec, (float*)d->out,
-                                  (long)d->out_stride, d->n_utt, st);
+                                  (long)d->out_stride, d->n_utt, n_spk, st);
   }
   SEP_HIP(hipStreamSynchronize(st));      // the scratch is freed on return
   return rc;

@@ -23,6 +23,8 @@ int ccx_launch_sep_ffn(ccx_ctx* ctx, float* h, const float* ln_g, const float* l
 // y = gLN(LayerNorm(h)) + xin per sequence (statistics over len x 128)
 int ccx_launch_sep_final_norm(ccx_ctx* ctx, const float* h, const float* xin, const int* seq_start, const int* seq_len, int n_seq,
                               const float* ln_g, const float* ln_b, const float* gln_g, const float* gln_b, float* y, hipStream_t st);
-// out [n_utt][out_stride][2] f32: mask * features, transposed convolution, trimmed / zero-padded to utt_T
+// out [n_utt][out_stride][n_spk] f32 from fc [rows][128 n_spk] (channel-major, source-minor): mask * features, transposed
+// convolution, trimmed / zero-padded to utt_T.  n_spk in [1, 4] (one instantiation each; anything else is CCX_ERR_ARG); out needs
+// no more than float alignment
 int ccx_launch_sep_decoder(ccx_ctx* ctx, const float* feats, const float* fc, const int* utt_tok0, const int* utt_L, const int* utt_T,
-                           const float* wdec, float* out, long out_stride, int n_utt, hipStream_t st);
+                           const float* wdec, float* out, long out_stride, int n_utt, int n_spk, hipStream_t st);

@@ -654,12 +654,16 @@ __global__ void sep_prelu_bf16_kernel(const float* __restrict__ x, const float* 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Mask (ReLU) * encoder output, ConvTranspose1d(128 -> 1, k16, s8) overlap-add, pad/trim to T:
-//   est[u][t][spk] = sum_{l in {t/8, t/8-1}} sum_c feats[l][c] * relu(fc[l][2c+spk]) * wdec[c][t-8l]
-// One wave per group of 8 output samples t = 8 l .. 8 l + 7 (both speakers): they all need exactly the token rows l (taps 0..7)
+// Mask (ReLU) * encoder output, ConvTranspose1d(128 -> 1, k16, s8) overlap-add, pad/trim to T, for NSPK sources:
+//   est[u][t][spk] = sum_{l in {t/8, t/8-1}} sum_c feats[l][c] * relu(fc[l][c*NSPK+spk]) * wdec[c][t-8l]
+// One wave per group of 8 output samples t = 8 l .. 8 l + 7 (all sources): they all need exactly the token rows l (taps 0..7)
 // and l - 1 (taps 8..15), which are read ONCE per wave -- with a wave per sample every 1.5 KB token row came out of L2
 // sixteen times (18 GB per pipeline step, the whole 5.2 ms of the kernel).  Lanes split the 128 channels.
+// A lane's 2 NSPK mask values start at byte 8 NSPK lane of the row: 16-byte pieces for an even NSPK, 8-byte pieces otherwise.  The
+// group's 8 NSPK results leave as one float per lane (lane = k NSPK + spk): utterance u starts at float u out_stride NSPK, which
+// for an odd out_stride is aligned to 4 bytes and no more.
 // ---------------------------------------------------------------------------------------------
+template <int NSPK>
 __global__ __launch_bounds__(256) void sep_decoder_kernel(const float* __restrict__ feats, const float* __restrict__ fc,
                                                           const int* __restrict__ utt_tok0, const int* __restrict__ utt_L,
                                                           const int* __restrict__ utt_T, const float* __restrict__ wdec,  // [128][16]
@@ -669,23 +673,37 @@ __global__ __launch_bounds__(256) void sep_decoder_kernel(const float* __restric
   const int T = utt_T[u], L = utt_L[u];
   const long t0 = 8L * l;
   if (t0 >= out_stride) return;
-  float2* dst = (float2*)(out + ((long)u * out_stride + t0) * 2);
+  float* dst = out + ((long)u * out_stride + t0) * NSPK;
+  const long t_mine = t0 + lane / NSPK;                                           // the sample this lane stores
+  const bool mine = lane < 8 * NSPK && t_mine < out_stride;
   if (t0 >= T || l > L) {  // rows past the utterance are zero (separate_batch pads / trims to T)
-    if (lane < 8 && t0 + lane < out_stride) dst[lane] = make_float2(0.f, 0.f);
+    if (mine) dst[lane] = 0.f;
     return;
   }
   // g[token][spk][channel of the lane]: feats * relu(mask); token 0 = l (taps k), token 1 = l - 1 (taps k + 8)
-  float g[2][2][2];
+  float g[2][NSPK][2];
 #pragma unroll
   for (int dl = 0; dl < 2; dl++) {
     const int ll = l - dl;
     const bool ok = ll >= 0 && ll < L;
     const long tok = utt_tok0[u] + (ok ? ll : 0);
     const float2 f = ((const float2*)(feats + tok * 128))[lane];          // channels 2*lane, 2*lane+1
-    const float4 m = ((const float4*)(fc + tok * 256))[lane];             // (c0,s0) (c0,s1) (c1,s0) (c1,s1)
+    const float* mrow = fc + tok * (128 * NSPK) + 2 * NSPK * lane;        // (c0,s0) .. (c0,s[NSPK-1]) (c1,s0) .. (c1,s[NSPK-1])
+    float2 mv[NSPK];
+    if constexpr (NSPK % 2 == 0) {
+#pragma unroll
+      for (int i = 0; i < NSPK / 2; i++) ((float4*)mv)[i] = ((const float4*)mrow)[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < NSPK; i++) mv[i] = ((const float2*)mrow)[i];
+    }
+    const float* m = (const float*)mv;
     const float z = ok ? 1.f : 0.f;
-    g[dl][0][0] = z * f.x * fmaxf(m.x, 0.f); g[dl][0][1] = z * f.y * fmaxf(m.z, 0.f);
-    g[dl][1][0] = z * f.x * fmaxf(m.y, 0.f); g[dl][1][1] = z * f.y * fmaxf(m.w, 0.f);
+#pragma unroll
+    for (int s = 0; s < NSPK; s++) {
+      g[dl][s][0] = z * f.x * fmaxf(m[s], 0.f);
+      g[dl][s][1] = z * f.y * fmaxf(m[NSPK + s], 0.f);
+    }
   }
   float4 w0[4], w1[4];                                                    // wdec rows of channels 2 lane, 2 lane + 1: 16 taps each
 #pragma unroll
@@ -695,18 +713,18 @@ __global__ __launch_bounds__(256) void sep_decoder_kernel(const float* __restric
   }
   const float* w0f = (const float*)w0;
   const float* w1f = (const float*)w1;
-  float2 res = make_float2(0.f, 0.f);
+  float res = 0.f;
 #pragma unroll
   for (int k = 0; k < 8; k++) {
-    float a0 = g[0][0][0] * w0f[k] + g[0][0][1] * w1f[k];
-    float a1 = g[0][1][0] * w0f[k] + g[0][1][1] * w1f[k];
-    a0 += g[1][0][0] * w0f[k + 8] + g[1][0][1] * w1f[k + 8];
-    a1 += g[1][1][0] * w0f[k + 8] + g[1][1][1] * w1f[k + 8];
-    a0 = wave_reduce_sum(a0);
-    a1 = wave_reduce_sum(a1);
-    if (lane == k) res = make_float2(a0, a1);
+#pragma unroll
+    for (int s = 0; s < NSPK; s++) {
+      float a = g[0][s][0] * w0f[k] + g[0][s][1] * w1f[k];
+      a += g[1][s][0] * w0f[k + 8] + g[1][s][1] * w1f[k + 8];
+      a = wave_reduce_sum(a);
+      if (lane == k * NSPK + s) res = a;
+    }
   }
-  if (lane < 8 && t0 + lane < out_stride) dst[lane] = (t0 + lane < T) ? res : make_float2(0.f, 0.f);
+  if (mine) dst[lane] = (t_mine < T) ? res : 0.f;
 }
 
 struct SepLayer {
@@ -771,9 +789,17 @@ int ccx_launch_sep_final_norm(ccx_ctx* ctx, const float* h, const float* xin, co
 }
 
 int ccx_launch_sep_decoder(ccx_ctx* ctx, const float* feats, const float* fc, const int* utt_tok0, const int* utt_L, const int* utt_T,
-                           const float* wdec, float* out, long out_stride, int n_utt, hipStream_t st) {
-  hipLaunchKernelGGL(sep_decoder_kernel, dim3(ccx_cdiv(ccx_cdiv((int)out_stride, 8), 4), n_utt), dim3(256), 0, st, feats, fc, utt_tok0, utt_L,
-                     utt_T, wdec, out, out_stride, n_utt);
+                           const float* wdec, float* out, long out_stride, int n_utt, int n_spk, hipStream_t st) {
+  const dim3 grid(ccx_cdiv(ccx_cdiv((int)out_stride, 8), 4), n_utt);
+#define SEP_DEC(NS)                                                                                                                  \
+  case NS:                                                                                                                           \
+    hipLaunchKernelGGL(sep_decoder_kernel<NS>, grid, dim3(256), 0, st, feats, fc, utt_tok0, utt_L, utt_T, wdec, out, out_stride, n_utt); \
+    break
+  switch (n_spk) {
+    SEP_DEC(1); SEP_DEC(2); SEP_DEC(3); SEP_DEC(4);
+    default: return ccx_fail(ctx, CCX_ERR_ARG, "sep_decoder: n_spk = %d, built for 1 to 4 sources", n_spk);
+  }
+#undef SEP_DEC
   CCX_CHECK_LAUNCH(ctx);
   return CCX_OK;
 }
@@ -865,8 +891,9 @@ int ccx_sepformer_create(ccx_ctx* ctx, const ccx_sepformer_dims* dims, int max_t
   if (!ctx) return CCX_ERR_ARG;
   CCX_REQUIRE(ctx, dims && out, "ccx_sepformer_create: null argument");
   const ccx_sepformer_dims& d = *dims;
-  CCX_REQUIRE(ctx, d.n_filters == 128 && d.d_model == 128 && d.kernel == 16 && d.stride == 8 && d.n_head == 8 && d.n_spk == 2,
-              "sepformer: only the resepformer-wsj02mix geometry (128 filters, k16 s8, d_model 128, 8 heads, 2 speakers) is built");
+  CCX_REQUIRE(ctx, d.n_filters == 128 && d.d_model == 128 && d.kernel == 16 && d.stride == 8 && d.n_head == 8,
+              "sepformer: only the resepformer-wsj0Nmix geometry (128 filters, k16 s8, d_model 128, 8 heads) is built");
+  CCX_REQUIRE(ctx, d.n_spk >= 1 && d.n_spk <= 4, "sepformer: n_spk = %d, the mask head and the decoder are built for 1 to 4 sources", d.n_spk);
   CCX_REQUIRE(ctx, d.d_ffn % 128 == 0 && d.d_ffn <= 1024 && d.segment >= 16 && d.n_layers >= 1 && d.n_blocks >= 1, "sepformer: bad dims");
   CCX_REQUIRE(ctx, max_tokens >= d.segment && max_utts >= 1, "sepformer: capacity too small");
   ccx_sepformer* s = new ccx_sepformer();
@@ -931,7 +958,7 @@ int ccx_sepformer_finalize(ccx_sepformer* s) {
   }
   const size_t T = (size_t)s->max_tokens;
   CCX_TRY(s->store.alloc(&s->feats, T * D, true)); CCX_TRY(s->store.alloc(&s->x, T * D, true)); CCX_TRY(s->store.alloc(&s->xin, T * D, true)); CCX_TRY(s->store.alloc(&s->h, T * D, true));
-  CCX_TRY(s->store.alloc(&s->fc, T * 2 * D, true)); CCX_TRY(s->store.alloc(&s->xn, T * D, true)); CCX_TRY(s->store.alloc(&s->qkv, T * 3 * D, true));
+  CCX_TRY(s->store.alloc(&s->fc, T * d.n_spk * D, true)); CCX_TRY(s->store.alloc(&s->xn, T * D, true)); CCX_TRY(s->store.alloc(&s->qkv, T * 3 * D, true));
   CCX_TRY(s->store.alloc(&s->att, T * D, true));
   CCX_TRY(s->store.alloc(&s->memx, (size_t)max_chunks * D, true)); CCX_TRY(s->store.alloc(&s->memxin, (size_t)max_chunks * D, true));
   CCX_TRY(s->store.alloc(&s->memh, (size_t)max_chunks * D, true)); CCX_TRY(s->store.alloc(&s->hc, (size_t)max_chunks * D, true));
@@ -1008,9 +1035,9 @@ int ccx_sepformer_separate(ccx_sepformer* s, const float* mix, int64_t stride, c
   CCX_CHECK_LAUNCH(ctx);
   GemmParams p;
   memset(&p, 0, sizeof(p));
-  p.A = s->xn; p.lda = D; p.W = s->W_fc; p.ldw = D; p.M = n_tok; p.N = 2 * D; p.K = D; p.bias = s->b_fc; p.out = s->fc; p.ldo = 2 * D;
+  p.A = s->xn; p.lda = D; p.W = s->W_fc; p.ldw = D; p.M = n_tok; p.N = d.n_spk * D; p.K = D; p.bias = s->b_fc; p.out = s->fc; p.ldo = d.n_spk * D;
   CCX_TRY(ccx_launch_gemm(ctx, EPI_F32, p, st));
-  return ccx_launch_sep_decoder(ctx, s->feats, s->fc, s->utt_tok0, s->utt_L, s->utt_T, s->w_dec, out, (long)stride, B, st);
+  return ccx_launch_sep_decoder(ctx, s->feats, s->fc, s->utt_tok0, s->utt_L, s->utt_T, s->w_dec, out, (long)stride, B, d.n_spk, st);
 }
 
 }  // extern "C"

@@ -17,7 +17,7 @@ from .pipelines import SpeakerDiarization, VoiceActivityDetection
 from .separator import SepformerSeparator
 from .speaker import ECAPAEmbedder, ResNetEmbedder, SegmentationNet, XVectorEmbedder
 from .weights import (SepDims, WhisperDims, find_ecapa_checkpoint, find_pipeline_config, find_pyannote_checkpoint, find_sepformer_checkpoint,
-                      find_whisper_checkpoint, synthetic_pyannet_state_dict, synthetic_resnet34_state_dict,
+                      find_whisper_checkpoint, sep_dims_from_state_dict, synthetic_pyannet_state_dict, synthetic_resnet34_state_dict,
                       synthetic_ecapa_state_dict, synthetic_sepformer_state_dict, synthetic_whisper_state_dict,
                       synthetic_xvector_state_dict)
 from .whisper import WhisperModel
@@ -42,10 +42,12 @@ def _check_denoise(denoise: str) -> str:
 
 
 def build_state_dicts(config=None, whisper_dims: Optional[WhisperDims] = None, sep_dims: Optional[SepDims] = None,
-                      seed: int = 0, embedding: str = "xvector") -> Dict[str, object]:
+                      seed: int = 0, embedding: str = "xvector", sep_checkpoint: str = "resepformer") -> Dict[str, object]:
     """Every weight of the path as host tensors: the real Whisper checkpoint when MODEL_CACHE_DIR holds one, seeded
     synthetic weights of the same architectures otherwise.  In a multi-GPU job rank 0 calls this and the result
-    travels by ONE broadcast (batch.broadcast_weights)."""
+    travels by ONE broadcast (batch.broadcast_weights).
+    sep_checkpoint: the separator's savedir under MODEL_CACHE_DIR (default: the reference's `resepformer`); a checkpoint found there
+    brings its own geometry (weights.sep_dims_from_state_dict: a 3-mix savedir gives n_spk = 3)."""
     _check_embedding(embedding)
     size = getattr(config, "whisper_model_size", "small.en") if config is not None else "small.en"
     ck = find_whisper_checkpoint(size) if whisper_dims is None else None
@@ -54,8 +56,8 @@ def build_state_dicts(config=None, whisper_dims: Optional[WhisperDims] = None, s
     else:
         wd = whisper_dims or WhisperDims.small_en()
         wsd = synthetic_whisper_state_dict(wd, seed=seed)
-    sd_ = sep_dims or SepDims()
-    sep_ck = find_sepformer_checkpoint() if sep_dims is None else None
+    sep_ck = find_sepformer_checkpoint(subdir=sep_checkpoint) if sep_dims is None else None
+    sd_ = sep_dims or (sep_dims_from_state_dict(sep_ck) if sep_ck is not None else SepDims())
     # pyannote-side networks (reference back/api.py:776-792): real checkpoints when the hub cache holds them, seeded otherwise
     synth = {"xvector": lambda: synthetic_xvector_state_dict(seed=seed + 2), "pyannet_diar": lambda: synthetic_pyannet_state_dict(7, seed=seed + 3),
              "pyannet_vad": lambda: synthetic_pyannet_state_dict(3, seed=seed + 4), "resnet34": lambda: synthetic_resnet34_state_dict(seed=seed + 5)}
@@ -88,7 +90,7 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
                 gate_max_clips: int = 32, gate_max_seconds: float = 30.0, word_alignment: bool = False,
                 word_probabilities: bool = False, embedding: str = "xvector", denoise: str = "stationary",
                 decoding_options: bool = False, whisper_cross_fp8: bool = False, whisper_audio_ctx=None,
-                whisper_token_logprobs: bool = False) -> Dict[str, object]:
+                whisper_token_logprobs: bool = False, sep_checkpoint: str = "resepformer") -> Dict[str, object]:
     """embedding: "xvector" (default: `pyannote/embedding`, what the reference loads) or "ecapa" (ECAPA-TDNN, 192-d) for
     `models["embedding_model"]`; the diarization pipeline keeps its ResNet-34 either way.
     denoise: the mode of `models["denoiser"]` -- "stationary" (default: what the reference asks noisereduce for) or "nonstationary"
@@ -98,14 +100,17 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
     whisper_audio_ctx (default None: off): "auto" or an integer builds every Whisper instance for the reduced audio context
     (WhisperModel.__init__ `audio_ctx`; not upstream's arithmetic, transcript quality on real checkpoints unmeasured).
     whisper_token_logprobs (default off): every Whisper instance holds the buffers of the per-token log-probabilities, and its
-    `transcribe` / `decode` take `logprobs=n` (WhisperModel.__init__ `token_logprobs`; parity unpinned)."""
+    `transcribe` / `decode` take `logprobs=n` (WhisperModel.__init__ `token_logprobs`; parity unpinned).
+    sep_checkpoint (default "resepformer", the reference's savedir): the separator's savedir under MODEL_CACHE_DIR, handed to
+    build_state_dicts when no state_dicts are given; `models["separator"].n_spk` says how many sources it returns."""
     _check_embedding(embedding)
     _check_denoise(denoise)
     if not torch.cuda.is_available():
         raise _lib.CcxError("load_models needs a ROCm GPU: the HIP path has no CPU fallback")
     dev_index = device.index if isinstance(device, torch.device) and device.index is not None else (device if isinstance(device, int) else 0)
     ctx = ctx or _lib.Context(dev_index)
-    W = state_dicts if state_dicts is not None else build_state_dicts(config, whisper_dims, sep_dims, seed, embedding=embedding)
+    W = state_dicts if state_dicts is not None else build_state_dicts(config, whisper_dims, sep_dims, seed, embedding=embedding,
+                                                                                  sep_checkpoint=sep_checkpoint)
     if embedding == "ecapa" and "ecapa" not in W:
         raise ValueError("load_models(embedding='ecapa'): state_dicts has no 'ecapa' entry (build_state_dicts(embedding='ecapa'))")
     wd, wsd = WhisperDims(**W["whisper_dims"]), W["whisper"]

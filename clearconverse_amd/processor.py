@@ -8,7 +8,7 @@ every input, checked against fixtures produced by executing the reference's own 
 
 The five model objects it drives are duck-typed exactly as in the reference:
     whisper_model.transcribe(np1d, initial_prompt=, word_timestamps=, condition_on_previous_text=, temperature=)['text']
-    separator.separate_batch(Tensor[1,T]) -> Tensor[1,T,2]
+    separator.separate_batch(Tensor[1,T]) -> Tensor[1,T,2]      (any number of sources on the last axis is taken)
     embedding_model({"waveform": Tensor[1,T], "sample_rate": int}) -> ndarray/Tensor [D]
     vad_pipeline(path) / diarization(path, min_speakers=, max_speakers=) -> object with itertracks(yield_label=True)
     denoiser(np1d, sr, prop_decrease) -> np1d            (noisereduce.reduce_noise in the reference)
@@ -17,7 +17,9 @@ tests inject scripted stubs through the same attributes.
 """
 from __future__ import annotations
 
+import itertools
 import logging
+import math
 import os
 import tempfile
 import traceback
@@ -38,6 +40,7 @@ PROMPT_TWO_PEOPLE = "This is a conversation between two people."
 PROMPT_COMPLETE = "This is a clear conversation with complete sentences."
 PROMPT_FAST = "This is a fast-paced conversation with quick speaker changes. "
 PROMPT_SINGLE = "This is a single speaker talking."
+SPEAKER_NAMES = ("SPEAKER_A", "SPEAKER_B", "SPEAKER_C", "SPEAKER_D")
 
 
 @dataclass
@@ -100,7 +103,16 @@ def _tracks(annotation) -> List[Tuple[float, float, str]]:
 
 class EnhancedAudioProcessor:
     def __init__(self, config: Config, load_models_immediately: bool = False, model_loader: Optional[Callable] = None,
-                 word_alignment: bool = False):
+                 word_alignment: bool = False, speakers: int = 2, all_overlap_sources: bool = False):
+        """speakers (2 to 4, default 2 as the reference): how many of the most frequent diarization labels get a name
+        (SPEAKER_A .. SPEAKER_D; the rest stay UNKNOWN) and the most speakers both diarization passes may report.
+        all_overlap_sources (default off: the reference keeps one voice per overlap region): every separated source of a region
+        that can be paired with an involved speaker becomes a segment of its own (_process_overlap_segment).  Neither is a Config
+        field: Config mirrors the reference's names."""
+        if isinstance(speakers, bool) or not isinstance(speakers, int) or not 2 <= speakers <= len(SPEAKER_NAMES):
+            raise ValueError(f"speakers={speakers!r}: must be an integer in [2, {len(SPEAKER_NAMES)}]")
+        self.speakers = speakers
+        self.all_overlap_sources = bool(all_overlap_sources)
         self.config = config
         # opt-in (default off: the reference never reads the words): the Whisper object aligns words on the GPU when the calls
         # below pass word_timestamps=True (back/api.py:1435, 1477); handed to the loader only when set
@@ -358,38 +370,87 @@ class EnhancedAudioProcessor:
             log.error("Error in diarization: %s", e)
             raise
 
+    @staticmethod
+    def _assign_sources(sim: Sequence[Sequence[float]]) -> List[Tuple[int, int]]:
+        """One-to-one assignment of sources (rows of `sim`) to candidates (columns) with the largest total similarity, as
+        (source, candidate) pairs in candidate order.  min(rows, columns) pairs are made.  Exhaustive: at most 4 x 4, a few hundred
+        cases.  Among equal totals the first wins in lexicographic order of the source index per candidate, a candidate left without
+        a source counting as index `rows`."""
+        n_src, n_cand = len(sim), (len(sim[0]) if len(sim) else 0)
+        pairs = min(n_src, n_cand)
+        best, best_total = None, -math.inf
+        for pick in itertools.product(range(n_src + 1), repeat=n_cand):          # generated in lexicographic order
+            used = [k for k in pick if k < n_src]
+            if len(used) != pairs or len(set(used)) != pairs:
+                continue
+            total = sum(float(sim[k][c]) for c, k in enumerate(pick) if k < n_src)
+            if total > best_total:
+                best, best_total = pick, total
+        return [(k, c) for c, k in enumerate(best or ()) if k < n_src]
+
+    def _overlap_record(self, rec: Dict, chosen: torch.Tensor, piece: torch.Tensor, jobs: Optional[List["_WhisperJob"]]) -> None:
+        """Transcribe `chosen` into `rec`, now or through `jobs`."""
+        if jobs is None:
+            rec["transcription"] = self._transcribe(chosen.squeeze().cpu().numpy(), initial_prompt=PROMPT_SINGLE,
+                                                    temperature=self.config.temperature)["text"]
+            return
+        # deferred (two-pass schedule): the fixed prompt makes this call independent of every other one.  A failing
+        # call turns the record into the reference's marker segment, exactly as the except branch of the caller does
+
+        def failed(e, rec=rec, piece=piece):
+            log.error("Error processing overlap subsegment: %s", e)
+            rec.update({"audio": piece, "transcription": "[Processing error]", "confidence": 0.0, "error": str(e)})
+        jobs.append(_WhisperJob(audio=chosen, prompt=PROMPT_SINGLE, dep=None, word_timestamps=False, condition=True,
+                                wrap_errors=True, done=lambda t, rec=rec: rec.__setitem__("transcription", t), failed=failed))
+
     def _process_overlap_segment(self, audio_segment: torch.Tensor, speaker_embeddings: Dict[str, torch.Tensor],
                                  involved_speakers: List[str], seg_start: float, seg_end: float,
                                  jobs: Optional[List["_WhisperJob"]] = None) -> List[Dict]:
-        """reference 1066-1118.  `jobs` (two-pass schedule): the transcription of every region is recorded there instead of run."""
+        """reference 1066-1118.  `jobs` (two-pass schedule): the transcription of every region is recorded there instead of run.
+
+        all_overlap_sources (not in the reference, which keeps the one source closest to the region's speaker): the candidates of
+        a region are its speaker `who` and then the other involved speakers that have a profile; the sources that could be embedded
+        are assigned to them one to one for the largest total similarity (_assign_sources) and every pair becomes a record --
+        `who`'s first -- with the candidate as speaker, the pair's similarity as confidence, that source as audio and
+        `overlap_source`, the source's index.  Sources left without a candidate are dropped.  Without a profile of `who` (or with
+        no source embedded) the region gets the single default record."""
         out: List[Dict] = []
         for ns, ne, who in self._resegment_overlap(audio_segment, seg_start, seg_end, speaker_embeddings):
             piece = self._extract_segment(audio_segment, ns - seg_start, ne - seg_start)
             try:
                 sources = self.separator.separate_batch(piece)
-                best, best_sim = None, -1.0
+                embedded: List[Tuple[int, torch.Tensor, torch.Tensor]] = []       # (source index, peak-normalised source, embedding)
                 for k in range(sources.shape[-1]):
                     src = sources[..., k]
                     src = src / (torch.max(torch.abs(src)) + 1e-8)
                     emb = self._extract_embedding(src)
                     if emb is None:
                         continue
+                    embedded.append((k, src, emb))
+                if self.all_overlap_sources and embedded and who in speaker_embeddings:
+                    cands = [who]
+                    for spk in involved_speakers:
+                        if spk not in cands and spk in speaker_embeddings:
+                            cands.append(spk)
+                    sim = [[self._calculate_embedding_similarity(emb, speaker_embeddings[c]) for c in cands] for _, _, emb in embedded]
+                    for i, c in self._assign_sources(sim):
+                        k, src, _ = embedded[i]
+                        rec = {"audio": src, "transcription": None, "speaker_id": cands[c], "confidence": sim[i][c], "overlap_source": k}
+                        try:
+                            self._overlap_record(rec, src, piece, jobs)
+                        except Exception as e:  # noqa: BLE001 -- an immediate call that fails marks its own source only
+                            log.error("Error processing overlap subsegment: %s", e)
+                            rec.update({"audio": piece, "transcription": "[Processing error]", "confidence": 0.0, "error": str(e)})
+                        out.append(rec)
+                    continue
+                best, best_sim = None, -1.0
+                for _, src, emb in embedded:
                     sim = self._calculate_embedding_similarity(emb, speaker_embeddings.get(who, emb))
                     if sim > best_sim:
                         best, best_sim = src, sim
                 chosen = best if best is not None else piece
                 rec = {"audio": chosen, "transcription": None, "speaker_id": who, "confidence": best_sim}
-                if jobs is None:
-                    rec["transcription"] = self._transcribe(chosen.squeeze().cpu().numpy(), initial_prompt=PROMPT_SINGLE,
-                                                            temperature=self.config.temperature)["text"]
-                else:
-                    # deferred (two-pass schedule): the fixed prompt makes this call independent of every other one.  A failing
-                    # call turns the record into the reference's marker segment, exactly as the except branch below does
-                    def failed(e, rec=rec, piece=piece):
-                        log.error("Error processing overlap subsegment: %s", e)
-                        rec.update({"audio": piece, "transcription": "[Processing error]", "confidence": 0.0, "error": str(e)})
-                    jobs.append(_WhisperJob(audio=chosen, prompt=PROMPT_SINGLE, dep=None, word_timestamps=False, condition=True,
-                                            wrap_errors=True, done=lambda t, rec=rec: rec.__setitem__("transcription", t), failed=failed))
+                self._overlap_record(rec, chosen, piece, jobs)
                 out.append(rec)
             except Exception as e:  # noqa: BLE001 -- the reference keeps going with a marker segment
                 log.error("Error processing overlap subsegment: %s", e)
@@ -405,7 +466,7 @@ class EnhancedAudioProcessor:
             with tempfile.TemporaryDirectory(prefix="ccx_seg_") as td:
                 path = os.path.join(td, "temp_segment.wav")
                 write_wav(path, audio_segment.detach().cpu().numpy(), self.config.target_sample_rate)
-                ann = self.diarization(path, min_speakers=1, max_speakers=2)
+                ann = self.diarization(path, min_speakers=1, max_speakers=self.speakers)
             found = _tracks(ann)
             if not found:
                 return [(seg_start, seg_end, "UNKNOWN")]
@@ -548,7 +609,9 @@ class EnhancedAudioProcessor:
         duration = audio.shape[-1] / sr
 
         vad_intervals = iv.get_vad_intervals(self.vad_pipeline(wav_path))
-        diar = self._diarize(wav_path, min_speakers=cfg.min_speakers, max_speakers=cfg.max_speakers)
+        # speakers > 2 (opt-in) lifts the cap to at least that many; at the default the reference's own value goes through untouched
+        max_spk = cfg.max_speakers if self.speakers == 2 else max(cfg.max_speakers, self.speakers)
+        diar = self._diarize(wav_path, min_speakers=cfg.min_speakers, max_speakers=max_spk)
         merged = iv.merge_diarization_segments(_tracks(diar), cfg.merge_gap_threshold)
         if cfg.use_vad_refinement:
             segs = []
@@ -568,8 +631,7 @@ class EnhancedAudioProcessor:
                 raise ValueError("No speakers detected in the audio file")
             names = {labels[0]: "SPEAKER_A"}
         else:
-            top = [lab for lab, _ in counts.most_common(2)]
-            names = {top[0]: "SPEAKER_A", top[1]: "SPEAKER_B"}
+            names = {lab: SPEAKER_NAMES[i] for i, (lab, _) in enumerate(counts.most_common(self.speakers))}
 
         overlaps = self._detect_overlap_regions(diar)
         segs.sort(key=lambda t: t[0])
@@ -612,6 +674,8 @@ class EnhancedAudioProcessor:
                     seg = AudioSegment(start=seg_start, end=seg_end, speaker_id=r["speaker_id"], audio_tensor=r["audio"],
                                        is_overlap=True, transcription=r["transcription"],
                                        confidence=r.get("confidence", 0.5), metadata={"overlap_speakers": involved})
+                    if "overlap_source" in r:           # all_overlap_sources: which separated source this segment carries
+                        seg.metadata["overlap_source"] = r["overlap_source"]
                     out.append(seg)
                     overlap_pairs.append((r, seg))      # a deferred transcription (or its failure) lands in the record first
                 prev_end = seg_end
@@ -660,4 +724,6 @@ class EnhancedAudioProcessor:
                 "speaker_b_segments": tally.get("SPEAKER_B", 0), "total_segments": len(out),
                 "speakers": list(names.values()),
                 "rapid_exchanges": sum(1 for s in out if s.metadata.get("rapid_exchange", False))}
+        if self.speakers != 2:      # speaker_a_segments / speaker_b_segments for every named speaker (the default keeps the reference's keys)
+            meta["speaker_segments"] = {name: tally.get(name, 0) for name in names.values()}
         return {"segments": out, "metadata": meta}

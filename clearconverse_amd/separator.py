@@ -1,7 +1,10 @@
 """`SepformerSeparator`: drop-in for the `self.separator` object of the reference
 (SepformerSeparation.from_hparams at /root/reference/back/api.py:713-717; called at 1077 as
 `separated = self.separator.separate_batch(subsegment)` with a [1, T] tensor, result indexed
-`separated[..., idx]`).  All arithmetic runs in libccx (csrc/sepformer.hip)."""
+`separated[..., idx]`).  All arithmetic runs in libccx (csrc/sepformer.hip).
+
+The reference loads the two-speaker model; `SepDims.n_spk` in [1, 4] builds the same network with a mask head of `128 * n_spk`
+rows (the layout of the 3-mix sibling checkpoint), and `separate_batch` then returns that many sources."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,6 +23,7 @@ class SepformerSeparator:
         if not torch.cuda.is_available():
             raise _lib.CcxError("SepformerSeparator needs a ROCm GPU: the HIP path has no CPU fallback")
         self.dims = dims
+        self.n_spk = int(dims.n_spk)            # sources per utterance: the last axis of separate_batch's result
         self.max_tokens, self.max_utts = int(max_tokens) // dims.segment * dims.segment, int(max_utts)
         self.device = torch.device("cuda", device)
         self.ctx = ctx or _lib.Context(device)
@@ -52,14 +56,14 @@ class SepformerSeparator:
             pass
 
     def separate_batch(self, mix: torch.Tensor, n_samples: Optional[Sequence[int]] = None) -> torch.Tensor:
-        """mix [B, T] -> [B, T, 2].  Rows are independent utterances; `n_samples` gives their true
-        lengths when the batch is ragged (zero padded to T)."""
+        """mix [B, T] -> [B, T, n_spk] (2 for the default geometry).  Rows are independent utterances; `n_samples` gives their true
+        lengths when the batch is ragged (zero padded to T); every source is zero past an utterance's length."""
         if mix.dim() == 1:
             mix = mix.unsqueeze(0)
         x = mix.to(self.device, torch.float32).contiguous()
         B, T = x.shape
         ns = (C.c_int * B)(*([T] * B if n_samples is None else [int(v) for v in n_samples]))
-        out = torch.empty(B, T, 2, device=self.device, dtype=torch.float32)
+        out = torch.empty(B, T, self.n_spk, device=self.device, dtype=torch.float32)
         self.ctx.check(self.lib.ccx_sepformer_separate(self.handle, x.data_ptr(), T, ns, B, out.data_ptr(), _lib.current_stream_ptr()),
                        "ccx_sepformer_separate")
         return out

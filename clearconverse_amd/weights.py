@@ -231,10 +231,34 @@ def synthetic_sepformer_state_dict(dims: SepDims, seed: int = 0) -> Dict[str, to
     return sd
 
 
-def find_sepformer_checkpoint(cache_dir: Optional[str] = None, apply_ft_overlay: Optional[bool] = None) -> Optional[Dict[str, torch.Tensor]]:
+def sep_dims_from_state_dict(sd: Dict[str, torch.Tensor]) -> SepDims:
+    """The geometry a flat RE-SepFormer state dict (find_sepformer_checkpoint's layout) was saved with, read from tensor shapes:
+    `n_filters` and `kernel` from `encoder.conv1d.weight` [N, 1, k]; `d_model` and `n_spk` from `masknet.model.output_fc.1.weight`
+    [N * n_spk, D, 1]; `d_ffn` from the first layer's `pos_ffn.ffn.0.weight`; `n_blocks` / `n_layers` by counting the `seg_model.<i>`
+    blocks and the layers of block 0.  `n_head`, `stride` and `segment` leave no trace in the weights and keep SepDims' defaults.  The
+    two-speaker checkpoint the reference names yields exactly SepDims(); its 3-mix sibling differs in n_spk alone."""
+    import re
+    base = SepDims()
+    enc, fc = sd["encoder.conv1d.weight"], sd["masknet.model.output_fc.1.weight"]
+    n_filters, kernel = int(enc.shape[0]), int(enc.shape[-1])
+    if fc.shape[0] % n_filters:
+        raise ValueError(f"masknet.model.output_fc.1.weight has {fc.shape[0]} rows, no multiple of the {n_filters} encoder filters")
+    blocks = {int(m.group(1)) for k in sd for m in [re.match(r"masknet\.model\.seg_model\.(\d+)\.", k)] if m}
+    layers = {int(m.group(1)) for k in sd for m in [re.match(r"masknet\.model\.seg_model\.0\.mdl\.layers\.(\d+)\.", k)] if m}
+    if not blocks or not layers:
+        raise ValueError("no masknet.model.seg_model.<i>.mdl.layers.<l> keys: not a RE-SepFormer state dict")
+    ffn = sd["masknet.model.seg_model.0.mdl.layers.0.pos_ffn.ffn.0.weight"]
+    return SepDims(n_filters=n_filters, kernel=kernel, stride=base.stride, d_model=int(fc.shape[1]), n_head=base.n_head,
+                   d_ffn=int(ffn.shape[0]), n_layers=max(layers) + 1, n_blocks=max(blocks) + 1, segment=base.segment,
+                   n_spk=int(fc.shape[0]) // n_filters)
+
+
+def find_sepformer_checkpoint(cache_dir: Optional[str] = None, apply_ft_overlay: Optional[bool] = None,
+                              subdir: str = "resepformer") -> Optional[Dict[str, torch.Tensor]]:
     """SpeechBrain savedir layout the reference uses (back/api.py:713-717): `<cache>/resepformer/{encoder,masknet,decoder}.ckpt`,
     each the state_dict of that module.  Returns one flat dict with `encoder.` / `masknet.` / `decoder.` prefixes, or None when
-    the base checkpoint is absent.  Files are read with weights_only=True.
+    the base checkpoint is absent.  Files are read with weights_only=True.  `subdir` names another savedir under the cache, such as
+    `resepformer-wsj03mix` for the three-speaker model (sep_dims_from_state_dict reads its geometry); the default is the reference's.
 
     The fine-tune overlay `<cache>/resepformer-ft/`: the reference calls
     `self.separator.load_state_dict({'masknet': {...}, 'encoder': {...}, 'decoder': {...}}, strict=False)` (back/api.py:739-746).
@@ -245,7 +269,7 @@ def find_sepformer_checkpoint(cache_dir: Optional[str] = None, apply_ft_overlay:
     cache_dir = cache_dir or os.environ.get("MODEL_CACHE_DIR", "models")
     if apply_ft_overlay is None:
         apply_ft_overlay = os.environ.get("CCX_APPLY_RESEPFORMER_FT", "0") not in ("", "0")
-    base = os.path.join(cache_dir, "resepformer")
+    base = os.path.join(cache_dir, subdir)
     parts = ("encoder", "masknet", "decoder")
     if not all(os.path.exists(os.path.join(base, f"{p}.ckpt")) for p in parts):
         return None

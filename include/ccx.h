@@ -951,7 +951,9 @@ typedef struct {
 } ccx_sepformer_dims;
 
 /* max_tokens: capacity in encoder frames summed over the utterances of one call (each padded to
- * whole `segment`-frame chunks); max_utts: utterances per call. */
+ * whole `segment`-frame chunks); max_utts: utterances per call.  The geometry is RE-SepFormer's (128 filters, kernel 16, stride 8,
+ * d_model 128, 8 heads) with n_spk in [1, 4] sources: `masknet.model.output_fc.1` then has 128 n_spk rows, row c n_spk + s the mask
+ * of channel c for source s. */
 int ccx_sepformer_create(ccx_ctx* ctx, const ccx_sepformer_dims* dims, int max_tokens, int max_utts,
                          ccx_sepformer** out);
 void ccx_sepformer_destroy(ccx_sepformer* s);
@@ -960,7 +962,9 @@ void ccx_sepformer_destroy(ccx_sepformer* s);
 int ccx_sepformer_set_tensor(ccx_sepformer* s, const char* name, const float* data, int64_t numel);
 int ccx_sepformer_finalize(ccx_sepformer* s);
 /* separate_batch for B independent utterances: mix_dev [B, stride] f32, n_samples host [B] ->
- * out_dev [B, stride, 2] f32 (rows past n_samples[b] are zero). */
+ * out_dev [B, stride, n_spk] f32, the sources interleaved per sample (rows past n_samples[b] are zero for every source).  n_spk
+ * is the handle's (ccx_sepformer_dims, 1 to 4; 2 for the model the reference loads): the mask head is one GEMM of 128 n_spk
+ * columns, the decoder one instantiation per n_spk. */
 int ccx_sepformer_separate(ccx_sepformer* s, const float* mix_dev, int64_t stride, const int* n_samples, int B,
                            float* out_dev, void* stream);
 
@@ -974,11 +978,12 @@ int ccx_sepformer_separate(ccx_sepformer* s, const float* mix_dev, int64_t strid
 #define CCX_SEP_ATTENTION 1    /* sep_attention_kernel: qkv -> att per sequence and head, any len */
 #define CCX_SEP_FFN 2          /* sep_ffn_kernel: h[0 .. n_tok) += W2 relu(W1 LN(h) + b1) + b2 */
 #define CCX_SEP_FINAL_NORM 3   /* sep_final_norm_kernel: y = gLN(LN(h)) + xin per sequence */
-#define CCX_SEP_DECODER 4      /* sep_decoder_kernel: out[u][t][spk] from feats * relu(fc), 16 taps, stride 8 */
+#define CCX_SEP_DECODER 4      /* sep_decoder_kernel<n_spk>: out[u][t][spk] from feats * relu(fc), 16 taps, stride 8 */
 
 typedef struct ccx_sep_desc {
   /* token buffers, `rows` rows each: h f32 [rows][128] (ops 0, 2: in and out; op 3: in), xin / y f32 [rows][128] (op 3: skip input /
-   * output), qkv bf16 [rows][384] and att bf16 [rows][128] (op 1), feats f32 [rows][128] and fc f32 [rows][256] (op 4) */
+   * output), qkv bf16 [rows][384] and att bf16 [rows][128] (op 1), feats f32 [rows][128] and fc f32 [rows][128 n_spk] (op 4:
+   * column c n_spk + s is the mask logit of channel c for source s) */
   void* h; const void* xin; void* y; const void* qkv; void* att; const void* feats; const void* fc;
   int64_t h_elems, xin_elems, y_elems, qkv_elems, att_elems, feats_elems, fc_elems;
   int rows;
@@ -995,9 +1000,12 @@ typedef struct ccx_sep_desc {
   int64_t ln_elems, gln_elems, wqkv_elems, bqkv_elems, wo_elems, bo_elems, w1_elems, b1_elems, w2_elems, b2_elems, wdec_elems;
   /* op 4: HOST tables of n_utt utterances: first token row, frames L >= 1, samples 16 <= T <= out_stride; an utterance owns the rows
    * of its frames padded to whole `segment`-row chunks (a full extra chunk when L is a multiple of it), all inside [0, rows).
-   * out f32 [n_utt][out_stride][2] */
+   * out f32 [n_utt][out_stride][n_spk] */
   const int* utt_tok0; const int* utt_L; const int* utt_T; int n_utt; int segment;
   void* out; int64_t out_stride; int64_t out_elems;
+  /* op 4: sources of the mask and of out, 1 to 4; 0 means 2 (a descriptor written before the field existed).  Anything else is
+   * CCX_ERR_ARG; fc_elems and out_elems are checked against it */
+  int n_spk;
 } ccx_sep_desc;
 
 int ccx_sep_op(ccx_ctx* ctx, int op, const ccx_sep_desc* desc, void* stream);
