@@ -243,6 +243,28 @@ class SepDesc(C.Structure):
 SEP_ATTN_BLOCK, SEP_ATTENTION, SEP_FFN, SEP_FINAL_NORM, SEP_DECODER = range(5)
 
 
+class DualPathDims(C.Structure):
+    """ccx_dualpath_dims (include/ccx.h)."""
+    _fields_ = [(n, C.c_int) for n in (
+        "n_filters", "kernel", "stride", "d_model", "n_head", "d_ffn", "n_layers", "n_blocks", "segment", "n_spk")]
+
+
+class DualPathDesc(C.Structure):
+    """ccx_dualpath_desc (include/ccx.h): one dual-path SepFormer kernel on its own."""
+    _fields_ = (
+        [(n, C.c_void_p) for n in ("in", "in2", "out", "w", "w2")]
+        + [(n, C.c_int64) for n in ("in_elems", "in2_elems", "out_elems", "w_elems", "w2_elems")]
+        + [("rows", C.c_int), ("frames", C.c_int), ("mode", C.c_int)]
+        + [("seq_first", C.POINTER(C.c_int)), ("seq_stride", C.POINTER(C.c_int)), ("seq_len", C.POINTER(C.c_int)), ("n_seq", C.c_int)]
+        + [("utt_row0", C.POINTER(C.c_int)), ("utt_rows", C.POINTER(C.c_int))]
+        + [(n, C.POINTER(C.c_int)) for n in ("utt_tok0", "utt_frame0", "utt_L", "utt_gap", "utt_S", "utt_T")]
+        + [("n_utt", C.c_int), ("segment", C.c_int), ("kernel", C.c_int), ("n_spk", C.c_int),
+           ("in_stride", C.c_int64), ("out_stride", C.c_int64)])
+
+
+(DP_ATTENTION, DP_GROUP_NORM, DP_SEGMENT, DP_OVERLAP_ADD, DP_PE_ADD, DP_GATE, DP_ENCODER, DP_DECODER, DP_PRELU) = range(9)
+
+
 class EcapaDesc(C.Structure):
     """ccx_ecapa_desc (include/ccx.h): one ECAPA-TDNN kernel on its own."""
     _fields_ = [
@@ -429,6 +451,12 @@ PROTOTYPES = {
     "ccx_sepformer_finalize": (_i, [_vp]),
     "ccx_sepformer_separate": (_i, [_vp, _vp, _i64, _ip, _i, _vp, _vp]),
     "ccx_sep_op": (_i, [_vp, _i, C.POINTER(SepDesc), _vp]),
+    "ccx_dualpath_create": (_i, [_vp, C.POINTER(DualPathDims), _i, _i, C.POINTER(_vp)]),
+    "ccx_dualpath_destroy": (None, [_vp]),
+    "ccx_dualpath_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i64]),
+    "ccx_dualpath_finalize": (_i, [_vp]),
+    "ccx_dualpath_separate": (_i, [_vp, _vp, _i64, _ip, _i, _vp, _vp]),
+    "ccx_dualpath_op": (_i, [_vp, _i, C.POINTER(DualPathDesc), _vp]),
     "ccx_speaker_create": (_i, [_vp, _i, _i, _i, _i, _i64, C.POINTER(_vp)]),
     "ccx_speaker_destroy": (None, [_vp]),
     "ccx_speaker_set_tensor": (_i, [_vp, C.c_char_p, _vp, _i64]),

@@ -14,9 +14,9 @@ import torch
 from . import _lib
 from .denoise import SpectralGate
 from .pipelines import SpeakerDiarization, VoiceActivityDetection
-from .separator import SepformerSeparator
+from .separator import DualPathSeparator, SepformerSeparator
 from .speaker import ECAPAEmbedder, ResNetEmbedder, SegmentationNet, XVectorEmbedder
-from .weights import (SepDims, WhisperDims, find_ecapa_checkpoint, find_pipeline_config, find_pyannote_checkpoint, find_sepformer_checkpoint,
+from .weights import (DualPathDims, SepDims, WhisperDims, find_separator_checkpoint, synthetic_dualpath_state_dict, find_ecapa_checkpoint, find_pipeline_config, find_pyannote_checkpoint, find_sepformer_checkpoint,
                       find_whisper_checkpoint, sep_dims_from_state_dict, synthetic_pyannet_state_dict, synthetic_resnet34_state_dict,
                       synthetic_ecapa_state_dict, synthetic_sepformer_state_dict, synthetic_whisper_state_dict,
                       synthetic_xvector_state_dict)
@@ -42,13 +42,19 @@ def _check_denoise(denoise: str) -> str:
 
 
 def build_state_dicts(config=None, whisper_dims: Optional[WhisperDims] = None, sep_dims: Optional[SepDims] = None,
-                      seed: int = 0, embedding: str = "xvector", sep_checkpoint: str = "resepformer") -> Dict[str, object]:
+                      seed: int = 0, embedding: str = "xvector", sep_checkpoint: str = "resepformer",
+                      sep_family: Optional[str] = None) -> Dict[str, object]:
     """Every weight of the path as host tensors: the real Whisper checkpoint when MODEL_CACHE_DIR holds one, seeded
     synthetic weights of the same architectures otherwise.  In a multi-GPU job rank 0 calls this and the result
     travels by ONE broadcast (batch.broadcast_weights).
     sep_checkpoint: the separator's savedir under MODEL_CACHE_DIR (default: the reference's `resepformer`); a checkpoint found there
-    brings its own geometry (weights.sep_dims_from_state_dict: a 3-mix savedir gives n_spk = 3)."""
+    brings its own geometry (weights.sep_dims_from_state_dict: a 3-mix savedir gives n_spk = 3) and its own family: a savedir of
+    the dual-path SepFormer (`masknet.dual_mdl.0....` keys, e.g. "sepformer-wsj03mix") yields `sep_family: "dualpath"` and DualPathDims.
+    sep_family: None (default: RE-SepFormer unless the savedir says otherwise) or "dualpath" for seeded synthetic weights of the
+    dual-path model when no checkpoint is found (sep_dims then is a DualPathDims or None)."""
     _check_embedding(embedding)
+    if sep_family not in (None, "resepformer", "dualpath"):
+        raise ValueError(f"sep_family={sep_family!r}: must be None, 'resepformer' or 'dualpath'")
     size = getattr(config, "whisper_model_size", "small.en") if config is not None else "small.en"
     ck = find_whisper_checkpoint(size) if whisper_dims is None else None
     if ck is not None:
@@ -57,7 +63,20 @@ def build_state_dicts(config=None, whisper_dims: Optional[WhisperDims] = None, s
         wd = whisper_dims or WhisperDims.small_en()
         wsd = synthetic_whisper_state_dict(wd, seed=seed)
     sep_ck = find_sepformer_checkpoint(subdir=sep_checkpoint) if sep_dims is None else None
-    sd_ = sep_dims or (sep_dims_from_state_dict(sep_ck) if sep_ck is not None else SepDims())
+    found = find_separator_checkpoint(subdir=sep_checkpoint) if sep_ck is not None else None
+    if found is not None and found[0] == "dualpath":
+        if sep_family == "resepformer":
+            raise ValueError(f"sep_family='resepformer' but the savedir '{sep_checkpoint}' holds a dual-path SepFormer")
+        sep_family, sd_ = "dualpath", found[2]
+    elif sep_family == "dualpath":
+        if found is not None:
+            raise ValueError(f"sep_family='dualpath' but the savedir '{sep_checkpoint}' holds a RE-SepFormer")
+        if sep_dims is not None and not isinstance(sep_dims, DualPathDims):
+            raise ValueError("sep_family='dualpath' needs sep_dims of type DualPathDims")
+        sd_ = sep_dims or DualPathDims()
+    else:
+        sd_ = sep_dims or (sep_dims_from_state_dict(sep_ck) if sep_ck is not None else SepDims())
+    dual = sep_family == "dualpath"
     # pyannote-side networks (reference back/api.py:776-792): real checkpoints when the hub cache holds them, seeded otherwise
     synth = {"xvector": lambda: synthetic_xvector_state_dict(seed=seed + 2), "pyannet_diar": lambda: synthetic_pyannet_state_dict(7, seed=seed + 3),
              "pyannet_vad": lambda: synthetic_pyannet_state_dict(3, seed=seed + 4), "resnet34": lambda: synthetic_resnet34_state_dict(seed=seed + 5)}
@@ -74,7 +93,8 @@ def build_state_dicts(config=None, whisper_dims: Optional[WhisperDims] = None, s
     return {
         "whisper_dims": dict(wd.__dict__), "whisper": wsd, "whisper_source": sources["whisper"],
         "sep_dims": dict(sd_.__dict__),
-        "sepformer": sep_ck or synthetic_sepformer_state_dict(sd_, seed=seed + 1),
+        "sepformer": sep_ck or (synthetic_dualpath_state_dict(sd_, seed=seed + 1) if dual else synthetic_sepformer_state_dict(sd_, seed=seed + 1)),
+        **({"sep_family": "dualpath"} if dual else {}),
         **nets,
         "weights_sources": sources,
         # pipeline hyper-parameters: the pipelines' own config.yaml when on disk, the published values otherwise
@@ -90,7 +110,8 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
                 gate_max_clips: int = 32, gate_max_seconds: float = 30.0, word_alignment: bool = False,
                 word_probabilities: bool = False, embedding: str = "xvector", denoise: str = "stationary",
                 decoding_options: bool = False, whisper_cross_fp8: bool = False, whisper_audio_ctx=None,
-                whisper_token_logprobs: bool = False, sep_checkpoint: str = "resepformer") -> Dict[str, object]:
+                whisper_token_logprobs: bool = False, sep_checkpoint: str = "resepformer",
+                sep_family: Optional[str] = None) -> Dict[str, object]:
     """embedding: "xvector" (default: `pyannote/embedding`, what the reference loads) or "ecapa" (ECAPA-TDNN, 192-d) for
     `models["embedding_model"]`; the diarization pipeline keeps its ResNet-34 either way.
     denoise: the mode of `models["denoiser"]` -- "stationary" (default: what the reference asks noisereduce for) or "nonstationary"
@@ -102,7 +123,10 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
     whisper_token_logprobs (default off): every Whisper instance holds the buffers of the per-token log-probabilities, and its
     `transcribe` / `decode` take `logprobs=n` (WhisperModel.__init__ `token_logprobs`; parity unpinned).
     sep_checkpoint (default "resepformer", the reference's savedir): the separator's savedir under MODEL_CACHE_DIR, handed to
-    build_state_dicts when no state_dicts are given; `models["separator"].n_spk` says how many sources it returns."""
+    build_state_dicts when no state_dicts are given; `models["separator"].n_spk` says how many sources it returns.  A savedir of the
+    dual-path SepFormer (e.g. "sepformer-wsj03mix"), or sep_family="dualpath" without one (synthetic weights), makes
+    `models["separator"]` a DualPathSeparator (state_dicts["sep_family"] == "dualpath"); the default stays the RE-SepFormer.  Its
+    capacity is min(sep_tokens, 64000) chunk rows (about 1 GB of workspaces at three sources: 30 s of 8 kHz audio per call)."""
     _check_embedding(embedding)
     _check_denoise(denoise)
     if not torch.cuda.is_available():
@@ -110,17 +134,20 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
     dev_index = device.index if isinstance(device, torch.device) and device.index is not None else (device if isinstance(device, int) else 0)
     ctx = ctx or _lib.Context(dev_index)
     W = state_dicts if state_dicts is not None else build_state_dicts(config, whisper_dims, sep_dims, seed, embedding=embedding,
-                                                                                  sep_checkpoint=sep_checkpoint)
+                                                                                  sep_checkpoint=sep_checkpoint,
+                                                                                  **({"sep_family": sep_family} if sep_family else {}))
+    dual = W.get("sep_family") == "dualpath"
+    sep_dims_t = DualPathDims if dual else SepDims
     if embedding == "ecapa" and "ecapa" not in W:
         raise ValueError("load_models(embedding='ecapa'): state_dicts has no 'ecapa' entry (build_state_dicts(embedding='ecapa'))")
     wd, wsd = WhisperDims(**W["whisper_dims"]), W["whisper"]
     if state_dicts is not None:         # the geometry travels WITH the weights: a contradicting argument is an error, not ignored
         if whisper_dims is not None and whisper_dims != wd:
             raise ValueError(f"load_models: whisper_dims {whisper_dims} contradicts state_dicts['whisper_dims'] {wd}")
-        if sep_dims is not None and sep_dims != SepDims(**W["sep_dims"]):
+        if sep_dims is not None and sep_dims != sep_dims_t(**W["sep_dims"]):
             raise ValueError(f"load_models: sep_dims {sep_dims} contradicts state_dicts['sep_dims'] {W['sep_dims']}")
     vp, dp = W.get("vad_params") or {}, W.get("diarization_params") or {}
-    sd_ = SepDims(**W["sep_dims"])      # the geometry the separator weights were built with (broadcast manifest included)
+    sd_ = sep_dims_t(**W["sep_dims"])   # the geometry the separator weights were built with (broadcast manifest included)
     # whisper_instances = 2: the software-pipelined batch driver (batch.py) encodes batch i + 1 into one instance while batch i
     # is still decoding out of the other (each holds its own cross-KV, workspaces and step graphs; the weights are 0.5 GB)
     # The further instances take the first one's log-mel / encoder workspaces (share_encoder_scratch; 32 GB at 768 windows): those
@@ -146,8 +173,11 @@ def load_models(config=None, device=None, whisper_batch: int = 8, ctx: Optional[
                                      share_encoder_scratch_with=whispers[0] if share_encoder_scratch else None,
                                      word_alignment=word_alignment, **wp))
     whisper = whispers[0]
-    separator = SepformerSeparator(sd_, W["sepformer"], max_tokens=sep_tokens, max_utts=64,
-                                   device=dev_index, ctx=ctx)
+    if dual:                            # opt-in: the published dual-path checkpoints (weights.DualPathDims)
+        separator = DualPathSeparator(sd_, W["sepformer"], max_tokens=min(int(sep_tokens), 64_000), max_utts=64, device=dev_index, ctx=ctx)
+    else:
+        separator = SepformerSeparator(sd_, W["sepformer"], max_tokens=sep_tokens, max_utts=64,
+                                       device=dev_index, ctx=ctx)
     if embedding == "ecapa":            # the x-vector handle is then not created
         embedder = ECAPAEmbedder(W["ecapa"], max_crops=int(emb_max_crops or max_crops), max_samples=16000 * 600, device=dev_index, ctx=ctx)
     else:

@@ -253,12 +253,144 @@ def sep_dims_from_state_dict(sd: Dict[str, torch.Tensor]) -> SepDims:
                    n_spk=int(fc.shape[0]) // n_filters)
 
 
+# ----------------------------------------------------------------------------------------------
+# Dual-path SepFormer (speechbrain/sepformer-wsj02mix / -wsj03mix / -wham / -whamr / -libri2mix / -libri3mix hyper-parameters
+# [UPSTREAM-RECALL], parity unpinned: tests/dualpath_reference.py)
+# ----------------------------------------------------------------------------------------------
+@dataclass
+class DualPathDims:
+    n_filters: int = 256
+    kernel: int = 16
+    stride: int = 8
+    d_model: int = 256
+    n_head: int = 8
+    d_ffn: int = 1024
+    n_layers: int = 8         # transformer layers of each intra / inter model
+    n_blocks: int = 2         # dual computation blocks
+    segment: int = 250        # chunk length K (50 % overlap)
+    n_spk: int = 2
+
+
+def synthetic_dualpath_state_dict(dims: DualPathDims, seed: int = 0, pos_enc_buffers: bool = False) -> Dict[str, torch.Tensor]:
+    """Seeded weights in the key layout of the published dual-path checkpoints (`encoder.ckpt`, `masknet.ckpt`, `decoder.ckpt`, each
+    prefixed with its module name).  `masknet.conv2d` is source-major: row s * N + c is channel c of source s.  pos_enc_buffers adds
+    the `....pos_enc.pe` buffers a real checkpoint carries (the loader ignores them)."""
+    g = torch.Generator().manual_seed(seed)
+    N, D, Fd = dims.n_filters, dims.d_model, dims.d_ffn
+    rn = lambda *s: torch.randn(*s, generator=g)
+    sd: Dict[str, torch.Tensor] = {}
+    sd["encoder.conv1d.weight"] = rn(N, 1, dims.kernel) / math.sqrt(dims.kernel) * 2.0
+    sd["decoder.weight"] = rn(N, 1, dims.kernel) / math.sqrt(N)
+    sd["masknet.norm.weight"] = 1 + 0.1 * rn(N)
+    sd["masknet.norm.bias"] = 0.1 * rn(N)
+    sd["masknet.conv1d.weight"] = rn(N, N, 1) / math.sqrt(N)
+    for b in range(dims.n_blocks):
+        for part in ("intra", "inter"):
+            prefix = f"masknet.dual_mdl.{b}.{part}_mdl"
+            for l in range(dims.n_layers):
+                p = f"{prefix}.mdl.layers.{l}"
+                sd[p + ".self_att.att.in_proj_weight"] = rn(3 * D, D) / math.sqrt(D)
+                sd[p + ".self_att.att.in_proj_bias"] = 0.1 * rn(3 * D)
+                sd[p + ".self_att.att.out_proj.weight"] = rn(D, D) / math.sqrt(D)
+                sd[p + ".self_att.att.out_proj.bias"] = 0.1 * rn(D)
+                sd[p + ".pos_ffn.ffn.0.weight"] = rn(Fd, D) / math.sqrt(D)
+                sd[p + ".pos_ffn.ffn.0.bias"] = 0.1 * rn(Fd)
+                sd[p + ".pos_ffn.ffn.3.weight"] = rn(D, Fd) / math.sqrt(Fd)
+                sd[p + ".pos_ffn.ffn.3.bias"] = 0.1 * rn(D)
+                for nm in ("norm1", "norm2"):
+                    sd[f"{p}.{nm}.norm.weight"] = 1 + 0.1 * rn(D)
+                    sd[f"{p}.{nm}.norm.bias"] = 0.1 * rn(D)
+            sd[prefix + ".mdl.norm.norm.weight"] = 1 + 0.1 * rn(D)
+            sd[prefix + ".mdl.norm.norm.bias"] = 0.1 * rn(D)
+            if pos_enc_buffers:
+                sd[prefix + ".pos_enc.pe"] = torch.zeros(1, 2500, D)
+            sd[f"masknet.dual_mdl.{b}.{part}_norm.weight"] = 1 + 0.1 * rn(N)
+            sd[f"masknet.dual_mdl.{b}.{part}_norm.bias"] = 0.1 * rn(N)
+    sd["masknet.prelu.weight"] = torch.tensor([0.25])
+    sd["masknet.conv2d.weight"] = rn(N * dims.n_spk, N, 1, 1) / math.sqrt(N)
+    sd["masknet.conv2d.bias"] = 0.1 * rn(N * dims.n_spk)
+    sd["masknet.output.0.weight"] = rn(N, N, 1) / math.sqrt(N)
+    sd["masknet.output.0.bias"] = 0.1 * rn(N)
+    sd["masknet.output_gate.0.weight"] = rn(N, N, 1) / math.sqrt(N)
+    sd["masknet.output_gate.0.bias"] = 0.1 * rn(N)
+    sd["masknet.end_conv1x1.weight"] = rn(N, N, 1) / math.sqrt(N)
+    return sd
+
+
+def sepformer_family(sd: Dict[str, torch.Tensor]) -> str:
+    """"dualpath" for a state dict with `masknet.dual_mdl.0....` keys, "resepformer" for one with `masknet.model....` keys."""
+    if any(k.startswith("masknet.dual_mdl.0.") for k in sd):
+        return "dualpath"
+    if any(k.startswith("masknet.model.") for k in sd):
+        return "resepformer"
+    raise ValueError("neither masknet.dual_mdl.0.* nor masknet.model.* keys: not a SepFormer state dict")
+
+
+def dual_path_dims_from_state_dict(sd: Dict[str, torch.Tensor], segment: Optional[int] = None) -> DualPathDims:
+    """The geometry of a flat dual-path state dict, from tensor shapes and key counts: `n_filters` / `kernel` from
+    `encoder.conv1d.weight` [N, 1, k] (stride = k / 2), `n_spk` from `masknet.conv2d.weight` [N * n_spk, N, 1, 1], `d_model` from the
+    first layer's in_proj_weight [3 D, D], `d_ffn` from its `pos_ffn.ffn.0.weight`, `n_blocks` / `n_layers` by counting.  The chunk
+    length K leaves no trace in the weights: `segment` (a savedir's hyperparams.yaml, dual_path_segment_from_yaml) or the published
+    250.  Refuses by name the tensors of use_global_pos_enc (`masknet.pos_enc.*`) and linear_layer_after_inter_intra
+    (`....intra_linear.*` / `....inter_linear.*`): neither is built, both are off in the published hparams."""
+    import re
+    for k in sd:
+        if k.startswith("masknet.pos_enc."):
+            raise ValueError(f"'{k}': the checkpoint was trained with use_global_pos_enc, which is not built")
+        if ".intra_linear." in k or ".inter_linear." in k:
+            raise ValueError(f"'{k}': the checkpoint was trained with linear_layer_after_inter_intra, which is not built")
+    base = DualPathDims()
+    enc, fc = sd["encoder.conv1d.weight"], sd["masknet.conv2d.weight"]
+    n_filters, kernel = int(enc.shape[0]), int(enc.shape[-1])
+    if fc.shape[0] % n_filters:
+        raise ValueError(f"masknet.conv2d.weight has {fc.shape[0]} rows, no multiple of the {n_filters} encoder filters")
+    blocks = {int(m.group(1)) for k in sd for m in [re.match(r"masknet\.dual_mdl\.(\d+)\.", k)] if m}
+    layers = {int(m.group(1)) for k in sd for m in [re.match(r"masknet\.dual_mdl\.0\.intra_mdl\.mdl\.layers\.(\d+)\.", k)] if m}
+    if not blocks or not layers:
+        raise ValueError("no masknet.dual_mdl.<b>.intra_mdl.mdl.layers.<l> keys: not a dual-path SepFormer state dict")
+    p = "masknet.dual_mdl.0.intra_mdl.mdl.layers.0"
+    return DualPathDims(n_filters=n_filters, kernel=kernel, stride=kernel // 2, d_model=int(sd[p + ".self_att.att.in_proj_weight"].shape[1]),
+                        n_head=base.n_head, d_ffn=int(sd[p + ".pos_ffn.ffn.0.weight"].shape[0]), n_layers=max(layers) + 1,
+                        n_blocks=max(blocks) + 1, segment=int(segment) if segment else base.segment, n_spk=int(fc.shape[0]) // n_filters)
+
+
+def dual_path_segment_from_yaml(savedir: str) -> Optional[int]:
+    """The chunk length of a dual-path savedir: the `K: <int>` line of its hyperparams.yaml (the masknet's `K: 250` argument in the
+    published files), or None when there is no such file or line.  The file is read as text, never evaluated."""
+    import re
+    path = os.path.join(savedir, "hyperparams.yaml")
+    if not os.path.exists(path):
+        return None
+    with open(path, "r", encoding="utf-8", errors="replace") as f:
+        for line in f:
+            m = re.match(r"\s*K:\s*(\d+)\s*(#.*)?$", line)
+            if m:
+                return int(m.group(1))
+    return None
+
+
+def find_separator_checkpoint(cache_dir: Optional[str] = None, subdir: str = "resepformer",
+                              apply_ft_overlay: Optional[bool] = None):
+    """find_sepformer_checkpoint + which family it found: None, or (family, state dict, dims) with family "resepformer" (dims: SepDims)
+    or "dualpath" (dims: DualPathDims, the chunk length from the savedir's hyperparams.yaml when it has one)."""
+    sd = find_sepformer_checkpoint(cache_dir, apply_ft_overlay, subdir)
+    if sd is None:
+        return None
+    family = sepformer_family(sd)
+    if family == "resepformer":
+        return family, sd, sep_dims_from_state_dict(sd)
+    base = os.path.join(cache_dir or os.environ.get("MODEL_CACHE_DIR", "models"), subdir)
+    return family, sd, dual_path_dims_from_state_dict(sd, dual_path_segment_from_yaml(base))
+
+
 def find_sepformer_checkpoint(cache_dir: Optional[str] = None, apply_ft_overlay: Optional[bool] = None,
                               subdir: str = "resepformer") -> Optional[Dict[str, torch.Tensor]]:
     """SpeechBrain savedir layout the reference uses (back/api.py:713-717): `<cache>/resepformer/{encoder,masknet,decoder}.ckpt`,
     each the state_dict of that module.  Returns one flat dict with `encoder.` / `masknet.` / `decoder.` prefixes, or None when
     the base checkpoint is absent.  Files are read with weights_only=True.  `subdir` names another savedir under the cache, such as
     `resepformer-wsj03mix` for the three-speaker model (sep_dims_from_state_dict reads its geometry); the default is the reference's.
+    A savedir of the dual-path SepFormer (`sepformer-wsj03mix`, ...) comes back the same way, one flat dict: sepformer_family tells the
+    two apart by their keys, find_separator_checkpoint returns the family and its geometry with the weights.
 
     The fine-tune overlay `<cache>/resepformer-ft/`: the reference calls
     `self.separator.load_state_dict({'masknet': {...}, 'encoder': {...}, 'decoder': {...}}, strict=False)` (back/api.py:739-746).

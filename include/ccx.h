@@ -1010,6 +1010,67 @@ typedef struct ccx_sep_desc {
 
 int ccx_sep_op(ccx_ctx* ctx, int op, const ccx_sep_desc* desc, void* stream);
 
+/* ---- dual-path SepFormer separator (SpeechBrain's Dual_Path_Model: sepformer-wsj02mix / -wsj03mix / -wham / -whamr / -libri2mix /
+ *      -libri3mix and the one-source enhancement models; csrc/dualpath.hip).  Opt-in: nothing else of the library calls it. -----
+ * Restated from recollection [UPSTREAM-RECALL], parity unpinned (tests/dualpath_reference.py is the fp64 statement it is checked
+ * against).  The geometry: n_filters == d_model == 256, n_head == 8 (heads of 32), kernel even in [2, 32] with stride == kernel / 2,
+ * segment K even in [2, 256] (chunks at 50 % overlap), d_ffn a multiple of 64 in [64, 2048], n_layers and n_blocks in [1, 8], n_spk
+ * in [1, 3]; anything else is CCX_ERR_ARG naming the field, before any allocation.  max_tokens counts chunk rows, S K per utterance
+ * with S = 2 (L + gap + K / 2) / K chunks, gap = K - (K / 2 + L % K) % K, L = (T - kernel) / stride + 1 frames. */
+typedef struct ccx_dualpath ccx_dualpath;
+typedef struct {
+  int n_filters, kernel, stride, d_model, n_head, d_ffn, n_layers, n_blocks, segment, n_spk;
+} ccx_dualpath_dims;
+
+int ccx_dualpath_create(ccx_ctx* ctx, const ccx_dualpath_dims* dims, int max_tokens, int max_utts, ccx_dualpath** out);
+void ccx_dualpath_destroy(ccx_dualpath* s);
+/* Tensors by SpeechBrain checkpoint key with the module prefix: "encoder.conv1d.weight", "decoder.weight", "masknet.norm.weight",
+ * "masknet.conv1d.weight", "masknet.dual_mdl.<b>.{intra,inter}_mdl.mdl.layers.<l>....", "masknet.dual_mdl.<b>.{intra,inter}_norm.*",
+ * "masknet.prelu.weight", "masknet.conv2d.*" (row s 256 + c: source s, channel c), "masknet.output.0.*", "masknet.output_gate.0.*",
+ * "masknet.end_conv1x1.weight".  f32.  "....pos_enc.pe" buffers of the transformers are accepted and ignored; "masknet.pos_enc.*"
+ * (use_global_pos_enc) and "....intra_linear.*" / "....inter_linear.*" (linear_layer_after_inter_intra) are refused by name. */
+int ccx_dualpath_set_tensor(ccx_dualpath* s, const char* name, const float* data, int64_t numel);
+int ccx_dualpath_finalize(ccx_dualpath* s);
+/* mix_dev [B, stride] f32, n_samples host [B] (kernel <= n_samples[b] <= stride) -> out_dev [B, stride, n_spk] f32, the sources
+ * interleaved per sample, zero from n_samples[b] on.  Rows are independent utterances. */
+int ccx_dualpath_separate(ccx_dualpath* s, const float* mix_dev, int64_t stride, const int* n_samples, int B, float* out_dev,
+                          void* stream);
+
+/* ---- the dual-path kernels on their own (for kernel parity tests; the product path does not call this).  One descriptor, one op
+ *      code.  Device pointers come with the element count (of the buffer's own type) behind them; tables are HOST arrays, checked
+ *      and uploaded into scratch that is freed on every path.  Everything the kernels assume is checked on the host before anything is
+ *      launched; a violation returns CCX_ERR_ARG (1) with a message naming "ccx_dualpath_op" and the field.  Synchronises the stream.
+ *      `rows` is the row count of token buffers, `frames` of frame buffers; every row holds 256 channels unless stated. */
+#define CCX_DP_ATTENTION 0    /* in = qkv bf16 [rows][768] -> out bf16 [rows][256]; seq_first / seq_stride / seq_len [n_seq] */
+#define CCX_DP_GROUP_NORM 1   /* in f32 [rows][256], utterance u = rows [utt_row0[u], + utt_rows[u]); w = gamma, w2 = beta f32 [256].
+                                 mode 0: out f32 = norm + in2 (skip, f32 [rows][256]; may be `out` itself); mode 1: out bf16, no skip */
+#define CCX_DP_SEGMENT 2      /* in f32 [frames][256] -> out f32 [rows][256]: chunks of `segment` at 50 % overlap, padding zeroed */
+#define CCX_DP_OVERLAP_ADD 3  /* in f32 [rows][256 n_spk] -> out bf16 [frames n_spk][256], row (frame0 + l) n_spk + s */
+#define CCX_DP_PE_ADD 4       /* out f32 = in f32 + w[pos][:], pos = position in the chunk (mode 0) or chunk index (mode 1); w f32 [.][256] */
+#define CCX_DP_GATE 5         /* in f32 [rows][512] -> out bf16 [rows][256] = tanh(in[r][c]) sigmoid(in[r][256 + c]) */
+#define CCX_DP_ENCODER 6      /* in = mix f32 [n_utt][in_stride], w f32 [256][kernel] -> out f32 [frames][256], ReLU */
+#define CCX_DP_DECODER 7      /* in = feats f32 [frames][256], in2 = mask f32 [frames n_spk][256], w = wdec f32 [256][kernel]
+                                 -> out f32 [n_utt][out_stride][n_spk] */
+#define CCX_DP_PRELU 8        /* in f32 [rows][256], w = slope f32 [1] -> out bf16 [rows][256] */
+
+typedef struct ccx_dualpath_desc {
+  const void* in; const void* in2; void* out; const void* w; const void* w2;
+  int64_t in_elems, in2_elems, out_elems, w_elems, w2_elems;
+  int rows, frames, mode;
+  /* op 0: HOST tables of n_seq sequences: first row >= 0, row stride >= 1, length >= 1, the last row inside [0, rows) */
+  const int* seq_first; const int* seq_stride; const int* seq_len; int n_seq;
+  /* op 1: HOST tables of n_utt row ranges inside [0, rows) */
+  const int* utt_row0; const int* utt_rows;
+  /* ops 2, 3, 4: HOST tables of n_utt utterances: first token row, first frame row, frames L >= 1, gap and S as the rule above gives
+   * them for `segment` (checked), the S segment rows inside [0, rows), the L frames inside [0, frames).  ops 6, 7: utt_frame0, utt_L
+   * and samples utt_T; op 6: utt_L == (utt_T - kernel) / (kernel / 2) + 1, utt_T <= in_stride; op 7: 1 <= utt_T <= out_stride */
+  const int* utt_tok0; const int* utt_frame0; const int* utt_L; const int* utt_gap; const int* utt_S; const int* utt_T; int n_utt;
+  int segment, kernel, n_spk;
+  int64_t in_stride, out_stride;
+} ccx_dualpath_desc;
+
+int ccx_dualpath_op(ccx_ctx* ctx, int op, const ccx_dualpath_desc* desc, void* stream);
+
 /* ---- pyannote-style speaker networks (replace self.embedding_model = Inference("pyannote/embedding",
  *      window="whole"), reference back/api.py:776-780, called at back/api.py:869; and the segmentation
  *      network inside self.vad_pipeline / self.diarization, reference back/api.py:782-792, called at
