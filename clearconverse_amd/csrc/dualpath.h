@@ -30,8 +30,6 @@ int ccx_launch_dp_pe_add(ccx_ctx* ctx, const float* x, const ccx_dp_utt* utt, in
                          float* out, hipStream_t st);
 // out bf16 [rows][256] = tanh(g[r][c]) * sigmoid(g[r][256 + c]) from g f32 [rows][512]
 int ccx_launch_dp_gate(ccx_ctx* ctx, const float* g, bf16_t* out, long rows, hipStream_t st);
-// out bf16 = x >= 0 ? x : slope[0] x over n f32 values (n a multiple of 4)
-int ccx_launch_dp_prelu(ccx_ctx* ctx, const float* x, const float* slope, bf16_t* out, long n, hipStream_t st);
 // frames [frame0 + l][c] = relu(sum_k w[c][k] mix[u][stride l + k]), stride = kernel / 2, l < L
 int ccx_launch_dp_encoder(ccx_ctx* ctx, const float* mix, long mix_stride, const ccx_dp_utt* utt, int n_utt, int max_L, int kernel,
                           const float* w, float* frames, hipStream_t st);

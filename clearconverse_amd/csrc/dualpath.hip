@@ -16,10 +16,11 @@
 #include "gemm_bf16.h"
 #include "model_store.h"
 #include "op_scratch.h"
+#include "sb_softmax.h"
+#include "sb_stack.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short bf16x4v;
 constexpr int D = CCX_DP_D;
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -27,8 +28,7 @@ constexpr int D = CCX_DP_D;
 // 16-query tile); a block is four heads.  S^T = K Q^T with ONE v_mfma_f32_16x16x32_bf16 per 16-key tile (the whole head in one
 // K-step), so a lane owns one query column and four keys of it; those accumulator registers are, unchanged, the A operand of
 // O = P V (v_mfma_f32_16x16x16_bf16: row = query, k = key), two of them for the 32 output columns.  Online softmax over blocks of
-// CCX_DP_KEY_BLOCK keys.  Rounding points as in sep_attention_kernel: q, k, v arrive as bf16; the un-normalised p is rounded to bf16
-// as the P V operand while the normaliser sums the unrounded p; O / l is rounded on the store.
+// CCX_DP_KEY_BLOCK keys: the step and its rounding rule are sb_softmax.h, shared with sep_attention_kernel; q, k, v arrive as bf16.
 // Rows past a sequence's length are never read: loads clamp to its last row, those keys score -inf, those queries are not stored.
 // ---------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dp_attention_kernel(const bf16_t* __restrict__ qkv, const int* __restrict__ seq,
@@ -45,54 +45,30 @@ __global__ __launch_bounds__(256) void dp_attention_kernel(const bf16_t* __restr
   const bf16x8 qf = *(const bf16x8*)(base + row_of(qt * 16 + l15) * (3 * D) + 8 * h4);
   float m_run = -1e30f, l_run = 0.f;
   f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;                        // O tiles: col = d (l15 / 16 + l15), rows = query 4 h4 + r
-  for (int kt0 = 0; kt0 < n_kt; kt0 += CCX_DP_KEY_BLOCK / 16) {
-    const int nk = (n_kt - kt0) < CCX_DP_KEY_BLOCK / 16 ? (n_kt - kt0) : CCX_DP_KEY_BLOCK / 16;
-    f32x4 s[CCX_DP_KEY_BLOCK / 16];
-    float mx = -1e30f;
+  constexpr int NT = CCX_DP_KEY_BLOCK / 16;
+  for (int kt0 = 0; kt0 < n_kt; kt0 += NT) {
+    const int nk = (n_kt - kt0) < NT ? (n_kt - kt0) : NT;
+    f32x4 s[NT];
 #pragma unroll
-    for (int t = 0; t < CCX_DP_KEY_BLOCK / 16; t++) {
+    for (int t = 0; t < NT; t++)
       if (t < nk) {
         // A operand: K[key l15][d = 8 h4 + j]
         const bf16x8 kf = *(const bf16x8*)(base + D + row_of((kt0 + t) * 16 + l15) * (3 * D) + 8 * h4);
         s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         // s[t][r] = score(query l15, key (kt0 + t) 16 + 4 h4 + r)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          if ((kt0 + t) * 16 + 4 * h4 + r >= len) s[t][r] = -INFINITY;
-          mx = fmaxf(mx, s[t][r]);
-        }
-      } else {
-        s[t] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
       }
-    }
-    mx = fmaxf(mx, lane_xor16(mx));
-    mx = fmaxf(mx, lane_xor32(mx));
-    mx = fmaxf(m_run, mx * scale_log2e);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - mx);
-    m_run = mx;
-    float ps = 0.f;
-#pragma unroll
-    for (int t = 0; t < CCX_DP_KEY_BLOCK / 16; t++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const float pv = __builtin_amdgcn_exp2f(fmaf(s[t][r], scale_log2e, -mx));   // exp2(-inf) = 0 for a masked key
-        s[t][r] = pv;
-        ps += pv;
-      }
-    l_run = l_run * alpha + ps;
-    // alpha belongs to query l15 but the O tiles hold queries 4 h4 + r on their rows: fetch per row
+    const float alpha = nk == NT ? sb_online_step<NT, true>(s, nk, kt0 * 16, len, h4, scale_log2e, m_run, l_run)
+                                 : sb_online_step<NT, false>(s, nk, kt0 * 16, len, h4, scale_log2e, m_run, l_run);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-      const float a = __shfl(alpha, 4 * h4 + r, 64);
+      const float a = sb_row_value(alpha, h4, r);
       o0[r] *= a;
       o1[r] *= a;
     }
 #pragma unroll
-    for (int t = 0; t < CCX_DP_KEY_BLOCK / 16; t++) {
+    for (int t = 0; t < NT; t++)
       if (t < nk) {
-        union { bf16x4v v; uint32_t u[2]; } pa;                      // A operand: P[query l15][key 4 h4 + j]
-        pa.u[0] = pack_bf16x2(s[t][0], s[t][1]);
-        pa.u[1] = pack_bf16x2(s[t][2], s[t][3]);
+        const bf16x4v pa = sb_pack_p(s[t]);                          // A operand: P[query l15][key 4 h4 + j]
         bf16x4v v0, v1;                                              // B operand: V[key 4 h4 + j][d = l15 (+ 16)]
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -100,17 +76,15 @@ __global__ __launch_bounds__(256) void dp_attention_kernel(const bf16_t* __restr
           v0[j] = (short)vr[l15];
           v1[j] = (short)vr[16 + l15];
         }
-        o0 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pa.v, v0, o0, 0, 0, 0);
-        o1 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pa.v, v1, o1, 0, 0, 0);
+        o0 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pa, v0, o0, 0, 0, 0);
+        o1 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pa, v1, o1, 0, 0, 0);
       }
-    }
   }
-  float lt = l_run + lane_xor16(l_run);
-  lt += lane_xor32(lt);
+  const float lt = sb_query_sum(l_run);
 #pragma unroll
   for (int r = 0; r < 4; r++) {
     const int q = qt * 16 + 4 * h4 + r;
-    const float inv = 1.0f / __shfl(lt, 4 * h4 + r, 64);
+    const float inv = 1.0f / sb_row_value(lt, h4, r);
     if (q < len) {
       bf16_t* o = out + ((long)first + (long)q * stride) * D + head * 32;
       o[l15] = f32_to_bf16(o0[r] * inv);
@@ -244,17 +218,6 @@ __global__ void dp_gate_kernel(const float* __restrict__ g, bf16_t* __restrict__
   ((uint2*)out)[i] = o;
 }
 
-__global__ void dp_prelu_kernel(const float* __restrict__ x, const float* __restrict__ slope, bf16_t* __restrict__ out, long n4) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const float a = slope[0];
-  const float4 v = ((const float4*)x)[i];
-  uint2 o;
-  o.x = pack_bf16x2(v.x >= 0 ? v.x : a * v.x, v.y >= 0 ? v.y : a * v.y);
-  o.y = pack_bf16x2(v.z >= 0 ? v.z : a * v.z, v.w >= 0 ? v.w : a * v.w);
-  ((uint2*)out)[i] = o;
-}
-
 // Encoder: Conv1d(1 -> 256, kernel, stride kernel / 2, no bias) + ReLU, frame-major.  One wave per frame, four filters per lane.
 __global__ __launch_bounds__(256) void dp_encoder_kernel(const float* __restrict__ mix, long mix_stride, const ccx_dp_utt* __restrict__ utt,
                                                          int kernel, const float* __restrict__ w, float* __restrict__ frames) {
@@ -323,15 +286,6 @@ __global__ __launch_bounds__(256) void dp_decoder_kernel(const float* __restrict
   const long t = t0 + lane / NSPK;
   if (lane < stride * NSPK && t < out_stride) out[((long)blockIdx.y * out_stride + t0) * NSPK + lane] = t < U.T ? res : 0.f;
 }
-
-struct DpLayer {
-  float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *bqkv, *bo, *b1, *b2;
-  bf16_t *Wqkv, *Wo, *W1, *W2;
-};
-struct DpTransformer {
-  std::vector<DpLayer> layers;
-  float *lnf_g, *lnf_b, *gn_g, *gn_b;
-};
 
 }  // namespace
 
@@ -403,16 +357,6 @@ int ccx_launch_dp_gate(ccx_ctx* ctx, const float* g, bf16_t* out, long rows, hip
   return CCX_OK;
 }
 
-int ccx_launch_dp_prelu(ccx_ctx* ctx, const float* x, const float* slope, bf16_t* out, long n, hipStream_t st) {
-  const long n4 = n / 4;
-  {
-    ccx_prof_scope ps(ctx, st, "dp_prelu_kernel", 0.0, 0.0);
-    hipLaunchKernelGGL(dp_prelu_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, slope, out, n4);
-  }
-  CCX_CHECK_LAUNCH(ctx);
-  return CCX_OK;
-}
-
 int ccx_launch_dp_encoder(ccx_ctx* ctx, const float* mix, long mix_stride, const ccx_dp_utt* utt, int n_utt, int max_L, int kernel,
                           const float* w, float* frames, hipStream_t st) {
   {
@@ -451,7 +395,7 @@ struct ccx_dualpath {
   ccx_dev_store store{"dualpath"};
   float *w_enc = nullptr, *w_dec = nullptr, *gn0_g = nullptr, *gn0_b = nullptr, *prelu = nullptr, *b_fc = nullptr, *b_og = nullptr, *pe = nullptr;
   bf16_t *W_in = nullptr, *W_fc = nullptr, *W_og = nullptr, *W_end = nullptr;
-  std::vector<DpTransformer> intra, inter;
+  std::vector<SbStack> intra, inter;
   // workspaces: frame buffers [frames][256], token buffers [tokens][.]
   float *feats = nullptr, *xf = nullptr, *x = nullptr, *h = nullptr, *y = nullptr, *fc = nullptr, *g2 = nullptr, *mk = nullptr, *part = nullptr;
   bf16_t *xn = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *ya = nullptr, *yb = nullptr;
@@ -475,32 +419,6 @@ int dp_check_dims(ccx_ctx* ctx, const ccx_dualpath_dims& d) {
   return CCX_OK;
 }
 
-int dp_load_transformer(ccx_dualpath* s, const std::string& prefix, const std::string& norm, DpTransformer& B) {
-  const int F = s->d.d_ffn;
-  B.layers.resize(s->d.n_layers);
-  for (int l = 0; l < s->d.n_layers; l++) {
-    const std::string p = prefix + ".mdl.layers." + std::to_string(l);
-    DpLayer& L = B.layers[l];
-    CCX_NEED(s->store, wi, p + ".self_att.att.in_proj_weight", 3 * D, D); CCX_NEED(s->store, bi, p + ".self_att.att.in_proj_bias", 3 * D);
-    CCX_NEED(s->store, wo, p + ".self_att.att.out_proj.weight", D, D); CCX_NEED(s->store, bo, p + ".self_att.att.out_proj.bias", D);
-    CCX_NEED(s->store, w1, p + ".pos_ffn.ffn.0.weight", F, D); CCX_NEED(s->store, b1, p + ".pos_ffn.ffn.0.bias", F);
-    CCX_NEED(s->store, w2, p + ".pos_ffn.ffn.3.weight", D, F); CCX_NEED(s->store, b2, p + ".pos_ffn.ffn.3.bias", D);
-    CCX_NEED(s->store, g1, p + ".norm1.norm.weight", D); CCX_NEED(s->store, be1, p + ".norm1.norm.bias", D);
-    CCX_NEED(s->store, g2, p + ".norm2.norm.weight", D); CCX_NEED(s->store, be2, p + ".norm2.norm.bias", D);
-    CCX_TRY(s->store.upload_bf16(&L.Wqkv, wi->data)); CCX_TRY(s->store.upload(&L.bqkv, bi->data));
-    CCX_TRY(s->store.upload_bf16(&L.Wo, wo->data)); CCX_TRY(s->store.upload(&L.bo, bo->data));
-    CCX_TRY(s->store.upload_bf16(&L.W1, w1->data)); CCX_TRY(s->store.upload(&L.b1, b1->data));
-    CCX_TRY(s->store.upload_bf16(&L.W2, w2->data)); CCX_TRY(s->store.upload(&L.b2, b2->data));
-    CCX_TRY(s->store.upload(&L.ln1_g, g1->data)); CCX_TRY(s->store.upload(&L.ln1_b, be1->data));
-    CCX_TRY(s->store.upload(&L.ln2_g, g2->data)); CCX_TRY(s->store.upload(&L.ln2_b, be2->data));
-  }
-  CCX_NEED(s->store, fg, prefix + ".mdl.norm.norm.weight", D); CCX_NEED(s->store, fb, prefix + ".mdl.norm.norm.bias", D);
-  CCX_NEED(s->store, gg, norm + ".weight", D); CCX_NEED(s->store, gb, norm + ".bias", D);
-  CCX_TRY(s->store.upload(&B.lnf_g, fg->data)); CCX_TRY(s->store.upload(&B.lnf_b, fb->data));
-  CCX_TRY(s->store.upload(&B.gn_g, gg->data)); CCX_TRY(s->store.upload(&B.gn_b, gb->data));
-  return CCX_OK;
-}
-
 int dp_gemm(ccx_ctx* ctx, int epi, const bf16_t* A, const bf16_t* W, int M, int N, int K, const float* bias, void* out, const float* resid,
             hipStream_t st) {
   GemmParams p;
@@ -510,12 +428,12 @@ int dp_gemm(ccx_ctx* ctx, int epi, const bf16_t* A, const bf16_t* W, int M, int 
 }
 
 // x += GroupNorm(transformer(x + pe)) over the sequences of `seq`: one SBTransformerBlock + the norm and skip of a dual block half
-int dp_run_transformer(ccx_dualpath* s, const DpTransformer& B, const int* seq, int n_seq, int max_len, int axis, int n_tok, int n_utt,
+int dp_run_transformer(ccx_dualpath* s, const SbStack& B, const int* seq, int n_seq, int max_len, int axis, int n_tok, int n_utt,
                        int max_S, hipStream_t st) {
   ccx_ctx* ctx = s->ctx;
   const int F = s->d.d_ffn, K = s->d.segment;
   CCX_TRY(ccx_launch_dp_pe_add(ctx, s->x, s->utt, n_utt, K, max_S, axis, s->pe, s->h, st));
-  for (const DpLayer& L : B.layers) {
+  for (const SbLayer& L : B.layers) {
     CCX_TRY(ccx_launch_layernorm(ctx, s->h, D, L.ln1_g, L.ln1_b, s->xn, nullptr, D, n_tok, D, 1e-6f, st));
     CCX_TRY(dp_gemm(ctx, EPI_BF16, s->xn, L.Wqkv, n_tok, 3 * D, D, L.bqkv, s->qkv, nullptr, st));
     CCX_TRY(ccx_launch_dp_attention(ctx, s->qkv, seq, n_seq, max_len, s->att, st));
@@ -525,7 +443,7 @@ int dp_run_transformer(ccx_dualpath* s, const DpTransformer& B, const int* seq, 
     CCX_TRY(dp_gemm(ctx, EPI_F32_RESID, s->hid, L.W2, n_tok, D, F, L.b2, s->h, s->h, st));
   }
   CCX_TRY(ccx_launch_layernorm(ctx, s->h, D, B.lnf_g, B.lnf_b, nullptr, s->y, D, n_tok, D, 1e-6f, st));
-  return ccx_launch_dp_group_norm(ctx, s->y, s->gn_tok, n_utt, max_S * K, B.gn_g, B.gn_b, s->x, s->x, nullptr, s->part, st);
+  return ccx_launch_dp_group_norm(ctx, s->y, s->gn_tok, n_utt, max_S * K, B.norm_g, B.norm_b, s->x, s->x, nullptr, s->part, st);
 }
 
 }  // namespace
@@ -597,23 +515,14 @@ int ccx_dualpath_finalize(ccx_dualpath* s) {
   s->inter.resize(d.n_blocks);
   for (int i = 0; i < d.n_blocks; i++) {
     const std::string b = "masknet.dual_mdl." + std::to_string(i);
-    CCX_TRY(dp_load_transformer(s, b + ".intra_mdl", b + ".intra_norm", s->intra[i]));
-    CCX_TRY(dp_load_transformer(s, b + ".inter_mdl", b + ".inter_norm", s->inter[i]));
+    CCX_TRY(sb_load_stack(s->store, b + ".intra_mdl", b + ".intra_norm", d.n_layers, D, F, s->intra[i]));
+    CCX_TRY(sb_load_stack(s->store, b + ".inter_mdl", b + ".inter_norm", d.n_layers, D, F, s->inter[i]));
   }
   s->store.staged.clear();
   // positional encoding table (interleaved sin / cos), long enough for a chunk and for the longest inter-chunk sequence
   const int max_chunks = s->max_tokens / d.segment;
   s->pe_len = d.segment > max_chunks ? d.segment : max_chunks;
-  {
-    std::vector<float> pe((size_t)s->pe_len * D);
-    for (int p = 0; p < s->pe_len; p++)
-      for (int i = 0; i < D; i += 2) {
-        const float den = expf((float)i * -(logf(10000.0f) / (float)D));
-        pe[(size_t)p * D + i] = sinf((float)p * den);
-        pe[(size_t)p * D + i + 1] = cosf((float)p * den);
-      }
-    CCX_TRY(s->store.upload(&s->pe, pe));
-  }
+  CCX_TRY(s->store.upload(&s->pe, sb_pos_enc_table(s->pe_len, D)));
   // frames of a call never exceed half its token rows (S K / 2 = L + gap + K / 2 per utterance)
   const size_t T = (size_t)s->max_tokens, Fr = T / 2 + 1, U = (size_t)s->max_utts;
   CCX_TRY(s->store.alloc(&s->feats, Fr * D, true)); CCX_TRY(s->store.alloc(&s->xf, Fr * D, true));
@@ -678,7 +587,7 @@ int ccx_dualpath_separate(ccx_dualpath* s, const float* mix, int64_t stride, con
     CCX_TRY(dp_run_transformer(s, s->intra[i], s->seq_intra, n_intra, K, 0, nt, B, max_S, st));
     CCX_TRY(dp_run_transformer(s, s->inter[i], s->seq_inter, n_inter, max_S, 1, nt, B, max_S, st));
   }
-  CCX_TRY(ccx_launch_dp_prelu(ctx, s->x, s->prelu, s->xn, (long)nt * D, st));
+  CCX_TRY(ccx_launch_prelu_bf16(ctx, s->x, s->prelu, s->xn, (long)nt * D, "dp_prelu_kernel", st));
   CCX_TRY(dp_gemm(ctx, EPI_F32, s->xn, s->W_fc, nt, NS * D, D, s->b_fc, s->fc, nullptr, st));
   CCX_TRY(ccx_launch_dp_overlap_add(ctx, s->fc, s->utt, B, K, max_L, NS, s->ya, st));
   CCX_TRY(dp_gemm(ctx, EPI_F32, s->ya, s->W_og, nf * NS, 2 * D, D, s->b_og, s->g2, nullptr, st));
@@ -850,7 +759,7 @@ int ccx_dualpath_op(ccx_ctx* ctx, int op, const ccx_dualpath_desc* d, void* stre
                                  (long)d->out_stride, st);
       break;
     default:
-      rc = ccx_launch_dp_prelu(ctx, (const float*)d->in, (const float*)d->w, (bf16_t*)d->out, (long)rows * D, st);
+      rc = ccx_launch_prelu_bf16(ctx, (const float*)d->in, (const float*)d->w, (bf16_t*)d->out, (long)rows * D, "dp_prelu_kernel", st);
   }
   DP_HIP(hipStreamSynchronize(st));      // the scratch is freed on return
   return rc;

@@ -11,6 +11,9 @@ int ccx_launch_layernorm_rows(ccx_ctx* ctx, const float* x, long ldx, const floa
                               long ldo, int M, int D, float eps, int rpb_in, int rpb_out, hipStream_t stream);
 // dst_bf16[i] = bf16(src_f32[i])
 int ccx_launch_f32_to_bf16(ccx_ctx* ctx, const float* src, bf16_t* dst, long n, hipStream_t stream);
+// PReLU with one slope to bf16 (the input of a separator's mask-head GEMM): out = x >= 0 ? x : slope[0] x over n f32 values (n a
+// multiple of 4).  `label` names the profile record; null: none
+int ccx_launch_prelu_bf16(ccx_ctx* ctx, const float* x, const float* slope, bf16_t* out, long n, const char* label, hipStream_t stream);
 int ccx_launch_fill_u16(ccx_ctx* ctx, bf16_t* dst, bf16_t v, long n, hipStream_t stream);
 int ccx_launch_peak_normalize(ccx_ctx* ctx, const float* x, float* y, long stride, const int* n_samples_dev, int B, float eps,
                               hipStream_t stream);

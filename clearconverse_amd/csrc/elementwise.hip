@@ -282,6 +282,29 @@ int ccx_launch_f32_to_bf16(ccx_ctx* ctx, const float* src, bf16_t* dst, long n, 
   return CCX_OK;
 }
 
+namespace {   // the kernel's name as profiles of the default pipeline have always recorded it
+__global__ void sep_prelu_bf16_kernel(const float* __restrict__ x, const float* __restrict__ slope, bf16_t* __restrict__ out, long n4) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const float a = slope[0];
+  const float4 v = ((const float4*)x)[i];
+  uint2 o;
+  o.x = pack_bf16x2(v.x >= 0 ? v.x : a * v.x, v.y >= 0 ? v.y : a * v.y);
+  o.y = pack_bf16x2(v.z >= 0 ? v.z : a * v.z, v.w >= 0 ? v.w : a * v.w);
+  ((uint2*)out)[i] = o;
+}
+}  // namespace
+
+int ccx_launch_prelu_bf16(ccx_ctx* ctx, const float* x, const float* slope, bf16_t* out, long n, const char* label, hipStream_t stream) {
+  const long n4 = n / 4;
+  {
+    ccx_prof_scope ps(label ? ctx : nullptr, stream, label, 0.0, 0.0);
+    hipLaunchKernelGGL(sep_prelu_bf16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, x, slope, out, n4);
+  }
+  CCX_CHECK_LAUNCH(ctx);
+  return CCX_OK;
+}
+
 int ccx_launch_fill_u16(ccx_ctx* ctx, bf16_t* dst, bf16_t v, long n, hipStream_t stream) {
   if (n <= 0) return CCX_OK;
   long blocks = (n + 255) / 256;

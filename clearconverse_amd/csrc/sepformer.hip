@@ -17,11 +17,11 @@
 #include <type_traits>
 #include "gemm_bf16.h"
 #include "model_store.h"
+#include "sb_softmax.h"
+#include "sb_stack.h"
 #include "sepformer.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) short bf16x4v;
 
 // ---------------------------------------------------------------------------------------------
 // Encoder: Conv1d(1 -> N=128, k=16, stride 8, no bias) + ReLU, written token-major [tok, 128] f32.
@@ -134,64 +134,25 @@ __global__ __launch_bounds__(256, 2) void sep_attention_kernel(const bf16_t* __r
           vf[t] = resident ? v_all[t] : load_v(kt0 + t);
         }
       }
-      // s[t][r] = score(query l15, key kt*16 + 4*h4 + r).  The kernel is VALU-bound (16-wide heads): keys past `len` can
-      // only sit in the last key tile, and the scale is folded into the one fma in front of exp2 (m_run is kept scaled).
-      float mx = -1e30f;
+      // s[t][r] = score(query l15, key kt*16 + 4*h4 + r).  The kernel is VALU-bound (16-wide heads): the softmax is sb_softmax.h
+      const float alpha = sb_online_step<10, FULL>(s, nk, kt0 * 16, len, h4, scale_log2e, m_run, l_run);
+#pragma unroll
+      for (int r = 0; r < 4; r++) o[r] *= sb_row_value(alpha, h4, r);
 #pragma unroll
       for (int t = 0; t < 10; t++)
-        if (FULL || t < nk) {
-          if ((kt0 + t) * 16 + 16 > len) {
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-              if ((kt0 + t) * 16 + 4 * h4 + r >= len) s[t][r] = -INFINITY;
-          }
-#pragma unroll
-          for (int r = 0; r < 4; r++) mx = fmaxf(mx, s[t][r]);
-        }
-      mx = fmaxf(mx, lane_xor16(mx));
-      mx = fmaxf(mx, lane_xor32(mx));
-      mx = fmaxf(m_run, mx * scale_log2e);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - mx);
-      m_run = mx;
-      float ps = 0.f;
-#pragma unroll
-      for (int t = 0; t < 10; t++)
-        if (FULL || t < nk) {
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const float pv = __builtin_amdgcn_exp2f(fmaf(s[t][r], scale_log2e, -mx));
-            s[t][r] = pv;
-            ps += pv;
-          }
-        }
-      l_run = l_run * alpha + ps;
-      // alpha belongs to query l15 but the O tile holds queries 4*h4 + r on its rows: fetch per row
-      float arow[4];
-#pragma unroll
-      for (int r = 0; r < 4; r++) arow[r] = __shfl(alpha, 4 * h4 + r, 64);
-#pragma unroll
-      for (int r = 0; r < 4; r++) o[r] *= arow[r];
-#pragma unroll
-      for (int t = 0; t < 10; t++)
-        if (FULL || t < nk) {
-          union { bf16x4v v; uint32_t u[2]; } pa;  // A operand: P[query l15][key 4*h4 + j]
-          pa.u[0] = pack_bf16x2(s[t][0], s[t][1]);
-          pa.u[1] = pack_bf16x2(s[t][2], s[t][3]);
-          o = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pa.v, vf[t], o, 0, 0, 0);
-        }
+        if (FULL || t < nk) o = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(sb_pack_p(s[t]), vf[t], o, 0, 0, 0);
     };
     for (int kt0 = 0; kt0 < n_kt; kt0 += 10) {
       const int nk = (n_kt - kt0) < 10 ? (n_kt - kt0) : 10;
       if (nk == 10) key_block(kt0, 10, std::true_type{});
       else key_block(kt0, nk, std::false_type{});
     }
-    float lt = l_run + lane_xor16(l_run);
-    lt += lane_xor32(lt);
+    const float lt = sb_query_sum(l_run);
     // rows of the O tile are queries 4*h4 + r: fetch their normalisers
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int q = qt * 16 + 4 * h4 + r;
-      const float inv = 1.0f / __shfl(lt, 4 * h4 + r, 64);
+      const float inv = 1.0f / sb_row_value(lt, h4, r);
       if (q < len) out[(long)(s0 + q) * 128 + head * 16 + l15] = f32_to_bf16(o[r] * inv);
     }
   }
@@ -393,7 +354,9 @@ __global__ __launch_bounds__(512) void sep_attn_block_kernel(float* __restrict__
     f32x4 sc[10];
 #pragma unroll
     for (int t = 0; t < 10; t++) sc[t] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(k_all[t], qf, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-    // sc[t][r] = score(query l15, key 16 t + 4 h4 + r)
+    // sc[t][r] = score(query l15, key 16 t + 4 h4 + r): one block, no running state -- the pieces of sb_softmax.h, the exponentials of
+    // a tile in front of its P V MFMA.  The masked maximum restates sb_block_max<10, true>(sc, 10, 0, len, h4): through the call the
+    // compiler lays this loop out differently (and unrolls the query loop), and this kernel's instruction stream is a tuned one
     float mx = -1e30f;
 #pragma unroll
     for (int t = 0; t < 10; t++) {
@@ -412,24 +375,15 @@ __global__ __launch_bounds__(512) void sep_attn_block_kernel(float* __restrict__
     f32x4 o = {0.f, 0.f, 0.f, 0.f};                       // O tile: col = d (l15), rows = query 4 h4 + r
 #pragma unroll
     for (int t = 0; t < 10; t++) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const float pv = __builtin_amdgcn_exp2f(fmaf(sc[t][r], scale_log2e, -mx));
-        sc[t][r] = pv;
-        ps += pv;
-      }
-      union { bf16x4v v; uint32_t u[2]; } pa;              // A operand: P[query l15][key 4 h4 + j]
-      pa.u[0] = pack_bf16x2(sc[t][0], sc[t][1]);
-      pa.u[1] = pack_bf16x2(sc[t][2], sc[t][3]);
-      o = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pa.v, v_all[t], o, 0, 0, 0);
+      sb_exp_tile(sc[t], scale_log2e, mx, ps);
+      o = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(sb_pack_p(sc[t]), v_all[t], o, 0, 0, 0);
     }
-    float lt = ps + lane_xor16(ps);
-    lt += lane_xor32(lt);
+    const float lt = sb_query_sum(ps);
     // rows of the O tile are queries 4 h4 + r: fetch their normalisers; column 16 wave + l15 of the attention output
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int row = qt * 16 + 4 * h4 + r;
-      const float inv = 1.0f / __shfl(lt, 4 * h4 + r, 64);
+      const float inv = 1.0f / sb_row_value(lt, h4, r);
       *(bf16_t*)(xs + ab_off(row, 2 * wave + (l15 >> 3)) + (l15 & 7) * 2) = f32_to_bf16(o[r] * inv);
     }
   }
@@ -641,18 +595,6 @@ __global__ __launch_bounds__(128) void sep_chunk_mean_kernel(const float* __rest
   mem[(long)chunk * 128 + c] = s / (float)seg;
 }
 
-// PReLU (single slope) -> bf16 (input of the output 1x1 conv GEMM)
-__global__ void sep_prelu_bf16_kernel(const float* __restrict__ x, const float* __restrict__ slope, bf16_t* __restrict__ out, long n4) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const float a = slope[0];
-  const float4 v = ((const float4*)x)[i];
-  uint2 o;
-  o.x = pack_bf16x2(v.x >= 0 ? v.x : a * v.x, v.y >= 0 ? v.y : a * v.y);
-  o.y = pack_bf16x2(v.z >= 0 ? v.z : a * v.z, v.w >= 0 ? v.w : a * v.w);
-  ((uint2*)out)[i] = o;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Mask (ReLU) * encoder output, ConvTranspose1d(128 -> 1, k16, s8) overlap-add, pad/trim to T, for NSPK sources:
 //   est[u][t][spk] = sum_{l in {t/8, t/8-1}} sum_c feats[l][c] * relu(fc[l][c*NSPK+spk]) * wdec[c][t-8l]
@@ -726,15 +668,6 @@ __global__ __launch_bounds__(256) void sep_decoder_kernel(const float* __restric
   }
   if (mine) dst[lane] = (t_mine < T) ? res : 0.f;
 }
-
-struct SepLayer {
-  float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *bqkv, *bo, *b1, *b2;
-  bf16_t *Wqkv, *Wo, *W1, *W2;
-};
-struct SepBlock {
-  std::vector<SepLayer> layers;
-  float *lnf_g, *lnf_b, *gln_g, *gln_b;
-};
 
 }  // namespace
 
@@ -812,7 +745,7 @@ struct ccx_sepformer {
   ccx_dev_store store{"sepformer"};
   float *w_enc = nullptr, *w_dec = nullptr, *prelu = nullptr, *b_fc = nullptr, *pe = nullptr;
   bf16_t* W_fc = nullptr;
-  std::vector<SepBlock> seg, mem;
+  std::vector<SbStack> seg, mem;
   // workspaces
   float *feats = nullptr, *x = nullptr, *xin = nullptr, *h = nullptr, *fc = nullptr, *memx = nullptr, *memxin = nullptr,
         *memh = nullptr, *hc = nullptr;
@@ -825,35 +758,9 @@ struct ccx_sepformer {
 
 namespace {
 
-int load_block(ccx_sepformer* s, const std::string& prefix, SepBlock& B) {
-  const int D = s->d.d_model, F = s->d.d_ffn;
-  B.layers.resize(s->d.n_layers);
-  for (int l = 0; l < s->d.n_layers; l++) {
-    const std::string p = prefix + ".mdl.layers." + std::to_string(l);
-    SepLayer& L = B.layers[l];
-    CCX_NEED(s->store, wi, p + ".self_att.att.in_proj_weight", 3 * D, D); CCX_NEED(s->store, bi, p + ".self_att.att.in_proj_bias", 3 * D);
-    CCX_NEED(s->store, wo, p + ".self_att.att.out_proj.weight", D, D); CCX_NEED(s->store, bo, p + ".self_att.att.out_proj.bias", D);
-    CCX_NEED(s->store, w1, p + ".pos_ffn.ffn.0.weight", F, D); CCX_NEED(s->store, b1, p + ".pos_ffn.ffn.0.bias", F);
-    CCX_NEED(s->store, w2, p + ".pos_ffn.ffn.3.weight", D, F); CCX_NEED(s->store, b2, p + ".pos_ffn.ffn.3.bias", D);
-    CCX_NEED(s->store, g1, p + ".norm1.norm.weight", D); CCX_NEED(s->store, be1, p + ".norm1.norm.bias", D);
-    CCX_NEED(s->store, g2, p + ".norm2.norm.weight", D); CCX_NEED(s->store, be2, p + ".norm2.norm.bias", D);
-    CCX_TRY(s->store.upload_bf16(&L.Wqkv, wi->data)); CCX_TRY(s->store.upload(&L.bqkv, bi->data.data(), 3 * D));
-    CCX_TRY(s->store.upload_bf16(&L.Wo, wo->data)); CCX_TRY(s->store.upload(&L.bo, bo->data.data(), D));
-    CCX_TRY(s->store.upload_bf16(&L.W1, w1->data)); CCX_TRY(s->store.upload(&L.b1, b1->data.data(), F));
-    CCX_TRY(s->store.upload_bf16(&L.W2, w2->data)); CCX_TRY(s->store.upload(&L.b2, b2->data.data(), D));
-    CCX_TRY(s->store.upload(&L.ln1_g, g1->data.data(), D)); CCX_TRY(s->store.upload(&L.ln1_b, be1->data.data(), D));
-    CCX_TRY(s->store.upload(&L.ln2_g, g2->data.data(), D)); CCX_TRY(s->store.upload(&L.ln2_b, be2->data.data(), D));
-  }
-  CCX_NEED(s->store, fg, prefix + ".mdl.norm.norm.weight", D); CCX_NEED(s->store, fb, prefix + ".mdl.norm.norm.bias", D);
-  CCX_NEED(s->store, gg, prefix + ".norm.weight", D); CCX_NEED(s->store, gb, prefix + ".norm.bias", D);
-  CCX_TRY(s->store.upload(&B.lnf_g, fg->data.data(), D)); CCX_TRY(s->store.upload(&B.lnf_b, fb->data.data(), D));
-  CCX_TRY(s->store.upload(&B.gln_g, gg->data.data(), D)); CCX_TRY(s->store.upload(&B.gln_b, gb->data.data(), D));
-  return CCX_OK;
-}
-
 // One SBTransformerBlock_wnormandskip over `n_tok` tokens organised in `n_seq` sequences.
 // `max_len`: the longest sequence of the call (host side); up to 160 tokens the attention half of a layer is one kernel.
-int run_block(ccx_sepformer* s, const SepBlock& B, const float* x, const float* hc, const int* tok_seq, const int* tok_pos,
+int run_block(ccx_sepformer* s, const SbStack& B, const float* x, const float* hc, const int* tok_seq, const int* tok_pos,
               const int* seq_start, const int* seq_len, int n_tok, int n_seq, int max_len, float* xin, float* h, float* y, hipStream_t st) {
   ccx_ctx* ctx = s->ctx;
   const int D = s->d.d_model, F = s->d.d_ffn;
@@ -862,7 +769,7 @@ int run_block(ccx_sepformer* s, const SepBlock& B, const float* x, const float* 
   CCX_CHECK_LAUNCH(ctx);
   const char* fenv = getenv("CCX_SEP_FUSED_ATTN");          // read per call: tests compare the two paths in one process
   const bool fused = (fenv ? atoi(fenv) != 0 : true) && max_len <= AB_MAX_TOK;
-  for (const SepLayer& L : B.layers) {
+  for (const SbLayer& L : B.layers) {
     GemmParams p;
     if (fused) {
       CCX_TRY(ccx_launch_sep_attn_block(ctx, h, L.ln1_g, L.ln1_b, L.Wqkv, L.bqkv, L.Wo, L.bo, seq_start, seq_len, n_seq, n_tok, max_len, st));
@@ -879,7 +786,7 @@ int run_block(ccx_sepformer* s, const SepBlock& B, const float* x, const float* 
     // LayerNorm 2 + Linear-ReLU-Linear + residual in one kernel (see sep_ffn_kernel)
     CCX_TRY(ccx_launch_sep_ffn(ctx, h, L.ln2_g, L.ln2_b, L.W1, L.b1, L.W2, L.b2, n_tok, F, st));
   }
-  CCX_TRY(ccx_launch_sep_final_norm(ctx, h, xin, seq_start, seq_len, n_seq, B.lnf_g, B.lnf_b, B.gln_g, B.gln_b, y, st));
+  CCX_TRY(ccx_launch_sep_final_norm(ctx, h, xin, seq_start, seq_len, n_seq, B.lnf_g, B.lnf_b, B.norm_g, B.norm_b, y, st));
   return CCX_OK;
 }
 
@@ -939,23 +846,15 @@ int ccx_sepformer_finalize(ccx_sepformer* s) {
   s->seg.resize(d.n_blocks);
   s->mem.resize(d.n_blocks > 0 ? d.n_blocks - 1 : 0);
   for (int i = 0; i < d.n_blocks; i++) {
-    CCX_TRY(load_block(s, "masknet.model.seg_model." + std::to_string(i), s->seg[i]));
-    if (i < d.n_blocks - 1) CCX_TRY(load_block(s, "masknet.model.mem_model." + std::to_string(i), s->mem[i]));
+    const std::string seg = "masknet.model.seg_model." + std::to_string(i), mem = "masknet.model.mem_model." + std::to_string(i);
+    CCX_TRY(sb_load_stack(s->store, seg, seg + ".norm", d.n_layers, D, F, s->seg[i]));
+    if (i < d.n_blocks - 1) CCX_TRY(sb_load_stack(s->store, mem, mem + ".norm", d.n_layers, D, F, s->mem[i]));
   }
   s->store.staged.clear();
   // positional encoding table (interleaved sin/cos), long enough for a chunk and for the longest memory sequence
   const int max_chunks = s->max_tokens / d.segment;
   s->pe_len = d.segment > max_chunks ? d.segment : max_chunks;
-  {
-    std::vector<float> pe((size_t)s->pe_len * D);
-    for (int p = 0; p < s->pe_len; p++)
-      for (int i = 0; i < D; i += 2) {
-        const float den = expf((float)i * -(logf(10000.0f) / (float)D));
-        pe[(size_t)p * D + i] = sinf((float)p * den);
-        pe[(size_t)p * D + i + 1] = cosf((float)p * den);
-      }
-    CCX_TRY(s->store.upload(&s->pe, pe));
-  }
+  CCX_TRY(s->store.upload(&s->pe, sb_pos_enc_table(s->pe_len, D)));
   const size_t T = (size_t)s->max_tokens;
   CCX_TRY(s->store.alloc(&s->feats, T * D, true)); CCX_TRY(s->store.alloc(&s->x, T * D, true)); CCX_TRY(s->store.alloc(&s->xin, T * D, true)); CCX_TRY(s->store.alloc(&s->h, T * D, true));
   CCX_TRY(s->store.alloc(&s->fc, T * d.n_spk * D, true)); CCX_TRY(s->store.alloc(&s->xn, T * D, true)); CCX_TRY(s->store.alloc(&s->qkv, T * 3 * D, true));
@@ -1031,8 +930,7 @@ int ccx_sepformer_separate(ccx_sepformer* s, const float* mix, int64_t stride, c
       hc = s->hc;
     }
   }
-  hipLaunchKernelGGL(sep_prelu_bf16_kernel, dim3(ccx_cdiv(n_tok * 32, 256)), dim3(256), 0, st, s->x, s->prelu, s->xn, (long)n_tok * 32);
-  CCX_CHECK_LAUNCH(ctx);
+  CCX_TRY(ccx_launch_prelu_bf16(ctx, s->x, s->prelu, s->xn, (long)n_tok * D, nullptr, st));
   GemmParams p;
   memset(&p, 0, sizeof(p));
   p.A = s->xn; p.lda = D; p.W = s->W_fc; p.ldw = D; p.M = n_tok; p.N = d.n_spk * D; p.K = D; p.bias = s->b_fc; p.out = s->fc; p.ldo = d.n_spk * D;

@@ -192,6 +192,27 @@ class SepDims:
     n_spk: int = 2
 
 
+def _synthetic_sb_stack(sd: Dict[str, torch.Tensor], prefix: str, n_layers: int, D: int, Fd: int, g: torch.Generator) -> None:
+    """Seeded weights of one SBTransformerBlock stack under `prefix`: the per-layer keys, then the stack's final LayerNorm.  The outer
+    norm of the block that wraps the stack stays with the caller (its shape differs between the families)."""
+    rn = lambda *s: torch.randn(*s, generator=g)
+    for l in range(n_layers):
+        p = f"{prefix}.mdl.layers.{l}"
+        sd[p + ".self_att.att.in_proj_weight"] = rn(3 * D, D) / math.sqrt(D)
+        sd[p + ".self_att.att.in_proj_bias"] = 0.1 * rn(3 * D)
+        sd[p + ".self_att.att.out_proj.weight"] = rn(D, D) / math.sqrt(D)
+        sd[p + ".self_att.att.out_proj.bias"] = 0.1 * rn(D)
+        sd[p + ".pos_ffn.ffn.0.weight"] = rn(Fd, D) / math.sqrt(D)
+        sd[p + ".pos_ffn.ffn.0.bias"] = 0.1 * rn(Fd)
+        sd[p + ".pos_ffn.ffn.3.weight"] = rn(D, Fd) / math.sqrt(Fd)
+        sd[p + ".pos_ffn.ffn.3.bias"] = 0.1 * rn(D)
+        for nm in ("norm1", "norm2"):
+            sd[f"{p}.{nm}.norm.weight"] = 1 + 0.1 * rn(D)
+            sd[f"{p}.{nm}.norm.bias"] = 0.1 * rn(D)
+    sd[prefix + ".mdl.norm.norm.weight"] = 1 + 0.1 * rn(D)
+    sd[prefix + ".mdl.norm.norm.bias"] = 0.1 * rn(D)
+
+
 def synthetic_sepformer_state_dict(dims: SepDims, seed: int = 0) -> Dict[str, torch.Tensor]:
     """Seeded weights in the SpeechBrain checkpoint key layout (`encoder.ckpt`, `masknet.ckpt`,
     `decoder.ckpt` of the reference's overlay, back/api.py:729-746, each prefixed with its module
@@ -203,21 +224,7 @@ def synthetic_sepformer_state_dict(dims: SepDims, seed: int = 0) -> Dict[str, to
     sd["decoder.weight"] = torch.randn(dims.n_filters, 1, dims.kernel, generator=g) / math.sqrt(dims.n_filters)
 
     def block(prefix):
-        for l in range(dims.n_layers):
-            p = f"{prefix}.mdl.layers.{l}"
-            sd[p + ".self_att.att.in_proj_weight"] = torch.randn(3 * D, D, generator=g) / math.sqrt(D)
-            sd[p + ".self_att.att.in_proj_bias"] = 0.1 * torch.randn(3 * D, generator=g)
-            sd[p + ".self_att.att.out_proj.weight"] = torch.randn(D, D, generator=g) / math.sqrt(D)
-            sd[p + ".self_att.att.out_proj.bias"] = 0.1 * torch.randn(D, generator=g)
-            sd[p + ".pos_ffn.ffn.0.weight"] = torch.randn(Fd, D, generator=g) / math.sqrt(D)
-            sd[p + ".pos_ffn.ffn.0.bias"] = 0.1 * torch.randn(Fd, generator=g)
-            sd[p + ".pos_ffn.ffn.3.weight"] = torch.randn(D, Fd, generator=g) / math.sqrt(Fd)
-            sd[p + ".pos_ffn.ffn.3.bias"] = 0.1 * torch.randn(D, generator=g)
-            for nm in ("norm1", "norm2"):
-                sd[f"{p}.{nm}.norm.weight"] = 1 + 0.1 * torch.randn(D, generator=g)
-                sd[f"{p}.{nm}.norm.bias"] = 0.1 * torch.randn(D, generator=g)
-        sd[prefix + ".mdl.norm.norm.weight"] = 1 + 0.1 * torch.randn(D, generator=g)
-        sd[prefix + ".mdl.norm.norm.bias"] = 0.1 * torch.randn(D, generator=g)
+        _synthetic_sb_stack(sd, prefix, dims.n_layers, D, Fd, g)
         sd[prefix + ".norm.weight"] = (1 + 0.1 * torch.randn(D, generator=g)).view(D, 1)
         sd[prefix + ".norm.bias"] = (0.1 * torch.randn(D, generator=g)).view(D, 1)
 
@@ -287,21 +294,7 @@ def synthetic_dualpath_state_dict(dims: DualPathDims, seed: int = 0, pos_enc_buf
     for b in range(dims.n_blocks):
         for part in ("intra", "inter"):
             prefix = f"masknet.dual_mdl.{b}.{part}_mdl"
-            for l in range(dims.n_layers):
-                p = f"{prefix}.mdl.layers.{l}"
-                sd[p + ".self_att.att.in_proj_weight"] = rn(3 * D, D) / math.sqrt(D)
-                sd[p + ".self_att.att.in_proj_bias"] = 0.1 * rn(3 * D)
-                sd[p + ".self_att.att.out_proj.weight"] = rn(D, D) / math.sqrt(D)
-                sd[p + ".self_att.att.out_proj.bias"] = 0.1 * rn(D)
-                sd[p + ".pos_ffn.ffn.0.weight"] = rn(Fd, D) / math.sqrt(D)
-                sd[p + ".pos_ffn.ffn.0.bias"] = 0.1 * rn(Fd)
-                sd[p + ".pos_ffn.ffn.3.weight"] = rn(D, Fd) / math.sqrt(Fd)
-                sd[p + ".pos_ffn.ffn.3.bias"] = 0.1 * rn(D)
-                for nm in ("norm1", "norm2"):
-                    sd[f"{p}.{nm}.norm.weight"] = 1 + 0.1 * rn(D)
-                    sd[f"{p}.{nm}.norm.bias"] = 0.1 * rn(D)
-            sd[prefix + ".mdl.norm.norm.weight"] = 1 + 0.1 * rn(D)
-            sd[prefix + ".mdl.norm.norm.bias"] = 0.1 * rn(D)
+            _synthetic_sb_stack(sd, prefix, dims.n_layers, D, Fd, g)
             if pos_enc_buffers:
                 sd[prefix + ".pos_enc.pe"] = torch.zeros(1, 2500, D)
             sd[f"masknet.dual_mdl.{b}.{part}_norm.weight"] = 1 + 0.1 * rn(N)

@@ -53,7 +53,9 @@ def _bits(t):
 
 
 # ---- attention ----------------------------------------------------------------------------------------------------------------
-ATT_LENS = ((1, 1), (15, 1), (16, 1), (17, 1), (250, 1), (257, 1), (10, 1), (2, 10), (37, 10), (2, 250), (19, 250))
+# 64 and 65: on and one past the block of CCX_DP_KEY_BLOCK keys, contiguous and strided
+ATT_LENS = ((1, 1), (15, 1), (16, 1), (17, 1), (250, 1), (257, 1), (10, 1), (2, 10), (37, 10), (2, 250), (19, 250), (64, 1), (65, 1),
+            (65, 10))
 
 
 def _att_run(ctx, qkv, seqs, rows, order=None):

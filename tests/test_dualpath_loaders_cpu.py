@@ -1,6 +1,8 @@
 """CPU: the loaders of the dual-path SepFormer -- family detection by keys, geometry from tensor shapes and key counts, the chunk length
 from a savedir's hyperparams.yaml, `pos_enc.pe` buffers carried along, the two refusals by name -- on savedirs written here in
 SpeechBrain's layout (no published checkpoint exists offline).  A RE-SepFormer savedir loads exactly as before."""
+import hashlib
+import json
 import os
 
 import pytest
@@ -128,3 +130,25 @@ def test_build_state_dicts_picks_the_family(monkeypatch, tmp_path):
     with pytest.raises(ValueError, match="sep_family"):
         models.build_state_dicts(sep_family="dprnn")
     assert W.DualPathDims is DualPathDims
+
+
+def test_synthetic_separator_weights_keep_their_bits():
+    """The seeded state dicts of both families (seed 1 of the default RE-SepFormer is the benchmark's) against digests recorded before
+    the per-layer keys moved into one helper: sha256 over every key, in order, followed by its tensor's bytes."""
+    def digest(sd):
+        h = hashlib.sha256()
+        for k, v in sd.items():
+            h.update(k.encode())
+            h.update(v.detach().contiguous().numpy().tobytes())
+        return h.hexdigest()
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "synthetic_separator_digests.json")) as f:
+        want = json.load(f)
+    got = {
+        "sepformer_default_seed0": digest(synthetic_sepformer_state_dict(SepDims(), 0)),
+        "sepformer_default_seed1": digest(synthetic_sepformer_state_dict(SepDims(), 1)),
+        "sepformer_3spk_seed0": digest(synthetic_sepformer_state_dict(SepDims(n_spk=3), 0)),
+        "dualpath_default_seed0": digest(synthetic_dualpath_state_dict(DualPathDims(), 0)),
+        "dualpath_3spk_seed0_pos_enc_buffers": digest(synthetic_dualpath_state_dict(DualPathDims(n_spk=3), 0, pos_enc_buffers=True)),
+    }
+    assert got == want
